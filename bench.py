@@ -9,8 +9,13 @@ bands), every physical parameter jittered log-uniformly by +-10 % so that the ba
 
 `python bench.py --gpus N --steps K --warmup W`; for N > 1 launch with torch.distributed.run (one rank per GPU): models are
 block-sharded (weak scaling: --batch models per rank) and each step ends with the all-gather of a per-model summary (8 B/model).
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR` writes
+what the last timed step computed (DIR/flux_density.npy, float64 [batch, bands, times]; under torchrun rank 0's block and the
+gathered per-model summary) -- seeded inputs, so two builds can be compared output for output.
 
-The same JSON line carries what BASELINE.json's north_star asks for, each next to the reference CPU path timed on this box:
+`--full` adds everything else: one untimed pass with the kernels' work tallies (the FP64 roofline's `achieved` / `frac`) and the
+legs below, which carry what BASELINE.json's north_star asks for, each next to the reference CPU path timed on this box
+(`--no-walkers` / `--no-cpu-baseline` prune them again):
   walker_steps*     MCMC walker-steps/s on configs[3] through the product's sharded evaluator (dist.WalkerSharder over
                     Fitter.device_evaluator): 1024 and 512 (red-blue half) walkers over all ranks, ln L read by the host after
                     every call as a sampler does; and, on one GPU, the per-rank shares of an 8-GPU run (128 / 64 walkers) with the
@@ -672,13 +677,33 @@ def emit(detail, real_stdout, world):
     os.write(real_stdout, (compact_line(detail, shown) + "\n").encode())
 
 
-def headline_record(world, rccl_world, nb, steps, warmup, elapsed, st, plan, nnu, nt):
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  One larger than its share of `limit` keeps a fixed, seeded
+    sample of its leading axis (the same rows on every run, in order), whose indices go to out_dir/<name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(len(arrays), 1) - 4096  # room for the .npy headers
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            row = a.nbytes // a.shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(share // (row + 8), 1), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def headline_record(world, rccl_world, nb, steps, warmup, elapsed, st, plan, nnu, nt, tallied=True):
     """The contract part of the record (same keys at every N; rank 0 prints it).  `st` = mean stage times of the timed steps
-    (grid, dynamics, cells, flux, reduce, total; HIP events on the kernels' own stream), `plan` = the tallied plan of one launch."""
+    (grid, dynamics, cells, flux, reduce, total; HIP events on the kernels' own stream), `plan` = the plan of one launch, with the
+    kernels' work tallies when `tallied` (--full); without them the FP64 roofline's flop counts, `achieved` and `frac` are null."""
     flux_s = st[3] * 1e-3
     # algorithmic work of ONE flux-kernel launch (DESIGN.md "Roofline accounting")
     alg_bytes = plan.n_cells * 18 * 8 + nb * nnu * nt * 8 + nb * (64 + 64) * 8
-    alg_flops = plan.spec_evals * F_SPEC + plan.interps * F_INTERP
+    alg_flops = plan.spec_evals * F_SPEC + plan.interps * F_INTERP if tallied else None
+    achieved = alg_flops / flux_s / 1e12 if tallied else None
     return {
         "metric": "light-curves/sec (single model) and MCMC walker-steps/sec at 1/2/4/8 MI355X",
         "value": world * nb * steps / elapsed,
@@ -695,9 +720,9 @@ def headline_record(world, rccl_world, nb, steps, warmup, elapsed, st, plan, nnu
         # the kernel's bound is the FP64 vector ALU: flop-equivalents of ONE launch (210 per spectrum evaluation,
         # 26 per interpolation, tallied by the kernel in an untimed pass) over its HIP-event time; `traffic` = its HBM bytes by counters
         "roofline": {"bound": "fp64_valu", "kernel": "vag_flux_grid_kernel",
-                     "achieved": alg_flops / flux_s / 1e12, "peak": PEAK_FP64_TFLOPS, "unit": "TFLOP/s",
-                     "frac": alg_flops / flux_s / 1e12 / PEAK_FP64_TFLOPS, "traffic": None,
-                     "spec_evals_per_launch": plan.spec_evals, "interps_per_launch": plan.interps,
+                     "achieved": achieved, "peak": PEAK_FP64_TFLOPS, "unit": "TFLOP/s",
+                     "frac": achieved / PEAK_FP64_TFLOPS if tallied else None, "traffic": None,
+                     "spec_evals_per_launch": plan.spec_evals if tallied else None, "interps_per_launch": plan.interps if tallied else None,
                      "flop_eq_per_launch": alg_flops, "ms_per_launch": st[3]},
         # BASELINE.json asks for HBM GB/s vs peak as well: the same launch's algorithmic bytes -- reported, not the bound
         "roofline_hbm": {"bound": "hbm (reported because BASELINE.json names it; the kernel is FP64-VALU bound)", "kernel": "vag_flux_grid_kernel",
@@ -717,8 +742,10 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=512, help="models per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-walkers", action="store_true", help="skip everything but the headline measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="also the work-tallied roofline pass, every secondary leg and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-walkers", action="store_true", help="with --full: skip every leg but the headline and its roofline")
     args = ap.parse_args()
 
     # stdout carries ONE JSON line and nothing else: RCCL prints its version banner to the C stdout when a communicator is
@@ -772,17 +799,21 @@ def main():
 
     sync, barrier, max_over_ranks = _dist_helpers(world, dev)
     elapsed = timed_steps(step, args.steps, args.warmup, world, sync, barrier, max_over_ranks)
+    if args.dump_outputs and rank == 0:  # the fluxes a caller of the timed path receives (and, at N > 1, what the all-gather hands it)
+        dump_outputs(args.dump_outputs, {"flux_density": d_out.cpu().numpy(),
+                                         **({"band_summed_flux_all_ranks": gathered.cpu().numpy()} if world > 1 else {})})
 
-    # one extra UNTIMED pass with the kernel's work tallies on: exact spectrum-evaluation / interpolation counts
-    _lib.check(lib.vag_ctx_count_work(h, 1))
-    step(False)
-    torch.cuda.synchronize()
-    _lib.check(lib.vag_ctx_count_work(h, 0))
+    if args.full:
+        # one extra UNTIMED pass with the kernel's work tallies on: exact spectrum-evaluation / interpolation counts
+        _lib.check(lib.vag_ctx_count_work(h, 1))
+        step(False)
+        torch.cuda.synchronize()
+        _lib.check(lib.vag_ctx_count_work(h, 0))
     plan = _lib.Plan()
     lib.vag_last_plan(h, C.byref(plan))
     if not bool(torch.isfinite(d_out).all()) or plan.n_models_ok != nb:
         raise SystemExit("bench produced non-finite fluxes or rejected models")
-    extra = not args.no_walkers
+    extra = args.full and not args.no_walkers
     walkers = walker_bench(lib, h, _lib, dev, rank, world, tally=True) if extra else None
     walkers_half = walker_bench(lib, h, _lib, dev, rank, world, nwalkers=512) if extra else None
     walkers_queued = walker_bench(lib, h, _lib, dev, rank, world, host_consumes=False) if extra else None
@@ -835,7 +866,7 @@ def main():
                                             "walker_steps_per_s_sharded": r["value"], "finite_walkers": r["finite_walkers"]}
         finally:
             dist.destroy_process_group()
-    with_cpu = not args.no_cpu_baseline and world == 1
+    with_cpu = args.full and not args.no_cpu_baseline and world == 1
     tophat = tophat_sweep(lib, h, _lib, dev, with_cpu) if (extra and world == 1) else None
     ensembles = ensemble_bench(lib, h, _lib, dev, with_cpu) if (extra and world == 1) else None
     threadpool = threadpool_bench(lib, h, _lib) if (extra and world == 1) else None
@@ -851,7 +882,7 @@ def main():
 
     if rank == 0:
         out = headline_record(world, dist.get_world_size() if world > 1 else 1, nb, args.steps, args.warmup, elapsed,
-                              np.mean(np.array(flux_ms), axis=0), plan, nnu, nt)
+                              np.mean(np.array(flux_ms), axis=0), plan, nnu, nt, tallied=args.full)
         # HBM traffic of the dominant kernel from the committed rocprofv3 PMC passes of this same command
         # (profiles/run_profile.sh; FETCH_SIZE x2 per the gfx950 note, calibrated on a kernel with known bytes)
         for name in ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json"):

@@ -670,3 +670,24 @@ def test_bench_line_is_short_and_complete_by_construction():
                       "c5_lc_per_s", "c3_table_frac", "implied_8gpu_walkers_8192", "implied_8gpu_walkers_1024", "implied_8gpu_ensemble_c5"):
                 assert k in line["extra"], k
         assert line["detail"] == "bench_detail.json"
+
+
+def test_bench_dump_outputs_stay_under_their_limit_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: arrays within the limit are written whole in float64; a larger one keeps the same seeded, sorted sample of
+    its leading axis on every run, with the row indices beside it, and the files together stay under the limit."""
+    import sys
+    sys.path.insert(0, _abi.ROOT)
+    import bench
+    small = np.arange(24, dtype=np.float32).reshape(2, 3, 4)
+    big = np.random.default_rng(5).random((400, 10, 20))
+    limit = 2 * 100 * 10 * 20 * 8
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big}, limit=limit)
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+    rows = np.load(tmp_path / "a" / "big_rows.npy")
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and 50 < rows.size < 100
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), big[rows.astype(int)])
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= limit
+    for name in ("small", "big", "big_rows"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))

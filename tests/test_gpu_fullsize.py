@@ -844,3 +844,36 @@ def test_a_long_mixed_loop_neither_grows_device_memory_nor_the_process(eng, orac
     for _ in range(5):
         cycle()
         assert lib.vag_device_bytes_in_use() == before
+
+
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_last_step(eng, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` in a process of its own: ONE line whose steps / ms_per_step / value
+    describe exactly K timed steps, no secondary leg (they need --full), and DIR/flux_density.npy = the fluxes of the seeded
+    headline batch, as the same models give them through the C-ABI here."""
+    import json
+    import subprocess
+    import bench
+    nb, steps = 64, 3
+    env = dict(os.environ, VAG_BENCH_DETAIL=str(tmp_path / "detail.json"))
+    run = subprocess.run([sys.executable, os.path.join(_abi.ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                          "--batch", str(nb), "--dump-outputs", str(tmp_path / "out")],
+                         cwd=_abi.ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = run.stdout.splitlines()
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f64"
+    assert line["unit"] == "light-curves/s" and line["higher_is_better"] is True and line["metric"].startswith("light-curves/sec")
+    assert line["value"] == pytest.approx(nb / (line["ms_per_step"] * 1e-3), rel=1e-4)
+    assert set(line["extra"]) <= {"hbm_GBps", "hbm_frac", "rccl_world"}  # the headline's own figures, none of a secondary leg
+    assert line["cpu_baseline"] is None and line["roofline"]["achieved"] is None
+    got = np.load(tmp_path / "out" / "flux_density.npy")
+    assert got.dtype == np.float64 and got.shape == (nb, configs.C2_NU.size, configs.C2_T.size)
+    lib, h = eng
+    arr = (_lib.ModelParams * nb)(*[_lib.ModelParams.from_buffer_copy(bytes(p)) for p in bench.c2_batch(nb, seed=1234)])
+    t, nu = np.ascontiguousarray(configs.C2_T), np.ascontiguousarray(configs.C2_NU)
+    want = np.empty((nb, nu.size, t.size))
+    _lib.check(lib.vag_flux_density_grid_batch(h, arr, nb, t.ctypes.data_as(dp), t.size, nu.ctypes.data_as(dp), nu.size,
+                                               want.ctypes.data_as(dp)))
+    assert np.all(np.isfinite(got)) and got.max() > 0
+    np.testing.assert_allclose(got, want, rtol=1e-12, atol=0)
