@@ -385,6 +385,13 @@ struct vag_ctx {
     int grid_large_idle = 0;  // consecutive batches that would have fitted the small one
     DevBuf d_gridscratch;     // level 2: the grid kernel's scratch arrays, one GridSharedHuge per model
     std::vector<SeriesOcc> series_occ;  // occupancy-query results of series launches seen so far
+    struct FluxOcc {
+        const void* fn;
+        size_t lds;
+        int wg;
+    };
+    std::vector<FluxOcc> flux_occ;  // ... and of persistent vag_flux_grid_kernel launches
+    DevBuf d_flux_order;            // [nb] deal order of a persistent vag_flux_grid_kernel launch (vag_flux_order_kernel)
     DevBuf d_partial2, d_ssc2;  // fused synchrotron + SSC flux pass: second partial-grid buffer / second scratch output
     DevBuf d_bandidx;  // [512 band index per point | 8 first point of each band] for the shared-node / row-per-lane series paths
     int h_bandbuf[512 + 8] = {};  // host mirror of d_bandidx (skips the upload while a fit keeps its data)
@@ -667,7 +674,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (DevBuf* b : {&c->d_partial2, &c->d_ssc2, &c->d_bandidx, &c->d_sptab, &c->d_workcount, &c->d_knlut, &c->d_icy, &c->d_cellq, &c->d_band, &c->d_ichdr, &c->d_icplan, &c->d_icpool, &c->d_icused, &c->d_icslow,
+    for (DevBuf* b : {&c->d_flux_order, &c->d_partial2, &c->d_ssc2, &c->d_bandidx, &c->d_sptab, &c->d_workcount, &c->d_knlut, &c->d_icy, &c->d_cellq, &c->d_band, &c->d_ichdr, &c->d_icplan, &c->d_icpool, &c->d_icused, &c->d_icslow,
                       &c->d_icstatus, &c->d_icunclamp, &c->d_ssc, &c->d_shock_r, &c->d_cellpar_r, &c->d_celldet_r, &c->d_icy_r,
                       &c->d_cellq_r, &c->d_params_rvs, &c->d_inj, &c->d_comp, &c->d_cellgeo, &c->d_fail, &c->d_dynrec, &c->d_gridscratch, &c->d_chi2, &c->d_bandobs, &c->d_params, &c->d_t, &c->d_nu, &c->d_lg2t, &c->d_lg2nu, &c->d_tminmax, &c->d_bandw, &c->d_out,
                       &c->d_meta, &c->d_phi, &c->d_theta, &c->d_rep_of, &c->d_rep_start, &c->d_tdec, &c->d_geo_th, &c->d_geo_ph, &c->d_row_off,
@@ -1249,6 +1256,42 @@ static void launch_reduce(hipStream_t st, const vag_model_params* d_params, cons
     }
 }
 
+// One launch of vag_flux_grid_kernel: a workgroup per (block, model), or -- persist = 1 and more items of at least
+// FLUX_PERSIST_MIN_PPB rows than stay resident at once, or persist = 2 (test hook) -- the persistent form with as many workgroups
+// as stay resident (occupancy query x CUs, remembered per kernel and LDS size), its items dealt by descending model cost
+// (vag_flux_order_kernel).  Returns whether it took the persistent form (its counter then has to go back to zero behind it).
+constexpr int FLUX_PERSIST_MIN_PPB = 128;
+template <bool COUNT, int MODE, bool SPREAD = false, int THREADS = FLUX_THREADS, bool PIECES = false>
+static bool launch_flux_grid(vag_ctx* c, FluxArgs a, int nb, size_t lds, int persist) {
+    const auto fn = vag_flux_grid_kernel<COUNT, MODE, SPREAD, THREADS, PIECES, true>;
+    int wg = -1;
+    if (persist) {
+        for (const auto& e : c->flux_occ)
+            if (e.fn == reinterpret_cast<const void*>(fn) && e.lds == lds) wg = e.wg;
+        if (wg < 0) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, THREADS, lds) != hipSuccess || wg < 1) wg = 1;
+            if (c->flux_occ.size() > 256) c->flux_occ.clear();
+            c->flux_occ.push_back({reinterpret_cast<const void*>(fn), lds, wg});
+        }
+    }
+    // A launch that fits in one round gains nothing from a deal order, and the item loop's spills cost the short ones up to 5 %.
+    // Short items lose too: every item starts with a round trip to the counter and two barriers, and on items of 32 rows (16384
+    // configs[0] top hats, ppb 64) the persistent form took 6.1 against 4.6 ms.  Measured to win at ppb 128 (configs[1], 512 models).
+    if (!persist || (persist == 1 && (a.n_items <= (long long)wg * c->n_cus || a.pairs_per_block < FLUX_PERSIST_MIN_PPB))) {
+        if (vag_hook("VAG_DEBUG_LAUNCH")) std::fprintf(stderr, "[vag] grid flux form: one item per workgroup, %d x %d\n", a.max_blocks, nb);
+        a.work = nullptr;
+        hipLaunchKernelGGL((vag_flux_grid_kernel<COUNT, MODE, SPREAD, THREADS, PIECES>), dim3(a.max_blocks, nb), dim3(THREADS), lds, c->stream, a);
+        return false;
+    }
+    const long long n_wg = std::min<long long>(a.n_items, (long long)wg * c->n_cus);
+    if (vag_hook("VAG_DEBUG_LAUNCH"))
+        std::fprintf(stderr, "[vag] grid flux form: persistent, %lld workgroups for %d items\n", n_wg, a.n_items);
+    hipLaunchKernelGGL(vag_flux_order_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, a.meta, nb, const_cast<int*>(a.order));
+    hipLaunchKernelGGL(fn, dim3((unsigned)n_wg), dim3(THREADS), lds, c->stream, a);
+    return true;
+}
+
 int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_lg2t, int nt,
                   const double* d_lg2nu, int nnu, const double* d_bandw, double* d_out, int mode = FLUX_SYN,
                   double* d_out2 = nullptr /* FLUX_FUSED: the SSC component */) {
@@ -1358,6 +1401,9 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
     const bool spreading = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
     a.rowgeo = nullptr;
     a.rowgeo_stride = 0;
+    a.work = nullptr;
+    a.order = nullptr;
+    a.n_items = nb * max_blocks;
     if (!spreading) {  // the models' row-geometry records, written by the grid kernel with the layout it ran with
         a.rowgeo = c->d_rowgeo.as<double>();
         a.rowgeo_stride = rowgeo_stride(c->layout_large);
@@ -1373,6 +1419,7 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
     c->plan.interps += c->total_pairs * (long long)nt * nnu;
     c->plan.flux_blocks = max_blocks * nb;
     c->plan.pairs_per_block = ppb;
+    bool persistent = false;
     if (c->n_rows > 0) {
         // requests with few (nu, t) slots and short rows keep less than half of a 512-lane workgroup busy: use 256 lanes
         // (+47 % on the C5 / C1b shapes; a 128-lane variant measured slower)
@@ -1395,15 +1442,24 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
         // (Measured and rejected, profiles/rejected/vag_flux_wide.h: ONE 1024-lane workgroup per CU sharing the staged row and tables, a
         // second boundary block in the LDS that frees, one barrier per row and balanced slot ownership -- bitwise the same fluxes,
         // 27.0-27.7 ms against 21.7 per 512 C2 models: sixteen wavefronts in lockstep lose the overlap two independent workgroups have.)
+        // Persistent launch (VAG_FLUX_PERSISTENT=0: a workgroup per item, the launch before it; =2: persistent whatever the shape):
+        // the resident workgroups take the items from a counter, the models by descending cost, so that the launch drains on its
+        // cheapest items.
+        int persist = 1;
+        if (const char* e = vag_hook("VAG_FLUX_PERSISTENT")) persist = std::atoi(e);
+        if (persist) {
+            if (c->d_flux_order.ensure(sizeof(int) * (size_t)nb)) return VAG_E_HIP;
+            a.work = work_counters(c);
+            a.order = c->d_flux_order.as<int>();
+        }
         if (pieces) {
             a.work_count = nullptr;  // the tallying instantiation has no piece loop: the plan keeps the upper bounds
-            const dim3 g(max_blocks, nb), b(FLUX_THREADS);
 #define VAG_PIECES_LAUNCH(M_)                                                                                          \
     do {                                                                                                               \
         if (spreading)                                                                                                 \
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, M_, true, FLUX_THREADS, true>), g, b, lds, st, a);          \
+            persistent = launch_flux_grid<false, M_, true, FLUX_THREADS, true>(c, a, nb, lds, persist);                         \
         else                                                                                                           \
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, M_, false, FLUX_THREADS, true>), g, b, lds, st, a);         \
+            persistent = launch_flux_grid<false, M_, false, FLUX_THREADS, true>(c, a, nb, lds, persist);                        \
     } while (0)
             if (mode == FLUX_FUSED)
                 VAG_PIECES_LAUNCH(FLUX_FUSED);
@@ -1415,31 +1471,31 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
                 VAG_PIECES_LAUNCH(FLUX_SYN);
 #undef VAG_PIECES_LAUNCH
         } else if (small && mode == FLUX_FUSED)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_FUSED, false, 256>), dim3(max_blocks, nb), dim3(256), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_FUSED, false, 256>(c, a, nb, lds, persist);
         else if (spreading && mode == FLUX_FUSED)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_FUSED, true>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_FUSED, true>(c, a, nb, lds, persist);
         else if (mode == FLUX_FUSED)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_FUSED>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_FUSED>(c, a, nb, lds, persist);
         else if (small && mode == FLUX_SYN_IC)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SYN_IC, false, 256>), dim3(max_blocks, nb), dim3(256), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SYN_IC, false, 256>(c, a, nb, lds, persist);
         else if (small && mode == FLUX_SSC)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SSC, false, 256>), dim3(max_blocks, nb), dim3(256), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SSC, false, 256>(c, a, nb, lds, persist);
         else if (small)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SYN, false, 256>), dim3(max_blocks, nb), dim3(256), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SYN, false, 256>(c, a, nb, lds, persist);
         else if (spreading && mode == FLUX_SYN_IC)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SYN_IC, true>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SYN_IC, true>(c, a, nb, lds, persist);
         else if (spreading && mode == FLUX_SSC)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SSC, true>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SSC, true>(c, a, nb, lds, persist);
         else if (spreading)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SYN, true>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SYN, true>(c, a, nb, lds, persist);
         else if (mode == FLUX_SYN_IC)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SYN_IC>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SYN_IC>(c, a, nb, lds, persist);
         else if (mode == FLUX_SSC)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SSC>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SSC>(c, a, nb, lds, persist);
         else if (a.work_count)
-            hipLaunchKernelGGL((vag_flux_grid_kernel<true, FLUX_SYN>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<true, FLUX_SYN>(c, a, nb, lds, persist);
         else
-            hipLaunchKernelGGL((vag_flux_grid_kernel<false, FLUX_SYN>), dim3(max_blocks, nb), dim3(FLUX_THREADS), lds, st, a);
+            persistent = launch_flux_grid<false, FLUX_SYN>(c, a, nb, lds, persist);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(c->ev[4], st));
@@ -1450,7 +1506,8 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
         c->plan.spec_evals += (long long)h[0] - c->eat_cells * nnu;
         c->plan.interps += (long long)h[1] - c->total_pairs * (long long)nt * nnu;
     }
-    launch_reduce(st, d_params, c->d_meta.as<VagGridMeta>(), c->d_partial.as<double>(), max_blocks, ppb, nt, nnu, d_bandw, d_out, nb);
+    launch_reduce(st, d_params, c->d_meta.as<VagGridMeta>(), c->d_partial.as<double>(), max_blocks, ppb, nt, nnu, d_bandw, d_out, nb,
+                  persistent ? a.work : nullptr);
     if (mode == FLUX_FUSED)
         launch_reduce(st, d_params, c->d_meta.as<VagGridMeta>(), c->d_partial2.as<double>(), max_blocks, ppb, nt, nnu, d_bandw, d_out2, nb);
     HIPCHK(hipGetLastError());

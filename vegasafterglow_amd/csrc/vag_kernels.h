@@ -707,6 +707,10 @@ struct FluxArgs {
     const double* cellgeo; // [rows][3][n_t] per-cell cos(theta), sin(theta), log2|dcos| of a spreading jet (SPREAD kernels)
     const double* rowgeo;  // [nb][rowgeo_stride] row-geometry records written by vag_grid_kernel (read by the non-spreading kernels)
     int rowgeo_stride;
+    // persistent launch of vag_flux_grid_kernel (PERSIST): item it = (model order[it / max_blocks], block it % max_blocks)
+    int* work;          // item counter (work_counters(); the reduction after the launch puts it back to zero)
+    const int* order;   // [nb] models by descending predicted cost (vag_flux_order_kernel)
+    int n_items;        // nb * max_blocks
 };
 
 constexpr int ROWGEO_HDR = VAG_ROWGEO_HDR;  // row-geometry records of a model: written by vag_grid_kernel (vag_grid_kernel.h), layout there
@@ -914,22 +918,20 @@ vag_eat_details_kernel(const vag_model_params* __restrict__ params, const VagGri
     out_dop[q] = 1.0 / (G - u * cos_v);
 }
 
-// COUNT = true is the instrumentation variant (exact work tallies); timed runs use COUNT = false.
-// MODE selects the photon source (FLUX_SYN / FLUX_SYN_IC / FLUX_SSC).
 // 128 VGPRs (four workgroups of 256, two of 512 per CU) is what the occupancy of every measured shape hangs on: the C2 launch asks
 // for 80 KB of LDS, two workgroups per CU, and a 136-VGPR scratch-free build of this kernel (launch bound 1) leaves ONE resident:
 // 39.3 ms instead of 24.0 ms per 512 models.  The few spilled values (36 B per lane) sit outside the inner loops.
 // PIECES: some lattice of the batch is longer than the staged row (see K_all below); the loop over pieces costs the C2 shape
 // 3 % when it is compiled in, so the one-piece form is its own instantiation.
-template <bool COUNT, int MODE, bool SPREAD = false, int THREADS = FLUX_THREADS, bool PIECES = false>
-__global__ void __launch_bounds__(THREADS, 4)
-vag_flux_grid_kernel(FluxArgs a) {
-    const int m = blockIdx.y;
+// One item of the launch: the rows [blk * ppb, (blk + 1) * ppb) of model m into partial[m][blk].  The softplus / log2 tables
+// are already in the LDS (vag_flux_grid_kernel stages them once per workgroup).
+template <bool COUNT, int MODE, bool SPREAD, int THREADS, bool PIECES>
+__device__ __forceinline__ void flux_grid_item(const FluxArgs& a, const int m, const int blk) {
     const VagGridMeta* Mp = a.meta + m;
     if (Mp->status != 0) return;
     const int n_phi_eff = Mp->n_phi_eff;
     const int n_pairs = Mp->n_theta * n_phi_eff;
-    const int p0 = blockIdx.x * a.pairs_per_block;
+    const int p0 = blk * a.pairs_per_block;
     if (p0 >= n_pairs) return;
     const int p1 = min(n_pairs, p0 + a.pairs_per_block);
     const int tid = threadIdx.x;
@@ -973,7 +975,6 @@ vag_flux_grid_kernel(FluxArgs a) {
         const double lg2_1pz = Mp->lg2_1pz;
         for (int i = tid; i < nt; i += THREADS) s_tobs[i] = a.lg2_t_obs[i];
         for (int l = tid; l < nnu; l += THREADS) s_nu[l] = a.lg2_nu_obs[l] + lg2_1pz;
-        for (int i = tid; i < SP_LDS_DOUBLES; i += THREADS) s_sp[i] = a.sp_table[i];  // softplus table + log2 table
     }
     SpecConst sc;
     sc.init(Pp->p);
@@ -1409,7 +1410,7 @@ vag_flux_grid_kernel(FluxArgs a) {
     }
     }  // pieces of the lattice
 #ifdef VAG_FLUX_STAMPS
-    if (blockIdx.y == 0 && blockIdx.x == 1 && (tid & 63) == 0)
+    if (m == 0 && blk == 1 && (tid & 63) == 0)
         printf("flux wave %d rows %d cycles: bracket+window %lld  A1 %lld  barrier1 %lld  A0next %lld  B %lld  barrier2 %lld  restage %lld  prologue %lld\n",
                tid >> 6, p1 - p0, c_ph[0], c_ph[1], c_ph[2], c_ph[3], c_ph[4], c_ph[5], c_ph[6], c_ph[7]);
 #endif
@@ -1424,12 +1425,66 @@ vag_flux_grid_kernel(FluxArgs a) {
     }
     __syncthreads();
     // partial grid of this workgroup, stored [l][idx] like the reference's F_nu (nu outer)
-    double* my_partial = a.partial + ((size_t)m * a.max_blocks + blockIdx.x) * slots;
+    double* my_partial = a.partial + ((size_t)m * a.max_blocks + blk) * slots;
     for (int s = tid; s < slots; s += THREADS) my_partial[s] = s_acc[s];
     if constexpr (MODE == FLUX_FUSED) {
-        double* my_partial2 = a.partial2 + ((size_t)m * a.max_blocks + blockIdx.x) * slots;
+        double* my_partial2 = a.partial2 + ((size_t)m * a.max_blocks + blk) * slots;
         for (int s = tid; s < slots; s += THREADS) my_partial2[s] = s_acc2[s];
     }
+}
+
+// COUNT = true is the instrumentation variant (exact work tallies); timed runs use COUNT = false.
+// MODE selects the photon source (FLUX_SYN / FLUX_SYN_IC / FLUX_SSC / FLUX_FUSED).
+// PERSIST = false: one item per workgroup, (blockIdx.y, blockIdx.x).  PERSIST = true: a resident set of workgroups takes the
+// items from the counter a.work in the order of a.order (the most expensive models first, so that the cheap ones fill the drain
+// at the end) and stages the tables once.  Either way an item writes the same partial grid with the same sums.  (Two
+// instantiations: the item loop costs the one-item form a dozen spilled VGPRs when both live in one kernel.)
+template <bool COUNT, int MODE, bool SPREAD = false, int THREADS = FLUX_THREADS, bool PIECES = false, bool PERSIST = false>
+__global__ void __launch_bounds__(THREADS, 4)
+vag_flux_grid_kernel(FluxArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    for (int i = threadIdx.x; i < SP_LDS_DOUBLES; i += THREADS) lds[i] = a.sp_table[i];  // softplus table + log2 table (s_sp)
+    if constexpr (!PERSIST) {
+        flux_grid_item<COUNT, MODE, SPREAD, THREADS, PIECES>(a, blockIdx.y, blockIdx.x);
+        return;
+    }
+    // the item number passes through the first word of s_par: an item writes it only after its first barrier
+    int* s_it = reinterpret_cast<int*>(lds + SP_LDS_DOUBLES);
+    for (;;) {
+        __syncthreads();  // the previous item is done with the LDS
+        if (threadIdx.x == 0) *s_it = __hip_atomic_fetch_add(a.work, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const int it = __builtin_amdgcn_readfirstlane(*s_it);
+        if (it >= a.n_items) break;
+        const int r = it / a.max_blocks;
+        flux_grid_item<COUNT, MODE, SPREAD, THREADS, PIECES>(a, a.order[r], it - r * a.max_blocks);
+    }
+}
+
+// Deal order of a persistent flux launch: the models by descending predicted cost, ties in model order; failed models last.  The
+// cost is rows x ALL lattice nodes of the row, not rows x window nodes: the window of a row is known only after that row's EAT
+// step inside the flux kernel, nothing earlier records it, and the EAT step itself scales with all nodes.  A model's rank is the
+// count of models ahead of it: a wavefront per model, its lanes over the batch (a lane per model walking the whole batch was a
+// chain of dependent LDS reads, 1 ms per 16384 models).  Measured: 6 us per 512 configs[1] models, 56 us per 4096 (beside a
+// 159 ms flux launch).
+__global__ void __launch_bounds__(256)
+vag_flux_order_kernel(const VagGridMeta* __restrict__ meta, int nb, int* __restrict__ order) {
+    auto cost = [&](int j) -> long long {
+        const VagGridMeta& M = meta[j];
+        return M.status == 0 ? (long long)M.n_theta * M.n_phi_eff * M.n_t : -1;
+    };
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (m >= nb) return;
+    const long long c = cost(m);
+    int ahead = 0;
+#pragma unroll 4
+    for (int j = lane; j < nb; j += 64) {
+        const long long d = cost(j);
+        ahead += d > c || (d == c && j < m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ahead += __shfl_xor(ahead, o);
+    if (lane == 0) order[ahead] = m;
 }
 
 // Deterministic sum over a model's workgroup partials + normalisation
