@@ -66,21 +66,22 @@ struct VagDevPlan {
 };
 
 // Per-cell parameter block: [row][VAG_NPAR][n_t] in HBM, [k][VAG_NPAR] (144 B per cell) once staged in LDS.
-// 0..12: cached SmoothPowerLawSyn members read by compute_log2_I_nu (src/radiation/smooth-power-law-syn.h:20-47);
+// 0..12: cached SmoothPowerLawSyn members read by compute_log2_I_nu (src/radiation/smooth-power-law-syn.h:20-47), three of
+// them folded with a neighbour so that the evaluator's affine pieces are one FMA or one add each (log2_I_nu_fast);
 // 13..17: what the EAT step needs (src/core/observer.cpp:143-205).  Members used together sit in 16-byte aligned
 // pairs, so the staged block is read with seven conflict-free ds_read_b128.
 enum {
     VP_LG2_LO = 0,  // log2_nu_lo_
-    VP_LG2_HI,      // log2_nu_hi_
+    VP_BHI,         // -diff_hi_ * log2_nu_hi_: the upper softplus argument is fma(diff_hi_, log2 nu, this)
     VP_DLO,         // diff_lo_
     VP_INV_SLO,     // 1 / smooth_lo_  (== log2_norm_, smooth-power-law-syn.cpp:151)
     VP_DHI,         // diff_hi_
     VP_INV_SHI,     // 1 / smooth_hi_
     VP_LG2_NUM,     // log2_nu_m
-    VP_TNORM,       // log2_thick_norm_
+    VP_TB,          // log2_thick_norm_ - 2.5 log2_nu_m: thick branch + norm is fma(2.5, log2 nu, this) (+ softplus)
     VP_SAB,         // s_a_blend_
     VP_INV_SAB,     // 1 / s_a_blend_
-    VP_LG2_I,       // log2_I_nu_max
+    VP_LG2_I_SLO,   // log2_I_nu_max + 1 / smooth_lo_
     VP_LG2_NUMAX,   // log2_nu_M
     VP_INV_NUMAX,   // log2(e) / nu_M
     VP_LG2_R2,      // 2 log2 r

@@ -800,18 +800,20 @@ VAG_DEV void syn_photons_build(CellOut& o, double gamma_m, double gamma_c, doubl
     }
     thick_a = (l_a < l_m) ? 2. * (l_a - l_m) : 2.5 * (l_a - l_m);
 
-    o.par[VP_LG2_I] = l_I;
+    // the evaluator's per-cell constants, folded once here (vag_common.h): see log2_I_nu_fast
+    const double inv_slo = 1.0 / smooth_lo;
+    o.par[VP_LG2_I_SLO] = l_I + inv_slo;
     o.par[VP_LG2_NUM] = l_m;
     o.par[VP_LG2_NUMAX] = l_M;
     o.par[VP_INV_NUMAX] = LOG2E * (1.0 / nu_M);
-    o.par[VP_TNORM] = thin_a - thick_a;
+    o.par[VP_TB] = (thin_a - thick_a) - 2.5 * l_m;
     o.par[VP_SAB] = s_a_blend;
     o.par[VP_INV_SAB] = 1.0 / s_a_blend;
     o.par[VP_LG2_LO] = l_lo;
-    o.par[VP_LG2_HI] = l_hi;
+    o.par[VP_BHI] = -(diff_hi * l_hi);
     o.par[VP_DLO] = diff_lo;
     o.par[VP_DHI] = diff_hi;
-    o.par[VP_INV_SLO] = 1.0 / smooth_lo;
+    o.par[VP_INV_SLO] = inv_slo;
     o.par[VP_INV_SHI] = 1.0 / smooth_hi;
     o.par[VP_GAMMA] = Gamma;
     o.par[VP_U] = sqrt((Gamma - 1) * (Gamma + 1));
@@ -934,18 +936,17 @@ struct SpecConst {
 // `c` points at the cell's parameter column with stride `st` between parameters.
 template <class PtrT>
 VAG_DEV double log2_I_nu(const PtrT c, int st, const SpecConst& sc, double lg2_nu) {
-    const double l_lo = c[VP_LG2_LO * st], l_hi = c[VP_LG2_HI * st];
+    const double l_lo = c[VP_LG2_LO * st];
     const double thin = (lg2_nu - l_lo) / 3.0 - log2_softplus(c[VP_DLO * st] * (lg2_nu - l_lo)) * c[VP_INV_SLO * st] -
-                        log2_softplus(c[VP_DHI * st] * (lg2_nu - l_hi)) * c[VP_INV_SHI * st];
+                        log2_softplus(fma(c[VP_DHI * st], lg2_nu, c[VP_BHI * st])) * c[VP_INV_SHI * st];
     const double lx = lg2_nu - c[VP_LG2_NUM * st];
-    double thick = 2.5 * lx;
+    double lb = fma(2.5, lg2_nu, c[VP_TB * st]);
     if (!(lx > sc.log2_x_far)) {
         const double s = -sc.smooth_thick * exp2(2. / 3 * lx);
-        thick += log2_softplus(-0.5 * lx + s);
+        lb += log2_softplus(-0.5 * lx + s);
     }
-    const double lb = thick + c[VP_TNORM * st];
     const double smooth_one = thin - log2_softplus(c[VP_SAB * st] * (thin - lb)) * c[VP_INV_SAB * st];
-    const double spec = c[VP_LG2_I * st] + (c[VP_INV_SLO * st] + smooth_one);
+    const double spec = c[VP_LG2_I_SLO * st] + smooth_one;
     if (lg2_nu - c[VP_LG2_NUMAX * st] < -20) return spec;
     return spec - c[VP_INV_NUMAX * st] * exp2(lg2_nu);
 }
@@ -1072,6 +1073,20 @@ VAG_DEV double exp2_fast(double x) {  // finite x only: +-inf would give inf - i
     return ldexp(p, (int)n);
 }
 
+// exp2_fast(isfinite(x) ? x : -2000.0) of the flux interpolation for x finite, -inf or NaN (a slope that is not finite): the select
+// folded into ONE v_max_f64, which takes NaN and -inf to -2000, where v_ldexp_f64 gives 0 (the select was v_cmp_class_f64 plus two
+// v_cndmask_b32).  Same bits as that form on its domain; +inf, which an interpolation of finite-or-(-inf) boundary values never
+// produces, is outside it.
+VAG_DEV double exp2_or_zero(double x) {
+#ifdef VAG_HOST_DEBUG
+    return exp2_fast(x >= -2000.0 ? x : -2000.0);
+#else
+    double c;
+    asm("v_max_f64 %0, %1, %2" : "=v"(c) : "v"(x), "s"(-2000.0));
+    return exp2_fast(c);
+#endif
+}
+
 // exp2_fast for arguments that may be +-inf (log2 of 0 / overflowed ratios in the ODE right-hand sides and the IC
 // corrections): saturates to 0 / inf like exp2; NaN passes through.
 VAG_DEV double exp2_sat(double x) { return exp2_fast(dmin(dmax(x, -1100.0), 1100.0)); }
@@ -1160,18 +1175,17 @@ VAG_DEV void lds_add_f64(double* p, double v) {
 // compute_log2_I_nu (smooth-power-law-syn.cpp:15-46,80-92,159-167) on the fast kernels above.
 template <class PtrT, class Tab>
 VAG_DEV double log2_I_nu_fast(const PtrT& c, int st, const SpecConst& sc, double lg2_nu, Tab sp) {
-    const double l_lo = c[VP_LG2_LO * st], l_hi = c[VP_LG2_HI * st];
+    const double l_lo = c[VP_LG2_LO * st];
     const double thin = (lg2_nu - l_lo) * (1.0 / 3.0) - sp_fast(c[VP_DLO * st] * (lg2_nu - l_lo), sp) * c[VP_INV_SLO * st] -
-                        sp_fast(c[VP_DHI * st] * (lg2_nu - l_hi), sp) * c[VP_INV_SHI * st];
+                        sp_fast(fma(c[VP_DHI * st], lg2_nu, c[VP_BHI * st]), sp) * c[VP_INV_SHI * st];
     const double lx = lg2_nu - c[VP_LG2_NUM * st];
-    double thick = 2.5 * lx;
+    double lb = fma(2.5, lg2_nu, c[VP_TB * st]);  // thick branch 2.5 lx + log2_thick_norm_
     if (!(lx > sc.log2_x_far)) {
         const double s = -sc.smooth_thick * exp2_fast(2. / 3 * lx);
-        thick += sp_fast(-0.5 * lx + s, sp);
+        lb += sp_fast(-0.5 * lx + s, sp);
     }
-    const double lb = thick + c[VP_TNORM * st];
     const double smooth_one = thin - sp_fast(c[VP_SAB * st] * (thin - lb), sp) * c[VP_INV_SAB * st];
-    const double spec = c[VP_LG2_I * st] + (c[VP_INV_SLO * st] + smooth_one);
+    const double spec = c[VP_LG2_I_SLO * st] + smooth_one;
     if (lg2_nu - c[VP_LG2_NUMAX * st] < -20) return spec;
     return spec - c[VP_INV_NUMAX * st] * exp2_fast(lg2_nu);
 }
@@ -1198,22 +1212,21 @@ VAG_DEV double sp_fast_sel(double z, Tab tab) {
 }
 template <class PtrT, class Tab>
 VAG_DEV void log2_I_nu_fast2(const PtrT& c, const SpecConst& sc, double xa, double xb, Tab sp, double& ba, double& bb) {
-    const double l_lo = c[VP_LG2_LO], l_hi = c[VP_LG2_HI];
+    const double l_lo = c[VP_LG2_LO];
     double out[2];
     const double xs[2] = {xa, xb};
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         const double lg2_nu = xs[e];
         const double thin = (lg2_nu - l_lo) * (1.0 / 3.0) - sp_fast_sel(c[VP_DLO] * (lg2_nu - l_lo), sp) * c[VP_INV_SLO] -
-                            sp_fast_sel(c[VP_DHI] * (lg2_nu - l_hi), sp) * c[VP_INV_SHI];
+                            sp_fast_sel(fma(c[VP_DHI], lg2_nu, c[VP_BHI]), sp) * c[VP_INV_SHI];
         const double lx = lg2_nu - c[VP_LG2_NUM];
         const bool far = lx > sc.log2_x_far;
         const double s = -sc.smooth_thick * exp2_fast(2. / 3 * (far ? 0.0 : lx));
-        const double th = 2.5 * lx;
-        const double thick = far ? th : th + sp_fast_sel(-0.5 * lx + s, sp);
-        const double lb = thick + c[VP_TNORM];
+        const double th = fma(2.5, lg2_nu, c[VP_TB]);
+        const double lb = far ? th : th + sp_fast_sel(-0.5 * lx + s, sp);
         const double smooth_one = thin - sp_fast_sel(c[VP_SAB] * (thin - lb), sp) * c[VP_INV_SAB];
-        const double spec = c[VP_LG2_I] + (c[VP_INV_SLO] + smooth_one);
+        const double spec = c[VP_LG2_I_SLO] + smooth_one;
         const bool below = lg2_nu - c[VP_LG2_NUMAX] < -20;
         const double cut = spec - c[VP_INV_NUMAX] * exp2_fast(below ? 0.0 : lg2_nu);
         out[e] = below ? spec : cut;

@@ -239,24 +239,23 @@ template <bool STRAIGHT = false, bool HAVE_NU = false, class P1, class Tab>
 VAG_DEV double log2_I_nu_ic_core(const P1 c, int st, bool corrected, const IcQ& q, const SpecConst& sc, double lg2_nu, Tab sp,
                                  double nu_val = 0.0) {
     auto sp_ = [&](double z) { return STRAIGHT ? sp_fast_sel(z, sp) : sp_fast(z, sp); };
-    const double l_lo = c[VP_LG2_LO * st], l_hi = c[VP_LG2_HI * st];
+    const double l_lo = c[VP_LG2_LO * st];
     double thin = (lg2_nu - l_lo) * (1.0 / 3.0) - sp_(c[VP_DLO * st] * (lg2_nu - l_lo)) * c[VP_INV_SLO * st] -
-                  sp_(c[VP_DHI * st] * (lg2_nu - l_hi)) * c[VP_INV_SHI * st];
+                  sp_(fma(c[VP_DHI * st], lg2_nu, c[VP_BHI * st])) * c[VP_INV_SHI * st];
     if (corrected) thin += ic_thin_correction(q, lg2_nu, sp);
     const double lx = lg2_nu - c[VP_LG2_NUM * st];
-    double thick = 2.5 * lx;
+    double lb = fma(2.5, lg2_nu, c[VP_TB * st]);  // thick branch 2.5 lx + log2_thick_norm_ (log2_I_nu_fast)
     if (STRAIGHT) {
         const bool far = lx > sc.log2_x_far;
         const double s = -sc.smooth_thick * exp2_fast(2. / 3 * (far ? 0.0 : lx));
         const double add = sp_(-0.5 * lx + s);
-        thick += far ? 0.0 : add;
+        lb += far ? 0.0 : add;
     } else if (!(lx > sc.log2_x_far)) {
         const double s = -sc.smooth_thick * exp2_fast(2. / 3 * lx);
-        thick += sp_(-0.5 * lx + s);
+        lb += sp_(-0.5 * lx + s);
     }
-    const double lb = thick + c[VP_TNORM * st];
     const double smooth_one = thin - sp_(c[VP_SAB * st] * (thin - lb)) * c[VP_INV_SAB * st];
-    const double spec = c[VP_LG2_I * st] + (c[VP_INV_SLO * st] + smooth_one);
+    const double spec = c[VP_LG2_I_SLO * st] + smooth_one;
     if (HAVE_NU) return (lg2_nu - c[VP_LG2_NUMAX * st] < -20) ? spec : spec - c[VP_INV_NUMAX * st] * nu_val;
     if (lg2_nu - c[VP_LG2_NUMAX * st] < -20) return spec;
     return spec - c[VP_INV_NUMAX * st] * exp2_fast(lg2_nu);
@@ -778,7 +777,7 @@ vag_ic_photon_kernel(IcPhotonArgs args_unused_directly) {
     sh.ex[lane] = my_cst;  // `ex` is not written before the Thomson CDF
     wave_sync();
     double cp[VAG_NPAR];
-    for (int q : {VP_LG2_LO, VP_LG2_HI, VP_DLO, VP_INV_SLO, VP_DHI, VP_INV_SHI, VP_LG2_NUM, VP_TNORM, VP_SAB, VP_INV_SAB, VP_LG2_I,
+    for (int q : {VP_LG2_LO, VP_BHI, VP_DLO, VP_INV_SLO, VP_DHI, VP_INV_SHI, VP_LG2_NUM, VP_TB, VP_SAB, VP_INV_SAB, VP_LG2_I_SLO,
                   VP_LG2_NUMAX, VP_INV_NUMAX})
         cp[q] = sh.ex[q];
     IcQ icq;

@@ -1327,10 +1327,10 @@ __device__ __forceinline__ void flux_grid_item(const FluxArgs& a, const int m, c
                     // the slope (hi - lo) / (t[k+1] - t[k]) is finite <=> hi - lo is (observer.h:422-426); with the position w in
                     // [0, 1) -- or NaN for a time outside the row -- the exponent is finite exactly for the terms that count
                     const double x = fma(hi[u] - lo[u], wq[u], lo[u]);
-                    aq[u] += exp2_fast(isfinite(x) ? x : -2000.0);
+                    aq[u] += exp2_or_zero(x);
                     if constexpr (MODE == FLUX_FUSED) {
                         const double x2 = fma(hi2[u] - lo2[u], wq[u], lo2[u]);
-                        aq2[u] += exp2_fast(isfinite(x2) ? x2 : -2000.0);
+                        aq2[u] += exp2_or_zero(x2);
                     }
                 }
 #pragma unroll
