@@ -206,6 +206,25 @@ int vag_flux_density_grid_components_batch(vag_ctx* ctx, const vag_model_params*
 int vag_flux_density_grid_components4_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt,
                                             const double* nu, int nnu, double* const* out4);
 
+/* Sky images (Model.sky_image; the engine's own definition, INTEGRATION.md -- not pinned to the reference's method of that name).
+ * Added after VAG_ABI_VERSION 13 without changing it: callers detect vag_sky_image_batch / vag_sky_moments_batch by symbol.
+ * Every (phi, theta) row's equal-arrival-time term of every (nu, t) -- the terms flux_density_grid sums, in the same units -- is
+ * placed on the sky at X = r (cos theta sin theta_v - sin theta cos phi cos theta_v) / D_A, Y = r sin theta sin phi / D_A
+ * [rad], D_A = d_L / (1 + z)^2, +X along the projected jet axis; log r interpolated like the term, phi spread over the row's
+ * azimuthal bin in max(1, ceil(n_az dphi / 2 pi)) parts (both signs of phi on mirrored grids).
+ * image [nb][nnu][nt][npixel][npixel], [iy][ix], pixel size fov / npixel, centred on the burst: a part goes to
+ * ix = floor((X + fov / 2) / (fov / npixel)), likewise iy; parts outside the image are summed into outside [nb][nnu][nt] (NULL:
+ * not wanted).  image.sum + outside = flux_density_grid up to summation order.  erg cm^-2 s^-1 Hz^-1 per pixel.
+ * fov finite and > 0, 1 <= npixel <= 4096, n_az <= 0: 4 * npixel.  Results are bitwise reproducible run to run. */
+int vag_sky_image_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                        double fov, int npixel, int n_az, double* image, double* outside);
+
+/* Flux-weighted moments of the same point set before any pixelation, moments [nb][nnu][nt][6]: F (= flux_density_grid), centroid
+ * Xbar, Ybar [rad], central second moments varX, varY, covXY [rad^2] (two passes: accurate for a centroid many widths off
+ * centre).  F = 0: NaN for the five shape values.  n_az <= 0: 256. */
+int vag_sky_moments_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                          int n_az, double* moments);
+
 /*
  * Model.flux_density(t[n] ascending, nu[n]) -> total[n]
  * (pybind/pybind.cpp:427, pybind/pymodel.cpp:373-389, src/core/observer.h:447-538),

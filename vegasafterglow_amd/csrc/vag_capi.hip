@@ -24,6 +24,7 @@
 #include "vag_rs_kernels.h"
 #include "vag_fit_rows.h"
 #include "vag_grid_rows.h"
+#include "vag_sky.h"
 
 using namespace vag;
 
@@ -401,6 +402,7 @@ struct vag_ctx {
     // SSC tables: a header per cell, the lattice plan between the plan and the spectrum kernel, and the pool of tables (each as long
     // as its own output lattice; offsets handed out by vag_ic_plan_kernel, d_icused counts the doubles in use)
     DevBuf d_ichdr, d_icplan, d_icpool, d_icused, d_icslow /* records of the cells on the spectrum kernel's slow path */;
+    DevBuf d_skyterms, d_skyimg, d_skymom;  // sky images / moments (vag_sky.h): term list, a chunk's images, moments + outside
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
     bool ic_all_cells = false;    // this request's SSC tables are built for every cell (the lazy selection was caught with a hole, see check_ic_status)
@@ -689,7 +691,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     c->h_fit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1873,6 +1875,130 @@ int grid_request_chunked(vag_ctx* c, const vag_model_params* d_params, int nb, i
     return rc;
 }
 
+// Sky images / image moments of the whole batch (vag_sky.h); model stages already run, d_lg2t / d_lg2nu prepared.  Every enabled
+// (emitter, pass) -- forward synchrotron, forward SSC, reverse synchrotron, reverse SSC, as grid_request runs them -- writes its
+// terms into its own slice of one term list, then the deposit and moment kernels read all slices in that fixed order.  The time axis
+// is cut into chunks whose term list and images stay within 256 MB (VAG_SKY_CHUNK_T: a test's chunk length).  Host outputs:
+// h_image [nb][nnu][nt][npixel^2], h_outside [nb][nnu][nt], h_moments [nb][nnu][nt][6]; any may be null.
+int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, int nnu, int n_az, double fov, int npixel,
+                double* h_image, double* h_outside, double* h_moments) {
+    hipStream_t st = c->stream;
+    struct SkyPass {
+        int e, pass;
+    };
+    std::vector<SkyPass> passes;
+    const int n_em = (c->batch_flags & VAG_FLAG_RVS) ? 2 : 1;
+    for (int e = 0; e < n_em; ++e) {
+        passes.push_back({e, 0});
+        if (c->batch_flags & (e == 0 ? VAG_FLAG_SSC : VAG_FLAG_RVS_SSC)) passes.push_back({e, 1});
+    }
+    const int n_pass = (int)passes.size();
+    const int R = std::max(1, c->max_pairs), ks = std::max(2, c->max_k);
+    const size_t npix2 = h_image ? (size_t)npixel * npixel : 0;
+    const size_t per_t = sizeof(double) * (size_t)nb * nnu * ((size_t)n_pass * 4 * R + npix2);
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>(nt, ((size_t)256 << 20) / per_t));
+    if (const char* e = vag_hook("VAG_SKY_CHUNK_T")) chunk = std::max(1, std::min(nt, std::atoi(e)));
+    const size_t lds = sizeof(double) * ((size_t)SP_LDS_DOUBLES + (size_t)SKY_WAVES * 3 * ks);
+    if (lds > 160 * 1024) return set_err(VAG_E_CAPACITY, "sky image: lattices of %d nodes exceed the terms kernel's LDS", ks);
+    const size_t G_max = (size_t)nb * nnu * chunk;
+    if (c->d_skyterms.ensure(sizeof(double) * (size_t)n_pass * 4 * G_max * R)) return VAG_E_HIP;
+    if (h_image && c->d_skyimg.ensure(sizeof(double) * G_max * npix2)) return VAG_E_HIP;
+    const size_t n_bins = (size_t)nb * nnu * nt;
+    if (c->d_skymom.ensure(sizeof(double) * n_bins * 7)) return VAG_E_HIP;
+    double* d_mom = c->d_skymom.as<double>();
+    double* d_out = d_mom + n_bins * 6;
+    const bool spreading = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
+    int rc = VAG_OK;
+    for (int t0 = 0; t0 < nt && rc == VAG_OK; t0 += chunk) {
+        const int n = std::min(chunk, nt - t0);
+        const size_t G = (size_t)nb * nnu * n;
+        for (int q = 0; q < n_pass && rc == VAG_OK; ++q) {
+            select_emitter(c, passes[q].e, d_params);
+            SkyArgs a{};
+            a.params = c->cur_params;
+            a.meta = c->d_meta.as<VagGridMeta>();
+            a.geo_th = c->d_geo_th.as<double>();
+            a.geo_ph = c->d_geo_ph.as<double>();
+            a.g_rep_of = c->d_rep_of.as<int>();
+            a.cell_off = c->d_cell_off.as<long long>();
+            a.cellpar = c->d_cellpar.as<double>();
+            a.cellq = c->d_cellq.as<double>();
+            a.cellgeo = c->d_cellgeo.as<double>();
+            a.sp_table = c->d_sptab.as<double>();
+            a.lg2_t_obs = c->d_lg2t.as<double>() + t0;
+            a.lg2_nu_obs = c->d_lg2nu.as<double>();
+            a.nt = n;
+            a.nnu = nnu;
+            a.R = R;
+            a.ks = ks;
+            a.terms = c->d_skyterms.as<double>() + (size_t)q * 4 * G * R;
+            const int mode = passes[q].pass == 1 ? FLUX_SSC : (c->cur_ssc ? FLUX_SYN_IC : FLUX_SYN);
+            auto launch = [&](auto kernel) -> int {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                hipLaunchKernelGGL(kernel, dim3((R + SKY_WAVES - 1) / SKY_WAVES, nb), dim3(64 * SKY_WAVES), lds, st, a);
+                HIPCHK(hipGetLastError());
+                return VAG_OK;
+            };
+            auto terms = [&]() -> int {
+                StageScope ps(c, mode == FLUX_SSC ? PS_SSC_FLUX : PS_SYNC_FLUX);
+                // the table build (re)allocates its buffers: their addresses are taken behind it, at the launch
+                a.ichdr = c->d_ichdr.as<double>();
+                a.icpool = c->d_icpool.as<double>();
+                a.ic_status = c->d_icstatus.as<int>();
+                if (mode == FLUX_SSC)
+                    return spreading ? launch(vag_sky_terms_kernel<FLUX_SSC, true>) : launch(vag_sky_terms_kernel<FLUX_SSC, false>);
+                if (mode == FLUX_SYN_IC)
+                    return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN_IC, true>) : launch(vag_sky_terms_kernel<FLUX_SYN_IC, false>);
+                return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN, true>) : launch(vag_sky_terms_kernel<FLUX_SYN, false>);
+            };
+            if (mode == FLUX_SSC) {  // the tables clamped to the requested frequencies exactly as a grid call clamps them
+                rc = ssc_attempts(c, nb, [&](bool rebuild) {
+                    const int rb = build_ssc_tables(c, c->cur_params, nb, c->d_lg2nu.as<double>(), nnu, rebuild);
+                    return rb ? rb : terms();
+                });
+            } else {
+                rc = terms();
+            }
+        }
+        select_emitter(c, 0, d_params);
+        if (rc) break;
+        SkyImgArgs b{};
+        b.meta = c->d_meta.as<VagGridMeta>();
+        b.phi = c->d_phi.as<double>();
+        b.terms = c->d_skyterms.as<double>();
+        b.n_pass = n_pass;
+        b.nnu = nnu;
+        b.nt = n;
+        b.R = R;
+        b.n_az = n_az;
+        b.nt_all = nt;
+        b.t0 = t0;
+        b.fov = h_image ? fov : 0.0;
+        b.npixel = h_image ? npixel : 1;
+        b.image = c->d_skyimg.as<double>();
+        b.image_chunk = 1;
+        b.moments = h_moments ? d_mom : nullptr;
+        b.outside = h_outside ? d_out : nullptr;
+        if (h_image) {
+            const int tiles = (npixel + SKY_TILE - 1) / SKY_TILE;
+            hipLaunchKernelGGL(vag_sky_deposit_kernel, dim3(tiles * tiles, (unsigned)G), dim3(64), 0, st, b);
+            HIPCHK(hipGetLastError());
+        }
+        if (b.moments || b.outside) {
+            hipLaunchKernelGGL(vag_sky_moments_kernel, dim3((unsigned)G), dim3(64), 0, st, b);
+            HIPCHK(hipGetLastError());
+        }
+        if (h_image)  // [nb * nnu][n][npixel^2] -> its place in [nb * nnu][nt][npixel^2]
+            HIPCHK(hipMemcpy2DAsync(h_image + (size_t)t0 * npix2, sizeof(double) * nt * npix2, c->d_skyimg.p, sizeof(double) * n * npix2,
+                                    sizeof(double) * n * npix2, (size_t)nb * nnu, hipMemcpyDeviceToHost, st));
+    }
+    if (rc) return rc;
+    if (h_moments) HIPCHK(hipMemcpyAsync(h_moments, d_mom, sizeof(double) * n_bins * 6, hipMemcpyDeviceToHost, st));
+    if (h_outside) HIPCHK(hipMemcpyAsync(h_outside, d_out, sizeof(double) * n_bins, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return VAG_OK;
+}
+
 // Fixed-order sum of the workgroup partials of a series request.  A workgroup is 64 points x 4 block groups: group g adds the
 // partial blocks b = g, g + 4, ... with four loads in flight, then the four group sums are added in order -- the same
 // result run to run, and the walk over up to a few hundred blocks is no longer one dependent load after another
@@ -2605,6 +2731,56 @@ int vag_flux_density_grid_components4_batch(vag_ctx* c, const vag_model_params* 
     if (!out4) return set_err(VAG_E_INVALID, "out4 must not be null");
     if (!nu) return set_err(VAG_E_INVALID, "null frequency array");
     return grid_components_impl(c, params, nb, t, nt, nu, nnu, out4);
+}
+
+// Model.sky_image / Model.sky_moments over a batch (vag_sky.h; the definition is the engine's own)
+static int sky_impl(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu, int n_az,
+                    double fov, int npixel, double* image, double* outside, double* moments) {
+    int rc = check_host_inputs(params, nb, t, nt);
+    if (rc) return rc;
+    if (!uniform_flags(params, nb)) {
+        const size_t st = (size_t)nnu * nt;
+        return run_flag_groups(params, nb, {{image, st * npixel * npixel}, {outside, st}, {moments, st * 6}},
+                               [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
+                                   return sky_impl(c, gp, ng, t, nt, nu, nnu, n_az, fov, npixel, o[0], o[1], o[2]);
+                               });
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
+    if (c->d_t.ensure(sizeof(double) * nt)) return VAG_E_HIP;
+    if (c->d_nu.ensure(sizeof(double) * nnu)) return VAG_E_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * nt, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_nu.p, nu, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream));
+    rc = prep_times(c, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu);
+    if (rc) return rc;
+    rc = run_model_stages(c, c->d_params.as<vag_model_params>(), nb, false);
+    if (rc) return rc;
+    rc = sky_request(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, n_az, fov, npixel, image, outside, moments);
+    if (rc) return rc;
+    return check_status(c, nb);  // (no collect_times: the flux events it reads are not recorded by the sky passes)
+}
+
+int vag_sky_image_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                        double fov, int npixel, int n_az, double* image, double* outside) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!nu || !image) return set_err(VAG_E_INVALID, "null frequency or image array");
+    if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
+    if (!(std::isfinite(fov) && fov > 0)) return set_err(VAG_E_INVALID, "fov must be positive and finite");
+    if (npixel < 1 || npixel > 4096) return set_err(VAG_E_INVALID, "npixel must be in [1, 4096]");
+    if (n_az <= 0) n_az = 4 * npixel;
+    return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, fov, npixel, image, outside, nullptr);
+}
+
+int vag_sky_moments_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                          int n_az, double* moments) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!nu || !moments) return set_err(VAG_E_INVALID, "null frequency or moments array");
+    if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
+    if (n_az <= 0) n_az = 256;
+    return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, 0.0, 1, nullptr, nullptr, moments);
 }
 
 int vag_flux_density_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, const double* nu, int n,

@@ -1,0 +1,355 @@
+// Sky images and flux-weighted image moments (Model.sky_image / sky_moments; the definition is the engine's own).
+//
+// Three kernels per (time chunk of a) request, all in a fixed order of summation:
+//   vag_sky_terms_kernel    one wavefront per (theta, phi) row: the row's EAT logs, the bracket of every requested time, the two
+//                           boundary spectra of every (nu, t) term with the grid flux pass's evaluators and roundings, the term
+//                           exp2(lo + f (hi - lo)) in flux units and its sky-position constants -> a dense term list
+//                           [pass][4][image][row] (weight, a, b, c: X = a - b cos phi, Y = c sin phi)
+//   vag_sky_deposit_kernel  one wavefront per (image, SKY_TILE^2 pixel tile): the term list in row order, every term split into
+//                           its azimuthal parts, the parts that land in the tile added to the tile in LDS with ds_add_f64 (the
+//                           lanes of one instruction are applied in lane order, and the tile belongs to one wavefront)
+//   vag_sky_moments_kernel  one wavefront per image: F, centroid, central second moments in two passes over the same parts, and
+//                           the weight that falls outside the image
+// DESIGN §4k.
+#pragma once
+
+namespace vag {
+
+constexpr int SKY_WAVES = 4;  // rows (wavefronts) per workgroup of the terms kernel
+constexpr int SKY_TILE = 64;  // pixels per side of a deposit tile (32 KB of LDS)
+
+struct SkyArgs {
+    const vag_model_params* params;  // of the selected emitter (the reverse shock's Radiation for emitter 1)
+    const VagGridMeta* meta;
+    const double* geo_th;  // [nb][3][th_stride]: cos theta, sin theta, log2 |dcos theta|
+    const double* geo_ph;  // [nb][2][ph_stride]: cos phi, log2 dphi
+    const int* g_rep_of;
+    const long long* cell_off;
+    const double* cellpar;  // [rows][VAG_NPAR][n_t] of the selected emitter
+    const double* cellq;    // FLUX_SYN_IC
+    const double* cellgeo;  // spreading jets: [rows][3][n_t] cos theta, sin theta, log2 |dcos|
+    const double* ichdr;    // FLUX_SSC
+    const double* icpool;
+    int* ic_status;
+    const double* sp_table;
+    const double* lg2_t_obs;   // [nt] of this chunk
+    const double* lg2_nu_obs;  // [nnu]
+    int nt, nnu, R;            // R: row stride of the term list (>= n_theta * n_phi_eff of every model)
+    int ks;                    // LDS row length (>= every lattice of the batch)
+    double* terms;             // [4][nb * nnu * nt][R] of this pass
+};
+
+// The terms of one (theta, phi) row for every (nu, t) of the chunk.  MODE / SPREAD as in vag_flux_grid_kernel.
+template <int MODE, bool SPREAD>
+__global__ void __launch_bounds__(64 * SKY_WAVES) vag_sky_terms_kernel(SkyArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* s_sp = lds;
+    for (int i = threadIdx.x; i < SP_LDS_DOUBLES; i += blockDim.x) s_sp[i] = a.sp_table[i];
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int m = blockIdx.y, p = blockIdx.x * SKY_WAVES + wave;
+    if (p >= a.R) return;
+    const VagGridMeta* Mp = a.meta + m;
+    const int nt = a.nt, nnu = a.nnu, slots = nt * nnu;
+    const size_t G = (size_t)gridDim.y * nnu * nt, plane = G * a.R;
+    double* out = a.terms + ((size_t)m * nnu * nt) * a.R + p;  // + (l * nt + idx) * R + comp * plane
+    const int n_pairs = Mp->status == 0 ? Mp->n_theta * Mp->n_phi_eff : 0;
+    if (p >= n_pairs) {
+        for (int s = lane; s < slots; s += 64)
+            for (int q = 0; q < 4; ++q) out[(size_t)s * a.R + q * plane] = 0.0;
+        return;
+    }
+    const LdsTab sp_tab = lds_tab(s_sp), lg_tab = lds_tab(s_sp + SP_TABLE_DOUBLES);
+    double* s_t = s_sp + SP_LDS_DOUBLES + (size_t)wave * 3 * a.ks;
+    double* s_dop = s_t + a.ks;
+    double* s_geom = s_dop + a.ks;
+    const int n_phi_eff = Mp->n_phi_eff, j = p / n_phi_eff, i = p - j * n_phi_eff;
+    const int K = Mp->n_t, ts = Mp->th_stride, ps = Mp->ph_stride;
+    const double* gth = a.geo_th + (size_t)m * 3 * ts;
+    const double* gph = a.geo_ph + (size_t)m * 2 * ps;
+    const int rep = a.g_rep_of[(size_t)m * ts + j] + i * Mp->rep_phi_stride;
+    const long long cell0 = a.cell_off[m] + (long long)rep * K;
+    const double* row = a.cellpar + cell0 * VAG_NPAR;  // [VAG_NPAR][K]
+    const double* geo = SPREAD ? a.cellgeo + cell0 * 3 : nullptr;
+    const vag_model_params* Pp = a.params + m;
+    const double one_plus_z = 1 + Pp->z;
+    const double cos_obs = Mp->cos_obs, sin_obs = Mp->sin_obs;
+    // EAT logs of the row: eat_row / eat_row_spread, expression for expression
+    const double cos_th = gth[j], sin_th = gth[ts + j], cph = gph[i];
+    const double cos_v_row = fma(cos_th, cos_obs, (sin_th * cph) * sin_obs);  // RowGeo::cos_view
+    const double t_coeff = (1 - cos_v_row) * (one_plus_z / C_C);
+    const double lg2_dOmega = gth[2 * ts + j] + gph[ps + i];
+    for (int k = lane; k < K; k += 64) {
+        const double G_ = row[VP_GAMMA * K + k], u = row[VP_U * K + k], r = row[VP_R * K + k], teng = row[VP_TENG * K + k];
+        const double lr2 = row[VP_LG2_R2 * K + k];
+        if constexpr (SPREAD) {
+            const double cos_v = geo[K + k] * cph * sin_obs + geo[k] * cos_obs;
+            const double lg2_dop = -log2_tab(G_ - u * cos_v, lg_tab);
+            const double time = (teng + (1 - cos_v) * r / C_C) * one_plus_z;
+            s_dop[k] = lg2_dop;
+            s_t[k] = log2_tab(time, lg_tab);
+            s_geom[k] = ((geo[2 * K + k] + gph[ps + i]) + lr2) + 3.0 * lg2_dop;
+        } else {
+            const double lg2_dop = -log2_tab(fma(-u, cos_v_row, G_), lg_tab);
+            s_dop[k] = lg2_dop;
+            s_t[k] = log2_tab(fma(t_coeff, r, teng * one_plus_z), lg_tab);
+            s_geom[k] = (lg2_dOmega + lr2) + 3.0 * lg2_dop;
+        }
+    }
+    wave_sync();
+    SpecConst sc;
+    sc.init(Pp->p);
+    int breach = 0;
+    auto boundary = [&](int k, double x) -> double {  // log2 I'(x) + geom_k: the grid flux pass's evaluator for MODE
+        if constexpr (MODE == FLUX_SYN) {
+            SpecRegs regs;
+#pragma unroll
+            for (int w = 0; w < 14; ++w) regs.v[w] = row[w * K + k];
+            return log2_I_nu_fast(regs, 1, sc, x, sp_tab) + s_geom[k];
+        } else if constexpr (MODE == FLUX_SYN_IC) {
+            double b0, b1;
+            log2_I_nu_ic_pair(row + k, K, a.cellq + cell0 * FLUX_NQ + k, K, sc, x, x, sp_tab, b0, b1);
+            return b0 + s_geom[k];
+        } else {
+            const double* hp = a.ichdr + (size_t)(cell0 + k) * FLUX_IC_HDR;
+            const double* tab = a.icpool + (unsigned long long)hp[5];
+            return ic_table_eval_hdr(tab, hp[0], hp[1], hp[2], hp[3], hp[4], x, &breach) + s_geom[k];
+        }
+    };
+    const double row_t0 = s_t[0], row_tN = s_t[K - 1];
+    const double d_L = Pp->lumi_dist * U_CM;
+    const double norm = one_plus_z / (d_L * d_L);
+    // a sky angle [rad] per unit radius: 1 / D_A, D_A = d_L / (1 + z)^2 (the observer's own d_L and z, also for the reverse shock)
+    const double inv_DA = (one_plus_z * one_plus_z) / d_L;
+    for (int s = lane; s < slots; s += 64) {
+        const int l = s / nt, idx = s - l * nt;
+        const double tq = a.lg2_t_obs[idx];
+        double wgt = 0, ca = 0, cb = 0, cc = 0;
+        if (tq >= row_t0 && tq < row_tN) {  // a time outside the row's lattice contributes nothing (observer.h:405-433)
+            int lo = 0, hi = K - 1;         // s_t[lo] <= tq < s_t[hi]
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_t[mid] <= tq)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            const double t_lo = s_t[lo];
+            const double f = (tq - t_lo) * (1.0 / (s_t[lo + 1] - t_lo));
+            const double nu = a.lg2_nu_obs[l] + Mp->lg2_1pz;
+            const double b_lo = boundary(lo, nu - s_dop[lo]), b_hi = boundary(lo + 1, nu - s_dop[lo + 1]);
+            const double x = fma(b_hi - b_lo, f, b_lo);
+            wgt = (exp2_or_zero(x) * norm) / U_FLUX_DEN_CGS;
+            if (wgt != 0) {
+                const double lr_lo = log2(row[VP_R * K + lo]), lr_hi = log2(row[VP_R * K + lo + 1]);
+                const double rr = exp2(lr_lo + f * (lr_hi - lr_lo)) * inv_DA;
+                double ct = cos_th, st = sin_th;
+                if constexpr (SPREAD) {
+                    const double th_lo = atan2(geo[K + lo], geo[lo]), th_hi = atan2(geo[K + lo + 1], geo[lo + 1]);
+                    const double th = th_lo + f * (th_hi - th_lo);
+                    ct = cos(th);
+                    st = sin(th);
+                }
+                ca = rr * ct * sin_obs;
+                cb = rr * st * cos_obs;
+                cc = rr * st;
+            }
+        }
+        double* o = out + (size_t)s * a.R;
+        o[0] = wgt;
+        o[plane] = ca;
+        o[2 * plane] = cb;
+        o[3 * plane] = cc;
+    }
+    if constexpr (MODE == FLUX_SSC) {
+        if (breach) atomicOr(a.ic_status + m, ic_breach_status(breach));
+    }
+}
+
+// The azimuthal bin of a row's phi node (the bin whose width enters its solid angle) and its number of parts.
+struct SkyBin {
+    double left, width;
+    int S;
+    bool mirrored;
+};
+VAG_DEV SkyBin sky_bin(const VagGridMeta& M, const double* phi, int p, int n_az) {
+    SkyBin b;
+    const int npe = M.n_phi_eff, i = p % npe, last = npe - 1;
+    b.mirrored = false;
+    if (npe == 1) {
+        b.left = 0.0;
+        b.width = 2 * C_PI;
+    } else if (M.phi_mirrored) {
+        b.mirrored = true;
+        b.left = (i > 0) ? 0.5 * (phi[i - 1] + phi[i]) : 0.0;
+        const double right = (i < last) ? 0.5 * (phi[i] + phi[i + 1]) : C_PI;
+        b.width = right - b.left;
+    } else {
+        b.left = (i > 0) ? 0.5 * (phi[i - 1] + phi[i]) : phi[0];
+        const double right = (i < last) ? 0.5 * (phi[i] + phi[i + 1]) : phi[last];
+        b.width = right - b.left;
+    }
+    b.S = max(1, (int)ceil((double)n_az * b.width / (2 * C_PI)));
+    return b;
+}
+
+struct SkyImgArgs {
+    const VagGridMeta* meta;
+    const double* phi;  // [nb][ph_stride]
+    const double* terms;
+    int n_pass, nnu, nt, R, n_az;
+    int nt_all, t0;  // the request's times, first time of this chunk
+    double fov;
+    int npixel;
+    double* image;    // [nb][nnu][nt_all][npixel][npixel] (deposit) or this chunk's [nb * nnu * nt][npixel^2]
+    int image_chunk;  // 1: image is the chunk's buffer
+    double* moments;  // [nb][nnu][nt_all][6] or nullptr
+    double* outside;  // [nb][nnu][nt_all] or nullptr
+};
+
+VAG_DEV size_t sky_out_index(const SkyImgArgs& a, int g) {  // image g of the chunk -> (m, l, t0 + idx) of the request
+    const int idx = g % a.nt, ml = g / a.nt;
+    return (size_t)ml * a.nt_all + a.t0 + idx;
+}
+
+// One wavefront per (pixel tile, image of the chunk).
+__global__ void __launch_bounds__(64) vag_sky_deposit_kernel(SkyImgArgs a) {
+    __shared__ double tile[SKY_TILE * SKY_TILE];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.y, n_tx = (a.npixel + SKY_TILE - 1) / SKY_TILE;
+    const int tx0 = (blockIdx.x % n_tx) * SKY_TILE, ty0 = (blockIdx.x / n_tx) * SKY_TILE;
+    const int m = g / (a.nnu * a.nt);
+    for (int q = lane; q < SKY_TILE * SKY_TILE; q += 64) tile[q] = 0.0;
+    wave_sync();
+    const VagGridMeta M = a.meta[m];
+    const double* phi = a.phi + (size_t)m * M.ph_stride;
+    const double half = 0.5 * a.fov, delta = a.fov / a.npixel;
+    const size_t G = (size_t)gridDim.y, plane = G * a.R;
+    // tile bounds in sky coordinates, one pixel wider on every side (a conservative cull; the pixel test below decides)
+    const double xlo = (tx0 - 1) * delta - half, xhi = (tx0 + SKY_TILE + 1) * delta - half;
+    const double ylo = (ty0 - 1) * delta - half, yhi = (ty0 + SKY_TILE + 1) * delta - half;
+    const int n_rows = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    for (int pass = 0; pass < a.n_pass; ++pass) {
+        const double* T = a.terms + (size_t)pass * 4 * plane + (size_t)g * a.R;
+        for (int r0 = 0; r0 < n_rows; r0 += 64) {
+            const int p = r0 + lane;
+            double w = 0, ca = 0, cb = 0, cc = 0;
+            if (p < n_rows) w = T[p], ca = T[plane + p], cb = T[2 * plane + p], cc = T[3 * plane + p];
+            if (!(w > 0)) continue;
+            if (ca + fabs(cb) < xlo || ca - fabs(cb) > xhi || fabs(cc) < ylo || -fabs(cc) > yhi) continue;
+            const SkyBin b = sky_bin(M, phi, p, a.n_az);
+            const double part = w / b.S, dphi = b.width / b.S;
+            const double wp = b.mirrored ? 0.5 * part : part;
+            for (int s = 0; s < b.S; ++s) {
+                const double ph = b.left + (s + 0.5) * dphi;
+                double sn, cs;
+                sincos(ph, &sn, &cs);
+                const double X = ca - cb * cs, Y = cc * sn;
+                const double fx = floor((X + half) / delta);
+                for (int h = 0; h < (b.mirrored ? 2 : 1); ++h) {
+                    const double fy = floor(((h ? -Y : Y) + half) / delta);
+                    if (fx >= tx0 && fx < tx0 + SKY_TILE && fx < a.npixel && fy >= ty0 && fy < ty0 + SKY_TILE && fy < a.npixel)
+                        lds_add_f64(&tile[((int)fy - ty0) * SKY_TILE + ((int)fx - tx0)], wp);
+                }
+            }
+        }
+    }
+    wave_sync();
+    const size_t npix2 = (size_t)a.npixel * a.npixel;
+    double* img = a.image + (a.image_chunk ? (size_t)g : sky_out_index(a, g)) * npix2;
+    for (int q = lane; q < SKY_TILE * SKY_TILE; q += 64) {
+        const int y = ty0 + q / SKY_TILE, x = tx0 + q % SKY_TILE;
+        if (x < a.npixel && y < a.npixel) img[(size_t)y * a.npixel + x] = tile[q];
+    }
+}
+
+// lane 0 adds the 64 lane values in lane order; every lane gets the sum
+VAG_DEV double sky_wave_sum(double v, double* s_red) {
+    wave_sync();
+    s_red[threadIdx.x] = v;
+    wave_sync();
+    double t = 0;
+    for (int q = 0; q < 64; ++q) t += s_red[q];  // every lane forms the same sum in the same order
+    wave_sync();
+    return t;
+}
+
+// One wavefront per image of the chunk: moments (a.moments) and / or the weight outside the image (a.outside, a.fov > 0).
+__global__ void __launch_bounds__(64) vag_sky_moments_kernel(SkyImgArgs a) {
+    __shared__ double s_red[64];
+    const int lane = threadIdx.x, g = blockIdx.x;
+    const int m = g / (a.nnu * a.nt);
+    const VagGridMeta M = a.meta[m];
+    const double* phi = a.phi + (size_t)m * M.ph_stride;
+    const size_t G = (size_t)gridDim.x, plane = G * a.R;
+    const int n_rows = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    const double half = 0.5 * a.fov, delta = a.fov / a.npixel;
+    // visit(fn): every part (weight, X, Y) of this lane's rows, rows in order, parts in order
+    auto visit = [&](auto&& fn) {
+#pragma unroll 1
+        for (int pass = 0; pass < a.n_pass; ++pass) {
+            const double* T = a.terms + (size_t)pass * 4 * plane + (size_t)g * a.R;
+#pragma unroll 1
+            for (int p = lane; p < n_rows; p += 64) {
+                const double w = T[p];
+                if (!(w > 0)) continue;
+                const double ca = T[plane + p], cb = T[2 * plane + p], cc = T[3 * plane + p];
+                const SkyBin b = sky_bin(M, phi, p, a.n_az);
+                const double part = w / b.S, dphi = b.width / b.S;
+                const double wp = b.mirrored ? 0.5 * part : part;
+#pragma unroll 1
+                for (int s = 0; s < b.S; ++s) {
+                    const double ph = b.left + (s + 0.5) * dphi;
+                    double sn, cs;
+                    sincos(ph, &sn, &cs);
+                    const double X = ca - cb * cs, Y = cc * sn;
+                    fn(wp, X, Y);
+                    if (b.mirrored) fn(wp, X, -Y);
+                }
+            }
+        }
+    };
+    double F = 0, SX = 0, SY = 0, out = 0;
+    const bool want_out = a.outside != nullptr;
+    visit([&](double w, double X, double Y) {
+        F += w;
+        SX += w * X;
+        SY += w * Y;
+        if (want_out) {
+            const double fx = floor((X + half) / delta), fy = floor((Y + half) / delta);
+            if (!(fx >= 0 && fx < a.npixel && fy >= 0 && fy < a.npixel)) out += w;
+        }
+    });
+    F = sky_wave_sum(F, s_red);
+    const size_t o = sky_out_index(a, g);
+    if (want_out) {
+        out = sky_wave_sum(out, s_red);
+        if (lane == 0) a.outside[o] = out;
+    }
+    if (!a.moments) return;
+    SX = sky_wave_sum(SX, s_red);
+    SY = sky_wave_sum(SY, s_red);
+    const double xb = SX / F, yb = SY / F;
+    double Sxx = 0, Syy = 0, Sxy = 0;
+    visit([&](double w, double X, double Y) {
+        const double dx = X - xb, dy = Y - yb;
+        Sxx += w * dx * dx;
+        Syy += w * dy * dy;
+        Sxy += w * dx * dy;
+    });
+    Sxx = sky_wave_sum(Sxx, s_red);
+    Syy = sky_wave_sum(Syy, s_red);
+    Sxy = sky_wave_sum(Sxy, s_red);
+    if (lane == 0) {
+        double* mo = a.moments + o * 6;
+        const bool ok = F > 0;
+        mo[0] = F;
+        mo[1] = ok ? xb : NAN;
+        mo[2] = ok ? yb : NAN;
+        mo[3] = ok ? Sxx / F : NAN;
+        mo[4] = ok ? Syy / F : NAN;
+        mo[5] = ok ? Sxy / F : NAN;
+    }
+}
+
+}  // namespace vag

@@ -268,6 +268,37 @@ class FluxDict:
             a.setflags(write=False)
 
 
+class SkyImage:
+    """Model.sky_image result.  image[..., iy, ix] in erg cm^-2 s^-1 Hz^-1 per pixel, (nnu, nt, npixel, npixel) -- (nt, npixel,
+    npixel) for a scalar nu --; outside: the flux that falls outside the image, same leading shape; extent = (-fov/2, fov/2,
+    -fov/2, fov/2) [rad] for imshow(image, origin="lower", extent=extent), +X along the projected jet axis; pixel_solid_angle
+    = (fov / npixel)^2 [sr]."""
+
+    def __init__(self, image, outside, fov, t, nu):
+        self.image, self.outside, self.fov, self.t, self.nu = image, outside, fov, t, nu
+        self.npixel = image.shape[-1]
+        self.extent = (-fov / 2, fov / 2, -fov / 2, fov / 2)
+        self.pixel_solid_angle = (fov / self.npixel) ** 2
+
+    def __repr__(self):
+        return f"SkyImage(shape={self.image.shape}, fov={self.fov!r})"
+
+
+class SkyMoments:
+    """Model.sky_moments result: flux F [erg cm^-2 s^-1 Hz^-1], centroid Xbar, Ybar [rad] and central second moments varX,
+    varY, covXY [rad^2] of the image before pixelation, each (nnu, nt) -- (nt,) for a scalar nu; NaN shape values where F = 0."""
+
+    names = ("F", "Xbar", "Ybar", "varX", "varY", "covXY")
+
+    def __init__(self, m, t, nu):
+        for q, n in enumerate(self.names):
+            setattr(self, n, m[..., q].copy())
+        self.t, self.nu = t, nu
+
+    def __repr__(self):
+        return f"SkyMoments(shape={self.F.shape})"
+
+
 _ctx_lock = threading.Lock()
 _ctx = {}
 
@@ -450,6 +481,51 @@ class Model:
                 h, C.byref(self.params), 1, t.ctypes.data_as(_dp), nu.ctypes.data_as(_dp), t.size,
                 out.ctypes.data_as(_dp)))
         return FluxDict(out)
+
+    # -- Model.sky_image / sky_moments: the engine's own definition, not pinned to the reference's sky_image --
+    def _sky_inputs(self, t, nu, n_az):
+        scalar = np.ndim(nu) == 0
+        t, nu = _as_f64(t, "t"), _as_f64(np.atleast_1d(nu), "nu")
+        _req(t.size > 0, "time array must be non-empty")
+        _req(nu.size > 0, "frequency array must be non-empty")
+        _req(bool(np.all(np.isfinite(t) & (t > 0))), "times must be positive and finite")
+        _req(bool(np.all(np.diff(t) >= 0)), "time array must be in ascending order")
+        _req(bool(np.all(np.isfinite(nu) & (nu > 0))), "frequencies must be positive and finite")
+        if n_az is not None:
+            _req(isinstance(n_az, (int, np.integer)) and n_az >= 1, f"n_az must be an integer >= 1, got {n_az}")
+        return t, nu, scalar
+
+    def sky_image(self, t, nu, fov, npixel=64, n_az=None):
+        """Image of the afterglow on the sky at times t [s] and frequencies nu [Hz]: a SkyImage with fov [rad] full width
+        and npixel x npixel pixels centred on the burst (units.mas converts).  n_az: azimuthal parts per full circle
+        (default 4 npixel)."""
+        t, nu, scalar = self._sky_inputs(t, nu, n_az)
+        fov = float(fov)
+        _req(math.isfinite(fov) and fov > 0, f"fov must be positive and finite, got {fov}")
+        _req(isinstance(npixel, (int, np.integer)) and 1 <= npixel <= 4096, f"npixel must be an integer in [1, 4096], got {npixel}")
+        npixel = int(npixel)
+        image = np.empty((nu.size, t.size, npixel, npixel))
+        outside = np.empty((nu.size, t.size))
+        h, lock = get_context(self._device)
+        with lock:
+            _lib.check(_lib.load().vag_sky_image_batch(
+                h, C.byref(self.params), 1, t.ctypes.data_as(_dp), t.size, nu.ctypes.data_as(_dp), nu.size, fov, npixel,
+                0 if n_az is None else int(n_az), image.ctypes.data_as(_dp), outside.ctypes.data_as(_dp)))
+        if scalar:
+            image, outside = image[0], outside[0]
+        return SkyImage(image, outside, fov, t, nu[0] if scalar else nu)
+
+    def sky_moments(self, t, nu, n_az=None):
+        """Flux-weighted moments of the sky image before pixelation (SkyMoments: F, Xbar, Ybar, varX, varY, covXY) at times
+        t [s] and frequencies nu [Hz].  n_az: azimuthal parts per full circle (default 256)."""
+        t, nu, scalar = self._sky_inputs(t, nu, n_az)
+        out = np.empty((nu.size, t.size, 6))
+        h, lock = get_context(self._device)
+        with lock:
+            _lib.check(_lib.load().vag_sky_moments_batch(
+                h, C.byref(self.params), 1, t.ctypes.data_as(_dp), t.size, nu.ctypes.data_as(_dp), nu.size,
+                0 if n_az is None else int(n_az), out.ctypes.data_as(_dp)))
+        return SkyMoments(out[0] if scalar else out, t, nu[0] if scalar else nu)
 
     # -- Model.flux: pybind.cpp:430, pymodel.cpp:391-410 --
     def flux(self, t, nu_min, nu_max, num_nu):
