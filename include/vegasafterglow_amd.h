@@ -225,6 +225,13 @@ int vag_sky_image_batch(vag_ctx* ctx, const vag_model_params* params, int nb, co
 int vag_sky_moments_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
                           int n_az, double* moments);
 
+/* The same moments with the azimuthal integral done exactly (the n_az -> infinity limit of vag_sky_moments_batch): every row's
+ * term is spread uniformly over its phi bin and its first and second moments there are taken in closed form, then the rows are
+ * combined with Chan's pairwise update in a fixed order.  Same output layout and NaN rule as vag_sky_moments_batch; results are
+ * bitwise reproducible and do not depend on the rest of the batch.  Added after VAG_ABI_VERSION 13 (detect by symbol). */
+int vag_sky_centroid_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                           double* moments);
+
 /*
  * Model.flux_density(t[n] ascending, nu[n]) -> total[n]
  * (pybind/pybind.cpp:427, pybind/pymodel.cpp:373-389, src/core/observer.h:447-538),
@@ -302,6 +309,37 @@ int vag_flux_density_batch_dev(vag_ctx* ctx, const vag_model_params* d_params, i
  * scales the point-data model fluxes by exp(-A_V * ext_kernel[i]) (fitter.py:512-519). */
 #define VAG_P_A_V 1000
 
+/* Not Model fields either: the sky placement of the centroid groups of vag_loglike_sky_batch (position angle of the projected
+ * jet axis +X, measured east of north [rad]; the burst's offset east and north of the reference position [rad]).  Only the
+ * centroid entry points accept them. */
+#define VAG_P_SKY_PA 1001
+#define VAG_P_SKY_EAST0 1002
+#define VAG_P_SKY_NORTH0 1003
+
+/* One group of VLBI centroid positions at one frequency (added after VAG_ABI_VERSION 13, detect by symbol).  The model centroid
+ * (Xbar, Ybar) of vag_sky_centroid_batch(t, nu) is placed on the sky as
+ *   east = east0 + Xbar sin PA + Ybar cos PA,   north = north0 + Xbar cos PA - Ybar sin PA
+ * (+X points at position angle PA, +Y at PA + 90 degrees, both measured from north through east; every named profile has Ybar = 0)
+ * and adds sum_i weight_i [((east_i - east) / err_east_i)^2 + ((north_i - north) / err_north_i)^2] to the walker's chi^2. */
+typedef struct vag_centroid_obs {
+    double nu;                /* [Hz] */
+    int32_t n;                /* epochs */
+    int32_t pad;
+    const double* t;          /* [n] ascending [s]: the group's own request (own grid from its own times) */
+    const double* east;       /* [n] [rad] */
+    const double* north;      /* [n] [rad] */
+    const double* err_east;   /* [n] > 0 [rad] */
+    const double* err_north;  /* [n] > 0 [rad] */
+    const double* weight;     /* [n] */
+} vag_centroid_obs;
+
+typedef struct vag_sky_fit_spec {
+    int32_t n_groups;
+    int32_t pad;
+    const vag_centroid_obs* groups;  /* [n_groups] */
+    double pa_fixed, east0_fixed, north0_fixed; /* values of PA / east0 / north0 that are not free parameters [rad] */
+} vag_sky_fit_spec;
+
 /* One band-integrated data group of Fitter.add_flux (fitter.py:316-377): Model.flux(t, nu_min, nu_max, num_points) is
  * evaluated as its own request (own grid from its own time range), exactly like the reference's loop (fitter.py:524-531). */
 typedef struct vag_band_obs {
@@ -354,6 +392,16 @@ typedef struct vag_fit_spec {
 /* theta is [nb][ndim] (host); out is [nb] log-likelihoods (host).  Walkers whose
  * transformed parameters fail validation get -inf, like eval_one's except branch. */
 int vag_loglike_batch(vag_ctx* ctx, const vag_fit_spec* spec, const double* theta, int nb, int ndim, double* out);
+
+/* vag_loglike_batch(_dev) with VLBI centroid groups: after the flux and band passes, every group of sky (NULL or n_groups = 0: none)
+ * runs as its own request and adds its chi^2 term (vag_centroid_obs).  Free parameters may also take the slots VAG_P_SKY_*.  A
+ * walker whose F <= 0 or non-finite moments at a centroid epoch, or whose centroid pass fails (grid, ODE rows, SSC tables), scores
+ * -inf.  With no centroid groups the result is bit for bit vag_loglike_batch's.  theta / out: host (vag_loglike_sky_batch) or device
+ * (vag_loglike_sky_batch_dev) pointers.  Added after VAG_ABI_VERSION 13 (detect by symbol). */
+int vag_loglike_sky_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const double* theta, int nb, int ndim,
+                          double* out);
+int vag_loglike_sky_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const double* d_theta, int nb,
+                              int ndim, double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

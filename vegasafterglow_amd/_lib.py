@@ -51,6 +51,18 @@ class BandObs(C.Structure):
 
 
 P_A_V = 1000  # VAG_P_A_V
+# VAG_P_SKY_*: the sky placement of the centroid groups (vag_loglike_sky_batch), not Model fields either
+SKY_SLOTS = {"pa": 1001, "east0": 1002, "north0": 1003}
+
+
+class CentroidObs(C.Structure):  # vag_centroid_obs
+    _fields_ = [("nu", C.c_double), ("n", C.c_int32), ("pad", C.c_int32)] + \
+               [(n, C.POINTER(C.c_double)) for n in ("t", "east", "north", "err_east", "err_north", "weight")]
+
+
+class SkyFitSpec(C.Structure):  # vag_sky_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(CentroidObs)),
+                ("pa_fixed", C.c_double), ("east0_fixed", C.c_double), ("north0_fixed", C.c_double)]
 
 
 class FitSpec(C.Structure):
@@ -113,7 +125,7 @@ EXPORTS = [
     "vag_flux_density_components4_batch", "vag_flux_density_grid_batch_dev", "vag_flux_density_batch_dev", "vag_loglike_batch", "vag_loglike_batch_dev",
     "vag_last_model_costs_dev", "vag_loglike_shard_dev", "vag_loglike_shard_finish_dev", "vag_loglike_shard_begin_dev", "vag_loglike_shard_end_dev", "vag_loglike_shard_state_dev", "vag_ctx_profile", "vag_last_profile", "vag_details", "vag_details_rvs", "vag_details_radiation", "vag_details_regime", "vag_details_eat", "vag_profile_eval", "vag_last_stage_times", "vag_last_plan", "vag_ctx_count_work",
     "vag_ctx_coalesce", "vag_ctx_coalesce_stats", "vag_flux_density_grid_coalesced", "vag_flux_density_coalesced", "vag_flux_coalesced",
-    "vag_sky_image_batch", "vag_sky_moments_batch",
+    "vag_sky_image_batch", "vag_sky_moments_batch", "vag_sky_centroid_batch", "vag_loglike_sky_batch", "vag_loglike_sky_batch_dev",
 ]
 
 _lib = None
@@ -159,6 +171,9 @@ def load():
     lib.vag_flux_density_grid_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_sky_image_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp]
     lib.vag_sky_moments_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp]
+    lib.vag_sky_centroid_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp]
+    lib.vag_loglike_sky_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), _dp, C.c_int, C.c_int, _dp]
+    lib.vag_loglike_sky_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

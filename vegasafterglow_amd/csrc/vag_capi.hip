@@ -403,6 +403,7 @@ struct vag_ctx {
     // as its own output lattice; offsets handed out by vag_ic_plan_kernel, d_icused counts the doubles in use)
     DevBuf d_ichdr, d_icplan, d_icpool, d_icused, d_icslow /* records of the cells on the spectrum kernel's slow path */;
     DevBuf d_skyterms, d_skyimg, d_skymom;  // sky images / moments (vag_sky.h): term list, a chunk's images, moments + outside
+    DevBuf d_skycen, d_skycmom, d_skyfit;  // exact centroids (vag_sky.h): row-block partials, moments, centroid-fit pass data
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
     bool ic_all_cells = false;    // this request's SSC tables are built for every cell (the lazy selection was caught with a hole, see check_ic_status)
@@ -456,8 +457,10 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit;
-    uint64_t fit_hash = 0;
+    HostBuf h_fit, h_skyfit;
+    uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
+    size_t skyfit_doubles = 0;
+    bool skyfit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -690,8 +693,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_chunk.release();
     c->d_icwork.release();
     c->h_fit.release();
+    c->h_skyfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skycen, &c->d_skycmom, &c->d_skyfit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1999,6 +2003,87 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
     return VAG_OK;
 }
 
+// Exact sky moments of the whole batch (vag_sky_centroid_kernel); model stages already run, d_lg2t / d_lg2nu prepared.  The passes
+// are sky_request's, each writing its row-block partials into its own slice; the combine reads the slices in that fixed order.  The
+// time axis is cut into chunks whose partials stay within 256 MB (VAG_SKY_CHUNK_T: a test's chunk length).  d_moments
+// [nb][nnu][nt][6] on the device.
+int centroid_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, int nnu, double* d_moments) {
+    hipStream_t st = c->stream;
+    struct SkyPass {
+        int e, pass;
+    };
+    std::vector<SkyPass> passes;
+    const int n_em = (c->batch_flags & VAG_FLAG_RVS) ? 2 : 1;
+    for (int e = 0; e < n_em; ++e) {
+        passes.push_back({e, 0});
+        if (c->batch_flags & (e == 0 ? VAG_FLAG_SSC : VAG_FLAG_RVS_SSC)) passes.push_back({e, 1});
+    }
+    const int n_pass = (int)passes.size();
+    const int n_blk = std::max(1, (c->max_pairs + SKYC_ROWS - 1) / SKYC_ROWS);
+    const size_t per_t = sizeof(double) * (size_t)n_pass * nb * nnu * n_blk * 6;
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>(nt, ((size_t)256 << 20) / per_t));
+    if (const char* e = vag_hook("VAG_SKY_CHUNK_T")) chunk = std::max(1, std::min(nt, std::atoi(e)));
+    if (c->d_skycen.ensure(per_t * chunk)) return VAG_E_HIP;
+    const bool spreading = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
+    int rc = VAG_OK;
+    for (int t0 = 0; t0 < nt && rc == VAG_OK; t0 += chunk) {
+        const int n = std::min(chunk, nt - t0);
+        for (int q = 0; q < n_pass && rc == VAG_OK; ++q) {
+            select_emitter(c, passes[q].e, d_params);
+            SkyCenArgs a{};
+            a.params = c->cur_params;
+            a.meta = c->d_meta.as<VagGridMeta>();
+            a.geo_th = c->d_geo_th.as<double>();
+            a.geo_ph = c->d_geo_ph.as<double>();
+            a.phi = c->d_phi.as<double>();
+            a.g_rep_of = c->d_rep_of.as<int>();
+            a.cell_off = c->d_cell_off.as<long long>();
+            a.cellpar = c->d_cellpar.as<double>();
+            a.cellq = c->d_cellq.as<double>();
+            a.cellgeo = c->d_cellgeo.as<double>();
+            a.sp_table = c->d_sptab.as<double>();
+            a.lg2_t_obs = c->d_lg2t.as<double>() + t0;
+            a.lg2_nu_obs = c->d_lg2nu.as<double>();
+            a.nt = n;
+            a.nnu = nnu;
+            a.n_blk = n_blk;
+            a.partial = c->d_skycen.as<double>() + (size_t)q * nb * nnu * n * n_blk * 6;
+            const int mode = passes[q].pass == 1 ? FLUX_SSC : (c->cur_ssc ? FLUX_SYN_IC : FLUX_SYN);
+            auto launch = [&](auto kernel) -> int {
+                hipLaunchKernelGGL(kernel, dim3((n_blk + SKYC_WAVES - 1) / SKYC_WAVES, nb), dim3(SKYC_ROWS * SKYC_WAVES), 0, st, a);
+                HIPCHK(hipGetLastError());
+                return VAG_OK;
+            };
+            auto rows = [&]() -> int {
+                StageScope ps(c, mode == FLUX_SSC ? PS_SSC_FLUX : PS_SYNC_FLUX);
+                a.ichdr = c->d_ichdr.as<double>();  // (behind the table build, which may reallocate them)
+                a.icpool = c->d_icpool.as<double>();
+                a.ic_status = c->d_icstatus.as<int>();
+                if (mode == FLUX_SSC)
+                    return spreading ? launch(vag_sky_centroid_kernel<FLUX_SSC, true>) : launch(vag_sky_centroid_kernel<FLUX_SSC, false>);
+                if (mode == FLUX_SYN_IC)
+                    return spreading ? launch(vag_sky_centroid_kernel<FLUX_SYN_IC, true>) : launch(vag_sky_centroid_kernel<FLUX_SYN_IC, false>);
+                return spreading ? launch(vag_sky_centroid_kernel<FLUX_SYN, true>) : launch(vag_sky_centroid_kernel<FLUX_SYN, false>);
+            };
+            if (mode == FLUX_SSC) {  // the tables clamped to the requested frequencies exactly as a grid call clamps them
+                rc = ssc_attempts(c, nb, [&](bool rebuild) {
+                    const int rb = build_ssc_tables(c, c->cur_params, nb, c->d_lg2nu.as<double>(), nnu, rebuild);
+                    return rb ? rb : rows();
+                });
+            } else {
+                rc = rows();
+            }
+        }
+        select_emitter(c, 0, d_params);
+        if (rc) break;
+        const int G = nb * nnu * n;
+        hipLaunchKernelGGL(vag_sky_centroid_combine, dim3((G + 255) / 256), dim3(256), 0, st, c->d_meta.as<VagGridMeta>(),
+                           c->d_skycen.as<double>(), n_pass, nb, nnu, n, n_blk, nt, t0, d_moments);
+        HIPCHK(hipGetLastError());
+    }
+    return rc;
+}
+
 // Fixed-order sum of the workgroup partials of a series request.  A workgroup is 64 points x 4 block groups: group g adds the
 // partial blocks b = g, g + 4, ... with four loads in flight, then the four group sums are added in order -- the same
 // result run to run, and the walk over up to a few hundred blocks is no longer one dependent load after another
@@ -2783,6 +2868,45 @@ int vag_sky_moments_batch(vag_ctx* c, const vag_model_params* params, int nb, co
     return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, 0.0, 1, nullptr, nullptr, moments);
 }
 
+// Model.sky_moments(exact=True) over a batch: the n_az -> infinity limit of sky_impl's moments (vag_sky_centroid_kernel)
+static int centroid_impl(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                         double* moments) {
+    int rc = check_host_inputs(params, nb, t, nt);
+    if (rc) return rc;
+    if (!uniform_flags(params, nb))
+        return run_flag_groups(params, nb, {{moments, (size_t)nnu * nt * 6}},
+                               [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
+                                   return centroid_impl(c, gp, ng, t, nt, nu, nnu, o[0]);
+                               });
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n_out = (size_t)nb * nnu * nt * 6;
+    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
+    if (c->d_t.ensure(sizeof(double) * nt)) return VAG_E_HIP;
+    if (c->d_nu.ensure(sizeof(double) * nnu)) return VAG_E_HIP;
+    if (c->d_skycmom.ensure(sizeof(double) * n_out)) return VAG_E_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * nt, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_nu.p, nu, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream));
+    rc = prep_times(c, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu);
+    if (rc) return rc;
+    rc = run_model_stages(c, c->d_params.as<vag_model_params>(), nb, false);
+    if (rc) return rc;
+    rc = centroid_request(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, c->d_skycmom.as<double>());
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(moments, c->d_skycmom.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return check_status(c, nb);
+}
+
+int vag_sky_centroid_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                           double* moments) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!nu || !moments) return set_err(VAG_E_INVALID, "null frequency or moments array");
+    if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
+    return centroid_impl(c, params, nb, t, nt, nu, nnu, moments);
+}
+
 int vag_flux_density_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, const double* nu, int n,
                            double* out) {
     ApiLock api_lock(c);
@@ -3038,13 +3162,14 @@ static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
     return h;
 }
 
-static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim) {
+static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false) {
     if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
     const int n = spec->n_data;
-    if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0)) return set_err(VAG_E_INVALID, "fit spec has no data");
+    if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky)) return set_err(VAG_E_INVALID, "fit spec has no data");
     for (int d = 0; d < ndim; ++d) {
         const int s = spec->slot[d];
         if (s == VAG_P_A_V) continue;
+        if (sky && s >= VAG_P_SKY_PA && s <= VAG_P_SKY_NORTH0) continue;
         if (s < 0 || (s >= VAG_P_COUNT && (s < VAG_P_RVS_EPS_E || s > VAG_P_MAG_Q))) return set_err(VAG_E_INVALID, "bad parameter slot");
     }
     if (spec->use_priors)
@@ -3180,7 +3305,7 @@ vag_fit_front_kernel(vag_model_params base, const double* __restrict__ theta, in
         const double val = is_log[d] ? pow(10.0, v) : v;
         if (slot[d] == VAG_P_A_V)
             av = val;  // not a Model field: scales the point-data fluxes (fitter.py:512-519)
-        else
+        else if (slot[d] < VAG_P_A_V)  // (VAG_P_SKY_*: read by vag_fit_sky_back_kernel)
             f[slot[d]] = val;
     }
     if (!inside) {  // never evaluated by the reference either: an invalid parameter set stops at the grid stage with no work
@@ -3253,7 +3378,124 @@ vag_fit_back_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const 
     }
 }
 
-static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec) {
+// ---- centroid groups (vag_loglike_sky_batch): their data in one device buffer, uploaded like the fit spec when its hash changes.
+//      Layout in doubles, per group: [nu | t | east | north | err_east | err_north | weight] (1 + 6 n). ----
+static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
+    if (sky->n_groups < 0 || (sky->n_groups > 0 && !sky->groups)) return set_err(VAG_E_INVALID, "bad centroid group list");
+    for (double v : {sky->pa_fixed, sky->east0_fixed, sky->north0_fixed})
+        if (!std::isfinite(v)) return set_err(VAG_E_INVALID, "fixed sky placement values must be finite");
+    uint64_t h = 1469598103934665603ull;
+    h = fnv1a(h, &sky->n_groups, sizeof sky->n_groups);
+    size_t total = 0;
+    for (int g = 0; g < sky->n_groups; ++g) {
+        const vag_centroid_obs& o = sky->groups[g];
+        if (o.n <= 0) return set_err(VAG_E_INVALID, "centroid group %d has no observations", g);
+        if (!o.t || !o.east || !o.north || !o.err_east || !o.err_north || !o.weight) return set_err(VAG_E_INVALID, "centroid group %d: null array", g);
+        h = fnv1a(h, &o.nu, sizeof o.nu);
+        h = fnv1a(h, &o.n, sizeof o.n);
+        for (const double* arr : {o.t, o.east, o.north, o.err_east, o.err_north, o.weight}) h = fnv1a(h, arr, sizeof(double) * o.n);
+        total += 1 + 6 * (size_t)o.n;
+    }
+    if (c->skyfit_hash_valid && c->skyfit_hash == h && c->skyfit_doubles == total) return VAG_OK;  // resident already
+    for (int g = 0; g < sky->n_groups; ++g) {
+        const vag_centroid_obs& o = sky->groups[g];
+        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "centroid group %d: frequency must be positive", g);
+        for (int i = 0; i < o.n; ++i) {
+            if (!(o.t[i] > 0) || !std::isfinite(o.t[i]) || (i > 0 && o.t[i] < o.t[i - 1]))
+                return set_err(VAG_E_INVALID, "centroid group %d: times must be positive and ascending", g);
+            if (!std::isfinite(o.east[i]) || !std::isfinite(o.north[i]) || !std::isfinite(o.weight[i]))
+                return set_err(VAG_E_INVALID, "centroid group %d: positions and weights must be finite", g);
+            if (!(o.err_east[i] > 0) || !(o.err_north[i] > 0) || !std::isfinite(o.err_east[i]) || !std::isfinite(o.err_north[i]))
+                return set_err(VAG_E_INVALID, "centroid group %d: errors must be positive and finite", g);
+        }
+    }
+    c->skyfit_hash_valid = false;
+    if (total == 0) return VAG_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_skyfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
+    if (c->d_skyfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
+    double* hp = c->h_skyfit.as<double>();
+    size_t off = 0;
+    for (int g = 0; g < sky->n_groups; ++g) {
+        const vag_centroid_obs& o = sky->groups[g];
+        hp[off++] = o.nu;
+        for (const double* arr : {o.t, o.east, o.north, o.err_east, o.err_north, o.weight}) {
+            std::memcpy(hp + off, arr, sizeof(double) * o.n);
+            off += o.n;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(c->d_skyfit.p, hp, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
+    c->skyfit_hash = h;
+    c->skyfit_doubles = total;
+    c->skyfit_hash_valid = true;
+    return VAG_OK;
+}
+
+// The back of one centroid pass, one wavefront per walker (vag_fit_back_kernel's protocol): the walker's sky placement (free
+// parameters with slots VAG_P_SKY_*, else the fixed values), the group's chi^2 term, and validity -- F > 0 and finite moments at
+// every epoch, grid, ODE rows and SSC tables of this pass.
+__global__ void __launch_bounds__(64)
+vag_fit_sky_back_kernel(const double* __restrict__ mom /* [nb][n][6] */, int n, const double* __restrict__ obs /* [t|e|n|ee|en|w] */,
+                        const double* __restrict__ theta, int ndim, const double* __restrict__ prior, double pa_fixed, double east0_fixed,
+                        double north0_fixed, const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status,
+                        const int* __restrict__ row_off, const int* __restrict__ ic_status, double* __restrict__ chi2, int* __restrict__ valid,
+                        const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out, int* __restrict__ fitstat,
+                        const int* __restrict__ order) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    const int walker = order ? order[m] : m;
+    const int* slot = reinterpret_cast<const int*>(prior + 64);
+    const int* is_log = slot + 16;
+    double pa = pa_fixed, e0 = east0_fixed, n0 = north0_fixed;
+    for (int d = 0; d < ndim; ++d) {
+        const int sl = slot[d];
+        if (sl < VAG_P_SKY_PA || sl > VAG_P_SKY_NORTH0) continue;
+        const double v = theta[(size_t)walker * ndim + d];
+        const double val = is_log[d] ? pow(10.0, v) : v;
+        if (sl == VAG_P_SKY_PA)
+            pa = val;
+        else if (sl == VAG_P_SKY_EAST0)
+            e0 = val;
+        else
+            n0 = val;
+    }
+    double sp, cp;
+    sincos(pa, &sp, &cp);
+    const double *e_obs = obs + n, *n_obs = obs + 2 * (size_t)n, *e_err = obs + 3 * (size_t)n, *n_err = obs + 4 * (size_t)n,
+                 *w = obs + 5 * (size_t)n;
+    const bool grid_ok = meta[m].status == 0;
+    double s = 0;
+    bool bad = false;
+    if (grid_ok)
+        for (int i = lane; i < n; i += 64) {
+            const double* mo = mom + ((size_t)m * n + i) * 6;
+            const double F = mo[0], X = mo[1], Y = mo[2];
+            bad = bad || !(F > 0) || !isfinite(F) || !isfinite(X) || !isfinite(Y);
+            const double east = e0 + (X * sp + Y * cp), north = n0 + (X * cp - Y * sp);
+            const double qe = (e_obs[i] - east) / e_err[i], qn = (n_obs[i] - north) / n_err[i];
+            s += w[i] * (qe * qe + qn * qn);
+        }
+    s = vag::wave_sum(s);
+    if (grid_ok)
+        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad = bad || row_status[r] == 1;
+    const bool any_bad = __any(bad);
+    if (lane == 0) {
+        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
+        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
+        const double acc = first ? s : chi2[m] + s;
+        valid[m] = ok;
+        chi2[m] = acc;
+        if (ic_bad) atomicAdd(fitstat + 1, 1);
+        if (last) {
+            const double lp = ln_prior[m];
+            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
+            out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
+            if (!fin) atomicAdd(fitstat, 1);
+        }
+    }
+}
+
+static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec,
+                        const vag_sky_fit_spec* sky = nullptr) {
     int rc = VAG_OK;
     const int n = spec->n_data;
     hipStream_t st = c->stream;
@@ -3287,7 +3529,8 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         order_made = true;
         return nxt.as<int>();
     };
-    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands;
+    const int n_groups = sky ? sky->n_groups : 0;
+    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // the SSC tables of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
     auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext) -> int {
@@ -3337,6 +3580,30 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         rc = band_request_dev(c, d_params, nb, db, bd.n, bd.nu_min, bd.nu_max, bd.num_points, c->d_series_flux.as<double>(), nullptr);
         if (rc == VAG_OK) rc = back(c->d_series_flux.as<double>(), bd.n, db + bd.n, db + 2 * (size_t)bd.n, db + 3 * (size_t)bd.n, nullptr);
     }
+    size_t soff = 0;
+    for (int g = 0; g < n_groups && rc == VAG_OK; ++g) {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
+        const vag_centroid_obs& o = sky->groups[g];
+        const double* ds = c->d_skyfit.as<double>() + soff;  // [nu | t | east | north | err_east | err_north | weight]
+        soff += 1 + 6 * (size_t)o.n;
+        if (c->d_skycmom.ensure(sizeof(double) * (size_t)nb * o.n * 6)) return VAG_E_HIP;
+        rc = prep_times(c, ds + 1, o.n, ds, 1);
+        c->order_next = d_order != nullptr;
+        c->last_order = d_order;
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
+        if (rc == VAG_OK) rc = centroid_request(c, d_params, nb, o.n, 1, c->d_skycmom.as<double>());
+        if (rc == VAG_OK) {
+            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
+            hipLaunchKernelGGL(vag_fit_sky_back_kernel, dim3(nb), dim3(64), 0, st, c->d_skycmom.as<double>(), o.n, ds + 1, d_theta, ndim,
+                               d_prior, sky->pa_fixed, sky->east0_fixed, sky->north0_fixed, c->d_meta.as<VagGridMeta>(),
+                               c->d_row_status.as<int>(), c->d_row_off.as<int>(), (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr,
+                               d_chi2, c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out,
+                               c->d_fitstat.as<int>(), d_order);
+            HIPCHK(hipGetLastError());
+            ++pass;
+            n_cap = std::max(n_cap, c->plan.n_models_capacity);
+            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+        }
+    }
     c->ic_soft_fail = false;
     c->plan.n_models_capacity = n_cap;
     c->plan.n_models_invalid = n_inv;
@@ -3361,6 +3628,26 @@ int vag_loglike_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const double* d_
     if (rc) return rc;
     rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work);
     if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false);
+    return rc;
+}
+
+int vag_loglike_sky_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const double* d_theta, int nb, int ndim,
+                              double* d_out) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    if (sky && sky->n_groups == 0) sky = nullptr;  // exactly vag_loglike_batch_dev
+    HIPCHK(hipSetDevice(c->device));
+    int rc = upload_fit_spec(c, spec, ndim, sky != nullptr);
+    if (rc) return rc;
+    if (sky) {
+        rc = upload_sky_spec(c, sky);
+        if (rc) return rc;
+    }
+    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky);
+    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky);
     return rc;
 }
 
@@ -3632,6 +3919,25 @@ int vag_loglike_batch(vag_ctx* c, const vag_fit_spec* spec, const double* theta,
     double* d_out = d_theta + (size_t)nb * ndim;
     HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
     int rc = vag_loglike_batch_dev(c, spec, d_theta, nb, ndim, d_out);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)collect_times(c);
+    return VAG_OK;
+}
+
+int vag_loglike_sky_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const double* theta, int nb, int ndim,
+                          double* out) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
+    double* d_theta = c->d_theta_in.as<double>();
+    double* d_out = d_theta + (size_t)nb * ndim;
+    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
+    int rc = vag_loglike_sky_batch_dev(c, spec, sky, d_theta, nb, ndim, d_out);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

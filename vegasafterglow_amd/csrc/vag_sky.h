@@ -12,6 +12,7 @@
 //                           the weight that falls outside the image
 // DESIGN §4k.
 #pragma once
+#include "vag_sky_moments.h"
 
 namespace vag {
 
@@ -166,12 +167,7 @@ __global__ void __launch_bounds__(64 * SKY_WAVES) vag_sky_terms_kernel(SkyArgs a
     }
 }
 
-// The azimuthal bin of a row's phi node (the bin whose width enters its solid angle) and its number of parts.
-struct SkyBin {
-    double left, width;
-    int S;
-    bool mirrored;
-};
+// The azimuthal bin of a row's phi node (SkyBin, vag_sky_moments.h).
 VAG_DEV SkyBin sky_bin(const VagGridMeta& M, const double* phi, int p, int n_az) {
     SkyBin b;
     const int npe = M.n_phi_eff, i = p % npe, last = npe - 1;
@@ -350,6 +346,211 @@ __global__ void __launch_bounds__(64) vag_sky_moments_kernel(SkyImgArgs a) {
         mo[4] = ok ? Syy / F : NAN;
         mo[5] = ok ? Sxy / F : NAN;
     }
+}
+
+// ---- exact centroids (vag_sky_centroid_batch and the likelihood's centroid groups): no term list, no azimuthal parts ----
+//   vag_sky_centroid_kernel   one (theta, phi) row per lane, 64 rows per wavefront: the row's EAT logs, bracket and boundary spectra
+//                             with vag_sky_terms_kernel's expressions, the term (w, a, b, c), its exact moments over the row's phi bin
+//                             (sky_term_moments), and a fixed butterfly of Chan updates over the wavefront -> one partial per
+//                             (pass, model, (nu, t) slot, block of 64 rows)
+//   vag_sky_centroid_combine  one thread per (model, slot): the partials in pass order, then block order -> F, centroid, moments
+// Both orders are fixed and a model's result depends on its own rows only: bitwise reproducible and independent of the batch.
+
+constexpr int SKYC_WAVES = 4;  // blocks of 64 rows (wavefronts) per workgroup
+constexpr int SKYC_ROWS = 64;
+
+struct SkyCenArgs {
+    const vag_model_params* params;  // of the selected emitter
+    const VagGridMeta* meta;
+    const double* geo_th;
+    const double* geo_ph;
+    const double* phi;  // [nb][ph_stride]
+    const int* g_rep_of;
+    const long long* cell_off;
+    const double* cellpar;
+    const double* cellq;
+    const double* cellgeo;
+    const double* ichdr;
+    const double* icpool;
+    int* ic_status;
+    const double* sp_table;
+    const double* lg2_t_obs;   // [nt] of this chunk
+    const double* lg2_nu_obs;  // [nnu]
+    int nt, nnu, n_blk;        // n_blk: blocks of 64 rows per model in the partial layout (>= every model's)
+    double* partial;           // this pass's [nb][nnu * nt][n_blk][6]
+};
+
+VAG_DEV SkyMom sky_mom_shfl_xor(const SkyMom& v, int off) {
+    SkyMom r;
+    r.w = __shfl_xor(v.w, off, 64);
+    r.x = __shfl_xor(v.x, off, 64);
+    r.y = __shfl_xor(v.y, off, 64);
+    r.mxx = __shfl_xor(v.mxx, off, 64);
+    r.myy = __shfl_xor(v.myy, off, 64);
+    r.mxy = __shfl_xor(v.mxy, off, 64);
+    return r;
+}
+
+template <int MODE, bool SPREAD>
+__global__ void __launch_bounds__(SKYC_ROWS * SKYC_WAVES) vag_sky_centroid_kernel(SkyCenArgs a) {
+    __shared__ double s_sp[SP_LDS_DOUBLES];
+    for (int i = threadIdx.x; i < SP_LDS_DOUBLES; i += blockDim.x) s_sp[i] = a.sp_table[i];
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int m = blockIdx.y, vb = blockIdx.x * SKYC_WAVES + wave;
+    const VagGridMeta* Mp = a.meta + m;
+    const int n_pairs = Mp->status == 0 ? Mp->n_theta * Mp->n_phi_eff : 0;
+    if (vb * SKYC_ROWS >= n_pairs) return;  // (the combine reads the blocks of live rows only)
+    const LdsTab sp_tab = lds_tab(s_sp), lg_tab = lds_tab(s_sp + SP_TABLE_DOUBLES);
+    const int nt = a.nt, slots = nt * a.nnu;
+    const bool live = vb * SKYC_ROWS + lane < n_pairs;
+    const int p = live ? vb * SKYC_ROWS + lane : n_pairs - 1;
+    const int n_phi_eff = Mp->n_phi_eff, j = p / n_phi_eff, i = p - j * n_phi_eff;
+    const int K = Mp->n_t, ts = Mp->th_stride, ps = Mp->ph_stride;
+    const double* gth = a.geo_th + (size_t)m * 3 * ts;
+    const double* gph = a.geo_ph + (size_t)m * 2 * ps;
+    const int rep = a.g_rep_of[(size_t)m * ts + j] + i * Mp->rep_phi_stride;
+    const long long cell0 = a.cell_off[m] + (long long)rep * K;
+    const double* row = a.cellpar + cell0 * VAG_NPAR;  // [VAG_NPAR][K]
+    const double* geo = SPREAD ? a.cellgeo + cell0 * 3 : nullptr;
+    const vag_model_params* Pp = a.params + m;
+    const double one_plus_z = 1 + Pp->z;
+    const double cos_obs = Mp->cos_obs, sin_obs = Mp->sin_obs;
+    const double cos_th = gth[j], sin_th = gth[ts + j], cph = gph[i];
+    const double cos_v_row = fma(cos_th, cos_obs, (sin_th * cph) * sin_obs);  // RowGeo::cos_view
+    const double t_coeff = (1 - cos_v_row) * (one_plus_z / C_C);
+    const double lg2_dOmega = gth[2 * ts + j] + gph[ps + i];
+    // node k of the row: log2 t_obs, log2 Doppler, log2 (dOmega r^2 D^3) -- vag_sky_terms_kernel's staged values, expression for expression
+    auto node_t = [&](int k) -> double {
+        const double u = row[VP_U * K + k], r = row[VP_R * K + k], teng = row[VP_TENG * K + k];
+        if constexpr (SPREAD) {
+            const double cos_v = geo[K + k] * cph * sin_obs + geo[k] * cos_obs;
+            return log2_tab((teng + (1 - cos_v) * r / C_C) * one_plus_z, lg_tab);
+        } else {
+            (void)u;
+            return log2_tab(fma(t_coeff, r, teng * one_plus_z), lg_tab);
+        }
+    };
+    auto node_dop_geom = [&](int k, double& dop, double& geom) {
+        const double G_ = row[VP_GAMMA * K + k], u = row[VP_U * K + k], lr2 = row[VP_LG2_R2 * K + k];
+        if constexpr (SPREAD) {
+            const double cos_v = geo[K + k] * cph * sin_obs + geo[k] * cos_obs;
+            dop = -log2_tab(G_ - u * cos_v, lg_tab);
+            geom = ((geo[2 * K + k] + gph[ps + i]) + lr2) + 3.0 * dop;
+        } else {
+            dop = -log2_tab(fma(-u, cos_v_row, G_), lg_tab);
+            geom = (lg2_dOmega + lr2) + 3.0 * dop;
+        }
+    };
+    SpecConst sc;
+    sc.init(Pp->p);
+    int breach = 0;
+    auto boundary = [&](int k, double x) -> double {  // log2 I'(x) without geom: the grid flux pass's evaluator for MODE
+        if constexpr (MODE == FLUX_SYN) {
+            SpecRegs regs;
+#pragma unroll
+            for (int w = 0; w < 14; ++w) regs.v[w] = row[w * K + k];
+            return log2_I_nu_fast(regs, 1, sc, x, sp_tab);
+        } else if constexpr (MODE == FLUX_SYN_IC) {
+            double b0, b1;
+            log2_I_nu_ic_pair(row + k, K, a.cellq + cell0 * FLUX_NQ + k, K, sc, x, x, sp_tab, b0, b1);
+            return b0;
+        } else {
+            const double* hp = a.ichdr + (size_t)(cell0 + k) * FLUX_IC_HDR;
+            const double* tab = a.icpool + (unsigned long long)hp[5];
+            return ic_table_eval_hdr(tab, hp[0], hp[1], hp[2], hp[3], hp[4], x, &breach);
+        }
+    };
+    const double row_t0 = node_t(0), row_tN = node_t(K - 1);
+    const double d_L = Pp->lumi_dist * U_CM;
+    const double norm = one_plus_z / (d_L * d_L);
+    const double inv_DA = (one_plus_z * one_plus_z) / d_L;
+    const SkyBin bin = sky_bin(*Mp, a.phi + (size_t)m * ps, p, 1);
+    double* out = a.partial + ((size_t)m * slots * a.n_blk + vb) * 6;
+#pragma unroll 1
+    for (int s = 0; s < slots; ++s) {
+        const int l = s / nt, idx = s - l * nt;
+        const double tq = a.lg2_t_obs[idx];
+        SkyMom r{0, 0, 0, 0, 0, 0};
+        if (live && tq >= row_t0 && tq < row_tN) {
+            int lo = 0, hi = K - 1;  // t[lo] <= tq < t[hi]
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (node_t(mid) <= tq)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            const double t_lo = node_t(lo);
+            const double f = (tq - t_lo) * (1.0 / (node_t(lo + 1) - t_lo));
+            const double nu = a.lg2_nu_obs[l] + Mp->lg2_1pz;
+            double dop_lo, geom_lo, dop_hi, geom_hi;
+            node_dop_geom(lo, dop_lo, geom_lo);
+            node_dop_geom(lo + 1, dop_hi, geom_hi);
+            const double b_lo = boundary(lo, nu - dop_lo) + geom_lo, b_hi = boundary(lo + 1, nu - dop_hi) + geom_hi;
+            const double x = fma(b_hi - b_lo, f, b_lo);
+            const double wgt = (exp2_or_zero(x) * norm) / U_FLUX_DEN_CGS;
+            if (wgt != 0) {
+                const double lr_lo = log2(row[VP_R * K + lo]), lr_hi = log2(row[VP_R * K + lo + 1]);
+                const double rr = exp2(lr_lo + f * (lr_hi - lr_lo)) * inv_DA;
+                double ct = cos_th, st = sin_th;
+                if constexpr (SPREAD) {
+                    const double th_lo = atan2(geo[K + lo], geo[lo]), th_hi = atan2(geo[K + lo + 1], geo[lo + 1]);
+                    const double th = th_lo + f * (th_hi - th_lo);
+                    ct = cos(th);
+                    st = sin(th);
+                }
+                r = sky_term_moments(wgt, rr * ct * sin_obs, rr * st * cos_obs, rr * st, bin);
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {  // the lower lane's set first: both lanes of a pair hold the same result
+            const SkyMom q = sky_mom_shfl_xor(r, off);
+            r = (lane & off) ? sky_mom_merge(q, r) : sky_mom_merge(r, q);
+        }
+        if (lane == 0) {
+            double* o = out + (size_t)s * a.n_blk * 6;
+            o[0] = r.w;
+            o[1] = r.x;
+            o[2] = r.y;
+            o[3] = r.mxx;
+            o[4] = r.myy;
+            o[5] = r.mxy;
+        }
+    }
+    if constexpr (MODE == FLUX_SSC) {
+        if (breach) atomicOr(a.ic_status + m, ic_breach_status(breach));
+    }
+}
+
+// One thread per (model, slot) of the chunk: moments [nb][nnu][nt_all][6] (F, Xbar, Ybar, varX, varY, covXY; F <= 0 or NaN: NaN shape).
+__global__ void __launch_bounds__(256) vag_sky_centroid_combine(const VagGridMeta* __restrict__ meta, const double* __restrict__ partial,
+                                                                int n_pass, int nb, int nnu, int nt, int n_blk, int nt_all, int t0,
+                                                                double* __restrict__ moments) {
+    const int slots = nnu * nt;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nb * slots) return;
+    const int m = g / slots, s = g - m * slots, l = s / nt, idx = s - l * nt;
+    const VagGridMeta M = meta[m];
+    const int n_pairs = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    const int nblk_m = (n_pairs + SKYC_ROWS - 1) / SKYC_ROWS;
+    const size_t pass_stride = (size_t)nb * slots * n_blk * 6;
+    SkyMom r{0, 0, 0, 0, 0, 0};
+    for (int q = 0; q < n_pass; ++q) {
+        const double* P = partial + q * pass_stride + ((size_t)g * n_blk) * 6;
+        for (int b = 0; b < nblk_m; ++b) {
+            const double* o = P + (size_t)b * 6;
+            r = sky_mom_merge(r, SkyMom{o[0], o[1], o[2], o[3], o[4], o[5]});
+        }
+    }
+    double* mo = moments + (((size_t)m * nnu + l) * nt_all + t0 + idx) * 6;
+    const bool ok = r.w > 0;
+    mo[0] = r.w;
+    mo[1] = ok ? r.x : NAN;
+    mo[2] = ok ? r.y : NAN;
+    mo[3] = ok ? r.mxx / r.w : NAN;
+    mo[4] = ok ? r.myy / r.w : NAN;
+    mo[5] = ok ? r.mxy / r.w : NAN;
 }
 
 }  // namespace vag

@@ -15,6 +15,10 @@ import torch
 import torch.distributed as dist
 
 
+_NO_CENTROIDS = ("sharded likelihood calls do not support centroid data (Fitter.add_centroid): evaluate on one device "
+                 "(Fitter.device_evaluator / log_prob_batch)")
+
+
 def shard_range(n, rank, world):
     """Contiguous block [lo, hi) of n units owned by `rank` (sizes differ by at most one)."""
     base, rem = divmod(n, world)
@@ -81,6 +85,8 @@ class WalkerSharder:
     """
 
     def __init__(self, eval_dev, group=None, device=None):
+        if getattr(eval_dev, "has_centroids", False):
+            raise NotImplementedError(_NO_CENTROIDS)
         self.eval_dev, self.group = eval_dev, group
         self.device = device if device is not None else _default_device(group)
         self.native = getattr(eval_dev, "native", None)
@@ -175,6 +181,8 @@ def sharded_loglike(samples, local_eval, group=None, device=None):
     same `samples` and gets the full [nb] vector back.  Kept for callers that hold numpy arrays; the device-resident,
     cost-balanced path is ``WalkerSharder``.
     """
+    if getattr(getattr(local_eval, "__self__", None), "has_centroids", False):
+        raise NotImplementedError(_NO_CENTROIDS)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     nb = samples.shape[0]
     if not (dist.is_available() and dist.is_initialized()):

@@ -166,6 +166,7 @@ class Fitter:
         self.device = device
         self._point_t, self._point_nu, self._point_flux, self._point_err, self._point_weights = [], [], [], [], []
         self._band_obs = []
+        self._centroid_obs = []  # VLBI centroid groups (add_centroid): one vag_centroid_obs each
         self._ext_kernel = None
         self._ext_kernels = {}  # z -> 0.4 ln10 k(lambda_rest) over the consolidated point data
         self._ext_z = float(z)
@@ -250,13 +251,49 @@ class Fitter:
                                    ln_err=np.ascontiguousarray(err[order] / flux[order]),
                                    weights=np.ascontiguousarray(w[order])))
 
+    def add_centroid(self, nu, t, east, north, err_east, err_north, weights=None):
+        """VLBI centroid positions at one frequency nu [Hz]: offsets east / north of a reference position and their errors [rad]
+        (units.mas converts) at ascending times t [s].  The group is its own request: the model centroid at (t_i, nu) is
+        Model.sky_moments(t, nu, exact=True) placed on the sky by the parameters "pa" (position angle of the jet, east of
+        north), "east0" and "north0" (free or fixed; 0 when not given), and adds
+        sum_i w_i [((east_i - east) / err_east_i)^2 + ((north_i - north) / err_north_i)^2] to chi^2."""
+        nu = float(np.asarray(nu, dtype=np.float64)) if np.ndim(nu) == 0 else None
+        if nu is None or not np.isfinite(nu) or nu <= 0:
+            raise ValueError("add_centroid: nu must be one finite frequency > 0")
+        arrs = [np.asarray(a, dtype=np.float64) for a in (t, east, north, err_east, err_north)]
+        t, east, north, err_east, err_north = arrs
+        if t.ndim != 1 or t.size == 0:
+            raise ValueError("add_centroid: t must be a non-empty 1-D array")
+        if any(a.shape != t.shape for a in arrs):
+            raise ValueError("add_centroid: t, east, north, err_east, err_north must have the same shape; got "
+                             f"{[a.shape for a in arrs]}")
+        if not all(np.isfinite(a).all() for a in arrs):
+            raise ValueError("add_centroid: t, positions and errors must be finite")
+        if (t <= 0).any() or (np.diff(t) < 0).any():
+            raise ValueError("add_centroid: times must be > 0 and ascending")
+        if (err_east <= 0).any() or (err_north <= 0).any():
+            raise ValueError("add_centroid: err_east and err_north must be > 0 at every epoch")
+        if weights is None:
+            w = np.ones_like(t)
+        else:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape != t.shape or not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError("add_centroid: weights must have the shape of t and be finite and >= 0")
+        self._centroid_obs.append(dict(nu=nu, t=np.ascontiguousarray(t), east=np.ascontiguousarray(east),
+                                       north=np.ascontiguousarray(north), err_east=np.ascontiguousarray(err_east),
+                                       err_north=np.ascontiguousarray(err_north), weights=np.ascontiguousarray(w)))
+
+    @property
+    def has_centroids(self):
+        return bool(self._centroid_obs)
+
     # fitter.py:407-451
     def _consolidate_data(self):
         if self._all_t is not None:
             return
         if not self._point_t:
-            if not self._band_obs:
-                raise ValueError("no data: call add_flux_density or add_flux first")
+            if not self._band_obs and not self._centroid_obs:
+                raise ValueError("no data: call add_flux_density, add_flux or add_centroid first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
             return
         t = np.concatenate(self._point_t)
@@ -333,7 +370,7 @@ class Fitter:
         # duration aliases ...) go straight into their slot, exactly like a free parameter would
         base_fields = (C.c_double * 40).from_address(C.addressof(spec.base) + _lib.ModelParams.theta_c.offset)
         for name, value in fixed.items():
-            if name in MODEL_PARAM_DEFAULTS or name == "A_V":
+            if name in MODEL_PARAM_DEFAULTS or name == "A_V" or name in _lib.SKY_SLOTS:
                 continue
             if name not in _lib.PARAM_SLOTS:
                 raise ValueError(f"parameter {name} is not accepted by the accelerated path")
@@ -342,12 +379,17 @@ class Fitter:
         for d, pd in enumerate(free):
             if pd.name == "A_V":
                 spec.slot[d] = _lib.P_A_V
+            elif pd.name in _lib.SKY_SLOTS:
+                spec.slot[d] = _lib.SKY_SLOTS[pd.name]
             elif pd.name not in _lib.PARAM_SLOTS:
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             else:
                 spec.slot[d] = _lib.PARAM_SLOTS[pd.name]
             spec.is_log[d] = 1 if pd.scale is Scale.log else 0
         spec.a_v_fixed = float(fixed.get("A_V", 0.0))
+        if any(pd.name in _lib.SKY_SLOTS for pd in param_defs) and not self._centroid_obs:
+            raise ValueError("the parameters 'pa', 'east0' and 'north0' need centroid data (Fitter.add_centroid)")
+        spec._sky = self._sky_spec(fixed) if self._centroid_obs else None
         if self.extinction is not None and any(pd.name == "z" for pd in free):
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
@@ -393,13 +435,28 @@ class Fitter:
             spec.prior_kind[d], spec.prior_a[d], spec.prior_b[d] = kind, a, b
         return spec, lower, upper
 
+    def _sky_spec(self, fixed):
+        """vag_sky_fit_spec of the centroid groups; it keeps the arrays it points at alive."""
+        sky = _lib.SkyFitSpec()
+        groups = (_lib.CentroidObs * len(self._centroid_obs))()
+        for g, cd in enumerate(self._centroid_obs):
+            o = groups[g]
+            o.nu, o.n = cd["nu"], cd["t"].size
+            for name in ("t", "east", "north", "err_east", "err_north"):
+                setattr(o, name, cd[name].ctypes.data_as(_dp))
+            o.weight = cd["weights"].ctypes.data_as(_dp)
+        sky.n_groups, sky.groups = len(self._centroid_obs), groups
+        sky.pa_fixed, sky.east0_fixed, sky.north0_fixed = (float(fixed.get(k, 0.0)) for k in ("pa", "east0", "north0"))
+        sky._keep_alive = (groups, list(self._centroid_obs))
+        return sky
+
     # fitting/params.py validate_parameters: the checks that do not depend on the sampler
     def validate_parameters(self, param_defs: Sequence[ParamDef]) -> None:
         names = [pd.name for pd in param_defs]
         if len(set(names)) != len(names):
             raise ValueError("duplicate parameter names")
         for pd in param_defs:
-            if pd.name != "A_V" and pd.name not in _lib.PARAM_SLOTS:
+            if pd.name != "A_V" and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS:
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             if pd.scale is Scale.fixed:
                 continue
@@ -423,6 +480,8 @@ class Fitter:
             val = 10.0 ** sample[d] if spec.is_log[d] else sample[d]
             if spec.slot[d] == _lib.P_A_V:
                 a_v = val
+            elif spec.slot[d] > _lib.P_A_V:  # (the sky placement: not a Model field)
+                continue
             else:
                 fields[spec.slot[d]] = val
         if resolution is not None:
@@ -509,12 +568,17 @@ class Fitter:
             costs = torch.empty((k,), dtype=torch.float64, device=dev) if want_costs else None
 
             def run():
-                _lib.check(lib.vag_loglike_batch_dev(h, C.byref(keep[0]), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
+                if keep[0]._sky is not None:
+                    _lib.check(lib.vag_loglike_sky_batch_dev(h, C.byref(keep[0]), C.byref(keep[0]._sky), theta.data_ptr(), k,
+                                                             keep[0].ndim, values.data_ptr()))
+                else:
+                    _lib.check(lib.vag_loglike_batch_dev(h, C.byref(keep[0]), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
                 if want_costs:  # (one more launch: only a sharder that deals by cost asks for it)
                     _lib.check(lib.vag_last_model_costs_dev(h, k, costs.data_ptr()))
             _on_current_stream(run)
             return values, costs
         eval_dev.optional_costs = True
+        eval_dev.has_centroids = spec._sky is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -525,6 +589,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._sky is not None:
+                    from .dist import _NO_CENTROIDS
+                    raise NotImplementedError(_NO_CENTROIDS)
                 ticket = C.c_uint64(0)
                 _on_current_stream(lambda: _lib.check(lib.vag_loglike_shard_begin_dev(
                     h, C.byref(keep[0]), theta_all.data_ptr(), nb, keep[0].ndim, rank, world, block.data_ptr(), C.byref(ticket))))
@@ -550,8 +617,12 @@ class Fitter:
         h, lock = get_context(self.device)
         plan = _lib.Plan()
         with lock:
-            _lib.check(_lib.load().vag_loglike_batch(h, C.byref(spec), samples.ctypes.data_as(_dp), samples.shape[0],
-                                                     spec.ndim, out.ctypes.data_as(_dp)))
+            if spec._sky is not None:
+                _lib.check(_lib.load().vag_loglike_sky_batch(h, C.byref(spec), C.byref(spec._sky), samples.ctypes.data_as(_dp),
+                                                             samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
+            else:
+                _lib.check(_lib.load().vag_loglike_batch(h, C.byref(spec), samples.ctypes.data_as(_dp), samples.shape[0],
+                                                         spec.ndim, out.ctypes.data_as(_dp)))
             _lib.load().vag_last_plan(h, C.byref(plan))
         if plan.n_models_capacity:
             # never silent: these walkers were NOT evaluated (their adaptive grid exceeds the engine's static limits)

@@ -515,16 +515,24 @@ class Model:
             image, outside = image[0], outside[0]
         return SkyImage(image, outside, fov, t, nu[0] if scalar else nu)
 
-    def sky_moments(self, t, nu, n_az=None):
+    def sky_moments(self, t, nu, n_az=None, exact=False):
         """Flux-weighted moments of the sky image before pixelation (SkyMoments: F, Xbar, Ybar, varX, varY, covXY) at times
-        t [s] and frequencies nu [Hz].  n_az: azimuthal parts per full circle (default 256)."""
+        t [s] and frequencies nu [Hz].  n_az: azimuthal parts per full circle (default 256).  exact=True: the azimuthal
+        integral in closed form (the n_az -> infinity limit, vag_sky_centroid_batch); n_az must then be None."""
+        if exact and n_az is not None:
+            raise ValueError("sky_moments: n_az does not apply with exact=True")
         t, nu, scalar = self._sky_inputs(t, nu, n_az)
         out = np.empty((nu.size, t.size, 6))
         h, lock = get_context(self._device)
         with lock:
-            _lib.check(_lib.load().vag_sky_moments_batch(
-                h, C.byref(self.params), 1, t.ctypes.data_as(_dp), t.size, nu.ctypes.data_as(_dp), nu.size,
-                0 if n_az is None else int(n_az), out.ctypes.data_as(_dp)))
+            if exact:
+                _lib.check(_lib.load().vag_sky_centroid_batch(
+                    h, C.byref(self.params), 1, t.ctypes.data_as(_dp), t.size, nu.ctypes.data_as(_dp), nu.size,
+                    out.ctypes.data_as(_dp)))
+            else:
+                _lib.check(_lib.load().vag_sky_moments_batch(
+                    h, C.byref(self.params), 1, t.ctypes.data_as(_dp), t.size, nu.ctypes.data_as(_dp), nu.size,
+                    0 if n_az is None else int(n_az), out.ctypes.data_as(_dp)))
         return SkyMoments(out[0] if scalar else out, t, nu[0] if scalar else nu)
 
     # -- Model.flux: pybind.cpp:430, pymodel.cpp:391-410 --
