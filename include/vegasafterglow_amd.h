@@ -232,6 +232,17 @@ int vag_sky_moments_batch(vag_ctx* ctx, const vag_model_params* params, int nb, 
 int vag_sky_centroid_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
                            double* moments);
 
+/* Complex visibilities of the same parts as vag_sky_moments_batch (a direct Fourier sum, no pixels).  Added after VAG_ABI_VERSION
+ * 13 (detect by symbol).  Every part (w, X, Y) is placed on the sky as the centroid likelihood places a centroid, east = X sin pa +
+ * Y cos pa, north = X cos pa - Y sin pa (pa [rad], no offset: a shift (east0, north0) multiplies V by
+ * exp(-2 pi i (u east0 + v north0))), and V(u, v) = sum w exp(-2 pi i (u east + v north)), u east, v north, in wavelengths.
+ * u, v [nnu][nt][nbl] are the baselines of every (nu, t) slot, shared by the batch; vis [nb][nnu][nt][nbl][2] (re, im), units of
+ * vag_flux_density_grid_batch, so V(0, 0) is the grid flux up to summation order.  1 <= nbl <= VAG_SKY_MAX_BASELINES, u, v and pa
+ * finite, n_az <= 0: 1024.  Results are bitwise reproducible and do not depend on the rest of the batch. */
+#define VAG_SKY_MAX_BASELINES 65536
+int vag_sky_visibility_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                             const double* u, const double* v, int nbl, double pa, int n_az, double* vis);
+
 /*
  * Model.flux_density(t[n] ascending, nu[n]) -> total[n]
  * (pybind/pybind.cpp:427, pybind/pymodel.cpp:373-389, src/core/observer.h:447-538),

@@ -126,6 +126,7 @@ EXPORTS = [
     "vag_last_model_costs_dev", "vag_loglike_shard_dev", "vag_loglike_shard_finish_dev", "vag_loglike_shard_begin_dev", "vag_loglike_shard_end_dev", "vag_loglike_shard_state_dev", "vag_ctx_profile", "vag_last_profile", "vag_details", "vag_details_rvs", "vag_details_radiation", "vag_details_regime", "vag_details_eat", "vag_profile_eval", "vag_last_stage_times", "vag_last_plan", "vag_ctx_count_work",
     "vag_ctx_coalesce", "vag_ctx_coalesce_stats", "vag_flux_density_grid_coalesced", "vag_flux_density_coalesced", "vag_flux_coalesced",
     "vag_sky_image_batch", "vag_sky_moments_batch", "vag_sky_centroid_batch", "vag_loglike_sky_batch", "vag_loglike_sky_batch_dev",
+    "vag_sky_visibility_batch",
 ]
 
 _lib = None
@@ -172,6 +173,7 @@ def load():
     lib.vag_sky_image_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp]
     lib.vag_sky_moments_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp]
     lib.vag_sky_centroid_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp]
+    lib.vag_sky_visibility_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_int, _dp]
     lib.vag_loglike_sky_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), _dp, C.c_int, C.c_int, _dp]
     lib.vag_loglike_sky_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]

@@ -403,6 +403,7 @@ struct vag_ctx {
     // as its own output lattice; offsets handed out by vag_ic_plan_kernel, d_icused counts the doubles in use)
     DevBuf d_ichdr, d_icplan, d_icpool, d_icused, d_icslow /* records of the cells on the spectrum kernel's slow path */;
     DevBuf d_skyterms, d_skyimg, d_skymom;  // sky images / moments (vag_sky.h): term list, a chunk's images, moments + outside
+    DevBuf d_skyvis, d_skyuv;  // visibilities (vag_sky.h): a chunk's row-block partials + combined values, a chunk's baselines
     DevBuf d_skycen, d_skycmom, d_skyfit;  // exact centroids (vag_sky.h): row-block partials, moments, centroid-fit pass data
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -695,7 +696,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_fit.release();
     c->h_skyfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skycen, &c->d_skycmom, &c->d_skyfit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skycen, &c->d_skycmom, &c->d_skyfit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1882,10 +1883,18 @@ int grid_request_chunked(vag_ctx* c, const vag_model_params* d_params, int nb, i
 // Sky images / image moments of the whole batch (vag_sky.h); model stages already run, d_lg2t / d_lg2nu prepared.  Every enabled
 // (emitter, pass) -- forward synchrotron, forward SSC, reverse synchrotron, reverse SSC, as grid_request runs them -- writes its
 // terms into its own slice of one term list, then the deposit and moment kernels read all slices in that fixed order.  The time axis
-// is cut into chunks whose term list and images stay within 256 MB (VAG_SKY_CHUNK_T: a test's chunk length).  Host outputs:
-// h_image [nb][nnu][nt][npixel^2], h_outside [nb][nnu][nt], h_moments [nb][nnu][nt][6]; any may be null.
+// is cut into chunks whose term list, images, visibility partials and baselines stay within 256 MB (VAG_SKY_CHUNK_T: a test's
+// chunk length).  Host outputs: h_image [nb][nnu][nt][npixel^2], h_outside [nb][nnu][nt], h_moments [nb][nnu][nt][6], vr->vis
+// [nb][nnu][nt][nbl][2]; any may be null.
+struct SkyVisReq {
+    const double* u;  // [nnu][nt][nbl] wavelengths, shared by the batch
+    const double* v;
+    int nbl;
+    double pa;    // [rad]
+    double* vis;  // [nb][nnu][nt][nbl][2] (re, im)
+};
 int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, int nnu, int n_az, double fov, int npixel,
-                double* h_image, double* h_outside, double* h_moments) {
+                double* h_image, double* h_outside, double* h_moments, const SkyVisReq* vr = nullptr) {
     hipStream_t st = c->stream;
     struct SkyPass {
         int e, pass;
@@ -1899,7 +1908,10 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
     const int n_pass = (int)passes.size();
     const int R = std::max(1, c->max_pairs), ks = std::max(2, c->max_k);
     const size_t npix2 = h_image ? (size_t)npixel * npixel : 0;
-    const size_t per_t = sizeof(double) * (size_t)nb * nnu * ((size_t)n_pass * 4 * R + npix2);
+    const bool want_vis = vr && vr->vis;
+    const int nbl = want_vis ? vr->nbl : 0, n_rblk = (R + SKYV_ROWS - 1) / SKYV_ROWS;
+    const size_t vis_per_image = want_vis ? (size_t)(n_rblk + 1) * nbl * 2 : 0;  // partials + the combined chunk
+    const size_t per_t = sizeof(double) * ((size_t)nb * nnu * ((size_t)n_pass * 4 * R + npix2 + vis_per_image) + (size_t)nnu * nbl * 2);
     int chunk = (int)std::max<size_t>(1, std::min<size_t>(nt, ((size_t)256 << 20) / per_t));
     if (const char* e = vag_hook("VAG_SKY_CHUNK_T")) chunk = std::max(1, std::min(nt, std::atoi(e)));
     const size_t lds = sizeof(double) * ((size_t)SP_LDS_DOUBLES + (size_t)SKY_WAVES * 3 * ks);
@@ -1907,6 +1919,8 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
     const size_t G_max = (size_t)nb * nnu * chunk;
     if (c->d_skyterms.ensure(sizeof(double) * (size_t)n_pass * 4 * G_max * R)) return VAG_E_HIP;
     if (h_image && c->d_skyimg.ensure(sizeof(double) * G_max * npix2)) return VAG_E_HIP;
+    if (want_vis && c->d_skyvis.ensure(sizeof(double) * G_max * vis_per_image)) return VAG_E_HIP;
+    if (want_vis && c->d_skyuv.ensure(sizeof(double) * (size_t)nnu * chunk * nbl * 2)) return VAG_E_HIP;
     const size_t n_bins = (size_t)nb * nnu * nt;
     if (c->d_skymom.ensure(sizeof(double) * n_bins * 7)) return VAG_E_HIP;
     double* d_mom = c->d_skymom.as<double>();
@@ -1995,6 +2009,39 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
         if (h_image)  // [nb * nnu][n][npixel^2] -> its place in [nb * nnu][nt][npixel^2]
             HIPCHK(hipMemcpy2DAsync(h_image + (size_t)t0 * npix2, sizeof(double) * nt * npix2, c->d_skyimg.p, sizeof(double) * n * npix2,
                                     sizeof(double) * n * npix2, (size_t)nb * nnu, hipMemcpyDeviceToHost, st));
+        if (want_vis) {
+            const size_t row = sizeof(double) * n * nbl;  // this chunk's baselines: [nnu][t0 : t0 + n][nbl] -> [nnu][n][nbl]
+            double* d_u = c->d_skyuv.as<double>();
+            double* d_v = d_u + (size_t)nnu * n * nbl;
+            HIPCHK(hipMemcpy2DAsync(d_u, row, vr->u + (size_t)t0 * nbl, sizeof(double) * nt * nbl, row, nnu, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpy2DAsync(d_v, row, vr->v + (size_t)t0 * nbl, sizeof(double) * nt * nbl, row, nnu, hipMemcpyHostToDevice, st));
+            SkyVisArgs va{};
+            va.meta = b.meta;
+            va.phi = b.phi;
+            va.terms = b.terms;
+            va.u = d_u;
+            va.v = d_v;
+            va.n_pass = n_pass;
+            va.nnu = nnu;
+            va.nt = n;
+            va.R = R;
+            va.n_az = n_az;
+            va.nbl = nbl;
+            va.sin_pa = std::sin(vr->pa);
+            va.cos_pa = std::cos(vr->pa);
+            va.partial = c->d_skyvis.as<double>();
+            double* d_vis = va.partial + (size_t)n_rblk * G * nbl * 2;
+            const int n_blb = (nbl + 63) / 64;
+            hipLaunchKernelGGL(vag_sky_visibility_kernel, dim3((unsigned)(G * n_blb), (unsigned)n_rblk), dim3(64), 0, st, va);
+            HIPCHK(hipGetLastError());
+            const size_t n_vis = G * nbl;
+            hipLaunchKernelGGL(vag_sky_visibility_combine, dim3((unsigned)((n_vis + 255) / 256)), dim3(256), 0, st, b.meta, va.partial,
+                               (int)G, nnu, n, nbl, d_vis);
+            HIPCHK(hipGetLastError());
+            // [nb * nnu][n][nbl][2] -> its place in [nb * nnu][nt][nbl][2]
+            HIPCHK(hipMemcpy2DAsync(vr->vis + (size_t)t0 * nbl * 2, sizeof(double) * nt * nbl * 2, d_vis, 2 * row, 2 * row, (size_t)nb * nnu,
+                                    hipMemcpyDeviceToHost, st));
+        }
     }
     if (rc) return rc;
     if (h_moments) HIPCHK(hipMemcpyAsync(h_moments, d_mom, sizeof(double) * n_bins * 6, hipMemcpyDeviceToHost, st));
@@ -2820,14 +2867,18 @@ int vag_flux_density_grid_components4_batch(vag_ctx* c, const vag_model_params* 
 
 // Model.sky_image / Model.sky_moments over a batch (vag_sky.h; the definition is the engine's own)
 static int sky_impl(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu, int n_az,
-                    double fov, int npixel, double* image, double* outside, double* moments) {
+                    double fov, int npixel, double* image, double* outside, double* moments, const SkyVisReq* vr = nullptr) {
     int rc = check_host_inputs(params, nb, t, nt);
     if (rc) return rc;
     if (!uniform_flags(params, nb)) {
         const size_t st = (size_t)nnu * nt;
-        return run_flag_groups(params, nb, {{image, st * npixel * npixel}, {outside, st}, {moments, st * 6}},
+        double* vis = vr ? vr->vis : nullptr;
+        const size_t vis_stride = vr ? st * vr->nbl * 2 : 0;
+        return run_flag_groups(params, nb, {{image, st * npixel * npixel}, {outside, st}, {moments, st * 6}, {vis, vis_stride}},
                                [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-                                   return sky_impl(c, gp, ng, t, nt, nu, nnu, n_az, fov, npixel, o[0], o[1], o[2]);
+                                   SkyVisReq gv{};
+                                   if (vr) gv = *vr, gv.vis = o[3];
+                                   return sky_impl(c, gp, ng, t, nt, nu, nnu, n_az, fov, npixel, o[0], o[1], o[2], vr ? &gv : nullptr);
                                });
     }
     HIPCHK(hipSetDevice(c->device));
@@ -2841,7 +2892,7 @@ static int sky_impl(vag_ctx* c, const vag_model_params* params, int nb, const do
     if (rc) return rc;
     rc = run_model_stages(c, c->d_params.as<vag_model_params>(), nb, false);
     if (rc) return rc;
-    rc = sky_request(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, n_az, fov, npixel, image, outside, moments);
+    rc = sky_request(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, n_az, fov, npixel, image, outside, moments, vr);
     if (rc) return rc;
     return check_status(c, nb);  // (no collect_times: the flux events it reads are not recorded by the sky passes)
 }
@@ -2866,6 +2917,25 @@ int vag_sky_moments_batch(vag_ctx* c, const vag_model_params* params, int nb, co
     if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
     if (n_az <= 0) n_az = 256;
     return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, 0.0, 1, nullptr, nullptr, moments);
+}
+
+int vag_sky_visibility_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                             const double* u, const double* v, int nbl, double pa, int n_az, double* vis) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!nu || !u || !v || !vis) return set_err(VAG_E_INVALID, "null frequency, baseline or visibility array");
+    if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
+    if (nbl <= 0 || nbl > VAG_SKY_MAX_BASELINES)
+        return set_err(VAG_E_INVALID, "nbl must be in [1, %d], got %d", VAG_SKY_MAX_BASELINES, nbl);
+    if (nt > 0) {  // (bad times: check_host_inputs)
+        const size_t n = (size_t)nnu * nt * nbl;
+        for (size_t i = 0; i < n; ++i)
+            if (!std::isfinite(u[i]) || !std::isfinite(v[i])) return set_err(VAG_E_INVALID, "baselines u, v must be finite");
+    }
+    if (!std::isfinite(pa)) return set_err(VAG_E_INVALID, "pa must be finite");
+    if (n_az <= 0) n_az = 1024;
+    const SkyVisReq vr{u, v, nbl, pa, vis};
+    return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, 0.0, 1, nullptr, nullptr, nullptr, &vr);
 }
 
 // Model.sky_moments(exact=True) over a batch: the n_az -> infinity limit of sky_impl's moments (vag_sky_centroid_kernel)

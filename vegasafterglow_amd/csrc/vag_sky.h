@@ -348,6 +348,96 @@ __global__ void __launch_bounds__(64) vag_sky_moments_kernel(SkyImgArgs a) {
     }
 }
 
+// ---- visibilities (vag_sky_visibility_batch): a direct Fourier sum over the parts of the term list, no pixels ----
+//   vag_sky_visibility_kernel   one wavefront per (image of the chunk, block of 64 baselines, block of SKYV_ROWS of the model's own
+//                               rows), lane = baseline: the passes in order, the rows of the block in order, every part in order (+Y
+//                               before -Y), V += w exp(-2 pi i (u east + v north)) in registers -> one partial per (row block, image,
+//                               baseline)
+//   vag_sky_visibility_combine  one thread per (image, baseline): the model's own row blocks in block order
+// The row blocks depend on the model's rows only: bitwise reproducible, independent of the batch and of the t-chunking.
+
+constexpr int SKYV_ROWS = 256;  // rows per row block of the visibility kernel
+
+struct SkyVisArgs {
+    const VagGridMeta* meta;
+    const double* phi;    // [nb][ph_stride]
+    const double* terms;  // the term list of this chunk (sky_request)
+    const double* u;      // this chunk's baselines [nnu][nt][nbl], wavelengths
+    const double* v;
+    int n_pass, nnu, nt, R, n_az, nbl;
+    double sin_pa, cos_pa;
+    double* partial;  // [n_rblk][nb * nnu * nt][nbl][2]
+};
+
+__global__ void __launch_bounds__(64) vag_sky_visibility_kernel(SkyVisArgs a) {
+    const int lane = threadIdx.x, n_blb = (a.nbl + 63) / 64;
+    const int g = blockIdx.x / n_blb, k = (blockIdx.x - g * n_blb) * 64 + lane, rb = blockIdx.y;
+    const int m = g / (a.nnu * a.nt), s = g % (a.nnu * a.nt);  // s = l * nt + idx
+    const VagGridMeta& M = a.meta[m];
+    const int n_rows = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    const int r0 = rb * SKYV_ROWS, r1 = min(n_rows, r0 + SKYV_ROWS);
+    if (r0 >= n_rows && r0 > 0) return;  // (the combine reads the blocks of the model's rows only; block 0 always)
+    const double* phi = a.phi + (size_t)m * M.ph_stride;
+    const size_t G = (size_t)gridDim.x / n_blb, plane = G * a.R;
+    const bool live = k < a.nbl;
+    const double u = live ? a.u[(size_t)s * a.nbl + k] : 0.0, v = live ? a.v[(size_t)s * a.nbl + k] : 0.0;
+    const double spa = a.sin_pa, cpa = a.cos_pa;
+    double re = 0, im = 0;
+    auto add = [&](double w, double X, double Y) {
+        const double east = X * spa + Y * cpa, north = X * cpa - Y * spa;
+        double sn, cs;
+        sincospi(2 * (u * east + v * north), &sn, &cs);
+        re += w * cs;
+        im -= w * sn;
+    };
+#pragma unroll 1
+    for (int pass = 0; pass < a.n_pass; ++pass) {
+        const double* T = a.terms + (size_t)pass * 4 * plane + (size_t)g * a.R;
+#pragma unroll 1
+        for (int p = r0; p < r1; ++p) {  // wave-uniform: every lane reads the same term
+            const double w = T[p];
+            if (!(w > 0)) continue;
+            const double ca = T[plane + p], cb = T[2 * plane + p], cc = T[3 * plane + p];
+            const SkyBin b = sky_bin(M, phi, p, a.n_az);
+            const double part = w / b.S, dphi = b.width / b.S;
+            const double wp = b.mirrored ? 0.5 * part : part;
+#pragma unroll 1
+            for (int q = 0; q < b.S; ++q) {
+                const double ph = b.left + (q + 0.5) * dphi;  // vag_sky_deposit_kernel's part, expression for expression
+                double sn, cs;
+                sincos(ph, &sn, &cs);
+                const double X = ca - cb * cs, Y = cc * sn;
+                add(wp, X, Y);
+                if (b.mirrored) add(wp, X, -Y);
+            }
+        }
+    }
+    if (live) {
+        double* o = a.partial + (((size_t)rb * G + g) * a.nbl + k) * 2;
+        o[0] = re;
+        o[1] = im;
+    }
+}
+
+// One thread per (image of the chunk, baseline): vis [nb * nnu * nt][nbl][2] of the chunk.
+__global__ void __launch_bounds__(256) vag_sky_visibility_combine(const VagGridMeta* __restrict__ meta, const double* __restrict__ partial,
+                                                                  int G, int nnu, int nt, int nbl, double* __restrict__ vis) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)G * nbl) return;
+    const int g = (int)(i / nbl), m = g / (nnu * nt);
+    const VagGridMeta M = meta[m];
+    const int n_rows = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    const int n_rblk = max(1, (n_rows + SKYV_ROWS - 1) / SKYV_ROWS);
+    const size_t blk = (size_t)G * nbl * 2;
+    double re = 0, im = 0;
+    for (int b = 0; b < n_rblk; ++b) {
+        re += partial[b * blk + 2 * i];
+        im += partial[b * blk + 2 * i + 1];
+    }
+    vis[2 * i] = re;
+    vis[2 * i + 1] = im;
+}
+
 // ---- exact centroids (vag_sky_centroid_batch and the likelihood's centroid groups): no term list, no azimuthal parts ----
 //   vag_sky_centroid_kernel   one (theta, phi) row per lane, 64 rows per wavefront: the row's EAT logs, bracket and boundary spectra
 //                             with vag_sky_terms_kernel's expressions, the term (w, a, b, c), its exact moments over the row's phi bin

@@ -535,6 +535,37 @@ class Model:
                     0 if n_az is None else int(n_az), out.ctypes.data_as(_dp)))
         return SkyMoments(out[0] if scalar else out, t, nu[0] if scalar else nu)
 
+    def sky_visibilities(self, t, nu, u, v, pa=0.0, n_az=None):
+        """Complex visibilities V(u, v) = sum w exp(-2 pi i (u east + v north)) of the parts of sky_moments at times t [s] and
+        frequencies nu [Hz] (vag_sky_visibility_batch).  u (east) and v (north) in wavelengths, equal shapes:
+        (nbl,) for every (nu, t), or (nnu, nt, nbl) per slot ((nt, nbl) also for a scalar nu).  pa [rad] turns the jet axis:
+        east = X sin pa + Y cos pa, north = X cos pa - Y sin pa.  n_az: azimuthal parts per full circle (default 1024).  Returns
+        complex128 (nnu, nt, nbl) -- (nt, nbl) for a scalar nu -- in erg cm^-2 s^-1 Hz^-1; V(0, 0) is flux_density_grid."""
+        t, nu, scalar = self._sky_inputs(t, nu, n_az)
+        u, v = np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64)
+        _req(u.shape == v.shape, f"u and v must have the same shape, got {u.shape} and {v.shape}")
+        if scalar and u.ndim == 2:
+            u, v = u[None], v[None]
+        _req(u.ndim == 1 or (u.ndim == 3 and u.shape[:2] == (nu.size, t.size)),
+             f"u and v must be (nbl,) or (nnu, nt, nbl) = ({nu.size}, {t.size}, nbl) arrays, got {u.shape}")
+        nbl = u.shape[-1]
+        _req(1 <= nbl <= 65536, f"the number of baselines must be in [1, 65536], got {nbl}")
+        _req(bool(np.all(np.isfinite(u)) and np.all(np.isfinite(v))), "baselines u, v must be finite")
+        pa = float(pa)
+        _req(math.isfinite(pa), f"pa must be finite, got {pa}")
+        shape = (nu.size, t.size, nbl)
+        u = np.ascontiguousarray(np.broadcast_to(u, shape))
+        v = np.ascontiguousarray(np.broadcast_to(v, shape))
+        out = np.empty(shape + (2,))
+        h, lock = get_context(self._device)
+        with lock:
+            _lib.check(_lib.load().vag_sky_visibility_batch(
+                h, C.byref(self.params), 1, t.ctypes.data_as(_dp), t.size, nu.ctypes.data_as(_dp), nu.size,
+                u.ctypes.data_as(_dp), v.ctypes.data_as(_dp), nbl, pa, 0 if n_az is None else int(n_az),
+                out.ctypes.data_as(_dp)))
+        vis = out[..., 0] + 1j * out[..., 1]
+        return vis[0] if scalar else vis
+
     # -- Model.flux: pybind.cpp:430, pymodel.cpp:391-410 --
     def flux(self, t, nu_min, nu_max, num_nu):
         t = _as_f64(t, "t")
