@@ -243,6 +243,28 @@ int vag_sky_centroid_batch(vag_ctx* ctx, const vag_model_params* params, int nb,
 int vag_sky_visibility_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
                              const double* u, const double* v, int nbl, double pa, int n_az, double* vis);
 
+/* Test-facing: evaluates device routine `fn` (VAG_MATH_*) of this library on n points, on the device, with the context's own
+ * softplus / log2 tables.  in: [n][n_in(fn)], out: [n][n_out(fn)].  Added after VAG_ABI_VERSION 13 (detect by symbol).
+ * n_in = n_out = 1 for the elementwise routines (the sp_fast forms take z and give log2(1 + 2^z)), except:
+ *   VAG_MATH_SYN_CELL  in  {gamma_m, gamma_c, gamma_a, gamma_M, column_den, B, p, x0, x1} (internal units, x = log2 nu);
+ *                      out {the VAG_NPAR block of syn_photons_build, log2_I_nu_fast on that block in registers at x0, x1, on it as a
+ *                      strided column at x0, x1, log2_I_nu_fast2(x0, x1), the exact-libm log2_I_nu at x0, x1}: VAG_NPAR + 8;
+ *   VAG_MATH_IC_CELL   in  {VAG_NPAR block, VAG_NQ IC extras, p, x0, x1}; out {log2_I_nu_ic, _straight, _pair, each at x0, x1};
+ *   VAG_MATH_LDS_ADD   in  {slot, value}: the 64 lanes of a wavefront add their values into the slots (integers in [0, 64)) they
+ *                      name with one ds_add_f64; out: slot `lane`'s total.
+ * The wave routines (WAVE_PREFIX_SUM, WAVE_SUM, SKY_WAVE_SUM, LDS_ADD) run one wavefront per 64 points and need n % 64 == 0.
+ * 0, VAG_E_INVALID (unknown fn, n <= 0, a null pointer, n % 64 != 0 for a wave routine, a bad slot) or VAG_E_HIP. */
+enum {
+    VAG_MATH_EXP2_FAST = 0, VAG_MATH_EXP2_ODE, VAG_MATH_EXP2_SAT, VAG_MATH_EXP2_OR_ZERO,
+    VAG_MATH_LOG2_FAST, VAG_MATH_LOG2_TAB, VAG_MATH_LOG2_TAB_NB,
+    VAG_MATH_RCP_FAST, VAG_MATH_RCP_ODE, VAG_MATH_RCP1, VAG_MATH_SQRT_FAST, VAG_MATH_SQRT_ODE, VAG_MATH_SQRT1,
+    VAG_MATH_SP_FAST, VAG_MATH_SP_FAST_GLOBAL, VAG_MATH_SP_FAST_SEL,
+    VAG_MATH_SYN_CELL, VAG_MATH_IC_CELL,
+    VAG_MATH_WAVE_PREFIX_SUM, VAG_MATH_WAVE_SUM, VAG_MATH_SKY_WAVE_SUM, VAG_MATH_LDS_ADD,
+    VAG_MATH_COUNT
+};
+int vag_debug_device_math(vag_ctx* ctx, int fn, const double* in, int n, double* out);
+
 /*
  * Model.flux_density(t[n] ascending, nu[n]) -> total[n]
  * (pybind/pybind.cpp:427, pybind/pymodel.cpp:373-389, src/core/observer.h:447-538),

@@ -50,6 +50,12 @@ class BandObs(C.Structure):
                 ("weight", C.POINTER(C.c_double))]
 
 
+# VAG_MATH_*: the device routines vag_debug_device_math evaluates (include/vegasafterglow_amd.h)
+MATH = {name: i for i, name in enumerate([
+    "exp2_fast", "exp2_ode", "exp2_sat", "exp2_or_zero", "log2_fast", "log2_tab", "log2_tab_nb",
+    "rcp_fast", "rcp_ode", "rcp1", "sqrt_fast", "sqrt_ode", "sqrt1", "sp_fast", "sp_fast_global", "sp_fast_sel",
+    "syn_cell", "ic_cell", "wave_prefix_sum", "wave_sum", "sky_wave_sum", "lds_add"])}
+
 P_A_V = 1000  # VAG_P_A_V
 # VAG_P_SKY_*: the sky placement of the centroid groups (vag_loglike_sky_batch), not Model fields either
 SKY_SLOTS = {"pa": 1001, "east0": 1002, "north0": 1003}
@@ -126,7 +132,7 @@ EXPORTS = [
     "vag_last_model_costs_dev", "vag_loglike_shard_dev", "vag_loglike_shard_finish_dev", "vag_loglike_shard_begin_dev", "vag_loglike_shard_end_dev", "vag_loglike_shard_state_dev", "vag_ctx_profile", "vag_last_profile", "vag_details", "vag_details_rvs", "vag_details_radiation", "vag_details_regime", "vag_details_eat", "vag_profile_eval", "vag_last_stage_times", "vag_last_plan", "vag_ctx_count_work",
     "vag_ctx_coalesce", "vag_ctx_coalesce_stats", "vag_flux_density_grid_coalesced", "vag_flux_density_coalesced", "vag_flux_coalesced",
     "vag_sky_image_batch", "vag_sky_moments_batch", "vag_sky_centroid_batch", "vag_loglike_sky_batch", "vag_loglike_sky_batch_dev",
-    "vag_sky_visibility_batch",
+    "vag_sky_visibility_batch", "vag_debug_device_math",
 ]
 
 _lib = None
@@ -174,6 +180,7 @@ def load():
     lib.vag_sky_moments_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp]
     lib.vag_sky_centroid_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp]
     lib.vag_sky_visibility_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_int, _dp]
+    lib.vag_debug_device_math.argtypes = [v, C.c_int, _dp, C.c_int, _dp]
     lib.vag_loglike_sky_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), _dp, C.c_int, C.c_int, _dp]
     lib.vag_loglike_sky_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]

@@ -25,6 +25,7 @@
 #include "vag_fit_rows.h"
 #include "vag_grid_rows.h"
 #include "vag_sky.h"
+#include "vag_debug_math.h"
 
 using namespace vag;
 
@@ -2936,6 +2937,40 @@ int vag_sky_visibility_batch(vag_ctx* c, const vag_model_params* params, int nb,
     if (n_az <= 0) n_az = 1024;
     const SkyVisReq vr{u, v, nbl, pa, vis};
     return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, 0.0, 1, nullptr, nullptr, nullptr, &vr);
+}
+
+// Test-facing probe of the device math (vag_debug_math.h): not on any product path, synchronous, its own buffers.
+int vag_debug_device_math(vag_ctx* c, int fn, const double* in, int n, double* out) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    const int n_in = math_n_in(fn), n_out = math_n_out(fn);
+    if (n_in == 0) return set_err(VAG_E_INVALID, "unknown device routine %d", fn);
+    if (!in || !out) return set_err(VAG_E_INVALID, "null input or output array");
+    if (n <= 0) return set_err(VAG_E_INVALID, "n must be positive, got %d", n);
+    if (math_is_wave(fn) && n % 64 != 0) return set_err(VAG_E_INVALID, "wave routine %d needs n %% 64 == 0, got %d", fn, n);
+    if (fn == VAG_MATH_LDS_ADD)
+        for (int i = 0; i < n; ++i)
+            if (!(in[2 * (size_t)i] >= 0 && in[2 * (size_t)i] < 64 && in[2 * (size_t)i] == std::floor(in[2 * (size_t)i])))
+                return set_err(VAG_E_INVALID, "point %d: lds_add_f64 slot must be an integer in [0, 64)", i);
+    HIPCHK(hipSetDevice(c->device));
+    struct Bufs {
+        DevBuf in, out, col;
+        ~Bufs() {
+            in.release();
+            out.release();
+            col.release();
+        }
+    } b;
+    const size_t bytes_in = sizeof(double) * (size_t)n * n_in, bytes_out = sizeof(double) * (size_t)n * n_out;
+    if (b.in.ensure(bytes_in) || b.out.ensure(bytes_out)) return VAG_E_HIP;
+    if (fn == VAG_MATH_SYN_CELL && b.col.ensure(sizeof(double) * (size_t)n * VAG_NPAR)) return VAG_E_HIP;
+    HIPCHK(hipMemcpyAsync(b.in.p, in, bytes_in, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(vag_math_probe_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), MATH_PROBE_LDS, c->stream, fn, n,
+                       b.in.as<double>(), b.out.as<double>(), c->d_sptab.as<double>(), b.col.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, b.out.p, bytes_out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return VAG_OK;
 }
 
 // Model.sky_moments(exact=True) over a batch: the n_az -> infinity limit of sky_impl's moments (vag_sky_centroid_kernel)

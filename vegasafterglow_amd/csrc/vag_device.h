@@ -81,10 +81,10 @@ VAG_DEV double sqrt_fast(double x) {
     double y = __builtin_amdgcn_rsq(x);               // ~ 1/sqrt(x)
     y = y * fma(-0.5 * x * y, y, 1.5);                // Newton on 1/sqrt
     double s = x * y;                                 // ~ sqrt(x)
-    s = fma(fma(-s, s, x), 0.5 * y, s);               // one correction with the residual in fma: 1.1e-16 measured
-    return s;                                         // (profiles/micro/rcp_accuracy.hip; a second one changes nothing)
+    s = fma(fma(-s, s, x), 0.5 * y, s);               // one correction with the residual in fma: 1.6e-16 (0.71 ulp) measured
+    return s;                                         // (tests/test_device_math.py; a second one changes nothing)
 }
-// 1/x to 2e-15 (one Newton step on the 4.6e-8 hardware estimate): enough inside an ODE right-hand side integrated to 1e-6
+// 1/x to 2.2e-15 (one Newton step on the 4.6e-8 hardware estimate): enough inside an ODE right-hand side integrated to 1e-6
 VAG_DEV double rcp_ode(double x) {
     const double r = __builtin_amdgcn_rcp(x);
     return fma(r, fma(-x, r, 1.0), r);
@@ -951,7 +951,8 @@ VAG_DEV double log2_I_nu(const PtrT c, int st, const SpecConst& sc, double lg2_n
     return spec - c[VP_INV_NUMAX * st] * exp2(lg2_nu);
 }
 
-// ---- fast FP64 kernels for the hot evaluator (accuracy verified at context creation / in tests) ----
+// ---- fast FP64 kernels for the hot evaluator (accuracy: tests/test_device_math.py, on the device against high-precision references;
+//      context creation checks the two host-built tables) ----
 // On CDNA4 every wave64 VALU instruction -- FP64 FMA, 32-bit integer add, register move alike -- occupies its SIMD for
 // four cycles, and 32-bit integer multiplies / 64-bit multiply-adds take four times that.  The kernels below are
 // therefore written for instruction COUNT: Horner chains with the coefficients in SGPRs (no accumulator copies),
@@ -1057,7 +1058,8 @@ VAG_DEV double exp2_fast(double x) {  // finite x only: +-inf would give inf - i
     const double p = fma(q8c, f8, q07);
 #else
     // minimax q of degree 10 for (2^f - 1) / f on [-1/2, 1/2] (profiles/micro/exp2_minimax.py: Remez in 60-digit arithmetic;
-    // the rounded Horner form is within 2.1e-16 of 2^f, the degree-12 Taylor form it replaces was at 3.3e-16 with one step more)
+    // the rounded Horner form is within 2.1e-16 of 2^f, the degree-12 Taylor form it replaces -- exp2_ode's -- is at 3.7e-16 with one
+    // step more; tests/test_device_math.py)
     double p = fma(4.4566755710138823e-10, f, 7.072586181346367e-09);
     p = fma3(p, f, 1.0178051727399186e-07);
     p = fma3(p, f, 1.321544258661287e-06);
@@ -1166,7 +1168,8 @@ VAG_DEV double wave_prefix_sum(double x) {  // inclusive sum over lanes 0..lane 
     return x;
 }
 VAG_DEV double from_lane_below(double v) { return dpp_zero<0x138, 0xf>(v); }  // wave_shr:1: lane - 1's value, 0 into lane 0
-// *p += v on an LDS word without a return value (the hardware applies the lanes of one instruction in lane order)
+// *p += v on an LDS word without a return value (the hardware applies the lanes of one instruction in lane order:
+// tests/test_device_math.py)
 VAG_DEV void lds_add_f64(double* p, double v) {
     asm volatile("ds_add_f64 %0, %1" ::"v"((unsigned)(size_t)(__attribute__((address_space(3))) double*)p), "v"(v) : "memory");
 }
@@ -1192,8 +1195,9 @@ VAG_DEV double log2_I_nu_fast(const PtrT& c, int st, const SpecConst& sc, double
 
 // The same evaluator for the TWO frequencies of a boundary work item as one straight-line block: no lane-divergent branches (the
 // +-20 softplus shortcuts, the far-thick cut and the nu_M cut-off become selects on the same values), so the two evaluations and
-// the independent softplus / exp2 chains inside each interleave.  Same arithmetic per taken path, hence the same bits as
-// log2_I_nu_fast.
+// the independent softplus / exp2 chains inside each interleave.  Same arithmetic per taken path; the compiler contracts products
+// into FMAs per inlined copy, so it is log2_I_nu_fast to one rounding of a folded term (one ulp of max(256, |value|):
+// tests/test_device_math.py), not bit for bit.
 template <class Tab>
 VAG_DEV double sp_fast_sel(double z, Tab tab) {
     const double a = fabs(z);

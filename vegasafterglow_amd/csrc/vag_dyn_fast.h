@@ -7,7 +7,7 @@
 // v_rcp/v_rsq_f64 and ~25 per compare-and-select on doubles (profiles/micro/issue_rate.hip), so the latency of ONE row --
 // which is the latency of a single light curve and of a small walker block -- is the instruction count of a step attempt.
 //   * The right-hand side is straight-line code: no library fall-backs, no IEEE division sequences, clamps through
-//     v_max/v_min_f64 instead of selects, one Newton step on the reciprocal / square-root estimates (2e-15 / 4e-15:
+//     v_max/v_min_f64 instead of selects, one Newton step on the reciprocal / square-root estimates (2.2e-15 / 4.2e-15:
 //     the states are integrated to 1e-6), merged reciprocals.  A step attempt is ONE basic block of ~1000 instructions
 //     (the general kernel: 4200 with 75 branches).
 //   * ONE flat loop of step attempts: a rejected step of one lane does not make its 63 neighbours repeat theirs
@@ -26,8 +26,8 @@ namespace vag {
 
 VAG_DEV double vmax(double a, double b) { return __builtin_fmax(a, b); }
 VAG_DEV double vmin(double a, double b) { return __builtin_fmin(a, b); }
-// sqrt(x) to 4e-15 for strictly positive normal x: v_rsq_f64 (5e-8) and one coupled correction, s0 + (y/2)(x - s0^2)
-// (profiles/micro/rsq_accuracy.hip)
+// sqrt(x) to 4.2e-15 for strictly positive normal x: v_rsq_f64 (5e-8) and one coupled correction, s0 + (y/2)(x - s0^2)
+// (tests/test_device_math.py)
 VAG_DEV double sqrt_ode(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     const double s0 = x * y;

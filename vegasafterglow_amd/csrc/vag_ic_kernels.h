@@ -225,15 +225,23 @@ VAG_DEV double ic_thin_correction(const IcQ& q, double lg2_nu, Tab sp) {
         z = q.c2 + q.s2 * lg;
     else if (n > 1 && lg >= q.l1)
         z = q.c1 + q.s1 * lg;
-    // log2(1 + 2^z) without the reference's +-20 softplus shortcut (this term is an exact log2 there)
+    // log2(1 + 2^z) without the reference's +-20 softplus shortcut (this term is an exact log2 there).  Beyond the table, a > 20:
+    // log2(1 + u) = log2(e) (u - u^2 / 2 + u^3 / 3 ...), u = 2^-a, to second order (the first-order form was 6.6e-13 off at a = 20)
     const double a = fabs(z);
-    const double g = a > 20.0 ? exp2_sat(-a) * LOG2E : (sp_fast(-a, sp));
+    double g;
+    if (a > 20.0) {
+        const double u = exp2_sat(-a);
+        g = fma(-0.5 * u, u, u) * LOG2E;
+    } else {
+        g = sp_fast(-a, sp);
+    }
     return q.l1pyc - (0.5 * (z + a) + g);
 }
 
 // IC-corrected synchrotron spectrum (compute_log2_spectrum, smooth-power-law-syn.cpp:80-92) given the thin-branch correction.
-// STRAIGHT: the +-20 softplus shortcuts as selects (sp_fast_sel) -- same values; for a caller whose table sits in global memory, so
-// that the three independent table reads of an evaluation are in flight together instead of one per branch.
+// STRAIGHT: the +-20 softplus shortcuts as selects (sp_fast_sel) -- same values to one rounding of a folded term; for a caller whose
+// table sits in global memory, so that the three independent table reads of an evaluation are in flight together instead of one per
+// branch.
 // HAVE_NU: the caller holds nu = 2^lg2_nu already (a lattice node of vag_ic_photon_kernel) and the cut-off term takes it as it is.
 template <bool STRAIGHT = false, bool HAVE_NU = false, class P1, class Tab>
 VAG_DEV double log2_I_nu_ic_core(const P1 c, int st, bool corrected, const IcQ& q, const SpecConst& sc, double lg2_nu, Tab sp,

@@ -106,8 +106,8 @@ VAG_DEV double sound_speed(double G) {  // compute_sound_speed, shock-physics.h:
     return sqrt(dmax(ad * (ad - 1) * (G - 1) / (1 + (G - 1) * ad), 0.0)) * C_C;
 }
 
-// ---- the same closed forms for the ODE right-hand side: hardware reciprocal / reciprocal square root + one Newton step (2e-15 /
-//      4e-15, vag_dyn_fast.h) instead of the IEEE division (~25 instructions) and square-root (~30) sequences.  The right-hand side
+// ---- the same closed forms for the ODE right-hand side: hardware reciprocal / reciprocal square root + one Newton step (2.2e-15 /
+//      4.2e-15, vag_dyn_fast.h) instead of the IEEE division (~25 instructions) and square-root (~30) sequences.  The right-hand side
 //      of FRShockEqn holds 22 divisions and 8 square roots; the states are integrated to 1e-6.  profiles/r03_pair_stamps.txt: a
 //      step attempt of vag_dynamics_pair_kernel took 50 k cycles with the library forms, two thirds of them these sequences. ----
 VAG_DEV double rcp1(double x) {  // 1/x, x finite, non-zero, normal
