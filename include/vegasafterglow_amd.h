@@ -342,9 +342,9 @@ int vag_flux_density_batch_dev(vag_ctx* ctx, const vag_model_params* d_params, i
  * scales the point-data model fluxes by exp(-A_V * ext_kernel[i]) (fitter.py:512-519). */
 #define VAG_P_A_V 1000
 
-/* Not Model fields either: the sky placement of the centroid groups of vag_loglike_sky_batch (position angle of the projected
- * jet axis +X, measured east of north [rad]; the burst's offset east and north of the reference position [rad]).  Only the
- * centroid entry points accept them. */
+/* Not Model fields either: the sky placement of the centroid groups of vag_loglike_sky_batch and of the visibility groups of
+ * vag_loglike_vis_batch (position angle of the projected jet axis +X, measured east of north [rad]; the burst's offset east and
+ * north of the reference position [rad]).  Only those entry points accept them, with at least one such group. */
 #define VAG_P_SKY_PA 1001
 #define VAG_P_SKY_EAST0 1002
 #define VAG_P_SKY_NORTH0 1003
@@ -435,6 +435,55 @@ int vag_loglike_sky_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_
                           double* out);
 int vag_loglike_sky_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const double* d_theta, int nb,
                               int ndim, double* d_out);
+
+/* One group of VLBI visibilities at one frequency (added after VAG_ABI_VERSION 13, detect by symbol): n_epochs strictly ascending
+ * times, and for every epoch its own list of baselines with the measured complex visibility (ragged: first[]).  The group is its own
+ * request (own grid from its own times).  The model visibility is
+ *   V_mod(u, v) = exp(-2 pi i (u east0 + v north0)) V_sky(u, v; PA, n_az)
+ * with V_sky exactly the Fourier sum of vag_sky_visibility_batch and PA / east0 / north0 the walker's sky placement (VAG_P_SKY_*,
+ * shared with the centroid groups).  kind = VAG_VIS_COMPLEX adds sum_k weight_k |V_obs,k - V_mod,k|^2 / err_k^2 to the walker's
+ * chi^2, kind = VAG_VIS_AMPLITUDE adds sum_k weight_k (re_k - |V_mod,k|)^2 / err_k^2 (east0 / north0 drop out).  Weights are used as
+ * given.  Limits: at most VAG_VIS_MAX_GROUPS groups, VAG_VIS_MAX_EPOCHS epochs per group and VAG_VIS_MAX_PER_EPOCH visibilities per
+ * epoch; more is refused with VAG_E_INVALID. */
+#define VAG_VIS_COMPLEX 0
+#define VAG_VIS_AMPLITUDE 1
+#define VAG_VIS_MAX_GROUPS 64
+#define VAG_VIS_MAX_EPOCHS 4096
+#define VAG_VIS_MAX_PER_EPOCH VAG_SKY_MAX_BASELINES
+typedef struct vag_visibility_obs {
+    double nu;             /* [Hz] */
+    int32_t n_epochs;      /* >= 1 */
+    int32_t n_vis;         /* all epochs together, >= 1 */
+    int32_t n_az;          /* azimuthal parts per circle of the model (vag_sky_visibility_batch); <= 0: 1024 */
+    int32_t kind;          /* VAG_VIS_COMPLEX / VAG_VIS_AMPLITUDE */
+    const double* t;       /* [n_epochs] strictly ascending [s] */
+    const int32_t* first;  /* [n_epochs + 1]: epoch e owns the visibilities first[e] .. first[e + 1] - 1; first[0] = 0,
+                              first[n_epochs] = n_vis, every epoch non-empty */
+    const double* u;       /* [n_vis] east  [wavelengths] */
+    const double* v;       /* [n_vis] north [wavelengths] */
+    const double* re;      /* [n_vis] Re V_obs, or the amplitude (kind = AMPLITUDE); units of vag_flux_density_grid_batch */
+    const double* im;      /* [n_vis] Im V_obs; ignored (may be NULL) for kind = AMPLITUDE */
+    const double* err;     /* [n_vis] > 0: standard deviation of the real and of the imaginary part */
+    const double* weight;  /* [n_vis] >= 0 */
+} vag_visibility_obs;
+
+typedef struct vag_vis_fit_spec {
+    int32_t n_groups;
+    int32_t pad;
+    const vag_visibility_obs* groups; /* [n_groups] */
+} vag_vis_fit_spec;
+
+/* vag_loglike_sky_batch(_dev) with visibility groups: after the flux, band and centroid passes every group of vis runs as its own
+ * pass and adds its chi^2 term (vag_visibility_obs), formed on the device; no visibility leaves it.  sky may be NULL (no centroid
+ * groups, placement 0) or have n_groups = 0 and still supply pa_fixed / east0_fixed / north0_fixed.  Free parameters may take the
+ * slots VAG_P_SKY_* whenever centroid or visibility groups are present.  A walker whose visibility pass fails (grid, ODE rows, SSC
+ * tables) or whose V_mod is not finite at a datum scores -inf; a model with no flux at an epoch is valid (V_mod = 0).  With vis NULL
+ * or n_groups = 0 the call is vag_loglike_sky_batch(_dev), bit for bit.  Results are bitwise reproducible and a walker's value does
+ * not depend on the rest of the batch.  The group data stay resident on the device by content hash. */
+int vag_loglike_vis_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                          const double* theta, int nb, int ndim, double* out);
+int vag_loglike_vis_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                              const double* d_theta, int nb, int ndim, double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

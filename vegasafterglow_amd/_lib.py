@@ -57,7 +57,7 @@ MATH = {name: i for i, name in enumerate([
     "syn_cell", "ic_cell", "wave_prefix_sum", "wave_sum", "sky_wave_sum", "lds_add"])}
 
 P_A_V = 1000  # VAG_P_A_V
-# VAG_P_SKY_*: the sky placement of the centroid groups (vag_loglike_sky_batch), not Model fields either
+# VAG_P_SKY_*: the sky placement of the centroid and visibility groups (vag_loglike_sky_batch / _vis_batch), not Model fields either
 SKY_SLOTS = {"pa": 1001, "east0": 1002, "north0": 1003}
 
 
@@ -69,6 +69,20 @@ class CentroidObs(C.Structure):  # vag_centroid_obs
 class SkyFitSpec(C.Structure):  # vag_sky_fit_spec
     _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(CentroidObs)),
                 ("pa_fixed", C.c_double), ("east0_fixed", C.c_double), ("north0_fixed", C.c_double)]
+
+
+VIS_COMPLEX, VIS_AMPLITUDE = 0, 1  # VAG_VIS_*
+VIS_KINDS = {"complex": VIS_COMPLEX, "amplitude": VIS_AMPLITUDE}
+
+
+class VisibilityObs(C.Structure):  # vag_visibility_obs
+    _fields_ = [("nu", C.c_double), ("n_epochs", C.c_int32), ("n_vis", C.c_int32), ("n_az", C.c_int32), ("kind", C.c_int32),
+                ("t", C.POINTER(C.c_double)), ("first", C.POINTER(C.c_int32))] + \
+               [(n, C.POINTER(C.c_double)) for n in ("u", "v", "re", "im", "err", "weight")]
+
+
+class VisFitSpec(C.Structure):  # vag_vis_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(VisibilityObs))]
 
 
 class FitSpec(C.Structure):
@@ -132,7 +146,7 @@ EXPORTS = [
     "vag_last_model_costs_dev", "vag_loglike_shard_dev", "vag_loglike_shard_finish_dev", "vag_loglike_shard_begin_dev", "vag_loglike_shard_end_dev", "vag_loglike_shard_state_dev", "vag_ctx_profile", "vag_last_profile", "vag_details", "vag_details_rvs", "vag_details_radiation", "vag_details_regime", "vag_details_eat", "vag_profile_eval", "vag_last_stage_times", "vag_last_plan", "vag_ctx_count_work",
     "vag_ctx_coalesce", "vag_ctx_coalesce_stats", "vag_flux_density_grid_coalesced", "vag_flux_density_coalesced", "vag_flux_coalesced",
     "vag_sky_image_batch", "vag_sky_moments_batch", "vag_sky_centroid_batch", "vag_loglike_sky_batch", "vag_loglike_sky_batch_dev",
-    "vag_sky_visibility_batch", "vag_debug_device_math",
+    "vag_sky_visibility_batch", "vag_debug_device_math", "vag_loglike_vis_batch", "vag_loglike_vis_batch_dev",
 ]
 
 _lib = None
@@ -183,6 +197,8 @@ def load():
     lib.vag_debug_device_math.argtypes = [v, C.c_int, _dp, C.c_int, _dp]
     lib.vag_loglike_sky_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), _dp, C.c_int, C.c_int, _dp]
     lib.vag_loglike_sky_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), v, C.c_int, C.c_int, v]
+    lib.vag_loglike_vis_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), _dp, C.c_int, C.c_int, _dp]
+    lib.vag_loglike_vis_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -406,6 +406,7 @@ struct vag_ctx {
     DevBuf d_skyterms, d_skyimg, d_skymom;  // sky images / moments (vag_sky.h): term list, a chunk's images, moments + outside
     DevBuf d_skyvis, d_skyuv;  // visibilities (vag_sky.h): a chunk's row-block partials + combined values, a chunk's baselines
     DevBuf d_skycen, d_skycmom, d_skyfit;  // exact centroids (vag_sky.h): row-block partials, moments, centroid-fit pass data
+    DevBuf d_visfit, d_visblk, d_vispart;  // visibility groups of the likelihood: their data, their 64-visibility blocks, chi^2 partials
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
     bool ic_all_cells = false;    // this request's SSC tables are built for every cell (the lazy selection was caught with a hole, see check_ic_status)
@@ -459,10 +460,19 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit;
+    HostBuf h_fit, h_skyfit, h_visfit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
+    uint64_t visfit_hash = 0;  // (d_visfit / d_visblk: the visibility groups of vag_loglike_vis_batch, upload_vis_spec)
+    size_t visfit_doubles = 0;
+    bool visfit_hash_valid = false;
+    struct VisLayout {  // of one resident group
+        size_t obs_off;              // its data in d_visfit [doubles]: nu | t | u | v | re | im | err | weight
+        int blk_off;                 // its blocks in d_visblk [blocks of 3 ints]
+        std::vector<int> epoch_blk;  // [n_epochs + 1]: first block of every epoch
+    };
+    std::vector<VisLayout> vis_layout;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -696,8 +706,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     c->h_fit.release();
     c->h_skyfit.release();
+    c->h_visfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skycen, &c->d_skycmom, &c->d_skyfit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1894,18 +1905,86 @@ struct SkyVisReq {
     double pa;    // [rad]
     double* vis;  // [nb][nnu][nt][nbl][2] (re, im)
 };
-int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, int nnu, int n_az, double fov, int npixel,
-                double* h_image, double* h_outside, double* h_moments, const SkyVisReq* vr = nullptr) {
-    hipStream_t st = c->stream;
-    struct SkyPass {
-        int e, pass;
-    };
+struct SkyPass {
+    int e, pass;
+};
+static std::vector<SkyPass> sky_passes(const vag_ctx* c) {
     std::vector<SkyPass> passes;
     const int n_em = (c->batch_flags & VAG_FLAG_RVS) ? 2 : 1;
     for (int e = 0; e < n_em; ++e) {
         passes.push_back({e, 0});
         if (c->batch_flags & (e == 0 ? VAG_FLAG_SSC : VAG_FLAG_RVS_SSC)) passes.push_back({e, 1});
     }
+    return passes;
+}
+
+// The terms stage of a sky request: the term list of the times t0 .. t0 + n - 1 of the prepared request (d_lg2t / d_lg2nu) for every
+// pass, [pass][4][nb * nnu * n][R] in d_skyterms (ensured by the caller).  Leaves emitter 0 selected.
+static int sky_terms_stage(vag_ctx* c, const vag_model_params* d_params, int nb, int t0, int n, int nnu, const std::vector<SkyPass>& passes,
+                           int R, int ks) {
+    hipStream_t st = c->stream;
+    const int n_pass = (int)passes.size();
+    const size_t lds = sizeof(double) * ((size_t)SP_LDS_DOUBLES + (size_t)SKY_WAVES * 3 * ks);
+    if (lds > 160 * 1024) return set_err(VAG_E_CAPACITY, "sky image: lattices of %d nodes exceed the terms kernel's LDS", ks);
+    const bool spreading = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
+    const size_t G = (size_t)nb * nnu * n;
+    int rc = VAG_OK;
+    for (int q = 0; q < n_pass && rc == VAG_OK; ++q) {
+        select_emitter(c, passes[q].e, d_params);
+        SkyArgs a{};
+        a.params = c->cur_params;
+        a.meta = c->d_meta.as<VagGridMeta>();
+        a.geo_th = c->d_geo_th.as<double>();
+        a.geo_ph = c->d_geo_ph.as<double>();
+        a.g_rep_of = c->d_rep_of.as<int>();
+        a.cell_off = c->d_cell_off.as<long long>();
+        a.cellpar = c->d_cellpar.as<double>();
+        a.cellq = c->d_cellq.as<double>();
+        a.cellgeo = c->d_cellgeo.as<double>();
+        a.sp_table = c->d_sptab.as<double>();
+        a.lg2_t_obs = c->d_lg2t.as<double>() + t0;
+        a.lg2_nu_obs = c->d_lg2nu.as<double>();
+        a.nt = n;
+        a.nnu = nnu;
+        a.R = R;
+        a.ks = ks;
+        a.terms = c->d_skyterms.as<double>() + (size_t)q * 4 * G * R;
+        const int mode = passes[q].pass == 1 ? FLUX_SSC : (c->cur_ssc ? FLUX_SYN_IC : FLUX_SYN);
+        auto launch = [&](auto kernel) -> int {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipLaunchKernelGGL(kernel, dim3((R + SKY_WAVES - 1) / SKY_WAVES, nb), dim3(64 * SKY_WAVES), lds, st, a);
+            HIPCHK(hipGetLastError());
+            return VAG_OK;
+        };
+        auto terms = [&]() -> int {
+            StageScope ps(c, mode == FLUX_SSC ? PS_SSC_FLUX : PS_SYNC_FLUX);
+            // the table build (re)allocates its buffers: their addresses are taken behind it, at the launch
+            a.ichdr = c->d_ichdr.as<double>();
+            a.icpool = c->d_icpool.as<double>();
+            a.ic_status = c->d_icstatus.as<int>();
+            if (mode == FLUX_SSC)
+                return spreading ? launch(vag_sky_terms_kernel<FLUX_SSC, true>) : launch(vag_sky_terms_kernel<FLUX_SSC, false>);
+            if (mode == FLUX_SYN_IC)
+                return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN_IC, true>) : launch(vag_sky_terms_kernel<FLUX_SYN_IC, false>);
+            return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN, true>) : launch(vag_sky_terms_kernel<FLUX_SYN, false>);
+        };
+        if (mode == FLUX_SSC) {  // the tables clamped to the requested frequencies exactly as a grid call clamps them
+            rc = ssc_attempts(c, nb, [&](bool rebuild) {
+                const int rb = build_ssc_tables(c, c->cur_params, nb, c->d_lg2nu.as<double>(), nnu, rebuild);
+                return rb ? rb : terms();
+            });
+        } else {
+            rc = terms();
+        }
+    }
+    select_emitter(c, 0, d_params);
+    return rc;
+}
+
+int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, int nnu, int n_az, double fov, int npixel,
+                double* h_image, double* h_outside, double* h_moments, const SkyVisReq* vr = nullptr) {
+    hipStream_t st = c->stream;
+    const std::vector<SkyPass> passes = sky_passes(c);
     const int n_pass = (int)passes.size();
     const int R = std::max(1, c->max_pairs), ks = std::max(2, c->max_k);
     const size_t npix2 = h_image ? (size_t)npixel * npixel : 0;
@@ -1915,8 +1994,6 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
     const size_t per_t = sizeof(double) * ((size_t)nb * nnu * ((size_t)n_pass * 4 * R + npix2 + vis_per_image) + (size_t)nnu * nbl * 2);
     int chunk = (int)std::max<size_t>(1, std::min<size_t>(nt, ((size_t)256 << 20) / per_t));
     if (const char* e = vag_hook("VAG_SKY_CHUNK_T")) chunk = std::max(1, std::min(nt, std::atoi(e)));
-    const size_t lds = sizeof(double) * ((size_t)SP_LDS_DOUBLES + (size_t)SKY_WAVES * 3 * ks);
-    if (lds > 160 * 1024) return set_err(VAG_E_CAPACITY, "sky image: lattices of %d nodes exceed the terms kernel's LDS", ks);
     const size_t G_max = (size_t)nb * nnu * chunk;
     if (c->d_skyterms.ensure(sizeof(double) * (size_t)n_pass * 4 * G_max * R)) return VAG_E_HIP;
     if (h_image && c->d_skyimg.ensure(sizeof(double) * G_max * npix2)) return VAG_E_HIP;
@@ -1926,60 +2003,11 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
     if (c->d_skymom.ensure(sizeof(double) * n_bins * 7)) return VAG_E_HIP;
     double* d_mom = c->d_skymom.as<double>();
     double* d_out = d_mom + n_bins * 6;
-    const bool spreading = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
     int rc = VAG_OK;
     for (int t0 = 0; t0 < nt && rc == VAG_OK; t0 += chunk) {
         const int n = std::min(chunk, nt - t0);
         const size_t G = (size_t)nb * nnu * n;
-        for (int q = 0; q < n_pass && rc == VAG_OK; ++q) {
-            select_emitter(c, passes[q].e, d_params);
-            SkyArgs a{};
-            a.params = c->cur_params;
-            a.meta = c->d_meta.as<VagGridMeta>();
-            a.geo_th = c->d_geo_th.as<double>();
-            a.geo_ph = c->d_geo_ph.as<double>();
-            a.g_rep_of = c->d_rep_of.as<int>();
-            a.cell_off = c->d_cell_off.as<long long>();
-            a.cellpar = c->d_cellpar.as<double>();
-            a.cellq = c->d_cellq.as<double>();
-            a.cellgeo = c->d_cellgeo.as<double>();
-            a.sp_table = c->d_sptab.as<double>();
-            a.lg2_t_obs = c->d_lg2t.as<double>() + t0;
-            a.lg2_nu_obs = c->d_lg2nu.as<double>();
-            a.nt = n;
-            a.nnu = nnu;
-            a.R = R;
-            a.ks = ks;
-            a.terms = c->d_skyterms.as<double>() + (size_t)q * 4 * G * R;
-            const int mode = passes[q].pass == 1 ? FLUX_SSC : (c->cur_ssc ? FLUX_SYN_IC : FLUX_SYN);
-            auto launch = [&](auto kernel) -> int {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                hipLaunchKernelGGL(kernel, dim3((R + SKY_WAVES - 1) / SKY_WAVES, nb), dim3(64 * SKY_WAVES), lds, st, a);
-                HIPCHK(hipGetLastError());
-                return VAG_OK;
-            };
-            auto terms = [&]() -> int {
-                StageScope ps(c, mode == FLUX_SSC ? PS_SSC_FLUX : PS_SYNC_FLUX);
-                // the table build (re)allocates its buffers: their addresses are taken behind it, at the launch
-                a.ichdr = c->d_ichdr.as<double>();
-                a.icpool = c->d_icpool.as<double>();
-                a.ic_status = c->d_icstatus.as<int>();
-                if (mode == FLUX_SSC)
-                    return spreading ? launch(vag_sky_terms_kernel<FLUX_SSC, true>) : launch(vag_sky_terms_kernel<FLUX_SSC, false>);
-                if (mode == FLUX_SYN_IC)
-                    return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN_IC, true>) : launch(vag_sky_terms_kernel<FLUX_SYN_IC, false>);
-                return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN, true>) : launch(vag_sky_terms_kernel<FLUX_SYN, false>);
-            };
-            if (mode == FLUX_SSC) {  // the tables clamped to the requested frequencies exactly as a grid call clamps them
-                rc = ssc_attempts(c, nb, [&](bool rebuild) {
-                    const int rb = build_ssc_tables(c, c->cur_params, nb, c->d_lg2nu.as<double>(), nnu, rebuild);
-                    return rb ? rb : terms();
-                });
-            } else {
-                rc = terms();
-            }
-        }
-        select_emitter(c, 0, d_params);
+        rc = sky_terms_stage(c, d_params, nb, t0, n, nnu, passes, R, ks);
         if (rc) break;
         SkyImgArgs b{};
         b.meta = c->d_meta.as<VagGridMeta>();
@@ -2130,6 +2158,49 @@ int centroid_request(vag_ctx* c, const vag_model_params* d_params, int nb, int n
         HIPCHK(hipGetLastError());
     }
     return rc;
+}
+
+// One visibility group of a likelihood call (vag_sky_vis_chi2_kernel); model stages already run on the group's epochs, d_lg2t /
+// d_lg2nu prepared.  The epochs are cut into chunks whose term list stays within 256 MB (VAG_SKY_CHUNK_T: a test's chunk length);
+// every (walker, visibility block) partial is written once, by the chunk of its epoch, so the cut does not change a bit.
+// d_vispart [nb][n_blk][2] afterwards.
+int vis_chi2_request(vag_ctx* c, const vag_model_params* d_params, int nb, const vag_visibility_obs& o, const vag_ctx::VisLayout& lay,
+                     SkyVisFitArgs va) {
+    hipStream_t st = c->stream;
+    const std::vector<SkyPass> passes = sky_passes(c);
+    const int n_pass = (int)passes.size(), nt = o.n_epochs;
+    const int R = std::max(1, c->max_pairs), ks = std::max(2, c->max_k);
+    const size_t per_t = sizeof(double) * (size_t)nb * n_pass * 4 * R;
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>(nt, ((size_t)256 << 20) / per_t));
+    if (const char* e = vag_hook("VAG_SKY_CHUNK_T")) chunk = std::max(1, std::min(nt, std::atoi(e)));
+    if (c->d_skyterms.ensure(per_t * chunk)) return VAG_E_HIP;
+    const int n_blk_all = lay.epoch_blk[nt];
+    if (c->d_vispart.ensure(sizeof(double) * 2 * (size_t)nb * n_blk_all)) return VAG_E_HIP;
+    va.meta = c->d_meta.as<VagGridMeta>();
+    va.phi = c->d_phi.as<double>();
+    va.obs = c->d_visfit.as<double>() + lay.obs_off + 1 + nt;
+    va.blocks = c->d_visblk.as<int>() + 3 * (size_t)lay.blk_off;
+    va.n_vis = o.n_vis;
+    va.n_blk_all = n_blk_all;
+    va.n_pass = n_pass;
+    va.R = R;
+    va.n_az = o.n_az > 0 ? o.n_az : 1024;
+    va.kind = o.kind;
+    va.partial = c->d_vispart.as<double>();
+    for (int t0 = 0; t0 < nt; t0 += chunk) {
+        const int n = std::min(chunk, nt - t0);
+        const int rc = sky_terms_stage(c, d_params, nb, t0, n, 1, passes, R, ks);
+        if (rc) return rc;
+        va.terms = c->d_skyterms.as<double>();
+        va.t0 = t0;
+        va.nt = n;
+        va.blk0 = lay.epoch_blk[t0];
+        va.n_blk = lay.epoch_blk[t0 + n] - va.blk0;
+        if ((size_t)nb * va.n_blk > 0x7fffffffull) return set_err(VAG_E_CAPACITY, "visibility group: too many (walker, visibility block) pairs");
+        hipLaunchKernelGGL(vag_sky_vis_chi2_kernel, dim3((unsigned)((size_t)nb * va.n_blk)), dim3(64), 0, st, va);
+        HIPCHK(hipGetLastError());
+    }
+    return VAG_OK;
 }
 
 // Fixed-order sum of the workgroup partials of a series request.  A workgroup is 64 points x 4 block groups: group g adds the
@@ -3548,21 +3619,8 @@ vag_fit_sky_back_kernel(const double* __restrict__ mom /* [nb][n][6] */, int n, 
                         const int* __restrict__ order) {
     const int m = blockIdx.x, lane = threadIdx.x;
     const int walker = order ? order[m] : m;
-    const int* slot = reinterpret_cast<const int*>(prior + 64);
-    const int* is_log = slot + 16;
     double pa = pa_fixed, e0 = east0_fixed, n0 = north0_fixed;
-    for (int d = 0; d < ndim; ++d) {
-        const int sl = slot[d];
-        if (sl < VAG_P_SKY_PA || sl > VAG_P_SKY_NORTH0) continue;
-        const double v = theta[(size_t)walker * ndim + d];
-        const double val = is_log[d] ? pow(10.0, v) : v;
-        if (sl == VAG_P_SKY_PA)
-            pa = val;
-        else if (sl == VAG_P_SKY_EAST0)
-            e0 = val;
-        else
-            n0 = val;
-    }
+    vag::sky_placement(theta, walker, ndim, prior, pa, e0, n0);
     double sp, cp;
     sincos(pa, &sp, &cp);
     const double *e_obs = obs + n, *n_obs = obs + 2 * (size_t)n, *e_err = obs + 3 * (size_t)n, *n_err = obs + 4 * (size_t)n,
@@ -3599,8 +3657,133 @@ vag_fit_sky_back_kernel(const double* __restrict__ mom /* [nb][n][6] */, int n, 
     }
 }
 
+// ---- visibility groups (vag_loglike_vis_batch): their data in one device buffer, uploaded like the centroid groups when the hash
+//      changes.  Layout in doubles, per group: [nu | t | u | v | re | im | err | weight] (1 + n_epochs + 6 n_vis); in d_visblk, per
+//      group, the blocks of at most 64 visibilities of one epoch as int32 [epoch, first visibility, visibilities]. ----
+static int upload_vis_spec(vag_ctx* c, const vag_vis_fit_spec* vis) {
+    if (vis->n_groups < 0 || !vis->groups) return set_err(VAG_E_INVALID, "bad visibility group list");
+    if (vis->n_groups > VAG_VIS_MAX_GROUPS) return set_err(VAG_E_INVALID, "at most %d visibility groups", VAG_VIS_MAX_GROUPS);
+    uint64_t h = 1469598103934665603ull;
+    h = fnv1a(h, &vis->n_groups, sizeof vis->n_groups);
+    size_t total = 0;
+    for (int g = 0; g < vis->n_groups; ++g) {
+        const vag_visibility_obs& o = vis->groups[g];
+        if (o.n_epochs < 1 || o.n_vis < 1) return set_err(VAG_E_INVALID, "visibility group %d has no observations", g);
+        if (o.n_epochs > VAG_VIS_MAX_EPOCHS) return set_err(VAG_E_INVALID, "visibility group %d: at most %d epochs", g, VAG_VIS_MAX_EPOCHS);
+        if (o.kind != VAG_VIS_COMPLEX && o.kind != VAG_VIS_AMPLITUDE) return set_err(VAG_E_INVALID, "visibility group %d: unknown kind %d", g, o.kind);
+        if (!o.t || !o.first || !o.u || !o.v || !o.re || !o.err || !o.weight || (o.kind == VAG_VIS_COMPLEX && !o.im))
+            return set_err(VAG_E_INVALID, "visibility group %d: null array", g);
+        const int head[4] = {o.n_epochs, o.n_vis, o.n_az > 0 ? o.n_az : 1024, o.kind};
+        h = fnv1a(h, &o.nu, sizeof o.nu);
+        h = fnv1a(h, head, sizeof head);
+        h = fnv1a(h, o.t, sizeof(double) * o.n_epochs);
+        h = fnv1a(h, o.first, sizeof(int32_t) * ((size_t)o.n_epochs + 1));
+        for (const double* arr : {o.u, o.v, o.re, o.kind == VAG_VIS_COMPLEX ? o.im : nullptr, o.err, o.weight})
+            if (arr) h = fnv1a(h, arr, sizeof(double) * o.n_vis);
+        total += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
+    }
+    if (c->visfit_hash_valid && c->visfit_hash == h && c->visfit_doubles == total) return VAG_OK;  // resident already
+    std::vector<vag_ctx::VisLayout> layout(vis->n_groups);
+    std::vector<int> blocks;
+    size_t off = 0;
+    for (int g = 0; g < vis->n_groups; ++g) {
+        const vag_visibility_obs& o = vis->groups[g];
+        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "visibility group %d: frequency must be positive", g);
+        if (o.first[0] != 0 || o.first[o.n_epochs] != o.n_vis)
+            return set_err(VAG_E_INVALID, "visibility group %d: first[0] must be 0 and first[n_epochs] n_vis", g);
+        vag_ctx::VisLayout& lay = layout[g];
+        lay.obs_off = off;
+        lay.blk_off = (int)(blocks.size() / 3);
+        off += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
+        for (int e = 0; e < o.n_epochs; ++e) {
+            if (!(o.t[e] > 0) || !std::isfinite(o.t[e]) || (e > 0 && !(o.t[e] > o.t[e - 1])))
+                return set_err(VAG_E_INVALID, "visibility group %d: times must be positive and strictly ascending", g);
+            const int k0 = o.first[e], k1 = o.first[e + 1];
+            if (k0 < 0 || k1 > o.n_vis || k1 <= k0) return set_err(VAG_E_INVALID, "visibility group %d: epoch %d is empty or first[] is not ascending", g, e);
+            if (k1 - k0 > VAG_VIS_MAX_PER_EPOCH)
+                return set_err(VAG_E_INVALID, "visibility group %d: at most %d visibilities per epoch", g, VAG_VIS_MAX_PER_EPOCH);
+            lay.epoch_blk.push_back((int)(blocks.size() / 3) - lay.blk_off);
+            for (int k = k0; k < k1; k += 64) blocks.insert(blocks.end(), {e, k, std::min(64, k1 - k)});
+        }
+        lay.epoch_blk.push_back((int)(blocks.size() / 3) - lay.blk_off);
+        for (int k = 0; k < o.n_vis; ++k) {
+            if (!std::isfinite(o.u[k]) || !std::isfinite(o.v[k]) || !std::isfinite(o.re[k]) || (o.kind == VAG_VIS_COMPLEX && !std::isfinite(o.im[k])))
+                return set_err(VAG_E_INVALID, "visibility group %d: baselines and visibilities must be finite", g);
+            if (!(o.err[k] > 0) || !std::isfinite(o.err[k])) return set_err(VAG_E_INVALID, "visibility group %d: errors must be positive and finite", g);
+            if (!(o.weight[k] >= 0) || !std::isfinite(o.weight[k])) return set_err(VAG_E_INVALID, "visibility group %d: weights must be finite and >= 0", g);
+        }
+    }
+    c->visfit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    const size_t blk_doubles = (blocks.size() + 1) / 2;  // the int32 blocks ride behind the doubles in the one staging buffer
+    if (c->h_visfit.ensure(sizeof(double) * (total + blk_doubles))) return VAG_E_HIP;
+    if (c->d_visfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
+    if (c->d_visblk.ensure(sizeof(int) * blocks.size())) return VAG_E_HIP;
+    double* hp = c->h_visfit.as<double>();
+    off = 0;
+    for (int g = 0; g < vis->n_groups; ++g) {
+        const vag_visibility_obs& o = vis->groups[g];
+        hp[off++] = o.nu;
+        std::memcpy(hp + off, o.t, sizeof(double) * o.n_epochs);
+        off += o.n_epochs;
+        for (const double* arr : {o.u, o.v, o.re, o.kind == VAG_VIS_COMPLEX ? o.im : nullptr, o.err, o.weight}) {
+            if (arr)
+                std::memcpy(hp + off, arr, sizeof(double) * o.n_vis);
+            else
+                std::memset(hp + off, 0, sizeof(double) * o.n_vis);
+            off += o.n_vis;
+        }
+    }
+    std::memcpy(hp + total, blocks.data(), sizeof(int) * blocks.size());
+    HIPCHK(hipMemcpyAsync(c->d_visfit.p, hp, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_visblk.p, hp + total, sizeof(int) * blocks.size(), hipMemcpyHostToDevice, c->stream));
+    c->vis_layout = std::move(layout);
+    c->visfit_hash = h;
+    c->visfit_doubles = total;
+    c->visfit_hash_valid = true;
+    return VAG_OK;
+}
+
+// The back of one visibility pass, one wavefront per walker (vag_fit_back_kernel's protocol): the walker's block partials in a
+// fixed order (lane-strided, then the wavefront sum), and validity -- finite V_mod at every datum, grid, ODE rows and SSC tables of
+// this pass.  A model with no flux is valid: its V_mod is 0.
+__global__ void __launch_bounds__(64)
+vag_fit_vis_back_kernel(const double* __restrict__ partial /* [nb][n_blk][2] */, int n_blk, const VagGridMeta* __restrict__ meta,
+                        const int* __restrict__ row_status, const int* __restrict__ row_off, const int* __restrict__ ic_status,
+                        double* __restrict__ chi2, int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last,
+                        double* __restrict__ out, int* __restrict__ fitstat, const int* __restrict__ order) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    const bool grid_ok = meta[m].status == 0;
+    double s = 0;
+    bool bad = false;
+    if (grid_ok)
+        for (int i = lane; i < n_blk; i += 64) {
+            const double* p = partial + ((size_t)m * n_blk + i) * 2;
+            s += p[0];
+            bad = bad || p[1] != 0.0;
+        }
+    s = vag::wave_sum(s);
+    if (grid_ok)
+        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad = bad || row_status[r] == 1;
+    const bool any_bad = __any(bad);
+    if (lane == 0) {
+        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
+        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
+        const double acc = first ? s : chi2[m] + s;
+        valid[m] = ok;
+        chi2[m] = acc;
+        if (ic_bad) atomicAdd(fitstat + 1, 1);
+        if (last) {
+            const double lp = ln_prior[m];
+            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
+            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
+            if (!fin) atomicAdd(fitstat, 1);
+        }
+    }
+}
+
 static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec,
-                        const vag_sky_fit_spec* sky = nullptr) {
+                        const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr) {
     int rc = VAG_OK;
     const int n = spec->n_data;
     hipStream_t st = c->stream;
@@ -3634,8 +3817,8 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         order_made = true;
         return nxt.as<int>();
     };
-    const int n_groups = sky ? sky->n_groups : 0;
-    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups;
+    const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = vis ? vis->n_groups : 0;
+    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // the SSC tables of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
     auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext) -> int {
@@ -3709,6 +3892,37 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
             n_inv = std::max(n_inv, c->plan.n_models_invalid);
         }
     }
+    for (int g = 0; g < n_vis_groups && rc == VAG_OK; ++g) {  // visibility groups: one pass each, the chi^2 formed by the chi2 kernel
+        const vag_visibility_obs& o = vis->groups[g];
+        const vag_ctx::VisLayout& lay = c->vis_layout[g];
+        const double* ds = c->d_visfit.as<double>() + lay.obs_off;  // [nu | t | ...]
+        rc = prep_times(c, ds + 1, o.n_epochs, ds, 1);
+        c->order_next = d_order != nullptr;
+        c->last_order = d_order;
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
+        if (rc == VAG_OK) {
+            SkyVisFitArgs va{};
+            va.theta = d_theta;
+            va.prior = d_prior;
+            va.order = d_order;
+            va.ndim = ndim;
+            va.pa_fixed = sky ? sky->pa_fixed : 0.0;
+            va.east0_fixed = sky ? sky->east0_fixed : 0.0;
+            va.north0_fixed = sky ? sky->north0_fixed : 0.0;
+            rc = vis_chi2_request(c, d_params, nb, o, lay, va);
+        }
+        if (rc == VAG_OK) {
+            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
+            hipLaunchKernelGGL(vag_fit_vis_back_kernel, dim3(nb), dim3(64), 0, st, c->d_vispart.as<double>(), lay.epoch_blk[o.n_epochs],
+                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
+                               (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
+                               pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order);
+            HIPCHK(hipGetLastError());
+            ++pass;
+            n_cap = std::max(n_cap, c->plan.n_models_capacity);
+            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+        }
+    }
     c->ic_soft_fail = false;
     c->plan.n_models_capacity = n_cap;
     c->plan.n_models_invalid = n_inv;
@@ -3753,6 +3967,28 @@ int vag_loglike_sky_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
     }
     rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky);
     if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky);
+    return rc;
+}
+
+int vag_loglike_vis_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                              const double* d_theta, int nb, int ndim, double* d_out) {
+    if (!vis || vis->n_groups == 0) return vag_loglike_sky_batch_dev(c, spec, sky, d_theta, nb, ndim, d_out);  // exactly that call
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    HIPCHK(hipSetDevice(c->device));
+    int rc = upload_fit_spec(c, spec, ndim, true);
+    if (rc) return rc;
+    if (sky) {  // (n_groups = 0: the fixed placement alone)
+        rc = upload_sky_spec(c, sky);
+        if (rc) return rc;
+    }
+    rc = upload_vis_spec(c, vis);
+    if (rc) return rc;
+    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis);
+    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis);
     return rc;
 }
 
@@ -4043,6 +4279,26 @@ int vag_loglike_sky_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fi
     double* d_out = d_theta + (size_t)nb * ndim;
     HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
     int rc = vag_loglike_sky_batch_dev(c, spec, sky, d_theta, nb, ndim, d_out);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)collect_times(c);
+    return VAG_OK;
+}
+
+int vag_loglike_vis_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                          const double* theta, int nb, int ndim, double* out) {
+    if (!vis || vis->n_groups == 0) return vag_loglike_sky_batch(c, spec, sky, theta, nb, ndim, out);  // exactly that call
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
+    double* d_theta = c->d_theta_in.as<double>();
+    double* d_out = d_theta + (size_t)nb * ndim;
+    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
+    int rc = vag_loglike_vis_batch_dev(c, spec, sky, vis, d_theta, nb, ndim, d_out);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -438,6 +438,139 @@ __global__ void __launch_bounds__(256) vag_sky_visibility_combine(const VagGridM
     vis[2 * i + 1] = im;
 }
 
+// ---- visibility groups of the likelihood (vag_loglike_vis_batch): the chi^2 of a walker's visibilities, formed in registers ----
+//   vag_sky_vis_chi2_kernel   one wavefront per (walker, block of <= 64 visibilities of ONE epoch), lane = visibility: the walker's
+//                             own placement from theta, the passes, rows and parts of vag_sky_visibility_kernel in its order (row
+//                             blocks of SKYV_ROWS summed on their own, then added in block order, as its combine does), the
+//                             baseline-independent part of every azimuthal part (sincos phi, X, Y) formed once per wavefront -- lanes
+//                             over parts -- and broadcast by v_readlane, then the residual against the datum and a fixed-order sum
+//                             over the wavefront -> one partial chi^2 and one not-finite flag per (walker, visibility block)
+// The wavefront walks all rows of its walker: no row-block partials, no V in HBM, and the value depends on the walker alone.
+
+// The walker's sky placement: free parameters with the slots VAG_P_SKY_*, else the fixed values.
+VAG_DEV void sky_placement(const double* __restrict__ theta, int walker, int ndim, const double* __restrict__ prior, double& pa,
+                           double& e0, double& n0) {
+    const int* slot = reinterpret_cast<const int*>(prior + 64);
+    const int* is_log = slot + 16;
+    for (int d = 0; d < ndim; ++d) {
+        const int sl = slot[d];
+        if (sl < VAG_P_SKY_PA || sl > VAG_P_SKY_NORTH0) continue;
+        const double v = theta[(size_t)walker * ndim + d];
+        const double val = is_log[d] ? pow(10.0, v) : v;
+        pa = sl == VAG_P_SKY_PA ? val : pa;  // (selects: an if chain becomes an indexed store to scratch)
+        e0 = sl == VAG_P_SKY_EAST0 ? val : e0;
+        n0 = sl == VAG_P_SKY_NORTH0 ? val : n0;
+    }
+}
+
+// lane j's value in every lane (j wave-uniform)
+VAG_DEV double wave_bcast(double v, int j) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
+}
+
+struct SkyVisFitArgs {
+    const VagGridMeta* meta;
+    const double* phi;     // [nb][ph_stride]
+    const double* terms;   // the term list of this chunk of epochs: [pass][4][nb * nt][R]
+    const double* theta;   // [nb][ndim] sampler space
+    const double* prior;   // the fit spec's prior block (slot map behind it)
+    const int* order;      // evaluation slot -> walker, or null
+    const double* obs;     // the group's [u | v | re | im | err | weight], n_vis each
+    const int* blocks;     // [n_blk_all][3]: epoch, first visibility, visibilities (<= 64) of every block, epochs ascending
+    double pa_fixed, east0_fixed, north0_fixed;
+    int ndim, n_vis, n_blk_all;
+    int blk0, n_blk;  // the blocks of this chunk's epochs
+    int t0, nt;       // this chunk's epochs t0 .. t0 + nt - 1
+    int n_pass, R, n_az, kind;
+    double* partial;  // [nb][n_blk_all][2]: chi^2 of the block, 1.0 when a V_mod of the block is not finite
+};
+
+__global__ void __launch_bounds__(64) vag_sky_vis_chi2_kernel(SkyVisFitArgs a) {
+    const int lane = threadIdx.x;
+    const int m = blockIdx.x / a.n_blk, blk = a.blk0 + (int)(blockIdx.x - (unsigned)m * a.n_blk);
+    const int nb = gridDim.x / a.n_blk;
+    const int e = a.blocks[3 * blk], k0 = a.blocks[3 * blk + 1], cnt = a.blocks[3 * blk + 2];
+    const int g = m * a.nt + (e - a.t0);  // image of the chunk
+    const VagGridMeta& M = a.meta[m];
+    const int n_rows = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    const double* phi = a.phi + (size_t)m * M.ph_stride;
+    const size_t G = (size_t)nb * a.nt, plane = G * a.R;
+    const bool live = lane < cnt;
+    const int k = live ? k0 + lane : k0;
+    const size_t nv = (size_t)a.n_vis;
+    const double u = a.obs[k], v = a.obs[nv + k];
+    double pa = a.pa_fixed, e0 = a.east0_fixed, n0 = a.north0_fixed;
+    sky_placement(a.theta, a.order ? a.order[m] : m, a.ndim, a.prior, pa, e0, n0);
+    double spa, cpa;
+    sincos(pa, &spa, &cpa);
+    double re = 0, im = 0, re_b = 0, im_b = 0;
+    auto add = [&](double w, double X, double Y) {  // vag_sky_visibility_kernel's
+        const double east = X * spa + Y * cpa, north = X * cpa - Y * spa;
+        double sn, cs;
+        sincospi(2 * (u * east + v * north), &sn, &cs);
+        re_b += w * cs;
+        im_b -= w * sn;
+    };
+#pragma unroll 1
+    for (int r0 = 0; r0 < n_rows; r0 += SKYV_ROWS) {
+        const int r1 = min(n_rows, r0 + SKYV_ROWS);
+        re_b = 0, im_b = 0;
+#pragma unroll 1
+        for (int pass = 0; pass < a.n_pass; ++pass) {
+            const double* T = a.terms + (size_t)pass * 4 * plane + (size_t)g * a.R;
+#pragma unroll 1
+            for (int p = r0; p < r1; ++p) {  // wave-uniform: every lane reads the same term
+                const double w = T[p];
+                if (!(w > 0)) continue;
+                const double ca = T[plane + p], cb = T[2 * plane + p], cc = T[3 * plane + p];
+                const SkyBin b = sky_bin(M, phi, p, a.n_az);
+                const double part = w / b.S, dphi = b.width / b.S;
+                const double wp = b.mirrored ? 0.5 * part : part;
+#pragma unroll 1
+                for (int q0 = 0; q0 < b.S; q0 += 64) {
+                    const double ph = b.left + ((q0 + lane) + 0.5) * dphi;  // lane = part: vag_sky_deposit_kernel's part
+                    double sn, cs;
+                    sincos(ph, &sn, &cs);
+                    const double X = ca - cb * cs, Y = cc * sn;
+                    const int nq = min(64, b.S - q0);
+#pragma unroll 1
+                    for (int j = 0; j < nq; ++j) {  // lane = visibility again: the parts in order
+                        const double Xj = wave_bcast(X, j), Yj = wave_bcast(Y, j);
+                        add(wp, Xj, Yj);
+                        if (b.mirrored) add(wp, Xj, -Yj);
+                    }
+                }
+            }
+        }
+        re += re_b;
+        im += im_b;
+    }
+    double term = 0;
+    bool bad = false;
+    if (live) {
+        const double o_re = a.obs[2 * nv + k], err = a.obs[4 * nv + k], wk = a.obs[5 * nv + k];
+        bad = !isfinite(re) || !isfinite(im);
+        double r2;
+        if (a.kind == VAG_VIS_AMPLITUDE) {
+            const double d = o_re - hypot(re, im);
+            r2 = d * d;
+        } else {
+            double sn, cs;  // exp(-2 pi i (u east0 + v north0))
+            sincospi(-2 * (u * e0 + v * n0), &sn, &cs);
+            const double dr = o_re - (re * cs - im * sn), di = a.obs[3 * nv + k] - (re * sn + im * cs);
+            r2 = dr * dr + di * di;
+        }
+        term = wk * r2 / (err * err);
+    }
+    term = wave_sum(term);
+    const bool any_bad = __any(bad);
+    if (lane == 0) {
+        double* o = a.partial + ((size_t)m * a.n_blk_all + blk) * 2;
+        o[0] = term;
+        o[1] = any_bad ? 1.0 : 0.0;
+    }
+}
+
 // ---- exact centroids (vag_sky_centroid_batch and the likelihood's centroid groups): no term list, no azimuthal parts ----
 //   vag_sky_centroid_kernel   one (theta, phi) row per lane, 64 rows per wavefront: the row's EAT logs, bracket and boundary spectra
 //                             with vag_sky_terms_kernel's expressions, the term (w, a, b, c), its exact moments over the row's phi bin

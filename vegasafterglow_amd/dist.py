@@ -17,6 +17,8 @@ import torch.distributed as dist
 
 _NO_CENTROIDS = ("sharded likelihood calls do not support centroid data (Fitter.add_centroid): evaluate on one device "
                  "(Fitter.device_evaluator / log_prob_batch)")
+_NO_VISIBILITIES = ("sharded likelihood calls do not support visibility data (Fitter.add_visibilities): evaluate on one "
+                    "device (Fitter.device_evaluator / log_prob_batch)")
 
 
 def shard_range(n, rank, world):
@@ -87,6 +89,8 @@ class WalkerSharder:
     def __init__(self, eval_dev, group=None, device=None):
         if getattr(eval_dev, "has_centroids", False):
             raise NotImplementedError(_NO_CENTROIDS)
+        if getattr(eval_dev, "has_visibilities", False):
+            raise NotImplementedError(_NO_VISIBILITIES)
         self.eval_dev, self.group = eval_dev, group
         self.device = device if device is not None else _default_device(group)
         self.native = getattr(eval_dev, "native", None)
@@ -183,6 +187,8 @@ def sharded_loglike(samples, local_eval, group=None, device=None):
     """
     if getattr(getattr(local_eval, "__self__", None), "has_centroids", False):
         raise NotImplementedError(_NO_CENTROIDS)
+    if getattr(getattr(local_eval, "__self__", None), "has_visibilities", False):
+        raise NotImplementedError(_NO_VISIBILITIES)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     nb = samples.shape[0]
     if not (dist.is_available() and dist.is_initialized()):

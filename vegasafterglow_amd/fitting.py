@@ -167,6 +167,7 @@ class Fitter:
         self._point_t, self._point_nu, self._point_flux, self._point_err, self._point_weights = [], [], [], [], []
         self._band_obs = []
         self._centroid_obs = []  # VLBI centroid groups (add_centroid): one vag_centroid_obs each
+        self._vis_obs = []  # VLBI visibility groups (add_visibilities): one vag_visibility_obs each
         self._ext_kernel = None
         self._ext_kernels = {}  # z -> 0.4 ln10 k(lambda_rest) over the consolidated point data
         self._ext_z = float(z)
@@ -287,13 +288,66 @@ class Fitter:
     def has_centroids(self):
         return bool(self._centroid_obs)
 
+    def add_visibilities(self, nu, t, u, v, vis, err, weights=None, n_az=None, kind="complex"):
+        """VLBI visibilities at one frequency nu [Hz]: flat arrays with one entry per visibility -- time t [s] (ascending; runs of
+        equal t are the epochs, each with its own baselines), baseline u (east) and v (north) [wavelengths], the measured complex
+        visibility ``vis`` [erg cm^-2 s^-1 Hz^-1] and ``err``, the standard deviation of its real and of its imaginary part.  The
+        group is its own request: the model visibility is Model.sky_visibilities(t, nu, u, v, pa, n_az) times
+        exp(-2 pi i (u east0 + v north0)), placed by the parameters "pa", "east0" and "north0" (free or fixed; 0 when not given;
+        shared with the centroid groups), and adds sum_k w_k |vis_k - V_mod,k|^2 / err_k^2 to chi^2.  kind="amplitude" is for data
+        without usable phases: ``vis`` holds real amplitudes and the term is sum_k w_k (vis_k - |V_mod,k|)^2 / err_k^2.  n_az:
+        azimuthal parts per circle of the model (default 1024, Model.sky_visibilities' own; a smaller value makes the fit cheaper
+        at the accuracy INTEGRATION.md states).  Weights are used as given."""
+        who = "add_visibilities"
+        nu = float(np.asarray(nu, dtype=np.float64)) if np.ndim(nu) == 0 else None
+        if nu is None or not np.isfinite(nu) or nu <= 0:
+            raise ValueError(f"{who}: nu must be one finite frequency > 0")
+        if kind not in _lib.VIS_KINDS:
+            raise ValueError(f"{who}: kind must be 'complex' or 'amplitude', got {kind!r}")
+        if n_az is not None and (int(n_az) != n_az or n_az < 1):
+            raise ValueError(f"{who}: n_az must be an integer >= 1 (or None for 1024), got {n_az!r}")
+        vis = np.asarray(vis)
+        if kind == "amplitude":
+            if np.iscomplexobj(vis):
+                raise ValueError(f"{who}: kind='amplitude' takes real amplitudes, got complex data")
+            vis = vis.astype(np.float64)
+        else:
+            vis = vis.astype(np.complex128)
+        t, u, v, err = (np.asarray(a, dtype=np.float64) for a in (t, u, v, err))
+        if t.ndim != 1 or t.size == 0:
+            raise ValueError(f"{who}: t must be a non-empty 1-D array")
+        if any(a.shape != t.shape for a in (u, v, vis, err)):
+            raise ValueError(f"{who}: t, u, v, vis, err must have the same shape; got {[a.shape for a in (t, u, v, vis, err)]}")
+        if not all(np.isfinite(a).all() for a in (t, u, v, vis, err)):
+            raise ValueError(f"{who}: t, baselines, visibilities and errors must be finite")
+        if (t <= 0).any() or (np.diff(t) < 0).any():
+            raise ValueError(f"{who}: times must be > 0 and ascending")
+        if (err <= 0).any():
+            raise ValueError(f"{who}: err must be > 0 at every visibility")
+        if weights is None:
+            w = np.ones_like(t)
+        else:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape != t.shape or not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError(f"{who}: weights must have the shape of t and be finite and >= 0")
+        starts = np.concatenate(([0], np.nonzero(np.diff(t) > 0)[0] + 1))  # runs of equal t are the epochs
+        first = np.ascontiguousarray(np.concatenate((starts, [t.size])), dtype=np.int32)
+        c = np.ascontiguousarray
+        self._vis_obs.append(dict(nu=nu, t=c(t[starts]), first=first, u=c(u), v=c(v), re=c(vis.real), err=c(err), weights=c(w),
+                                  im=c(vis.imag) if kind == "complex" else None, n_az=None if n_az is None else int(n_az),
+                                  kind=kind))
+
+    @property
+    def has_visibilities(self):
+        return bool(self._vis_obs)
+
     # fitter.py:407-451
     def _consolidate_data(self):
         if self._all_t is not None:
             return
         if not self._point_t:
-            if not self._band_obs and not self._centroid_obs:
-                raise ValueError("no data: call add_flux_density, add_flux or add_centroid first")
+            if not self._band_obs and not self._centroid_obs and not self._vis_obs:
+                raise ValueError("no data: call add_flux_density, add_flux, add_centroid or add_visibilities first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
             return
         t = np.concatenate(self._point_t)
@@ -387,9 +441,12 @@ class Fitter:
                 spec.slot[d] = _lib.PARAM_SLOTS[pd.name]
             spec.is_log[d] = 1 if pd.scale is Scale.log else 0
         spec.a_v_fixed = float(fixed.get("A_V", 0.0))
-        if any(pd.name in _lib.SKY_SLOTS for pd in param_defs) and not self._centroid_obs:
-            raise ValueError("the parameters 'pa', 'east0' and 'north0' need centroid data (Fitter.add_centroid)")
-        spec._sky = self._sky_spec(fixed) if self._centroid_obs else None
+        if any(pd.name in _lib.SKY_SLOTS for pd in param_defs) and not self._centroid_obs and not self._vis_obs:
+            raise ValueError("the parameters 'pa', 'east0' and 'north0' need centroid data (Fitter.add_centroid) or visibility "
+                             "data (Fitter.add_visibilities)")
+        # (a fit with visibility groups only still carries the fixed placement in a vag_sky_fit_spec without groups)
+        spec._sky = self._sky_spec(fixed) if self._centroid_obs or self._vis_obs else None
+        spec._vis = self._vis_spec() if self._vis_obs else None
         if self.extinction is not None and any(pd.name == "z" for pd in free):
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
@@ -438,7 +495,7 @@ class Fitter:
     def _sky_spec(self, fixed):
         """vag_sky_fit_spec of the centroid groups; it keeps the arrays it points at alive."""
         sky = _lib.SkyFitSpec()
-        groups = (_lib.CentroidObs * len(self._centroid_obs))()
+        groups = (_lib.CentroidObs * max(len(self._centroid_obs), 1))()
         for g, cd in enumerate(self._centroid_obs):
             o = groups[g]
             o.nu, o.n = cd["nu"], cd["t"].size
@@ -449,6 +506,49 @@ class Fitter:
         sky.pa_fixed, sky.east0_fixed, sky.north0_fixed = (float(fixed.get(k, 0.0)) for k in ("pa", "east0", "north0"))
         sky._keep_alive = (groups, list(self._centroid_obs))
         return sky
+
+    def _vis_spec(self):
+        """vag_vis_fit_spec of the visibility groups; it keeps the arrays it points at alive."""
+        vis = _lib.VisFitSpec()
+        groups = (_lib.VisibilityObs * len(self._vis_obs))()
+        for g, vd in enumerate(self._vis_obs):
+            o = groups[g]
+            o.nu, o.n_epochs, o.n_vis = vd["nu"], vd["t"].size, vd["u"].size
+            o.n_az, o.kind = vd["n_az"] or 0, _lib.VIS_KINDS[vd["kind"]]
+            o.first = vd["first"].ctypes.data_as(C.POINTER(C.c_int32))
+            for name in ("t", "u", "v", "re", "err"):
+                setattr(o, name, vd[name].ctypes.data_as(_dp))
+            o.im = vd["im"].ctypes.data_as(_dp) if vd["im"] is not None else None
+            o.weight = vd["weights"].ctypes.data_as(_dp)
+        vis.n_groups, vis.groups = len(self._vis_obs), groups
+        vis._keep_alive = (groups, list(self._vis_obs))
+        return vis
+
+    def visibilities(self, best_params, param_defs, resolution=None):
+        """The model visibilities at the data of every visibility group at a point of sampler space: a list of complex128 arrays,
+        one per group, in the order and layout the data were added.  Each group is one Model.sky_visibilities request at the
+        group's epochs, frequency and n_az with the walker's pa; the phase of east0 / north0 is applied on the host."""
+        spec, _, _ = self.build_spec(param_defs)
+        sample = np.asarray(best_params, dtype=np.float64).reshape(-1)
+        place = dict(pa=spec._sky.pa_fixed, east0=spec._sky.east0_fixed, north0=spec._sky.north0_fixed) if spec._sky is not None \
+            else dict(pa=0.0, east0=0.0, north0=0.0)
+        by_slot = {slot: name for name, slot in _lib.SKY_SLOTS.items()}
+        for d in range(spec.ndim):
+            if spec.slot[d] in by_slot:
+                place[by_slot[spec.slot[d]]] = 10.0 ** sample[d] if spec.is_log[d] else sample[d]
+        model = self.model(best_params, param_defs, resolution)
+        out = []
+        for vd in self._vis_obs:
+            first, ne = vd["first"], vd["t"].size
+            nbl = int(np.diff(first).max())
+            u, v = np.zeros((1, ne, nbl)), np.zeros((1, ne, nbl))  # the ragged epochs padded to a rectangle
+            for e in range(ne):
+                n = first[e + 1] - first[e]
+                u[0, e, :n], v[0, e, :n] = vd["u"][first[e]:first[e + 1]], vd["v"][first[e]:first[e + 1]]
+            rect = model.sky_visibilities(vd["t"], np.array([vd["nu"]]), u, v, pa=place["pa"], n_az=vd["n_az"])[0]
+            flat = np.concatenate([rect[e, :first[e + 1] - first[e]] for e in range(ne)])
+            out.append(flat * np.exp(-2j * np.pi * (vd["u"] * place["east0"] + vd["v"] * place["north0"])))
+        return out
 
     # fitting/params.py validate_parameters: the checks that do not depend on the sampler
     def validate_parameters(self, param_defs: Sequence[ParamDef]) -> None:
@@ -568,7 +668,10 @@ class Fitter:
             costs = torch.empty((k,), dtype=torch.float64, device=dev) if want_costs else None
 
             def run():
-                if keep[0]._sky is not None:
+                if keep[0]._vis is not None:
+                    _lib.check(lib.vag_loglike_vis_batch_dev(h, C.byref(keep[0]), C.byref(keep[0]._sky), C.byref(keep[0]._vis),
+                                                             theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
+                elif keep[0]._sky is not None:
                     _lib.check(lib.vag_loglike_sky_batch_dev(h, C.byref(keep[0]), C.byref(keep[0]._sky), theta.data_ptr(), k,
                                                              keep[0].ndim, values.data_ptr()))
                 else:
@@ -578,7 +681,8 @@ class Fitter:
             _on_current_stream(run)
             return values, costs
         eval_dev.optional_costs = True
-        eval_dev.has_centroids = spec._sky is not None
+        eval_dev.has_centroids = spec._sky is not None and spec._sky.n_groups > 0
+        eval_dev.has_visibilities = spec._vis is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -589,6 +693,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._vis is not None:
+                    from .dist import _NO_VISIBILITIES
+                    raise NotImplementedError(_NO_VISIBILITIES)
                 if keep[0]._sky is not None:
                     from .dist import _NO_CENTROIDS
                     raise NotImplementedError(_NO_CENTROIDS)
@@ -617,7 +724,11 @@ class Fitter:
         h, lock = get_context(self.device)
         plan = _lib.Plan()
         with lock:
-            if spec._sky is not None:
+            if spec._vis is not None:
+                _lib.check(_lib.load().vag_loglike_vis_batch(h, C.byref(spec), C.byref(spec._sky), C.byref(spec._vis),
+                                                             samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
+                                                             out.ctypes.data_as(_dp)))
+            elif spec._sky is not None:
                 _lib.check(_lib.load().vag_loglike_sky_batch(h, C.byref(spec), C.byref(spec._sky), samples.ctypes.data_as(_dp),
                                                              samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
             else:
