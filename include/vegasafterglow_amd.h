@@ -243,6 +243,31 @@ int vag_sky_centroid_batch(vag_ctx* ctx, const vag_model_params* params, int nb,
 int vag_sky_visibility_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
                              const double* u, const double* v, int nbl, double pa, int n_az, double* vis);
 
+/* Linear polarization of the same parts ("Polarization"; the engine's own definition).  Added after
+ * VAG_ABI_VERSION 13 (detect by symbol).  A random magnetic field, axially symmetric about the shock normal (taken as the radial
+ * direction), of anisotropy b = 2 <B_par^2> / <B_perp^2> (0: in the shock plane, 1: isotropic): a part seen at the fluid-frame
+ * angle theta' from the normal, s = sin^2 theta' = (1 - mu^2) / (Gamma - u mu)^2, is polarized by
+ * Pi = pi_max (b - 1) s / (2 + (b - 1) s) along (Pi < 0) or across (Pi > 0) the projected normal psi = atan2(Y, X):
+ * Q = -Pi w cos 2 psi, U = -Pi w sin 2 psi.  SSC passes are unpolarized.  Index 0: forward shock, 1: reverse shock; b finite and
+ * >= 0; pi_max <= 1, pi_max < 0: (p + 1) / (p + 7/3) with that shock's own p.  One spec per model. */
+typedef struct vag_pol_spec {
+    double b[2];
+    double pi_max[2];
+} vag_pol_spec;
+
+/* Integrated Stokes parameters, out [nb][nnu][nt][3]: I (= flux_density_grid up to summation order), Q, U on the sky with +X at
+ * position angle pa [rad] east of north: Q_sky = Q cos 2pa - U sin 2pa, U_sky = Q sin 2pa + U cos 2pa, so 1/2 atan2(U, Q) is the
+ * IAU polarization angle.  On a mirrored grid the jet-frame U is exactly 0.  n_az <= 0: 256.  Results are bitwise reproducible and
+ * do not depend on the rest of the batch. */
+int vag_sky_polarization_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu,
+                               int nnu, const vag_pol_spec* pol, double pa, int n_az, double* out);
+
+/* Stokes maps on the pixel grid of vag_sky_image_batch, in the jet frame: image [nb][nnu][nt][3][npixel][npixel] (I, Q, U; the I
+ * map is bit for bit vag_sky_image_batch's image), outside [nb][nnu][nt][3] (NULL: not wanted) the Stokes sums of the parts outside
+ * the image.  fov, npixel, n_az as vag_sky_image_batch. */
+int vag_sky_stokes_image_batch(vag_ctx* ctx, const vag_model_params* params, int nb, const double* t, int nt, const double* nu,
+                               int nnu, const vag_pol_spec* pol, double fov, int npixel, int n_az, double* image, double* outside);
+
 /* Test-facing: evaluates device routine `fn` (VAG_MATH_*) of this library on n points, on the device, with the context's own
  * softplus / log2 tables.  in: [n][n_in(fn)], out: [n][n_out(fn)].  Added after VAG_ABI_VERSION 13 (detect by symbol).
  * n_in = n_out = 1 for the elementwise routines (the sp_fast forms take z and give log2(1 + 2^z)), except:

@@ -81,6 +81,10 @@ class VisibilityObs(C.Structure):  # vag_visibility_obs
                [(n, C.POINTER(C.c_double)) for n in ("u", "v", "re", "im", "err", "weight")]
 
 
+class PolSpec(C.Structure):  # vag_pol_spec: index 0 forward, 1 reverse shock; pi_max < 0: the default from p
+    _fields_ = [("b", C.c_double * 2), ("pi_max", C.c_double * 2)]
+
+
 class VisFitSpec(C.Structure):  # vag_vis_fit_spec
     _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(VisibilityObs))]
 
@@ -147,6 +151,7 @@ EXPORTS = [
     "vag_ctx_coalesce", "vag_ctx_coalesce_stats", "vag_flux_density_grid_coalesced", "vag_flux_density_coalesced", "vag_flux_coalesced",
     "vag_sky_image_batch", "vag_sky_moments_batch", "vag_sky_centroid_batch", "vag_loglike_sky_batch", "vag_loglike_sky_batch_dev",
     "vag_sky_visibility_batch", "vag_debug_device_math", "vag_loglike_vis_batch", "vag_loglike_vis_batch_dev",
+    "vag_sky_polarization_batch", "vag_sky_stokes_image_batch",
 ]
 
 _lib = None
@@ -194,6 +199,9 @@ def load():
     lib.vag_sky_moments_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp]
     lib.vag_sky_centroid_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp]
     lib.vag_sky_visibility_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_int, _dp]
+    lib.vag_sky_polarization_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.POINTER(PolSpec), C.c_double, C.c_int, _dp]
+    lib.vag_sky_stokes_image_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.POINTER(PolSpec), C.c_double, C.c_int,
+                                               C.c_int, _dp, _dp]
     lib.vag_debug_device_math.argtypes = [v, C.c_int, _dp, C.c_int, _dp]
     lib.vag_loglike_sky_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), _dp, C.c_int, C.c_int, _dp]
     lib.vag_loglike_sky_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), v, C.c_int, C.c_int, v]

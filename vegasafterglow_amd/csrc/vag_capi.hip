@@ -404,6 +404,7 @@ struct vag_ctx {
     // as its own output lattice; offsets handed out by vag_ic_plan_kernel, d_icused counts the doubles in use)
     DevBuf d_ichdr, d_icplan, d_icpool, d_icused, d_icslow /* records of the cells on the spectrum kernel's slow path */;
     DevBuf d_skyterms, d_skyimg, d_skymom;  // sky images / moments (vag_sky.h): term list, a chunk's images, moments + outside
+    DevBuf d_skypol, d_skystokes;  // polarization (vag_sky.h): a chunk's row-block partials, the models' spec + Stokes sums + outside
     DevBuf d_skyvis, d_skyuv;  // visibilities (vag_sky.h): a chunk's row-block partials + combined values, a chunk's baselines
     DevBuf d_skycen, d_skycmom, d_skyfit;  // exact centroids (vag_sky.h): row-block partials, moments, centroid-fit pass data
     DevBuf d_visfit, d_visblk, d_vispart;  // visibility groups of the likelihood: their data, their 64-visibility blocks, chi^2 partials
@@ -708,7 +709,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_skyfit.release();
     c->h_visfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1905,6 +1906,15 @@ struct SkyVisReq {
     double pa;    // [rad]
     double* vis;  // [nb][nnu][nt][nbl][2] (re, im)
 };
+// Polarization of a sky request: Stokes sums on the sky and / or Stokes maps (then h_image of sky_request is null and fov, npixel are
+// the maps').  spec: host [nb][4], b - 1 of the forward and reverse shock, then their Pi_max, defaults resolved.
+struct SkyPolReq {
+    const double* spec;
+    double pa;
+    double* stokes;   // [nb][nnu][nt][3] I, Q, U on the sky, or null
+    double* image;    // [nb][nnu][nt][3][npixel^2] in the jet frame, or null
+    double* outside;  // [nb][nnu][nt][3] in the jet frame, or null
+};
 struct SkyPass {
     int e, pass;
 };
@@ -1919,9 +1929,10 @@ static std::vector<SkyPass> sky_passes(const vag_ctx* c) {
 }
 
 // The terms stage of a sky request: the term list of the times t0 .. t0 + n - 1 of the prepared request (d_lg2t / d_lg2nu) for every
-// pass, [pass][4][nb * nnu * n][R] in d_skyterms (ensured by the caller).  Leaves emitter 0 selected.
+// pass, [pass][4][nb * nnu * n][R] in d_skyterms (ensured by the caller).  d_pol: also the polarization list [pass][3][nb * nnu * n][R]
+// (the synchrotron passes' slices only; an SSC pass is unpolarized).  Leaves emitter 0 selected.
 static int sky_terms_stage(vag_ctx* c, const vag_model_params* d_params, int nb, int t0, int n, int nnu, const std::vector<SkyPass>& passes,
-                           int R, int ks) {
+                           int R, int ks, double* d_pol = nullptr) {
     hipStream_t st = c->stream;
     const int n_pass = (int)passes.size();
     const size_t lds = sizeof(double) * ((size_t)SP_LDS_DOUBLES + (size_t)SKY_WAVES * 3 * ks);
@@ -1949,6 +1960,7 @@ static int sky_terms_stage(vag_ctx* c, const vag_model_params* d_params, int nb,
         a.R = R;
         a.ks = ks;
         a.terms = c->d_skyterms.as<double>() + (size_t)q * 4 * G * R;
+        a.pol = d_pol ? d_pol + (size_t)q * 3 * G * R : nullptr;
         const int mode = passes[q].pass == 1 ? FLUX_SSC : (c->cur_ssc ? FLUX_SYN_IC : FLUX_SYN);
         auto launch = [&](auto kernel) -> int {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1964,6 +1976,12 @@ static int sky_terms_stage(vag_ctx* c, const vag_model_params* d_params, int nb,
             a.ic_status = c->d_icstatus.as<int>();
             if (mode == FLUX_SSC)
                 return spreading ? launch(vag_sky_terms_kernel<FLUX_SSC, true>) : launch(vag_sky_terms_kernel<FLUX_SSC, false>);
+            if (d_pol) {
+                if (mode == FLUX_SYN_IC)
+                    return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN_IC, true, true>)
+                                     : launch(vag_sky_terms_kernel<FLUX_SYN_IC, false, true>);
+                return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN, true, true>) : launch(vag_sky_terms_kernel<FLUX_SYN, false, true>);
+            }
             if (mode == FLUX_SYN_IC)
                 return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN_IC, true>) : launch(vag_sky_terms_kernel<FLUX_SYN_IC, false>);
             return spreading ? launch(vag_sky_terms_kernel<FLUX_SYN, true>) : launch(vag_sky_terms_kernel<FLUX_SYN, false>);
@@ -1982,8 +2000,10 @@ static int sky_terms_stage(vag_ctx* c, const vag_model_params* d_params, int nb,
 }
 
 int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, int nnu, int n_az, double fov, int npixel,
-                double* h_image, double* h_outside, double* h_moments, const SkyVisReq* vr = nullptr) {
+                double* h_image, double* h_outside, double* h_moments, const SkyVisReq* vr = nullptr, const SkyPolReq* pr = nullptr) {
     hipStream_t st = c->stream;
+    const int planes = pr ? 3 : 1;
+    if (pr) h_image = pr->image;
     const std::vector<SkyPass> passes = sky_passes(c);
     const int n_pass = (int)passes.size();
     const int R = std::max(1, c->max_pairs), ks = std::max(2, c->max_k);
@@ -1991,23 +2011,36 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
     const bool want_vis = vr && vr->vis;
     const int nbl = want_vis ? vr->nbl : 0, n_rblk = (R + SKYV_ROWS - 1) / SKYV_ROWS;
     const size_t vis_per_image = want_vis ? (size_t)(n_rblk + 1) * nbl * 2 : 0;  // partials + the combined chunk
-    const size_t per_t = sizeof(double) * ((size_t)nb * nnu * ((size_t)n_pass * 4 * R + npix2 + vis_per_image) + (size_t)nnu * nbl * 2);
+    const int n_pblk = (R + SKYP_ROWS - 1) / SKYP_ROWS;
+    const size_t pol_per_image = pr ? (size_t)n_pass * 3 * R + (size_t)n_pblk * 6 : 0;  // the polarization list + the Stokes partials
+    const size_t per_t = sizeof(double) * ((size_t)nb * nnu * ((size_t)n_pass * 4 * R + planes * npix2 + vis_per_image + pol_per_image) +
+                                           (size_t)nnu * nbl * 2);
     int chunk = (int)std::max<size_t>(1, std::min<size_t>(nt, ((size_t)256 << 20) / per_t));
     if (const char* e = vag_hook("VAG_SKY_CHUNK_T")) chunk = std::max(1, std::min(nt, std::atoi(e)));
     const size_t G_max = (size_t)nb * nnu * chunk;
-    if (c->d_skyterms.ensure(sizeof(double) * (size_t)n_pass * 4 * G_max * R)) return VAG_E_HIP;
-    if (h_image && c->d_skyimg.ensure(sizeof(double) * G_max * npix2)) return VAG_E_HIP;
+    if (c->d_skyterms.ensure(sizeof(double) * (size_t)n_pass * (pr ? 7 : 4) * G_max * R)) return VAG_E_HIP;
+    if (h_image && c->d_skyimg.ensure(sizeof(double) * G_max * planes * npix2)) return VAG_E_HIP;
     if (want_vis && c->d_skyvis.ensure(sizeof(double) * G_max * vis_per_image)) return VAG_E_HIP;
     if (want_vis && c->d_skyuv.ensure(sizeof(double) * (size_t)nnu * chunk * nbl * 2)) return VAG_E_HIP;
     const size_t n_bins = (size_t)nb * nnu * nt;
     if (c->d_skymom.ensure(sizeof(double) * n_bins * 7)) return VAG_E_HIP;
     double* d_mom = c->d_skymom.as<double>();
     double* d_out = d_mom + n_bins * 6;
+    double* d_pol = pr ? c->d_skyterms.as<double>() + (size_t)n_pass * 4 * G_max * R : nullptr;  // behind the largest chunk's term list
+    double *d_spec = nullptr, *d_stokes = nullptr, *d_pout = nullptr;
+    if (pr) {
+        if (c->d_skypol.ensure(sizeof(double) * (size_t)n_pblk * G_max * 6)) return VAG_E_HIP;
+        if (c->d_skystokes.ensure(sizeof(double) * ((size_t)nb * 4 + n_bins * 6))) return VAG_E_HIP;
+        d_spec = c->d_skystokes.as<double>();
+        d_stokes = d_spec + (size_t)nb * 4;
+        d_pout = d_stokes + n_bins * 3;
+        HIPCHK(hipMemcpyAsync(d_spec, pr->spec, sizeof(double) * (size_t)nb * 4, hipMemcpyHostToDevice, st));
+    }
     int rc = VAG_OK;
     for (int t0 = 0; t0 < nt && rc == VAG_OK; t0 += chunk) {
         const int n = std::min(chunk, nt - t0);
         const size_t G = (size_t)nb * nnu * n;
-        rc = sky_terms_stage(c, d_params, nb, t0, n, nnu, passes, R, ks);
+        rc = sky_terms_stage(c, d_params, nb, t0, n, nnu, passes, R, ks, d_pol);
         if (rc) break;
         SkyImgArgs b{};
         b.meta = c->d_meta.as<VagGridMeta>();
@@ -2024,6 +2057,7 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
         b.npixel = h_image ? npixel : 1;
         b.image = c->d_skyimg.as<double>();
         b.image_chunk = 1;
+        b.extra_planes = planes - 1;
         b.moments = h_moments ? d_mom : nullptr;
         b.outside = h_outside ? d_out : nullptr;
         if (h_image) {
@@ -2035,9 +2069,45 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
             hipLaunchKernelGGL(vag_sky_moments_kernel, dim3((unsigned)G), dim3(64), 0, st, b);
             HIPCHK(hipGetLastError());
         }
-        if (h_image)  // [nb * nnu][n][npixel^2] -> its place in [nb * nnu][nt][npixel^2]
-            HIPCHK(hipMemcpy2DAsync(h_image + (size_t)t0 * npix2, sizeof(double) * nt * npix2, c->d_skyimg.p, sizeof(double) * n * npix2,
-                                    sizeof(double) * n * npix2, (size_t)nb * nnu, hipMemcpyDeviceToHost, st));
+        if (pr) {
+            SkyPolArgs pa{};
+            pa.meta = b.meta;
+            pa.phi = b.phi;
+            pa.terms = b.terms;
+            pa.pol = d_pol;
+            pa.spec = d_spec;
+            for (int q = 0; q < n_pass; ++q) pa.pass_em[q] = passes[q].pass == 0 ? passes[q].e : -1;
+            pa.n_pass = n_pass;
+            pa.nnu = nnu;
+            pa.nt = n;
+            pa.R = R;
+            pa.n_az = n_az;
+            pa.nt_all = nt;
+            pa.t0 = t0;
+            pa.fov = pr->outside ? fov : 0.0;
+            pa.npixel = pr->outside ? npixel : 1;
+            pa.sin_2pa = std::sin(2 * pr->pa);
+            pa.cos_2pa = std::cos(2 * pr->pa);
+            pa.partial = c->d_skypol.as<double>();
+            pa.stokes = pr->stokes ? d_stokes : nullptr;
+            pa.outside = pr->outside ? d_pout : nullptr;
+            if (pa.stokes || pa.outside) {
+                hipLaunchKernelGGL(vag_sky_stokes_kernel, dim3((unsigned)G, (unsigned)n_pblk), dim3(64), 0, st, pa);
+                HIPCHK(hipGetLastError());
+                hipLaunchKernelGGL(vag_sky_stokes_combine, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, pa, (int)G);
+                HIPCHK(hipGetLastError());
+            }
+            if (h_image) {
+                const int tiles = (npixel + SKY_TILE - 1) / SKY_TILE;
+                hipLaunchKernelGGL(vag_sky_stokes_deposit_kernel, dim3(tiles * tiles, (unsigned)G, 2), dim3(64), 0, st, b, pa);
+                HIPCHK(hipGetLastError());
+            }
+        }
+        if (h_image) {  // [nb * nnu][n][planes][npixel^2] -> its place in [nb * nnu][nt][planes][npixel^2]
+            const size_t img = sizeof(double) * planes * npix2;
+            HIPCHK(hipMemcpy2DAsync(h_image + (size_t)t0 * planes * npix2, nt * img, c->d_skyimg.p, n * img, n * img, (size_t)nb * nnu,
+                                    hipMemcpyDeviceToHost, st));
+        }
         if (want_vis) {
             const size_t row = sizeof(double) * n * nbl;  // this chunk's baselines: [nnu][t0 : t0 + n][nbl] -> [nnu][n][nbl]
             double* d_u = c->d_skyuv.as<double>();
@@ -2075,6 +2145,8 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
     if (rc) return rc;
     if (h_moments) HIPCHK(hipMemcpyAsync(h_moments, d_mom, sizeof(double) * n_bins * 6, hipMemcpyDeviceToHost, st));
     if (h_outside) HIPCHK(hipMemcpyAsync(h_outside, d_out, sizeof(double) * n_bins, hipMemcpyDeviceToHost, st));
+    if (pr && pr->stokes) HIPCHK(hipMemcpyAsync(pr->stokes, d_stokes, sizeof(double) * n_bins * 3, hipMemcpyDeviceToHost, st));
+    if (pr && pr->outside) HIPCHK(hipMemcpyAsync(pr->outside, d_pout, sizeof(double) * n_bins * 3, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return VAG_OK;
 }
@@ -2626,7 +2698,8 @@ int check_status(vag_ctx* c, int nb) {
 // One launch sequence serves one flag set (the flags pick kernels and passes).  The reference evaluates any mix of models
 // side by side (samplers.py:59-91), so a mixed batch handed over the host-pointer API is split by flags, every group runs as
 // its own batch -- same entry point, same arithmetic as if the caller had split it --, and the groups' rows are put back in
-// place.  OutRows: one output array of `stride` doubles per model (NULL: not requested).
+// place.  OutRows: one output array of `stride` doubles per model (NULL: not requested).  ins: per-model input arrays of the same
+// form, gathered per group and handed to the call behind the outputs.
 struct OutRows {
     double* p;
     size_t stride;
@@ -2637,7 +2710,8 @@ static bool uniform_flags(const vag_model_params* params, int nb) {
     return true;
 }
 template <class Call>
-static int run_flag_groups(const vag_model_params* params, int nb, const std::vector<OutRows>& outs, Call call) {
+static int run_flag_groups(const vag_model_params* params, int nb, const std::vector<OutRows>& outs, Call call,
+                           const std::vector<OutRows>& ins = {}) {
     std::vector<int> keys;
     std::vector<std::vector<int>> groups;
     for (int m = 0; m < nb; ++m) {
@@ -2653,12 +2727,20 @@ static int run_flag_groups(const vag_model_params* params, int nb, const std::ve
         const int ng = (int)idx.size();
         std::vector<vag_model_params> gp(ng);
         for (int i = 0; i < ng; ++i) gp[i] = params[idx[i]];
-        std::vector<std::vector<double>> bufs(outs.size());
-        std::vector<double*> ptrs(outs.size(), nullptr);
+        std::vector<std::vector<double>> bufs(outs.size() + ins.size());
+        std::vector<double*> ptrs(outs.size() + ins.size(), nullptr);
         for (size_t q = 0; q < outs.size(); ++q)
             if (outs[q].p) {
                 bufs[q].resize((size_t)ng * outs[q].stride);
                 ptrs[q] = bufs[q].data();
+            }
+        for (size_t q = 0; q < ins.size(); ++q)
+            if (ins[q].p) {
+                std::vector<double>& buf = bufs[outs.size() + q];
+                buf.resize((size_t)ng * ins[q].stride);
+                for (int i = 0; i < ng; ++i)
+                    std::memcpy(buf.data() + (size_t)i * ins[q].stride, ins[q].p + (size_t)idx[i] * ins[q].stride, sizeof(double) * ins[q].stride);
+                ptrs[outs.size() + q] = buf.data();
             }
         const int rc = call(gp.data(), ng, ptrs);
         if (rc) return rc;
@@ -2939,19 +3021,27 @@ int vag_flux_density_grid_components4_batch(vag_ctx* c, const vag_model_params* 
 
 // Model.sky_image / Model.sky_moments over a batch (vag_sky.h; the definition is the engine's own)
 static int sky_impl(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu, int n_az,
-                    double fov, int npixel, double* image, double* outside, double* moments, const SkyVisReq* vr = nullptr) {
+                    double fov, int npixel, double* image, double* outside, double* moments, const SkyVisReq* vr = nullptr,
+                    const SkyPolReq* pr = nullptr) {
     int rc = check_host_inputs(params, nb, t, nt);
     if (rc) return rc;
     if (!uniform_flags(params, nb)) {
         const size_t st = (size_t)nnu * nt;
         double* vis = vr ? vr->vis : nullptr;
         const size_t vis_stride = vr ? st * vr->nbl * 2 : 0;
-        return run_flag_groups(params, nb, {{image, st * npixel * npixel}, {outside, st}, {moments, st * 6}, {vis, vis_stride}},
-                               [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-                                   SkyVisReq gv{};
-                                   if (vr) gv = *vr, gv.vis = o[3];
-                                   return sky_impl(c, gp, ng, t, nt, nu, nnu, n_az, fov, npixel, o[0], o[1], o[2], vr ? &gv : nullptr);
-                               });
+        const SkyPolReq none{};
+        const SkyPolReq& P = pr ? *pr : none;
+        return run_flag_groups(
+            params, nb,
+            {{image, st * npixel * npixel}, {outside, st}, {moments, st * 6}, {vis, vis_stride}, {P.stokes, st * 3},
+             {P.image, st * 3 * npixel * npixel}, {P.outside, st * 3}},
+            [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
+                SkyVisReq gv{};
+                if (vr) gv = *vr, gv.vis = o[3];
+                const SkyPolReq gpol{o[7], P.pa, o[4], o[5], o[6]};
+                return sky_impl(c, gp, ng, t, nt, nu, nnu, n_az, fov, npixel, o[0], o[1], o[2], vr ? &gv : nullptr, pr ? &gpol : nullptr);
+            },
+            {{const_cast<double*>(P.spec), 4}});
     }
     HIPCHK(hipSetDevice(c->device));
     if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
@@ -2964,7 +3054,7 @@ static int sky_impl(vag_ctx* c, const vag_model_params* params, int nb, const do
     if (rc) return rc;
     rc = run_model_stages(c, c->d_params.as<vag_model_params>(), nb, false);
     if (rc) return rc;
-    rc = sky_request(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, n_az, fov, npixel, image, outside, moments, vr);
+    rc = sky_request(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, n_az, fov, npixel, image, outside, moments, vr, pr);
     if (rc) return rc;
     return check_status(c, nb);  // (no collect_times: the flux events it reads are not recorded by the sky passes)
 }
@@ -3008,6 +3098,53 @@ int vag_sky_visibility_batch(vag_ctx* c, const vag_model_params* params, int nb,
     if (n_az <= 0) n_az = 1024;
     const SkyVisReq vr{u, v, nbl, pa, vis};
     return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, 0.0, 1, nullptr, nullptr, nullptr, &vr);
+}
+
+// Model.sky_polarization / Model.sky_stokes_image over a batch ("Polarization").  spec [nb][4]: b - 1 of the forward
+// and reverse shock, then their Pi_max (pi_max < 0: (p + 1) / (p + 7/3) with that emitter's own p).
+static int pol_spec(const vag_model_params* params, int nb, const vag_pol_spec* pol, std::vector<double>& spec) {
+    if (!params || nb <= 0) return VAG_OK;  // (check_host_inputs reports it)
+    spec.resize((size_t)nb * 4);
+    for (int m = 0; m < nb; ++m)
+        for (int e = 0; e < 2; ++e) {
+            const double b = pol[m].b[e], p = e == 0 ? params[m].p : params[m].rvs_p;
+            double pm = pol[m].pi_max[e];
+            if (!(std::isfinite(b) && b >= 0)) return set_err(VAG_E_INVALID, "model %d: pol.b[%d] must be finite and >= 0", m, e);
+            if (std::isnan(pm) || pm > 1) return set_err(VAG_E_INVALID, "model %d: pol.pi_max[%d] must be <= 1 (< 0: from p)", m, e);
+            if (pm < 0) pm = (p + 1) / (p + 7.0 / 3.0);
+            spec[4 * (size_t)m + e] = b - 1;
+            spec[4 * (size_t)m + 2 + e] = pm;
+        }
+    return VAG_OK;
+}
+
+int vag_sky_polarization_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                               const vag_pol_spec* pol, double pa, int n_az, double* out) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!nu || !pol || !out) return set_err(VAG_E_INVALID, "null frequency, polarization spec or output array");
+    if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
+    if (!std::isfinite(pa)) return set_err(VAG_E_INVALID, "pa must be finite");
+    std::vector<double> spec;
+    if (int rc = pol_spec(params, nb, pol, spec)) return rc;
+    if (n_az <= 0) n_az = 256;
+    const SkyPolReq pr{spec.data(), pa, out, nullptr, nullptr};
+    return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, 0.0, 1, nullptr, nullptr, nullptr, nullptr, &pr);
+}
+
+int vag_sky_stokes_image_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
+                               const vag_pol_spec* pol, double fov, int npixel, int n_az, double* image, double* outside) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!nu || !pol || !image) return set_err(VAG_E_INVALID, "null frequency, polarization spec or image array");
+    if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
+    if (!(std::isfinite(fov) && fov > 0)) return set_err(VAG_E_INVALID, "fov must be positive and finite");
+    if (npixel < 1 || npixel > 4096) return set_err(VAG_E_INVALID, "npixel must be in [1, 4096]");
+    std::vector<double> spec;
+    if (int rc = pol_spec(params, nb, pol, spec)) return rc;
+    if (n_az <= 0) n_az = 4 * npixel;
+    const SkyPolReq pr{spec.data(), 0.0, nullptr, image, outside};
+    return sky_impl(c, params, nb, t, nt, nu, nnu, n_az, fov, npixel, nullptr, nullptr, nullptr, nullptr, &pr);
 }
 
 // Test-facing probe of the device math (vag_debug_math.h): not on any product path, synchronous, its own buffers.

@@ -10,7 +10,8 @@
 //                           lanes of one instruction are applied in lane order, and the tile belongs to one wavefront)
 //   vag_sky_moments_kernel  one wavefront per image: F, centroid, central second moments in two passes over the same parts, and
 //                           the weight that falls outside the image
-// DESIGN §4k.
+// Further consumers of the term list below: visibilities, the visibility groups of the likelihood, and linear polarization (Stokes
+// sums and maps, with a second list of what the polarization of a term needs).  DESIGN §4k.
 #pragma once
 #include "vag_sky_moments.h"
 
@@ -38,10 +39,12 @@ struct SkyArgs {
     int nt, nnu, R;            // R: row stride of the term list (>= n_theta * n_phi_eff of every model)
     int ks;                    // LDS row length (>= every lattice of the batch)
     double* terms;             // [4][nb * nnu * nt][R] of this pass
+    double* pol;               // POL: [3][nb * nnu * nt][R] of this pass (u, m0, m1: cos between sight line and radius = m0 + m1 cos phi)
 };
 
-// The terms of one (theta, phi) row for every (nu, t) of the chunk.  MODE / SPREAD as in vag_flux_grid_kernel.
-template <int MODE, bool SPREAD>
+// The terms of one (theta, phi) row for every (nu, t) of the chunk.  MODE / SPREAD as in vag_flux_grid_kernel.  POL: also what the
+// polarization of a term needs (vag_sky_stokes_kernel), written for the terms of non-zero weight only.
+template <int MODE, bool SPREAD, bool POL = false>
 __global__ void __launch_bounds__(64 * SKY_WAVES) vag_sky_terms_kernel(SkyArgs a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* s_sp = lds;
@@ -154,6 +157,13 @@ __global__ void __launch_bounds__(64 * SKY_WAVES) vag_sky_terms_kernel(SkyArgs a
                 ca = rr * ct * sin_obs;
                 cb = rr * st * cos_obs;
                 cc = rr * st;
+                if constexpr (POL) {
+                    const double u_lo = row[VP_U * K + lo];
+                    double* po = a.pol + ((size_t)m * nnu * nt + s) * a.R + p;
+                    po[0] = u_lo + f * (row[VP_U * K + lo + 1] - u_lo);
+                    po[plane] = ct * cos_obs;
+                    po[2 * plane] = st * sin_obs;
+                }
             }
         }
         double* o = out + (size_t)s * a.R;
@@ -199,6 +209,7 @@ struct SkyImgArgs {
     int npixel;
     double* image;    // [nb][nnu][nt_all][npixel][npixel] (deposit) or this chunk's [nb * nnu * nt][npixel^2]
     int image_chunk;  // 1: image is the chunk's buffer
+    int extra_planes;  // planes that follow every image in `image` (Stokes maps: 2, Q and U)
     double* moments;  // [nb][nnu][nt_all][6] or nullptr
     double* outside;  // [nb][nnu][nt_all] or nullptr
 };
@@ -252,7 +263,7 @@ __global__ void __launch_bounds__(64) vag_sky_deposit_kernel(SkyImgArgs a) {
     }
     wave_sync();
     const size_t npix2 = (size_t)a.npixel * a.npixel;
-    double* img = a.image + (a.image_chunk ? (size_t)g : sky_out_index(a, g)) * npix2;
+    double* img = a.image + (a.image_chunk ? (size_t)g : sky_out_index(a, g)) * (1 + a.extra_planes) * npix2;
     for (int q = lane; q < SKY_TILE * SKY_TILE; q += 64) {
         const int y = ty0 + q / SKY_TILE, x = tx0 + q % SKY_TILE;
         if (x < a.npixel && y < a.npixel) img[(size_t)y * a.npixel + x] = tile[q];
@@ -774,6 +785,217 @@ __global__ void __launch_bounds__(256) vag_sky_centroid_combine(const VagGridMet
     mo[3] = ok ? r.mxx / r.w : NAN;
     mo[4] = ok ? r.myy / r.w : NAN;
     mo[5] = ok ? r.mxy / r.w : NAN;
+}
+
+// ---- linear polarization (vag_sky_polarization_batch / vag_sky_stokes_image_batch; the definition: INTEGRATION.md, "Polarization") ----
+//   vag_sky_stokes_kernel          one wavefront per (block of SKYP_ROWS of the model's own rows, image of the chunk), lane = row: the
+//                                  passes in order, the row's parts in order, I, Q, U (and their shares outside the image) in
+//                                  registers, a fixed-order sum over the wavefront -> one partial per (row block, image)
+//   vag_sky_stokes_combine         one thread per image: the model's own row blocks in block order, then the turn by 2 pa
+//   vag_sky_stokes_deposit_kernel  vag_sky_deposit_kernel for the signed planes Q and U (blockIdx.z); the I plane is that kernel's
+// A synchrotron pass carries the polarization of its emitter; an SSC pass adds to I only.  The row blocks depend on the model's rows
+// only: bitwise reproducible, independent of the batch and of the t-chunking.
+
+constexpr int SKYP_ROWS = 64;  // rows per row block of the Stokes kernel (one per lane)
+
+struct SkyPolArgs {
+    const VagGridMeta* meta;
+    const double* phi;    // [nb][ph_stride]
+    const double* terms;  // the term list of this chunk (sky_request)
+    const double* pol;    // its polarization list [pass][3][image][row]
+    const double* spec;   // [nb][4]: b - 1 of the forward, reverse shock, Pi_max of the forward, reverse shock
+    int pass_em[4];       // the emitter of every pass, -1: unpolarized (SSC)
+    int n_pass, nnu, nt, R, n_az;
+    int nt_all, t0;
+    double fov;  // > 0: also the Stokes sums outside the image of npixel^2 pixels
+    int npixel;
+    double sin_2pa, cos_2pa;
+    double* partial;  // [n_rblk][nb * nnu * nt][6]: I, Q, U, then the same outside the image
+    double* stokes;   // [nb][nnu][nt_all][3] on the sky, or nullptr
+    double* outside;  // [nb][nnu][nt_all][3] in the jet frame, or nullptr
+};
+
+// what is per term in the polarization of its parts
+struct SkyPolTerm {
+    double u, Gam, m0, m1, kb;  // Gamma beta, Gamma, mu = m0 + m1 cos phi, b - 1
+    double pw;                  // Pi_max times the weight of a part
+};
+
+VAG_DEV SkyPolTerm sky_pol_term(const double* P, size_t plane, int p, double kb, double pi_max, double part) {
+    SkyPolTerm t;
+    t.u = P[p];
+    t.m0 = P[plane + p];
+    t.m1 = P[2 * plane + p];
+    t.Gam = sqrt(fma(t.u, t.u, 1.0));
+    t.kb = kb;
+    t.pw = pi_max * part;
+    return t;
+}
+
+// Q and U of one part of full weight at (X, Y), cs = cos phi of the part: two divisions, no atan2.
+//   s = sin^2 theta' = (1 - mu^2) / (Gamma - u mu)^2,  Pi = Pi_max (b - 1) s / (2 + (b - 1) s),
+//   Q = -Pi w cos 2psi, U = -Pi w sin 2psi with cos 2psi = (X^2 - Y^2) / (X^2 + Y^2), sin 2psi = 2 X Y / (X^2 + Y^2)
+VAG_DEV void sky_part_qu(const SkyPolTerm& t, double cs, double X, double Y, double& qv, double& uv) {
+    const double mu = fma(t.m1, cs, t.m0);
+    const double den = fma(-t.u, mu, t.Gam);
+    const double sv = dmin(dmax(fma(-mu, mu, 1.0) / (den * den), 0.0), 1.0);
+    const double ks = t.kb * sv;  // >= -1
+    const double xx = X * X, yy = Y * Y, r2 = xx + yy;
+    qv = 0.0, uv = 0.0;
+    if (r2 > 0) {
+        const double f = -t.pw * (ks / ((2.0 + ks) * r2));
+        qv = f * (xx - yy);
+        uv = f * (2 * (X * Y));
+    }
+}
+
+__global__ void __launch_bounds__(64) vag_sky_stokes_kernel(SkyPolArgs a) {
+    const int lane = threadIdx.x, g = blockIdx.x, rb = blockIdx.y;
+    const int m = g / (a.nnu * a.nt);
+    const VagGridMeta& M = a.meta[m];
+    const int n_rows = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    if (rb * SKYP_ROWS >= n_rows && rb > 0) return;  // (the combine reads the blocks of the model's rows only; block 0 always)
+    const double* phi = a.phi + (size_t)m * M.ph_stride;
+    const size_t G = (size_t)gridDim.x, plane = G * a.R;
+    const int p = rb * SKYP_ROWS + lane;
+    const bool live = p < n_rows;
+    const bool want_out = a.fov > 0;
+    const double half = 0.5 * a.fov, delta = a.fov / a.npixel;
+    auto is_out = [&](double X, double Y) {
+        const double fx = floor((X + half) / delta), fy = floor((Y + half) / delta);
+        return !(fx >= 0 && fx < a.npixel && fy >= 0 && fy < a.npixel);
+    };
+    SkyBin b{0.0, 0.0, 0, false};
+    if (live) b = sky_bin(M, phi, p, a.n_az);
+    const double dphi = live ? b.width / b.S : 0.0;
+    double sI = 0, sQ = 0, sU = 0, oI = 0, oQ = 0, oU = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < a.n_pass; ++pass) {
+        const double* T = a.terms + (size_t)pass * 4 * plane + (size_t)g * a.R;
+        const double w = live ? T[p] : 0.0;
+        if (!(w > 0)) continue;
+        const double ca = T[plane + p], cb = T[2 * plane + p], cc = T[3 * plane + p];
+        const double part = w / b.S;
+        const int em = a.pass_em[pass];  // wave-uniform
+        SkyPolTerm t{0, 1, 0, 0, 0, 0};
+        if (em >= 0)
+            t = sky_pol_term(a.pol + (size_t)pass * 3 * plane + (size_t)g * a.R, plane, p, a.spec[4 * m + em], a.spec[4 * m + 2 + em], part);
+#pragma unroll 1
+        for (int s = 0; s < b.S; ++s) {
+            const double ph = b.left + (s + 0.5) * dphi;  // vag_sky_deposit_kernel's part, expression for expression
+            double sn, cs;
+            sincos(ph, &sn, &cs);
+            const double X = ca - cb * cs, Y = cc * sn;
+            double qv = 0, uv = 0;
+            if (em >= 0) sky_part_qu(t, cs, X, Y, qv, uv);
+            sI += part;
+            sQ += qv;
+            if (b.mirrored) {  // the halves at +Y and -Y together: Q of the whole part, no U
+                if (want_out) {
+                    const bool o_hi = is_out(X, Y), o_lo = is_out(X, -Y);
+                    if (o_hi) oI += 0.5 * part, oQ += 0.5 * qv, oU += 0.5 * uv;
+                    if (o_lo) oI += 0.5 * part, oQ += 0.5 * qv, oU -= 0.5 * uv;
+                }
+            } else {
+                sU += uv;
+                if (want_out && is_out(X, Y)) oI += part, oQ += qv, oU += uv;
+            }
+        }
+    }
+    sI = wave_sum(sI);
+    sQ = wave_sum(sQ);
+    sU = wave_sum(sU);
+    if (want_out) {
+        oI = wave_sum(oI);
+        oQ = wave_sum(oQ);
+        oU = wave_sum(oU);
+    }
+    if (lane == 0) {
+        double* o = a.partial + ((size_t)rb * G + g) * 6;
+        o[0] = sI, o[1] = sQ, o[2] = sU, o[3] = oI, o[4] = oQ, o[5] = oU;
+    }
+}
+
+// One thread per image of the chunk.
+__global__ void __launch_bounds__(256) vag_sky_stokes_combine(SkyPolArgs a, int G) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    const int m = g / (a.nnu * a.nt);
+    const VagGridMeta M = a.meta[m];
+    const int n_rows = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    const int n_rblk = max(1, (n_rows + SKYP_ROWS - 1) / SKYP_ROWS);
+    double v[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < n_rblk; ++b) {
+        const double* o = a.partial + ((size_t)b * G + g) * 6;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[q] += o[q];
+    }
+    const int idx = g % a.nt, ml = g / a.nt;
+    const size_t o = ((size_t)ml * a.nt_all + a.t0 + idx) * 3;
+    if (a.stokes) {
+        a.stokes[o] = v[0];
+        a.stokes[o + 1] = v[1] * a.cos_2pa - v[2] * a.sin_2pa;
+        a.stokes[o + 2] = v[1] * a.sin_2pa + v[2] * a.cos_2pa;
+    }
+    if (a.outside) a.outside[o] = v[3], a.outside[o + 1] = v[4], a.outside[o + 2] = v[5];
+}
+
+// One wavefront per (pixel tile, image of the chunk, plane Q or U): vag_sky_deposit_kernel's walk and tile, the value of a part its
+// Q or U (half of it at +Y and at -Y on a mirrored grid, U with the sign of Y).  a.image is the chunk's [image][3][npixel^2].
+__global__ void __launch_bounds__(64) vag_sky_stokes_deposit_kernel(SkyImgArgs a, SkyPolArgs pa) {
+    __shared__ double tile[SKY_TILE * SKY_TILE];
+    const int lane = threadIdx.x;
+    const int g = blockIdx.y, n_tx = (a.npixel + SKY_TILE - 1) / SKY_TILE;
+    const int tx0 = (blockIdx.x % n_tx) * SKY_TILE, ty0 = (blockIdx.x / n_tx) * SKY_TILE;
+    const bool want_u = blockIdx.z == 1;
+    const int m = g / (a.nnu * a.nt);
+    for (int q = lane; q < SKY_TILE * SKY_TILE; q += 64) tile[q] = 0.0;
+    wave_sync();
+    const VagGridMeta M = a.meta[m];
+    const double* phi = a.phi + (size_t)m * M.ph_stride;
+    const double half = 0.5 * a.fov, delta = a.fov / a.npixel;
+    const size_t G = (size_t)gridDim.y, plane = G * a.R;
+    const double xlo = (tx0 - 1) * delta - half, xhi = (tx0 + SKY_TILE + 1) * delta - half;
+    const double ylo = (ty0 - 1) * delta - half, yhi = (ty0 + SKY_TILE + 1) * delta - half;
+    const int n_rows = M.status == 0 ? M.n_theta * M.n_phi_eff : 0;
+    for (int pass = 0; pass < a.n_pass; ++pass) {
+        const int em = pa.pass_em[pass];
+        if (em < 0) continue;
+        const double* T = a.terms + (size_t)pass * 4 * plane + (size_t)g * a.R;
+        const double* P = pa.pol + (size_t)pass * 3 * plane + (size_t)g * a.R;
+        for (int r0 = 0; r0 < n_rows; r0 += 64) {
+            const int p = r0 + lane;
+            double w = 0, ca = 0, cb = 0, cc = 0;
+            if (p < n_rows) w = T[p], ca = T[plane + p], cb = T[2 * plane + p], cc = T[3 * plane + p];
+            if (!(w > 0)) continue;
+            if (ca + fabs(cb) < xlo || ca - fabs(cb) > xhi || fabs(cc) < ylo || -fabs(cc) > yhi) continue;
+            const SkyBin b = sky_bin(M, phi, p, a.n_az);
+            const double part = w / b.S, dphi = b.width / b.S;
+            const SkyPolTerm t = sky_pol_term(P, plane, p, pa.spec[4 * m + em], pa.spec[4 * m + 2 + em], part);
+            for (int s = 0; s < b.S; ++s) {
+                const double ph = b.left + (s + 0.5) * dphi;
+                double sn, cs;
+                sincos(ph, &sn, &cs);
+                const double X = ca - cb * cs, Y = cc * sn;
+                double qv, uv;
+                sky_part_qu(t, cs, X, Y, qv, uv);
+                const double val = b.mirrored ? 0.5 * (want_u ? uv : qv) : (want_u ? uv : qv);
+                const double fx = floor((X + half) / delta);
+                for (int h = 0; h < (b.mirrored ? 2 : 1); ++h) {
+                    const double fy = floor(((h ? -Y : Y) + half) / delta);
+                    if (fx >= tx0 && fx < tx0 + SKY_TILE && fx < a.npixel && fy >= ty0 && fy < ty0 + SKY_TILE && fy < a.npixel)
+                        lds_add_f64(&tile[((int)fy - ty0) * SKY_TILE + ((int)fx - tx0)], (h && want_u) ? -val : val);
+                }
+            }
+        }
+    }
+    wave_sync();
+    const size_t npix2 = (size_t)a.npixel * a.npixel;
+    double* img = a.image + ((size_t)g * 3 + 1 + blockIdx.z) * npix2;
+    for (int q = lane; q < SKY_TILE * SKY_TILE; q += 64) {
+        const int y = ty0 + q / SKY_TILE, x = tx0 + q % SKY_TILE;
+        if (x < a.npixel && y < a.npixel) img[(size_t)y * a.npixel + x] = tile[q];
+    }
 }
 
 }  // namespace vag

@@ -299,6 +299,55 @@ class SkyMoments:
         return f"SkyMoments(shape={self.F.shape})"
 
 
+class SkyPolarization:
+    """Model.sky_polarization result: Stokes I, Q, U [erg cm^-2 s^-1 Hz^-1] on the sky, each (nnu, nt) -- (nt,) for a scalar nu;
+    q = Q / I, u = U / I, degree = hypot(Q, U) / I and angle = 1/2 atan2(U, Q) [rad east of north, the IAU polarization angle];
+    NaN for the four ratios where I <= 0."""
+
+    def __init__(self, iqu, t, nu):
+        self.I, self.Q, self.U = (iqu[..., q].copy() for q in range(3))
+        self.t, self.nu = t, nu
+
+    def _ratio(self, x):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(self.I > 0, x / self.I, np.nan)
+
+    @property
+    def q(self):
+        return self._ratio(self.Q)
+
+    @property
+    def u(self):
+        return self._ratio(self.U)
+
+    @property
+    def degree(self):
+        return self._ratio(np.hypot(self.Q, self.U))
+
+    @property
+    def angle(self):
+        return np.where(self.I > 0, 0.5 * np.arctan2(self.U, self.Q), np.nan)
+
+    def __repr__(self):
+        return f"SkyPolarization(shape={self.I.shape})"
+
+
+class SkyStokesImage:
+    """Model.sky_stokes_image result: maps I, Q, U [..., iy, ix] in erg cm^-2 s^-1 Hz^-1 per pixel, (nnu, nt, npixel, npixel) --
+    (nt, npixel, npixel) for a scalar nu --, in the jet frame (+X along the projected jet axis, Q > 0: E-vector along +X); outside:
+    the Stokes sums (..., 3) of what falls outside the image; extent and pixel_solid_angle as SkyImage."""
+
+    def __init__(self, maps, outside, fov, t, nu):
+        self.I, self.Q, self.U = (maps[..., q, :, :] for q in range(3))
+        self.outside, self.fov, self.t, self.nu = outside, fov, t, nu
+        self.npixel = maps.shape[-1]
+        self.extent = (-fov / 2, fov / 2, -fov / 2, fov / 2)
+        self.pixel_solid_angle = (fov / self.npixel) ** 2
+
+    def __repr__(self):
+        return f"SkyStokesImage(shape={self.I.shape}, fov={self.fov!r})"
+
+
 _ctx_lock = threading.Lock()
 _ctx = {}
 
@@ -565,6 +614,58 @@ class Model:
                 out.ctypes.data_as(_dp)))
         vis = out[..., 0] + 1j * out[..., 1]
         return vis[0] if scalar else vis
+
+    def _pol_spec(self, b, pi_max, b_rvs, pi_max_rvs):
+        """The vag_pol_spec of a polarization call: b_rvs defaults to b, a pi_max of None to the shock's own (p + 1) / (p + 7/3)."""
+        spec = _lib.PolSpec()
+        for e, (name, bv, pm) in enumerate((("b", b, pi_max), ("b_rvs", b if b_rvs is None else b_rvs, pi_max_rvs))):
+            bv = float(bv)
+            _req(math.isfinite(bv) and bv >= 0, f"{name} must be finite and >= 0, got {bv}")
+            if pm is not None:
+                pm = float(pm)
+                _req(0 <= pm <= 1, f"pi_max{'_rvs' if e else ''} must be in [0, 1], got {pm}")
+            spec.b[e] = bv
+            spec.pi_max[e] = -1.0 if pm is None else pm
+        return spec
+
+    def sky_polarization(self, t, nu, b=0.0, pi_max=None, b_rvs=None, pi_max_rvs=None, pa=0.0, n_az=None):
+        """Linear polarization of the afterglow at times t [s] and frequencies nu [Hz] for a random magnetic field behind the shock,
+        axially symmetric about the shock normal, of anisotropy b = 2 <B_par^2> / <B_perp^2> (0: in the shock plane, 1: isotropic;
+        vag_sky_polarization_batch): a SkyPolarization with the Stokes I, Q, U on the sky for the projected jet axis
+        at position angle pa [rad east of north].  pi_max: the local polarization of a uniform field, default (p + 1) / (p + 7/3);
+        b_rvs / pi_max_rvs: the reverse shock's (default: b / its own p).  SSC is unpolarized.  n_az: azimuthal parts per full circle
+        (default 256)."""
+        t, nu, scalar = self._sky_inputs(t, nu, n_az)
+        spec = self._pol_spec(b, pi_max, b_rvs, pi_max_rvs)
+        pa = float(pa)
+        _req(math.isfinite(pa), f"pa must be finite, got {pa}")
+        out = np.empty((nu.size, t.size, 3))
+        h, lock = get_context(self._device)
+        with lock:
+            _lib.check(_lib.load().vag_sky_polarization_batch(
+                h, C.byref(self.params), 1, t.ctypes.data_as(_dp), t.size, nu.ctypes.data_as(_dp), nu.size, C.byref(spec), pa,
+                0 if n_az is None else int(n_az), out.ctypes.data_as(_dp)))
+        return SkyPolarization(out[0] if scalar else out, t, nu[0] if scalar else nu)
+
+    def sky_stokes_image(self, t, nu, fov, npixel=64, b=0.0, pi_max=None, b_rvs=None, pi_max_rvs=None, n_az=None):
+        """Stokes I, Q, U maps of the afterglow on the pixel grid of sky_image (a SkyStokesImage, in the jet frame; the I map is
+        sky_image's image).  b, pi_max, b_rvs, pi_max_rvs as sky_polarization; fov, npixel, n_az as sky_image."""
+        t, nu, scalar = self._sky_inputs(t, nu, n_az)
+        fov = float(fov)
+        _req(math.isfinite(fov) and fov > 0, f"fov must be positive and finite, got {fov}")
+        _req(isinstance(npixel, (int, np.integer)) and 1 <= npixel <= 4096, f"npixel must be an integer in [1, 4096], got {npixel}")
+        npixel = int(npixel)
+        spec = self._pol_spec(b, pi_max, b_rvs, pi_max_rvs)
+        maps = np.empty((nu.size, t.size, 3, npixel, npixel))
+        outside = np.empty((nu.size, t.size, 3))
+        h, lock = get_context(self._device)
+        with lock:
+            _lib.check(_lib.load().vag_sky_stokes_image_batch(
+                h, C.byref(self.params), 1, t.ctypes.data_as(_dp), t.size, nu.ctypes.data_as(_dp), nu.size, C.byref(spec), fov, npixel,
+                0 if n_az is None else int(n_az), maps.ctypes.data_as(_dp), outside.ctypes.data_as(_dp)))
+        if scalar:
+            maps, outside = maps[0], outside[0]
+        return SkyStokesImage(maps, outside, fov, t, nu[0] if scalar else nu)
 
     # -- Model.flux: pybind.cpp:430, pymodel.cpp:391-410 --
     def flux(self, t, nu_min, nu_max, num_nu):
