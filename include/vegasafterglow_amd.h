@@ -374,6 +374,14 @@ int vag_flux_density_batch_dev(vag_ctx* ctx, const vag_model_params* d_params, i
 #define VAG_P_SKY_EAST0 1002
 #define VAG_P_SKY_NORTH0 1003
 
+/* Nor are these: the magnetic field behind the shocks as the polarization groups of vag_loglike_pol_batch see it (vag_pol_spec: the
+ * anisotropy b and Pi_max of the forward shock, then of the reverse shock).  Only that entry point accepts them, with at least one
+ * polarization group; VAG_P_SKY_PA is accepted there too. */
+#define VAG_P_POL_B 1004
+#define VAG_P_POL_PI_MAX 1005
+#define VAG_P_POL_B_RVS 1006
+#define VAG_P_POL_PI_MAX_RVS 1007
+
 /* One group of VLBI centroid positions at one frequency (added after VAG_ABI_VERSION 13, detect by symbol).  The model centroid
  * (Xbar, Ybar) of vag_sky_centroid_batch(t, nu) is placed on the sky as
  *   east = east0 + Xbar sin PA + Ybar cos PA,   north = north0 + Xbar cos PA - Ybar sin PA
@@ -509,6 +517,58 @@ int vag_loglike_vis_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_
                           const double* theta, int nb, int ndim, double* out);
 int vag_loglike_vis_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                               const double* d_theta, int nb, int ndim, double* d_out);
+
+/* One group of polarization measurements at one frequency (added after VAG_ABI_VERSION 13, detect by symbol): n ascending times
+ * with a measurement, errors and a weight each.  The group is its own request (own grid from its own times).  The model I, Q, U at
+ * (t_i, nu) are exactly those of vag_sky_polarization_batch for the walker's parameters, the walker's vag_pol_spec (VAG_P_POL_*, else
+ * the fixed values of vag_pol_fit_spec), the walker's position angle (VAG_P_SKY_PA, shared with the centroid and visibility groups)
+ * and the group's n_az.  kind = VAG_POL_QU: q, u are Q/I and U/I on the sky (IAU) and the group adds
+ *   sum_i weight_i [((q_i - Q_sky/I) / err_q_i)^2 + ((u_i - U_sky/I) / err_u_i)^2]
+ * to the walker's chi^2; kind = VAG_POL_DEGREE: q, err_q hold the degree Pi_i and its error, u and err_u are ignored (may be NULL),
+ * and the group adds sum_i weight_i ((Pi_i - hypot(Q, U)/I) / err_q_i)^2 (the position angle drops out).  Weights are used as given.
+ * Limits: at most VAG_POL_MAX_GROUPS groups of at most VAG_VIS_MAX_EPOCHS epochs; more is refused with VAG_E_INVALID.  Upper
+ * limits, circular polarization and several frequencies in one group are not supported. */
+#define VAG_POL_QU 0
+#define VAG_POL_DEGREE 1
+#define VAG_POL_MAX_GROUPS 64
+typedef struct vag_polarization_obs {
+    double nu;            /* [Hz] */
+    int32_t n;            /* epochs, >= 1 */
+    int32_t n_az;         /* azimuthal parts per circle of the model (vag_sky_polarization_batch); <= 0: 256 */
+    int32_t kind;         /* VAG_POL_QU / VAG_POL_DEGREE */
+    int32_t pad;
+    const double* t;      /* [n] ascending, > 0 [s] */
+    const double* q;      /* [n] Q/I on the sky, or the degree (kind = DEGREE) */
+    const double* u;      /* [n] U/I on the sky; ignored for kind = DEGREE */
+    const double* err_q;  /* [n] > 0 */
+    const double* err_u;  /* [n] > 0; ignored for kind = DEGREE */
+    const double* weight; /* [n] >= 0 */
+} vag_polarization_obs;
+
+/* The polarization groups of a likelihood call and the values of the VAG_P_POL_* parameters that are not free (index 0: forward
+ * shock, 1: reverse shock): pi_max_fixed[e] < 0: (p + 1) / (p + 7/3) with the walker's own p of that shock; b_fixed[1] < 0: the
+ * reverse shock follows the walker's forward b. */
+typedef struct vag_pol_fit_spec {
+    int32_t n_groups;
+    int32_t pad;
+    const vag_polarization_obs* groups; /* [n_groups] */
+    double b_fixed[2];
+    double pi_max_fixed[2];
+} vag_pol_fit_spec;
+
+/* vag_loglike_vis_batch(_dev) with polarization groups: after the flux, band, centroid and visibility passes every group of pol
+ * runs as its own pass and adds its chi^2 term (vag_polarization_obs), formed on the device; no Stokes value leaves it.  sky may be
+ * NULL (position angle 0) or have n_groups = 0 and still supply pa_fixed.  Free parameters may take the slot VAG_P_SKY_PA and the
+ * slots VAG_P_POL_* whenever a polarization group is present.  A walker scores -inf (and counts in n_walkers_rejected) when its own
+ * vag_pol_spec would be refused by vag_sky_polarization_batch (b not finite or < 0, pi_max NaN or > 1), when a pass of a group fails
+ * (grid, ODE rows, SSC tables), or when I <= 0 or I, Q or U is not finite at an epoch of a group (q is undefined there: the
+ * centroid groups' F <= 0 rule).  With pol NULL or n_groups = 0 the call is vag_loglike_vis_batch(_dev), bit for bit.  Results are
+ * bitwise reproducible and a walker's value does not depend on the rest of the batch.  The group data stay resident on the device
+ * by content hash. */
+int vag_loglike_pol_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                          const vag_pol_fit_spec* pol, const double* theta, int nb, int ndim, double* out);
+int vag_loglike_pol_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                              const vag_pol_fit_spec* pol, const double* d_theta, int nb, int ndim, double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

@@ -59,6 +59,8 @@ MATH = {name: i for i, name in enumerate([
 P_A_V = 1000  # VAG_P_A_V
 # VAG_P_SKY_*: the sky placement of the centroid and visibility groups (vag_loglike_sky_batch / _vis_batch), not Model fields either
 SKY_SLOTS = {"pa": 1001, "east0": 1002, "north0": 1003}
+# VAG_P_POL_*: the field behind the shocks as the polarization groups see it (vag_loglike_pol_batch), not Model fields either
+POL_SLOTS = {"pol_b": 1004, "pol_pi_max": 1005, "pol_b_rvs": 1006, "pol_pi_max_rvs": 1007}
 
 
 class CentroidObs(C.Structure):  # vag_centroid_obs
@@ -87,6 +89,20 @@ class PolSpec(C.Structure):  # vag_pol_spec: index 0 forward, 1 reverse shock; p
 
 class VisFitSpec(C.Structure):  # vag_vis_fit_spec
     _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(VisibilityObs))]
+
+
+POL_QU, POL_DEGREE = 0, 1  # VAG_POL_*
+POL_KINDS = {"qu": POL_QU, "degree": POL_DEGREE}
+
+
+class PolarizationObs(C.Structure):  # vag_polarization_obs
+    _fields_ = [("nu", C.c_double), ("n", C.c_int32), ("n_az", C.c_int32), ("kind", C.c_int32), ("pad", C.c_int32)] + \
+               [(n, C.POINTER(C.c_double)) for n in ("t", "q", "u", "err_q", "err_u", "weight")]
+
+
+class PolFitSpec(C.Structure):  # vag_pol_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(PolarizationObs)),
+                ("b_fixed", C.c_double * 2), ("pi_max_fixed", C.c_double * 2)]
 
 
 class FitSpec(C.Structure):
@@ -151,7 +167,7 @@ EXPORTS = [
     "vag_ctx_coalesce", "vag_ctx_coalesce_stats", "vag_flux_density_grid_coalesced", "vag_flux_density_coalesced", "vag_flux_coalesced",
     "vag_sky_image_batch", "vag_sky_moments_batch", "vag_sky_centroid_batch", "vag_loglike_sky_batch", "vag_loglike_sky_batch_dev",
     "vag_sky_visibility_batch", "vag_debug_device_math", "vag_loglike_vis_batch", "vag_loglike_vis_batch_dev",
-    "vag_sky_polarization_batch", "vag_sky_stokes_image_batch",
+    "vag_sky_polarization_batch", "vag_sky_stokes_image_batch", "vag_loglike_pol_batch", "vag_loglike_pol_batch_dev",
 ]
 
 _lib = None
@@ -207,6 +223,10 @@ def load():
     lib.vag_loglike_sky_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_loglike_vis_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), _dp, C.c_int, C.c_int, _dp]
     lib.vag_loglike_vis_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), v, C.c_int, C.c_int, v]
+    lib.vag_loglike_pol_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec), _dp,
+                                          C.c_int, C.c_int, _dp]
+    lib.vag_loglike_pol_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec), v,
+                                              C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

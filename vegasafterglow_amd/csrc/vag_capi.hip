@@ -408,6 +408,7 @@ struct vag_ctx {
     DevBuf d_skyvis, d_skyuv;  // visibilities (vag_sky.h): a chunk's row-block partials + combined values, a chunk's baselines
     DevBuf d_skycen, d_skycmom, d_skyfit;  // exact centroids (vag_sky.h): row-block partials, moments, centroid-fit pass data
     DevBuf d_visfit, d_visblk, d_vispart;  // visibility groups of the likelihood: their data, their 64-visibility blocks, chi^2 partials
+    DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
     bool ic_all_cells = false;    // this request's SSC tables are built for every cell (the lazy selection was caught with a hole, see check_ic_status)
@@ -461,7 +462,7 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit;
+    HostBuf h_fit, h_skyfit, h_visfit, h_polfit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
@@ -474,6 +475,9 @@ struct vag_ctx {
         std::vector<int> epoch_blk;  // [n_epochs + 1]: first block of every epoch
     };
     std::vector<VisLayout> vis_layout;
+    uint64_t polfit_hash = 0;  // (d_polfit: the polarization groups of vag_loglike_pol_batch, upload_pol_spec)
+    size_t polfit_doubles = 0;
+    bool polfit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -708,8 +712,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_fit.release();
     c->h_skyfit.release();
     c->h_visfit.release();
+    c->h_polfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1999,6 +2004,39 @@ static int sky_terms_stage(vag_ctx* c, const vag_model_params* d_params, int nb,
     return rc;
 }
 
+// The polarization leg of a chunk of a sky request, shared by sky_request and the likelihood's polarization groups: what the Stokes
+// kernels read of the chunk's term and polarization lists (sky_terms_stage), with the spec [nb][4] on the device.  The caller sets
+// the turn by 2 pa, the outputs and, for sums outside an image, fov and npixel.
+static SkyPolArgs sky_pol_args(vag_ctx* c, const std::vector<SkyPass>& passes, int nnu, int n, int R, int n_az, int nt_all, int t0,
+                               const double* d_pol, const double* d_spec) {
+    SkyPolArgs pa{};
+    pa.meta = c->d_meta.as<VagGridMeta>();
+    pa.phi = c->d_phi.as<double>();
+    pa.terms = c->d_skyterms.as<double>();
+    pa.pol = d_pol;
+    pa.spec = d_spec;
+    pa.n_pass = (int)passes.size();
+    for (int q = 0; q < pa.n_pass; ++q) pa.pass_em[q] = passes[q].pass == 0 ? passes[q].e : -1;
+    pa.nnu = nnu;
+    pa.nt = n;
+    pa.R = R;
+    pa.n_az = n_az;
+    pa.nt_all = nt_all;
+    pa.t0 = t0;
+    pa.fov = 0.0;
+    pa.npixel = 1;
+    pa.partial = c->d_skypol.as<double>();
+    return pa;
+}
+// vag_sky_stokes_kernel and vag_sky_stokes_combine over the G images of the chunk (d_skypol ensured by the caller)
+static int sky_stokes_stage(vag_ctx* c, const SkyPolArgs& pa, size_t G, int n_pblk) {
+    hipLaunchKernelGGL(vag_sky_stokes_kernel, dim3((unsigned)G, (unsigned)n_pblk), dim3(64), 0, c->stream, pa);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(vag_sky_stokes_combine, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, c->stream, pa, (int)G);
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
 int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, int nnu, int n_az, double fov, int npixel,
                 double* h_image, double* h_outside, double* h_moments, const SkyVisReq* vr = nullptr, const SkyPolReq* pr = nullptr) {
     hipStream_t st = c->stream;
@@ -2070,32 +2108,16 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
             HIPCHK(hipGetLastError());
         }
         if (pr) {
-            SkyPolArgs pa{};
-            pa.meta = b.meta;
-            pa.phi = b.phi;
-            pa.terms = b.terms;
-            pa.pol = d_pol;
-            pa.spec = d_spec;
-            for (int q = 0; q < n_pass; ++q) pa.pass_em[q] = passes[q].pass == 0 ? passes[q].e : -1;
-            pa.n_pass = n_pass;
-            pa.nnu = nnu;
-            pa.nt = n;
-            pa.R = R;
-            pa.n_az = n_az;
-            pa.nt_all = nt;
-            pa.t0 = t0;
+            SkyPolArgs pa = sky_pol_args(c, passes, nnu, n, R, n_az, nt, t0, d_pol, d_spec);
             pa.fov = pr->outside ? fov : 0.0;
             pa.npixel = pr->outside ? npixel : 1;
             pa.sin_2pa = std::sin(2 * pr->pa);
             pa.cos_2pa = std::cos(2 * pr->pa);
-            pa.partial = c->d_skypol.as<double>();
             pa.stokes = pr->stokes ? d_stokes : nullptr;
             pa.outside = pr->outside ? d_pout : nullptr;
             if (pa.stokes || pa.outside) {
-                hipLaunchKernelGGL(vag_sky_stokes_kernel, dim3((unsigned)G, (unsigned)n_pblk), dim3(64), 0, st, pa);
-                HIPCHK(hipGetLastError());
-                hipLaunchKernelGGL(vag_sky_stokes_combine, dim3((unsigned)((G + 255) / 256)), dim3(256), 0, st, pa, (int)G);
-                HIPCHK(hipGetLastError());
+                rc = sky_stokes_stage(c, pa, G, n_pblk);
+                if (rc) break;
             }
             if (h_image) {
                 const int tiles = (npixel + SKY_TILE - 1) / SKY_TILE;
@@ -2271,6 +2293,38 @@ int vis_chi2_request(vag_ctx* c, const vag_model_params* d_params, int nb, const
         if ((size_t)nb * va.n_blk > 0x7fffffffull) return set_err(VAG_E_CAPACITY, "visibility group: too many (walker, visibility block) pairs");
         hipLaunchKernelGGL(vag_sky_vis_chi2_kernel, dim3((unsigned)((size_t)nb * va.n_blk)), dim3(64), 0, st, va);
         HIPCHK(hipGetLastError());
+    }
+    return VAG_OK;
+}
+
+// One polarization group of a likelihood call; model stages already run on the group's epochs, d_lg2t / d_lg2nu prepared, the walkers'
+// spec [nb][4] on the device.  The polarized terms stage and the Stokes kernels of sky_request, unchanged, without the turn by 2 pa:
+// jet-frame I, Q, U into d_stokes [nb][nt][3], the bits of vag_sky_polarization_batch at pa = 0.  The epochs are cut into chunks
+// whose term, polarization and partial lists stay within 256 MB (VAG_SKY_CHUNK_T: a test's chunk length); an epoch's sums do not
+// depend on the cut.
+int pol_stokes_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, int n_az, const double* d_spec, double* d_stokes) {
+    const std::vector<SkyPass> passes = sky_passes(c);
+    const int n_pass = (int)passes.size();
+    const int R = std::max(1, c->max_pairs), ks = std::max(2, c->max_k);
+    const int n_pblk = (R + SKYP_ROWS - 1) / SKYP_ROWS;
+    const size_t per_t = sizeof(double) * (size_t)nb * ((size_t)n_pass * 7 * R + (size_t)n_pblk * 6);
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>(nt, ((size_t)256 << 20) / per_t));
+    if (const char* e = vag_hook("VAG_SKY_CHUNK_T")) chunk = std::max(1, std::min(nt, std::atoi(e)));
+    const size_t G_max = (size_t)nb * chunk;
+    if (G_max > 0x7fffffffull) return set_err(VAG_E_CAPACITY, "polarization group: too many (walker, epoch) pairs");
+    if (c->d_skyterms.ensure(sizeof(double) * (size_t)n_pass * 7 * G_max * R)) return VAG_E_HIP;
+    if (c->d_skypol.ensure(sizeof(double) * (size_t)n_pblk * G_max * 6)) return VAG_E_HIP;
+    double* d_pol = c->d_skyterms.as<double>() + (size_t)n_pass * 4 * G_max * R;  // behind the largest chunk's term list
+    for (int t0 = 0; t0 < nt; t0 += chunk) {
+        const int n = std::min(chunk, nt - t0);
+        int rc = sky_terms_stage(c, d_params, nb, t0, n, 1, passes, R, ks, d_pol);
+        if (rc) return rc;
+        SkyPolArgs pa = sky_pol_args(c, passes, 1, n, R, n_az, nt, t0, d_pol, d_spec);
+        pa.sin_2pa = 0.0;
+        pa.cos_2pa = 1.0;
+        pa.stokes = d_stokes;
+        rc = sky_stokes_stage(c, pa, (size_t)nb * n, n_pblk);
+        if (rc) return rc;
     }
     return VAG_OK;
 }
@@ -3475,14 +3529,15 @@ static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
     return h;
 }
 
-static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false) {
+static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false) {
     if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
     const int n = spec->n_data;
-    if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky)) return set_err(VAG_E_INVALID, "fit spec has no data");
+    if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky && !pol)) return set_err(VAG_E_INVALID, "fit spec has no data");
     for (int d = 0; d < ndim; ++d) {
         const int s = spec->slot[d];
         if (s == VAG_P_A_V) continue;
         if (sky && s >= VAG_P_SKY_PA && s <= VAG_P_SKY_NORTH0) continue;
+        if (pol && (s == VAG_P_SKY_PA || (s >= VAG_P_POL_B && s <= VAG_P_POL_PI_MAX_RVS))) continue;
         if (s < 0 || (s >= VAG_P_COUNT && (s < VAG_P_RVS_EPS_E || s > VAG_P_MAG_Q))) return set_err(VAG_E_INVALID, "bad parameter slot");
     }
     if (spec->use_priors)
@@ -3919,8 +3974,173 @@ vag_fit_vis_back_kernel(const double* __restrict__ partial /* [nb][n_blk][2] */,
     }
 }
 
+// ---- polarization groups (vag_loglike_pol_batch): their data in one device buffer, uploaded like the centroid groups when the hash
+//      changes.  Layout in doubles, per group: [nu | t | q | u | err_q | err_u | weight] (1 + 6 n); u and err_u of a DEGREE group are
+//      zeros. ----
+static int upload_pol_spec(vag_ctx* c, const vag_pol_fit_spec* pol) {
+    if (pol->n_groups < 0 || !pol->groups) return set_err(VAG_E_INVALID, "bad polarization group list");
+    if (pol->n_groups > VAG_POL_MAX_GROUPS) return set_err(VAG_E_INVALID, "at most %d polarization groups", VAG_POL_MAX_GROUPS);
+    for (int e = 0; e < 2; ++e)
+        if (std::isnan(pol->b_fixed[e]) || std::isnan(pol->pi_max_fixed[e]))
+            return set_err(VAG_E_INVALID, "fixed polarization values must not be NaN");
+    uint64_t h = 1469598103934665603ull;
+    h = fnv1a(h, &pol->n_groups, sizeof pol->n_groups);
+    size_t total = 0;
+    for (int g = 0; g < pol->n_groups; ++g) {
+        const vag_polarization_obs& o = pol->groups[g];
+        if (o.n < 1) return set_err(VAG_E_INVALID, "polarization group %d has no observations", g);
+        if (o.n > VAG_VIS_MAX_EPOCHS) return set_err(VAG_E_INVALID, "polarization group %d: at most %d epochs", g, VAG_VIS_MAX_EPOCHS);
+        if (o.kind != VAG_POL_QU && o.kind != VAG_POL_DEGREE) return set_err(VAG_E_INVALID, "polarization group %d: unknown kind %d", g, o.kind);
+        if (!o.t || !o.q || !o.err_q || !o.weight || (o.kind == VAG_POL_QU && (!o.u || !o.err_u)))
+            return set_err(VAG_E_INVALID, "polarization group %d: null array", g);
+        const int head[3] = {o.n, o.n_az > 0 ? o.n_az : 256, o.kind};
+        h = fnv1a(h, &o.nu, sizeof o.nu);
+        h = fnv1a(h, head, sizeof head);
+        for (const double* arr : {o.t, o.q, o.kind == VAG_POL_QU ? o.u : nullptr, o.err_q, o.kind == VAG_POL_QU ? o.err_u : nullptr, o.weight})
+            if (arr) h = fnv1a(h, arr, sizeof(double) * o.n);
+        total += 1 + 6 * (size_t)o.n;
+    }
+    if (c->polfit_hash_valid && c->polfit_hash == h && c->polfit_doubles == total) return VAG_OK;  // resident already
+    for (int g = 0; g < pol->n_groups; ++g) {
+        const vag_polarization_obs& o = pol->groups[g];
+        const bool qu = o.kind == VAG_POL_QU;
+        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "polarization group %d: frequency must be positive", g);
+        for (int i = 0; i < o.n; ++i) {
+            if (!(o.t[i] > 0) || !std::isfinite(o.t[i]) || (i > 0 && o.t[i] < o.t[i - 1]))
+                return set_err(VAG_E_INVALID, "polarization group %d: times must be positive and ascending", g);
+            if (!std::isfinite(o.q[i]) || (qu && !std::isfinite(o.u[i])) || !std::isfinite(o.weight[i]) || o.weight[i] < 0)
+                return set_err(VAG_E_INVALID, "polarization group %d: measurements must be finite, weights finite and >= 0", g);
+            if (!(o.err_q[i] > 0) || !std::isfinite(o.err_q[i]) || (qu && (!(o.err_u[i] > 0) || !std::isfinite(o.err_u[i]))))
+                return set_err(VAG_E_INVALID, "polarization group %d: errors must be positive and finite", g);
+        }
+    }
+    c->polfit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_polfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
+    if (c->d_polfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
+    double* hp = c->h_polfit.as<double>();
+    size_t off = 0;
+    for (int g = 0; g < pol->n_groups; ++g) {
+        const vag_polarization_obs& o = pol->groups[g];
+        const bool qu = o.kind == VAG_POL_QU;
+        hp[off++] = o.nu;
+        for (const double* arr : {o.t, o.q, qu ? o.u : nullptr, o.err_q, qu ? o.err_u : nullptr, o.weight}) {
+            if (arr)
+                std::memcpy(hp + off, arr, sizeof(double) * o.n);
+            else
+                std::memset(hp + off, 0, sizeof(double) * o.n);
+            off += o.n;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(c->d_polfit.p, hp, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
+    c->polfit_hash = h;
+    c->polfit_doubles = total;
+    c->polfit_hash_valid = true;
+    return VAG_OK;
+}
+
+// The walkers' polarization spec, one thread per evaluation slot: spec[m] = {b - 1 of the forward, reverse shock, Pi_max of the forward,
+// reverse shock} as pol_spec() resolves a vag_pol_spec -- free parameters with the slots VAG_P_POL_*, else the fixed values; a reverse
+// b that is neither free nor given (< 0) follows the walker's forward b; a Pi_max < 0 is (p + 1) / (p + 7/3) with the p of the walker's
+// transformed parameters.  bad[m] = 1 where pol_spec() would refuse the walker (its spec is then 0: unpolarized, never read back).
+__global__ void __launch_bounds__(128)
+vag_fit_pol_spec_kernel(const double* __restrict__ theta, int nb, int ndim, const double* __restrict__ prior,
+                        const vag_model_params* __restrict__ params, double b0, double b1, double pm0, double pm1,
+                        const int* __restrict__ order, double* __restrict__ spec, int* __restrict__ bad) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= nb) return;
+    const int walker = order ? order[m] : m;
+    const int* slot = reinterpret_cast<const int*>(prior + 64);
+    const int* is_log = slot + 16;
+    bool b1_given = !(b1 < 0);
+    for (int d = 0; d < ndim; ++d) {
+        const int sl = slot[d];
+        if (sl < VAG_P_POL_B || sl > VAG_P_POL_PI_MAX_RVS) continue;
+        const double v = theta[(size_t)walker * ndim + d];
+        const double val = is_log[d] ? pow(10.0, v) : v;
+        b0 = sl == VAG_P_POL_B ? val : b0;  // (selects, as in sky_placement)
+        pm0 = sl == VAG_P_POL_PI_MAX ? val : pm0;
+        b1 = sl == VAG_P_POL_B_RVS ? val : b1;
+        pm1 = sl == VAG_P_POL_PI_MAX_RVS ? val : pm1;
+        b1_given = b1_given || sl == VAG_P_POL_B_RVS;
+    }
+    if (!b1_given) b1 = b0;
+    const bool ok = isfinite(b0) && b0 >= 0 && isfinite(b1) && b1 >= 0 && !(pm0 != pm0) && !(pm0 > 1) && !(pm1 != pm1) && !(pm1 > 1);
+    const double p0 = params[m].p, p1 = params[m].rvs_p;
+    if (pm0 < 0) pm0 = (p0 + 1) / (p0 + 7.0 / 3.0);
+    if (pm1 < 0) pm1 = (p1 + 1) / (p1 + 7.0 / 3.0);
+    double* o = spec + 4 * (size_t)m;
+    o[0] = ok ? b0 - 1 : 0.0;
+    o[1] = ok ? b1 - 1 : 0.0;
+    o[2] = ok ? pm0 : 0.0;
+    o[3] = ok ? pm1 : 0.0;
+    bad[m] = ok ? 0 : 1;
+}
+
+// The back of one polarization pass, one wavefront per walker (vag_fit_back_kernel's protocol): the walker's position angle (the free
+// parameter with the slot VAG_P_SKY_PA, else the fixed value), the turn of the jet-frame Q, U by 2 pa, the residuals of up to 64
+// epochs at a time, one per lane, added in epoch order, and validity -- a valid spec, I > 0 and finite I, Q, U at every epoch, grid,
+// ODE rows and SSC tables of this pass.  A DEGREE group reads hypot(Q, U) of the jet frame: the position angle does not enter.
+__global__ void __launch_bounds__(64)
+vag_fit_pol_back_kernel(const double* __restrict__ stokes /* [nb][n][3] jet frame */, int n, int kind,
+                        const double* __restrict__ obs /* [t|q|u|eq|eu|w] */, const int* __restrict__ spec_bad,
+                        const double* __restrict__ theta, int ndim, const double* __restrict__ prior, double pa_fixed,
+                        const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status, const int* __restrict__ row_off,
+                        const int* __restrict__ ic_status, double* __restrict__ chi2, int* __restrict__ valid,
+                        const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out, int* __restrict__ fitstat,
+                        const int* __restrict__ order) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    const int walker = order ? order[m] : m;
+    double pa = pa_fixed, e0 = 0, n0 = 0;
+    vag::sky_placement(theta, walker, ndim, prior, pa, e0, n0);
+    double s2, c2;
+    sincos(2 * pa, &s2, &c2);
+    const double *q_obs = obs + n, *u_obs = obs + 2 * (size_t)n, *q_err = obs + 3 * (size_t)n, *u_err = obs + 4 * (size_t)n,
+                 *w = obs + 5 * (size_t)n;
+    const bool grid_ok = meta[m].status == 0;
+    double s = 0;
+    bool bad = spec_bad[m] != 0;
+    if (grid_ok)
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane, cnt = min(64, n - i0);
+            double term = 0;
+            if (i < n) {
+                const double* sk = stokes + ((size_t)m * n + i) * 3;
+                const double I = sk[0], Q = sk[1], U = sk[2];
+                bad = bad || !(I > 0) || !isfinite(I) || !isfinite(Q) || !isfinite(U);
+                if (kind == VAG_POL_DEGREE) {
+                    const double r = (q_obs[i] - hypot(Q, U) / I) / q_err[i];
+                    term = w[i] * (r * r);
+                } else {
+                    const double Qs = Q * c2 - U * s2, Us = Q * s2 + U * c2;
+                    const double rq = (q_obs[i] - Qs / I) / q_err[i], ru = (u_obs[i] - Us / I) / u_err[i];
+                    term = w[i] * (rq * rq + ru * ru);
+                }
+            }
+            for (int j = 0; j < cnt; ++j) s += vag::wave_bcast(term, j);  // every lane: the epochs in order
+        }
+    if (grid_ok)
+        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad = bad || row_status[r] == 1;
+    const bool any_bad = __any(bad);
+    if (lane == 0) {
+        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
+        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
+        const double acc = first ? s : chi2[m] + s;
+        valid[m] = ok;
+        chi2[m] = acc;
+        if (ic_bad) atomicAdd(fitstat + 1, 1);
+        if (last) {
+            const double lp = ln_prior[m];
+            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
+            out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
+            if (!fin) atomicAdd(fitstat, 1);
+        }
+    }
+}
+
 static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec,
-                        const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr) {
+                        const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
+                        const vag_pol_fit_spec* pol = nullptr) {
     int rc = VAG_OK;
     const int n = spec->n_data;
     hipStream_t st = c->stream;
@@ -3954,8 +4174,8 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         order_made = true;
         return nxt.as<int>();
     };
-    const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = vis ? vis->n_groups : 0;
-    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups;
+    const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = vis ? vis->n_groups : 0, n_pol_groups = pol ? pol->n_groups : 0;
+    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // the SSC tables of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
     auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext) -> int {
@@ -4060,6 +4280,38 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
             n_inv = std::max(n_inv, c->plan.n_models_invalid);
         }
     }
+    size_t poff = 0;
+    if (n_pol_groups > 0 && rc == VAG_OK) {  // the walkers' own field: once per call, in the evaluation order of d_params
+        if (c->d_polspec.ensure(sizeof(double) * 5 * (size_t)nb)) return VAG_E_HIP;  // [nb][4] spec | int [nb] flags
+        hipLaunchKernelGGL(vag_fit_pol_spec_kernel, dim3((nb + 127) / 128), dim3(128), 0, st, d_theta, nb, ndim, d_prior, d_params,
+                           pol->b_fixed[0], pol->b_fixed[1], pol->pi_max_fixed[0], pol->pi_max_fixed[1], d_order,
+                           c->d_polspec.as<double>(), reinterpret_cast<int*>(c->d_polspec.as<double>() + 4 * (size_t)nb));
+        HIPCHK(hipGetLastError());
+    }
+    for (int g = 0; g < n_pol_groups && rc == VAG_OK; ++g) {  // polarization groups: one pass each, the Stokes sums of sky_request
+        const vag_polarization_obs& o = pol->groups[g];
+        const double* ds = c->d_polfit.as<double>() + poff;  // [nu | t | q | u | err_q | err_u | weight]
+        poff += 1 + 6 * (size_t)o.n;
+        if (c->d_polstokes.ensure(sizeof(double) * (size_t)nb * o.n * 3)) return VAG_E_HIP;
+        rc = prep_times(c, ds + 1, o.n, ds, 1);
+        c->order_next = d_order != nullptr;
+        c->last_order = d_order;
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
+        if (rc == VAG_OK)
+            rc = pol_stokes_request(c, d_params, nb, o.n, o.n_az > 0 ? o.n_az : 256, c->d_polspec.as<double>(), c->d_polstokes.as<double>());
+        if (rc == VAG_OK) {
+            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
+            hipLaunchKernelGGL(vag_fit_pol_back_kernel, dim3(nb), dim3(64), 0, st, c->d_polstokes.as<double>(), o.n, o.kind, ds + 1,
+                               reinterpret_cast<const int*>(c->d_polspec.as<double>() + 4 * (size_t)nb), d_theta, ndim, d_prior,
+                               sky ? sky->pa_fixed : 0.0, c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
+                               (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
+                               pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order);
+            HIPCHK(hipGetLastError());
+            ++pass;
+            n_cap = std::max(n_cap, c->plan.n_models_capacity);
+            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+        }
+    }
     c->ic_soft_fail = false;
     c->plan.n_models_capacity = n_cap;
     c->plan.n_models_invalid = n_inv;
@@ -4126,6 +4378,34 @@ int vag_loglike_vis_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
     if (rc) return rc;
     rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis);
     if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis);
+    return rc;
+}
+
+int vag_loglike_pol_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                              const vag_pol_fit_spec* pol, const double* d_theta, int nb, int ndim, double* d_out) {
+    if (!pol || pol->n_groups == 0) return vag_loglike_vis_batch_dev(c, spec, sky, vis, d_theta, nb, ndim, d_out);  // exactly that call
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    if (vis && vis->n_groups == 0) vis = nullptr;
+    HIPCHK(hipSetDevice(c->device));
+    // (east0 / north0 place centroid and visibility groups only: without such a group they are refused as before)
+    int rc = upload_fit_spec(c, spec, ndim, (sky && sky->n_groups > 0) || vis, true);
+    if (rc) return rc;
+    if (sky) {  // (n_groups = 0: the fixed position angle alone)
+        rc = upload_sky_spec(c, sky);
+        if (rc) return rc;
+    }
+    if (vis) {
+        rc = upload_vis_spec(c, vis);
+        if (rc) return rc;
+    }
+    rc = upload_pol_spec(c, pol);
+    if (rc) return rc;
+    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol);
+    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol);
     return rc;
 }
 
@@ -4436,6 +4716,26 @@ int vag_loglike_vis_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fi
     double* d_out = d_theta + (size_t)nb * ndim;
     HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
     int rc = vag_loglike_vis_batch_dev(c, spec, sky, vis, d_theta, nb, ndim, d_out);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)collect_times(c);
+    return VAG_OK;
+}
+
+int vag_loglike_pol_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                          const vag_pol_fit_spec* pol, const double* theta, int nb, int ndim, double* out) {
+    if (!pol || pol->n_groups == 0) return vag_loglike_vis_batch(c, spec, sky, vis, theta, nb, ndim, out);  // exactly that call
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
+    double* d_theta = c->d_theta_in.as<double>();
+    double* d_out = d_theta + (size_t)nb * ndim;
+    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
+    int rc = vag_loglike_pol_batch_dev(c, spec, sky, vis, pol, d_theta, nb, ndim, d_out);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

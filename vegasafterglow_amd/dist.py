@@ -19,6 +19,8 @@ _NO_CENTROIDS = ("sharded likelihood calls do not support centroid data (Fitter.
                  "(Fitter.device_evaluator / log_prob_batch)")
 _NO_VISIBILITIES = ("sharded likelihood calls do not support visibility data (Fitter.add_visibilities): evaluate on one "
                     "device (Fitter.device_evaluator / log_prob_batch)")
+_NO_POLARIZATION = ("sharded likelihood calls do not support polarization data (Fitter.add_polarization): evaluate on one "
+                    "device (Fitter.device_evaluator / log_prob_batch)")
 
 
 def shard_range(n, rank, world):
@@ -91,6 +93,8 @@ class WalkerSharder:
             raise NotImplementedError(_NO_CENTROIDS)
         if getattr(eval_dev, "has_visibilities", False):
             raise NotImplementedError(_NO_VISIBILITIES)
+        if getattr(eval_dev, "has_polarization", False):
+            raise NotImplementedError(_NO_POLARIZATION)
         self.eval_dev, self.group = eval_dev, group
         self.device = device if device is not None else _default_device(group)
         self.native = getattr(eval_dev, "native", None)
@@ -189,6 +193,8 @@ def sharded_loglike(samples, local_eval, group=None, device=None):
         raise NotImplementedError(_NO_CENTROIDS)
     if getattr(getattr(local_eval, "__self__", None), "has_visibilities", False):
         raise NotImplementedError(_NO_VISIBILITIES)
+    if getattr(getattr(local_eval, "__self__", None), "has_polarization", False):
+        raise NotImplementedError(_NO_POLARIZATION)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     nb = samples.shape[0]
     if not (dist.is_available() and dist.is_initialized()):

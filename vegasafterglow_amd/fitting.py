@@ -168,6 +168,7 @@ class Fitter:
         self._band_obs = []
         self._centroid_obs = []  # VLBI centroid groups (add_centroid): one vag_centroid_obs each
         self._vis_obs = []  # VLBI visibility groups (add_visibilities): one vag_visibility_obs each
+        self._pol_obs = []  # polarization groups (add_polarization): one vag_polarization_obs each
         self._ext_kernel = None
         self._ext_kernels = {}  # z -> 0.4 ln10 k(lambda_rest) over the consolidated point data
         self._ext_z = float(z)
@@ -341,13 +342,68 @@ class Fitter:
     def has_visibilities(self):
         return bool(self._vis_obs)
 
+    def add_polarization(self, nu, t, q, u=None, err_q=None, err_u=None, weights=None, n_az=None, kind="qu"):
+        """Linear polarization measurements at one frequency nu [Hz] at ascending times t [s].  kind="qu": q = Q/I and u = U/I on
+        the sky (IAU, as SkyPolarization.q / .u) with errors err_q, err_u; the group is its own request: the model Stokes values
+        are Model.sky_polarization(t, nu, b, pi_max, b_rvs, pi_max_rvs, pa, n_az) with the parameters "pol_b", "pol_pi_max",
+        "pol_b_rvs", "pol_pi_max_rvs" (free or fixed; defaults as sky_polarization: b = 0, the reverse shock follows the forward b,
+        pi_max from the walker's own p) and "pa" (shared with the centroid and visibility groups), and adds
+        sum_i w_i [((q_i - Q/I) / err_q_i)^2 + ((u_i - U/I) / err_u_i)^2] to chi^2.  kind="degree": q holds the polarization degree
+        and err_q its error (u, err_u are not used); the term is sum_i w_i ((q_i - hypot(Q, U)/I) / err_q_i)^2 and "pa" drops out.
+        n_az: azimuthal parts per circle of the model (default 256, Model.sky_polarization's own).  Weights are used as given."""
+        who = "add_polarization"
+        nu = float(np.asarray(nu, dtype=np.float64)) if np.ndim(nu) == 0 else None
+        if nu is None or not np.isfinite(nu) or nu <= 0:
+            raise ValueError(f"{who}: nu must be one finite frequency > 0")
+        if kind not in _lib.POL_KINDS:
+            raise ValueError(f"{who}: kind must be 'qu' or 'degree', got {kind!r}")
+        if n_az is not None and (int(n_az) != n_az or n_az < 1):
+            raise ValueError(f"{who}: n_az must be an integer >= 1 (or None for 256), got {n_az!r}")
+        if err_q is None:
+            raise ValueError(f"{who}: err_q is required")
+        qu = kind == "qu"
+        if qu and (u is None or err_u is None):
+            raise ValueError(f"{who}: kind='qu' needs u and err_u")
+        names = ("t", "q", "err_q") + (("u", "err_u") if qu else ())
+        given = dict(t=t, q=q, err_q=err_q, u=u, err_u=err_u)
+        arrs = {k: np.asarray(given[k], dtype=np.float64) for k in names}
+        t = arrs["t"]
+        if t.ndim != 1 or t.size == 0:
+            raise ValueError(f"{who}: t must be a non-empty 1-D array")
+        if any(a.shape != t.shape for a in arrs.values()):
+            raise ValueError(f"{who}: {', '.join(names)} must have the same shape; got {[a.shape for a in arrs.values()]}")
+        if not all(np.isfinite(a).all() for a in arrs.values()):
+            raise ValueError(f"{who}: t, measurements and errors must be finite")
+        if (t <= 0).any() or (np.diff(t) < 0).any():
+            raise ValueError(f"{who}: times must be > 0 and ascending")
+        if any((arrs[k] <= 0).any() for k in names if k.startswith("err")):
+            raise ValueError(f"{who}: errors must be > 0 at every epoch")
+        if qu and ((np.abs(arrs["q"]) > 1).any() or (np.abs(arrs["u"]) > 1).any()):
+            raise ValueError(f"{who}: |q| and |u| must be <= 1")
+        if not qu and ((arrs["q"] < 0).any() or (arrs["q"] > 1).any()):
+            raise ValueError(f"{who}: the polarization degree must be in [0, 1]")
+        if weights is None:
+            w = np.ones_like(t)
+        else:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape != t.shape or not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError(f"{who}: weights must have the shape of t and be finite and >= 0")
+        c = np.ascontiguousarray
+        self._pol_obs.append(dict(nu=nu, t=c(t), q=c(arrs["q"]), err_q=c(arrs["err_q"]), u=c(arrs["u"]) if qu else None,
+                                  err_u=c(arrs["err_u"]) if qu else None, weights=c(w), n_az=None if n_az is None else int(n_az),
+                                  kind=kind))
+
+    @property
+    def has_polarization(self):
+        return bool(self._pol_obs)
+
     # fitter.py:407-451
     def _consolidate_data(self):
         if self._all_t is not None:
             return
         if not self._point_t:
-            if not self._band_obs and not self._centroid_obs and not self._vis_obs:
-                raise ValueError("no data: call add_flux_density, add_flux, add_centroid or add_visibilities first")
+            if not self._band_obs and not self._centroid_obs and not self._vis_obs and not self._pol_obs:
+                raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities or add_polarization first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
             return
         t = np.concatenate(self._point_t)
@@ -424,7 +480,7 @@ class Fitter:
         # duration aliases ...) go straight into their slot, exactly like a free parameter would
         base_fields = (C.c_double * 40).from_address(C.addressof(spec.base) + _lib.ModelParams.theta_c.offset)
         for name, value in fixed.items():
-            if name in MODEL_PARAM_DEFAULTS or name == "A_V" or name in _lib.SKY_SLOTS:
+            if name in MODEL_PARAM_DEFAULTS or name == "A_V" or name in _lib.SKY_SLOTS or name in _lib.POL_SLOTS:
                 continue
             if name not in _lib.PARAM_SLOTS:
                 raise ValueError(f"parameter {name} is not accepted by the accelerated path")
@@ -435,18 +491,19 @@ class Fitter:
                 spec.slot[d] = _lib.P_A_V
             elif pd.name in _lib.SKY_SLOTS:
                 spec.slot[d] = _lib.SKY_SLOTS[pd.name]
+            elif pd.name in _lib.POL_SLOTS:
+                spec.slot[d] = _lib.POL_SLOTS[pd.name]
             elif pd.name not in _lib.PARAM_SLOTS:
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             else:
                 spec.slot[d] = _lib.PARAM_SLOTS[pd.name]
             spec.is_log[d] = 1 if pd.scale is Scale.log else 0
         spec.a_v_fixed = float(fixed.get("A_V", 0.0))
-        if any(pd.name in _lib.SKY_SLOTS for pd in param_defs) and not self._centroid_obs and not self._vis_obs:
-            raise ValueError("the parameters 'pa', 'east0' and 'north0' need centroid data (Fitter.add_centroid) or visibility "
-                             "data (Fitter.add_visibilities)")
-        # (a fit with visibility groups only still carries the fixed placement in a vag_sky_fit_spec without groups)
-        spec._sky = self._sky_spec(fixed) if self._centroid_obs or self._vis_obs else None
+        self._check_sky_parameters(param_defs)
+        # (a fit with visibility or polarization groups only still carries the fixed placement in a vag_sky_fit_spec without groups)
+        spec._sky = self._sky_spec(fixed) if self._centroid_obs or self._vis_obs or self._pol_obs else None
         spec._vis = self._vis_spec() if self._vis_obs else None
+        spec._pol = self._pol_spec(fixed) if self._pol_obs else None
         if self.extinction is not None and any(pd.name == "z" for pd in free):
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
@@ -524,6 +581,64 @@ class Fitter:
         vis._keep_alive = (groups, list(self._vis_obs))
         return vis
 
+    def _check_sky_parameters(self, param_defs):
+        """The parameters that are read by sky data only need such data."""
+        names = [pd.name for pd in param_defs]
+        placed = self._centroid_obs or self._vis_obs
+        self._check_pol_parameters(names)
+        if "pa" in names and not placed and not self._pol_obs:
+            raise ValueError("the parameters 'pa', 'east0' and 'north0' need centroid data (Fitter.add_centroid) or visibility "
+                             "data (Fitter.add_visibilities); 'pa' is also read by polarization data (Fitter.add_polarization)")
+        if any(n in ("east0", "north0") for n in names) and not placed:
+            raise ValueError("the parameters 'east0' and 'north0' need centroid data (Fitter.add_centroid) or visibility data "
+                             "(Fitter.add_visibilities)")
+
+    def _check_pol_parameters(self, names):
+        if any(n in _lib.POL_SLOTS for n in names) and not self._pol_obs:
+            raise ValueError("the parameters 'pol_b', 'pol_pi_max', 'pol_b_rvs' and 'pol_pi_max_rvs' need polarization data "
+                             "(Fitter.add_polarization)")
+
+    def _pol_spec(self, fixed):
+        """vag_pol_fit_spec of the polarization groups and the fixed field parameters; it keeps the arrays it points at alive."""
+        pol = _lib.PolFitSpec()
+        groups = (_lib.PolarizationObs * len(self._pol_obs))()
+        for g, pd in enumerate(self._pol_obs):
+            o = groups[g]
+            o.nu, o.n, o.n_az, o.kind = pd["nu"], pd["t"].size, pd["n_az"] or 0, _lib.POL_KINDS[pd["kind"]]
+            for name in ("t", "q", "u", "err_q", "err_u"):
+                setattr(o, name, pd[name].ctypes.data_as(_dp) if pd[name] is not None else None)
+            o.weight = pd["weights"].ctypes.data_as(_dp)
+        pol.n_groups, pol.groups = len(self._pol_obs), groups
+        # the defaults of Model.sky_polarization: b = 0, the reverse shock follows the forward b (< 0), pi_max from p (< 0)
+        pol.b_fixed[0], pol.b_fixed[1] = float(fixed.get("pol_b", 0.0)), float(fixed.get("pol_b_rvs", -1.0))
+        pol.pi_max_fixed[0], pol.pi_max_fixed[1] = float(fixed.get("pol_pi_max", -1.0)), float(fixed.get("pol_pi_max_rvs", -1.0))
+        for name in _lib.POL_SLOTS:
+            if name in fixed and (not np.isfinite(fixed[name]) or fixed[name] < 0 or (name.startswith("pol_pi_max") and fixed[name] > 1)):
+                raise ValueError(f"a fixed {name} must be finite and >= 0" + (" and <= 1" if name.startswith("pol_pi_max") else ""))
+        pol._keep_alive = (groups, list(self._pol_obs))
+        return pol
+
+    def polarization(self, best_params, param_defs, resolution=None):
+        """The model polarization at the epochs of every polarization group at a point of sampler space: a list of
+        SkyPolarization, one per group, each one Model.sky_polarization request at the group's epochs, frequency and n_az with
+        the sample's pa and field parameters."""
+        spec, _, _ = self.build_spec(param_defs)
+        sample = np.asarray(best_params, dtype=np.float64).reshape(-1)
+        vals = dict(pa=spec._sky.pa_fixed if spec._sky is not None else 0.0, pol_b=0.0, pol_pi_max=None, pol_b_rvs=None,
+                    pol_pi_max_rvs=None)
+        if spec._pol is not None:
+            vals["pol_b"] = spec._pol.b_fixed[0]
+            vals["pol_b_rvs"] = spec._pol.b_fixed[1] if spec._pol.b_fixed[1] >= 0 else None
+            vals["pol_pi_max"] = spec._pol.pi_max_fixed[0] if spec._pol.pi_max_fixed[0] >= 0 else None
+            vals["pol_pi_max_rvs"] = spec._pol.pi_max_fixed[1] if spec._pol.pi_max_fixed[1] >= 0 else None
+        by_slot = {slot: name for name, slot in {**_lib.SKY_SLOTS, **_lib.POL_SLOTS}.items()}
+        for d in range(spec.ndim):
+            if by_slot.get(spec.slot[d]) in vals:
+                vals[by_slot[spec.slot[d]]] = 10.0 ** sample[d] if spec.is_log[d] else sample[d]
+        model = self.model(best_params, param_defs, resolution)
+        return [model.sky_polarization(pd["t"], pd["nu"], b=vals["pol_b"], pi_max=vals["pol_pi_max"], b_rvs=vals["pol_b_rvs"],
+                                       pi_max_rvs=vals["pol_pi_max_rvs"], pa=vals["pa"], n_az=pd["n_az"]) for pd in self._pol_obs]
+
     def visibilities(self, best_params, param_defs, resolution=None):
         """The model visibilities at the data of every visibility group at a point of sampler space: a list of complex128 arrays,
         one per group, in the order and layout the data were added.  Each group is one Model.sky_visibilities request at the
@@ -556,7 +671,7 @@ class Fitter:
         if len(set(names)) != len(names):
             raise ValueError("duplicate parameter names")
         for pd in param_defs:
-            if pd.name != "A_V" and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS:
+            if pd.name != "A_V" and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS and pd.name not in _lib.POL_SLOTS:
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             if pd.scale is Scale.fixed:
                 continue
@@ -566,6 +681,7 @@ class Fitter:
                 raise ValueError(f"{pd.name}: log-scale parameters need lower > 0")
         if "A_V" in names and self.extinction is None:
             raise ValueError("A_V needs Fitter(extinction=...)")
+        self._check_pol_parameters(names)
 
     def _params_at(self, sample, param_defs, resolution=None):
         """vag_model_params and A_V of one point of sampler space (the transformer of fitting/utils.py:110-135)."""
@@ -668,7 +784,11 @@ class Fitter:
             costs = torch.empty((k,), dtype=torch.float64, device=dev) if want_costs else None
 
             def run():
-                if keep[0]._vis is not None:
+                if keep[0]._pol is not None:
+                    _lib.check(lib.vag_loglike_pol_batch_dev(
+                        h, C.byref(keep[0]), C.byref(keep[0]._sky), C.byref(keep[0]._vis) if keep[0]._vis is not None else None,
+                        C.byref(keep[0]._pol), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
+                elif keep[0]._vis is not None:
                     _lib.check(lib.vag_loglike_vis_batch_dev(h, C.byref(keep[0]), C.byref(keep[0]._sky), C.byref(keep[0]._vis),
                                                              theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
                 elif keep[0]._sky is not None:
@@ -683,6 +803,7 @@ class Fitter:
         eval_dev.optional_costs = True
         eval_dev.has_centroids = spec._sky is not None and spec._sky.n_groups > 0
         eval_dev.has_visibilities = spec._vis is not None
+        eval_dev.has_polarization = spec._pol is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -693,6 +814,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._pol is not None:
+                    from .dist import _NO_POLARIZATION
+                    raise NotImplementedError(_NO_POLARIZATION)
                 if keep[0]._vis is not None:
                     from .dist import _NO_VISIBILITIES
                     raise NotImplementedError(_NO_VISIBILITIES)
@@ -724,7 +848,11 @@ class Fitter:
         h, lock = get_context(self.device)
         plan = _lib.Plan()
         with lock:
-            if spec._vis is not None:
+            if spec._pol is not None:
+                _lib.check(_lib.load().vag_loglike_pol_batch(
+                    h, C.byref(spec), C.byref(spec._sky), C.byref(spec._vis) if spec._vis is not None else None, C.byref(spec._pol),
+                    samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
+            elif spec._vis is not None:
                 _lib.check(_lib.load().vag_loglike_vis_batch(h, C.byref(spec), C.byref(spec._sky), C.byref(spec._vis),
                                                              samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
                                                              out.ctypes.data_as(_dp)))
