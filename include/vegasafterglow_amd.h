@@ -286,6 +286,7 @@ enum {
     VAG_MATH_SP_FAST, VAG_MATH_SP_FAST_GLOBAL, VAG_MATH_SP_FAST_SEL,
     VAG_MATH_SYN_CELL, VAG_MATH_IC_CELL,
     VAG_MATH_WAVE_PREFIX_SUM, VAG_MATH_WAVE_SUM, VAG_MATH_SKY_WAVE_SUM, VAG_MATH_LDS_ADD,
+    VAG_MATH_LOG_NDTR, /* ln Phi(z) of the upper-limit term (vag_loglike_lim_batch) */
     VAG_MATH_COUNT
 };
 int vag_debug_device_math(vag_ctx* ctx, int fn, const double* in, int n, double* out);
@@ -527,7 +528,8 @@ int vag_loglike_vis_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_
  * to the walker's chi^2; kind = VAG_POL_DEGREE: q, err_q hold the degree Pi_i and its error, u and err_u are ignored (may be NULL),
  * and the group adds sum_i weight_i ((Pi_i - hypot(Q, U)/I) / err_q_i)^2 (the position angle drops out).  Weights are used as given.
  * Limits: at most VAG_POL_MAX_GROUPS groups of at most VAG_VIS_MAX_EPOCHS epochs; more is refused with VAG_E_INVALID.  Upper
- * limits, circular polarization and several frequencies in one group are not supported. */
+ * limits on the degree (kind = VAG_POL_DEGREE) are supported through vag_loglike_lim_batch (vag_limit_fit_spec.pol_kind); upper
+ * limits on q / u, on visibilities and on centroids, circular polarization and several frequencies in one group are not supported. */
 #define VAG_POL_QU 0
 #define VAG_POL_DEGREE 1
 #define VAG_POL_MAX_GROUPS 64
@@ -569,6 +571,47 @@ int vag_loglike_pol_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_
                           const vag_pol_fit_spec* pol, const double* theta, int nb, int ndim, double* out);
 int vag_loglike_pol_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                               const vag_pol_fit_spec* pol, const double* d_theta, int nb, int ndim, double* d_out);
+
+/* Upper limits (non-detections) in the likelihood (added after VAG_ABI_VERSION 13, detect by symbol).  A limit row has a limit value
+ * L and a noise level sigma > 0, both in the units of the datum it replaces, and adds
+ *   -2 weight ln Phi((L - M) / sigma)
+ * to the walker's chi^2 (ln L gains weight ln Phi(z)); Phi is the standard normal CDF, the weight is used as given, and M is the model
+ * value: for a point row the model flux density after the extinction factor exp(-A_V k_i), without the 1e-300 clamp of the detection
+ * term (a model with no flux satisfies a limit); for a row of a band group the band-integrated model flux; for a row of a
+ * polarization group of kind VAG_POL_DEGREE hypot(Q, U) / I.  "A 3 sigma upper limit of X" is L = X, sigma = X / 3: the noise is
+ * additive, so the term is in linear flux, not in ln F like the detections.  ln Phi is evaluated in FP64 in a form that stays finite
+ * and accurate far into the tail (a model 1e6 sigma above a limit scores a finite, very negative value).
+ * vag_limit_rows is parallel to the n rows it annotates: the rows keep their place in the sorted rows of vag_fit_spec / vag_band_obs
+ * and ride in the pass that is evaluated anyway; on a limit row ln_flux / ln_err are ignored (the host writes 0 and 1 there). */
+#define VAG_OBS_DETECTION 0
+#define VAG_OBS_UPPER_LIMIT 1
+typedef struct vag_limit_rows {      /* parallel to the n rows it annotates; kind == NULL: no limit row */
+    const int32_t* kind;             /* [n] VAG_OBS_* */
+    const double* limit;             /* [n] L  (read on limit rows only) */
+    const double* sigma;             /* [n] > 0 (read on limit rows only) */
+} vag_limit_rows;
+typedef struct vag_limit_fit_spec {
+    vag_limit_rows point;            /* parallel to spec->t[n_data] */
+    int32_t n_bands, pad;            /* 0 or spec->n_bands */
+    const vag_limit_rows* bands;     /* [n_bands], parallel to spec->bands[g] */
+    int32_t n_pol_groups, pad2;      /* 0 or pol->n_groups */
+    const int32_t* const* pol_kind;  /* [n_pol_groups] each [n] or NULL; L = q[i], sigma = err_q[i] of the group */
+} vag_limit_fit_spec;
+
+/* vag_loglike_pol_batch(_dev) with upper limits: every row flagged VAG_OBS_UPPER_LIMIT adds the limit term above instead of its
+ * detection term, in the same pass and at the same place of the sum.  Validity is unchanged: a NaN model value makes chi^2
+ * non-finite and the walker scores -inf, a polarization limit keeps its group's I <= 0 rule, a failed pass scores -inf; all of them
+ * count in n_walkers_rejected.  Refused with VAG_E_INVALID (the message names the row): a kind other than VAG_OBS_*, a limit that
+ * is not finite or (fluxes) < 0, a sigma that is not finite and > 0, a polarization limit outside [0, 1], a limit row in a
+ * VAG_POL_QU group, n_bands / n_pol_groups that are neither 0 nor their partner's count.  With lim NULL or no limit row anywhere
+ * the call is vag_loglike_pol_batch(_dev), bit for bit; a block whose kind is NULL (or all VAG_OBS_DETECTION) takes the same code
+ * as there.  Results are bitwise reproducible and a walker's value does not depend on the rest of the batch.  The limit arrays stay
+ * resident on the device by content hash. */
+int vag_loglike_lim_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                          const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const double* theta, int nb, int ndim, double* out);
+int vag_loglike_lim_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                              const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const double* d_theta, int nb, int ndim,
+                              double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

@@ -54,7 +54,7 @@ class BandObs(C.Structure):
 MATH = {name: i for i, name in enumerate([
     "exp2_fast", "exp2_ode", "exp2_sat", "exp2_or_zero", "log2_fast", "log2_tab", "log2_tab_nb",
     "rcp_fast", "rcp_ode", "rcp1", "sqrt_fast", "sqrt_ode", "sqrt1", "sp_fast", "sp_fast_global", "sp_fast_sel",
-    "syn_cell", "ic_cell", "wave_prefix_sum", "wave_sum", "sky_wave_sum", "lds_add"])}
+    "syn_cell", "ic_cell", "wave_prefix_sum", "wave_sum", "sky_wave_sum", "lds_add", "log_ndtr"])}
 
 P_A_V = 1000  # VAG_P_A_V
 # VAG_P_SKY_*: the sky placement of the centroid and visibility groups (vag_loglike_sky_batch / _vis_batch), not Model fields either
@@ -103,6 +103,18 @@ class PolarizationObs(C.Structure):  # vag_polarization_obs
 class PolFitSpec(C.Structure):  # vag_pol_fit_spec
     _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(PolarizationObs)),
                 ("b_fixed", C.c_double * 2), ("pi_max_fixed", C.c_double * 2)]
+
+
+OBS_DETECTION, OBS_UPPER_LIMIT = 0, 1  # VAG_OBS_*
+
+
+class LimitRows(C.Structure):  # vag_limit_rows
+    _fields_ = [("kind", C.POINTER(C.c_int32)), ("limit", C.POINTER(C.c_double)), ("sigma", C.POINTER(C.c_double))]
+
+
+class LimitFitSpec(C.Structure):  # vag_limit_fit_spec
+    _fields_ = [("point", LimitRows), ("n_bands", C.c_int32), ("pad", C.c_int32), ("bands", C.POINTER(LimitRows)),
+                ("n_pol_groups", C.c_int32), ("pad2", C.c_int32), ("pol_kind", C.POINTER(C.POINTER(C.c_int32)))]
 
 
 class FitSpec(C.Structure):
@@ -168,6 +180,7 @@ EXPORTS = [
     "vag_sky_image_batch", "vag_sky_moments_batch", "vag_sky_centroid_batch", "vag_loglike_sky_batch", "vag_loglike_sky_batch_dev",
     "vag_sky_visibility_batch", "vag_debug_device_math", "vag_loglike_vis_batch", "vag_loglike_vis_batch_dev",
     "vag_sky_polarization_batch", "vag_sky_stokes_image_batch", "vag_loglike_pol_batch", "vag_loglike_pol_batch_dev",
+    "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev",
 ]
 
 _lib = None
@@ -227,6 +240,10 @@ def load():
                                           C.c_int, C.c_int, _dp]
     lib.vag_loglike_pol_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec), v,
                                               C.c_int, C.c_int, v]
+    lib.vag_loglike_lim_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
+                                          C.POINTER(LimitFitSpec), _dp, C.c_int, C.c_int, _dp]
+    lib.vag_loglike_lim_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
+                                              C.POINTER(LimitFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -26,6 +26,7 @@
 #include "vag_grid_rows.h"
 #include "vag_sky.h"
 #include "vag_debug_math.h"
+#include "vag_log_ndtr.h"
 
 using namespace vag;
 
@@ -409,6 +410,7 @@ struct vag_ctx {
     DevBuf d_skycen, d_skycmom, d_skyfit;  // exact centroids (vag_sky.h): row-block partials, moments, centroid-fit pass data
     DevBuf d_visfit, d_visblk, d_vispart;  // visibility groups of the likelihood: their data, their 64-visibility blocks, chi^2 partials
     DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
+    DevBuf d_limfit;  // upper-limit rows of the likelihood (vag_loglike_lim_batch): per block [limit | sigma | kind], see LimLayout
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
     bool ic_all_cells = false;    // this request's SSC tables are built for every cell (the lazy selection was caught with a hole, see check_ic_status)
@@ -462,7 +464,7 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit, h_polfit;
+    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
@@ -478,6 +480,9 @@ struct vag_ctx {
     uint64_t polfit_hash = 0;  // (d_polfit: the polarization groups of vag_loglike_pol_batch, upload_pol_spec)
     size_t polfit_doubles = 0;
     bool polfit_hash_valid = false;
+    uint64_t limfit_hash = 0;  // (d_limfit: the limit rows of vag_loglike_lim_batch, upload_lim_spec)
+    size_t limfit_doubles = 0;
+    bool limfit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -713,8 +718,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_skyfit.release();
     c->h_visfit.release();
     c->h_polfit.release();
+    c->h_limfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3746,6 +3752,72 @@ vag_fit_back_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const 
     }
 }
 
+// vag_fit_back_kernel for a pass with upper-limit rows (vag_loglike_lim_batch): a row with lim_kind[i] == VAG_OBS_UPPER_LIMIT adds
+//   -2 w_i ln Phi((L_i - F_model,i e^{-A_V k_i}) / sigma_i)   (vag::log_ndtr; no 1e-300 clamp: a model with no flux satisfies a limit)
+// instead of its detection term, at the same place of the lane's sum; everything else is that kernel's, statement for statement.
+// A kernel of its own so that a pass without limit rows runs the instructions it always ran.
+__global__ void __launch_bounds__(64)
+vag_fit_back_lim_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const double* __restrict__ ln_flux,
+                    const double* __restrict__ ln_err, const double* __restrict__ weight, const double* __restrict__ ext /* or null */,
+                    const double* __restrict__ a_v, const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status,
+                    const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */, double* __restrict__ chi2,
+                    int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out,
+                    int* __restrict__ fitstat /* [0] walkers scored -inf, [1] of those: SSC table failures */,
+                    const int* __restrict__ order /* evaluation slot -> walker, or null */,
+                    const float* __restrict__ cost /* with next_order: the slots' costs of THIS call (the grid kernel's plan scan leaves them) */,
+                    int nb, int* __restrict__ next_order /* or null: [rank] = walker, descending cost */,
+                    const int* __restrict__ lim_kind /* [n] VAG_OBS_* */, const double* __restrict__ lim_L /* [n] */,
+                    const double* __restrict__ lim_sigma /* [n] */) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    // next_order[rank] = walker, ranks by descending cost of the slot in THIS call (cost[] is in evaluation-slot order: `order` maps a slot
+    // back to its walker; null = identity).  Ranking by counting: the lanes compare this wavefront's slot with all others.  (Until round 5
+    // a launch of its own, vag_order_kernel, behind this kernel.)
+    if (next_order) {
+        const float mine = cost[m];
+        int rank = 0;
+        for (int i0 = 0; i0 < nb; i0 += 64) {
+            const int i = i0 + lane;
+            const float c = i < nb ? cost[i] : -1.0f;
+            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
+        }
+        if (lane == 0) next_order[rank] = order ? order[m] : m;
+    }
+    const double av = (ext != nullptr) ? a_v[m] : 0.0;
+    const bool grid_ok = meta[m].status == 0;
+    double s = 0;
+    if (grid_ok)
+        for (int i = lane; i < n; i += 64) {
+            double f = flux[(size_t)m * n + i];
+            if (av != 0.0) f = f * exp(-av * ext[i]);
+            if (lim_kind[i] == VAG_OBS_UPPER_LIMIT) {
+                s += weight[i] * (-2.0 * vag::log_ndtr((lim_L[i] - f) / lim_sigma[i]));
+                continue;
+            }
+            const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+            const double q = (ln_flux[i] - log(fm)) / ln_err[i];
+            s += weight[i] * (q * q);
+        }
+    s = vag::wave_sum(s);
+    bool bad_row = false;
+    if (grid_ok)
+        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
+    const bool any_bad = __any(bad_row);
+    if (lane == 0) {
+        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
+        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
+        const double acc = first ? s : chi2[m] + s;
+        valid[m] = ok;
+        chi2[m] = acc;
+        if (ic_bad) atomicAdd(fitstat + 1, 1);
+        if (last) {
+            const double lp = ln_prior[m];
+            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
+            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
+            if (!fin) atomicAdd(fitstat, 1);
+        }
+    }
+}
+
 // ---- centroid groups (vag_loglike_sky_batch): their data in one device buffer, uploaded like the fit spec when its hash changes.
 //      Layout in doubles, per group: [nu | t | east | north | err_east | err_north | weight] (1 + 6 n). ----
 static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
@@ -4138,9 +4210,178 @@ vag_fit_pol_back_kernel(const double* __restrict__ stokes /* [nb][n][3] jet fram
     }
 }
 
+// vag_fit_pol_back_kernel for a DEGREE group with upper-limit epochs (vag_loglike_lim_batch): an epoch with lim_kind[i] ==
+// VAG_OBS_UPPER_LIMIT adds -2 w_i ln Phi((q_i - hypot(Q, U) / I) / err_q_i) instead of its detection term (q holds the limit, err_q
+// its noise level); the I <= 0 rule stays.  Everything else is that kernel's, statement for statement; a kernel of its own so that
+// a group without limit epochs runs the instructions it always ran.
+__global__ void __launch_bounds__(64)
+vag_fit_pol_back_lim_kernel(const double* __restrict__ stokes /* [nb][n][3] jet frame */, int n, int kind,
+                        const double* __restrict__ obs /* [t|q|u|eq|eu|w] */, const int* __restrict__ spec_bad,
+                        const double* __restrict__ theta, int ndim, const double* __restrict__ prior, double pa_fixed,
+                        const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status, const int* __restrict__ row_off,
+                        const int* __restrict__ ic_status, double* __restrict__ chi2, int* __restrict__ valid,
+                        const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out, int* __restrict__ fitstat,
+                        const int* __restrict__ order, const int* __restrict__ lim_kind /* [n] VAG_OBS_* */) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    const int walker = order ? order[m] : m;
+    double pa = pa_fixed, e0 = 0, n0 = 0;
+    vag::sky_placement(theta, walker, ndim, prior, pa, e0, n0);
+    double s2, c2;
+    sincos(2 * pa, &s2, &c2);
+    const double *q_obs = obs + n, *u_obs = obs + 2 * (size_t)n, *q_err = obs + 3 * (size_t)n, *u_err = obs + 4 * (size_t)n,
+                 *w = obs + 5 * (size_t)n;
+    const bool grid_ok = meta[m].status == 0;
+    double s = 0;
+    bool bad = spec_bad[m] != 0;
+    if (grid_ok)
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane, cnt = min(64, n - i0);
+            double term = 0;
+            if (i < n) {
+                const double* sk = stokes + ((size_t)m * n + i) * 3;
+                const double I = sk[0], Q = sk[1], U = sk[2];
+                bad = bad || !(I > 0) || !isfinite(I) || !isfinite(Q) || !isfinite(U);
+                if (kind == VAG_POL_DEGREE) {
+                    const double r = (q_obs[i] - hypot(Q, U) / I) / q_err[i];
+                    term = w[i] * (lim_kind[i] == VAG_OBS_UPPER_LIMIT ? -2.0 * vag::log_ndtr(r) : r * r);
+                } else {
+                    const double Qs = Q * c2 - U * s2, Us = Q * s2 + U * c2;
+                    const double rq = (q_obs[i] - Qs / I) / q_err[i], ru = (u_obs[i] - Us / I) / u_err[i];
+                    term = w[i] * (rq * rq + ru * ru);
+                }
+            }
+            for (int j = 0; j < cnt; ++j) s += vag::wave_bcast(term, j);  // every lane: the epochs in order
+        }
+    if (grid_ok)
+        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad = bad || row_status[r] == 1;
+    const bool any_bad = __any(bad);
+    if (lane == 0) {
+        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
+        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
+        const double acc = first ? s : chi2[m] + s;
+        valid[m] = ok;
+        chi2[m] = acc;
+        if (ic_bad) atomicAdd(fitstat + 1, 1);
+        if (last) {
+            const double lp = ln_prior[m];
+            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
+            out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
+            if (!fin) atomicAdd(fitstat, 1);
+        }
+    }
+}
+
+// ---- upper-limit rows (vag_loglike_lim_batch): the blocks that hold a limit row, in one device buffer, uploaded like the other spec
+//      blocks when the hash changes.  Layout in doubles: a flux block (the point rows, a band group) of n rows is
+//      [limit | sigma | kind] (n, n, int32 [n] in (n + 1) / 2 doubles), a polarization group's block [kind] alone (its L and sigma are
+//      the group's q and err_q in d_polfit).  A block without a limit row is not stored (offset -1): its pass is the pass without
+//      limits.  Rows that are detections hold limit 0 and sigma 1, whatever the caller's arrays hold there. ----
+struct LimLayout {
+    long point = -1;              // offset of the point rows' block in d_limfit, or -1
+    std::vector<long> band, pol;  // the same per band group / polarization group
+    bool any = false;             // some limit row exists
+};
+
+static void lim_push_kinds(std::vector<double>& stage, const int32_t* kind, int n) {
+    const size_t at = stage.size();
+    stage.resize(at + ((size_t)n + 1) / 2, 0.0);
+    std::memcpy(stage.data() + at, kind, sizeof(int32_t) * n);
+}
+
+// Checks one flux block of lim (what / g name it in messages) and appends it to stage when it holds a limit row.
+static int lim_flux_block(const vag_limit_rows& r, int n, const char* what, int g, std::vector<double>& stage, long& off, bool& any) {
+    off = -1;
+    if (!r.kind || n <= 0) return VAG_OK;
+    bool here = false;
+    for (int i = 0; i < n; ++i) {
+        if (r.kind[i] != VAG_OBS_DETECTION && r.kind[i] != VAG_OBS_UPPER_LIMIT)
+            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: unknown kind %d", what, g, i, r.kind[i]);
+        if (r.kind[i] != VAG_OBS_UPPER_LIMIT) continue;
+        if (!r.limit || !r.sigma) return set_err(VAG_E_INVALID, "limit rows, %s %d: null limit or sigma array", what, g);
+        if (!std::isfinite(r.limit[i]) || r.limit[i] < 0)
+            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: the limit must be finite and >= 0", what, g, i);
+        if (!std::isfinite(r.sigma[i]) || !(r.sigma[i] > 0))
+            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: sigma must be finite and > 0", what, g, i);
+        here = true;
+    }
+    if (!here) return VAG_OK;
+    any = true;
+    off = (long)stage.size();
+    for (int i = 0; i < n; ++i) stage.push_back(r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.limit[i] : 0.0);
+    for (int i = 0; i < n; ++i) stage.push_back(r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.sigma[i] : 1.0);
+    lim_push_kinds(stage, r.kind, n);
+    return VAG_OK;
+}
+
+// Validates lim against its partners and lays its blocks out in stage (host work only: no context is touched).
+static int lim_scan(const vag_fit_spec* spec, const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, std::vector<double>& stage,
+                    LimLayout& lay) {
+    const int n_pol = pol ? pol->n_groups : 0;
+    if (lim->n_bands != 0 && lim->n_bands != spec->n_bands)
+        return set_err(VAG_E_INVALID, "limit rows: n_bands must be 0 or the fit spec's %d, got %d", spec->n_bands, lim->n_bands);
+    if (lim->n_pol_groups != 0 && lim->n_pol_groups != n_pol)
+        return set_err(VAG_E_INVALID, "limit rows: n_pol_groups must be 0 or the %d polarization groups, got %d", n_pol, lim->n_pol_groups);
+    if ((lim->n_bands > 0 && !lim->bands) || (lim->n_pol_groups > 0 && !lim->pol_kind))
+        return set_err(VAG_E_INVALID, "limit rows: null band or polarization list");
+    if (lim->point.kind && spec->n_data > 0 && !spec->t) return set_err(VAG_E_INVALID, "limit rows: the fit spec has no point rows");
+    int rc = lim_flux_block(lim->point, spec->n_data, "point rows", 0, stage, lay.point, lay.any);
+    if (rc) return rc;
+    lay.band.assign(std::max(spec->n_bands, 0), -1);
+    for (int g = 0; g < lim->n_bands; ++g) {
+        if (!spec->bands) return set_err(VAG_E_INVALID, "limit rows: the fit spec has no band groups");
+        rc = lim_flux_block(lim->bands[g], spec->bands[g].n, "band group", g, stage, lay.band[g], lay.any);
+        if (rc) return rc;
+    }
+    lay.pol.assign(std::max(n_pol, 0), -1);
+    for (int g = 0; g < lim->n_pol_groups; ++g) {
+        const int32_t* kind = lim->pol_kind[g];
+        if (!kind) continue;
+        if (!pol->groups) return set_err(VAG_E_INVALID, "bad polarization group list");
+        const vag_polarization_obs& o = pol->groups[g];
+        bool here = false;
+        for (int i = 0; i < o.n; ++i) {
+            if (kind[i] != VAG_OBS_DETECTION && kind[i] != VAG_OBS_UPPER_LIMIT)
+                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: unknown kind %d", g, i, kind[i]);
+            if (kind[i] != VAG_OBS_UPPER_LIMIT) continue;
+            if (o.kind != VAG_POL_DEGREE)
+                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: only VAG_POL_DEGREE groups take upper limits", g, i);
+            if (!o.q || !o.err_q) return set_err(VAG_E_INVALID, "polarization group %d: null array", g);
+            if (!std::isfinite(o.q[i]) || o.q[i] < 0 || o.q[i] > 1)
+                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: the limit must lie in [0, 1]", g, i);
+            if (!std::isfinite(o.err_q[i]) || !(o.err_q[i] > 0))
+                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: sigma must be finite and > 0", g, i);
+            here = true;
+        }
+        if (!here) continue;
+        lay.any = true;
+        lay.pol[g] = (long)stage.size();
+        lim_push_kinds(stage, kind, o.n);
+    }
+    return VAG_OK;
+}
+
+static int upload_lim_spec(vag_ctx* c, const std::vector<double>& stage, const LimLayout& lay) {
+    uint64_t h = 1469598103934665603ull;
+    h = fnv1a(h, &lay.point, sizeof lay.point);
+    if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
+    if (!lay.pol.empty()) h = fnv1a(h, lay.pol.data(), sizeof(long) * lay.pol.size());
+    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
+    if (c->limfit_hash_valid && c->limfit_hash == h && c->limfit_doubles == stage.size()) return VAG_OK;  // resident already
+    c->limfit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_limfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    if (c->d_limfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    std::memcpy(c->h_limfit.as<double>(), stage.data(), sizeof(double) * stage.size());
+    HIPCHK(hipMemcpyAsync(c->d_limfit.p, c->h_limfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
+    c->limfit_hash = h;
+    c->limfit_doubles = stage.size();
+    c->limfit_hash_valid = true;
+    return VAG_OK;
+}
+
 static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec,
                         const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
-                        const vag_pol_fit_spec* pol = nullptr) {
+                        const vag_pol_fit_spec* pol = nullptr, const LimLayout* lim = nullptr) {
     int rc = VAG_OK;
     const int n = spec->n_data;
     hipStream_t st = c->stream;
@@ -4178,13 +4419,23 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
     const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // the SSC tables of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
-    auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext) -> int {
+    // lim_off: where the pass's block of limit rows starts in d_limfit, or -1 (no limit row: the kernel as it was)
+    auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext,
+                    long lim_off) -> int {
         const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
-        hipLaunchKernelGGL(vag_fit_back_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av,
-                           c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
-                           (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
-                           pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order, c->d_cost_f.as<float>(), nb,
-                           next_order());
+        const double* lb = lim_off >= 0 ? c->d_limfit.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
+        const int* icst = (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr;
+        if (!lb)
+            hipLaunchKernelGGL(vag_fit_back_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av,
+                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(), icst, d_chi2,
+                               c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(),
+                               d_order, c->d_cost_f.as<float>(), nb, next_order());
+        else
+            hipLaunchKernelGGL(vag_fit_back_lim_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av,
+                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(), icst, d_chi2,
+                               c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(),
+                               d_order, c->d_cost_f.as<float>(), nb, next_order(), reinterpret_cast<const int*>(lb + 2 * (size_t)npts),
+                               lb, lb + npts);
         HIPCHK(hipGetLastError());
         ++pass;
         n_cap = std::max(n_cap, c->plan.n_models_capacity);
@@ -4202,7 +4453,7 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         if (rc == VAG_OK) rc = series_request(c, d_params, nb, n, c->d_series_flux.as<double>(), upload_series_bands(c, spec->nu, n));
         if (rc == VAG_OK)
             rc = back(c->d_series_flux.as<double>(), n, d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n,
-                      spec->ext_kernel ? d + 5 * (size_t)n : nullptr);
+                      spec->ext_kernel ? d + 5 * (size_t)n : nullptr, lim ? lim->point : -1);
         if (rc == VAG_OK) {
             rc = finish_speculation(c);  // before a band group's own grid pass reuses the plan buffers
             n_cap = std::max(n_cap, c->plan.n_models_capacity);
@@ -4223,7 +4474,9 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         c->order_next = d_order != nullptr;
         c->last_order = d_order;
         rc = band_request_dev(c, d_params, nb, db, bd.n, bd.nu_min, bd.nu_max, bd.num_points, c->d_series_flux.as<double>(), nullptr);
-        if (rc == VAG_OK) rc = back(c->d_series_flux.as<double>(), bd.n, db + bd.n, db + 2 * (size_t)bd.n, db + 3 * (size_t)bd.n, nullptr);
+        if (rc == VAG_OK)
+            rc = back(c->d_series_flux.as<double>(), bd.n, db + bd.n, db + 2 * (size_t)bd.n, db + 3 * (size_t)bd.n, nullptr,
+                      lim ? lim->band[g] : -1);
     }
     size_t soff = 0;
     for (int g = 0; g < n_groups && rc == VAG_OK; ++g) {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
@@ -4301,11 +4554,20 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
             rc = pol_stokes_request(c, d_params, nb, o.n, o.n_az > 0 ? o.n_az : 256, c->d_polspec.as<double>(), c->d_polstokes.as<double>());
         if (rc == VAG_OK) {
             const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
-            hipLaunchKernelGGL(vag_fit_pol_back_kernel, dim3(nb), dim3(64), 0, st, c->d_polstokes.as<double>(), o.n, o.kind, ds + 1,
-                               reinterpret_cast<const int*>(c->d_polspec.as<double>() + 4 * (size_t)nb), d_theta, ndim, d_prior,
-                               sky ? sky->pa_fixed : 0.0, c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
-                               (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
-                               pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order);
+            const int* lk = (lim && lim->pol[g] >= 0) ? reinterpret_cast<const int*>(c->d_limfit.as<double>() + lim->pol[g]) : nullptr;
+            const int* bad = reinterpret_cast<const int*>(c->d_polspec.as<double>() + 4 * (size_t)nb);
+            const int* icst = (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr;
+            const double pa_fixed = sky ? sky->pa_fixed : 0.0;
+            if (!lk)
+                hipLaunchKernelGGL(vag_fit_pol_back_kernel, dim3(nb), dim3(64), 0, st, c->d_polstokes.as<double>(), o.n, o.kind, ds + 1, bad,
+                                   d_theta, ndim, d_prior, pa_fixed, c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(),
+                                   c->d_row_off.as<int>(), icst, d_chi2, c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0,
+                                   pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order);
+            else
+                hipLaunchKernelGGL(vag_fit_pol_back_lim_kernel, dim3(nb), dim3(64), 0, st, c->d_polstokes.as<double>(), o.n, o.kind, ds + 1,
+                                   bad, d_theta, ndim, d_prior, pa_fixed, c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(),
+                                   c->d_row_off.as<int>(), icst, d_chi2, c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0,
+                                   pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order, lk);
             HIPCHK(hipGetLastError());
             ++pass;
             n_cap = std::max(n_cap, c->plan.n_models_capacity);
@@ -4406,6 +4668,47 @@ int vag_loglike_pol_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
     if (rc) return rc;
     rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol);
     if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol);
+    return rc;
+}
+
+int vag_loglike_lim_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                              const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const double* d_theta, int nb, int ndim,
+                              double* d_out) {
+    std::vector<double> stage;
+    LimLayout lay;
+    if (lim && spec) {
+        const int rc = lim_scan(spec, pol, lim, stage, lay);
+        if (rc) return rc;
+    }
+    if (!lay.any) return vag_loglike_pol_batch_dev(c, spec, sky, vis, pol, d_theta, nb, ndim, d_out);  // exactly that call
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    if (pol && pol->n_groups == 0) pol = nullptr;
+    if (vis && vis->n_groups == 0) vis = nullptr;
+    const bool placed = (sky && sky->n_groups > 0) || vis;
+    if (!pol && !placed) sky = nullptr;  // (as vag_loglike_sky_batch_dev: nothing reads the placement)
+    HIPCHK(hipSetDevice(c->device));
+    int rc = upload_fit_spec(c, spec, ndim, placed, pol != nullptr);
+    if (rc) return rc;
+    if (sky) {
+        rc = upload_sky_spec(c, sky);
+        if (rc) return rc;
+    }
+    if (vis) {
+        rc = upload_vis_spec(c, vis);
+        if (rc) return rc;
+    }
+    if (pol) {
+        rc = upload_pol_spec(c, pol);
+        if (rc) return rc;
+    }
+    rc = upload_lim_spec(c, stage, lay);
+    if (rc) return rc;
+    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, &lay);
+    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, &lay);
     return rc;
 }
 
@@ -4736,6 +5039,34 @@ int vag_loglike_pol_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fi
     double* d_out = d_theta + (size_t)nb * ndim;
     HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
     int rc = vag_loglike_pol_batch_dev(c, spec, sky, vis, pol, d_theta, nb, ndim, d_out);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)collect_times(c);
+    return VAG_OK;
+}
+
+int vag_loglike_lim_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                          const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const double* theta, int nb, int ndim, double* out) {
+    bool any = false;
+    if (lim && spec) {  // (checked again, and laid out, by the _dev form)
+        std::vector<double> stage;
+        LimLayout lay;
+        const int rc = lim_scan(spec, pol, lim, stage, lay);
+        if (rc) return rc;
+        any = lay.any;
+    }
+    if (!any) return vag_loglike_pol_batch(c, spec, sky, vis, pol, theta, nb, ndim, out);  // exactly that call
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
+    double* d_theta = c->d_theta_in.as<double>();
+    double* d_out = d_theta + (size_t)nb * ndim;
+    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
+    int rc = vag_loglike_lim_batch_dev(c, spec, sky, vis, pol, lim, d_theta, nb, ndim, d_out);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

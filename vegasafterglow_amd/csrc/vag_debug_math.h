@@ -3,6 +3,7 @@
 // inline.  Nothing here is on a product call path.  tests/test_device_math.py holds each routine to a high-precision reference.
 #pragma once
 #include "vag_ic_kernels.h"
+#include "vag_log_ndtr.h"
 #include "vag_rs.h"
 #include "vag_sky.h"
 
@@ -126,6 +127,7 @@ __global__ void __launch_bounds__(64) vag_math_probe_kernel(int fn, int n, const
         case VAG_MATH_SP_FAST: y = sp_fast(x, sp); break;
         case VAG_MATH_SP_FAST_GLOBAL: y = sp_fast(x, sp_table); break;
         case VAG_MATH_SP_FAST_SEL: y = sp_fast_sel(x, sp); break;
+        case VAG_MATH_LOG_NDTR: y = log_ndtr(x); break;
         default: return;
     }
     out[i] = y;

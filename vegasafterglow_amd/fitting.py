@@ -165,6 +165,7 @@ class Fitter:
         self.resolution, self.rtol, self.radiative_fireball = tuple(resolution), float(rtol), bool(radiative_fireball)
         self.device = device
         self._point_t, self._point_nu, self._point_flux, self._point_err, self._point_weights = [], [], [], [], []
+        self._point_lim = []  # per add_* call: the boolean mask of its upper-limit rows (upper_limit=...)
         self._band_obs = []
         self._centroid_obs = []  # VLBI centroid groups (add_centroid): one vag_centroid_obs each
         self._vis_obs = []  # VLBI visibility groups (add_visibilities): one vag_visibility_obs each
@@ -199,7 +200,26 @@ class Fitter:
                 raise ValueError(f"{who}: weights must be finite and >= 0 at every point")
         return t, f_nu, err, w
 
-    def _add_points(self, t, nu, f_nu, err, w):
+    @staticmethod
+    def _limit_mask(upper_limit, t, values, who):
+        """The boolean mask of the rows that are upper limits: ``upper_limit`` is None / a bool (no / every row) or a boolean
+        array of the shape of t.  On a flagged row the flux argument is the limit L >= 0 and the error argument the noise level
+        sigma: the row adds -2 w ln Phi((L - model) / sigma) to chi^2 ("a 3 sigma limit of X" is L = X, sigma = X / 3)."""
+        if upper_limit is None:
+            return np.zeros(t.shape, dtype=bool)
+        m = np.asarray(upper_limit)
+        if m.dtype != np.bool_:
+            raise ValueError(f"{who}: upper_limit must be a bool or a boolean mask, got dtype {m.dtype}")
+        if m.ndim == 0:
+            m = np.full(t.shape, bool(m))
+        elif m.shape != t.shape:
+            raise ValueError(f"{who}: an upper_limit mask must have the shape of t, got {m.shape} vs {t.shape}")
+        if (values[m] < 0).any():
+            raise ValueError(f"{who}: an upper limit must be >= 0")
+        return m.copy()
+
+    def _add_points(self, t, nu, f_nu, err, w, lim):
+        self._point_lim.append(lim)
         self._point_t.append(t)
         self._point_nu.append(nu)
         self._point_flux.append(f_nu)
@@ -208,19 +228,23 @@ class Fitter:
         self._all_t = None
 
     # fitter.py:256-282
-    def add_flux_density(self, nu, t, f_nu, err, weights=None, label=None):
-        """Light-curve data at one frequency nu [Hz] (`label` is accepted for API compatibility; it only names plot legends)."""
+    def add_flux_density(self, nu, t, f_nu, err, weights=None, label=None, upper_limit=None):
+        """Light-curve data at one frequency nu [Hz] (`label` is accepted for API compatibility; it only names plot legends).
+        upper_limit: None, a bool or a boolean mask of the shape of t; on a flagged row f_nu is the limit L and err the noise level
+        sigma (Fitter._limit_mask)."""
         nu_arr = np.asarray(nu, dtype=np.float64)
         if not np.isfinite(nu_arr).all() or (nu_arr <= 0).any():
             raise ValueError(f"add_flux_density: nu must be finite and > 0, got {nu}")
         t, f_nu, err, w = self._checked_observations(t, f_nu, err, weights, "add_flux_density")
         if nu_arr.ndim != 0 and nu_arr.shape != t.shape:  # extension: one frequency per point
             raise ValueError(f"add_flux_density: an array nu must have the shape of t, got {nu_arr.shape} vs {t.shape}")
-        self._add_points(t, np.full_like(t, float(nu_arr)) if nu_arr.ndim == 0 else nu_arr.copy(), f_nu, err, w)
+        lim = self._limit_mask(upper_limit, t, f_nu, "add_flux_density")
+        self._add_points(t, np.full_like(t, float(nu_arr)) if nu_arr.ndim == 0 else nu_arr.copy(), f_nu, err, w, lim)
 
     # fitter.py:284-314
-    def add_spectrum(self, t, nu, f_nu, err, weights=None):
-        """A broadband spectrum at one time t [s]: one point-data row per frequency."""
+    def add_spectrum(self, t, nu, f_nu, err, weights=None, upper_limit=None):
+        """A broadband spectrum at one time t [s]: one point-data row per frequency.  upper_limit: None, a bool or a boolean mask of
+        the shape of nu; on a flagged row f_nu is the limit L and err the noise level sigma (Fitter._limit_mask)."""
         if np.ndim(t) != 0 or not np.isfinite(t) or t <= 0:
             raise ValueError(f"add_spectrum: t must be finite and > 0, got {t}")
         nu = np.asarray(nu, dtype=np.float64)
@@ -228,11 +252,14 @@ class Fitter:
             raise ValueError(f"add_spectrum: nu must be finite and > 0 at every point (got min={float(nu.min())}, "
                              f"max={float(nu.max())})")
         nu, f_nu, err, w = self._checked_observations(nu, f_nu, err, weights, "add_spectrum")  # nu is the axis array here
-        self._add_points(np.full_like(nu, float(t)), nu, f_nu, err, w)
+        lim = self._limit_mask(upper_limit, nu, f_nu, "add_spectrum")
+        self._add_points(np.full_like(nu, float(t)), nu, f_nu, err, w, lim)
 
     # fitter.py:316-377
-    def add_flux(self, band, t, flux, err, num_points=5, weights=None):
-        """Band-integrated fluxes [erg/cm^2/s] over band = (nu_min, nu_max) [Hz]; each group is one Model.flux request."""
+    def add_flux(self, band, t, flux, err, num_points=5, weights=None, upper_limit=None):
+        """Band-integrated fluxes [erg/cm^2/s] over band = (nu_min, nu_max) [Hz]; each group is one Model.flux request.
+        upper_limit: None, a bool or a boolean mask of the shape of t; on a flagged row flux is the limit L >= 0 and err the noise
+        level sigma (Fitter._limit_mask); detections need strictly positive fluxes."""
         try:
             nu_min, nu_max = band
         except (TypeError, ValueError):
@@ -245,13 +272,21 @@ class Fitter:
         t, flux, err, w = self._checked_observations(t, flux, err, weights, "add_flux")
         if t.ndim != 1:
             raise ValueError("add_flux: t, flux and err must be 1-D arrays")
-        if np.any(flux <= 0):
+        lim = self._limit_mask(upper_limit, t, flux, "add_flux")
+        if np.any(flux[~lim] <= 0):
             raise ValueError("add_flux: the log-flux likelihood requires strictly positive fluxes")
         order = np.argsort(t)
-        self._band_obs.append(dict(nu_min=float(nu_min), nu_max=float(nu_max), num_points=int(num_points),
-                                   t=np.ascontiguousarray(t[order]), ln_flux=np.ascontiguousarray(np.log(flux[order])),
-                                   ln_err=np.ascontiguousarray(err[order] / flux[order]),
-                                   weights=np.ascontiguousarray(w[order])))
+        bd = dict(nu_min=float(nu_min), nu_max=float(nu_max), num_points=int(num_points),
+                  t=np.ascontiguousarray(t[order]), weights=np.ascontiguousarray(w[order]), lim=None)
+        if lim.any():  # limit rows: ln_flux / ln_err are not read there (0 and 1); L and sigma go into their own arrays
+            lim, flux, err = lim[order], flux[order], err[order]
+            safe = np.where(lim, 1.0, flux)
+            bd.update(ln_flux=np.ascontiguousarray(np.where(lim, 0.0, np.log(safe))),
+                      ln_err=np.ascontiguousarray(np.where(lim, 1.0, err / safe)), lim=np.ascontiguousarray(lim, dtype=np.int32),
+                      limit=np.ascontiguousarray(np.where(lim, flux, 0.0)), sigma=np.ascontiguousarray(np.where(lim, err, 1.0)))
+        else:
+            bd.update(ln_flux=np.ascontiguousarray(np.log(flux[order])), ln_err=np.ascontiguousarray(err[order] / flux[order]))
+        self._band_obs.append(bd)
 
     def add_centroid(self, nu, t, east, north, err_east, err_north, weights=None):
         """VLBI centroid positions at one frequency nu [Hz]: offsets east / north of a reference position and their errors [rad]
@@ -342,7 +377,7 @@ class Fitter:
     def has_visibilities(self):
         return bool(self._vis_obs)
 
-    def add_polarization(self, nu, t, q, u=None, err_q=None, err_u=None, weights=None, n_az=None, kind="qu"):
+    def add_polarization(self, nu, t, q, u=None, err_q=None, err_u=None, weights=None, n_az=None, kind="qu", upper_limit=None):
         """Linear polarization measurements at one frequency nu [Hz] at ascending times t [s].  kind="qu": q = Q/I and u = U/I on
         the sky (IAU, as SkyPolarization.q / .u) with errors err_q, err_u; the group is its own request: the model Stokes values
         are Model.sky_polarization(t, nu, b, pi_max, b_rvs, pi_max_rvs, pa, n_az) with the parameters "pol_b", "pol_pi_max",
@@ -350,7 +385,9 @@ class Fitter:
         pi_max from the walker's own p) and "pa" (shared with the centroid and visibility groups), and adds
         sum_i w_i [((q_i - Q/I) / err_q_i)^2 + ((u_i - U/I) / err_u_i)^2] to chi^2.  kind="degree": q holds the polarization degree
         and err_q its error (u, err_u are not used); the term is sum_i w_i ((q_i - hypot(Q, U)/I) / err_q_i)^2 and "pa" drops out.
-        n_az: azimuthal parts per circle of the model (default 256, Model.sky_polarization's own).  Weights are used as given."""
+        n_az: azimuthal parts per circle of the model (default 256, Model.sky_polarization's own).  Weights are used as given.
+        upper_limit (kind="degree" only): None, a bool or a boolean mask of the shape of t; on a flagged epoch q is the limit on the
+        degree ("Pi < 12 %": q = 0.12) and err_q its noise level, and the term is -2 w ln Phi((q - hypot(Q, U)/I) / err_q)."""
         who = "add_polarization"
         nu = float(np.asarray(nu, dtype=np.float64)) if np.ndim(nu) == 0 else None
         if nu is None or not np.isfinite(nu) or nu <= 0:
@@ -388,14 +425,23 @@ class Fitter:
             w = np.asarray(weights, dtype=np.float64)
             if w.shape != t.shape or not np.isfinite(w).all() or (w < 0).any():
                 raise ValueError(f"{who}: weights must have the shape of t and be finite and >= 0")
+        lim = self._limit_mask(upper_limit, t, arrs["q"], who)
+        if qu and lim.any():
+            raise ValueError(f"{who}: upper limits need kind='degree' (limits on q / u are not supported)")
         c = np.ascontiguousarray
         self._pol_obs.append(dict(nu=nu, t=c(t), q=c(arrs["q"]), err_q=c(arrs["err_q"]), u=c(arrs["u"]) if qu else None,
                                   err_u=c(arrs["err_u"]) if qu else None, weights=c(w), n_az=None if n_az is None else int(n_az),
-                                  kind=kind))
+                                  kind=kind, lim=c(lim, dtype=np.int32) if lim.any() else None))
 
     @property
     def has_polarization(self):
         return bool(self._pol_obs)
+
+    @property
+    def has_limits(self):
+        """Some row of the data is an upper limit (upper_limit=... of add_flux_density / add_spectrum / add_flux / add_polarization)."""
+        return (any(m.any() for m in self._point_lim) or any(bd["lim"] is not None for bd in self._band_obs)
+                or any(pd["lim"] is not None for pd in self._pol_obs))
 
     # fitter.py:407-451
     def _consolidate_data(self):
@@ -405,22 +451,43 @@ class Fitter:
             if not self._band_obs and not self._centroid_obs and not self._vis_obs and not self._pol_obs:
                 raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities or add_polarization first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
+            self._all_lim = None
             return
         t = np.concatenate(self._point_t)
         nu = np.concatenate(self._point_nu)
         f = np.concatenate(self._point_flux)
         e = np.concatenate(self._point_err)
         w = np.concatenate(self._point_weights)
+        lim = np.concatenate(self._point_lim)
         order = np.argsort(t)
         t, nu, f, e, w = t[order], nu[order], f[order], e[order], w[order].copy()
-        s = w.sum()
-        if s > 0:
-            w *= len(w) / s
-        if np.any(f <= 0) or np.any(e <= 0):
-            raise ValueError("the log-flux likelihood requires strictly positive fluxes and errors")
+        if lim.any():
+            # upper-limit rows: the weights of the DETECTIONS are normalised to sum to their count, as without the limit rows; a limit
+            # row keeps its weight as given.  ln_flux / ln_err are not read on a limit row (0 and 1).
+            lim = lim[order]
+            det = ~lim
+            wd = w[det]
+            s = wd.sum()
+            if s > 0:
+                wd *= len(wd) / s
+                w[det] = wd
+            if np.any(f[det] <= 0) or np.any(e <= 0):
+                raise ValueError("the log-flux likelihood requires strictly positive fluxes and errors")
+            safe = np.where(lim, 1.0, f)
+            self._all_log_flux = np.ascontiguousarray(np.where(lim, 0.0, np.log(safe)))
+            self._all_log_err = np.ascontiguousarray(np.where(lim, 1.0, e / safe))
+            self._all_lim = dict(kind=np.ascontiguousarray(lim, dtype=np.int32), limit=np.ascontiguousarray(np.where(lim, f, 0.0)),
+                                 sigma=np.ascontiguousarray(np.where(lim, e, 1.0)))
+        else:
+            s = w.sum()
+            if s > 0:
+                w *= len(w) / s
+            if np.any(f <= 0) or np.any(e <= 0):
+                raise ValueError("the log-flux likelihood requires strictly positive fluxes and errors")
+            self._all_log_flux = np.ascontiguousarray(np.log(f))
+            self._all_log_err = np.ascontiguousarray(e / f)
+            self._all_lim = None
         self._all_t, self._all_nu = np.ascontiguousarray(t), np.ascontiguousarray(nu)
-        self._all_log_flux = np.ascontiguousarray(np.log(f))
-        self._all_log_err = np.ascontiguousarray(e / f)
         self._all_weights = np.ascontiguousarray(w)
         if self.extinction is not None:  # fitter.py:439-449: rest-frame wavelengths, kernel = 0.4 ln10 k(lambda)
             self._ext_z = self.z
@@ -504,6 +571,7 @@ class Fitter:
         spec._sky = self._sky_spec(fixed) if self._centroid_obs or self._vis_obs or self._pol_obs else None
         spec._vis = self._vis_spec() if self._vis_obs else None
         spec._pol = self._pol_spec(fixed) if self._pol_obs else None
+        spec._lim = self._lim_spec() if self.has_limits else None
         if self.extinction is not None and any(pd.name == "z" for pd in free):
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
@@ -617,6 +685,36 @@ class Fitter:
                 raise ValueError(f"a fixed {name} must be finite and >= 0" + (" and <= 1" if name.startswith("pol_pi_max") else ""))
         pol._keep_alive = (groups, list(self._pol_obs))
         return pol
+
+    def _lim_spec(self):
+        """vag_limit_fit_spec of the upper-limit rows (parallel to the consolidated point rows, the band groups and the polarization
+        groups); it keeps the arrays it points at alive."""
+        ip = C.POINTER(C.c_int32)
+        lim = _lib.LimitFitSpec()
+        keep = []
+
+        def fill(rows, d):
+            rows.kind, rows.limit, rows.sigma = d["kind"].ctypes.data_as(ip), d["limit"].ctypes.data_as(_dp), d["sigma"].ctypes.data_as(_dp)
+            keep.append(d)
+        if self._all_lim is not None:
+            fill(lim.point, self._all_lim)
+        if any(bd["lim"] is not None for bd in self._band_obs):
+            bands = (_lib.LimitRows * len(self._band_obs))()
+            for g, bd in enumerate(self._band_obs):
+                if bd["lim"] is not None:
+                    fill(bands[g], dict(kind=bd["lim"], limit=bd["limit"], sigma=bd["sigma"]))
+            lim.n_bands, lim.bands = len(self._band_obs), bands
+            keep.append(bands)
+        if any(pd["lim"] is not None for pd in self._pol_obs):
+            kinds = (ip * len(self._pol_obs))()
+            for g, pd in enumerate(self._pol_obs):
+                if pd["lim"] is not None:
+                    kinds[g] = pd["lim"].ctypes.data_as(ip)
+                    keep.append(pd["lim"])
+            lim.n_pol_groups, lim.pol_kind = len(self._pol_obs), kinds
+            keep.append(kinds)
+        lim._keep_alive = keep
+        return lim
 
     def polarization(self, best_params, param_defs, resolution=None):
         """The model polarization at the epochs of every polarization group at a point of sampler space: a list of
@@ -784,7 +882,12 @@ class Fitter:
             costs = torch.empty((k,), dtype=torch.float64, device=dev) if want_costs else None
 
             def run():
-                if keep[0]._pol is not None:
+                ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+                if keep[0]._lim is not None:
+                    _lib.check(lib.vag_loglike_lim_batch_dev(
+                        h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), C.byref(keep[0]._lim),
+                        theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
+                elif keep[0]._pol is not None:
                     _lib.check(lib.vag_loglike_pol_batch_dev(
                         h, C.byref(keep[0]), C.byref(keep[0]._sky), C.byref(keep[0]._vis) if keep[0]._vis is not None else None,
                         C.byref(keep[0]._pol), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
@@ -804,6 +907,7 @@ class Fitter:
         eval_dev.has_centroids = spec._sky is not None and spec._sky.n_groups > 0
         eval_dev.has_visibilities = spec._vis is not None
         eval_dev.has_polarization = spec._pol is not None
+        eval_dev.has_limits = spec._lim is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -814,6 +918,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._lim is not None:
+                    from .dist import _NO_LIMITS
+                    raise NotImplementedError(_NO_LIMITS)
                 if keep[0]._pol is not None:
                     from .dist import _NO_POLARIZATION
                     raise NotImplementedError(_NO_POLARIZATION)
@@ -848,7 +955,12 @@ class Fitter:
         h, lock = get_context(self.device)
         plan = _lib.Plan()
         with lock:
-            if spec._pol is not None:
+            if spec._lim is not None:
+                ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+                _lib.check(_lib.load().vag_loglike_lim_batch(
+                    h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), C.byref(spec._lim),
+                    samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
+            elif spec._pol is not None:
                 _lib.check(_lib.load().vag_loglike_pol_batch(
                     h, C.byref(spec), C.byref(spec._sky), C.byref(spec._vis) if spec._vis is not None else None, C.byref(spec._pol),
                     samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
