@@ -383,6 +383,11 @@ int vag_flux_density_batch_dev(vag_ctx* ctx, const vag_model_params* d_params, i
 #define VAG_P_POL_B_RVS 1006
 #define VAG_P_POL_PI_MAX_RVS 1007
 
+/* Nor are these: the fractional systematic s_g of noise group g of vag_loglike_noise_batch, g = 0 .. VAG_NOISE_MAX_GROUPS - 1.
+ * Only that entry point accepts VAG_P_NOISE_SYS0 + g, and only when its vag_noise_fit_spec has group g (g < n_groups). */
+#define VAG_P_NOISE_SYS0 1008
+#define VAG_NOISE_MAX_GROUPS 8
+
 /* One group of VLBI centroid positions at one frequency (added after VAG_ABI_VERSION 13, detect by symbol).  The model centroid
  * (Xbar, Ybar) of vag_sky_centroid_batch(t, nu) is placed on the sky as
  *   east = east0 + Xbar sin PA + Ybar cos PA,   north = north0 + Xbar cos PA - Ybar sin PA
@@ -612,6 +617,41 @@ int vag_loglike_lim_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_
 int vag_loglike_lim_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                               const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const double* d_theta, int nb, int ndim,
                               double* d_out);
+
+/* Systematic and calibration errors per data set (added after VAG_ABI_VERSION 13, detect by symbol).  Each detection row -- a point
+ * row or a row of a band group -- belongs to a noise group g in 0 .. n_groups - 1 (n_groups <= VAG_NOISE_MAX_GROUPS) or to none (-1).
+ * A group has a fractional systematic s_g >= 0 (a free parameter with the slot VAG_P_NOISE_SYS0 + g, else sys_fixed[g]) and a
+ * calibration fraction c_g >= 0 (calib[g], fixed per fit).  With f_i the model flux after the extinction factor,
+ * r_i = ln F_obs,i - ln max(f_i, 1e-300), sigma_i the row's ln_err and w_i its weight, the grouped detection rows of group g add
+ *   v_i = sigma_i^2 + s_g^2,  p_i = w_i / v_i,
+ *   A = sum p_i r_i^2,  B = sum p_i r_i,  P = sum p_i,  N = sum w_i log1p(s_g^2 / sigma_i^2),
+ *   chi^2_g = A - c_g^2 B^2 / (1 + c_g^2 P) + N + log1p(c_g^2 P)
+ * to the walker's chi^2 in place of sum w_i (r_i / sigma_i)^2.  With all weights 1 this is r^T C^-1 r + ln det C - ln det diag(sigma^2)
+ * for C = diag(sigma^2 + s^2) + c^2 1 1^T: the Gaussian in ln F with a common scale factor of prior width c marginalised, normalised
+ * so that s = c = 0 is the fixed-error term.  Ungrouped rows keep that term; a row that vag_limit_fit_spec flags as an upper limit
+ * keeps its limit term whatever its group id and does not enter A, B, P, N.  s_g may span the point rows and any number of band
+ * groups (its sums are separable); a group with c_g > 0 must lie in one pass: point rows only, or exactly one band group. */
+typedef struct vag_noise_fit_spec {
+    int32_t n_groups;                /* 0 .. VAG_NOISE_MAX_GROUPS */
+    int32_t n_bands;                 /* spec->n_bands */
+    const int32_t* point_group;      /* [spec->n_data] group id or -1; NULL: no point row is grouped */
+    const int32_t* band_group;       /* [n_bands] the group id of every row of band group b, or -1 */
+    double sys_fixed[VAG_NOISE_MAX_GROUPS]; /* s_g of a group without a free parameter (0 when not given) */
+    double calib[VAG_NOISE_MAX_GROUPS];     /* c_g */
+} vag_noise_fit_spec;
+
+/* vag_loglike_lim_batch(_dev) with noise groups.  With noise NULL or no grouped row it is exactly that call (lim may be NULL as
+ * there); a pass without grouped rows launches what it launches there.  Validity, the evaluation order and the rejection counts are
+ * unchanged.  Refused with VAG_E_INVALID: n_groups outside 0 .. VAG_NOISE_MAX_GROUPS, a group id outside [-1, n_groups), a sys_fixed
+ * or calib that is negative or not finite, n_bands other than the fit spec's, a group with calib > 0 in more than one pass, and a
+ * parameter slot VAG_P_NOISE_SYS0 + g without group g ("bad parameter slot").  Results are bitwise reproducible and a walker's value
+ * does not depend on the rest of the batch.  The group ids stay resident on the device by content hash. */
+int vag_loglike_noise_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                            const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                            const double* theta, int nb, int ndim, double* out);
+int vag_loglike_noise_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                                const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                                const double* d_theta, int nb, int ndim, double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

@@ -61,6 +61,9 @@ P_A_V = 1000  # VAG_P_A_V
 SKY_SLOTS = {"pa": 1001, "east0": 1002, "north0": 1003}
 # VAG_P_POL_*: the field behind the shocks as the polarization groups see it (vag_loglike_pol_batch), not Model fields either
 POL_SLOTS = {"pol_b": 1004, "pol_pi_max": 1005, "pol_b_rvs": 1006, "pol_pi_max_rvs": 1007}
+# VAG_P_NOISE_SYS0 + g: the fractional systematic of noise group g (vag_loglike_noise_batch), the parameter "sys_<label>" of a Fitter
+P_NOISE_SYS0, NOISE_MAX_GROUPS = 1008, 8
+NOISE_PREFIX = "sys_"
 
 
 class CentroidObs(C.Structure):  # vag_centroid_obs
@@ -115,6 +118,11 @@ class LimitRows(C.Structure):  # vag_limit_rows
 class LimitFitSpec(C.Structure):  # vag_limit_fit_spec
     _fields_ = [("point", LimitRows), ("n_bands", C.c_int32), ("pad", C.c_int32), ("bands", C.POINTER(LimitRows)),
                 ("n_pol_groups", C.c_int32), ("pad2", C.c_int32), ("pol_kind", C.POINTER(C.POINTER(C.c_int32)))]
+
+
+class NoiseFitSpec(C.Structure):  # vag_noise_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("n_bands", C.c_int32), ("point_group", C.POINTER(C.c_int32)),
+                ("band_group", C.POINTER(C.c_int32)), ("sys_fixed", C.c_double * 8), ("calib", C.c_double * 8)]
 
 
 class FitSpec(C.Structure):
@@ -180,7 +188,7 @@ EXPORTS = [
     "vag_sky_image_batch", "vag_sky_moments_batch", "vag_sky_centroid_batch", "vag_loglike_sky_batch", "vag_loglike_sky_batch_dev",
     "vag_sky_visibility_batch", "vag_debug_device_math", "vag_loglike_vis_batch", "vag_loglike_vis_batch_dev",
     "vag_sky_polarization_batch", "vag_sky_stokes_image_batch", "vag_loglike_pol_batch", "vag_loglike_pol_batch_dev",
-    "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev",
+    "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev", "vag_loglike_noise_batch", "vag_loglike_noise_batch_dev",
 ]
 
 _lib = None
@@ -244,6 +252,10 @@ def load():
                                           C.POINTER(LimitFitSpec), _dp, C.c_int, C.c_int, _dp]
     lib.vag_loglike_lim_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
                                               C.POINTER(LimitFitSpec), v, C.c_int, C.c_int, v]
+    lib.vag_loglike_noise_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
+                                            C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec), _dp, C.c_int, C.c_int, _dp]
+    lib.vag_loglike_noise_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
+                                                C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -410,6 +410,7 @@ struct vag_ctx {
     DevBuf d_skycen, d_skycmom, d_skyfit;  // exact centroids (vag_sky.h): row-block partials, moments, centroid-fit pass data
     DevBuf d_visfit, d_visblk, d_vispart;  // visibility groups of the likelihood: their data, their 64-visibility blocks, chi^2 partials
     DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
+    DevBuf d_noisefit;  // noise groups of the likelihood (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
     DevBuf d_limfit;  // upper-limit rows of the likelihood (vag_loglike_lim_batch): per block [limit | sigma | kind], see LimLayout
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -464,7 +465,7 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit;
+    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
@@ -483,6 +484,9 @@ struct vag_ctx {
     uint64_t limfit_hash = 0;  // (d_limfit: the limit rows of vag_loglike_lim_batch, upload_lim_spec)
     size_t limfit_doubles = 0;
     bool limfit_hash_valid = false;
+    uint64_t noisefit_hash = 0;  // (d_noisefit: the noise groups of vag_loglike_noise_batch, upload_noise_spec)
+    size_t noisefit_doubles = 0;
+    bool noisefit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -719,8 +723,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_visfit.release();
     c->h_polfit.release();
     c->h_limfit.release();
+    c->h_noisefit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3535,7 +3540,7 @@ static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
     return h;
 }
 
-static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false) {
+static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false, int noise_groups = 0) {
     if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
     const int n = spec->n_data;
     if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky && !pol)) return set_err(VAG_E_INVALID, "fit spec has no data");
@@ -3544,6 +3549,7 @@ static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool 
         if (s == VAG_P_A_V) continue;
         if (sky && s >= VAG_P_SKY_PA && s <= VAG_P_SKY_NORTH0) continue;
         if (pol && (s == VAG_P_SKY_PA || (s >= VAG_P_POL_B && s <= VAG_P_POL_PI_MAX_RVS))) continue;
+        if (s >= VAG_P_NOISE_SYS0 && s < VAG_P_NOISE_SYS0 + noise_groups) continue;  // (the systematic of a group the noise spec has)
         if (s < 0 || (s >= VAG_P_COUNT && (s < VAG_P_RVS_EPS_E || s > VAG_P_MAG_Q))) return set_err(VAG_E_INVALID, "bad parameter slot");
     }
     if (spec->use_priors)
@@ -3813,6 +3819,119 @@ vag_fit_back_lim_kernel(const double* __restrict__ flux /* [nb][n] */, int n, co
             const double lp = ln_prior[m];
             const bool fin = ok && isfinite(acc) && lp > -INFINITY;
             out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
+            if (!fin) atomicAdd(fitstat, 1);
+        }
+    }
+}
+
+// vag_fit_back_lim_kernel for a pass with rows in noise groups (vag_loglike_noise_batch).  Rows without a group (grp[i] < 0) and
+// upper-limit rows (whatever their group) add the terms of that kernel, statement for statement.  The detection rows of every group g
+// the pass holds (bit g of `present`) add, with s_g the walker's systematic -- the free parameter with the slot VAG_P_NOISE_SYS0 + g
+// (found as vag::sky_placement finds pa), else noise[g] -- and c_g = noise[8 + g]:
+//   v_i = sigma_i^2 + s_g^2, p_i = w_i / v_i, A = sum p_i r_i^2, B = sum p_i r_i, P = sum p_i, N = sum w_i log1p(s_g^2 / sigma_i^2),
+//   c_g == 0: A + N  (separable: the group may span passes);  c_g > 0: A - c_g^2 B^2 / (1 + c_g^2 P) + N + log1p(c_g^2 P)  (the pass
+//   holds all of the group: noise_scan refuses anything else).
+// Every sum is a fixed lane-strided sum followed by vag::wave_sum, group after group in ascending g: the value depends on the walker's
+// row alone, not on its evaluation slot.  The groups are walked one at a time (a wave-uniform loop over the set bits), so the four
+// accumulators are scalars in registers; a row's log is taken once, in the turn of its own group.  A kernel of its own so that a pass
+// without grouped rows runs the instructions it always ran.
+__global__ void __launch_bounds__(64)
+vag_fit_back_noise_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const double* __restrict__ ln_flux,
+                    const double* __restrict__ ln_err, const double* __restrict__ weight, const double* __restrict__ ext /* or null */,
+                    const double* __restrict__ a_v, const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status,
+                    const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */, double* __restrict__ chi2,
+                    int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out,
+                    int* __restrict__ fitstat /* [0] walkers scored -inf, [1] of those: SSC table failures */,
+                    const int* __restrict__ order /* evaluation slot -> walker, or null */,
+                    const float* __restrict__ cost /* with next_order: the slots' costs of THIS call (the grid kernel's plan scan leaves them) */,
+                    int nb, int* __restrict__ next_order /* or null: [rank] = walker, descending cost */,
+                    const int* __restrict__ lim_kind /* [n] VAG_OBS_*, or null: no limit row in this pass */,
+                    const double* __restrict__ lim_L /* [n] */, const double* __restrict__ lim_sigma /* [n] */,
+                    const double* __restrict__ theta /* [nb][ndim] */, int ndim, const double* __restrict__ prior,
+                    const double* __restrict__ noise /* [sys_fixed 8 | calib 8] */, const int* __restrict__ grp /* [n] group id or -1 */,
+                    unsigned present /* bit g: some row of the pass is in group g */) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    if (next_order) {  // (as vag_fit_back_kernel)
+        const float mine = cost[m];
+        int rank = 0;
+        for (int i0 = 0; i0 < nb; i0 += 64) {
+            const int i = i0 + lane;
+            const float c = i < nb ? cost[i] : -1.0f;
+            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
+        }
+        if (lane == 0) next_order[rank] = order ? order[m] : m;
+    }
+    const int walker = order ? order[m] : m;
+    const double av = (ext != nullptr) ? a_v[m] : 0.0;
+    const bool grid_ok = meta[m].status == 0;
+    double s = 0;
+    if (grid_ok)
+        for (int i = lane; i < n; i += 64) {
+            const bool is_lim = lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT;
+            if (grp[i] >= 0 && !is_lim) continue;  // a grouped detection: in the turn of its group below
+            double f = flux[(size_t)m * n + i];
+            if (av != 0.0) f = f * exp(-av * ext[i]);
+            if (is_lim) {
+                s += weight[i] * (-2.0 * vag::log_ndtr((lim_L[i] - f) / lim_sigma[i]));
+                continue;
+            }
+            const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+            const double q = (ln_flux[i] - log(fm)) / ln_err[i];
+            s += weight[i] * (q * q);
+        }
+    s = vag::wave_sum(s);
+    if (grid_ok) {
+        const int* slot = reinterpret_cast<const int*>(prior + 64);
+        const int* is_log = slot + 16;
+        for (int g = 0; g < VAG_NOISE_MAX_GROUPS; ++g) {
+            if (!((present >> g) & 1u)) continue;
+            double sg = noise[g];
+            for (int d = 0; d < ndim; ++d) {
+                if (slot[d] != VAG_P_NOISE_SYS0 + g) continue;
+                const double v = theta[(size_t)walker * ndim + d];
+                sg = is_log[d] ? pow(10.0, v) : v;
+            }
+            const double s2 = sg * sg, cg = noise[VAG_NOISE_MAX_GROUPS + g];
+            double A = 0, B = 0, P = 0, N = 0;
+            for (int i = lane; i < n; i += 64) {
+                if (grp[i] != g || (lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT)) continue;
+                double f = flux[(size_t)m * n + i];
+                if (av != 0.0) f = f * exp(-av * ext[i]);
+                const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+                const double r = ln_flux[i] - log(fm), sig2 = ln_err[i] * ln_err[i];
+                const double p = weight[i] / (sig2 + s2);
+                A += p * (r * r);
+                B += p * r;
+                P += p;
+                N += weight[i] * log1p(s2 / sig2);
+            }
+            A = vag::wave_sum(A);
+            N = vag::wave_sum(N);
+            double term = A + N;
+            if (cg > 0) {  // (wave-uniform) the calibration scale marginalised: a rank-one update of the diagonal covariance
+                B = vag::wave_sum(B);
+                P = vag::wave_sum(P);
+                const double c2 = cg * cg;
+                term = A - c2 * (B * B) / (1.0 + c2 * P) + N + log1p(c2 * P);
+            }
+            s += term;  // (every lane holds the same sums; lane 0 stores)
+        }
+    }
+    bool bad_row = false;
+    if (grid_ok)
+        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
+    const bool any_bad = __any(bad_row);
+    if (lane == 0) {
+        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
+        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
+        const double acc = first ? s : chi2[m] + s;
+        valid[m] = ok;
+        chi2[m] = acc;
+        if (ic_bad) atomicAdd(fitstat + 1, 1);
+        if (last) {
+            const double lp = ln_prior[m];
+            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
+            out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
             if (!fin) atomicAdd(fitstat, 1);
         }
     }
@@ -4379,9 +4498,101 @@ static int upload_lim_spec(vag_ctx* c, const std::vector<double>& stage, const L
     return VAG_OK;
 }
 
+// ---- noise groups (vag_loglike_noise_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
+//      in doubles: [sys_fixed 8 | calib 8], then for every pass that holds a grouped row -- the point rows, a band group -- the rows'
+//      group ids (int32 [n] in (n + 1) / 2 doubles).  A pass without a grouped row is not stored (offset -1): it is the pass without
+//      noise groups. ----
+struct NoiseLayout {
+    long point = -1;                    // offset of the point rows' ids in d_noisefit, or -1
+    std::vector<long> band;             // the same per band group
+    unsigned point_present = 0;         // bit g: some point row is in group g
+    std::vector<unsigned> band_present; // the same per band group
+    int n_groups = 0;
+    bool any = false;                   // some row is grouped
+};
+
+// Validates noise against the fit spec and lays its blocks out in stage (host work only: no context is touched).
+static int noise_scan(const vag_fit_spec* spec, const vag_noise_fit_spec* nz, std::vector<double>& stage, NoiseLayout& lay) {
+    if (nz->n_groups < 0 || nz->n_groups > VAG_NOISE_MAX_GROUPS)
+        return set_err(VAG_E_INVALID, "noise groups: n_groups must be in 0..%d, got %d", VAG_NOISE_MAX_GROUPS, nz->n_groups);
+    if (nz->n_bands != spec->n_bands)
+        return set_err(VAG_E_INVALID, "noise groups: n_bands must be the fit spec's %d, got %d", spec->n_bands, nz->n_bands);
+    if (nz->n_bands > 0 && (!nz->band_group || !spec->bands)) return set_err(VAG_E_INVALID, "noise groups: null band list");
+    for (int g = 0; g < nz->n_groups; ++g) {
+        if (!std::isfinite(nz->sys_fixed[g]) || nz->sys_fixed[g] < 0)
+            return set_err(VAG_E_INVALID, "noise group %d: the systematic must be finite and >= 0", g);
+        if (!std::isfinite(nz->calib[g]) || nz->calib[g] < 0)
+            return set_err(VAG_E_INVALID, "noise group %d: the calibration fraction must be finite and >= 0", g);
+    }
+    lay.n_groups = nz->n_groups;
+    stage.assign(2 * VAG_NOISE_MAX_GROUPS, 0.0);
+    for (int g = 0; g < nz->n_groups; ++g) {
+        stage[g] = nz->sys_fixed[g];
+        stage[VAG_NOISE_MAX_GROUPS + g] = nz->calib[g];
+    }
+    int passes[VAG_NOISE_MAX_GROUPS] = {0};  // in how many passes a group has rows
+    auto push_ids = [&](const int32_t* ids, int32_t same, int n) -> long {
+        const long at = (long)stage.size();
+        stage.resize(at + ((size_t)n + 1) / 2, 0.0);
+        int32_t* dst = reinterpret_cast<int32_t*>(stage.data() + at);
+        for (int i = 0; i < n; ++i) dst[i] = ids ? ids[i] : same;
+        return at;
+    };
+    const int n = spec->n_data;
+    if (nz->point_group && n > 0) {
+        for (int i = 0; i < n; ++i) {
+            const int id = nz->point_group[i];
+            if (id < -1 || id >= nz->n_groups)
+                return set_err(VAG_E_INVALID, "noise groups, point row %d: group %d is outside [-1, %d)", i, id, nz->n_groups);
+            if (id >= 0) lay.point_present |= 1u << id;
+        }
+        if (lay.point_present) {
+            lay.any = true;
+            lay.point = push_ids(nz->point_group, 0, n);
+            for (int g = 0; g < nz->n_groups; ++g) passes[g] += (lay.point_present >> g) & 1u;
+        }
+    }
+    lay.band.assign(std::max(spec->n_bands, 0), -1);
+    lay.band_present.assign(std::max(spec->n_bands, 0), 0u);
+    for (int b = 0; b < nz->n_bands; ++b) {
+        const int id = nz->band_group[b];
+        if (id < -1 || id >= nz->n_groups)
+            return set_err(VAG_E_INVALID, "noise groups, band group %d: group %d is outside [-1, %d)", b, id, nz->n_groups);
+        if (id < 0 || spec->bands[b].n <= 0) continue;
+        lay.any = true;
+        lay.band_present[b] = 1u << id;
+        lay.band[b] = push_ids(nullptr, id, spec->bands[b].n);
+        ++passes[id];
+    }
+    for (int g = 0; g < nz->n_groups; ++g)
+        if (nz->calib[g] > 0 && passes[g] > 1)
+            return set_err(VAG_E_INVALID,
+                           "noise group %d has a calibration fraction and rows in %d passes: such a group must hold point rows only or "
+                           "exactly one band group", g, passes[g]);
+    return VAG_OK;
+}
+
+static int upload_noise_spec(vag_ctx* c, const std::vector<double>& stage, const NoiseLayout& lay) {
+    uint64_t h = 1469598103934665603ull;
+    h = fnv1a(h, &lay.point, sizeof lay.point);
+    if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
+    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
+    if (c->noisefit_hash_valid && c->noisefit_hash == h && c->noisefit_doubles == stage.size()) return VAG_OK;  // resident already
+    c->noisefit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_noisefit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    if (c->d_noisefit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    std::memcpy(c->h_noisefit.as<double>(), stage.data(), sizeof(double) * stage.size());
+    HIPCHK(hipMemcpyAsync(c->d_noisefit.p, c->h_noisefit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
+    c->noisefit_hash = h;
+    c->noisefit_doubles = stage.size();
+    c->noisefit_hash_valid = true;
+    return VAG_OK;
+}
+
 static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec,
                         const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
-                        const vag_pol_fit_spec* pol = nullptr, const LimLayout* lim = nullptr) {
+                        const vag_pol_fit_spec* pol = nullptr, const LimLayout* lim = nullptr, const NoiseLayout* noise = nullptr) {
     int rc = VAG_OK;
     const int n = spec->n_data;
     hipStream_t st = c->stream;
@@ -4420,12 +4631,21 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // the SSC tables of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
     // lim_off: where the pass's block of limit rows starts in d_limfit, or -1 (no limit row: the kernel as it was)
+    // noise_off, present: where the pass's group ids start in d_noisefit, or -1 (no grouped row: the kernels as they were), and its groups
     auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext,
-                    long lim_off) -> int {
+                    long lim_off, long noise_off = -1, unsigned present = 0) -> int {
         const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
         const double* lb = lim_off >= 0 ? c->d_limfit.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
         const int* icst = (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr;
-        if (!lb)
+        if (noise_off >= 0) {
+            const double* nz = c->d_noisefit.as<double>();
+            hipLaunchKernelGGL(vag_fit_back_noise_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av,
+                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(), icst, d_chi2,
+                               c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(),
+                               d_order, c->d_cost_f.as<float>(), nb, next_order(),
+                               lb ? reinterpret_cast<const int*>(lb + 2 * (size_t)npts) : nullptr, lb, lb ? lb + npts : nullptr, d_theta,
+                               ndim, d_prior, nz, reinterpret_cast<const int*>(nz + noise_off), present);
+        } else if (!lb)
             hipLaunchKernelGGL(vag_fit_back_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av,
                                c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(), icst, d_chi2,
                                c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(),
@@ -4453,7 +4673,8 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         if (rc == VAG_OK) rc = series_request(c, d_params, nb, n, c->d_series_flux.as<double>(), upload_series_bands(c, spec->nu, n));
         if (rc == VAG_OK)
             rc = back(c->d_series_flux.as<double>(), n, d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n,
-                      spec->ext_kernel ? d + 5 * (size_t)n : nullptr, lim ? lim->point : -1);
+                      spec->ext_kernel ? d + 5 * (size_t)n : nullptr, lim ? lim->point : -1, noise ? noise->point : -1,
+                      noise ? noise->point_present : 0u);
         if (rc == VAG_OK) {
             rc = finish_speculation(c);  // before a band group's own grid pass reuses the plan buffers
             n_cap = std::max(n_cap, c->plan.n_models_capacity);
@@ -4476,7 +4697,7 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         rc = band_request_dev(c, d_params, nb, db, bd.n, bd.nu_min, bd.nu_max, bd.num_points, c->d_series_flux.as<double>(), nullptr);
         if (rc == VAG_OK)
             rc = back(c->d_series_flux.as<double>(), bd.n, db + bd.n, db + 2 * (size_t)bd.n, db + 3 * (size_t)bd.n, nullptr,
-                      lim ? lim->band[g] : -1);
+                      lim ? lim->band[g] : -1, noise ? noise->band[g] : -1, noise ? noise->band_present[g] : 0u);
     }
     size_t soff = 0;
     for (int g = 0; g < n_groups && rc == VAG_OK; ++g) {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
@@ -4709,6 +4930,57 @@ int vag_loglike_lim_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
     if (rc) return rc;
     rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, &lay);
     if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, &lay);
+    return rc;
+}
+
+int vag_loglike_noise_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                                const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                                const double* d_theta, int nb, int ndim, double* d_out) {
+    std::vector<double> nstage, lstage;
+    NoiseLayout nlay;
+    LimLayout llay;
+    if (noise && spec) {
+        const int rc = noise_scan(spec, noise, nstage, nlay);
+        if (rc) return rc;
+    }
+    if (!nlay.any) return vag_loglike_lim_batch_dev(c, spec, sky, vis, pol, lim, d_theta, nb, ndim, d_out);  // exactly that call
+    if (lim) {
+        const int rc = lim_scan(spec, pol, lim, lstage, llay);
+        if (rc) return rc;
+    }
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    if (pol && pol->n_groups == 0) pol = nullptr;
+    if (vis && vis->n_groups == 0) vis = nullptr;
+    const bool placed = (sky && sky->n_groups > 0) || vis;
+    if (!pol && !placed) sky = nullptr;  // (as vag_loglike_sky_batch_dev: nothing reads the placement)
+    HIPCHK(hipSetDevice(c->device));
+    int rc = upload_fit_spec(c, spec, ndim, placed, pol != nullptr, nlay.n_groups);
+    if (rc) return rc;
+    if (sky) {
+        rc = upload_sky_spec(c, sky);
+        if (rc) return rc;
+    }
+    if (vis) {
+        rc = upload_vis_spec(c, vis);
+        if (rc) return rc;
+    }
+    if (pol) {
+        rc = upload_pol_spec(c, pol);
+        if (rc) return rc;
+    }
+    if (llay.any) {
+        rc = upload_lim_spec(c, lstage, llay);
+        if (rc) return rc;
+    }
+    rc = upload_noise_spec(c, nstage, nlay);
+    if (rc) return rc;
+    const LimLayout* lp = llay.any ? &llay : nullptr;
+    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, lp, &nlay);
+    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, lp, &nlay);
     return rc;
 }
 
@@ -5067,6 +5339,41 @@ int vag_loglike_lim_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fi
     double* d_out = d_theta + (size_t)nb * ndim;
     HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
     int rc = vag_loglike_lim_batch_dev(c, spec, sky, vis, pol, lim, d_theta, nb, ndim, d_out);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)collect_times(c);
+    return VAG_OK;
+}
+
+int vag_loglike_noise_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                            const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                            const double* theta, int nb, int ndim, double* out) {
+    bool any = false;
+    if (noise && spec) {  // (checked again, and laid out, by the _dev form)
+        std::vector<double> stage;
+        NoiseLayout lay;
+        const int rc = noise_scan(spec, noise, stage, lay);
+        if (rc) return rc;
+        any = lay.any;
+    }
+    if (!any) return vag_loglike_lim_batch(c, spec, sky, vis, pol, lim, theta, nb, ndim, out);  // exactly that call
+    if (lim) {
+        std::vector<double> stage;
+        LimLayout lay;
+        const int rc = lim_scan(spec, pol, lim, stage, lay);
+        if (rc) return rc;
+    }
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
+    double* d_theta = c->d_theta_in.as<double>();
+    double* d_out = d_theta + (size_t)nb * ndim;
+    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
+    int rc = vag_loglike_noise_batch_dev(c, spec, sky, vis, pol, lim, noise, d_theta, nb, ndim, d_out);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

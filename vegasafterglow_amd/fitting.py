@@ -9,6 +9,7 @@ third-party: hand ``Fitter.log_prob_batch`` to ``emcee.EnsembleSampler(..., vect
 import ctypes as C
 import logging
 import math
+import re
 from dataclasses import dataclass
 from enum import Enum
 from typing import Optional, Sequence
@@ -166,6 +167,9 @@ class Fitter:
         self.device = device
         self._point_t, self._point_nu, self._point_flux, self._point_err, self._point_weights = [], [], [], [], []
         self._point_lim = []  # per add_* call: the boolean mask of its upper-limit rows (upper_limit=...)
+        self._point_grp = []  # per add_* call: the noise group id of its rows (noise=...), -1 = none
+        self._noise_labels = []  # the noise groups in order of first mention: group g is self._noise_labels[g]
+        self._noise_calib = {}  # label -> its calibration fraction, once a call has stated one
         self._band_obs = []
         self._centroid_obs = []  # VLBI centroid groups (add_centroid): one vag_centroid_obs each
         self._vis_obs = []  # VLBI visibility groups (add_visibilities): one vag_visibility_obs each
@@ -218,8 +222,39 @@ class Fitter:
             raise ValueError(f"{who}: an upper limit must be >= 0")
         return m.copy()
 
-    def _add_points(self, t, nu, f_nu, err, w, lim):
+    def _noise_group(self, noise, calibration, who):
+        """The id of the noise group ``noise`` names (-1 for None), declared at its first mention.  noise: a label matching
+        [A-Za-z0-9_]+; the rows join the group whose fractional systematic is the parameter ``sys_<label>`` (free or fixed; 0 when
+        not given), added in quadrature to each row's relative error with the Gaussian normalisation.  calibration: the fraction
+        c >= 0 by which the group's common flux scale is uncertain (a Gaussian prior on ln scale, marginalised); every call that
+        states it for a label must state the same value.  At most 8 groups.  Nothing is recorded when the call raises."""
+        if noise is None:
+            if calibration is not None:
+                raise ValueError(f"{who}: calibration needs noise=<label> (it is the calibration of a noise group)")
+            return -1
+        if not isinstance(noise, str) or not re.fullmatch(r"[A-Za-z0-9_]+", noise):
+            raise ValueError(f"{who}: noise must be a label matching [A-Za-z0-9_]+, got {noise!r}")
+        if calibration is not None:
+            try:
+                calibration = float(calibration)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: calibration must be a number >= 0, got {calibration!r}") from None
+            if not np.isfinite(calibration) or calibration < 0:
+                raise ValueError(f"{who}: calibration must be finite and >= 0, got {calibration!r}")
+            if self._noise_calib.get(noise, calibration) != calibration:
+                raise ValueError(f"{who}: noise group {noise!r} has calibration={self._noise_calib[noise]!r} from an earlier call, "
+                                 f"got {calibration!r}")
+        if noise not in self._noise_labels and len(self._noise_labels) >= _lib.NOISE_MAX_GROUPS:
+            raise ValueError(f"{who}: at most {_lib.NOISE_MAX_GROUPS} noise groups, {noise!r} would be one more")
+        if noise not in self._noise_labels:
+            self._noise_labels.append(noise)
+        if calibration is not None:
+            self._noise_calib[noise] = calibration
+        return self._noise_labels.index(noise)
+
+    def _add_points(self, t, nu, f_nu, err, w, lim, grp=-1):
         self._point_lim.append(lim)
+        self._point_grp.append(np.full(t.shape, grp, dtype=np.int32))
         self._point_t.append(t)
         self._point_nu.append(nu)
         self._point_flux.append(f_nu)
@@ -228,10 +263,11 @@ class Fitter:
         self._all_t = None
 
     # fitter.py:256-282
-    def add_flux_density(self, nu, t, f_nu, err, weights=None, label=None, upper_limit=None):
+    def add_flux_density(self, nu, t, f_nu, err, weights=None, label=None, upper_limit=None, noise=None, calibration=None):
         """Light-curve data at one frequency nu [Hz] (`label` is accepted for API compatibility; it only names plot legends).
         upper_limit: None, a bool or a boolean mask of the shape of t; on a flagged row f_nu is the limit L and err the noise level
-        sigma (Fitter._limit_mask)."""
+        sigma (Fitter._limit_mask).  noise, calibration: the noise group of the rows and its calibration fraction
+        (Fitter._noise_group)."""
         nu_arr = np.asarray(nu, dtype=np.float64)
         if not np.isfinite(nu_arr).all() or (nu_arr <= 0).any():
             raise ValueError(f"add_flux_density: nu must be finite and > 0, got {nu}")
@@ -239,12 +275,14 @@ class Fitter:
         if nu_arr.ndim != 0 and nu_arr.shape != t.shape:  # extension: one frequency per point
             raise ValueError(f"add_flux_density: an array nu must have the shape of t, got {nu_arr.shape} vs {t.shape}")
         lim = self._limit_mask(upper_limit, t, f_nu, "add_flux_density")
-        self._add_points(t, np.full_like(t, float(nu_arr)) if nu_arr.ndim == 0 else nu_arr.copy(), f_nu, err, w, lim)
+        grp = self._noise_group(noise, calibration, "add_flux_density")
+        self._add_points(t, np.full_like(t, float(nu_arr)) if nu_arr.ndim == 0 else nu_arr.copy(), f_nu, err, w, lim, grp)
 
     # fitter.py:284-314
-    def add_spectrum(self, t, nu, f_nu, err, weights=None, upper_limit=None):
+    def add_spectrum(self, t, nu, f_nu, err, weights=None, upper_limit=None, noise=None, calibration=None):
         """A broadband spectrum at one time t [s]: one point-data row per frequency.  upper_limit: None, a bool or a boolean mask of
-        the shape of nu; on a flagged row f_nu is the limit L and err the noise level sigma (Fitter._limit_mask)."""
+        the shape of nu; on a flagged row f_nu is the limit L and err the noise level sigma (Fitter._limit_mask).  noise, calibration:
+        the noise group of the rows and its calibration fraction (Fitter._noise_group)."""
         if np.ndim(t) != 0 or not np.isfinite(t) or t <= 0:
             raise ValueError(f"add_spectrum: t must be finite and > 0, got {t}")
         nu = np.asarray(nu, dtype=np.float64)
@@ -253,13 +291,16 @@ class Fitter:
                              f"max={float(nu.max())})")
         nu, f_nu, err, w = self._checked_observations(nu, f_nu, err, weights, "add_spectrum")  # nu is the axis array here
         lim = self._limit_mask(upper_limit, nu, f_nu, "add_spectrum")
-        self._add_points(np.full_like(nu, float(t)), nu, f_nu, err, w, lim)
+        grp = self._noise_group(noise, calibration, "add_spectrum")
+        self._add_points(np.full_like(nu, float(t)), nu, f_nu, err, w, lim, grp)
 
     # fitter.py:316-377
-    def add_flux(self, band, t, flux, err, num_points=5, weights=None, upper_limit=None):
+    def add_flux(self, band, t, flux, err, num_points=5, weights=None, upper_limit=None, noise=None, calibration=None):
         """Band-integrated fluxes [erg/cm^2/s] over band = (nu_min, nu_max) [Hz]; each group is one Model.flux request.
         upper_limit: None, a bool or a boolean mask of the shape of t; on a flagged row flux is the limit L >= 0 and err the noise
-        level sigma (Fitter._limit_mask); detections need strictly positive fluxes."""
+        level sigma (Fitter._limit_mask); detections need strictly positive fluxes.  noise, calibration: the noise group of the rows
+        and its calibration fraction (Fitter._noise_group); a group with calibration > 0 holds point rows only or exactly one
+        add_flux call (build_spec checks it)."""
         try:
             nu_min, nu_max = band
         except (TypeError, ValueError):
@@ -277,7 +318,8 @@ class Fitter:
             raise ValueError("add_flux: the log-flux likelihood requires strictly positive fluxes")
         order = np.argsort(t)
         bd = dict(nu_min=float(nu_min), nu_max=float(nu_max), num_points=int(num_points),
-                  t=np.ascontiguousarray(t[order]), weights=np.ascontiguousarray(w[order]), lim=None)
+                  t=np.ascontiguousarray(t[order]), weights=np.ascontiguousarray(w[order]), lim=None,
+                  noise=self._noise_group(noise, calibration, "add_flux"))
         if lim.any():  # limit rows: ln_flux / ln_err are not read there (0 and 1); L and sigma go into their own arrays
             lim, flux, err = lim[order], flux[order], err[order]
             safe = np.where(lim, 1.0, flux)
@@ -443,6 +485,11 @@ class Fitter:
         return (any(m.any() for m in self._point_lim) or any(bd["lim"] is not None for bd in self._band_obs)
                 or any(pd["lim"] is not None for pd in self._pol_obs))
 
+    @property
+    def has_noise_groups(self):
+        """Some rows belong to a noise group (noise=... of add_flux_density / add_spectrum / add_flux)."""
+        return bool(self._noise_labels)
+
     # fitter.py:407-451
     def _consolidate_data(self):
         if self._all_t is not None:
@@ -451,7 +498,7 @@ class Fitter:
             if not self._band_obs and not self._centroid_obs and not self._vis_obs and not self._pol_obs:
                 raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities or add_polarization first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
-            self._all_lim = None
+            self._all_lim = self._all_grp = None
             return
         t = np.concatenate(self._point_t)
         nu = np.concatenate(self._point_nu)
@@ -461,6 +508,8 @@ class Fitter:
         lim = np.concatenate(self._point_lim)
         order = np.argsort(t)
         t, nu, f, e, w = t[order], nu[order], f[order], e[order], w[order].copy()
+        grp = np.concatenate(self._point_grp)[order]  # the noise group ids follow the sort
+        self._all_grp = np.ascontiguousarray(grp, dtype=np.int32) if (grp >= 0).any() else None
         if lim.any():
             # upper-limit rows: the weights of the DETECTIONS are normalised to sum to their count, as without the limit rows; a limit
             # row keeps its weight as given.  ln_flux / ln_err are not read on a limit row (0 and 1).
@@ -537,6 +586,7 @@ class Fitter:
         carries the sampler-space bounds and the priors of fitting/params.py:209-227 (Uniform(lower, upper) unless ``priors``
         names another one), so that the device applies the bounds mask and adds sum ln prior (samplers.py:72-91)."""
         self._consolidate_data()
+        self._check_noise_parameters(param_defs)
         fixed = {pd.name: (pd.initial if pd.initial is not None else pd.lower) for pd in param_defs if pd.scale is Scale.fixed}
         free = [pd for pd in param_defs if pd.scale is not Scale.fixed]
         if len(free) > 16:
@@ -549,6 +599,8 @@ class Fitter:
         for name, value in fixed.items():
             if name in MODEL_PARAM_DEFAULTS or name == "A_V" or name in _lib.SKY_SLOTS or name in _lib.POL_SLOTS:
                 continue
+            if self._noise_id(name) is not None:  # (goes into vag_noise_fit_spec.sys_fixed)
+                continue
             if name not in _lib.PARAM_SLOTS:
                 raise ValueError(f"parameter {name} is not accepted by the accelerated path")
             base_fields[_lib.PARAM_SLOTS[name]] = float(value)
@@ -560,6 +612,8 @@ class Fitter:
                 spec.slot[d] = _lib.SKY_SLOTS[pd.name]
             elif pd.name in _lib.POL_SLOTS:
                 spec.slot[d] = _lib.POL_SLOTS[pd.name]
+            elif self._noise_id(pd.name) is not None:
+                spec.slot[d] = _lib.P_NOISE_SYS0 + self._noise_id(pd.name)
             elif pd.name not in _lib.PARAM_SLOTS:
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             else:
@@ -572,6 +626,7 @@ class Fitter:
         spec._vis = self._vis_spec() if self._vis_obs else None
         spec._pol = self._pol_spec(fixed) if self._pol_obs else None
         spec._lim = self._lim_spec() if self.has_limits else None
+        spec._noise = self._noise_spec(fixed) if self.has_noise_groups else None
         if self.extinction is not None and any(pd.name == "z" for pd in free):
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
@@ -686,6 +741,48 @@ class Fitter:
         pol._keep_alive = (groups, list(self._pol_obs))
         return pol
 
+    def _noise_id(self, name):
+        """The group id of the parameter name ``sys_<label>`` of a declared noise group, else None."""
+        if not name.startswith(_lib.NOISE_PREFIX) or name[len(_lib.NOISE_PREFIX):] not in self._noise_labels:
+            return None
+        return self._noise_labels.index(name[len(_lib.NOISE_PREFIX):])
+
+    def _check_noise_parameters(self, param_defs):
+        """``sys_<label>`` needs the noise group <label>; a fixed one is >= 0, a free one has lower >= 0 (> 0 on log scale)."""
+        for pd in param_defs:
+            if not pd.name.startswith(_lib.NOISE_PREFIX):
+                continue
+            if self._noise_id(pd.name) is None:
+                raise ValueError(f"the parameter {pd.name!r} needs data added with noise={pd.name[len(_lib.NOISE_PREFIX):]!r} "
+                                 f"(declared noise groups: {self._noise_labels})")
+            if pd.scale is Scale.fixed:
+                value = pd.initial if pd.initial is not None else pd.lower
+                if not np.isfinite(value) or value < 0:
+                    raise ValueError(f"a fixed {pd.name} must be finite and >= 0, got {value!r}")
+            elif not pd.lower >= 0 or (pd.scale is Scale.log and not pd.lower > 0):
+                raise ValueError(f"{pd.name}: a free systematic needs lower >= 0 (> 0 on log scale), got lower={pd.lower!r}")
+
+    def _noise_spec(self, fixed):
+        """vag_noise_fit_spec of the noise groups: the group ids of the consolidated point rows and of the band groups, the fixed
+        systematics and the calibration fractions; it keeps the arrays it points at alive.  A group with a calibration fraction
+        must lie in one pass of the likelihood call -- point rows only, or exactly one band group."""
+        ip = C.POINTER(C.c_int32)
+        nz = _lib.NoiseFitSpec()
+        nz.n_groups, nz.n_bands = len(self._noise_labels), len(self._band_obs)
+        band_ids = np.ascontiguousarray([bd["noise"] for bd in self._band_obs], dtype=np.int32)
+        for g, label in enumerate(self._noise_labels):
+            nz.sys_fixed[g] = float(fixed.get(_lib.NOISE_PREFIX + label, 0.0))
+            nz.calib[g] = float(self._noise_calib.get(label, 0.0))
+            passes = int(self._all_grp is not None and bool((self._all_grp == g).any())) + int((band_ids == g).sum())
+            if nz.calib[g] > 0 and passes > 1:
+                raise ValueError(f"noise group {label!r} has calibration={nz.calib[g]!r} and rows in {passes} passes of the "
+                                 "likelihood call: a group with a calibration fraction must hold point rows only (add_flux_density / "
+                                 "add_spectrum) or exactly one add_flux call")
+        nz.point_group = self._all_grp.ctypes.data_as(ip) if self._all_grp is not None else None
+        nz.band_group = band_ids.ctypes.data_as(ip) if band_ids.size else None
+        nz._keep_alive = (self._all_grp, band_ids)
+        return nz
+
     def _lim_spec(self):
         """vag_limit_fit_spec of the upper-limit rows (parallel to the consolidated point rows, the band groups and the polarization
         groups); it keeps the arrays it points at alive."""
@@ -769,7 +866,8 @@ class Fitter:
         if len(set(names)) != len(names):
             raise ValueError("duplicate parameter names")
         for pd in param_defs:
-            if pd.name != "A_V" and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS and pd.name not in _lib.POL_SLOTS:
+            if pd.name != "A_V" and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS and pd.name not in _lib.POL_SLOTS \
+                    and not pd.name.startswith(_lib.NOISE_PREFIX):  # (sys_<label>: _check_noise_parameters below)
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             if pd.scale is Scale.fixed:
                 continue
@@ -780,6 +878,7 @@ class Fitter:
         if "A_V" in names and self.extinction is None:
             raise ValueError("A_V needs Fitter(extinction=...)")
         self._check_pol_parameters(names)
+        self._check_noise_parameters(param_defs)
 
     def _params_at(self, sample, param_defs, resolution=None):
         """vag_model_params and A_V of one point of sampler space (the transformer of fitting/utils.py:110-135)."""
@@ -883,7 +982,11 @@ class Fitter:
 
             def run():
                 ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
-                if keep[0]._lim is not None:
+                if keep[0]._noise is not None:
+                    _lib.check(lib.vag_loglike_noise_batch_dev(
+                        h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
+                        C.byref(keep[0]._noise), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
+                elif keep[0]._lim is not None:
                     _lib.check(lib.vag_loglike_lim_batch_dev(
                         h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), C.byref(keep[0]._lim),
                         theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
@@ -908,6 +1011,7 @@ class Fitter:
         eval_dev.has_visibilities = spec._vis is not None
         eval_dev.has_polarization = spec._pol is not None
         eval_dev.has_limits = spec._lim is not None
+        eval_dev.has_noise_groups = spec._noise is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -918,6 +1022,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._noise is not None:
+                    from .dist import _NO_NOISE
+                    raise NotImplementedError(_NO_NOISE)
                 if keep[0]._lim is not None:
                     from .dist import _NO_LIMITS
                     raise NotImplementedError(_NO_LIMITS)
@@ -955,8 +1062,12 @@ class Fitter:
         h, lock = get_context(self.device)
         plan = _lib.Plan()
         with lock:
-            if spec._lim is not None:
-                ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+            ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+            if spec._noise is not None:
+                _lib.check(_lib.load().vag_loglike_noise_batch(
+                    h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), C.byref(spec._noise),
+                    samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
+            elif spec._lim is not None:
                 _lib.check(_lib.load().vag_loglike_lim_batch(
                     h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), C.byref(spec._lim),
                     samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
