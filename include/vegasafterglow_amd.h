@@ -275,6 +275,7 @@ int vag_sky_stokes_image_batch(vag_ctx* ctx, const vag_model_params* params, int
  *                      out {the VAG_NPAR block of syn_photons_build, log2_I_nu_fast on that block in registers at x0, x1, on it as a
  *                      strided column at x0, x1, log2_I_nu_fast2(x0, x1), the exact-libm log2_I_nu at x0, x1}: VAG_NPAR + 8;
  *   VAG_MATH_IC_CELL   in  {VAG_NPAR block, VAG_NQ IC extras, p, x0, x1}; out {log2_I_nu_ic, _straight, _pair, each at x0, x1};
+ *   VAG_MATH_POISSON_DEVIANCE  in {N, mu}; out the Poisson deviance D(N, mu) (n_in = 2, n_out = 1);
  *   VAG_MATH_LDS_ADD   in  {slot, value}: the 64 lanes of a wavefront add their values into the slots (integers in [0, 64)) they
  *                      name with one ds_add_f64; out: slot `lane`'s total.
  * The wave routines (WAVE_PREFIX_SUM, WAVE_SUM, SKY_WAVE_SUM, LDS_ADD) run one wavefront per 64 points and need n % 64 == 0.
@@ -287,6 +288,7 @@ enum {
     VAG_MATH_SYN_CELL, VAG_MATH_IC_CELL,
     VAG_MATH_WAVE_PREFIX_SUM, VAG_MATH_WAVE_SUM, VAG_MATH_SKY_WAVE_SUM, VAG_MATH_LDS_ADD,
     VAG_MATH_LOG_NDTR, /* ln Phi(z) of the upper-limit term (vag_loglike_lim_batch) */
+    VAG_MATH_POISSON_DEVIANCE, /* in {N, mu}, out D = mu - N - N ln(mu / N) (mu for N = 0) of the counts term (vag_loglike_counts_batch) */
     VAG_MATH_COUNT
 };
 int vag_debug_device_math(vag_ctx* ctx, int fn, const double* in, int n, double* out);
@@ -652,6 +654,56 @@ int vag_loglike_noise_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sk
 int vag_loglike_noise_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                                 const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                                 const double* d_theta, int nb, int ndim, double* d_out);
+
+/* Photon counts with a Poisson likelihood (added after VAG_ABI_VERSION 13, detect by symbol).  A counts group is one band
+ * (nu_min, nu_max, num_points Boole nodes, as vag_band_obs) with n rows; row i holds the observed counts N_i (a non-negative integer
+ * carried as a double, at most 2^53), a background expectation B_i >= 0 [counts], a scale a_i > 0 [counts per erg cm^-2 s^-1 per
+ * sample], a weight w_i >= 0 and m >= 1 indices into the group's sample times.  With F(t) the walker's band-integrated flux
+ *   mu_i = B_i + a_i sum_{k = 0 .. m-1} F(t_sample[sample_idx[i m + k]])   (summed in k order),
+ *   ln L += sum_i w_i [N_i ln mu_i - mu_i - ln N_i!],
+ * formed as chi^2 += 2 sum_i w_i D_i - 2 sum_i w_i S_i with the deviance D_i = mu_i - N_i - N_i ln(mu_i / N_i) >= 0 (mu_i for
+ * N_i = 0; vag::poisson_deviance, on the device) and the constant S_i = N_i ln N_i - N_i - ln N_i! (0 for N_i = 0; once per spec, on
+ * the host).  mu_i = 0 with N_i > 0 scores -inf for the walker, with N_i = 0 it adds 0; a NaN model value scores -inf; a row with
+ * w_i = 0 adds nothing whatever its model value.  Each group is its own pass: one band request on t_sample (its own grid from its own
+ * times, as a band group), then vag_fit_back_counts_kernel. */
+typedef struct vag_counts_obs {
+    double nu_min, nu_max;      /* [Hz] */
+    int32_t num_points;         /* Boole nodes across the band */
+    int32_t n;                  /* rows */
+    int32_t m;                  /* samples per row */
+    int32_t n_samples;          /* distinct sample times */
+    const double* t_sample;     /* [n_samples] strictly ascending, > 0 [s] */
+    const int32_t* sample_idx;  /* [n * m] in [0, n_samples) */
+    const double* counts;       /* [n] N_i */
+    const double* background;   /* [n] B_i */
+    const double* scale;        /* [n] a_i */
+    const double* weight;       /* [n] w_i */
+} vag_counts_obs;
+
+typedef struct vag_counts_fit_spec {
+    int32_t n_groups;
+    int32_t pad;
+    const vag_counts_obs* groups;  /* [n_groups] */
+} vag_counts_fit_spec;
+
+/* vag_loglike_noise_batch(_dev) with counts groups, which are passes of their own after the polarization groups.  With counts NULL
+ * or n_groups == 0 it is exactly that call (the other specs may be NULL as there); the fit spec may then hold no other data.  A walker
+ * a counts pass rejects (grid capacity, ODE rows, SSC tables) scores -inf and is counted like one a band group rejects.  Refused
+ * with VAG_E_INVALID before the device is touched, the message naming group and row: counts that are not finite, negative, not an
+ * integer or above 2^53; a background that is negative or not finite; a scale that is not finite and > 0; a weight that is negative or
+ * not finite; n < 1, m < 1 or n_samples < 1; an index outside [0, n_samples); t_sample that is not finite, <= 0 or not strictly
+ * ascending; a band or num_points that vag_band_obs would refuse; a null array.  Results are bitwise reproducible and do not depend
+ * on the evaluation order.  A walker's counts term does not depend on the rest of the batch either, with two limits: every model of
+ * the batches compared has at most 512 time nodes in its lattice (longer ones are summed in pieces), and for fits with SSC the choice
+ * between the fused and the two-pass flux launch, which follows the batch's longest lattice, has not been shown to keep the bits.
+ * (The other passes of the call keep their own behaviour: a band group's flux follows the batch in its last bits.)  The group arrays
+ * stay resident on the device by content hash. */
+int vag_loglike_counts_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                             const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                             const vag_counts_fit_spec* counts, const double* theta, int nb, int ndim, double* out);
+int vag_loglike_counts_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                                 const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                                 const vag_counts_fit_spec* counts, const double* d_theta, int nb, int ndim, double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

@@ -55,6 +55,9 @@ MATH = {name: i for i, name in enumerate([
     "exp2_fast", "exp2_ode", "exp2_sat", "exp2_or_zero", "log2_fast", "log2_tab", "log2_tab_nb",
     "rcp_fast", "rcp_ode", "rcp1", "sqrt_fast", "sqrt_ode", "sqrt1", "sp_fast", "sp_fast_global", "sp_fast_sel",
     "syn_cell", "ic_cell", "wave_prefix_sum", "wave_sum", "sky_wave_sum", "lds_add", "log_ndtr"])}
+# VAG_MATH_* appended after VAG_MATH_LOG_NDTR.  They have a mapping of their own: MATH is pinned to end with log_ndtr
+# (tests/test_limits_host.py), and the ids of both mappings are the enum's, one numbering.
+MATH_MORE = {name: len(MATH) + i for i, name in enumerate(["poisson_deviance"])}
 
 P_A_V = 1000  # VAG_P_A_V
 # VAG_P_SKY_*: the sky placement of the centroid and visibility groups (vag_loglike_sky_batch / _vis_batch), not Model fields either
@@ -125,6 +128,16 @@ class NoiseFitSpec(C.Structure):  # vag_noise_fit_spec
                 ("band_group", C.POINTER(C.c_int32)), ("sys_fixed", C.c_double * 8), ("calib", C.c_double * 8)]
 
 
+class CountsObs(C.Structure):  # vag_counts_obs
+    _fields_ = [("nu_min", C.c_double), ("nu_max", C.c_double), ("num_points", C.c_int32), ("n", C.c_int32), ("m", C.c_int32),
+                ("n_samples", C.c_int32), ("t_sample", C.POINTER(C.c_double)), ("sample_idx", C.POINTER(C.c_int32))] + \
+               [(n, C.POINTER(C.c_double)) for n in ("counts", "background", "scale", "weight")]
+
+
+class CountsFitSpec(C.Structure):  # vag_counts_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(CountsObs))]
+
+
 class FitSpec(C.Structure):
     _fields_ = [
         ("base", ModelParams), ("ndim", C.c_int32), ("slot", C.c_int32 * 16), ("is_log", C.c_int32 * 16),
@@ -189,6 +202,7 @@ EXPORTS = [
     "vag_sky_visibility_batch", "vag_debug_device_math", "vag_loglike_vis_batch", "vag_loglike_vis_batch_dev",
     "vag_sky_polarization_batch", "vag_sky_stokes_image_batch", "vag_loglike_pol_batch", "vag_loglike_pol_batch_dev",
     "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev", "vag_loglike_noise_batch", "vag_loglike_noise_batch_dev",
+    "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev",
 ]
 
 _lib = None
@@ -256,6 +270,12 @@ def load():
                                             C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec), _dp, C.c_int, C.c_int, _dp]
     lib.vag_loglike_noise_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
                                                 C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec), v, C.c_int, C.c_int, v]
+    lib.vag_loglike_counts_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
+                                             C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec), C.POINTER(CountsFitSpec), _dp, C.c_int,
+                                             C.c_int, _dp]
+    lib.vag_loglike_counts_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec),
+                                                 C.POINTER(PolFitSpec), C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec),
+                                                 C.POINTER(CountsFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -27,6 +28,7 @@
 #include "vag_sky.h"
 #include "vag_debug_math.h"
 #include "vag_log_ndtr.h"
+#include "vag_poisson.h"
 
 using namespace vag;
 
@@ -411,6 +413,7 @@ struct vag_ctx {
     DevBuf d_visfit, d_visblk, d_vispart;  // visibility groups of the likelihood: their data, their 64-visibility blocks, chi^2 partials
     DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_noisefit;  // noise groups of the likelihood (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
+    DevBuf d_countsfit;  // counts groups of the likelihood (vag_loglike_counts_batch): per group [t_sample | N | B | a | w | idx], see CountsLayout
     DevBuf d_limfit;  // upper-limit rows of the likelihood (vag_loglike_lim_batch): per block [limit | sigma | kind], see LimLayout
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -465,7 +468,7 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit;
+    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
@@ -487,6 +490,9 @@ struct vag_ctx {
     uint64_t noisefit_hash = 0;  // (d_noisefit: the noise groups of vag_loglike_noise_batch, upload_noise_spec)
     size_t noisefit_doubles = 0;
     bool noisefit_hash_valid = false;
+    uint64_t countsfit_hash = 0;  // (d_countsfit: the counts groups of vag_loglike_counts_batch, upload_counts_spec)
+    size_t countsfit_doubles = 0;
+    bool countsfit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -495,6 +501,7 @@ struct vag_ctx {
     bool ic_slow_unread = false;     // the last table build did not wait for its counters: vag_last_plan reads the slow path's from HBM
     // plan of the last grid pass
     int nb = 0, n_rows = 0, max_k = 0, max_pairs = 0;
+    int ppb_pin = 0;  // > 0: the (theta, phi) pairs per flux workgroup of the next grid / band request, whatever the batch holds (choose_pairs_per_block)
     long long n_cells = 0, total_pairs = 0, eat_cells = 0;
     int n_ok = 0;
     vag_plan plan{};
@@ -724,8 +731,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_polfit.release();
     c->h_limfit.release();
     c->h_noisefit.release();
+    c->h_countsfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -1242,6 +1250,12 @@ int choose_pairs_per_block(const vag_ctx* c) {
         const int v = std::atoi(e);
         if (v > 0) return std::min(v, std::max(1, c->max_pairs));
     }
+    // a pinned value (a counts pass of the likelihood): the partial sums of a model are then cut at the same pairs in every batch -- a
+    // model with fewer pairs than the value is one workgroup either way.  With run_flux_grid keeping such a request off the
+    // row-per-lane kernel, this is what makes the flux independent of the rest of the batch; the other launch choices the batch
+    // decides -- 256 or 512 lanes, the persistent form -- do not change the sums (tests/test_counts.py holds them to the bits), and
+    // the piece loop of lattices longer than the staged row (max_k > 512) is outside the guarantee
+    if (c->ppb_pin > 0) return std::min(c->ppb_pin, std::max(1, c->max_pairs));
     // enough workgroups to fill 256 CUs several times over, but not so many that staging the photon rows
     // and the partial grids dominate
     long long ppb = (c->total_pairs + 16383) / 16384;
@@ -1346,12 +1360,13 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
         return set_err(VAG_E_CAPACITY, "nt*nnu = %d exceeds %d per launch", slots, FLUX_MAX_SLOTS);
     // Small grids of large batches: a (theta, phi) row per lane (vag_grid_rows.h).  A lone model would walk its lattice as one
     // sequential chain there, so the batch must bring blocks of 64 rows enough to fill the GPU; models of a few rows (on-axis
-    // top hats: 32 rows) would leave lanes empty.
+    // top hats: 32 rows) would leave lanes empty.  The choice is the batch's (total_pairs) and the kernel sums in another order, so
+    // a request whose result must not depend on the batch (vag_ctx::ppb_pin, a counts pass) stays on the workgroup kernel below.
     {
         const long long blocks = (c->total_pairs + FITROWS_ROWS - 1) / FITROWS_ROWS;
         if (mode != FLUX_FUSED && !(c->batch_flags & VAG_FLAG_SPREADING) && !c->count_work && slots <= GRIDROWS_MAX_SLOTS &&
             nnu <= GRIDROWS_BANDS && nt <= GRIDROWS_MAX_NT && blocks >= 4096 && c->total_pairs >= 128LL * nb && c->n_rows > 0 &&
-            !vag_hook("VAG_GRID_ROW_PER_WORKGROUP")) {
+            !c->ppb_pin && !vag_hook("VAG_GRID_ROW_PER_WORKGROUP")) {
             const int max_blocks = std::max(1, (c->max_pairs + FITROWS_ROWS - 1) / FITROWS_ROWS);
             if (c->d_partial.ensure(sizeof(double) * (size_t)nb * max_blocks * slots)) return VAG_E_HIP;
             SeriesArgs a{};
@@ -3540,10 +3555,11 @@ static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
     return h;
 }
 
-static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false, int noise_groups = 0) {
+static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false, int noise_groups = 0,
+                           bool counts = false) {
     if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
     const int n = spec->n_data;
-    if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky && !pol)) return set_err(VAG_E_INVALID, "fit spec has no data");
+    if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky && !pol && !counts)) return set_err(VAG_E_INVALID, "fit spec has no data");
     for (int d = 0; d < ndim; ++d) {
         const int s = spec->slot[d];
         if (s == VAG_P_A_V) continue;
@@ -3932,6 +3948,66 @@ vag_fit_back_noise_kernel(const double* __restrict__ flux /* [nb][n] */, int n, 
             const double lp = ln_prior[m];
             const bool fin = ok && isfinite(acc) && lp > -INFINITY;
             out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
+            if (!fin) atomicAdd(fitstat, 1);
+        }
+    }
+}
+
+// The back of a counts pass (vag_loglike_counts_batch), one wavefront per walker like its siblings.  flux [nb][ns] holds the walker's
+// band-integrated flux at the group's ns sample times; row i gathers its m samples in k order, mu_i = B_i + a_i sum_k F[idx[i m + k]],
+// and adds w_i D(N_i, mu_i) (vag::poisson_deviance) to the lane's sum; a row with w_i = 0 adds nothing.  The lanes' sums are closed by
+// vag::wave_sum in the fixed order of the other back kernels, so the value depends on the walker's own row of flux alone.  The pass
+// adds 2 sum_i w_i D_i + const2 to chi^2, const2 = -2 sum_i w_i S_i being the walker-independent half the host formed (counts_scan).
+// Validity, the first / last pass flags, the rejection counters and the evaluation-order hand-over are vag_fit_back_kernel's.
+__global__ void __launch_bounds__(64)
+vag_fit_back_counts_kernel(const double* __restrict__ flux /* [nb][ns] */, int ns, int n, int mm, const int* __restrict__ idx /* [n][mm] */,
+                           const double* __restrict__ counts, const double* __restrict__ background, const double* __restrict__ scale,
+                           const double* __restrict__ weight, double const2, const VagGridMeta* __restrict__ meta,
+                           const int* __restrict__ row_status, const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */,
+                           double* __restrict__ chi2, int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last,
+                           double* __restrict__ out, int* __restrict__ fitstat, const int* __restrict__ order /* evaluation slot -> walker, or null */,
+                           const float* __restrict__ cost, int nb, int* __restrict__ next_order /* or null */) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    if (next_order) {  // (as vag_fit_back_kernel)
+        const float mine = cost[m];
+        int rank = 0;
+        for (int i0 = 0; i0 < nb; i0 += 64) {
+            const int i = i0 + lane;
+            const float c = i < nb ? cost[i] : -1.0f;
+            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
+        }
+        if (lane == 0) next_order[rank] = order ? order[m] : m;
+    }
+    const bool grid_ok = meta[m].status == 0;
+    double s = 0;
+    if (grid_ok) {
+        const double* f = flux + (size_t)m * ns;
+        for (int i = lane; i < n; i += 64) {
+            const double w = weight[i];
+            if (w == 0.0) continue;
+            const int* ix = idx + (size_t)i * mm;
+            double sum = 0;
+            for (int k = 0; k < mm; ++k) sum += f[ix[k]];
+            const double mu = background[i] + scale[i] * sum;
+            s += w * vag::poisson_deviance(counts[i], mu);
+        }
+    }
+    s = 2.0 * vag::wave_sum(s) + const2;
+    bool bad_row = false;
+    if (grid_ok)
+        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
+    const bool any_bad = __any(bad_row);
+    if (lane == 0) {
+        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
+        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
+        const double acc = first ? s : chi2[m] + s;
+        valid[m] = ok;
+        chi2[m] = acc;
+        if (ic_bad) atomicAdd(fitstat + 1, 1);
+        if (last) {
+            const double lp = ln_prior[m];
+            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
+            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
             if (!fin) atomicAdd(fitstat, 1);
         }
     }
@@ -4590,9 +4666,94 @@ static int upload_noise_spec(vag_ctx* c, const std::vector<double>& stage, const
     return VAG_OK;
 }
 
+// ---- counts groups (vag_loglike_counts_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
+//      in doubles, per group: [t_sample ns | N n | B n | a n | w n], then the sample indices (int32 [n m] in (n m + 1) / 2 doubles). ----
+constexpr int COUNTS_PPB = 64;  // (theta, phi) pairs per flux workgroup of a counts pass (vag_ctx::ppb_pin)
+
+struct CountsLayout {
+    std::vector<long> off;       // where group g starts in d_countsfit
+    std::vector<double> const2;  // -2 sum_i w_i S_i of group g (vag::poisson_const): the walker-independent half of its chi^2
+    int n_groups = 0;
+};
+
+// Validates the counts groups and lays their blocks out in stage (host work only: no context is touched).
+static int counts_scan(const vag_counts_fit_spec* cs, std::vector<double>& stage, CountsLayout& lay) {
+    if (cs->n_groups < 0 || !cs->groups) return set_err(VAG_E_INVALID, "counts groups: n_groups must be >= 0 with a group list, got %d", cs->n_groups);
+    lay.n_groups = cs->n_groups;
+    stage.clear();
+    for (int g = 0; g < cs->n_groups; ++g) {
+        const vag_counts_obs& o = cs->groups[g];
+        if (!(std::isfinite(o.nu_min) && std::isfinite(o.nu_max) && o.nu_min > 0 && o.nu_max > o.nu_min))
+            return set_err(VAG_E_INVALID, "counts group %d: the band needs 0 < nu_min < nu_max, both finite", g);
+        if (o.num_points < 2 || o.num_points > VAG_MAX_NU)
+            return set_err(VAG_E_INVALID, "counts group %d: num_points must be in 2..%d, got %d", g, VAG_MAX_NU, o.num_points);
+        if (o.n < 1) return set_err(VAG_E_INVALID, "counts group %d has no rows", g);
+        if (o.m < 1) return set_err(VAG_E_INVALID, "counts group %d: m (samples per row) must be >= 1, got %d", g, o.m);
+        if (o.n_samples < 1) return set_err(VAG_E_INVALID, "counts group %d has no sample times", g);
+        if (!o.t_sample || !o.sample_idx || !o.counts || !o.background || !o.scale || !o.weight)
+            return set_err(VAG_E_INVALID, "counts group %d: null array", g);
+        for (int j = 0; j < o.n_samples; ++j)
+            if (!std::isfinite(o.t_sample[j]) || !(o.t_sample[j] > 0) || (j > 0 && !(o.t_sample[j] > o.t_sample[j - 1])))
+                return set_err(VAG_E_INVALID, "counts group %d, sample %d: sample times must be finite, > 0 and strictly ascending", g, j);
+        double wS = 0;
+        for (int i = 0; i < o.n; ++i) {
+            const double N = o.counts[i];
+            if (!std::isfinite(N) || N < 0 || N != std::floor(N))
+                return set_err(VAG_E_INVALID, "counts group %d, row %d: counts must be a finite integer >= 0, got %g", g, i, N);
+            if (N > 9007199254740992.0) return set_err(VAG_E_INVALID, "counts group %d, row %d: counts above 2^53", g, i);
+            if (!std::isfinite(o.background[i]) || o.background[i] < 0)
+                return set_err(VAG_E_INVALID, "counts group %d, row %d: the background must be finite and >= 0", g, i);
+            if (!std::isfinite(o.scale[i]) || !(o.scale[i] > 0))
+                return set_err(VAG_E_INVALID, "counts group %d, row %d: the scale must be finite and > 0", g, i);
+            if (!std::isfinite(o.weight[i]) || o.weight[i] < 0)
+                return set_err(VAG_E_INVALID, "counts group %d, row %d: the weight must be finite and >= 0", g, i);
+            for (int k = 0; k < o.m; ++k) {
+                const int j = o.sample_idx[(size_t)i * o.m + k];
+                if (j < 0 || j >= o.n_samples)
+                    return set_err(VAG_E_INVALID, "counts group %d, row %d: sample index %d is outside [0, %d)", g, i, j, o.n_samples);
+            }
+            if (o.weight[i] > 0) wS += o.weight[i] * vag::poisson_const(N);
+        }
+        const size_t at = stage.size(), n = (size_t)o.n, nm = n * (size_t)o.m;
+        lay.off.push_back((long)at);
+        lay.const2.push_back(-2.0 * wS);
+        stage.resize(at + (size_t)o.n_samples + 4 * n + (nm + 1) / 2, 0.0);
+        double* dst = stage.data() + at;
+        std::memcpy(dst, o.t_sample, sizeof(double) * o.n_samples);
+        dst += o.n_samples;
+        for (const double* src : {o.counts, o.background, o.scale, o.weight}) {
+            std::memcpy(dst, src, sizeof(double) * n);
+            dst += n;
+        }
+        std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
+    }
+    return VAG_OK;
+}
+
+static int upload_counts_spec(vag_ctx* c, const vag_counts_fit_spec* cs, const std::vector<double>& stage, const CountsLayout& lay) {
+    uint64_t h = 1469598103934665603ull;
+    for (int g = 0; g < cs->n_groups; ++g) {  // (the shapes: two groups whose blocks hold the same bytes are still two layouts)
+        const int head[4] = {cs->groups[g].n, cs->groups[g].m, cs->groups[g].n_samples, cs->groups[g].num_points};
+        h = fnv1a(h, head, sizeof head);
+    }
+    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
+    if (c->countsfit_hash_valid && c->countsfit_hash == h && c->countsfit_doubles == stage.size()) return VAG_OK;  // resident already
+    c->countsfit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_countsfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    if (c->d_countsfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    std::memcpy(c->h_countsfit.as<double>(), stage.data(), sizeof(double) * stage.size());
+    HIPCHK(hipMemcpyAsync(c->d_countsfit.p, c->h_countsfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
+    c->countsfit_hash = h;
+    c->countsfit_doubles = stage.size();
+    c->countsfit_hash_valid = true;
+    return VAG_OK;
+}
+
 static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec,
                         const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
-                        const vag_pol_fit_spec* pol = nullptr, const LimLayout* lim = nullptr, const NoiseLayout* noise = nullptr) {
+                        const vag_pol_fit_spec* pol = nullptr, const LimLayout* lim = nullptr, const NoiseLayout* noise = nullptr,
+                        const vag_counts_fit_spec* counts = nullptr, const CountsLayout* clay = nullptr) {
     int rc = VAG_OK;
     const int n = spec->n_data;
     hipStream_t st = c->stream;
@@ -4627,7 +4788,8 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         return nxt.as<int>();
     };
     const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = vis ? vis->n_groups : 0, n_pol_groups = pol ? pol->n_groups : 0;
-    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups;
+    const int n_counts_groups = counts ? counts->n_groups : 0;
+    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups + n_counts_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // the SSC tables of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
     // lim_off: where the pass's block of limit rows starts in d_limfit, or -1 (no limit row: the kernel as it was)
@@ -4795,6 +4957,34 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
             n_inv = std::max(n_inv, c->plan.n_models_invalid);
         }
     }
+    for (int g = 0; g < n_counts_groups && rc == VAG_OK; ++g) {  // counts groups: one band request on the sample times each, then the Poisson term
+        const vag_counts_obs& o = counts->groups[g];
+        const double* dc = c->d_countsfit.as<double>() + clay->off[g];  // [t_sample | N | B | a | w | idx]
+        const size_t ns = (size_t)o.n_samples, nr = (size_t)o.n;
+        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(ns, (size_t)std::max(n, 1)))) return VAG_E_HIP;
+        c->order_next = d_order != nullptr;
+        c->last_order = d_order;
+        // the band request takes two things from the batch's total work -- the number of (theta, phi) pairs per workgroup, and from
+        // 262144 pairs on, for bands of at most 4 nodes, the row-per-lane kernel -- so a band group's flux depends on the batch in its
+        // last bits; here both are pinned (COUNTS_PPB pairs, the workgroup kernel), and a walker's counts term is the same bits alone
+        // and in any batch whose lattices fit the staged row (512 nodes)
+        c->ppb_pin = COUNTS_PPB;
+        rc = band_request_dev(c, d_params, nb, dc, o.n_samples, o.nu_min, o.nu_max, o.num_points, c->d_series_flux.as<double>(), nullptr);
+        c->ppb_pin = 0;
+        if (rc == VAG_OK) {
+            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
+            hipLaunchKernelGGL(vag_fit_back_counts_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n_samples, o.n, o.m,
+                               reinterpret_cast<const int*>(dc + ns + 4 * nr), dc + ns, dc + ns + nr, dc + ns + 2 * nr, dc + ns + 3 * nr,
+                               clay->const2[g], c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
+                               (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
+                               pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order,
+                               c->d_cost_f.as<float>(), nb, next_order());
+            HIPCHK(hipGetLastError());
+            ++pass;
+            n_cap = std::max(n_cap, c->plan.n_models_capacity);
+            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+        }
+    }
     c->ic_soft_fail = false;
     c->plan.n_models_capacity = n_cap;
     c->plan.n_models_invalid = n_inv;
@@ -4933,32 +5123,25 @@ int vag_loglike_lim_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
     return rc;
 }
 
-int vag_loglike_noise_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
-                                const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
-                                const double* d_theta, int nb, int ndim, double* d_out) {
-    std::vector<double> nstage, lstage;
-    NoiseLayout nlay;
-    LimLayout llay;
-    if (noise && spec) {
-        const int rc = noise_scan(spec, noise, nstage, nlay);
-        if (rc) return rc;
-    }
-    if (!nlay.any) return vag_loglike_lim_batch_dev(c, spec, sky, vis, pol, lim, d_theta, nb, ndim, d_out);  // exactly that call
-    if (lim) {
-        const int rc = lim_scan(spec, pol, lim, lstage, llay);
-        if (rc) return rc;
-    }
+// The body the chained entry points share once their specs are scanned: the context checks, the uploads of every spec block that is
+// present, and the call (repeated once on the waiting path when a planned-ahead call fails).  llay / nlay are used when their `any` is
+// set; counts with clay when counts is not null.
+static int loglike_chained_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                               const vag_pol_fit_spec* pol, const std::vector<double>& lstage, const LimLayout& llay,
+                               const std::vector<double>& nstage, const NoiseLayout& nlay, const vag_counts_fit_spec* counts,
+                               const std::vector<double>& cstage, const CountsLayout& clay, const double* d_theta, int nb, int ndim,
+                               double* d_out) {
     ApiLock api_lock(c);
     HandoffScope handoff(c);
     if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
+    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
     if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
     if (pol && pol->n_groups == 0) pol = nullptr;
     if (vis && vis->n_groups == 0) vis = nullptr;
     const bool placed = (sky && sky->n_groups > 0) || vis;
     if (!pol && !placed) sky = nullptr;  // (as vag_loglike_sky_batch_dev: nothing reads the placement)
     HIPCHK(hipSetDevice(c->device));
-    int rc = upload_fit_spec(c, spec, ndim, placed, pol != nullptr, nlay.n_groups);
+    int rc = upload_fit_spec(c, spec, ndim, placed, pol != nullptr, nlay.any ? nlay.n_groups : 0, counts != nullptr);
     if (rc) return rc;
     if (sky) {
         rc = upload_sky_spec(c, sky);
@@ -4976,12 +5159,60 @@ int vag_loglike_noise_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_
         rc = upload_lim_spec(c, lstage, llay);
         if (rc) return rc;
     }
-    rc = upload_noise_spec(c, nstage, nlay);
-    if (rc) return rc;
+    if (nlay.any) {
+        rc = upload_noise_spec(c, nstage, nlay);
+        if (rc) return rc;
+    }
+    if (counts) {
+        rc = upload_counts_spec(c, counts, cstage, clay);
+        if (rc) return rc;
+    }
     const LimLayout* lp = llay.any ? &llay : nullptr;
-    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, lp, &nlay);
-    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, lp, &nlay);
+    const NoiseLayout* np = nlay.any ? &nlay : nullptr;
+    const CountsLayout* cp = counts ? &clay : nullptr;
+    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, lp, np, counts, cp);
+    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, lp, np, counts, cp);
     return rc;
+}
+
+int vag_loglike_noise_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                                const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                                const double* d_theta, int nb, int ndim, double* d_out) {
+    std::vector<double> nstage, lstage;
+    NoiseLayout nlay;
+    LimLayout llay;
+    if (noise && spec) {
+        const int rc = noise_scan(spec, noise, nstage, nlay);
+        if (rc) return rc;
+    }
+    if (!nlay.any) return vag_loglike_lim_batch_dev(c, spec, sky, vis, pol, lim, d_theta, nb, ndim, d_out);  // exactly that call
+    if (lim) {
+        const int rc = lim_scan(spec, pol, lim, lstage, llay);
+        if (rc) return rc;
+    }
+    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, nullptr, {}, CountsLayout{}, d_theta, nb, ndim, d_out);
+}
+
+int vag_loglike_counts_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                                 const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                                 const vag_counts_fit_spec* counts, const double* d_theta, int nb, int ndim, double* d_out) {
+    if (!counts || counts->n_groups == 0)  // exactly that call
+        return vag_loglike_noise_batch_dev(c, spec, sky, vis, pol, lim, noise, d_theta, nb, ndim, d_out);
+    std::vector<double> cstage, nstage, lstage;
+    CountsLayout clay;
+    NoiseLayout nlay;
+    LimLayout llay;
+    int rc = counts_scan(counts, cstage, clay);
+    if (rc) return rc;
+    if (noise && spec) {
+        rc = noise_scan(spec, noise, nstage, nlay);
+        if (rc) return rc;
+    }
+    if (lim && spec) {
+        rc = lim_scan(spec, pol, lim, lstage, llay);
+        if (rc) return rc;
+    }
+    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, counts, cstage, clay, d_theta, nb, ndim, d_out);
 }
 
 __global__ void vag_model_cost_kernel(const VagGridMeta* __restrict__ meta, int nb, double* __restrict__ cost,
@@ -5346,6 +5577,27 @@ int vag_loglike_lim_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fi
     return VAG_OK;
 }
 
+// The host-pointer form of a chained entry point once its specs are scanned: theta goes up, dev_call(d_theta, d_out) runs the
+// device-pointer form, the values come back.
+static int loglike_chained_host(vag_ctx* c, const vag_fit_spec* spec, const double* theta, int nb, int ndim, double* out,
+                                const std::function<int(double*, double*)>& dev_call) {
+    ApiLock api_lock(c);
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
+    double* d_theta = c->d_theta_in.as<double>();
+    double* d_out = d_theta + (size_t)nb * ndim;
+    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
+    const int rc = dev_call(d_theta, d_out);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)collect_times(c);
+    return VAG_OK;
+}
+
 int vag_loglike_noise_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                             const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                             const double* theta, int nb, int ndim, double* out) {
@@ -5364,21 +5616,35 @@ int vag_loglike_noise_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_
         const int rc = lim_scan(spec, pol, lim, stage, lay);
         if (rc) return rc;
     }
-    ApiLock api_lock(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
-    double* d_theta = c->d_theta_in.as<double>();
-    double* d_out = d_theta + (size_t)nb * ndim;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
-    int rc = vag_loglike_noise_batch_dev(c, spec, sky, vis, pol, lim, noise, d_theta, nb, ndim, d_out);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return VAG_OK;
+    return loglike_chained_host(c, spec, theta, nb, ndim, out, [&](double* d_theta, double* d_out) {
+        return vag_loglike_noise_batch_dev(c, spec, sky, vis, pol, lim, noise, d_theta, nb, ndim, d_out);
+    });
+}
+
+int vag_loglike_counts_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                             const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                             const vag_counts_fit_spec* counts, const double* theta, int nb, int ndim, double* out) {
+    if (!counts || counts->n_groups == 0)  // exactly that call
+        return vag_loglike_noise_batch(c, spec, sky, vis, pol, lim, noise, theta, nb, ndim, out);
+    {  // (checked again, and laid out, by the _dev form)
+        std::vector<double> stage;
+        CountsLayout clay;
+        int rc = counts_scan(counts, stage, clay);
+        if (rc) return rc;
+        if (noise && spec) {
+            NoiseLayout lay;
+            rc = noise_scan(spec, noise, stage, lay);
+            if (rc) return rc;
+        }
+        if (lim && spec) {
+            LimLayout lay;
+            rc = lim_scan(spec, pol, lim, stage, lay);
+            if (rc) return rc;
+        }
+    }
+    return loglike_chained_host(c, spec, theta, nb, ndim, out, [&](double* d_theta, double* d_out) {
+        return vag_loglike_counts_batch_dev(c, spec, sky, vis, pol, lim, noise, counts, d_theta, nb, ndim, d_out);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #pragma once
 #include "vag_ic_kernels.h"
 #include "vag_log_ndtr.h"
+#include "vag_poisson.h"
 #include "vag_rs.h"
 #include "vag_sky.h"
 
@@ -20,6 +21,7 @@ inline int math_n_in(int fn) {
         case VAG_MATH_SYN_CELL: return MATH_SYN_IN;
         case VAG_MATH_IC_CELL: return MATH_IC_IN;
         case VAG_MATH_LDS_ADD: return 2;  // slot (an integer in [0, 64)), value
+        case VAG_MATH_POISSON_DEVIANCE: return 2;  // N, mu
         default: return (fn >= 0 && fn < VAG_MATH_COUNT) ? 1 : 0;
     }
 }
@@ -105,6 +107,9 @@ __global__ void __launch_bounds__(64) vag_math_probe_kernel(int fn, int n, const
             out[i] = s_slot[lane];
             return;
         }
+        case VAG_MATH_POISSON_DEVIANCE:
+            if (ok) out[i] = poisson_deviance(in[2 * (size_t)i], in[2 * (size_t)i + 1]);
+            return;
         default: break;
     }
     if (!ok) return;

@@ -25,6 +25,8 @@ _NO_LIMITS = ("sharded likelihood calls do not support upper limits (upper_limit
               "add_flux / add_polarization): evaluate on one device (Fitter.device_evaluator / log_prob_batch)")
 _NO_NOISE = ("sharded likelihood calls do not support noise groups (noise=... of Fitter.add_flux_density / add_spectrum / "
              "add_flux): evaluate on one device (Fitter.device_evaluator / log_prob_batch)")
+_NO_COUNTS = ("sharded likelihood calls do not support photon counts (Fitter.add_counts): evaluate on one device "
+              "(Fitter.device_evaluator / log_prob_batch)")
 
 
 def shard_range(n, rank, world):
@@ -103,6 +105,8 @@ class WalkerSharder:
             raise NotImplementedError(_NO_LIMITS)
         if getattr(eval_dev, "has_noise_groups", False):
             raise NotImplementedError(_NO_NOISE)
+        if getattr(eval_dev, "has_counts", False):
+            raise NotImplementedError(_NO_COUNTS)
         self.eval_dev, self.group = eval_dev, group
         self.device = device if device is not None else _default_device(group)
         self.native = getattr(eval_dev, "native", None)
@@ -207,6 +211,8 @@ def sharded_loglike(samples, local_eval, group=None, device=None):
         raise NotImplementedError(_NO_LIMITS)
     if getattr(getattr(local_eval, "__self__", None), "has_noise_groups", False):
         raise NotImplementedError(_NO_NOISE)
+    if getattr(getattr(local_eval, "__self__", None), "has_counts", False):
+        raise NotImplementedError(_NO_COUNTS)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     nb = samples.shape[0]
     if not (dist.is_available() and dist.is_initialized()):

@@ -174,6 +174,7 @@ class Fitter:
         self._centroid_obs = []  # VLBI centroid groups (add_centroid): one vag_centroid_obs each
         self._vis_obs = []  # VLBI visibility groups (add_visibilities): one vag_visibility_obs each
         self._pol_obs = []  # polarization groups (add_polarization): one vag_polarization_obs each
+        self._counts_obs = []  # photon-count groups (add_counts): one vag_counts_obs each
         self._ext_kernel = None
         self._ext_kernels = {}  # z -> 0.4 ln10 k(lambda_rest) over the consolidated point data
         self._ext_z = float(z)
@@ -329,6 +330,81 @@ class Fitter:
         else:
             bd.update(ln_flux=np.ascontiguousarray(np.log(flux[order])), ln_err=np.ascontiguousarray(err[order] / flux[order]))
         self._band_obs.append(bd)
+
+    def add_counts(self, band, t_start, exposure, counts, conversion, background=0.0, num_points=5, num_exposure_points=1,
+                   weights=None):
+        """Photon counts with a Poisson likelihood (the Cash statistic): row i observed counts[i] photons in band = (nu_min, nu_max)
+        [Hz] during [t_start[i], t_start[i] + exposure[i]] [s].  The expected counts are
+            mu_i = background_i + conversion_i * exposure_i * <F>_i,
+        conversion [counts per erg cm^-2] (effective area over mean photon energy; a scalar or one per row), background [counts]
+        (a scalar or one per row, >= 0), <F>_i the model's band-integrated flux (Model.flux with num_points Boole nodes) averaged
+        over the window: num_exposure_points = 1 takes the midpoint t_start + exposure / 2, m >= 2 the mean of the m equally spaced
+        samples t_start + k exposure / (m - 1), k = 0 .. m-1 (both ends, as Model.flux_density_exposures).  The row adds
+        w_i [N_i ln mu_i - mu_i - ln N_i!] to ln L; N_i = 0 is a valid row (a non-detection).  The samples of all rows are merged into
+        one strictly ascending list, equal times evaluated once, so contiguous bins share their end points; the group is one
+        Model.flux request on that list.  Weights are used as given.  Nothing is recorded when the call raises."""
+        who = "add_counts"
+        try:
+            nu_min, nu_max = band
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: band must be a (nu_min, nu_max) tuple in Hz, got {band!r}") from None
+        if not (np.isfinite(nu_min) and np.isfinite(nu_max) and 0 < nu_min < nu_max):
+            raise ValueError(f"{who}: band must satisfy 0 < nu_min < nu_max with both finite; got nu_min={nu_min}, nu_max={nu_max}")
+        if int(num_points) != num_points or num_points < 2:
+            raise ValueError(f"{who}: num_points must be an integer >= 2 for band integration, got {num_points!r}")
+        if int(num_exposure_points) != num_exposure_points or num_exposure_points < 1:
+            raise ValueError(f"{who}: num_exposure_points must be an integer >= 1, got {num_exposure_points!r}")
+        m = int(num_exposure_points)
+        t0, expo, N = (np.asarray(a, dtype=np.float64) for a in (t_start, exposure, counts))
+        if t0.ndim != 1 or t0.size == 0:
+            raise ValueError(f"{who}: t_start must be a non-empty 1-D array")
+        if not (t0.shape == expo.shape == N.shape):
+            raise ValueError(f"{who}: t_start, exposure and counts must have the same shape; got {t0.shape}, {expo.shape}, {N.shape}")
+        if not np.isfinite(t0).all() or (t0 <= 0).any():
+            raise ValueError(f"{who}: t_start must be finite and > 0 at every row")
+        if not np.isfinite(expo).all() or (expo <= 0).any():
+            raise ValueError(f"{who}: exposure must be finite and > 0 at every row")
+        if not np.isfinite(N).all() or (N < 0).any() or (N != np.floor(N)).any():
+            raise ValueError(f"{who}: counts must be finite integers >= 0")
+        if (N > 2.0 ** 53).any():
+            raise ValueError(f"{who}: counts above 2^53 are not supported")
+
+        def per_row(value, name):
+            a = np.asarray(value, dtype=np.float64)
+            if a.ndim != 0 and a.shape != t0.shape:
+                raise ValueError(f"{who}: {name} must be a scalar or have the shape of t_start, got {a.shape} vs {t0.shape}")
+            return np.broadcast_to(a, t0.shape).copy()
+        conv, bkg = per_row(conversion, "conversion"), per_row(background, "background")
+        if not np.isfinite(conv).all() or (conv <= 0).any():
+            raise ValueError(f"{who}: conversion must be finite and > 0 at every row")
+        if not np.isfinite(bkg).all() or (bkg < 0).any():
+            raise ValueError(f"{who}: background must be finite and >= 0 at every row")
+        if weights is None:
+            w = np.ones_like(t0)
+        else:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape != t0.shape or not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError(f"{who}: weights must have the shape of t_start and be finite and >= 0")
+        if m == 1:
+            times = (t0 + 0.5 * expo)[:, None]
+        else:
+            times = t0[:, None] + np.arange(m, dtype=np.float64)[None, :] * (expo / float(m - 1))[:, None]
+        if not np.isfinite(times).all():
+            raise ValueError(f"{who}: t_start + exposure must be finite")
+        t_sample, inverse = np.unique(times.ravel(), return_inverse=True)  # ascending, equal times once
+        with np.errstate(over="ignore"):
+            scale = conv * expo / float(m)
+        if not np.isfinite(scale).all() or (scale <= 0).any():
+            raise ValueError(f"{who}: conversion * exposure must be finite and > 0 at every row")
+        c = np.ascontiguousarray
+        self._counts_obs.append(dict(nu_min=float(nu_min), nu_max=float(nu_max), num_points=int(num_points), m=m,
+                                     t_sample=c(t_sample), sample_idx=c(inverse.reshape(t0.size, m), dtype=np.int32), counts=c(N),
+                                     background=c(bkg), scale=c(scale), weights=c(w)))
+
+    @property
+    def has_counts(self):
+        """Some data are photon counts (add_counts)."""
+        return bool(self._counts_obs)
 
     def add_centroid(self, nu, t, east, north, err_east, err_north, weights=None):
         """VLBI centroid positions at one frequency nu [Hz]: offsets east / north of a reference position and their errors [rad]
@@ -495,8 +571,9 @@ class Fitter:
         if self._all_t is not None:
             return
         if not self._point_t:
-            if not self._band_obs and not self._centroid_obs and not self._vis_obs and not self._pol_obs:
-                raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities or add_polarization first")
+            if not self._band_obs and not self._centroid_obs and not self._vis_obs and not self._pol_obs and not self._counts_obs:
+                raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities, add_polarization or "
+                                 "add_counts first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
             self._all_lim = self._all_grp = None
             return
@@ -627,6 +704,7 @@ class Fitter:
         spec._pol = self._pol_spec(fixed) if self._pol_obs else None
         spec._lim = self._lim_spec() if self.has_limits else None
         spec._noise = self._noise_spec(fixed) if self.has_noise_groups else None
+        spec._counts = self._counts_spec() if self._counts_obs else None
         if self.extinction is not None and any(pd.name == "z" for pd in free):
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
@@ -686,6 +764,23 @@ class Fitter:
         sky.pa_fixed, sky.east0_fixed, sky.north0_fixed = (float(fixed.get(k, 0.0)) for k in ("pa", "east0", "north0"))
         sky._keep_alive = (groups, list(self._centroid_obs))
         return sky
+
+    def _counts_spec(self):
+        """vag_counts_fit_spec of the counts groups; it keeps the arrays it points at alive."""
+        cs = _lib.CountsFitSpec()
+        groups = (_lib.CountsObs * len(self._counts_obs))()
+        for g, cd in enumerate(self._counts_obs):
+            o = groups[g]
+            o.nu_min, o.nu_max, o.num_points = cd["nu_min"], cd["nu_max"], cd["num_points"]
+            o.n, o.m, o.n_samples = cd["counts"].size, cd["m"], cd["t_sample"].size
+            o.t_sample = cd["t_sample"].ctypes.data_as(_dp)
+            o.sample_idx = cd["sample_idx"].ctypes.data_as(C.POINTER(C.c_int32))
+            for name in ("counts", "background", "scale"):
+                setattr(o, name, cd[name].ctypes.data_as(_dp))
+            o.weight = cd["weights"].ctypes.data_as(_dp)
+        cs.n_groups, cs.groups = len(self._counts_obs), groups
+        cs._keep_alive = (groups, list(self._counts_obs))
+        return cs
 
     def _vis_spec(self):
         """vag_vis_fit_spec of the visibility groups; it keeps the arrays it points at alive."""
@@ -833,6 +928,27 @@ class Fitter:
         model = self.model(best_params, param_defs, resolution)
         return [model.sky_polarization(pd["t"], pd["nu"], b=vals["pol_b"], pi_max=vals["pol_pi_max"], b_rvs=vals["pol_b_rvs"],
                                        pi_max_rvs=vals["pol_pi_max_rvs"], pa=vals["pa"], n_az=pd["n_az"]) for pd in self._pol_obs]
+
+    def counts(self, best_params, param_defs, resolution=None):
+        """The expected counts mu of every counts group at a point of sampler space: a list of float64 arrays, one per group, in
+        the order the rows were added.  Each group is one vag_flux_batch request on the group's merged sample times;
+        mu_i = background_i + scale_i * sum_k F[sample_idx[i, k]], summed in k order.  The likelihood forms mu the same way on the
+        same request, but with its flux workgroups at a pinned size (so that a walker's term does not depend on the batch):
+        the two agree to rounding (1e-15 relative), not to the bits."""
+        p, _ = self._params_at(best_params, param_defs, resolution)
+        h, lock = get_context(self.device)
+        out = []
+        for cd in self._counts_obs:
+            ts = cd["t_sample"]
+            flux = np.empty(ts.size)
+            with lock:  # (vag_flux_batch: the total of the enabled components as the likelihood's own band request forms it)
+                _lib.check(_lib.load().vag_flux_batch(h, C.byref(p), 1, ts.ctypes.data_as(_dp), ts.size, cd["nu_min"], cd["nu_max"],
+                                                      cd["num_points"], flux.ctypes.data_as(_dp)))
+            total = np.zeros(cd["counts"].size)
+            for k in range(cd["m"]):
+                total = total + flux[cd["sample_idx"][:, k]]
+            out.append(cd["background"] + cd["scale"] * total)
+        return out
 
     def visibilities(self, best_params, param_defs, resolution=None):
         """The model visibilities at the data of every visibility group at a point of sampler space: a list of complex128 arrays,
@@ -982,7 +1098,11 @@ class Fitter:
 
             def run():
                 ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
-                if keep[0]._noise is not None:
+                if keep[0]._counts is not None:
+                    _lib.check(lib.vag_loglike_counts_batch_dev(
+                        h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
+                        ref(keep[0]._noise), C.byref(keep[0]._counts), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
+                elif keep[0]._noise is not None:
                     _lib.check(lib.vag_loglike_noise_batch_dev(
                         h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
                         C.byref(keep[0]._noise), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
@@ -1012,6 +1132,7 @@ class Fitter:
         eval_dev.has_polarization = spec._pol is not None
         eval_dev.has_limits = spec._lim is not None
         eval_dev.has_noise_groups = spec._noise is not None
+        eval_dev.has_counts = spec._counts is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -1022,6 +1143,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._counts is not None:
+                    from .dist import _NO_COUNTS
+                    raise NotImplementedError(_NO_COUNTS)
                 if keep[0]._noise is not None:
                     from .dist import _NO_NOISE
                     raise NotImplementedError(_NO_NOISE)
@@ -1063,7 +1187,11 @@ class Fitter:
         plan = _lib.Plan()
         with lock:
             ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
-            if spec._noise is not None:
+            if spec._counts is not None:
+                _lib.check(_lib.load().vag_loglike_counts_batch(
+                    h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
+                    C.byref(spec._counts), samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
+            elif spec._noise is not None:
                 _lib.check(_lib.load().vag_loglike_noise_batch(
                     h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), C.byref(spec._noise),
                     samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
