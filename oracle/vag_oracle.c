@@ -3632,6 +3632,7 @@ static int details_impl(const vag_model_params* p, double t_min, double t_max, v
             if (EX_(14))
                 for (int s = 0; s < n_probe; ++s) EX_(14)[q * n_probe + s] = compute_log2_I_nu(ph, probe_lg2_nu[s]);
             if (EX_(15)) EX_(15)[q] = (double)shock->injection_idx[q / nt];
+            if (EX_(16)) EX_(16)[q] = shock->theta[q]; /* the polar angle of the cell (evolved, on a spreading jet) */
         }
         const size_t ne = (size_t)pl.eat.n_phi_eff * n;
         if (EX_(11)) memcpy(EX_(11), pl.eat.lg2_t, sizeof(double) * ne);

@@ -39,7 +39,7 @@ int vag_oracle_flux_density_exposures(const vag_model_params* p, const double* t
 int vag_oracle_details(const vag_model_params* p, double t_min, double t_max, vag_details_shape* shape,
                        const vag_details_out* out, double** extra, int n_extra, int* n_phi_eff,
                        const double* probe_lg2_nu, int n_probe);
-/* same for the reverse shock of a Model(rvs_rad=...); extra[15] = injection_idx per cell */
+/* same for the reverse shock of a Model(rvs_rad=...); extra[15] = injection_idx per cell, extra[16] = the cell's polar angle */
 int vag_oracle_details_rvs(const vag_model_params* p, double t_min, double t_max, vag_details_shape* shape,
                            const vag_details_out* out, double** extra, int n_extra, int* n_phi_eff,
                            const double* probe_lg2_nu, int n_probe);

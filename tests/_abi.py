@@ -210,7 +210,7 @@ class CpuLib:
         return (sh.n_phi, sh.n_theta, sh.n_t, sh.n_reps, sh.symmetry, sh.phi_mirrored)
 
     EXTRA_NAMES = ["gamma_m", "gamma_c", "gamma_a", "gamma_M", "N_e", "column_den", "nu_m", "nu_c", "nu_a",
-                   "nu_M", "I_nu_max", "lg2_t", "lg2_doppler", "lg2_geom", "lg2_I_probe", "injection_idx"]
+                   "nu_M", "I_nu_max", "lg2_t", "lg2_doppler", "lg2_geom", "lg2_I_probe", "injection_idx", "theta_cell"]
 
     def details(self, prm, t_min, t_max, probe_lg2_nu=None, rvs=False):
         """Intermediates of the forward shock (or, rvs=True, of the reverse shock of a Model(rvs_rad=...))."""
@@ -234,8 +234,10 @@ class CpuLib:
             ex[n] = np.zeros((npe, nth, nt))
         ex["lg2_I_probe"] = np.zeros((nth, nt, max(probe.size, 1)))
         ex["injection_idx"] = np.zeros((nth, nt))
-        arr = (_dp * 16)(*[_p(ex[n]) for n in self.EXTRA_NAMES])
-        self._check(fn(C.byref(prm), t_min, t_max, C.byref(sh), C.byref(out), arr, 16, C.byref(nphi_eff),
+        ex["theta_cell"] = np.zeros((nth, nt))
+        n_extra = 17 if self.prefix == "vag_oracle" else 16  # (the reference driver has no per-cell angle)
+        arr = (_dp * 17)(*[_p(ex[n]) for n in self.EXTRA_NAMES])
+        self._check(fn(C.byref(prm), t_min, t_max, C.byref(sh), C.byref(out), arr, n_extra, C.byref(nphi_eff),
                        _p(probe) if probe.size else None, probe.size))
         d.update(ex)
         d["shape"] = dict(n_phi=nphi, n_theta=nth, n_t=nt, n_reps=sh.n_reps, symmetry=sh.symmetry,

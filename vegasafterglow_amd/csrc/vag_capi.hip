@@ -1403,6 +1403,9 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
             const dim3 g_all((max_blocks + GRIDROWS_WAVES - 1) / GRIDROWS_WAVES, nb), b(SERIES_THREADS * GRIDROWS_WAVES);
             const dim3 g_pers((unsigned)std::max<long long>(1, std::min<long long>(wg_need, 3LL * c->n_cus)));
             const size_t lds = grid_rows_lds_bytes(slots);
+            if (vag_hook("VAG_DEBUG_LAUNCH"))
+                std::fprintf(stderr, "[vag] grid rows launch: mode %d nt=%d nnu=%d blocks=%lld persistent=%d lds=%zu B\n", mode, nt, nnu, blocks,
+                             (int)persistent, lds);
             if (mode == FLUX_SYN_IC)
                 hipLaunchKernelGGL((vag_flux_grid_rows_kernel<FLUX_SYN_IC>), g_all, b, lds, st, a);
             else if (mode == FLUX_SSC)
@@ -2466,6 +2469,9 @@ int run_flux_series(vag_ctx* c, const vag_model_params* d_params, int nb, const 
             a.cellgeo = c->d_cellgeo.as<double>();
             // vag_ctx_count_work: the tallying instantiation (plain synchrotron, <= 4 bands, no spreading: the walker metric's case)
             const bool tally = c->count_work && mode == FLUX_SYN && !spread && n_bands <= 4;
+            if (vag_hook("VAG_DEBUG_LAUNCH"))
+                std::fprintf(stderr, "[vag] fit rows launch: mode %d n=%d bands=%d blocks=%lld waves/block=%d spreading=%d lds=%zu B\n", mode, n,
+                             n_bands, blocks, wpb, (int)spread, lds);
             if (tally) {
                 if (c->d_workcount.ensure(2 * sizeof(unsigned long long))) return VAG_E_HIP;
                 HIPCHK(hipMemsetAsync(c->d_workcount.p, 0, 2 * sizeof(unsigned long long), st));
@@ -5938,9 +5944,10 @@ int vag_details_eat(vag_ctx* c, const vag_model_params* params, double t_min, do
     if (tmp.ensure(sizeof(double) * 2 * total)) return VAG_E_HIP;
     double* d_t = tmp.as<double>();
     hipLaunchKernelGGL(vag_eat_details_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
-                       c->d_params.as<vag_model_params>(), c->d_meta.as<VagGridMeta>(), c->d_geo_th.as<double>(),
-                       c->d_geo_ph.as<double>(), c->d_rep_of.as<int>(), c->d_cellpar.as<double>(),
-                       (params->flags & VAG_FLAG_SPREADING) ? c->d_cellgeo.as<double>() : nullptr, d_t, d_t + total);
+                       c->d_params.as<vag_model_params>(), c->d_meta.as<VagGridMeta>(), c->d_theta.as<double>(),
+                       c->d_phi.as<double>(), c->d_rep_of.as<int>(), c->d_cellpar.as<double>(),
+                       (params->flags & VAG_FLAG_SPREADING) ? c->d_shock.as<double>() + (size_t)VS_THETA * c->n_cells : nullptr, d_t,
+                       d_t + total);
     if (hipGetLastError() != hipSuccess) {
         tmp.release();
         return set_err(VAG_E_HIP, "vag_eat_details_kernel launch failed");

@@ -888,10 +888,17 @@ vag_profile_kernel(const vag_model_params* __restrict__ params, int kind, const 
 // Model.details(): observer time [s] and Doppler factor of every (phi, theta, k) cell of model 0, the linear forms of what
 // eat_row keeps as logs (ShockDetails.t_obs = obs.time / sec, .Doppler = exp2(lg2_doppler), pybind/pymodel.cpp:296-298).
 // out_* are [n_phi_eff][n_theta][n_t]; one lane per cell.
+// Both are formed without their cancellations, so that they are good to a few ulp of what r, Gamma, t_src and the angles say
+// (tests/test_flux_stage.py holds them to 1e-13 of an extended-precision lattice).  Written as the flux kernels form them,
+// 1 - cos_v from cos_v and Gamma - u cos_v, a head-on cell of Lorentz factor 300 loses 2 Gamma^2 eps ~ 2e-11 in both: harmless in a
+// flux (the interpolation is continuous in t and nu), but not what a details call should report.  Here
+//   1 - cos_v = 2 sin^2((theta - theta_obs) / 2) + 2 sin(theta) sin(theta_obs) sin^2(phi / 2)   (a sum of non-negative terms),
+//   Gamma - u cos_v = 1 / (Gamma + u) + u (1 - cos_v).
 __global__ void __launch_bounds__(256)
 vag_eat_details_kernel(const vag_model_params* __restrict__ params, const VagGridMeta* __restrict__ meta,
-                       const double* __restrict__ geo_th, const double* __restrict__ geo_ph, const int* __restrict__ rep_of,
-                       const double* __restrict__ cellpar, const double* __restrict__ cellgeo /* spreading jets, else null */,
+                       const double* __restrict__ theta /* [n_theta] */, const double* __restrict__ phi /* [n_phi] */,
+                       const int* __restrict__ rep_of, const double* __restrict__ cellpar,
+                       const double* __restrict__ cell_theta /* spreading jets: the evolved polar angle per cell, else null */,
                        double* __restrict__ out_t, double* __restrict__ out_dop) {
     const VagGridMeta M = meta[0];
     if (M.status != 0) return;
@@ -901,21 +908,16 @@ vag_eat_details_kernel(const vag_model_params* __restrict__ params, const VagGri
     if (q >= total) return;
     const int k = (int)(q % K), j = (int)((q / K) % nth), i = (int)(q / ((long long)K * nth));
     const vag_model_params P = params[0];
-    const double one_plus_z = 1 + P.z, cos_obs = cos(P.theta_obs), sin_obs = sin(P.theta_obs);
+    const double one_plus_z = 1 + P.z;
     const int rep = rep_of[j] + i * M.rep_phi_stride;  // ((phi, theta) pair rows of a non-axisymmetric spreading jet)
     const double* par = cellpar + (long long)rep * K * VAG_NPAR;
-    const double G = par[VP_GAMMA * K + k], u = par[VP_U * K + k], r = par[VP_R * K + k], teng = par[VP_TENG * K + k];
-    double cos_v, time;
-    if (cellgeo) {
-        const double* geo = cellgeo + (long long)rep * K * 3;
-        cos_v = geo[K + k] * geo_ph[i] * sin_obs + geo[k] * cos_obs;
-        time = (teng + (1 - cos_v) * r / C_C) * one_plus_z;
-    } else {
-        cos_v = geo_th[M.th_stride + j] * geo_ph[i] * sin_obs + geo_th[j] * cos_obs;
-        time = teng * one_plus_z + (1 - cos_v) / C_C * one_plus_z * r;
-    }
-    out_t[q] = time / U_SEC;
-    out_dop[q] = 1.0 / (G - u * cos_v);
+    const double G = par[VP_GAMMA * K + k], r = par[VP_R * K + k], teng = par[VP_TENG * K + k];
+    const double th = cell_theta ? cell_theta[(long long)rep * K + k] : theta[j];
+    const double s_half = sin(0.5 * (th - P.theta_obs)), s_phi = sin(0.5 * phi[i]);
+    const double one_minus_cos_v = 2 * s_half * s_half + 2 * sin(th) * sin(P.theta_obs) * (s_phi * s_phi);
+    const double u = sqrt((G - 1) * (G + 1));
+    out_t[q] = (teng + one_minus_cos_v * r / C_C) * one_plus_z / U_SEC;
+    out_dop[q] = 1.0 / (1.0 / (G + u) + u * one_minus_cos_v);
 }
 
 // 128 VGPRs (four workgroups of 256, two of 512 per CU) is what the occupancy of every measured shape hangs on: the C2 launch asks
