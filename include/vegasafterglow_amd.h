@@ -276,6 +276,8 @@ int vag_sky_stokes_image_batch(vag_ctx* ctx, const vag_model_params* params, int
  *                      strided column at x0, x1, log2_I_nu_fast2(x0, x1), the exact-libm log2_I_nu at x0, x1}: VAG_NPAR + 8;
  *   VAG_MATH_IC_CELL   in  {VAG_NPAR block, VAG_NQ IC extras, p, x0, x1}; out {log2_I_nu_ic, _straight, _pair, each at x0, x1};
  *   VAG_MATH_POISSON_DEVIANCE  in {N, mu}; out the Poisson deviance D(N, mu) (n_in = 2, n_out = 1);
+ *   VAG_MATH_LOG_SLOPE  in {F_0 .. F_7, c_0 .. c_7, K}; out sum_{k = 1 .. K-1} c_k ln(F_k / F_0), NaN unless F_0 .. F_{K-1} are all
+ *                      finite and > 0 (n_in = 17, n_out = 1; entries from K on are not read);
  *   VAG_MATH_LDS_ADD   in  {slot, value}: the 64 lanes of a wavefront add their values into the slots (integers in [0, 64)) they
  *                      name with one ds_add_f64; out: slot `lane`'s total.
  * The wave routines (WAVE_PREFIX_SUM, WAVE_SUM, SKY_WAVE_SUM, LDS_ADD) run one wavefront per 64 points and need n % 64 == 0.
@@ -289,6 +291,7 @@ enum {
     VAG_MATH_WAVE_PREFIX_SUM, VAG_MATH_WAVE_SUM, VAG_MATH_SKY_WAVE_SUM, VAG_MATH_LDS_ADD,
     VAG_MATH_LOG_NDTR, /* ln Phi(z) of the upper-limit term (vag_loglike_lim_batch) */
     VAG_MATH_POISSON_DEVIANCE, /* in {N, mu}, out D = mu - N - N ln(mu / N) (mu for N = 0) of the counts term (vag_loglike_counts_batch) */
+    VAG_MATH_LOG_SLOPE, /* in {8 fluxes, 8 coefficients, K}, out the pivot-form log-slope of the spectral-index term (vag_loglike_index_batch) */
     VAG_MATH_COUNT
 };
 int vag_debug_device_math(vag_ctx* ctx, int fn, const double* in, int n, double* out);
@@ -704,6 +707,53 @@ int vag_loglike_counts_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_s
 int vag_loglike_counts_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                                  const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                                  const vag_counts_fit_spec* counts, const double* d_theta, int nb, int ndim, double* d_out);
+
+/* Spectral indices (added after VAG_ABI_VERSION 13, detect by symbol).  A spectral-index group is k frequencies
+ * nu_0 < .. < nu_{k-1} (2 <= k <= VAG_INDEX_MAX_NODES), k coefficients c_j (c_0 is carried but never read), a scalar ext_slope, and
+ * n >= 1 rows (t_i, s_i, sigma_i, w_i); times are ascending, equal times are allowed.  With F the walker's flux density (the sum of
+ * every enabled component, as for point rows) and A_V the walker's extinction (free or vag_fit_spec::a_v_fixed):
+ *   S_i    = sum_{j = 1 .. k-1} c_j ln(F(t_i, nu_j) / F(t_i, nu_0)) - A_V ext_slope   (summed in j order; vag::log_slope),
+ *   chi^2 += sum_i w_i ((S_i - s_i) / sigma_i)^2.
+ * The pivot form is part of the definition: the sum is not sum_j c_j ln F_j (vag_index.h says why).  A row with w_i = 0 adds nothing
+ * whatever its model values; a row with w_i > 0 at which some F(t_i, nu_j) is <= 0 or not finite makes the walker score -inf (the
+ * slope is undefined; counted in n_walkers_rejected) -- the rule of the centroid and polarization groups, not the 1e-300 clamp of
+ * the point rows.  Each group is its own pass: the n k points (t_i, nu_j), i outer, as one series request (the path of the point
+ * rows, its own grid from its own times), then vag_fit_back_index_kernel. */
+#define VAG_INDEX_MAX_NODES 8
+typedef struct vag_index_obs {
+    int32_t n;             /* rows */
+    int32_t k;             /* frequencies */
+    const double* nu;      /* [k] strictly ascending, > 0 [Hz] */
+    const double* coef;    /* [k] c_j */
+    double ext_slope;      /* sum_{j >= 1} c_j (kappa_j - kappa_0), kappa = 0.4 ln10 k(lambda_rest); 0 without an extinction law */
+    const double* t;       /* [n] ascending, > 0 [s] */
+    const double* value;   /* [n] s_i: the observed slope d ln F / d ln nu */
+    const double* err;     /* [n] sigma_i > 0 */
+    const double* weight;  /* [n] w_i >= 0 */
+} vag_index_obs;
+
+typedef struct vag_index_fit_spec {
+    int32_t n_groups;
+    int32_t pad;
+    const vag_index_obs* groups;  /* [n_groups] */
+} vag_index_fit_spec;
+
+/* vag_loglike_counts_batch(_dev) with spectral-index groups, which are passes of their own after the counts groups.  With index NULL
+ * or n_groups == 0 it is exactly that call (the other specs may be NULL as there); the fit spec may then hold no other data.  A
+ * walker an index pass rejects (grid capacity, ODE rows, SSC tables) scores -inf and is counted like one any other pass rejects.
+ * Refused with VAG_E_INVALID before the device is touched, the message naming group and row: k outside 2..VAG_INDEX_MAX_NODES; a
+ * frequency that is not finite, not positive or not strictly ascending; a coefficient or ext_slope that is not finite; a time that
+ * is not finite, <= 0 or descending; a value that is not finite; an err that is not finite and > 0; a weight that is negative or
+ * not finite; a null array; n < 1.  Results are bitwise reproducible.  The group arrays stay resident on the device by content
+ * hash. */
+int vag_loglike_index_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                            const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                            const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* theta, int nb, int ndim,
+                            double* out);
+int vag_loglike_index_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                                const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                                const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* d_theta, int nb,
+                                int ndim, double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

@@ -57,7 +57,7 @@ MATH = {name: i for i, name in enumerate([
     "syn_cell", "ic_cell", "wave_prefix_sum", "wave_sum", "sky_wave_sum", "lds_add", "log_ndtr"])}
 # VAG_MATH_* appended after VAG_MATH_LOG_NDTR.  They have a mapping of their own: MATH is pinned to end with log_ndtr
 # (tests/test_limits_host.py), and the ids of both mappings are the enum's, one numbering.
-MATH_MORE = {name: len(MATH) + i for i, name in enumerate(["poisson_deviance"])}
+MATH_MORE = {name: len(MATH) + i for i, name in enumerate(["poisson_deviance", "log_slope"])}
 
 P_A_V = 1000  # VAG_P_A_V
 # VAG_P_SKY_*: the sky placement of the centroid and visibility groups (vag_loglike_sky_batch / _vis_batch), not Model fields either
@@ -138,6 +138,18 @@ class CountsFitSpec(C.Structure):  # vag_counts_fit_spec
     _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(CountsObs))]
 
 
+INDEX_MAX_NODES = 8  # VAG_INDEX_MAX_NODES
+
+
+class IndexObs(C.Structure):  # vag_index_obs
+    _fields_ = [("n", C.c_int32), ("k", C.c_int32), ("nu", C.POINTER(C.c_double)), ("coef", C.POINTER(C.c_double)),
+                ("ext_slope", C.c_double)] + [(n, C.POINTER(C.c_double)) for n in ("t", "value", "err", "weight")]
+
+
+class IndexFitSpec(C.Structure):  # vag_index_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(IndexObs))]
+
+
 class FitSpec(C.Structure):
     _fields_ = [
         ("base", ModelParams), ("ndim", C.c_int32), ("slot", C.c_int32 * 16), ("is_log", C.c_int32 * 16),
@@ -202,7 +214,7 @@ EXPORTS = [
     "vag_sky_visibility_batch", "vag_debug_device_math", "vag_loglike_vis_batch", "vag_loglike_vis_batch_dev",
     "vag_sky_polarization_batch", "vag_sky_stokes_image_batch", "vag_loglike_pol_batch", "vag_loglike_pol_batch_dev",
     "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev", "vag_loglike_noise_batch", "vag_loglike_noise_batch_dev",
-    "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev",
+    "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev", "vag_loglike_index_batch", "vag_loglike_index_batch_dev",
 ]
 
 _lib = None
@@ -276,6 +288,12 @@ def load():
     lib.vag_loglike_counts_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec),
                                                  C.POINTER(PolFitSpec), C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec),
                                                  C.POINTER(CountsFitSpec), v, C.c_int, C.c_int, v]
+    lib.vag_loglike_index_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
+                                            C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec), C.POINTER(CountsFitSpec),
+                                            C.POINTER(IndexFitSpec), _dp, C.c_int, C.c_int, _dp]
+    lib.vag_loglike_index_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec),
+                                                C.POINTER(PolFitSpec), C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec),
+                                                C.POINTER(CountsFitSpec), C.POINTER(IndexFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -29,6 +29,7 @@
 #include "vag_debug_math.h"
 #include "vag_log_ndtr.h"
 #include "vag_poisson.h"
+#include "vag_index.h"
 
 using namespace vag;
 
@@ -414,6 +415,7 @@ struct vag_ctx {
     DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_noisefit;  // noise groups of the likelihood (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
     DevBuf d_countsfit;  // counts groups of the likelihood (vag_loglike_counts_batch): per group [t_sample | N | B | a | w | idx], see CountsLayout
+    DevBuf d_indexfit;  // spectral-index groups of the likelihood (vag_loglike_index_batch): per group [t | nu | s | sigma | w | c], see IndexLayout
     DevBuf d_limfit;  // upper-limit rows of the likelihood (vag_loglike_lim_batch): per block [limit | sigma | kind], see LimLayout
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -468,7 +470,7 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit;
+    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit, h_indexfit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
@@ -493,6 +495,9 @@ struct vag_ctx {
     uint64_t countsfit_hash = 0;  // (d_countsfit: the counts groups of vag_loglike_counts_batch, upload_counts_spec)
     size_t countsfit_doubles = 0;
     bool countsfit_hash_valid = false;
+    uint64_t indexfit_hash = 0;  // (d_indexfit: the spectral-index groups of vag_loglike_index_batch, upload_index_spec)
+    size_t indexfit_doubles = 0;
+    bool indexfit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -732,8 +737,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_limfit.release();
     c->h_noisefit.release();
     c->h_countsfit.release();
+    c->h_indexfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit, &c->d_indexfit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -4019,6 +4025,64 @@ vag_fit_back_counts_kernel(const double* __restrict__ flux /* [nb][ns] */, int n
     }
 }
 
+// The back of a spectral-index pass (vag_loglike_index_batch), one wavefront per walker like its siblings.  flux [nb][n K] holds the
+// walker's flux density at the group's points (t_i, nu_k), i outer; lane i strides the rows, reads its K consecutive values, forms
+// S_i = vag::log_slope - A_V ext_slope and adds w_i ((S_i - s_i) / sigma_i)^2 to the lane's sum; a row with w_i = 0 adds nothing.  A row
+// whose slope is undefined (some F <= 0 or not finite) makes the sum NaN, which the last pass turns into -inf and counts.  The lanes'
+// sums are closed by vag::wave_sum in the fixed order of the other back kernels, so the value depends on the walker's own row of flux
+// alone.  Validity, the first / last pass flags, the rejection counters and the evaluation-order hand-over are vag_fit_back_kernel's.
+__global__ void __launch_bounds__(64)
+vag_fit_back_index_kernel(const double* __restrict__ flux /* [nb][n K] */, int n, int K, const double* __restrict__ value,
+                          const double* __restrict__ err, const double* __restrict__ weight, const double* __restrict__ coef /* [K] */,
+                          double ext_slope, const double* __restrict__ a_v, const VagGridMeta* __restrict__ meta,
+                          const int* __restrict__ row_status, const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */,
+                          double* __restrict__ chi2, int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last,
+                          double* __restrict__ out, int* __restrict__ fitstat, const int* __restrict__ order /* evaluation slot -> walker, or null */,
+                          const float* __restrict__ cost, int nb, int* __restrict__ next_order /* or null */) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    if (next_order) {  // (as vag_fit_back_kernel)
+        const float mine = cost[m];
+        int rank = 0;
+        for (int i0 = 0; i0 < nb; i0 += 64) {
+            const int i = i0 + lane;
+            const float c = i < nb ? cost[i] : -1.0f;
+            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
+        }
+        if (lane == 0) next_order[rank] = order ? order[m] : m;
+    }
+    const double shift = ext_slope != 0.0 ? a_v[m] * ext_slope : 0.0;
+    const bool grid_ok = meta[m].status == 0;
+    double s = 0;
+    if (grid_ok) {
+        const double* f = flux + (size_t)m * n * K;
+        for (int i = lane; i < n; i += 64) {
+            const double w = weight[i];
+            if (w == 0.0) continue;
+            const double q = (vag::log_slope(f + (size_t)i * K, 1, coef, K) - shift - value[i]) / err[i];
+            s += w * (q * q);
+        }
+    }
+    s = vag::wave_sum(s);
+    bool bad_row = false;
+    if (grid_ok)
+        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
+    const bool any_bad = __any(bad_row);
+    if (lane == 0) {
+        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
+        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
+        const double acc = first ? s : chi2[m] + s;
+        valid[m] = ok;
+        chi2[m] = acc;
+        if (ic_bad) atomicAdd(fitstat + 1, 1);
+        if (last) {
+            const double lp = ln_prior[m];
+            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
+            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
+            if (!fin) atomicAdd(fitstat, 1);
+        }
+    }
+}
+
 // ---- centroid groups (vag_loglike_sky_batch): their data in one device buffer, uploaded like the fit spec when its hash changes.
 //      Layout in doubles, per group: [nu | t | east | north | err_east | err_north | weight] (1 + 6 n). ----
 static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
@@ -4756,10 +4820,86 @@ static int upload_counts_spec(vag_ctx* c, const vag_counts_fit_spec* cs, const s
     return VAG_OK;
 }
 
+// ---- spectral-index groups (vag_loglike_index_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
+//      Layout in doubles, per group: [t n K | nu n K | s n | sigma n | w n | c K]; the first two are the series points (t_i, nu_k), i
+//      outer, as prep_times takes them. ----
+struct IndexLayout {
+    std::vector<long> off;  // where group g starts in d_indexfit
+    int n_groups = 0;
+};
+
+// Validates the spectral-index groups and lays their blocks out in stage (host work only: no context is touched).
+static int index_scan(const vag_index_fit_spec* is, std::vector<double>& stage, IndexLayout& lay) {
+    if (is->n_groups < 0 || !is->groups) return set_err(VAG_E_INVALID, "index groups: n_groups must be >= 0 with a group list, got %d", is->n_groups);
+    lay.n_groups = is->n_groups;
+    lay.off.clear();
+    stage.clear();
+    for (int g = 0; g < is->n_groups; ++g) {
+        const vag_index_obs& o = is->groups[g];
+        if (o.k < 2 || o.k > VAG_INDEX_MAX_NODES)
+            return set_err(VAG_E_INVALID, "index group %d: k (frequencies) must be in 2..%d, got %d", g, VAG_INDEX_MAX_NODES, o.k);
+        if (o.n < 1) return set_err(VAG_E_INVALID, "index group %d has no rows", g);
+        if (o.n > (1 << 24)) return set_err(VAG_E_INVALID, "index group %d: more than %d rows", g, 1 << 24);
+        if (!o.nu || !o.coef || !o.t || !o.value || !o.err || !o.weight) return set_err(VAG_E_INVALID, "index group %d: null array", g);
+        for (int k = 0; k < o.k; ++k) {
+            if (!std::isfinite(o.nu[k]) || !(o.nu[k] > 0) || (k > 0 && !(o.nu[k] > o.nu[k - 1])))
+                return set_err(VAG_E_INVALID, "index group %d, frequency %d: frequencies must be finite, > 0 and strictly ascending", g, k);
+            if (!std::isfinite(o.coef[k])) return set_err(VAG_E_INVALID, "index group %d, coefficient %d is not finite", g, k);
+        }
+        if (!std::isfinite(o.ext_slope)) return set_err(VAG_E_INVALID, "index group %d: ext_slope is not finite", g);
+        for (int i = 0; i < o.n; ++i) {
+            if (!std::isfinite(o.t[i]) || !(o.t[i] > 0) || (i > 0 && o.t[i] < o.t[i - 1]))
+                return set_err(VAG_E_INVALID, "index group %d, row %d: times must be finite, > 0 and ascending", g, i);
+            if (!std::isfinite(o.value[i])) return set_err(VAG_E_INVALID, "index group %d, row %d: the index is not finite", g, i);
+            if (!std::isfinite(o.err[i]) || !(o.err[i] > 0))
+                return set_err(VAG_E_INVALID, "index group %d, row %d: the error must be finite and > 0", g, i);
+            if (!std::isfinite(o.weight[i]) || o.weight[i] < 0)
+                return set_err(VAG_E_INVALID, "index group %d, row %d: the weight must be finite and >= 0", g, i);
+        }
+        const size_t at = stage.size(), n = (size_t)o.n, K = (size_t)o.k;
+        lay.off.push_back((long)at);
+        stage.resize(at + 2 * n * K + 3 * n + K, 0.0);
+        double* dst = stage.data() + at;
+        for (size_t i = 0; i < n; ++i)
+            for (size_t k = 0; k < K; ++k) {
+                dst[i * K + k] = o.t[i];
+                dst[n * K + i * K + k] = o.nu[k];
+            }
+        dst += 2 * n * K;
+        for (const double* src : {o.value, o.err, o.weight}) {
+            std::memcpy(dst, src, sizeof(double) * n);
+            dst += n;
+        }
+        std::memcpy(dst, o.coef, sizeof(double) * K);
+    }
+    return VAG_OK;
+}
+
+static int upload_index_spec(vag_ctx* c, const vag_index_fit_spec* is, const std::vector<double>& stage) {
+    uint64_t h = 1469598103934665603ull;
+    for (int g = 0; g < is->n_groups; ++g) {  // (the shapes: two groups whose blocks hold the same bytes are still two layouts)
+        const int head[2] = {is->groups[g].n, is->groups[g].k};
+        h = fnv1a(h, head, sizeof head);
+    }
+    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
+    if (c->indexfit_hash_valid && c->indexfit_hash == h && c->indexfit_doubles == stage.size()) return VAG_OK;  // resident already
+    c->indexfit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_indexfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    if (c->d_indexfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    std::memcpy(c->h_indexfit.as<double>(), stage.data(), sizeof(double) * stage.size());
+    HIPCHK(hipMemcpyAsync(c->d_indexfit.p, c->h_indexfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
+    c->indexfit_hash = h;
+    c->indexfit_doubles = stage.size();
+    c->indexfit_hash_valid = true;
+    return VAG_OK;
+}
+
 static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec,
                         const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
                         const vag_pol_fit_spec* pol = nullptr, const LimLayout* lim = nullptr, const NoiseLayout* noise = nullptr,
-                        const vag_counts_fit_spec* counts = nullptr, const CountsLayout* clay = nullptr) {
+                        const vag_counts_fit_spec* counts = nullptr, const CountsLayout* clay = nullptr,
+                        const vag_index_fit_spec* index = nullptr, const IndexLayout* ilay = nullptr) {
     int rc = VAG_OK;
     const int n = spec->n_data;
     hipStream_t st = c->stream;
@@ -4795,7 +4935,8 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
     };
     const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = vis ? vis->n_groups : 0, n_pol_groups = pol ? pol->n_groups : 0;
     const int n_counts_groups = counts ? counts->n_groups : 0;
-    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups + n_counts_groups;
+    const int n_index_groups = index ? index->n_groups : 0;
+    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups + n_counts_groups + n_index_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // the SSC tables of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
     // lim_off: where the pass's block of limit rows starts in d_limfit, or -1 (no limit row: the kernel as it was)
@@ -4991,6 +5132,38 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
             n_inv = std::max(n_inv, c->plan.n_models_invalid);
         }
     }
+    for (int g = 0; g < n_index_groups && rc == VAG_OK; ++g) {  // spectral-index groups: the n K points as one series request each, then the slope term
+        const vag_index_obs& o = index->groups[g];
+        const double* di = c->d_indexfit.as<double>() + ilay->off[g];  // [t n K | nu n K | s | sigma | w | c]
+        const size_t nr = (size_t)o.n, np = nr * (size_t)o.k;
+        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(np, (size_t)std::max(n, 1)))) return VAG_E_HIP;
+        rc = prep_times(c, di, (int)np, di + np, (int)np);
+        c->order_next = d_order != nullptr;
+        c->last_order = d_order;
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
+        if (rc == VAG_OK) {
+            int shared = 0;  // K <= 8 distinct frequencies: the shared-node path of a short series
+            if (np <= (size_t)FITROWS_MAX_POINTS) {
+                double nu_pts[FITROWS_MAX_POINTS];
+                for (size_t i = 0; i < np; ++i) nu_pts[i] = o.nu[i % (size_t)o.k];
+                shared = upload_series_bands(c, nu_pts, (int)np);
+            }
+            rc = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), shared);
+        }
+        if (rc == VAG_OK) {
+            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
+            hipLaunchKernelGGL(vag_fit_back_index_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, o.k,
+                               di + 2 * np, di + 2 * np + nr, di + 2 * np + 2 * nr, di + 2 * np + 3 * nr, o.ext_slope, d_av,
+                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
+                               (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
+                               pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order,
+                               c->d_cost_f.as<float>(), nb, next_order());
+            HIPCHK(hipGetLastError());
+            ++pass;
+            n_cap = std::max(n_cap, c->plan.n_models_capacity);
+            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+        }
+    }
     c->ic_soft_fail = false;
     c->plan.n_models_capacity = n_cap;
     c->plan.n_models_invalid = n_inv;
@@ -5131,11 +5304,12 @@ int vag_loglike_lim_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
 
 // The body the chained entry points share once their specs are scanned: the context checks, the uploads of every spec block that is
 // present, and the call (repeated once on the waiting path when a planned-ahead call fails).  llay / nlay are used when their `any` is
-// set; counts with clay when counts is not null.
+// set; counts with clay when counts is not null, index with ilay when index is not null.
 static int loglike_chained_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                                const vag_pol_fit_spec* pol, const std::vector<double>& lstage, const LimLayout& llay,
                                const std::vector<double>& nstage, const NoiseLayout& nlay, const vag_counts_fit_spec* counts,
-                               const std::vector<double>& cstage, const CountsLayout& clay, const double* d_theta, int nb, int ndim,
+                               const std::vector<double>& cstage, const CountsLayout& clay, const vag_index_fit_spec* index,
+                               const std::vector<double>& istage, const IndexLayout& ilay, const double* d_theta, int nb, int ndim,
                                double* d_out) {
     ApiLock api_lock(c);
     HandoffScope handoff(c);
@@ -5147,7 +5321,7 @@ static int loglike_chained_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_s
     const bool placed = (sky && sky->n_groups > 0) || vis;
     if (!pol && !placed) sky = nullptr;  // (as vag_loglike_sky_batch_dev: nothing reads the placement)
     HIPCHK(hipSetDevice(c->device));
-    int rc = upload_fit_spec(c, spec, ndim, placed, pol != nullptr, nlay.any ? nlay.n_groups : 0, counts != nullptr);
+    int rc = upload_fit_spec(c, spec, ndim, placed, pol != nullptr, nlay.any ? nlay.n_groups : 0, counts != nullptr || index != nullptr);
     if (rc) return rc;
     if (sky) {
         rc = upload_sky_spec(c, sky);
@@ -5173,11 +5347,16 @@ static int loglike_chained_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_s
         rc = upload_counts_spec(c, counts, cstage, clay);
         if (rc) return rc;
     }
+    if (index) {
+        rc = upload_index_spec(c, index, istage);
+        if (rc) return rc;
+    }
     const LimLayout* lp = llay.any ? &llay : nullptr;
     const NoiseLayout* np = nlay.any ? &nlay : nullptr;
     const CountsLayout* cp = counts ? &clay : nullptr;
-    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, lp, np, counts, cp);
-    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, lp, np, counts, cp);
+    const IndexLayout* ip = index ? &ilay : nullptr;
+    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, lp, np, counts, cp, index, ip);
+    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, lp, np, counts, cp, index, ip);
     return rc;
 }
 
@@ -5196,7 +5375,8 @@ int vag_loglike_noise_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_
         const int rc = lim_scan(spec, pol, lim, lstage, llay);
         if (rc) return rc;
     }
-    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, nullptr, {}, CountsLayout{}, d_theta, nb, ndim, d_out);
+    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, nullptr, {}, CountsLayout{}, nullptr, {}, IndexLayout{}, d_theta, nb,
+                               ndim, d_out);
 }
 
 int vag_loglike_counts_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
@@ -5218,7 +5398,38 @@ int vag_loglike_counts_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag
         rc = lim_scan(spec, pol, lim, lstage, llay);
         if (rc) return rc;
     }
-    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, counts, cstage, clay, d_theta, nb, ndim, d_out);
+    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, counts, cstage, clay, nullptr, {}, IndexLayout{}, d_theta,
+                               nb, ndim, d_out);
+}
+
+int vag_loglike_index_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                                const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                                const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* d_theta, int nb,
+                                int ndim, double* d_out) {
+    if (!index || index->n_groups == 0)  // exactly that call
+        return vag_loglike_counts_batch_dev(c, spec, sky, vis, pol, lim, noise, counts, d_theta, nb, ndim, d_out);
+    std::vector<double> istage, cstage, nstage, lstage;
+    IndexLayout ilay;
+    CountsLayout clay;
+    NoiseLayout nlay;
+    LimLayout llay;
+    int rc = index_scan(index, istage, ilay);
+    if (rc) return rc;
+    if (counts && counts->n_groups == 0) counts = nullptr;
+    if (counts) {
+        rc = counts_scan(counts, cstage, clay);
+        if (rc) return rc;
+    }
+    if (noise && spec) {
+        rc = noise_scan(spec, noise, nstage, nlay);
+        if (rc) return rc;
+    }
+    if (lim && spec) {
+        rc = lim_scan(spec, pol, lim, lstage, llay);
+        if (rc) return rc;
+    }
+    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, counts, cstage, clay, index, istage, ilay, d_theta, nb,
+                               ndim, d_out);
 }
 
 __global__ void vag_model_cost_kernel(const VagGridMeta* __restrict__ meta, int nb, double* __restrict__ cost,
@@ -5650,6 +5861,38 @@ int vag_loglike_counts_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky
     }
     return loglike_chained_host(c, spec, theta, nb, ndim, out, [&](double* d_theta, double* d_out) {
         return vag_loglike_counts_batch_dev(c, spec, sky, vis, pol, lim, noise, counts, d_theta, nb, ndim, d_out);
+    });
+}
+
+int vag_loglike_index_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                            const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                            const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* theta, int nb, int ndim,
+                            double* out) {
+    if (!index || index->n_groups == 0)  // exactly that call
+        return vag_loglike_counts_batch(c, spec, sky, vis, pol, lim, noise, counts, theta, nb, ndim, out);
+    {  // (checked again, and laid out, by the _dev form)
+        std::vector<double> stage;
+        IndexLayout ilay;
+        int rc = index_scan(index, stage, ilay);
+        if (rc) return rc;
+        if (counts && counts->n_groups > 0) {
+            CountsLayout clay;
+            rc = counts_scan(counts, stage, clay);
+            if (rc) return rc;
+        }
+        if (noise && spec) {
+            NoiseLayout lay;
+            rc = noise_scan(spec, noise, stage, lay);
+            if (rc) return rc;
+        }
+        if (lim && spec) {
+            LimLayout lay;
+            rc = lim_scan(spec, pol, lim, stage, lay);
+            if (rc) return rc;
+        }
+    }
+    return loglike_chained_host(c, spec, theta, nb, ndim, out, [&](double* d_theta, double* d_out) {
+        return vag_loglike_index_batch_dev(c, spec, sky, vis, pol, lim, noise, counts, index, d_theta, nb, ndim, d_out);
     });
 }
 

@@ -3,6 +3,7 @@
 // inline.  Nothing here is on a product call path.  tests/test_device_math.py holds each routine to a high-precision reference.
 #pragma once
 #include "vag_ic_kernels.h"
+#include "vag_index.h"
 #include "vag_log_ndtr.h"
 #include "vag_poisson.h"
 #include "vag_rs.h"
@@ -22,6 +23,7 @@ inline int math_n_in(int fn) {
         case VAG_MATH_IC_CELL: return MATH_IC_IN;
         case VAG_MATH_LDS_ADD: return 2;  // slot (an integer in [0, 64)), value
         case VAG_MATH_POISSON_DEVIANCE: return 2;  // N, mu
+        case VAG_MATH_LOG_SLOPE: return 2 * INDEX_MAX_NODES + 1;  // 8 fluxes, 8 coefficients, K
         default: return (fn >= 0 && fn < VAG_MATH_COUNT) ? 1 : 0;
     }
 }
@@ -110,6 +112,13 @@ __global__ void __launch_bounds__(64) vag_math_probe_kernel(int fn, int n, const
         case VAG_MATH_POISSON_DEVIANCE:
             if (ok) out[i] = poisson_deviance(in[2 * (size_t)i], in[2 * (size_t)i + 1]);
             return;
+        case VAG_MATH_LOG_SLOPE: {
+            if (!ok) return;
+            const double* a = in + (size_t)i * (2 * INDEX_MAX_NODES + 1);
+            const int K = (int)a[2 * INDEX_MAX_NODES];
+            out[i] = (K >= 2 && K <= INDEX_MAX_NODES) ? log_slope(a, 1, a + INDEX_MAX_NODES, K) : NAN;
+            return;
+        }
         default: break;
     }
     if (!ok) return;

@@ -132,6 +132,47 @@ def host_ln_prior(samples, lower, upper, prior_specs):
     return lp
 
 
+INDEX_CONVENTIONS = ("slope", "beta", "photon")
+
+
+def index_coefficients(nu):
+    """The least-squares coefficients of a spectral-index group: c_k = (x_k - mean x) / sum_j (x_j - mean x)^2 with x = ln nu, so
+    that sum_k c_k ln F_k is the least-squares slope d ln F / d ln nu over the nodes (sum c = 0 and sum c x = 1 to rounding).  Two
+    nodes: c = (-1, 1) / ln(nu_1 / nu_0)."""
+    nu = np.asarray(nu, dtype=np.float64)
+    x = np.log(nu / nu[0])  # (the shift by ln nu_0 changes no c_k; it keeps the rounding of ln nu ~ 40 out of the differences)
+    if x.size == 2:
+        return np.array([-1.0 / x[1], 1.0 / x[1]])
+    dx = x - x.mean()
+    return dx / np.sum(dx * dx)
+
+
+def index_slope(F, coef):
+    """S = sum_{k >= 1} c_k ln(F_k / F_0) along the last axis of F, summed in k order: the statement of the device's
+    vag::log_slope (the pivot form: every log is taken of a ratio to F_0; c_0 is not read).  NaN where some F_k is <= 0 or not
+    finite."""
+    F = np.asarray(F, dtype=np.float64)
+    coef = np.asarray(coef, dtype=np.float64)
+    ok = np.all(np.isfinite(F) & (F > 0), axis=-1)
+    s = np.zeros(F.shape[:-1])
+    with np.errstate(all="ignore"):
+        for k in range(1, F.shape[-1]):
+            s = s + coef[k] * np.log(F[..., k] / F[..., 0])
+    return np.where(ok, s, np.nan)
+
+
+def index_from_slope(slope, convention):
+    """A slope s (F_nu ~ nu^s) in the convention of the data: "slope" s, "beta" -s (F_nu ~ nu^-beta), "photon" 1 - s
+    (N_E ~ E^-Gamma).  The map is its own inverse."""
+    if convention == "slope":
+        return +np.asarray(slope, dtype=np.float64)
+    if convention == "beta":
+        return -np.asarray(slope, dtype=np.float64)
+    if convention == "photon":
+        return 1.0 - np.asarray(slope, dtype=np.float64)
+    raise ValueError(f"unknown spectral-index convention {convention!r}: one of {INDEX_CONVENTIONS}")
+
+
 class Fitter:
     """Fitter(*, z=0.0, lumi_dist=1e26, jet=..., medium=..., resolution=..., rtol=...): keyword-only with the reference's
     defaults (fitter.py:96-135)."""
@@ -175,6 +216,7 @@ class Fitter:
         self._vis_obs = []  # VLBI visibility groups (add_visibilities): one vag_visibility_obs each
         self._pol_obs = []  # polarization groups (add_polarization): one vag_polarization_obs each
         self._counts_obs = []  # photon-count groups (add_counts): one vag_counts_obs each
+        self._index_obs = []  # spectral-index groups (add_spectral_index): one vag_index_obs each
         self._ext_kernel = None
         self._ext_kernels = {}  # z -> 0.4 ln10 k(lambda_rest) over the consolidated point data
         self._ext_z = float(z)
@@ -406,6 +448,60 @@ class Fitter:
         """Some data are photon counts (add_counts)."""
         return bool(self._counts_obs)
 
+    def add_spectral_index(self, band, t, index, err, num_points=2, convention="slope", weights=None):
+        """Measured spectral indices over band = (nu_min, nu_max) [Hz] at times t [s]: a photon index per X-ray epoch, an optical
+        slope per night.  The model's index is the least-squares slope d ln F_nu / d ln nu of the flux density over num_points
+        (2..8) nodes, logspace(nu_min, nu_max) with the last node exactly nu_max; two nodes give ln(F_1 / F_0) / ln(nu_1 / nu_0).
+        convention: "slope" (F_nu ~ nu^index), "beta" (F_nu ~ nu^-index) or "photon" (N_E ~ E^-index, slope = 1 - index); err is
+        the error of the index in any of them.  A row adds w ((S - s) / err)^2 to chi^2; with Fitter(extinction=...) the model
+        slope carries the law's reddening over the nodes times the walker's A_V.  A walker whose flux is not positive at some node
+        of a row with w > 0 scores -inf.  Weights are used as given; rows are sorted by t.  Nothing is recorded when the call
+        raises."""
+        who = "add_spectral_index"
+        try:
+            nu_min, nu_max = band
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: band must be a (nu_min, nu_max) tuple in Hz, got {band!r}") from None
+        if not (np.isfinite(nu_min) and np.isfinite(nu_max) and 0 < nu_min < nu_max):
+            raise ValueError(f"{who}: band must satisfy 0 < nu_min < nu_max with both finite; got nu_min={nu_min}, nu_max={nu_max}")
+        if int(num_points) != num_points or not (2 <= num_points <= _lib.INDEX_MAX_NODES):
+            raise ValueError(f"{who}: num_points must be an integer in 2..{_lib.INDEX_MAX_NODES}, got {num_points!r}")
+        if convention not in INDEX_CONVENTIONS:
+            raise ValueError(f"{who}: unknown convention {convention!r}: one of {INDEX_CONVENTIONS}")
+        t, idx, err = (np.asarray(a, dtype=np.float64) for a in (t, index, err))
+        if t.ndim != 1 or t.size == 0:
+            raise ValueError(f"{who}: t must be a non-empty 1-D array")
+        if not (t.shape == idx.shape == err.shape):
+            raise ValueError(f"{who}: t, index and err must have the same shape; got {t.shape}, {idx.shape}, {err.shape}")
+        if not np.isfinite(t).all() or (t <= 0).any():
+            raise ValueError(f"{who}: t must be finite and > 0 at every row")
+        if not np.isfinite(idx).all():
+            raise ValueError(f"{who}: index must be finite at every row")
+        if not np.isfinite(err).all() or (err <= 0).any():
+            raise ValueError(f"{who}: err must be finite and > 0 at every row")
+        if weights is None:
+            w = np.ones_like(t)
+        else:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape != t.shape or not np.isfinite(w).all() or (w < 0).any():
+                raise ValueError(f"{who}: weights must have the shape of t and be finite and >= 0")
+        nu = np.logspace(np.log10(float(nu_min)), np.log10(float(nu_max)), int(num_points))
+        nu[-1] = float(nu_max)
+        if not (np.isfinite(nu).all() and (np.diff(nu) > 0).all()):
+            raise ValueError(f"{who}: the band is too narrow for {num_points} distinct nodes; got nu_min={nu_min}, nu_max={nu_max}")
+        coef = index_coefficients(nu)
+        if not np.isfinite(coef).all():
+            raise ValueError(f"{who}: the band is too narrow for finite slope coefficients; got nu_min={nu_min}, nu_max={nu_max}")
+        order = np.argsort(t, kind="stable")
+        c = np.ascontiguousarray
+        self._index_obs.append(dict(nu=c(nu), coef=c(coef), convention=convention, t=c(t[order]),
+                                    value=c(index_from_slope(idx[order], convention)), err=c(err[order]), weights=c(w[order])))
+
+    @property
+    def has_spectral_indices(self):
+        """Some data are spectral indices (add_spectral_index)."""
+        return bool(self._index_obs)
+
     def add_centroid(self, nu, t, east, north, err_east, err_north, weights=None):
         """VLBI centroid positions at one frequency nu [Hz]: offsets east / north of a reference position and their errors [rad]
         (units.mas converts) at ascending times t [s].  The group is its own request: the model centroid at (t_i, nu) is
@@ -571,9 +667,9 @@ class Fitter:
         if self._all_t is not None:
             return
         if not self._point_t:
-            if not self._band_obs and not self._centroid_obs and not self._vis_obs and not self._pol_obs and not self._counts_obs:
-                raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities, add_polarization or "
-                                 "add_counts first")
+            if not (self._band_obs or self._centroid_obs or self._vis_obs or self._pol_obs or self._counts_obs or self._index_obs):
+                raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities, add_polarization, "
+                                 "add_counts or add_spectral_index first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
             self._all_lim = self._all_grp = None
             return
@@ -708,6 +804,7 @@ class Fitter:
         if self.extinction is not None and any(pd.name == "z" for pd in free):
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
+        spec._index = self._index_spec(z_eff) if self._index_obs else None
         if self.extinction is not None and self._all_t.size and z_eff != self._ext_z:
             # a fixed 'z' ParamDef overrides Fitter.z in the model: the rest-frame wavelengths of the law must follow it.  One
             # kernel per z, all kept for the Fitter's lifetime: earlier specs (a device_evaluator's closure) still point at theirs
@@ -781,6 +878,33 @@ class Fitter:
         cs.n_groups, cs.groups = len(self._counts_obs), groups
         cs._keep_alive = (groups, list(self._counts_obs))
         return cs
+
+    def _index_ext_slope(self, gd, z):
+        """ext_slope of a spectral-index group at redshift z: sum_{k >= 1} c_k (kappa_k - kappa_0), kappa = 0.4 ln10 k(lambda_rest),
+        the kernel of the point rows; 0 without an extinction law."""
+        if self.extinction is None:
+            return 0.0
+        lam_rest_cm = (2.99792458e10 / gd["nu"]) / (1.0 + z)
+        kappa = 0.4 * np.log(10.0) * np.asarray(self._k_lambda(lam_rest_cm), dtype=np.float64)
+        s = 0.0
+        for k in range(1, kappa.size):
+            s = s + gd["coef"][k] * (kappa[k] - kappa[0])
+        return float(s)
+
+    def _index_spec(self, z):
+        """vag_index_fit_spec of the spectral-index groups (the law's reddening at redshift z); it keeps the arrays it points at
+        alive."""
+        ispec = _lib.IndexFitSpec()
+        groups = (_lib.IndexObs * len(self._index_obs))()
+        for g, gd in enumerate(self._index_obs):
+            o = groups[g]
+            o.n, o.k, o.ext_slope = gd["t"].size, gd["nu"].size, self._index_ext_slope(gd, z)
+            for name in ("nu", "coef", "t", "value", "err"):
+                setattr(o, name, gd[name].ctypes.data_as(_dp))
+            o.weight = gd["weights"].ctypes.data_as(_dp)
+        ispec.n_groups, ispec.groups = len(self._index_obs), groups
+        ispec._keep_alive = (groups, list(self._index_obs))
+        return ispec
 
     def _vis_spec(self):
         """vag_vis_fit_spec of the visibility groups; it keeps the arrays it points at alive."""
@@ -950,6 +1074,25 @@ class Fitter:
             out.append(cd["background"] + cd["scale"] * total)
         return out
 
+    def spectral_indices(self, best_params, param_defs, resolution=None):
+        """The model index of every row of every spectral-index group at a point of sampler space, in the group's own convention
+        and with the A_V term: a list of float64 arrays, one per group, rows in ascending t.  Each group is one
+        vag_flux_density_batch request at its n K points (t_i, nu_k), i outer, and index_slope on the result -- the likelihood's
+        own request and arithmetic (its flux may differ from this call's in the last bits)."""
+        p, a_v = self._params_at(best_params, param_defs, resolution)
+        h, lock = get_context(self.device)
+        out = []
+        for gd in self._index_obs:
+            n, K = gd["t"].size, gd["nu"].size
+            ts, nus = np.ascontiguousarray(np.repeat(gd["t"], K)), np.ascontiguousarray(np.tile(gd["nu"], n))
+            flux = np.empty(n * K)
+            with lock:
+                _lib.check(_lib.load().vag_flux_density_batch(h, C.byref(p), 1, ts.ctypes.data_as(_dp), nus.ctypes.data_as(_dp), n * K,
+                                                              flux.ctypes.data_as(_dp)))
+            slope = index_slope(flux.reshape(n, K), gd["coef"]) - a_v * self._index_ext_slope(gd, float(p.z))
+            out.append(index_from_slope(slope, gd["convention"]))
+        return out
+
     def visibilities(self, best_params, param_defs, resolution=None):
         """The model visibilities at the data of every visibility group at a point of sampler space: a list of complex128 arrays,
         one per group, in the order and layout the data were added.  Each group is one Model.sky_visibilities request at the
@@ -1098,7 +1241,12 @@ class Fitter:
 
             def run():
                 ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
-                if keep[0]._counts is not None:
+                if keep[0]._index is not None:
+                    _lib.check(lib.vag_loglike_index_batch_dev(
+                        h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
+                        ref(keep[0]._noise), ref(keep[0]._counts), C.byref(keep[0]._index), theta.data_ptr(), k, keep[0].ndim,
+                        values.data_ptr()))
+                elif keep[0]._counts is not None:
                     _lib.check(lib.vag_loglike_counts_batch_dev(
                         h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
                         ref(keep[0]._noise), C.byref(keep[0]._counts), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
@@ -1133,6 +1281,7 @@ class Fitter:
         eval_dev.has_limits = spec._lim is not None
         eval_dev.has_noise_groups = spec._noise is not None
         eval_dev.has_counts = spec._counts is not None
+        eval_dev.has_spectral_indices = spec._index is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -1143,6 +1292,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._index is not None:
+                    from .dist import _NO_INDEX
+                    raise NotImplementedError(_NO_INDEX)
                 if keep[0]._counts is not None:
                     from .dist import _NO_COUNTS
                     raise NotImplementedError(_NO_COUNTS)
@@ -1187,7 +1339,12 @@ class Fitter:
         plan = _lib.Plan()
         with lock:
             ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
-            if spec._counts is not None:
+            if spec._index is not None:
+                _lib.check(_lib.load().vag_loglike_index_batch(
+                    h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
+                    ref(spec._counts), C.byref(spec._index), samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
+                    out.ctypes.data_as(_dp)))
+            elif spec._counts is not None:
                 _lib.check(_lib.load().vag_loglike_counts_batch(
                     h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
                     C.byref(spec._counts), samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
