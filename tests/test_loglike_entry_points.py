@@ -1,0 +1,200 @@
+"""The sixteen likelihood entry points (vag_loglike_{,sky_,vis_,pol_,lim_,noise_,counts_,index_}batch and their _dev forms) are one
+request path: a request whose optional blocks are absent or empty is the narrower entry point's request, bit for bit; the host form
+is the device-pointer form; a call does not depend on the evaluation order; an invalid walker scores -inf through the back kernels'
+shared closing block and leaves the others alone.
+
+Two fixtures, both on C4 (configs.C4_TRUTH): (a) the 60 point rows alone; (b) one fitter with every kind of data the likelihood
+takes.  Two batch sizes: 3 walkers (evaluated in the identity order) and 64, the smallest batch evaluated in cost order.
+profiles/loglike_bits.py writes ln L of the same fixtures to a file, to compare two builds."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import _abi
+import configs
+import test_counts as tc
+import test_index as ti
+import test_limits as tl
+import test_sky_polfit as tp
+import test_sky_visfit as tv
+import vegasafterglow_amd as va
+from vegasafterglow_amd import _lib, fitting
+
+pytestmark = pytest.mark.gpu
+dp = C.POINTER(C.c_double)
+ip = C.POINTER(C.c_int32)
+P = fitting.ParamDef
+BATCHES = (3, 64)
+DAY = 86400.0
+
+
+def fixture_a():
+    """The C4 point data (60 rows): the device's own truth with 5 % noise, 10 % errors.  Returns (fitter, parameter list)."""
+    t, nu = configs.c4_mock_data()
+    truth = tl.device_series([_abi.make_params(**configs.C4_TRUTH)], t, nu)[0]
+    obs = truth * (1 + 0.05 * np.random.default_rng(42).standard_normal(t.size))
+    f = tc.new_fitter()
+    f.add_flux_density(nu, t, obs, 0.1 * truth)
+    return f, tl.defs()
+
+
+def fixture_b():
+    """One fitter with a point block (8 rows at 3 GHz, plus 4 rows at 5 GHz in the noise group "a" with a calibration term, one of
+    them a limit row), a band group with a limit row, a centroid group, a visibility group, a degree-polarization group with a limit
+    epoch, a counts group and a spectral-index group: 2 to 4 epochs each, built by the helpers of the tests of each kind.  Free:
+    theta_c, theta_v, E_iso, pa, east0, pol_b, sys_a.  Returns (fitter, parameter list)."""
+    f = tv._c4_fitter(with_centroid=True)  # 8 point rows, 3 centroid epochs
+    truth = tv._c4_truth()
+    rng = np.random.default_rng(7)
+    t4 = np.array([20.0, 60.0, 150.0, 260.0]) * DAY
+    f4 = truth.flux_density_grid(t4, 5e9).total[0]
+    lim4 = np.array([False, True, False, False])
+    f.add_flux_density(5e9, t4, np.where(lim4, 1.3 * f4, f4 * (1 + 0.05 * rng.standard_normal(4))), 0.1 * f4, upper_limit=lim4,
+                       noise="a", calibration=0.05)
+    bt = tc.EPOCHS[2::6]  # 3 epochs
+    bflux = tc.device_flux([_abi.make_params(**configs.C4_TRUTH)], bt, tl.BAND, 7)[0]
+    blim = np.array([False, False, True])
+    f.add_flux(tl.BAND, bt, np.where(blim, 1.2 * bflux, bflux * (1 + 0.05 * rng.standard_normal(3))), 0.1 * bflux, num_points=7,
+               upper_limit=blim)
+    tv.add_group(f, tv.make_group(truth, tv.VIS_T, tv.VIS_NU, (4, 3, 5), tv.PA_TRUE, tv.EAST0_TRUE), n_az=64)
+    pol = tp.make_group(truth)  # 4 epochs
+    degree = np.hypot(pol["q"], pol["u"])
+    plim = np.array([False, True, False, False])
+    f.add_polarization(pol["nu"], pol["t"], np.where(plim, degree + 0.02, degree), err_q=pol["err"], kind="degree",
+                       weights=[1.0, 0.5, 2.0, 1.5], upper_limit=plim)
+    f.add_counts(**tc.make_group(tc.EPOCHS[3::6], np.full(3, 5e4), 1, seed=11))
+    f.add_spectral_index(**ti.make_group(ti.X_BAND, tc.EPOCHS[1::6], 2, "photon", seed=31))
+    d = tv.FLUX_DEFS + tv.SKY_DEFS + [tp.POL_DEFS[1], P("sys_a", 0.0, 0.2)] + tv._c4_fixed(skip=("theta_c", "theta_v", "E_iso"))
+    return f, d
+
+
+def walkers_a(nb):
+    return np.ascontiguousarray(tv._walkers(nb, seed=12)[0])
+
+
+def walkers_b(nb):
+    th, sky = tv._walkers(nb, seed=12)
+    rng = np.random.default_rng(21)
+    return np.ascontiguousarray(np.column_stack([th, sky, rng.uniform(0.2, 0.8, nb), rng.uniform(0.0, 0.2, nb)]))
+
+
+@pytest.fixture(scope="module")
+def fit_a():
+    return fixture_a()
+
+
+@pytest.fixture(scope="module")
+def fit_b():
+    return fixture_b()
+
+
+ENTRY_POINTS = ("", "sky_", "vis_", "pol_", "lim_", "noise_", "counts_", "index_")  # entry point k takes the first k optional specs
+
+
+def call(name, spec, optional, samples, dev=False):
+    """One entry point by name on the shared context: `optional` are its spec arguments after the fit spec (ctypes structs or None).
+    dev: the device-pointer form, its arguments torch tensors on the GPU.  Returns ln L as a numpy array."""
+    lib = _lib.load()
+    h, lock = va.get_context(0)
+    ref = [C.byref(x) if x is not None else None for x in optional]
+    nb = samples.shape[0]
+    if not dev:
+        out = np.empty(nb)
+        with lock:
+            _lib.check(getattr(lib, name)(h, C.byref(spec), *ref, samples.ctypes.data_as(dp), nb, spec.ndim, out.ctypes.data_as(dp)))
+        return out
+    import torch
+    theta = torch.from_numpy(samples).to("cuda:0")
+    out = torch.empty((nb,), dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    with lock:
+        _lib.check(getattr(lib, name + "_dev")(h, C.byref(spec), *ref, theta.data_ptr(), nb, spec.ndim, out.data_ptr()))
+        _lib.check(lib.vag_ctx_synchronize(h))
+    return out.cpu().numpy()
+
+
+def all_specs(spec):
+    return [spec._sky, spec._vis, spec._pol, spec._lim, spec._noise, spec._counts, spec._index]
+
+
+@pytest.mark.parametrize("nb", BATCHES)
+def test_point_data_through_all_sixteen_entry_points(fit_a, nb):
+    """Fixture (a) through every entry point, host and device-pointer form: with the optional specs NULL, and with them present
+    and empty (n_groups = 0; the limit and noise specs cover every row and flag none).  The bits of vag_loglike_batch every time."""
+    f, d = fit_a
+    spec, _, _ = f.build_spec(d)
+    assert all(s is None for s in all_specs(spec)) and spec.n_data == 60 and spec.n_bands == 0
+    th = walkers_a(nb)
+    base = call("vag_loglike_batch", spec, [], th)
+    assert np.all(np.isfinite(base))
+    kind = np.zeros(60, dtype=np.int32)  # all detections; limit / sigma stay NULL: they are not read
+    lim = _lib.LimitFitSpec()
+    lim.point.kind = kind.ctypes.data_as(ip)
+    group = np.full(60, -1, dtype=np.int32)  # no row in a group
+    noise = _lib.NoiseFitSpec()
+    noise.point_group = group.ctypes.data_as(ip)
+    empty = [_lib.SkyFitSpec(), _lib.VisFitSpec(), _lib.PolFitSpec(), lim, noise, _lib.CountsFitSpec(), _lib.IndexFitSpec()]
+    for k, name in enumerate(ENTRY_POINTS):
+        for optional in ([None] * k, empty[:k]):
+            for dev in (False, True):
+                got = call(f"vag_loglike_{name}batch", spec, optional, th, dev=dev)
+                assert np.array_equal(got, base), (name, dev, optional[:1])
+
+
+@pytest.mark.parametrize("nb", BATCHES)
+def test_every_kind_of_data_in_one_fit(fit_b, nb):
+    """Fixture (b): the host form equals the device-pointer form, a repeat call (at 64 walkers: in the evaluation order the first
+    call left) and a call under VAG_NO_ORDER are equal, and Fitter.loglike_batch is vag_loglike_index_batch -- all to the bits."""
+    f, d = fit_b
+    spec, _, _ = f.build_spec(d)
+    assert all(s is not None for s in all_specs(spec))
+    assert (spec.n_data, spec.n_bands, spec._sky.n_groups, spec._vis.n_groups, spec._pol.n_groups) == (12, 1, 1, 1, 1)
+    assert (spec._counts.n_groups, spec._index.n_groups, spec._noise.n_groups) == (1, 1, 1)
+    th = walkers_b(nb)
+    a = call("vag_loglike_index_batch", spec, all_specs(spec), th)
+    assert np.all(np.isfinite(a))
+    assert np.array_equal(call("vag_loglike_index_batch", spec, all_specs(spec), th, dev=True), a)
+    assert np.array_equal(call("vag_loglike_index_batch", spec, all_specs(spec), th), a)
+    assert np.array_equal(tv._with_hook("VAG_NO_ORDER", "1", lambda: call("vag_loglike_index_batch", spec, all_specs(spec), th)), a)
+    assert np.array_equal(f.loglike_batch(th, d), a)
+    assert f.last_plan.n_walkers_rejected == 0
+
+
+@pytest.mark.parametrize("nb", BATCHES)
+def test_an_out_of_range_walker_scores_minus_infinity(fit_b, nb):
+    """theta_c < 0 in one walker of fixture (b): the walker is -inf, the others keep their bits, the plan counts one rejection.
+
+    Both calls run with the (theta, phi) pairs per flux workgroup pinned (the VAG_PAIRS_PER_BLOCK hook, at 4: the floor of the
+    engine's own choice).  A band request takes that number from the batch's total work (choose_pairs_per_block), the rejected
+    walker's lattice leaves the total, and the partial sums of the other walkers' band fluxes are then cut elsewhere -- the batch
+    dependence of a band group's last bits that loglike_body describes where it pins the number for a counts pass.  It is the flux
+    request's, not the closing block's: unpinned, one walker of the 64 (walker 16) moves by 1 ulp of ln L, in this build and in
+    the build before the back kernels shared their closing block alike; at 3 walkers none moves."""
+    f, d = fit_b
+    th = walkers_b(nb)
+    bad = th.copy()
+    bad[1, 0] = -0.05
+
+    def both():
+        base = f.loglike_batch(th, d)
+        return base, f.loglike_batch(bad, d), f.last_plan.n_walkers_rejected
+
+    base, out, rejected = tv._with_hook("VAG_PAIRS_PER_BLOCK", "4", both)
+    assert np.all(np.isfinite(base))
+    assert out[1] == -np.inf and np.array_equal(np.delete(out, 1), np.delete(base, 1))
+    assert rejected == 1
+
+
+@pytest.mark.parametrize("nb", BATCHES)
+def test_an_out_of_range_walker_of_the_point_data(fit_a, nb):
+    """The same on fixture (a), nothing pinned: a series request does not take its partial sums from the batch."""
+    f, d = fit_a
+    th = walkers_a(nb)
+    base = f.loglike_batch(th, d)
+    assert np.all(np.isfinite(base))
+    bad = th.copy()
+    bad[1, 0] = -0.05
+    out = f.loglike_batch(bad, d)
+    assert out[1] == -np.inf and np.array_equal(np.delete(out, 1), np.delete(base, 1))
+    assert f.last_plan.n_walkers_rejected == 1

@@ -9,7 +9,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -30,6 +29,7 @@
 #include "vag_log_ndtr.h"
 #include "vag_poisson.h"
 #include "vag_index.h"
+#include "vag_fit_kernels.h"
 
 using namespace vag;
 
@@ -3662,427 +3662,6 @@ static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool 
     return VAG_OK;
 }
 
-// The front of a likelihood call, one launch: bounds mask and ln prior (log_prob_batch, fitting/samplers.py:72-91), the
-// transformer of fitting/utils.py:110-135 (theta[nb][ndim] -> params[nb], 10^theta for log-scale parameters), A_V per walker,
-// and -- block 0 -- log2 of the point data's times / frequencies and their time extrema for the grid stage.
-__global__ void __launch_bounds__(128)
-vag_fit_front_kernel(vag_model_params base, const double* __restrict__ theta, int nb, int ndim, const double* __restrict__ prior,
-                     int use_priors, double a_v_fixed, vag_model_params* __restrict__ out, double* __restrict__ a_v,
-                     double* __restrict__ ln_prior, int* __restrict__ fitstat, const double* __restrict__ t, int n,
-                     const double* __restrict__ nu, double* __restrict__ lg2_t, double* __restrict__ lg2_nu,
-                     double* __restrict__ tminmax, const int* __restrict__ order /* evaluation slot -> walker, or null */) {
-    const int* slot = reinterpret_cast<const int*>(prior + 64);
-    const int* is_log = slot + 16;
-    const int* kind = slot + 32;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < 4) fitstat[threadIdx.x] = 0;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            lg2_t[i] = log2(t[i] * U_SEC);  // xt::log2(t_obs), observer.h:359
-            lg2_nu[i] = log2(nu[i] * U_HZ);
-        }
-        if (threadIdx.x == 0 && n > 0) {  // ascending data (fitter.py:420-428)
-            tminmax[0] = t[0];
-            tminmax[1] = t[n - 1];
-        }
-    }
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    out[b] = base;  // the sampled fields are patched in place (a private copy indexed by slot would live in scratch)
-    double* f = &out[b].theta_c;
-    double av = a_v_fixed, lp = 0;
-    bool inside = true;
-    const int walker = order ? order[b] : b;
-    for (int d = 0; d < ndim; ++d) {
-        const double v = theta[(size_t)walker * ndim + d];
-        if (use_priors) {
-            const double lo = prior[d], hi = prior[16 + d];
-            inside = inside && (v >= lo) && (v <= hi);
-            if (kind[d] == VAG_PRIOR_GAUSSIAN) {
-                const double z = (v - prior[32 + d]) / prior[48 + d];
-                lp += -0.5 * z * z - log(prior[48 + d] * 2.5066282746310002);
-            } else if (kind[d] == VAG_PRIOR_LOG_UNIFORM) {
-                const double mn = prior[32 + d], mx = prior[48 + d];
-                lp += (v >= mn && v <= mx) ? -log(v * log(mx / mn)) : -INFINITY;
-            } else if (kind[d] == VAG_PRIOR_UNIFORM) {
-                lp += -log(hi - lo);
-            } else if (kind[d] == VAG_PRIOR_UNIFORM_RANGE) {
-                const double mn = prior[32 + d], mx = prior[48 + d];
-                lp += (v >= mn && v <= mx) ? -log(mx - mn) : -INFINITY;
-            }
-        }
-        const double val = is_log[d] ? pow(10.0, v) : v;
-        if (slot[d] == VAG_P_A_V)
-            av = val;  // not a Model field: scales the point-data fluxes (fitter.py:512-519)
-        else if (slot[d] < VAG_P_A_V)  // (VAG_P_SKY_*: read by vag_fit_sky_back_kernel)
-            f[slot[d]] = val;
-    }
-    if (!inside) {  // never evaluated by the reference either: an invalid parameter set stops at the grid stage with no work
-        out[b].theta_c = NAN;
-        lp = -INFINITY;
-    }
-    a_v[b] = av;
-    ln_prior[b] = use_priors ? lp : 0.0;
-}
-
-// The back of one pass of a likelihood call, one wavefront per walker:
-//   chi2[m] (+)= sum_i w_i ((ln F_obs,i - ln max(F_model,i e^{-A_V k_i}, 1e-300)) / sigma_i)^2   (Fitter._chi2_sum, fitter.py:497-501,
-//   with the extinction factor of fitter.py:512-519);
-//   valid[m] &= this pass evaluated the walker -- parameters valid, grid within the engine limits, no ODE row without an acceptable
-//   step, SSC tables within their capacity -- else the walker scores -inf like eval_one's except branch (samplers.py:61-70);
-//   last pass: out[m] = valid ? -chi2 / 2 + ln prior : -inf.
-__global__ void __launch_bounds__(64)
-vag_fit_back_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const double* __restrict__ ln_flux,
-                    const double* __restrict__ ln_err, const double* __restrict__ weight, const double* __restrict__ ext /* or null */,
-                    const double* __restrict__ a_v, const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status,
-                    const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */, double* __restrict__ chi2,
-                    int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out,
-                    int* __restrict__ fitstat /* [0] walkers scored -inf, [1] of those: SSC table failures */,
-                    const int* __restrict__ order /* evaluation slot -> walker, or null */,
-                    const float* __restrict__ cost /* with next_order: the slots' costs of THIS call (the grid kernel's plan scan leaves them) */,
-                    int nb, int* __restrict__ next_order /* or null: [rank] = walker, descending cost */) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    // next_order[rank] = walker, ranks by descending cost of the slot in THIS call (cost[] is in evaluation-slot order: `order` maps a slot
-    // back to its walker; null = identity).  Ranking by counting: the lanes compare this wavefront's slot with all others.  (Until round 5
-    // a launch of its own, vag_order_kernel, behind this kernel.)
-    if (next_order) {
-        const float mine = cost[m];
-        int rank = 0;
-        for (int i0 = 0; i0 < nb; i0 += 64) {
-            const int i = i0 + lane;
-            const float c = i < nb ? cost[i] : -1.0f;
-            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
-        }
-        if (lane == 0) next_order[rank] = order ? order[m] : m;
-    }
-    const double av = (ext != nullptr) ? a_v[m] : 0.0;
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    if (grid_ok)
-        for (int i = lane; i < n; i += 64) {
-            double f = flux[(size_t)m * n + i];
-            if (av != 0.0) f = f * exp(-av * ext[i]);
-            const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
-            const double q = (ln_flux[i] - log(fm)) / ln_err[i];
-            s += weight[i] * (q * q);
-        }
-    s = vag::wave_sum(s);
-    bool bad_row = false;
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
-    const bool any_bad = __any(bad_row);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
-}
-
-// vag_fit_back_kernel for a pass with upper-limit rows (vag_loglike_lim_batch): a row with lim_kind[i] == VAG_OBS_UPPER_LIMIT adds
-//   -2 w_i ln Phi((L_i - F_model,i e^{-A_V k_i}) / sigma_i)   (vag::log_ndtr; no 1e-300 clamp: a model with no flux satisfies a limit)
-// instead of its detection term, at the same place of the lane's sum; everything else is that kernel's, statement for statement.
-// A kernel of its own so that a pass without limit rows runs the instructions it always ran.
-__global__ void __launch_bounds__(64)
-vag_fit_back_lim_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const double* __restrict__ ln_flux,
-                    const double* __restrict__ ln_err, const double* __restrict__ weight, const double* __restrict__ ext /* or null */,
-                    const double* __restrict__ a_v, const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status,
-                    const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */, double* __restrict__ chi2,
-                    int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out,
-                    int* __restrict__ fitstat /* [0] walkers scored -inf, [1] of those: SSC table failures */,
-                    const int* __restrict__ order /* evaluation slot -> walker, or null */,
-                    const float* __restrict__ cost /* with next_order: the slots' costs of THIS call (the grid kernel's plan scan leaves them) */,
-                    int nb, int* __restrict__ next_order /* or null: [rank] = walker, descending cost */,
-                    const int* __restrict__ lim_kind /* [n] VAG_OBS_* */, const double* __restrict__ lim_L /* [n] */,
-                    const double* __restrict__ lim_sigma /* [n] */) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    // next_order[rank] = walker, ranks by descending cost of the slot in THIS call (cost[] is in evaluation-slot order: `order` maps a slot
-    // back to its walker; null = identity).  Ranking by counting: the lanes compare this wavefront's slot with all others.  (Until round 5
-    // a launch of its own, vag_order_kernel, behind this kernel.)
-    if (next_order) {
-        const float mine = cost[m];
-        int rank = 0;
-        for (int i0 = 0; i0 < nb; i0 += 64) {
-            const int i = i0 + lane;
-            const float c = i < nb ? cost[i] : -1.0f;
-            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
-        }
-        if (lane == 0) next_order[rank] = order ? order[m] : m;
-    }
-    const double av = (ext != nullptr) ? a_v[m] : 0.0;
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    if (grid_ok)
-        for (int i = lane; i < n; i += 64) {
-            double f = flux[(size_t)m * n + i];
-            if (av != 0.0) f = f * exp(-av * ext[i]);
-            if (lim_kind[i] == VAG_OBS_UPPER_LIMIT) {
-                s += weight[i] * (-2.0 * vag::log_ndtr((lim_L[i] - f) / lim_sigma[i]));
-                continue;
-            }
-            const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
-            const double q = (ln_flux[i] - log(fm)) / ln_err[i];
-            s += weight[i] * (q * q);
-        }
-    s = vag::wave_sum(s);
-    bool bad_row = false;
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
-    const bool any_bad = __any(bad_row);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
-}
-
-// vag_fit_back_lim_kernel for a pass with rows in noise groups (vag_loglike_noise_batch).  Rows without a group (grp[i] < 0) and
-// upper-limit rows (whatever their group) add the terms of that kernel, statement for statement.  The detection rows of every group g
-// the pass holds (bit g of `present`) add, with s_g the walker's systematic -- the free parameter with the slot VAG_P_NOISE_SYS0 + g
-// (found as vag::sky_placement finds pa), else noise[g] -- and c_g = noise[8 + g]:
-//   v_i = sigma_i^2 + s_g^2, p_i = w_i / v_i, A = sum p_i r_i^2, B = sum p_i r_i, P = sum p_i, N = sum w_i log1p(s_g^2 / sigma_i^2),
-//   c_g == 0: A + N  (separable: the group may span passes);  c_g > 0: A - c_g^2 B^2 / (1 + c_g^2 P) + N + log1p(c_g^2 P)  (the pass
-//   holds all of the group: noise_scan refuses anything else).
-// Every sum is a fixed lane-strided sum followed by vag::wave_sum, group after group in ascending g: the value depends on the walker's
-// row alone, not on its evaluation slot.  The groups are walked one at a time (a wave-uniform loop over the set bits), so the four
-// accumulators are scalars in registers; a row's log is taken once, in the turn of its own group.  A kernel of its own so that a pass
-// without grouped rows runs the instructions it always ran.
-__global__ void __launch_bounds__(64)
-vag_fit_back_noise_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const double* __restrict__ ln_flux,
-                    const double* __restrict__ ln_err, const double* __restrict__ weight, const double* __restrict__ ext /* or null */,
-                    const double* __restrict__ a_v, const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status,
-                    const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */, double* __restrict__ chi2,
-                    int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out,
-                    int* __restrict__ fitstat /* [0] walkers scored -inf, [1] of those: SSC table failures */,
-                    const int* __restrict__ order /* evaluation slot -> walker, or null */,
-                    const float* __restrict__ cost /* with next_order: the slots' costs of THIS call (the grid kernel's plan scan leaves them) */,
-                    int nb, int* __restrict__ next_order /* or null: [rank] = walker, descending cost */,
-                    const int* __restrict__ lim_kind /* [n] VAG_OBS_*, or null: no limit row in this pass */,
-                    const double* __restrict__ lim_L /* [n] */, const double* __restrict__ lim_sigma /* [n] */,
-                    const double* __restrict__ theta /* [nb][ndim] */, int ndim, const double* __restrict__ prior,
-                    const double* __restrict__ noise /* [sys_fixed 8 | calib 8] */, const int* __restrict__ grp /* [n] group id or -1 */,
-                    unsigned present /* bit g: some row of the pass is in group g */) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    if (next_order) {  // (as vag_fit_back_kernel)
-        const float mine = cost[m];
-        int rank = 0;
-        for (int i0 = 0; i0 < nb; i0 += 64) {
-            const int i = i0 + lane;
-            const float c = i < nb ? cost[i] : -1.0f;
-            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
-        }
-        if (lane == 0) next_order[rank] = order ? order[m] : m;
-    }
-    const int walker = order ? order[m] : m;
-    const double av = (ext != nullptr) ? a_v[m] : 0.0;
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    if (grid_ok)
-        for (int i = lane; i < n; i += 64) {
-            const bool is_lim = lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT;
-            if (grp[i] >= 0 && !is_lim) continue;  // a grouped detection: in the turn of its group below
-            double f = flux[(size_t)m * n + i];
-            if (av != 0.0) f = f * exp(-av * ext[i]);
-            if (is_lim) {
-                s += weight[i] * (-2.0 * vag::log_ndtr((lim_L[i] - f) / lim_sigma[i]));
-                continue;
-            }
-            const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
-            const double q = (ln_flux[i] - log(fm)) / ln_err[i];
-            s += weight[i] * (q * q);
-        }
-    s = vag::wave_sum(s);
-    if (grid_ok) {
-        const int* slot = reinterpret_cast<const int*>(prior + 64);
-        const int* is_log = slot + 16;
-        for (int g = 0; g < VAG_NOISE_MAX_GROUPS; ++g) {
-            if (!((present >> g) & 1u)) continue;
-            double sg = noise[g];
-            for (int d = 0; d < ndim; ++d) {
-                if (slot[d] != VAG_P_NOISE_SYS0 + g) continue;
-                const double v = theta[(size_t)walker * ndim + d];
-                sg = is_log[d] ? pow(10.0, v) : v;
-            }
-            const double s2 = sg * sg, cg = noise[VAG_NOISE_MAX_GROUPS + g];
-            double A = 0, B = 0, P = 0, N = 0;
-            for (int i = lane; i < n; i += 64) {
-                if (grp[i] != g || (lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT)) continue;
-                double f = flux[(size_t)m * n + i];
-                if (av != 0.0) f = f * exp(-av * ext[i]);
-                const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
-                const double r = ln_flux[i] - log(fm), sig2 = ln_err[i] * ln_err[i];
-                const double p = weight[i] / (sig2 + s2);
-                A += p * (r * r);
-                B += p * r;
-                P += p;
-                N += weight[i] * log1p(s2 / sig2);
-            }
-            A = vag::wave_sum(A);
-            N = vag::wave_sum(N);
-            double term = A + N;
-            if (cg > 0) {  // (wave-uniform) the calibration scale marginalised: a rank-one update of the diagonal covariance
-                B = vag::wave_sum(B);
-                P = vag::wave_sum(P);
-                const double c2 = cg * cg;
-                term = A - c2 * (B * B) / (1.0 + c2 * P) + N + log1p(c2 * P);
-            }
-            s += term;  // (every lane holds the same sums; lane 0 stores)
-        }
-    }
-    bool bad_row = false;
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
-    const bool any_bad = __any(bad_row);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
-}
-
-// The back of a counts pass (vag_loglike_counts_batch), one wavefront per walker like its siblings.  flux [nb][ns] holds the walker's
-// band-integrated flux at the group's ns sample times; row i gathers its m samples in k order, mu_i = B_i + a_i sum_k F[idx[i m + k]],
-// and adds w_i D(N_i, mu_i) (vag::poisson_deviance) to the lane's sum; a row with w_i = 0 adds nothing.  The lanes' sums are closed by
-// vag::wave_sum in the fixed order of the other back kernels, so the value depends on the walker's own row of flux alone.  The pass
-// adds 2 sum_i w_i D_i + const2 to chi^2, const2 = -2 sum_i w_i S_i being the walker-independent half the host formed (counts_scan).
-// Validity, the first / last pass flags, the rejection counters and the evaluation-order hand-over are vag_fit_back_kernel's.
-__global__ void __launch_bounds__(64)
-vag_fit_back_counts_kernel(const double* __restrict__ flux /* [nb][ns] */, int ns, int n, int mm, const int* __restrict__ idx /* [n][mm] */,
-                           const double* __restrict__ counts, const double* __restrict__ background, const double* __restrict__ scale,
-                           const double* __restrict__ weight, double const2, const VagGridMeta* __restrict__ meta,
-                           const int* __restrict__ row_status, const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */,
-                           double* __restrict__ chi2, int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last,
-                           double* __restrict__ out, int* __restrict__ fitstat, const int* __restrict__ order /* evaluation slot -> walker, or null */,
-                           const float* __restrict__ cost, int nb, int* __restrict__ next_order /* or null */) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    if (next_order) {  // (as vag_fit_back_kernel)
-        const float mine = cost[m];
-        int rank = 0;
-        for (int i0 = 0; i0 < nb; i0 += 64) {
-            const int i = i0 + lane;
-            const float c = i < nb ? cost[i] : -1.0f;
-            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
-        }
-        if (lane == 0) next_order[rank] = order ? order[m] : m;
-    }
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    if (grid_ok) {
-        const double* f = flux + (size_t)m * ns;
-        for (int i = lane; i < n; i += 64) {
-            const double w = weight[i];
-            if (w == 0.0) continue;
-            const int* ix = idx + (size_t)i * mm;
-            double sum = 0;
-            for (int k = 0; k < mm; ++k) sum += f[ix[k]];
-            const double mu = background[i] + scale[i] * sum;
-            s += w * vag::poisson_deviance(counts[i], mu);
-        }
-    }
-    s = 2.0 * vag::wave_sum(s) + const2;
-    bool bad_row = false;
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
-    const bool any_bad = __any(bad_row);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
-}
-
-// The back of a spectral-index pass (vag_loglike_index_batch), one wavefront per walker like its siblings.  flux [nb][n K] holds the
-// walker's flux density at the group's points (t_i, nu_k), i outer; lane i strides the rows, reads its K consecutive values, forms
-// S_i = vag::log_slope - A_V ext_slope and adds w_i ((S_i - s_i) / sigma_i)^2 to the lane's sum; a row with w_i = 0 adds nothing.  A row
-// whose slope is undefined (some F <= 0 or not finite) makes the sum NaN, which the last pass turns into -inf and counts.  The lanes'
-// sums are closed by vag::wave_sum in the fixed order of the other back kernels, so the value depends on the walker's own row of flux
-// alone.  Validity, the first / last pass flags, the rejection counters and the evaluation-order hand-over are vag_fit_back_kernel's.
-__global__ void __launch_bounds__(64)
-vag_fit_back_index_kernel(const double* __restrict__ flux /* [nb][n K] */, int n, int K, const double* __restrict__ value,
-                          const double* __restrict__ err, const double* __restrict__ weight, const double* __restrict__ coef /* [K] */,
-                          double ext_slope, const double* __restrict__ a_v, const VagGridMeta* __restrict__ meta,
-                          const int* __restrict__ row_status, const int* __restrict__ row_off, const int* __restrict__ ic_status /* or null */,
-                          double* __restrict__ chi2, int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last,
-                          double* __restrict__ out, int* __restrict__ fitstat, const int* __restrict__ order /* evaluation slot -> walker, or null */,
-                          const float* __restrict__ cost, int nb, int* __restrict__ next_order /* or null */) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    if (next_order) {  // (as vag_fit_back_kernel)
-        const float mine = cost[m];
-        int rank = 0;
-        for (int i0 = 0; i0 < nb; i0 += 64) {
-            const int i = i0 + lane;
-            const float c = i < nb ? cost[i] : -1.0f;
-            rank += __popcll(__ballot(c > mine || (c == mine && i < m)));
-        }
-        if (lane == 0) next_order[rank] = order ? order[m] : m;
-    }
-    const double shift = ext_slope != 0.0 ? a_v[m] * ext_slope : 0.0;
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    if (grid_ok) {
-        const double* f = flux + (size_t)m * n * K;
-        for (int i = lane; i < n; i += 64) {
-            const double w = weight[i];
-            if (w == 0.0) continue;
-            const double q = (vag::log_slope(f + (size_t)i * K, 1, coef, K) - shift - value[i]) / err[i];
-            s += w * (q * q);
-        }
-    }
-    s = vag::wave_sum(s);
-    bool bad_row = false;
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad_row = bad_row || row_status[r] == 1;
-    const bool any_bad = __any(bad_row);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
-}
-
 // ---- centroid groups (vag_loglike_sky_batch): their data in one device buffer, uploaded like the fit spec when its hash changes.
 //      Layout in doubles, per group: [nu | t | east | north | err_east | err_north | weight] (1 + 6 n). ----
 static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
@@ -4134,56 +3713,6 @@ static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
     c->skyfit_doubles = total;
     c->skyfit_hash_valid = true;
     return VAG_OK;
-}
-
-// The back of one centroid pass, one wavefront per walker (vag_fit_back_kernel's protocol): the walker's sky placement (free
-// parameters with slots VAG_P_SKY_*, else the fixed values), the group's chi^2 term, and validity -- F > 0 and finite moments at
-// every epoch, grid, ODE rows and SSC tables of this pass.
-__global__ void __launch_bounds__(64)
-vag_fit_sky_back_kernel(const double* __restrict__ mom /* [nb][n][6] */, int n, const double* __restrict__ obs /* [t|e|n|ee|en|w] */,
-                        const double* __restrict__ theta, int ndim, const double* __restrict__ prior, double pa_fixed, double east0_fixed,
-                        double north0_fixed, const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status,
-                        const int* __restrict__ row_off, const int* __restrict__ ic_status, double* __restrict__ chi2, int* __restrict__ valid,
-                        const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out, int* __restrict__ fitstat,
-                        const int* __restrict__ order) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    const int walker = order ? order[m] : m;
-    double pa = pa_fixed, e0 = east0_fixed, n0 = north0_fixed;
-    vag::sky_placement(theta, walker, ndim, prior, pa, e0, n0);
-    double sp, cp;
-    sincos(pa, &sp, &cp);
-    const double *e_obs = obs + n, *n_obs = obs + 2 * (size_t)n, *e_err = obs + 3 * (size_t)n, *n_err = obs + 4 * (size_t)n,
-                 *w = obs + 5 * (size_t)n;
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    bool bad = false;
-    if (grid_ok)
-        for (int i = lane; i < n; i += 64) {
-            const double* mo = mom + ((size_t)m * n + i) * 6;
-            const double F = mo[0], X = mo[1], Y = mo[2];
-            bad = bad || !(F > 0) || !isfinite(F) || !isfinite(X) || !isfinite(Y);
-            const double east = e0 + (X * sp + Y * cp), north = n0 + (X * cp - Y * sp);
-            const double qe = (e_obs[i] - east) / e_err[i], qn = (n_obs[i] - north) / n_err[i];
-            s += w[i] * (qe * qe + qn * qn);
-        }
-    s = vag::wave_sum(s);
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad = bad || row_status[r] == 1;
-    const bool any_bad = __any(bad);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
 }
 
 // ---- visibility groups (vag_loglike_vis_batch): their data in one device buffer, uploaded like the centroid groups when the hash
@@ -4273,44 +3802,6 @@ static int upload_vis_spec(vag_ctx* c, const vag_vis_fit_spec* vis) {
     return VAG_OK;
 }
 
-// The back of one visibility pass, one wavefront per walker (vag_fit_back_kernel's protocol): the walker's block partials in a
-// fixed order (lane-strided, then the wavefront sum), and validity -- finite V_mod at every datum, grid, ODE rows and SSC tables of
-// this pass.  A model with no flux is valid: its V_mod is 0.
-__global__ void __launch_bounds__(64)
-vag_fit_vis_back_kernel(const double* __restrict__ partial /* [nb][n_blk][2] */, int n_blk, const VagGridMeta* __restrict__ meta,
-                        const int* __restrict__ row_status, const int* __restrict__ row_off, const int* __restrict__ ic_status,
-                        double* __restrict__ chi2, int* __restrict__ valid, const double* __restrict__ ln_prior, int first, int last,
-                        double* __restrict__ out, int* __restrict__ fitstat, const int* __restrict__ order) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    bool bad = false;
-    if (grid_ok)
-        for (int i = lane; i < n_blk; i += 64) {
-            const double* p = partial + ((size_t)m * n_blk + i) * 2;
-            s += p[0];
-            bad = bad || p[1] != 0.0;
-        }
-    s = vag::wave_sum(s);
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad = bad || row_status[r] == 1;
-    const bool any_bad = __any(bad);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[order ? order[m] : m] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
-}
-
 // ---- polarization groups (vag_loglike_pol_batch): their data in one device buffer, uploaded like the centroid groups when the hash
 //      changes.  Layout in doubles, per group: [nu | t | q | u | err_q | err_u | weight] (1 + 6 n); u and err_u of a DEGREE group are
 //      zeros. ----
@@ -4374,166 +3865,6 @@ static int upload_pol_spec(vag_ctx* c, const vag_pol_fit_spec* pol) {
     c->polfit_doubles = total;
     c->polfit_hash_valid = true;
     return VAG_OK;
-}
-
-// The walkers' polarization spec, one thread per evaluation slot: spec[m] = {b - 1 of the forward, reverse shock, Pi_max of the forward,
-// reverse shock} as pol_spec() resolves a vag_pol_spec -- free parameters with the slots VAG_P_POL_*, else the fixed values; a reverse
-// b that is neither free nor given (< 0) follows the walker's forward b; a Pi_max < 0 is (p + 1) / (p + 7/3) with the p of the walker's
-// transformed parameters.  bad[m] = 1 where pol_spec() would refuse the walker (its spec is then 0: unpolarized, never read back).
-__global__ void __launch_bounds__(128)
-vag_fit_pol_spec_kernel(const double* __restrict__ theta, int nb, int ndim, const double* __restrict__ prior,
-                        const vag_model_params* __restrict__ params, double b0, double b1, double pm0, double pm1,
-                        const int* __restrict__ order, double* __restrict__ spec, int* __restrict__ bad) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= nb) return;
-    const int walker = order ? order[m] : m;
-    const int* slot = reinterpret_cast<const int*>(prior + 64);
-    const int* is_log = slot + 16;
-    bool b1_given = !(b1 < 0);
-    for (int d = 0; d < ndim; ++d) {
-        const int sl = slot[d];
-        if (sl < VAG_P_POL_B || sl > VAG_P_POL_PI_MAX_RVS) continue;
-        const double v = theta[(size_t)walker * ndim + d];
-        const double val = is_log[d] ? pow(10.0, v) : v;
-        b0 = sl == VAG_P_POL_B ? val : b0;  // (selects, as in sky_placement)
-        pm0 = sl == VAG_P_POL_PI_MAX ? val : pm0;
-        b1 = sl == VAG_P_POL_B_RVS ? val : b1;
-        pm1 = sl == VAG_P_POL_PI_MAX_RVS ? val : pm1;
-        b1_given = b1_given || sl == VAG_P_POL_B_RVS;
-    }
-    if (!b1_given) b1 = b0;
-    const bool ok = isfinite(b0) && b0 >= 0 && isfinite(b1) && b1 >= 0 && !(pm0 != pm0) && !(pm0 > 1) && !(pm1 != pm1) && !(pm1 > 1);
-    const double p0 = params[m].p, p1 = params[m].rvs_p;
-    if (pm0 < 0) pm0 = (p0 + 1) / (p0 + 7.0 / 3.0);
-    if (pm1 < 0) pm1 = (p1 + 1) / (p1 + 7.0 / 3.0);
-    double* o = spec + 4 * (size_t)m;
-    o[0] = ok ? b0 - 1 : 0.0;
-    o[1] = ok ? b1 - 1 : 0.0;
-    o[2] = ok ? pm0 : 0.0;
-    o[3] = ok ? pm1 : 0.0;
-    bad[m] = ok ? 0 : 1;
-}
-
-// The back of one polarization pass, one wavefront per walker (vag_fit_back_kernel's protocol): the walker's position angle (the free
-// parameter with the slot VAG_P_SKY_PA, else the fixed value), the turn of the jet-frame Q, U by 2 pa, the residuals of up to 64
-// epochs at a time, one per lane, added in epoch order, and validity -- a valid spec, I > 0 and finite I, Q, U at every epoch, grid,
-// ODE rows and SSC tables of this pass.  A DEGREE group reads hypot(Q, U) of the jet frame: the position angle does not enter.
-__global__ void __launch_bounds__(64)
-vag_fit_pol_back_kernel(const double* __restrict__ stokes /* [nb][n][3] jet frame */, int n, int kind,
-                        const double* __restrict__ obs /* [t|q|u|eq|eu|w] */, const int* __restrict__ spec_bad,
-                        const double* __restrict__ theta, int ndim, const double* __restrict__ prior, double pa_fixed,
-                        const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status, const int* __restrict__ row_off,
-                        const int* __restrict__ ic_status, double* __restrict__ chi2, int* __restrict__ valid,
-                        const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out, int* __restrict__ fitstat,
-                        const int* __restrict__ order) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    const int walker = order ? order[m] : m;
-    double pa = pa_fixed, e0 = 0, n0 = 0;
-    vag::sky_placement(theta, walker, ndim, prior, pa, e0, n0);
-    double s2, c2;
-    sincos(2 * pa, &s2, &c2);
-    const double *q_obs = obs + n, *u_obs = obs + 2 * (size_t)n, *q_err = obs + 3 * (size_t)n, *u_err = obs + 4 * (size_t)n,
-                 *w = obs + 5 * (size_t)n;
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    bool bad = spec_bad[m] != 0;
-    if (grid_ok)
-        for (int i0 = 0; i0 < n; i0 += 64) {
-            const int i = i0 + lane, cnt = min(64, n - i0);
-            double term = 0;
-            if (i < n) {
-                const double* sk = stokes + ((size_t)m * n + i) * 3;
-                const double I = sk[0], Q = sk[1], U = sk[2];
-                bad = bad || !(I > 0) || !isfinite(I) || !isfinite(Q) || !isfinite(U);
-                if (kind == VAG_POL_DEGREE) {
-                    const double r = (q_obs[i] - hypot(Q, U) / I) / q_err[i];
-                    term = w[i] * (r * r);
-                } else {
-                    const double Qs = Q * c2 - U * s2, Us = Q * s2 + U * c2;
-                    const double rq = (q_obs[i] - Qs / I) / q_err[i], ru = (u_obs[i] - Us / I) / u_err[i];
-                    term = w[i] * (rq * rq + ru * ru);
-                }
-            }
-            for (int j = 0; j < cnt; ++j) s += vag::wave_bcast(term, j);  // every lane: the epochs in order
-        }
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad = bad || row_status[r] == 1;
-    const bool any_bad = __any(bad);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
-}
-
-// vag_fit_pol_back_kernel for a DEGREE group with upper-limit epochs (vag_loglike_lim_batch): an epoch with lim_kind[i] ==
-// VAG_OBS_UPPER_LIMIT adds -2 w_i ln Phi((q_i - hypot(Q, U) / I) / err_q_i) instead of its detection term (q holds the limit, err_q
-// its noise level); the I <= 0 rule stays.  Everything else is that kernel's, statement for statement; a kernel of its own so that
-// a group without limit epochs runs the instructions it always ran.
-__global__ void __launch_bounds__(64)
-vag_fit_pol_back_lim_kernel(const double* __restrict__ stokes /* [nb][n][3] jet frame */, int n, int kind,
-                        const double* __restrict__ obs /* [t|q|u|eq|eu|w] */, const int* __restrict__ spec_bad,
-                        const double* __restrict__ theta, int ndim, const double* __restrict__ prior, double pa_fixed,
-                        const VagGridMeta* __restrict__ meta, const int* __restrict__ row_status, const int* __restrict__ row_off,
-                        const int* __restrict__ ic_status, double* __restrict__ chi2, int* __restrict__ valid,
-                        const double* __restrict__ ln_prior, int first, int last, double* __restrict__ out, int* __restrict__ fitstat,
-                        const int* __restrict__ order, const int* __restrict__ lim_kind /* [n] VAG_OBS_* */) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    const int walker = order ? order[m] : m;
-    double pa = pa_fixed, e0 = 0, n0 = 0;
-    vag::sky_placement(theta, walker, ndim, prior, pa, e0, n0);
-    double s2, c2;
-    sincos(2 * pa, &s2, &c2);
-    const double *q_obs = obs + n, *u_obs = obs + 2 * (size_t)n, *q_err = obs + 3 * (size_t)n, *u_err = obs + 4 * (size_t)n,
-                 *w = obs + 5 * (size_t)n;
-    const bool grid_ok = meta[m].status == 0;
-    double s = 0;
-    bool bad = spec_bad[m] != 0;
-    if (grid_ok)
-        for (int i0 = 0; i0 < n; i0 += 64) {
-            const int i = i0 + lane, cnt = min(64, n - i0);
-            double term = 0;
-            if (i < n) {
-                const double* sk = stokes + ((size_t)m * n + i) * 3;
-                const double I = sk[0], Q = sk[1], U = sk[2];
-                bad = bad || !(I > 0) || !isfinite(I) || !isfinite(Q) || !isfinite(U);
-                if (kind == VAG_POL_DEGREE) {
-                    const double r = (q_obs[i] - hypot(Q, U) / I) / q_err[i];
-                    term = w[i] * (lim_kind[i] == VAG_OBS_UPPER_LIMIT ? -2.0 * vag::log_ndtr(r) : r * r);
-                } else {
-                    const double Qs = Q * c2 - U * s2, Us = Q * s2 + U * c2;
-                    const double rq = (q_obs[i] - Qs / I) / q_err[i], ru = (u_obs[i] - Us / I) / u_err[i];
-                    term = w[i] * (rq * rq + ru * ru);
-                }
-            }
-            for (int j = 0; j < cnt; ++j) s += vag::wave_bcast(term, j);  // every lane: the epochs in order
-        }
-    if (grid_ok)
-        for (int r = row_off[m] + lane; r < row_off[m + 1]; r += 64) bad = bad || row_status[r] == 1;
-    const bool any_bad = __any(bad);
-    if (lane == 0) {
-        const bool ic_bad = grid_ok && ic_status && ic_status[m] != 0;
-        const int ok = (first ? 1 : valid[m]) && grid_ok && !any_bad && !ic_bad;
-        const double acc = first ? s : chi2[m] + s;
-        valid[m] = ok;
-        chi2[m] = acc;
-        if (ic_bad) atomicAdd(fitstat + 1, 1);
-        if (last) {
-            const double lp = ln_prior[m];
-            const bool fin = ok && isfinite(acc) && lp > -INFINITY;
-            out[walker] = fin ? -0.5 * acc + lp : -INFINITY;
-            if (!fin) atomicAdd(fitstat, 1);
-        }
-    }
 }
 
 // ---- upper-limit rows (vag_loglike_lim_batch): the blocks that hold a limit row, in one device buffer, uploaded like the other spec
@@ -4895,11 +4226,53 @@ static int upload_index_spec(vag_ctx* c, const vag_index_fit_spec* is, const std
     return VAG_OK;
 }
 
-static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec,
-                        const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
-                        const vag_pol_fit_spec* pol = nullptr, const LimLayout* lim = nullptr, const NoiseLayout* noise = nullptr,
-                        const vag_counts_fit_spec* counts = nullptr, const CountsLayout* clay = nullptr,
-                        const vag_index_fit_spec* index = nullptr, const IndexLayout* ilay = nullptr) {
+// ---- one likelihood request.  Every vag_loglike_*_batch entry point fills a FitRequest from its arguments (a spec it does not take
+//      stays null) and calls loglike_dev or loglike_host; a request whose optional blocks are null or empty is therefore the narrower
+//      entry point's request, statement for statement. ----
+namespace {
+struct FitRequest {
+    const vag_fit_spec* spec = nullptr;
+    const vag_sky_fit_spec* sky = nullptr;      // after fit_request_prepare: null when nothing reads the placement
+    const vag_vis_fit_spec* vis = nullptr;      // after fit_request_prepare: null when it has no group; so pol, counts, index
+    const vag_pol_fit_spec* pol = nullptr;
+    const vag_limit_fit_spec* lim = nullptr;    // after fit_request_prepare: null when no row is a limit (llay.any)
+    const vag_noise_fit_spec* noise = nullptr;  // after fit_request_prepare: null when no row is grouped (nlay.any)
+    const vag_counts_fit_spec* counts = nullptr;
+    const vag_index_fit_spec* index = nullptr;
+    LimLayout llay;
+    NoiseLayout nlay;
+    CountsLayout clay;
+    IndexLayout ilay;
+    std::vector<double> lstage, nstage, cstage, istage;  // what the scans lay out for upload_{lim,noise,counts,index}_spec
+    bool placed = false;                                 // some group reads east0 / north0
+    bool prepared = false;                               // fit_request_prepare has run
+};
+}  // namespace
+
+// Normalises the request and scans its host-side blocks, once per call (host work only: no context is touched).  spec is not null.
+static int fit_request_prepare(FitRequest& r) {
+    if (r.prepared) return VAG_OK;
+    if (r.vis && r.vis->n_groups == 0) r.vis = nullptr;
+    if (r.counts && r.counts->n_groups == 0) r.counts = nullptr;
+    if (r.index && r.index->n_groups == 0) r.index = nullptr;
+    int rc = VAG_OK;
+    if (r.index && (rc = index_scan(r.index, r.istage, r.ilay))) return rc;
+    if (r.counts && (rc = counts_scan(r.counts, r.cstage, r.clay))) return rc;
+    if (r.noise && (rc = noise_scan(r.spec, r.noise, r.nstage, r.nlay))) return rc;
+    if (r.lim && (rc = lim_scan(r.spec, r.pol, r.lim, r.lstage, r.llay))) return rc;  // (pol as given: an empty list checks n_pol_groups)
+    if (!r.nlay.any) r.noise = nullptr;
+    if (!r.llay.any) r.lim = nullptr;
+    if (r.pol && r.pol->n_groups == 0) r.pol = nullptr;
+    r.placed = (r.sky && r.sky->n_groups > 0) || r.vis;
+    // (east0 / north0 place centroid and visibility groups only: without such a group they are refused as free parameters)
+    if (!r.pol && !r.placed) r.sky = nullptr;  // nothing reads the placement
+    r.prepared = true;
+    return VAG_OK;
+}
+
+static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec) {
+    const vag_fit_spec* spec = req.spec;
+    const vag_sky_fit_spec* sky = req.sky;
     int rc = VAG_OK;
     const int n = spec->n_data;
     hipStream_t st = c->stream;
@@ -4924,66 +4297,71 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
                        c->d_lg2t.as<double>(), c->d_lg2nu.as<double>(), c->d_tminmax.as<double>(), d_order);
     HIPCHK(hipGetLastError());
     bool order_made = false;
-    // once per call, from the first pass's grids: the order the NEXT call evaluates in -- made by the first back kernel (its wavefronts are
-    // one per evaluation slot: no launch of its own on the call's critical path since round 6)
-    auto next_order = [&]() -> int* {
-        if (!can_order || order_made) return nullptr;
+    // once per call, from the first pass's grids: the order the NEXT call evaluates in -- made by the first back kernel that can be a
+    // call's first (its wavefronts are one per evaluation slot: no launch of its own on the call's critical path since round 6)
+    auto next_order = [&]() -> FitOrderOut {
+        FitOrderOut o{c->d_cost_f.as<float>(), nb, nullptr};
+        if (!can_order || order_made) return o;
         DevBuf& nxt = c->d_order[c->order_cur ^ 1];
-        if (nxt.ensure(sizeof(int) * (size_t)nb)) return nullptr;
+        if (nxt.ensure(sizeof(int) * (size_t)nb)) return o;
         order_made = true;
-        return nxt.as<int>();
+        o.next_order = nxt.as<int>();
+        return o;
     };
-    const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = vis ? vis->n_groups : 0, n_pol_groups = pol ? pol->n_groups : 0;
-    const int n_counts_groups = counts ? counts->n_groups : 0;
-    const int n_index_groups = index ? index->n_groups : 0;
+    const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = req.vis ? req.vis->n_groups : 0;
+    const int n_pol_groups = req.pol ? req.pol->n_groups : 0, n_counts_groups = req.counts ? req.counts->n_groups : 0;
+    const int n_index_groups = req.index ? req.index->n_groups : 0;
     const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups + n_counts_groups + n_index_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
-    // the SSC tables of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
-    // lim_off: where the pass's block of limit rows starts in d_limfit, or -1 (no limit row: the kernel as it was)
-    // noise_off, present: where the pass's group ids start in d_noisefit, or -1 (no grouped row: the kernels as they were), and its groups
-    auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext,
-                    long lim_off, long noise_off = -1, unsigned present = 0) -> int {
+    // what the current pass's back kernel receives (built at its launch: the model stages may have moved the buffers); the SSC tables
+    // of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
+    auto fit_pass = [&]() -> FitPass {
         const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
-        const double* lb = lim_off >= 0 ? c->d_limfit.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
-        const int* icst = (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr;
-        if (noise_off >= 0) {
-            const double* nz = c->d_noisefit.as<double>();
-            hipLaunchKernelGGL(vag_fit_back_noise_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av,
-                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(), icst, d_chi2,
-                               c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(),
-                               d_order, c->d_cost_f.as<float>(), nb, next_order(),
-                               lb ? reinterpret_cast<const int*>(lb + 2 * (size_t)npts) : nullptr, lb, lb ? lb + npts : nullptr, d_theta,
-                               ndim, d_prior, nz, reinterpret_cast<const int*>(nz + noise_off), present);
-        } else if (!lb)
-            hipLaunchKernelGGL(vag_fit_back_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av,
-                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(), icst, d_chi2,
-                               c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(),
-                               d_order, c->d_cost_f.as<float>(), nb, next_order());
-        else
-            hipLaunchKernelGGL(vag_fit_back_lim_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av,
-                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(), icst, d_chi2,
-                               c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(),
-                               d_order, c->d_cost_f.as<float>(), nb, next_order(), reinterpret_cast<const int*>(lb + 2 * (size_t)npts),
-                               lb, lb + npts);
+        return {c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
+                (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0,
+                pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order};
+    };
+    auto begin_pass = [&] {  // before the pass's model request
+        c->order_next = d_order != nullptr;
+        c->last_order = d_order;
+    };
+    auto end_pass = [&]() -> int {  // behind the pass's back kernel
         HIPCHK(hipGetLastError());
         ++pass;
         n_cap = std::max(n_cap, c->plan.n_models_capacity);
         n_inv = std::max(n_inv, c->plan.n_models_invalid);
         return VAG_OK;
     };
+    // the back of a flux pass.  lim_off: where the pass's block of limit rows starts in d_limfit, or -1 (no limit row: the kernel as it
+    // was); noise_off, present: where the pass's group ids start in d_noisefit, or -1 (no grouped row: the kernels as they were), and
+    // its groups
+    auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext,
+                    long lim_off, long noise_off, unsigned present) -> int {
+        const double* lb = lim_off >= 0 ? c->d_limfit.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
+        const int* lk = lb ? reinterpret_cast<const int*>(lb + 2 * (size_t)npts) : nullptr;
+        const double* ls = lb ? lb + npts : nullptr;
+        if (noise_off >= 0) {
+            const double* nz = c->d_noisefit.as<double>();
+            hipLaunchKernelGGL(vag_fit_back_noise_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av, fit_pass(),
+                               next_order(), lk, lb, ls, d_theta, ndim, d_prior, nz, reinterpret_cast<const int*>(nz + noise_off), present);
+        } else {
+            hipLaunchKernelGGL(lb ? vag_fit_back_kernel<true> : vag_fit_back_kernel<false>, dim3(nb), dim3(64), 0, st, flux, npts, lnf,
+                               lne, w, ext, d_av, fit_pass(), next_order(), lk, lb, ls);
+        }
+        return end_pass();
+    };
     c->ic_soft_fail = true;
     if (n > 0) {  // point data: one (t, nu) series per walker (fitter.py:510-522)
         if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * n)) return VAG_E_HIP;
         c->allow_spec = try_spec;
-        c->order_next = d_order != nullptr;
-        c->last_order = d_order;
+        begin_pass();
         rc = run_model_stages(c, d_params, nb, false);
         c->allow_spec = false;
         if (rc == VAG_OK) rc = series_request(c, d_params, nb, n, c->d_series_flux.as<double>(), upload_series_bands(c, spec->nu, n));
         if (rc == VAG_OK)
             rc = back(c->d_series_flux.as<double>(), n, d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n,
-                      spec->ext_kernel ? d + 5 * (size_t)n : nullptr, lim ? lim->point : -1, noise ? noise->point : -1,
-                      noise ? noise->point_present : 0u);
+                      spec->ext_kernel ? d + 5 * (size_t)n : nullptr, req.lim ? req.llay.point : -1, req.noise ? req.nlay.point : -1,
+                      req.noise ? req.nlay.point_present : 0u);
         if (rc == VAG_OK) {
             rc = finish_speculation(c);  // before a band group's own grid pass reuses the plan buffers
             n_cap = std::max(n_cap, c->plan.n_models_capacity);
@@ -5001,12 +4379,11 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(bd.n, n))) return VAG_E_HIP;
         double* db = d + off;
         off += 4 * (size_t)bd.n;
-        c->order_next = d_order != nullptr;
-        c->last_order = d_order;
+        begin_pass();
         rc = band_request_dev(c, d_params, nb, db, bd.n, bd.nu_min, bd.nu_max, bd.num_points, c->d_series_flux.as<double>(), nullptr);
         if (rc == VAG_OK)
             rc = back(c->d_series_flux.as<double>(), bd.n, db + bd.n, db + 2 * (size_t)bd.n, db + 3 * (size_t)bd.n, nullptr,
-                      lim ? lim->band[g] : -1, noise ? noise->band[g] : -1, noise ? noise->band_present[g] : 0u);
+                      req.lim ? req.llay.band[g] : -1, req.noise ? req.nlay.band[g] : -1, req.noise ? req.nlay.band_present[g] : 0u);
     }
     size_t soff = 0;
     for (int g = 0; g < n_groups && rc == VAG_OK; ++g) {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
@@ -5015,30 +4392,21 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         soff += 1 + 6 * (size_t)o.n;
         if (c->d_skycmom.ensure(sizeof(double) * (size_t)nb * o.n * 6)) return VAG_E_HIP;
         rc = prep_times(c, ds + 1, o.n, ds, 1);
-        c->order_next = d_order != nullptr;
-        c->last_order = d_order;
+        begin_pass();
         if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
         if (rc == VAG_OK) rc = centroid_request(c, d_params, nb, o.n, 1, c->d_skycmom.as<double>());
         if (rc == VAG_OK) {
-            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
             hipLaunchKernelGGL(vag_fit_sky_back_kernel, dim3(nb), dim3(64), 0, st, c->d_skycmom.as<double>(), o.n, ds + 1, d_theta, ndim,
-                               d_prior, sky->pa_fixed, sky->east0_fixed, sky->north0_fixed, c->d_meta.as<VagGridMeta>(),
-                               c->d_row_status.as<int>(), c->d_row_off.as<int>(), (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr,
-                               d_chi2, c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out,
-                               c->d_fitstat.as<int>(), d_order);
-            HIPCHK(hipGetLastError());
-            ++pass;
-            n_cap = std::max(n_cap, c->plan.n_models_capacity);
-            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+                               d_prior, sky->pa_fixed, sky->east0_fixed, sky->north0_fixed, fit_pass());
+            rc = end_pass();
         }
     }
     for (int g = 0; g < n_vis_groups && rc == VAG_OK; ++g) {  // visibility groups: one pass each, the chi^2 formed by the chi2 kernel
-        const vag_visibility_obs& o = vis->groups[g];
+        const vag_visibility_obs& o = req.vis->groups[g];
         const vag_ctx::VisLayout& lay = c->vis_layout[g];
         const double* ds = c->d_visfit.as<double>() + lay.obs_off;  // [nu | t | ...]
         rc = prep_times(c, ds + 1, o.n_epochs, ds, 1);
-        c->order_next = d_order != nullptr;
-        c->last_order = d_order;
+        begin_pass();
         if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
         if (rc == VAG_OK) {
             SkyVisFitArgs va{};
@@ -5052,65 +4420,44 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
             rc = vis_chi2_request(c, d_params, nb, o, lay, va);
         }
         if (rc == VAG_OK) {
-            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
             hipLaunchKernelGGL(vag_fit_vis_back_kernel, dim3(nb), dim3(64), 0, st, c->d_vispart.as<double>(), lay.epoch_blk[o.n_epochs],
-                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
-                               (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
-                               pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order);
-            HIPCHK(hipGetLastError());
-            ++pass;
-            n_cap = std::max(n_cap, c->plan.n_models_capacity);
-            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+                               fit_pass());
+            rc = end_pass();
         }
     }
     size_t poff = 0;
     if (n_pol_groups > 0 && rc == VAG_OK) {  // the walkers' own field: once per call, in the evaluation order of d_params
         if (c->d_polspec.ensure(sizeof(double) * 5 * (size_t)nb)) return VAG_E_HIP;  // [nb][4] spec | int [nb] flags
         hipLaunchKernelGGL(vag_fit_pol_spec_kernel, dim3((nb + 127) / 128), dim3(128), 0, st, d_theta, nb, ndim, d_prior, d_params,
-                           pol->b_fixed[0], pol->b_fixed[1], pol->pi_max_fixed[0], pol->pi_max_fixed[1], d_order,
+                           req.pol->b_fixed[0], req.pol->b_fixed[1], req.pol->pi_max_fixed[0], req.pol->pi_max_fixed[1], d_order,
                            c->d_polspec.as<double>(), reinterpret_cast<int*>(c->d_polspec.as<double>() + 4 * (size_t)nb));
         HIPCHK(hipGetLastError());
     }
     for (int g = 0; g < n_pol_groups && rc == VAG_OK; ++g) {  // polarization groups: one pass each, the Stokes sums of sky_request
-        const vag_polarization_obs& o = pol->groups[g];
+        const vag_polarization_obs& o = req.pol->groups[g];
         const double* ds = c->d_polfit.as<double>() + poff;  // [nu | t | q | u | err_q | err_u | weight]
         poff += 1 + 6 * (size_t)o.n;
         if (c->d_polstokes.ensure(sizeof(double) * (size_t)nb * o.n * 3)) return VAG_E_HIP;
         rc = prep_times(c, ds + 1, o.n, ds, 1);
-        c->order_next = d_order != nullptr;
-        c->last_order = d_order;
+        begin_pass();
         if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
         if (rc == VAG_OK)
             rc = pol_stokes_request(c, d_params, nb, o.n, o.n_az > 0 ? o.n_az : 256, c->d_polspec.as<double>(), c->d_polstokes.as<double>());
         if (rc == VAG_OK) {
-            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
-            const int* lk = (lim && lim->pol[g] >= 0) ? reinterpret_cast<const int*>(c->d_limfit.as<double>() + lim->pol[g]) : nullptr;
+            const int* lk = (req.lim && req.llay.pol[g] >= 0) ? reinterpret_cast<const int*>(c->d_limfit.as<double>() + req.llay.pol[g]) : nullptr;
             const int* bad = reinterpret_cast<const int*>(c->d_polspec.as<double>() + 4 * (size_t)nb);
-            const int* icst = (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr;
-            const double pa_fixed = sky ? sky->pa_fixed : 0.0;
-            if (!lk)
-                hipLaunchKernelGGL(vag_fit_pol_back_kernel, dim3(nb), dim3(64), 0, st, c->d_polstokes.as<double>(), o.n, o.kind, ds + 1, bad,
-                                   d_theta, ndim, d_prior, pa_fixed, c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(),
-                                   c->d_row_off.as<int>(), icst, d_chi2, c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0,
-                                   pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order);
-            else
-                hipLaunchKernelGGL(vag_fit_pol_back_lim_kernel, dim3(nb), dim3(64), 0, st, c->d_polstokes.as<double>(), o.n, o.kind, ds + 1,
-                                   bad, d_theta, ndim, d_prior, pa_fixed, c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(),
-                                   c->d_row_off.as<int>(), icst, d_chi2, c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0,
-                                   pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order, lk);
-            HIPCHK(hipGetLastError());
-            ++pass;
-            n_cap = std::max(n_cap, c->plan.n_models_capacity);
-            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+            hipLaunchKernelGGL(lk ? vag_fit_pol_back_kernel<true> : vag_fit_pol_back_kernel<false>, dim3(nb), dim3(64), 0, st,
+                               c->d_polstokes.as<double>(), o.n, o.kind, ds + 1, bad, d_theta, ndim, d_prior, sky ? sky->pa_fixed : 0.0,
+                               fit_pass(), lk);
+            rc = end_pass();
         }
     }
     for (int g = 0; g < n_counts_groups && rc == VAG_OK; ++g) {  // counts groups: one band request on the sample times each, then the Poisson term
-        const vag_counts_obs& o = counts->groups[g];
-        const double* dc = c->d_countsfit.as<double>() + clay->off[g];  // [t_sample | N | B | a | w | idx]
+        const vag_counts_obs& o = req.counts->groups[g];
+        const double* dc = c->d_countsfit.as<double>() + req.clay.off[g];  // [t_sample | N | B | a | w | idx]
         const size_t ns = (size_t)o.n_samples, nr = (size_t)o.n;
         if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(ns, (size_t)std::max(n, 1)))) return VAG_E_HIP;
-        c->order_next = d_order != nullptr;
-        c->last_order = d_order;
+        begin_pass();
         // the band request takes two things from the batch's total work -- the number of (theta, phi) pairs per workgroup, and from
         // 262144 pairs on, for bands of at most 4 nodes, the row-per-lane kernel -- so a band group's flux depends on the batch in its
         // last bits; here both are pinned (COUNTS_PPB pairs, the workgroup kernel), and a walker's counts term is the same bits alone
@@ -5119,27 +4466,19 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
         rc = band_request_dev(c, d_params, nb, dc, o.n_samples, o.nu_min, o.nu_max, o.num_points, c->d_series_flux.as<double>(), nullptr);
         c->ppb_pin = 0;
         if (rc == VAG_OK) {
-            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
             hipLaunchKernelGGL(vag_fit_back_counts_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n_samples, o.n, o.m,
                                reinterpret_cast<const int*>(dc + ns + 4 * nr), dc + ns, dc + ns + nr, dc + ns + 2 * nr, dc + ns + 3 * nr,
-                               clay->const2[g], c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
-                               (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
-                               pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order,
-                               c->d_cost_f.as<float>(), nb, next_order());
-            HIPCHK(hipGetLastError());
-            ++pass;
-            n_cap = std::max(n_cap, c->plan.n_models_capacity);
-            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+                               req.clay.const2[g], fit_pass(), next_order());
+            rc = end_pass();
         }
     }
     for (int g = 0; g < n_index_groups && rc == VAG_OK; ++g) {  // spectral-index groups: the n K points as one series request each, then the slope term
-        const vag_index_obs& o = index->groups[g];
-        const double* di = c->d_indexfit.as<double>() + ilay->off[g];  // [t n K | nu n K | s | sigma | w | c]
+        const vag_index_obs& o = req.index->groups[g];
+        const double* di = c->d_indexfit.as<double>() + req.ilay.off[g];  // [t n K | nu n K | s | sigma | w | c]
         const size_t nr = (size_t)o.n, np = nr * (size_t)o.k;
         if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(np, (size_t)std::max(n, 1)))) return VAG_E_HIP;
         rc = prep_times(c, di, (int)np, di + np, (int)np);
-        c->order_next = d_order != nullptr;
-        c->last_order = d_order;
+        begin_pass();
         if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
         if (rc == VAG_OK) {
             int shared = 0;  // K <= 8 distinct frequencies: the shared-node path of a short series
@@ -5151,17 +4490,10 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
             rc = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), shared);
         }
         if (rc == VAG_OK) {
-            const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
             hipLaunchKernelGGL(vag_fit_back_index_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, o.k,
-                               di + 2 * np, di + 2 * np + nr, di + 2 * np + 2 * nr, di + 2 * np + 3 * nr, o.ext_slope, d_av,
-                               c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
-                               (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp,
-                               pass == 0 ? 1 : 0, pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order,
-                               c->d_cost_f.as<float>(), nb, next_order());
-            HIPCHK(hipGetLastError());
-            ++pass;
-            n_cap = std::max(n_cap, c->plan.n_models_capacity);
-            n_inv = std::max(n_inv, c->plan.n_models_invalid);
+                               di + 2 * np, di + 2 * np + nr, di + 2 * np + 2 * nr, di + 2 * np + 3 * nr, o.ext_slope, d_av, fit_pass(),
+                               next_order());
+            rc = end_pass();
         }
     }
     c->ic_soft_fail = false;
@@ -5177,259 +4509,114 @@ static int loglike_body(vag_ctx* c, const vag_fit_spec* spec, const double* d_th
     return rc;
 }
 
-int vag_loglike_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out) {
+// A likelihood call on device pointers: the scans, the checks, the uploads of every spec block the request holds, and the call
+// (repeated once on the waiting path when a planned-ahead call fails).  The scans come first, as they always did in the entry points
+// that scan: what they refuse is refused without a look at the context.
+static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int nb, int ndim, double* d_out) {
     ApiLock api_lock(c);
     HandoffScope handoff(c);
+    int rc = req.spec ? fit_request_prepare(req) : VAG_OK;
+    if (rc) return rc;
     if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
+    if (!req.spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
     if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
     HIPCHK(hipSetDevice(c->device));
-    int rc = upload_fit_spec(c, spec, ndim);
+    rc = upload_fit_spec(c, req.spec, ndim, req.placed, req.pol != nullptr, req.noise ? req.nlay.n_groups : 0, req.counts || req.index);
+    if (rc == VAG_OK && req.sky) rc = upload_sky_spec(c, req.sky);  // (n_groups = 0: the fixed placement alone)
+    if (rc == VAG_OK && req.vis) rc = upload_vis_spec(c, req.vis);
+    if (rc == VAG_OK && req.pol) rc = upload_pol_spec(c, req.pol);
+    if (rc == VAG_OK && req.lim) rc = upload_lim_spec(c, req.lstage, req.llay);
+    if (rc == VAG_OK && req.noise) rc = upload_noise_spec(c, req.nstage, req.nlay);
+    if (rc == VAG_OK && req.counts) rc = upload_counts_spec(c, req.counts, req.cstage, req.clay);
+    if (rc == VAG_OK && req.index) rc = upload_index_spec(c, req.index, req.istage);
     if (rc) return rc;
-    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work);
-    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false);
+    rc = loglike_body(c, req, d_theta, nb, ndim, d_out, !c->count_work);
+    if (rc == VAG_RETRY) rc = loglike_body(c, req, d_theta, nb, ndim, d_out, false);
     return rc;
+}
+
+// The host-pointer form: the scans (before anything goes to the device), then theta goes up, loglike_dev runs, the values come back.
+static int loglike_host(vag_ctx* c, FitRequest& req, const double* theta, int nb, int ndim, double* out) {
+    ApiLock api_lock(c);
+    if (req.spec) {
+        const int rc = fit_request_prepare(req);
+        if (rc) return rc;
+    }
+    if (!c) return set_err(VAG_E_INVALID, "null context");
+    if (!req.spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
+    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
+    double* d_theta = c->d_theta_in.as<double>();
+    double* d_out = d_theta + (size_t)nb * ndim;
+    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
+    const int rc = loglike_dev(c, req, d_theta, nb, ndim, d_out);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)collect_times(c);
+    return VAG_OK;
+}
+
+static FitRequest fit_request(const vag_fit_spec* spec, const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
+                              const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr,
+                              const vag_noise_fit_spec* noise = nullptr, const vag_counts_fit_spec* counts = nullptr,
+                              const vag_index_fit_spec* index = nullptr) {
+    FitRequest r;
+    r.spec = spec, r.sky = sky, r.vis = vis, r.pol = pol, r.lim = lim, r.noise = noise, r.counts = counts, r.index = index;
+    return r;
+}
+
+int vag_loglike_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out) {
+    FitRequest r = fit_request(spec);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
 int vag_loglike_sky_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const double* d_theta, int nb, int ndim,
                               double* d_out) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    if (sky && sky->n_groups == 0) sky = nullptr;  // exactly vag_loglike_batch_dev
-    HIPCHK(hipSetDevice(c->device));
-    int rc = upload_fit_spec(c, spec, ndim, sky != nullptr);
-    if (rc) return rc;
-    if (sky) {
-        rc = upload_sky_spec(c, sky);
-        if (rc) return rc;
-    }
-    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky);
-    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky);
-    return rc;
+    FitRequest r = fit_request(spec, sky);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
 int vag_loglike_vis_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                               const double* d_theta, int nb, int ndim, double* d_out) {
-    if (!vis || vis->n_groups == 0) return vag_loglike_sky_batch_dev(c, spec, sky, d_theta, nb, ndim, d_out);  // exactly that call
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    HIPCHK(hipSetDevice(c->device));
-    int rc = upload_fit_spec(c, spec, ndim, true);
-    if (rc) return rc;
-    if (sky) {  // (n_groups = 0: the fixed placement alone)
-        rc = upload_sky_spec(c, sky);
-        if (rc) return rc;
-    }
-    rc = upload_vis_spec(c, vis);
-    if (rc) return rc;
-    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis);
-    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis);
-    return rc;
+    FitRequest r = fit_request(spec, sky, vis);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
 int vag_loglike_pol_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                               const vag_pol_fit_spec* pol, const double* d_theta, int nb, int ndim, double* d_out) {
-    if (!pol || pol->n_groups == 0) return vag_loglike_vis_batch_dev(c, spec, sky, vis, d_theta, nb, ndim, d_out);  // exactly that call
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    if (vis && vis->n_groups == 0) vis = nullptr;
-    HIPCHK(hipSetDevice(c->device));
-    // (east0 / north0 place centroid and visibility groups only: without such a group they are refused as before)
-    int rc = upload_fit_spec(c, spec, ndim, (sky && sky->n_groups > 0) || vis, true);
-    if (rc) return rc;
-    if (sky) {  // (n_groups = 0: the fixed position angle alone)
-        rc = upload_sky_spec(c, sky);
-        if (rc) return rc;
-    }
-    if (vis) {
-        rc = upload_vis_spec(c, vis);
-        if (rc) return rc;
-    }
-    rc = upload_pol_spec(c, pol);
-    if (rc) return rc;
-    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol);
-    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol);
-    return rc;
+    FitRequest r = fit_request(spec, sky, vis, pol);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
 int vag_loglike_lim_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                               const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const double* d_theta, int nb, int ndim,
                               double* d_out) {
-    std::vector<double> stage;
-    LimLayout lay;
-    if (lim && spec) {
-        const int rc = lim_scan(spec, pol, lim, stage, lay);
-        if (rc) return rc;
-    }
-    if (!lay.any) return vag_loglike_pol_batch_dev(c, spec, sky, vis, pol, d_theta, nb, ndim, d_out);  // exactly that call
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    if (pol && pol->n_groups == 0) pol = nullptr;
-    if (vis && vis->n_groups == 0) vis = nullptr;
-    const bool placed = (sky && sky->n_groups > 0) || vis;
-    if (!pol && !placed) sky = nullptr;  // (as vag_loglike_sky_batch_dev: nothing reads the placement)
-    HIPCHK(hipSetDevice(c->device));
-    int rc = upload_fit_spec(c, spec, ndim, placed, pol != nullptr);
-    if (rc) return rc;
-    if (sky) {
-        rc = upload_sky_spec(c, sky);
-        if (rc) return rc;
-    }
-    if (vis) {
-        rc = upload_vis_spec(c, vis);
-        if (rc) return rc;
-    }
-    if (pol) {
-        rc = upload_pol_spec(c, pol);
-        if (rc) return rc;
-    }
-    rc = upload_lim_spec(c, stage, lay);
-    if (rc) return rc;
-    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, &lay);
-    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, &lay);
-    return rc;
-}
-
-// The body the chained entry points share once their specs are scanned: the context checks, the uploads of every spec block that is
-// present, and the call (repeated once on the waiting path when a planned-ahead call fails).  llay / nlay are used when their `any` is
-// set; counts with clay when counts is not null, index with ilay when index is not null.
-static int loglike_chained_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
-                               const vag_pol_fit_spec* pol, const std::vector<double>& lstage, const LimLayout& llay,
-                               const std::vector<double>& nstage, const NoiseLayout& nlay, const vag_counts_fit_spec* counts,
-                               const std::vector<double>& cstage, const CountsLayout& clay, const vag_index_fit_spec* index,
-                               const std::vector<double>& istage, const IndexLayout& ilay, const double* d_theta, int nb, int ndim,
-                               double* d_out) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    if (pol && pol->n_groups == 0) pol = nullptr;
-    if (vis && vis->n_groups == 0) vis = nullptr;
-    const bool placed = (sky && sky->n_groups > 0) || vis;
-    if (!pol && !placed) sky = nullptr;  // (as vag_loglike_sky_batch_dev: nothing reads the placement)
-    HIPCHK(hipSetDevice(c->device));
-    int rc = upload_fit_spec(c, spec, ndim, placed, pol != nullptr, nlay.any ? nlay.n_groups : 0, counts != nullptr || index != nullptr);
-    if (rc) return rc;
-    if (sky) {
-        rc = upload_sky_spec(c, sky);
-        if (rc) return rc;
-    }
-    if (vis) {
-        rc = upload_vis_spec(c, vis);
-        if (rc) return rc;
-    }
-    if (pol) {
-        rc = upload_pol_spec(c, pol);
-        if (rc) return rc;
-    }
-    if (llay.any) {
-        rc = upload_lim_spec(c, lstage, llay);
-        if (rc) return rc;
-    }
-    if (nlay.any) {
-        rc = upload_noise_spec(c, nstage, nlay);
-        if (rc) return rc;
-    }
-    if (counts) {
-        rc = upload_counts_spec(c, counts, cstage, clay);
-        if (rc) return rc;
-    }
-    if (index) {
-        rc = upload_index_spec(c, index, istage);
-        if (rc) return rc;
-    }
-    const LimLayout* lp = llay.any ? &llay : nullptr;
-    const NoiseLayout* np = nlay.any ? &nlay : nullptr;
-    const CountsLayout* cp = counts ? &clay : nullptr;
-    const IndexLayout* ip = index ? &ilay : nullptr;
-    rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, !c->count_work, sky, vis, pol, lp, np, counts, cp, index, ip);
-    if (rc == VAG_RETRY) rc = loglike_body(c, spec, d_theta, nb, ndim, d_out, false, sky, vis, pol, lp, np, counts, cp, index, ip);
-    return rc;
+    FitRequest r = fit_request(spec, sky, vis, pol, lim);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
 int vag_loglike_noise_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                                 const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                                 const double* d_theta, int nb, int ndim, double* d_out) {
-    std::vector<double> nstage, lstage;
-    NoiseLayout nlay;
-    LimLayout llay;
-    if (noise && spec) {
-        const int rc = noise_scan(spec, noise, nstage, nlay);
-        if (rc) return rc;
-    }
-    if (!nlay.any) return vag_loglike_lim_batch_dev(c, spec, sky, vis, pol, lim, d_theta, nb, ndim, d_out);  // exactly that call
-    if (lim) {
-        const int rc = lim_scan(spec, pol, lim, lstage, llay);
-        if (rc) return rc;
-    }
-    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, nullptr, {}, CountsLayout{}, nullptr, {}, IndexLayout{}, d_theta, nb,
-                               ndim, d_out);
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
 int vag_loglike_counts_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                                  const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                                  const vag_counts_fit_spec* counts, const double* d_theta, int nb, int ndim, double* d_out) {
-    if (!counts || counts->n_groups == 0)  // exactly that call
-        return vag_loglike_noise_batch_dev(c, spec, sky, vis, pol, lim, noise, d_theta, nb, ndim, d_out);
-    std::vector<double> cstage, nstage, lstage;
-    CountsLayout clay;
-    NoiseLayout nlay;
-    LimLayout llay;
-    int rc = counts_scan(counts, cstage, clay);
-    if (rc) return rc;
-    if (noise && spec) {
-        rc = noise_scan(spec, noise, nstage, nlay);
-        if (rc) return rc;
-    }
-    if (lim && spec) {
-        rc = lim_scan(spec, pol, lim, lstage, llay);
-        if (rc) return rc;
-    }
-    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, counts, cstage, clay, nullptr, {}, IndexLayout{}, d_theta,
-                               nb, ndim, d_out);
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
 int vag_loglike_index_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                                 const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                                 const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* d_theta, int nb,
                                 int ndim, double* d_out) {
-    if (!index || index->n_groups == 0)  // exactly that call
-        return vag_loglike_counts_batch_dev(c, spec, sky, vis, pol, lim, noise, counts, d_theta, nb, ndim, d_out);
-    std::vector<double> istage, cstage, nstage, lstage;
-    IndexLayout ilay;
-    CountsLayout clay;
-    NoiseLayout nlay;
-    LimLayout llay;
-    int rc = index_scan(index, istage, ilay);
-    if (rc) return rc;
-    if (counts && counts->n_groups == 0) counts = nullptr;
-    if (counts) {
-        rc = counts_scan(counts, cstage, clay);
-        if (rc) return rc;
-    }
-    if (noise && spec) {
-        rc = noise_scan(spec, noise, nstage, nlay);
-        if (rc) return rc;
-    }
-    if (lim && spec) {
-        rc = lim_scan(spec, pol, lim, lstage, llay);
-        if (rc) return rc;
-    }
-    return loglike_chained_dev(c, spec, sky, vis, pol, lstage, llay, nstage, nlay, counts, cstage, clay, index, istage, ilay, d_theta, nb,
-                               ndim, d_out);
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
 __global__ void vag_model_cost_kernel(const VagGridMeta* __restrict__ meta, int nb, double* __restrict__ cost,
@@ -5585,8 +4772,9 @@ static int shard_begin(vag_ctx* c, const vag_fit_spec* spec, const double* d_the
     c->shard_last_dealt = slot;  // (kept for inspection even if the evaluation below fails)
     const int* d_order = nullptr;
     if (n_mine > 0) {
-        int rc = loglike_body(c, spec, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>(), !c->count_work);
-        if (rc == VAG_RETRY) rc = loglike_body(c, spec, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>(), false);
+        FitRequest req = fit_request(spec);
+        int rc = loglike_body(c, req, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>(), !c->count_work);
+        if (rc == VAG_RETRY) rc = loglike_body(c, req, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>(), false);
         if (rc) {  // (no block went out: there is nothing to finish, the slot is free)
             if (replaces) fl.in_use = false, --c->shard_costs[entry].in_flight;
             return rc;
@@ -5690,210 +4878,54 @@ int vag_loglike_shard_state_dev(vag_ctx* c, int nb_all, int world, int32_t* d_ta
 }
 
 int vag_loglike_batch(vag_ctx* c, const vag_fit_spec* spec, const double* theta, int nb, int ndim, double* out) {
-    ApiLock api_lock(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
-    double* d_theta = c->d_theta_in.as<double>();
-    double* d_out = d_theta + (size_t)nb * ndim;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
-    int rc = vag_loglike_batch_dev(c, spec, d_theta, nb, ndim, d_out);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return VAG_OK;
+    FitRequest r = fit_request(spec);
+    return loglike_host(c, r, theta, nb, ndim, out);
 }
 
 int vag_loglike_sky_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const double* theta, int nb, int ndim,
                           double* out) {
-    ApiLock api_lock(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
-    double* d_theta = c->d_theta_in.as<double>();
-    double* d_out = d_theta + (size_t)nb * ndim;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
-    int rc = vag_loglike_sky_batch_dev(c, spec, sky, d_theta, nb, ndim, d_out);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return VAG_OK;
+    FitRequest r = fit_request(spec, sky);
+    return loglike_host(c, r, theta, nb, ndim, out);
 }
 
 int vag_loglike_vis_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                           const double* theta, int nb, int ndim, double* out) {
-    if (!vis || vis->n_groups == 0) return vag_loglike_sky_batch(c, spec, sky, theta, nb, ndim, out);  // exactly that call
-    ApiLock api_lock(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
-    double* d_theta = c->d_theta_in.as<double>();
-    double* d_out = d_theta + (size_t)nb * ndim;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
-    int rc = vag_loglike_vis_batch_dev(c, spec, sky, vis, d_theta, nb, ndim, d_out);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return VAG_OK;
+    FitRequest r = fit_request(spec, sky, vis);
+    return loglike_host(c, r, theta, nb, ndim, out);
 }
 
 int vag_loglike_pol_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                           const vag_pol_fit_spec* pol, const double* theta, int nb, int ndim, double* out) {
-    if (!pol || pol->n_groups == 0) return vag_loglike_vis_batch(c, spec, sky, vis, theta, nb, ndim, out);  // exactly that call
-    ApiLock api_lock(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
-    double* d_theta = c->d_theta_in.as<double>();
-    double* d_out = d_theta + (size_t)nb * ndim;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
-    int rc = vag_loglike_pol_batch_dev(c, spec, sky, vis, pol, d_theta, nb, ndim, d_out);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return VAG_OK;
+    FitRequest r = fit_request(spec, sky, vis, pol);
+    return loglike_host(c, r, theta, nb, ndim, out);
 }
 
 int vag_loglike_lim_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                           const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const double* theta, int nb, int ndim, double* out) {
-    bool any = false;
-    if (lim && spec) {  // (checked again, and laid out, by the _dev form)
-        std::vector<double> stage;
-        LimLayout lay;
-        const int rc = lim_scan(spec, pol, lim, stage, lay);
-        if (rc) return rc;
-        any = lay.any;
-    }
-    if (!any) return vag_loglike_pol_batch(c, spec, sky, vis, pol, theta, nb, ndim, out);  // exactly that call
-    ApiLock api_lock(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
-    double* d_theta = c->d_theta_in.as<double>();
-    double* d_out = d_theta + (size_t)nb * ndim;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
-    int rc = vag_loglike_lim_batch_dev(c, spec, sky, vis, pol, lim, d_theta, nb, ndim, d_out);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return VAG_OK;
-}
-
-// The host-pointer form of a chained entry point once its specs are scanned: theta goes up, dev_call(d_theta, d_out) runs the
-// device-pointer form, the values come back.
-static int loglike_chained_host(vag_ctx* c, const vag_fit_spec* spec, const double* theta, int nb, int ndim, double* out,
-                                const std::function<int(double*, double*)>& dev_call) {
-    ApiLock api_lock(c);
-    if (!c) return set_err(VAG_E_INVALID, "null context");
-    if (!spec || !theta || !out || ndim <= 0) return set_err(VAG_E_INVALID, "null spec, sample or output array");
-    if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_theta_in.ensure(sizeof(double) * (size_t)nb * (ndim + 1))) return VAG_E_HIP;
-    double* d_theta = c->d_theta_in.as<double>();
-    double* d_out = d_theta + (size_t)nb * ndim;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)nb * ndim, hipMemcpyHostToDevice, c->stream));
-    const int rc = dev_call(d_theta, d_out);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return VAG_OK;
+    FitRequest r = fit_request(spec, sky, vis, pol, lim);
+    return loglike_host(c, r, theta, nb, ndim, out);
 }
 
 int vag_loglike_noise_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                             const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                             const double* theta, int nb, int ndim, double* out) {
-    bool any = false;
-    if (noise && spec) {  // (checked again, and laid out, by the _dev form)
-        std::vector<double> stage;
-        NoiseLayout lay;
-        const int rc = noise_scan(spec, noise, stage, lay);
-        if (rc) return rc;
-        any = lay.any;
-    }
-    if (!any) return vag_loglike_lim_batch(c, spec, sky, vis, pol, lim, theta, nb, ndim, out);  // exactly that call
-    if (lim) {
-        std::vector<double> stage;
-        LimLayout lay;
-        const int rc = lim_scan(spec, pol, lim, stage, lay);
-        if (rc) return rc;
-    }
-    return loglike_chained_host(c, spec, theta, nb, ndim, out, [&](double* d_theta, double* d_out) {
-        return vag_loglike_noise_batch_dev(c, spec, sky, vis, pol, lim, noise, d_theta, nb, ndim, d_out);
-    });
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise);
+    return loglike_host(c, r, theta, nb, ndim, out);
 }
 
 int vag_loglike_counts_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                              const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                              const vag_counts_fit_spec* counts, const double* theta, int nb, int ndim, double* out) {
-    if (!counts || counts->n_groups == 0)  // exactly that call
-        return vag_loglike_noise_batch(c, spec, sky, vis, pol, lim, noise, theta, nb, ndim, out);
-    {  // (checked again, and laid out, by the _dev form)
-        std::vector<double> stage;
-        CountsLayout clay;
-        int rc = counts_scan(counts, stage, clay);
-        if (rc) return rc;
-        if (noise && spec) {
-            NoiseLayout lay;
-            rc = noise_scan(spec, noise, stage, lay);
-            if (rc) return rc;
-        }
-        if (lim && spec) {
-            LimLayout lay;
-            rc = lim_scan(spec, pol, lim, stage, lay);
-            if (rc) return rc;
-        }
-    }
-    return loglike_chained_host(c, spec, theta, nb, ndim, out, [&](double* d_theta, double* d_out) {
-        return vag_loglike_counts_batch_dev(c, spec, sky, vis, pol, lim, noise, counts, d_theta, nb, ndim, d_out);
-    });
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts);
+    return loglike_host(c, r, theta, nb, ndim, out);
 }
 
 int vag_loglike_index_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
                             const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                             const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* theta, int nb, int ndim,
                             double* out) {
-    if (!index || index->n_groups == 0)  // exactly that call
-        return vag_loglike_counts_batch(c, spec, sky, vis, pol, lim, noise, counts, theta, nb, ndim, out);
-    {  // (checked again, and laid out, by the _dev form)
-        std::vector<double> stage;
-        IndexLayout ilay;
-        int rc = index_scan(index, stage, ilay);
-        if (rc) return rc;
-        if (counts && counts->n_groups > 0) {
-            CountsLayout clay;
-            rc = counts_scan(counts, stage, clay);
-            if (rc) return rc;
-        }
-        if (noise && spec) {
-            NoiseLayout lay;
-            rc = noise_scan(spec, noise, stage, lay);
-            if (rc) return rc;
-        }
-        if (lim && spec) {
-            LimLayout lay;
-            rc = lim_scan(spec, pol, lim, stage, lay);
-            if (rc) return rc;
-        }
-    }
-    return loglike_chained_host(c, spec, theta, nb, ndim, out, [&](double* d_theta, double* d_out) {
-        return vag_loglike_index_batch_dev(c, spec, sky, vis, pol, lim, noise, counts, index, d_theta, nb, ndim, d_out);
-    });
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index);
+    return loglike_host(c, r, theta, nb, ndim, out);
 }
 
 // ------------------------------------------------------------------------------------------------

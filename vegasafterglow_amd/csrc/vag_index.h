@@ -1,6 +1,6 @@
 // vag_index.h -- the log-slope S = sum_{k >= 1} c_k ln(F_k / F_0) of a spectral-index row in FP64: the spectral-index term of the
 // walker likelihood (vag_loglike_index_batch; w ((S - A_V ext_slope - s) / sigma)^2 per row, formed by vag_fit_back_index_kernel of
-// vag_capi.hip).
+// vag_fit_kernels.h).
 #pragma once
 #include <cmath>
 

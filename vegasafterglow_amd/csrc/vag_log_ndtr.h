@@ -1,5 +1,5 @@
 // vag_log_ndtr.h -- ln Phi(z), the log of the standard normal CDF, in FP64: the upper-limit term of the walker likelihood
-// (vag_loglike_lim_batch; -2 w ln Phi((L - M) / sigma) per limit row, formed by the back kernels of vag_capi.hip).
+// (vag_loglike_lim_batch; -2 w ln Phi((L - M) / sigma) per limit row, formed by the back kernels of vag_fit_kernels.h).
 #pragma once
 #include "vag_device.h"
 

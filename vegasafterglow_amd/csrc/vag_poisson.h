@@ -1,5 +1,5 @@
 // vag_poisson.h -- the Poisson deviance D(N, mu) = mu - N - N ln(mu / N) >= 0 in FP64: the counts term of the walker likelihood
-// (vag_loglike_counts_batch; 2 w D per row, formed by vag_fit_back_counts_kernel of vag_capi.hip), and the walker-independent
+// (vag_loglike_counts_batch; 2 w D per row, formed by vag_fit_back_counts_kernel of vag_fit_kernels.h), and the walker-independent
 // constant S(N) = N ln N - N - ln N! the host adds once per spec, so that ln P(N | mu) = -D + S.
 #pragma once
 #include <cmath>

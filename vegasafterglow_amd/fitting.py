@@ -1241,35 +1241,11 @@ class Fitter:
 
             def run():
                 ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
-                if keep[0]._index is not None:
-                    _lib.check(lib.vag_loglike_index_batch_dev(
-                        h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
-                        ref(keep[0]._noise), ref(keep[0]._counts), C.byref(keep[0]._index), theta.data_ptr(), k, keep[0].ndim,
-                        values.data_ptr()))
-                elif keep[0]._counts is not None:
-                    _lib.check(lib.vag_loglike_counts_batch_dev(
-                        h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
-                        ref(keep[0]._noise), C.byref(keep[0]._counts), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
-                elif keep[0]._noise is not None:
-                    _lib.check(lib.vag_loglike_noise_batch_dev(
-                        h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
-                        C.byref(keep[0]._noise), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
-                elif keep[0]._lim is not None:
-                    _lib.check(lib.vag_loglike_lim_batch_dev(
-                        h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), C.byref(keep[0]._lim),
-                        theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
-                elif keep[0]._pol is not None:
-                    _lib.check(lib.vag_loglike_pol_batch_dev(
-                        h, C.byref(keep[0]), C.byref(keep[0]._sky), C.byref(keep[0]._vis) if keep[0]._vis is not None else None,
-                        C.byref(keep[0]._pol), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
-                elif keep[0]._vis is not None:
-                    _lib.check(lib.vag_loglike_vis_batch_dev(h, C.byref(keep[0]), C.byref(keep[0]._sky), C.byref(keep[0]._vis),
-                                                             theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
-                elif keep[0]._sky is not None:
-                    _lib.check(lib.vag_loglike_sky_batch_dev(h, C.byref(keep[0]), C.byref(keep[0]._sky), theta.data_ptr(), k,
-                                                             keep[0].ndim, values.data_ptr()))
-                else:
-                    _lib.check(lib.vag_loglike_batch_dev(h, C.byref(keep[0]), theta.data_ptr(), k, keep[0].ndim, values.data_ptr()))
+                # the widest entry point: with a block absent (None) it is the narrower entry point, bit for bit
+                _lib.check(lib.vag_loglike_index_batch_dev(
+                    h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
+                    ref(keep[0]._noise), ref(keep[0]._counts), ref(keep[0]._index), theta.data_ptr(), k, keep[0].ndim,
+                    values.data_ptr()))
                 if want_costs:  # (one more launch: only a sharder that deals by cost asks for it)
                     _lib.check(lib.vag_last_model_costs_dev(h, k, costs.data_ptr()))
             _on_current_stream(run)
@@ -1339,37 +1315,11 @@ class Fitter:
         plan = _lib.Plan()
         with lock:
             ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
-            if spec._index is not None:
-                _lib.check(_lib.load().vag_loglike_index_batch(
-                    h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
-                    ref(spec._counts), C.byref(spec._index), samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
-                    out.ctypes.data_as(_dp)))
-            elif spec._counts is not None:
-                _lib.check(_lib.load().vag_loglike_counts_batch(
-                    h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
-                    C.byref(spec._counts), samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
-            elif spec._noise is not None:
-                _lib.check(_lib.load().vag_loglike_noise_batch(
-                    h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), C.byref(spec._noise),
-                    samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
-            elif spec._lim is not None:
-                _lib.check(_lib.load().vag_loglike_lim_batch(
-                    h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), C.byref(spec._lim),
-                    samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
-            elif spec._pol is not None:
-                _lib.check(_lib.load().vag_loglike_pol_batch(
-                    h, C.byref(spec), C.byref(spec._sky), C.byref(spec._vis) if spec._vis is not None else None, C.byref(spec._pol),
-                    samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
-            elif spec._vis is not None:
-                _lib.check(_lib.load().vag_loglike_vis_batch(h, C.byref(spec), C.byref(spec._sky), C.byref(spec._vis),
-                                                             samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
-                                                             out.ctypes.data_as(_dp)))
-            elif spec._sky is not None:
-                _lib.check(_lib.load().vag_loglike_sky_batch(h, C.byref(spec), C.byref(spec._sky), samples.ctypes.data_as(_dp),
-                                                             samples.shape[0], spec.ndim, out.ctypes.data_as(_dp)))
-            else:
-                _lib.check(_lib.load().vag_loglike_batch(h, C.byref(spec), samples.ctypes.data_as(_dp), samples.shape[0],
-                                                         spec.ndim, out.ctypes.data_as(_dp)))
+            # the widest entry point: with a block absent (None) it is the narrower entry point, bit for bit
+            _lib.check(_lib.load().vag_loglike_index_batch(
+                h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
+                ref(spec._counts), ref(spec._index), samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
+                out.ctypes.data_as(_dp)))
             _lib.load().vag_last_plan(h, C.byref(plan))
         if plan.n_models_capacity:
             # never silent: these walkers were NOT evaluated (their adaptive grid exceeds the engine's static limits)
