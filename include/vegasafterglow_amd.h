@@ -392,6 +392,9 @@ int vag_flux_density_batch_dev(vag_ctx* ctx, const vag_model_params* d_params, i
  * Only that entry point accepts VAG_P_NOISE_SYS0 + g, and only when its vag_noise_fit_spec has group g (g < n_groups). */
 #define VAG_P_NOISE_SYS0 1008
 #define VAG_NOISE_MAX_GROUPS 8
+/* Nor is this: the absorbing column N_H [cm^-2] of the count-spectrum groups of vag_loglike_fold_batch.  Only that entry point accepts
+ * it, and only when some group carries a cross-section (vag_fold_obs::sigma). */
+#define VAG_P_N_H 1016
 
 /* One group of VLBI centroid positions at one frequency (added after VAG_ABI_VERSION 13, detect by symbol).  The model centroid
  * (Xbar, Ybar) of vag_sky_centroid_batch(t, nu) is placed on the sky as
@@ -754,6 +757,72 @@ int vag_loglike_index_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const va
                                 const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                                 const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* d_theta, int nb,
                                 int ndim, double* d_out);
+
+/* Count spectra through an instrument response (added after VAG_ABI_VERSION 13, detect by symbol).  A fold group holds J energy bins
+ * [E_lo_j, E_hi_j] [keV, observer frame; 0 < E_lo_j < E_hi_j, ascending, non-overlapping, gaps allowed], C channels, a response
+ * R[c][j] >= 0 [cm^2: counts in channel c per photon cm^-2 arriving in bin j; the caller rebins the instrument's matrix to these bins
+ * and folds in any fixed Galactic absorption], n spectra (rows) with t_start_i, exposure_i, observed counts N[i][c], a background
+ * expectation B[i][c] >= 0 and weights w[i][c] >= 0 (w = 0 ignores a channel), m samples per window on the merged, strictly ascending
+ * t_sample list of the counts groups, and optionally a cross-section sigma_j >= 0 [cm^2 per H atom] at each bin, as the caller's
+ * table gives it for the absorber's redshift (the engine does not shift it).  With h Planck's constant [erg s]:
+ *   nodes        nu_j = sqrt(E_lo_j E_hi_j) keV / h;
+ *   host matrix  A[j][c] = R[c][j] ln(E_hi_j / E_lo_j) / h   [counts s^-1 per erg cm^-2 s^-1 Hz^-1]: the midpoint rule in ln E of
+ *                int_bin N_E dE = int (F_nu / h) d ln E; for F_nu ~ nu^-beta the folded value over the exact one is x / sinh x,
+ *                x = beta ln(E_hi / E_lo) / 2;
+ *   per walker   T_j = exp(-N_H sigma_j), or 1 without sigma (N_H: the free parameter with the slot VAG_P_N_H, else n_h_fixed);
+ *   G[i][j]  = T_j ((exposure_i / m) sum_s F_nu(t_sample[sample_idx[i m + s]], nu_j))   (summed in s order; F_nu the total of every
+ *              enabled component, as for point rows);
+ *   mu[i][c] = B[i][c] + sum_j A[j][c] G[i][j]   (summed in ascending j from 0, one fma per term, B added last; vag::fold_mu);
+ *   ln L += sum_{i,c} w [N ln mu - mu - ln N!],
+ * formed as chi^2 += 2 sum w D(N, mu) + const2 with vag::poisson_deviance and the host-side constant exactly as for counts groups.
+ * mu = 0 with N > 0 and w > 0 scores -inf; mu = 0 with N = 0 adds 0; a NaN model value scores -inf; w = 0 adds nothing whatever
+ * the model value; a walker the pass rejects (grid capacity, ODE rows, SSC tables) scores -inf and is counted in n_walkers_rejected.
+ * Each group is its own pass after the index groups: the n_samples J points (t, nu), t outer and nu inner, as one series request (the
+ * path of the point rows; it goes through in chunks above 512 points), then vag_fit_back_fold_kernel.  The struct carries nu and A,
+ * not the bins and R. */
+#define VAG_FOLD_MAX_BINS 64
+#define VAG_FOLD_MAX_CHANNELS 256
+typedef struct vag_fold_obs {
+    int32_t J;                     /* energy bins, 1 .. VAG_FOLD_MAX_BINS */
+    int32_t C;                     /* channels, 1 .. VAG_FOLD_MAX_CHANNELS */
+    int32_t n;                     /* spectra (rows) */
+    int32_t m;                     /* samples per row */
+    int32_t n_samples;             /* distinct sample times */
+    int32_t pad;
+    const double* nu;              /* [J] strictly ascending, > 0 [Hz] */
+    const double* A;               /* [J * C] A[j][c] >= 0 */
+    const double* sigma;           /* [J] sigma_j >= 0 [cm^2], or NULL: no absorber */
+    const double* t_sample;        /* [n_samples] strictly ascending, > 0 [s] */
+    const int32_t* sample_idx;     /* [n * m] in [0, n_samples) */
+    const double* exposure_over_m; /* [n] exposure_i / m > 0 [s] */
+    const double* counts;          /* [n * C] N[i][c]: non-negative integers carried as doubles, at most 2^53 */
+    const double* background;      /* [n * C] B[i][c] >= 0 */
+    const double* weight;          /* [n * C] w[i][c] >= 0 */
+} vag_fold_obs;
+
+typedef struct vag_fold_fit_spec {
+    int32_t n_groups;
+    int32_t pad;
+    const vag_fold_obs* groups;  /* [n_groups] */
+    double n_h_fixed;            /* N_H [cm^-2] when it is not a free parameter; one N_H serves every group that carries a sigma */
+} vag_fold_fit_spec;
+
+/* vag_loglike_index_batch(_dev) with fold groups, which are passes of their own after the index groups.  With fold NULL or
+ * n_groups == 0 it is exactly that call (the other specs may be NULL as there); the fit spec may then hold no other data.  Refused
+ * with VAG_E_INVALID before the device is touched, the message naming group, row and channel: J, C outside their caps, n < 1, m < 1,
+ * n_samples < 1; a null array; an entry of A, sigma, background or weight that is negative or not finite; counts that are not
+ * non-negative integers <= 2^53; nu that is not finite, > 0 and strictly ascending; t_sample that is not finite, > 0 and strictly
+ * ascending; an index outside [0, n_samples); an exposure_over_m that is not finite and > 0; an n_h_fixed that is negative or not
+ * finite; a free parameter with the slot VAG_P_N_H when no group has sigma ("bad parameter slot").  Results are bitwise
+ * reproducible.  The group arrays stay resident on the device by content hash. */
+int vag_loglike_fold_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                           const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                           const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                           const double* theta, int nb, int ndim, double* out);
+int vag_loglike_fold_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                               const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                               const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                               const double* d_theta, int nb, int ndim, double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

@@ -67,6 +67,8 @@ POL_SLOTS = {"pol_b": 1004, "pol_pi_max": 1005, "pol_b_rvs": 1006, "pol_pi_max_r
 # VAG_P_NOISE_SYS0 + g: the fractional systematic of noise group g (vag_loglike_noise_batch), the parameter "sys_<label>" of a Fitter
 P_NOISE_SYS0, NOISE_MAX_GROUPS = 1008, 8
 NOISE_PREFIX = "sys_"
+# VAG_P_N_H: the absorbing column of the count-spectrum groups (vag_loglike_fold_batch), the parameter "N_H" of a Fitter
+P_N_H = 1016
 
 
 class CentroidObs(C.Structure):  # vag_centroid_obs
@@ -150,6 +152,19 @@ class IndexFitSpec(C.Structure):  # vag_index_fit_spec
     _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(IndexObs))]
 
 
+FOLD_MAX_BINS, FOLD_MAX_CHANNELS = 64, 256  # VAG_FOLD_MAX_BINS, VAG_FOLD_MAX_CHANNELS
+
+
+class FoldObs(C.Structure):  # vag_fold_obs
+    _fields_ = [(n, C.c_int32) for n in ("J", "C", "n", "m", "n_samples", "pad")] + \
+               [(n, C.POINTER(C.c_double)) for n in ("nu", "A", "sigma", "t_sample")] + [("sample_idx", C.POINTER(C.c_int32))] + \
+               [(n, C.POINTER(C.c_double)) for n in ("exposure_over_m", "counts", "background", "weight")]
+
+
+class FoldFitSpec(C.Structure):  # vag_fold_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(FoldObs)), ("n_h_fixed", C.c_double)]
+
+
 class FitSpec(C.Structure):
     _fields_ = [
         ("base", ModelParams), ("ndim", C.c_int32), ("slot", C.c_int32 * 16), ("is_log", C.c_int32 * 16),
@@ -215,6 +230,7 @@ EXPORTS = [
     "vag_sky_polarization_batch", "vag_sky_stokes_image_batch", "vag_loglike_pol_batch", "vag_loglike_pol_batch_dev",
     "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev", "vag_loglike_noise_batch", "vag_loglike_noise_batch_dev",
     "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev", "vag_loglike_index_batch", "vag_loglike_index_batch_dev",
+    "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev",
 ]
 
 _lib = None
@@ -294,6 +310,14 @@ def load():
     lib.vag_loglike_index_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec),
                                                 C.POINTER(PolFitSpec), C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec),
                                                 C.POINTER(CountsFitSpec), C.POINTER(IndexFitSpec), v, C.c_int, C.c_int, v]
+    if hasattr(lib, "vag_loglike_fold_batch"):  # (detected by symbol: VAG_LIB_PATH may name an older build of ABI 13)
+        lib.vag_loglike_fold_batch.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec),
+                                               C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec), C.POINTER(CountsFitSpec),
+                                               C.POINTER(IndexFitSpec), C.POINTER(FoldFitSpec), _dp, C.c_int, C.c_int, _dp]
+        lib.vag_loglike_fold_batch_dev.argtypes = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec),
+                                                   C.POINTER(PolFitSpec), C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec),
+                                                   C.POINTER(CountsFitSpec), C.POINTER(IndexFitSpec), C.POINTER(FoldFitSpec), v, C.c_int,
+                                                   C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -415,6 +415,7 @@ struct vag_ctx {
     DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_noisefit;  // noise groups of the likelihood (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
     DevBuf d_countsfit;  // counts groups of the likelihood (vag_loglike_counts_batch): per group [t_sample | N | B | a | w | idx], see CountsLayout
+    DevBuf d_foldfit;   // fold groups of the likelihood (vag_loglike_fold_batch): per group the block FoldLayout describes
     DevBuf d_indexfit;  // spectral-index groups of the likelihood (vag_loglike_index_batch): per group [t | nu | s | sigma | w | c], see IndexLayout
     DevBuf d_limfit;  // upper-limit rows of the likelihood (vag_loglike_lim_batch): per block [limit | sigma | kind], see LimLayout
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
@@ -470,7 +471,7 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit, h_indexfit;
+    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit, h_indexfit, h_foldfit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
@@ -498,6 +499,9 @@ struct vag_ctx {
     uint64_t indexfit_hash = 0;  // (d_indexfit: the spectral-index groups of vag_loglike_index_batch, upload_index_spec)
     size_t indexfit_doubles = 0;
     bool indexfit_hash_valid = false;
+    uint64_t foldfit_hash = 0;  // (d_foldfit: the fold groups of vag_loglike_fold_batch, upload_fold_spec)
+    size_t foldfit_doubles = 0;
+    bool foldfit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -738,8 +742,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_noisefit.release();
     c->h_countsfit.release();
     c->h_indexfit.release();
+    c->h_foldfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit, &c->d_indexfit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit, &c->d_indexfit, &c->d_foldfit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3568,7 +3573,7 @@ static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
 }
 
 static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false, int noise_groups = 0,
-                           bool counts = false) {
+                           bool counts = false, bool n_h = false) {
     if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
     const int n = spec->n_data;
     if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky && !pol && !counts)) return set_err(VAG_E_INVALID, "fit spec has no data");
@@ -3578,6 +3583,7 @@ static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool 
         if (sky && s >= VAG_P_SKY_PA && s <= VAG_P_SKY_NORTH0) continue;
         if (pol && (s == VAG_P_SKY_PA || (s >= VAG_P_POL_B && s <= VAG_P_POL_PI_MAX_RVS))) continue;
         if (s >= VAG_P_NOISE_SYS0 && s < VAG_P_NOISE_SYS0 + noise_groups) continue;  // (the systematic of a group the noise spec has)
+        if (n_h && s == VAG_P_N_H) continue;  // (the absorbing column of a fold group with a cross-section)
         if (s < 0 || (s >= VAG_P_COUNT && (s < VAG_P_RVS_EPS_E || s > VAG_P_MAG_Q))) return set_err(VAG_E_INVALID, "bad parameter slot");
     }
     if (spec->use_priors)
@@ -4226,6 +4232,127 @@ static int upload_index_spec(vag_ctx* c, const vag_index_fit_spec* is, const std
     return VAG_OK;
 }
 
+// ---- fold groups (vag_loglike_fold_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout in
+//      doubles, per group: [t ns J | nu ns J | A J C | sigma J | exposure / m n | N n C | B n C | w n C], then the sample indices
+//      (int32 [n m] in (n m + 1) / 2 doubles); the first two are the series points (t_sample_s, nu_j), s outer, as prep_times takes
+//      them; sigma is zeros for a group without one (the kernel is handed a null pointer then). ----
+struct FoldLayout {
+    std::vector<long> off;       // where group g starts in d_foldfit
+    std::vector<double> const2;  // -2 sum_{i,c} w S of group g (vag::poisson_const): the walker-independent half of its chi^2
+    bool any_sigma = false;      // some group carries a cross-section: N_H is read
+    int n_groups = 0;
+};
+
+// Validates the fold groups and lays their blocks out in stage (host work only: no context is touched).
+static int fold_scan(const vag_fit_spec* spec, const vag_fold_fit_spec* fs, std::vector<double>& stage, FoldLayout& lay) {
+    if (fs->n_groups < 0 || !fs->groups) return set_err(VAG_E_INVALID, "fold groups: n_groups must be >= 0 with a group list, got %d", fs->n_groups);
+    if (!std::isfinite(fs->n_h_fixed) || fs->n_h_fixed < 0) return set_err(VAG_E_INVALID, "fold groups: n_h_fixed must be finite and >= 0");
+    lay.n_groups = fs->n_groups;
+    lay.off.clear();
+    lay.const2.clear();
+    lay.any_sigma = false;
+    stage.clear();
+    for (int g = 0; g < fs->n_groups; ++g) {
+        const vag_fold_obs& o = fs->groups[g];
+        if (o.J < 1 || o.J > VAG_FOLD_MAX_BINS)
+            return set_err(VAG_E_INVALID, "fold group %d: J (energy bins) must be in 1..%d, got %d", g, VAG_FOLD_MAX_BINS, o.J);
+        if (o.C < 1 || o.C > VAG_FOLD_MAX_CHANNELS)
+            return set_err(VAG_E_INVALID, "fold group %d: C (channels) must be in 1..%d, got %d", g, VAG_FOLD_MAX_CHANNELS, o.C);
+        if (o.n < 1) return set_err(VAG_E_INVALID, "fold group %d has no rows", g);
+        if (o.m < 1) return set_err(VAG_E_INVALID, "fold group %d: m (samples per row) must be >= 1, got %d", g, o.m);
+        if (o.n_samples < 1) return set_err(VAG_E_INVALID, "fold group %d has no sample times", g);
+        if (o.n > (1 << 16) || o.m > (1 << 10) || o.n_samples > (1 << 18))
+            return set_err(VAG_E_INVALID, "fold group %d: more than %d rows, %d samples per row or %d sample times", g, 1 << 16, 1 << 10, 1 << 18);
+        if (!o.nu || !o.A || !o.t_sample || !o.sample_idx || !o.exposure_over_m || !o.counts || !o.background || !o.weight)
+            return set_err(VAG_E_INVALID, "fold group %d: null array", g);
+        for (int j = 0; j < o.J; ++j) {
+            if (!std::isfinite(o.nu[j]) || !(o.nu[j] > 0) || (j > 0 && !(o.nu[j] > o.nu[j - 1])))
+                return set_err(VAG_E_INVALID, "fold group %d, bin %d: frequencies must be finite, > 0 and strictly ascending", g, j);
+            if (o.sigma && (!std::isfinite(o.sigma[j]) || o.sigma[j] < 0))
+                return set_err(VAG_E_INVALID, "fold group %d, bin %d: the cross-section must be finite and >= 0", g, j);
+            for (int ch = 0; ch < o.C; ++ch) {
+                const double a = o.A[(size_t)j * o.C + ch];
+                if (!std::isfinite(a) || a < 0)
+                    return set_err(VAG_E_INVALID, "fold group %d, bin %d, channel %d: the response must be finite and >= 0", g, j, ch);
+            }
+        }
+        for (int j = 0; j < o.n_samples; ++j)
+            if (!std::isfinite(o.t_sample[j]) || !(o.t_sample[j] > 0) || (j > 0 && !(o.t_sample[j] > o.t_sample[j - 1])))
+                return set_err(VAG_E_INVALID, "fold group %d, sample %d: sample times must be finite, > 0 and strictly ascending", g, j);
+        double wS = 0;
+        for (int i = 0; i < o.n; ++i) {
+            if (!std::isfinite(o.exposure_over_m[i]) || !(o.exposure_over_m[i] > 0))
+                return set_err(VAG_E_INVALID, "fold group %d, row %d: exposure_over_m must be finite and > 0", g, i);
+            for (int k = 0; k < o.m; ++k) {
+                const int j = o.sample_idx[(size_t)i * o.m + k];
+                if (j < 0 || j >= o.n_samples)
+                    return set_err(VAG_E_INVALID, "fold group %d, row %d: sample index %d is outside [0, %d)", g, i, j, o.n_samples);
+            }
+            for (int ch = 0; ch < o.C; ++ch) {
+                const size_t at = (size_t)i * o.C + ch;
+                const double N = o.counts[at];
+                if (!std::isfinite(N) || N < 0 || N != std::floor(N))
+                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: counts must be a finite integer >= 0, got %g", g, i, ch, N);
+                if (N > 9007199254740992.0) return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: counts above 2^53", g, i, ch);
+                if (!std::isfinite(o.background[at]) || o.background[at] < 0)
+                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: the background must be finite and >= 0", g, i, ch);
+                if (!std::isfinite(o.weight[at]) || o.weight[at] < 0)
+                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: the weight must be finite and >= 0", g, i, ch);
+                if (o.weight[at] > 0) wS += o.weight[at] * vag::poisson_const(N);
+            }
+        }
+        if (o.sigma) lay.any_sigma = true;
+        const size_t at = stage.size(), J = (size_t)o.J, C = (size_t)o.C, n = (size_t)o.n, ns = (size_t)o.n_samples, nm = n * (size_t)o.m;
+        lay.off.push_back((long)at);
+        lay.const2.push_back(-2.0 * wS);
+        stage.resize(at + 2 * ns * J + J * C + J + n + 3 * n * C + (nm + 1) / 2, 0.0);
+        double* dst = stage.data() + at;
+        for (size_t q = 0; q < ns; ++q)
+            for (size_t j = 0; j < J; ++j) {
+                dst[q * J + j] = o.t_sample[q];
+                dst[ns * J + q * J + j] = o.nu[j];
+            }
+        dst += 2 * ns * J;
+        std::memcpy(dst, o.A, sizeof(double) * J * C);
+        dst += J * C;
+        if (o.sigma) std::memcpy(dst, o.sigma, sizeof(double) * J);
+        dst += J;
+        std::memcpy(dst, o.exposure_over_m, sizeof(double) * n);
+        dst += n;
+        for (const double* src : {o.counts, o.background, o.weight}) {
+            std::memcpy(dst, src, sizeof(double) * n * C);
+            dst += n * C;
+        }
+        std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
+    }
+    // (N_H is read by groups with a cross-section only: without one it is refused as a free parameter, the rule of east0 / north0)
+    if (!lay.any_sigma)
+        for (int d = 0; d < spec->ndim && d < 16; ++d)
+            if (spec->slot[d] == VAG_P_N_H) return set_err(VAG_E_INVALID, "bad parameter slot");
+    return VAG_OK;
+}
+
+static int upload_fold_spec(vag_ctx* c, const vag_fold_fit_spec* fs, const std::vector<double>& stage) {
+    uint64_t h = 1469598103934665603ull;
+    for (int g = 0; g < fs->n_groups; ++g) {  // (the shapes: two groups whose blocks hold the same bytes are still two layouts)
+        const vag_fold_obs& o = fs->groups[g];
+        const int head[6] = {o.J, o.C, o.n, o.m, o.n_samples, o.sigma ? 1 : 0};
+        h = fnv1a(h, head, sizeof head);
+    }
+    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
+    if (c->foldfit_hash_valid && c->foldfit_hash == h && c->foldfit_doubles == stage.size()) return VAG_OK;  // resident already
+    c->foldfit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_foldfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    if (c->d_foldfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    std::memcpy(c->h_foldfit.as<double>(), stage.data(), sizeof(double) * stage.size());
+    HIPCHK(hipMemcpyAsync(c->d_foldfit.p, c->h_foldfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
+    c->foldfit_hash = h;
+    c->foldfit_doubles = stage.size();
+    c->foldfit_hash_valid = true;
+    return VAG_OK;
+}
+
 // ---- one likelihood request.  Every vag_loglike_*_batch entry point fills a FitRequest from its arguments (a spec it does not take
 //      stays null) and calls loglike_dev or loglike_host; a request whose optional blocks are null or empty is therefore the narrower
 //      entry point's request, statement for statement. ----
@@ -4233,17 +4360,19 @@ namespace {
 struct FitRequest {
     const vag_fit_spec* spec = nullptr;
     const vag_sky_fit_spec* sky = nullptr;      // after fit_request_prepare: null when nothing reads the placement
-    const vag_vis_fit_spec* vis = nullptr;      // after fit_request_prepare: null when it has no group; so pol, counts, index
+    const vag_vis_fit_spec* vis = nullptr;      // after fit_request_prepare: null when it has no group; so pol, counts, index, fold
     const vag_pol_fit_spec* pol = nullptr;
     const vag_limit_fit_spec* lim = nullptr;    // after fit_request_prepare: null when no row is a limit (llay.any)
     const vag_noise_fit_spec* noise = nullptr;  // after fit_request_prepare: null when no row is grouped (nlay.any)
     const vag_counts_fit_spec* counts = nullptr;
     const vag_index_fit_spec* index = nullptr;
+    const vag_fold_fit_spec* fold = nullptr;
     LimLayout llay;
     NoiseLayout nlay;
     CountsLayout clay;
     IndexLayout ilay;
-    std::vector<double> lstage, nstage, cstage, istage;  // what the scans lay out for upload_{lim,noise,counts,index}_spec
+    FoldLayout flay;
+    std::vector<double> lstage, nstage, cstage, istage, fstage;  // what the scans lay out for upload_{lim,noise,counts,index,fold}_spec
     bool placed = false;                                 // some group reads east0 / north0
     bool prepared = false;                               // fit_request_prepare has run
 };
@@ -4255,7 +4384,9 @@ static int fit_request_prepare(FitRequest& r) {
     if (r.vis && r.vis->n_groups == 0) r.vis = nullptr;
     if (r.counts && r.counts->n_groups == 0) r.counts = nullptr;
     if (r.index && r.index->n_groups == 0) r.index = nullptr;
+    if (r.fold && r.fold->n_groups == 0) r.fold = nullptr;
     int rc = VAG_OK;
+    if (r.fold && (rc = fold_scan(r.spec, r.fold, r.fstage, r.flay))) return rc;
     if (r.index && (rc = index_scan(r.index, r.istage, r.ilay))) return rc;
     if (r.counts && (rc = counts_scan(r.counts, r.cstage, r.clay))) return rc;
     if (r.noise && (rc = noise_scan(r.spec, r.noise, r.nstage, r.nlay))) return rc;
@@ -4310,8 +4441,9 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     };
     const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = req.vis ? req.vis->n_groups : 0;
     const int n_pol_groups = req.pol ? req.pol->n_groups : 0, n_counts_groups = req.counts ? req.counts->n_groups : 0;
-    const int n_index_groups = req.index ? req.index->n_groups : 0;
-    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups + n_counts_groups + n_index_groups;
+    const int n_index_groups = req.index ? req.index->n_groups : 0, n_fold_groups = req.fold ? req.fold->n_groups : 0;
+    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups + n_counts_groups + n_index_groups +
+                       n_fold_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // what the current pass's back kernel receives (built at its launch: the model stages may have moved the buffers); the SSC tables
     // of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
@@ -4496,6 +4628,34 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
             rc = end_pass();
         }
     }
+    for (int g = 0; g < n_fold_groups && rc == VAG_OK; ++g) {  // fold groups: the n_samples J points as one series request each, then the folded Poisson term
+        const vag_fold_obs& o = req.fold->groups[g];
+        const double* df = c->d_foldfit.as<double>() + req.flay.off[g];  // [t ns J | nu ns J | A | sigma | exposure / m | N | B | w | idx]
+        const size_t J = (size_t)o.J, nc = (size_t)o.n * (size_t)o.C, np = (size_t)o.n_samples * J;
+        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(np, (size_t)std::max(n, 1)))) return VAG_E_HIP;
+        rc = prep_times(c, df, (int)np, df + np, (int)np);
+        begin_pass();
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
+        if (rc == VAG_OK) {
+            int shared = 0;  // J <= 8 distinct frequencies: the shared-node path of a short series
+            if (np <= (size_t)FITROWS_MAX_POINTS) {
+                double nu_pts[FITROWS_MAX_POINTS];
+                for (size_t i = 0; i < np; ++i) nu_pts[i] = o.nu[i % J];
+                shared = upload_series_bands(c, nu_pts, (int)np);
+            }
+            rc = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), shared);  // (in chunks above 512 points)
+        }
+        if (rc == VAG_OK) {
+            const double* dA = df + 2 * np;
+            const double* dsig = dA + J * (size_t)o.C;
+            const double* deom = dsig + J;
+            const double* dN = deom + o.n;
+            hipLaunchKernelGGL(vag_fit_back_fold_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n_samples, o.J, o.C,
+                               o.n, o.m, reinterpret_cast<const int*>(dN + 3 * nc), dA, o.sigma ? dsig : nullptr, deom, dN, dN + nc,
+                               dN + 2 * nc, req.flay.const2[g], d_theta, ndim, d_prior, req.fold->n_h_fixed, fit_pass(), next_order());
+            rc = end_pass();
+        }
+    }
     c->ic_soft_fail = false;
     c->plan.n_models_capacity = n_cap;
     c->plan.n_models_invalid = n_inv;
@@ -4521,7 +4681,8 @@ static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int n
     if (!req.spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
     if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
     HIPCHK(hipSetDevice(c->device));
-    rc = upload_fit_spec(c, req.spec, ndim, req.placed, req.pol != nullptr, req.noise ? req.nlay.n_groups : 0, req.counts || req.index);
+    rc = upload_fit_spec(c, req.spec, ndim, req.placed, req.pol != nullptr, req.noise ? req.nlay.n_groups : 0,
+                         req.counts || req.index || req.fold, req.fold && req.flay.any_sigma);
     if (rc == VAG_OK && req.sky) rc = upload_sky_spec(c, req.sky);  // (n_groups = 0: the fixed placement alone)
     if (rc == VAG_OK && req.vis) rc = upload_vis_spec(c, req.vis);
     if (rc == VAG_OK && req.pol) rc = upload_pol_spec(c, req.pol);
@@ -4529,6 +4690,7 @@ static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int n
     if (rc == VAG_OK && req.noise) rc = upload_noise_spec(c, req.nstage, req.nlay);
     if (rc == VAG_OK && req.counts) rc = upload_counts_spec(c, req.counts, req.cstage, req.clay);
     if (rc == VAG_OK && req.index) rc = upload_index_spec(c, req.index, req.istage);
+    if (rc == VAG_OK && req.fold) rc = upload_fold_spec(c, req.fold, req.fstage);
     if (rc) return rc;
     rc = loglike_body(c, req, d_theta, nb, ndim, d_out, !c->count_work);
     if (rc == VAG_RETRY) rc = loglike_body(c, req, d_theta, nb, ndim, d_out, false);
@@ -4561,9 +4723,9 @@ static int loglike_host(vag_ctx* c, FitRequest& req, const double* theta, int nb
 static FitRequest fit_request(const vag_fit_spec* spec, const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
                               const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr,
                               const vag_noise_fit_spec* noise = nullptr, const vag_counts_fit_spec* counts = nullptr,
-                              const vag_index_fit_spec* index = nullptr) {
+                              const vag_index_fit_spec* index = nullptr, const vag_fold_fit_spec* fold = nullptr) {
     FitRequest r;
-    r.spec = spec, r.sky = sky, r.vis = vis, r.pol = pol, r.lim = lim, r.noise = noise, r.counts = counts, r.index = index;
+    r.spec = spec, r.sky = sky, r.vis = vis, r.pol = pol, r.lim = lim, r.noise = noise, r.counts = counts, r.index = index, r.fold = fold;
     return r;
 }
 
@@ -4616,6 +4778,14 @@ int vag_loglike_index_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_
                                 const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* d_theta, int nb,
                                 int ndim, double* d_out) {
     FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
+}
+
+int vag_loglike_fold_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                               const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                               const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                               const double* d_theta, int nb, int ndim, double* d_out) {
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold);
     return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
@@ -4925,6 +5095,14 @@ int vag_loglike_index_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_
                             const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const double* theta, int nb, int ndim,
                             double* out) {
     FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index);
+    return loglike_host(c, r, theta, nb, ndim, out);
+}
+
+int vag_loglike_fold_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                           const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                           const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                           const double* theta, int nb, int ndim, double* out) {
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold);
     return loglike_host(c, r, theta, nb, ndim, out);
 }
 

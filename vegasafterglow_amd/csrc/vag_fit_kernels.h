@@ -1,8 +1,9 @@
 // vag_fit_kernels.h -- the kernels of a likelihood call (vag_loglike_*_batch): its front, the back kernel of every kind of pass, and
 // the walkers' polarization spec.  A call is one front launch and then one pass per block of data -- the point rows, every band,
-// centroid, visibility, polarization, counts and spectral-index group -- each pass a model request followed by its back kernel, one
+// centroid, visibility, polarization, counts, spectral-index and fold group -- each pass a model request followed by its back kernel, one
 // wavefront per walker.  What the back kernels share is the pass protocol below: FitPass and the two helpers.
 #pragma once
+#include "vag_fold.h"
 #include "vag_ic_kernels.h"
 #include "vag_index.h"
 #include "vag_kernels.h"
@@ -309,6 +310,63 @@ vag_fit_back_index_kernel(const double* __restrict__ flux /* [nb][n K] */, int n
         }
     }
     s = wave_sum(s);
+    fit_close_pass(pass, m, lane, grid_ok, false, s);
+}
+
+// The back of a fold pass (vag_loglike_fold_batch).  flux [nb][ns J] holds the walker's flux density at the group's points
+// (t_sample_s, nu_j), s outer.  The walker's N_H is the free parameter with the slot VAG_P_N_H (found as sky_placement finds pa), else
+// n_h_fixed; lane j < J keeps T_j = exp(-N_H sigma_j) (1 without sigma).  Row after row: lane j gathers its bin's m samples in s
+// order and writes G[i][j] = T_j ((exposure_i / m) sum) to the LDS row; after the barrier the lanes stride the channels, lane c
+// running j = 0 .. J-1 over the LDS broadcast and A[j][c] (fold_mu: the wavefront's loads of A are consecutive in c), and adds
+// w D(N, mu) (poisson_deviance) to its sum; a channel with w = 0 adds nothing.  The second barrier keeps the next row's writes behind
+// this row's reads.  The lanes' sums are closed by wave_sum in the fixed order of the other back kernels, so the value depends on
+// the walker's own row of flux alone.  The pass adds 2 sum w D + const2 to chi^2, const2 the walker-independent half the host
+// formed (fold_scan).  One wavefront per block: the barriers are wave-uniform (grid_ok and the row loop are).
+__global__ void __launch_bounds__(64)
+vag_fit_back_fold_kernel(const double* __restrict__ flux /* [nb][ns J] */, int ns, int J, int C, int n, int mm,
+                         const int* __restrict__ idx /* [n][mm] */, const double* __restrict__ A /* [J][C] */,
+                         const double* __restrict__ sigma /* [J] or null */, const double* __restrict__ eom /* [n] exposure / m */,
+                         const double* __restrict__ counts /* [n][C] */, const double* __restrict__ background,
+                         const double* __restrict__ weight, double const2, const double* __restrict__ theta /* [nb][ndim] */, int ndim,
+                         const double* __restrict__ prior, double n_h_fixed, FitPass pass, FitOrderOut ord) {
+    __shared__ double s_g[FOLD_MAX_BINS];
+    const int m = blockIdx.x, lane = threadIdx.x;
+    const bool grid_ok = pass.meta[m].status == 0;
+    fit_hand_over_order(pass, ord, m, lane);
+    double s = 0;
+    if (grid_ok) {
+        double T = 1.0;
+        if (sigma != nullptr && lane < J) {
+            const int walker = pass.order ? pass.order[m] : m;
+            const int* slot = reinterpret_cast<const int*>(prior + 64);
+            const int* is_log = slot + 16;
+            double nh = n_h_fixed;
+            for (int d = 0; d < ndim; ++d) {
+                if (slot[d] != VAG_P_N_H) continue;
+                const double v = theta[(size_t)walker * ndim + d];
+                nh = is_log[d] ? pow(10.0, v) : v;
+            }
+            T = exp(-(nh * sigma[lane]));
+        }
+        const double* f = flux + (size_t)m * ns * J;
+        for (int i = 0; i < n; ++i) {
+            if (lane < J) {
+                const int* ix = idx + (size_t)i * mm;
+                double sum = 0;
+                for (int k = 0; k < mm; ++k) sum += f[(size_t)ix[k] * J + lane];
+                s_g[lane] = T * (eom[i] * sum);
+            }
+            __syncthreads();
+            for (int c = lane; c < C; c += 64) {
+                const size_t at = (size_t)i * C + c;
+                const double w = weight[at];
+                if (w == 0.0) continue;
+                s += w * poisson_deviance(counts[at], fold_mu(background[at], A + c, C, s_g, J));
+            }
+            __syncthreads();
+        }
+    }
+    s = 2.0 * wave_sum(s) + const2;
     fit_close_pass(pass, m, lane, grid_ok, false, s);
 }
 

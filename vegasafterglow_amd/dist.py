@@ -29,6 +29,8 @@ _NO_COUNTS = ("sharded likelihood calls do not support photon counts (Fitter.add
               "(Fitter.device_evaluator / log_prob_batch)")
 _NO_INDEX = ("sharded likelihood calls do not support spectral indices (Fitter.add_spectral_index): evaluate on one device "
              "(Fitter.device_evaluator / log_prob_batch)")
+_NO_FOLD = ("sharded likelihood calls do not support count spectra (Fitter.add_count_spectrum): evaluate on one device "
+            "(Fitter.device_evaluator / log_prob_batch)")
 
 
 def shard_range(n, rank, world):
@@ -111,6 +113,8 @@ class WalkerSharder:
             raise NotImplementedError(_NO_COUNTS)
         if getattr(eval_dev, "has_spectral_indices", False):
             raise NotImplementedError(_NO_INDEX)
+        if getattr(eval_dev, "has_count_spectra", False):
+            raise NotImplementedError(_NO_FOLD)
         self.eval_dev, self.group = eval_dev, group
         self.device = device if device is not None else _default_device(group)
         self.native = getattr(eval_dev, "native", None)
@@ -219,6 +223,8 @@ def sharded_loglike(samples, local_eval, group=None, device=None):
         raise NotImplementedError(_NO_COUNTS)
     if getattr(getattr(local_eval, "__self__", None), "has_spectral_indices", False):
         raise NotImplementedError(_NO_INDEX)
+    if getattr(getattr(local_eval, "__self__", None), "has_count_spectra", False):
+        raise NotImplementedError(_NO_FOLD)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     nb = samples.shape[0]
     if not (dist.is_available() and dist.is_initialized()):

@@ -173,13 +173,66 @@ def index_from_slope(slope, convention):
     raise ValueError(f"unknown spectral-index convention {convention!r}: one of {INDEX_CONVENTIONS}")
 
 
+def _widest_entry(lib, spec, suffix):
+    """The widest likelihood entry point of the loaded library and its trailing spec arguments: vag_loglike_fold_batch<suffix>, added
+    after ABI 13 and detected by symbol.  A library without it (VAG_LIB_PATH naming an older build) serves every fit without count
+    spectra through vag_loglike_index_batch<suffix>, the same call bit for bit; a fit with count spectra is an error there."""
+    name = "vag_loglike_fold_batch" + suffix
+    if hasattr(lib, name):
+        return getattr(lib, name), (C.byref(spec._fold) if spec._fold is not None else None,)
+    if spec._fold is not None:
+        raise RuntimeError(f"the loaded library has no {name}: count spectra (Fitter.add_count_spectrum) need a newer build")
+    return getattr(lib, "vag_loglike_index_batch" + suffix), ()
+
+
+def _poisson_const(N):
+    """S(N) = N ln N - N - ln N! per entry (0 for N = 0), as vag::poisson_const forms it: Stirling's remainder series from N = 16 on
+    (no difference of large numbers), the three-term difference below."""
+    N = np.asarray(N, dtype=np.float64)
+    big = N >= 16
+    i = 1.0 / np.where(big, N, 1.0)
+    i2 = i * i
+    series = i * (1 / 12 + i2 * (-1 / 360 + i2 * (1 / 1260 + i2 * (-1 / 1680 + i2 * (1 / 1188 + i2 * (-691 / 360360))))))
+    out = np.where(big, -(0.5 * np.log(2 * np.pi * np.where(big, N, 1.0)) + series), 0.0)
+    small = (N > 0) & ~big
+    if small.any():
+        out[small] = [n * math.log(n) - n - math.lgamma(n + 1.0) for n in N[small]]
+    return out
+
+
+def fold_expected(F, group, n_h=0.0):
+    """The expected counts mu [..., n, C] of a count-spectrum group (an entry of Fitter._fold_obs) on model flux densities
+    F [..., n_samples * J] at the group's points (t_sample_s, nu_j), s outer -- the numpy statement of the fold term:
+        G[i][j]  = T_j ((exposure_i / m) sum_s F[sample_idx[i][s]][j])   (summed in s order), T_j = exp(-N_H sigma_j) or 1,
+        mu[i][c] = B[i][c] + sum_j A[j][c] G[i][j]                       (summed in ascending j from 0, B added last).
+    n_h: a scalar or an array of the leading shape of F; not read by a group without absorption."""
+    gd = group
+    J, ns, n = gd["nu"].size, gd["t_sample"].size, gd["exposure_over_m"].size
+    F = np.asarray(F, dtype=np.float64)
+    if F.shape[-1] != ns * J:
+        raise ValueError(f"fold_expected: F must hold n_samples * J = {ns * J} values along its last axis, got {F.shape}")
+    F = F.reshape(F.shape[:-1] + (ns, J))
+    with np.errstate(all="ignore"):
+        total = np.zeros(F.shape[:-2] + (n, J))
+        for k in range(gd["m"]):
+            total = total + F[..., gd["sample_idx"][:, k], :]
+        G = gd["exposure_over_m"][:, None] * total
+        if gd["sigma"] is not None:
+            T = np.exp(-(np.asarray(n_h, dtype=np.float64)[..., None] * gd["sigma"]))
+            G = T[..., None, :] * G
+        acc = np.zeros(F.shape[:-2] + (n, gd["A"].shape[1]))
+        for j in range(J):
+            acc = acc + gd["A"][j] * G[..., j, None]
+        return gd["background"] + acc
+
+
 class Fitter:
     """Fitter(*, z=0.0, lumi_dist=1e26, jet=..., medium=..., resolution=..., rtol=...): keyword-only with the reference's
     defaults (fitter.py:96-135)."""
 
     def __init__(self, *, z=0.0, lumi_dist=1e26, jet="tophat", medium="ism", resolution=None, rtol=1e-6,
                  radiative_fireball=True, device=0, fwd_ssc=False, kn=False, rvs_shock=False, rvs_ssc=False,
-                 magnetar=False, extinction=None):
+                 magnetar=False, extinction=None, n_h=0.0):
         # extinction: k(lambda_rest [cm]) -> A_lambda / A_V of the host-galaxy law (a callable; fitter.py:379-397).  The
         # point-data model fluxes are scaled by exp(-A_V * 0.4 ln10 * k) with A_V a (free or fixed) parameter.
         # A name selects a built-in Pei92 law; a custom callable is evaluated ONCE per data set (it must not depend on the
@@ -192,6 +245,10 @@ class Fitter:
         elif extinction is not None and not callable(extinction):
             raise ValueError("extinction must be None, 'smc' / 'lmc' / 'mw', or a callable k(lambda_rest_cm)")
         self.extinction = extinction
+        # n_h: the absorbing column N_H [cm^-2] of the count-spectrum groups with absorption=... when N_H is not a parameter
+        if not np.isfinite(n_h) or n_h < 0:
+            raise ValueError(f"n_h must be finite and >= 0, got {n_h!r}")
+        self.n_h = float(n_h)
         self.magnetar = bool(magnetar)
         if rvs_ssc and not rvs_shock:
             rvs_ssc = False  # the reference only builds rvs_rad when rvs_shock is on (fitter.py:476-484)
@@ -217,6 +274,7 @@ class Fitter:
         self._pol_obs = []  # polarization groups (add_polarization): one vag_polarization_obs each
         self._counts_obs = []  # photon-count groups (add_counts): one vag_counts_obs each
         self._index_obs = []  # spectral-index groups (add_spectral_index): one vag_index_obs each
+        self._fold_obs = []  # count-spectrum groups (add_count_spectrum): one vag_fold_obs each
         self._ext_kernel = None
         self._ext_kernels = {}  # z -> 0.4 ln10 k(lambda_rest) over the consolidated point data
         self._ext_z = float(z)
@@ -502,6 +560,106 @@ class Fitter:
         """Some data are spectral indices (add_spectral_index)."""
         return bool(self._index_obs)
 
+    def add_count_spectrum(self, energy_lo, energy_hi, response, t_start, exposure, counts, background=0.0, num_exposure_points=1,
+                           weights=None, absorption=None):
+        """Counts per detector channel of n spectra, compared with the model photon spectrum folded through the instrument
+        response -- a Poisson likelihood (the Cash statistic) per row and channel.
+        energy_lo, energy_hi [J]: the energy bins [keV, observer frame], 0 < lo < hi, ascending and non-overlapping (gaps are
+        allowed), J <= 64.  response [C][J] >= 0 [cm^2]: counts in channel c per photon cm^-2 arriving in bin j (effective area x
+        redistribution, rebinned to these bins, any fixed Galactic absorption folded in), C <= 256.  Row i observed counts[i][c] during
+        [t_start[i], t_start[i] + exposure[i]] [s]; background [counts] and weights broadcast from a scalar, [C] or [n][C]; a weight of
+        0 ignores a channel.  absorption [J]: a cross-section sigma_j >= 0 [cm^2 per H atom] at each bin, as the caller's table gives
+        it for the absorber's redshift; the model is then multiplied by exp(-N_H sigma_j), N_H [cm^-2] the parameter "N_H" (free,
+        fixed, or Fitter(n_h=...)), one N_H for all groups with absorption.  The expected counts are
+            mu[i][c] = background[i][c] + sum_j A[j][c] T_j (exposure_i / m) sum_s F_nu(t_s, nu_j),
+        nu_j = sqrt(lo_j hi_j) keV / h, A[j][c] = response[c][j] ln(hi_j / lo_j) / h (the midpoint rule in ln E of the photon
+        spectrum over the bin), the m = num_exposure_points samples of a window and the merged sample list as in add_counts.  The
+        term adds w [N ln mu - mu - ln N!] to ln L.  Each group is one flux-density request at its n_samples J points.  Nothing is
+        recorded when the call raises."""
+        who = "add_count_spectrum"
+        from . import units
+        lo, hi = (np.asarray(a, dtype=np.float64) for a in (energy_lo, energy_hi))
+        if lo.ndim != 1 or lo.size == 0 or lo.shape != hi.shape:
+            raise ValueError(f"{who}: energy_lo and energy_hi must be non-empty 1-D arrays of one shape; got {lo.shape}, {hi.shape}")
+        if lo.size > _lib.FOLD_MAX_BINS:
+            raise ValueError(f"{who}: energy_lo holds {lo.size} bins, at most {_lib.FOLD_MAX_BINS} are supported")
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (lo <= 0).any() or (hi <= lo).any():
+            raise ValueError(f"{who}: energy_lo and energy_hi must be finite with 0 < energy_lo < energy_hi in every bin")
+        if (lo[1:] < hi[:-1]).any():
+            raise ValueError(f"{who}: the bins of energy_lo / energy_hi must be ascending and must not overlap")
+        J = lo.size
+        R = np.asarray(response, dtype=np.float64)
+        if R.ndim != 2 or R.shape[1] != J or R.shape[0] == 0:
+            raise ValueError(f"{who}: response must be [channels][{J} bins], got {R.shape}")
+        if R.shape[0] > _lib.FOLD_MAX_CHANNELS:
+            raise ValueError(f"{who}: response holds {R.shape[0]} channels, at most {_lib.FOLD_MAX_CHANNELS} are supported")
+        if not np.isfinite(R).all() or (R < 0).any():
+            raise ValueError(f"{who}: response must be finite and >= 0")
+        nC = R.shape[0]
+        if int(num_exposure_points) != num_exposure_points or num_exposure_points < 1:
+            raise ValueError(f"{who}: num_exposure_points must be an integer >= 1, got {num_exposure_points!r}")
+        m = int(num_exposure_points)
+        t0, expo, N = (np.asarray(a, dtype=np.float64) for a in (t_start, exposure, counts))
+        if t0.ndim != 1 or t0.size == 0:
+            raise ValueError(f"{who}: t_start must be a non-empty 1-D array")
+        if expo.shape != t0.shape:
+            raise ValueError(f"{who}: t_start and exposure must have the same shape; got {t0.shape}, {expo.shape}")
+        if N.shape != (t0.size, nC):
+            raise ValueError(f"{who}: counts must be [{t0.size} rows][{nC} channels], got {N.shape}")
+        if not np.isfinite(t0).all() or (t0 <= 0).any():
+            raise ValueError(f"{who}: t_start must be finite and > 0 at every row")
+        if not np.isfinite(expo).all() or (expo <= 0).any():
+            raise ValueError(f"{who}: exposure must be finite and > 0 at every row")
+        if not np.isfinite(N).all() or (N < 0).any() or (N != np.floor(N)).any():
+            raise ValueError(f"{who}: counts must be finite integers >= 0")
+        if (N > 2.0 ** 53).any():
+            raise ValueError(f"{who}: counts above 2^53 are not supported")
+
+        def per_channel(value, name):
+            a = np.asarray(value, dtype=np.float64)
+            if a.ndim != 0 and a.shape != (nC,) and a.shape != N.shape:
+                raise ValueError(f"{who}: {name} must be a scalar, [{nC} channels] or [{t0.size} rows][{nC} channels], got {a.shape}")
+            return np.broadcast_to(a, N.shape).copy()
+        bkg = per_channel(background, "background")
+        if not np.isfinite(bkg).all() or (bkg < 0).any():
+            raise ValueError(f"{who}: background must be finite and >= 0")
+        w = per_channel(1.0 if weights is None else weights, "weights")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError(f"{who}: weights must be finite and >= 0")
+        sigma = None
+        if absorption is not None:
+            sigma = np.asarray(absorption, dtype=np.float64)
+            if sigma.shape != lo.shape or not np.isfinite(sigma).all() or (sigma < 0).any():
+                raise ValueError(f"{who}: absorption must be [{J} bins], finite and >= 0, got shape {sigma.shape}")
+        with np.errstate(over="ignore"):
+            if m == 1:
+                times = (t0 + 0.5 * expo)[:, None]
+            else:
+                times = t0[:, None] + np.arange(m, dtype=np.float64)[None, :] * (expo / float(m - 1))[:, None]
+        if not np.isfinite(times).all():
+            raise ValueError(f"{who}: t_start + exposure must be finite")
+        t_sample, inverse = np.unique(times.ravel(), return_inverse=True)  # ascending, equal times once
+        eom = expo / float(m)
+        if not np.isfinite(eom).all() or (eom <= 0).any():
+            raise ValueError(f"{who}: exposure / num_exposure_points must be finite and > 0 at every row")
+        nu = np.sqrt(lo * hi) * units.keV
+        with np.errstate(over="ignore"):
+            A = (R * (np.log(hi / lo) / units._PLANCK_ERG_S)[None, :]).T
+        if not (np.isfinite(nu).all() and (np.diff(nu) > 0).all() and (nu > 0).all()):
+            raise ValueError(f"{who}: the bins of energy_lo / energy_hi do not give distinct, finite nodes sqrt(lo hi)")
+        if not np.isfinite(A).all():
+            raise ValueError(f"{who}: response * ln(energy_hi / energy_lo) / h must be finite")
+        c = np.ascontiguousarray
+        self._fold_obs.append(dict(energy_lo=c(lo), energy_hi=c(hi), response=c(R), nu=c(nu), A=c(A), sigma=None if sigma is None else c(sigma),
+                                   m=m, t_sample=c(t_sample), sample_idx=c(inverse.reshape(t0.size, m), dtype=np.int32),
+                                   exposure_over_m=c(eom), counts=c(N), background=c(bkg), weights=c(w),
+                                   const2=float(-2.0 * np.sum(np.where(w > 0, w * _poisson_const(N), 0.0)))))
+
+    @property
+    def has_count_spectra(self):
+        """Some data are count spectra (add_count_spectrum)."""
+        return bool(self._fold_obs)
+
     def add_centroid(self, nu, t, east, north, err_east, err_north, weights=None):
         """VLBI centroid positions at one frequency nu [Hz]: offsets east / north of a reference position and their errors [rad]
         (units.mas converts) at ascending times t [s].  The group is its own request: the model centroid at (t_i, nu) is
@@ -667,9 +825,10 @@ class Fitter:
         if self._all_t is not None:
             return
         if not self._point_t:
-            if not (self._band_obs or self._centroid_obs or self._vis_obs or self._pol_obs or self._counts_obs or self._index_obs):
+            if not (self._band_obs or self._centroid_obs or self._vis_obs or self._pol_obs or self._counts_obs or self._index_obs
+                    or self._fold_obs):
                 raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities, add_polarization, "
-                                 "add_counts or add_spectral_index first")
+                                 "add_counts, add_spectral_index or add_count_spectrum first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
             self._all_lim = self._all_grp = None
             return
@@ -770,7 +929,7 @@ class Fitter:
         # duration aliases ...) go straight into their slot, exactly like a free parameter would
         base_fields = (C.c_double * 40).from_address(C.addressof(spec.base) + _lib.ModelParams.theta_c.offset)
         for name, value in fixed.items():
-            if name in MODEL_PARAM_DEFAULTS or name == "A_V" or name in _lib.SKY_SLOTS or name in _lib.POL_SLOTS:
+            if name in MODEL_PARAM_DEFAULTS or name in ("A_V", "N_H") or name in _lib.SKY_SLOTS or name in _lib.POL_SLOTS:
                 continue
             if self._noise_id(name) is not None:  # (goes into vag_noise_fit_spec.sys_fixed)
                 continue
@@ -781,6 +940,8 @@ class Fitter:
         for d, pd in enumerate(free):
             if pd.name == "A_V":
                 spec.slot[d] = _lib.P_A_V
+            elif pd.name == "N_H":
+                spec.slot[d] = _lib.P_N_H
             elif pd.name in _lib.SKY_SLOTS:
                 spec.slot[d] = _lib.SKY_SLOTS[pd.name]
             elif pd.name in _lib.POL_SLOTS:
@@ -805,6 +966,8 @@ class Fitter:
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
         spec._index = self._index_spec(z_eff) if self._index_obs else None
+        self._check_n_h_parameter(param_defs)
+        spec._fold = self._fold_spec(fixed) if self._fold_obs else None
         if self.extinction is not None and self._all_t.size and z_eff != self._ext_z:
             # a fixed 'z' ParamDef overrides Fitter.z in the model: the rest-frame wavelengths of the law must follow it.  One
             # kernel per z, all kept for the Fitter's lifetime: earlier specs (a device_evaluator's closure) still point at theirs
@@ -878,6 +1041,38 @@ class Fitter:
         cs.n_groups, cs.groups = len(self._counts_obs), groups
         cs._keep_alive = (groups, list(self._counts_obs))
         return cs
+
+    def _check_n_h_parameter(self, param_defs):
+        """N_H is read by count-spectrum groups with absorption only; a fixed one is >= 0, a free one has lower >= 0."""
+        for pd in param_defs:
+            if pd.name != "N_H":
+                continue
+            if not any(gd["sigma"] is not None for gd in self._fold_obs):
+                raise ValueError("the parameter 'N_H' needs count spectra with a cross-section (Fitter.add_count_spectrum(..., "
+                                 "absorption=...))")
+            if pd.scale is Scale.fixed:
+                value = pd.initial if pd.initial is not None else pd.lower
+                if not np.isfinite(value) or value < 0:
+                    raise ValueError(f"a fixed N_H must be finite and >= 0, got {value!r}")
+            elif not pd.lower >= 0:
+                raise ValueError(f"N_H: a free column needs lower >= 0, got lower={pd.lower!r}")
+
+    def _fold_spec(self, fixed):
+        """vag_fold_fit_spec of the count-spectrum groups and the fixed N_H; it keeps the arrays it points at alive."""
+        fs = _lib.FoldFitSpec()
+        groups = (_lib.FoldObs * len(self._fold_obs))()
+        for g, gd in enumerate(self._fold_obs):
+            o = groups[g]
+            o.J, o.C, o.n, o.m, o.n_samples = gd["nu"].size, gd["A"].shape[1], gd["exposure_over_m"].size, gd["m"], gd["t_sample"].size
+            for name in ("nu", "A", "t_sample", "exposure_over_m", "counts", "background"):
+                setattr(o, name, gd[name].ctypes.data_as(_dp))
+            o.sigma = gd["sigma"].ctypes.data_as(_dp) if gd["sigma"] is not None else None
+            o.sample_idx = gd["sample_idx"].ctypes.data_as(C.POINTER(C.c_int32))
+            o.weight = gd["weights"].ctypes.data_as(_dp)
+        fs.n_groups, fs.groups = len(self._fold_obs), groups
+        fs.n_h_fixed = float(fixed.get("N_H", self.n_h))
+        fs._keep_alive = (groups, list(self._fold_obs))
+        return fs
 
     def _index_ext_slope(self, gd, z):
         """ext_slope of a spectral-index group at redshift z: sum_{k >= 1} c_k (kappa_k - kappa_0), kappa = 0.4 ln10 k(lambda_rest),
@@ -1093,6 +1288,30 @@ class Fitter:
             out.append(index_from_slope(slope, gd["convention"]))
         return out
 
+    def count_spectra(self, best_params, param_defs, resolution=None):
+        """The expected counts mu [n][C] of every count-spectrum group at a point of sampler space: a list of float64 arrays, one per
+        group.  Each group is one vag_flux_density_batch request at its n_samples J points (t_sample_s, nu_j), s outer, and
+        fold_expected on the result with the sample's N_H -- the likelihood's own request and arithmetic (its flux may differ from
+        this call's in the last bits)."""
+        p, _ = self._params_at(best_params, param_defs, resolution)
+        spec, _, _ = self.build_spec(param_defs)
+        sample = np.asarray(best_params, dtype=np.float64).reshape(-1)
+        n_h = spec._fold.n_h_fixed if spec._fold is not None else self.n_h
+        for d in range(spec.ndim):
+            if spec.slot[d] == _lib.P_N_H:
+                n_h = 10.0 ** sample[d] if spec.is_log[d] else sample[d]
+        h, lock = get_context(self.device)
+        out = []
+        for gd in self._fold_obs:
+            ns, J = gd["t_sample"].size, gd["nu"].size
+            ts, nus = np.ascontiguousarray(np.repeat(gd["t_sample"], J)), np.ascontiguousarray(np.tile(gd["nu"], ns))
+            flux = np.empty(ns * J)
+            with lock:
+                _lib.check(_lib.load().vag_flux_density_batch(h, C.byref(p), 1, ts.ctypes.data_as(_dp), nus.ctypes.data_as(_dp), ns * J,
+                                                              flux.ctypes.data_as(_dp)))
+            out.append(fold_expected(flux, gd, n_h))
+        return out
+
     def visibilities(self, best_params, param_defs, resolution=None):
         """The model visibilities at the data of every visibility group at a point of sampler space: a list of complex128 arrays,
         one per group, in the order and layout the data were added.  Each group is one Model.sky_visibilities request at the
@@ -1125,7 +1344,7 @@ class Fitter:
         if len(set(names)) != len(names):
             raise ValueError("duplicate parameter names")
         for pd in param_defs:
-            if pd.name != "A_V" and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS and pd.name not in _lib.POL_SLOTS \
+            if pd.name not in ("A_V", "N_H") and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS and pd.name not in _lib.POL_SLOTS \
                     and not pd.name.startswith(_lib.NOISE_PREFIX):  # (sys_<label>: _check_noise_parameters below)
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             if pd.scale is Scale.fixed:
@@ -1138,6 +1357,7 @@ class Fitter:
             raise ValueError("A_V needs Fitter(extinction=...)")
         self._check_pol_parameters(names)
         self._check_noise_parameters(param_defs)
+        self._check_n_h_parameter(param_defs)
 
     def _params_at(self, sample, param_defs, resolution=None):
         """vag_model_params and A_V of one point of sampler space (the transformer of fitting/utils.py:110-135)."""
@@ -1242,10 +1462,10 @@ class Fitter:
             def run():
                 ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
                 # the widest entry point: with a block absent (None) it is the narrower entry point, bit for bit
-                _lib.check(lib.vag_loglike_index_batch_dev(
-                    h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
-                    ref(keep[0]._noise), ref(keep[0]._counts), ref(keep[0]._index), theta.data_ptr(), k, keep[0].ndim,
-                    values.data_ptr()))
+                fn, fold = _widest_entry(lib, keep[0], "_dev")
+                _lib.check(fn(h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
+                              ref(keep[0]._noise), ref(keep[0]._counts), ref(keep[0]._index), *fold, theta.data_ptr(), k, keep[0].ndim,
+                              values.data_ptr()))
                 if want_costs:  # (one more launch: only a sharder that deals by cost asks for it)
                     _lib.check(lib.vag_last_model_costs_dev(h, k, costs.data_ptr()))
             _on_current_stream(run)
@@ -1258,6 +1478,7 @@ class Fitter:
         eval_dev.has_noise_groups = spec._noise is not None
         eval_dev.has_counts = spec._counts is not None
         eval_dev.has_spectral_indices = spec._index is not None
+        eval_dev.has_count_spectra = spec._fold is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -1268,6 +1489,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._fold is not None:
+                    from .dist import _NO_FOLD
+                    raise NotImplementedError(_NO_FOLD)
                 if keep[0]._index is not None:
                     from .dist import _NO_INDEX
                     raise NotImplementedError(_NO_INDEX)
@@ -1316,10 +1540,10 @@ class Fitter:
         with lock:
             ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
             # the widest entry point: with a block absent (None) it is the narrower entry point, bit for bit
-            _lib.check(_lib.load().vag_loglike_index_batch(
-                h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
-                ref(spec._counts), ref(spec._index), samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
-                out.ctypes.data_as(_dp)))
+            fn, fold = _widest_entry(_lib.load(), spec, "")
+            _lib.check(fn(h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
+                          ref(spec._counts), ref(spec._index), *fold, samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
+                          out.ctypes.data_as(_dp)))
             _lib.load().vag_last_plan(h, C.byref(plan))
         if plan.n_models_capacity:
             # never silent: these walkers were NOT evaluated (their adaptive grid exceeds the engine's static limits)
