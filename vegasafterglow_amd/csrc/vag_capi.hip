@@ -630,6 +630,7 @@ static int ctx_init(vag_ctx* c) {
                            reinterpret_cast<const void*>(vag_flux_grid_kernel<false, FLUX_FUSED>),
                            reinterpret_cast<const void*>(vag_flux_grid_kernel<false, FLUX_FUSED, false, 256>),
                            reinterpret_cast<const void*>(vag_flux_grid_kernel<false, FLUX_FUSED, true>),
+                           reinterpret_cast<const void*>(vag_flux_grid_split_kernel),
                            reinterpret_cast<const void*>(vag_flux_series_kernel<FLUX_SYN, true>),
                            reinterpret_cast<const void*>(vag_flux_series_kernel<FLUX_SYN_IC, true>),
                            reinterpret_cast<const void*>(vag_flux_series_kernel<FLUX_SSC, true>)})
@@ -1298,6 +1299,11 @@ static size_t flux_grid_lds_bytes(int mode, int ks, int nt, int nnu) {
     return sizeof(double) * d + sizeof(int) * nt + 16;  // + s_win: [2][2] observation-window counts (WinCount)
 }
 
+// dynamic LDS of vag_flux_grid_split_kernel (FluxSplitLds is the layout), and the most it may ask for: two workgroups stay
+// resident per CU, like the kernel it stands in for
+constexpr size_t FLUX_SPLIT_LDS_BUDGET = 81920;
+static size_t flux_split_lds_bytes(int ks, int nt, int nnu) { return FluxSplitLds(ks, nt, nnu).bytes; }
+
 // Stage 4-5 for a (t, nu) grid request: d_lg2t/d_lg2nu are log2 of code-unit times / frequencies.
 int run_flux_series(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_lg2t, const double* d_lg2nu, int n,
                     double* d_out, int mode = FLUX_SYN, int n_bands = 0, int grid_nt = 0);
@@ -1322,6 +1328,7 @@ static void launch_reduce(hipStream_t st, const vag_model_params* d_params, cons
 // as stay resident (occupancy query x CUs, remembered per kernel and LDS size), its items dealt by descending model cost
 // (vag_flux_order_kernel).  Returns whether it took the persistent form (its counter then has to go back to zero behind it).
 constexpr int FLUX_PERSIST_MIN_PPB = 128;
+constexpr int FLUX_SPLIT_MIN_KS = 192;  // shortest staged lattice the split form takes unforced (measured at 199 nodes)
 template <bool COUNT, int MODE, bool SPREAD = false, int THREADS = FLUX_THREADS, bool PIECES = false>
 static bool launch_flux_grid(vag_ctx* c, FluxArgs a, int nb, size_t lds, int persist) {
     const auto fn = vag_flux_grid_kernel<COUNT, MODE, SPREAD, THREADS, PIECES, true>;
@@ -1350,6 +1357,40 @@ static bool launch_flux_grid(vag_ctx* c, FluxArgs a, int nb, size_t lds, int per
         std::fprintf(stderr, "[vag] grid flux form: persistent, %lld workgroups for %d items\n", n_wg, a.n_items);
     hipLaunchKernelGGL(vag_flux_order_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, a.meta, nb, const_cast<int*>(a.order));
     hipLaunchKernelGGL(fn, dim3((unsigned)n_wg), dim3(THREADS), lds, c->stream, a);
+    return true;
+}
+
+// The split form of the headline launch (vag_flux_grid_split_kernel: fixed wavefront roles, one barrier per row) where the request
+// is one it serves -- the caller has checked plain synchrotron, non-spreading, one piece, 512 lanes, no tallies -- and
+// launch_flux_grid would go persistent.  split = 1: the shapes it is measured to win on; 2 (test hook): wherever it is legal.
+// Returns false with nothing launched where the present kernel has to take the request.
+static bool launch_flux_grid_split(vag_ctx* c, FluxArgs a, int nb, int persist, int split) {
+    if (!split || !persist || !a.rowgeo) return false;
+    const size_t lds = flux_split_lds_bytes(a.k_stride, a.nt, a.nnu);
+    if (lds > FLUX_SPLIT_LDS_BUDGET || a.nnu > FLUX_SPLIT_MAX_NNU || a.nt > FLUX_SPLIT_MAX_NT) return false;
+    // Unforced only on what was measured, the headline shape (lattices of 199 nodes, 200 times x 10 frequencies): all ten frequencies
+    // (fewer take the B team's chain-after-chain loop, which lost), times in the range where B lanes own two, and a lattice about as
+    // long -- the A team's work scales with the lattice, the B team's two wavefronts carry every (nu, t) slot whatever its length,
+    // so on shorter lattices they are what a row waits for.  The LDS budget bounds the lattice from above (204 nodes at this grid).
+    if (split == 1 && (a.nnu != FLUX_SPLIT_MAX_NNU || a.nt <= FLUX_SPLIT_B * 64 || a.k_stride < FLUX_SPLIT_MIN_KS)) return false;
+    const auto fn = vag_flux_grid_split_kernel;
+    int wg = -1;
+    for (const auto& e : c->flux_occ)
+        if (e.fn == reinterpret_cast<const void*>(fn) && e.lds == lds) wg = e.wg;
+    if (wg < 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, FLUX_THREADS, lds) != hipSuccess || wg < 1) wg = 1;
+        if (c->flux_occ.size() > 256) c->flux_occ.clear();
+        c->flux_occ.push_back({reinterpret_cast<const void*>(fn), lds, wg});
+    }
+    if (persist == 1 && (a.n_items <= (long long)wg * c->n_cus || a.pairs_per_block < FLUX_PERSIST_MIN_PPB)) return false;
+    const long long n_wg = std::min<long long>(a.n_items, (long long)wg * c->n_cus);
+    if (vag_hook("VAG_DEBUG_LAUNCH")) {
+        std::fprintf(stderr, "[vag] grid flux form: persistent, %lld workgroups for %d items\n", n_wg, a.n_items);
+        std::fprintf(stderr, "[vag] grid flux split: %d + %d wavefronts (boundary spectra + interpolation), lds=%zu B wg/CU=%d\n", FLUX_SPLIT_A,
+                     FLUX_SPLIT_B, lds, wg);
+    }
+    hipLaunchKernelGGL(vag_flux_order_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, a.meta, nb, const_cast<int*>(a.order));
+    hipLaunchKernelGGL(fn, dim3((unsigned)n_wg), dim3(FLUX_THREADS), lds, c->stream, a);
     return true;
 }
 
@@ -1491,6 +1532,7 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
         const bool small = !spreading && !a.work_count && (long long)nt * nnu <= 512 && (long long)ks * ((nnu + 1) / 2) <= 512 &&
                            !vag_hook("VAG_FLUX_WIDE");
         if (vag_hook("VAG_DEBUG_LAUNCH")) {
+            // (lds / wg/CU are the present kernel's also where the split form then takes the launch: its own are on its "grid flux split" line)
             int occ = -1;
             if (small && mode == FLUX_SSC)
                 (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vag_flux_grid_kernel<false, FLUX_SSC, false, 256>, 256, lds);
@@ -1512,6 +1554,8 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
         // cheapest items.
         int persist = 1;
         if (const char* e = vag_hook("VAG_FLUX_PERSISTENT")) persist = std::atoi(e);
+        int split = 1;
+        if (const char* e = vag_hook("VAG_FLUX_SPLIT")) split = std::atoi(e);
         if (persist) {
             if (c->d_flux_order.ensure(sizeof(int) * (size_t)nb)) return VAG_E_HIP;
             a.work = work_counters(c);
@@ -1559,6 +1603,8 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
             persistent = launch_flux_grid<false, FLUX_SSC>(c, a, nb, lds, persist);
         else if (a.work_count)
             persistent = launch_flux_grid<true, FLUX_SYN>(c, a, nb, lds, persist);
+        else if (launch_flux_grid_split(c, a, nb, persist, split))  // VAG_FLUX_SPLIT=0: never; =2: wherever the split form is legal
+            persistent = true;
         else
             persistent = launch_flux_grid<false, FLUX_SYN>(c, a, nb, lds, persist);
         HIPCHK(hipGetLastError());

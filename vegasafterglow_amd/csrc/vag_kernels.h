@@ -812,6 +812,12 @@ VAG_DEV RowGeo sload_rowgeo(const double* rg, int th_byte, int j, int i) {
 VAG_DEV int sload_i32(const int* p) { return *p; }
 #endif
 
+// The EAT expressions of one lattice node (calc_eat_non_spreading + finalize_log_grids, observer.cpp:143-205, 439-454), written once
+// with their roundings spelled out: every flux kernel forms them, and a model's fluxes must not depend on which one served it.
+VAG_DEV double eat_doppler_arg(vdouble2 Gu, double cos_v) { return fma(-Gu.y, cos_v, Gu.x); }  // Gamma - u cos(view): 1 / Doppler factor
+VAG_DEV double eat_time_arg(vdouble2 rt, double t_coeff, double one_plus_z) { return fma(t_coeff, rt.x, rt.y * one_plus_z); }  // observer time
+VAG_DEV double eat_geom(double lg2_dOmega, double lg2_r2, double lg2_dop) { return (lg2_dOmega + lg2_r2) + 3.0 * lg2_dop; }  // log2(dOmega r^2 D^3)
+
 // EAT quantities of one (theta j, phi i) row: Doppler, observer time and geometry logs
 // (calc_eat_non_spreading + finalize_log_grids, observer.cpp:143-205,439-454) -> LDS.  s_par holds the staged row as
 // [k][VAG_NPAR] blocks (144 B apart: conflict-free 16-byte LDS reads, one address per cell).  win != null: also the row's
@@ -830,12 +836,12 @@ VAG_DEV void eat_row(const double* __restrict__ s_par, int KS, int K, int tid, i
         s_dop[k] = G, s_t[k] = 3.0 + 0.1 * k + u, s_geom[k] = r;
         continue;
 #endif
-        const double lg2_dop = -log2_tab(fma(-u, cos_v, G), lg);  // explicit roundings: the flux kernels form these in two places
-        const double time = fma(t_coeff, r, rt.y * one_plus_z);
+        const double lg2_dop = -log2_tab(eat_doppler_arg(Gu, cos_v), lg);
+        const double time = eat_time_arg(rt, t_coeff, one_plus_z);
         const double lt = log2_tab(time, lg);
         s_dop[k] = lg2_dop;
         s_t[k] = lt;
-        s_geom[k] = (lg2_dOmega + c[VP_LG2_R2]) + 3.0 * lg2_dop;
+        s_geom[k] = eat_geom(lg2_dOmega, c[VP_LG2_R2], lg2_dop);
         if (win) wc.add(true, lt, w_lo, w_hi);
     }
     if (win) wc.store(win, tid);
@@ -918,6 +924,62 @@ vag_eat_details_kernel(const vag_model_params* __restrict__ params, const VagGri
     const double u = sqrt((G - 1) * (G + 1));
     out_t[q] = (teng + one_minus_cos_v * r / C_C) * one_plus_z / U_SEC;
     out_dop[q] = 1.0 / (1.0 / (G + u) + u * one_minus_cos_v);
+}
+
+// The photon block of one representative row into its staged form: `src` is the row's [VAG_NPAR][K_all] block in HBM from node k0
+// on, s_par the [k][VAG_NPAR] block of K nodes in LDS.  All lanes of the workgroup.
+VAG_DEV void stage_photon_block(double* __restrict__ s_par, const double* __restrict__ src, int K, int K_all, int tid, int nthreads) {
+#pragma unroll 1
+    for (int q = tid; q < VAG_NPAR * K; q += nthreads) {  // rare path: keep its register footprint small
+        const int par = (int)(((float)q + 0.5f) / (float)K);
+        s_par[(q - par * K) * VAG_NPAR + par] = src[(size_t)par * K_all + (q - par * K)];
+    }
+}
+
+// Bracket of one requested time in a row's sorted log2 observer times: kk with t_row[kk] <= tq < t_row[kk + 1] (iterate_to,
+// observer.h:309-313, 405-433) and the position w inside the interval, shared by all nu.  The caller has checked
+// t_row[0] <= tq < t_row[K - 1].  `hint` holds the interval the previous row gave this time (0: none yet).  One rule for every
+// form of the grid flux pass, so that they choose the same interval where a lattice repeats a node.
+VAG_DEV void flux_bracket(const double* __restrict__ s_tc, int K, double tq, const int* hint, int& kk, double& w) {
+    // invariant: s_tc[lo] <= tq < s_tc[hi].  Neighbouring rows shift the lattice only slightly: the previous row's
+    // interval and its two neighbours are requested together -- four reads in flight, one round
+    // trip in the common case -- and only a larger shift grows the bracket outwards and bisects it.
+    int lo = *hint, hi;
+    lo = min(max(lo, 1), K - 3);  // first row of the workgroup / a time the previous row did not cover: node 1
+    const double ta = s_tc[lo - 1], tb = s_tc[lo], tc = s_tc[lo + 1], td = s_tc[lo + 2];
+    if (K >= 4 && ta <= tq && tq < td) {
+        lo = tq < tb ? lo - 1 : (tq < tc ? lo : lo + 1);
+    } else {
+        lo = K >= 4 ? lo : 0;
+        if (s_tc[lo] <= tq) {
+            int step = 1;
+            hi = lo + 1;
+            while (hi < K - 1 && s_tc[hi] <= tq) {
+                lo = hi;
+                step <<= 1;
+                hi = min(lo + step, K - 1);
+            }
+        } else {
+            int step = 1;
+            hi = lo;
+            lo = hi - 1;
+            while (s_tc[lo] > tq) {  // ends at the latest at node 0: s_tc[0] = row_t0 <= tq
+                hi = lo;
+                step <<= 1;
+                lo = max(hi - step, 0);
+            }
+        }
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_tc[mid] <= tq)
+                lo = mid;
+            else
+                hi = mid;
+        }
+    }
+    kk = lo;
+    const double t_lo = s_tc[lo];
+    w = (tq - t_lo) * (1.0 / (s_tc[lo + 1] - t_lo));
 }
 
 // 128 VGPRs (four workgroups of 256, two of 512 per CU) is what the occupancy of every measured shape hangs on: the C2 launch asks
@@ -1054,11 +1116,7 @@ __device__ __forceinline__ void flux_grid_item(const FluxArgs& a, const int m, c
         const int rep = rep_at(j, i);
         if (rep != staged_rep) {
             const double* src = a.cellpar + (a.cell_off[m] + (long long)rep * K_all) * VAG_NPAR + k0;
-#pragma unroll 1
-            for (int q = tid; q < VAG_NPAR * K; q += THREADS) {  // rare path: keep its register footprint small
-                const int par = (int)(((float)q + 0.5f) / (float)K);
-                s_par[(q - par * K) * VAG_NPAR + par] = src[(size_t)par * K_all + (q - par * K)];
-            }
+            stage_photon_block(s_par, src, K, K_all, tid, THREADS);
             if constexpr (MODE == FLUX_SSC) {
                 // the SSC pass never evaluates the synchrotron block: its first six rows carry the table headers
                 // (n, first node, last node, theory_min, theory_max, pool offset) instead, saving a dependent global round trip per evaluation
@@ -1116,45 +1174,7 @@ __device__ __forceinline__ void flux_grid_item(const FluxArgs& a, const int m, c
 #else
             if (tq >= row_t0 && tq < row_tN) {
 #endif
-                // invariant: s_tc[lo] <= tq < s_tc[hi].  Neighbouring rows shift the lattice only slightly: the previous row's
-                // interval (still in s_kidx) and its two neighbours are requested together -- four reads in flight, one round
-                // trip in the common case -- and only a larger shift grows the bracket outwards and bisects it.
-                int lo = s_kidx[idx], hi;
-                lo = min(max(lo, 1), K - 3);  // first row of the workgroup / a time the previous row did not cover: node 1
-                const double ta = s_tc[lo - 1], tb = s_tc[lo], tc = s_tc[lo + 1], td = s_tc[lo + 2];
-                if (K >= 4 && ta <= tq && tq < td) {
-                    lo = tq < tb ? lo - 1 : (tq < tc ? lo : lo + 1);
-                } else {
-                    lo = K >= 4 ? lo : 0;
-                    if (s_tc[lo] <= tq) {
-                        int step = 1;
-                        hi = lo + 1;
-                        while (hi < K - 1 && s_tc[hi] <= tq) {
-                            lo = hi;
-                            step <<= 1;
-                            hi = min(lo + step, K - 1);
-                        }
-                    } else {
-                        int step = 1;
-                        hi = lo;
-                        lo = hi - 1;
-                        while (s_tc[lo] > tq) {  // ends at the latest at node 0: s_tc[0] = row_t0 <= tq
-                            hi = lo;
-                            step <<= 1;
-                            lo = max(hi - step, 0);
-                        }
-                    }
-                    while (hi - lo > 1) {
-                        const int mid = (lo + hi) >> 1;
-                        if (s_tc[mid] <= tq)
-                            lo = mid;
-                        else
-                            hi = mid;
-                    }
-                }
-                kk = lo;
-                const double t_lo = s_tc[lo];
-                w = (tq - t_lo) * (1.0 / (s_tc[lo + 1] - t_lo));  // position inside the interval, shared by all nu
+                flux_bracket(s_tc, K, tq, s_kidx + idx, kk, w);
             }
             s_kidx[idx] = kk;
             s_w[idx] = w;
@@ -1321,8 +1341,8 @@ __device__ __forceinline__ void flux_grid_item(const FluxArgs& a, const int m, c
                 [[maybe_unused]] bool sp_a = false, sp_b = false;
                 [[maybe_unused]] double e_dop = 0, e_lt = 0;
                 if constexpr (decltype(with_eat)::value) {
-                    e_dop = -log2_tab_core(fma(-e_Gu.y, e_cos, e_Gu.x), lg_tab, sp_a);  // eat_row's expressions, rounding for rounding
-                    e_lt = log2_tab_core(fma(e_tc, e_rt.x, e_rt.y * one_plus_z), lg_tab, sp_b);
+                    e_dop = -log2_tab_core(eat_doppler_arg(e_Gu, e_cos), lg_tab, sp_a);  // eat_row's expressions
+                    e_lt = log2_tab_core(eat_time_arg(e_rt, e_tc, one_plus_z), lg_tab, sp_b);
                 }
 #pragma unroll
                 for (int u = UB; u < UE; ++u) {
@@ -1342,15 +1362,15 @@ __device__ __forceinline__ void flux_grid_item(const FluxArgs& a, const int m, c
                         if constexpr (MODE == FLUX_FUSED) s_acc2[slot0 + u * THREADS] = aq2[u];
                     }
                 if constexpr (decltype(with_eat)::value) {
-                    if (sp_a) e_dop = -log2(fma(-e_Gu.y, e_cos, e_Gu.x));  // never in practice: arguments the table does not serve
-                    if (__builtin_expect(sp_b, 0)) e_lt = log2(fma(e_tc, e_rt.x, e_rt.y * one_plus_z));
+                    if (sp_a) e_dop = -log2(eat_doppler_arg(e_Gu, e_cos));  // never in practice: arguments the table does not serve
+                    if (__builtin_expect(sp_b, 0)) e_lt = log2(eat_time_arg(e_rt, e_tc, one_plus_z));
                     WinCount wc;
                     wc.add(tid < K, e_lt, w_lo, w_hi);
                     wc.store(s_win + (buf ^ 1) * 2, tid);
                     if (tid < K) {
                         s_dop[ek] = e_dop;
                         s_t[(buf ^ 1) * KS + ek] = e_lt;
-                        s_geom[ek] = (e_dom + e_r2) + 3.0 * e_dop;
+                        s_geom[ek] = eat_geom(e_dom, e_r2, e_dop);
                     }
                 }
             };
@@ -1385,11 +1405,11 @@ __device__ __forceinline__ void flux_grid_item(const FluxArgs& a, const int m, c
                         const double* c = s_par + k * VAG_NPAR;
                         const LdsTab c2 = lds_tab(c);
                         const vdouble2 Gu = c2[VP_GAMMA / 2], rt = c2[VP_R / 2];
-                        const double lg2_dop = -log2_tab(fma(-Gu.y, cos_v, Gu.x), lg_tab);
-                        const double lt = log2_tab(fma(t_coeff, rt.x, rt.y * one_plus_z), lg_tab);
+                        const double lg2_dop = -log2_tab(eat_doppler_arg(Gu, cos_v), lg_tab);
+                        const double lt = log2_tab(eat_time_arg(rt, t_coeff, one_plus_z), lg_tab);
                         s_dop[k] = lg2_dop;
                         s_t[(buf ^ 1) * KS + k] = lt;
-                        s_geom[k] = (lg2_dOmega + c[VP_LG2_R2]) + 3.0 * lg2_dop;
+                        s_geom[k] = eat_geom(lg2_dOmega, c[VP_LG2_R2], lg2_dop);
                         wc.add(true, lt, w_lo, w_hi);
                     }
                     wc.store(s_win + (buf ^ 1) * 2, tid);
@@ -1462,6 +1482,307 @@ vag_flux_grid_kernel(FluxArgs a) {
         flux_grid_item<COUNT, MODE, SPREAD, THREADS, PIECES>(a, a.order[r], it - r * a.max_blocks);
     }
 }
+
+#ifndef VAG_HOST_DEBUG
+// ---- Split form of the headline pass: fixed wavefront roles, one barrier per row ------------------------------------------------
+// Plain synchrotron, non-spreading, one piece, 512 lanes, persistent launch (the conditions are checked where it is launched).
+// The wavefronts of a workgroup keep one role for a whole item:
+//   A team (the first FLUX_SPLIT_A wavefronts): boundary spectra of row p + 1 into s_B[(p + 1) & 1]; work item (cell, frequency
+//     pair), k fastest, as in flux_grid_item.  It never interpolates, so nothing of the interpolation lives in its registers.
+//   B team (the others): a lane owns whole requested times -- time btid with all its frequencies, and time btid + lanes where nt
+//     exceeds the team -- looks their interval up itself (flux_bracket, hint in a register), interpolates from s_B[p & 1] and adds
+//     into accumulators it holds in registers for the whole item.
+//   The EAT logarithms and window counts of row p + 2 are formed by FLUX_SPLIT_E wavefronts behind their own work (see below).
+// One __syncthreads() per row; a change of the staged photon block adds the re-staging's two.  What row p + 1 needs of its EAT step
+// is double buffered (s_dop, the window counts; log2(dOmega r^2 D^3) is formed by the A team from s_dop and the cell's staged
+// log2 r^2 with eat_row's expression, so it needs no array), s_t has three buffers (rows p, p + 1, p + 2 are all in use).
+// Every (nu, t) sum receives the addends of flux_grid_item in its row order: the partial grids are bitwise the same.
+// Team sizes: measured at 6 + 2, 5 + 3 and 4 + 4 (profiles/flux_split_ab.txt); a row's ~855 boundary items are 14 wavefront
+// passes, so of six A wavefronts the first two make three passes and the others two.
+constexpr int FLUX_SPLIT_A = 6;                                     // wavefronts 0 .. FLUX_SPLIT_A - 1: A team
+constexpr int FLUX_SPLIT_B = FLUX_THREADS / 64 - FLUX_SPLIT_A;      // the rest: B team
+constexpr int FLUX_SPLIT_TIMES = 2;                                 // requested times a B lane can own
+constexpr int FLUX_SPLIT_MAX_NT = FLUX_SPLIT_TIMES * FLUX_SPLIT_B * 64;
+constexpr int FLUX_SPLIT_MAX_NNU = 10;                              // accumulators per owned time
+// The EAT step of row p + 2 is taken by the LAST two A wavefronts, behind their spectra: they have a pass less to make, the EAT
+// chains fill the gap, and the B team keeps the interval for its interpolation (on the B team the same split lost).
+constexpr int FLUX_SPLIT_E = 2;                                     // wavefronts of the EAT step
+constexpr int FLUX_SPLIT_E0 = FLUX_SPLIT_A - FLUX_SPLIT_E;          // the first of them
+constexpr int FLUX_SPLIT_GROUP = 5;                                 // interpolation chains of one time the B team interleaves
+static_assert(FLUX_SPLIT_A >= FLUX_SPLIT_E && FLUX_SPLIT_B >= 1, "both teams need wavefronts, the A team those of the EAT step");
+static_assert(FLUX_SPLIT_MAX_NNU % FLUX_SPLIT_GROUP == 0, "the full set of frequencies is taken in whole groups");
+
+// LDS layout of the split form, offsets in doubles (the kernel and the launch's budget read the same numbers)
+struct FluxSplitLds {
+    int par, t, dop, B, tobs, nu, win;
+    size_t bytes;
+    __host__ __device__ FluxSplitLds(int ks, int nt, int nnu) {
+        par = SP_LDS_DOUBLES;        // [ks][VAG_NPAR] staged photon block, behind the softplus / log2 tables
+        t = par + VAG_NPAR * ks;     // [3][ks] log2 observer times of rows p, p + 1, p + 2
+        dop = t + 3 * ks;            // [2][ks] log2 Doppler factor
+        B = dop + 2 * ks;            // [2][nnu][ks] boundary log2-luminosities
+        tobs = B + 2 * nnu * ks;     // [nt]
+        nu = tobs + nt;              // [nnu]
+        win = nu + nnu;              // int [2][FLUX_SPLIT_E][2] window counts per wavefront of the EAT step
+        bytes = sizeof(double) * (size_t)win + sizeof(int) * 4 * FLUX_SPLIT_E;
+    }
+};
+
+__device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, const int blk) {
+    constexpr int THREADS = FLUX_THREADS, NB = FLUX_SPLIT_B, AL = FLUX_SPLIT_A * 64, BL = NB * 64, NE = FLUX_SPLIT_E, EL = NE * 64;
+    const VagGridMeta* Mp = a.meta + m;
+    if (Mp->status != 0) return;
+    const int n_phi_eff = Mp->n_phi_eff;
+    const int n_pairs = Mp->n_theta * n_phi_eff;
+    const int p0 = blk * a.pairs_per_block;
+    if (p0 >= n_pairs) return;
+    const int n_rows = min(n_pairs, p0 + a.pairs_per_block) - p0;
+    const int tid = threadIdx.x;
+    const int K = Mp->n_t, KS = a.k_stride;  // K <= KS: no piece loop in this form
+    const int nt = a.nt, nnu = a.nnu;
+
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const FluxSplitLds L(KS, nt, nnu);
+    double* s_sp = lds;
+    double* s_par = lds + L.par;
+    double* s_t = lds + L.t;
+    double* s_dop = lds + L.dop;
+    double* s_B = lds + L.B;
+    double* s_tobs = lds + L.tobs;
+    double* s_nu = lds + L.nu;
+    int* s_win = reinterpret_cast<int*>(lds + L.win);
+
+    const vag_model_params* Pp = a.params + m;
+    const double one_plus_z = 1 + Pp->z;
+    const double opz_over_c = one_plus_z / C_C;
+    {
+        const double lg2_1pz = Mp->lg2_1pz;
+        for (int i = tid; i < nt; i += THREADS) s_tobs[i] = a.lg2_t_obs[i];
+        for (int l = tid; l < nnu; l += THREADS) s_nu[l] = a.lg2_nu_obs[l] + lg2_1pz;
+    }
+    SpecConst sc;
+    sc.init(Pp->p);
+    const double* rg = a.rowgeo + (size_t)m * a.rowgeo_stride;
+    const int rg_th = sload_i32(reinterpret_cast<const int*>(rg + 2));
+    auto rep_at = [&](int j) { return sload_i32(reinterpret_cast<const int*>(reinterpret_cast<const char*>(rg) + rg_th + 32 * j + 24)); };
+    const LdsTab sp_tab = lds_tab(s_sp), lg_tab = lds_tab(s_sp + SP_TABLE_DOUBLES);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool a_team = wave < FLUX_SPLIT_A;
+    const int lane = tid & 63;
+
+    auto stage = [&](int rep) {  // all lanes: the photon block of a representative row
+        const double* src = a.cellpar + (a.cell_off[m] + (long long)rep * K) * VAG_NPAR;
+        stage_photon_block(s_par, src, K, K, tid, THREADS);
+    };
+    // The rows of the item and the one barrier per row.  Interval n (n = -1: the pipeline fills; n = n_rows - 1: it drains):
+    //   A team: spectra of row n + 1        B team: interpolation of row n        EAT wavefronts, behind their own work: row n + 2
+    // `work(n, j1, i1, j2, i2, tb0, tb1, tb2, eat_now)`: (j, i) of rows n + 1 and n + 2, the s_t buffers of rows n, n + 1, n + 2.  A row
+    // n + 2 of another photon block is staged behind the barrier, when the A team is done with the present block; its EAT step
+    // (`late_eat`) follows alone.  Both teams run this with the same block-uniform decisions, so their barriers pair up.
+    auto pipeline = [&](auto&& work, auto&& late_eat) {
+        int j1 = p0 / n_phi_eff, i1 = p0 - j1 * n_phi_eff;
+        int staged_rep = rep_at(j1);
+        __syncthreads();  // s_tobs, s_nu
+        stage(staged_rep);
+        __syncthreads();
+        late_eat(j1, i1, 0, 0);
+        __syncthreads();
+        int tb0 = 2, tb1 = 0, tb2 = 1;
+        for (int n = -1; n < n_rows; ++n) {
+            int j2 = j1, i2 = i1 + 1;
+            if (i2 == n_phi_eff) i2 = 0, ++j2;
+            const bool have2 = n + 2 < n_rows;
+            const int rep2 = have2 ? rep_at(j2) : staged_rep;
+            const bool same = rep2 == staged_rep;
+            work(n, j1, i1, j2, i2, tb0, tb1, tb2, have2 && same);
+            __syncthreads();
+            if (__builtin_expect(!same, 0)) {  // once per theta row
+                stage(rep2);
+                staged_rep = rep2;
+                __syncthreads();
+                late_eat(j2, i2, n + 2, tb2);
+                __syncthreads();
+            }
+            j1 = j2, i1 = i2;
+            tb0 = tb1, tb1 = tb2, tb2 = tb2 == 2 ? 0 : tb2 + 1;
+        }
+    };
+
+    // EAT step of row r at (theta j, phi i) by the wavefronts FLUX_SPLIT_E0 .. + FLUX_SPLIT_E - 1: eat_row's expressions, rounding
+    // for rounding; a wavefront's window counts go to its own pair of words (no atomics, nothing to clear)
+    auto eat = [&](int j, int i, int r, int tb) {
+        const int etid = tid - FLUX_SPLIT_E0 * 64, ew = wave - FLUX_SPLIT_E0;
+        if (ew < 0) return;  // wavefront-uniform: the A wavefronts ahead of the EAT ones
+        const double w_lo = s_tobs[0], w_hi = s_tobs[nt - 1];
+        const RowGeo g = sload_rowgeo(rg, rg_th, j, i);
+        const double cos_v = g.cos_view();
+        const double t_coeff = (1 - cos_v) * opz_over_c;
+        double* st = s_t + tb * KS;
+        double* sd = s_dop + (r & 1) * KS;
+        int n_lt = 0, n_le = 0;
+        for (int k = etid; k < K; k += EL) {
+            const LdsTab c2 = lds_tab(s_par + k * VAG_NPAR);
+            const vdouble2 Gu = c2[VP_GAMMA / 2], rt = c2[VP_R / 2];
+            bool sp_a, sp_b;
+            double dop = -log2_tab_core(eat_doppler_arg(Gu, cos_v), lg_tab, sp_a);
+            double lt = log2_tab_core(eat_time_arg(rt, t_coeff, one_plus_z), lg_tab, sp_b);
+            if (__builtin_expect(sp_a, 0)) dop = -log2(eat_doppler_arg(Gu, cos_v));  // never in practice: arguments the table does not serve
+            if (__builtin_expect(sp_b, 0)) lt = log2(eat_time_arg(rt, t_coeff, one_plus_z));
+            sd[k] = dop;
+            st[k] = lt;
+            n_lt += __popcll(__ballot(lt < w_lo));
+            n_le += __popcll(__ballot(lt <= w_hi));
+        }
+        if (lane == 0) {
+            int* win = s_win + ((r & 1) * NE + ew) * 2;
+            win[0] = n_lt, win[1] = n_le;
+        }
+    };
+    if (a_team) {
+        const int atid = tid;  // the A team is the first wavefronts
+        auto spectra_of = [&](int n, int j1, int i1, int tb1) {
+            const int r = n + 1;
+            if (r >= n_rows) return;
+            const double* s_tc = s_t + tb1 * KS;
+            const double row_t0 = s_tc[0], row_tN = s_tc[K - 1];
+            const double w_lo = s_tobs[0], w_hi = s_tobs[nt - 1];
+            if (row_tN < w_lo || row_t0 > w_hi) return;  // block-uniform: the B team skips the row too
+            const int* win = s_win + (r & 1) * 2 * NE;
+            int n_lt = 0, n_le = 0;
+#pragma unroll
+            for (int w = 0; w < NE; ++w) {
+                n_lt += __builtin_amdgcn_readfirstlane(win[2 * w]);
+                n_le += __builtin_amdgcn_readfirstlane(win[2 * w + 1]);
+            }
+            const int k_lo = n_lt > 0 ? n_lt - 1 : 0;
+            const int k_hi = min(max(n_le, k_lo + 1), K - 1);
+            const RowGeo g = sload_rowgeo(rg, rg_th, j1, i1);
+            const double lg2_dOmega = g.dth + g.dph;
+            const double* dopv = s_dop + (r & 1) * KS;
+            double* sB = s_B + (r & 1) * nnu * KS;
+            // item q = lg * nk + kk walks in steps of the team's lanes, as in flux_grid_item
+            const int nk = k_hi - k_lo + 1;
+            const int total = nk * ((nnu + 1) >> 1);
+            const float inv_nk = __builtin_amdgcn_rcpf((float)nk);
+            const int dq_l = AL / nk, dq_k = AL - dq_l * nk;
+            int lg = (int)(((float)atid + 0.5f) * inv_nk);
+            int kk = atid - __mul24(lg, nk);
+            int bofs = __mul24(lg, 2 * KS);
+            const int top = (nnu - 1) * KS;
+            for (int q = atid; q < total; q += AL) {
+                const int k = k_lo + kk;
+                const int l0 = lg * 2, l1 = min(l0 + 1, nnu - 1);
+                const double dop = dopv[k];
+                const SpecRegs regs = load_spec_regs(lds_tab(s_par) + __mul24(k, VAG_NPAR / 2));
+                const double geom = eat_geom(lg2_dOmega, regs[VP_LG2_R2], dop);  // eat_row's s_geom[k]
+                const double b0 = log2_I_nu_fast(regs, 1, sc, s_nu[l0] - dop, sp_tab);
+                const double b1 = log2_I_nu_fast(regs, 1, sc, s_nu[l1] - dop, sp_tab);
+                sB[bofs + k] = b0 + geom;
+                sB[min(bofs + KS, top) + k] = b1 + geom;
+                kk += dq_k;
+                lg += dq_l;
+                bofs += dq_l * 2 * KS;
+                if (kk >= nk) {
+                    kk -= nk;
+                    ++lg;
+                    bofs += 2 * KS;
+                }
+            }
+        };
+        auto spectra = [&](int n, int j1, int i1, int j2, int i2, int, int tb1, int tb2, bool eat_now) {
+            spectra_of(n, j1, i1, tb1);
+            if (eat_now) eat(j2, i2, n + 2, tb2);
+        };
+        pipeline(spectra, eat);
+    } else {
+        const int btid = tid - AL;
+        const double w_lo = a.lg2_t_obs[0], w_hi = a.lg2_t_obs[nt - 1];  // == s_tobs[0], s_tobs[nt - 1]
+        double acc[FLUX_SPLIT_TIMES][FLUX_SPLIT_MAX_NNU];
+        int hint[FLUX_SPLIT_TIMES];
+        double tq[FLUX_SPLIT_TIMES];
+#pragma unroll
+        for (int o = 0; o < FLUX_SPLIT_TIMES; ++o) {
+            hint[o] = 0;
+            tq[o] = a.lg2_t_obs[min(btid + o * BL, nt - 1)];
+#pragma unroll
+            for (int l = 0; l < FLUX_SPLIT_MAX_NNU; ++l) acc[o][l] = 0;
+        }
+        auto interp = [&](int n, int, int, int, int, int tb0, int, int, bool) {
+            if (n >= 0) {
+                const double* s_tc = s_t + tb0 * KS;
+                const double row_t0 = s_tc[0], row_tN = s_tc[K - 1];
+                if (row_tN < w_lo || row_t0 > w_hi) {  // block-uniform; no time of such a row has an interval (flux_grid_item leaves 0)
+#pragma unroll
+                    for (int o = 0; o < FLUX_SPLIT_TIMES; ++o) hint[o] = 0;
+                } else {
+                    const double* sB = s_B + (n & 1) * nnu * KS;
+#pragma unroll
+                    for (int o = 0; o < FLUX_SPLIT_TIMES; ++o) {
+                        const bool owned = btid + o * BL < nt;
+                        // a requested time outside the row's lattice keeps interval 0 and adds exp2(-2000) = 0 in flux_grid_item:
+                        // the sums keep their bits without that addend
+                        const bool inside = owned && tq[o] >= row_t0 && tq[o] < row_tN;
+                        int kk = 0;
+                        double w = NAN;
+                        if (inside) flux_bracket(s_tc, K, tq[o], &hint[o], kk, w);
+                        hint[o] = kk;
+                        if (inside) {
+                            if (nnu == FLUX_SPLIT_MAX_NNU) {  // block-uniform: the full set as straight-line code, its chains interleave
+#pragma unroll
+                                for (int l0 = 0; l0 < FLUX_SPLIT_MAX_NNU; l0 += FLUX_SPLIT_GROUP) {
+                                    double lo[FLUX_SPLIT_GROUP], hi[FLUX_SPLIT_GROUP];
+#pragma unroll
+                                    for (int g = 0; g < FLUX_SPLIT_GROUP; ++g) lo[g] = sB[(l0 + g) * KS + kk], hi[g] = sB[(l0 + g) * KS + kk + 1];
+#pragma unroll
+                                    for (int g = 0; g < FLUX_SPLIT_GROUP; ++g) acc[o][l0 + g] += exp2_or_zero(fma(hi[g] - lo[g], w, lo[g]));
+                                    __builtin_amdgcn_sched_barrier(0);  // one group's chains at a time: ten at once spill
+                                }
+                            } else {
+#pragma unroll
+                                for (int l = 0; l < FLUX_SPLIT_MAX_NNU; ++l) {
+                                    if (l < nnu) {
+                                        const double lo = sB[l * KS + kk], hi = sB[l * KS + kk + 1];
+                                        acc[o][l] += exp2_or_zero(fma(hi - lo, w, lo));
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        };
+        pipeline(interp, [](int, int, int, int) {});
+        // partial grid of this workgroup, stored [l][idx] like the reference's F_nu (nu outer)
+        double* my_partial = a.partial + ((size_t)m * a.max_blocks + blk) * ((size_t)nt * nnu);
+#pragma unroll
+        for (int o = 0; o < FLUX_SPLIT_TIMES; ++o) {
+            const int idx = btid + o * BL;
+            if (idx < nt) {
+#pragma unroll
+                for (int l = 0; l < FLUX_SPLIT_MAX_NNU; ++l)
+                    if (l < nnu) my_partial[l * nt + idx] = acc[o][l];
+            }
+        }
+    }
+}
+
+// The persistent launch of vag_flux_grid_kernel (items from the counter a.work in the order of a.order) around the split item.
+__global__ void __launch_bounds__(FLUX_THREADS, 4)
+vag_flux_grid_split_kernel(FluxArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    for (int i = threadIdx.x; i < SP_LDS_DOUBLES; i += FLUX_THREADS) lds[i] = a.sp_table[i];
+    int* s_it = reinterpret_cast<int*>(lds + SP_LDS_DOUBLES);  // first word of s_par: an item writes it only after its first barrier
+    for (;;) {
+        __syncthreads();  // the previous item is done with the LDS
+        if (threadIdx.x == 0) *s_it = __hip_atomic_fetch_add(a.work, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const int it = __builtin_amdgcn_readfirstlane(*s_it);
+        if (it >= a.n_items) break;
+        const int r = it / a.max_blocks;
+        flux_split_item(a, a.order[r], it - r * a.max_blocks);
+    }
+}
+#endif  // VAG_HOST_DEBUG
 
 // Deal order of a persistent flux launch: the models by descending predicted cost, ties in model order; failed models last.  The
 // cost is rows x ALL lattice nodes of the row, not rows x window nodes: the window of a row is known only after that row's EAT
