@@ -1176,7 +1176,11 @@ VAG_DEV void lds_add_f64(double* p, double v) {
 #endif
 
 // compute_log2_I_nu (smooth-power-law-syn.cpp:15-46,80-92,159-167) on the fast kernels above.
-template <class PtrT, class Tab>
+// THICK_BOUND: leave the thick branch's softplus term out where the absorption blend below drops the whole branch.  The term is
+// >= 0 (sp_fast), so lb >= th = 2.5 lg2_nu + VP_TB also after rounding, and with SAB > 0 (rounding is monotone)
+// SAB (thin - lb) <= SAB (thin - th): where the right side is < -20 the blend's softplus returns exactly 0 for either lb, and the
+// result has the bits of the full path.  NaN compares false and takes the full path.
+template <bool THICK_BOUND = false, class PtrT, class Tab>
 VAG_DEV double log2_I_nu_fast(const PtrT& c, int st, const SpecConst& sc, double lg2_nu, Tab sp) {
     const double l_lo = c[VP_LG2_LO * st];
     const double thin = (lg2_nu - l_lo) * (1.0 / 3.0) - sp_fast(c[VP_DLO * st] * (lg2_nu - l_lo), sp) * c[VP_INV_SLO * st] -
@@ -1184,8 +1188,10 @@ VAG_DEV double log2_I_nu_fast(const PtrT& c, int st, const SpecConst& sc, double
     const double lx = lg2_nu - c[VP_LG2_NUM * st];
     double lb = fma(2.5, lg2_nu, c[VP_TB * st]);  // thick branch 2.5 lx + log2_thick_norm_
     if (!(lx > sc.log2_x_far)) {
-        const double s = -sc.smooth_thick * exp2_fast(2. / 3 * lx);
-        lb += sp_fast(-0.5 * lx + s, sp);
+        if (!THICK_BOUND || !(c[VP_SAB * st] * (thin - lb) < -20.0 && c[VP_SAB * st] > 0)) {
+            const double s = -sc.smooth_thick * exp2_fast(2. / 3 * lx);
+            lb += sp_fast(-0.5 * lx + s, sp);
+        }
     }
     const double smooth_one = thin - sp_fast(c[VP_SAB * st] * (thin - lb), sp) * c[VP_INV_SAB * st];
     const double spec = c[VP_LG2_I_SLO * st] + smooth_one;
