@@ -395,6 +395,10 @@ int vag_flux_density_batch_dev(vag_ctx* ctx, const vag_model_params* d_params, i
 /* Nor is this: the absorbing column N_H [cm^-2] of the count-spectrum groups of vag_loglike_fold_batch.  Only that entry point accepts
  * it, and only when some group carries a cross-section (vag_fold_obs::sigma). */
 #define VAG_P_N_H 1016
+/* Nor are these: the amplitude a_c of additive template c of vag_loglike_tmpl_batch, c = 0 .. VAG_TMPL_MAX - 1.  Only that entry point
+ * accepts VAG_P_TMPL_AMP0 + c, and only when its vag_template_fit_spec has template c (c < n_templates). */
+#define VAG_P_TMPL_AMP0 1017
+#define VAG_TMPL_MAX 8
 
 /* One group of VLBI centroid positions at one frequency (added after VAG_ABI_VERSION 13, detect by symbol).  The model centroid
  * (Xbar, Ybar) of vag_sky_centroid_batch(t, nu) is placed on the sky as
@@ -823,6 +827,45 @@ int vag_loglike_fold_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag
                                const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
                                const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
                                const double* d_theta, int nb, int ndim, double* d_out);
+
+/* Additive templates in the flux passes (added after VAG_ABI_VERSION 13, detect by symbol): a host galaxy's constant flux, a supernova
+ * or kilonova bump -- a fixed shape per data set whose amplitude is a fit parameter.  A fit has up to VAG_TMPL_MAX templates.
+ * Template c has an amplitude a_c >= 0 (the free parameter with the slot VAG_P_TMPL_AMP0 + c, else amp_fixed[c]), a flag
+ * extinguished[c], and a value T_c,i >= 0, finite, for every row i of every flux pass (the point rows, a band group); T_c,i = 0:
+ * the template does not touch the row.  With F_i the walker's model flux at the row (band-integrated for a band row) the row's
+ * model value becomes
+ *   e_i = sum_c a_c T_c,i over the templates with extinguished = 0,
+ *   x_i = sum_c a_c T_c,i over the templates with extinguished = 1,
+ *   f_i = (F_i + x_i) exp(-A_V k_i) + e_i
+ * (both sums from 0 in ascending c, one fma per term; the extinction factor exactly where it applies today: a pass without an
+ * extinction kernel has factor 1).  f_i replaces the model value in every term a flux pass forms: the detection term with its 1e-300
+ * clamp and NaN rule, the limit term (no clamp), and r_i of the noise-group sums.  Nothing else reads templates: counts, index, fold,
+ * centroid, visibility and polarization groups do not.  Units are the row's own: a point-row template is in the unit of the flux
+ * density at T = 1, a band-row template in erg cm^-2 s^-1.  A walker whose free amplitude is not finite or is negative scores -inf
+ * and is counted in vag_plan.n_walkers_rejected. */
+typedef struct vag_template_fit_spec {
+    int32_t n_templates;               /* 0 .. VAG_TMPL_MAX */
+    int32_t n_bands;                   /* 0 or spec->n_bands */
+    const double* point;               /* [n_templates][spec->n_data] row-major, or NULL: no template touches a point row */
+    const double* const* bands;        /* [n_bands]: each [n_templates][n of that band group], or NULL */
+    double  amp_fixed[VAG_TMPL_MAX];   /* a_c of a template without a free parameter */
+    int32_t extinguished[VAG_TMPL_MAX]; /* 1: the template is behind the host's dust (x_i), 0: it is not (e_i) */
+} vag_template_fit_spec;
+
+/* vag_loglike_fold_batch(_dev) with templates.  With tmpl NULL or no touched row (every T = 0) it is exactly that call, bit for
+ * bit; a pass no template touches launches what it launches there.  Refused with VAG_E_INVALID before the device is touched, the
+ * message naming template and row: n_templates outside 0 .. VAG_TMPL_MAX; n_bands neither 0 nor the fit spec's; an entry of T that
+ * is negative or not finite; an amp_fixed that is negative or not finite; an extinguished other than 0 or 1; a parameter slot
+ * VAG_P_TMPL_AMP0 + c with c >= n_templates ("bad parameter slot").  Results are bitwise reproducible and a walker's value does not
+ * depend on the rest of the batch or on its evaluation slot.  The template values stay resident on the device by content hash. */
+int vag_loglike_tmpl_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                           const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                           const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                           const vag_template_fit_spec* tmpl, const double* theta, int nb, int ndim, double* out);
+int vag_loglike_tmpl_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                               const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                               const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                               const vag_template_fit_spec* tmpl, const double* d_theta, int nb, int ndim, double* d_out);
 
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.

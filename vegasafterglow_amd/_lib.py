@@ -69,6 +69,9 @@ P_NOISE_SYS0, NOISE_MAX_GROUPS = 1008, 8
 NOISE_PREFIX = "sys_"
 # VAG_P_N_H: the absorbing column of the count-spectrum groups (vag_loglike_fold_batch), the parameter "N_H" of a Fitter
 P_N_H = 1016
+# VAG_P_TMPL_AMP0 + c: the amplitude of additive template c (vag_loglike_tmpl_batch), the parameter "amp_<name>" of a Fitter
+P_TMPL_AMP0, TMPL_MAX = 1017, 8
+TMPL_PREFIX = "amp_"
 
 
 class CentroidObs(C.Structure):  # vag_centroid_obs
@@ -165,6 +168,11 @@ class FoldFitSpec(C.Structure):  # vag_fold_fit_spec
     _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(FoldObs)), ("n_h_fixed", C.c_double)]
 
 
+class TemplateFitSpec(C.Structure):  # vag_template_fit_spec
+    _fields_ = [("n_templates", C.c_int32), ("n_bands", C.c_int32), ("point", C.POINTER(C.c_double)),
+                ("bands", C.POINTER(C.POINTER(C.c_double))), ("amp_fixed", C.c_double * 8), ("extinguished", C.c_int32 * 8)]
+
+
 class FitSpec(C.Structure):
     _fields_ = [
         ("base", ModelParams), ("ndim", C.c_int32), ("slot", C.c_int32 * 16), ("is_log", C.c_int32 * 16),
@@ -230,7 +238,7 @@ EXPORTS = [
     "vag_sky_polarization_batch", "vag_sky_stokes_image_batch", "vag_loglike_pol_batch", "vag_loglike_pol_batch_dev",
     "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev", "vag_loglike_noise_batch", "vag_loglike_noise_batch_dev",
     "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev", "vag_loglike_index_batch", "vag_loglike_index_batch_dev",
-    "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev",
+    "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev", "vag_loglike_tmpl_batch", "vag_loglike_tmpl_batch_dev",
 ]
 
 _lib = None
@@ -318,6 +326,12 @@ def load():
                                                    C.POINTER(PolFitSpec), C.POINTER(LimitFitSpec), C.POINTER(NoiseFitSpec),
                                                    C.POINTER(CountsFitSpec), C.POINTER(IndexFitSpec), C.POINTER(FoldFitSpec), v, C.c_int,
                                                    C.c_int, v]
+    if hasattr(lib, "vag_loglike_tmpl_batch"):  # (detected by symbol, like the fold entry)
+        wide = [v, C.POINTER(FitSpec), C.POINTER(SkyFitSpec), C.POINTER(VisFitSpec), C.POINTER(PolFitSpec), C.POINTER(LimitFitSpec),
+                C.POINTER(NoiseFitSpec), C.POINTER(CountsFitSpec), C.POINTER(IndexFitSpec), C.POINTER(FoldFitSpec),
+                C.POINTER(TemplateFitSpec)]
+        lib.vag_loglike_tmpl_batch.argtypes = wide + [_dp, C.c_int, C.c_int, _dp]
+        lib.vag_loglike_tmpl_batch_dev.argtypes = wide + [v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -414,6 +414,7 @@ struct vag_ctx {
     DevBuf d_visfit, d_visblk, d_vispart;  // visibility groups of the likelihood: their data, their 64-visibility blocks, chi^2 partials
     DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_noisefit;  // noise groups of the likelihood (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
+    DevBuf d_tmplfit;  // additive templates of the likelihood (vag_loglike_tmpl_batch): [amp_fixed 8] then per touched pass its [n_templates][n] values, see TmplLayout
     DevBuf d_countsfit;  // counts groups of the likelihood (vag_loglike_counts_batch): per group [t_sample | N | B | a | w | idx], see CountsLayout
     DevBuf d_foldfit;   // fold groups of the likelihood (vag_loglike_fold_batch): per group the block FoldLayout describes
     DevBuf d_indexfit;  // spectral-index groups of the likelihood (vag_loglike_index_batch): per group [t | nu | s | sigma | w | c], see IndexLayout
@@ -471,7 +472,7 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit, h_indexfit, h_foldfit;
+    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit, h_indexfit, h_foldfit, h_tmplfit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
@@ -502,6 +503,9 @@ struct vag_ctx {
     uint64_t foldfit_hash = 0;  // (d_foldfit: the fold groups of vag_loglike_fold_batch, upload_fold_spec)
     size_t foldfit_doubles = 0;
     bool foldfit_hash_valid = false;
+    uint64_t tmplfit_hash = 0;  // (d_tmplfit: the templates of vag_loglike_tmpl_batch, upload_tmpl_spec)
+    size_t tmplfit_doubles = 0;
+    bool tmplfit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -744,8 +748,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_countsfit.release();
     c->h_indexfit.release();
     c->h_foldfit.release();
+    c->h_tmplfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit, &c->d_indexfit, &c->d_foldfit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit, &c->d_indexfit, &c->d_foldfit, &c->d_tmplfit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3619,7 +3624,7 @@ static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
 }
 
 static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false, int noise_groups = 0,
-                           bool counts = false, bool n_h = false) {
+                           bool counts = false, bool n_h = false, int n_templates = 0) {
     if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
     const int n = spec->n_data;
     if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky && !pol && !counts)) return set_err(VAG_E_INVALID, "fit spec has no data");
@@ -3630,6 +3635,7 @@ static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool 
         if (pol && (s == VAG_P_SKY_PA || (s >= VAG_P_POL_B && s <= VAG_P_POL_PI_MAX_RVS))) continue;
         if (s >= VAG_P_NOISE_SYS0 && s < VAG_P_NOISE_SYS0 + noise_groups) continue;  // (the systematic of a group the noise spec has)
         if (n_h && s == VAG_P_N_H) continue;  // (the absorbing column of a fold group with a cross-section)
+        if (s >= VAG_P_TMPL_AMP0 && s < VAG_P_TMPL_AMP0 + n_templates) continue;  // (the amplitude of a template the template spec has)
         if (s < 0 || (s >= VAG_P_COUNT && (s < VAG_P_RVS_EPS_E || s > VAG_P_MAG_Q))) return set_err(VAG_E_INVALID, "bad parameter slot");
     }
     if (spec->use_priors)
@@ -4119,6 +4125,85 @@ static int upload_noise_spec(vag_ctx* c, const std::vector<double>& stage, const
     return VAG_OK;
 }
 
+// ---- additive templates (vag_loglike_tmpl_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
+//      Layout in doubles: [amp_fixed 8], then for every pass with a touched row -- the point rows, a band group -- its values
+//      [n_templates][n].  A pass no template touches is not stored (offset -1): it is the pass without templates. ----
+struct TmplLayout {
+    long point = -1;                    // offset of the point rows' values in d_tmplfit, or -1
+    std::vector<long> band;             // the same per band group
+    unsigned point_present = 0;         // bit c: template c touches some point row
+    std::vector<unsigned> band_present; // the same per band group
+    unsigned ext_mask = 0;              // bit c: template c is extinguished
+    int n_templates = 0;
+    bool any = false;                   // some row is touched
+};
+
+// Validates tmpl against the fit spec and lays its blocks out in stage (host work only: no context is touched).
+static int tmpl_scan(const vag_fit_spec* spec, const vag_template_fit_spec* tp, std::vector<double>& stage, TmplLayout& lay) {
+    if (tp->n_templates < 0 || tp->n_templates > VAG_TMPL_MAX)
+        return set_err(VAG_E_INVALID, "templates: n_templates must be in 0..%d, got %d", VAG_TMPL_MAX, tp->n_templates);
+    if (tp->n_bands != 0 && tp->n_bands != spec->n_bands)
+        return set_err(VAG_E_INVALID, "templates: n_bands must be 0 or the fit spec's %d, got %d", spec->n_bands, tp->n_bands);
+    if (tp->n_bands > 0 && (!tp->bands || !spec->bands)) return set_err(VAG_E_INVALID, "templates: null band list");
+    const int nt = tp->n_templates;
+    for (int c = 0; c < nt; ++c) {
+        if (!std::isfinite(tp->amp_fixed[c]) || tp->amp_fixed[c] < 0)
+            return set_err(VAG_E_INVALID, "template %d: the fixed amplitude must be finite and >= 0", c);
+        if (tp->extinguished[c] != 0 && tp->extinguished[c] != 1)
+            return set_err(VAG_E_INVALID, "template %d: extinguished must be 0 or 1, got %d", c, tp->extinguished[c]);
+        lay.ext_mask |= (unsigned)tp->extinguished[c] << c;
+    }
+    lay.n_templates = nt;
+    stage.assign(VAG_TMPL_MAX, 0.0);
+    for (int c = 0; c < nt; ++c) stage[c] = tp->amp_fixed[c];
+    // one pass's block: checked, and stored when some value is not 0
+    auto push = [&](const double* T, int n, const char* what, int b, long& at, unsigned& present) -> int {
+        for (int c = 0; c < nt; ++c)
+            for (int i = 0; i < n; ++i) {
+                const double v = T[(size_t)c * n + i];
+                if (!std::isfinite(v) || v < 0) {
+                    if (b < 0) return set_err(VAG_E_INVALID, "template %d, %s %d: the value must be finite and >= 0", c, what, i);
+                    return set_err(VAG_E_INVALID, "template %d, %s %d, row %d: the value must be finite and >= 0", c, what, b, i);
+                }
+                if (v != 0.0) present |= 1u << c;
+            }
+        if (present) {
+            lay.any = true;
+            at = (long)stage.size();
+            stage.insert(stage.end(), T, T + (size_t)nt * n);
+        }
+        return VAG_OK;
+    };
+    int rc = VAG_OK;
+    if (tp->point && nt > 0 && spec->n_data > 0 && (rc = push(tp->point, spec->n_data, "point row", -1, lay.point, lay.point_present)))
+        return rc;
+    lay.band.assign(std::max(spec->n_bands, 0), -1);
+    lay.band_present.assign(std::max(spec->n_bands, 0), 0u);
+    for (int b = 0; b < tp->n_bands && nt > 0; ++b) {
+        if (!tp->bands[b] || spec->bands[b].n <= 0) continue;
+        if ((rc = push(tp->bands[b], spec->bands[b].n, "band group", b, lay.band[b], lay.band_present[b]))) return rc;
+    }
+    return VAG_OK;
+}
+
+static int upload_tmpl_spec(vag_ctx* c, const std::vector<double>& stage, const TmplLayout& lay) {
+    uint64_t h = 1469598103934665603ull;
+    h = fnv1a(h, &lay.point, sizeof lay.point);
+    if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
+    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
+    if (c->tmplfit_hash_valid && c->tmplfit_hash == h && c->tmplfit_doubles == stage.size()) return VAG_OK;  // resident already
+    c->tmplfit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_tmplfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    if (c->d_tmplfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    std::memcpy(c->h_tmplfit.as<double>(), stage.data(), sizeof(double) * stage.size());
+    HIPCHK(hipMemcpyAsync(c->d_tmplfit.p, c->h_tmplfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
+    c->tmplfit_hash = h;
+    c->tmplfit_doubles = stage.size();
+    c->tmplfit_hash_valid = true;
+    return VAG_OK;
+}
+
 // ---- counts groups (vag_loglike_counts_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
 //      in doubles, per group: [t_sample ns | N n | B n | a n | w n], then the sample indices (int32 [n m] in (n m + 1) / 2 doubles). ----
 constexpr int COUNTS_PPB = 64;  // (theta, phi) pairs per flux workgroup of a counts pass (vag_ctx::ppb_pin)
@@ -4413,12 +4498,14 @@ struct FitRequest {
     const vag_counts_fit_spec* counts = nullptr;
     const vag_index_fit_spec* index = nullptr;
     const vag_fold_fit_spec* fold = nullptr;
+    const vag_template_fit_spec* tmpl = nullptr;  // after fit_request_prepare: null when no row is touched (tlay.any)
     LimLayout llay;
     NoiseLayout nlay;
     CountsLayout clay;
     IndexLayout ilay;
     FoldLayout flay;
-    std::vector<double> lstage, nstage, cstage, istage, fstage;  // what the scans lay out for upload_{lim,noise,counts,index,fold}_spec
+    TmplLayout tlay;
+    std::vector<double> lstage, nstage, cstage, istage, fstage, tstage;  // what the scans lay out for upload_{lim,noise,counts,index,fold,tmpl}_spec
     bool placed = false;                                 // some group reads east0 / north0
     bool prepared = false;                               // fit_request_prepare has run
 };
@@ -4432,6 +4519,7 @@ static int fit_request_prepare(FitRequest& r) {
     if (r.index && r.index->n_groups == 0) r.index = nullptr;
     if (r.fold && r.fold->n_groups == 0) r.fold = nullptr;
     int rc = VAG_OK;
+    if (r.tmpl && (rc = tmpl_scan(r.spec, r.tmpl, r.tstage, r.tlay))) return rc;
     if (r.fold && (rc = fold_scan(r.spec, r.fold, r.fstage, r.flay))) return rc;
     if (r.index && (rc = index_scan(r.index, r.istage, r.ilay))) return rc;
     if (r.counts && (rc = counts_scan(r.counts, r.cstage, r.clay))) return rc;
@@ -4439,6 +4527,7 @@ static int fit_request_prepare(FitRequest& r) {
     if (r.lim && (rc = lim_scan(r.spec, r.pol, r.lim, r.lstage, r.llay))) return rc;  // (pol as given: an empty list checks n_pol_groups)
     if (!r.nlay.any) r.noise = nullptr;
     if (!r.llay.any) r.lim = nullptr;
+    if (!r.tlay.any) r.tmpl = nullptr;  // (tlay.n_templates stays: the amplitude slots of the spec's templates are accepted)
     if (r.pol && r.pol->n_groups == 0) r.pol = nullptr;
     r.placed = (r.sky && r.sky->n_groups > 0) || r.vis;
     // (east0 / north0 place centroid and visibility groups only: without such a group they are refused as free parameters)
@@ -4512,13 +4601,20 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     };
     // the back of a flux pass.  lim_off: where the pass's block of limit rows starts in d_limfit, or -1 (no limit row: the kernel as it
     // was); noise_off, present: where the pass's group ids start in d_noisefit, or -1 (no grouped row: the kernels as they were), and
-    // its groups
+    // its groups; tmpl_off, tpresent: where the pass's template values start in d_tmplfit, or -1 (no touched row: the kernels as they
+    // were), and the templates that touch it
     auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext,
-                    long lim_off, long noise_off, unsigned present) -> int {
+                    long lim_off, long noise_off, unsigned present, long tmpl_off, unsigned tpresent) -> int {
         const double* lb = lim_off >= 0 ? c->d_limfit.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
         const int* lk = lb ? reinterpret_cast<const int*>(lb + 2 * (size_t)npts) : nullptr;
         const double* ls = lb ? lb + npts : nullptr;
-        if (noise_off >= 0) {
+        if (tmpl_off >= 0) {
+            const double* nz = noise_off >= 0 ? c->d_noisefit.as<double>() : nullptr;
+            const double* tp = c->d_tmplfit.as<double>();  // [amp_fixed 8 | the passes' values]
+            hipLaunchKernelGGL(vag_fit_back_tmpl_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av, fit_pass(),
+                               next_order(), lk, lb, ls, d_theta, ndim, d_prior, nz, nz ? reinterpret_cast<const int*>(nz + noise_off) : nullptr,
+                               nz ? present : 0u, tp + tmpl_off, req.tlay.n_templates, tpresent, tp, req.tlay.ext_mask);
+        } else if (noise_off >= 0) {
             const double* nz = c->d_noisefit.as<double>();
             hipLaunchKernelGGL(vag_fit_back_noise_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av, fit_pass(),
                                next_order(), lk, lb, ls, d_theta, ndim, d_prior, nz, reinterpret_cast<const int*>(nz + noise_off), present);
@@ -4539,7 +4635,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
         if (rc == VAG_OK)
             rc = back(c->d_series_flux.as<double>(), n, d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n,
                       spec->ext_kernel ? d + 5 * (size_t)n : nullptr, req.lim ? req.llay.point : -1, req.noise ? req.nlay.point : -1,
-                      req.noise ? req.nlay.point_present : 0u);
+                      req.noise ? req.nlay.point_present : 0u, req.tmpl ? req.tlay.point : -1, req.tmpl ? req.tlay.point_present : 0u);
         if (rc == VAG_OK) {
             rc = finish_speculation(c);  // before a band group's own grid pass reuses the plan buffers
             n_cap = std::max(n_cap, c->plan.n_models_capacity);
@@ -4561,7 +4657,8 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
         rc = band_request_dev(c, d_params, nb, db, bd.n, bd.nu_min, bd.nu_max, bd.num_points, c->d_series_flux.as<double>(), nullptr);
         if (rc == VAG_OK)
             rc = back(c->d_series_flux.as<double>(), bd.n, db + bd.n, db + 2 * (size_t)bd.n, db + 3 * (size_t)bd.n, nullptr,
-                      req.lim ? req.llay.band[g] : -1, req.noise ? req.nlay.band[g] : -1, req.noise ? req.nlay.band_present[g] : 0u);
+                      req.lim ? req.llay.band[g] : -1, req.noise ? req.nlay.band[g] : -1, req.noise ? req.nlay.band_present[g] : 0u,
+                      req.tmpl ? req.tlay.band[g] : -1, req.tmpl ? req.tlay.band_present[g] : 0u);
     }
     size_t soff = 0;
     for (int g = 0; g < n_groups && rc == VAG_OK; ++g) {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
@@ -4728,7 +4825,7 @@ static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int n
     if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
     HIPCHK(hipSetDevice(c->device));
     rc = upload_fit_spec(c, req.spec, ndim, req.placed, req.pol != nullptr, req.noise ? req.nlay.n_groups : 0,
-                         req.counts || req.index || req.fold, req.fold && req.flay.any_sigma);
+                         req.counts || req.index || req.fold, req.fold && req.flay.any_sigma, req.tlay.n_templates);
     if (rc == VAG_OK && req.sky) rc = upload_sky_spec(c, req.sky);  // (n_groups = 0: the fixed placement alone)
     if (rc == VAG_OK && req.vis) rc = upload_vis_spec(c, req.vis);
     if (rc == VAG_OK && req.pol) rc = upload_pol_spec(c, req.pol);
@@ -4737,6 +4834,7 @@ static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int n
     if (rc == VAG_OK && req.counts) rc = upload_counts_spec(c, req.counts, req.cstage, req.clay);
     if (rc == VAG_OK && req.index) rc = upload_index_spec(c, req.index, req.istage);
     if (rc == VAG_OK && req.fold) rc = upload_fold_spec(c, req.fold, req.fstage);
+    if (rc == VAG_OK && req.tmpl) rc = upload_tmpl_spec(c, req.tstage, req.tlay);
     if (rc) return rc;
     rc = loglike_body(c, req, d_theta, nb, ndim, d_out, !c->count_work);
     if (rc == VAG_RETRY) rc = loglike_body(c, req, d_theta, nb, ndim, d_out, false);
@@ -4769,9 +4867,11 @@ static int loglike_host(vag_ctx* c, FitRequest& req, const double* theta, int nb
 static FitRequest fit_request(const vag_fit_spec* spec, const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
                               const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr,
                               const vag_noise_fit_spec* noise = nullptr, const vag_counts_fit_spec* counts = nullptr,
-                              const vag_index_fit_spec* index = nullptr, const vag_fold_fit_spec* fold = nullptr) {
+                              const vag_index_fit_spec* index = nullptr, const vag_fold_fit_spec* fold = nullptr,
+                              const vag_template_fit_spec* tmpl = nullptr) {
     FitRequest r;
     r.spec = spec, r.sky = sky, r.vis = vis, r.pol = pol, r.lim = lim, r.noise = noise, r.counts = counts, r.index = index, r.fold = fold;
+    r.tmpl = tmpl;
     return r;
 }
 
@@ -4832,6 +4932,14 @@ int vag_loglike_fold_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_s
                                const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
                                const double* d_theta, int nb, int ndim, double* d_out) {
     FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
+}
+
+int vag_loglike_tmpl_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                               const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                               const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                               const vag_template_fit_spec* tmpl, const double* d_theta, int nb, int ndim, double* d_out) {
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl);
     return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
@@ -5149,6 +5257,14 @@ int vag_loglike_fold_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_f
                            const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
                            const double* theta, int nb, int ndim, double* out) {
     FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold);
+    return loglike_host(c, r, theta, nb, ndim, out);
+}
+
+int vag_loglike_tmpl_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                           const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                           const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                           const vag_template_fit_spec* tmpl, const double* theta, int nb, int ndim, double* out) {
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl);
     return loglike_host(c, r, theta, nb, ndim, out);
 }
 

@@ -257,6 +257,129 @@ vag_fit_back_noise_kernel(const double* __restrict__ flux /* [nb][n] */, int n, 
     fit_close_pass(pass, m, lane, grid_ok, false, s);
 }
 
+// The model value of row i of a flux pass with additive templates (vag_loglike_tmpl_batch): with T [.][n] the pass's template block,
+// a[c] the walker's amplitudes and bit c of extm the template's `extinguished` flag,
+//   e = sum a_c T_c,i over the plain templates, x = sum a_c T_c,i over the extinguished ones (both from 0 in ascending c, one fma per
+//   term, only the templates of `present` read),  f = (F + x) exp(-A_V k_i) + e,
+// the extinction factor applied exactly where the other back kernels apply it.  The loop over the 8 bits is unrolled: a[] is indexed
+// by constants only and stays in registers.  All amplitudes 0: x = e = 0 and f is the other kernels' value, bit for bit.
+__device__ __forceinline__ double tmpl_model_value(double F, int i, int n, const double* __restrict__ T, unsigned present, unsigned extm,
+                                                   const double (&a)[VAG_TMPL_MAX], double av, const double* __restrict__ ext) {
+    double e = 0, x = 0;
+#pragma unroll
+    for (int c = 0; c < VAG_TMPL_MAX; ++c) {
+        if (!((present >> c) & 1u)) continue;
+        const double t = T[(size_t)c * n + i];
+        if ((extm >> c) & 1u)
+            x = fma(a[c], t, x);
+        else
+            e = fma(a[c], t, e);
+    }
+    double f = F + x;
+    if (av != 0.0) f = f * exp(-av * ext[i]);
+    return f + e;
+}
+
+// The back of a flux pass with a row that a template touches (vag_loglike_tmpl_batch).  The walker's amplitudes come first, once:
+// a_c is the free parameter with the slot VAG_P_TMPL_AMP0 + c (found as the noise kernel finds s_g), else amp_fixed[c], for
+// c < n_tmpl; they are wave-uniform.  A free amplitude that is not finite or is negative makes the walker `bad`: it scores -inf and
+// is counted like a walker whose vag_pol_spec is refused.  Then the terms of vag_fit_back_kernel<true> and vag_fit_back_noise_kernel,
+// statement for statement and in the same lane-strided order, on f_i = tmpl_model_value(...) in place of the model flux; grp is null
+// (and gpresent 0) when the pass has no grouped row.  A kernel of its own so that a pass no template touches runs the instructions it
+// always ran.
+__global__ void __launch_bounds__(64)
+vag_fit_back_tmpl_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const double* __restrict__ ln_flux,
+                         const double* __restrict__ ln_err, const double* __restrict__ weight, const double* __restrict__ ext /* or null */,
+                         const double* __restrict__ a_v, FitPass pass, FitOrderOut ord,
+                         const int* __restrict__ lim_kind /* [n] VAG_OBS_*, or null: no limit row in this pass */,
+                         const double* __restrict__ lim_L /* [n] */, const double* __restrict__ lim_sigma /* [n] */,
+                         const double* __restrict__ theta /* [nb][ndim] */, int ndim, const double* __restrict__ prior,
+                         const double* __restrict__ noise /* [sys_fixed 8 | calib 8], or null */,
+                         const int* __restrict__ grp /* [n] group id or -1, or null: no grouped row in this pass */,
+                         unsigned gpresent /* bit g: some row of the pass is in group g */,
+                         const double* __restrict__ tmpl /* [n_tmpl][n] the pass's template values */, int n_tmpl,
+                         unsigned tpresent /* bit c: template c touches some row of the pass */,
+                         const double* __restrict__ amp_fixed /* [8] */, unsigned extm /* bit c: template c is extinguished */) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    const bool grid_ok = pass.meta[m].status == 0;
+    fit_hand_over_order(pass, ord, m, lane);
+    const int walker = pass.order ? pass.order[m] : m;
+    const double av = (ext != nullptr) ? a_v[m] : 0.0;
+    const int* slot = reinterpret_cast<const int*>(prior + 64);
+    const int* is_log = slot + 16;
+    double a[VAG_TMPL_MAX];
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < VAG_TMPL_MAX; ++c) {
+        a[c] = 0.0;
+        if (c >= n_tmpl) continue;
+        a[c] = amp_fixed[c];
+        for (int d = 0; d < ndim; ++d) {
+            if (slot[d] != VAG_P_TMPL_AMP0 + c) continue;
+            const double v = theta[(size_t)walker * ndim + d];
+            a[c] = is_log[d] ? pow(10.0, v) : v;
+            bad = bad || !isfinite(a[c]) || a[c] < 0;
+        }
+    }
+    // The rounding of the lane's sum is stated, not left to the compiler, so that all amplitudes 0 is the pass without templates bit
+    // for bit: vag_fit_back_kernel<false> (no limit row, no group: a straight-line loop) accumulates with one fma per row,
+    // s = fma(w, q^2, s); the kernels whose loop branches on a limit row add the rounded product, s = s + w q^2.
+    const bool fused = !lim_kind && !grp;
+    double s = 0;
+    if (grid_ok)
+        for (int i = lane; i < n; i += 64) {
+            const bool is_lim = lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT;
+            if (grp && grp[i] >= 0 && !is_lim) continue;  // a grouped detection: in the turn of its group below
+            const double f = tmpl_model_value(flux[(size_t)m * n + i], i, n, tmpl, tpresent, extm, a, av, ext);
+            {
+#pragma clang fp contract(off)
+                if (is_lim) {
+                    s = s + weight[i] * (-2.0 * log_ndtr((lim_L[i] - f) / lim_sigma[i]));
+                    continue;
+                }
+                const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+                const double q = (ln_flux[i] - log(fm)) / ln_err[i];
+                s = fused ? fma(weight[i], q * q, s) : s + weight[i] * (q * q);
+            }
+        }
+    s = wave_sum(s);
+    if (grid_ok && grp) {
+        for (int g = 0; g < VAG_NOISE_MAX_GROUPS; ++g) {
+            if (!((gpresent >> g) & 1u)) continue;
+            double sg = noise[g];
+            for (int d = 0; d < ndim; ++d) {
+                if (slot[d] != VAG_P_NOISE_SYS0 + g) continue;
+                const double v = theta[(size_t)walker * ndim + d];
+                sg = is_log[d] ? pow(10.0, v) : v;
+            }
+            const double s2 = sg * sg, cg = noise[VAG_NOISE_MAX_GROUPS + g];
+            double A = 0, B = 0, P = 0, N = 0;
+            for (int i = lane; i < n; i += 64) {
+                if (grp[i] != g || (lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT)) continue;
+                const double f = tmpl_model_value(flux[(size_t)m * n + i], i, n, tmpl, tpresent, extm, a, av, ext);
+                const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+                const double r = ln_flux[i] - log(fm), sig2 = ln_err[i] * ln_err[i];
+                const double p = weight[i] / (sig2 + s2);
+                A += p * (r * r);
+                B += p * r;
+                P += p;
+                N += weight[i] * log1p(s2 / sig2);
+            }
+            A = wave_sum(A);
+            N = wave_sum(N);
+            double term = A + N;
+            if (cg > 0) {  // (wave-uniform) the calibration scale marginalised, as in vag_fit_back_noise_kernel
+                B = wave_sum(B);
+                P = wave_sum(P);
+                const double c2 = cg * cg;
+                term = A - c2 * (B * B) / (1.0 + c2 * P) + N + log1p(c2 * P);
+            }
+            s += term;  // (every lane holds the same sums; lane 0 stores)
+        }
+    }
+    fit_close_pass(pass, m, lane, grid_ok, bad, s);
+}
+
 // The back of a counts pass (vag_loglike_counts_batch).  flux [nb][ns] holds the walker's band-integrated flux at the group's ns
 // sample times; row i gathers its m samples in k order, mu_i = B_i + a_i sum_k F[idx[i m + k]], and adds w_i D(N_i, mu_i)
 // (poisson_deviance) to the lane's sum; a row with w_i = 0 adds nothing.  The lanes' sums are closed by wave_sum in the fixed order of

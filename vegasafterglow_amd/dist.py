@@ -31,6 +31,8 @@ _NO_INDEX = ("sharded likelihood calls do not support spectral indices (Fitter.a
              "(Fitter.device_evaluator / log_prob_batch)")
 _NO_FOLD = ("sharded likelihood calls do not support count spectra (Fitter.add_count_spectrum): evaluate on one device "
             "(Fitter.device_evaluator / log_prob_batch)")
+_NO_TEMPLATES = ("sharded likelihood calls do not support additive templates (templates=... of Fitter.add_flux_density / add_spectrum / "
+                 "add_flux): evaluate on one device (Fitter.device_evaluator / log_prob_batch)")
 
 
 def shard_range(n, rank, world):
@@ -115,6 +117,8 @@ class WalkerSharder:
             raise NotImplementedError(_NO_INDEX)
         if getattr(eval_dev, "has_count_spectra", False):
             raise NotImplementedError(_NO_FOLD)
+        if getattr(eval_dev, "has_templates", False):
+            raise NotImplementedError(_NO_TEMPLATES)
         self.eval_dev, self.group = eval_dev, group
         self.device = device if device is not None else _default_device(group)
         self.native = getattr(eval_dev, "native", None)
@@ -225,6 +229,8 @@ def sharded_loglike(samples, local_eval, group=None, device=None):
         raise NotImplementedError(_NO_INDEX)
     if getattr(getattr(local_eval, "__self__", None), "has_count_spectra", False):
         raise NotImplementedError(_NO_FOLD)
+    if getattr(getattr(local_eval, "__self__", None), "has_templates", False):
+        raise NotImplementedError(_NO_TEMPLATES)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     nb = samples.shape[0]
     if not (dist.is_available() and dist.is_initialized()):

@@ -174,15 +174,62 @@ def index_from_slope(slope, convention):
 
 
 def _widest_entry(lib, spec, suffix):
-    """The widest likelihood entry point of the loaded library and its trailing spec arguments: vag_loglike_fold_batch<suffix>, added
-    after ABI 13 and detected by symbol.  A library without it (VAG_LIB_PATH naming an older build) serves every fit without count
-    spectra through vag_loglike_index_batch<suffix>, the same call bit for bit; a fit with count spectra is an error there."""
+    """The widest likelihood entry point of the loaded library and its trailing spec arguments: vag_loglike_tmpl_batch<suffix>, then
+    vag_loglike_fold_batch<suffix>, both added after ABI 13 and detected by symbol.  A library without the first (VAG_LIB_PATH naming
+    an older build) serves every fit without templates through the fold entry, and one without that every fit without count spectra
+    through vag_loglike_index_batch<suffix>, the same call bit for bit; a fit with templates or count spectra is an error there."""
+    tmpl = getattr(spec, "_tmpl", None)
+    name = "vag_loglike_tmpl_batch" + suffix
+    if hasattr(lib, name):
+        return getattr(lib, name), (C.byref(spec._fold) if spec._fold is not None else None, C.byref(tmpl) if tmpl is not None else None)
+    if tmpl is not None:
+        raise RuntimeError(f"the loaded library has no {name}: additive templates (templates=... of Fitter.add_flux_density / "
+                           "add_spectrum / add_flux) need a newer build")
     name = "vag_loglike_fold_batch" + suffix
     if hasattr(lib, name):
         return getattr(lib, name), (C.byref(spec._fold) if spec._fold is not None else None,)
     if spec._fold is not None:
         raise RuntimeError(f"the loaded library has no {name}: count spectra (Fitter.add_count_spectrum) need a newer build")
     return getattr(lib, "vag_loglike_index_batch" + suffix), ()
+
+
+def _fma(a, b, c):
+    """a * b + c with one rounding, in numpy: the product split without error (Veltkamp / Dekker), the sum without error (Knuth), the
+    two error terms added to the rounded sum.  For finite operands far from overflow and underflow, as template values are."""
+    a, b, c = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (a, b, c)))
+    with np.errstate(all="ignore"):
+        p = a * b
+        ta, tb = 134217729.0 * a, 134217729.0 * b
+        ah, bh = ta - (ta - a), tb - (tb - b)
+        al, bl = a - ah, b - bh
+        ep = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+        s = p + c
+        v = s - p
+        es = (p - (s - v)) + (c - v)
+        return np.where(np.isfinite(ep + es), s + (ep + es), s)
+
+
+def template_terms(T, amp, extinguished):
+    """(e, x) of the additive templates, the numpy statement of the device's term: T [n_templates, n] the templates' values at the
+    rows, amp [..., n_templates] the amplitudes (one set per walker), extinguished [n_templates] flags;
+        e[..., i] = sum_c amp[..., c] T[c, i] over the templates with extinguished = 0,
+        x[..., i] = the same over the templates with extinguished = 1,
+    both from 0 in ascending c with one fma per term (_fma: exact to a rounding).  A row's model value is then
+    (F + x) exp(-A_V k) + e."""
+    T = np.asarray(T, dtype=np.float64)
+    amp = np.asarray(amp, dtype=np.float64)
+    flags = np.asarray(extinguished).astype(bool).reshape(-1)
+    if T.ndim != 2 or amp.shape[-1] != T.shape[0] or flags.size != T.shape[0]:
+        raise ValueError(f"template_terms: T must be [n_templates, n] with one amplitude and one flag per template, got T {T.shape}, "
+                         f"amp {amp.shape}, extinguished {flags.shape}")
+    e = np.zeros(amp.shape[:-1] + (T.shape[1],))
+    x = np.zeros_like(e)
+    for c in range(T.shape[0]):
+        if flags[c]:
+            x = _fma(amp[..., c, None], T[c], x)
+        else:
+            e = _fma(amp[..., c, None], T[c], e)
+    return e, x
 
 
 def _poisson_const(N):
@@ -268,6 +315,10 @@ class Fitter:
         self._point_grp = []  # per add_* call: the noise group id of its rows (noise=...), -1 = none
         self._noise_labels = []  # the noise groups in order of first mention: group g is self._noise_labels[g]
         self._noise_calib = {}  # label -> its calibration fraction, once a call has stated one
+        self._point_tmpl = []  # per add_* call: {template id: its values at the call's rows} (templates=...)
+        self._tmpl_names = []  # the templates in order of first mention: template c is self._tmpl_names[c]
+        self._tmpl_ext = []  # per template: its extinguished flag (add_template)
+        self._tmpl_used = set()  # the ids of the templates some row carries
         self._band_obs = []
         self._centroid_obs = []  # VLBI centroid groups (add_centroid): one vag_centroid_obs each
         self._vis_obs = []  # VLBI visibility groups (add_visibilities): one vag_visibility_obs each
@@ -353,7 +404,69 @@ class Fitter:
             self._noise_calib[noise] = calibration
         return self._noise_labels.index(noise)
 
-    def _add_points(self, t, nu, f_nu, err, w, lim, grp=-1):
+    def _checked_templates(self, templates, shape, who):
+        """{name: float64 array of ``shape``} of a templates= argument, checked and with nothing recorded: a dict of names matching
+        [A-Za-z0-9_]+ to a scalar or an array of the shape of the rows, finite and >= 0; at most 8 templates per fit."""
+        if templates is None:
+            return {}
+        if not isinstance(templates, dict):
+            raise ValueError(f"{who}: templates must be a dict {{name: values}}, got {type(templates).__name__}")
+        out = {}
+        for name, values in templates.items():
+            if not isinstance(name, str) or not re.fullmatch(r"[A-Za-z0-9_]+", name):
+                raise ValueError(f"{who}: a template name must match [A-Za-z0-9_]+, got {name!r}")
+            try:
+                v = np.asarray(values, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: the values of template {name!r} must be numbers") from None
+            if v.ndim != 0 and v.shape != shape:
+                raise ValueError(f"{who}: the values of template {name!r} must be a scalar or have the shape of the rows {shape}, "
+                                 f"got {v.shape}")
+            if not np.isfinite(v).all() or (v < 0).any():
+                raise ValueError(f"{who}: the values of template {name!r} must be finite and >= 0")
+            out[name] = np.full(shape, float(v)) if v.ndim == 0 else v.copy()
+        new = [name for name in out if name not in self._tmpl_names]
+        if len(self._tmpl_names) + len(new) > _lib.TMPL_MAX:
+            raise ValueError(f"{who}: at most {_lib.TMPL_MAX} templates, {new[_lib.TMPL_MAX - len(self._tmpl_names)]!r} would be one more")
+        return out
+
+    def _record_templates(self, checked):
+        """{template id: values} of what _checked_templates returned; new names are declared plain, in order of mention."""
+        out = {}
+        for name, v in checked.items():
+            if name not in self._tmpl_names:
+                self._tmpl_names.append(name)
+                self._tmpl_ext.append(False)
+            c = self._tmpl_names.index(name)
+            self._tmpl_used.add(c)
+            out[c] = v
+        return out
+
+    def add_template(self, name, extinguished=False):
+        """Declares the additive template ``name`` ahead of its first mention in a templates= argument -- the only way to set its
+        flag.  extinguished=True: the template's light passes the host's dust like the afterglow's (a supernova, a kilonova); False:
+        it does not (a host galaxy measured as it is seen).  A row's model value is (F + x) exp(-A_V k) + e with x / e the sums of
+        amplitude * value over the extinguished / plain templates; the amplitude is the parameter ``amp_<name>`` (free on linear
+        scale with lower >= 0, on log scale with lower > 0, or fixed >= 0; 0 when not given).  At most 8 templates per fit; the
+        flag cannot change once rows carry the template."""
+        if not isinstance(name, str) or not re.fullmatch(r"[A-Za-z0-9_]+", name):
+            raise ValueError(f"add_template: a template name must match [A-Za-z0-9_]+, got {name!r}")
+        if not isinstance(extinguished, (bool, np.bool_)):
+            raise ValueError(f"add_template: extinguished must be a bool, got {extinguished!r}")
+        if name in self._tmpl_names:
+            c = self._tmpl_names.index(name)
+            if c in self._tmpl_used and self._tmpl_ext[c] != bool(extinguished):
+                raise ValueError(f"add_template: rows already carry template {name!r} with extinguished={self._tmpl_ext[c]}: declare "
+                                 "it before its first mention")
+            self._tmpl_ext[c] = bool(extinguished)
+            return
+        if len(self._tmpl_names) >= _lib.TMPL_MAX:
+            raise ValueError(f"add_template: at most {_lib.TMPL_MAX} templates, {name!r} would be one more")
+        self._tmpl_names.append(name)
+        self._tmpl_ext.append(bool(extinguished))
+
+    def _add_points(self, t, nu, f_nu, err, w, lim, grp=-1, tmpl=None):
+        self._point_tmpl.append(tmpl or {})
         self._point_lim.append(lim)
         self._point_grp.append(np.full(t.shape, grp, dtype=np.int32))
         self._point_t.append(t)
@@ -364,11 +477,14 @@ class Fitter:
         self._all_t = None
 
     # fitter.py:256-282
-    def add_flux_density(self, nu, t, f_nu, err, weights=None, label=None, upper_limit=None, noise=None, calibration=None):
+    def add_flux_density(self, nu, t, f_nu, err, weights=None, label=None, upper_limit=None, noise=None, calibration=None,
+                         templates=None):
         """Light-curve data at one frequency nu [Hz] (`label` is accepted for API compatibility; it only names plot legends).
         upper_limit: None, a bool or a boolean mask of the shape of t; on a flagged row f_nu is the limit L and err the noise level
         sigma (Fitter._limit_mask).  noise, calibration: the noise group of the rows and its calibration fraction
-        (Fitter._noise_group)."""
+        (Fitter._noise_group).  templates: {name: values} of the additive templates at these rows, values a scalar or an array of the
+        shape of t in the unit of f_nu (Fitter.add_template); a host galaxy: templates={"host_r": 1.0} with the parameter
+        amp_host_r."""
         nu_arr = np.asarray(nu, dtype=np.float64)
         if not np.isfinite(nu_arr).all() or (nu_arr <= 0).any():
             raise ValueError(f"add_flux_density: nu must be finite and > 0, got {nu}")
@@ -376,14 +492,17 @@ class Fitter:
         if nu_arr.ndim != 0 and nu_arr.shape != t.shape:  # extension: one frequency per point
             raise ValueError(f"add_flux_density: an array nu must have the shape of t, got {nu_arr.shape} vs {t.shape}")
         lim = self._limit_mask(upper_limit, t, f_nu, "add_flux_density")
+        tmpl = self._checked_templates(templates, t.shape, "add_flux_density")
         grp = self._noise_group(noise, calibration, "add_flux_density")
-        self._add_points(t, np.full_like(t, float(nu_arr)) if nu_arr.ndim == 0 else nu_arr.copy(), f_nu, err, w, lim, grp)
+        self._add_points(t, np.full_like(t, float(nu_arr)) if nu_arr.ndim == 0 else nu_arr.copy(), f_nu, err, w, lim, grp,
+                         self._record_templates(tmpl))
 
     # fitter.py:284-314
-    def add_spectrum(self, t, nu, f_nu, err, weights=None, upper_limit=None, noise=None, calibration=None):
+    def add_spectrum(self, t, nu, f_nu, err, weights=None, upper_limit=None, noise=None, calibration=None, templates=None):
         """A broadband spectrum at one time t [s]: one point-data row per frequency.  upper_limit: None, a bool or a boolean mask of
         the shape of nu; on a flagged row f_nu is the limit L and err the noise level sigma (Fitter._limit_mask).  noise, calibration:
-        the noise group of the rows and its calibration fraction (Fitter._noise_group)."""
+        the noise group of the rows and its calibration fraction (Fitter._noise_group).  templates: {name: values} of the additive
+        templates at these rows, values a scalar or an array of the shape of nu (Fitter.add_template)."""
         if np.ndim(t) != 0 or not np.isfinite(t) or t <= 0:
             raise ValueError(f"add_spectrum: t must be finite and > 0, got {t}")
         nu = np.asarray(nu, dtype=np.float64)
@@ -392,16 +511,19 @@ class Fitter:
                              f"max={float(nu.max())})")
         nu, f_nu, err, w = self._checked_observations(nu, f_nu, err, weights, "add_spectrum")  # nu is the axis array here
         lim = self._limit_mask(upper_limit, nu, f_nu, "add_spectrum")
+        tmpl = self._checked_templates(templates, nu.shape, "add_spectrum")
         grp = self._noise_group(noise, calibration, "add_spectrum")
-        self._add_points(np.full_like(nu, float(t)), nu, f_nu, err, w, lim, grp)
+        self._add_points(np.full_like(nu, float(t)), nu, f_nu, err, w, lim, grp, self._record_templates(tmpl))
 
     # fitter.py:316-377
-    def add_flux(self, band, t, flux, err, num_points=5, weights=None, upper_limit=None, noise=None, calibration=None):
+    def add_flux(self, band, t, flux, err, num_points=5, weights=None, upper_limit=None, noise=None, calibration=None,
+                 templates=None):
         """Band-integrated fluxes [erg/cm^2/s] over band = (nu_min, nu_max) [Hz]; each group is one Model.flux request.
         upper_limit: None, a bool or a boolean mask of the shape of t; on a flagged row flux is the limit L >= 0 and err the noise
         level sigma (Fitter._limit_mask); detections need strictly positive fluxes.  noise, calibration: the noise group of the rows
         and its calibration fraction (Fitter._noise_group); a group with calibration > 0 holds point rows only or exactly one
-        add_flux call (build_spec checks it)."""
+        add_flux call (build_spec checks it).  templates: {name: values} of the additive templates at these rows, values a scalar or
+        an array of the shape of t in erg/cm^2/s (Fitter.add_template)."""
         try:
             nu_min, nu_max = band
         except (TypeError, ValueError):
@@ -417,10 +539,12 @@ class Fitter:
         lim = self._limit_mask(upper_limit, t, flux, "add_flux")
         if np.any(flux[~lim] <= 0):
             raise ValueError("add_flux: the log-flux likelihood requires strictly positive fluxes")
+        tmpl = self._checked_templates(templates, t.shape, "add_flux")
         order = np.argsort(t)
         bd = dict(nu_min=float(nu_min), nu_max=float(nu_max), num_points=int(num_points),
                   t=np.ascontiguousarray(t[order]), weights=np.ascontiguousarray(w[order]), lim=None,
                   noise=self._noise_group(noise, calibration, "add_flux"))
+        bd["tmpl"] = {c: np.ascontiguousarray(v[order]) for c, v in self._record_templates(tmpl).items()}  # the values follow the sort
         if lim.any():  # limit rows: ln_flux / ln_err are not read there (0 and 1); L and sigma go into their own arrays
             lim, flux, err = lim[order], flux[order], err[order]
             safe = np.where(lim, 1.0, flux)
@@ -820,6 +944,11 @@ class Fitter:
         """Some rows belong to a noise group (noise=... of add_flux_density / add_spectrum / add_flux)."""
         return bool(self._noise_labels)
 
+    @property
+    def has_templates(self):
+        """The fit has additive templates (templates=... of add_flux_density / add_spectrum / add_flux, or add_template)."""
+        return bool(self._tmpl_names)
+
     # fitter.py:407-451
     def _consolidate_data(self):
         if self._all_t is not None:
@@ -831,6 +960,7 @@ class Fitter:
                                  "add_counts, add_spectral_index or add_count_spectrum first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
             self._all_lim = self._all_grp = None
+            self._all_tmpl = {}
             return
         t = np.concatenate(self._point_t)
         nu = np.concatenate(self._point_nu)
@@ -841,6 +971,9 @@ class Fitter:
         order = np.argsort(t)
         t, nu, f, e, w = t[order], nu[order], f[order], e[order], w[order].copy()
         grp = np.concatenate(self._point_grp)[order]  # the noise group ids follow the sort
+        self._all_tmpl = {}  # template id -> its values at the consolidated rows (0 where a call did not mention it): they follow the sort
+        for c in sorted(set().union(*[set(d) for d in self._point_tmpl])):
+            self._all_tmpl[c] = np.concatenate([d[c] if c in d else np.zeros(ti.shape) for d, ti in zip(self._point_tmpl, self._point_t)])[order]
         self._all_grp = np.ascontiguousarray(grp, dtype=np.int32) if (grp >= 0).any() else None
         if lim.any():
             # upper-limit rows: the weights of the DETECTIONS are normalised to sum to their count, as without the limit rows; a limit
@@ -919,6 +1052,7 @@ class Fitter:
         names another one), so that the device applies the bounds mask and adds sum ln prior (samplers.py:72-91)."""
         self._consolidate_data()
         self._check_noise_parameters(param_defs)
+        self._check_template_parameters(param_defs)
         fixed = {pd.name: (pd.initial if pd.initial is not None else pd.lower) for pd in param_defs if pd.scale is Scale.fixed}
         free = [pd for pd in param_defs if pd.scale is not Scale.fixed]
         if len(free) > 16:
@@ -932,6 +1066,8 @@ class Fitter:
             if name in MODEL_PARAM_DEFAULTS or name in ("A_V", "N_H") or name in _lib.SKY_SLOTS or name in _lib.POL_SLOTS:
                 continue
             if self._noise_id(name) is not None:  # (goes into vag_noise_fit_spec.sys_fixed)
+                continue
+            if self._tmpl_id(name) is not None:  # (goes into vag_template_fit_spec.amp_fixed)
                 continue
             if name not in _lib.PARAM_SLOTS:
                 raise ValueError(f"parameter {name} is not accepted by the accelerated path")
@@ -948,6 +1084,8 @@ class Fitter:
                 spec.slot[d] = _lib.POL_SLOTS[pd.name]
             elif self._noise_id(pd.name) is not None:
                 spec.slot[d] = _lib.P_NOISE_SYS0 + self._noise_id(pd.name)
+            elif self._tmpl_id(pd.name) is not None:
+                spec.slot[d] = _lib.P_TMPL_AMP0 + self._tmpl_id(pd.name)
             elif pd.name not in _lib.PARAM_SLOTS:
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             else:
@@ -962,6 +1100,7 @@ class Fitter:
         spec._lim = self._lim_spec() if self.has_limits else None
         spec._noise = self._noise_spec(fixed) if self.has_noise_groups else None
         spec._counts = self._counts_spec() if self._counts_obs else None
+        spec._tmpl = self._tmpl_spec(fixed) if self.has_templates else None
         if self.extinction is not None and any(pd.name == "z" for pd in free):
             raise ValueError("a free 'z' cannot be combined with Fitter(extinction=...): the law's rest-frame wavelengths are fixed per fit")
         z_eff = float(fixed.get("z", self.z))
@@ -1197,6 +1336,72 @@ class Fitter:
         nz._keep_alive = (self._all_grp, band_ids)
         return nz
 
+    def _tmpl_id(self, name):
+        """The id of the parameter name ``amp_<name>`` of a declared template, else None."""
+        if not name.startswith(_lib.TMPL_PREFIX) or name[len(_lib.TMPL_PREFIX):] not in self._tmpl_names:
+            return None
+        return self._tmpl_names.index(name[len(_lib.TMPL_PREFIX):])
+
+    def _check_template_parameters(self, param_defs):
+        """``amp_<name>`` needs the template <name>; a fixed one is >= 0, a free one has lower >= 0 (> 0 on log scale)."""
+        for pd in param_defs:
+            if not pd.name.startswith(_lib.TMPL_PREFIX):
+                continue
+            if self._tmpl_id(pd.name) is None:
+                raise ValueError(f"the parameter {pd.name!r} needs the template {pd.name[len(_lib.TMPL_PREFIX):]!r} (templates=... of "
+                                 f"add_flux_density / add_spectrum / add_flux, or add_template; declared templates: {self._tmpl_names})")
+            if pd.scale is Scale.fixed:
+                value = pd.initial if pd.initial is not None else pd.lower
+                if not np.isfinite(value) or value < 0:
+                    raise ValueError(f"a fixed {pd.name} must be finite and >= 0, got {value!r}")
+            elif not pd.lower >= 0 or (pd.scale is Scale.log and not pd.lower > 0):
+                raise ValueError(f"{pd.name}: a free amplitude needs lower >= 0 (> 0 on log scale), got lower={pd.lower!r}")
+
+    def _tmpl_spec(self, fixed):
+        """vag_template_fit_spec of the templates: their values at the consolidated point rows and at the rows of the band groups
+        (0 where a template does not touch a row), the fixed amplitudes and the flags; it keeps the arrays it points at alive."""
+        tp = _lib.TemplateFitSpec()
+        nt = len(self._tmpl_names)
+        tp.n_templates = nt
+        for c, name in enumerate(self._tmpl_names):
+            tp.amp_fixed[c] = float(fixed.get(_lib.TMPL_PREFIX + name, 0.0))
+            tp.extinguished[c] = 1 if self._tmpl_ext[c] else 0
+        keep = []
+        if self._all_tmpl:
+            point = np.zeros((nt, self._all_t.size))
+            for c, v in self._all_tmpl.items():
+                point[c] = v
+            tp.point = point.ctypes.data_as(_dp)
+            keep.append(point)
+        if any(bd.get("tmpl") for bd in self._band_obs):
+            bands = (_dp * len(self._band_obs))()
+            for g, bd in enumerate(self._band_obs):
+                if not bd.get("tmpl"):
+                    continue  # (a null pointer: no template touches the group)
+                block = np.zeros((nt, bd["t"].size))
+                for c, v in bd["tmpl"].items():
+                    block[c] = v
+                bands[g] = block.ctypes.data_as(_dp)
+                keep.append(block)
+            tp.n_bands, tp.bands = len(self._band_obs), bands
+            keep.append(bands)
+        tp._keep_alive = keep
+        return tp
+
+    def template_amplitudes(self, sample, param_defs):
+        """{name: amplitude} of every template at a point of sampler space, in linear units (10^value for a log-scale parameter,
+        the fixed value, 0 when the parameter is not given): what multiplies the template's values in the model."""
+        spec, _, _ = self.build_spec(param_defs)
+        sample = np.asarray(sample, dtype=np.float64).reshape(-1)
+        if sample.size != spec.ndim:
+            raise ValueError(f"expected {spec.ndim} free parameters, got {sample.size}")
+        out = {name: (float(spec._tmpl.amp_fixed[c]) if spec._tmpl is not None else 0.0) for c, name in enumerate(self._tmpl_names)}
+        for d in range(spec.ndim):
+            c = spec.slot[d] - _lib.P_TMPL_AMP0
+            if 0 <= c < len(self._tmpl_names):
+                out[self._tmpl_names[c]] = float(10.0 ** sample[d] if spec.is_log[d] else sample[d])
+        return out
+
     def _lim_spec(self):
         """vag_limit_fit_spec of the upper-limit rows (parallel to the consolidated point rows, the band groups and the polarization
         groups); it keeps the arrays it points at alive."""
@@ -1345,7 +1550,8 @@ class Fitter:
             raise ValueError("duplicate parameter names")
         for pd in param_defs:
             if pd.name not in ("A_V", "N_H") and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS and pd.name not in _lib.POL_SLOTS \
-                    and not pd.name.startswith(_lib.NOISE_PREFIX):  # (sys_<label>: _check_noise_parameters below)
+                    and not pd.name.startswith(_lib.NOISE_PREFIX) and not pd.name.startswith(_lib.TMPL_PREFIX):
+                # (sys_<label>, amp_<name>: _check_noise_parameters, _check_template_parameters below)
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             if pd.scale is Scale.fixed:
                 continue
@@ -1357,6 +1563,7 @@ class Fitter:
             raise ValueError("A_V needs Fitter(extinction=...)")
         self._check_pol_parameters(names)
         self._check_noise_parameters(param_defs)
+        self._check_template_parameters(param_defs)
         self._check_n_h_parameter(param_defs)
 
     def _params_at(self, sample, param_defs, resolution=None):
@@ -1462,7 +1669,7 @@ class Fitter:
             def run():
                 ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
                 # the widest entry point: with a block absent (None) it is the narrower entry point, bit for bit
-                fn, fold = _widest_entry(lib, keep[0], "_dev")
+                fn, fold = _widest_entry(lib, keep[0], "_dev")  # (fold: the trailing specs, the fold block and the templates)
                 _lib.check(fn(h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
                               ref(keep[0]._noise), ref(keep[0]._counts), ref(keep[0]._index), *fold, theta.data_ptr(), k, keep[0].ndim,
                               values.data_ptr()))
@@ -1479,6 +1686,7 @@ class Fitter:
         eval_dev.has_counts = spec._counts is not None
         eval_dev.has_spectral_indices = spec._index is not None
         eval_dev.has_count_spectra = spec._fold is not None
+        eval_dev.has_templates = spec._tmpl is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -1489,6 +1697,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._tmpl is not None:
+                    from .dist import _NO_TEMPLATES
+                    raise NotImplementedError(_NO_TEMPLATES)
                 if keep[0]._fold is not None:
                     from .dist import _NO_FOLD
                     raise NotImplementedError(_NO_FOLD)
