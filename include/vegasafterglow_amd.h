@@ -867,6 +867,58 @@ int vag_loglike_tmpl_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag
                                const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
                                const vag_template_fit_spec* tmpl, const double* d_theta, int nb, int ndim, double* d_out);
 
+/* Correlated errors (added after VAG_ABI_VERSION 13, detect by symbol): radio light curves with interstellar scintillation,
+ * photometry that shares a zero point or a host subtraction, unfolded spectra with correlated bins.  A correlated group is n rows
+ * (t_i, nu_i), 1 <= n <= VAG_COV_MAX_ROWS; a fit holds at most VAG_COV_MAX_GROUPS groups.  Each group has rows with times ascending
+ * (equal times allowed), observed log fluxes ln_flux[i], an optional extinction kernel ext[i] = 0.4 ln10 k(lambda_rest) as on the
+ * point rows, a scalar weight w >= 0, and a whitener W: lower triangular with positive diagonal, W C_ln W^T = I, C_ln the covariance
+ * of the ln F_obs.  With F the walker's flux density at the rows, the sum of every enabled component as for point rows,
+ *   f_i = F_i exp(-A_V ext_i)               (the factor only when ext is given and A_V != 0, as vag_fit_back_kernel)
+ *   r_i = ln_flux_i - ln max(f_i, 1e-300)   (a NaN f_i stays NaN: the walker scores -inf)
+ *   y_i = sum_{j=0..i} W_ij r_j             (from 0, ascending j, one fma per term)
+ *   chi^2 += w sum_i y_i^2                  (lane-strided sums closed by wave_sum, the fixed order of the other back kernels)
+ * This is w r^T C_ln^-1 r.  The walker-independent ln det C_ln is not added, just as the plain chi^2 carries no sum ln sigma^2.  With
+ * C_ln = diag(sigma_ln^2) the term is the point rows' sum ((ln F_obs - ln f) / sigma_ln)^2; with C_ln = diag(sigma_ln^2) + c^2 1 1^T
+ * it is the calibration group's r^T C^-1 r.  Each group is a pass of its own, after the fold groups: one series request at its n
+ * points, then vag_fit_back_cov_kernel; a group with w = 0 still makes its request (the walker's validity is that of the pass) and
+ * adds 0.  A fit may hold nothing but correlated groups.  Out of scope: a free jitter or systematic on a correlated group, upper
+ * limits and templates inside one, correlations across groups, band-integrated rows with a covariance, n > VAG_COV_MAX_ROWS, and
+ * sharded calls. */
+#define VAG_COV_MAX_ROWS 256
+#define VAG_COV_MAX_GROUPS 8
+typedef struct vag_cov_obs {
+    int32_t n;                /* rows, 1 .. VAG_COV_MAX_ROWS */
+    const double* t;          /* [n] s, ascending */
+    const double* nu;         /* [n] Hz */
+    const double* ln_flux;    /* [n] ln F_obs */
+    const double* ext;        /* [n] 0.4 ln10 k(lambda_rest), or NULL */
+    const double* whitener;   /* [n][n] row-major; the entries j <= i are read */
+    double weight;            /* w >= 0 */
+} vag_cov_obs;
+typedef struct vag_cov_fit_spec {
+    int32_t n_groups;         /* 0 .. VAG_COV_MAX_GROUPS */
+    const vag_cov_obs* groups;
+} vag_cov_fit_spec;
+
+/* vag_loglike_tmpl_batch(_dev) with correlated groups.  With cov NULL or n_groups = 0 it is exactly that call, bit for bit: a fit
+ * without correlated groups launches what it launches there.  Refused with VAG_E_INVALID before the device is touched, the message
+ * naming group and row: n outside 1 .. VAG_COV_MAX_ROWS or n_groups outside 0 .. VAG_COV_MAX_GROUPS; a null array; a t or nu that is
+ * not finite or not positive, or descending t; a ln_flux or ext that is not finite; a whitener entry with j <= i that is not finite,
+ * or a diagonal entry <= 0; a weight that is negative or not finite.  A walker the pass rejects (grid capacity, ODE rows, SSC tables)
+ * scores -inf and is counted in vag_plan.n_walkers_rejected.  Results are bitwise reproducible and a walker's term does not depend on
+ * the rest of the batch or on its evaluation slot, under the conditions the index groups state.  The groups stay resident on the
+ * device by content hash, W stored transposed. */
+int vag_loglike_cov_batch(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                          const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                          const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                          const vag_template_fit_spec* tmpl, const vag_cov_fit_spec* cov, const double* theta, int nb, int ndim,
+                          double* out);
+int vag_loglike_cov_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                              const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                              const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                              const vag_template_fit_spec* tmpl, const vag_cov_fit_spec* cov, const double* d_theta, int nb, int ndim,
+                              double* d_out);
+
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.
  * Stream-ordered on the context stream, but host-blocking: the call returns after the batch's device plan has been read back

@@ -173,6 +173,18 @@ class TemplateFitSpec(C.Structure):  # vag_template_fit_spec
                 ("bands", C.POINTER(C.POINTER(C.c_double))), ("amp_fixed", C.c_double * 8), ("extinguished", C.c_int32 * 8)]
 
 
+COV_MAX_ROWS, COV_MAX_GROUPS = 256, 8  # VAG_COV_MAX_ROWS, VAG_COV_MAX_GROUPS
+
+
+class CovObs(C.Structure):  # vag_cov_obs
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + \
+               [(n, C.POINTER(C.c_double)) for n in ("t", "nu", "ln_flux", "ext", "whitener")] + [("weight", C.c_double)]
+
+
+class CovFitSpec(C.Structure):  # vag_cov_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(CovObs))]
+
+
 class FitSpec(C.Structure):
     _fields_ = [
         ("base", ModelParams), ("ndim", C.c_int32), ("slot", C.c_int32 * 16), ("is_log", C.c_int32 * 16),
@@ -239,6 +251,7 @@ EXPORTS = [
     "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev", "vag_loglike_noise_batch", "vag_loglike_noise_batch_dev",
     "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev", "vag_loglike_index_batch", "vag_loglike_index_batch_dev",
     "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev", "vag_loglike_tmpl_batch", "vag_loglike_tmpl_batch_dev",
+    "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev",
 ]
 
 _lib = None
@@ -332,6 +345,9 @@ def load():
                 C.POINTER(TemplateFitSpec)]
         lib.vag_loglike_tmpl_batch.argtypes = wide + [_dp, C.c_int, C.c_int, _dp]
         lib.vag_loglike_tmpl_batch_dev.argtypes = wide + [v, C.c_int, C.c_int, v]
+        if hasattr(lib, "vag_loglike_cov_batch"):  # (detected by symbol too: the template entry with the correlated groups behind it)
+            lib.vag_loglike_cov_batch.argtypes = wide + [C.POINTER(CovFitSpec), _dp, C.c_int, C.c_int, _dp]
+            lib.vag_loglike_cov_batch_dev.argtypes = wide + [C.POINTER(CovFitSpec), v, C.c_int, C.c_int, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

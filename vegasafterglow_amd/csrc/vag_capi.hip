@@ -415,6 +415,7 @@ struct vag_ctx {
     DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_noisefit;  // noise groups of the likelihood (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
     DevBuf d_tmplfit;  // additive templates of the likelihood (vag_loglike_tmpl_batch): [amp_fixed 8] then per touched pass its [n_templates][n] values, see TmplLayout
+    DevBuf d_covfit;  // correlated groups of the likelihood (vag_loglike_cov_batch): per group [t | nu | ln_flux | ext | Wt], see CovLayout
     DevBuf d_countsfit;  // counts groups of the likelihood (vag_loglike_counts_batch): per group [t_sample | N | B | a | w | idx], see CountsLayout
     DevBuf d_foldfit;   // fold groups of the likelihood (vag_loglike_fold_batch): per group the block FoldLayout describes
     DevBuf d_indexfit;  // spectral-index groups of the likelihood (vag_loglike_index_batch): per group [t | nu | s | sigma | w | c], see IndexLayout
@@ -472,7 +473,7 @@ struct vag_ctx {
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
     DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit, h_indexfit, h_foldfit, h_tmplfit;
+    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit, h_indexfit, h_foldfit, h_tmplfit, h_covfit;
     uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
     size_t skyfit_doubles = 0;
     bool skyfit_hash_valid = false;
@@ -506,6 +507,9 @@ struct vag_ctx {
     uint64_t tmplfit_hash = 0;  // (d_tmplfit: the templates of vag_loglike_tmpl_batch, upload_tmpl_spec)
     size_t tmplfit_doubles = 0;
     bool tmplfit_hash_valid = false;
+    uint64_t covfit_hash = 0;  // (d_covfit: the correlated groups of vag_loglike_cov_batch, upload_cov_spec)
+    size_t covfit_doubles = 0;
+    bool covfit_hash_valid = false;
     size_t fit_doubles = 0, fit_prior_off = 0;
     bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
@@ -749,8 +753,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->h_indexfit.release();
     c->h_foldfit.release();
     c->h_tmplfit.release();
+    c->h_covfit.release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit, &c->d_indexfit, &c->d_foldfit, &c->d_tmplfit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit, &c->d_indexfit, &c->d_foldfit, &c->d_tmplfit, &c->d_covfit})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -4484,6 +4489,79 @@ static int upload_fold_spec(vag_ctx* c, const vag_fold_fit_spec* fs, const std::
     return VAG_OK;
 }
 
+// ---- correlated groups (vag_loglike_cov_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
+//      in doubles, per group: [t n | nu n | ln_flux n | ext n | Wt n n]; the first two are the series points as prep_times takes
+//      them; ext is zeros for a group without one (the kernel is handed a null pointer then); Wt[j n + i] = W_ij for j <= i, else 0:
+//      the whitener transposed, so that a wavefront whose lanes hold consecutive rows i loads consecutive doubles. ----
+struct CovLayout {
+    std::vector<long> off;  // where group g starts in d_covfit
+    int n_groups = 0;
+};
+
+// Validates the correlated groups and lays their blocks out in stage (host work only: no context is touched).
+static int cov_scan(const vag_cov_fit_spec* cs, std::vector<double>& stage, CovLayout& lay) {
+    if (cs->n_groups < 0 || cs->n_groups > VAG_COV_MAX_GROUPS)
+        return set_err(VAG_E_INVALID, "correlated groups: n_groups must be in 0..%d, got %d", VAG_COV_MAX_GROUPS, cs->n_groups);
+    if (!cs->groups) return set_err(VAG_E_INVALID, "correlated groups: null group list");
+    lay.n_groups = cs->n_groups;
+    lay.off.clear();
+    stage.clear();
+    for (int g = 0; g < cs->n_groups; ++g) {
+        const vag_cov_obs& o = cs->groups[g];
+        if (o.n < 1 || o.n > VAG_COV_MAX_ROWS)
+            return set_err(VAG_E_INVALID, "correlated group %d: n (rows) must be in 1..%d, got %d", g, VAG_COV_MAX_ROWS, o.n);
+        if (!o.t || !o.nu || !o.ln_flux || !o.whitener) return set_err(VAG_E_INVALID, "correlated group %d: null array", g);
+        if (!std::isfinite(o.weight) || o.weight < 0)
+            return set_err(VAG_E_INVALID, "correlated group %d: the weight must be finite and >= 0", g);
+        const size_t n = (size_t)o.n;
+        for (int i = 0; i < o.n; ++i) {
+            if (!std::isfinite(o.t[i]) || !(o.t[i] > 0) || (i > 0 && o.t[i] < o.t[i - 1]))
+                return set_err(VAG_E_INVALID, "correlated group %d, row %d: times must be finite, > 0 and ascending", g, i);
+            if (!std::isfinite(o.nu[i]) || !(o.nu[i] > 0))
+                return set_err(VAG_E_INVALID, "correlated group %d, row %d: the frequency must be finite and > 0", g, i);
+            if (!std::isfinite(o.ln_flux[i])) return set_err(VAG_E_INVALID, "correlated group %d, row %d: ln_flux is not finite", g, i);
+            if (o.ext && !std::isfinite(o.ext[i])) return set_err(VAG_E_INVALID, "correlated group %d, row %d: ext is not finite", g, i);
+            for (int j = 0; j <= i; ++j)
+                if (!std::isfinite(o.whitener[i * n + j]))
+                    return set_err(VAG_E_INVALID, "correlated group %d, row %d: whitener entry %d is not finite", g, i, j);
+            if (!(o.whitener[i * n + i] > 0))
+                return set_err(VAG_E_INVALID, "correlated group %d, row %d: the whitener's diagonal entry must be > 0", g, i);
+        }
+        const size_t at = stage.size();
+        lay.off.push_back((long)at);
+        stage.resize(at + 4 * n + n * n, 0.0);
+        double* dst = stage.data() + at;
+        std::memcpy(dst, o.t, sizeof(double) * n);
+        std::memcpy(dst + n, o.nu, sizeof(double) * n);
+        std::memcpy(dst + 2 * n, o.ln_flux, sizeof(double) * n);
+        if (o.ext) std::memcpy(dst + 3 * n, o.ext, sizeof(double) * n);
+        double* Wt = dst + 4 * n;
+        for (size_t i = 0; i < n; ++i)
+            for (size_t j = 0; j <= i; ++j) Wt[j * n + i] = o.whitener[i * n + j];
+    }
+    return VAG_OK;
+}
+
+static int upload_cov_spec(vag_ctx* c, const vag_cov_fit_spec* cs, const std::vector<double>& stage) {
+    uint64_t h = 1469598103934665603ull;
+    for (int g = 0; g < cs->n_groups; ++g) {  // (the shapes: two groups whose blocks hold the same bytes are still two layouts)
+        const int head[2] = {cs->groups[g].n, cs->groups[g].ext ? 1 : 0};
+        h = fnv1a(h, head, sizeof head);
+    }
+    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
+    if (c->covfit_hash_valid && c->covfit_hash == h && c->covfit_doubles == stage.size()) return VAG_OK;  // resident already
+    c->covfit_hash_valid = false;
+    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
+    if (c->h_covfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    if (c->d_covfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
+    std::memcpy(c->h_covfit.as<double>(), stage.data(), sizeof(double) * stage.size());
+    HIPCHK(hipMemcpyAsync(c->d_covfit.p, c->h_covfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
+    c->covfit_hash = h;
+    c->covfit_doubles = stage.size();
+    c->covfit_hash_valid = true;
+    return VAG_OK;
+}
+
 // ---- one likelihood request.  Every vag_loglike_*_batch entry point fills a FitRequest from its arguments (a spec it does not take
 //      stays null) and calls loglike_dev or loglike_host; a request whose optional blocks are null or empty is therefore the narrower
 //      entry point's request, statement for statement. ----
@@ -4499,13 +4577,15 @@ struct FitRequest {
     const vag_index_fit_spec* index = nullptr;
     const vag_fold_fit_spec* fold = nullptr;
     const vag_template_fit_spec* tmpl = nullptr;  // after fit_request_prepare: null when no row is touched (tlay.any)
+    const vag_cov_fit_spec* cov = nullptr;        // after fit_request_prepare: null when it has no group
     LimLayout llay;
     NoiseLayout nlay;
     CountsLayout clay;
     IndexLayout ilay;
     FoldLayout flay;
     TmplLayout tlay;
-    std::vector<double> lstage, nstage, cstage, istage, fstage, tstage;  // what the scans lay out for upload_{lim,noise,counts,index,fold,tmpl}_spec
+    CovLayout vlay;
+    std::vector<double> lstage, nstage, cstage, istage, fstage, tstage, vstage;  // what the scans lay out for upload_{lim,noise,counts,index,fold,tmpl,cov}_spec
     bool placed = false;                                 // some group reads east0 / north0
     bool prepared = false;                               // fit_request_prepare has run
 };
@@ -4518,7 +4598,9 @@ static int fit_request_prepare(FitRequest& r) {
     if (r.counts && r.counts->n_groups == 0) r.counts = nullptr;
     if (r.index && r.index->n_groups == 0) r.index = nullptr;
     if (r.fold && r.fold->n_groups == 0) r.fold = nullptr;
+    if (r.cov && r.cov->n_groups == 0) r.cov = nullptr;
     int rc = VAG_OK;
+    if (r.cov && (rc = cov_scan(r.cov, r.vstage, r.vlay))) return rc;
     if (r.tmpl && (rc = tmpl_scan(r.spec, r.tmpl, r.tstage, r.tlay))) return rc;
     if (r.fold && (rc = fold_scan(r.spec, r.fold, r.fstage, r.flay))) return rc;
     if (r.index && (rc = index_scan(r.index, r.istage, r.ilay))) return rc;
@@ -4577,8 +4659,9 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = req.vis ? req.vis->n_groups : 0;
     const int n_pol_groups = req.pol ? req.pol->n_groups : 0, n_counts_groups = req.counts ? req.counts->n_groups : 0;
     const int n_index_groups = req.index ? req.index->n_groups : 0, n_fold_groups = req.fold ? req.fold->n_groups : 0;
+    const int n_cov_groups = req.cov ? req.cov->n_groups : 0;
     const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups + n_counts_groups + n_index_groups +
-                       n_fold_groups;
+                       n_fold_groups + n_cov_groups;
     int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // what the current pass's back kernel receives (built at its launch: the model stages may have moved the buffers); the SSC tables
     // of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
@@ -4799,6 +4882,22 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
             rc = end_pass();
         }
     }
+    for (int g = 0; g < n_cov_groups && rc == VAG_OK; ++g) {  // correlated groups: the n rows as one series request each, then the whitened term
+        const vag_cov_obs& o = req.cov->groups[g];
+        const double* dv = c->d_covfit.as<double>() + req.vlay.off[g];  // [t | nu | ln_flux | ext | Wt]
+        const size_t nr = (size_t)o.n;
+        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(nr, (size_t)std::max(n, 1)))) return VAG_E_HIP;
+        rc = prep_times(c, dv, o.n, dv + nr, o.n);
+        begin_pass();
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
+        if (rc == VAG_OK)  // (n <= 256 points: the shared-node path of a short series when the rows hold <= 8 distinct frequencies)
+            rc = series_request(c, d_params, nb, o.n, c->d_series_flux.as<double>(), upload_series_bands(c, o.nu, o.n));
+        if (rc == VAG_OK) {
+            hipLaunchKernelGGL(vag_fit_back_cov_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, dv + 2 * nr,
+                               o.ext ? dv + 3 * nr : nullptr, dv + 4 * nr, o.weight, d_av, fit_pass(), next_order());
+            rc = end_pass();
+        }
+    }
     c->ic_soft_fail = false;
     c->plan.n_models_capacity = n_cap;
     c->plan.n_models_invalid = n_inv;
@@ -4825,7 +4924,7 @@ static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int n
     if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
     HIPCHK(hipSetDevice(c->device));
     rc = upload_fit_spec(c, req.spec, ndim, req.placed, req.pol != nullptr, req.noise ? req.nlay.n_groups : 0,
-                         req.counts || req.index || req.fold, req.fold && req.flay.any_sigma, req.tlay.n_templates);
+                         req.counts || req.index || req.fold || req.cov, req.fold && req.flay.any_sigma, req.tlay.n_templates);
     if (rc == VAG_OK && req.sky) rc = upload_sky_spec(c, req.sky);  // (n_groups = 0: the fixed placement alone)
     if (rc == VAG_OK && req.vis) rc = upload_vis_spec(c, req.vis);
     if (rc == VAG_OK && req.pol) rc = upload_pol_spec(c, req.pol);
@@ -4835,6 +4934,7 @@ static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int n
     if (rc == VAG_OK && req.index) rc = upload_index_spec(c, req.index, req.istage);
     if (rc == VAG_OK && req.fold) rc = upload_fold_spec(c, req.fold, req.fstage);
     if (rc == VAG_OK && req.tmpl) rc = upload_tmpl_spec(c, req.tstage, req.tlay);
+    if (rc == VAG_OK && req.cov) rc = upload_cov_spec(c, req.cov, req.vstage);
     if (rc) return rc;
     rc = loglike_body(c, req, d_theta, nb, ndim, d_out, !c->count_work);
     if (rc == VAG_RETRY) rc = loglike_body(c, req, d_theta, nb, ndim, d_out, false);
@@ -4868,10 +4968,10 @@ static FitRequest fit_request(const vag_fit_spec* spec, const vag_sky_fit_spec* 
                               const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr,
                               const vag_noise_fit_spec* noise = nullptr, const vag_counts_fit_spec* counts = nullptr,
                               const vag_index_fit_spec* index = nullptr, const vag_fold_fit_spec* fold = nullptr,
-                              const vag_template_fit_spec* tmpl = nullptr) {
+                              const vag_template_fit_spec* tmpl = nullptr, const vag_cov_fit_spec* cov = nullptr) {
     FitRequest r;
     r.spec = spec, r.sky = sky, r.vis = vis, r.pol = pol, r.lim = lim, r.noise = noise, r.counts = counts, r.index = index, r.fold = fold;
-    r.tmpl = tmpl;
+    r.tmpl = tmpl, r.cov = cov;
     return r;
 }
 
@@ -4940,6 +5040,15 @@ int vag_loglike_tmpl_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_s
                                const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
                                const vag_template_fit_spec* tmpl, const double* d_theta, int nb, int ndim, double* d_out) {
     FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
+}
+
+int vag_loglike_cov_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                              const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                              const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                              const vag_template_fit_spec* tmpl, const vag_cov_fit_spec* cov, const double* d_theta, int nb, int ndim,
+                              double* d_out) {
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl, cov);
     return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
@@ -5265,6 +5374,15 @@ int vag_loglike_tmpl_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_f
                            const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
                            const vag_template_fit_spec* tmpl, const double* theta, int nb, int ndim, double* out) {
     FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl);
+    return loglike_host(c, r, theta, nb, ndim, out);
+}
+
+int vag_loglike_cov_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fit_spec* sky, const vag_vis_fit_spec* vis,
+                          const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, const vag_noise_fit_spec* noise,
+                          const vag_counts_fit_spec* counts, const vag_index_fit_spec* index, const vag_fold_fit_spec* fold,
+                          const vag_template_fit_spec* tmpl, const vag_cov_fit_spec* cov, const double* theta, int nb, int ndim,
+                          double* out) {
+    FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl, cov);
     return loglike_host(c, r, theta, nb, ndim, out);
 }
 

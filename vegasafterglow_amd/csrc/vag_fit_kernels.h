@@ -1,6 +1,6 @@
 // vag_fit_kernels.h -- the kernels of a likelihood call (vag_loglike_*_batch): its front, the back kernel of every kind of pass, and
 // the walkers' polarization spec.  A call is one front launch and then one pass per block of data -- the point rows, every band,
-// centroid, visibility, polarization, counts, spectral-index and fold group -- each pass a model request followed by its back kernel, one
+// centroid, visibility, polarization, counts, spectral-index, fold and correlated group -- each pass a model request followed by its back kernel, one
 // wavefront per walker.  What the back kernels share is the pass protocol below: FitPass and the two helpers.
 #pragma once
 #include "vag_fold.h"
@@ -490,6 +490,52 @@ vag_fit_back_fold_kernel(const double* __restrict__ flux /* [nb][ns J] */, int n
         }
     }
     s = 2.0 * wave_sum(s) + const2;
+    fit_close_pass(pass, m, lane, grid_ok, false, s);
+}
+
+// The back of a correlated group's pass (vag_loglike_cov_batch).  flux [nb][n] holds the walker's flux density at the group's rows.
+// Phase 1: the lanes stride the rows and write r_i = ln F_obs,i - ln max(F_i e^{-A_V k_i}, 1e-300) (the statements of
+// vag_fit_back_kernel: a NaN stays NaN) to the LDS row.  Phase 2, behind the barrier: lane l takes the rows i = l, l + 64, ... in
+// ascending order and forms y_i = sum_{j=0..i} W_ij r_j from 0 in ascending j with one fma per term, r_j the LDS broadcast and W_ij
+// read from the transposed copy Wt[j n + i] (the wavefront's loads are consecutive doubles), then s = fma(y_i, y_i, s).  The j loop
+// is wave-uniform: it runs to the largest row of the wavefront's block of 64, and a lane keeps its y where j > i (a select, not a
+// product with the stored zero: the value is that of a loop to the lane's own i, whatever r_j holds); a lane past n reads row n - 1
+// and keeps nothing.  The lanes' sums are closed by wave_sum in the fixed order of the other back kernels, so the value depends on
+// the walker's own row of flux alone; the pass adds w sum y^2, and 0 without reading a row when w = 0.  One wavefront per block: the
+// barrier is wave-uniform (grid_ok and w are).
+__global__ void __launch_bounds__(64)
+vag_fit_back_cov_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const double* __restrict__ ln_flux,
+                        const double* __restrict__ ext /* [n] or null */, const double* __restrict__ Wt /* [n][n]: Wt[j n + i] = W_ij */,
+                        double w, const double* __restrict__ a_v, FitPass pass, FitOrderOut ord) {
+    __shared__ double s_r[VAG_COV_MAX_ROWS];
+    const int m = blockIdx.x, lane = threadIdx.x;
+    const bool grid_ok = pass.meta[m].status == 0;
+    fit_hand_over_order(pass, ord, m, lane);
+    const double av = (ext != nullptr) ? a_v[m] : 0.0;
+    double s = 0;
+    if (grid_ok && w != 0.0) {  // (w = 0: the pass's validity alone, the term is 0)
+        for (int i = lane; i < n; i += 64) {
+            double f = flux[(size_t)m * n + i];
+            if (av != 0.0) f = f * exp(-av * ext[i]);
+            const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+            s_r[i] = ln_flux[i] - log(fm);
+        }
+        __syncthreads();
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const bool on = i < n;
+            const double* col = Wt + (on ? i : n - 1);
+            const int j_end = min(i0 + 64, n);  // one past the block's largest row
+            double y = 0;
+#pragma unroll 4
+            for (int j = 0; j < j_end; ++j) {
+                const double yj = fma(col[(size_t)j * n], s_r[j], y);
+                y = j <= i ? yj : y;
+            }
+            s = on ? fma(y, y, s) : s;
+        }
+    }
+    s = w * wave_sum(s);
     fit_close_pass(pass, m, lane, grid_ok, false, s);
 }
 

@@ -33,6 +33,8 @@ _NO_FOLD = ("sharded likelihood calls do not support count spectra (Fitter.add_c
             "(Fitter.device_evaluator / log_prob_batch)")
 _NO_TEMPLATES = ("sharded likelihood calls do not support additive templates (templates=... of Fitter.add_flux_density / add_spectrum / "
                  "add_flux): evaluate on one device (Fitter.device_evaluator / log_prob_batch)")
+_NO_CORRELATED = ("sharded likelihood calls do not support correlated groups (Fitter.add_correlated): evaluate on one device "
+                  "(Fitter.device_evaluator / log_prob_batch)")
 
 
 def shard_range(n, rank, world):
@@ -119,6 +121,8 @@ class WalkerSharder:
             raise NotImplementedError(_NO_FOLD)
         if getattr(eval_dev, "has_templates", False):
             raise NotImplementedError(_NO_TEMPLATES)
+        if getattr(eval_dev, "has_correlated", False):
+            raise NotImplementedError(_NO_CORRELATED)
         self.eval_dev, self.group = eval_dev, group
         self.device = device if device is not None else _default_device(group)
         self.native = getattr(eval_dev, "native", None)
@@ -231,6 +235,8 @@ def sharded_loglike(samples, local_eval, group=None, device=None):
         raise NotImplementedError(_NO_FOLD)
     if getattr(getattr(local_eval, "__self__", None), "has_templates", False):
         raise NotImplementedError(_NO_TEMPLATES)
+    if getattr(getattr(local_eval, "__self__", None), "has_correlated", False):
+        raise NotImplementedError(_NO_CORRELATED)
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     nb = samples.shape[0]
     if not (dist.is_available() and dist.is_initialized()):

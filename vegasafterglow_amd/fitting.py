@@ -174,11 +174,20 @@ def index_from_slope(slope, convention):
 
 
 def _widest_entry(lib, spec, suffix):
-    """The widest likelihood entry point of the loaded library and its trailing spec arguments: vag_loglike_tmpl_batch<suffix>, then
-    vag_loglike_fold_batch<suffix>, both added after ABI 13 and detected by symbol.  A library without the first (VAG_LIB_PATH naming
-    an older build) serves every fit without templates through the fold entry, and one without that every fit without count spectra
-    through vag_loglike_index_batch<suffix>, the same call bit for bit; a fit with templates or count spectra is an error there."""
+    """The likelihood entry point that serves the spec, and its trailing spec arguments.  A fit with correlated groups goes through
+    vag_loglike_cov_batch<suffix>; every other fit through the widest of vag_loglike_tmpl_batch<suffix> and
+    vag_loglike_fold_batch<suffix> that the loaded library has, the call it always made.  All three were added after ABI 13 and are
+    detected by symbol.  A library without the template entry (VAG_LIB_PATH naming an older build) serves every fit without templates
+    through the fold entry, and one without that every fit without count spectra through vag_loglike_index_batch<suffix>, the same
+    call bit for bit; a fit with correlated groups, templates or count spectra is an error where its entry is missing."""
     tmpl = getattr(spec, "_tmpl", None)
+    cov = getattr(spec, "_cov", None)
+    if cov is not None:
+        name = "vag_loglike_cov_batch" + suffix
+        if not hasattr(lib, name):
+            raise RuntimeError(f"the loaded library has no {name}: correlated groups (Fitter.add_correlated) need a newer build")
+        return getattr(lib, name), (C.byref(spec._fold) if spec._fold is not None else None, C.byref(tmpl) if tmpl is not None else None,
+                                    C.byref(cov))
     name = "vag_loglike_tmpl_batch" + suffix
     if hasattr(lib, name):
         return getattr(lib, name), (C.byref(spec._fold) if spec._fold is not None else None, C.byref(tmpl) if tmpl is not None else None)
@@ -230,6 +239,59 @@ def template_terms(T, amp, extinguished):
         else:
             e = _fma(amp[..., c, None], T[c], e)
     return e, x
+
+
+def covariance_whitener(C):
+    """The whitener W of a covariance C [n, n]: lower triangular with positive diagonal, W C W^T = I -- the inverse of C's Cholesky
+    factor L, formed column by column by forward substitution.  C must be finite, symmetric (|C_ij - C_ji| <= 1e-12 sqrt(C_ii C_jj))
+    and positive definite.  Raises ValueError("... too ill-conditioned") when max |W C W^T - I|, formed in numpy.longdouble, exceeds
+    1e-6: the fitter's default rtol, beyond which the term is wrong at the level of the model itself."""
+    C_ = np.asarray(C, dtype=np.float64)
+    if C_.ndim != 2 or C_.shape[0] != C_.shape[1] or C_.shape[0] == 0:
+        raise ValueError(f"covariance_whitener: the covariance must be [n, n] with n >= 1, got {C_.shape}")
+    if not np.isfinite(C_).all():
+        raise ValueError("covariance_whitener: the covariance must be finite")
+    n = C_.shape[0]
+    if n > _lib.COV_MAX_ROWS:
+        raise ValueError(f"covariance_whitener: at most {_lib.COV_MAX_ROWS} rows per correlated group, got {n}")
+    d = np.diag(C_)
+    if (d <= 0).any():
+        raise ValueError("covariance_whitener: the covariance is not positive definite (a diagonal entry is <= 0)")
+    scale = np.sqrt(d[:, None] * d[None, :])
+    if (np.abs(C_ - C_.T) > 1e-12 * scale).any():
+        raise ValueError("covariance_whitener: the covariance is not symmetric (|C_ij - C_ji| > 1e-12 sqrt(C_ii C_jj))")
+    try:
+        L = np.linalg.cholesky(C_)
+    except np.linalg.LinAlgError:
+        raise ValueError("covariance_whitener: the covariance is not positive definite") from None
+    W = np.zeros_like(C_)
+    for k in range(n):  # column k of L^-1: forward substitution on the k-th unit vector
+        for i in range(k, n):
+            s = (1.0 if i == k else 0.0) - np.dot(L[i, k:i], W[k:i, k])
+            W[i, k] = s / L[i, i]
+    Wl, Cl = W.astype(np.longdouble), C_.astype(np.longdouble)
+    resid = np.abs(Wl @ Cl @ Wl.T - np.eye(n, dtype=np.longdouble)).max()
+    if not np.isfinite(W).all() or not resid <= 1e-6:
+        raise ValueError(f"covariance_whitener: the covariance is too ill-conditioned (max |W C W^T - I| = {float(resid):.3g} > 1e-6)")
+    return W
+
+
+def whitened_chi2(r, W):
+    """sum_i (sum_{j <= i} W_ij r_j)^2 along the last axis of r [..., n], W [n, n] lower triangular: the numpy statement of the
+    device's correlated-group term.  Each y_i is summed from 0 in ascending j, then the squares in ascending i (the device forms y_i
+    with one fma per term and closes lane-strided sums: the two agree to rounding)."""
+    r = np.asarray(r, dtype=np.float64)
+    W = np.asarray(W, dtype=np.float64)
+    n = r.shape[-1]
+    if W.shape != (n, n):
+        raise ValueError(f"whitened_chi2: W must be [{n}, {n}], got {W.shape}")
+    chi2 = np.zeros(r.shape[:-1])
+    for i in range(n):
+        y = np.zeros(r.shape[:-1])
+        for j in range(i + 1):
+            y = y + W[i, j] * r[..., j]
+        chi2 = chi2 + y * y
+    return chi2
 
 
 def _poisson_const(N):
@@ -326,6 +388,7 @@ class Fitter:
         self._counts_obs = []  # photon-count groups (add_counts): one vag_counts_obs each
         self._index_obs = []  # spectral-index groups (add_spectral_index): one vag_index_obs each
         self._fold_obs = []  # count-spectrum groups (add_count_spectrum): one vag_fold_obs each
+        self._cov_obs = []  # correlated groups (add_correlated): one vag_cov_obs each
         self._ext_kernel = None
         self._ext_kernels = {}  # z -> 0.4 ln10 k(lambda_rest) over the consolidated point data
         self._ext_z = float(z)
@@ -684,6 +747,60 @@ class Fitter:
         """Some data are spectral indices (add_spectral_index)."""
         return bool(self._index_obs)
 
+    def add_correlated(self, nu, t, f_nu, cov, weight=1.0):
+        """Flux densities f_nu at times t [s] and frequency nu [Hz] (a scalar or an array of the shape of t) whose errors are
+        correlated: cov [n, n] is their covariance in the unit of f_nu squared, 1 <= n <= 256; a fit holds at most 8 such groups.
+        The group adds weight * r^T C_ln^-1 r to chi^2, r_i = ln f_nu,i - ln F_model,i (with the host's extinction as on the point
+        rows) and C_ln,ij = cov_ij / (f_i f_j) the covariance of the log fluxes; the walker-independent ln det C_ln is not added.
+        The rows are sorted by t (a stable sort), C_ln is permuted with them and then factored (covariance_whitener).  Recipes --
+        a zero point shared by the rows, known to a fraction c:  cov = np.diag(err**2) + c**2 * np.outer(f_nu, f_nu);
+        interstellar scintillation with modulation index m, a kernel in ln t and ln nu:
+            cov = np.diag(err**2) + m**2 * np.outer(f_nu, f_nu) * np.exp(-0.5 * ((np.subtract.outer(np.log(t), np.log(t)) / l_t)**2
+                                                                             + (np.subtract.outer(np.log(nu), np.log(nu)) / l_nu)**2)).
+        Not supported inside a group: a free jitter or systematic, upper limits, templates, band-integrated rows; groups are
+        independent of each other and of every other row.  Nothing is recorded when the call raises."""
+        who = "add_correlated"
+        nu_arr = np.asarray(nu, dtype=np.float64)
+        t, f = np.asarray(t, dtype=np.float64), np.asarray(f_nu, dtype=np.float64)
+        if t.ndim != 1 or t.size == 0:
+            raise ValueError(f"{who}: t must be a non-empty 1-D array")
+        n = t.size
+        if n > _lib.COV_MAX_ROWS:
+            raise ValueError(f"{who}: at most {_lib.COV_MAX_ROWS} rows per correlated group, got {n}")
+        if f.shape != t.shape:
+            raise ValueError(f"{who}: t and f_nu must have the same shape; got {t.shape}, {f.shape}")
+        if nu_arr.ndim != 0 and nu_arr.shape != t.shape:
+            raise ValueError(f"{who}: an array nu must have the shape of t, got {nu_arr.shape} vs {t.shape}")
+        if not np.isfinite(nu_arr).all() or (nu_arr <= 0).any():
+            raise ValueError(f"{who}: nu must be finite and > 0")
+        if not np.isfinite(t).all() or (t <= 0).any():
+            raise ValueError(f"{who}: t must be finite and > 0 at every row")
+        if not np.isfinite(f).all() or (f <= 0).any():
+            raise ValueError(f"{who}: f_nu must be finite and > 0 at every row (the likelihood is in ln f_nu)")
+        cov = np.asarray(cov, dtype=np.float64)
+        if cov.shape != (n, n):
+            raise ValueError(f"{who}: cov must be [{n}, {n}], got {cov.shape}")
+        if np.ndim(weight) != 0 or not np.isfinite(weight) or weight < 0:
+            raise ValueError(f"{who}: weight must be a finite scalar >= 0, got {weight!r}")
+        if len(self._cov_obs) >= _lib.COV_MAX_GROUPS:
+            raise ValueError(f"{who}: at most {_lib.COV_MAX_GROUPS} correlated groups per fit")
+        order = np.argsort(t, kind="stable")
+        t, f = t[order], f[order]
+        nu_rows = np.full_like(t, float(nu_arr)) if nu_arr.ndim == 0 else nu_arr[order]
+        with np.errstate(all="ignore"):
+            c_ln = cov[np.ix_(order, order)] / (f[:, None] * f[None, :])
+        try:
+            W = covariance_whitener(c_ln)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        c = np.ascontiguousarray
+        self._cov_obs.append(dict(t=c(t), nu=c(nu_rows), ln_flux=c(np.log(f)), whitener=c(W), weight=float(weight)))
+
+    @property
+    def has_correlated(self):
+        """Some data are correlated groups (add_correlated)."""
+        return bool(self._cov_obs)
+
     def add_count_spectrum(self, energy_lo, energy_hi, response, t_start, exposure, counts, background=0.0, num_exposure_points=1,
                            weights=None, absorption=None):
         """Counts per detector channel of n spectra, compared with the model photon spectrum folded through the instrument
@@ -955,9 +1072,9 @@ class Fitter:
             return
         if not self._point_t:
             if not (self._band_obs or self._centroid_obs or self._vis_obs or self._pol_obs or self._counts_obs or self._index_obs
-                    or self._fold_obs):
+                    or self._fold_obs or self._cov_obs):
                 raise ValueError("no data: call add_flux_density, add_flux, add_centroid, add_visibilities, add_polarization, "
-                                 "add_counts, add_spectral_index or add_count_spectrum first")
+                                 "add_counts, add_spectral_index, add_count_spectrum or add_correlated first")
             self._all_t = self._all_nu = self._all_log_flux = self._all_log_err = self._all_weights = np.array([])
             self._all_lim = self._all_grp = None
             self._all_tmpl = {}
@@ -1107,6 +1224,7 @@ class Fitter:
         spec._index = self._index_spec(z_eff) if self._index_obs else None
         self._check_n_h_parameter(param_defs)
         spec._fold = self._fold_spec(fixed) if self._fold_obs else None
+        spec._cov = self._cov_spec(z_eff) if self._cov_obs else None
         if self.extinction is not None and self._all_t.size and z_eff != self._ext_z:
             # a fixed 'z' ParamDef overrides Fitter.z in the model: the rest-frame wavelengths of the law must follow it.  One
             # kernel per z, all kept for the Fitter's lifetime: earlier specs (a device_evaluator's closure) still point at theirs
@@ -1212,6 +1330,30 @@ class Fitter:
         fs.n_h_fixed = float(fixed.get("N_H", self.n_h))
         fs._keep_alive = (groups, list(self._fold_obs))
         return fs
+
+    def _cov_ext(self, gd, z):
+        """The extinction kernel 0.4 ln10 k(lambda_rest) at the rows of a correlated group at redshift z, formed as for the point
+        rows; None without an extinction law."""
+        if self.extinction is None:
+            return None
+        lam_rest_cm = (2.99792458e10 / gd["nu"]) / (1.0 + z)
+        return np.ascontiguousarray(0.4 * np.log(10.0) * np.asarray(self._k_lambda(lam_rest_cm), dtype=np.float64))
+
+    def _cov_spec(self, z):
+        """vag_cov_fit_spec of the correlated groups (the law's kernel at redshift z); it keeps the arrays it points at alive."""
+        cs = _lib.CovFitSpec()
+        groups = (_lib.CovObs * len(self._cov_obs))()
+        exts = []
+        for g, gd in enumerate(self._cov_obs):
+            o = groups[g]
+            o.n, o.weight = gd["t"].size, gd["weight"]
+            for name in ("t", "nu", "ln_flux", "whitener"):
+                setattr(o, name, gd[name].ctypes.data_as(_dp))
+            exts.append(self._cov_ext(gd, z))
+            o.ext = exts[-1].ctypes.data_as(_dp) if exts[-1] is not None else None
+        cs.n_groups, cs.groups = len(self._cov_obs), groups
+        cs._keep_alive = (groups, list(self._cov_obs), exts)
+        return cs
 
     def _index_ext_slope(self, gd, z):
         """ext_slope of a spectral-index group at redshift z: sum_{k >= 1} c_k (kappa_k - kappa_0), kappa = 0.4 ln10 k(lambda_rest),
@@ -1493,6 +1635,32 @@ class Fitter:
             out.append(index_from_slope(slope, gd["convention"]))
         return out
 
+    def correlated(self, best_params, param_defs, resolution=None):
+        """Every correlated group at a point of sampler space: a list of dict(model=f, residual=r, whitened=y, chi2=w sum y^2), one per
+        group, rows in ascending t; f is the model flux density with extinction applied, r = ln f_nu - ln max(f, 1e-300), y = W r.
+        Each group is one vag_flux_density_batch request at its rows and whitened_chi2's arithmetic on the result -- the
+        likelihood's own request and arithmetic (its flux may differ from this call's in the last bits: 1e-15 relative, as
+        Fitter.counts documents for an unpinned request)."""
+        p, a_v = self._params_at(best_params, param_defs, resolution)
+        h, lock = get_context(self.device)
+        out = []
+        for gd in self._cov_obs:
+            n = gd["t"].size
+            flux = np.empty(n)
+            with lock:
+                _lib.check(_lib.load().vag_flux_density_batch(h, C.byref(p), 1, gd["t"].ctypes.data_as(_dp), gd["nu"].ctypes.data_as(_dp), n,
+                                                              flux.ctypes.data_as(_dp)))
+            ext = self._cov_ext(gd, float(p.z))
+            f = flux * np.exp(-a_v * ext) if ext is not None and a_v != 0.0 else flux
+            with np.errstate(all="ignore"):
+                r = gd["ln_flux"] - np.log(np.where(f > 1e-300, f, np.where(np.isnan(f), f, 1e-300)))
+            W = gd["whitener"]
+            y = np.zeros(n)
+            for j in range(n):  # y_i = sum_{j <= i} W_ij r_j, ascending j (W is lower triangular)
+                y = y + W[:, j] * r[j]
+            out.append(dict(model=f, residual=r, whitened=y, chi2=gd["weight"] * float(whitened_chi2(r, W))))
+        return out
+
     def count_spectra(self, best_params, param_defs, resolution=None):
         """The expected counts mu [n][C] of every count-spectrum group at a point of sampler space: a list of float64 arrays, one per
         group.  Each group is one vag_flux_density_batch request at its n_samples J points (t_sample_s, nu_j), s outer, and
@@ -1669,7 +1837,7 @@ class Fitter:
             def run():
                 ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
                 # the widest entry point: with a block absent (None) it is the narrower entry point, bit for bit
-                fn, fold = _widest_entry(lib, keep[0], "_dev")  # (fold: the trailing specs, the fold block and the templates)
+                fn, fold = _widest_entry(lib, keep[0], "_dev")  # (fold: the trailing specs -- the fold block, the templates, the correlated groups)
                 _lib.check(fn(h, C.byref(keep[0]), ref(keep[0]._sky), ref(keep[0]._vis), ref(keep[0]._pol), ref(keep[0]._lim),
                               ref(keep[0]._noise), ref(keep[0]._counts), ref(keep[0]._index), *fold, theta.data_ptr(), k, keep[0].ndim,
                               values.data_ptr()))
@@ -1687,6 +1855,7 @@ class Fitter:
         eval_dev.has_spectral_indices = spec._index is not None
         eval_dev.has_count_spectra = spec._fold is not None
         eval_dev.has_templates = spec._tmpl is not None
+        eval_dev.has_correlated = spec._cov is not None
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -1697,6 +1866,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
+                if keep[0]._cov is not None:
+                    from .dist import _NO_CORRELATED
+                    raise NotImplementedError(_NO_CORRELATED)
                 if keep[0]._tmpl is not None:
                     from .dist import _NO_TEMPLATES
                     raise NotImplementedError(_NO_TEMPLATES)
