@@ -1,12 +1,13 @@
-"""ln L of two small seeded fits, written to an .npy, to compare two builds of the engine byte for byte: run it once per build
+"""ln L of three small seeded fits, written to an .npy, to compare two builds of the engine byte for byte: run it once per build
 (VAG_LIB_PATH selects the library) in the same visit and compare the files with --compare.
 
 The fits are those of tests/test_loglike_entry_points.py: (a) the 60 C4 point rows alone; (b) one fitter with a point block, a band
 group, a centroid group, a visibility group, a degree-polarization group with a limit epoch, limit rows, a noise group with a
-calibration term, a counts group and a spectral-index group.  Each is evaluated with 3 walkers (no ordering) and with 64 (the
-smallest batch evaluated in cost order), twice: the second call runs in the order the first one left.  The array is the eight
-results in that order, concatenated (2 x (3 + 3 + 64 + 64) values).  The data of the fits are made by model calls of the build
-under test, so a difference may come from the model requests as well as from the likelihood.
+calibration term, a counts group and a spectral-index group; (c) the same plus a count-spectrum group with a cross-section, a
+template on point rows and two correlated groups (2 and 65 rows): every spec block the likelihood has.  Each is evaluated with 3
+walkers (no ordering) and with 64 (the smallest batch evaluated in cost order), twice: the second call runs in the order the first
+one left.  The array is the twelve results in that order, concatenated (3 x (3 + 3 + 64 + 64) values).  The data of the fits are
+made by model calls of the build under test, so a difference may come from the model requests as well as from the likelihood.
 
     VAG_LIB_PATH=a.so python profiles/loglike_bits.py --out a.npy
     VAG_LIB_PATH=b.so python profiles/loglike_bits.py --out b.npy
@@ -25,7 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def evaluate():
     import test_loglike_entry_points as ep  # noqa: E402
     out = []
-    for fixture, walkers in ((ep.fixture_a, ep.walkers_a), (ep.fixture_b, ep.walkers_b)):
+    for fixture, walkers in ((ep.fixture_a, ep.walkers_a), (ep.fixture_b, ep.walkers_b), (ep.fixture_c, ep.walkers_c)):
         f, d = fixture()
         for nb in ep.BATCHES:
             th = walkers(nb)

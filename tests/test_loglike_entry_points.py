@@ -1,10 +1,11 @@
-"""The sixteen likelihood entry points (vag_loglike_{,sky_,vis_,pol_,lim_,noise_,counts_,index_}batch and their _dev forms) are one
-request path: a request whose optional blocks are absent or empty is the narrower entry point's request, bit for bit; the host form
+"""The twenty-two likelihood entry points (vag_loglike_{,sky_,vis_,pol_,lim_,noise_,counts_,index_,fold_,tmpl_,cov_}batch and their _dev
+forms) are one request path: a request whose optional blocks are absent or empty is the narrower entry point's request, bit for bit; the host form
 is the device-pointer form; a call does not depend on the evaluation order; an invalid walker scores -inf through the back kernels'
 shared closing block and leaves the others alone.
 
-Two fixtures, both on C4 (configs.C4_TRUTH): (a) the 60 point rows alone; (b) one fitter with every kind of data the likelihood
-takes.  Two batch sizes: 3 walkers (evaluated in the identity order) and 64, the smallest batch evaluated in cost order.
+Three fixtures, all on C4 (configs.C4_TRUTH): (a) the 60 point rows alone; (b) one fitter with every kind of data the first sixteen
+entry points take; (c) the same plus a count spectrum, a template and two correlated groups: every kind of data the likelihood takes,
+through the widest entry point.  Two batch sizes: 3 walkers (evaluated in the identity order) and 64, the smallest batch evaluated in cost order.
 profiles/loglike_bits.py writes ln L of the same fixtures to a file, to compare two builds."""
 import ctypes as C
 
@@ -14,10 +15,13 @@ import pytest
 import _abi
 import configs
 import test_counts as tc
+import test_cov as tcov
+import test_fold as tf
 import test_index as ti
 import test_limits as tl
 import test_sky_polfit as tp
 import test_sky_visfit as tv
+import test_templates as tt
 import vegasafterglow_amd as va
 from vegasafterglow_amd import _lib, fitting
 
@@ -69,6 +73,24 @@ def fixture_b():
     return f, d
 
 
+def fixture_c():
+    """Fixture (b)'s fitter plus the three kinds it lacks: a count-spectrum group (4 bins, 2 channels, 3 epochs, with a cross-section:
+    N_H is read), 3 point rows at 8 GHz that carry the template "sn", and two correlated groups of 2 and 65 rows (each side of the
+    64-lane stride), built by the helpers of the tests of each kind.  Free on top of (b): amp_sn, N_H.  Returns (fitter, parameter
+    list)."""
+    f, d = fixture_b()
+    truth_n_h, d_n_h = np.append(tc.TRUTH, tf.LOG_N_H_TRUE), tf.defs(tf.N_H_DEF)
+    f.add_count_spectrum(**tf.make_group(4, 2, tc.EPOCHS[4::6], np.full(3, 4e4), 1, seed=51, absorption=True, truth=truth_n_h, d=d_n_h))
+    t3 = np.array([40.0, 70.0, 120.0]) * DAY
+    f3 = tv._c4_truth().flux_density_grid(t3, 8e9).total[0]
+    bump = tt.sn_bump(t3)
+    f.add_flux_density(8e9, t3, f3 * (1 + 0.3 * bump), 0.1 * f3, templates={"sn": f3.max() * bump})
+    for n, kind in ((2, "cal"), (65, "gp")):
+        f.add_correlated(**tcov.make_data(n, kind))
+    free = len(tv.FLUX_DEFS + tv.SKY_DEFS) + 2
+    return f, d[:free] + [P("amp_sn", 0.0, 1.0)] + tf.N_H_DEF + d[free:]
+
+
 def walkers_a(nb):
     return np.ascontiguousarray(tv._walkers(nb, seed=12)[0])
 
@@ -79,6 +101,11 @@ def walkers_b(nb):
     return np.ascontiguousarray(np.column_stack([th, sky, rng.uniform(0.2, 0.8, nb), rng.uniform(0.0, 0.2, nb)]))
 
 
+def walkers_c(nb):
+    rng = np.random.default_rng(33)
+    return np.ascontiguousarray(np.column_stack([walkers_b(nb), rng.uniform(0.1, 0.6, nb), rng.uniform(21.5, 22.5, nb)]))
+
+
 @pytest.fixture(scope="module")
 def fit_a():
     return fixture_a()
@@ -87,6 +114,11 @@ def fit_a():
 @pytest.fixture(scope="module")
 def fit_b():
     return fixture_b()
+
+
+@pytest.fixture(scope="module")
+def fit_c():
+    return fixture_c()
 
 
 ENTRY_POINTS = ("", "sky_", "vis_", "pol_", "lim_", "noise_", "counts_", "index_")  # entry point k takes the first k optional specs
@@ -116,6 +148,10 @@ def call(name, spec, optional, samples, dev=False):
 
 def all_specs(spec):
     return [spec._sky, spec._vis, spec._pol, spec._lim, spec._noise, spec._counts, spec._index]
+
+
+def widest_specs(spec):
+    return all_specs(spec) + [spec._fold, spec._tmpl, spec._cov]
 
 
 @pytest.mark.parametrize("nb", BATCHES)
@@ -159,6 +195,43 @@ def test_every_kind_of_data_in_one_fit(fit_b, nb):
     assert np.array_equal(tv._with_hook("VAG_NO_ORDER", "1", lambda: call("vag_loglike_index_batch", spec, all_specs(spec), th)), a)
     assert np.array_equal(f.loglike_batch(th, d), a)
     assert f.last_plan.n_walkers_rejected == 0
+
+
+@pytest.mark.parametrize("nb", BATCHES)
+def test_every_kind_of_data_through_the_widest_entry_point(fit_c, nb):
+    """Fixture (c), what fixture (b) gets: the host form equals the device-pointer form, a repeat call and a call under VAG_NO_ORDER
+    are equal, and Fitter.loglike_batch is vag_loglike_cov_batch -- all to the bits."""
+    f, d = fit_c
+    spec, _, _ = f.build_spec(d)
+    assert all(s is not None for s in widest_specs(spec))
+    assert (spec.n_data, spec.n_bands, spec._fold.n_groups, spec._tmpl.n_templates, spec._cov.n_groups) == (15, 1, 1, 1, 2)
+    assert sorted(spec._cov.groups[g].n for g in range(2)) == [2, 65] and bool(spec._fold.groups[0].sigma)
+    th = walkers_c(nb)
+    a = call("vag_loglike_cov_batch", spec, widest_specs(spec), th)
+    assert np.all(np.isfinite(a))
+    assert np.array_equal(call("vag_loglike_cov_batch", spec, widest_specs(spec), th, dev=True), a)
+    assert np.array_equal(call("vag_loglike_cov_batch", spec, widest_specs(spec), th), a)
+    assert np.array_equal(tv._with_hook("VAG_NO_ORDER", "1", lambda: call("vag_loglike_cov_batch", spec, widest_specs(spec), th)), a)
+    assert np.array_equal(f.loglike_batch(th, d), a)
+    assert f.last_plan.n_walkers_rejected == 0
+
+
+@pytest.mark.parametrize("nb", BATCHES)
+def test_an_out_of_range_walker_of_every_kind_of_data(fit_c, nb):
+    """The same as the next test on fixture (c), under the same pin and for the same reason."""
+    f, d = fit_c
+    th = walkers_c(nb)
+    bad = th.copy()
+    bad[1, 0] = -0.05
+
+    def both():
+        base = f.loglike_batch(th, d)
+        return base, f.loglike_batch(bad, d), f.last_plan.n_walkers_rejected
+
+    base, out, rejected = tv._with_hook("VAG_PAIRS_PER_BLOCK", "4", both)
+    assert np.all(np.isfinite(base))
+    assert out[1] == -np.inf and np.array_equal(np.delete(out, 1), np.delete(base, 1))
+    assert rejected == 1
 
 
 @pytest.mark.parametrize("nb", BATCHES)

@@ -30,22 +30,11 @@
 #include "vag_poisson.h"
 #include "vag_index.h"
 #include "vag_fit_kernels.h"
+#include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
 
 using namespace vag;
 
 namespace {
-
-thread_local std::string g_err;
-
-int set_err(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
 
 
 // Developer / test hooks (VAG_* environment variables).  The process environment is read ONCE -- when the first hook is asked for, i.e.
@@ -151,6 +140,46 @@ struct HostBuf {  // pinned
     template <class T>
     T* as() const {
         return reinterpret_cast<T*>(p);
+    }
+};
+
+// One spec block of the likelihood, resident on the device: the block goes up through its pinned staging copy only when its content
+// hash or its size changes (a sampler loop calls with the same spec); a hit issues no HIP call.
+struct ResidentBlock {
+    HostBuf h;  // pinned staging copy
+    DevBuf d;   // what the kernels read
+    uint64_t hash = 0;
+    size_t doubles = 0;  // of d
+    bool valid = false;
+    bool resident(uint64_t content, size_t n) const { return valid && hash == content && doubles == n; }
+    // A miss: nothing is resident until commit().  Waits for an earlier staging copy that may still be in flight, sizes both buffers
+    // and hands out the pinned one; n_staged > n when more than the block rides in it (the visibility blocks behind the doubles).
+    int stage(hipStream_t st, size_t n, double** hp, size_t n_staged = 0) {
+        valid = false;
+        HIPCHK(hipStreamSynchronize(st));
+        if (h.ensure(sizeof(double) * std::max(n, n_staged))) return VAG_E_HIP;
+        if (d.ensure(sizeof(double) * n)) return VAG_E_HIP;
+        *hp = h.as<double>();
+        return VAG_OK;
+    }
+    int commit(hipStream_t st, uint64_t content, size_t n) {
+        HIPCHK(hipMemcpyAsync(d.p, h.p, sizeof(double) * n, hipMemcpyHostToDevice, st));
+        hash = content;
+        doubles = n;
+        valid = true;
+        return VAG_OK;
+    }
+    // the whole of it for a block a scan has laid out
+    int upload(hipStream_t st, uint64_t content, const std::vector<double>& staged) {
+        if (resident(content, staged.size())) return VAG_OK;
+        double* hp = nullptr;
+        if (int rc = stage(st, staged.size(), &hp)) return rc;
+        std::memcpy(hp, staged.data(), sizeof(double) * staged.size());
+        return commit(st, content, staged.size());
+    }
+    void release() {
+        h.release();
+        d.release();
     }
 };
 
@@ -410,16 +439,9 @@ struct vag_ctx {
     DevBuf d_skyterms, d_skyimg, d_skymom;  // sky images / moments (vag_sky.h): term list, a chunk's images, moments + outside
     DevBuf d_skypol, d_skystokes;  // polarization (vag_sky.h): a chunk's row-block partials, the models' spec + Stokes sums + outside
     DevBuf d_skyvis, d_skyuv;  // visibilities (vag_sky.h): a chunk's row-block partials + combined values, a chunk's baselines
-    DevBuf d_skycen, d_skycmom, d_skyfit;  // exact centroids (vag_sky.h): row-block partials, moments, centroid-fit pass data
-    DevBuf d_visfit, d_visblk, d_vispart;  // visibility groups of the likelihood: their data, their 64-visibility blocks, chi^2 partials
-    DevBuf d_polfit, d_polspec, d_polstokes;  // polarization groups of the likelihood: their data, the walkers' spec + its flag, jet-frame I, Q, U
-    DevBuf d_noisefit;  // noise groups of the likelihood (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
-    DevBuf d_tmplfit;  // additive templates of the likelihood (vag_loglike_tmpl_batch): [amp_fixed 8] then per touched pass its [n_templates][n] values, see TmplLayout
-    DevBuf d_covfit;  // correlated groups of the likelihood (vag_loglike_cov_batch): per group [t | nu | ln_flux | ext | Wt], see CovLayout
-    DevBuf d_countsfit;  // counts groups of the likelihood (vag_loglike_counts_batch): per group [t_sample | N | B | a | w | idx], see CountsLayout
-    DevBuf d_foldfit;   // fold groups of the likelihood (vag_loglike_fold_batch): per group the block FoldLayout describes
-    DevBuf d_indexfit;  // spectral-index groups of the likelihood (vag_loglike_index_batch): per group [t | nu | s | sigma | w | c], see IndexLayout
-    DevBuf d_limfit;  // upper-limit rows of the likelihood (vag_loglike_lim_batch): per block [limit | sigma | kind], see LimLayout
+    DevBuf d_skycen, d_skycmom;  // exact centroids (vag_sky.h): row-block partials, moments
+    DevBuf d_visblk, d_vispart;  // visibility groups of the likelihood (their data: vis below): their 64-visibility blocks, chi^2 partials
+    DevBuf d_polspec, d_polstokes;  // polarization groups of the likelihood (their data: pol below): the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
     bool ic_all_cells = false;    // this request's SSC tables are built for every cell (the lazy selection was caught with a hole, see check_ic_status)
@@ -471,47 +493,26 @@ struct vag_ctx {
     bool meta_on_host = false;    // h_meta holds the current batch's grid results (copied on demand)
     // compact per-row / per-cell storage
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
-    // fit spec cache (upload_fit_spec): content hash of what d_fit holds, its size, where the prior block starts
-    DevBuf d_fit, d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    HostBuf h_fit, h_skyfit, h_visfit, h_polfit, h_limfit, h_noisefit, h_countsfit, h_indexfit, h_foldfit, h_tmplfit, h_covfit;
-    uint64_t fit_hash = 0, skyfit_hash = 0;  // (d_skyfit: the centroid groups of vag_loglike_sky_batch, upload_sky_spec)
-    size_t skyfit_doubles = 0;
-    bool skyfit_hash_valid = false;
-    uint64_t visfit_hash = 0;  // (d_visfit / d_visblk: the visibility groups of vag_loglike_vis_batch, upload_vis_spec)
-    size_t visfit_doubles = 0;
-    bool visfit_hash_valid = false;
+    DevBuf d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
+    // the likelihood's spec blocks, one ResidentBlock each (layouts: upload_{fit,sky,vis,pol}_spec, the scans of vag_fit_request.h)
+    ResidentBlock fit;     // the observation arrays, the slot map and the priors of the vag_fit_spec; fit_prior_off: where the prior block starts
+    ResidentBlock sky;     // centroid groups (vag_loglike_sky_batch)
+    ResidentBlock vis;     // visibility groups (vag_loglike_vis_batch); their int32 blocks are d_visblk, their places vis_layout
+    ResidentBlock pol;     // polarization groups (vag_loglike_pol_batch)
+    ResidentBlock lim;     // upper-limit rows (vag_loglike_lim_batch): per block [limit | sigma | kind], see LimLayout
+    ResidentBlock noise;   // noise groups (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
+    ResidentBlock counts;  // counts groups (vag_loglike_counts_batch): per group [t_sample | N | B | a | w | idx], see CountsLayout
+    ResidentBlock index;   // spectral-index groups (vag_loglike_index_batch): per group [t | nu | s | sigma | w | c], see IndexLayout
+    ResidentBlock fold;    // fold groups (vag_loglike_fold_batch): per group the block FoldLayout describes
+    ResidentBlock tmpl;    // additive templates (vag_loglike_tmpl_batch): [amp_fixed 8] then per touched pass its [n_templates][n] values, see TmplLayout
+    ResidentBlock cov;     // correlated groups (vag_loglike_cov_batch): per group [t | nu | ln_flux | ext | Wt], see CovLayout
+    size_t fit_prior_off = 0;
     struct VisLayout {  // of one resident group
-        size_t obs_off;              // its data in d_visfit [doubles]: nu | t | u | v | re | im | err | weight
+        size_t obs_off;              // its data in vis.d [doubles]: nu | t | u | v | re | im | err | weight
         int blk_off;                 // its blocks in d_visblk [blocks of 3 ints]
         std::vector<int> epoch_blk;  // [n_epochs + 1]: first block of every epoch
     };
     std::vector<VisLayout> vis_layout;
-    uint64_t polfit_hash = 0;  // (d_polfit: the polarization groups of vag_loglike_pol_batch, upload_pol_spec)
-    size_t polfit_doubles = 0;
-    bool polfit_hash_valid = false;
-    uint64_t limfit_hash = 0;  // (d_limfit: the limit rows of vag_loglike_lim_batch, upload_lim_spec)
-    size_t limfit_doubles = 0;
-    bool limfit_hash_valid = false;
-    uint64_t noisefit_hash = 0;  // (d_noisefit: the noise groups of vag_loglike_noise_batch, upload_noise_spec)
-    size_t noisefit_doubles = 0;
-    bool noisefit_hash_valid = false;
-    uint64_t countsfit_hash = 0;  // (d_countsfit: the counts groups of vag_loglike_counts_batch, upload_counts_spec)
-    size_t countsfit_doubles = 0;
-    bool countsfit_hash_valid = false;
-    uint64_t indexfit_hash = 0;  // (d_indexfit: the spectral-index groups of vag_loglike_index_batch, upload_index_spec)
-    size_t indexfit_doubles = 0;
-    bool indexfit_hash_valid = false;
-    uint64_t foldfit_hash = 0;  // (d_foldfit: the fold groups of vag_loglike_fold_batch, upload_fold_spec)
-    size_t foldfit_doubles = 0;
-    bool foldfit_hash_valid = false;
-    uint64_t tmplfit_hash = 0;  // (d_tmplfit: the templates of vag_loglike_tmpl_batch, upload_tmpl_spec)
-    size_t tmplfit_doubles = 0;
-    bool tmplfit_hash_valid = false;
-    uint64_t covfit_hash = 0;  // (d_covfit: the correlated groups of vag_loglike_cov_batch, upload_cov_spec)
-    size_t covfit_doubles = 0;
-    bool covfit_hash_valid = false;
-    size_t fit_doubles = 0, fit_prior_off = 0;
-    bool fit_hash_valid = false;
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
     bool ic_need_reset = true;       // first SSC table build of a pass clears d_icstatus
     bool ic_soft_fail = false;       // likelihood calls: SSC table failures invalidate the walker instead of raising
@@ -735,7 +736,7 @@ void vag_ctx_destroy(vag_ctx* c) {
                       &c->d_cellq_r, &c->d_params_rvs, &c->d_inj, &c->d_comp, &c->d_cellgeo, &c->d_fail, &c->d_dynrec, &c->d_gridscratch, &c->d_chi2, &c->d_bandobs, &c->d_params, &c->d_t, &c->d_nu, &c->d_lg2t, &c->d_lg2nu, &c->d_tminmax, &c->d_bandw, &c->d_out,
                       &c->d_meta, &c->d_phi, &c->d_theta, &c->d_rep_of, &c->d_rep_start, &c->d_tdec, &c->d_geo_th, &c->d_geo_ph, &c->d_row_off,
                       &c->d_cell_off, &c->d_shock, &c->d_cellpar, &c->d_row_status, &c->d_celldet, &c->d_partial,
-                      &c->d_fit, &c->d_theta_in, &c->d_valid, &c->d_series_flux})
+                      &c->d_theta_in, &c->d_valid, &c->d_series_flux})
         b->release();
     c->h_meta.release();
     c->h_off.release();
@@ -743,19 +744,9 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_plan.release();
     c->d_chunk.release();
     c->d_icwork.release();
-    c->h_fit.release();
-    c->h_skyfit.release();
-    c->h_visfit.release();
-    c->h_polfit.release();
-    c->h_limfit.release();
-    c->h_noisefit.release();
-    c->h_countsfit.release();
-    c->h_indexfit.release();
-    c->h_foldfit.release();
-    c->h_tmplfit.release();
-    c->h_covfit.release();
+    for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_skyfit, &c->d_visfit, &c->d_visblk, &c->d_vispart, &c->d_polfit, &c->d_polspec, &c->d_polstokes, &c->d_limfit, &c->d_noisefit, &c->d_countsfit, &c->d_indexfit, &c->d_foldfit, &c->d_tmplfit, &c->d_covfit})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -2368,7 +2359,7 @@ int vis_chi2_request(vag_ctx* c, const vag_model_params* d_params, int nb, const
     if (c->d_vispart.ensure(sizeof(double) * 2 * (size_t)nb * n_blk_all)) return VAG_E_HIP;
     va.meta = c->d_meta.as<VagGridMeta>();
     va.phi = c->d_phi.as<double>();
-    va.obs = c->d_visfit.as<double>() + lay.obs_off + 1 + nt;
+    va.obs = c->vis.d.as<double>() + lay.obs_off + 1 + nt;
     va.blocks = c->d_visblk.as<int>() + 3 * (size_t)lay.blk_off;
     va.n_vis = o.n_vis;
     va.n_blk_all = n_blk_all;
@@ -3622,12 +3613,6 @@ static int upload_series_bands(vag_ctx* c, const double* nu, int n) {
 //      through one pinned staging copy only when their content hash changes (a sampler loop calls with the same spec) ----
 // layout in doubles: [t | nu | ln_flux | ln_err | weight | ext] (n each), then per band group [t | ln_flux | ln_err | weight]
 // (bd.n each), then [lower | upper | prior_a | prior_b] (16 each), then int32 [slot | is_log | prior_kind] (16 each).
-static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
-    return h;
-}
-
 static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false, int noise_groups = 0,
                            bool counts = false, bool n_h = false, int n_templates = 0) {
     if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
@@ -3679,7 +3664,7 @@ static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool 
     const size_t prior_off = total;
     total += 4 * 16 + 3 * 16 / 2;  // four double[16] + three int32[16]
     c->fit_prior_off = prior_off;
-    if (c->fit_hash_valid && c->fit_hash == h && c->fit_doubles == total) return VAG_OK;  // resident already
+    if (c->fit.resident(h, total)) return VAG_OK;
 
     // content changed: validate it (once), stage and upload
     for (int i = 0; i < n; ++i)
@@ -3692,11 +3677,8 @@ static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool 
             if (!(bd.t[i] > 0) || (i > 0 && bd.t[i] < bd.t[i - 1]))
                 return set_err(VAG_E_INVALID, "band group %d: times must be positive and ascending", g);
     }
-    c->fit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_fit.ensure(sizeof(double) * total)) return VAG_E_HIP;
-    if (c->d_fit.ensure(sizeof(double) * total)) return VAG_E_HIP;
-    double* hp = c->h_fit.as<double>();
+    double* hp = nullptr;
+    if (int rc = c->fit.stage(c->stream, total, &hp)) return rc;
     std::memset(hp, 0, sizeof(double) * total);
     if (n > 0) {
         const double* src[6] = {spec->t, spec->nu, spec->ln_flux, spec->ln_err, spec->weight, spec->ext_kernel};
@@ -3718,11 +3700,7 @@ static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool 
     std::memcpy(hi, spec->slot, sizeof spec->slot);
     std::memcpy(hi + 16, spec->is_log, sizeof spec->is_log);
     std::memcpy(hi + 32, spec->prior_kind, sizeof spec->prior_kind);
-    HIPCHK(hipMemcpyAsync(c->d_fit.p, hp, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
-    c->fit_hash = h;
-    c->fit_doubles = total;
-    c->fit_hash_valid = true;
-    return VAG_OK;
+    return c->fit.commit(c->stream, h, total);
 }
 
 // ---- centroid groups (vag_loglike_sky_batch): their data in one device buffer, uploaded like the fit spec when its hash changes.
@@ -3743,7 +3721,7 @@ static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
         for (const double* arr : {o.t, o.east, o.north, o.err_east, o.err_north, o.weight}) h = fnv1a(h, arr, sizeof(double) * o.n);
         total += 1 + 6 * (size_t)o.n;
     }
-    if (c->skyfit_hash_valid && c->skyfit_hash == h && c->skyfit_doubles == total) return VAG_OK;  // resident already
+    if (c->sky.resident(h, total)) return VAG_OK;
     for (int g = 0; g < sky->n_groups; ++g) {
         const vag_centroid_obs& o = sky->groups[g];
         if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "centroid group %d: frequency must be positive", g);
@@ -3756,12 +3734,10 @@ static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
                 return set_err(VAG_E_INVALID, "centroid group %d: errors must be positive and finite", g);
         }
     }
-    c->skyfit_hash_valid = false;
-    if (total == 0) return VAG_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_skyfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
-    if (c->d_skyfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
-    double* hp = c->h_skyfit.as<double>();
+    c->sky.valid = false;
+    if (total == 0) return VAG_OK;  // (the fixed placement alone: nothing to hold)
+    double* hp = nullptr;
+    if (int rc = c->sky.stage(c->stream, total, &hp)) return rc;
     size_t off = 0;
     for (int g = 0; g < sky->n_groups; ++g) {
         const vag_centroid_obs& o = sky->groups[g];
@@ -3771,11 +3747,7 @@ static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
             off += o.n;
         }
     }
-    HIPCHK(hipMemcpyAsync(c->d_skyfit.p, hp, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
-    c->skyfit_hash = h;
-    c->skyfit_doubles = total;
-    c->skyfit_hash_valid = true;
-    return VAG_OK;
+    return c->sky.commit(c->stream, h, total);
 }
 
 // ---- visibility groups (vag_loglike_vis_batch): their data in one device buffer, uploaded like the centroid groups when the hash
@@ -3803,7 +3775,7 @@ static int upload_vis_spec(vag_ctx* c, const vag_vis_fit_spec* vis) {
             if (arr) h = fnv1a(h, arr, sizeof(double) * o.n_vis);
         total += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
     }
-    if (c->visfit_hash_valid && c->visfit_hash == h && c->visfit_doubles == total) return VAG_OK;  // resident already
+    if (c->vis.resident(h, total)) return VAG_OK;
     std::vector<vag_ctx::VisLayout> layout(vis->n_groups);
     std::vector<int> blocks;
     size_t off = 0;
@@ -3834,13 +3806,10 @@ static int upload_vis_spec(vag_ctx* c, const vag_vis_fit_spec* vis) {
             if (!(o.weight[k] >= 0) || !std::isfinite(o.weight[k])) return set_err(VAG_E_INVALID, "visibility group %d: weights must be finite and >= 0", g);
         }
     }
-    c->visfit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
     const size_t blk_doubles = (blocks.size() + 1) / 2;  // the int32 blocks ride behind the doubles in the one staging buffer
-    if (c->h_visfit.ensure(sizeof(double) * (total + blk_doubles))) return VAG_E_HIP;
-    if (c->d_visfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
+    double* hp = nullptr;
+    if (int rc = c->vis.stage(c->stream, total, &hp, total + blk_doubles)) return rc;
     if (c->d_visblk.ensure(sizeof(int) * blocks.size())) return VAG_E_HIP;
-    double* hp = c->h_visfit.as<double>();
     off = 0;
     for (int g = 0; g < vis->n_groups; ++g) {
         const vag_visibility_obs& o = vis->groups[g];
@@ -3856,13 +3825,9 @@ static int upload_vis_spec(vag_ctx* c, const vag_vis_fit_spec* vis) {
         }
     }
     std::memcpy(hp + total, blocks.data(), sizeof(int) * blocks.size());
-    HIPCHK(hipMemcpyAsync(c->d_visfit.p, hp, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_visblk.p, hp + total, sizeof(int) * blocks.size(), hipMemcpyHostToDevice, c->stream));
     c->vis_layout = std::move(layout);
-    c->visfit_hash = h;
-    c->visfit_doubles = total;
-    c->visfit_hash_valid = true;
-    return VAG_OK;
+    return c->vis.commit(c->stream, h, total);
 }
 
 // ---- polarization groups (vag_loglike_pol_batch): their data in one device buffer, uploaded like the centroid groups when the hash
@@ -3891,7 +3856,7 @@ static int upload_pol_spec(vag_ctx* c, const vag_pol_fit_spec* pol) {
             if (arr) h = fnv1a(h, arr, sizeof(double) * o.n);
         total += 1 + 6 * (size_t)o.n;
     }
-    if (c->polfit_hash_valid && c->polfit_hash == h && c->polfit_doubles == total) return VAG_OK;  // resident already
+    if (c->pol.resident(h, total)) return VAG_OK;
     for (int g = 0; g < pol->n_groups; ++g) {
         const vag_polarization_obs& o = pol->groups[g];
         const bool qu = o.kind == VAG_POL_QU;
@@ -3905,11 +3870,8 @@ static int upload_pol_spec(vag_ctx* c, const vag_pol_fit_spec* pol) {
                 return set_err(VAG_E_INVALID, "polarization group %d: errors must be positive and finite", g);
         }
     }
-    c->polfit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_polfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
-    if (c->d_polfit.ensure(sizeof(double) * total)) return VAG_E_HIP;
-    double* hp = c->h_polfit.as<double>();
+    double* hp = nullptr;
+    if (int rc = c->pol.stage(c->stream, total, &hp)) return rc;
     size_t off = 0;
     for (int g = 0; g < pol->n_groups; ++g) {
         const vag_polarization_obs& o = pol->groups[g];
@@ -3923,193 +3885,18 @@ static int upload_pol_spec(vag_ctx* c, const vag_pol_fit_spec* pol) {
             off += o.n;
         }
     }
-    HIPCHK(hipMemcpyAsync(c->d_polfit.p, hp, sizeof(double) * total, hipMemcpyHostToDevice, c->stream));
-    c->polfit_hash = h;
-    c->polfit_doubles = total;
-    c->polfit_hash_valid = true;
-    return VAG_OK;
+    return c->pol.commit(c->stream, h, total);
 }
 
-// ---- upper-limit rows (vag_loglike_lim_batch): the blocks that hold a limit row, in one device buffer, uploaded like the other spec
-//      blocks when the hash changes.  Layout in doubles: a flux block (the point rows, a band group) of n rows is
-//      [limit | sigma | kind] (n, n, int32 [n] in (n + 1) / 2 doubles), a polarization group's block [kind] alone (its L and sigma are
-//      the group's q and err_q in d_polfit).  A block without a limit row is not stored (offset -1): its pass is the pass without
-//      limits.  Rows that are detections hold limit 0 and sigma 1, whatever the caller's arrays hold there. ----
-struct LimLayout {
-    long point = -1;              // offset of the point rows' block in d_limfit, or -1
-    std::vector<long> band, pol;  // the same per band group / polarization group
-    bool any = false;             // some limit row exists
-};
-
-static void lim_push_kinds(std::vector<double>& stage, const int32_t* kind, int n) {
-    const size_t at = stage.size();
-    stage.resize(at + ((size_t)n + 1) / 2, 0.0);
-    std::memcpy(stage.data() + at, kind, sizeof(int32_t) * n);
-}
-
-// Checks one flux block of lim (what / g name it in messages) and appends it to stage when it holds a limit row.
-static int lim_flux_block(const vag_limit_rows& r, int n, const char* what, int g, std::vector<double>& stage, long& off, bool& any) {
-    off = -1;
-    if (!r.kind || n <= 0) return VAG_OK;
-    bool here = false;
-    for (int i = 0; i < n; ++i) {
-        if (r.kind[i] != VAG_OBS_DETECTION && r.kind[i] != VAG_OBS_UPPER_LIMIT)
-            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: unknown kind %d", what, g, i, r.kind[i]);
-        if (r.kind[i] != VAG_OBS_UPPER_LIMIT) continue;
-        if (!r.limit || !r.sigma) return set_err(VAG_E_INVALID, "limit rows, %s %d: null limit or sigma array", what, g);
-        if (!std::isfinite(r.limit[i]) || r.limit[i] < 0)
-            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: the limit must be finite and >= 0", what, g, i);
-        if (!std::isfinite(r.sigma[i]) || !(r.sigma[i] > 0))
-            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: sigma must be finite and > 0", what, g, i);
-        here = true;
-    }
-    if (!here) return VAG_OK;
-    any = true;
-    off = (long)stage.size();
-    for (int i = 0; i < n; ++i) stage.push_back(r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.limit[i] : 0.0);
-    for (int i = 0; i < n; ++i) stage.push_back(r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.sigma[i] : 1.0);
-    lim_push_kinds(stage, r.kind, n);
-    return VAG_OK;
-}
-
-// Validates lim against its partners and lays its blocks out in stage (host work only: no context is touched).
-static int lim_scan(const vag_fit_spec* spec, const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, std::vector<double>& stage,
-                    LimLayout& lay) {
-    const int n_pol = pol ? pol->n_groups : 0;
-    if (lim->n_bands != 0 && lim->n_bands != spec->n_bands)
-        return set_err(VAG_E_INVALID, "limit rows: n_bands must be 0 or the fit spec's %d, got %d", spec->n_bands, lim->n_bands);
-    if (lim->n_pol_groups != 0 && lim->n_pol_groups != n_pol)
-        return set_err(VAG_E_INVALID, "limit rows: n_pol_groups must be 0 or the %d polarization groups, got %d", n_pol, lim->n_pol_groups);
-    if ((lim->n_bands > 0 && !lim->bands) || (lim->n_pol_groups > 0 && !lim->pol_kind))
-        return set_err(VAG_E_INVALID, "limit rows: null band or polarization list");
-    if (lim->point.kind && spec->n_data > 0 && !spec->t) return set_err(VAG_E_INVALID, "limit rows: the fit spec has no point rows");
-    int rc = lim_flux_block(lim->point, spec->n_data, "point rows", 0, stage, lay.point, lay.any);
-    if (rc) return rc;
-    lay.band.assign(std::max(spec->n_bands, 0), -1);
-    for (int g = 0; g < lim->n_bands; ++g) {
-        if (!spec->bands) return set_err(VAG_E_INVALID, "limit rows: the fit spec has no band groups");
-        rc = lim_flux_block(lim->bands[g], spec->bands[g].n, "band group", g, stage, lay.band[g], lay.any);
-        if (rc) return rc;
-    }
-    lay.pol.assign(std::max(n_pol, 0), -1);
-    for (int g = 0; g < lim->n_pol_groups; ++g) {
-        const int32_t* kind = lim->pol_kind[g];
-        if (!kind) continue;
-        if (!pol->groups) return set_err(VAG_E_INVALID, "bad polarization group list");
-        const vag_polarization_obs& o = pol->groups[g];
-        bool here = false;
-        for (int i = 0; i < o.n; ++i) {
-            if (kind[i] != VAG_OBS_DETECTION && kind[i] != VAG_OBS_UPPER_LIMIT)
-                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: unknown kind %d", g, i, kind[i]);
-            if (kind[i] != VAG_OBS_UPPER_LIMIT) continue;
-            if (o.kind != VAG_POL_DEGREE)
-                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: only VAG_POL_DEGREE groups take upper limits", g, i);
-            if (!o.q || !o.err_q) return set_err(VAG_E_INVALID, "polarization group %d: null array", g);
-            if (!std::isfinite(o.q[i]) || o.q[i] < 0 || o.q[i] > 1)
-                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: the limit must lie in [0, 1]", g, i);
-            if (!std::isfinite(o.err_q[i]) || !(o.err_q[i] > 0))
-                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: sigma must be finite and > 0", g, i);
-            here = true;
-        }
-        if (!here) continue;
-        lay.any = true;
-        lay.pol[g] = (long)stage.size();
-        lim_push_kinds(stage, kind, o.n);
-    }
-    return VAG_OK;
-}
-
+// ---- the blocks a scan of vag_fit_request.h has laid out (layouts: there).  A block's hash covers what tells two layouts of the same
+//      bytes apart -- the passes' offsets, or the groups' shapes -- and then the bytes; ResidentBlock::upload does the rest. ----
 static int upload_lim_spec(vag_ctx* c, const std::vector<double>& stage, const LimLayout& lay) {
     uint64_t h = 1469598103934665603ull;
     h = fnv1a(h, &lay.point, sizeof lay.point);
     if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
     if (!lay.pol.empty()) h = fnv1a(h, lay.pol.data(), sizeof(long) * lay.pol.size());
     h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    if (c->limfit_hash_valid && c->limfit_hash == h && c->limfit_doubles == stage.size()) return VAG_OK;  // resident already
-    c->limfit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_limfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    if (c->d_limfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    std::memcpy(c->h_limfit.as<double>(), stage.data(), sizeof(double) * stage.size());
-    HIPCHK(hipMemcpyAsync(c->d_limfit.p, c->h_limfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
-    c->limfit_hash = h;
-    c->limfit_doubles = stage.size();
-    c->limfit_hash_valid = true;
-    return VAG_OK;
-}
-
-// ---- noise groups (vag_loglike_noise_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
-//      in doubles: [sys_fixed 8 | calib 8], then for every pass that holds a grouped row -- the point rows, a band group -- the rows'
-//      group ids (int32 [n] in (n + 1) / 2 doubles).  A pass without a grouped row is not stored (offset -1): it is the pass without
-//      noise groups. ----
-struct NoiseLayout {
-    long point = -1;                    // offset of the point rows' ids in d_noisefit, or -1
-    std::vector<long> band;             // the same per band group
-    unsigned point_present = 0;         // bit g: some point row is in group g
-    std::vector<unsigned> band_present; // the same per band group
-    int n_groups = 0;
-    bool any = false;                   // some row is grouped
-};
-
-// Validates noise against the fit spec and lays its blocks out in stage (host work only: no context is touched).
-static int noise_scan(const vag_fit_spec* spec, const vag_noise_fit_spec* nz, std::vector<double>& stage, NoiseLayout& lay) {
-    if (nz->n_groups < 0 || nz->n_groups > VAG_NOISE_MAX_GROUPS)
-        return set_err(VAG_E_INVALID, "noise groups: n_groups must be in 0..%d, got %d", VAG_NOISE_MAX_GROUPS, nz->n_groups);
-    if (nz->n_bands != spec->n_bands)
-        return set_err(VAG_E_INVALID, "noise groups: n_bands must be the fit spec's %d, got %d", spec->n_bands, nz->n_bands);
-    if (nz->n_bands > 0 && (!nz->band_group || !spec->bands)) return set_err(VAG_E_INVALID, "noise groups: null band list");
-    for (int g = 0; g < nz->n_groups; ++g) {
-        if (!std::isfinite(nz->sys_fixed[g]) || nz->sys_fixed[g] < 0)
-            return set_err(VAG_E_INVALID, "noise group %d: the systematic must be finite and >= 0", g);
-        if (!std::isfinite(nz->calib[g]) || nz->calib[g] < 0)
-            return set_err(VAG_E_INVALID, "noise group %d: the calibration fraction must be finite and >= 0", g);
-    }
-    lay.n_groups = nz->n_groups;
-    stage.assign(2 * VAG_NOISE_MAX_GROUPS, 0.0);
-    for (int g = 0; g < nz->n_groups; ++g) {
-        stage[g] = nz->sys_fixed[g];
-        stage[VAG_NOISE_MAX_GROUPS + g] = nz->calib[g];
-    }
-    int passes[VAG_NOISE_MAX_GROUPS] = {0};  // in how many passes a group has rows
-    auto push_ids = [&](const int32_t* ids, int32_t same, int n) -> long {
-        const long at = (long)stage.size();
-        stage.resize(at + ((size_t)n + 1) / 2, 0.0);
-        int32_t* dst = reinterpret_cast<int32_t*>(stage.data() + at);
-        for (int i = 0; i < n; ++i) dst[i] = ids ? ids[i] : same;
-        return at;
-    };
-    const int n = spec->n_data;
-    if (nz->point_group && n > 0) {
-        for (int i = 0; i < n; ++i) {
-            const int id = nz->point_group[i];
-            if (id < -1 || id >= nz->n_groups)
-                return set_err(VAG_E_INVALID, "noise groups, point row %d: group %d is outside [-1, %d)", i, id, nz->n_groups);
-            if (id >= 0) lay.point_present |= 1u << id;
-        }
-        if (lay.point_present) {
-            lay.any = true;
-            lay.point = push_ids(nz->point_group, 0, n);
-            for (int g = 0; g < nz->n_groups; ++g) passes[g] += (lay.point_present >> g) & 1u;
-        }
-    }
-    lay.band.assign(std::max(spec->n_bands, 0), -1);
-    lay.band_present.assign(std::max(spec->n_bands, 0), 0u);
-    for (int b = 0; b < nz->n_bands; ++b) {
-        const int id = nz->band_group[b];
-        if (id < -1 || id >= nz->n_groups)
-            return set_err(VAG_E_INVALID, "noise groups, band group %d: group %d is outside [-1, %d)", b, id, nz->n_groups);
-        if (id < 0 || spec->bands[b].n <= 0) continue;
-        lay.any = true;
-        lay.band_present[b] = 1u << id;
-        lay.band[b] = push_ids(nullptr, id, spec->bands[b].n);
-        ++passes[id];
-    }
-    for (int g = 0; g < nz->n_groups; ++g)
-        if (nz->calib[g] > 0 && passes[g] > 1)
-            return set_err(VAG_E_INVALID,
-                           "noise group %d has a calibration fraction and rows in %d passes: such a group must hold point rows only or "
-                           "exactly one band group", g, passes[g]);
-    return VAG_OK;
+    return c->lim.upload(c->stream, h, stage);
 }
 
 static int upload_noise_spec(vag_ctx* c, const std::vector<double>& stage, const NoiseLayout& lay) {
@@ -4117,78 +3904,7 @@ static int upload_noise_spec(vag_ctx* c, const std::vector<double>& stage, const
     h = fnv1a(h, &lay.point, sizeof lay.point);
     if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
     h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    if (c->noisefit_hash_valid && c->noisefit_hash == h && c->noisefit_doubles == stage.size()) return VAG_OK;  // resident already
-    c->noisefit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_noisefit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    if (c->d_noisefit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    std::memcpy(c->h_noisefit.as<double>(), stage.data(), sizeof(double) * stage.size());
-    HIPCHK(hipMemcpyAsync(c->d_noisefit.p, c->h_noisefit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
-    c->noisefit_hash = h;
-    c->noisefit_doubles = stage.size();
-    c->noisefit_hash_valid = true;
-    return VAG_OK;
-}
-
-// ---- additive templates (vag_loglike_tmpl_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
-//      Layout in doubles: [amp_fixed 8], then for every pass with a touched row -- the point rows, a band group -- its values
-//      [n_templates][n].  A pass no template touches is not stored (offset -1): it is the pass without templates. ----
-struct TmplLayout {
-    long point = -1;                    // offset of the point rows' values in d_tmplfit, or -1
-    std::vector<long> band;             // the same per band group
-    unsigned point_present = 0;         // bit c: template c touches some point row
-    std::vector<unsigned> band_present; // the same per band group
-    unsigned ext_mask = 0;              // bit c: template c is extinguished
-    int n_templates = 0;
-    bool any = false;                   // some row is touched
-};
-
-// Validates tmpl against the fit spec and lays its blocks out in stage (host work only: no context is touched).
-static int tmpl_scan(const vag_fit_spec* spec, const vag_template_fit_spec* tp, std::vector<double>& stage, TmplLayout& lay) {
-    if (tp->n_templates < 0 || tp->n_templates > VAG_TMPL_MAX)
-        return set_err(VAG_E_INVALID, "templates: n_templates must be in 0..%d, got %d", VAG_TMPL_MAX, tp->n_templates);
-    if (tp->n_bands != 0 && tp->n_bands != spec->n_bands)
-        return set_err(VAG_E_INVALID, "templates: n_bands must be 0 or the fit spec's %d, got %d", spec->n_bands, tp->n_bands);
-    if (tp->n_bands > 0 && (!tp->bands || !spec->bands)) return set_err(VAG_E_INVALID, "templates: null band list");
-    const int nt = tp->n_templates;
-    for (int c = 0; c < nt; ++c) {
-        if (!std::isfinite(tp->amp_fixed[c]) || tp->amp_fixed[c] < 0)
-            return set_err(VAG_E_INVALID, "template %d: the fixed amplitude must be finite and >= 0", c);
-        if (tp->extinguished[c] != 0 && tp->extinguished[c] != 1)
-            return set_err(VAG_E_INVALID, "template %d: extinguished must be 0 or 1, got %d", c, tp->extinguished[c]);
-        lay.ext_mask |= (unsigned)tp->extinguished[c] << c;
-    }
-    lay.n_templates = nt;
-    stage.assign(VAG_TMPL_MAX, 0.0);
-    for (int c = 0; c < nt; ++c) stage[c] = tp->amp_fixed[c];
-    // one pass's block: checked, and stored when some value is not 0
-    auto push = [&](const double* T, int n, const char* what, int b, long& at, unsigned& present) -> int {
-        for (int c = 0; c < nt; ++c)
-            for (int i = 0; i < n; ++i) {
-                const double v = T[(size_t)c * n + i];
-                if (!std::isfinite(v) || v < 0) {
-                    if (b < 0) return set_err(VAG_E_INVALID, "template %d, %s %d: the value must be finite and >= 0", c, what, i);
-                    return set_err(VAG_E_INVALID, "template %d, %s %d, row %d: the value must be finite and >= 0", c, what, b, i);
-                }
-                if (v != 0.0) present |= 1u << c;
-            }
-        if (present) {
-            lay.any = true;
-            at = (long)stage.size();
-            stage.insert(stage.end(), T, T + (size_t)nt * n);
-        }
-        return VAG_OK;
-    };
-    int rc = VAG_OK;
-    if (tp->point && nt > 0 && spec->n_data > 0 && (rc = push(tp->point, spec->n_data, "point row", -1, lay.point, lay.point_present)))
-        return rc;
-    lay.band.assign(std::max(spec->n_bands, 0), -1);
-    lay.band_present.assign(std::max(spec->n_bands, 0), 0u);
-    for (int b = 0; b < tp->n_bands && nt > 0; ++b) {
-        if (!tp->bands[b] || spec->bands[b].n <= 0) continue;
-        if ((rc = push(tp->bands[b], spec->bands[b].n, "band group", b, lay.band[b], lay.band_present[b]))) return rc;
-    }
-    return VAG_OK;
+    return c->noise.upload(c->stream, h, stage);
 }
 
 static int upload_tmpl_spec(vag_ctx* c, const std::vector<double>& stage, const TmplLayout& lay) {
@@ -4196,81 +3912,7 @@ static int upload_tmpl_spec(vag_ctx* c, const std::vector<double>& stage, const 
     h = fnv1a(h, &lay.point, sizeof lay.point);
     if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
     h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    if (c->tmplfit_hash_valid && c->tmplfit_hash == h && c->tmplfit_doubles == stage.size()) return VAG_OK;  // resident already
-    c->tmplfit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_tmplfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    if (c->d_tmplfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    std::memcpy(c->h_tmplfit.as<double>(), stage.data(), sizeof(double) * stage.size());
-    HIPCHK(hipMemcpyAsync(c->d_tmplfit.p, c->h_tmplfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
-    c->tmplfit_hash = h;
-    c->tmplfit_doubles = stage.size();
-    c->tmplfit_hash_valid = true;
-    return VAG_OK;
-}
-
-// ---- counts groups (vag_loglike_counts_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
-//      in doubles, per group: [t_sample ns | N n | B n | a n | w n], then the sample indices (int32 [n m] in (n m + 1) / 2 doubles). ----
-constexpr int COUNTS_PPB = 64;  // (theta, phi) pairs per flux workgroup of a counts pass (vag_ctx::ppb_pin)
-
-struct CountsLayout {
-    std::vector<long> off;       // where group g starts in d_countsfit
-    std::vector<double> const2;  // -2 sum_i w_i S_i of group g (vag::poisson_const): the walker-independent half of its chi^2
-    int n_groups = 0;
-};
-
-// Validates the counts groups and lays their blocks out in stage (host work only: no context is touched).
-static int counts_scan(const vag_counts_fit_spec* cs, std::vector<double>& stage, CountsLayout& lay) {
-    if (cs->n_groups < 0 || !cs->groups) return set_err(VAG_E_INVALID, "counts groups: n_groups must be >= 0 with a group list, got %d", cs->n_groups);
-    lay.n_groups = cs->n_groups;
-    stage.clear();
-    for (int g = 0; g < cs->n_groups; ++g) {
-        const vag_counts_obs& o = cs->groups[g];
-        if (!(std::isfinite(o.nu_min) && std::isfinite(o.nu_max) && o.nu_min > 0 && o.nu_max > o.nu_min))
-            return set_err(VAG_E_INVALID, "counts group %d: the band needs 0 < nu_min < nu_max, both finite", g);
-        if (o.num_points < 2 || o.num_points > VAG_MAX_NU)
-            return set_err(VAG_E_INVALID, "counts group %d: num_points must be in 2..%d, got %d", g, VAG_MAX_NU, o.num_points);
-        if (o.n < 1) return set_err(VAG_E_INVALID, "counts group %d has no rows", g);
-        if (o.m < 1) return set_err(VAG_E_INVALID, "counts group %d: m (samples per row) must be >= 1, got %d", g, o.m);
-        if (o.n_samples < 1) return set_err(VAG_E_INVALID, "counts group %d has no sample times", g);
-        if (!o.t_sample || !o.sample_idx || !o.counts || !o.background || !o.scale || !o.weight)
-            return set_err(VAG_E_INVALID, "counts group %d: null array", g);
-        for (int j = 0; j < o.n_samples; ++j)
-            if (!std::isfinite(o.t_sample[j]) || !(o.t_sample[j] > 0) || (j > 0 && !(o.t_sample[j] > o.t_sample[j - 1])))
-                return set_err(VAG_E_INVALID, "counts group %d, sample %d: sample times must be finite, > 0 and strictly ascending", g, j);
-        double wS = 0;
-        for (int i = 0; i < o.n; ++i) {
-            const double N = o.counts[i];
-            if (!std::isfinite(N) || N < 0 || N != std::floor(N))
-                return set_err(VAG_E_INVALID, "counts group %d, row %d: counts must be a finite integer >= 0, got %g", g, i, N);
-            if (N > 9007199254740992.0) return set_err(VAG_E_INVALID, "counts group %d, row %d: counts above 2^53", g, i);
-            if (!std::isfinite(o.background[i]) || o.background[i] < 0)
-                return set_err(VAG_E_INVALID, "counts group %d, row %d: the background must be finite and >= 0", g, i);
-            if (!std::isfinite(o.scale[i]) || !(o.scale[i] > 0))
-                return set_err(VAG_E_INVALID, "counts group %d, row %d: the scale must be finite and > 0", g, i);
-            if (!std::isfinite(o.weight[i]) || o.weight[i] < 0)
-                return set_err(VAG_E_INVALID, "counts group %d, row %d: the weight must be finite and >= 0", g, i);
-            for (int k = 0; k < o.m; ++k) {
-                const int j = o.sample_idx[(size_t)i * o.m + k];
-                if (j < 0 || j >= o.n_samples)
-                    return set_err(VAG_E_INVALID, "counts group %d, row %d: sample index %d is outside [0, %d)", g, i, j, o.n_samples);
-            }
-            if (o.weight[i] > 0) wS += o.weight[i] * vag::poisson_const(N);
-        }
-        const size_t at = stage.size(), n = (size_t)o.n, nm = n * (size_t)o.m;
-        lay.off.push_back((long)at);
-        lay.const2.push_back(-2.0 * wS);
-        stage.resize(at + (size_t)o.n_samples + 4 * n + (nm + 1) / 2, 0.0);
-        double* dst = stage.data() + at;
-        std::memcpy(dst, o.t_sample, sizeof(double) * o.n_samples);
-        dst += o.n_samples;
-        for (const double* src : {o.counts, o.background, o.scale, o.weight}) {
-            std::memcpy(dst, src, sizeof(double) * n);
-            dst += n;
-        }
-        std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
-    }
-    return VAG_OK;
+    return c->tmpl.upload(c->stream, h, stage);
 }
 
 static int upload_counts_spec(vag_ctx* c, const vag_counts_fit_spec* cs, const std::vector<double>& stage, const CountsLayout& lay) {
@@ -4280,72 +3922,7 @@ static int upload_counts_spec(vag_ctx* c, const vag_counts_fit_spec* cs, const s
         h = fnv1a(h, head, sizeof head);
     }
     h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    if (c->countsfit_hash_valid && c->countsfit_hash == h && c->countsfit_doubles == stage.size()) return VAG_OK;  // resident already
-    c->countsfit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_countsfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    if (c->d_countsfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    std::memcpy(c->h_countsfit.as<double>(), stage.data(), sizeof(double) * stage.size());
-    HIPCHK(hipMemcpyAsync(c->d_countsfit.p, c->h_countsfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
-    c->countsfit_hash = h;
-    c->countsfit_doubles = stage.size();
-    c->countsfit_hash_valid = true;
-    return VAG_OK;
-}
-
-// ---- spectral-index groups (vag_loglike_index_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
-//      Layout in doubles, per group: [t n K | nu n K | s n | sigma n | w n | c K]; the first two are the series points (t_i, nu_k), i
-//      outer, as prep_times takes them. ----
-struct IndexLayout {
-    std::vector<long> off;  // where group g starts in d_indexfit
-    int n_groups = 0;
-};
-
-// Validates the spectral-index groups and lays their blocks out in stage (host work only: no context is touched).
-static int index_scan(const vag_index_fit_spec* is, std::vector<double>& stage, IndexLayout& lay) {
-    if (is->n_groups < 0 || !is->groups) return set_err(VAG_E_INVALID, "index groups: n_groups must be >= 0 with a group list, got %d", is->n_groups);
-    lay.n_groups = is->n_groups;
-    lay.off.clear();
-    stage.clear();
-    for (int g = 0; g < is->n_groups; ++g) {
-        const vag_index_obs& o = is->groups[g];
-        if (o.k < 2 || o.k > VAG_INDEX_MAX_NODES)
-            return set_err(VAG_E_INVALID, "index group %d: k (frequencies) must be in 2..%d, got %d", g, VAG_INDEX_MAX_NODES, o.k);
-        if (o.n < 1) return set_err(VAG_E_INVALID, "index group %d has no rows", g);
-        if (o.n > (1 << 24)) return set_err(VAG_E_INVALID, "index group %d: more than %d rows", g, 1 << 24);
-        if (!o.nu || !o.coef || !o.t || !o.value || !o.err || !o.weight) return set_err(VAG_E_INVALID, "index group %d: null array", g);
-        for (int k = 0; k < o.k; ++k) {
-            if (!std::isfinite(o.nu[k]) || !(o.nu[k] > 0) || (k > 0 && !(o.nu[k] > o.nu[k - 1])))
-                return set_err(VAG_E_INVALID, "index group %d, frequency %d: frequencies must be finite, > 0 and strictly ascending", g, k);
-            if (!std::isfinite(o.coef[k])) return set_err(VAG_E_INVALID, "index group %d, coefficient %d is not finite", g, k);
-        }
-        if (!std::isfinite(o.ext_slope)) return set_err(VAG_E_INVALID, "index group %d: ext_slope is not finite", g);
-        for (int i = 0; i < o.n; ++i) {
-            if (!std::isfinite(o.t[i]) || !(o.t[i] > 0) || (i > 0 && o.t[i] < o.t[i - 1]))
-                return set_err(VAG_E_INVALID, "index group %d, row %d: times must be finite, > 0 and ascending", g, i);
-            if (!std::isfinite(o.value[i])) return set_err(VAG_E_INVALID, "index group %d, row %d: the index is not finite", g, i);
-            if (!std::isfinite(o.err[i]) || !(o.err[i] > 0))
-                return set_err(VAG_E_INVALID, "index group %d, row %d: the error must be finite and > 0", g, i);
-            if (!std::isfinite(o.weight[i]) || o.weight[i] < 0)
-                return set_err(VAG_E_INVALID, "index group %d, row %d: the weight must be finite and >= 0", g, i);
-        }
-        const size_t at = stage.size(), n = (size_t)o.n, K = (size_t)o.k;
-        lay.off.push_back((long)at);
-        stage.resize(at + 2 * n * K + 3 * n + K, 0.0);
-        double* dst = stage.data() + at;
-        for (size_t i = 0; i < n; ++i)
-            for (size_t k = 0; k < K; ++k) {
-                dst[i * K + k] = o.t[i];
-                dst[n * K + i * K + k] = o.nu[k];
-            }
-        dst += 2 * n * K;
-        for (const double* src : {o.value, o.err, o.weight}) {
-            std::memcpy(dst, src, sizeof(double) * n);
-            dst += n;
-        }
-        std::memcpy(dst, o.coef, sizeof(double) * K);
-    }
-    return VAG_OK;
+    return c->counts.upload(c->stream, h, stage);
 }
 
 static int upload_index_spec(vag_ctx* c, const vag_index_fit_spec* is, const std::vector<double>& stage) {
@@ -4355,117 +3932,7 @@ static int upload_index_spec(vag_ctx* c, const vag_index_fit_spec* is, const std
         h = fnv1a(h, head, sizeof head);
     }
     h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    if (c->indexfit_hash_valid && c->indexfit_hash == h && c->indexfit_doubles == stage.size()) return VAG_OK;  // resident already
-    c->indexfit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_indexfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    if (c->d_indexfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    std::memcpy(c->h_indexfit.as<double>(), stage.data(), sizeof(double) * stage.size());
-    HIPCHK(hipMemcpyAsync(c->d_indexfit.p, c->h_indexfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
-    c->indexfit_hash = h;
-    c->indexfit_doubles = stage.size();
-    c->indexfit_hash_valid = true;
-    return VAG_OK;
-}
-
-// ---- fold groups (vag_loglike_fold_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout in
-//      doubles, per group: [t ns J | nu ns J | A J C | sigma J | exposure / m n | N n C | B n C | w n C], then the sample indices
-//      (int32 [n m] in (n m + 1) / 2 doubles); the first two are the series points (t_sample_s, nu_j), s outer, as prep_times takes
-//      them; sigma is zeros for a group without one (the kernel is handed a null pointer then). ----
-struct FoldLayout {
-    std::vector<long> off;       // where group g starts in d_foldfit
-    std::vector<double> const2;  // -2 sum_{i,c} w S of group g (vag::poisson_const): the walker-independent half of its chi^2
-    bool any_sigma = false;      // some group carries a cross-section: N_H is read
-    int n_groups = 0;
-};
-
-// Validates the fold groups and lays their blocks out in stage (host work only: no context is touched).
-static int fold_scan(const vag_fit_spec* spec, const vag_fold_fit_spec* fs, std::vector<double>& stage, FoldLayout& lay) {
-    if (fs->n_groups < 0 || !fs->groups) return set_err(VAG_E_INVALID, "fold groups: n_groups must be >= 0 with a group list, got %d", fs->n_groups);
-    if (!std::isfinite(fs->n_h_fixed) || fs->n_h_fixed < 0) return set_err(VAG_E_INVALID, "fold groups: n_h_fixed must be finite and >= 0");
-    lay.n_groups = fs->n_groups;
-    lay.off.clear();
-    lay.const2.clear();
-    lay.any_sigma = false;
-    stage.clear();
-    for (int g = 0; g < fs->n_groups; ++g) {
-        const vag_fold_obs& o = fs->groups[g];
-        if (o.J < 1 || o.J > VAG_FOLD_MAX_BINS)
-            return set_err(VAG_E_INVALID, "fold group %d: J (energy bins) must be in 1..%d, got %d", g, VAG_FOLD_MAX_BINS, o.J);
-        if (o.C < 1 || o.C > VAG_FOLD_MAX_CHANNELS)
-            return set_err(VAG_E_INVALID, "fold group %d: C (channels) must be in 1..%d, got %d", g, VAG_FOLD_MAX_CHANNELS, o.C);
-        if (o.n < 1) return set_err(VAG_E_INVALID, "fold group %d has no rows", g);
-        if (o.m < 1) return set_err(VAG_E_INVALID, "fold group %d: m (samples per row) must be >= 1, got %d", g, o.m);
-        if (o.n_samples < 1) return set_err(VAG_E_INVALID, "fold group %d has no sample times", g);
-        if (o.n > (1 << 16) || o.m > (1 << 10) || o.n_samples > (1 << 18))
-            return set_err(VAG_E_INVALID, "fold group %d: more than %d rows, %d samples per row or %d sample times", g, 1 << 16, 1 << 10, 1 << 18);
-        if (!o.nu || !o.A || !o.t_sample || !o.sample_idx || !o.exposure_over_m || !o.counts || !o.background || !o.weight)
-            return set_err(VAG_E_INVALID, "fold group %d: null array", g);
-        for (int j = 0; j < o.J; ++j) {
-            if (!std::isfinite(o.nu[j]) || !(o.nu[j] > 0) || (j > 0 && !(o.nu[j] > o.nu[j - 1])))
-                return set_err(VAG_E_INVALID, "fold group %d, bin %d: frequencies must be finite, > 0 and strictly ascending", g, j);
-            if (o.sigma && (!std::isfinite(o.sigma[j]) || o.sigma[j] < 0))
-                return set_err(VAG_E_INVALID, "fold group %d, bin %d: the cross-section must be finite and >= 0", g, j);
-            for (int ch = 0; ch < o.C; ++ch) {
-                const double a = o.A[(size_t)j * o.C + ch];
-                if (!std::isfinite(a) || a < 0)
-                    return set_err(VAG_E_INVALID, "fold group %d, bin %d, channel %d: the response must be finite and >= 0", g, j, ch);
-            }
-        }
-        for (int j = 0; j < o.n_samples; ++j)
-            if (!std::isfinite(o.t_sample[j]) || !(o.t_sample[j] > 0) || (j > 0 && !(o.t_sample[j] > o.t_sample[j - 1])))
-                return set_err(VAG_E_INVALID, "fold group %d, sample %d: sample times must be finite, > 0 and strictly ascending", g, j);
-        double wS = 0;
-        for (int i = 0; i < o.n; ++i) {
-            if (!std::isfinite(o.exposure_over_m[i]) || !(o.exposure_over_m[i] > 0))
-                return set_err(VAG_E_INVALID, "fold group %d, row %d: exposure_over_m must be finite and > 0", g, i);
-            for (int k = 0; k < o.m; ++k) {
-                const int j = o.sample_idx[(size_t)i * o.m + k];
-                if (j < 0 || j >= o.n_samples)
-                    return set_err(VAG_E_INVALID, "fold group %d, row %d: sample index %d is outside [0, %d)", g, i, j, o.n_samples);
-            }
-            for (int ch = 0; ch < o.C; ++ch) {
-                const size_t at = (size_t)i * o.C + ch;
-                const double N = o.counts[at];
-                if (!std::isfinite(N) || N < 0 || N != std::floor(N))
-                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: counts must be a finite integer >= 0, got %g", g, i, ch, N);
-                if (N > 9007199254740992.0) return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: counts above 2^53", g, i, ch);
-                if (!std::isfinite(o.background[at]) || o.background[at] < 0)
-                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: the background must be finite and >= 0", g, i, ch);
-                if (!std::isfinite(o.weight[at]) || o.weight[at] < 0)
-                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: the weight must be finite and >= 0", g, i, ch);
-                if (o.weight[at] > 0) wS += o.weight[at] * vag::poisson_const(N);
-            }
-        }
-        if (o.sigma) lay.any_sigma = true;
-        const size_t at = stage.size(), J = (size_t)o.J, C = (size_t)o.C, n = (size_t)o.n, ns = (size_t)o.n_samples, nm = n * (size_t)o.m;
-        lay.off.push_back((long)at);
-        lay.const2.push_back(-2.0 * wS);
-        stage.resize(at + 2 * ns * J + J * C + J + n + 3 * n * C + (nm + 1) / 2, 0.0);
-        double* dst = stage.data() + at;
-        for (size_t q = 0; q < ns; ++q)
-            for (size_t j = 0; j < J; ++j) {
-                dst[q * J + j] = o.t_sample[q];
-                dst[ns * J + q * J + j] = o.nu[j];
-            }
-        dst += 2 * ns * J;
-        std::memcpy(dst, o.A, sizeof(double) * J * C);
-        dst += J * C;
-        if (o.sigma) std::memcpy(dst, o.sigma, sizeof(double) * J);
-        dst += J;
-        std::memcpy(dst, o.exposure_over_m, sizeof(double) * n);
-        dst += n;
-        for (const double* src : {o.counts, o.background, o.weight}) {
-            std::memcpy(dst, src, sizeof(double) * n * C);
-            dst += n * C;
-        }
-        std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
-    }
-    // (N_H is read by groups with a cross-section only: without one it is refused as a free parameter, the rule of east0 / north0)
-    if (!lay.any_sigma)
-        for (int d = 0; d < spec->ndim && d < 16; ++d)
-            if (spec->slot[d] == VAG_P_N_H) return set_err(VAG_E_INVALID, "bad parameter slot");
-    return VAG_OK;
+    return c->index.upload(c->stream, h, stage);
 }
 
 static int upload_fold_spec(vag_ctx* c, const vag_fold_fit_spec* fs, const std::vector<double>& stage) {
@@ -4476,70 +3943,7 @@ static int upload_fold_spec(vag_ctx* c, const vag_fold_fit_spec* fs, const std::
         h = fnv1a(h, head, sizeof head);
     }
     h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    if (c->foldfit_hash_valid && c->foldfit_hash == h && c->foldfit_doubles == stage.size()) return VAG_OK;  // resident already
-    c->foldfit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_foldfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    if (c->d_foldfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    std::memcpy(c->h_foldfit.as<double>(), stage.data(), sizeof(double) * stage.size());
-    HIPCHK(hipMemcpyAsync(c->d_foldfit.p, c->h_foldfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
-    c->foldfit_hash = h;
-    c->foldfit_doubles = stage.size();
-    c->foldfit_hash_valid = true;
-    return VAG_OK;
-}
-
-// ---- correlated groups (vag_loglike_cov_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
-//      in doubles, per group: [t n | nu n | ln_flux n | ext n | Wt n n]; the first two are the series points as prep_times takes
-//      them; ext is zeros for a group without one (the kernel is handed a null pointer then); Wt[j n + i] = W_ij for j <= i, else 0:
-//      the whitener transposed, so that a wavefront whose lanes hold consecutive rows i loads consecutive doubles. ----
-struct CovLayout {
-    std::vector<long> off;  // where group g starts in d_covfit
-    int n_groups = 0;
-};
-
-// Validates the correlated groups and lays their blocks out in stage (host work only: no context is touched).
-static int cov_scan(const vag_cov_fit_spec* cs, std::vector<double>& stage, CovLayout& lay) {
-    if (cs->n_groups < 0 || cs->n_groups > VAG_COV_MAX_GROUPS)
-        return set_err(VAG_E_INVALID, "correlated groups: n_groups must be in 0..%d, got %d", VAG_COV_MAX_GROUPS, cs->n_groups);
-    if (!cs->groups) return set_err(VAG_E_INVALID, "correlated groups: null group list");
-    lay.n_groups = cs->n_groups;
-    lay.off.clear();
-    stage.clear();
-    for (int g = 0; g < cs->n_groups; ++g) {
-        const vag_cov_obs& o = cs->groups[g];
-        if (o.n < 1 || o.n > VAG_COV_MAX_ROWS)
-            return set_err(VAG_E_INVALID, "correlated group %d: n (rows) must be in 1..%d, got %d", g, VAG_COV_MAX_ROWS, o.n);
-        if (!o.t || !o.nu || !o.ln_flux || !o.whitener) return set_err(VAG_E_INVALID, "correlated group %d: null array", g);
-        if (!std::isfinite(o.weight) || o.weight < 0)
-            return set_err(VAG_E_INVALID, "correlated group %d: the weight must be finite and >= 0", g);
-        const size_t n = (size_t)o.n;
-        for (int i = 0; i < o.n; ++i) {
-            if (!std::isfinite(o.t[i]) || !(o.t[i] > 0) || (i > 0 && o.t[i] < o.t[i - 1]))
-                return set_err(VAG_E_INVALID, "correlated group %d, row %d: times must be finite, > 0 and ascending", g, i);
-            if (!std::isfinite(o.nu[i]) || !(o.nu[i] > 0))
-                return set_err(VAG_E_INVALID, "correlated group %d, row %d: the frequency must be finite and > 0", g, i);
-            if (!std::isfinite(o.ln_flux[i])) return set_err(VAG_E_INVALID, "correlated group %d, row %d: ln_flux is not finite", g, i);
-            if (o.ext && !std::isfinite(o.ext[i])) return set_err(VAG_E_INVALID, "correlated group %d, row %d: ext is not finite", g, i);
-            for (int j = 0; j <= i; ++j)
-                if (!std::isfinite(o.whitener[i * n + j]))
-                    return set_err(VAG_E_INVALID, "correlated group %d, row %d: whitener entry %d is not finite", g, i, j);
-            if (!(o.whitener[i * n + i] > 0))
-                return set_err(VAG_E_INVALID, "correlated group %d, row %d: the whitener's diagonal entry must be > 0", g, i);
-        }
-        const size_t at = stage.size();
-        lay.off.push_back((long)at);
-        stage.resize(at + 4 * n + n * n, 0.0);
-        double* dst = stage.data() + at;
-        std::memcpy(dst, o.t, sizeof(double) * n);
-        std::memcpy(dst + n, o.nu, sizeof(double) * n);
-        std::memcpy(dst + 2 * n, o.ln_flux, sizeof(double) * n);
-        if (o.ext) std::memcpy(dst + 3 * n, o.ext, sizeof(double) * n);
-        double* Wt = dst + 4 * n;
-        for (size_t i = 0; i < n; ++i)
-            for (size_t j = 0; j <= i; ++j) Wt[j * n + i] = o.whitener[i * n + j];
-    }
-    return VAG_OK;
+    return c->fold.upload(c->stream, h, stage);
 }
 
 static int upload_cov_spec(vag_ctx* c, const vag_cov_fit_spec* cs, const std::vector<double>& stage) {
@@ -4549,74 +3953,10 @@ static int upload_cov_spec(vag_ctx* c, const vag_cov_fit_spec* cs, const std::ve
         h = fnv1a(h, head, sizeof head);
     }
     h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    if (c->covfit_hash_valid && c->covfit_hash == h && c->covfit_doubles == stage.size()) return VAG_OK;  // resident already
-    c->covfit_hash_valid = false;
-    HIPCHK(hipStreamSynchronize(c->stream));  // an earlier staging copy may still be in flight
-    if (c->h_covfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    if (c->d_covfit.ensure(sizeof(double) * stage.size())) return VAG_E_HIP;
-    std::memcpy(c->h_covfit.as<double>(), stage.data(), sizeof(double) * stage.size());
-    HIPCHK(hipMemcpyAsync(c->d_covfit.p, c->h_covfit.as<double>(), sizeof(double) * stage.size(), hipMemcpyHostToDevice, c->stream));
-    c->covfit_hash = h;
-    c->covfit_doubles = stage.size();
-    c->covfit_hash_valid = true;
-    return VAG_OK;
+    return c->cov.upload(c->stream, h, stage);
 }
 
-// ---- one likelihood request.  Every vag_loglike_*_batch entry point fills a FitRequest from its arguments (a spec it does not take
-//      stays null) and calls loglike_dev or loglike_host; a request whose optional blocks are null or empty is therefore the narrower
-//      entry point's request, statement for statement. ----
-namespace {
-struct FitRequest {
-    const vag_fit_spec* spec = nullptr;
-    const vag_sky_fit_spec* sky = nullptr;      // after fit_request_prepare: null when nothing reads the placement
-    const vag_vis_fit_spec* vis = nullptr;      // after fit_request_prepare: null when it has no group; so pol, counts, index, fold
-    const vag_pol_fit_spec* pol = nullptr;
-    const vag_limit_fit_spec* lim = nullptr;    // after fit_request_prepare: null when no row is a limit (llay.any)
-    const vag_noise_fit_spec* noise = nullptr;  // after fit_request_prepare: null when no row is grouped (nlay.any)
-    const vag_counts_fit_spec* counts = nullptr;
-    const vag_index_fit_spec* index = nullptr;
-    const vag_fold_fit_spec* fold = nullptr;
-    const vag_template_fit_spec* tmpl = nullptr;  // after fit_request_prepare: null when no row is touched (tlay.any)
-    const vag_cov_fit_spec* cov = nullptr;        // after fit_request_prepare: null when it has no group
-    LimLayout llay;
-    NoiseLayout nlay;
-    CountsLayout clay;
-    IndexLayout ilay;
-    FoldLayout flay;
-    TmplLayout tlay;
-    CovLayout vlay;
-    std::vector<double> lstage, nstage, cstage, istage, fstage, tstage, vstage;  // what the scans lay out for upload_{lim,noise,counts,index,fold,tmpl,cov}_spec
-    bool placed = false;                                 // some group reads east0 / north0
-    bool prepared = false;                               // fit_request_prepare has run
-};
-}  // namespace
-
-// Normalises the request and scans its host-side blocks, once per call (host work only: no context is touched).  spec is not null.
-static int fit_request_prepare(FitRequest& r) {
-    if (r.prepared) return VAG_OK;
-    if (r.vis && r.vis->n_groups == 0) r.vis = nullptr;
-    if (r.counts && r.counts->n_groups == 0) r.counts = nullptr;
-    if (r.index && r.index->n_groups == 0) r.index = nullptr;
-    if (r.fold && r.fold->n_groups == 0) r.fold = nullptr;
-    if (r.cov && r.cov->n_groups == 0) r.cov = nullptr;
-    int rc = VAG_OK;
-    if (r.cov && (rc = cov_scan(r.cov, r.vstage, r.vlay))) return rc;
-    if (r.tmpl && (rc = tmpl_scan(r.spec, r.tmpl, r.tstage, r.tlay))) return rc;
-    if (r.fold && (rc = fold_scan(r.spec, r.fold, r.fstage, r.flay))) return rc;
-    if (r.index && (rc = index_scan(r.index, r.istage, r.ilay))) return rc;
-    if (r.counts && (rc = counts_scan(r.counts, r.cstage, r.clay))) return rc;
-    if (r.noise && (rc = noise_scan(r.spec, r.noise, r.nstage, r.nlay))) return rc;
-    if (r.lim && (rc = lim_scan(r.spec, r.pol, r.lim, r.lstage, r.llay))) return rc;  // (pol as given: an empty list checks n_pol_groups)
-    if (!r.nlay.any) r.noise = nullptr;
-    if (!r.llay.any) r.lim = nullptr;
-    if (!r.tlay.any) r.tmpl = nullptr;  // (tlay.n_templates stays: the amplitude slots of the spec's templates are accepted)
-    if (r.pol && r.pol->n_groups == 0) r.pol = nullptr;
-    r.placed = (r.sky && r.sky->n_groups > 0) || r.vis;
-    // (east0 / north0 place centroid and visibility groups only: without such a group they are refused as free parameters)
-    if (!r.pol && !r.placed) r.sky = nullptr;  // nothing reads the placement
-    r.prepared = true;
-    return VAG_OK;
-}
+constexpr int COUNTS_PPB = 64;  // (theta, phi) pairs per flux workgroup of a counts pass (vag_ctx::ppb_pin)
 
 static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec) {
     const vag_fit_spec* spec = req.spec;
@@ -4634,7 +3974,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     double* d_chi2 = c->d_chi2.as<double>();
     double* d_av = d_chi2 + nb;
     double* d_lp = d_chi2 + 2 * (size_t)nb;
-    double* d = c->d_fit.as<double>();
+    double* d = c->fit.d.as<double>();
     const double* d_prior = d + c->fit_prior_off;
     vag_model_params* d_params = c->d_params.as<vag_model_params>();
     // evaluation order: by the costs of the previous call with this batch size (see vag_ctx::d_order)
@@ -4682,23 +4022,23 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
         n_inv = std::max(n_inv, c->plan.n_models_invalid);
         return VAG_OK;
     };
-    // the back of a flux pass.  lim_off: where the pass's block of limit rows starts in d_limfit, or -1 (no limit row: the kernel as it
-    // was); noise_off, present: where the pass's group ids start in d_noisefit, or -1 (no grouped row: the kernels as they were), and
-    // its groups; tmpl_off, tpresent: where the pass's template values start in d_tmplfit, or -1 (no touched row: the kernels as they
+    // the back of a flux pass.  lim_off: where the pass's block of limit rows starts in lim.d, or -1 (no limit row: the kernel as it
+    // was); noise_off, present: where the pass's group ids start in noise.d, or -1 (no grouped row: the kernels as they were), and
+    // its groups; tmpl_off, tpresent: where the pass's template values start in tmpl.d, or -1 (no touched row: the kernels as they
     // were), and the templates that touch it
     auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext,
                     long lim_off, long noise_off, unsigned present, long tmpl_off, unsigned tpresent) -> int {
-        const double* lb = lim_off >= 0 ? c->d_limfit.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
+        const double* lb = lim_off >= 0 ? c->lim.d.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
         const int* lk = lb ? reinterpret_cast<const int*>(lb + 2 * (size_t)npts) : nullptr;
         const double* ls = lb ? lb + npts : nullptr;
         if (tmpl_off >= 0) {
-            const double* nz = noise_off >= 0 ? c->d_noisefit.as<double>() : nullptr;
-            const double* tp = c->d_tmplfit.as<double>();  // [amp_fixed 8 | the passes' values]
+            const double* nz = noise_off >= 0 ? c->noise.d.as<double>() : nullptr;
+            const double* tp = c->tmpl.d.as<double>();  // [amp_fixed 8 | the passes' values]
             hipLaunchKernelGGL(vag_fit_back_tmpl_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av, fit_pass(),
                                next_order(), lk, lb, ls, d_theta, ndim, d_prior, nz, nz ? reinterpret_cast<const int*>(nz + noise_off) : nullptr,
                                nz ? present : 0u, tp + tmpl_off, req.tlay.n_templates, tpresent, tp, req.tlay.ext_mask);
         } else if (noise_off >= 0) {
-            const double* nz = c->d_noisefit.as<double>();
+            const double* nz = c->noise.d.as<double>();
             hipLaunchKernelGGL(vag_fit_back_noise_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av, fit_pass(),
                                next_order(), lk, lb, ls, d_theta, ndim, d_prior, nz, reinterpret_cast<const int*>(nz + noise_off), present);
         } else {
@@ -4706,6 +4046,18 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
                                lne, w, ext, d_av, fit_pass(), next_order(), lk, lb, ls);
         }
         return end_pass();
+    };
+    // the front half of a series-group pass (index, fold, cov groups): the group's np points, whose times and frequencies lie at d_t
+    // and d_nu of its resident block, through the model stages and one series request.  nu_pts: the points' frequencies on the host
+    // for the shared-node test of a short series, or null for none.  Leaves the fluxes in d_series_flux or sets rc; not 0: no memory.
+    auto series_group_flux = [&](const double* d_t, const double* d_nu, size_t np, const double* nu_pts) -> int {
+        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(np, (size_t)std::max(n, 1)))) return VAG_E_HIP;
+        rc = prep_times(c, d_t, (int)np, d_nu, (int)np);
+        begin_pass();
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
+        if (rc == VAG_OK)  // (in chunks above 512 points)
+            rc = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), nu_pts ? upload_series_bands(c, nu_pts, (int)np) : 0);
+        return VAG_OK;
     };
     c->ic_soft_fail = true;
     if (n > 0) {  // point data: one (t, nu) series per walker (fitter.py:510-522)
@@ -4746,7 +4098,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     size_t soff = 0;
     for (int g = 0; g < n_groups && rc == VAG_OK; ++g) {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
         const vag_centroid_obs& o = sky->groups[g];
-        const double* ds = c->d_skyfit.as<double>() + soff;  // [nu | t | east | north | err_east | err_north | weight]
+        const double* ds = c->sky.d.as<double>() + soff;  // [nu | t | east | north | err_east | err_north | weight]
         soff += 1 + 6 * (size_t)o.n;
         if (c->d_skycmom.ensure(sizeof(double) * (size_t)nb * o.n * 6)) return VAG_E_HIP;
         rc = prep_times(c, ds + 1, o.n, ds, 1);
@@ -4762,7 +4114,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     for (int g = 0; g < n_vis_groups && rc == VAG_OK; ++g) {  // visibility groups: one pass each, the chi^2 formed by the chi2 kernel
         const vag_visibility_obs& o = req.vis->groups[g];
         const vag_ctx::VisLayout& lay = c->vis_layout[g];
-        const double* ds = c->d_visfit.as<double>() + lay.obs_off;  // [nu | t | ...]
+        const double* ds = c->vis.d.as<double>() + lay.obs_off;  // [nu | t | ...]
         rc = prep_times(c, ds + 1, o.n_epochs, ds, 1);
         begin_pass();
         if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
@@ -4793,7 +4145,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     }
     for (int g = 0; g < n_pol_groups && rc == VAG_OK; ++g) {  // polarization groups: one pass each, the Stokes sums of sky_request
         const vag_polarization_obs& o = req.pol->groups[g];
-        const double* ds = c->d_polfit.as<double>() + poff;  // [nu | t | q | u | err_q | err_u | weight]
+        const double* ds = c->pol.d.as<double>() + poff;  // [nu | t | q | u | err_q | err_u | weight]
         poff += 1 + 6 * (size_t)o.n;
         if (c->d_polstokes.ensure(sizeof(double) * (size_t)nb * o.n * 3)) return VAG_E_HIP;
         rc = prep_times(c, ds + 1, o.n, ds, 1);
@@ -4802,7 +4154,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
         if (rc == VAG_OK)
             rc = pol_stokes_request(c, d_params, nb, o.n, o.n_az > 0 ? o.n_az : 256, c->d_polspec.as<double>(), c->d_polstokes.as<double>());
         if (rc == VAG_OK) {
-            const int* lk = (req.lim && req.llay.pol[g] >= 0) ? reinterpret_cast<const int*>(c->d_limfit.as<double>() + req.llay.pol[g]) : nullptr;
+            const int* lk = (req.lim && req.llay.pol[g] >= 0) ? reinterpret_cast<const int*>(c->lim.d.as<double>() + req.llay.pol[g]) : nullptr;
             const int* bad = reinterpret_cast<const int*>(c->d_polspec.as<double>() + 4 * (size_t)nb);
             hipLaunchKernelGGL(lk ? vag_fit_pol_back_kernel<true> : vag_fit_pol_back_kernel<false>, dim3(nb), dim3(64), 0, st,
                                c->d_polstokes.as<double>(), o.n, o.kind, ds + 1, bad, d_theta, ndim, d_prior, sky ? sky->pa_fixed : 0.0,
@@ -4812,7 +4164,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     }
     for (int g = 0; g < n_counts_groups && rc == VAG_OK; ++g) {  // counts groups: one band request on the sample times each, then the Poisson term
         const vag_counts_obs& o = req.counts->groups[g];
-        const double* dc = c->d_countsfit.as<double>() + req.clay.off[g];  // [t_sample | N | B | a | w | idx]
+        const double* dc = c->counts.d.as<double>() + req.clay.off[g];  // [t_sample | N | B | a | w | idx]
         const size_t ns = (size_t)o.n_samples, nr = (size_t)o.n;
         if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(ns, (size_t)std::max(n, 1)))) return VAG_E_HIP;
         begin_pass();
@@ -4832,21 +4184,12 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     }
     for (int g = 0; g < n_index_groups && rc == VAG_OK; ++g) {  // spectral-index groups: the n K points as one series request each, then the slope term
         const vag_index_obs& o = req.index->groups[g];
-        const double* di = c->d_indexfit.as<double>() + req.ilay.off[g];  // [t n K | nu n K | s | sigma | w | c]
+        const double* di = c->index.d.as<double>() + req.ilay.off[g];  // [t n K | nu n K | s | sigma | w | c]
         const size_t nr = (size_t)o.n, np = nr * (size_t)o.k;
-        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(np, (size_t)std::max(n, 1)))) return VAG_E_HIP;
-        rc = prep_times(c, di, (int)np, di + np, (int)np);
-        begin_pass();
-        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
-        if (rc == VAG_OK) {
-            int shared = 0;  // K <= 8 distinct frequencies: the shared-node path of a short series
-            if (np <= (size_t)FITROWS_MAX_POINTS) {
-                double nu_pts[FITROWS_MAX_POINTS];
-                for (size_t i = 0; i < np; ++i) nu_pts[i] = o.nu[i % (size_t)o.k];
-                shared = upload_series_bands(c, nu_pts, (int)np);
-            }
-            rc = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), shared);
-        }
+        double nu_pts[FITROWS_MAX_POINTS];  // K <= 8 distinct frequencies: the shared-node path of a short series
+        const bool is_short = np <= (size_t)FITROWS_MAX_POINTS;
+        for (size_t i = 0; is_short && i < np; ++i) nu_pts[i] = o.nu[i % (size_t)o.k];
+        if (series_group_flux(di, di + np, np, is_short ? nu_pts : nullptr)) return VAG_E_HIP;
         if (rc == VAG_OK) {
             hipLaunchKernelGGL(vag_fit_back_index_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, o.k,
                                di + 2 * np, di + 2 * np + nr, di + 2 * np + 2 * nr, di + 2 * np + 3 * nr, o.ext_slope, d_av, fit_pass(),
@@ -4856,21 +4199,12 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     }
     for (int g = 0; g < n_fold_groups && rc == VAG_OK; ++g) {  // fold groups: the n_samples J points as one series request each, then the folded Poisson term
         const vag_fold_obs& o = req.fold->groups[g];
-        const double* df = c->d_foldfit.as<double>() + req.flay.off[g];  // [t ns J | nu ns J | A | sigma | exposure / m | N | B | w | idx]
+        const double* df = c->fold.d.as<double>() + req.flay.off[g];  // [t ns J | nu ns J | A | sigma | exposure / m | N | B | w | idx]
         const size_t J = (size_t)o.J, nc = (size_t)o.n * (size_t)o.C, np = (size_t)o.n_samples * J;
-        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(np, (size_t)std::max(n, 1)))) return VAG_E_HIP;
-        rc = prep_times(c, df, (int)np, df + np, (int)np);
-        begin_pass();
-        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
-        if (rc == VAG_OK) {
-            int shared = 0;  // J <= 8 distinct frequencies: the shared-node path of a short series
-            if (np <= (size_t)FITROWS_MAX_POINTS) {
-                double nu_pts[FITROWS_MAX_POINTS];
-                for (size_t i = 0; i < np; ++i) nu_pts[i] = o.nu[i % J];
-                shared = upload_series_bands(c, nu_pts, (int)np);
-            }
-            rc = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), shared);  // (in chunks above 512 points)
-        }
+        double nu_pts[FITROWS_MAX_POINTS];  // J <= 8 distinct frequencies: the shared-node path of a short series
+        const bool is_short = np <= (size_t)FITROWS_MAX_POINTS;
+        for (size_t i = 0; is_short && i < np; ++i) nu_pts[i] = o.nu[i % J];
+        if (series_group_flux(df, df + np, np, is_short ? nu_pts : nullptr)) return VAG_E_HIP;
         if (rc == VAG_OK) {
             const double* dA = df + 2 * np;
             const double* dsig = dA + J * (size_t)o.C;
@@ -4884,14 +4218,10 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     }
     for (int g = 0; g < n_cov_groups && rc == VAG_OK; ++g) {  // correlated groups: the n rows as one series request each, then the whitened term
         const vag_cov_obs& o = req.cov->groups[g];
-        const double* dv = c->d_covfit.as<double>() + req.vlay.off[g];  // [t | nu | ln_flux | ext | Wt]
+        const double* dv = c->cov.d.as<double>() + req.vlay.off[g];  // [t | nu | ln_flux | ext | Wt]
         const size_t nr = (size_t)o.n;
-        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(nr, (size_t)std::max(n, 1)))) return VAG_E_HIP;
-        rc = prep_times(c, dv, o.n, dv + nr, o.n);
-        begin_pass();
-        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
-        if (rc == VAG_OK)  // (n <= 256 points: the shared-node path of a short series when the rows hold <= 8 distinct frequencies)
-            rc = series_request(c, d_params, nb, o.n, c->d_series_flux.as<double>(), upload_series_bands(c, o.nu, o.n));
+        // (n <= 256 points: the shared-node path of a short series when the rows hold <= 8 distinct frequencies)
+        if (series_group_flux(dv, dv + nr, nr, o.nu)) return VAG_E_HIP;
         if (rc == VAG_OK) {
             hipLaunchKernelGGL(vag_fit_back_cov_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, dv + 2 * nr,
                                o.ext ? dv + 3 * nr : nullptr, dv + 4 * nr, o.weight, d_av, fit_pass(), next_order());
@@ -4962,17 +4292,6 @@ static int loglike_host(vag_ctx* c, FitRequest& req, const double* theta, int nb
     HIPCHK(hipStreamSynchronize(c->stream));
     (void)collect_times(c);
     return VAG_OK;
-}
-
-static FitRequest fit_request(const vag_fit_spec* spec, const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
-                              const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr,
-                              const vag_noise_fit_spec* noise = nullptr, const vag_counts_fit_spec* counts = nullptr,
-                              const vag_index_fit_spec* index = nullptr, const vag_fold_fit_spec* fold = nullptr,
-                              const vag_template_fit_spec* tmpl = nullptr, const vag_cov_fit_spec* cov = nullptr) {
-    FitRequest r;
-    r.spec = spec, r.sky = sky, r.vis = vis, r.pol = pol, r.lim = lim, r.noise = noise, r.counts = counts, r.index = index, r.fold = fold;
-    r.tmpl = tmpl, r.cov = cov;
-    return r;
 }
 
 int vag_loglike_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int nb, int ndim, double* d_out) {
@@ -5168,7 +4487,7 @@ static int shard_begin(vag_ctx* c, const vag_fit_spec* spec, const double* d_the
     int entry = -1, victim = -1;
     for (int i = 0; i < 4; ++i) {
         const vag_ctx::ShardCosts& e = c->shard_costs[i];
-        if (e.nb == nb_all && e.world == world && e.hash == c->fit_hash) entry = i;
+        if (e.nb == nb_all && e.world == world && e.hash == c->fit.hash) entry = i;
         if (e.in_flight == 0 && (victim < 0 || e.used < c->shard_costs[victim].used)) victim = i;
     }
     int slot = -1;  // a free flight slot, the least recently dealt one
@@ -5184,7 +4503,7 @@ static int shard_begin(vag_ctx* c, const vag_fit_spec* spec, const double* d_the
         entry = victim;
         c->shard_costs[entry].nb = nb_all;
         c->shard_costs[entry].world = world;
-        c->shard_costs[entry].hash = c->fit_hash;
+        c->shard_costs[entry].hash = c->fit.hash;
         c->shard_costs[entry].valid = false;  // until its first call finishes
         if (c->shard_last == entry) c->shard_last = -1;
     }

@@ -1,0 +1,597 @@
+// vag_fit_request.h -- the host side of one likelihood request: the scans that validate the optional spec blocks and lay them out for
+// the device (int32 arrays packed into doubles, transposed whiteners, ...), the request that carries them, and its normalisation.
+// Plain C++17, no device header and no context: a host compiler builds it, and tests/fit_request_check.cpp runs every scan under
+// the host sanitizers.  vag_capi.hip, the one translation unit of the library, includes it and uploads what the scans staged.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "vag_common.h"
+#include "vag_poisson_const.h"
+
+// the calling thread's last error text (vag_last_error); set_err formats it and hands the code back
+static thread_local std::string g_err;
+
+static int set_err(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+// content hash of a spec block (FNV-1a, 64 bit): what decides whether the block is resident already
+static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
+    return h;
+}
+
+// ---- upper-limit rows (vag_loglike_lim_batch): the blocks that hold a limit row, in one device buffer, uploaded like the other spec
+//      blocks when the hash changes.  Layout in doubles: a flux block (the point rows, a band group) of n rows is
+//      [limit | sigma | kind] (n, n, int32 [n] in (n + 1) / 2 doubles), a polarization group's block [kind] alone (its L and sigma are
+//      the group's q and err_q in the pol block).  A block without a limit row is not stored (offset -1): its pass is the pass without
+//      limits.  Rows that are detections hold limit 0 and sigma 1, whatever the caller's arrays hold there. ----
+struct LimLayout {
+    long point = -1;              // offset of the point rows' block in the lim block, or -1
+    std::vector<long> band, pol;  // the same per band group / polarization group
+    bool any = false;             // some limit row exists
+};
+
+static void lim_push_kinds(std::vector<double>& stage, const int32_t* kind, int n) {
+    const size_t at = stage.size();
+    stage.resize(at + ((size_t)n + 1) / 2, 0.0);
+    std::memcpy(stage.data() + at, kind, sizeof(int32_t) * n);
+}
+
+// Checks one flux block of lim (what / g name it in messages) and appends it to stage when it holds a limit row.
+static int lim_flux_block(const vag_limit_rows& r, int n, const char* what, int g, std::vector<double>& stage, long& off, bool& any) {
+    off = -1;
+    if (!r.kind || n <= 0) return VAG_OK;
+    bool here = false;
+    for (int i = 0; i < n; ++i) {
+        if (r.kind[i] != VAG_OBS_DETECTION && r.kind[i] != VAG_OBS_UPPER_LIMIT)
+            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: unknown kind %d", what, g, i, r.kind[i]);
+        if (r.kind[i] != VAG_OBS_UPPER_LIMIT) continue;
+        if (!r.limit || !r.sigma) return set_err(VAG_E_INVALID, "limit rows, %s %d: null limit or sigma array", what, g);
+        if (!std::isfinite(r.limit[i]) || r.limit[i] < 0)
+            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: the limit must be finite and >= 0", what, g, i);
+        if (!std::isfinite(r.sigma[i]) || !(r.sigma[i] > 0))
+            return set_err(VAG_E_INVALID, "limit rows, %s %d, row %d: sigma must be finite and > 0", what, g, i);
+        here = true;
+    }
+    if (!here) return VAG_OK;
+    any = true;
+    off = (long)stage.size();
+    for (int i = 0; i < n; ++i) stage.push_back(r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.limit[i] : 0.0);
+    for (int i = 0; i < n; ++i) stage.push_back(r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.sigma[i] : 1.0);
+    lim_push_kinds(stage, r.kind, n);
+    return VAG_OK;
+}
+
+// Validates lim against its partners and lays its blocks out in stage (host work only: no context is touched).
+static int lim_scan(const vag_fit_spec* spec, const vag_pol_fit_spec* pol, const vag_limit_fit_spec* lim, std::vector<double>& stage,
+                    LimLayout& lay) {
+    const int n_pol = pol ? pol->n_groups : 0;
+    if (lim->n_bands != 0 && lim->n_bands != spec->n_bands)
+        return set_err(VAG_E_INVALID, "limit rows: n_bands must be 0 or the fit spec's %d, got %d", spec->n_bands, lim->n_bands);
+    if (lim->n_pol_groups != 0 && lim->n_pol_groups != n_pol)
+        return set_err(VAG_E_INVALID, "limit rows: n_pol_groups must be 0 or the %d polarization groups, got %d", n_pol, lim->n_pol_groups);
+    if ((lim->n_bands > 0 && !lim->bands) || (lim->n_pol_groups > 0 && !lim->pol_kind))
+        return set_err(VAG_E_INVALID, "limit rows: null band or polarization list");
+    if (lim->point.kind && spec->n_data > 0 && !spec->t) return set_err(VAG_E_INVALID, "limit rows: the fit spec has no point rows");
+    int rc = lim_flux_block(lim->point, spec->n_data, "point rows", 0, stage, lay.point, lay.any);
+    if (rc) return rc;
+    lay.band.assign(std::max(spec->n_bands, 0), -1);
+    for (int g = 0; g < lim->n_bands; ++g) {
+        if (!spec->bands) return set_err(VAG_E_INVALID, "limit rows: the fit spec has no band groups");
+        rc = lim_flux_block(lim->bands[g], spec->bands[g].n, "band group", g, stage, lay.band[g], lay.any);
+        if (rc) return rc;
+    }
+    lay.pol.assign(std::max(n_pol, 0), -1);
+    for (int g = 0; g < lim->n_pol_groups; ++g) {
+        const int32_t* kind = lim->pol_kind[g];
+        if (!kind) continue;
+        if (!pol->groups) return set_err(VAG_E_INVALID, "bad polarization group list");
+        const vag_polarization_obs& o = pol->groups[g];
+        bool here = false;
+        for (int i = 0; i < o.n; ++i) {
+            if (kind[i] != VAG_OBS_DETECTION && kind[i] != VAG_OBS_UPPER_LIMIT)
+                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: unknown kind %d", g, i, kind[i]);
+            if (kind[i] != VAG_OBS_UPPER_LIMIT) continue;
+            if (o.kind != VAG_POL_DEGREE)
+                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: only VAG_POL_DEGREE groups take upper limits", g, i);
+            if (!o.q || !o.err_q) return set_err(VAG_E_INVALID, "polarization group %d: null array", g);
+            if (!std::isfinite(o.q[i]) || o.q[i] < 0 || o.q[i] > 1)
+                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: the limit must lie in [0, 1]", g, i);
+            if (!std::isfinite(o.err_q[i]) || !(o.err_q[i] > 0))
+                return set_err(VAG_E_INVALID, "limit rows, polarization group %d, epoch %d: sigma must be finite and > 0", g, i);
+            here = true;
+        }
+        if (!here) continue;
+        lay.any = true;
+        lay.pol[g] = (long)stage.size();
+        lim_push_kinds(stage, kind, o.n);
+    }
+    return VAG_OK;
+}
+
+// ---- noise groups (vag_loglike_noise_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
+//      in doubles: [sys_fixed 8 | calib 8], then for every pass that holds a grouped row -- the point rows, a band group -- the rows'
+//      group ids (int32 [n] in (n + 1) / 2 doubles).  A pass without a grouped row is not stored (offset -1): it is the pass without
+//      noise groups. ----
+struct NoiseLayout {
+    long point = -1;                    // offset of the point rows' ids in the noise block, or -1
+    std::vector<long> band;             // the same per band group
+    unsigned point_present = 0;         // bit g: some point row is in group g
+    std::vector<unsigned> band_present; // the same per band group
+    int n_groups = 0;
+    bool any = false;                   // some row is grouped
+};
+
+// Validates noise against the fit spec and lays its blocks out in stage (host work only: no context is touched).
+static int noise_scan(const vag_fit_spec* spec, const vag_noise_fit_spec* nz, std::vector<double>& stage, NoiseLayout& lay) {
+    if (nz->n_groups < 0 || nz->n_groups > VAG_NOISE_MAX_GROUPS)
+        return set_err(VAG_E_INVALID, "noise groups: n_groups must be in 0..%d, got %d", VAG_NOISE_MAX_GROUPS, nz->n_groups);
+    if (nz->n_bands != spec->n_bands)
+        return set_err(VAG_E_INVALID, "noise groups: n_bands must be the fit spec's %d, got %d", spec->n_bands, nz->n_bands);
+    if (nz->n_bands > 0 && (!nz->band_group || !spec->bands)) return set_err(VAG_E_INVALID, "noise groups: null band list");
+    for (int g = 0; g < nz->n_groups; ++g) {
+        if (!std::isfinite(nz->sys_fixed[g]) || nz->sys_fixed[g] < 0)
+            return set_err(VAG_E_INVALID, "noise group %d: the systematic must be finite and >= 0", g);
+        if (!std::isfinite(nz->calib[g]) || nz->calib[g] < 0)
+            return set_err(VAG_E_INVALID, "noise group %d: the calibration fraction must be finite and >= 0", g);
+    }
+    lay.n_groups = nz->n_groups;
+    stage.assign(2 * VAG_NOISE_MAX_GROUPS, 0.0);
+    for (int g = 0; g < nz->n_groups; ++g) {
+        stage[g] = nz->sys_fixed[g];
+        stage[VAG_NOISE_MAX_GROUPS + g] = nz->calib[g];
+    }
+    int passes[VAG_NOISE_MAX_GROUPS] = {0};  // in how many passes a group has rows
+    auto push_ids = [&](const int32_t* ids, int32_t same, int n) -> long {
+        const long at = (long)stage.size();
+        stage.resize(at + ((size_t)n + 1) / 2, 0.0);
+        int32_t* dst = reinterpret_cast<int32_t*>(stage.data() + at);
+        for (int i = 0; i < n; ++i) dst[i] = ids ? ids[i] : same;
+        return at;
+    };
+    const int n = spec->n_data;
+    if (nz->point_group && n > 0) {
+        for (int i = 0; i < n; ++i) {
+            const int id = nz->point_group[i];
+            if (id < -1 || id >= nz->n_groups)
+                return set_err(VAG_E_INVALID, "noise groups, point row %d: group %d is outside [-1, %d)", i, id, nz->n_groups);
+            if (id >= 0) lay.point_present |= 1u << id;
+        }
+        if (lay.point_present) {
+            lay.any = true;
+            lay.point = push_ids(nz->point_group, 0, n);
+            for (int g = 0; g < nz->n_groups; ++g) passes[g] += (lay.point_present >> g) & 1u;
+        }
+    }
+    lay.band.assign(std::max(spec->n_bands, 0), -1);
+    lay.band_present.assign(std::max(spec->n_bands, 0), 0u);
+    for (int b = 0; b < nz->n_bands; ++b) {
+        const int id = nz->band_group[b];
+        if (id < -1 || id >= nz->n_groups)
+            return set_err(VAG_E_INVALID, "noise groups, band group %d: group %d is outside [-1, %d)", b, id, nz->n_groups);
+        if (id < 0 || spec->bands[b].n <= 0) continue;
+        lay.any = true;
+        lay.band_present[b] = 1u << id;
+        lay.band[b] = push_ids(nullptr, id, spec->bands[b].n);
+        ++passes[id];
+    }
+    for (int g = 0; g < nz->n_groups; ++g)
+        if (nz->calib[g] > 0 && passes[g] > 1)
+            return set_err(VAG_E_INVALID,
+                           "noise group %d has a calibration fraction and rows in %d passes: such a group must hold point rows only or "
+                           "exactly one band group", g, passes[g]);
+    return VAG_OK;
+}
+
+// ---- additive templates (vag_loglike_tmpl_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
+//      Layout in doubles: [amp_fixed 8], then for every pass with a touched row -- the point rows, a band group -- its values
+//      [n_templates][n].  A pass no template touches is not stored (offset -1): it is the pass without templates. ----
+struct TmplLayout {
+    long point = -1;                    // offset of the point rows' values in the tmpl block, or -1
+    std::vector<long> band;             // the same per band group
+    unsigned point_present = 0;         // bit c: template c touches some point row
+    std::vector<unsigned> band_present; // the same per band group
+    unsigned ext_mask = 0;              // bit c: template c is extinguished
+    int n_templates = 0;
+    bool any = false;                   // some row is touched
+};
+
+// Validates tmpl against the fit spec and lays its blocks out in stage (host work only: no context is touched).
+static int tmpl_scan(const vag_fit_spec* spec, const vag_template_fit_spec* tp, std::vector<double>& stage, TmplLayout& lay) {
+    if (tp->n_templates < 0 || tp->n_templates > VAG_TMPL_MAX)
+        return set_err(VAG_E_INVALID, "templates: n_templates must be in 0..%d, got %d", VAG_TMPL_MAX, tp->n_templates);
+    if (tp->n_bands != 0 && tp->n_bands != spec->n_bands)
+        return set_err(VAG_E_INVALID, "templates: n_bands must be 0 or the fit spec's %d, got %d", spec->n_bands, tp->n_bands);
+    if (tp->n_bands > 0 && (!tp->bands || !spec->bands)) return set_err(VAG_E_INVALID, "templates: null band list");
+    const int nt = tp->n_templates;
+    for (int c = 0; c < nt; ++c) {
+        if (!std::isfinite(tp->amp_fixed[c]) || tp->amp_fixed[c] < 0)
+            return set_err(VAG_E_INVALID, "template %d: the fixed amplitude must be finite and >= 0", c);
+        if (tp->extinguished[c] != 0 && tp->extinguished[c] != 1)
+            return set_err(VAG_E_INVALID, "template %d: extinguished must be 0 or 1, got %d", c, tp->extinguished[c]);
+        lay.ext_mask |= (unsigned)tp->extinguished[c] << c;
+    }
+    lay.n_templates = nt;
+    stage.assign(VAG_TMPL_MAX, 0.0);
+    for (int c = 0; c < nt; ++c) stage[c] = tp->amp_fixed[c];
+    // one pass's block: checked, and stored when some value is not 0
+    auto push = [&](const double* T, int n, const char* what, int b, long& at, unsigned& present) -> int {
+        for (int c = 0; c < nt; ++c)
+            for (int i = 0; i < n; ++i) {
+                const double v = T[(size_t)c * n + i];
+                if (!std::isfinite(v) || v < 0) {
+                    if (b < 0) return set_err(VAG_E_INVALID, "template %d, %s %d: the value must be finite and >= 0", c, what, i);
+                    return set_err(VAG_E_INVALID, "template %d, %s %d, row %d: the value must be finite and >= 0", c, what, b, i);
+                }
+                if (v != 0.0) present |= 1u << c;
+            }
+        if (present) {
+            lay.any = true;
+            at = (long)stage.size();
+            stage.insert(stage.end(), T, T + (size_t)nt * n);
+        }
+        return VAG_OK;
+    };
+    int rc = VAG_OK;
+    if (tp->point && nt > 0 && spec->n_data > 0 && (rc = push(tp->point, spec->n_data, "point row", -1, lay.point, lay.point_present)))
+        return rc;
+    lay.band.assign(std::max(spec->n_bands, 0), -1);
+    lay.band_present.assign(std::max(spec->n_bands, 0), 0u);
+    for (int b = 0; b < tp->n_bands && nt > 0; ++b) {
+        if (!tp->bands[b] || spec->bands[b].n <= 0) continue;
+        if ((rc = push(tp->bands[b], spec->bands[b].n, "band group", b, lay.band[b], lay.band_present[b]))) return rc;
+    }
+    return VAG_OK;
+}
+
+// ---- counts groups (vag_loglike_counts_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
+//      in doubles, per group: [t_sample ns | N n | B n | a n | w n], then the sample indices (int32 [n m] in (n m + 1) / 2 doubles). ----
+struct CountsLayout {
+    std::vector<long> off;       // where group g starts in the counts block
+    std::vector<double> const2;  // -2 sum_i w_i S_i of group g (vag::poisson_const): the walker-independent half of its chi^2
+    int n_groups = 0;
+};
+
+// Validates the counts groups and lays their blocks out in stage (host work only: no context is touched).
+static int counts_scan(const vag_counts_fit_spec* cs, std::vector<double>& stage, CountsLayout& lay) {
+    if (cs->n_groups < 0 || !cs->groups) return set_err(VAG_E_INVALID, "counts groups: n_groups must be >= 0 with a group list, got %d", cs->n_groups);
+    lay.n_groups = cs->n_groups;
+    stage.clear();
+    for (int g = 0; g < cs->n_groups; ++g) {
+        const vag_counts_obs& o = cs->groups[g];
+        if (!(std::isfinite(o.nu_min) && std::isfinite(o.nu_max) && o.nu_min > 0 && o.nu_max > o.nu_min))
+            return set_err(VAG_E_INVALID, "counts group %d: the band needs 0 < nu_min < nu_max, both finite", g);
+        if (o.num_points < 2 || o.num_points > VAG_MAX_NU)
+            return set_err(VAG_E_INVALID, "counts group %d: num_points must be in 2..%d, got %d", g, VAG_MAX_NU, o.num_points);
+        if (o.n < 1) return set_err(VAG_E_INVALID, "counts group %d has no rows", g);
+        if (o.m < 1) return set_err(VAG_E_INVALID, "counts group %d: m (samples per row) must be >= 1, got %d", g, o.m);
+        if (o.n_samples < 1) return set_err(VAG_E_INVALID, "counts group %d has no sample times", g);
+        if (!o.t_sample || !o.sample_idx || !o.counts || !o.background || !o.scale || !o.weight)
+            return set_err(VAG_E_INVALID, "counts group %d: null array", g);
+        for (int j = 0; j < o.n_samples; ++j)
+            if (!std::isfinite(o.t_sample[j]) || !(o.t_sample[j] > 0) || (j > 0 && !(o.t_sample[j] > o.t_sample[j - 1])))
+                return set_err(VAG_E_INVALID, "counts group %d, sample %d: sample times must be finite, > 0 and strictly ascending", g, j);
+        double wS = 0;
+        for (int i = 0; i < o.n; ++i) {
+            const double N = o.counts[i];
+            if (!std::isfinite(N) || N < 0 || N != std::floor(N))
+                return set_err(VAG_E_INVALID, "counts group %d, row %d: counts must be a finite integer >= 0, got %g", g, i, N);
+            if (N > 9007199254740992.0) return set_err(VAG_E_INVALID, "counts group %d, row %d: counts above 2^53", g, i);
+            if (!std::isfinite(o.background[i]) || o.background[i] < 0)
+                return set_err(VAG_E_INVALID, "counts group %d, row %d: the background must be finite and >= 0", g, i);
+            if (!std::isfinite(o.scale[i]) || !(o.scale[i] > 0))
+                return set_err(VAG_E_INVALID, "counts group %d, row %d: the scale must be finite and > 0", g, i);
+            if (!std::isfinite(o.weight[i]) || o.weight[i] < 0)
+                return set_err(VAG_E_INVALID, "counts group %d, row %d: the weight must be finite and >= 0", g, i);
+            for (int k = 0; k < o.m; ++k) {
+                const int j = o.sample_idx[(size_t)i * o.m + k];
+                if (j < 0 || j >= o.n_samples)
+                    return set_err(VAG_E_INVALID, "counts group %d, row %d: sample index %d is outside [0, %d)", g, i, j, o.n_samples);
+            }
+            if (o.weight[i] > 0) wS += o.weight[i] * vag::poisson_const(N);
+        }
+        const size_t at = stage.size(), n = (size_t)o.n, nm = n * (size_t)o.m;
+        lay.off.push_back((long)at);
+        lay.const2.push_back(-2.0 * wS);
+        stage.resize(at + (size_t)o.n_samples + 4 * n + (nm + 1) / 2, 0.0);
+        double* dst = stage.data() + at;
+        std::memcpy(dst, o.t_sample, sizeof(double) * o.n_samples);
+        dst += o.n_samples;
+        for (const double* src : {o.counts, o.background, o.scale, o.weight}) {
+            std::memcpy(dst, src, sizeof(double) * n);
+            dst += n;
+        }
+        std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
+    }
+    return VAG_OK;
+}
+
+// ---- spectral-index groups (vag_loglike_index_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
+//      Layout in doubles, per group: [t n K | nu n K | s n | sigma n | w n | c K]; the first two are the series points (t_i, nu_k), i
+//      outer, as prep_times takes them. ----
+struct IndexLayout {
+    std::vector<long> off;  // where group g starts in the index block
+    int n_groups = 0;
+};
+
+// Validates the spectral-index groups and lays their blocks out in stage (host work only: no context is touched).
+static int index_scan(const vag_index_fit_spec* is, std::vector<double>& stage, IndexLayout& lay) {
+    if (is->n_groups < 0 || !is->groups) return set_err(VAG_E_INVALID, "index groups: n_groups must be >= 0 with a group list, got %d", is->n_groups);
+    lay.n_groups = is->n_groups;
+    lay.off.clear();
+    stage.clear();
+    for (int g = 0; g < is->n_groups; ++g) {
+        const vag_index_obs& o = is->groups[g];
+        if (o.k < 2 || o.k > VAG_INDEX_MAX_NODES)
+            return set_err(VAG_E_INVALID, "index group %d: k (frequencies) must be in 2..%d, got %d", g, VAG_INDEX_MAX_NODES, o.k);
+        if (o.n < 1) return set_err(VAG_E_INVALID, "index group %d has no rows", g);
+        if (o.n > (1 << 24)) return set_err(VAG_E_INVALID, "index group %d: more than %d rows", g, 1 << 24);
+        if (!o.nu || !o.coef || !o.t || !o.value || !o.err || !o.weight) return set_err(VAG_E_INVALID, "index group %d: null array", g);
+        for (int k = 0; k < o.k; ++k) {
+            if (!std::isfinite(o.nu[k]) || !(o.nu[k] > 0) || (k > 0 && !(o.nu[k] > o.nu[k - 1])))
+                return set_err(VAG_E_INVALID, "index group %d, frequency %d: frequencies must be finite, > 0 and strictly ascending", g, k);
+            if (!std::isfinite(o.coef[k])) return set_err(VAG_E_INVALID, "index group %d, coefficient %d is not finite", g, k);
+        }
+        if (!std::isfinite(o.ext_slope)) return set_err(VAG_E_INVALID, "index group %d: ext_slope is not finite", g);
+        for (int i = 0; i < o.n; ++i) {
+            if (!std::isfinite(o.t[i]) || !(o.t[i] > 0) || (i > 0 && o.t[i] < o.t[i - 1]))
+                return set_err(VAG_E_INVALID, "index group %d, row %d: times must be finite, > 0 and ascending", g, i);
+            if (!std::isfinite(o.value[i])) return set_err(VAG_E_INVALID, "index group %d, row %d: the index is not finite", g, i);
+            if (!std::isfinite(o.err[i]) || !(o.err[i] > 0))
+                return set_err(VAG_E_INVALID, "index group %d, row %d: the error must be finite and > 0", g, i);
+            if (!std::isfinite(o.weight[i]) || o.weight[i] < 0)
+                return set_err(VAG_E_INVALID, "index group %d, row %d: the weight must be finite and >= 0", g, i);
+        }
+        const size_t at = stage.size(), n = (size_t)o.n, K = (size_t)o.k;
+        lay.off.push_back((long)at);
+        stage.resize(at + 2 * n * K + 3 * n + K, 0.0);
+        double* dst = stage.data() + at;
+        for (size_t i = 0; i < n; ++i)
+            for (size_t k = 0; k < K; ++k) {
+                dst[i * K + k] = o.t[i];
+                dst[n * K + i * K + k] = o.nu[k];
+            }
+        dst += 2 * n * K;
+        for (const double* src : {o.value, o.err, o.weight}) {
+            std::memcpy(dst, src, sizeof(double) * n);
+            dst += n;
+        }
+        std::memcpy(dst, o.coef, sizeof(double) * K);
+    }
+    return VAG_OK;
+}
+
+// ---- fold groups (vag_loglike_fold_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout in
+//      doubles, per group: [t ns J | nu ns J | A J C | sigma J | exposure / m n | N n C | B n C | w n C], then the sample indices
+//      (int32 [n m] in (n m + 1) / 2 doubles); the first two are the series points (t_sample_s, nu_j), s outer, as prep_times takes
+//      them; sigma is zeros for a group without one (the kernel is handed a null pointer then). ----
+struct FoldLayout {
+    std::vector<long> off;       // where group g starts in the fold block
+    std::vector<double> const2;  // -2 sum_{i,c} w S of group g (vag::poisson_const): the walker-independent half of its chi^2
+    bool any_sigma = false;      // some group carries a cross-section: N_H is read
+    int n_groups = 0;
+};
+
+// Validates the fold groups and lays their blocks out in stage (host work only: no context is touched).
+static int fold_scan(const vag_fit_spec* spec, const vag_fold_fit_spec* fs, std::vector<double>& stage, FoldLayout& lay) {
+    if (fs->n_groups < 0 || !fs->groups) return set_err(VAG_E_INVALID, "fold groups: n_groups must be >= 0 with a group list, got %d", fs->n_groups);
+    if (!std::isfinite(fs->n_h_fixed) || fs->n_h_fixed < 0) return set_err(VAG_E_INVALID, "fold groups: n_h_fixed must be finite and >= 0");
+    lay.n_groups = fs->n_groups;
+    lay.off.clear();
+    lay.const2.clear();
+    lay.any_sigma = false;
+    stage.clear();
+    for (int g = 0; g < fs->n_groups; ++g) {
+        const vag_fold_obs& o = fs->groups[g];
+        if (o.J < 1 || o.J > VAG_FOLD_MAX_BINS)
+            return set_err(VAG_E_INVALID, "fold group %d: J (energy bins) must be in 1..%d, got %d", g, VAG_FOLD_MAX_BINS, o.J);
+        if (o.C < 1 || o.C > VAG_FOLD_MAX_CHANNELS)
+            return set_err(VAG_E_INVALID, "fold group %d: C (channels) must be in 1..%d, got %d", g, VAG_FOLD_MAX_CHANNELS, o.C);
+        if (o.n < 1) return set_err(VAG_E_INVALID, "fold group %d has no rows", g);
+        if (o.m < 1) return set_err(VAG_E_INVALID, "fold group %d: m (samples per row) must be >= 1, got %d", g, o.m);
+        if (o.n_samples < 1) return set_err(VAG_E_INVALID, "fold group %d has no sample times", g);
+        if (o.n > (1 << 16) || o.m > (1 << 10) || o.n_samples > (1 << 18))
+            return set_err(VAG_E_INVALID, "fold group %d: more than %d rows, %d samples per row or %d sample times", g, 1 << 16, 1 << 10, 1 << 18);
+        if (!o.nu || !o.A || !o.t_sample || !o.sample_idx || !o.exposure_over_m || !o.counts || !o.background || !o.weight)
+            return set_err(VAG_E_INVALID, "fold group %d: null array", g);
+        for (int j = 0; j < o.J; ++j) {
+            if (!std::isfinite(o.nu[j]) || !(o.nu[j] > 0) || (j > 0 && !(o.nu[j] > o.nu[j - 1])))
+                return set_err(VAG_E_INVALID, "fold group %d, bin %d: frequencies must be finite, > 0 and strictly ascending", g, j);
+            if (o.sigma && (!std::isfinite(o.sigma[j]) || o.sigma[j] < 0))
+                return set_err(VAG_E_INVALID, "fold group %d, bin %d: the cross-section must be finite and >= 0", g, j);
+            for (int ch = 0; ch < o.C; ++ch) {
+                const double a = o.A[(size_t)j * o.C + ch];
+                if (!std::isfinite(a) || a < 0)
+                    return set_err(VAG_E_INVALID, "fold group %d, bin %d, channel %d: the response must be finite and >= 0", g, j, ch);
+            }
+        }
+        for (int j = 0; j < o.n_samples; ++j)
+            if (!std::isfinite(o.t_sample[j]) || !(o.t_sample[j] > 0) || (j > 0 && !(o.t_sample[j] > o.t_sample[j - 1])))
+                return set_err(VAG_E_INVALID, "fold group %d, sample %d: sample times must be finite, > 0 and strictly ascending", g, j);
+        double wS = 0;
+        for (int i = 0; i < o.n; ++i) {
+            if (!std::isfinite(o.exposure_over_m[i]) || !(o.exposure_over_m[i] > 0))
+                return set_err(VAG_E_INVALID, "fold group %d, row %d: exposure_over_m must be finite and > 0", g, i);
+            for (int k = 0; k < o.m; ++k) {
+                const int j = o.sample_idx[(size_t)i * o.m + k];
+                if (j < 0 || j >= o.n_samples)
+                    return set_err(VAG_E_INVALID, "fold group %d, row %d: sample index %d is outside [0, %d)", g, i, j, o.n_samples);
+            }
+            for (int ch = 0; ch < o.C; ++ch) {
+                const size_t at = (size_t)i * o.C + ch;
+                const double N = o.counts[at];
+                if (!std::isfinite(N) || N < 0 || N != std::floor(N))
+                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: counts must be a finite integer >= 0, got %g", g, i, ch, N);
+                if (N > 9007199254740992.0) return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: counts above 2^53", g, i, ch);
+                if (!std::isfinite(o.background[at]) || o.background[at] < 0)
+                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: the background must be finite and >= 0", g, i, ch);
+                if (!std::isfinite(o.weight[at]) || o.weight[at] < 0)
+                    return set_err(VAG_E_INVALID, "fold group %d, row %d, channel %d: the weight must be finite and >= 0", g, i, ch);
+                if (o.weight[at] > 0) wS += o.weight[at] * vag::poisson_const(N);
+            }
+        }
+        if (o.sigma) lay.any_sigma = true;
+        const size_t at = stage.size(), J = (size_t)o.J, C = (size_t)o.C, n = (size_t)o.n, ns = (size_t)o.n_samples, nm = n * (size_t)o.m;
+        lay.off.push_back((long)at);
+        lay.const2.push_back(-2.0 * wS);
+        stage.resize(at + 2 * ns * J + J * C + J + n + 3 * n * C + (nm + 1) / 2, 0.0);
+        double* dst = stage.data() + at;
+        for (size_t q = 0; q < ns; ++q)
+            for (size_t j = 0; j < J; ++j) {
+                dst[q * J + j] = o.t_sample[q];
+                dst[ns * J + q * J + j] = o.nu[j];
+            }
+        dst += 2 * ns * J;
+        std::memcpy(dst, o.A, sizeof(double) * J * C);
+        dst += J * C;
+        if (o.sigma) std::memcpy(dst, o.sigma, sizeof(double) * J);
+        dst += J;
+        std::memcpy(dst, o.exposure_over_m, sizeof(double) * n);
+        dst += n;
+        for (const double* src : {o.counts, o.background, o.weight}) {
+            std::memcpy(dst, src, sizeof(double) * n * C);
+            dst += n * C;
+        }
+        std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
+    }
+    // (N_H is read by groups with a cross-section only: without one it is refused as a free parameter, the rule of east0 / north0)
+    if (!lay.any_sigma)
+        for (int d = 0; d < spec->ndim && d < 16; ++d)
+            if (spec->slot[d] == VAG_P_N_H) return set_err(VAG_E_INVALID, "bad parameter slot");
+    return VAG_OK;
+}
+
+// ---- correlated groups (vag_loglike_cov_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
+//      in doubles, per group: [t n | nu n | ln_flux n | ext n | Wt n n]; the first two are the series points as prep_times takes
+//      them; ext is zeros for a group without one (the kernel is handed a null pointer then); Wt[j n + i] = W_ij for j <= i, else 0:
+//      the whitener transposed, so that a wavefront whose lanes hold consecutive rows i loads consecutive doubles. ----
+struct CovLayout {
+    std::vector<long> off;  // where group g starts in the cov block
+    int n_groups = 0;
+};
+
+// Validates the correlated groups and lays their blocks out in stage (host work only: no context is touched).
+static int cov_scan(const vag_cov_fit_spec* cs, std::vector<double>& stage, CovLayout& lay) {
+    if (cs->n_groups < 0 || cs->n_groups > VAG_COV_MAX_GROUPS)
+        return set_err(VAG_E_INVALID, "correlated groups: n_groups must be in 0..%d, got %d", VAG_COV_MAX_GROUPS, cs->n_groups);
+    if (!cs->groups) return set_err(VAG_E_INVALID, "correlated groups: null group list");
+    lay.n_groups = cs->n_groups;
+    lay.off.clear();
+    stage.clear();
+    for (int g = 0; g < cs->n_groups; ++g) {
+        const vag_cov_obs& o = cs->groups[g];
+        if (o.n < 1 || o.n > VAG_COV_MAX_ROWS)
+            return set_err(VAG_E_INVALID, "correlated group %d: n (rows) must be in 1..%d, got %d", g, VAG_COV_MAX_ROWS, o.n);
+        if (!o.t || !o.nu || !o.ln_flux || !o.whitener) return set_err(VAG_E_INVALID, "correlated group %d: null array", g);
+        if (!std::isfinite(o.weight) || o.weight < 0)
+            return set_err(VAG_E_INVALID, "correlated group %d: the weight must be finite and >= 0", g);
+        const size_t n = (size_t)o.n;
+        for (int i = 0; i < o.n; ++i) {
+            if (!std::isfinite(o.t[i]) || !(o.t[i] > 0) || (i > 0 && o.t[i] < o.t[i - 1]))
+                return set_err(VAG_E_INVALID, "correlated group %d, row %d: times must be finite, > 0 and ascending", g, i);
+            if (!std::isfinite(o.nu[i]) || !(o.nu[i] > 0))
+                return set_err(VAG_E_INVALID, "correlated group %d, row %d: the frequency must be finite and > 0", g, i);
+            if (!std::isfinite(o.ln_flux[i])) return set_err(VAG_E_INVALID, "correlated group %d, row %d: ln_flux is not finite", g, i);
+            if (o.ext && !std::isfinite(o.ext[i])) return set_err(VAG_E_INVALID, "correlated group %d, row %d: ext is not finite", g, i);
+            for (int j = 0; j <= i; ++j)
+                if (!std::isfinite(o.whitener[i * n + j]))
+                    return set_err(VAG_E_INVALID, "correlated group %d, row %d: whitener entry %d is not finite", g, i, j);
+            if (!(o.whitener[i * n + i] > 0))
+                return set_err(VAG_E_INVALID, "correlated group %d, row %d: the whitener's diagonal entry must be > 0", g, i);
+        }
+        const size_t at = stage.size();
+        lay.off.push_back((long)at);
+        stage.resize(at + 4 * n + n * n, 0.0);
+        double* dst = stage.data() + at;
+        std::memcpy(dst, o.t, sizeof(double) * n);
+        std::memcpy(dst + n, o.nu, sizeof(double) * n);
+        std::memcpy(dst + 2 * n, o.ln_flux, sizeof(double) * n);
+        if (o.ext) std::memcpy(dst + 3 * n, o.ext, sizeof(double) * n);
+        double* Wt = dst + 4 * n;
+        for (size_t i = 0; i < n; ++i)
+            for (size_t j = 0; j <= i; ++j) Wt[j * n + i] = o.whitener[i * n + j];
+    }
+    return VAG_OK;
+}
+
+// ---- one likelihood request.  Every vag_loglike_*_batch entry point fills a FitRequest from its arguments (a spec it does not take
+//      stays null) and calls loglike_dev or loglike_host; a request whose optional blocks are null or empty is therefore the narrower
+//      entry point's request, statement for statement. ----
+namespace {
+struct FitRequest {
+    const vag_fit_spec* spec = nullptr;
+    const vag_sky_fit_spec* sky = nullptr;      // after fit_request_prepare: null when nothing reads the placement
+    const vag_vis_fit_spec* vis = nullptr;      // after fit_request_prepare: null when it has no group; so pol, counts, index, fold
+    const vag_pol_fit_spec* pol = nullptr;
+    const vag_limit_fit_spec* lim = nullptr;    // after fit_request_prepare: null when no row is a limit (llay.any)
+    const vag_noise_fit_spec* noise = nullptr;  // after fit_request_prepare: null when no row is grouped (nlay.any)
+    const vag_counts_fit_spec* counts = nullptr;
+    const vag_index_fit_spec* index = nullptr;
+    const vag_fold_fit_spec* fold = nullptr;
+    const vag_template_fit_spec* tmpl = nullptr;  // after fit_request_prepare: null when no row is touched (tlay.any)
+    const vag_cov_fit_spec* cov = nullptr;        // after fit_request_prepare: null when it has no group
+    LimLayout llay;
+    NoiseLayout nlay;
+    CountsLayout clay;
+    IndexLayout ilay;
+    FoldLayout flay;
+    TmplLayout tlay;
+    CovLayout vlay;
+    std::vector<double> lstage, nstage, cstage, istage, fstage, tstage, vstage;  // what the scans lay out: one resident block each
+    bool placed = false;                                 // some group reads east0 / north0
+    bool prepared = false;                               // fit_request_prepare has run
+};
+}  // namespace
+
+// Normalises the request and scans its host-side blocks, once per call (host work only: no context is touched).  spec is not null.
+static int fit_request_prepare(FitRequest& r) {
+    if (r.prepared) return VAG_OK;
+    if (r.vis && r.vis->n_groups == 0) r.vis = nullptr;
+    if (r.counts && r.counts->n_groups == 0) r.counts = nullptr;
+    if (r.index && r.index->n_groups == 0) r.index = nullptr;
+    if (r.fold && r.fold->n_groups == 0) r.fold = nullptr;
+    if (r.cov && r.cov->n_groups == 0) r.cov = nullptr;
+    int rc = VAG_OK;
+    if (r.cov && (rc = cov_scan(r.cov, r.vstage, r.vlay))) return rc;
+    if (r.tmpl && (rc = tmpl_scan(r.spec, r.tmpl, r.tstage, r.tlay))) return rc;
+    if (r.fold && (rc = fold_scan(r.spec, r.fold, r.fstage, r.flay))) return rc;
+    if (r.index && (rc = index_scan(r.index, r.istage, r.ilay))) return rc;
+    if (r.counts && (rc = counts_scan(r.counts, r.cstage, r.clay))) return rc;
+    if (r.noise && (rc = noise_scan(r.spec, r.noise, r.nstage, r.nlay))) return rc;
+    if (r.lim && (rc = lim_scan(r.spec, r.pol, r.lim, r.lstage, r.llay))) return rc;  // (pol as given: an empty list checks n_pol_groups)
+    if (!r.nlay.any) r.noise = nullptr;
+    if (!r.llay.any) r.lim = nullptr;
+    if (!r.tlay.any) r.tmpl = nullptr;  // (tlay.n_templates stays: the amplitude slots of the spec's templates are accepted)
+    if (r.pol && r.pol->n_groups == 0) r.pol = nullptr;
+    r.placed = (r.sky && r.sky->n_groups > 0) || r.vis;
+    // (east0 / north0 place centroid and visibility groups only: without such a group they are refused as free parameters)
+    if (!r.pol && !r.placed) r.sky = nullptr;  // nothing reads the placement
+    r.prepared = true;
+    return VAG_OK;
+}
+
+static FitRequest fit_request(const vag_fit_spec* spec, const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
+                              const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr,
+                              const vag_noise_fit_spec* noise = nullptr, const vag_counts_fit_spec* counts = nullptr,
+                              const vag_index_fit_spec* index = nullptr, const vag_fold_fit_spec* fold = nullptr,
+                              const vag_template_fit_spec* tmpl = nullptr, const vag_cov_fit_spec* cov = nullptr) {
+    FitRequest r;
+    r.spec = spec, r.sky = sky, r.vis = vis, r.pol = pol, r.lim = lim, r.noise = noise, r.counts = counts, r.index = index, r.fold = fold;
+    r.tmpl = tmpl, r.cov = cov;
+    return r;
+}

@@ -15,26 +15,42 @@ import torch
 import torch.distributed as dist
 
 
-_NO_CENTROIDS = ("sharded likelihood calls do not support centroid data (Fitter.add_centroid): evaluate on one device "
-                 "(Fitter.device_evaluator / log_prob_batch)")
-_NO_VISIBILITIES = ("sharded likelihood calls do not support visibility data (Fitter.add_visibilities): evaluate on one "
-                    "device (Fitter.device_evaluator / log_prob_batch)")
-_NO_POLARIZATION = ("sharded likelihood calls do not support polarization data (Fitter.add_polarization): evaluate on one "
-                    "device (Fitter.device_evaluator / log_prob_batch)")
-_NO_LIMITS = ("sharded likelihood calls do not support upper limits (upper_limit=... of Fitter.add_flux_density / add_spectrum / "
-              "add_flux / add_polarization): evaluate on one device (Fitter.device_evaluator / log_prob_batch)")
-_NO_NOISE = ("sharded likelihood calls do not support noise groups (noise=... of Fitter.add_flux_density / add_spectrum / "
-             "add_flux): evaluate on one device (Fitter.device_evaluator / log_prob_batch)")
-_NO_COUNTS = ("sharded likelihood calls do not support photon counts (Fitter.add_counts): evaluate on one device "
-              "(Fitter.device_evaluator / log_prob_batch)")
-_NO_INDEX = ("sharded likelihood calls do not support spectral indices (Fitter.add_spectral_index): evaluate on one device "
-             "(Fitter.device_evaluator / log_prob_batch)")
-_NO_FOLD = ("sharded likelihood calls do not support count spectra (Fitter.add_count_spectrum): evaluate on one device "
-            "(Fitter.device_evaluator / log_prob_batch)")
-_NO_TEMPLATES = ("sharded likelihood calls do not support additive templates (templates=... of Fitter.add_flux_density / add_spectrum / "
-                 "add_flux): evaluate on one device (Fitter.device_evaluator / log_prob_batch)")
-_NO_CORRELATED = ("sharded likelihood calls do not support correlated groups (Fitter.add_correlated): evaluate on one device "
-                  "(Fitter.device_evaluator / log_prob_batch)")
+def _no(what):
+    return f"sharded likelihood calls do not support {what}: evaluate on one device (Fitter.device_evaluator / log_prob_batch)"
+
+
+_NO_CENTROIDS = _no("centroid data (Fitter.add_centroid)")
+_NO_VISIBILITIES = _no("visibility data (Fitter.add_visibilities)")
+_NO_POLARIZATION = _no("polarization data (Fitter.add_polarization)")
+_NO_LIMITS = _no("upper limits (upper_limit=... of Fitter.add_flux_density / add_spectrum / add_flux / add_polarization)")
+_NO_NOISE = _no("noise groups (noise=... of Fitter.add_flux_density / add_spectrum / add_flux)")
+_NO_COUNTS = _no("photon counts (Fitter.add_counts)")
+_NO_INDEX = _no("spectral indices (Fitter.add_spectral_index)")
+_NO_FOLD = _no("count spectra (Fitter.add_count_spectrum)")
+_NO_TEMPLATES = _no("additive templates (templates=... of Fitter.add_flux_density / add_spectrum / add_flux)")
+_NO_CORRELATED = _no("correlated groups (Fitter.add_correlated)")
+
+# The optional data kinds of a fit, in the order of the engine's entry points: the attribute of the fit spec that holds the kind's
+# block (None: the fit has none), the has_* name of Fitter and of its device evaluator, and why a sharded call refuses the kind.
+DATA_KINDS = (
+    ("_sky", "has_centroids", _NO_CENTROIDS),
+    ("_vis", "has_visibilities", _NO_VISIBILITIES),
+    ("_pol", "has_polarization", _NO_POLARIZATION),
+    ("_lim", "has_limits", _NO_LIMITS),
+    ("_noise", "has_noise_groups", _NO_NOISE),
+    ("_counts", "has_counts", _NO_COUNTS),
+    ("_index", "has_spectral_indices", _NO_INDEX),
+    ("_fold", "has_count_spectra", _NO_FOLD),
+    ("_tmpl", "has_templates", _NO_TEMPLATES),
+    ("_cov", "has_correlated", _NO_CORRELATED),
+)
+
+
+def _refuse_data_kinds(obj):
+    """Raises for the first data kind, in table order, that obj (an evaluator, a Fitter, or None) says it has."""
+    for _, has, why in DATA_KINDS:
+        if getattr(obj, has, False):
+            raise NotImplementedError(why)
 
 
 def shard_range(n, rank, world):
@@ -103,26 +119,7 @@ class WalkerSharder:
     """
 
     def __init__(self, eval_dev, group=None, device=None):
-        if getattr(eval_dev, "has_centroids", False):
-            raise NotImplementedError(_NO_CENTROIDS)
-        if getattr(eval_dev, "has_visibilities", False):
-            raise NotImplementedError(_NO_VISIBILITIES)
-        if getattr(eval_dev, "has_polarization", False):
-            raise NotImplementedError(_NO_POLARIZATION)
-        if getattr(eval_dev, "has_limits", False):
-            raise NotImplementedError(_NO_LIMITS)
-        if getattr(eval_dev, "has_noise_groups", False):
-            raise NotImplementedError(_NO_NOISE)
-        if getattr(eval_dev, "has_counts", False):
-            raise NotImplementedError(_NO_COUNTS)
-        if getattr(eval_dev, "has_spectral_indices", False):
-            raise NotImplementedError(_NO_INDEX)
-        if getattr(eval_dev, "has_count_spectra", False):
-            raise NotImplementedError(_NO_FOLD)
-        if getattr(eval_dev, "has_templates", False):
-            raise NotImplementedError(_NO_TEMPLATES)
-        if getattr(eval_dev, "has_correlated", False):
-            raise NotImplementedError(_NO_CORRELATED)
+        _refuse_data_kinds(eval_dev)
         self.eval_dev, self.group = eval_dev, group
         self.device = device if device is not None else _default_device(group)
         self.native = getattr(eval_dev, "native", None)
@@ -217,26 +214,7 @@ def sharded_loglike(samples, local_eval, group=None, device=None):
     same `samples` and gets the full [nb] vector back.  Kept for callers that hold numpy arrays; the device-resident,
     cost-balanced path is ``WalkerSharder``.
     """
-    if getattr(getattr(local_eval, "__self__", None), "has_centroids", False):
-        raise NotImplementedError(_NO_CENTROIDS)
-    if getattr(getattr(local_eval, "__self__", None), "has_visibilities", False):
-        raise NotImplementedError(_NO_VISIBILITIES)
-    if getattr(getattr(local_eval, "__self__", None), "has_polarization", False):
-        raise NotImplementedError(_NO_POLARIZATION)
-    if getattr(getattr(local_eval, "__self__", None), "has_limits", False):
-        raise NotImplementedError(_NO_LIMITS)
-    if getattr(getattr(local_eval, "__self__", None), "has_noise_groups", False):
-        raise NotImplementedError(_NO_NOISE)
-    if getattr(getattr(local_eval, "__self__", None), "has_counts", False):
-        raise NotImplementedError(_NO_COUNTS)
-    if getattr(getattr(local_eval, "__self__", None), "has_spectral_indices", False):
-        raise NotImplementedError(_NO_INDEX)
-    if getattr(getattr(local_eval, "__self__", None), "has_count_spectra", False):
-        raise NotImplementedError(_NO_FOLD)
-    if getattr(getattr(local_eval, "__self__", None), "has_templates", False):
-        raise NotImplementedError(_NO_TEMPLATES)
-    if getattr(getattr(local_eval, "__self__", None), "has_correlated", False):
-        raise NotImplementedError(_NO_CORRELATED)
+    _refuse_data_kinds(getattr(local_eval, "__self__", None))
     samples = np.ascontiguousarray(samples, dtype=np.float64)
     nb = samples.shape[0]
     if not (dist.is_available() and dist.is_initialized()):

@@ -1846,16 +1846,10 @@ class Fitter:
             _on_current_stream(run)
             return values, costs
         eval_dev.optional_costs = True
-        eval_dev.has_centroids = spec._sky is not None and spec._sky.n_groups > 0
-        eval_dev.has_visibilities = spec._vis is not None
-        eval_dev.has_polarization = spec._pol is not None
-        eval_dev.has_limits = spec._lim is not None
-        eval_dev.has_noise_groups = spec._noise is not None
-        eval_dev.has_counts = spec._counts is not None
-        eval_dev.has_spectral_indices = spec._index is not None
-        eval_dev.has_count_spectra = spec._fold is not None
-        eval_dev.has_templates = spec._tmpl is not None
-        eval_dev.has_correlated = spec._cov is not None
+        from .dist import DATA_KINDS
+        for attr, has, _ in DATA_KINDS:
+            setattr(eval_dev, has, getattr(spec, attr) is not None)
+        eval_dev.has_centroids = eval_dev.has_centroids and spec._sky.n_groups > 0  # (n_groups = 0: the fixed placement alone)
 
         class _Native:
             """The engine's own sharded call for dist.WalkerSharder: deal + this rank's block, then the scatter after the
@@ -1866,36 +1860,9 @@ class Fitter:
             @staticmethod
             def shard(theta_all, nb, rank, world, block):
                 """Returns the ticket that names this call in flight; finish() takes it (ABI v13)."""
-                if keep[0]._cov is not None:
-                    from .dist import _NO_CORRELATED
-                    raise NotImplementedError(_NO_CORRELATED)
-                if keep[0]._tmpl is not None:
-                    from .dist import _NO_TEMPLATES
-                    raise NotImplementedError(_NO_TEMPLATES)
-                if keep[0]._fold is not None:
-                    from .dist import _NO_FOLD
-                    raise NotImplementedError(_NO_FOLD)
-                if keep[0]._index is not None:
-                    from .dist import _NO_INDEX
-                    raise NotImplementedError(_NO_INDEX)
-                if keep[0]._counts is not None:
-                    from .dist import _NO_COUNTS
-                    raise NotImplementedError(_NO_COUNTS)
-                if keep[0]._noise is not None:
-                    from .dist import _NO_NOISE
-                    raise NotImplementedError(_NO_NOISE)
-                if keep[0]._lim is not None:
-                    from .dist import _NO_LIMITS
-                    raise NotImplementedError(_NO_LIMITS)
-                if keep[0]._pol is not None:
-                    from .dist import _NO_POLARIZATION
-                    raise NotImplementedError(_NO_POLARIZATION)
-                if keep[0]._vis is not None:
-                    from .dist import _NO_VISIBILITIES
-                    raise NotImplementedError(_NO_VISIBILITIES)
-                if keep[0]._sky is not None:
-                    from .dist import _NO_CENTROIDS
-                    raise NotImplementedError(_NO_CENTROIDS)
+                for attr, _, why in reversed(DATA_KINDS):
+                    if getattr(keep[0], attr) is not None:
+                        raise NotImplementedError(why)
                 ticket = C.c_uint64(0)
                 _on_current_stream(lambda: _lib.check(lib.vag_loglike_shard_begin_dev(
                     h, C.byref(keep[0]), theta_all.data_ptr(), nb, keep[0].ndim, rank, world, block.data_ptr(), C.byref(ticket))))
