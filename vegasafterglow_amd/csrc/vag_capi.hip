@@ -31,6 +31,7 @@
 #include "vag_index.h"
 #include "vag_fit_kernels.h"
 #include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
+#include "vag_flux_plan.h"    // (host only: the launch decisions of the flux stage)
 
 using namespace vag;
 
@@ -359,8 +360,10 @@ static double append_log2_table(std::vector<double>& tab) {
     return maxerr;
 }
 
-struct SeriesOcc {
-    int waves;
+// one answer of the occupancy query: resident workgroups per CU of a kernel at a block size and dynamic LDS (-1: the query failed)
+struct Occupancy {
+    const void* fn;
+    int threads;
     size_t lds;
     int wg;
 };
@@ -419,13 +422,7 @@ struct vag_ctx {
     int grid_large = 0;       // layout level of the grid kernel in use: 1 / 2 after a recent batch needed more than the small / large layout holds
     int grid_large_idle = 0;  // consecutive batches that would have fitted the small one
     DevBuf d_gridscratch;     // level 2: the grid kernel's scratch arrays, one GridSharedHuge per model
-    std::vector<SeriesOcc> series_occ;  // occupancy-query results of series launches seen so far
-    struct FluxOcc {
-        const void* fn;
-        size_t lds;
-        int wg;
-    };
-    std::vector<FluxOcc> flux_occ;  // ... and of persistent vag_flux_grid_kernel launches
+    std::vector<Occupancy> occ;     // occupancy-query results of the flux launches seen so far (wg_per_cu)
     DevBuf d_flux_order;            // [nb] deal order of a persistent vag_flux_grid_kernel launch (vag_flux_order_kernel)
     DevBuf d_partial2, d_ssc2;  // fused synchrotron + SSC flux pass: second partial-grid buffer / second scratch output
     DevBuf d_bandidx;  // [512 band index per point | 8 first point of each band] for the shared-node / row-per-lane series paths
@@ -450,7 +447,7 @@ struct vag_ctx {
     // flux passes always read d_shock, d_cellpar, ...; select_emitter() swaps the reverse shock's buffers in and out.
     DevBuf d_shock_r, d_cellpar_r, d_celldet_r, d_icy_r, d_cellq_r, d_params_rvs, d_inj, d_comp;
     DevBuf d_fail;     // int[16], reset per batch by the grid kernel: ODE rows per status ([1] step underflow, [2] step cap, [3] stalled); three 64-bit tallies at
-                       // [8..13] (vag_ctx_count_work: right-hand sides, live lanes over the attempts, lane slots of the attempts); [14] the row queue of the refill kernel
+                       // [8..13] (vag_ctx_count_work: right-hand sides, live lanes over the attempts, lane slots of the attempts).  (The row queue of the refill kernel is not here: it lives in d_dynrec.)
     DevBuf d_dynrec;   // [rows][DYN_ROWREC] start records of vag_dynamics_refill_kernel (vag_dyn_prep_kernel)
     int dyn_refill_wg_per_cu = 0;  // resident wavefronts of that kernel per CU (occupancy query, once)
     DevBuf d_cellgeo;  // spreading jets (VAG_FLAG_SPREADING): per-cell cos/sin(theta), log2|dcos|, shared by both shocks
@@ -860,7 +857,6 @@ int vag_ctx_synchronize(vag_ctx* c) {
     return VAG_OK;
 }
 
-static int collect_times_fwd(vag_ctx* c);
 int vag_ctx_profile(vag_ctx* c, int enable) {
     ApiLock api_lock(c);
     if (!c) return set_err(VAG_E_INVALID, "null context");
@@ -886,15 +882,6 @@ int vag_last_profile(vag_ctx* c, vag_profile* out) {
     *out = vag_profile{acc[PS_DYNAMICS], 0.0, acc[PS_SYN_ELECTRONS], acc[PS_SYN_PHOTONS], acc[PS_COOLING], acc[PS_SYNC_FLUX],
                        acc[PS_IC_PHOTONS], acc[PS_SSC_FLUX], (double)last};
     return VAG_OK;
-}
-
-int vag_last_stage_times(vag_ctx* c, vag_stage_times* out) {
-    ApiLock api_lock(c);
-    if (!c || !out) return set_err(VAG_E_INVALID, "null context or output");
-    // measured with HIP events recorded on the context stream around each kernel of the last batch call
-    const int rc = collect_times_fwd(c);
-    *out = c->times;
-    return rc;
 }
 
 }  // extern "C"
@@ -1258,34 +1245,61 @@ int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool 
     return VAG_OK;
 }
 
-int choose_pairs_per_block(const vag_ctx* c) {
-    if (const char* e = vag_hook("VAG_PAIRS_PER_BLOCK")) {  // tuning/debug override
-        const int v = std::atoi(e);
-        if (v > 0) return std::min(v, std::max(1, c->max_pairs));
-    }
-    // a pinned value (a counts pass of the likelihood): the partial sums of a model are then cut at the same pairs in every batch -- a
-    // model with fewer pairs than the value is one workgroup either way.  With run_flux_grid keeping such a request off the
-    // row-per-lane kernel, this is what makes the flux independent of the rest of the batch; the other launch choices the batch
-    // decides -- 256 or 512 lanes, the persistent form -- do not change the sums (tests/test_counts.py holds them to the bits), and
-    // the piece loop of lattices longer than the staged row (max_k > 512) is outside the guarantee
-    if (c->ppb_pin > 0) return std::min(c->ppb_pin, std::max(1, c->max_pairs));
-    // enough workgroups to fill 256 CUs several times over, but not so many that staging the photon rows
-    // and the partial grids dominate
-    long long ppb = (c->total_pairs + 16383) / 16384;
-    long long lo = 4;
-    if (c->total_pairs / 16 >= 2048) lo = 16;
-    if (c->total_pairs / 64 >= 4096) lo = 64;
-    ppb = std::max(ppb, lo);
-    ppb = std::min<long long>(ppb, std::max(1, c->max_pairs));
-    return (int)std::max<long long>(1, ppb);
+// ---- the flux launch layer.  What is launched is decided in vag_flux_plan.h (host arithmetic, tested on the CPU); here are the
+//      inputs of those decisions, one selector per kernel family that maps a variant to its kernel, and the launches ----
+
+static FluxBatch flux_batch(const vag_ctx* c, int nb) {  // (FluxBatch's members in their order)
+    return {nb,        c->n_rows,     c->max_k,   c->max_pairs, c->total_pairs,
+            c->n_cus,  c->count_work, c->ppb_pin, (c->batch_flags & VAG_FLAG_SPREADING) != 0};
 }
 
-// Lattice nodes the flux kernels stage at a time (their LDS scales with it).  Longer lattices are taken in overlapping pieces
-// inside the kernels; VAG_FLUX_K_CAP is a test hook that makes ordinary models take that path.
-static int flux_ks(const vag_ctx* c) {
-    int cap = 512;
-    if (const char* e = vag_hook("VAG_FLUX_K_CAP")) cap = std::max(4, std::atoi(e));
-    return std::max(2, std::min(c->max_k, cap));
+static FluxHooks flux_hooks() {  // (FluxHooks' members in their order)
+    auto get = [](const char* name) {
+        const char* e = vag_hook(name);
+        return e ? std::max(std::atoi(e), HOOK_UNSET + 1) : HOOK_UNSET;
+    };
+    return {get("VAG_PAIRS_PER_BLOCK"), get("VAG_FLUX_K_CAP"), get("VAG_FLUX_WIDE"), get("VAG_GRID_ROWWISE"),
+            get("VAG_GRID_ROW_PER_WORKGROUP"), get("VAG_FLUX_PERSISTENT"), get("VAG_FLUX_SPLIT"), get("VAG_NO_FUSED"),
+            get("VAG_FORCE_FUSED"), get("VAG_SERIES_ROW_PER_WAVE"), get("VAG_FIT_WAVES_PER_BLOCK"), get("VAG_SERIES_PPB"),
+            get("VAG_SERIES_WAVES")};
+}
+
+static int flux_ks(const vag_ctx* c) { return flux_ks(flux_batch(c, 0), flux_hooks()); }
+
+// The batch's device pointers that every flux and sky argument struct carries (FluxArgs, SeriesArgs, SkyArgs, SkyCenArgs: a new
+// per-batch buffer is bound here, once).  d_params: of the selected emitter.  The row / cell offsets differ per struct and stay
+// with the caller (bind_layout), as do the request's own members.  The SSC tables' three pointers are valid only behind the table
+// build, which may reallocate them: a caller that builds tables after this binds those three again.
+template <class A>
+static void bind_batch(A& a, const vag_ctx* c, const vag_model_params* d_params) {
+    a.params = d_params;
+    a.meta = c->d_meta.as<VagGridMeta>();
+    a.geo_th = c->d_geo_th.as<double>();
+    a.geo_ph = c->d_geo_ph.as<double>();
+    a.g_rep_of = c->d_rep_of.as<int>();
+    a.cellpar = c->d_cellpar.as<double>();
+    a.cellq = c->d_cellq.as<double>();
+    a.cellgeo = c->d_cellgeo.as<double>();
+    a.sp_table = c->d_sptab.as<double>();
+    a.ichdr = c->d_ichdr.as<double>();
+    a.icpool = c->d_icpool.as<double>();
+    a.ic_status = c->d_icstatus.as<int>();
+}
+template <class A>
+static void bind_layout(A& a, const vag_ctx* c) { a.cell_off = c->d_cell_off.as<long long>(); }
+static void bind_layout(SeriesArgs& a, const vag_ctx* c) { a.lay = Layout{c->d_row_off.as<int>(), c->d_cell_off.as<long long>()}; }
+
+// Resident workgroups per CU of `fn` with `threads` lanes and `lds` bytes: the occupancy query, remembered per shape; -1 where the
+// query fails.  raise_lds: the kernel's dynamic-LDS limit is lifted to a CU's before the first query.
+static int wg_per_cu(vag_ctx* c, const void* fn, int threads, size_t lds, bool raise_lds = false) {
+    for (const auto& e : c->occ)
+        if (e.fn == fn && e.threads == threads && e.lds == lds) return e.wg;
+    int wg = -1;
+    if (raise_lds) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CU_LDS_BYTES);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, threads, lds) != hipSuccess) wg = -1;
+    if (c->occ.size() > 256) c->occ.clear();
+    c->occ.push_back({fn, threads, lds, wg});
+    return wg;
 }
 
 // the work-item counter of a persistent launch (SeriesArgs::work), in the zeroed words behind the device plan: the kernel behind every
@@ -1299,11 +1313,6 @@ static size_t flux_grid_lds_bytes(int mode, int ks, int nt, int nnu) {
     if (mode == FLUX_FUSED) d += 6 * (size_t)ks + (size_t)ks * nnu + slots;
     return sizeof(double) * d + sizeof(int) * nt + 16;  // + s_win: [2][2] observation-window counts (WinCount)
 }
-
-// dynamic LDS of vag_flux_grid_split_kernel (FluxSplitLds is the layout), and the most it may ask for: two workgroups stay
-// resident per CU, like the kernel it stands in for
-constexpr size_t FLUX_SPLIT_LDS_BUDGET = 81920;
-static size_t flux_split_lds_bytes(int ks, int nt, int nnu) { return FluxSplitLds(ks, nt, nnu).bytes; }
 
 // Stage 4-5 for a (t, nu) grid request: d_lg2t/d_lg2nu are log2 of code-unit times / frequencies.
 int run_flux_series(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_lg2t, const double* d_lg2nu, int n,
@@ -1324,74 +1333,81 @@ static void launch_reduce(hipStream_t st, const vag_model_params* d_params, cons
     }
 }
 
-// One launch of vag_flux_grid_kernel: a workgroup per (block, model), or -- persist = 1 and more items of at least
-// FLUX_PERSIST_MIN_PPB rows than stay resident at once, or persist = 2 (test hook) -- the persistent form with as many workgroups
-// as stay resident (occupancy query x CUs, remembered per kernel and LDS size), its items dealt by descending model cost
-// (vag_flux_order_kernel).  Returns whether it took the persistent form (its counter then has to go back to zero behind it).
-constexpr int FLUX_PERSIST_MIN_PPB = 128;
-constexpr int FLUX_SPLIT_MIN_KS = 192;  // shortest staged lattice the split form takes unforced (measured at 199 nodes)
+// The workgroup kernel of a grid request: the 21 variants grid_variant can give, each as the kernel of one item per workgroup and
+// as the persistent one (42 kernels; what is not listed is not instantiated).
+using FluxKernel = void (*)(FluxArgs);
+struct GridKernels {
+    FluxKernel one = nullptr, persistent = nullptr;
+};
 template <bool COUNT, int MODE, bool SPREAD = false, int THREADS = FLUX_THREADS, bool PIECES = false>
-static bool launch_flux_grid(vag_ctx* c, FluxArgs a, int nb, size_t lds, int persist) {
-    const auto fn = vag_flux_grid_kernel<COUNT, MODE, SPREAD, THREADS, PIECES, true>;
-    int wg = -1;
-    if (persist) {
-        for (const auto& e : c->flux_occ)
-            if (e.fn == reinterpret_cast<const void*>(fn) && e.lds == lds) wg = e.wg;
-        if (wg < 0) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, THREADS, lds) != hipSuccess || wg < 1) wg = 1;
-            if (c->flux_occ.size() > 256) c->flux_occ.clear();
-            c->flux_occ.push_back({reinterpret_cast<const void*>(fn), lds, wg});
-        }
+static GridKernels grid_pair() {
+    return {vag_flux_grid_kernel<COUNT, MODE, SPREAD, THREADS, PIECES>, vag_flux_grid_kernel<COUNT, MODE, SPREAD, THREADS, PIECES, true>};
+}
+constexpr int grid_key(int mode, bool spread, int lanes, bool pieces, bool count = false) {
+    return mode | (spread ? 4 : 0) | (lanes == 256 ? 8 : 0) | (pieces ? 16 : 0) | (count ? 32 : 0);
+}
+static GridKernels grid_kernels(const GridVariant& v) {
+    constexpr int W = FLUX_THREADS;
+    switch (grid_key(v.mode, v.spread, v.lanes, v.pieces, v.count)) {
+        case grid_key(FLUX_SYN, false, W, false): return grid_pair<false, FLUX_SYN>();
+        case grid_key(FLUX_SYN_IC, false, W, false): return grid_pair<false, FLUX_SYN_IC>();
+        case grid_key(FLUX_SSC, false, W, false): return grid_pair<false, FLUX_SSC>();
+        case grid_key(FLUX_FUSED, false, W, false): return grid_pair<false, FLUX_FUSED>();
+        case grid_key(FLUX_SYN, false, W, false, true): return grid_pair<true, FLUX_SYN>();
+        case grid_key(FLUX_SYN, true, W, false): return grid_pair<false, FLUX_SYN, true>();
+        case grid_key(FLUX_SYN_IC, true, W, false): return grid_pair<false, FLUX_SYN_IC, true>();
+        case grid_key(FLUX_SSC, true, W, false): return grid_pair<false, FLUX_SSC, true>();
+        case grid_key(FLUX_FUSED, true, W, false): return grid_pair<false, FLUX_FUSED, true>();
+        case grid_key(FLUX_SYN, false, 256, false): return grid_pair<false, FLUX_SYN, false, 256>();
+        case grid_key(FLUX_SYN_IC, false, 256, false): return grid_pair<false, FLUX_SYN_IC, false, 256>();
+        case grid_key(FLUX_SSC, false, 256, false): return grid_pair<false, FLUX_SSC, false, 256>();
+        case grid_key(FLUX_FUSED, false, 256, false): return grid_pair<false, FLUX_FUSED, false, 256>();
+        case grid_key(FLUX_SYN, false, W, true): return grid_pair<false, FLUX_SYN, false, W, true>();
+        case grid_key(FLUX_SYN_IC, false, W, true): return grid_pair<false, FLUX_SYN_IC, false, W, true>();
+        case grid_key(FLUX_SSC, false, W, true): return grid_pair<false, FLUX_SSC, false, W, true>();
+        case grid_key(FLUX_FUSED, false, W, true): return grid_pair<false, FLUX_FUSED, false, W, true>();
+        case grid_key(FLUX_SYN, true, W, true): return grid_pair<false, FLUX_SYN, true, W, true>();
+        case grid_key(FLUX_SYN_IC, true, W, true): return grid_pair<false, FLUX_SYN_IC, true, W, true>();
+        case grid_key(FLUX_SSC, true, W, true): return grid_pair<false, FLUX_SSC, true, W, true>();
+        case grid_key(FLUX_FUSED, true, W, true): return grid_pair<false, FLUX_FUSED, true, W, true>();
     }
-    // A launch that fits in one round gains nothing from a deal order, and the item loop's spills cost the short ones up to 5 %.
-    // Short items lose too: every item starts with a round trip to the counter and two barriers, and on items of 32 rows (16384
-    // configs[0] top hats, ppb 64) the persistent form took 6.1 against 4.6 ms.  Measured to win at ppb 128 (configs[1], 512 models).
-    if (!persist || (persist == 1 && (a.n_items <= (long long)wg * c->n_cus || a.pairs_per_block < FLUX_PERSIST_MIN_PPB))) {
-        if (vag_hook("VAG_DEBUG_LAUNCH")) std::fprintf(stderr, "[vag] grid flux form: one item per workgroup, %d x %d\n", a.max_blocks, nb);
-        a.work = nullptr;
-        hipLaunchKernelGGL((vag_flux_grid_kernel<COUNT, MODE, SPREAD, THREADS, PIECES>), dim3(a.max_blocks, nb), dim3(THREADS), lds, c->stream, a);
-        return false;
-    }
-    const long long n_wg = std::min<long long>(a.n_items, (long long)wg * c->n_cus);
-    if (vag_hook("VAG_DEBUG_LAUNCH"))
-        std::fprintf(stderr, "[vag] grid flux form: persistent, %lld workgroups for %d items\n", n_wg, a.n_items);
-    hipLaunchKernelGGL(vag_flux_order_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, a.meta, nb, const_cast<int*>(a.order));
-    hipLaunchKernelGGL(fn, dim3((unsigned)n_wg), dim3(THREADS), lds, c->stream, a);
-    return true;
+    return {};
 }
 
-// The split form of the headline launch (vag_flux_grid_split_kernel: fixed wavefront roles, one barrier per row) where the request
-// is one it serves -- the caller has checked plain synchrotron, non-spreading, one piece, 512 lanes, no tallies -- and
-// launch_flux_grid would go persistent.  split = 1: the shapes it is measured to win on; 2 (test hook): wherever it is legal.
-// Returns false with nothing launched where the present kernel has to take the request.
-static bool launch_flux_grid_split(vag_ctx* c, FluxArgs a, int nb, int persist, int split) {
-    if (!split || !persist || !a.rowgeo) return false;
-    const size_t lds = flux_split_lds_bytes(a.k_stride, a.nt, a.nnu);
-    if (lds > FLUX_SPLIT_LDS_BUDGET || a.nnu > FLUX_SPLIT_MAX_NNU || a.nt > FLUX_SPLIT_MAX_NT) return false;
-    // Unforced only on what was measured, the headline shape (lattices of 199 nodes, 200 times x 10 frequencies): all ten frequencies
-    // (fewer take the B team's chain-after-chain loop, which lost), times in the range where B lanes own two, and a lattice about as
-    // long -- the A team's work scales with the lattice, the B team's two wavefronts carry every (nu, t) slot whatever its length,
-    // so on shorter lattices they are what a row waits for.  The LDS budget bounds the lattice from above (204 nodes at this grid).
-    if (split == 1 && (a.nnu != FLUX_SPLIT_MAX_NNU || a.nt <= FLUX_SPLIT_B * 64 || a.k_stride < FLUX_SPLIT_MIN_KS)) return false;
-    const auto fn = vag_flux_grid_split_kernel;
-    int wg = -1;
-    for (const auto& e : c->flux_occ)
-        if (e.fn == reinterpret_cast<const void*>(fn) && e.lds == lds) wg = e.wg;
-    if (wg < 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, FLUX_THREADS, lds) != hipSuccess || wg < 1) wg = 1;
-        if (c->flux_occ.size() > 256) c->flux_occ.clear();
-        c->flux_occ.push_back({reinterpret_cast<const void*>(fn), lds, wg});
+// vag_flux_grid_rows_kernel: one instantiation per photon source (3)
+using SeriesKernel = void (*)(SeriesArgs);
+static SeriesKernel grid_rows_kernel(int mode) {
+    switch (mode) {
+        case FLUX_SYN_IC: return vag_flux_grid_rows_kernel<FLUX_SYN_IC>;
+        case FLUX_SSC: return vag_flux_grid_rows_kernel<FLUX_SSC>;
+        default: return vag_flux_grid_rows_kernel<FLUX_SYN>;
     }
-    if (persist == 1 && (a.n_items <= (long long)wg * c->n_cus || a.pairs_per_block < FLUX_PERSIST_MIN_PPB)) return false;
-    const long long n_wg = std::min<long long>(a.n_items, (long long)wg * c->n_cus);
-    if (vag_hook("VAG_DEBUG_LAUNCH")) {
-        std::fprintf(stderr, "[vag] grid flux form: persistent, %lld workgroups for %d items\n", n_wg, a.n_items);
-        std::fprintf(stderr, "[vag] grid flux split: %d + %d wavefronts (boundary spectra + interpolation), lds=%zu B wg/CU=%d\n", FLUX_SPLIT_A,
-                     FLUX_SPLIT_B, lds, wg);
+}
+
+// One launch over the work items of `a` (a.n_items = models x blocks): a workgroup per item with `one`, or -- where persist_plan
+// says so -- the persistent kernel `pers` with as many workgroups as stay resident, its items dealt by descending model cost
+// (vag_flux_order_kernel).  one == nullptr (the split form, which has no one-item kernel): nothing is launched where the launch
+// does not go persistent.  Returns whether it took the persistent form (its counter then has to go back to zero behind it).
+static bool launch_flux_items(vag_ctx* c, FluxArgs a, int nb, FluxKernel one, FluxKernel pers, int threads, size_t lds, int persist) {
+    const bool debug = vag_hook("VAG_DEBUG_LAUNCH") != nullptr;
+    // (a failed query counts as one resident workgroup; the present kernel's LDS limit is lifted with its first query, as it always was)
+    const int wg = persist ? std::max(1, wg_per_cu(c, reinterpret_cast<const void*>(pers), threads, lds, one != nullptr)) : -1;
+    const PersistPlan p = persist_plan(persist, a.n_items, wg, c->n_cus, a.pairs_per_block);
+    if (!p.persistent) {
+        if (!one) return false;
+        if (debug) std::fprintf(stderr, "[vag] grid flux form: one item per workgroup, %d x %d\n", a.max_blocks, nb);
+        a.work = nullptr;
+        hipLaunchKernelGGL(one, dim3(a.max_blocks, nb), dim3(threads), lds, c->stream, a);
+        return false;
+    }
+    if (debug) {
+        std::fprintf(stderr, "[vag] grid flux form: persistent, %lld workgroups for %d items\n", p.n_wg, a.n_items);
+        if (!one)
+            std::fprintf(stderr, "[vag] grid flux split: %d + %d wavefronts (boundary spectra + interpolation), lds=%zu B wg/CU=%d\n", FLUX_SPLIT_A,
+                         FLUX_SPLIT_B, lds, wg);
     }
     hipLaunchKernelGGL(vag_flux_order_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, a.meta, nb, const_cast<int*>(a.order));
-    hipLaunchKernelGGL(fn, dim3((unsigned)n_wg), dim3(FLUX_THREADS), lds, c->stream, a);
+    hipLaunchKernelGGL(pers, dim3((unsigned)p.n_wg), dim3(threads), lds, c->stream, a);
     return true;
 }
 
@@ -1401,94 +1417,62 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
     hipStream_t st = c->stream;
     StageScope ps(c, mode == FLUX_SSC ? PS_SSC_FLUX : PS_SYNC_FLUX);
     const int slots = nt * nnu;
+    const FluxBatch batch = flux_batch(c, nb);
+    const FluxHooks hooks = flux_hooks();
+    const bool debug = vag_hook("VAG_DEBUG_LAUNCH") != nullptr;
     // Rows of a few hundred (nu, t) slots keep a 256-lane workgroup 22-78 % busy between its two barriers (C3, C5, C1: four or
     // three frequencies).  The wavefront-per-row kernel can serve them (VAG_GRID_ROWWISE=1: same algorithm -- boundary spectra
     // per (nu, lattice node of the window), log-log interpolation --, no workgroup barrier, accumulators in registers), but
     // MEASURED SLOWER on every such shape (C5 2.2 k vs 4.5 k light curves/s, C3 1.27 k vs 1.79 k, C1a 1.28 M vs 2.58 M: eight
     // points per lane cost the occupancy, and every lane walks its own bracket searches), so the workgroup kernel stays.
-    if (slots <= SERIES_THREADS * SERIES_MAX_SLOTS && nnu <= SERIES_MAX_BANDS && !d_bandw && mode != FLUX_FUSED && !c->count_work &&
-        vag_hook("VAG_GRID_ROWWISE") && !(c->batch_flags & VAG_FLAG_SPREADING))
+    if (grid_rowwise(batch, hooks, mode, nt, nnu, d_bandw != nullptr))
         return run_flux_series(c, d_params, nb, d_lg2t, d_lg2nu, slots, d_out, mode, nnu, nt);
     if (slots > FLUX_MAX_SLOTS)
         return set_err(VAG_E_CAPACITY, "nt*nnu = %d exceeds %d per launch", slots, FLUX_MAX_SLOTS);
-    // Small grids of large batches: a (theta, phi) row per lane (vag_grid_rows.h).  A lone model would walk its lattice as one
-    // sequential chain there, so the batch must bring blocks of 64 rows enough to fill the GPU; models of a few rows (on-axis
-    // top hats: 32 rows) would leave lanes empty.  The choice is the batch's (total_pairs) and the kernel sums in another order, so
-    // a request whose result must not depend on the batch (vag_ctx::ppb_pin, a counts pass) stays on the workgroup kernel below.
-    {
-        const long long blocks = (c->total_pairs + FITROWS_ROWS - 1) / FITROWS_ROWS;
-        if (mode != FLUX_FUSED && !(c->batch_flags & VAG_FLAG_SPREADING) && !c->count_work && slots <= GRIDROWS_MAX_SLOTS &&
-            nnu <= GRIDROWS_BANDS && nt <= GRIDROWS_MAX_NT && blocks >= 4096 && c->total_pairs >= 128LL * nb && c->n_rows > 0 &&
-            !c->ppb_pin && !vag_hook("VAG_GRID_ROW_PER_WORKGROUP")) {
-            const int max_blocks = std::max(1, (c->max_pairs + FITROWS_ROWS - 1) / FITROWS_ROWS);
-            if (c->d_partial.ensure(sizeof(double) * (size_t)nb * max_blocks * slots)) return VAG_E_HIP;
-            SeriesArgs a{};
-            a.params = d_params;
-            a.meta = c->d_meta.as<VagGridMeta>();
-            a.geo_th = c->d_geo_th.as<double>();
-            a.geo_ph = c->d_geo_ph.as<double>();
-            a.g_rep_of = c->d_rep_of.as<int>();
-            a.lay = Layout{c->d_row_off.as<int>(), c->d_cell_off.as<long long>()};
-            a.cellpar = c->d_cellpar.as<double>();
-            a.lg2_t_obs = d_lg2t;
-            a.lg2_nu_obs = d_lg2nu;
-            a.n = slots;
-            a.grid_nt = nt;
-            a.n_bands = nnu;
-            a.max_chunks = max_blocks;
-            a.partial = c->d_partial.as<double>();
-            a.sp_table = c->d_sptab.as<double>();
-            a.cellq = c->d_cellq.as<double>();
-            a.ichdr = c->d_ichdr.as<double>();
-            a.icpool = c->d_icpool.as<double>();
-            a.ic_status = c->d_icstatus.as<int>();
-            c->plan.spec_evals += c->eat_cells * nnu;
-            c->plan.interps += c->total_pairs * (long long)nt * nnu;
-            c->plan.flux_blocks = max_blocks * nb;
-            c->plan.pairs_per_block = FITROWS_ROWS;
-            // The plain-synchrotron pass is a persistent launch like vag_flux_fit_rows_kernel (three workgroups per CU that take blocks
-            // until none is left: vag_grid_rows.h); the IC-corrected and the tabulated-SSC pass keep one workgroup per four blocks (the
-            // first has no registers for the loop -- 61 against 47 ms per 1024 C5 members, measured -- the second nothing to gain).
-            const bool persistent = mode != FLUX_SYN_IC && mode != FLUX_SSC;
-            a.nb = nb;
-            a.work = work_counters(c);
-            const long long wg_need = (blocks + nb + GRIDROWS_WAVES - 1) / GRIDROWS_WAVES;  // (total_pairs may be the previous call's)
-            const dim3 g_all((max_blocks + GRIDROWS_WAVES - 1) / GRIDROWS_WAVES, nb), b(SERIES_THREADS * GRIDROWS_WAVES);
-            const dim3 g_pers((unsigned)std::max<long long>(1, std::min<long long>(wg_need, 3LL * c->n_cus)));
-            const size_t lds = grid_rows_lds_bytes(slots);
-            if (vag_hook("VAG_DEBUG_LAUNCH"))
-                std::fprintf(stderr, "[vag] grid rows launch: mode %d nt=%d nnu=%d blocks=%lld persistent=%d lds=%zu B\n", mode, nt, nnu, blocks,
-                             (int)persistent, lds);
-            if (mode == FLUX_SYN_IC)
-                hipLaunchKernelGGL((vag_flux_grid_rows_kernel<FLUX_SYN_IC>), g_all, b, lds, st, a);
-            else if (mode == FLUX_SSC)
-                hipLaunchKernelGGL((vag_flux_grid_rows_kernel<FLUX_SSC>), g_all, b, lds, st, a);
-            else
-                hipLaunchKernelGGL((vag_flux_grid_rows_kernel<FLUX_SYN>), g_pers, b, lds, st, a);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(c->ev[4], st));
-            launch_reduce(st, d_params, c->d_meta.as<VagGridMeta>(), c->d_partial.as<double>(), max_blocks, FITROWS_ROWS, nt, nnu, d_bandw, d_out, nb,
-                          persistent ? work_counters(c) : nullptr);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(c->ev[5], st));
-            return VAG_OK;
-        }
+    if (const GridRowsPlan p = grid_rows_plan(batch, hooks, mode, nt, nnu); p.take) {  // a (theta, phi) row per lane (vag_grid_rows.h)
+        if (c->d_partial.ensure(sizeof(double) * (size_t)nb * p.max_blocks * slots)) return VAG_E_HIP;
+        SeriesArgs a{};
+        bind_batch(a, c, d_params);
+        bind_layout(a, c);
+        a.cellgeo = nullptr;  // (never a spreading batch)
+        a.lg2_t_obs = d_lg2t;
+        a.lg2_nu_obs = d_lg2nu;
+        a.n = slots;
+        a.grid_nt = nt;
+        a.n_bands = nnu;
+        a.max_chunks = p.max_blocks;
+        a.partial = c->d_partial.as<double>();
+        c->plan.spec_evals += c->eat_cells * nnu;
+        c->plan.interps += c->total_pairs * (long long)nt * nnu;
+        c->plan.flux_blocks = p.max_blocks * nb;
+        c->plan.pairs_per_block = FITROWS_ROWS;
+        a.nb = nb;
+        a.work = work_counters(c);
+        const size_t lds = grid_rows_lds_bytes(slots);
+        if (debug)
+            std::fprintf(stderr, "[vag] grid rows launch: mode %d nt=%d nnu=%d blocks=%lld persistent=%d lds=%zu B\n", mode, nt, nnu, p.blocks,
+                         (int)p.persistent, lds);
+        hipLaunchKernelGGL(grid_rows_kernel(mode), p.persistent ? dim3(p.wg_persistent) : dim3(p.wg_all, nb),
+                           dim3(SERIES_THREADS * GRIDROWS_WAVES), lds, st, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev[4], st));
+        launch_reduce(st, d_params, c->d_meta.as<VagGridMeta>(), c->d_partial.as<double>(), p.max_blocks, FITROWS_ROWS, nt, nnu, d_bandw, d_out,
+                      nb, p.persistent ? work_counters(c) : nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev[5], st));
+        return VAG_OK;
     }
-    const int ppb = choose_pairs_per_block(c);
+    const int ppb = choose_pairs_per_block(batch, hooks);
     const int max_blocks = std::max(1, (c->max_pairs + ppb - 1) / ppb);
     if (c->d_partial.ensure(sizeof(double) * (size_t)nb * max_blocks * slots)) return VAG_E_HIP;
-    const int ks = flux_ks(c);
+    const int ks = flux_ks(batch, hooks);
     const size_t lds = flux_grid_lds_bytes(mode, ks, nt, nnu);
-    if (lds > 160 * 1024) return set_err(VAG_E_CAPACITY, "LDS request %zu B exceeds 160 KiB (n_t=%d, nnu=%d)", lds, ks, nnu);
+    if (lds > CU_LDS_BYTES) return set_err(VAG_E_CAPACITY, "LDS request %zu B exceeds 160 KiB (n_t=%d, nnu=%d)", lds, ks, nnu);
     if (mode == FLUX_FUSED && c->d_partial2.ensure(sizeof(double) * (size_t)nb * max_blocks * slots)) return VAG_E_HIP;
-    FluxArgs a;
-    a.params = d_params;
-    a.meta = c->d_meta.as<VagGridMeta>();
-    a.geo_th = c->d_geo_th.as<double>();
-    a.geo_ph = c->d_geo_ph.as<double>();
-    a.g_rep_of = c->d_rep_of.as<int>();
-    a.cell_off = c->d_cell_off.as<long long>();
-    a.cellpar = c->d_cellpar.as<double>();
+    const GridVariant v = grid_variant(batch, hooks, mode, nt, nnu, ks);
+    FluxArgs a{};  // (work_count, rowgeo, work and order stay null where nothing below sets them)
+    bind_batch(a, c, d_params);
+    bind_layout(a, c);
     a.lg2_t_obs = d_lg2t;
     a.lg2_nu_obs = d_lg2nu;
     a.nt = nt;
@@ -1498,24 +1482,12 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
     a.k_stride = ks;
     a.partial = c->d_partial.as<double>();
     a.partial2 = c->d_partial2.as<double>();
-    a.sp_table = c->d_sptab.as<double>();
-    a.work_count = nullptr;
-    a.cellq = c->d_cellq.as<double>();
-    a.ichdr = c->d_ichdr.as<double>();
-    a.icpool = c->d_icpool.as<double>();
-    a.ic_status = c->d_icstatus.as<int>();
-    a.cellgeo = c->d_cellgeo.as<double>();
-    const bool spreading = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
-    a.rowgeo = nullptr;
-    a.rowgeo_stride = 0;
-    a.work = nullptr;
-    a.order = nullptr;
     a.n_items = nb * max_blocks;
-    if (!spreading) {  // the models' row-geometry records, written by the grid kernel with the layout it ran with
+    if (!batch.spreading) {  // the models' row-geometry records, written by the grid kernel with the layout it ran with
         a.rowgeo = c->d_rowgeo.as<double>();
         a.rowgeo_stride = rowgeo_stride(c->layout_large);
     }
-    if (c->count_work && mode == FLUX_SYN && !spreading) {
+    if (v.count) {
         if (c->d_workcount.ensure(2 * sizeof(unsigned long long))) return VAG_E_HIP;
         HIPCHK(hipMemsetAsync(c->d_workcount.p, 0, 2 * sizeof(unsigned long long), st));
         a.work_count = c->d_workcount.as<unsigned long long>();
@@ -1528,86 +1500,32 @@ int run_flux_grid(vag_ctx* c, const vag_model_params* d_params, int nb, const do
     c->plan.pairs_per_block = ppb;
     bool persistent = false;
     if (c->n_rows > 0) {
-        // requests with few (nu, t) slots and short rows keep less than half of a 512-lane workgroup busy: use 256 lanes
-        // (+47 % on the C5 / C1b shapes; a 128-lane variant measured slower)
-        const bool small = !spreading && !a.work_count && (long long)nt * nnu <= 512 && (long long)ks * ((nnu + 1) / 2) <= 512 &&
-                           !vag_hook("VAG_FLUX_WIDE");
-        if (vag_hook("VAG_DEBUG_LAUNCH")) {
-            // (lds / wg/CU are the present kernel's also where the split form then takes the launch: its own are on its "grid flux split" line)
-            int occ = -1;
-            if (small && mode == FLUX_SSC)
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vag_flux_grid_kernel<false, FLUX_SSC, false, 256>, 256, lds);
-            else if (small && mode == FLUX_SYN_IC)
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vag_flux_grid_kernel<false, FLUX_SYN_IC, false, 256>, 256, lds);
-            else if (small)
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vag_flux_grid_kernel<false, FLUX_SYN, false, 256>, 256, lds);
-            else if (mode == FLUX_SYN && !spreading)
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vag_flux_grid_kernel<false, FLUX_SYN>, FLUX_THREADS, lds);
+        const GridKernels k = grid_kernels(v);
+        if (!k.one) return set_err(VAG_E_INVALID, "no flux grid kernel for mode %d", mode);
+        if (debug)  // (lds / wg/CU are the present kernel's also where the split form then takes the launch: its own are on its "grid flux split" line)
             std::fprintf(stderr, "[vag] grid flux launch: mode %d nt=%d nnu=%d ks=%d rows/wg=%d lanes=%d lds=%zu B wg/CU=%d\n", mode, nt, nnu, ks,
-                         ppb, small ? 256 : FLUX_THREADS, lds, occ);
-        }
-        const bool pieces = c->max_k > ks;  // some lattice is longer than the staged row: the instantiations with the piece loop
+                         ppb, v.lanes, lds, wg_per_cu(c, reinterpret_cast<const void*>(k.one), v.lanes, lds));
         // (Measured and rejected, profiles/rejected/vag_flux_wide.h: ONE 1024-lane workgroup per CU sharing the staged row and tables, a
         // second boundary block in the LDS that frees, one barrier per row and balanced slot ownership -- bitwise the same fluxes,
         // 27.0-27.7 ms against 21.7 per 512 C2 models: sixteen wavefronts in lockstep lose the overlap two independent workgroups have.)
         // Persistent launch (VAG_FLUX_PERSISTENT=0: a workgroup per item, the launch before it; =2: persistent whatever the shape):
         // the resident workgroups take the items from a counter, the models by descending cost, so that the launch drains on its
         // cheapest items.
-        int persist = 1;
-        if (const char* e = vag_hook("VAG_FLUX_PERSISTENT")) persist = std::atoi(e);
-        int split = 1;
-        if (const char* e = vag_hook("VAG_FLUX_SPLIT")) split = std::atoi(e);
+        const int persist = hook_or(hooks.persistent, 1);
         if (persist) {
             if (c->d_flux_order.ensure(sizeof(int) * (size_t)nb)) return VAG_E_HIP;
             a.work = work_counters(c);
             a.order = c->d_flux_order.as<int>();
         }
-        if (pieces) {
-            a.work_count = nullptr;  // the tallying instantiation has no piece loop: the plan keeps the upper bounds
-#define VAG_PIECES_LAUNCH(M_)                                                                                          \
-    do {                                                                                                               \
-        if (spreading)                                                                                                 \
-            persistent = launch_flux_grid<false, M_, true, FLUX_THREADS, true>(c, a, nb, lds, persist);                         \
-        else                                                                                                           \
-            persistent = launch_flux_grid<false, M_, false, FLUX_THREADS, true>(c, a, nb, lds, persist);                        \
-    } while (0)
-            if (mode == FLUX_FUSED)
-                VAG_PIECES_LAUNCH(FLUX_FUSED);
-            else if (mode == FLUX_SYN_IC)
-                VAG_PIECES_LAUNCH(FLUX_SYN_IC);
-            else if (mode == FLUX_SSC)
-                VAG_PIECES_LAUNCH(FLUX_SSC);
-            else
-                VAG_PIECES_LAUNCH(FLUX_SYN);
-#undef VAG_PIECES_LAUNCH
-        } else if (small && mode == FLUX_FUSED)
-            persistent = launch_flux_grid<false, FLUX_FUSED, false, 256>(c, a, nb, lds, persist);
-        else if (spreading && mode == FLUX_FUSED)
-            persistent = launch_flux_grid<false, FLUX_FUSED, true>(c, a, nb, lds, persist);
-        else if (mode == FLUX_FUSED)
-            persistent = launch_flux_grid<false, FLUX_FUSED>(c, a, nb, lds, persist);
-        else if (small && mode == FLUX_SYN_IC)
-            persistent = launch_flux_grid<false, FLUX_SYN_IC, false, 256>(c, a, nb, lds, persist);
-        else if (small && mode == FLUX_SSC)
-            persistent = launch_flux_grid<false, FLUX_SSC, false, 256>(c, a, nb, lds, persist);
-        else if (small)
-            persistent = launch_flux_grid<false, FLUX_SYN, false, 256>(c, a, nb, lds, persist);
-        else if (spreading && mode == FLUX_SYN_IC)
-            persistent = launch_flux_grid<false, FLUX_SYN_IC, true>(c, a, nb, lds, persist);
-        else if (spreading && mode == FLUX_SSC)
-            persistent = launch_flux_grid<false, FLUX_SSC, true>(c, a, nb, lds, persist);
-        else if (spreading)
-            persistent = launch_flux_grid<false, FLUX_SYN, true>(c, a, nb, lds, persist);
-        else if (mode == FLUX_SYN_IC)
-            persistent = launch_flux_grid<false, FLUX_SYN_IC>(c, a, nb, lds, persist);
-        else if (mode == FLUX_SSC)
-            persistent = launch_flux_grid<false, FLUX_SSC>(c, a, nb, lds, persist);
-        else if (a.work_count)
-            persistent = launch_flux_grid<true, FLUX_SYN>(c, a, nb, lds, persist);
-        else if (launch_flux_grid_split(c, a, nb, persist, split))  // VAG_FLUX_SPLIT=0: never; =2: wherever the split form is legal
-            persistent = true;
-        else
-            persistent = launch_flux_grid<false, FLUX_SYN>(c, a, nb, lds, persist);
+        // The split form of the headline launch (vag_flux_grid_split_kernel: fixed wavefront roles, one barrier per row) where the
+        // request is one it serves and the launch goes persistent (VAG_FLUX_SPLIT=0: never; =2: wherever the split form is legal);
+        // FluxSplitLds is its LDS layout
+        if (grid_variant_plain(v)) {
+            const size_t lds_split = FluxSplitLds(ks, nt, nnu).bytes;
+            if (split_takes(hook_or(hooks.split, 1), persist, a.rowgeo != nullptr, lds_split, nt, nnu, ks))
+                persistent = launch_flux_items(c, a, nb, nullptr, vag_flux_grid_split_kernel, FLUX_THREADS, lds_split, persist);
+        }
+        if (!persistent) persistent = launch_flux_items(c, a, nb, k.one, k.persistent, v.lanes, lds, persist);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(c->ev[4], st));
@@ -1833,15 +1751,10 @@ int run_flux_ssc(vag_ctx* c, const vag_model_params* d_params, int nb, const dou
 // spectra ride the same EAT logs, bracket search and barriers (the two-pass form pays that row skeleton twice -- 35-45 %
 // of a pass on the C5 / C3 shapes).  Falls back to two passes when the doubled buffers would not fit in LDS twice.
 static bool fused_fits(vag_ctx* c, int nt, int nnu) {
-    if (vag_hook("VAG_NO_FUSED")) return false;
-    if (vag_hook("VAG_GRID_ROWWISE") && nt * nnu <= SERIES_THREADS * SERIES_MAX_SLOTS && nnu <= SERIES_MAX_BANDS && !c->count_work)
-        return false;  // experiment switch of run_flux_grid: two passes of the wavefront-per-row kernel
-    // the second set of buffers must not cost a resident workgroup: on the C5 / C3 shapes it does (63 vs 51 KB: two
-    // workgroups per CU instead of three) and the fused pass measured 18 % SLOWER than two passes there
-    const size_t cu = 160 * 1024, fused = flux_grid_lds_bytes(FLUX_FUSED, flux_ks(c), nt, nnu),
-                 two = flux_grid_lds_bytes(FLUX_SYN_IC, flux_ks(c), nt, nnu);
-    if (vag_hook("VAG_FORCE_FUSED")) return fused <= cu;
-    return fused <= cu && std::min<size_t>(cu / fused, 4) >= std::min<size_t>(cu / two, 4);
+    const FluxBatch batch = flux_batch(c, 0);
+    const FluxHooks hooks = flux_hooks();
+    const int ks = flux_ks(batch, hooks);
+    return fused_fits(batch, hooks, nt, nnu, flux_grid_lds_bytes(FLUX_FUSED, ks, nt, nnu), flux_grid_lds_bytes(FLUX_SYN_IC, ks, nt, nnu));
 }
 int run_flux_fused(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_lg2t, int nt, const double* d_lg2nu,
                    int nnu, const double* d_bandw, double* d_syn, double* d_ssc, const double* d_lg2nu_all, int nnu_all) {
@@ -2035,16 +1948,8 @@ static int sky_terms_stage(vag_ctx* c, const vag_model_params* d_params, int nb,
     for (int q = 0; q < n_pass && rc == VAG_OK; ++q) {
         select_emitter(c, passes[q].e, d_params);
         SkyArgs a{};
-        a.params = c->cur_params;
-        a.meta = c->d_meta.as<VagGridMeta>();
-        a.geo_th = c->d_geo_th.as<double>();
-        a.geo_ph = c->d_geo_ph.as<double>();
-        a.g_rep_of = c->d_rep_of.as<int>();
-        a.cell_off = c->d_cell_off.as<long long>();
-        a.cellpar = c->d_cellpar.as<double>();
-        a.cellq = c->d_cellq.as<double>();
-        a.cellgeo = c->d_cellgeo.as<double>();
-        a.sp_table = c->d_sptab.as<double>();
+        bind_batch(a, c, c->cur_params);
+        bind_layout(a, c);
         a.lg2_t_obs = c->d_lg2t.as<double>() + t0;
         a.lg2_nu_obs = c->d_lg2nu.as<double>();
         a.nt = n;
@@ -2260,6 +2165,14 @@ int sky_request(vag_ctx* c, const vag_model_params* d_params, int nb, int nt, in
     return VAG_OK;
 }
 
+static void (*centroid_kernel(int mode, bool spread))(SkyCenArgs) {  // vag_sky_centroid_kernel<mode, spread>: 3 photon sources x 2
+    switch (mode) {
+        case FLUX_SSC: return spread ? vag_sky_centroid_kernel<FLUX_SSC, true> : vag_sky_centroid_kernel<FLUX_SSC, false>;
+        case FLUX_SYN_IC: return spread ? vag_sky_centroid_kernel<FLUX_SYN_IC, true> : vag_sky_centroid_kernel<FLUX_SYN_IC, false>;
+        default: return spread ? vag_sky_centroid_kernel<FLUX_SYN, true> : vag_sky_centroid_kernel<FLUX_SYN, false>;
+    }
+}
+
 // Exact sky moments of the whole batch (vag_sky_centroid_kernel); model stages already run, d_lg2t / d_lg2nu prepared.  The passes
 // are sky_request's, each writing its row-block partials into its own slice; the combine reads the slices in that fixed order.  The
 // time axis is cut into chunks whose partials stay within 256 MB (VAG_SKY_CHUNK_T: a test's chunk length).  d_moments
@@ -2288,17 +2201,9 @@ int centroid_request(vag_ctx* c, const vag_model_params* d_params, int nb, int n
         for (int q = 0; q < n_pass && rc == VAG_OK; ++q) {
             select_emitter(c, passes[q].e, d_params);
             SkyCenArgs a{};
-            a.params = c->cur_params;
-            a.meta = c->d_meta.as<VagGridMeta>();
-            a.geo_th = c->d_geo_th.as<double>();
-            a.geo_ph = c->d_geo_ph.as<double>();
+            bind_batch(a, c, c->cur_params);
+            bind_layout(a, c);
             a.phi = c->d_phi.as<double>();
-            a.g_rep_of = c->d_rep_of.as<int>();
-            a.cell_off = c->d_cell_off.as<long long>();
-            a.cellpar = c->d_cellpar.as<double>();
-            a.cellq = c->d_cellq.as<double>();
-            a.cellgeo = c->d_cellgeo.as<double>();
-            a.sp_table = c->d_sptab.as<double>();
             a.lg2_t_obs = c->d_lg2t.as<double>() + t0;
             a.lg2_nu_obs = c->d_lg2nu.as<double>();
             a.nt = n;
@@ -2306,21 +2211,15 @@ int centroid_request(vag_ctx* c, const vag_model_params* d_params, int nb, int n
             a.n_blk = n_blk;
             a.partial = c->d_skycen.as<double>() + (size_t)q * nb * nnu * n * n_blk * 6;
             const int mode = passes[q].pass == 1 ? FLUX_SSC : (c->cur_ssc ? FLUX_SYN_IC : FLUX_SYN);
-            auto launch = [&](auto kernel) -> int {
-                hipLaunchKernelGGL(kernel, dim3((n_blk + SKYC_WAVES - 1) / SKYC_WAVES, nb), dim3(SKYC_ROWS * SKYC_WAVES), 0, st, a);
-                HIPCHK(hipGetLastError());
-                return VAG_OK;
-            };
             auto rows = [&]() -> int {
                 StageScope ps(c, mode == FLUX_SSC ? PS_SSC_FLUX : PS_SYNC_FLUX);
                 a.ichdr = c->d_ichdr.as<double>();  // (behind the table build, which may reallocate them)
                 a.icpool = c->d_icpool.as<double>();
                 a.ic_status = c->d_icstatus.as<int>();
-                if (mode == FLUX_SSC)
-                    return spreading ? launch(vag_sky_centroid_kernel<FLUX_SSC, true>) : launch(vag_sky_centroid_kernel<FLUX_SSC, false>);
-                if (mode == FLUX_SYN_IC)
-                    return spreading ? launch(vag_sky_centroid_kernel<FLUX_SYN_IC, true>) : launch(vag_sky_centroid_kernel<FLUX_SYN_IC, false>);
-                return spreading ? launch(vag_sky_centroid_kernel<FLUX_SYN, true>) : launch(vag_sky_centroid_kernel<FLUX_SYN, false>);
+                hipLaunchKernelGGL(centroid_kernel(mode, spreading), dim3((n_blk + SKYC_WAVES - 1) / SKYC_WAVES, nb),
+                                   dim3(SKYC_ROWS * SKYC_WAVES), 0, st, a);
+                HIPCHK(hipGetLastError());
+                return VAG_OK;
             };
             if (mode == FLUX_SSC) {  // the tables clamped to the requested frequencies exactly as a grid call clamps them
                 rc = ssc_attempts(c, nb, [&](bool rebuild) {
@@ -2455,17 +2354,53 @@ vag_series_reduce_kernel(const vag_model_params* __restrict__ params, const VagG
     }
 }
 
-// resident workgroups per CU of a series launch with `waves` wavefronts and `lds` bytes (occupancy query, remembered per shape)
-static int series_wg_per_cu(vag_ctx* c, int waves, size_t lds) {
-    for (const auto& e : c->series_occ)
-        if (e.waves == waves && e.lds == lds) return e.wg;
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vag_flux_series_kernel<FLUX_SYN, false, 1>, SERIES_THREADS * waves, lds) !=
-        hipSuccess)
-        occ = (int)((144 * 1024) / std::max<size_t>(lds, 1));
-    if (c->series_occ.size() > 256) c->series_occ.clear();
-    c->series_occ.push_back({waves, lds, occ});
-    return occ;
+// vag_flux_fit_rows_kernel<mode, bands, spread, tally>: the 13 variants fit_rows_plan can give
+static SeriesKernel fit_rows_kernel(const FitRowsVariant& v) {
+    constexpr auto key = [](int mode, int bands, bool spread, bool tally = false) {
+        return mode | (bands == 8 ? 4 : 0) | (spread ? 8 : 0) | (tally ? 16 : 0);
+    };
+    switch (key(v.mode, v.bands, v.spread, v.tally)) {
+        case key(FLUX_SYN, 4, false): return vag_flux_fit_rows_kernel<FLUX_SYN, 4>;
+        case key(FLUX_SYN, 8, false): return vag_flux_fit_rows_kernel<FLUX_SYN, 8>;
+        case key(FLUX_SYN, 4, true): return vag_flux_fit_rows_kernel<FLUX_SYN, 4, true>;
+        case key(FLUX_SYN, 8, true): return vag_flux_fit_rows_kernel<FLUX_SYN, 8, true>;
+        case key(FLUX_SYN_IC, 4, false): return vag_flux_fit_rows_kernel<FLUX_SYN_IC, 4>;
+        case key(FLUX_SYN_IC, 8, false): return vag_flux_fit_rows_kernel<FLUX_SYN_IC, 8>;
+        case key(FLUX_SYN_IC, 4, true): return vag_flux_fit_rows_kernel<FLUX_SYN_IC, 4, true>;
+        case key(FLUX_SYN_IC, 8, true): return vag_flux_fit_rows_kernel<FLUX_SYN_IC, 8, true>;
+        case key(FLUX_SSC, 4, false): return vag_flux_fit_rows_kernel<FLUX_SSC, 4>;
+        case key(FLUX_SSC, 8, false): return vag_flux_fit_rows_kernel<FLUX_SSC, 8>;
+        case key(FLUX_SSC, 4, true): return vag_flux_fit_rows_kernel<FLUX_SSC, 4, true>;
+        case key(FLUX_SSC, 8, true): return vag_flux_fit_rows_kernel<FLUX_SSC, 8, true>;
+        case key(FLUX_SYN, 4, false, true): return vag_flux_fit_rows_kernel<FLUX_SYN, 4, false, true>;
+    }
+    return nullptr;
+}
+
+// vag_flux_series_kernel<mode, spread, points per lane, grid>: the 15 variants series_plan can give
+static SeriesKernel series_kernel(const SeriesVariant& v) {
+    constexpr int N = SERIES_MAX_SLOTS;
+    constexpr auto key = [](int mode, bool spread, int slots, bool grid = false) {
+        return mode | (spread ? 4 : 0) | (slots == 1 ? 8 : 0) | (grid ? 16 : 0);
+    };
+    switch (key(v.mode, v.spread, v.slots, v.grid)) {
+        case key(FLUX_SYN, false, 1): return vag_flux_series_kernel<FLUX_SYN, false, 1>;
+        case key(FLUX_SYN, false, N): return vag_flux_series_kernel<FLUX_SYN, false, N>;
+        case key(FLUX_SYN, true, 1): return vag_flux_series_kernel<FLUX_SYN, true, 1>;
+        case key(FLUX_SYN, true, N): return vag_flux_series_kernel<FLUX_SYN, true, N>;
+        case key(FLUX_SYN_IC, false, 1): return vag_flux_series_kernel<FLUX_SYN_IC, false, 1>;
+        case key(FLUX_SYN_IC, false, N): return vag_flux_series_kernel<FLUX_SYN_IC, false, N>;
+        case key(FLUX_SYN_IC, true, 1): return vag_flux_series_kernel<FLUX_SYN_IC, true, 1>;
+        case key(FLUX_SYN_IC, true, N): return vag_flux_series_kernel<FLUX_SYN_IC, true, N>;
+        case key(FLUX_SSC, false, 1): return vag_flux_series_kernel<FLUX_SSC, false, 1>;
+        case key(FLUX_SSC, false, N): return vag_flux_series_kernel<FLUX_SSC, false, N>;
+        case key(FLUX_SSC, true, 1): return vag_flux_series_kernel<FLUX_SSC, true, 1>;
+        case key(FLUX_SSC, true, N): return vag_flux_series_kernel<FLUX_SSC, true, N>;
+        case key(FLUX_SYN, false, N, true): return vag_flux_series_kernel<FLUX_SYN, false, N, true>;
+        case key(FLUX_SYN_IC, false, N, true): return vag_flux_series_kernel<FLUX_SYN_IC, false, N, true>;
+        case key(FLUX_SSC, false, N, true): return vag_flux_series_kernel<FLUX_SSC, false, N, true>;
+    }
+    return nullptr;
 }
 
 int run_flux_series(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_lg2t, const double* d_lg2nu,
@@ -2474,208 +2409,114 @@ int run_flux_series(vag_ctx* c, const vag_model_params* d_params, int nb, const 
     StageScope ps(c, mode == FLUX_SSC ? PS_SSC_FLUX : PS_SYNC_FLUX);
     if (n > SERIES_THREADS * SERIES_MAX_SLOTS)
         return set_err(VAG_E_CAPACITY, "series length %d exceeds %d", n, SERIES_THREADS * SERIES_MAX_SLOTS);
-    // A fit's shape (plain synchrotron, <= 64 points in a few bands): the row-per-lane kernel (vag_fit_rows.h)
-    if (mode != FLUX_FUSED && grid_nt == 0 && n <= FITROWS_MAX_POINTS && n_bands > 0 &&
-        n_bands <= FITROWS_BANDS && !vag_hook("VAG_SERIES_ROW_PER_WAVE")) {
-        const int max_blocks = std::max(1, (c->max_pairs + FITROWS_ROWS - 1) / FITROWS_ROWS);
-        if (c->d_partial.ensure(sizeof(double) * (size_t)nb * max_blocks * FITROWS_SEGS * n)) return VAG_E_HIP;
-        SeriesArgs a{};
-        a.params = d_params;
-        a.meta = c->d_meta.as<VagGridMeta>();
-        a.geo_th = c->d_geo_th.as<double>();
-        a.geo_ph = c->d_geo_ph.as<double>();
-        a.g_rep_of = c->d_rep_of.as<int>();
-        a.lay = Layout{c->d_row_off.as<int>(), c->d_cell_off.as<long long>()};
-        a.cellpar = c->d_cellpar.as<double>();
-        a.lg2_t_obs = d_lg2t;
-        a.lg2_nu_obs = d_lg2nu;
-        a.n = n;
+    const FluxBatch batch = flux_batch(c, nb);
+    const FluxHooks hooks = flux_hooks();
+    const bool debug = vag_hook("VAG_DEBUG_LAUNCH") != nullptr;
+    SeriesArgs a{};
+    bind_batch(a, c, d_params);
+    bind_layout(a, c);
+    a.lg2_t_obs = d_lg2t;
+    a.lg2_nu_obs = d_lg2nu;
+    a.n = n;
+    a.band_idx = c->d_bandidx.as<int>();
+    a.band_first = c->d_bandidx.as<int>() + FITROWS_MAX_POINTS;
+    // A fit's shape (plain synchrotron, <= 512 points in a few bands): the row-per-lane kernel (vag_fit_rows.h)
+    if (fit_rows_takes(hooks, mode, grid_nt, n, n_bands)) {
+        const FitRowsPlan p = fit_rows_plan(batch, hooks, mode, n_bands);
+        if (c->d_partial.ensure(sizeof(double) * (size_t)nb * p.max_blocks * FITROWS_SEGS * n)) return VAG_E_HIP;
         a.pairs_per_block = FITROWS_ROWS;
-        a.max_blocks = max_blocks;
-        a.max_chunks = max_blocks * FITROWS_SEGS;  // one partial sum per (block of 64 rows, lattice segment)
+        a.max_blocks = p.max_blocks;
+        a.max_chunks = p.max_blocks * FITROWS_SEGS;  // one partial sum per (block of 64 rows, lattice segment)
         a.chunk = FITROWS_ROWS;
         a.partial = c->d_partial.as<double>();
-        a.sp_table = c->d_sptab.as<double>();
         a.n_bands = n_bands;
-        a.band_idx = c->d_bandidx.as<int>();
-        a.band_first = c->d_bandidx.as<int>() + FITROWS_MAX_POINTS;
-        a.cellq = c->d_cellq.as<double>();
-        a.ichdr = c->d_ichdr.as<double>();
-        a.icpool = c->d_icpool.as<double>();
-        a.ic_status = c->d_icstatus.as<int>();
         // (+=: a call with several series passes or chunks reports all of them; the plan is reset by the model stage of the call)
         const long long upper_evals = 2 * c->total_pairs * (long long)n, upper_interps = c->total_pairs * (long long)n;
         c->plan.spec_evals += upper_evals;
         c->plan.interps += upper_interps;
-        c->plan.flux_blocks = max_blocks * nb;
+        c->plan.flux_blocks = p.max_blocks * nb;
         c->plan.pairs_per_block = FITROWS_ROWS;
         if (c->n_rows > 0) {
-            // wavefronts per block of 64 rows: four while the batch leaves the GPU room (each walks a quarter of the lattice),
-            // one when there are blocks enough to fill it (one prologue per block).  The partial sums are the same either way.
-            const long long blocks = (c->total_pairs + FITROWS_ROWS - 1) / FITROWS_ROWS;
-            int wpb = blocks <= 1024 ? 4 : (blocks <= 4608 ? 2 : 1);  // measured (persistent launch, 4 / 2 / 1): 0.8 k blocks 0.072 / 0.088 / 0.140 ms, 1.6 k 0.115 / 0.105 / 0.142, 6.2 k 0.333 / 0.267 / 0.269
-            if (const char* e = vag_hook("VAG_FIT_WAVES_PER_BLOCK")) wpb = std::atoi(e) == 4 ? 4 : (std::atoi(e) == 2 ? 2 : 1);
-            a.grid_nt = wpb;
+            a.grid_nt = p.waves_per_block;
             a.nb = nb;
             a.work = work_counters(c);
-            // persistent workgroups: as many as the GPU holds (three per CU), fewer when there are fewer items (blocks x wavefronts per block)
-            const long long items = (blocks + nb) * wpb;  // (total_pairs may be the previous call's: every model can own one block more)
-            const int wgs = (int)std::max<long long>(1, std::min<long long>((items + FITROWS_WAVES - 1) / FITROWS_WAVES, 3LL * c->n_cus));
-            const dim3 g(wgs), b(SERIES_THREADS * FITROWS_WAVES);
             const size_t lds = fit_rows_lds_bytes(n);
-            const bool spread = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
-            a.cellgeo = c->d_cellgeo.as<double>();
-            // vag_ctx_count_work: the tallying instantiation (plain synchrotron, <= 4 bands, no spreading: the walker metric's case)
-            const bool tally = c->count_work && mode == FLUX_SYN && !spread && n_bands <= 4;
-            if (vag_hook("VAG_DEBUG_LAUNCH"))
+            const SeriesKernel kernel = fit_rows_kernel(p.v);
+            if (!kernel) return set_err(VAG_E_INVALID, "no fit rows kernel for mode %d", mode);
+            if (debug)
                 std::fprintf(stderr, "[vag] fit rows launch: mode %d n=%d bands=%d blocks=%lld waves/block=%d spreading=%d lds=%zu B\n", mode, n,
-                             n_bands, blocks, wpb, (int)spread, lds);
-            if (tally) {
+                             n_bands, p.blocks, p.waves_per_block, (int)batch.spreading, lds);
+            if (p.v.tally) {  // vag_ctx_count_work
                 if (c->d_workcount.ensure(2 * sizeof(unsigned long long))) return VAG_E_HIP;
                 HIPCHK(hipMemsetAsync(c->d_workcount.p, 0, 2 * sizeof(unsigned long long), st));
                 a.tally = c->d_workcount.as<unsigned long long>();
-                hipLaunchKernelGGL((vag_flux_fit_rows_kernel<FLUX_SYN, 4, false, true>), g, b, lds, st, a);
-                HIPCHK(hipGetLastError());
+            }
+            hipLaunchKernelGGL(kernel, dim3(p.workgroups), dim3(SERIES_THREADS * FITROWS_WAVES), lds, st, a);
+            HIPCHK(hipGetLastError());
+            if (p.v.tally) {
                 unsigned long long hcount[2] = {0, 0};
                 HIPCHK(hipMemcpyAsync(hcount, c->d_workcount.p, sizeof hcount, hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
                 c->plan.spec_evals += (long long)hcount[0] - upper_evals;  // the tallied counts replace this pass's upper bounds
                 c->plan.interps += (long long)hcount[1] - upper_interps;
-            } else
-#define VAG_FIT_LAUNCH(M_)                                                                      \
-    do {                                                                                        \
-        if (spread && n_bands <= 4)                                                             \
-            hipLaunchKernelGGL((vag_flux_fit_rows_kernel<M_, 4, true>), g, b, lds, st, a);       \
-        else if (spread)                                                                        \
-            hipLaunchKernelGGL((vag_flux_fit_rows_kernel<M_, 8, true>), g, b, lds, st, a);       \
-        else if (n_bands <= 4)                                                                  \
-            hipLaunchKernelGGL((vag_flux_fit_rows_kernel<M_, 4>), g, b, lds, st, a);             \
-        else                                                                                    \
-            hipLaunchKernelGGL((vag_flux_fit_rows_kernel<M_, 8>), g, b, lds, st, a);             \
-    } while (0)
-            {
-            if (mode == FLUX_SYN_IC)
-                VAG_FIT_LAUNCH(FLUX_SYN_IC);
-            else if (mode == FLUX_SYN)
-                VAG_FIT_LAUNCH(FLUX_SYN);
-            else
-                VAG_FIT_LAUNCH(FLUX_SSC);
             }
-#undef VAG_FIT_LAUNCH
-            HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(c->ev[4], st));
         hipLaunchKernelGGL(vag_series_reduce_kernel, dim3((n + 63) / 64, nb), dim3(256), 0, st, d_params, c->d_meta.as<VagGridMeta>(),
-                           c->d_partial.as<double>(), max_blocks * FITROWS_SEGS, FITROWS_ROWS, n, d_out, FITROWS_SEGS, work_counters(c));
+                           c->d_partial.as<double>(), p.max_blocks * FITROWS_SEGS, FITROWS_ROWS, n, d_out, FITROWS_SEGS, work_counters(c));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev[5], st));
         return VAG_OK;
     }
-    // series work per (theta, phi) row is small: fewer, longer wavefronts as the batch grows.  The partial sums are kept per
-    // SERIES_CHUNK rows whatever this choice is, so a model's result does not depend on what else is in the batch (a walker
-    // scores the same bits alone, in a block of 64, or among 1024).
-    long long ppb = std::max<long long>(SERIES_CHUNK, (c->total_pairs + 32767) / 32768);
-    ppb = (ppb + SERIES_CHUNK - 1) / SERIES_CHUNK * SERIES_CHUNK;
-    if (const char* e = vag_hook("VAG_SERIES_PPB")) ppb = std::max(1, std::atoi(e)) * SERIES_CHUNK;  // tuning override (in chunks)
-    const int max_blocks = std::max(1, (int)((c->max_pairs + ppb - 1) / ppb));
-    // a small (nu, t) grid served by this kernel keeps one partial per wavefront (its 128 x 128 rows would need thousands of
-    // 8-row chunks per model); a grid request makes no batch-independence promise, as the workgroup kernel does not either
-    const int chunk = grid_nt > 0 ? (int)ppb : SERIES_CHUNK;
-    const int max_chunks = std::max(1, (c->max_pairs + chunk - 1) / chunk);
-    if (c->d_partial.ensure(sizeof(double) * (size_t)nb * max_chunks * n)) return VAG_E_HIP;
-    const int ks = flux_ks(c);
-    if (n > SERIES_THREADS && grid_nt == 0) n_bands = 0;  // a fit's shared-node path keeps one point per lane
+    const SeriesPlan p = series_plan(batch, hooks, mode, n, n_bands, grid_nt);
+    if (c->d_partial.ensure(sizeof(double) * (size_t)nb * p.max_chunks * n)) return VAG_E_HIP;
+    const int ks = flux_ks(batch, hooks);
     // wavefronts per workgroup: four when their private rows fit next to the shared tables, else two or one
     auto lds_for = [&](int w) {
-        return sizeof(double) * ((size_t)w * series_region_doubles(ks, mode == FLUX_SYN_IC, n_bands) + SP_LDS_DOUBLES + SERIES_MAX_BANDS);
+        return sizeof(double) * ((size_t)w * series_region_doubles(ks, mode == FLUX_SYN_IC, p.n_bands) + SP_LDS_DOUBLES + SERIES_MAX_BANDS);
     };
-    // the workgroup shape that keeps the most wavefronts resident on a CU (each workgroup carries one copy of the tables);
-    // ties go to the smaller workgroup
-    // (the runtime's occupancy query decides what fits: two 80 KB workgroups do not share a CU's 160 KB)
-    int waves = 1, best = 0;
-    for (int w = 1; w <= SERIES_WAVES; w <<= 1) {
-        if (lds_for(w) > 160 * 1024) break;
-        const int resident = std::min(series_wg_per_cu(c, w, lds_for(w)) * w, 16);
-        if (resident >= best) best = resident, waves = w;
-    }
-    if (const char* e = vag_hook("VAG_SERIES_WAVES")) waves = std::max(1, std::min(SERIES_WAVES, std::atoi(e)));
+    // (the runtime's occupancy query decides what fits: two 80 KB workgroups do not share a CU's 160 KB.  The figure is the one of
+    // <FLUX_SYN, false, 1> whatever variant is launched, as it was measured with)
+    const void* const occ_fn = reinterpret_cast<const void*>(vag_flux_series_kernel<FLUX_SYN, false, 1>);
+    auto occ_for = [&](int w) {
+        const int wg = wg_per_cu(c, occ_fn, SERIES_THREADS * w, lds_for(w));
+        return wg < 0 ? (int)((144 * 1024) / std::max<size_t>(lds_for(w), 1)) : wg;
+    };
+    int wg[3] = {-1, -1, -1};
+    for (int i = 0; i < 3 && lds_for(1 << i) <= CU_LDS_BYTES; ++i) wg[i] = occ_for(1 << i);
+    const int waves = series_waves(hooks, wg);
     const size_t lds = lds_for(waves);
-    if (lds > 160 * 1024) return set_err(VAG_E_CAPACITY, "LDS request %zu B exceeds 160 KiB (n_t=%d)", lds, ks);
-    const dim3 sgrid((max_blocks + waves - 1) / waves, nb), sblock(SERIES_THREADS * waves);
-    if (vag_hook("VAG_DEBUG_LAUNCH")) {
-        int occ = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vag_flux_series_kernel<FLUX_SYN, false, 1>, SERIES_THREADS * waves, lds);
+    if (lds > CU_LDS_BYTES) return set_err(VAG_E_CAPACITY, "LDS request %zu B exceeds 160 KiB (n_t=%d)", lds, ks);
+    const dim3 sgrid((p.max_blocks + waves - 1) / waves, nb), sblock(SERIES_THREADS * waves);
+    if (debug)
         std::fprintf(stderr, "[vag] series launch: n=%d bands=%d max_k=%d rows/wave=%lld waves/wg=%d lds=%zu B grid=(%u,%u) wg/CU=%d\n", n,
-                     n_bands, ks, ppb, waves, lds, sgrid.x, sgrid.y, occ);
-    }
-    SeriesArgs a{};
-    a.cellq = c->d_cellq.as<double>();
-    a.ichdr = c->d_ichdr.as<double>();
-    a.icpool = c->d_icpool.as<double>();
-    a.ic_status = c->d_icstatus.as<int>();
-    a.cellgeo = c->d_cellgeo.as<double>();
-    a.n_bands = n_bands;
+                     p.n_bands, ks, p.ppb, waves, lds, sgrid.x, sgrid.y, wg_per_cu(c, occ_fn, SERIES_THREADS * waves, lds));
+    a.n_bands = p.n_bands;
     a.grid_nt = grid_nt;
-    a.chunk = chunk;
-    a.band_idx = c->d_bandidx.as<int>();
-    a.band_first = c->d_bandidx.as<int>() + FITROWS_MAX_POINTS;
-    const bool spreading = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
-    a.params = d_params;
-    a.meta = c->d_meta.as<VagGridMeta>();
-    a.geo_th = c->d_geo_th.as<double>();
-    a.geo_ph = c->d_geo_ph.as<double>();
-    a.g_rep_of = c->d_rep_of.as<int>();
-    a.lay = Layout{c->d_row_off.as<int>(), c->d_cell_off.as<long long>()};
-    a.cellpar = c->d_cellpar.as<double>();
-    a.lg2_t_obs = d_lg2t;
-    a.lg2_nu_obs = d_lg2nu;
-    a.n = n;
-    a.pairs_per_block = (int)ppb;
-    a.max_blocks = max_blocks;
-    a.max_chunks = max_chunks;
+    a.chunk = p.chunk;
+    a.pairs_per_block = (int)p.ppb;
+    a.max_blocks = p.max_blocks;
+    a.max_chunks = p.max_chunks;
     a.k_stride = ks;
     a.partial = c->d_partial.as<double>();
-    a.sp_table = c->d_sptab.as<double>();
     c->plan.spec_evals = 2 * c->total_pairs * (long long)n;
     c->plan.interps = c->total_pairs * (long long)n;
-    c->plan.flux_blocks = max_blocks * nb;
-    c->plan.pairs_per_block = (int)ppb;
+    c->plan.flux_blocks = p.max_blocks * nb;
+    c->plan.pairs_per_block = (int)p.ppb;
     if (c->n_rows > 0) {
-        const bool one = n <= SERIES_THREADS;  // one data point per lane
-#define VAG_SERIES_LAUNCH(M_, S_)                                                                              \
-    do {                                                                                                       \
-        if (grid_nt > 0)                                                                                       \
-            hipLaunchKernelGGL((vag_flux_series_kernel<M_, false, SERIES_MAX_SLOTS, true>), sgrid, sblock, lds, st, a); \
-        else if (one)                                                                                          \
-            hipLaunchKernelGGL((vag_flux_series_kernel<M_, S_, 1>), sgrid, sblock, lds, st, a);                 \
-        else                                                                                                   \
-            hipLaunchKernelGGL((vag_flux_series_kernel<M_, S_, SERIES_MAX_SLOTS>), sgrid, sblock, lds, st, a);  \
-    } while (0)
-        if (spreading && mode == FLUX_SYN_IC)
-            VAG_SERIES_LAUNCH(FLUX_SYN_IC, true);
-        else if (spreading && mode == FLUX_SSC)
-            VAG_SERIES_LAUNCH(FLUX_SSC, true);
-        else if (spreading)
-            VAG_SERIES_LAUNCH(FLUX_SYN, true);
-        else if (mode == FLUX_SYN_IC)
-            VAG_SERIES_LAUNCH(FLUX_SYN_IC, false);
-        else if (mode == FLUX_SSC)
-            VAG_SERIES_LAUNCH(FLUX_SSC, false);
-        else
-            VAG_SERIES_LAUNCH(FLUX_SYN, false);
-#undef VAG_SERIES_LAUNCH
+        const SeriesKernel kernel = series_kernel(p.v);
+        if (!kernel) return set_err(VAG_E_INVALID, "no series kernel for mode %d", mode);
+        hipLaunchKernelGGL(kernel, sgrid, sblock, lds, st, a);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(c->ev[4], st));
     hipLaunchKernelGGL(vag_series_reduce_kernel, dim3((n + 63) / 64, nb), dim3(256), 0, st, d_params,
-                       c->d_meta.as<VagGridMeta>(), c->d_partial.as<double>(), max_chunks, chunk, n, d_out, 1);
+                       c->d_meta.as<VagGridMeta>(), c->d_partial.as<double>(), p.max_chunks, p.chunk, n, d_out, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev[5], st));
     return VAG_OK;
 }
 
-// One chunk of a (t, nu) series for the batch: the sum of every enabled component -> d_out[nb][n].  The comoving band
-// of an SSC table spans ALL requested frequencies (d_lg2nu_all[n_all], pymodel.h:896-909), not only this chunk's.
 // One chunk of a (t, nu) series for the batch.  d_out (optional) [nb][n] receives the sum of every enabled component in
 // PyFlux::calc_total order; d_comp (optional) -> d_comp[i] != nullptr receives component i of {fwd.sync, fwd.ssc, rvs.sync,
 // rvs.ssc} [nb][n], zeros when that component is disabled.
@@ -2748,10 +2589,6 @@ int collect_times(vag_ctx* c) {
     c->times.total_ms = v;
     return VAG_OK;
 }
-
-}  // namespace
-static int collect_times_fwd(vag_ctx* c) { return collect_times(c); }
-namespace {
 
 int prep_times(vag_ctx* c, const double* d_t, int nt, const double* d_nu, int nnu) {
     if (c->d_lg2t.ensure(sizeof(double) * nt)) return VAG_E_HIP;
@@ -2898,6 +2735,15 @@ static int run_flag_groups(const vag_model_params* params, int nb, const std::ve
 }
 
 extern "C" {
+
+int vag_last_stage_times(vag_ctx* c, vag_stage_times* out) {
+    ApiLock api_lock(c);
+    if (!c || !out) return set_err(VAG_E_INVALID, "null context or output");
+    // measured with HIP events recorded on the context stream around each kernel of the last batch call
+    const int rc = collect_times(c);
+    *out = c->times;
+    return rc;
+}
 
 }  // extern "C"
 

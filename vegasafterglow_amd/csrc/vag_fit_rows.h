@@ -25,11 +25,7 @@
 
 namespace vag {
 
-constexpr int FITROWS_WAVES = 4;   // wavefronts per workgroup (they only share the tables and the data points)
-constexpr int FITROWS_BANDS = 8;   // distinct frequencies handled (instantiations for <= 4 and <= 8; more: vag_flux_series_kernel)
-constexpr int FITROWS_MAX_POINTS = 512;  // data points of a pass (SERIES_THREADS * SERIES_MAX_SLOTS)
-constexpr int FITROWS_ROWS = 64;   // rows per block = lanes of a wavefront
-constexpr int FITROWS_SEGS = 4;    // lattice segments per block: each (block, segment) is one partial sum of the model's tree
+// (FITROWS_WAVES, _BANDS, _MAX_POINTS, _ROWS, _SEGS: vag_flux_limits.h)
 #ifndef VAG_FITROWS_STRIPES
 #define VAG_FITROWS_STRIPES 4
 #endif

@@ -17,16 +17,7 @@
 
 namespace vag {
 
-#ifndef VAG_GRIDROWS_WAVES
-#define VAG_GRIDROWS_WAVES 4
-#endif
-constexpr int GRIDROWS_WAVES = VAG_GRIDROWS_WAVES;
-constexpr int GRIDROWS_BANDS = 4;     // frequencies
-#ifndef VAG_GRIDROWS_MAX_NT
-#define VAG_GRIDROWS_MAX_NT 128
-#endif
-constexpr int GRIDROWS_MAX_NT = VAG_GRIDROWS_MAX_NT;  // requested times
-constexpr int GRIDROWS_MAX_SLOTS = 512;
+// (GRIDROWS_WAVES, _BANDS, _MAX_NT, _MAX_SLOTS, the first and third from -DVAG_GRIDROWS_WAVES / -DVAG_GRIDROWS_MAX_NT: vag_flux_limits.h)
 
 // (Build option VAG_ROWS_RING=1, measured slower and off by default -- DESIGN.md 4h.)  With it the interpolation work of a wavefront
 // goes through a RING of items in LDS: a lane pushes {the four exponents of one requested

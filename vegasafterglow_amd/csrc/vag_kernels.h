@@ -3,6 +3,7 @@
 #include "vag_device.h"
 #include "vag_grid_kernel.h"
 #include "vag_dyn_fast.h"
+#include "vag_flux_limits.h"  // FLUX_*, SERIES_*: the limits the host's launch decisions read too
 
 namespace vag {
 
@@ -678,9 +679,7 @@ vag_cells_kernel(const vag_model_params* __restrict__ params, int nb, const VagG
 // Each lane owns fixed (idx, l) output slots, so the (phi, theta) sum needs no cross-lane reduction; a
 // workgroup writes one partial grid, reduced deterministically by vag_reduce_kernel.
 // ------------------------------------------------------------------------------------------------
-constexpr int FLUX_THREADS = 512;
-constexpr int FLUX_MAX_SLOTS = 8192;  // (l, idx) output slots per launch, accumulated in LDS  // (l, idx) slots per lane: nt * nnu <= FLUX_THREADS * FLUX_MAX_SLOTS
-
+// (FLUX_THREADS, FLUX_MAX_SLOTS and the FLUX_SYN ... FLUX_FUSED photon sources: vag_flux_limits.h)
 struct FluxArgs {
     const vag_model_params* params;
     const VagGridMeta* meta;
@@ -714,12 +713,6 @@ struct FluxArgs {
 };
 
 constexpr int ROWGEO_HDR = VAG_ROWGEO_HDR;  // row-geometry records of a model: written by vag_grid_kernel (vag_grid_kernel.h), layout there
-
-// photon source of the flux kernels
-constexpr int FLUX_SYN = 0;     // synchrotron, no inverse-Compton cooling
-constexpr int FLUX_SYN_IC = 1;  // synchrotron with the IC correction above nu_c
-constexpr int FLUX_SSC = 2;     // SSC tables
-constexpr int FLUX_FUSED = 3;   // FLUX_SYN_IC and FLUX_SSC in one pass: EAT logs, bracket search and barriers paid once
 
 template <class P1, class P2, class Tab>
 VAG_DEV double log2_I_nu_ic(const P1 c, int st, const P2 qv, int qst, const SpecConst& sc, double lg2_nu, Tab sp);
@@ -1499,11 +1492,7 @@ vag_flux_grid_kernel(FluxArgs a) {
 // Every (nu, t) sum receives the addends of flux_grid_item in its row order: the partial grids are bitwise the same.
 // Team sizes: measured at 6 + 2, 5 + 3 and 4 + 4 (profiles/flux_split_ab.txt); a row's ~855 boundary items are 14 wavefront
 // passes, so of six A wavefronts the first two make three passes and the others two.
-constexpr int FLUX_SPLIT_A = 6;                                     // wavefronts 0 .. FLUX_SPLIT_A - 1: A team
-constexpr int FLUX_SPLIT_B = FLUX_THREADS / 64 - FLUX_SPLIT_A;      // the rest: B team
-constexpr int FLUX_SPLIT_TIMES = 2;                                 // requested times a B lane can own
-constexpr int FLUX_SPLIT_MAX_NT = FLUX_SPLIT_TIMES * FLUX_SPLIT_B * 64;
-constexpr int FLUX_SPLIT_MAX_NNU = 10;                              // accumulators per owned time
+// (FLUX_SPLIT_A, _B, _TIMES, _MAX_NT, _MAX_NNU: vag_flux_limits.h)
 // The EAT step of row p + 2 is taken by the LAST two A wavefronts, behind their spectra: they have a pass less to make, the EAT
 // chains fill the gap, and the B team keeps the interval for its interpolation (on the B team the same split lost).
 constexpr int FLUX_SPLIT_E = 2;                                     // wavefronts of the EAT step
@@ -1887,11 +1876,7 @@ vag_reduce_grid_kernel(const vag_model_params* __restrict__ params, const VagGri
 // (row, point).  Sharing of boundary values between equal-frequency runs in the reference changes cost,
 // not values.  Output partial[m][block][n].
 // ------------------------------------------------------------------------------------------------
-constexpr int SERIES_THREADS = 64;    // lanes that share one (theta, phi) row: ONE wavefront, so rows need no block barrier
-constexpr int SERIES_WAVES = 4;       // most independent wavefronts per workgroup (the host picks 4, 2 or 1 by what stays resident); they only share the tables
-constexpr int SERIES_MAX_SLOTS = 8;   // data points per lane: n <= 512
-constexpr int SERIES_CHUNK = 8;       // (theta, phi) rows per partial sum: the unit of a model's summation tree, whatever the batch
-constexpr int SERIES_MAX_BANDS = 8;   // distinct frequencies the shared-node path handles
+// (SERIES_THREADS, _WAVES, _MAX_SLOTS, _CHUNK, _MAX_BANDS: vag_flux_limits.h)
 // doubles of LDS one series wavefront owns (kept even: the cell blocks are read with 16-byte loads)
 __host__ __device__ inline int series_region_doubles(int ks, bool ic, int n_bands) {
     (void)ic;  // the IC-correction constants are read from L2, not staged
