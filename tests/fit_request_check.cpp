@@ -4,8 +4,11 @@
 // Every scan lays out one accepted spec at the smallest shapes that reach every branch of its layout arithmetic; the offsets of its
 // *Layout and every staged double and int32 are compared with what this file writes down from the documented layout, not with anything
 // the scan computed.  Every input array lives on the heap at exactly its advertised length, so a read one element past it is an
-// AddressSanitizer report.  Then two requests through fit_request_prepare, and one refusal per scan.  One "ok <case>" line per case.
+// AddressSanitizer report.  The four blocks that are hashed in place (fit, sky, pol, vis) are filled into a heap buffer of exactly the
+// scan's size; their hashes are compared across equal and changed content, and every one of their refusals is reached with its text.
+// Then two requests through fit_request_prepare, and one refusal per scan.  One "ok <case>" line per case.
 #include <cstdio>
+#include <functional>
 #include <initializer_list>
 #include <memory>
 
@@ -39,6 +42,10 @@ struct Want {
     std::vector<double> v;
     Want& d(std::initializer_list<double> x) {
         v.insert(v.end(), x);
+        return *this;
+    }
+    Want& z(size_t n) {  // n doubles of zeros
+        v.resize(v.size() + n, 0.0);
         return *this;
     }
     Want& i(std::initializer_list<int32_t> x) {
@@ -316,6 +323,399 @@ static void check_cov() {
     done("cov_scan layout", before);
 }
 
+// ---- the four blocks hashed in place (fit, sky, pol, vis): the scan's offsets and size, then the miss half's fill into a heap buffer of
+//      exactly that size, against the documented layout; the hashes; every refusal with its text
+template <class T>
+static T* heap_v(const std::vector<T>& v) {  // a heap copy of exactly these elements, for the caller to change
+    T* p = new T[v.size()];
+    std::copy(v.begin(), v.end(), p);
+    g_keep.emplace_back(p, [](void* q) { delete[] static_cast<T*>(q); });
+    return p;
+}
+template <class T>
+static T* own(const T*& p, size_t n) {  // re-seats p on a copy of its n elements and hands the copy out
+    T* q = heap_v(std::vector<T>(p, p + n));
+    p = q;
+    return q;
+}
+static std::vector<double> ramp(size_t n, double first) {  // first, first + 1, ...
+    std::vector<double> v(n);
+    for (size_t i = 0; i < n; ++i) v[i] = first + (double)i;
+    return v;
+}
+static Want& operator+=(Want& w, const std::vector<double>& x) {
+    w.v.insert(w.v.end(), x.begin(), x.end());
+    return w;
+}
+static bool sizes(const std::vector<size_t>& got, std::initializer_list<size_t> want) { return got == std::vector<size_t>(want); }
+
+// 3 point rows (odd), two band groups of 2 and 3 rows, two free parameters with priors
+static vag_fit_spec fit_full(bool with_ext, int n_point = 3) {
+    vag_fit_spec s{};
+    s.ndim = 2, s.slot[0] = 0, s.slot[1] = 1, s.is_log[0] = 1;
+    if ((s.n_data = n_point)) {
+        s.t = D({1e5, 2e5, 3e5}), s.nu = D({1e9, 2e9, 3e9}), s.ln_flux = D({-60.0, -61.0, -62.0}), s.ln_err = D({0.1, 0.2, 0.3});
+        s.weight = D({1.0, 0.5, 0.25});
+        if (with_ext) s.ext_kernel = D({0.7, 0.8, 0.9});
+    }
+    vag_band_obs b0{}, b1{};
+    b0.n = 2, b0.t = D({1e4, 2e4}), b0.ln_flux = D({-50.0, -51.0}), b0.ln_err = D({0.01, 0.02}), b0.weight = D({1.0, 2.0});
+    b1.n = 3, b1.t = D({1e4, 1e4, 3e4}), b1.ln_flux = D({-52.0, -53.0, -54.0}), b1.ln_err = D({0.03, 0.04, 0.05}), b1.weight = D({3.0, 4.0, 5.0});
+    s.n_bands = 2;
+    s.bands = heap<vag_band_obs>({b0, b1});
+    s.use_priors = 1;
+    s.lower[0] = 0.1, s.lower[1] = -1.0, s.upper[0] = 1.0, s.upper[1] = 2.0;
+    s.prior_kind[0] = VAG_PRIOR_LOG_UNIFORM, s.prior_kind[1] = VAG_PRIOR_GAUSSIAN;
+    s.prior_a[0] = 0.1, s.prior_a[1] = 0.5, s.prior_b[0] = 1.0, s.prior_b[1] = 0.25;
+    return s;
+}
+
+static Want& fit_tail(Want& w) {  // the band groups and the prior block of fit_full
+    w.d({1e4, 2e4, -50.0, -51.0, 0.01, 0.02, 1.0, 2.0}).d({1e4, 1e4, 3e4, -52.0, -53.0, -54.0, 0.03, 0.04, 0.05, 3.0, 4.0, 5.0});
+    w.d({0.1, -1.0}).z(14).d({1.0, 2.0}).z(14).d({0.1, 0.5}).z(14).d({1.0, 0.25}).z(14);  // lower | upper | prior_a | prior_b
+    return w.i({0, 1}).z(7).i({1, 0}).z(7).i({VAG_PRIOR_LOG_UNIFORM, VAG_PRIOR_GAUSSIAN}).z(7);  // slot | is_log | prior_kind
+}
+
+static std::vector<double> filled(size_t n, const std::function<void(double*)>& fill) {
+    std::vector<double> got(n, NAN);  // (exactly the scan's size: a write past it is a report; NAN: a double the fill leaves is seen)
+    fill(got.data());
+    return got;
+}
+
+static void check_fit() {
+    const int before = g_failed;
+    FitLayout lay;
+    for (const bool with_ext : {true, false}) {
+        const vag_fit_spec s = fit_full(with_ext);
+        CHECK(fit_scan(&s, 2, FitAccepts{}, lay) == VAG_OK && fit_rows(&s) == VAG_OK);
+        // the point block 6 * 3 = 18, band group 0 at 18 (4 * 2), band group 1 at 26 (4 * 3), the priors at 38, then 64 + 24
+        CHECK(lay.nu == 3 && lay.ln_flux == 6 && lay.ln_err == 9 && lay.weight == 12 && lay.ext == 15);
+        CHECK(sizes(lay.band, {18, 26}) && lay.prior == 38 && lay.doubles == 126);
+        Want w;
+        w.d({1e5, 2e5, 3e5, 1e9, 2e9, 3e9, -60.0, -61.0, -62.0, 0.1, 0.2, 0.3, 1.0, 0.5, 0.25});
+        with_ext ? w.d({0.7, 0.8, 0.9}) : w.z(3);
+        CHECK(same_bytes(filled(lay.doubles, [&](double* hp) { fit_fill(&s, lay, hp); }), fit_tail(w)));
+    }
+    const vag_fit_spec s = fit_full(false, 0);  // no point row: the point block is 6 * max(n, 1) = 6 doubles of zeros
+    CHECK(fit_scan(&s, 2, FitAccepts{}, lay) == VAG_OK && fit_rows(&s) == VAG_OK);
+    CHECK(sizes(lay.band, {6, 14}) && lay.prior == 26 && lay.doubles == 114);
+    Want w;
+    const std::vector<double> got = filled(lay.doubles, [&](double* hp) { fit_fill(&s, lay, hp); });
+    CHECK(same_bytes(got, fit_tail(w.z(6))));
+    CHECK(ints_at(got, 26 + 64, {0, 1, 0, 0}) && ints_at(got, 26 + 64 + 8, {1, 0}) && ints_at(got, 26 + 64 + 16, {2, 1}));  // three int32[16]
+    // the accepted slots
+    vag_fit_spec a = fit_full(true);
+    a.slot[0] = VAG_P_SKY_EAST0, a.slot[1] = VAG_P_TMPL_AMP0 + 1;
+    FitAccepts acc;
+    acc.sky = true, acc.n_templates = 2;
+    CHECK(fit_scan(&a, 2, acc, lay) == VAG_OK);
+    a.n_data = a.n_bands = 0;  // no flux row at all: data only through another block
+    acc.counts = true;
+    CHECK(fit_scan(&a, 2, acc, lay) == VAG_OK && lay.prior == 6 && lay.doubles == 94);
+    done("fit block layout", before);
+}
+
+static vag_sky_fit_spec sky_full() {  // two centroid groups of 1 and 2 epochs
+    vag_centroid_obs a{}, b{};
+    a.nu = 5e9, a.n = 1, a.t = D({1e6}), a.east = D({0.1}), a.north = D({0.2}), a.err_east = D({0.01}), a.err_north = D({0.02}), a.weight = D({1.0});
+    b.nu = 8e9, b.n = 2, b.t = D({2e6, 3e6}), b.east = D({0.3, 0.4}), b.north = D({0.5, 0.6}), b.err_east = D({0.03, 0.04});
+    b.err_north = D({0.05, 0.06}), b.weight = D({2.0, 3.0});
+    vag_sky_fit_spec s{};
+    s.n_groups = 2;
+    s.groups = heap<vag_centroid_obs>({a, b});
+    return s;
+}
+
+static void check_sky() {
+    const int before = g_failed;
+    const vag_sky_fit_spec s = sky_full();
+    SkyLayout lay;
+    CHECK(sky_scan(&s, lay) == VAG_OK && sky_rows(&s) == VAG_OK);
+    CHECK(sizes(lay.off, {0, 7}) && lay.doubles == 20);  // per group [nu | six arrays of n]: 1 + 6, then 1 + 12
+    CHECK(same_bytes(filled(lay.doubles, [&](double* hp) { six_fill(&s, lay, hp); }),
+                     Want().d({5e9, 1e6, 0.1, 0.2, 0.01, 0.02, 1.0}).d({8e9, 2e6, 3e6, 0.3, 0.4, 0.5, 0.6, 0.03, 0.04, 0.05, 0.06, 2.0, 3.0})));
+    vag_sky_fit_spec none{};  // no group, a fixed placement: nothing to hold
+    none.pa_fixed = 0.3;
+    CHECK(sky_scan(&none, lay) == VAG_OK && sky_rows(&none) == VAG_OK && lay.off.empty() && lay.doubles == 0);
+    CHECK(filled(0, [&](double* hp) { six_fill(&none, lay, hp); }).empty());
+    done("sky block layout", before);
+}
+
+static vag_pol_fit_spec pol_full() {  // a QU group of 2 epochs, a DEGREE group of 1 epoch without u and err_u
+    vag_polarization_obs a{}, b{};
+    a.nu = 3e9, a.n = 2, a.kind = VAG_POL_QU, a.t = D({1e5, 2e5}), a.q = D({0.1, 0.2}), a.u = D({-0.1, -0.2}), a.err_q = D({0.01, 0.02});
+    a.err_u = D({0.03, 0.04}), a.weight = D({1.0, 2.0});
+    b.nu = 4e9, b.n = 1, b.kind = VAG_POL_DEGREE, b.t = D({3e5}), b.q = D({0.3}), b.err_q = D({0.05}), b.weight = D({3.0});
+    vag_pol_fit_spec p{};
+    p.n_groups = 2;
+    p.groups = heap<vag_polarization_obs>({a, b});
+    return p;
+}
+
+static void check_pol() {
+    const int before = g_failed;
+    const vag_pol_fit_spec p = pol_full();
+    PolLayout lay;
+    CHECK(pol_scan(&p, lay) == VAG_OK && pol_rows(&p) == VAG_OK);
+    CHECK(sizes(lay.off, {0, 13}) && lay.doubles == 20);  // [nu | t | q | u | err_q | err_u | weight]: 1 + 12, then 1 + 6 with two zeros
+    CHECK(same_bytes(filled(lay.doubles, [&](double* hp) { six_fill(&p, lay, hp); }),
+                     Want().d({3e9, 1e5, 2e5, 0.1, 0.2, -0.1, -0.2, 0.01, 0.02, 0.03, 0.04, 1.0, 2.0}).d({4e9, 3e5, 0.3, 0.0, 0.05, 0.0, 3.0})));
+    done("pol block layout", before);
+}
+
+// a COMPLEX group with three epochs of 1, 64 and 65 visibilities, an AMPLITUDE group of one epoch of 2 without im
+static vag_vis_fit_spec vis_full() {
+    vag_visibility_obs a{}, b{};
+    a.nu = 2e10, a.n_epochs = 3, a.n_vis = 130, a.kind = VAG_VIS_COMPLEX, a.t = D({1e5, 2e5, 3e5}), a.first = I({0, 1, 65, 130});
+    a.u = heap_v(ramp(130, 1000.0)), a.v = heap_v(ramp(130, 2000.0)), a.re = heap_v(ramp(130, 3000.0)), a.im = heap_v(ramp(130, 4000.0));
+    a.err = heap_v(ramp(130, 5000.0)), a.weight = heap_v(ramp(130, 6000.0));
+    b.nu = 4e10, b.n_epochs = 1, b.n_vis = 2, b.kind = VAG_VIS_AMPLITUDE, b.t = D({4e5}), b.first = I({0, 2});
+    b.u = D({1.0, 2.0}), b.v = D({3.0, 4.0}), b.re = D({5.0, 6.0}), b.err = D({7.0, 8.0}), b.weight = D({9.0, 10.0});
+    vag_vis_fit_spec s{};
+    s.n_groups = 2;
+    s.groups = heap<vag_visibility_obs>({a, b});
+    return s;
+}
+
+static void check_vis() {
+    const int before = g_failed;
+    const vag_vis_fit_spec s = vis_full();
+    BlockKey key;
+    std::vector<VisLayout> lay;
+    std::vector<int> blocks;
+    CHECK(vis_scan(&s, key) == VAG_OK && vis_rows(&s, lay, blocks) == VAG_OK);
+    // per group [nu | t n_epochs | six arrays of n_vis]: 1 + 3 + 780 = 784, then 1 + 1 + 12; the first group's epochs are cut into
+    // blocks of at most 64 -- 1, 1 and 2 of them -- so the second group's blocks start at 4
+    CHECK(key.doubles == 798 && lay.size() == 2 && lay[0].obs_off == 0 && lay[1].obs_off == 784 && lay[0].blk_off == 0 && lay[1].blk_off == 4);
+    CHECK(lay[0].epoch_blk == std::vector<int>({0, 1, 2, 4}) && lay[1].epoch_blk == std::vector<int>({0, 1}));
+    CHECK(blocks == std::vector<int>({0, 0, 1, 1, 1, 64, 2, 65, 64, 2, 129, 1, 0, 0, 2}));
+    Want w;
+    w.d({2e10, 1e5, 2e5, 3e5});
+    for (const double first : {1000.0, 2000.0, 3000.0, 4000.0, 5000.0, 6000.0}) w += ramp(130, first);
+    w.d({4e10, 4e5}).d({1.0, 2.0, 3.0, 4.0, 5.0, 6.0, 0.0, 0.0, 7.0, 8.0, 9.0, 10.0});
+    CHECK(same_bytes(filled(key.doubles, [&](double* hp) { vis_fill(&s, lay, hp); }), w));
+    done("vis block layout", before);
+}
+
+template <class Spec, class Hash>
+static void hashes_of(Spec (*make)(), Hash hash, void (*one_double)(Spec&)) {
+    Spec a = make(), b = make();  // equal content in other arrays
+    CHECK(hash(a) == hash(b));
+    one_double(b);
+    CHECK(hash(a) != hash(b));
+}
+
+static void check_hashes() {
+    const int before = g_failed;
+    auto fit_hash = [](const vag_fit_spec& s) {
+        FitLayout lay;
+        CHECK(fit_scan(&s, 2, FitAccepts{}, lay) == VAG_OK);
+        return lay.hash;
+    };
+    auto sky_hash = [](const vag_sky_fit_spec& s) {
+        SkyLayout lay;
+        CHECK(sky_scan(&s, lay) == VAG_OK);
+        return lay.hash;
+    };
+    auto pol_hash = [](const vag_pol_fit_spec& s) {
+        PolLayout lay;
+        CHECK(pol_scan(&s, lay) == VAG_OK);
+        return lay.hash;
+    };
+    auto vis_hash = [](const vag_vis_fit_spec& s) {
+        BlockKey key;
+        CHECK(vis_scan(&s, key) == VAG_OK);
+        return key.hash;
+    };
+    hashes_of<vag_fit_spec>([] { return fit_full(true); }, fit_hash, [](vag_fit_spec& s) { own(own(s.bands, 2)[1].weight, 3)[2] = 5.5; });
+    hashes_of<vag_sky_fit_spec>(sky_full, sky_hash, [](vag_sky_fit_spec& s) { own(own(s.groups, 2)[1].north, 2)[1] = 0.61; });
+    hashes_of<vag_pol_fit_spec>(pol_full, pol_hash, [](vag_pol_fit_spec& s) { own(own(s.groups, 2)[0].err_u, 2)[0] = 0.031; });
+    hashes_of<vag_vis_fit_spec>(vis_full, vis_hash, [](vag_vis_fit_spec& s) { own(own(s.groups, 2)[0].im, 130)[129] = 0.5; });
+    // a kind
+    vag_fit_spec f = fit_full(true);
+    f.prior_kind[1] = VAG_PRIOR_NONE;
+    CHECK(fit_hash(f) != fit_hash(fit_full(true)));
+    vag_pol_fit_spec p = pol_full();
+    own(p.groups, 2)[0].kind = VAG_POL_DEGREE;
+    CHECK(pol_hash(p) != pol_hash(pol_full()));
+    vag_vis_fit_spec v = vis_full();
+    own(v.groups, 2)[0].kind = VAG_VIS_AMPLITUDE;
+    CHECK(vis_hash(v) != vis_hash(vis_full()));
+    // n_az: 0 is the default the code substitutes, 1024 for a visibility group and 256 for a polarization group
+    own(v.groups, 2)[0].kind = VAG_VIS_COMPLEX;
+    own(v.groups, 2)[1].n_az = 512;
+    CHECK(vis_hash(v) != vis_hash(vis_full()));
+    own(v.groups, 2)[1].n_az = 1024;
+    CHECK(vis_hash(v) == vis_hash(vis_full()));
+    p = pol_full();
+    own(p.groups, 2)[1].n_az = 256;
+    CHECK(pol_hash(p) == pol_hash(pol_full()));
+    own(p.groups, 2)[1].n_az = 128;
+    CHECK(pol_hash(p) != pol_hash(pol_full()));
+    done("block hashes", before);
+}
+
+// The scanned blocks: the key a scan leaves is the stage vector's size and a hash of the shapes and the staged bytes.
+static void check_scan_keys(const vag_fit_spec& spec) {
+    const int before = g_failed;
+    auto cov_key = [](const vag_cov_fit_spec& cs) {
+        std::vector<double> stage;
+        CovLayout lay;
+        CHECK(cov_scan(&cs, stage, lay) == VAG_OK && lay.doubles == stage.size() && lay.doubles == 26);
+        return lay.hash;
+    };
+    vag_cov_fit_spec c = cov_spec();
+    CHECK(cov_key(c) == cov_key(cov_spec()));  // equal content in other arrays
+    own(own(c.groups, 2)[1].ln_flux, 3)[2] = -63.5;
+    CHECK(cov_key(c) != cov_key(cov_spec()));
+    c = cov_spec();
+    own(own(c.groups, 2)[1].whitener, 9)[1] = 7.0;  // (the unread upper half is not staged: not content)
+    CHECK(cov_key(c) == cov_key(cov_spec()));
+    const vag_pol_fit_spec pol = pol_spec();
+    const vag_limit_fit_spec lim = lim_spec();
+    vag_limit_fit_spec lim2 = lim_spec();
+    own(own(lim2.bands, 2)[1].sigma, 3)[0] = 0.3;
+    std::vector<double> s1, s2, s3;
+    LimLayout l1, l2, l3;
+    CHECK(lim_scan(&spec, &pol, &lim, s1, l1) == VAG_OK && lim_scan(&spec, &pol, &lim, s2, l2) == VAG_OK && lim_scan(&spec, &pol, &lim2, s3, l3) == VAG_OK);
+    CHECK(l1.doubles == 18 && l1.hash == l2.hash && l3.doubles == 18 && l3.hash != l1.hash);
+    const vag_counts_fit_spec cs = counts_spec();
+    const vag_index_fit_spec is = index_spec();
+    const vag_fold_fit_spec fs = fold_spec();
+    const vag_noise_fit_spec nz = noise_spec();
+    const vag_template_fit_spec tp = tmpl_spec();
+    std::vector<double> stage;
+    CountsLayout cl;
+    IndexLayout il;
+    FoldLayout fl;
+    NoiseLayout nl;
+    TmplLayout tl;
+    CHECK(counts_scan(&cs, stage, cl) == VAG_OK && cl.doubles == 32 && cl.hash != 0);
+    CHECK(index_scan(&is, stage, il) == VAG_OK && il.doubles == 50 && il.hash != cl.hash);
+    CHECK(fold_scan(&spec, &fs, stage, fl) == VAG_OK && fl.doubles == 74 && fl.hash != il.hash);
+    CHECK(noise_scan(&spec, &nz, stage, nl) == VAG_OK && nl.doubles == 19 && nl.hash != fl.hash);
+    CHECK(tmpl_scan(&spec, &tp, stage, tl) == VAG_OK && tl.doubles == 14 && tl.hash != nl.hash);
+    done("scan keys", before);
+}
+
+// Every refusal of one block: a change to the accepted spec, where it must be refused (the scan, or the rows behind a scan that
+// accepts), and the text, word for word.
+template <class Spec>
+struct Refusal {
+    const char* text;
+    bool in_rows;
+    std::function<void(Spec&)> change;
+};
+
+template <class Spec>
+static void refusals_of(const char* name, Spec (*make)(), int (*scan)(const Spec&), int (*rows)(const Spec&),
+                        std::initializer_list<Refusal<Spec>> table) {
+    const int before = g_failed;
+    for (const Refusal<Spec>& r : table) {
+        Spec s = make();
+        r.change(s);
+        g_err.clear();
+        const int rc = scan(s);
+        if (r.in_rows) CHECK(rc == VAG_OK && rows(s) == VAG_E_INVALID);
+        else CHECK(rc == VAG_E_INVALID);
+        if (g_err != r.text) {
+            std::printf("FAIL %s: wanted \"%s\", got \"%s\"\n", name, r.text, g_err.c_str());
+            ++g_failed;
+        }
+    }
+    done(name, before);
+}
+
+static void check_block_refusals() {
+    using F = vag_fit_spec;
+    refusals_of<F>(
+        "fit block refusals", [] { return fit_full(true); },
+        [](const F& s) {
+            FitLayout lay;
+            return fit_scan(&s, 2, FitAccepts{}, lay);
+        },
+        [](const F& s) { return fit_rows(&s); },
+        {{"ndim must match spec and be in 1..16", false, [](F& s) { s.ndim = 3; }},
+         {"fit spec has no data", false, [](F& s) { s.n_data = s.n_bands = 0; }},
+         {"bad parameter slot", false, [](F& s) { s.slot[1] = VAG_P_SKY_PA; }},
+         {"prior bounds of parameter 1: need lower < upper", false, [](F& s) { s.upper[1] = s.lower[1]; }},
+         {"unknown prior kind 7", false, [](F& s) { s.prior_kind[0] = 7; }},
+         {"Uniform prior needs maximum > minimum", false, [](F& s) { s.prior_kind[0] = VAG_PRIOR_UNIFORM_RANGE, s.prior_b[0] = s.prior_a[0]; }},
+         {"Gaussian prior needs sigma > 0", false, [](F& s) { s.prior_b[1] = 0.0; }},
+         {"LogUniform prior needs 0 < minimum < maximum", false, [](F& s) { s.prior_a[0] = 0.0; }},
+         {"band group 1 has no observations", false, [](F& s) { own(s.bands, 2)[1].n = 0; }},
+         {"data times must be positive", true, [](F& s) { own(s.t, 3)[1] = -2e5; }},
+         {"data times must be ascending (fitter.py:420-428)", true, [](F& s) { own(s.t, 3)[2] = 1.5e5; }},
+         {"band group 1: times must be positive and ascending", true, [](F& s) { own(own(s.bands, 2)[1].t, 3)[1] = 0.5e4; }}});
+    using S = vag_sky_fit_spec;
+    refusals_of<S>(
+        "sky block refusals", sky_full,
+        [](const S& s) {
+            SkyLayout lay;
+            return sky_scan(&s, lay);
+        },
+        [](const S& s) { return sky_rows(&s); },
+        {{"bad centroid group list", false, [](S& s) { s.n_groups = -1; }},
+         {"fixed sky placement values must be finite", false, [](S& s) { s.north0_fixed = INFINITY; }},
+         {"centroid group 1 has no observations", false, [](S& s) { own(s.groups, 2)[1].n = 0; }},
+         {"centroid group 0: null array", false, [](S& s) { own(s.groups, 2)[0].east = nullptr; }},
+         {"centroid group 1: frequency must be positive", true, [](S& s) { own(s.groups, 2)[1].nu = -8e9; }},
+         {"centroid group 1: times must be positive and ascending", true, [](S& s) { own(own(s.groups, 2)[1].t, 2)[1] = 1e6; }},
+         {"centroid group 0: positions and weights must be finite", true, [](S& s) { own(own(s.groups, 2)[0].north, 1)[0] = INFINITY; }},
+         {"centroid group 0: errors must be positive and finite", true, [](S& s) { own(own(s.groups, 2)[0].err_east, 1)[0] = 0.0; }}});
+    using P = vag_pol_fit_spec;
+    refusals_of<P>(
+        "pol block refusals", pol_full,
+        [](const P& s) {
+            PolLayout lay;
+            return pol_scan(&s, lay);
+        },
+        [](const P& s) { return pol_rows(&s); },
+        {{"bad polarization group list", false, [](P& s) { s.groups = nullptr; }},
+         {"at most 64 polarization groups", false, [](P& s) { s.n_groups = VAG_POL_MAX_GROUPS + 1; }},
+         {"fixed polarization values must not be NaN", false, [](P& s) { s.pi_max_fixed[1] = NAN; }},
+         {"polarization group 0 has no observations", false, [](P& s) { own(s.groups, 2)[0].n = 0; }},
+         {"polarization group 1: at most 4096 epochs", false, [](P& s) { own(s.groups, 2)[1].n = VAG_VIS_MAX_EPOCHS + 1; }},
+         {"polarization group 0: unknown kind 5", false, [](P& s) { own(s.groups, 2)[0].kind = 5; }},
+         {"polarization group 0: null array", false, [](P& s) { own(s.groups, 2)[0].err_u = nullptr; }},
+         {"polarization group 1: frequency must be positive", true, [](P& s) { own(s.groups, 2)[1].nu = INFINITY; }},
+         {"polarization group 0: times must be positive and ascending", true, [](P& s) { own(own(s.groups, 2)[0].t, 2)[1] = 0.5e5; }},
+         {"polarization group 1: measurements must be finite, weights finite and >= 0", true, [](P& s) { own(own(s.groups, 2)[1].weight, 1)[0] = -1.0; }},
+         {"polarization group 0: errors must be positive and finite", true, [](P& s) { own(own(s.groups, 2)[0].err_u, 2)[1] = 0.0; }}});
+    using V = vag_vis_fit_spec;
+    static_assert(VAG_VIS_MAX_GROUPS == 64 && VAG_VIS_MAX_EPOCHS == 4096 && VAG_VIS_MAX_PER_EPOCH == 65536, "the texts below hold these");
+    refusals_of<V>(
+        "vis block refusals", vis_full,
+        [](const V& s) {
+            BlockKey key;
+            return vis_scan(&s, key);
+        },
+        [](const V& s) {
+            std::vector<VisLayout> lay;
+            std::vector<int> blocks;
+            return vis_rows(&s, lay, blocks);
+        },
+        {{"bad visibility group list", false, [](V& s) { s.groups = nullptr; }},
+         {"at most 64 visibility groups", false, [](V& s) { s.n_groups = VAG_VIS_MAX_GROUPS + 1; }},
+         {"visibility group 1 has no observations", false, [](V& s) { own(s.groups, 2)[1].n_epochs = 0; }},
+         {"visibility group 0: at most 4096 epochs", false, [](V& s) { own(s.groups, 2)[0].n_epochs = VAG_VIS_MAX_EPOCHS + 1; }},
+         {"visibility group 1: unknown kind 2", false, [](V& s) { own(s.groups, 2)[1].kind = 2; }},
+         {"visibility group 1: null array", false, [](V& s) { own(s.groups, 2)[1].kind = VAG_VIS_COMPLEX; }},  // (and no im)
+         {"visibility group 1: frequency must be positive", true, [](V& s) { own(s.groups, 2)[1].nu = 0.0; }},
+         {"visibility group 0: first[0] must be 0 and first[n_epochs] n_vis", true, [](V& s) { own(own(s.groups, 2)[0].first, 4)[3] = 129; }},
+         {"visibility group 0: times must be positive and strictly ascending", true, [](V& s) { own(own(s.groups, 2)[0].t, 3)[2] = 2e5; }},
+         {"visibility group 0: epoch 1 is empty or first[] is not ascending", true, [](V& s) { own(own(s.groups, 2)[0].first, 4)[2] = 1; }},
+         {"visibility group 0: at most 65536 visibilities per epoch", true,
+          [](V& s) {  // one epoch of 65537
+              vag_visibility_obs& o = own(s.groups, 2)[0];
+              o.n_epochs = 1, o.n_vis = VAG_VIS_MAX_PER_EPOCH + 1, o.first = I({0, VAG_VIS_MAX_PER_EPOCH + 1});
+              o.u = o.v = o.re = o.im = o.err = o.weight = heap_v(std::vector<double>(o.n_vis, 1.0));
+          }},
+         {"visibility group 0: baselines and visibilities must be finite", true, [](V& s) { own(own(s.groups, 2)[0].im, 130)[129] = NAN; }},
+         {"visibility group 1: errors must be positive and finite", true, [](V& s) { own(own(s.groups, 2)[1].err, 2)[1] = 0.0; }},
+         {"visibility group 1: weights must be finite and >= 0", true, [](V& s) { own(own(s.groups, 2)[1].weight, 2)[0] = -9.0; }}});
+}
+
 // ---- through fit_request_prepare
 static void check_prepare(const vag_fit_spec& spec) {
     int before = g_failed;
@@ -434,8 +834,15 @@ int main() {
     check_index();
     check_fold(spec);
     check_cov();
+    check_fit();
+    check_sky();
+    check_pol();
+    check_vis();
+    check_hashes();
+    check_scan_keys(spec);
     check_prepare(spec);
     check_refusals(spec);
+    check_block_refusals();
     if (g_failed) std::printf("%d checks failed\n", g_failed);
     return g_failed ? 1 : 0;
 }

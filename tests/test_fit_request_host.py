@@ -1,4 +1,5 @@
-"""The host side of a likelihood request (csrc/vag_fit_request.h: the seven scans, FitRequest, fit_request_prepare) under the host
+"""The host side of a likelihood request (csrc/vag_fit_request.h: the scans, the miss halves of the four blocks hashed in place,
+FitRequest, fit_request_prepare) under the host
 sanitizers: tests/fit_request_check.cpp is built with the system C++ compiler and AddressSanitizer + UndefinedBehaviorSanitizer linked
 in, and run as a child process.  The program compares every layout offset and every staged double and int32 with values written down
 from the documented layouts, on heap inputs of exactly the advertised lengths; here: exit status 0 and one "ok" line per case.  No
@@ -11,8 +12,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 SCANS = ("lim", "noise", "tmpl", "counts", "index", "fold", "cov")
-CASES = [f"{s}_scan layout" for s in SCANS] + ["fit_request_prepare empty blocks", "fit_request_prepare full request"] + \
-        [f"{s}_scan refusal" for s in SCANS]
+BLOCKS = ("fit", "sky", "pol", "vis")  # hashed in place: a scan, and a miss half of row checks and a fill
+CASES = [f"{s}_scan layout" for s in SCANS] + [f"{b} block layout" for b in BLOCKS] + ["block hashes", "scan keys"] + \
+        ["fit_request_prepare empty blocks", "fit_request_prepare full request"] + \
+        [f"{s}_scan refusal" for s in SCANS] + [f"{b} block refusals" for b in BLOCKS]
 STATIC = ["-static-libasan", "-static-libubsan"]  # g++ links its sanitizer runtimes dynamically unless told; clang++ statically, and knows no such flag
 
 

@@ -43,12 +43,14 @@ def fixture_a():
     return f, tl.defs()
 
 
-def fixture_b():
+def fixture_b(other=False):
     """One fitter with a point block (8 rows at 3 GHz, plus 4 rows at 5 GHz in the noise group "a" with a calibration term, one of
     them a limit row), a band group with a limit row, a centroid group, a visibility group, a degree-polarization group with a limit
     epoch, a counts group and a spectral-index group: 2 to 4 epochs each, built by the helpers of the tests of each kind.  Free:
-    theta_c, theta_v, E_iso, pa, east0, pol_b, sys_a.  Returns (fitter, parameter list)."""
-    f = tv._c4_fitter(with_centroid=True)  # 8 point rows, 3 centroid epochs
+    theta_c, theta_v, E_iso, pa, east0, pol_b, sys_a.  other: the same shapes with other values -- the centroids' east coordinate
+    shifted by 0.1 mas, the visibilities' real parts scaled by 1.1, the polarization degrees by 0.9.  Returns (fitter, parameter
+    list)."""
+    f = tv._c4_fitter(with_centroid=True, east0_true=tv.EAST0_TRUE + (0.1 * tv.units.mas if other else 0.0))  # 8 point rows, 3 centroid epochs
     truth = tv._c4_truth()
     rng = np.random.default_rng(7)
     t4 = np.array([20.0, 60.0, 150.0, 260.0]) * DAY
@@ -61,9 +63,10 @@ def fixture_b():
     blim = np.array([False, False, True])
     f.add_flux(tl.BAND, bt, np.where(blim, 1.2 * bflux, bflux * (1 + 0.05 * rng.standard_normal(3))), 0.1 * bflux, num_points=7,
                upper_limit=blim)
-    tv.add_group(f, tv.make_group(truth, tv.VIS_T, tv.VIS_NU, (4, 3, 5), tv.PA_TRUE, tv.EAST0_TRUE), n_az=64)
+    vd = tv.make_group(truth, tv.VIS_T, tv.VIS_NU, (4, 3, 5), tv.PA_TRUE, tv.EAST0_TRUE)
+    tv.add_group(f, vd[:3] + (vd[3] + 0.1 * vd[3].real,) + vd[4:] if other else vd, n_az=64)
     pol = tp.make_group(truth)  # 4 epochs
-    degree = np.hypot(pol["q"], pol["u"])
+    degree = np.hypot(pol["q"], pol["u"]) * (0.9 if other else 1.0)
     plim = np.array([False, True, False, False])
     f.add_polarization(pol["nu"], pol["t"], np.where(plim, degree + 0.02, degree), err_q=pol["err"], kind="degree",
                        weights=[1.0, 0.5, 2.0, 1.5], upper_limit=plim)
@@ -195,6 +198,21 @@ def test_every_kind_of_data_in_one_fit(fit_b, nb):
     assert np.array_equal(tv._with_hook("VAG_NO_ORDER", "1", lambda: call("vag_loglike_index_batch", spec, all_specs(spec), th)), a)
     assert np.array_equal(f.loglike_batch(th, d), a)
     assert f.last_plan.n_walkers_rejected == 0
+
+
+def test_the_resident_centroid_visibility_and_polarization_blocks_follow_the_data(fit_b):
+    """Two fitters of fixture (b)'s shapes whose centroid, visibility and polarization groups hold other values, called A, A, B, A,
+    B on the shared context at 3 walkers: a block of the same size and another content is uploaded anew each time the data change,
+    so every A is the first A, every B the first B, and A is not B -- all to the bits."""
+    (fa, d), (fb, _) = fit_b, fixture_b(other=True)
+    sa, sb = fa.build_spec(d)[0], fb.build_spec(d)[0]
+    assert (sa._sky.groups[0].n, sa._vis.groups[0].n_vis, sa._pol.groups[0].n) == (sb._sky.groups[0].n, sb._vis.groups[0].n_vis, sb._pol.groups[0].n)
+    th = walkers_b(3)
+    a1, a2, b1, a3, b2 = (call("vag_loglike_index_batch", s, all_specs(s), th) for s in (sa, sa, sb, sa, sb))
+    assert np.all(np.isfinite(a1)) and np.all(np.isfinite(b1))
+    assert np.array_equal(a2, a1) and np.array_equal(a3, a1)
+    assert np.array_equal(b2, b1)
+    assert np.all(a1 != b1)
 
 
 @pytest.mark.parametrize("nb", BATCHES)

@@ -152,31 +152,30 @@ struct ResidentBlock {
     uint64_t hash = 0;
     size_t doubles = 0;  // of d
     bool valid = false;
-    bool resident(uint64_t content, size_t n) const { return valid && hash == content && doubles == n; }
-    // A miss: nothing is resident until commit().  Waits for an earlier staging copy that may still be in flight, sizes both buffers
-    // and hands out the pinned one; n_staged > n when more than the block rides in it (the visibility blocks behind the doubles).
-    int stage(hipStream_t st, size_t n, double** hp, size_t n_staged = 0) {
+    // The whole of it.  A hit returns.  A miss validates first: a refusal leaves the resident block as it was.  Then the stage (nothing
+    // is resident, an earlier staging copy that may still be in flight is waited for, both buffers are sized), the fill of the pinned
+    // buffer, and the commit.  tail: int32 the validation made; they ride behind the doubles in the pinned buffer and go to d_tail
+    // (the visibility blocks).  A block of no doubles ends validated, not valid, nothing held.
+    template <class Validate, class Fill>
+    int upload(hipStream_t st, const BlockKey& key, Validate validate, Fill fill, const std::vector<int>* tail = nullptr, DevBuf* d_tail = nullptr) {
+        const size_t n = key.doubles;
+        if (valid && hash == key.hash && doubles == n) return VAG_OK;
+        if (int rc = validate()) return rc;
+        const size_t n_tail = tail ? tail->size() : 0;  // (the validation has made them)
         valid = false;
+        if (n == 0) return VAG_OK;
         HIPCHK(hipStreamSynchronize(st));
-        if (h.ensure(sizeof(double) * std::max(n, n_staged))) return VAG_E_HIP;
-        if (d.ensure(sizeof(double) * n)) return VAG_E_HIP;
-        *hp = h.as<double>();
+        if (h.ensure(sizeof(double) * (n + (n_tail + 1) / 2)) || d.ensure(sizeof(double) * n)) return VAG_E_HIP;
+        double* hp = h.as<double>();
+        fill(hp);
+        if (tail) {
+            if (d_tail->ensure(sizeof(int) * n_tail)) return VAG_E_HIP;
+            std::memcpy(hp + n, tail->data(), sizeof(int) * n_tail);
+            HIPCHK(hipMemcpyAsync(d_tail->p, hp + n, sizeof(int) * n_tail, hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(hipMemcpyAsync(d.p, hp, sizeof(double) * n, hipMemcpyHostToDevice, st));
+        hash = key.hash, doubles = n, valid = true;
         return VAG_OK;
-    }
-    int commit(hipStream_t st, uint64_t content, size_t n) {
-        HIPCHK(hipMemcpyAsync(d.p, h.p, sizeof(double) * n, hipMemcpyHostToDevice, st));
-        hash = content;
-        doubles = n;
-        valid = true;
-        return VAG_OK;
-    }
-    // the whole of it for a block a scan has laid out
-    int upload(hipStream_t st, uint64_t content, const std::vector<double>& staged) {
-        if (resident(content, staged.size())) return VAG_OK;
-        double* hp = nullptr;
-        if (int rc = stage(st, staged.size(), &hp)) return rc;
-        std::memcpy(hp, staged.data(), sizeof(double) * staged.size());
-        return commit(st, content, staged.size());
     }
     void release() {
         h.release();
@@ -491,11 +490,11 @@ struct vag_ctx {
     // compact per-row / per-cell storage
     DevBuf d_row_off, d_cell_off, d_shock, d_cellpar, d_row_status, d_celldet, d_partial;
     DevBuf d_theta_in, d_valid, d_series_flux, d_chi2, d_bandobs, d_fitstat;
-    // the likelihood's spec blocks, one ResidentBlock each (layouts: upload_{fit,sky,vis,pol}_spec, the scans of vag_fit_request.h)
-    ResidentBlock fit;     // the observation arrays, the slot map and the priors of the vag_fit_spec; fit_prior_off: where the prior block starts
-    ResidentBlock sky;     // centroid groups (vag_loglike_sky_batch)
+    // the likelihood's spec blocks, one ResidentBlock each (layouts, scans and fills: vag_fit_request.h; uploads: upload_blocks)
+    ResidentBlock fit;     // the observation arrays, the slot map and the priors of the vag_fit_spec, see FitLayout
+    ResidentBlock sky;     // centroid groups (vag_loglike_sky_batch): per group [nu | six arrays], see SkyLayout
     ResidentBlock vis;     // visibility groups (vag_loglike_vis_batch); their int32 blocks are d_visblk, their places vis_layout
-    ResidentBlock pol;     // polarization groups (vag_loglike_pol_batch)
+    ResidentBlock pol;     // polarization groups (vag_loglike_pol_batch): per group [nu | six arrays], see PolLayout
     ResidentBlock lim;     // upper-limit rows (vag_loglike_lim_batch): per block [limit | sigma | kind], see LimLayout
     ResidentBlock noise;   // noise groups (vag_loglike_noise_batch): [sys_fixed 8 | calib 8] then per pass the rows' group ids, see NoiseLayout
     ResidentBlock counts;  // counts groups (vag_loglike_counts_batch): per group [t_sample | N | B | a | w | idx], see CountsLayout
@@ -503,13 +502,7 @@ struct vag_ctx {
     ResidentBlock fold;    // fold groups (vag_loglike_fold_batch): per group the block FoldLayout describes
     ResidentBlock tmpl;    // additive templates (vag_loglike_tmpl_batch): [amp_fixed 8] then per touched pass its [n_templates][n] values, see TmplLayout
     ResidentBlock cov;     // correlated groups (vag_loglike_cov_batch): per group [t | nu | ln_flux | ext | Wt], see CovLayout
-    size_t fit_prior_off = 0;
-    struct VisLayout {  // of one resident group
-        size_t obs_off;              // its data in vis.d [doubles]: nu | t | u | v | re | im | err | weight
-        int blk_off;                 // its blocks in d_visblk [blocks of 3 ints]
-        std::vector<int> epoch_blk;  // [n_epochs + 1]: first block of every epoch
-    };
-    std::vector<VisLayout> vis_layout;
+    std::vector<VisLayout> vis_layout;  // of the resident visibility groups: made by the miss that made them resident
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
     bool ic_need_reset = true;       // first SSC table build of a pass clears d_icstatus
     bool ic_soft_fail = false;       // likelihood calls: SSC table failures invalidate the walker instead of raising
@@ -2244,7 +2237,7 @@ int centroid_request(vag_ctx* c, const vag_model_params* d_params, int nb, int n
 // d_lg2nu prepared.  The epochs are cut into chunks whose term list stays within 256 MB (VAG_SKY_CHUNK_T: a test's chunk length);
 // every (walker, visibility block) partial is written once, by the chunk of its epoch, so the cut does not change a bit.
 // d_vispart [nb][n_blk][2] afterwards.
-int vis_chi2_request(vag_ctx* c, const vag_model_params* d_params, int nb, const vag_visibility_obs& o, const vag_ctx::VisLayout& lay,
+int vis_chi2_request(vag_ctx* c, const vag_model_params* d_params, int nb, const vag_visibility_obs& o, const VisLayout& lay,
                      SkyVisFitArgs va) {
     hipStream_t st = c->stream;
     const std::vector<SkyPass> passes = sky_passes(c);
@@ -3455,351 +3448,33 @@ static int upload_series_bands(vag_ctx* c, const double* nu, int n) {
     return nbands;
 }
 
-// ---- fit data cache: the observation arrays, the slot map and the priors of a vag_fit_spec live in ONE device buffer, uploaded
-//      through one pinned staging copy only when their content hash changes (a sampler loop calls with the same spec) ----
-// layout in doubles: [t | nu | ln_flux | ln_err | weight | ext] (n each), then per band group [t | ln_flux | ln_err | weight]
-// (bd.n each), then [lower | upper | prior_a | prior_b] (16 each), then int32 [slot | is_log | prior_kind] (16 each).
-static int upload_fit_spec(vag_ctx* c, const vag_fit_spec* spec, int ndim, bool sky = false, bool pol = false, int noise_groups = 0,
-                           bool counts = false, bool n_h = false, int n_templates = 0) {
-    if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
-    const int n = spec->n_data;
-    if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !sky && !pol && !counts)) return set_err(VAG_E_INVALID, "fit spec has no data");
-    for (int d = 0; d < ndim; ++d) {
-        const int s = spec->slot[d];
-        if (s == VAG_P_A_V) continue;
-        if (sky && s >= VAG_P_SKY_PA && s <= VAG_P_SKY_NORTH0) continue;
-        if (pol && (s == VAG_P_SKY_PA || (s >= VAG_P_POL_B && s <= VAG_P_POL_PI_MAX_RVS))) continue;
-        if (s >= VAG_P_NOISE_SYS0 && s < VAG_P_NOISE_SYS0 + noise_groups) continue;  // (the systematic of a group the noise spec has)
-        if (n_h && s == VAG_P_N_H) continue;  // (the absorbing column of a fold group with a cross-section)
-        if (s >= VAG_P_TMPL_AMP0 && s < VAG_P_TMPL_AMP0 + n_templates) continue;  // (the amplitude of a template the template spec has)
-        if (s < 0 || (s >= VAG_P_COUNT && (s < VAG_P_RVS_EPS_E || s > VAG_P_MAG_Q))) return set_err(VAG_E_INVALID, "bad parameter slot");
+// ---- the uploads of a request's spec blocks (layouts, scans and miss halves: vag_fit_request.h), in the order in which their
+//      refusals surface.  A block hashed in place is scanned here, when its turn comes; one that fit_request_prepare has scanned and
+//      staged has no miss half but the copy of its stage vector.  fit_only: the fit block alone (a sharded call). ----
+static int upload_blocks(vag_ctx* c, FitRequest& r, bool fit_only = false) {
+    hipStream_t st = c->stream;
+    int rc = fit_scan(r.spec, r.ndim, fit_accepts(r), r.fit);
+    if (!rc) rc = c->fit.upload(st, r.fit, [&] { return fit_rows(r.spec); }, [&](double* hp) { fit_fill(r.spec, r.fit, hp); });
+    if (rc || fit_only) return rc;
+    if (r.sky && !(rc = sky_scan(r.sky, r.slay)))  // (n_groups = 0: the fixed placement alone)
+        rc = c->sky.upload(st, r.slay, [&] { return sky_rows(r.sky); }, [&](double* hp) { six_fill(r.sky, r.slay, hp); });
+    if (!rc && r.vis && !(rc = vis_scan(r.vis, r.vkey))) {  // (its int32 blocks ride behind the doubles, to d_visblk)
+        rc = c->vis.upload(st, r.vkey, [&] { return vis_rows(r.vis, r.vis_groups, r.vis_blocks); },
+                           [&](double* hp) { vis_fill(r.vis, r.vis_groups, hp); }, &r.vis_blocks, &c->d_visblk);
+        if (!rc && !r.vis_groups.empty()) c->vis_layout = std::move(r.vis_groups);  // (a miss: vis_rows has laid the groups out anew)
     }
-    if (spec->use_priors)
-        for (int d = 0; d < ndim; ++d) {
-            if (!(spec->lower[d] < spec->upper[d])) return set_err(VAG_E_INVALID, "prior bounds of parameter %d: need lower < upper", d);
-            const int k = spec->prior_kind[d];
-            if (k < VAG_PRIOR_UNIFORM || k > VAG_PRIOR_UNIFORM_RANGE) return set_err(VAG_E_INVALID, "unknown prior kind %d", k);
-            if (k == VAG_PRIOR_UNIFORM_RANGE && !(spec->prior_b[d] > spec->prior_a[d])) return set_err(VAG_E_INVALID, "Uniform prior needs maximum > minimum");
-            if (k == VAG_PRIOR_GAUSSIAN && !(spec->prior_b[d] > 0)) return set_err(VAG_E_INVALID, "Gaussian prior needs sigma > 0");
-            if (k == VAG_PRIOR_LOG_UNIFORM && !(spec->prior_a[d] > 0 && spec->prior_b[d] > spec->prior_a[d]))
-                return set_err(VAG_E_INVALID, "LogUniform prior needs 0 < minimum < maximum");
-        }
-    uint64_t h = 1469598103934665603ull;
-    const int head[4] = {n, spec->n_bands, ndim, spec->ext_kernel ? 1 : 0};
-    h = fnv1a(h, head, sizeof head);
-    size_t total = 6 * (size_t)std::max(n, 1);
-    for (const double* arr : {spec->t, spec->nu, spec->ln_flux, spec->ln_err, spec->weight, spec->ext_kernel})
-        if (arr && n > 0) h = fnv1a(h, arr, sizeof(double) * n);
-    for (int g = 0; g < spec->n_bands; ++g) {
-        const vag_band_obs& bd = spec->bands[g];
-        if (bd.n <= 0) return set_err(VAG_E_INVALID, "band group %d has no observations", g);
-        h = fnv1a(h, &bd.n, sizeof bd.n);
-        for (const double* arr : {bd.t, bd.ln_flux, bd.ln_err, bd.weight}) h = fnv1a(h, arr, sizeof(double) * bd.n);
-        total += 4 * (size_t)bd.n;
-    }
-    h = fnv1a(h, spec->slot, sizeof spec->slot);
-    h = fnv1a(h, spec->is_log, sizeof spec->is_log);
-    h = fnv1a(h, &spec->use_priors, sizeof spec->use_priors);
-    if (spec->use_priors) {
-        h = fnv1a(h, spec->lower, sizeof spec->lower);
-        h = fnv1a(h, spec->upper, sizeof spec->upper);
-        h = fnv1a(h, spec->prior_kind, sizeof spec->prior_kind);
-        h = fnv1a(h, spec->prior_a, sizeof spec->prior_a);
-        h = fnv1a(h, spec->prior_b, sizeof spec->prior_b);
-    }
-    const size_t prior_off = total;
-    total += 4 * 16 + 3 * 16 / 2;  // four double[16] + three int32[16]
-    c->fit_prior_off = prior_off;
-    if (c->fit.resident(h, total)) return VAG_OK;
-
-    // content changed: validate it (once), stage and upload
-    for (int i = 0; i < n; ++i)
-        if (!(spec->t[i] > 0)) return set_err(VAG_E_INVALID, "data times must be positive");
-    for (int i = 1; i < n; ++i)
-        if (spec->t[i] < spec->t[i - 1]) return set_err(VAG_E_INVALID, "data times must be ascending (fitter.py:420-428)");
-    for (int g = 0; g < spec->n_bands; ++g) {
-        const vag_band_obs& bd = spec->bands[g];
-        for (int i = 0; i < bd.n; ++i)
-            if (!(bd.t[i] > 0) || (i > 0 && bd.t[i] < bd.t[i - 1]))
-                return set_err(VAG_E_INVALID, "band group %d: times must be positive and ascending", g);
-    }
-    double* hp = nullptr;
-    if (int rc = c->fit.stage(c->stream, total, &hp)) return rc;
-    std::memset(hp, 0, sizeof(double) * total);
-    if (n > 0) {
-        const double* src[6] = {spec->t, spec->nu, spec->ln_flux, spec->ln_err, spec->weight, spec->ext_kernel};
-        for (int q = 0; q < 6; ++q)
-            if (src[q]) std::memcpy(hp + (size_t)q * n, src[q], sizeof(double) * n);
-    }
-    size_t off = 6 * (size_t)std::max(n, 1);
-    for (int g = 0; g < spec->n_bands; ++g) {
-        const vag_band_obs& bd = spec->bands[g];
-        const double* src[4] = {bd.t, bd.ln_flux, bd.ln_err, bd.weight};
-        for (int q = 0; q < 4; ++q) std::memcpy(hp + off + (size_t)q * bd.n, src[q], sizeof(double) * bd.n);
-        off += 4 * (size_t)bd.n;
-    }
-    std::memcpy(hp + prior_off, spec->lower, sizeof spec->lower);
-    std::memcpy(hp + prior_off + 16, spec->upper, sizeof spec->upper);
-    std::memcpy(hp + prior_off + 32, spec->prior_a, sizeof spec->prior_a);
-    std::memcpy(hp + prior_off + 48, spec->prior_b, sizeof spec->prior_b);
-    int* hi = reinterpret_cast<int*>(hp + prior_off + 64);
-    std::memcpy(hi, spec->slot, sizeof spec->slot);
-    std::memcpy(hi + 16, spec->is_log, sizeof spec->is_log);
-    std::memcpy(hi + 32, spec->prior_kind, sizeof spec->prior_kind);
-    return c->fit.commit(c->stream, h, total);
-}
-
-// ---- centroid groups (vag_loglike_sky_batch): their data in one device buffer, uploaded like the fit spec when its hash changes.
-//      Layout in doubles, per group: [nu | t | east | north | err_east | err_north | weight] (1 + 6 n). ----
-static int upload_sky_spec(vag_ctx* c, const vag_sky_fit_spec* sky) {
-    if (sky->n_groups < 0 || (sky->n_groups > 0 && !sky->groups)) return set_err(VAG_E_INVALID, "bad centroid group list");
-    for (double v : {sky->pa_fixed, sky->east0_fixed, sky->north0_fixed})
-        if (!std::isfinite(v)) return set_err(VAG_E_INVALID, "fixed sky placement values must be finite");
-    uint64_t h = 1469598103934665603ull;
-    h = fnv1a(h, &sky->n_groups, sizeof sky->n_groups);
-    size_t total = 0;
-    for (int g = 0; g < sky->n_groups; ++g) {
-        const vag_centroid_obs& o = sky->groups[g];
-        if (o.n <= 0) return set_err(VAG_E_INVALID, "centroid group %d has no observations", g);
-        if (!o.t || !o.east || !o.north || !o.err_east || !o.err_north || !o.weight) return set_err(VAG_E_INVALID, "centroid group %d: null array", g);
-        h = fnv1a(h, &o.nu, sizeof o.nu);
-        h = fnv1a(h, &o.n, sizeof o.n);
-        for (const double* arr : {o.t, o.east, o.north, o.err_east, o.err_north, o.weight}) h = fnv1a(h, arr, sizeof(double) * o.n);
-        total += 1 + 6 * (size_t)o.n;
-    }
-    if (c->sky.resident(h, total)) return VAG_OK;
-    for (int g = 0; g < sky->n_groups; ++g) {
-        const vag_centroid_obs& o = sky->groups[g];
-        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "centroid group %d: frequency must be positive", g);
-        for (int i = 0; i < o.n; ++i) {
-            if (!(o.t[i] > 0) || !std::isfinite(o.t[i]) || (i > 0 && o.t[i] < o.t[i - 1]))
-                return set_err(VAG_E_INVALID, "centroid group %d: times must be positive and ascending", g);
-            if (!std::isfinite(o.east[i]) || !std::isfinite(o.north[i]) || !std::isfinite(o.weight[i]))
-                return set_err(VAG_E_INVALID, "centroid group %d: positions and weights must be finite", g);
-            if (!(o.err_east[i] > 0) || !(o.err_north[i] > 0) || !std::isfinite(o.err_east[i]) || !std::isfinite(o.err_north[i]))
-                return set_err(VAG_E_INVALID, "centroid group %d: errors must be positive and finite", g);
-        }
-    }
-    c->sky.valid = false;
-    if (total == 0) return VAG_OK;  // (the fixed placement alone: nothing to hold)
-    double* hp = nullptr;
-    if (int rc = c->sky.stage(c->stream, total, &hp)) return rc;
-    size_t off = 0;
-    for (int g = 0; g < sky->n_groups; ++g) {
-        const vag_centroid_obs& o = sky->groups[g];
-        hp[off++] = o.nu;
-        for (const double* arr : {o.t, o.east, o.north, o.err_east, o.err_north, o.weight}) {
-            std::memcpy(hp + off, arr, sizeof(double) * o.n);
-            off += o.n;
-        }
-    }
-    return c->sky.commit(c->stream, h, total);
-}
-
-// ---- visibility groups (vag_loglike_vis_batch): their data in one device buffer, uploaded like the centroid groups when the hash
-//      changes.  Layout in doubles, per group: [nu | t | u | v | re | im | err | weight] (1 + n_epochs + 6 n_vis); in d_visblk, per
-//      group, the blocks of at most 64 visibilities of one epoch as int32 [epoch, first visibility, visibilities]. ----
-static int upload_vis_spec(vag_ctx* c, const vag_vis_fit_spec* vis) {
-    if (vis->n_groups < 0 || !vis->groups) return set_err(VAG_E_INVALID, "bad visibility group list");
-    if (vis->n_groups > VAG_VIS_MAX_GROUPS) return set_err(VAG_E_INVALID, "at most %d visibility groups", VAG_VIS_MAX_GROUPS);
-    uint64_t h = 1469598103934665603ull;
-    h = fnv1a(h, &vis->n_groups, sizeof vis->n_groups);
-    size_t total = 0;
-    for (int g = 0; g < vis->n_groups; ++g) {
-        const vag_visibility_obs& o = vis->groups[g];
-        if (o.n_epochs < 1 || o.n_vis < 1) return set_err(VAG_E_INVALID, "visibility group %d has no observations", g);
-        if (o.n_epochs > VAG_VIS_MAX_EPOCHS) return set_err(VAG_E_INVALID, "visibility group %d: at most %d epochs", g, VAG_VIS_MAX_EPOCHS);
-        if (o.kind != VAG_VIS_COMPLEX && o.kind != VAG_VIS_AMPLITUDE) return set_err(VAG_E_INVALID, "visibility group %d: unknown kind %d", g, o.kind);
-        if (!o.t || !o.first || !o.u || !o.v || !o.re || !o.err || !o.weight || (o.kind == VAG_VIS_COMPLEX && !o.im))
-            return set_err(VAG_E_INVALID, "visibility group %d: null array", g);
-        const int head[4] = {o.n_epochs, o.n_vis, o.n_az > 0 ? o.n_az : 1024, o.kind};
-        h = fnv1a(h, &o.nu, sizeof o.nu);
-        h = fnv1a(h, head, sizeof head);
-        h = fnv1a(h, o.t, sizeof(double) * o.n_epochs);
-        h = fnv1a(h, o.first, sizeof(int32_t) * ((size_t)o.n_epochs + 1));
-        for (const double* arr : {o.u, o.v, o.re, o.kind == VAG_VIS_COMPLEX ? o.im : nullptr, o.err, o.weight})
-            if (arr) h = fnv1a(h, arr, sizeof(double) * o.n_vis);
-        total += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
-    }
-    if (c->vis.resident(h, total)) return VAG_OK;
-    std::vector<vag_ctx::VisLayout> layout(vis->n_groups);
-    std::vector<int> blocks;
-    size_t off = 0;
-    for (int g = 0; g < vis->n_groups; ++g) {
-        const vag_visibility_obs& o = vis->groups[g];
-        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "visibility group %d: frequency must be positive", g);
-        if (o.first[0] != 0 || o.first[o.n_epochs] != o.n_vis)
-            return set_err(VAG_E_INVALID, "visibility group %d: first[0] must be 0 and first[n_epochs] n_vis", g);
-        vag_ctx::VisLayout& lay = layout[g];
-        lay.obs_off = off;
-        lay.blk_off = (int)(blocks.size() / 3);
-        off += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
-        for (int e = 0; e < o.n_epochs; ++e) {
-            if (!(o.t[e] > 0) || !std::isfinite(o.t[e]) || (e > 0 && !(o.t[e] > o.t[e - 1])))
-                return set_err(VAG_E_INVALID, "visibility group %d: times must be positive and strictly ascending", g);
-            const int k0 = o.first[e], k1 = o.first[e + 1];
-            if (k0 < 0 || k1 > o.n_vis || k1 <= k0) return set_err(VAG_E_INVALID, "visibility group %d: epoch %d is empty or first[] is not ascending", g, e);
-            if (k1 - k0 > VAG_VIS_MAX_PER_EPOCH)
-                return set_err(VAG_E_INVALID, "visibility group %d: at most %d visibilities per epoch", g, VAG_VIS_MAX_PER_EPOCH);
-            lay.epoch_blk.push_back((int)(blocks.size() / 3) - lay.blk_off);
-            for (int k = k0; k < k1; k += 64) blocks.insert(blocks.end(), {e, k, std::min(64, k1 - k)});
-        }
-        lay.epoch_blk.push_back((int)(blocks.size() / 3) - lay.blk_off);
-        for (int k = 0; k < o.n_vis; ++k) {
-            if (!std::isfinite(o.u[k]) || !std::isfinite(o.v[k]) || !std::isfinite(o.re[k]) || (o.kind == VAG_VIS_COMPLEX && !std::isfinite(o.im[k])))
-                return set_err(VAG_E_INVALID, "visibility group %d: baselines and visibilities must be finite", g);
-            if (!(o.err[k] > 0) || !std::isfinite(o.err[k])) return set_err(VAG_E_INVALID, "visibility group %d: errors must be positive and finite", g);
-            if (!(o.weight[k] >= 0) || !std::isfinite(o.weight[k])) return set_err(VAG_E_INVALID, "visibility group %d: weights must be finite and >= 0", g);
-        }
-    }
-    const size_t blk_doubles = (blocks.size() + 1) / 2;  // the int32 blocks ride behind the doubles in the one staging buffer
-    double* hp = nullptr;
-    if (int rc = c->vis.stage(c->stream, total, &hp, total + blk_doubles)) return rc;
-    if (c->d_visblk.ensure(sizeof(int) * blocks.size())) return VAG_E_HIP;
-    off = 0;
-    for (int g = 0; g < vis->n_groups; ++g) {
-        const vag_visibility_obs& o = vis->groups[g];
-        hp[off++] = o.nu;
-        std::memcpy(hp + off, o.t, sizeof(double) * o.n_epochs);
-        off += o.n_epochs;
-        for (const double* arr : {o.u, o.v, o.re, o.kind == VAG_VIS_COMPLEX ? o.im : nullptr, o.err, o.weight}) {
-            if (arr)
-                std::memcpy(hp + off, arr, sizeof(double) * o.n_vis);
-            else
-                std::memset(hp + off, 0, sizeof(double) * o.n_vis);
-            off += o.n_vis;
-        }
-    }
-    std::memcpy(hp + total, blocks.data(), sizeof(int) * blocks.size());
-    HIPCHK(hipMemcpyAsync(c->d_visblk.p, hp + total, sizeof(int) * blocks.size(), hipMemcpyHostToDevice, c->stream));
-    c->vis_layout = std::move(layout);
-    return c->vis.commit(c->stream, h, total);
-}
-
-// ---- polarization groups (vag_loglike_pol_batch): their data in one device buffer, uploaded like the centroid groups when the hash
-//      changes.  Layout in doubles, per group: [nu | t | q | u | err_q | err_u | weight] (1 + 6 n); u and err_u of a DEGREE group are
-//      zeros. ----
-static int upload_pol_spec(vag_ctx* c, const vag_pol_fit_spec* pol) {
-    if (pol->n_groups < 0 || !pol->groups) return set_err(VAG_E_INVALID, "bad polarization group list");
-    if (pol->n_groups > VAG_POL_MAX_GROUPS) return set_err(VAG_E_INVALID, "at most %d polarization groups", VAG_POL_MAX_GROUPS);
-    for (int e = 0; e < 2; ++e)
-        if (std::isnan(pol->b_fixed[e]) || std::isnan(pol->pi_max_fixed[e]))
-            return set_err(VAG_E_INVALID, "fixed polarization values must not be NaN");
-    uint64_t h = 1469598103934665603ull;
-    h = fnv1a(h, &pol->n_groups, sizeof pol->n_groups);
-    size_t total = 0;
-    for (int g = 0; g < pol->n_groups; ++g) {
-        const vag_polarization_obs& o = pol->groups[g];
-        if (o.n < 1) return set_err(VAG_E_INVALID, "polarization group %d has no observations", g);
-        if (o.n > VAG_VIS_MAX_EPOCHS) return set_err(VAG_E_INVALID, "polarization group %d: at most %d epochs", g, VAG_VIS_MAX_EPOCHS);
-        if (o.kind != VAG_POL_QU && o.kind != VAG_POL_DEGREE) return set_err(VAG_E_INVALID, "polarization group %d: unknown kind %d", g, o.kind);
-        if (!o.t || !o.q || !o.err_q || !o.weight || (o.kind == VAG_POL_QU && (!o.u || !o.err_u)))
-            return set_err(VAG_E_INVALID, "polarization group %d: null array", g);
-        const int head[3] = {o.n, o.n_az > 0 ? o.n_az : 256, o.kind};
-        h = fnv1a(h, &o.nu, sizeof o.nu);
-        h = fnv1a(h, head, sizeof head);
-        for (const double* arr : {o.t, o.q, o.kind == VAG_POL_QU ? o.u : nullptr, o.err_q, o.kind == VAG_POL_QU ? o.err_u : nullptr, o.weight})
-            if (arr) h = fnv1a(h, arr, sizeof(double) * o.n);
-        total += 1 + 6 * (size_t)o.n;
-    }
-    if (c->pol.resident(h, total)) return VAG_OK;
-    for (int g = 0; g < pol->n_groups; ++g) {
-        const vag_polarization_obs& o = pol->groups[g];
-        const bool qu = o.kind == VAG_POL_QU;
-        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "polarization group %d: frequency must be positive", g);
-        for (int i = 0; i < o.n; ++i) {
-            if (!(o.t[i] > 0) || !std::isfinite(o.t[i]) || (i > 0 && o.t[i] < o.t[i - 1]))
-                return set_err(VAG_E_INVALID, "polarization group %d: times must be positive and ascending", g);
-            if (!std::isfinite(o.q[i]) || (qu && !std::isfinite(o.u[i])) || !std::isfinite(o.weight[i]) || o.weight[i] < 0)
-                return set_err(VAG_E_INVALID, "polarization group %d: measurements must be finite, weights finite and >= 0", g);
-            if (!(o.err_q[i] > 0) || !std::isfinite(o.err_q[i]) || (qu && (!(o.err_u[i] > 0) || !std::isfinite(o.err_u[i]))))
-                return set_err(VAG_E_INVALID, "polarization group %d: errors must be positive and finite", g);
-        }
-    }
-    double* hp = nullptr;
-    if (int rc = c->pol.stage(c->stream, total, &hp)) return rc;
-    size_t off = 0;
-    for (int g = 0; g < pol->n_groups; ++g) {
-        const vag_polarization_obs& o = pol->groups[g];
-        const bool qu = o.kind == VAG_POL_QU;
-        hp[off++] = o.nu;
-        for (const double* arr : {o.t, o.q, qu ? o.u : nullptr, o.err_q, qu ? o.err_u : nullptr, o.weight}) {
-            if (arr)
-                std::memcpy(hp + off, arr, sizeof(double) * o.n);
-            else
-                std::memset(hp + off, 0, sizeof(double) * o.n);
-            off += o.n;
-        }
-    }
-    return c->pol.commit(c->stream, h, total);
-}
-
-// ---- the blocks a scan of vag_fit_request.h has laid out (layouts: there).  A block's hash covers what tells two layouts of the same
-//      bytes apart -- the passes' offsets, or the groups' shapes -- and then the bytes; ResidentBlock::upload does the rest. ----
-static int upload_lim_spec(vag_ctx* c, const std::vector<double>& stage, const LimLayout& lay) {
-    uint64_t h = 1469598103934665603ull;
-    h = fnv1a(h, &lay.point, sizeof lay.point);
-    if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
-    if (!lay.pol.empty()) h = fnv1a(h, lay.pol.data(), sizeof(long) * lay.pol.size());
-    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    return c->lim.upload(c->stream, h, stage);
-}
-
-static int upload_noise_spec(vag_ctx* c, const std::vector<double>& stage, const NoiseLayout& lay) {
-    uint64_t h = 1469598103934665603ull;
-    h = fnv1a(h, &lay.point, sizeof lay.point);
-    if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
-    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    return c->noise.upload(c->stream, h, stage);
-}
-
-static int upload_tmpl_spec(vag_ctx* c, const std::vector<double>& stage, const TmplLayout& lay) {
-    uint64_t h = 1469598103934665603ull;
-    h = fnv1a(h, &lay.point, sizeof lay.point);
-    if (!lay.band.empty()) h = fnv1a(h, lay.band.data(), sizeof(long) * lay.band.size());
-    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    return c->tmpl.upload(c->stream, h, stage);
-}
-
-static int upload_counts_spec(vag_ctx* c, const vag_counts_fit_spec* cs, const std::vector<double>& stage, const CountsLayout& lay) {
-    uint64_t h = 1469598103934665603ull;
-    for (int g = 0; g < cs->n_groups; ++g) {  // (the shapes: two groups whose blocks hold the same bytes are still two layouts)
-        const int head[4] = {cs->groups[g].n, cs->groups[g].m, cs->groups[g].n_samples, cs->groups[g].num_points};
-        h = fnv1a(h, head, sizeof head);
-    }
-    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    return c->counts.upload(c->stream, h, stage);
-}
-
-static int upload_index_spec(vag_ctx* c, const vag_index_fit_spec* is, const std::vector<double>& stage) {
-    uint64_t h = 1469598103934665603ull;
-    for (int g = 0; g < is->n_groups; ++g) {  // (the shapes: two groups whose blocks hold the same bytes are still two layouts)
-        const int head[2] = {is->groups[g].n, is->groups[g].k};
-        h = fnv1a(h, head, sizeof head);
-    }
-    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    return c->index.upload(c->stream, h, stage);
-}
-
-static int upload_fold_spec(vag_ctx* c, const vag_fold_fit_spec* fs, const std::vector<double>& stage) {
-    uint64_t h = 1469598103934665603ull;
-    for (int g = 0; g < fs->n_groups; ++g) {  // (the shapes: two groups whose blocks hold the same bytes are still two layouts)
-        const vag_fold_obs& o = fs->groups[g];
-        const int head[6] = {o.J, o.C, o.n, o.m, o.n_samples, o.sigma ? 1 : 0};
-        h = fnv1a(h, head, sizeof head);
-    }
-    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    return c->fold.upload(c->stream, h, stage);
-}
-
-static int upload_cov_spec(vag_ctx* c, const vag_cov_fit_spec* cs, const std::vector<double>& stage) {
-    uint64_t h = 1469598103934665603ull;
-    for (int g = 0; g < cs->n_groups; ++g) {  // (the shapes: two groups whose blocks hold the same bytes are still two layouts)
-        const int head[2] = {cs->groups[g].n, cs->groups[g].ext ? 1 : 0};
-        h = fnv1a(h, head, sizeof head);
-    }
-    h = fnv1a(h, stage.data(), sizeof(double) * stage.size());
-    return c->cov.upload(c->stream, h, stage);
+    if (!rc && r.pol && !(rc = pol_scan(r.pol, r.play)))
+        rc = c->pol.upload(st, r.play, [&] { return pol_rows(r.pol); }, [&](double* hp) { six_fill(r.pol, r.play, hp); });
+    const struct { ResidentBlock* block; const void* spec; const BlockKey* key; const std::vector<double>* staged; } scanned[7] = {  // (spec null: not held)
+        {&c->lim, r.lim, &r.llay, &r.lstage},       {&c->noise, r.noise, &r.nlay, &r.nstage},
+        {&c->counts, r.counts, &r.clay, &r.cstage}, {&c->index, r.index, &r.ilay, &r.istage},
+        {&c->fold, r.fold, &r.flay, &r.fstage},     {&c->tmpl, r.tmpl, &r.tlay, &r.tstage},
+        {&c->cov, r.cov, &r.vlay, &r.vstage}};
+    for (const auto& s : scanned)
+        if (!rc && s.spec)
+            rc = s.block->upload(st, *s.key, [] { return VAG_OK; },
+                                 [&](double* hp) { std::memcpy(hp, s.staged->data(), sizeof(double) * s.staged->size()); });
+    return rc;
 }
 
 constexpr int COUNTS_PPB = 64;  // (theta, phi) pairs per flux workgroup of a counts pass (vag_ctx::ppb_pin)
@@ -3820,14 +3495,16 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     double* d_chi2 = c->d_chi2.as<double>();
     double* d_av = d_chi2 + nb;
     double* d_lp = d_chi2 + 2 * (size_t)nb;
-    double* d = c->fit.d.as<double>();
-    const double* d_prior = d + c->fit_prior_off;
+    const FitLayout& fl = req.fit;
+    double* d = c->fit.d.as<double>();  // the point block: [t | nu | ln_flux | ln_err | weight | ext]
+    const double *ln_flux = d + fl.ln_flux, *ln_err = d + fl.ln_err, *weight = d + fl.weight, *ext = d + fl.ext;
+    const double* d_prior = d + fl.prior;
     vag_model_params* d_params = c->d_params.as<vag_model_params>();
     // evaluation order: by the costs of the previous call with this batch size (see vag_ctx::d_order)
     const bool can_order = nb >= 64 && nb <= 8192 && !vag_hook("VAG_NO_ORDER");
     const int* d_order = (can_order && c->order_nb == nb) ? c->d_order[c->order_cur].as<int>() : nullptr;
     hipLaunchKernelGGL(vag_fit_front_kernel, dim3((nb + 127) / 128), dim3(128), 0, st, spec->base, d_theta, nb, ndim, d_prior,
-                       spec->use_priors, spec->a_v_fixed, d_params, d_av, d_lp, c->d_fitstat.as<int>(), d, n, d + n,
+                       spec->use_priors, spec->a_v_fixed, d_params, d_av, d_lp, c->d_fitstat.as<int>(), d, n, d + fl.nu,
                        c->d_lg2t.as<double>(), c->d_lg2nu.as<double>(), c->d_tminmax.as<double>(), d_order);
     HIPCHK(hipGetLastError());
     bool order_made = false;
@@ -3914,9 +3591,9 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
         c->allow_spec = false;
         if (rc == VAG_OK) rc = series_request(c, d_params, nb, n, c->d_series_flux.as<double>(), upload_series_bands(c, spec->nu, n));
         if (rc == VAG_OK)
-            rc = back(c->d_series_flux.as<double>(), n, d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n,
-                      spec->ext_kernel ? d + 5 * (size_t)n : nullptr, req.lim ? req.llay.point : -1, req.noise ? req.nlay.point : -1,
-                      req.noise ? req.nlay.point_present : 0u, req.tmpl ? req.tlay.point : -1, req.tmpl ? req.tlay.point_present : 0u);
+            rc = back(c->d_series_flux.as<double>(), n, ln_flux, ln_err, weight, spec->ext_kernel ? ext : nullptr,
+                      req.lim ? req.llay.point : -1, req.noise ? req.nlay.point : -1, req.noise ? req.nlay.point_present : 0u,
+                      req.tmpl ? req.tlay.point : -1, req.tmpl ? req.tlay.point_present : 0u);
         if (rc == VAG_OK) {
             rc = finish_speculation(c);  // before a band group's own grid pass reuses the plan buffers
             n_cap = std::max(n_cap, c->plan.n_models_capacity);
@@ -3928,12 +3605,10 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
             rc = VAG_RETRY;
         }
     }
-    size_t off = 6 * (size_t)std::max(n, 1);
     for (int g = 0; g < spec->n_bands && rc == VAG_OK; ++g) {  // band-integrated groups: one Model.flux request each (fitter.py:524-531)
         const vag_band_obs& bd = spec->bands[g];
         if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(bd.n, n))) return VAG_E_HIP;
-        double* db = d + off;
-        off += 4 * (size_t)bd.n;
+        double* db = d + fl.band[g];  // [t | ln_flux | ln_err | weight]
         begin_pass();
         rc = band_request_dev(c, d_params, nb, db, bd.n, bd.nu_min, bd.nu_max, bd.num_points, c->d_series_flux.as<double>(), nullptr);
         if (rc == VAG_OK)
@@ -3941,11 +3616,9 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
                       req.lim ? req.llay.band[g] : -1, req.noise ? req.nlay.band[g] : -1, req.noise ? req.nlay.band_present[g] : 0u,
                       req.tmpl ? req.tlay.band[g] : -1, req.tmpl ? req.tlay.band_present[g] : 0u);
     }
-    size_t soff = 0;
     for (int g = 0; g < n_groups && rc == VAG_OK; ++g) {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
         const vag_centroid_obs& o = sky->groups[g];
-        const double* ds = c->sky.d.as<double>() + soff;  // [nu | t | east | north | err_east | err_north | weight]
-        soff += 1 + 6 * (size_t)o.n;
+        const double* ds = c->sky.d.as<double>() + req.slay.off[g];  // [nu | t | east | north | err_east | err_north | weight]
         if (c->d_skycmom.ensure(sizeof(double) * (size_t)nb * o.n * 6)) return VAG_E_HIP;
         rc = prep_times(c, ds + 1, o.n, ds, 1);
         begin_pass();
@@ -3959,7 +3632,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     }
     for (int g = 0; g < n_vis_groups && rc == VAG_OK; ++g) {  // visibility groups: one pass each, the chi^2 formed by the chi2 kernel
         const vag_visibility_obs& o = req.vis->groups[g];
-        const vag_ctx::VisLayout& lay = c->vis_layout[g];
+        const VisLayout& lay = c->vis_layout[g];
         const double* ds = c->vis.d.as<double>() + lay.obs_off;  // [nu | t | ...]
         rc = prep_times(c, ds + 1, o.n_epochs, ds, 1);
         begin_pass();
@@ -3981,7 +3654,6 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
             rc = end_pass();
         }
     }
-    size_t poff = 0;
     if (n_pol_groups > 0 && rc == VAG_OK) {  // the walkers' own field: once per call, in the evaluation order of d_params
         if (c->d_polspec.ensure(sizeof(double) * 5 * (size_t)nb)) return VAG_E_HIP;  // [nb][4] spec | int [nb] flags
         hipLaunchKernelGGL(vag_fit_pol_spec_kernel, dim3((nb + 127) / 128), dim3(128), 0, st, d_theta, nb, ndim, d_prior, d_params,
@@ -3991,8 +3663,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     }
     for (int g = 0; g < n_pol_groups && rc == VAG_OK; ++g) {  // polarization groups: one pass each, the Stokes sums of sky_request
         const vag_polarization_obs& o = req.pol->groups[g];
-        const double* ds = c->pol.d.as<double>() + poff;  // [nu | t | q | u | err_q | err_u | weight]
-        poff += 1 + 6 * (size_t)o.n;
+        const double* ds = c->pol.d.as<double>() + req.play.off[g];  // [nu | t | q | u | err_q | err_u | weight]
         if (c->d_polstokes.ensure(sizeof(double) * (size_t)nb * o.n * 3)) return VAG_E_HIP;
         rc = prep_times(c, ds + 1, o.n, ds, 1);
         begin_pass();
@@ -4099,18 +3770,8 @@ static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int n
     if (!req.spec || !d_theta || !d_out) return set_err(VAG_E_INVALID, "null spec or device pointer");
     if (nb <= 0) return set_err(VAG_E_INVALID, "batch must be non-empty");
     HIPCHK(hipSetDevice(c->device));
-    rc = upload_fit_spec(c, req.spec, ndim, req.placed, req.pol != nullptr, req.noise ? req.nlay.n_groups : 0,
-                         req.counts || req.index || req.fold || req.cov, req.fold && req.flay.any_sigma, req.tlay.n_templates);
-    if (rc == VAG_OK && req.sky) rc = upload_sky_spec(c, req.sky);  // (n_groups = 0: the fixed placement alone)
-    if (rc == VAG_OK && req.vis) rc = upload_vis_spec(c, req.vis);
-    if (rc == VAG_OK && req.pol) rc = upload_pol_spec(c, req.pol);
-    if (rc == VAG_OK && req.lim) rc = upload_lim_spec(c, req.lstage, req.llay);
-    if (rc == VAG_OK && req.noise) rc = upload_noise_spec(c, req.nstage, req.nlay);
-    if (rc == VAG_OK && req.counts) rc = upload_counts_spec(c, req.counts, req.cstage, req.clay);
-    if (rc == VAG_OK && req.index) rc = upload_index_spec(c, req.index, req.istage);
-    if (rc == VAG_OK && req.fold) rc = upload_fold_spec(c, req.fold, req.fstage);
-    if (rc == VAG_OK && req.tmpl) rc = upload_tmpl_spec(c, req.tstage, req.tlay);
-    if (rc == VAG_OK && req.cov) rc = upload_cov_spec(c, req.cov, req.vstage);
+    req.ndim = ndim;
+    rc = upload_blocks(c, req);
     if (rc) return rc;
     rc = loglike_body(c, req, d_theta, nb, ndim, d_out, !c->count_work);
     if (rc == VAG_RETRY) rc = loglike_body(c, req, d_theta, nb, ndim, d_out, false);
@@ -4326,10 +3987,9 @@ static int shard_begin(vag_ctx* c, const vag_fit_spec* spec, const double* d_the
     if (c->d_shard_theta.ensure(sizeof(double) * (size_t)per * ndim)) return VAG_E_HIP;
     if (c->d_shard_ll.ensure(sizeof(double) * (size_t)per)) return VAG_E_HIP;
     // every rank needs the same deal, whether or not it holds a walker: the key of the costs is the spec's content hash
-    {
-        const int rc = upload_fit_spec(c, spec, ndim);
-        if (rc) return rc;
-    }
+    FitRequest req = fit_request(spec);  // (the fit block alone, no optional block)
+    req.ndim = ndim;
+    if (const int rc = upload_blocks(c, req, true)) return rc;
     int entry = -1, victim = -1;
     for (int i = 0; i < 4; ++i) {
         const vag_ctx::ShardCosts& e = c->shard_costs[i];
@@ -4370,7 +4030,6 @@ static int shard_begin(vag_ctx* c, const vag_fit_spec* spec, const double* d_the
     c->shard_last_dealt = slot;  // (kept for inspection even if the evaluation below fails)
     const int* d_order = nullptr;
     if (n_mine > 0) {
-        FitRequest req = fit_request(spec);
         int rc = loglike_body(c, req, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>(), !c->count_work);
         if (rc == VAG_RETRY) rc = loglike_body(c, req, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>(), false);
         if (rc) {  // (no block went out: there is nothing to finish, the slot is free)

@@ -1,7 +1,10 @@
-// vag_fit_request.h -- the host side of one likelihood request: the scans that validate the optional spec blocks and lay them out for
-// the device (int32 arrays packed into doubles, transposed whiteners, ...), the request that carries them, and its normalisation.
-// Plain C++17, no device header and no context: a host compiler builds it, and tests/fit_request_check.cpp runs every scan under
-// the host sanitizers.  vag_capi.hip, the one translation unit of the library, includes it and uploads what the scans staged.
+// vag_fit_request.h -- the host side of one likelihood request: what is done to its eleven spec blocks before a HIP call, the request
+// that carries them, and its normalisation.  Two conventions.  Scanned every call (lim, noise, tmpl, counts, index, fold, cov): *_scan
+// validates the block and lays it out in a stage vector (int32 arrays packed into doubles, transposed whiteners, ...); a miss copies
+// it.  Hashed in place, filled on a miss (fit, sky, vis, pol): *_scan makes the cheap checks and hashes the caller's arrays where they
+// lie; only a miss runs *_rows (the row validation), then *_fill (into the pinned buffer).  Either way the scan leaves the block's
+// BlockKey and its offsets in a *Layout, which the passes read.  Plain C++17, no device header and no context: a host compiler builds
+// it, and tests/fit_request_check.cpp runs it under the host sanitizers.  vag_capi.hip keeps the uploads and the launches.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -34,13 +37,28 @@ static uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
     for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
     return h;
 }
+constexpr uint64_t FNV_SEED = 1469598103934665603ull;
+
+// what says whether a block is resident already: the hash of its content, and its size.  Every *Layout is one.
+struct BlockKey { uint64_t hash = 0; size_t doubles = 0; };
+
+// The key of a block a scan has staged: what tells two layouts of the same bytes apart is in h already -- the passes' offsets, or the
+// groups' shapes -- and the bytes follow.
+static void key_staged(BlockKey& k, uint64_t h, const std::vector<double>& stage) {
+    k.hash = fnv1a(h, stage.data(), sizeof(double) * stage.size());
+    k.doubles = stage.size();
+}
+static uint64_t hash_offsets(long point, const std::vector<long>& band) {
+    const uint64_t h = fnv1a(FNV_SEED, &point, sizeof point);
+    return band.empty() ? h : fnv1a(h, band.data(), sizeof(long) * band.size());
+}
 
 // ---- upper-limit rows (vag_loglike_lim_batch): the blocks that hold a limit row, in one device buffer, uploaded like the other spec
 //      blocks when the hash changes.  Layout in doubles: a flux block (the point rows, a band group) of n rows is
 //      [limit | sigma | kind] (n, n, int32 [n] in (n + 1) / 2 doubles), a polarization group's block [kind] alone (its L and sigma are
 //      the group's q and err_q in the pol block).  A block without a limit row is not stored (offset -1): its pass is the pass without
 //      limits.  Rows that are detections hold limit 0 and sigma 1, whatever the caller's arrays hold there. ----
-struct LimLayout {
+struct LimLayout : BlockKey {
     long point = -1;              // offset of the point rows' block in the lim block, or -1
     std::vector<long> band, pol;  // the same per band group / polarization group
     bool any = false;             // some limit row exists
@@ -121,6 +139,8 @@ static int lim_scan(const vag_fit_spec* spec, const vag_pol_fit_spec* pol, const
         lay.pol[g] = (long)stage.size();
         lim_push_kinds(stage, kind, o.n);
     }
+    const uint64_t h = hash_offsets(lay.point, lay.band);
+    key_staged(lay, lay.pol.empty() ? h : fnv1a(h, lay.pol.data(), sizeof(long) * lay.pol.size()), stage);
     return VAG_OK;
 }
 
@@ -128,7 +148,7 @@ static int lim_scan(const vag_fit_spec* spec, const vag_pol_fit_spec* pol, const
 //      in doubles: [sys_fixed 8 | calib 8], then for every pass that holds a grouped row -- the point rows, a band group -- the rows'
 //      group ids (int32 [n] in (n + 1) / 2 doubles).  A pass without a grouped row is not stored (offset -1): it is the pass without
 //      noise groups. ----
-struct NoiseLayout {
+struct NoiseLayout : BlockKey {
     long point = -1;                    // offset of the point rows' ids in the noise block, or -1
     std::vector<long> band;             // the same per band group
     unsigned point_present = 0;         // bit g: some point row is in group g
@@ -195,13 +215,14 @@ static int noise_scan(const vag_fit_spec* spec, const vag_noise_fit_spec* nz, st
             return set_err(VAG_E_INVALID,
                            "noise group %d has a calibration fraction and rows in %d passes: such a group must hold point rows only or "
                            "exactly one band group", g, passes[g]);
+    key_staged(lay, hash_offsets(lay.point, lay.band), stage);
     return VAG_OK;
 }
 
 // ---- additive templates (vag_loglike_tmpl_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
 //      Layout in doubles: [amp_fixed 8], then for every pass with a touched row -- the point rows, a band group -- its values
 //      [n_templates][n].  A pass no template touches is not stored (offset -1): it is the pass without templates. ----
-struct TmplLayout {
+struct TmplLayout : BlockKey {
     long point = -1;                    // offset of the point rows' values in the tmpl block, or -1
     std::vector<long> band;             // the same per band group
     unsigned point_present = 0;         // bit c: template c touches some point row
@@ -256,12 +277,13 @@ static int tmpl_scan(const vag_fit_spec* spec, const vag_template_fit_spec* tp, 
         if (!tp->bands[b] || spec->bands[b].n <= 0) continue;
         if ((rc = push(tp->bands[b], spec->bands[b].n, "band group", b, lay.band[b], lay.band_present[b]))) return rc;
     }
+    key_staged(lay, hash_offsets(lay.point, lay.band), stage);
     return VAG_OK;
 }
 
 // ---- counts groups (vag_loglike_counts_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
 //      in doubles, per group: [t_sample ns | N n | B n | a n | w n], then the sample indices (int32 [n m] in (n m + 1) / 2 doubles). ----
-struct CountsLayout {
+struct CountsLayout : BlockKey {
     std::vector<long> off;       // where group g starts in the counts block
     std::vector<double> const2;  // -2 sum_i w_i S_i of group g (vag::poisson_const): the walker-independent half of its chi^2
     int n_groups = 0;
@@ -272,8 +294,11 @@ static int counts_scan(const vag_counts_fit_spec* cs, std::vector<double>& stage
     if (cs->n_groups < 0 || !cs->groups) return set_err(VAG_E_INVALID, "counts groups: n_groups must be >= 0 with a group list, got %d", cs->n_groups);
     lay.n_groups = cs->n_groups;
     stage.clear();
+    uint64_t h = FNV_SEED;  // (the shapes: two groups whose blocks hold the same bytes are still two layouts; so index, fold, cov)
     for (int g = 0; g < cs->n_groups; ++g) {
         const vag_counts_obs& o = cs->groups[g];
+        const int head[4] = {o.n, o.m, o.n_samples, o.num_points};
+        h = fnv1a(h, head, sizeof head);
         if (!(std::isfinite(o.nu_min) && std::isfinite(o.nu_max) && o.nu_min > 0 && o.nu_max > o.nu_min))
             return set_err(VAG_E_INVALID, "counts group %d: the band needs 0 < nu_min < nu_max, both finite", g);
         if (o.num_points < 2 || o.num_points > VAG_MAX_NU)
@@ -318,13 +343,14 @@ static int counts_scan(const vag_counts_fit_spec* cs, std::vector<double>& stage
         }
         std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
     }
+    key_staged(lay, h, stage);
     return VAG_OK;
 }
 
 // ---- spectral-index groups (vag_loglike_index_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
 //      Layout in doubles, per group: [t n K | nu n K | s n | sigma n | w n | c K]; the first two are the series points (t_i, nu_k), i
 //      outer, as prep_times takes them. ----
-struct IndexLayout {
+struct IndexLayout : BlockKey {
     std::vector<long> off;  // where group g starts in the index block
     int n_groups = 0;
 };
@@ -335,8 +361,11 @@ static int index_scan(const vag_index_fit_spec* is, std::vector<double>& stage, 
     lay.n_groups = is->n_groups;
     lay.off.clear();
     stage.clear();
+    uint64_t h = FNV_SEED;
     for (int g = 0; g < is->n_groups; ++g) {
         const vag_index_obs& o = is->groups[g];
+        const int head[2] = {o.n, o.k};
+        h = fnv1a(h, head, sizeof head);
         if (o.k < 2 || o.k > VAG_INDEX_MAX_NODES)
             return set_err(VAG_E_INVALID, "index group %d: k (frequencies) must be in 2..%d, got %d", g, VAG_INDEX_MAX_NODES, o.k);
         if (o.n < 1) return set_err(VAG_E_INVALID, "index group %d has no rows", g);
@@ -373,6 +402,7 @@ static int index_scan(const vag_index_fit_spec* is, std::vector<double>& stage, 
         }
         std::memcpy(dst, o.coef, sizeof(double) * K);
     }
+    key_staged(lay, h, stage);
     return VAG_OK;
 }
 
@@ -380,7 +410,7 @@ static int index_scan(const vag_index_fit_spec* is, std::vector<double>& stage, 
 //      doubles, per group: [t ns J | nu ns J | A J C | sigma J | exposure / m n | N n C | B n C | w n C], then the sample indices
 //      (int32 [n m] in (n m + 1) / 2 doubles); the first two are the series points (t_sample_s, nu_j), s outer, as prep_times takes
 //      them; sigma is zeros for a group without one (the kernel is handed a null pointer then). ----
-struct FoldLayout {
+struct FoldLayout : BlockKey {
     std::vector<long> off;       // where group g starts in the fold block
     std::vector<double> const2;  // -2 sum_{i,c} w S of group g (vag::poisson_const): the walker-independent half of its chi^2
     bool any_sigma = false;      // some group carries a cross-section: N_H is read
@@ -396,8 +426,11 @@ static int fold_scan(const vag_fit_spec* spec, const vag_fold_fit_spec* fs, std:
     lay.const2.clear();
     lay.any_sigma = false;
     stage.clear();
+    uint64_t h = FNV_SEED;
     for (int g = 0; g < fs->n_groups; ++g) {
         const vag_fold_obs& o = fs->groups[g];
+        const int head[6] = {o.J, o.C, o.n, o.m, o.n_samples, o.sigma ? 1 : 0};
+        h = fnv1a(h, head, sizeof head);
         if (o.J < 1 || o.J > VAG_FOLD_MAX_BINS)
             return set_err(VAG_E_INVALID, "fold group %d: J (energy bins) must be in 1..%d, got %d", g, VAG_FOLD_MAX_BINS, o.J);
         if (o.C < 1 || o.C > VAG_FOLD_MAX_CHANNELS)
@@ -473,6 +506,7 @@ static int fold_scan(const vag_fit_spec* spec, const vag_fold_fit_spec* fs, std:
     if (!lay.any_sigma)
         for (int d = 0; d < spec->ndim && d < 16; ++d)
             if (spec->slot[d] == VAG_P_N_H) return set_err(VAG_E_INVALID, "bad parameter slot");
+    key_staged(lay, h, stage);
     return VAG_OK;
 }
 
@@ -480,7 +514,7 @@ static int fold_scan(const vag_fit_spec* spec, const vag_fold_fit_spec* fs, std:
 //      in doubles, per group: [t n | nu n | ln_flux n | ext n | Wt n n]; the first two are the series points as prep_times takes
 //      them; ext is zeros for a group without one (the kernel is handed a null pointer then); Wt[j n + i] = W_ij for j <= i, else 0:
 //      the whitener transposed, so that a wavefront whose lanes hold consecutive rows i loads consecutive doubles. ----
-struct CovLayout {
+struct CovLayout : BlockKey {
     std::vector<long> off;  // where group g starts in the cov block
     int n_groups = 0;
 };
@@ -493,8 +527,11 @@ static int cov_scan(const vag_cov_fit_spec* cs, std::vector<double>& stage, CovL
     lay.n_groups = cs->n_groups;
     lay.off.clear();
     stage.clear();
+    uint64_t h = FNV_SEED;
     for (int g = 0; g < cs->n_groups; ++g) {
         const vag_cov_obs& o = cs->groups[g];
+        const int head[2] = {o.n, o.ext ? 1 : 0};
+        h = fnv1a(h, head, sizeof head);
         if (o.n < 1 || o.n > VAG_COV_MAX_ROWS)
             return set_err(VAG_E_INVALID, "correlated group %d: n (rows) must be in 1..%d, got %d", g, VAG_COV_MAX_ROWS, o.n);
         if (!o.t || !o.nu || !o.ln_flux || !o.whitener) return set_err(VAG_E_INVALID, "correlated group %d: null array", g);
@@ -526,7 +563,302 @@ static int cov_scan(const vag_cov_fit_spec* cs, std::vector<double>& stage, CovL
         for (size_t i = 0; i < n; ++i)
             for (size_t j = 0; j <= i; ++j) Wt[j * n + i] = o.whitener[i * n + j];
     }
+    key_staged(lay, h, stage);
     return VAG_OK;
+}
+
+// ---- the fit spec (every vag_loglike_*_batch): the observation arrays, the slot map and the priors in one device buffer.  Layout in
+//      doubles: [t | nu | ln_flux | ln_err | weight | ext] (n each, in 6 max(n, 1); ext is zeros without an ext_kernel), then per band
+//      group [t | ln_flux | ln_err | weight] (bd.n each), then [lower | upper | prior_a | prior_b] (16 each), then int32
+//      [slot | is_log | prior_kind] (16 each). ----
+struct FitLayout : BlockKey {
+    size_t nu = 0, ln_flux = 0, ln_err = 0, weight = 0, ext = 0;  // the point rows' columns (t is at 0)
+    std::vector<size_t> band;                                     // where band group g starts
+    size_t prior = 0;                                             // where the prior block starts
+};
+
+// The slots a fit spec may free beyond the model's own, by what else the request holds: the placement (some group reads it), the
+// field of polarization groups, N_H (a fold group with a cross-section), the systematic of a noise group and the amplitude of a
+// template that exist.  counts: some group is data without a flux row (counts, index, fold, cov).
+struct FitAccepts {
+    bool sky = false, pol = false, n_h = false, counts = false;
+    int noise_groups = 0, n_templates = 0;
+};
+
+static int fit_scan(const vag_fit_spec* spec, int ndim, const FitAccepts& acc, FitLayout& lay) {
+    if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
+    const int n = spec->n_data;
+    if (n < 0 || spec->n_bands < 0 || (n == 0 && spec->n_bands == 0 && !acc.sky && !acc.pol && !acc.counts))
+        return set_err(VAG_E_INVALID, "fit spec has no data");
+    for (int d = 0; d < ndim; ++d) {
+        const int s = spec->slot[d];
+        if (s == VAG_P_A_V) continue;
+        if (acc.sky && s >= VAG_P_SKY_PA && s <= VAG_P_SKY_NORTH0) continue;
+        if (acc.pol && (s == VAG_P_SKY_PA || (s >= VAG_P_POL_B && s <= VAG_P_POL_PI_MAX_RVS))) continue;
+        if (s >= VAG_P_NOISE_SYS0 && s < VAG_P_NOISE_SYS0 + acc.noise_groups) continue;
+        if (acc.n_h && s == VAG_P_N_H) continue;
+        if (s >= VAG_P_TMPL_AMP0 && s < VAG_P_TMPL_AMP0 + acc.n_templates) continue;
+        if (s < 0 || (s >= VAG_P_COUNT && (s < VAG_P_RVS_EPS_E || s > VAG_P_MAG_Q))) return set_err(VAG_E_INVALID, "bad parameter slot");
+    }
+    if (spec->use_priors)
+        for (int d = 0; d < ndim; ++d) {
+            if (!(spec->lower[d] < spec->upper[d])) return set_err(VAG_E_INVALID, "prior bounds of parameter %d: need lower < upper", d);
+            const int k = spec->prior_kind[d];
+            if (k < VAG_PRIOR_UNIFORM || k > VAG_PRIOR_UNIFORM_RANGE) return set_err(VAG_E_INVALID, "unknown prior kind %d", k);
+            if (k == VAG_PRIOR_UNIFORM_RANGE && !(spec->prior_b[d] > spec->prior_a[d])) return set_err(VAG_E_INVALID, "Uniform prior needs maximum > minimum");
+            if (k == VAG_PRIOR_GAUSSIAN && !(spec->prior_b[d] > 0)) return set_err(VAG_E_INVALID, "Gaussian prior needs sigma > 0");
+            if (k == VAG_PRIOR_LOG_UNIFORM && !(spec->prior_a[d] > 0 && spec->prior_b[d] > spec->prior_a[d]))
+                return set_err(VAG_E_INVALID, "LogUniform prior needs 0 < minimum < maximum");
+        }
+    const int head[4] = {n, spec->n_bands, ndim, spec->ext_kernel ? 1 : 0};
+    uint64_t& h = lay.hash = fnv1a(FNV_SEED, head, sizeof head);
+    lay.nu = n, lay.ln_flux = 2 * (size_t)n, lay.ln_err = 3 * (size_t)n, lay.weight = 4 * (size_t)n, lay.ext = 5 * (size_t)n;
+    size_t total = 6 * (size_t)std::max(n, 1);
+    for (const double* arr : {spec->t, spec->nu, spec->ln_flux, spec->ln_err, spec->weight, spec->ext_kernel})
+        if (arr && n > 0) h = fnv1a(h, arr, sizeof(double) * n);
+    lay.band.clear();
+    for (int g = 0; g < spec->n_bands; ++g) {
+        const vag_band_obs& bd = spec->bands[g];
+        if (bd.n <= 0) return set_err(VAG_E_INVALID, "band group %d has no observations", g);
+        h = fnv1a(h, &bd.n, sizeof bd.n);
+        for (const double* arr : {bd.t, bd.ln_flux, bd.ln_err, bd.weight}) h = fnv1a(h, arr, sizeof(double) * bd.n);
+        lay.band.push_back(total);
+        total += 4 * (size_t)bd.n;
+    }
+    h = fnv1a(h, spec->slot, sizeof spec->slot);
+    h = fnv1a(h, spec->is_log, sizeof spec->is_log);
+    h = fnv1a(h, &spec->use_priors, sizeof spec->use_priors);
+    if (spec->use_priors) {
+        h = fnv1a(fnv1a(h, spec->lower, sizeof spec->lower), spec->upper, sizeof spec->upper);
+        h = fnv1a(h, spec->prior_kind, sizeof spec->prior_kind);
+        h = fnv1a(fnv1a(h, spec->prior_a, sizeof spec->prior_a), spec->prior_b, sizeof spec->prior_b);
+    }
+    lay.prior = total;
+    lay.doubles = total + 4 * 16 + 3 * 16 / 2;  // four double[16] + three int32[16]
+    return VAG_OK;
+}
+
+static int fit_rows(const vag_fit_spec* spec) {
+    const int n = spec->n_data;
+    for (int i = 0; i < n; ++i)
+        if (!(spec->t[i] > 0)) return set_err(VAG_E_INVALID, "data times must be positive");
+    for (int i = 1; i < n; ++i)
+        if (spec->t[i] < spec->t[i - 1]) return set_err(VAG_E_INVALID, "data times must be ascending (fitter.py:420-428)");
+    for (int g = 0; g < spec->n_bands; ++g) {
+        const vag_band_obs& bd = spec->bands[g];
+        for (int i = 0; i < bd.n; ++i)
+            if (!(bd.t[i] > 0) || (i > 0 && bd.t[i] < bd.t[i - 1]))
+                return set_err(VAG_E_INVALID, "band group %d: times must be positive and ascending", g);
+    }
+    return VAG_OK;
+}
+
+static void fit_fill(const vag_fit_spec* spec, const FitLayout& lay, double* hp) {
+    const size_t n = (size_t)spec->n_data;
+    std::memset(hp, 0, sizeof(double) * lay.doubles);
+    const double* src[6] = {spec->t, spec->nu, spec->ln_flux, spec->ln_err, spec->weight, spec->ext_kernel};
+    const size_t at[6] = {0, lay.nu, lay.ln_flux, lay.ln_err, lay.weight, lay.ext};
+    for (int q = 0; q < 6 && n > 0; ++q)
+        if (src[q]) std::memcpy(hp + at[q], src[q], sizeof(double) * n);
+    for (int g = 0; g < spec->n_bands; ++g) {
+        const vag_band_obs& bd = spec->bands[g];
+        const double* col[4] = {bd.t, bd.ln_flux, bd.ln_err, bd.weight};
+        for (int q = 0; q < 4; ++q) std::memcpy(hp + lay.band[g] + (size_t)q * bd.n, col[q], sizeof(double) * bd.n);
+    }
+    const double* pd[4] = {spec->lower, spec->upper, spec->prior_a, spec->prior_b};
+    for (int q = 0; q < 4; ++q) std::memcpy(hp + lay.prior + 16 * q, pd[q], sizeof spec->lower);
+    const int32_t* pi[3] = {spec->slot, spec->is_log, spec->prior_kind};
+    for (int q = 0; q < 3; ++q) std::memcpy(hp + lay.prior + 64 + 8 * q, pi[q], sizeof spec->slot);
+}
+
+// ---- centroid groups (vag_loglike_sky_batch) and polarization groups (vag_loglike_pol_batch): one device buffer each, of one shape.
+//      Layout in doubles, per group: [nu | six arrays of n] (1 + 6 n) -- [t | east | north | err_east | err_north | weight] of a centroid
+//      group, [t | q | u | err_q | err_u | weight] of a polarization group, u and err_u of a DEGREE group zeros. ----
+struct SixGroup {  // one such group; a null array is stored as zeros
+    double nu;
+    int n;
+    const double* col[6];
+};
+static void six_cols(const double* const col[6], size_t n, double* dst) {  // n doubles of each array, zeros for a null one
+    for (int q = 0; q < 6; ++q, dst += n) {
+        if (col[q])
+            std::memcpy(dst, col[q], sizeof(double) * n);
+        else
+            std::memset(dst, 0, sizeof(double) * n);
+    }
+}
+static SixGroup six_group(const vag_centroid_obs& o) { return {o.nu, o.n, {o.t, o.east, o.north, o.err_east, o.err_north, o.weight}}; }
+static SixGroup six_group(const vag_polarization_obs& o) {
+    const bool qu = o.kind == VAG_POL_QU;
+    return {o.nu, o.n, {o.t, o.q, qu ? o.u : nullptr, o.err_q, qu ? o.err_u : nullptr, o.weight}};
+}
+
+struct SixLayout : BlockKey { std::vector<size_t> off; };  // off: where group g starts in the block
+using SkyLayout = SixLayout;
+using PolLayout = SixLayout;
+
+static void six_begin(SixLayout& lay, int n_groups) { lay = {}, lay.hash = fnv1a(FNV_SEED, &n_groups, sizeof n_groups); }
+// hash and place of the next group: nu, its shape integers, the arrays it has
+static void six_push(SixLayout& lay, const SixGroup& g, const int* head, size_t n_head) {
+    lay.hash = fnv1a(fnv1a(lay.hash, &g.nu, sizeof g.nu), head, sizeof(int) * n_head);
+    for (const double* arr : g.col)
+        if (arr) lay.hash = fnv1a(lay.hash, arr, sizeof(double) * g.n);
+    lay.off.push_back(lay.doubles);
+    lay.doubles += 1 + 6 * (size_t)g.n;
+}
+template <class Spec>
+static void six_fill(const Spec* s, const SixLayout& lay, double* hp) {
+    for (int g = 0; g < s->n_groups; ++g) {
+        const SixGroup o = six_group(s->groups[g]);
+        hp[lay.off[g]] = o.nu;
+        six_cols(o.col, o.n, hp + lay.off[g] + 1);
+    }
+}
+
+static int sky_scan(const vag_sky_fit_spec* sky, SkyLayout& lay) {
+    if (sky->n_groups < 0 || (sky->n_groups > 0 && !sky->groups)) return set_err(VAG_E_INVALID, "bad centroid group list");
+    for (double v : {sky->pa_fixed, sky->east0_fixed, sky->north0_fixed})
+        if (!std::isfinite(v)) return set_err(VAG_E_INVALID, "fixed sky placement values must be finite");
+    six_begin(lay, sky->n_groups);
+    for (int g = 0; g < sky->n_groups; ++g) {
+        const vag_centroid_obs& o = sky->groups[g];
+        if (o.n <= 0) return set_err(VAG_E_INVALID, "centroid group %d has no observations", g);
+        if (!o.t || !o.east || !o.north || !o.err_east || !o.err_north || !o.weight) return set_err(VAG_E_INVALID, "centroid group %d: null array", g);
+        six_push(lay, six_group(o), &o.n, 1);
+    }
+    return VAG_OK;
+}
+
+static int sky_rows(const vag_sky_fit_spec* sky) {
+    for (int g = 0; g < sky->n_groups; ++g) {
+        const vag_centroid_obs& o = sky->groups[g];
+        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "centroid group %d: frequency must be positive", g);
+        for (int i = 0; i < o.n; ++i) {
+            if (!(o.t[i] > 0) || !std::isfinite(o.t[i]) || (i > 0 && o.t[i] < o.t[i - 1]))
+                return set_err(VAG_E_INVALID, "centroid group %d: times must be positive and ascending", g);
+            if (!std::isfinite(o.east[i]) || !std::isfinite(o.north[i]) || !std::isfinite(o.weight[i]))
+                return set_err(VAG_E_INVALID, "centroid group %d: positions and weights must be finite", g);
+            if (!(o.err_east[i] > 0) || !(o.err_north[i] > 0) || !std::isfinite(o.err_east[i]) || !std::isfinite(o.err_north[i]))
+                return set_err(VAG_E_INVALID, "centroid group %d: errors must be positive and finite", g);
+        }
+    }
+    return VAG_OK;
+}
+
+static int pol_scan(const vag_pol_fit_spec* pol, PolLayout& lay) {
+    if (pol->n_groups < 0 || !pol->groups) return set_err(VAG_E_INVALID, "bad polarization group list");
+    if (pol->n_groups > VAG_POL_MAX_GROUPS) return set_err(VAG_E_INVALID, "at most %d polarization groups", VAG_POL_MAX_GROUPS);
+    for (int e = 0; e < 2; ++e)
+        if (std::isnan(pol->b_fixed[e]) || std::isnan(pol->pi_max_fixed[e]))
+            return set_err(VAG_E_INVALID, "fixed polarization values must not be NaN");
+    six_begin(lay, pol->n_groups);
+    for (int g = 0; g < pol->n_groups; ++g) {
+        const vag_polarization_obs& o = pol->groups[g];
+        if (o.n < 1) return set_err(VAG_E_INVALID, "polarization group %d has no observations", g);
+        if (o.n > VAG_VIS_MAX_EPOCHS) return set_err(VAG_E_INVALID, "polarization group %d: at most %d epochs", g, VAG_VIS_MAX_EPOCHS);
+        if (o.kind != VAG_POL_QU && o.kind != VAG_POL_DEGREE) return set_err(VAG_E_INVALID, "polarization group %d: unknown kind %d", g, o.kind);
+        if (!o.t || !o.q || !o.err_q || !o.weight || (o.kind == VAG_POL_QU && (!o.u || !o.err_u)))
+            return set_err(VAG_E_INVALID, "polarization group %d: null array", g);
+        const int head[3] = {o.n, o.n_az > 0 ? o.n_az : 256, o.kind};
+        six_push(lay, six_group(o), head, 3);
+    }
+    return VAG_OK;
+}
+
+static int pol_rows(const vag_pol_fit_spec* pol) {
+    for (int g = 0; g < pol->n_groups; ++g) {
+        const vag_polarization_obs& o = pol->groups[g];
+        const bool qu = o.kind == VAG_POL_QU;
+        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "polarization group %d: frequency must be positive", g);
+        for (int i = 0; i < o.n; ++i) {
+            if (!(o.t[i] > 0) || !std::isfinite(o.t[i]) || (i > 0 && o.t[i] < o.t[i - 1]))
+                return set_err(VAG_E_INVALID, "polarization group %d: times must be positive and ascending", g);
+            if (!std::isfinite(o.q[i]) || (qu && !std::isfinite(o.u[i])) || !std::isfinite(o.weight[i]) || o.weight[i] < 0)
+                return set_err(VAG_E_INVALID, "polarization group %d: measurements must be finite, weights finite and >= 0", g);
+            if (!(o.err_q[i] > 0) || !std::isfinite(o.err_q[i]) || (qu && (!(o.err_u[i] > 0) || !std::isfinite(o.err_u[i]))))
+                return set_err(VAG_E_INVALID, "polarization group %d: errors must be positive and finite", g);
+        }
+    }
+    return VAG_OK;
+}
+
+// ---- visibility groups (vag_loglike_vis_batch): one device buffer.  Layout in doubles, per group: [nu | t | u | v | re | im | err |
+//      weight] (1 + n_epochs + 6 n_vis), im of an AMPLITUDE group zeros; beside it, per group, the blocks of at most 64 visibilities of
+//      one epoch as int32 [epoch, first visibility, visibilities] (d_visblk). ----
+struct VisLayout {               // of one group; made on a miss, from the validated first[]
+    size_t obs_off;              // its data in the vis block [doubles]
+    int blk_off;                 // its blocks in d_visblk [blocks of 3 ints]
+    std::vector<int> epoch_blk;  // [n_epochs + 1]: first block of every epoch
+};
+
+static int vis_scan(const vag_vis_fit_spec* vis, BlockKey& key) {
+    if (vis->n_groups < 0 || !vis->groups) return set_err(VAG_E_INVALID, "bad visibility group list");
+    if (vis->n_groups > VAG_VIS_MAX_GROUPS) return set_err(VAG_E_INVALID, "at most %d visibility groups", VAG_VIS_MAX_GROUPS);
+    key = {fnv1a(FNV_SEED, &vis->n_groups, sizeof vis->n_groups), 0};
+    uint64_t& h = key.hash;
+    for (int g = 0; g < vis->n_groups; ++g) {
+        const vag_visibility_obs& o = vis->groups[g];
+        if (o.n_epochs < 1 || o.n_vis < 1) return set_err(VAG_E_INVALID, "visibility group %d has no observations", g);
+        if (o.n_epochs > VAG_VIS_MAX_EPOCHS) return set_err(VAG_E_INVALID, "visibility group %d: at most %d epochs", g, VAG_VIS_MAX_EPOCHS);
+        if (o.kind != VAG_VIS_COMPLEX && o.kind != VAG_VIS_AMPLITUDE) return set_err(VAG_E_INVALID, "visibility group %d: unknown kind %d", g, o.kind);
+        if (!o.t || !o.first || !o.u || !o.v || !o.re || !o.err || !o.weight || (o.kind == VAG_VIS_COMPLEX && !o.im))
+            return set_err(VAG_E_INVALID, "visibility group %d: null array", g);
+        const int head[4] = {o.n_epochs, o.n_vis, o.n_az > 0 ? o.n_az : 1024, o.kind};
+        h = fnv1a(h, &o.nu, sizeof o.nu);
+        h = fnv1a(h, head, sizeof head);
+        h = fnv1a(h, o.t, sizeof(double) * o.n_epochs);
+        h = fnv1a(h, o.first, sizeof(int32_t) * ((size_t)o.n_epochs + 1));
+        for (const double* arr : {o.u, o.v, o.re, o.kind == VAG_VIS_COMPLEX ? o.im : nullptr, o.err, o.weight})
+            if (arr) h = fnv1a(h, arr, sizeof(double) * o.n_vis);
+        key.doubles += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
+    }
+    return VAG_OK;
+}
+
+// Validates the groups' rows; lays the groups out in layout and cuts their epochs into blocks.
+static int vis_rows(const vag_vis_fit_spec* vis, std::vector<VisLayout>& layout, std::vector<int>& blocks) {
+    layout.assign(vis->n_groups, VisLayout{});
+    blocks.clear();
+    size_t off = 0;
+    for (int g = 0; g < vis->n_groups; ++g) {
+        const vag_visibility_obs& o = vis->groups[g];
+        if (!(o.nu > 0) || !std::isfinite(o.nu)) return set_err(VAG_E_INVALID, "visibility group %d: frequency must be positive", g);
+        if (o.first[0] != 0 || o.first[o.n_epochs] != o.n_vis)
+            return set_err(VAG_E_INVALID, "visibility group %d: first[0] must be 0 and first[n_epochs] n_vis", g);
+        VisLayout& lay = layout[g];
+        lay.obs_off = off;
+        lay.blk_off = (int)(blocks.size() / 3);
+        off += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
+        for (int e = 0; e < o.n_epochs; ++e) {
+            if (!(o.t[e] > 0) || !std::isfinite(o.t[e]) || (e > 0 && !(o.t[e] > o.t[e - 1])))
+                return set_err(VAG_E_INVALID, "visibility group %d: times must be positive and strictly ascending", g);
+            const int k0 = o.first[e], k1 = o.first[e + 1];
+            if (k0 < 0 || k1 > o.n_vis || k1 <= k0) return set_err(VAG_E_INVALID, "visibility group %d: epoch %d is empty or first[] is not ascending", g, e);
+            if (k1 - k0 > VAG_VIS_MAX_PER_EPOCH)
+                return set_err(VAG_E_INVALID, "visibility group %d: at most %d visibilities per epoch", g, VAG_VIS_MAX_PER_EPOCH);
+            lay.epoch_blk.push_back((int)(blocks.size() / 3) - lay.blk_off);
+            for (int k = k0; k < k1; k += 64) blocks.insert(blocks.end(), {e, k, std::min(64, k1 - k)});
+        }
+        lay.epoch_blk.push_back((int)(blocks.size() / 3) - lay.blk_off);
+        for (int k = 0; k < o.n_vis; ++k) {
+            if (!std::isfinite(o.u[k]) || !std::isfinite(o.v[k]) || !std::isfinite(o.re[k]) || (o.kind == VAG_VIS_COMPLEX && !std::isfinite(o.im[k])))
+                return set_err(VAG_E_INVALID, "visibility group %d: baselines and visibilities must be finite", g);
+            if (!(o.err[k] > 0) || !std::isfinite(o.err[k])) return set_err(VAG_E_INVALID, "visibility group %d: errors must be positive and finite", g);
+            if (!(o.weight[k] >= 0) || !std::isfinite(o.weight[k])) return set_err(VAG_E_INVALID, "visibility group %d: weights must be finite and >= 0", g);
+        }
+    }
+    return VAG_OK;
+}
+
+static void vis_fill(const vag_vis_fit_spec* vis, const std::vector<VisLayout>& layout, double* hp) {
+    for (int g = 0; g < vis->n_groups; ++g) {
+        const vag_visibility_obs& o = vis->groups[g];
+        const double* col[6] = {o.u, o.v, o.re, o.kind == VAG_VIS_COMPLEX ? o.im : nullptr, o.err, o.weight};
+        double* dst = hp + layout[g].obs_off;
+        *dst++ = o.nu;
+        std::memcpy(dst, o.t, sizeof(double) * o.n_epochs);
+        six_cols(col, o.n_vis, dst + o.n_epochs);
+    }
 }
 
 // ---- one likelihood request.  Every vag_loglike_*_batch entry point fills a FitRequest from its arguments (a spec it does not take
@@ -545,6 +877,13 @@ struct FitRequest {
     const vag_fold_fit_spec* fold = nullptr;
     const vag_template_fit_spec* tmpl = nullptr;  // after fit_request_prepare: null when no row is touched (tlay.any)
     const vag_cov_fit_spec* cov = nullptr;        // after fit_request_prepare: null when it has no group
+    int ndim = 0;                                 // of the call: fit_scan holds the spec's against it
+    FitLayout fit;                                // the four blocks hashed in place (fit, sky, vis, pol): scanned in the upload sequence
+    SkyLayout slay;
+    BlockKey vkey;
+    PolLayout play;
+    std::vector<VisLayout> vis_groups;  // what vis_rows made on a miss, with vis_blocks: the context keeps them beside the block
+    std::vector<int> vis_blocks;
     LimLayout llay;
     NoiseLayout nlay;
     CountsLayout clay;
@@ -585,13 +924,14 @@ static int fit_request_prepare(FitRequest& r) {
     return VAG_OK;
 }
 
+static FitAccepts fit_accepts(const FitRequest& r) {
+    return {r.placed, r.pol != nullptr, r.fold && r.flay.any_sigma, r.counts || r.index || r.fold || r.cov,
+            r.noise ? r.nlay.n_groups : 0, r.tlay.n_templates};
+}
+
 static FitRequest fit_request(const vag_fit_spec* spec, const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
-                              const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr,
-                              const vag_noise_fit_spec* noise = nullptr, const vag_counts_fit_spec* counts = nullptr,
-                              const vag_index_fit_spec* index = nullptr, const vag_fold_fit_spec* fold = nullptr,
-                              const vag_template_fit_spec* tmpl = nullptr, const vag_cov_fit_spec* cov = nullptr) {
-    FitRequest r;
-    r.spec = spec, r.sky = sky, r.vis = vis, r.pol = pol, r.lim = lim, r.noise = noise, r.counts = counts, r.index = index, r.fold = fold;
-    r.tmpl = tmpl, r.cov = cov;
-    return r;
+                              const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr, const vag_noise_fit_spec* noise = nullptr,
+                              const vag_counts_fit_spec* counts = nullptr, const vag_index_fit_spec* index = nullptr,
+                              const vag_fold_fit_spec* fold = nullptr, const vag_template_fit_spec* tmpl = nullptr, const vag_cov_fit_spec* cov = nullptr) {
+    return FitRequest{spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl, cov};
 }
