@@ -919,6 +919,57 @@ int vag_loglike_cov_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_
                               const vag_template_fit_spec* tmpl, const vag_cov_fit_spec* cov, const double* d_theta, int nb, int ndim,
                               double* d_out);
 
+/* The ensemble sampler on the device (added after VAG_ABI_VERSION 13, detect by symbol): the Goodman & Weare stretch move in its
+ * parallel form with fixed halves (Foreman-Mackey et al. 2013, section 3).  n_walkers is even and >= 2 ndim; half 0 is walkers
+ * [0, n_walkers / 2), half 1 the rest; a step updates half 0 against half 1, then half 1 against the updated half 0; there is no
+ * permutation.  The draws are Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85) with key
+ * (seed & 0xffffffff, seed >> 32) and counter (w, step & 0xffffffff, step >> 32, stream): w the walker's index in the whole
+ * ensemble, step the absolute step number, stream 0 the proposal and 1 the acceptance.  A uniform of two output words is
+ * u(hi, lo) = ((hi >> 5) 2^26 + (lo >> 6)) 2^-53.  With x0..x3 of stream 0: u_z = u(x0, x1), the partner is walker
+ * (uint64(x2) half) >> 32 of the other half, t = fma(a - 1, u_z, 1), z = t t / a (the largest double below a where that quotient reaches a), prop[d] = fma(z, pos[w][d] - pos[partner][d],
+ * pos[partner][d]).  With y0, y1 of stream 1: u_a = u(y0, y1); a proposal whose ln p is not finite is rejected, any other is accepted
+ * iff log(u_a) < (ndim - 1) log(z) + (lp_new - lp[w]).  A chain is therefore a function of (seed, step, walker) and of ln p alone. */
+typedef struct vag_loglike_request {  /* the spec blocks of vag_loglike_cov_batch_dev; a null pointer: the block is absent */
+    const vag_fit_spec* spec;
+    const vag_sky_fit_spec* sky;
+    const vag_vis_fit_spec* vis;
+    const vag_pol_fit_spec* pol;
+    const vag_limit_fit_spec* lim;
+    const vag_noise_fit_spec* noise;
+    const vag_counts_fit_spec* counts;
+    const vag_index_fit_spec* index;
+    const vag_fold_fit_spec* fold;
+    const vag_template_fit_spec* tmpl;
+    const vag_cov_fit_spec* cov;
+} vag_loglike_request;
+typedef struct vag_stretch_spec {
+    uint64_t seed;
+    double a;           /* the stretch scale, finite and > 1 (2 is customary) */
+    int32_t n_walkers;  /* even, >= 2 ndim */
+    int32_t ndim;       /* 1 .. 16 */
+    int32_t thin;       /* >= 1: step s is stored when (s + 1) % thin == 0 */
+} vag_stretch_spec;
+
+/* The two halves of a half-step as building blocks (no model): a caller with an evaluator of its own -- a sharded one -- puts its
+ * call between them.  half is 0 or 1; d_pos[n_walkers][ndim], d_prop[n_walkers / 2][ndim] the proposals of the half's walkers in
+ * their order, d_lp_new[n_walkers / 2] their ln p, d_lp[n_walkers] ln p of d_pos, d_accepted[n_walkers] counts.  Stream-ordered on
+ * the context's stream, no host synchronisation.  Refused with VAG_E_INVALID (the context stays usable): a null context, spec or
+ * buffer; n_walkers odd or < 2 ndim; ndim outside 1 .. 16; a not finite or <= 1; thin < 1; half not 0 or 1. */
+int vag_stretch_propose_dev(vag_ctx* ctx, const vag_stretch_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop);
+int vag_stretch_accept_dev(vag_ctx* ctx, const vag_stretch_spec* sp, uint64_t step, int half, const double* d_prop,
+                           const double* d_lp_new, double* d_pos, double* d_lp, int64_t* d_accepted);
+
+/* Steps step0 .. step0 + n_steps - 1 of the move on the likelihood of `request` (ln L + ln prior with the bounds mask under
+ * spec->use_priors): per step and half, propose, the likelihood call of the n_walkers / 2 proposals, accept.  On entry d_lp holds
+ * ln p of d_pos.  The blocks are scanned and uploaded once per call; between the steps there is no copy and no stream synchronisation
+ * (a likelihood call itself waits for its device plan, as vag_loglike_batch_dev does).  A stored step writes its row
+ * [n_walkers][ndim] of d_chain and [n_walkers] of d_logp; rows are consecutive from the pointers given, which the caller sizes and
+ * moves between calls; both null: nothing is stored.  n_steps = 0 does nothing and returns VAG_OK.  Refusals as above, and:
+ * a null request or request->spec, ndim different from request->spec->ndim, n_steps < 0, one of d_chain / d_logp null alone, and
+ * whatever the likelihood call refuses. */
+int vag_stretch_run_dev(vag_ctx* ctx, const vag_loglike_request* request, const vag_stretch_spec* sp, uint64_t step0, int n_steps,
+                        double* d_pos, double* d_lp, int64_t* d_accepted, double* d_chain, double* d_logp);
+
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.
  * Stream-ordered on the context stream, but host-blocking: the call returns after the batch's device plan has been read back

@@ -199,6 +199,28 @@ class FitSpec(C.Structure):
     ]
 
 
+class LoglikeRequest(C.Structure):  # vag_loglike_request: the spec blocks of the widest likelihood entry, None = absent
+    _fields_ = [("spec", C.POINTER(FitSpec)), ("sky", C.POINTER(SkyFitSpec)), ("vis", C.POINTER(VisFitSpec)), ("pol", C.POINTER(PolFitSpec)),
+                ("lim", C.POINTER(LimitFitSpec)), ("noise", C.POINTER(NoiseFitSpec)), ("counts", C.POINTER(CountsFitSpec)),
+                ("index", C.POINTER(IndexFitSpec)), ("fold", C.POINTER(FoldFitSpec)), ("tmpl", C.POINTER(TemplateFitSpec)),
+                ("cov", C.POINTER(CovFitSpec))]
+
+
+class StretchSpec(C.Structure):  # vag_stretch_spec
+    _fields_ = [("seed", C.c_uint64), ("a", C.c_double), ("n_walkers", C.c_int32), ("ndim", C.c_int32), ("thin", C.c_int32)]
+
+
+STRETCH_ENTRIES = ("vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev")
+
+
+def stretch_entry(lib, name):
+    """One of the device sampler's entry points, added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build)."""
+    if not hasattr(lib, name):
+        raise RuntimeError(f"the loaded library has no {name}: the device sampler (sampling.StretchMove, run_stretch_move_device, "
+                           "fit(sampler='device')) needs a newer build")
+    return getattr(lib, name)
+
+
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_LOG_UNIFORM, PRIOR_NONE, PRIOR_UNIFORM_RANGE = 0, 1, 2, 3, 4
 
 
@@ -251,7 +273,7 @@ EXPORTS = [
     "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev", "vag_loglike_noise_batch", "vag_loglike_noise_batch_dev",
     "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev", "vag_loglike_index_batch", "vag_loglike_index_batch_dev",
     "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev", "vag_loglike_tmpl_batch", "vag_loglike_tmpl_batch_dev",
-    "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev",
+    "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev", "vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev",
 ]
 
 _lib = None
@@ -348,6 +370,11 @@ def load():
         if hasattr(lib, "vag_loglike_cov_batch"):  # (detected by symbol too: the template entry with the correlated groups behind it)
             lib.vag_loglike_cov_batch.argtypes = wide + [C.POINTER(CovFitSpec), _dp, C.c_int, C.c_int, _dp]
             lib.vag_loglike_cov_batch_dev.argtypes = wide + [C.POINTER(CovFitSpec), v, C.c_int, C.c_int, v]
+    if hasattr(lib, "vag_stretch_run_dev"):  # (detected by symbol: the device sampler)
+        sp = C.POINTER(StretchSpec)
+        lib.vag_stretch_propose_dev.argtypes = [v, sp, C.c_uint64, C.c_int, v, v]
+        lib.vag_stretch_accept_dev.argtypes = [v, sp, C.c_uint64, C.c_int, v, v, v, v, v]
+        lib.vag_stretch_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), sp, C.c_uint64, C.c_int, v, v, v, v, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

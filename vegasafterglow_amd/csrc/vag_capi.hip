@@ -30,6 +30,7 @@
 #include "vag_poisson.h"
 #include "vag_index.h"
 #include "vag_fit_kernels.h"
+#include "vag_sampler.h"
 #include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
 #include "vag_flux_plan.h"    // (host only: the launch decisions of the flux stage)
 
@@ -437,6 +438,7 @@ struct vag_ctx {
     DevBuf d_skyvis, d_skyuv;  // visibilities (vag_sky.h): a chunk's row-block partials + combined values, a chunk's baselines
     DevBuf d_skycen, d_skycmom;  // exact centroids (vag_sky.h): row-block partials, moments
     DevBuf d_visblk, d_vispart;  // visibility groups of the likelihood (their data: vis below): their 64-visibility blocks, chi^2 partials
+    DevBuf d_stretch_prop, d_stretch_lp;  // the device sampler (vag_stretch_run_dev): a half's proposals [half][ndim] and their ln p [half]
     DevBuf d_polspec, d_polstokes;  // polarization groups of the likelihood (their data: pol below): the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -736,7 +738,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_stretch_prop, &c->d_stretch_lp})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3758,6 +3760,14 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     return rc;
 }
 
+// The call behind the uploads: the passes, repeated once on the waiting path when a planned-ahead call fails.  What loglike_dev, a
+// sharded call and every half-step of the device sampler run on a request whose blocks are resident.
+static int loglike_call(vag_ctx* c, const FitRequest& req, const double* d_theta, int nb, int ndim, double* d_out) {
+    int rc = loglike_body(c, req, d_theta, nb, ndim, d_out, !c->count_work);
+    if (rc == VAG_RETRY) rc = loglike_body(c, req, d_theta, nb, ndim, d_out, false);
+    return rc;
+}
+
 // A likelihood call on device pointers: the scans, the checks, the uploads of every spec block the request holds, and the call
 // (repeated once on the waiting path when a planned-ahead call fails).  The scans come first, as they always did in the entry points
 // that scan: what they refuse is refused without a look at the context.
@@ -3773,9 +3783,7 @@ static int loglike_dev(vag_ctx* c, FitRequest& req, const double* d_theta, int n
     req.ndim = ndim;
     rc = upload_blocks(c, req);
     if (rc) return rc;
-    rc = loglike_body(c, req, d_theta, nb, ndim, d_out, !c->count_work);
-    if (rc == VAG_RETRY) rc = loglike_body(c, req, d_theta, nb, ndim, d_out, false);
-    return rc;
+    return loglike_call(c, req, d_theta, nb, ndim, d_out);
 }
 
 // The host-pointer form: the scans (before anything goes to the device), then theta goes up, loglike_dev runs, the values come back.
@@ -3876,6 +3884,98 @@ int vag_loglike_cov_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
                               double* d_out) {
     FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl, cov);
     return loglike_dev(c, r, d_theta, nb, ndim, d_out);
+}
+
+// ---- the device sampler (kernels: vag_sampler.h; the move: the public header) ----
+
+static int stretch_spec_check(const vag_stretch_spec* sp) {  // (not null)
+    if (sp->ndim < 1 || sp->ndim > 16) return set_err(VAG_E_INVALID, "stretch move: ndim must be 1..16, got %d", sp->ndim);
+    if (sp->n_walkers < 2 * sp->ndim || (sp->n_walkers & 1))
+        return set_err(VAG_E_INVALID, "stretch move: need an even number of walkers, at least 2 * ndim = %d, got %d", 2 * sp->ndim, sp->n_walkers);
+    if (!std::isfinite(sp->a) || !(sp->a > 1.0)) return set_err(VAG_E_INVALID, "stretch move: the scale a must be finite and > 1, got %g", sp->a);
+    if (sp->thin < 1) return set_err(VAG_E_INVALID, "stretch move: thin must be >= 1, got %d", sp->thin);
+    return VAG_OK;
+}
+
+static int stretch_propose(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int which, const double* d_pos, double* d_prop) {
+    const int half = sp->n_walkers / 2;
+    hipLaunchKernelGGL(vag_stretch_propose_kernel, dim3((half + STRETCH_LANES - 1) / STRETCH_LANES), dim3(STRETCH_LANES), 0, c->stream,
+                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), sp->a, (unsigned long long)step, which, half,
+                       sp->ndim, d_pos, d_prop);
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+static int stretch_accept(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int which, const double* d_prop, const double* d_lp_new,
+                          double* d_pos, double* d_lp, int64_t* d_accepted, double* d_chain_row, double* d_logp_row) {
+    const int half = sp->n_walkers / 2;
+    hipLaunchKernelGGL(vag_stretch_accept_kernel, dim3((half + STRETCH_LANES - 1) / STRETCH_LANES), dim3(STRETCH_LANES), 0, c->stream,
+                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), sp->a, (unsigned long long)step, which, half,
+                       sp->ndim, d_prop, d_lp_new, d_pos, d_lp, reinterpret_cast<long long*>(d_accepted), d_chain_row, d_logp_row);
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+int vag_stretch_propose_dev(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !sp || !d_pos || !d_prop) return set_err(VAG_E_INVALID, "null context, stretch spec or buffer");
+    if (const int rc = stretch_spec_check(sp)) return rc;
+    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "stretch move: half must be 0 or 1, got %d", half);
+    HIPCHK(hipSetDevice(c->device));
+    return stretch_propose(c, sp, step, half, d_pos, d_prop);
+}
+
+int vag_stretch_accept_dev(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int half, const double* d_prop, const double* d_lp_new,
+                           double* d_pos, double* d_lp, int64_t* d_accepted) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !sp || !d_prop || !d_lp_new || !d_pos || !d_lp || !d_accepted)
+        return set_err(VAG_E_INVALID, "null context, stretch spec or buffer");
+    if (const int rc = stretch_spec_check(sp)) return rc;
+    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "stretch move: half must be 0 or 1, got %d", half);
+    HIPCHK(hipSetDevice(c->device));
+    return stretch_accept(c, sp, step, half, d_prop, d_lp_new, d_pos, d_lp, d_accepted, nullptr, nullptr);
+}
+
+int vag_stretch_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_stretch_spec* sp, uint64_t step0, int n_steps, double* d_pos,
+                        double* d_lp, int64_t* d_accepted, double* d_chain, double* d_logp) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !q || !q->spec || !sp || !d_pos || !d_lp || !d_accepted)
+        return set_err(VAG_E_INVALID, "null context, request, fit spec, stretch spec or buffer");
+    if ((d_chain == nullptr) != (d_logp == nullptr)) return set_err(VAG_E_INVALID, "stretch move: the chain and its ln p are stored together or not at all");
+    if (const int rc = stretch_spec_check(sp)) return rc;
+    if (sp->ndim != q->spec->ndim)
+        return set_err(VAG_E_INVALID, "stretch move: ndim %d is not the fit spec's %d", sp->ndim, q->spec->ndim);
+    if (n_steps < 0) return set_err(VAG_E_INVALID, "stretch move: n_steps must be >= 0, got %d", n_steps);
+    if (n_steps == 0) return VAG_OK;
+    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
+    int rc = fit_request_prepare(req);  // the scans, once per call of many steps
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const int ndim = sp->ndim, nw = sp->n_walkers, half = nw / 2;
+    req.ndim = ndim;
+    rc = upload_blocks(c, req);  // and the uploads
+    if (rc) return rc;
+    if (c->d_stretch_prop.ensure(sizeof(double) * (size_t)half * ndim)) return VAG_E_HIP;
+    if (c->d_stretch_lp.ensure(sizeof(double) * (size_t)half)) return VAG_E_HIP;
+    double* d_prop = c->d_stretch_prop.as<double>();
+    double* d_lp_new = c->d_stretch_lp.as<double>();
+    size_t row = 0;  // stored rows so far
+    for (int k = 0; k < n_steps; ++k) {
+        const uint64_t step = step0 + (uint64_t)k;
+        const bool stored = d_chain && (step + 1) % (uint64_t)sp->thin == 0;
+        for (int which = 0; which < 2; ++which) {
+            if ((rc = stretch_propose(c, sp, step, which, d_pos, d_prop))) return rc;
+            if ((rc = loglike_call(c, req, d_prop, half, ndim, d_lp_new))) return rc;
+            if ((rc = stretch_accept(c, sp, step, which, d_prop, d_lp_new, d_pos, d_lp, d_accepted,
+                                     stored ? d_chain + row * (size_t)nw * ndim : nullptr, stored ? d_logp + row * (size_t)nw : nullptr)))
+                return rc;
+        }
+        if (stored) ++row;
+    }
+    return VAG_OK;
 }
 
 __global__ void vag_model_cost_kernel(const VagGridMeta* __restrict__ meta, int nb, double* __restrict__ cost,
@@ -4030,8 +4130,7 @@ static int shard_begin(vag_ctx* c, const vag_fit_spec* spec, const double* d_the
     c->shard_last_dealt = slot;  // (kept for inspection even if the evaluation below fails)
     const int* d_order = nullptr;
     if (n_mine > 0) {
-        int rc = loglike_body(c, req, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>(), !c->count_work);
-        if (rc == VAG_RETRY) rc = loglike_body(c, req, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>(), false);
+        const int rc = loglike_call(c, req, c->d_shard_theta.as<double>(), n_mine, ndim, c->d_shard_ll.as<double>());
         if (rc) {  // (no block went out: there is nothing to finish, the slot is free)
             if (replaces) fl.in_use = false, --c->shard_costs[entry].in_flight;
             return rc;

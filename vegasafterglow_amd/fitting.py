@@ -202,6 +202,29 @@ def _widest_entry(lib, spec, suffix):
     return getattr(lib, "vag_loglike_index_batch" + suffix), ()
 
 
+def on_current_stream(lib, h, lock, dev, fn):
+    """fn() with the context (h, lock) on torch's current stream of ``dev``: the context follows that stream for the duration of the
+    call and then goes back to the stream it was on -- a stream the caller destroys later must not stay bound to the (shared)
+    context."""
+    import torch
+    with lock:
+        prev = C.c_void_p()
+        _lib.check(lib.vag_ctx_get_stream(h, C.byref(prev)))
+        _lib.check(lib.vag_ctx_set_stream(h, _lib.torch_stream_handle(torch.cuda.current_stream(dev))))
+        try:
+            return fn()
+        finally:
+            lib.vag_ctx_set_stream(h, prev)
+
+
+def loglike_request(spec):
+    """vag_loglike_request of a spec made by Fitter.build_spec: the eleven blocks of the widest likelihood entry, None where the fit
+    has none.  The struct points into ``spec``: keep both."""
+    ptr = lambda x: C.pointer(x) if x is not None else None  # noqa: E731
+    return _lib.LoglikeRequest(C.pointer(spec), ptr(spec._sky), ptr(spec._vis), ptr(spec._pol), ptr(spec._lim), ptr(spec._noise),
+                               ptr(spec._counts), ptr(spec._index), ptr(spec._fold), ptr(spec._tmpl), ptr(spec._cov))
+
+
 def _fma(a, b, c):
     """a * b + c with one rounding, in numpy: the product split without error (Veltkamp / Dekker), the sum without error (Knuth), the
     two error terms added to the rounded sum.  For finite operands far from overflow and underflow, as template values are."""
@@ -1782,11 +1805,14 @@ class Fitter:
         return self.model(best_params, param_defs, resolution).flux(t, nu_min, nu_max, num_points)
 
     # fitter.py:545-674 (the emcee branch; the stretch-move sampler of vegasafterglow_amd.sampling needs no third-party package)
-    def fit(self, param_defs, nwalkers=None, nsteps=1000, nburn=0, seed=0, **kw):
+    def fit(self, param_defs, nwalkers=None, nsteps=1000, nburn=0, seed=0, sampler="host", **kw):
+        """sampling.fit on this fitter.  ``sampler="host"``: the numpy stretch move around one device call per half-step;
+        ``sampler="device"``: the whole run on the device (sampling.run_stretch_move_device)."""
         from . import sampling
         self.validate_parameters(param_defs)
         ndim = sum(1 for pd in param_defs if pd.scale is not Scale.fixed)
-        return sampling.fit(self, param_defs, nwalkers=nwalkers or max(2 * ndim + 2, 32), nsteps=nsteps, nburn=nburn, seed=seed, **kw)
+        return sampling.fit(self, param_defs, nwalkers=nwalkers or max(2 * ndim + 2, 32), nsteps=nsteps, nburn=nburn, seed=seed,
+                            sampler=sampler, **kw)
 
     def loglike_batch(self, samples, param_defs):
         """ln L for each row of samples[nb, ndim] (one batched device call)."""
@@ -1804,10 +1830,7 @@ class Fitter:
         here (the device path must be self-contained)."""
         import torch
         spec, _, _ = self.build_spec(param_defs, priors=priors, use_priors=use_priors)
-        param_defs_free = [pd.name for pd in param_defs if pd.scale is not Scale.fixed]
-        if self._host_priors:
-            raise ValueError("device_evaluator: only Uniform / Gaussian / LogUniform priors (or their tuple forms) run on the device; "
-                             f"got host-only priors for {[param_defs_free[d] for d, _ in self._host_priors]}")
+        self._refuse_host_priors(param_defs, "device_evaluator")
         lib = _lib.load()
         if context is None:
             h, lock = get_context(self.device)
@@ -1817,16 +1840,7 @@ class Fitter:
         keep = [spec]  # the spec's arrays are owned by this Fitter; the struct itself by this closure
 
         def _on_current_stream(fn):
-            # the context follows torch's current stream for the duration of the call and then goes back to the stream it was on:
-            # a stream the caller destroys later must not stay bound to the (shared) context
-            with lock:
-                prev = C.c_void_p()
-                _lib.check(lib.vag_ctx_get_stream(h, C.byref(prev)))
-                _lib.check(lib.vag_ctx_set_stream(h, _lib.torch_stream_handle(torch.cuda.current_stream(dev))))
-                try:
-                    return fn()
-                finally:
-                    lib.vag_ctx_set_stream(h, prev)
+            return on_current_stream(lib, h, lock, dev, fn)
 
         def eval_dev(theta, want_costs=True):
             theta = theta.contiguous()
@@ -1883,6 +1897,22 @@ class Fitter:
         eval_dev.native = _Native
         return eval_dev
 
+    def _refuse_host_priors(self, param_defs, who):
+        """After build_spec: a path that must be self-contained on the device takes no prior that only exists as a host object."""
+        if self._host_priors:
+            free = [pd.name for pd in param_defs if pd.scale is not Scale.fixed]
+            raise ValueError(f"{who}: only Uniform / Gaussian / LogUniform priors (or their tuple forms) run on the device; "
+                             f"got host-only priors for {[free[d] for d, _ in self._host_priors]}")
+
+    @staticmethod
+    def _log_plan_warnings(plan, nb):
+        if plan.n_models_capacity:
+            # never silent: these walkers were NOT evaluated (their adaptive grid exceeds the engine's static limits)
+            logger.warning("%d of %d walkers exceeded the engine grid limits and were assigned -inf", plan.n_models_capacity, nb)
+        if plan.n_walkers_ssc_failed:
+            logger.warning("%d of %d walkers had SSC tables outside the engine's capacity and were assigned -inf",
+                           plan.n_walkers_ssc_failed, nb)
+
     def _device_loglike(self, spec, samples):
         out = np.empty(samples.shape[0])
         h, lock = get_context(self.device)
@@ -1895,13 +1925,7 @@ class Fitter:
                           ref(spec._counts), ref(spec._index), *fold, samples.ctypes.data_as(_dp), samples.shape[0], spec.ndim,
                           out.ctypes.data_as(_dp)))
             _lib.load().vag_last_plan(h, C.byref(plan))
-        if plan.n_models_capacity:
-            # never silent: these walkers were NOT evaluated (their adaptive grid exceeds the engine's static limits)
-            logger.warning("%d of %d walkers exceeded the engine grid limits and were assigned -inf",
-                           plan.n_models_capacity, samples.shape[0])
-        if plan.n_walkers_ssc_failed:
-            logger.warning("%d of %d walkers had SSC tables outside the engine's capacity and were assigned -inf",
-                           plan.n_walkers_ssc_failed, samples.shape[0])
+        self._log_plan_warnings(plan, samples.shape[0])
         self.last_plan = plan
         return out
 

@@ -8,6 +8,9 @@ walkers over a thread pool (VegasAfterglow/fitting/samplers.py:59-106).  Here th
 * ``run_stretch_move`` -- a dependency-free affine-invariant ensemble sampler (Goodman & Weare stretch move with the
   red-blue split emcee uses by default), so an end-to-end fit runs wherever the engine does.  Each half-step
   proposes nwalkers/2 walkers and evaluates them in ONE ``log_prob_batch`` call;
+* ``run_stretch_move_device`` / ``StretchMove`` -- the stretch move itself on the device (fixed halves, Philox draws keyed by
+  (seed, step, walker)): a run of steps is launches only, positions, ln p and the chain stay in HBM.  ``run_stretch_move_philox``,
+  ``stretch_proposals`` and ``stretch_accepts`` state the same move in numpy, to the bit;
 * ``BatchPool`` -- the object handed to ``bilby.run_sampler(pool=...)`` in place of the reference's thread pool
   (samplers.py:146-170): ``pool.map(loglikelihood, points)`` becomes one device call over the whole live-point queue.
 """
@@ -123,15 +126,276 @@ def run_stretch_move(log_prob_batch: Callable[[np.ndarray], np.ndarray], pos0: n
     return chain, logp, accepted / max(nsteps, 1)
 
 
+# ---- the stretch move with fixed halves and counter-based draws: the host statement of the device sampler (INTEGRATION.md
+#      "The device sampler").  A chain is a pure function of (seed, step, walker) and of ln p. ----
+
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon et al. 2011, the Random123 constants), vectorised: counter[..., 4] and key[..., 2] of 32-bit words
+    (broadcast against each other) -> uint32[..., 4]."""
+    counter, key = np.asarray(counter, dtype=np.uint64), np.asarray(key, dtype=np.uint64)
+    shape = np.broadcast_shapes(counter.shape[:-1], key.shape[:-1])
+    c = [np.broadcast_to(counter[..., i] & _MASK32, shape) for i in range(4)]
+    k = [np.broadcast_to(key[..., i] & _MASK32, shape) for i in range(2)]
+    s32 = np.uint64(32)
+    for r in range(10):
+        k0 = (k[0] + np.uint64((r * _PHILOX_W0) & 0xFFFFFFFF)) & _MASK32
+        k1 = (k[1] + np.uint64((r * _PHILOX_W1) & 0xFFFFFFFF)) & _MASK32
+        p0, p1 = _PHILOX_M0 * c[0], _PHILOX_M1 * c[2]  # (32 x 32 bits: exact in 64)
+        c = [(p1 >> s32) ^ c[1] ^ k0, p1 & _MASK32, (p0 >> s32) ^ c[3] ^ k1, p0 & _MASK32]
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def _u53(hi, lo):
+    """The uniform in [0, 1) of two Philox words: ((hi >> 5) 2^26 + (lo >> 6)) 2^-53, exact in a double."""
+    hi, lo = np.asarray(hi, dtype=np.uint64), np.asarray(lo, dtype=np.uint64)
+    return (((hi >> np.uint64(5)) << np.uint64(26)) + (lo >> np.uint64(6))).astype(np.float64) * 2.0 ** -53
+
+
+def _stretch_words(nwalkers, step, half, seed, stream):
+    """The four Philox words of every walker of half `half` (0: walkers [0, nwalkers / 2), 1: the rest) at absolute step `step`."""
+    nh = nwalkers // 2
+    step, seed = int(step), int(seed)
+    counter = np.empty((nh, 4), dtype=np.uint64)
+    counter[:, 0] = half * nh + np.arange(nh)
+    counter[:, 1], counter[:, 2], counter[:, 3] = step & 0xFFFFFFFF, (step >> 32) & 0xFFFFFFFF, stream
+    return philox4x32(counter, np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint64))
+
+
+def _check_stretch(nwalkers, ndim, a=2.0, thin=1):
+    if nwalkers % 2 or nwalkers < 2 * ndim:
+        raise ValueError("need an even number of walkers, at least 2 * ndim")
+    if not 1 <= ndim <= 16:
+        raise ValueError("the stretch move takes 1..16 dimensions")
+    if not (np.isfinite(a) and a > 1.0):
+        raise ValueError("the stretch scale a must be finite and > 1")
+    if thin < 1:
+        raise ValueError("thin must be >= 1")
+
+
+def stretch_z(a, u):
+    """vag::stretch_z in numpy: z = t t / a with t = fma(a - 1, u, 1), g(z) ~ 1 / sqrt(z) on [1 / a, a).  The half-open end is kept
+    in floating point: for the last few u below 1 the fma rounds t up to a, and z is then the largest double below a."""
+    from .fitting import _fma
+    t = _fma(a - 1.0, u, 1.0)
+    z = t * t / a
+    return np.where(z < a, z, np.nextafter(a, 0.0))
+
+
+def stretch_proposals(pos, step, half, seed, a=2.0):
+    """The proposals of half `half` (0 or 1) at absolute step `step`: (prop[nw / 2, ndim], z[nw / 2], partner[nw / 2]), partner the
+    index in the whole ensemble of the walker of the other half each one stretches from.  Bit for bit what
+    vag_stretch_propose_dev computes (fitting._fma for its two fused operations)."""
+    from .fitting import _fma
+    pos = np.asarray(pos, dtype=np.float64)
+    nw = pos.shape[0]
+    nh = nw // 2
+    x = _stretch_words(nw, step, half, seed, 0)
+    z = stretch_z(a, _u53(x[:, 0], x[:, 1]))
+    partner = (1 - half) * nh + ((x[:, 2].astype(np.uint64) * np.uint64(nh)) >> np.uint64(32)).astype(np.int64)
+    other = pos[partner]
+    return _fma(z[:, None], pos[half * nh:(half + 1) * nh] - other, other), z, partner
+
+
+def stretch_accepts(step, half, seed, z, lp_new, lp_old, ndim):
+    """The decisions of half `half` at step `step`: (take[nw / 2], margin[nw / 2]).  A proposal whose ln p is not finite is rejected
+    (margin -inf); any other is taken iff log(u_a) < (ndim - 1) log z + (lp_new - lp_old), and margin is that right side minus the
+    left: a decision whose |margin| is far above the rounding of the logarithms is the same on every machine."""
+    z, lp_new, lp_old = (np.asarray(v, dtype=np.float64) for v in (z, lp_new, lp_old))
+    y = _stretch_words(2 * z.size, step, half, seed, 1)
+    finite = np.isfinite(lp_new)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        margin = ((ndim - 1.0) * np.log(z) + (lp_new - lp_old)) - np.log(_u53(y[:, 0], y[:, 1]))  # (u_a = 0: log = -inf, taken)
+    margin = np.where(finite, margin, -np.inf)
+    return finite & (margin > 0), margin
+
+
+def run_stretch_move_philox(log_prob_batch: Callable[[np.ndarray], np.ndarray], pos0: np.ndarray, nsteps: int, seed: int = 0,
+                            a: float = 2.0, thin: int = 1, step0: int = 0, margins: Optional[list] = None):
+    """The chain of the device sampler through any host callable: the stretch move with fixed halves (half 0 = walkers
+    [0, nw / 2) against half 1, then half 1 against the updated half 0, no permutation) and Philox draws keyed by (seed, step,
+    walker).  Runs steps step0 .. step0 + nsteps - 1 and stores step s when (s + 1) % thin == 0.
+
+    Returns (chain[rows, nw, ndim], log_prob[rows, nw], acceptance[nw]).  ``margins``: a list that receives every half-step's
+    margin array (stretch_accepts)."""
+    pos = np.array(pos0, dtype=np.float64, copy=True)
+    nw, ndim = pos.shape
+    _check_stretch(nw, ndim, a, thin)
+    lp = np.asarray(log_prob_batch(pos), dtype=np.float64).copy()
+    if not np.all(np.isfinite(lp)):
+        raise ValueError("initial positions must have finite log-probability")
+    rows = (step0 + nsteps) // thin - step0 // thin
+    chain, logp = np.empty((rows, nw, ndim)), np.empty((rows, nw))
+    accepted = np.zeros(nw, dtype=np.int64)
+    nh, row = nw // 2, 0
+    for step in range(step0, step0 + nsteps):
+        for half in (0, 1):
+            s = slice(half * nh, (half + 1) * nh)
+            prop, z, _ = stretch_proposals(pos, step, half, seed, a)
+            lp_new = np.asarray(log_prob_batch(prop), dtype=np.float64)
+            take, margin = stretch_accepts(step, half, seed, z, lp_new, lp[s], ndim)
+            if margins is not None:
+                margins.append(margin)
+            pos[s][take] = prop[take]
+            lp[s][take] = lp_new[take]
+            accepted[s][take] += 1
+        if (step + 1) % thin == 0:
+            chain[row], logp[row] = pos, lp
+            row += 1
+    return chain, logp, accepted / max(nsteps, 1)
+
+
+class StretchMove:
+    """The two halves of a half-step on the device (vag_stretch_propose_dev / vag_stretch_accept_dev), on float64 torch tensors and
+    torch's current stream; nothing crosses PCIe and nothing synchronises.  They need no model: any evaluator on device tensors goes
+    between them, a dist.WalkerSharder for instance::
+
+        move = StretchMove(nw, ndim, seed=7)
+        lp, _ = eval_dev(pos)                                # ln p of the whole ensemble, float64[nw] on the device
+        accepted = torch.zeros(nw, dtype=torch.int64, device=pos.device)
+        for step in range(nsteps):
+            for half in (0, 1):
+                prop = move.propose(step, half, pos)         # [nw / 2, ndim]
+                lp_new = sharder.log_prob(prop)              # or eval_dev(prop)[0]: any float64[nw / 2] on the device
+                move.accept(step, half, prop, lp_new, pos, lp, accepted)   # pos, lp, accepted change in place
+
+    The chain is the one sampling.run_stretch_move_philox makes from the same ln p."""
+
+    def __init__(self, nwalkers: int, ndim: int, seed: int = 0, a: float = 2.0, device: int = 0):
+        _check_stretch(nwalkers, ndim, a)
+        import torch
+        from . import _lib
+        from .model import get_context
+        self.nwalkers, self.ndim = int(nwalkers), int(ndim)
+        self._lib = _lib.load()
+        self._propose = _lib.stretch_entry(self._lib, "vag_stretch_propose_dev")
+        self._accept = _lib.stretch_entry(self._lib, "vag_stretch_accept_dev")
+        self._spec = _lib.StretchSpec(int(seed) & (2 ** 64 - 1), float(a), self.nwalkers, self.ndim, 1)
+        self._h, self._lock = get_context(device)
+        self._dev = torch.device("cuda", device)
+
+    def _run(self, fn):
+        from .fitting import on_current_stream
+        return on_current_stream(self._lib, self._h, self._lock, self._dev, fn)
+
+    def _checked(self, t, shape, dtype, what):
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != self._dev or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor {shape} on {self._dev}")
+        return t
+
+    def propose(self, step: int, half: int, pos):
+        import ctypes as C
+        import torch
+        from . import _lib
+        nh = self.nwalkers // 2
+        self._checked(pos, (self.nwalkers, self.ndim), torch.float64, "pos")
+        prop = torch.empty((nh, self.ndim), dtype=torch.float64, device=self._dev)
+        self._run(lambda: _lib.check(self._propose(self._h, C.byref(self._spec), int(step), int(half), pos.data_ptr(), prop.data_ptr())))
+        return prop
+
+    def accept(self, step: int, half: int, prop, lp_new, pos, lp, accepted):
+        import ctypes as C
+        import torch
+        from . import _lib
+        nh = self.nwalkers // 2
+        self._checked(prop, (nh, self.ndim), torch.float64, "prop")
+        self._checked(lp_new, (nh,), torch.float64, "lp_new")
+        self._checked(pos, (self.nwalkers, self.ndim), torch.float64, "pos")
+        self._checked(lp, (self.nwalkers,), torch.float64, "lp")
+        self._checked(accepted, (self.nwalkers,), torch.int64, "accepted")
+        self._run(lambda: _lib.check(self._accept(self._h, C.byref(self._spec), int(step), int(half), prop.data_ptr(), lp_new.data_ptr(),
+                                                  pos.data_ptr(), lp.data_ptr(), accepted.data_ptr())))
+
+
+def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, nsteps: int, seed: int = 0,
+                            a: float = 2.0, thin: int = 1, priors=None, chunk: int = 64, progress: Optional[Callable] = None):
+    """The stretch move of run_stretch_move_philox with everything on the device: the spec is built once, and every `chunk` steps are
+    ONE call (vag_stretch_run_dev) that scans and uploads the spec blocks once and then only launches -- positions, ln p, the chain
+    and the acceptance counts stay in HBM, nothing is copied and the stream is not synchronised between steps.  ln p is
+    ln L + sum ln prior with the bounds mask (Fitter.log_prob_batch); only priors that run on the device are accepted.
+
+    Returns (chain[nsteps // thin, nw, ndim], log_prob[nsteps // thin, nw], acceptance[nw]) as numpy arrays.  The chunk size does
+    not change a bit of them.  ``progress(step, pos, lp)`` is called once per chunk with the last step of the chunk; the context's
+    lock is free between chunks."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .fitting import _widest_entry, loglike_request, on_current_stream
+    from .model import get_context
+    pos0 = np.ascontiguousarray(pos0, dtype=np.float64)
+    if pos0.ndim != 2:
+        raise ValueError("pos0 must be [nwalkers, ndim]")
+    nw, ndim = pos0.shape
+    _check_stretch(nw, ndim, a, thin)
+    if chunk < 1 or nsteps < 0:
+        raise ValueError("chunk must be >= 1 and nsteps >= 0")
+    spec, _, _ = fitter.build_spec(param_defs, priors=priors, use_priors=True)
+    if spec.ndim != ndim:
+        raise ValueError("pos0 must be [nwalkers, ndim]")
+    fitter._refuse_host_priors(param_defs, "run_stretch_move_device")
+    lib = _lib.load()
+    run = _lib.stretch_entry(lib, "vag_stretch_run_dev")
+    h, lock = get_context(fitter.device)
+    dev = torch.device("cuda", fitter.device)
+    request = loglike_request(spec)
+    stretch = _lib.StretchSpec(int(seed) & (2 ** 64 - 1), float(a), nw, ndim, int(thin))
+    pos = torch.from_numpy(pos0).to(dev)
+    lp = torch.empty((nw,), dtype=torch.float64, device=dev)
+    accepted = torch.zeros((nw,), dtype=torch.int64, device=dev)
+    rows = nsteps // thin
+    chain = torch.empty((rows, nw, ndim), dtype=torch.float64, device=dev)
+    logp = torch.empty((rows, nw), dtype=torch.float64, device=dev)
+    ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+
+    def initial():
+        fn, fold = _widest_entry(lib, spec, "_dev")
+        _lib.check(fn(h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
+                      ref(spec._counts), ref(spec._index), *fold, pos.data_ptr(), nw, ndim, lp.data_ptr()))
+    on_current_stream(lib, h, lock, dev, initial)
+    if not bool(torch.isfinite(lp).all()):
+        raise ValueError("initial positions must have finite log-probability")
+    for step0 in range(0, nsteps, chunk):
+        n = min(chunk, nsteps - step0)
+        row = step0 // thin
+        stored = row < rows
+        on_current_stream(lib, h, lock, dev, lambda: _lib.check(run(
+            h, C.byref(request), C.byref(stretch), step0, n, pos.data_ptr(), lp.data_ptr(), accepted.data_ptr(),
+            chain.data_ptr() + 8 * row * nw * ndim if stored else None, logp.data_ptr() + 8 * row * nw if stored else None)))
+        if progress is not None:
+            progress(step0 + n - 1, pos.cpu().numpy(), lp.cpu().numpy())
+    plan = _lib.Plan()
+    with lock:
+        lib.vag_last_plan(h, C.byref(plan))
+    fitter._log_plan_warnings(plan, nw // 2)
+    fitter.last_plan = plan
+    return chain.cpu().numpy(), logp.cpu().numpy(), accepted.cpu().numpy() / max(nsteps, 1)
+
+
 def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: int, nburn: int = 0, seed: int = 0,
-        loglike_fn: Optional[Callable] = None, center: Optional[np.ndarray] = None, spread: float = 0.1):
+        loglike_fn: Optional[Callable] = None, center: Optional[np.ndarray] = None, spread: float = 0.1, sampler: str = "host"):
     """Convenience driver: uniform priors over the ParamDef boxes, stretch-move sampling on the device likelihood.
-    Returns dict(samples[flat, ndim], log_prob[flat], acceptance, best) in sampler space (log10 for LOG parameters)."""
+    Returns dict(samples[flat, ndim], log_prob[flat], acceptance, best) in sampler space (log10 for LOG parameters).
+    ``sampler="host"``: run_stretch_move in numpy around one device call per half-step; ``"device"``: run_stretch_move_device, the
+    whole run on the device (fixed halves and Philox draws keyed by `seed`: another chain than the host sampler's, the same
+    distribution)."""
+    if sampler not in ("host", "device"):
+        raise ValueError(f"unknown sampler {sampler!r}: 'host' or 'device'")
+    if sampler == "device" and loglike_fn is not None:
+        raise ValueError("sampler='device' evaluates the fitter's own likelihood on the device: it cannot be combined with loglike_fn "
+                         "(compose sampling.StretchMove with your evaluator instead)")
     rng = np.random.default_rng(seed)
     _, lower, upper = fitter.build_spec(param_defs)
-    log_prob_batch = fitter.make_log_prob_batch(param_defs, loglike_fn=loglike_fn)
-    pos0 = initial_positions(lower, upper, nwalkers, rng, center=center, spread=spread)
-    chain, logp, acc = run_stretch_move(log_prob_batch, pos0, nsteps, rng=rng)
+    if sampler == "device":
+        pos0 = initial_positions(lower, upper, nwalkers, rng, center=center, spread=spread)
+        chain, logp, acc = run_stretch_move_device(fitter, param_defs, pos0, nsteps, seed=seed)
+    else:
+        log_prob_batch = fitter.make_log_prob_batch(param_defs, loglike_fn=loglike_fn)
+        pos0 = initial_positions(lower, upper, nwalkers, rng, center=center, spread=spread)
+        chain, logp, acc = run_stretch_move(log_prob_batch, pos0, nsteps, rng=rng)
     flat = chain[nburn:].reshape(-1, chain.shape[-1])
     flat_lp = logp[nburn:].reshape(-1)
     return {"samples": flat, "log_prob": flat_lp, "acceptance": acc, "best": flat[np.argmax(flat_lp)], "chain": chain}
