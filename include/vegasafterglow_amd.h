@@ -278,6 +278,11 @@ int vag_sky_stokes_image_batch(vag_ctx* ctx, const vag_model_params* params, int
  *   VAG_MATH_POISSON_DEVIANCE  in {N, mu}; out the Poisson deviance D(N, mu) (n_in = 2, n_out = 1);
  *   VAG_MATH_LOG_SLOPE  in {F_0 .. F_7, c_0 .. c_7, K}; out sum_{k = 1 .. K-1} c_k ln(F_k / F_0), NaN unless F_0 .. F_{K-1} are all
  *                      finite and > 0 (n_in = 17, n_out = 1; entries from K on are not read);
+ *   VAG_MATH_ELEC_CELL in  {t_comv, r, Gamma_th, B, N_p, eps_e, p, xi_e, relic flag (0 / 1), inj.gamma_M, inj.gamma_m, inj.gamma_c}
+ *                      (internal units; the inj electrons are read for a relic cell only): syn_cell with Gamma = 1, t_eng = 0;
+ *                      out {gamma_m, gamma_c, gamma_a, gamma_M, N_e, column_den, nu_m, nu_c, nu_a, nu_M, I_nu_max} (n_in = 12, n_out = 11);
+ *   VAG_MATH_FWD_STATE in  {Gamma, rho, U_th, m2, eps_B} (internal units): the shock state vag_cells_kernel finishes per cell;
+ *                      out {Gamma_th, B, N_p, compression ratio} (n_in = 5, n_out = 4; m2 = 0, an unshocked cell, gives 1, 0, 0, 0);
  *   VAG_MATH_LDS_ADD   in  {slot, value}: the 64 lanes of a wavefront add their values into the slots (integers in [0, 64)) they
  *                      name with one ds_add_f64; out: slot `lane`'s total.
  * The wave routines (WAVE_PREFIX_SUM, WAVE_SUM, SKY_WAVE_SUM, LDS_ADD) run one wavefront per 64 points and need n % 64 == 0.
@@ -292,6 +297,8 @@ enum {
     VAG_MATH_LOG_NDTR, /* ln Phi(z) of the upper-limit term (vag_loglike_lim_batch) */
     VAG_MATH_POISSON_DEVIANCE, /* in {N, mu}, out D = mu - N - N ln(mu / N) (mu for N = 0) of the counts term (vag_loglike_counts_batch) */
     VAG_MATH_LOG_SLOPE, /* in {8 fluxes, 8 coefficients, K}, out the pivot-form log-slope of the spectral-index term (vag_loglike_index_batch) */
+    VAG_MATH_ELEC_CELL, /* syn_cell: the electrons and break frequencies of one cell (vag_cells_kernel) */
+    VAG_MATH_FWD_STATE, /* fwd_shock_state: Gamma_th, B, N_p of one forward-shock cell from the raw ODE state (vag_cells_kernel) */
     VAG_MATH_COUNT
 };
 int vag_debug_device_math(vag_ctx* ctx, int fn, const double* in, int n, double* out);

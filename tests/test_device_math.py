@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import _elecref as E
 import _mathref as R
 
 pytestmark = pytest.mark.gpu
@@ -33,9 +34,10 @@ def dev():
     def run(name, x, n_out=1):
         x = np.ascontiguousarray(x, dtype=np.float64)
         out = np.full((x.shape[0], n_out), np.nan)
-        _lib.check(lib.vag_debug_device_math(ctx, _lib.MATH[name], x.ctypes.data_as(_dp), x.shape[0], out.ctypes.data_as(_dp)))
+        _lib.check(lib.vag_debug_device_math(ctx, ids[name], x.ctypes.data_as(_dp), x.shape[0], out.ctypes.data_as(_dp)))
         return out if n_out > 1 else out[:, 0]
-    run.lib, run.ctx, run.ids = lib, ctx, _lib.MATH
+    ids = {**_lib.MATH, **_lib.MATH_MORE}
+    run.lib, run.ctx, run.ids = lib, ctx, ids
     yield run
     lib.vag_ctx_destroy(ctx)
     if MEASURED:
@@ -239,6 +241,12 @@ def test_elementwise_shapes(dev, n):
     full = dev("exp2_fast", x)
     assert np.array_equal(dev("exp2_fast", x[:n]), full[:n])
     assert np.array_equal(dev("sp_fast", x[-n:]), dev("sp_fast", x)[-n:])
+    # the electron stage and the forward shock's state (tests/test_electron_stage.py): rows of 12 -> 11 and of 5 -> 4 doubles
+    for name, rows, n_out in (("elec_cell", E.probe_set(2.3)[0], 11), ("fwd_state", E.fwd_state_rows(), 4)):
+        full = dev(name, rows, n_out)
+        assert full.shape == (rows.shape[0], n_out) and not np.isnan(full[:, 0]).any()
+        assert np.array_equal(dev(name, rows[:n], n_out), full[:n], equal_nan=True)
+        assert np.array_equal(dev(name, rows[-n:], n_out), full[-n:], equal_nan=True)
 
 
 # ---------------------------------------------------------------- synchrotron cell
@@ -505,6 +513,14 @@ def test_probe_rejects_bad_arguments(dev):
     assert lib.vag_debug_device_math(ctx, ids["exp2_fast"], px, 1, None) == -1
     assert lib.vag_debug_device_math(None, ids["exp2_fast"], px, 1, py) == -1
     assert lib.vag_debug_device_math(ctx, ids["wave_sum"], px, 63, py) == -1
+    for name in ("elec_cell", "fwd_state"):
+        assert lib.vag_debug_device_math(ctx, ids[name], px, 0, py) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], px, -3, py) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], None, 1, py) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], px, 1, None) == -1
+        assert lib.vag_debug_device_math(None, ids[name], px, 1, py) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], px, 1, py) == 0  # (128 doubles hold one point of either)
+    assert lib.vag_debug_device_math(ctx, max(ids.values()) + 1, px, 1, py) == -1
     bad = np.zeros((64, 2))
     bad[5, 0] = 64.0
     assert lib.vag_debug_device_math(ctx, ids["lds_add"], bad.ctypes.data_as(_dp), 64, np.zeros(64).ctypes.data_as(_dp)) == -1

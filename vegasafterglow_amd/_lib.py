@@ -57,7 +57,7 @@ MATH = {name: i for i, name in enumerate([
     "syn_cell", "ic_cell", "wave_prefix_sum", "wave_sum", "sky_wave_sum", "lds_add", "log_ndtr"])}
 # VAG_MATH_* appended after VAG_MATH_LOG_NDTR.  They have a mapping of their own: MATH is pinned to end with log_ndtr
 # (tests/test_limits_host.py), and the ids of both mappings are the enum's, one numbering.
-MATH_MORE = {name: len(MATH) + i for i, name in enumerate(["poisson_deviance", "log_slope"])}
+MATH_MORE = {name: len(MATH) + i for i, name in enumerate(["poisson_deviance", "log_slope", "elec_cell", "fwd_state"])}
 
 P_A_V = 1000  # VAG_P_A_V
 # VAG_P_SKY_*: the sky placement of the centroid and visibility groups (vag_loglike_sky_batch / _vis_batch), not Model fields either

@@ -15,6 +15,10 @@ constexpr int MATH_SYN_IN = 9;                        // gamma_m, gamma_c, gamma
 constexpr int MATH_SYN_OUT = VAG_NPAR + 8;            // block, then fast (regs) x0 x1, fast (strided) x0 x1, fast2 x0 x1, exact x0 x1
 constexpr int MATH_IC_IN = VAG_NPAR + VAG_NQ + 3;     // block, IC extras, p, x0, x1
 constexpr int MATH_IC_OUT = 6;                        // log2_I_nu_ic x0 x1, _straight x0 x1, _pair x0 x1
+constexpr int MATH_ELEC_IN = 12;                      // t_comv, r, Gamma_th, B, N_p, eps_e, p, xi_e, relic, inj.gamma_M, inj.gamma_m, inj.gamma_c
+constexpr int MATH_ELEC_OUT = 11;                     // gamma_m, gamma_c, gamma_a, gamma_M, N_e, column_den, nu_m, nu_c, nu_a, nu_M, I_nu_max
+constexpr int MATH_FWD_IN = 5;                        // Gamma, rho, U_th, m2, eps_B
+constexpr int MATH_FWD_OUT = 4;                       // Gamma_th, B, N_p, compression
 
 // [n_in, n_out] per point of routine `fn` (VAG_MATH_*); 0 for an unknown routine
 inline int math_n_in(int fn) {
@@ -24,6 +28,8 @@ inline int math_n_in(int fn) {
         case VAG_MATH_LDS_ADD: return 2;  // slot (an integer in [0, 64)), value
         case VAG_MATH_POISSON_DEVIANCE: return 2;  // N, mu
         case VAG_MATH_LOG_SLOPE: return 2 * INDEX_MAX_NODES + 1;  // 8 fluxes, 8 coefficients, K
+        case VAG_MATH_ELEC_CELL: return MATH_ELEC_IN;
+        case VAG_MATH_FWD_STATE: return MATH_FWD_IN;
         default: return (fn >= 0 && fn < VAG_MATH_COUNT) ? 1 : 0;
     }
 }
@@ -31,6 +37,8 @@ inline int math_n_out(int fn) {
     switch (fn) {
         case VAG_MATH_SYN_CELL: return MATH_SYN_OUT;
         case VAG_MATH_IC_CELL: return MATH_IC_OUT;
+        case VAG_MATH_ELEC_CELL: return MATH_ELEC_OUT;
+        case VAG_MATH_FWD_STATE: return MATH_FWD_OUT;
         default: return (fn >= 0 && fn < VAG_MATH_COUNT) ? 1 : 0;
     }
 }
@@ -117,6 +125,24 @@ __global__ void __launch_bounds__(64) vag_math_probe_kernel(int fn, int n, const
             const double* a = in + (size_t)i * (2 * INDEX_MAX_NODES + 1);
             const int K = (int)a[2 * INDEX_MAX_NODES];
             out[i] = (K >= 2 && K <= INDEX_MAX_NODES) ? log_slope(a, 1, a + INDEX_MAX_NODES, K) : NAN;
+            return;
+        }
+        case VAG_MATH_ELEC_CELL: {  // the cell as vag_cells_kernel computes it (syn_cell), details rows in the kernel's order
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_ELEC_IN;
+            CellOut o;
+            syn_cell(o, 0.0, a[0], a[1], 1.0, a[2], a[3], a[4], a[5], a[6], a[7], a[8] != 0, ElecBasic{a[9], a[10], a[11]});
+            const double v[MATH_ELEC_OUT] = {o.gamma_m, o.gamma_c, o.gamma_a, o.gamma_M, o.N_e, o.column_den,
+                                             o.nu_m, o.nu_c, o.nu_a, o.nu_M, o.I_nu_max};
+            for (int q = 0; q < MATH_ELEC_OUT; ++q) out[(size_t)i * MATH_ELEC_OUT + q] = v[q];
+            return;
+        }
+        case VAG_MATH_FWD_STATE: {
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_FWD_IN;
+            const FwdState s = fwd_shock_state(a[0], a[1], a[2], a[3], a[4]);
+            double* r = out + (size_t)i * MATH_FWD_OUT;
+            r[0] = s.Gamma_th, r[1] = s.B, r[2] = s.N_p, r[3] = s.compression;
             return;
         }
         default: break;

@@ -734,6 +734,23 @@ VAG_DEV double compression_fwd(double Gd) {
     return (u_down == 0.) ? 4 * g : u_up * rcp_fast(u_down);
 }
 
+// save_fwd_shock_state (forward-shock.tpp:151-173) on the interpolated ODE state of one cell: Gamma, the upstream density rho,
+// the thermal energy U_th and the swept mass m2 (per solid angle).  An unshocked cell (m2 == 0) keeps Gamma_th = 1, B = 0, N_p = 0.
+struct FwdState {
+    double Gamma_th, B, N_p, compression;
+};
+VAG_DEV FwdState fwd_shock_state(double Gamma, double rho, double U, double m2, double eps_B) {
+    FwdState s{1, 0, 0, 0};
+    if (m2 != 0) {
+        s.compression = compression_fwd(Gamma);
+        s.Gamma_th = U * rcp_fast(m2 * C_C2) + 1;
+        const double e_th = (s.Gamma_th - 1) * (rho * s.compression) * C_C2;
+        s.B = sqrt_fast(8 * C_PI * eps_B * e_th);
+        s.N_p = m2 / C_MP;
+    }
+    return s;
+}
+
 // ---- synchrotron electrons + photons for one cell: src/radiation/synchrotron.cpp:45-254,315-408,
 //      smooth-power-law-syn.cpp:49-153.  Writes the VAG_NPAR block. ----
 VAG_DEV double syn_freq(double gamma, double B) {

@@ -629,12 +629,8 @@ vag_cells_kernel(const vag_model_params* __restrict__ params, int nb, const VagG
         if (m2 != 0) {
             Medium med;
             medium_init(med, P);
-            const double comp = compression_fwd(shock[VS_GAMMA * n_cells + c]);
-            const double rho = medium_rho(med, shock[VS_R * n_cells + c]);
-            c_Gth = U * rcp_fast(m2 * C_C2) + 1;
-            const double e_th = (c_Gth - 1) * (rho * comp) * C_C2;
-            c_B = sqrt_fast(8 * C_PI * P.eps_B * e_th);
-            c_Np = m2 / C_MP;
+            const FwdState s = fwd_shock_state(shock[VS_GAMMA * n_cells + c], medium_rho(med, shock[VS_R * n_cells + c]), U, m2, P.eps_B);
+            c_Gth = s.Gamma_th, c_B = s.B, c_Np = s.N_p;
         }
         if (write_back) {
             raw_shock[VS_GAMMA_TH * n_cells + c] = c_Gth;
