@@ -977,6 +977,68 @@ int vag_stretch_accept_dev(vag_ctx* ctx, const vag_stretch_spec* sp, uint64_t st
 int vag_stretch_run_dev(vag_ctx* ctx, const vag_loglike_request* request, const vag_stretch_spec* sp, uint64_t step0, int n_steps,
                         double* d_pos, double* d_lp, int64_t* d_accepted, double* d_chain, double* d_logp);
 
+/* Parallel tempering around the stretch move (added after VAG_ABI_VERSION 13, detect by symbol).
+ * The ladder: n_temps = T temperatures, 1 <= T <= VAG_TEMPER_MAX; the inverse temperatures betas[T] are finite, betas[0] = 1,
+ * strictly descending, betas[T - 1] >= 0 (0, the prior, is allowed as the last rung).  Temperature t targets
+ * ln p_t = betas[t] ln L + ln prior with an ensemble of n_walkers walkers of its own (even, >= 2 ndim, ndim 1 .. 16).  Layouts:
+ * pos[T][n_walkers][ndim], lnl[T][n_walkers], lnprior[T][n_walkers], prop[T][n_walkers / 2][ndim], accepted[T][n_walkers],
+ * swapped[max(T - 1, 1)][n_walkers].
+ * The draws are the stretch move's: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (r, step & 0xffffffff, step >> 32, stream), r = t n_walkers + w the replica's index in the whole ladder, stream 0 the proposal,
+ * 1 the acceptance, 2 the exchange; with T = 1 the counters are those of vag_stretch_*_dev.
+ * A step is half 0, half 1, then the exchanges.  Half h: every temperature proposes the walkers of its own half h against its own
+ * other half exactly as the stretch move does (z and the partner from stream 0, prop = fma(z, pos[t][w] - pos[t][partner],
+ * pos[t][partner])).  A proposal whose ln L or ln prior is not finite is rejected at every temperature, beta = 0 included (so every
+ * current state has both finite, and the beta = 0 rung is the prior restricted to where the model evaluates); any other is accepted
+ * iff log(u_a) < (ndim - 1) log(z) + fma(beta_t, lnl_new - lnl_old, lnprior_new - lnprior_old), u_a from stream 1.  An accepted
+ * walker takes the proposal, its ln L and its ln prior, and accepted[t][w] counts one.
+ * The exchanges of step s: the pairs (t, t + 1) with t + s even (deterministic even-odd), walker w of t with walker w of t + 1
+ * (the walkers of an ensemble are exchangeable: a fixed pairing keeps detailed balance).  With u_s from stream 2 at
+ * r = t n_walkers + w the pair exchanges iff log(u_s) < (beta_t - beta_t+1) (lnl[t + 1][w] - lnl[t][w]); it then swaps positions,
+ * ln L and ln prior, and swapped[t][w] counts one.  T = 1 has no exchanges.
+ * Step s is stored when (s + 1) % thin == 0: the state after the exchanges. */
+#define VAG_TEMPER_MAX 64
+typedef struct vag_tempered_spec {
+    uint64_t seed;
+    double a;             /* the stretch scale, finite and > 1 */
+    int32_t n_temps;      /* T: 1 .. VAG_TEMPER_MAX */
+    int32_t n_walkers;    /* per temperature: even, >= 2 ndim */
+    int32_t ndim;         /* 1 .. 16 */
+    int32_t thin;         /* >= 1 */
+    const double* betas;  /* host, [n_temps] */
+} vag_tempered_spec;
+
+/* A likelihood call (the blocks of `request`, as vag_loglike_cov_batch_dev) that returns ln L and ln prior apart, by walker:
+ * d_lnl[i] = -chi2 / 2 where the walker was evaluated and its chi^2 is finite, else -inf; d_lnprior[i] the sum of ln prior under
+ * spec->use_priors (-inf outside the bounds), else 0.  d_lnl + d_lnprior equals the output of the likelihood entry to the bit
+ * wherever that is finite; where that is -inf, at least one of the two is.  Stream-ordered, host-blocking as
+ * vag_loglike_batch_dev is. */
+int vag_loglike_split_dev(vag_ctx* ctx, const vag_loglike_request* request, const double* d_theta, int nb, int ndim, double* d_lnl,
+                          double* d_lnprior);
+
+/* The building blocks (no model), as vag_stretch_propose_dev / vag_stretch_accept_dev: a caller's evaluator of the T n_walkers / 2
+ * proposals goes between propose and accept, and swap follows the two halves.  Device pointers, the context's stream, no host
+ * synchronisation.  Refused with VAG_E_INVALID (the context stays usable): whatever the stretch entries refuse; n_temps outside
+ * 1 .. VAG_TEMPER_MAX (or n_temps n_walkers above 2^30); null betas; betas[0] != 1; a rung that is not finite, not strictly below
+ * the one before it, or negative; half not 0 or 1. */
+int vag_tempered_propose_dev(vag_ctx* ctx, const vag_tempered_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop);
+int vag_tempered_accept_dev(vag_ctx* ctx, const vag_tempered_spec* sp, uint64_t step, int half, const double* d_prop,
+                            const double* d_lnl_new, const double* d_lnprior_new, double* d_pos, double* d_lnl, double* d_lnprior,
+                            int64_t* d_accepted);
+int vag_tempered_swap_dev(vag_ctx* ctx, const vag_tempered_spec* sp, uint64_t step, double* d_pos, double* d_lnl, double* d_lnprior,
+                          int64_t* d_swapped);
+
+/* Steps step0 .. step0 + n_steps - 1 on the likelihood of `request`: per step and half, propose, ONE likelihood call of the
+ * T n_walkers / 2 proposals, its split into ln L and ln prior, accept; then the exchanges.  On entry d_lnl / d_lnprior hold those of
+ * d_pos, all finite.  The blocks are scanned and uploaded once per call; between the steps there is no copy to the host and no stream
+ * synchronisation (a likelihood call itself waits for its device plan).  A stored step writes its row [T][n_walkers][ndim] of
+ * d_chain and [T][n_walkers] of d_lnl_chain and d_lnprior_chain, consecutive from the pointers given; all three null: nothing is
+ * stored.  n_steps = 0 does nothing.  Refusals as above, and: a null request or request->spec, ndim different from
+ * request->spec->ndim, n_steps < 0, the three chain pointers not all null or all set, and whatever the likelihood call refuses. */
+int vag_tempered_run_dev(vag_ctx* ctx, const vag_loglike_request* request, const vag_tempered_spec* sp, uint64_t step0, int n_steps,
+                         double* d_pos, double* d_lnl, double* d_lnprior, int64_t* d_accepted, int64_t* d_swapped, double* d_chain,
+                         double* d_lnl_chain, double* d_lnprior_chain);
+
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.
  * Stream-ordered on the context stream, but host-blocking: the call returns after the batch's device plan has been read back

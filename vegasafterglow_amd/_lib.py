@@ -221,6 +221,24 @@ def stretch_entry(lib, name):
     return getattr(lib, name)
 
 
+class TemperedSpec(C.Structure):  # vag_tempered_spec; betas points into a host array the caller keeps
+    _fields_ = [("seed", C.c_uint64), ("a", C.c_double), ("n_temps", C.c_int32), ("n_walkers", C.c_int32), ("ndim", C.c_int32),
+                ("thin", C.c_int32), ("betas", C.POINTER(C.c_double))]
+
+
+TEMPER_MAX = 64  # VAG_TEMPER_MAX
+TEMPERED_ENTRIES = ("vag_loglike_split_dev", "vag_tempered_propose_dev", "vag_tempered_accept_dev", "vag_tempered_swap_dev",
+                    "vag_tempered_run_dev")
+
+
+def tempered_entry(lib, name):
+    """One of the parallel-tempering entry points, added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build)."""
+    if not hasattr(lib, name):
+        raise RuntimeError(f"the loaded library has no {name}: parallel tempering (sampling.TemperedMove, run_tempered_device, "
+                           "Fitter.log_like_and_prior_batch, fit(sampler='tempered')) needs a newer build")
+    return getattr(lib, name)
+
+
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_LOG_UNIFORM, PRIOR_NONE, PRIOR_UNIFORM_RANGE = 0, 1, 2, 3, 4
 
 
@@ -274,6 +292,7 @@ EXPORTS = [
     "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev", "vag_loglike_index_batch", "vag_loglike_index_batch_dev",
     "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev", "vag_loglike_tmpl_batch", "vag_loglike_tmpl_batch_dev",
     "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev", "vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev",
+    "vag_loglike_split_dev", "vag_tempered_propose_dev", "vag_tempered_accept_dev", "vag_tempered_swap_dev", "vag_tempered_run_dev",
 ]
 
 _lib = None
@@ -375,6 +394,13 @@ def load():
         lib.vag_stretch_propose_dev.argtypes = [v, sp, C.c_uint64, C.c_int, v, v]
         lib.vag_stretch_accept_dev.argtypes = [v, sp, C.c_uint64, C.c_int, v, v, v, v, v]
         lib.vag_stretch_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), sp, C.c_uint64, C.c_int, v, v, v, v, v]
+    if hasattr(lib, "vag_tempered_run_dev"):  # (detected by symbol: parallel tempering)
+        tp = C.POINTER(TemperedSpec)
+        lib.vag_loglike_split_dev.argtypes = [v, C.POINTER(LoglikeRequest), v, C.c_int, C.c_int, v, v]
+        lib.vag_tempered_propose_dev.argtypes = [v, tp, C.c_uint64, C.c_int, v, v]
+        lib.vag_tempered_accept_dev.argtypes = [v, tp, C.c_uint64, C.c_int, v, v, v, v, v, v, v]
+        lib.vag_tempered_swap_dev.argtypes = [v, tp, C.c_uint64, v, v, v, v]
+        lib.vag_tempered_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), tp, C.c_uint64, C.c_int, v, v, v, v, v, v, v, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -31,6 +31,7 @@
 #include "vag_index.h"
 #include "vag_fit_kernels.h"
 #include "vag_sampler.h"
+#include "vag_tempering.h"
 #include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
 #include "vag_flux_plan.h"    // (host only: the launch decisions of the flux stage)
 
@@ -439,6 +440,7 @@ struct vag_ctx {
     DevBuf d_skycen, d_skycmom;  // exact centroids (vag_sky.h): row-block partials, moments
     DevBuf d_visblk, d_vispart;  // visibility groups of the likelihood (their data: vis below): their 64-visibility blocks, chi^2 partials
     DevBuf d_stretch_prop, d_stretch_lp;  // the device sampler (vag_stretch_run_dev): a half's proposals [half][ndim] and their ln p [half]
+    DevBuf d_temper_prop, d_temper_lnl, d_temper_lnprior;  // parallel tempering (vag_tempered_run_dev): all temperatures' proposals of a half [T][half][ndim], their ln L and ln prior [T][half]
     DevBuf d_polspec, d_polstokes;  // polarization groups of the likelihood (their data: pol below): the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -738,7 +740,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_stretch_prop, &c->d_stretch_lp})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_stretch_prop, &c->d_stretch_lp, &c->d_temper_prop, &c->d_temper_lnl, &c->d_temper_lnprior})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3505,6 +3507,7 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
     // evaluation order: by the costs of the previous call with this batch size (see vag_ctx::d_order)
     const bool can_order = nb >= 64 && nb <= 8192 && !vag_hook("VAG_NO_ORDER");
     const int* d_order = (can_order && c->order_nb == nb) ? c->d_order[c->order_cur].as<int>() : nullptr;
+    c->last_order = d_order;  // (every pass sets it again; a call without a pass leaves no stale order to vag_fit_split_kernel)
     hipLaunchKernelGGL(vag_fit_front_kernel, dim3((nb + 127) / 128), dim3(128), 0, st, spec->base, d_theta, nb, ndim, d_prior,
                        spec->use_priors, spec->a_v_fixed, d_params, d_av, d_lp, c->d_fitstat.as<int>(), d, n, d + fl.nu,
                        c->d_lg2t.as<double>(), c->d_lg2nu.as<double>(), c->d_tminmax.as<double>(), d_order);
@@ -3974,6 +3977,170 @@ int vag_stretch_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_stre
                 return rc;
         }
         if (stored) ++row;
+    }
+    return VAG_OK;
+}
+
+// ---- parallel tempering (kernels: vag_tempering.h; the move: the public header) ----
+
+// ln L and ln prior of the last likelihood call's nb walkers apart, from what loglike_body leaves by evaluation slot
+static int fit_split(vag_ctx* c, int nb, double* d_lnl, double* d_lnprior) {
+    const double* d_chi2 = c->d_chi2.as<double>();  // [chi2 | A_V | ln prior]
+    hipLaunchKernelGGL(vag_fit_split_kernel, dim3((nb + STRETCH_LANES - 1) / STRETCH_LANES), dim3(STRETCH_LANES), 0, c->stream, d_chi2,
+                       c->d_valid.as<int>(), d_chi2 + 2 * (size_t)nb, nb, c->last_order, d_lnl, d_lnprior);
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+int vag_loglike_split_dev(vag_ctx* c, const vag_loglike_request* q, const double* d_theta, int nb, int ndim, double* d_lnl,
+                          double* d_lnprior) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);  // (closes behind the split, after the one of the call inside)
+    if (!c || !q || !q->spec || !d_theta || !d_lnl || !d_lnprior) return set_err(VAG_E_INVALID, "null context, request, fit spec or device pointer");
+    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
+    const int rc = loglike_dev(c, req, d_theta, nb, ndim, d_lnl);  // (ln L + ln prior by walker, which the split then replaces)
+    if (rc) return rc;
+    return fit_split(c, nb, d_lnl, d_lnprior);
+}
+
+static_assert(VAG_TEMPER_MAX == VAG_TEMPER_MAX_RUNGS, "the public ladder limit is the kernels'");
+
+// the checks of a tempered spec (not null); fills the ladder the kernels take by value
+static int tempered_spec_check(const vag_tempered_spec* sp, TemperLadder& ladder) {
+    const vag_stretch_spec one{sp->seed, sp->a, sp->n_walkers, sp->ndim, sp->thin};
+    if (const int rc = stretch_spec_check(&one)) return rc;
+    if (sp->n_temps < 1 || sp->n_temps > VAG_TEMPER_MAX)
+        return set_err(VAG_E_INVALID, "tempering: n_temps must be 1..%d, got %d", VAG_TEMPER_MAX, sp->n_temps);
+    if ((long long)sp->n_temps * sp->n_walkers > (1ll << 30))
+        return set_err(VAG_E_INVALID, "tempering: n_temps * n_walkers must not exceed 2^30, got %lld", (long long)sp->n_temps * sp->n_walkers);
+    if (!sp->betas) return set_err(VAG_E_INVALID, "tempering: null betas");
+    if (sp->betas[0] != 1.0) return set_err(VAG_E_INVALID, "tempering: betas[0] must be 1, got %g", sp->betas[0]);
+    for (int t = 0; t < VAG_TEMPER_MAX; ++t) ladder.beta[t] = 0.0;
+    for (int t = 0; t < sp->n_temps; ++t) {
+        const double b = sp->betas[t];
+        if (!std::isfinite(b) || b < 0.0 || (t > 0 && !(b < sp->betas[t - 1])))
+            return set_err(VAG_E_INVALID, "tempering: betas must be finite, strictly descending and >= 0; betas[%d] = %g", t, b);
+        ladder.beta[t] = b;
+    }
+    return VAG_OK;
+}
+
+static inline dim3 tempered_groups(long long items) { return dim3((unsigned)((items + STRETCH_LANES - 1) / STRETCH_LANES)); }
+
+static int tempered_propose(vag_ctx* c, const vag_tempered_spec* sp, uint64_t step, int which, const double* d_pos, double* d_prop) {
+    const int half = sp->n_walkers / 2;
+    hipLaunchKernelGGL(vag_tempered_propose_kernel, tempered_groups((long long)sp->n_temps * half), dim3(STRETCH_LANES), 0, c->stream,
+                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), sp->a, (unsigned long long)step, which, half,
+                       sp->ndim, sp->n_temps, d_pos, d_prop);
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+static int tempered_accept(vag_ctx* c, const vag_tempered_spec* sp, const TemperLadder& ladder, uint64_t step, int which,
+                           const double* d_prop, const double* d_lnl_new, const double* d_lnprior_new, double* d_pos, double* d_lnl,
+                           double* d_lnprior, int64_t* d_accepted) {
+    const int half = sp->n_walkers / 2;
+    hipLaunchKernelGGL(vag_tempered_accept_kernel, tempered_groups((long long)sp->n_temps * half), dim3(STRETCH_LANES), 0, c->stream,
+                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), sp->a, (unsigned long long)step, which, half,
+                       sp->ndim, sp->n_temps, ladder, d_prop, d_lnl_new, d_lnprior_new, d_pos, d_lnl, d_lnprior,
+                       reinterpret_cast<long long*>(d_accepted));
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+static int tempered_swap(vag_ctx* c, const vag_tempered_spec* sp, const TemperLadder& ladder, uint64_t step, double* d_pos, double* d_lnl,
+                         double* d_lnprior, int64_t* d_swapped) {
+    const int n_pairs = (sp->n_temps - (int)(step & 1u)) / 2;  // the pairs (t, t + 1) with t + step even
+    if (n_pairs <= 0) return VAG_OK;
+    hipLaunchKernelGGL(vag_tempered_swap_kernel, tempered_groups((long long)n_pairs * sp->n_walkers), dim3(STRETCH_LANES), 0, c->stream,
+                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), (unsigned long long)step, sp->n_walkers, sp->ndim,
+                       n_pairs, ladder, d_pos, d_lnl, d_lnprior, reinterpret_cast<long long*>(d_swapped));
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+int vag_tempered_propose_dev(vag_ctx* c, const vag_tempered_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !sp || !d_pos || !d_prop) return set_err(VAG_E_INVALID, "null context, tempered spec or buffer");
+    TemperLadder ladder;
+    if (const int rc = tempered_spec_check(sp, ladder)) return rc;
+    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "tempering: half must be 0 or 1, got %d", half);
+    HIPCHK(hipSetDevice(c->device));
+    return tempered_propose(c, sp, step, half, d_pos, d_prop);
+}
+
+int vag_tempered_accept_dev(vag_ctx* c, const vag_tempered_spec* sp, uint64_t step, int half, const double* d_prop,
+                            const double* d_lnl_new, const double* d_lnprior_new, double* d_pos, double* d_lnl, double* d_lnprior,
+                            int64_t* d_accepted) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !sp || !d_prop || !d_lnl_new || !d_lnprior_new || !d_pos || !d_lnl || !d_lnprior || !d_accepted)
+        return set_err(VAG_E_INVALID, "null context, tempered spec or buffer");
+    TemperLadder ladder;
+    if (const int rc = tempered_spec_check(sp, ladder)) return rc;
+    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "tempering: half must be 0 or 1, got %d", half);
+    HIPCHK(hipSetDevice(c->device));
+    return tempered_accept(c, sp, ladder, step, half, d_prop, d_lnl_new, d_lnprior_new, d_pos, d_lnl, d_lnprior, d_accepted);
+}
+
+int vag_tempered_swap_dev(vag_ctx* c, const vag_tempered_spec* sp, uint64_t step, double* d_pos, double* d_lnl, double* d_lnprior,
+                          int64_t* d_swapped) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !sp || !d_pos || !d_lnl || !d_lnprior || !d_swapped) return set_err(VAG_E_INVALID, "null context, tempered spec or buffer");
+    TemperLadder ladder;
+    if (const int rc = tempered_spec_check(sp, ladder)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return tempered_swap(c, sp, ladder, step, d_pos, d_lnl, d_lnprior, d_swapped);
+}
+
+int vag_tempered_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_tempered_spec* sp, uint64_t step0, int n_steps,
+                         double* d_pos, double* d_lnl, double* d_lnprior, int64_t* d_accepted, int64_t* d_swapped, double* d_chain,
+                         double* d_lnl_chain, double* d_lnprior_chain) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !q || !q->spec || !sp || !d_pos || !d_lnl || !d_lnprior || !d_accepted || !d_swapped)
+        return set_err(VAG_E_INVALID, "null context, request, fit spec, tempered spec or buffer");
+    if ((d_chain == nullptr) != (d_lnl_chain == nullptr) || (d_chain == nullptr) != (d_lnprior_chain == nullptr))
+        return set_err(VAG_E_INVALID, "tempering: the chain, its ln L and its ln prior are stored together or not at all");
+    TemperLadder ladder;
+    if (const int rc = tempered_spec_check(sp, ladder)) return rc;
+    if (sp->ndim != q->spec->ndim) return set_err(VAG_E_INVALID, "tempering: ndim %d is not the fit spec's %d", sp->ndim, q->spec->ndim);
+    if (n_steps < 0) return set_err(VAG_E_INVALID, "tempering: n_steps must be >= 0, got %d", n_steps);
+    if (n_steps == 0) return VAG_OK;
+    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
+    int rc = fit_request_prepare(req);  // the scans, once per call of many steps
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const int ndim = sp->ndim, nw = sp->n_walkers, half = nw / 2, nb = sp->n_temps * half;
+    const size_t replicas = (size_t)sp->n_temps * nw;
+    req.ndim = ndim;
+    rc = upload_blocks(c, req);  // and the uploads
+    if (rc) return rc;
+    if (c->d_temper_prop.ensure(sizeof(double) * (size_t)nb * ndim)) return VAG_E_HIP;
+    if (c->d_temper_lnl.ensure(sizeof(double) * (size_t)nb)) return VAG_E_HIP;
+    if (c->d_temper_lnprior.ensure(sizeof(double) * (size_t)nb)) return VAG_E_HIP;
+    double* d_prop = c->d_temper_prop.as<double>();
+    double* d_lnl_new = c->d_temper_lnl.as<double>();
+    double* d_lnprior_new = c->d_temper_lnprior.as<double>();
+    size_t row = 0;  // stored rows so far
+    for (int k = 0; k < n_steps; ++k) {
+        const uint64_t step = step0 + (uint64_t)k;
+        for (int which = 0; which < 2; ++which) {  // all temperatures' proposals of the half in ONE likelihood call
+            if ((rc = tempered_propose(c, sp, step, which, d_pos, d_prop))) return rc;
+            if ((rc = loglike_call(c, req, d_prop, nb, ndim, d_lnl_new))) return rc;
+            if ((rc = fit_split(c, nb, d_lnl_new, d_lnprior_new))) return rc;
+            if ((rc = tempered_accept(c, sp, ladder, step, which, d_prop, d_lnl_new, d_lnprior_new, d_pos, d_lnl, d_lnprior, d_accepted)))
+                return rc;
+        }
+        if ((rc = tempered_swap(c, sp, ladder, step, d_pos, d_lnl, d_lnprior, d_swapped))) return rc;
+        if (d_chain && (step + 1) % (uint64_t)sp->thin == 0) {  // the state after the exchanges (device-to-device, stream-ordered)
+            HIPCHK(hipMemcpyAsync(d_chain + row * replicas * ndim, d_pos, sizeof(double) * replicas * ndim, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_lnl_chain + row * replicas, d_lnl, sizeof(double) * replicas, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_lnprior_chain + row * replicas, d_lnprior, sizeof(double) * replicas, hipMemcpyDeviceToDevice, c->stream));
+            ++row;
+        }
     }
     return VAG_OK;
 }

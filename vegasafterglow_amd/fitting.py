@@ -1807,7 +1807,9 @@ class Fitter:
     # fitter.py:545-674 (the emcee branch; the stretch-move sampler of vegasafterglow_amd.sampling needs no third-party package)
     def fit(self, param_defs, nwalkers=None, nsteps=1000, nburn=0, seed=0, sampler="host", **kw):
         """sampling.fit on this fitter.  ``sampler="host"``: the numpy stretch move around one device call per half-step;
-        ``sampler="device"``: the whole run on the device (sampling.run_stretch_move_device)."""
+        ``sampler="device"``: the whole run on the device (sampling.run_stretch_move_device); ``sampler="tempered"``: parallel
+        tempering on the device (sampling.run_tempered_device; ``ntemps``, ``beta_min``, ``prior_rung`` shape the ladder, `nwalkers`
+        is per temperature), which also returns the evidence by thermodynamic integration."""
         from . import sampling
         self.validate_parameters(param_defs)
         ndim = sum(1 for pd in param_defs if pd.scale is not Scale.fixed)
@@ -1944,6 +1946,33 @@ class Fitter:
             out = out + np.asarray(prior.ln_prob(samples[:, d]), dtype=np.float64)
         out[~np.isfinite(out)] = -np.inf
         return out
+
+    def log_like_and_prior_batch(self, samples, param_defs, priors=None):
+        """(ln L, ln prior) of each row of samples[nb, ndim], apart, in ONE device call (vag_loglike_split_dev): what tempering
+        needs, which scales ln L alone.  ln prior is the sum of the priors with the bounds mask, as in log_prob_batch (host-only
+        priors are added on the host); ln L is -inf for a walker that was not evaluated, one outside the bounds included.
+        ln L + ln prior equals log_prob_batch to the bit wherever that is finite."""
+        import torch
+        from . import sampling
+        spec, _, _ = self.build_spec(param_defs, priors=priors, use_priors=True)
+        samples = np.ascontiguousarray(np.atleast_2d(np.asarray(samples, dtype=np.float64)))
+        if samples.shape[1] != spec.ndim:
+            raise ValueError("samples must be [nb, ndim]")
+        dev = torch.device("cuda", self.device)
+        theta = torch.from_numpy(samples).to(dev)
+        lnl = torch.empty((samples.shape[0],), dtype=torch.float64, device=dev)
+        lnprior = torch.empty_like(lnl)
+        sampling.loglike_split_device(self, spec, theta, lnl, lnprior)
+        plan = _lib.Plan()
+        h, lock = get_context(self.device)
+        with lock:
+            _lib.load().vag_last_plan(h, C.byref(plan))
+        self._log_plan_warnings(plan, samples.shape[0])
+        self.last_plan = plan
+        lnl, lnprior = lnl.cpu().numpy(), lnprior.cpu().numpy()
+        for d, prior in self._host_priors:
+            lnprior = lnprior + np.asarray(prior.ln_prob(samples[:, d]), dtype=np.float64)
+        return lnl, lnprior
 
     def make_log_prob_batch(self, param_defs, loglike_fn=None, priors=None):
         """log_prob_batch(samples) of fitting/samplers.py:72-91: out-of-bounds -> -inf; otherwise ln L + sum ln prior, evaluated

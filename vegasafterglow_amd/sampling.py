@@ -11,6 +11,10 @@ walkers over a thread pool (VegasAfterglow/fitting/samplers.py:59-106).  Here th
 * ``run_stretch_move_device`` / ``StretchMove`` -- the stretch move itself on the device (fixed halves, Philox draws keyed by
   (seed, step, walker)): a run of steps is launches only, positions, ln p and the chain stay in HBM.  ``run_stretch_move_philox``,
   ``stretch_proposals`` and ``stretch_accepts`` state the same move in numpy, to the bit;
+* ``run_tempered_device`` / ``TemperedMove`` -- parallel tempering around that move on the device: a ladder of inverse temperatures
+  (``geometric_betas``), all temperatures' proposals in one likelihood call per half-step, exchanges between neighbours, and the
+  evidence by thermodynamic integration (``thermodynamic_evidence``).  ``run_tempered_philox``, ``tempered_proposals``,
+  ``tempered_accepts`` and ``tempered_swaps`` state it in numpy, to the bit;
 * ``BatchPool`` -- the object handed to ``bilby.run_sampler(pool=...)`` in place of the reference's thread pool
   (samplers.py:146-170): ``pool.map(loglikelihood, points)`` becomes one device call over the whole live-point queue.
 """
@@ -375,19 +379,390 @@ def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0
     return chain.cpu().numpy(), logp.cpu().numpy(), accepted.cpu().numpy() / max(nsteps, 1)
 
 
+# ---- parallel tempering around that move (INTEGRATION.md "Parallel tempering"): a ladder of T inverse temperatures, temperature t
+#      sampling beta_t ln L + ln prior with an ensemble of its own, exchanges between neighbours, the evidence by thermodynamic
+#      integration.  The numpy statement first, then the device. ----
+
+TEMPER_MAX = 64  # VAG_TEMPER_MAX
+
+
+def geometric_betas(ntemps: int, beta_min: float = 1e-3, prior_rung: bool = False) -> np.ndarray:
+    """The ladder beta_t = beta_min ** (t / (ntemps - 1)), t = 0 .. ntemps - 1: from 1 down to beta_min in equal ratios.  With
+    ``prior_rung`` the last rung is 0 (the prior) and the others are spread over ntemps - 1: beta_min ** (t / (ntemps - 2))."""
+    ntemps = int(ntemps)
+    if not 1 <= ntemps <= TEMPER_MAX:
+        raise ValueError(f"ntemps must be 1..{TEMPER_MAX}")
+    if not (np.isfinite(beta_min) and 0.0 < beta_min < 1.0):
+        raise ValueError("beta_min must lie in (0, 1)")
+    n = ntemps - 1 if prior_rung else ntemps
+    if prior_rung and ntemps < 2:
+        raise ValueError("a ladder with a prior rung has at least two temperatures")
+    betas = np.ones(n) if n == 1 else float(beta_min) ** (np.arange(n) / (n - 1.0))
+    betas[0] = 1.0
+    return np.append(betas, 0.0) if prior_rung else betas
+
+
+def _check_betas(betas) -> np.ndarray:
+    betas = np.ascontiguousarray(betas, dtype=np.float64)
+    if betas.ndim != 1 or not 1 <= betas.size <= TEMPER_MAX:
+        raise ValueError(f"betas must hold 1..{TEMPER_MAX} inverse temperatures")
+    if betas[0] != 1.0:
+        raise ValueError("betas must start at 1")
+    if not np.all(np.isfinite(betas)) or np.any(np.diff(betas) >= 0.0) or betas[-1] < 0.0:
+        raise ValueError("betas must be finite, strictly descending and >= 0")
+    return betas
+
+
+def _tempered_words(ntemps, nwalkers, walkers, step, seed, stream):
+    """The four Philox words of the replicas r = t nwalkers + w, w in `walkers`, of every temperature: uint32[T, len(walkers), 4]."""
+    step, seed = int(step), int(seed)
+    r = (np.arange(ntemps, dtype=np.uint64)[:, None] * np.uint64(nwalkers) + np.asarray(walkers, dtype=np.uint64)[None, :])
+    counter = np.empty(r.shape + (4,), dtype=np.uint64)
+    counter[..., 0] = r
+    counter[..., 1], counter[..., 2], counter[..., 3] = step & 0xFFFFFFFF, (step >> 32) & 0xFFFFFFFF, stream
+    return philox4x32(counter, np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint64))
+
+
+def tempered_log_ratio(beta, lnl_new, lnl_old, lnprior_new, lnprior_old):
+    """vag::tempered_log_ratio in numpy: fma(beta, lnl_new - lnl_old, lnprior_new - lnprior_old)."""
+    from .fitting import _fma
+    lnl_new, lnl_old, lnprior_new, lnprior_old = (np.asarray(v, dtype=np.float64) for v in (lnl_new, lnl_old, lnprior_new, lnprior_old))
+    return _fma(beta, lnl_new - lnl_old, lnprior_new - lnprior_old)
+
+
+def swap_log_ratio(beta_lo, beta_hi, lnl_lo, lnl_hi):
+    """vag::swap_log_ratio in numpy: (beta_lo - beta_hi) (lnl_hi - lnl_lo)."""
+    return (np.asarray(beta_lo, dtype=np.float64) - beta_hi) * (np.asarray(lnl_hi, dtype=np.float64) - lnl_lo)
+
+
+def tempered_proposals(pos, step, half, seed, a=2.0):
+    """The proposals of half `half` of every temperature at absolute step `step`, from pos[T, nw, ndim]:
+    (prop[T, nw / 2, ndim], z[T, nw / 2], partner[T, nw / 2]), partner the index within the temperature's ensemble.  Bit for bit
+    what vag_tempered_propose_dev computes."""
+    from .fitting import _fma
+    pos = np.asarray(pos, dtype=np.float64)
+    ntemps, nw, _ = pos.shape
+    nh = nw // 2
+    x = _tempered_words(ntemps, nw, half * nh + np.arange(nh), step, seed, 0)
+    z = stretch_z(a, _u53(x[..., 0], x[..., 1]))
+    partner = (1 - half) * nh + ((x[..., 2].astype(np.uint64) * np.uint64(nh)) >> np.uint64(32)).astype(np.int64)
+    other = np.take_along_axis(pos, partner[..., None], axis=1)
+    return _fma(z[..., None], pos[:, half * nh:(half + 1) * nh] - other, other), z, partner
+
+
+def tempered_accepts(step, half, seed, z, betas, lnl_new, lnprior_new, lnl_old, lnprior_old, ndim):
+    """The decisions of half `half` of every temperature at step `step`: (take[T, nw / 2], margin[T, nw / 2]).  A proposal whose
+    ln L or ln prior is not finite is rejected at every temperature (margin -inf); any other is taken iff
+    log(u_a) < (ndim - 1) log z + fma(beta_t, lnl_new - lnl_old, lnprior_new - lnprior_old), and margin is that right side minus the
+    left, as in stretch_accepts."""
+    z, lnl_new, lnprior_new, lnl_old, lnprior_old = (np.asarray(v, dtype=np.float64) for v in (z, lnl_new, lnprior_new, lnl_old, lnprior_old))
+    ntemps, nh = z.shape
+    y = _tempered_words(ntemps, 2 * nh, half * nh + np.arange(nh), step, seed, 1)
+    finite = np.isfinite(lnl_new) & np.isfinite(lnprior_new)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        ratio = tempered_log_ratio(np.asarray(betas, dtype=np.float64)[:, None], np.where(finite, lnl_new, 0.0), lnl_old,
+                                   np.where(finite, lnprior_new, 0.0), lnprior_old)
+        margin = ((ndim - 1.0) * np.log(z) + ratio) - np.log(_u53(y[..., 0], y[..., 1]))  # (u_a = 0: log = -inf, taken)
+    margin = np.where(finite, margin, -np.inf)
+    return finite & (margin > 0), margin
+
+
+def tempered_swaps(step, seed, betas, lnl):
+    """The exchanges of step `step` from lnl[T, nw]: (lower[npairs], take[npairs, nw], margin[npairs, nw]).  lower holds the t of
+    the attempted pairs (t, t + 1), those with t + step even; walker w of t pairs with walker w of t + 1 and they exchange iff
+    log(u_s) < (beta_t - beta_t+1) (lnl[t + 1, w] - lnl[t, w]), u_s from stream 2 at r = t nw + w; margin is the right side minus
+    the left."""
+    betas, lnl = np.asarray(betas, dtype=np.float64), np.asarray(lnl, dtype=np.float64)
+    ntemps, nw = lnl.shape
+    lower = np.arange(int(step) & 1, ntemps - 1, 2)
+    y = _tempered_words(ntemps, nw, np.arange(nw), step, seed, 2)[lower]
+    with np.errstate(divide="ignore"):
+        margin = swap_log_ratio(betas[lower, None], betas[lower + 1, None], lnl[lower], lnl[lower + 1]) - np.log(_u53(y[..., 0], y[..., 1]))
+    return lower, margin > 0, margin
+
+
+def swap_attempts(ntemps, step0, nsteps):
+    """How often each pair (t, t + 1) is attempted in steps step0 .. step0 + nsteps - 1: the steps s with t + s even."""
+    t = np.arange(max(ntemps - 1, 0))
+    first = step0 + ((t + step0) & 1)  # the first such step
+    return np.maximum(0, (step0 + nsteps - first + 1) // 2)
+
+
+def run_tempered_philox(log_like_batch: Callable[[np.ndarray], np.ndarray], log_prior_batch: Callable[[np.ndarray], np.ndarray],
+                        pos0: np.ndarray, betas, nsteps: int, seed: int = 0, a: float = 2.0, thin: int = 1, step0: int = 0,
+                        margins: Optional[list] = None):
+    """Parallel tempering through any two host callables (ln L and ln prior of rows [n, ndim]): the chain of the device's tempered
+    sampler.  pos0[T, nw, ndim]; a step is half 0 and half 1 of every temperature (the stretch move with fixed halves on
+    beta_t ln L + ln prior, the T nw / 2 proposals in one call of each callable), then the exchanges of tempered_swaps.  Runs steps
+    step0 .. step0 + nsteps - 1 and stores step s, the state after its exchanges, when (s + 1) % thin == 0.
+
+    Returns (chain[rows, T, nw, ndim], lnl[rows, T, nw], lnprior[rows, T, nw], acceptance[T, nw], swap_fraction[T - 1]):
+    swap_fraction is accepted over attempted exchanges of the pair (t, t + 1).  ``margins``: a list that receives every half-step's
+    and every exchange phase's margin array."""
+    pos = np.array(pos0, dtype=np.float64, copy=True)
+    if pos.ndim != 3:
+        raise ValueError("pos0 must be [ntemps, nwalkers, ndim]")
+    betas = _check_betas(betas)
+    ntemps, nw, ndim = pos.shape
+    if ntemps != betas.size:
+        raise ValueError("pos0 must be [ntemps, nwalkers, ndim] with one ensemble per entry of betas")
+    _check_stretch(nw, ndim, a, thin)
+    lnl = np.asarray(log_like_batch(pos.reshape(-1, ndim)), dtype=np.float64).reshape(ntemps, nw).copy()
+    lnprior = np.asarray(log_prior_batch(pos.reshape(-1, ndim)), dtype=np.float64).reshape(ntemps, nw).copy()
+    if not (np.all(np.isfinite(lnl)) and np.all(np.isfinite(lnprior))):
+        raise ValueError("initial positions must have finite ln L and ln prior")
+    rows = (step0 + nsteps) // thin - step0 // thin
+    chain, lnl_chain, lnprior_chain = np.empty((rows, ntemps, nw, ndim)), np.empty((rows, ntemps, nw)), np.empty((rows, ntemps, nw))
+    accepted = np.zeros((ntemps, nw), dtype=np.int64)
+    swapped = np.zeros((max(ntemps - 1, 1), nw), dtype=np.int64)
+    nh, row = nw // 2, 0
+    for step in range(step0, step0 + nsteps):
+        for half in (0, 1):
+            s = slice(half * nh, (half + 1) * nh)
+            prop, z, _ = tempered_proposals(pos, step, half, seed, a)
+            flat = prop.reshape(-1, ndim)
+            lnl_new = np.asarray(log_like_batch(flat), dtype=np.float64).reshape(ntemps, nh)
+            lnprior_new = np.asarray(log_prior_batch(flat), dtype=np.float64).reshape(ntemps, nh)
+            take, margin = tempered_accepts(step, half, seed, z, betas, lnl_new, lnprior_new, lnl[:, s], lnprior[:, s], ndim)
+            if margins is not None:
+                margins.append(margin)
+            pos[:, s][take] = prop[take]
+            lnl[:, s][take] = lnl_new[take]
+            lnprior[:, s][take] = lnprior_new[take]
+            accepted[:, s][take] += 1
+        if ntemps > 1:
+            lower, take, margin = tempered_swaps(step, seed, betas, lnl)
+            if margins is not None:
+                margins.append(margin)
+            for k, t in enumerate(lower):
+                w = take[k]
+                for arr in (pos, lnl, lnprior):
+                    arr[t, w], arr[t + 1, w] = arr[t + 1, w].copy(), arr[t, w].copy()
+                swapped[t, w] += 1
+        if (step + 1) % thin == 0:
+            chain[row], lnl_chain[row], lnprior_chain[row] = pos, lnl, lnprior
+            row += 1
+    attempts = swap_attempts(ntemps, step0, nsteps)
+    swap_fraction = swapped[:ntemps - 1].sum(axis=1) / np.maximum(attempts * nw, 1)
+    return chain, lnl_chain, lnprior_chain, accepted / max(nsteps, 1), swap_fraction
+
+
+def thermodynamic_evidence(betas, mean_lnl):
+    """ln Z = integral over beta from 0 to 1 of <ln L>_beta by thermodynamic integration: the trapezoid rule over the ladder on
+    mean_lnl[T], the mean of ln L at each rung (after burn-in).  Returns (ln_z, error_estimate), the estimate being the difference
+    to the same rule on every second rung, as ptemcee does.
+
+    The integral runs from 0: the ladder must reach beta = 0 (geometric_betas(..., prior_rung=True)) or close to it for the number
+    to mean anything -- the part below the last rung is simply missing.  The estimate says nothing about that, and the rule's
+    discretisation error (<ln L>_beta is steep towards small beta) is the caller's to control through the ladder."""
+    betas, mean_lnl = np.asarray(betas, dtype=np.float64), np.asarray(mean_lnl, dtype=np.float64)
+    if betas.ndim != 1 or betas.shape != mean_lnl.shape:
+        raise ValueError("betas and mean_lnl must be one value per rung")
+
+    def trapezoid(b, m):  # (descending beta: the differences are negative)
+        return float(-np.sum(np.diff(b) * 0.5 * (m[1:] + m[:-1])))
+    ln_z = trapezoid(betas, mean_lnl)
+    coarse = np.arange(0, betas.size, 2)
+    if coarse[-1] != betas.size - 1:
+        coarse = np.append(coarse, betas.size - 1)  # (both rules cover the same range)
+    return ln_z, abs(ln_z - trapezoid(betas[coarse], mean_lnl[coarse]))
+
+
+class TemperedMove:
+    """The building blocks of a tempered step on the device (vag_tempered_propose_dev / _accept_dev / _swap_dev), on float64 torch
+    tensors and torch's current stream, like StretchMove; they need no model::
+
+        move = TemperedMove(betas, nw, ndim, seed=7)
+        for step in range(nsteps):
+            for half in (0, 1):
+                prop = move.propose(step, half, pos)                      # [T, nw / 2, ndim] from pos[T, nw, ndim]
+                lnl_new, lnprior_new = evaluate(prop.reshape(-1, ndim))   # any float64[T * nw / 2] pair on the device
+                move.accept(step, half, prop, lnl_new.reshape(T, -1), lnprior_new.reshape(T, -1), pos, lnl, lnprior, accepted)
+            move.swap(step, pos, lnl, lnprior, swapped)                   # swapped: int64[max(T - 1, 1), nw]
+
+    The chain is the one sampling.run_tempered_philox makes from the same ln L and ln prior."""
+
+    def __init__(self, betas, nwalkers: int, ndim: int, seed: int = 0, a: float = 2.0, device: int = 0):
+        self.betas = _check_betas(betas)
+        _check_stretch(nwalkers, ndim, a)
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .model import get_context
+        self.ntemps, self.nwalkers, self.ndim = int(self.betas.size), int(nwalkers), int(ndim)
+        self._lib = _lib.load()
+        self._propose = _lib.tempered_entry(self._lib, "vag_tempered_propose_dev")
+        self._accept = _lib.tempered_entry(self._lib, "vag_tempered_accept_dev")
+        self._swap = _lib.tempered_entry(self._lib, "vag_tempered_swap_dev")
+        self._spec = _lib.TemperedSpec(int(seed) & (2 ** 64 - 1), float(a), self.ntemps, self.nwalkers, self.ndim, 1,
+                                       self.betas.ctypes.data_as(C.POINTER(C.c_double)))
+        self._h, self._lock = get_context(device)
+        self._dev = torch.device("cuda", device)
+
+    _run = StretchMove._run
+    _checked = StretchMove._checked
+
+    def propose(self, step: int, half: int, pos):
+        import ctypes as C
+        import torch
+        from . import _lib
+        nh = self.nwalkers // 2
+        self._checked(pos, (self.ntemps, self.nwalkers, self.ndim), torch.float64, "pos")
+        prop = torch.empty((self.ntemps, nh, self.ndim), dtype=torch.float64, device=self._dev)
+        self._run(lambda: _lib.check(self._propose(self._h, C.byref(self._spec), int(step), int(half), pos.data_ptr(), prop.data_ptr())))
+        return prop
+
+    def accept(self, step: int, half: int, prop, lnl_new, lnprior_new, pos, lnl, lnprior, accepted):
+        import ctypes as C
+        import torch
+        from . import _lib
+        T, nw, nh = self.ntemps, self.nwalkers, self.nwalkers // 2
+        self._checked(prop, (T, nh, self.ndim), torch.float64, "prop")
+        self._checked(lnl_new, (T, nh), torch.float64, "lnl_new")
+        self._checked(lnprior_new, (T, nh), torch.float64, "lnprior_new")
+        self._checked(pos, (T, nw, self.ndim), torch.float64, "pos")
+        self._checked(lnl, (T, nw), torch.float64, "lnl")
+        self._checked(lnprior, (T, nw), torch.float64, "lnprior")
+        self._checked(accepted, (T, nw), torch.int64, "accepted")
+        self._run(lambda: _lib.check(self._accept(self._h, C.byref(self._spec), int(step), int(half), prop.data_ptr(), lnl_new.data_ptr(),
+                                                  lnprior_new.data_ptr(), pos.data_ptr(), lnl.data_ptr(), lnprior.data_ptr(),
+                                                  accepted.data_ptr())))
+
+    def swap(self, step: int, pos, lnl, lnprior, swapped):
+        import ctypes as C
+        import torch
+        from . import _lib
+        T, nw = self.ntemps, self.nwalkers
+        self._checked(pos, (T, nw, self.ndim), torch.float64, "pos")
+        self._checked(lnl, (T, nw), torch.float64, "lnl")
+        self._checked(lnprior, (T, nw), torch.float64, "lnprior")
+        self._checked(swapped, (max(T - 1, 1), nw), torch.int64, "swapped")
+        self._run(lambda: _lib.check(self._swap(self._h, C.byref(self._spec), int(step), pos.data_ptr(), lnl.data_ptr(),
+                                                lnprior.data_ptr(), swapped.data_ptr())))
+
+
+def loglike_split_device(fitter: Fitter, spec, theta, lnl, lnprior):
+    """vag_loglike_split_dev on float64 device tensors and torch's current stream: ln L and ln prior of theta[nb, ndim] into
+    lnl[nb] and lnprior[nb], for a spec made by Fitter.build_spec (use_priors=True for a prior other than 0)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .fitting import loglike_request, on_current_stream
+    from .model import get_context
+    lib = _lib.load()
+    split = _lib.tempered_entry(lib, "vag_loglike_split_dev")
+    h, lock = get_context(fitter.device)
+    dev = torch.device("cuda", fitter.device)
+    nb = int(theta.shape[0])
+    for t, shape, what in ((theta, (nb, spec.ndim), "theta"), (lnl, (nb,), "lnl"), (lnprior, (nb,), "lnprior")):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float64 tensor {shape} on {dev}")
+    request = loglike_request(spec)
+    on_current_stream(lib, h, lock, dev, lambda: _lib.check(split(h, C.byref(request), theta.data_ptr(), nb, spec.ndim, lnl.data_ptr(),
+                                                                   lnprior.data_ptr())))
+
+
+def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, betas, nsteps: int, seed: int = 0,
+                        a: float = 2.0, thin: int = 1, priors=None, chunk: int = 64, progress: Optional[Callable] = None):
+    """run_tempered_philox with everything on the device: the spec is built once, and every `chunk` steps are ONE call
+    (vag_tempered_run_dev) that scans and uploads the spec blocks once and then only launches.  Per half-step the T nw / 2 proposals
+    of all temperatures go through one likelihood call; positions, ln L, ln prior, the chain and the counts stay in HBM.  ln L is the
+    fitter's, ln prior the sum of the priors with the bounds mask (Fitter.log_like_and_prior_batch); only priors that run on the
+    device are accepted.
+
+    Returns (chain[nsteps // thin, T, nw, ndim], lnl[.., T, nw], lnprior[.., T, nw], acceptance[T, nw], swap_fraction[T - 1]) as
+    numpy arrays.  The chunk size does not change a bit of them.  ``progress(step, pos, lnl, lnprior)`` is called once per chunk
+    with the last step of the chunk; the context's lock is free between chunks."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .fitting import loglike_request, on_current_stream
+    from .model import get_context
+    pos0 = np.ascontiguousarray(pos0, dtype=np.float64)
+    if pos0.ndim != 3:
+        raise ValueError("pos0 must be [ntemps, nwalkers, ndim]")
+    betas = _check_betas(betas)
+    ntemps, nw, ndim = pos0.shape
+    if ntemps != betas.size:
+        raise ValueError("pos0 must be [ntemps, nwalkers, ndim] with one ensemble per entry of betas")
+    _check_stretch(nw, ndim, a, thin)
+    if chunk < 1 or nsteps < 0:
+        raise ValueError("chunk must be >= 1 and nsteps >= 0")
+    spec, _, _ = fitter.build_spec(param_defs, priors=priors, use_priors=True)
+    if spec.ndim != ndim:
+        raise ValueError("pos0 must be [ntemps, nwalkers, ndim]")
+    fitter._refuse_host_priors(param_defs, "run_tempered_device")
+    lib = _lib.load()
+    run = _lib.tempered_entry(lib, "vag_tempered_run_dev")
+    h, lock = get_context(fitter.device)
+    dev = torch.device("cuda", fitter.device)
+    request = loglike_request(spec)
+    tempered = _lib.TemperedSpec(int(seed) & (2 ** 64 - 1), float(a), ntemps, nw, ndim, int(thin),
+                                 betas.ctypes.data_as(C.POINTER(C.c_double)))
+    pos = torch.from_numpy(pos0).to(dev)
+    lnl = torch.empty((ntemps, nw), dtype=torch.float64, device=dev)
+    lnprior = torch.empty((ntemps, nw), dtype=torch.float64, device=dev)
+    accepted = torch.zeros((ntemps, nw), dtype=torch.int64, device=dev)
+    swapped = torch.zeros((max(ntemps - 1, 1), nw), dtype=torch.int64, device=dev)
+    rows = nsteps // thin
+    chain = torch.empty((rows, ntemps, nw, ndim), dtype=torch.float64, device=dev)
+    lnl_chain = torch.empty((rows, ntemps, nw), dtype=torch.float64, device=dev)
+    lnprior_chain = torch.empty((rows, ntemps, nw), dtype=torch.float64, device=dev)
+    loglike_split_device(fitter, spec, pos.view(-1, ndim), lnl.view(-1), lnprior.view(-1))
+    if not bool((torch.isfinite(lnl) & torch.isfinite(lnprior)).all()):
+        raise ValueError("initial positions must have finite ln L and ln prior")
+    per_row = ntemps * nw
+    for step0 in range(0, nsteps, chunk):
+        n = min(chunk, nsteps - step0)
+        row = step0 // thin
+        stored = row < rows
+        on_current_stream(lib, h, lock, dev, lambda: _lib.check(run(
+            h, C.byref(request), C.byref(tempered), step0, n, pos.data_ptr(), lnl.data_ptr(), lnprior.data_ptr(), accepted.data_ptr(),
+            swapped.data_ptr(), chain.data_ptr() + 8 * row * per_row * ndim if stored else None,
+            lnl_chain.data_ptr() + 8 * row * per_row if stored else None, lnprior_chain.data_ptr() + 8 * row * per_row if stored else None)))
+        if progress is not None:
+            progress(step0 + n - 1, pos.cpu().numpy(), lnl.cpu().numpy(), lnprior.cpu().numpy())
+    plan = _lib.Plan()
+    with lock:
+        lib.vag_last_plan(h, C.byref(plan))
+    fitter._log_plan_warnings(plan, ntemps * nw // 2)
+    fitter.last_plan = plan
+    attempts = swap_attempts(ntemps, 0, nsteps)
+    swap_fraction = swapped.cpu().numpy()[:ntemps - 1].sum(axis=1) / np.maximum(attempts * nw, 1)
+    return (chain.cpu().numpy(), lnl_chain.cpu().numpy(), lnprior_chain.cpu().numpy(), accepted.cpu().numpy() / max(nsteps, 1),
+            swap_fraction)
+
+
 def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: int, nburn: int = 0, seed: int = 0,
-        loglike_fn: Optional[Callable] = None, center: Optional[np.ndarray] = None, spread: float = 0.1, sampler: str = "host"):
+        loglike_fn: Optional[Callable] = None, center: Optional[np.ndarray] = None, spread: float = 0.1, sampler: str = "host",
+        ntemps: int = 8, beta_min: float = 1e-3, prior_rung: bool = True):
     """Convenience driver: uniform priors over the ParamDef boxes, stretch-move sampling on the device likelihood.
     Returns dict(samples[flat, ndim], log_prob[flat], acceptance, best) in sampler space (log10 for LOG parameters).
     ``sampler="host"``: run_stretch_move in numpy around one device call per half-step; ``"device"``: run_stretch_move_device, the
     whole run on the device (fixed halves and Philox draws keyed by `seed`: another chain than the host sampler's, the same
-    distribution)."""
-    if sampler not in ("host", "device"):
-        raise ValueError(f"unknown sampler {sampler!r}: 'host' or 'device'")
-    if sampler == "device" and loglike_fn is not None:
-        raise ValueError("sampler='device' evaluates the fitter's own likelihood on the device: it cannot be combined with loglike_fn "
-                         "(compose sampling.StretchMove with your evaluator instead)")
+    distribution); ``"tempered"``: run_tempered_device on the ladder geometric_betas(ntemps, beta_min, prior_rung), `nwalkers` per
+    temperature.  The keys above are then filled from the cold chain (beta = 1, log_prob = ln L + ln prior), and the dict also holds
+    "betas", "log_like" (the mean of ln L per rung after the burn-in), "log_evidence" and "log_evidence_error"
+    (thermodynamic_evidence of those means: read its caveats) and "swap_fraction"."""
+    if sampler not in ("host", "device", "tempered"):
+        raise ValueError(f"unknown sampler {sampler!r}: 'host', 'device' or 'tempered'")
+    if sampler != "host" and loglike_fn is not None:
+        raise ValueError(f"sampler={sampler!r} evaluates the fitter's own likelihood on the device: it cannot be combined with "
+                         "loglike_fn (compose sampling.StretchMove or sampling.TemperedMove with your evaluator instead)")
     rng = np.random.default_rng(seed)
+    if sampler == "tempered":
+        betas = geometric_betas(ntemps, beta_min, prior_rung)
+        _, lower, upper = fitter.build_spec(param_defs)
+        pos0 = initial_positions(lower, upper, betas.size * nwalkers, rng, center=center, spread=spread).reshape(betas.size, nwalkers, -1)
+        chain, lnl, lnprior, acc, swap_fraction = run_tempered_device(fitter, param_defs, pos0, betas, nsteps, seed=seed)
+        cold, logp = chain[:, 0], lnl[:, 0] + lnprior[:, 0]
+        flat = cold[nburn:].reshape(-1, cold.shape[-1])
+        flat_lp = logp[nburn:].reshape(-1)
+        log_like = lnl[nburn:].mean(axis=(0, 2)) if lnl[nburn:].size else np.full(betas.size, np.nan)
+        ln_z, ln_z_err = thermodynamic_evidence(betas, log_like)
+        return {"samples": flat, "log_prob": flat_lp, "acceptance": acc[0], "best": flat[np.argmax(flat_lp)], "chain": cold,
+                "betas": betas, "log_like": log_like, "log_evidence": ln_z, "log_evidence_error": ln_z_err,
+                "swap_fraction": swap_fraction}
     _, lower, upper = fitter.build_spec(param_defs)
     if sampler == "device":
         pos0 = initial_positions(lower, upper, nwalkers, rng, center=center, spread=spread)
