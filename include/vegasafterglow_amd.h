@@ -977,6 +977,65 @@ int vag_stretch_accept_dev(vag_ctx* ctx, const vag_stretch_spec* sp, uint64_t st
 int vag_stretch_run_dev(vag_ctx* ctx, const vag_loglike_request* request, const vag_stretch_spec* sp, uint64_t step0, int n_steps,
                         double* d_pos, double* d_lp, int64_t* d_accepted, double* d_chain, double* d_logp);
 
+/* The move mix of the device sampler (added after VAG_ABI_VERSION 13, detect by symbol): the stretch move, the differential-evolution
+ * move (ter Braak 2006, with the scale jitter of Nelson et al. 2013 that emcee 3 uses) and the snooker move (ter Braak & Vrugt 2008),
+ * chosen per step by weight.  The reference's emcee configuration is DE at 0.8 and snooker at 0.2.  The framing is that of
+ * vag_stretch_*: nh = n_walkers / 2, half h is updated against the other half, which does not move during that half-step; the draws
+ * are Philox4x32-10 with the key and the counter (w, step & 0xffffffff, step >> 32, stream) described above.  Streams 0 (proposal),
+ * 1 (acceptance) and 2 (exchange, tempering) keep their meaning; stream 3 is the move choice and stream 4 a second block of proposal
+ * words.  x0..x3 are the words of stream 0 at walker w, v0..v3 those of stream 4, u(hi, lo) the uniform above.
+ * The choice: one per step, shared by both halves.  With u_c = u of the first two words of counter (0, step lo, step hi, 3) and the
+ * weights (w_s, w_de, w_sn) = weights[VAG_MOVE_*] (non-negative, finite, sum > 0; only their ratios matter): t = u_c ((w_s + w_de) +
+ * w_sn); the stretch move if t < w_s, else DE if t < w_s + w_de, else snooker.  The host evaluates this and launches the kernel of
+ * the kind; a kind of weight 0 is never chosen.
+ * The stretch kind: vag_stretch_propose_dev's proposal, bit for bit, and factor = (ndim - 1) log(z).
+ * The DE kind (nh >= 2): walker w draws a != b of the other half, a = (uint64(x2) nh) >> 32, b = (a + 1 + ((uint64(x3) (nh - 1))
+ * >> 32)) mod nh, and a standard normal n = sqrt(-2 log(1 - u(x0, x1))) cos(2 pi u(v0, v1)) (2 pi the double 6.283185307179586),
+ * which is quantised to a multiple of 2^-20, n_q = rint(n 2^20) 2^-20 (this changes gamma by 1e-11 relative: of no statistical
+ * consequence; it makes n_q independent of the last bits of log and cos unless n 2^20 lies within their rounding, about 1e-9, of a
+ * half-integer).  gamma = gamma0 fma(sigma, n_q, 1), gamma0 = 0 standing for 2.38 / sqrt(2 ndim); prop[d] = fma(gamma, pos[a][d] -
+ * pos[b][d], pos[w][d]); factor = 0.
+ * The snooker kind (nh >= 3): walker w draws three distinct walkers z, z1, z2 of the other half: z and z1 as a and b above, z2 =
+ * (uint64(v2) (nh - 2)) >> 32 stepped over the two taken indices in ascending order (+1 if >= the smaller, then +1 if >= the larger).
+ * With delta = pos[w] - pos[z], r2 = delta . delta and proj = delta . (pos[z1] - pos[z2]) (both summed from 0 in ascending d, one fma
+ * per term): c = gamma_snooker (proj / r2), prop[d] = fma(c, delta[d], pos[w][d]), and factor = ((ndim - 1) / 2) log(|prop - pos[z]|^2
+ * / r2), the squared norm summed the same way.  This projects z1 - z2 on the UNIT vector along delta, as the paper does (emcee's
+ * DESnookerMove divides delta by sqrt(|delta|) instead, which is not a unit vector: its step carries a factor |delta|).  A walker with r2 = 0, or
+ * whose factor is not finite, proposes its own position with factor = -inf and is rejected.
+ * The acceptance, for every kind: a proposal whose ln p is not finite is rejected; any other is accepted iff
+ * log(u_a) < factor + (lp_new - lp[w]), u_a = u(y0, y1) of stream 1 exactly as in vag_stretch_accept_dev. */
+#define VAG_MOVE_STRETCH 0
+#define VAG_MOVE_DE 1
+#define VAG_MOVE_SNOOKER 2
+typedef struct vag_move_spec {
+    uint64_t seed;
+    double a;              /* the stretch scale, finite and > 1 (checked whatever the weights) */
+    double gamma0;         /* the DE scale, finite and >= 0; 0: the default 2.38 / sqrt(2 ndim) */
+    double sigma;          /* the relative jitter of the DE scale, finite (1e-5 is customary) */
+    double gamma_snooker;  /* the snooker scale, finite (1.7 is customary) */
+    double weights[3];     /* by VAG_MOVE_*: finite, >= 0, not all zero */
+    int32_t n_walkers;     /* even, >= 2 ndim; >= 4 with weights[VAG_MOVE_DE] > 0, >= 6 with weights[VAG_MOVE_SNOOKER] > 0 */
+    int32_t ndim;          /* 1 .. 16 */
+    int32_t thin;          /* >= 1: step s is stored when (s + 1) % thin == 0 */
+} vag_move_spec;
+
+/* The building blocks, as vag_stretch_propose_dev / vag_stretch_accept_dev with d_factor[n_walkers / 2] between them: propose writes
+ * the ln of the Hastings factor of each proposal, accept reads it.  Stream-ordered on the context's stream, no host synchronisation.
+ * Refused with VAG_E_INVALID (the context stays usable): whatever the stretch entries refuse; a weight that is negative or not
+ * finite, or all three zero; weights[VAG_MOVE_DE] > 0 with n_walkers / 2 < 2; weights[VAG_MOVE_SNOOKER] > 0 with n_walkers / 2 < 3;
+ * gamma0, sigma or gamma_snooker not finite; gamma0 < 0. */
+int vag_move_propose_dev(vag_ctx* ctx, const vag_move_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop,
+                         double* d_factor);
+int vag_move_accept_dev(vag_ctx* ctx, const vag_move_spec* sp, uint64_t step, int half, const double* d_prop, const double* d_factor,
+                        const double* d_lp_new, double* d_pos, double* d_lp, int64_t* d_accepted);
+
+/* vag_stretch_run_dev with the move mix: steps step0 .. step0 + n_steps - 1 on the likelihood of `request`, per step the choice of
+ * the kind, and per half propose, the likelihood call of the n_walkers / 2 proposals, accept.  Buffers, storing, scans, uploads and
+ * refusals as there, with the refusals of the building blocks above.  With weights (1, 0, 0) the chain is vag_stretch_run_dev's
+ * wherever no decision lies within the rounding of its margin. */
+int vag_move_run_dev(vag_ctx* ctx, const vag_loglike_request* request, const vag_move_spec* sp, uint64_t step0, int n_steps,
+                     double* d_pos, double* d_lp, int64_t* d_accepted, double* d_chain, double* d_logp);
+
 /* Parallel tempering around the stretch move (added after VAG_ABI_VERSION 13, detect by symbol).
  * The ladder: n_temps = T temperatures, 1 <= T <= VAG_TEMPER_MAX; the inverse temperatures betas[T] are finite, betas[0] = 1,
  * strictly descending, betas[T - 1] >= 0 (0, the prior, is allowed as the last rung).  Temperature t targets

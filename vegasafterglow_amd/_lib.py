@@ -221,6 +221,23 @@ def stretch_entry(lib, name):
     return getattr(lib, name)
 
 
+class MoveSpec(C.Structure):  # vag_move_spec
+    _fields_ = [("seed", C.c_uint64), ("a", C.c_double), ("gamma0", C.c_double), ("sigma", C.c_double), ("gamma_snooker", C.c_double),
+                ("weights", C.c_double * 3), ("n_walkers", C.c_int32), ("ndim", C.c_int32), ("thin", C.c_int32)]
+
+
+MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER = 0, 1, 2  # VAG_MOVE_*
+MOVE_ENTRIES = ("vag_move_propose_dev", "vag_move_accept_dev", "vag_move_run_dev")
+
+
+def move_entry(lib, name):
+    """One of the move-mix entry points, added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build)."""
+    if not hasattr(lib, name):
+        raise RuntimeError(f"the loaded library has no {name}: the DE and snooker moves (sampling.EnsembleMoves, run_moves_device, "
+                           "fit(sampler='device', moves=...)) need a newer build")
+    return getattr(lib, name)
+
+
 class TemperedSpec(C.Structure):  # vag_tempered_spec; betas points into a host array the caller keeps
     _fields_ = [("seed", C.c_uint64), ("a", C.c_double), ("n_temps", C.c_int32), ("n_walkers", C.c_int32), ("ndim", C.c_int32),
                 ("thin", C.c_int32), ("betas", C.POINTER(C.c_double))]
@@ -293,6 +310,7 @@ EXPORTS = [
     "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev", "vag_loglike_tmpl_batch", "vag_loglike_tmpl_batch_dev",
     "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev", "vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev",
     "vag_loglike_split_dev", "vag_tempered_propose_dev", "vag_tempered_accept_dev", "vag_tempered_swap_dev", "vag_tempered_run_dev",
+    "vag_move_propose_dev", "vag_move_accept_dev", "vag_move_run_dev",
 ]
 
 _lib = None
@@ -394,6 +412,11 @@ def load():
         lib.vag_stretch_propose_dev.argtypes = [v, sp, C.c_uint64, C.c_int, v, v]
         lib.vag_stretch_accept_dev.argtypes = [v, sp, C.c_uint64, C.c_int, v, v, v, v, v]
         lib.vag_stretch_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), sp, C.c_uint64, C.c_int, v, v, v, v, v]
+    if hasattr(lib, "vag_move_run_dev"):  # (detected by symbol: the move mix of the device sampler)
+        mp = C.POINTER(MoveSpec)
+        lib.vag_move_propose_dev.argtypes = [v, mp, C.c_uint64, C.c_int, v, v, v]
+        lib.vag_move_accept_dev.argtypes = [v, mp, C.c_uint64, C.c_int, v, v, v, v, v, v]
+        lib.vag_move_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), mp, C.c_uint64, C.c_int, v, v, v, v, v]
     if hasattr(lib, "vag_tempered_run_dev"):  # (detected by symbol: parallel tempering)
         tp = C.POINTER(TemperedSpec)
         lib.vag_loglike_split_dev.argtypes = [v, C.POINTER(LoglikeRequest), v, C.c_int, C.c_int, v, v]

@@ -32,6 +32,7 @@
 #include "vag_fit_kernels.h"
 #include "vag_sampler.h"
 #include "vag_tempering.h"
+#include "vag_moves.h"
 #include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
 #include "vag_flux_plan.h"    // (host only: the launch decisions of the flux stage)
 
@@ -441,6 +442,7 @@ struct vag_ctx {
     DevBuf d_visblk, d_vispart;  // visibility groups of the likelihood (their data: vis below): their 64-visibility blocks, chi^2 partials
     DevBuf d_stretch_prop, d_stretch_lp;  // the device sampler (vag_stretch_run_dev): a half's proposals [half][ndim] and their ln p [half]
     DevBuf d_temper_prop, d_temper_lnl, d_temper_lnprior;  // parallel tempering (vag_tempered_run_dev): all temperatures' proposals of a half [T][half][ndim], their ln L and ln prior [T][half]
+    DevBuf d_move_factor;  // the move mix (vag_move_run_dev): ln of the Hastings factor of a half's proposals [half]; the proposals and their ln p go through d_stretch_prop / d_stretch_lp
     DevBuf d_polspec, d_polstokes;  // polarization groups of the likelihood (their data: pol below): the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -740,7 +742,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_stretch_prop, &c->d_stretch_lp, &c->d_temper_prop, &c->d_temper_lnl, &c->d_temper_lnprior})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_stretch_prop, &c->d_stretch_lp, &c->d_temper_prop, &c->d_temper_lnl, &c->d_temper_lnprior, &c->d_move_factor})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3974,6 +3976,136 @@ int vag_stretch_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_stre
             if ((rc = loglike_call(c, req, d_prop, half, ndim, d_lp_new))) return rc;
             if ((rc = stretch_accept(c, sp, step, which, d_prop, d_lp_new, d_pos, d_lp, d_accepted,
                                      stored ? d_chain + row * (size_t)nw * ndim : nullptr, stored ? d_logp + row * (size_t)nw : nullptr)))
+                return rc;
+        }
+        if (stored) ++row;
+    }
+    return VAG_OK;
+}
+
+// ---- the move mix: stretch, differential evolution, snooker (kernels and the choice: vag_moves.h; the moves: the public header) ----
+
+static_assert(VAG_MOVE_STRETCH == MOVE_STRETCH && VAG_MOVE_DE == MOVE_DE && VAG_MOVE_SNOOKER == MOVE_SNOOKER, "the public kinds are the header's");
+
+static int move_spec_check(const vag_move_spec* sp) {  // (not null)
+    const vag_stretch_spec one{sp->seed, sp->a, sp->n_walkers, sp->ndim, sp->thin};
+    if (const int rc = stretch_spec_check(&one)) return rc;
+    double sum = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(sp->weights[k]) || sp->weights[k] < 0.0)
+            return set_err(VAG_E_INVALID, "move mix: weight %d must be finite and >= 0, got %g", k, sp->weights[k]);
+        sum += sp->weights[k];
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum)) return set_err(VAG_E_INVALID, "move mix: the weights must have a finite sum > 0");
+    const int half = sp->n_walkers / 2;
+    if (sp->weights[MOVE_DE] > 0.0 && half < 2)
+        return set_err(VAG_E_INVALID, "move mix: the DE move needs two walkers of the other half, n_walkers >= 4, got %d", sp->n_walkers);
+    if (sp->weights[MOVE_SNOOKER] > 0.0 && half < 3)
+        return set_err(VAG_E_INVALID, "move mix: the snooker move needs three walkers of the other half, n_walkers >= 6, got %d", sp->n_walkers);
+    if (!std::isfinite(sp->gamma0) || sp->gamma0 < 0.0)
+        return set_err(VAG_E_INVALID, "move mix: gamma0 must be finite and >= 0 (0: 2.38 / sqrt(2 ndim)), got %g", sp->gamma0);
+    if (!std::isfinite(sp->sigma)) return set_err(VAG_E_INVALID, "move mix: sigma must be finite, got %g", sp->sigma);
+    if (!std::isfinite(sp->gamma_snooker)) return set_err(VAG_E_INVALID, "move mix: gamma_snooker must be finite, got %g", sp->gamma_snooker);
+    return VAG_OK;
+}
+
+// the kind of `step`, chosen on the host: the kernels do not branch on it
+static int move_kind(const vag_move_spec* sp, uint64_t step) {
+    const double u = move_choice_uniform((uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), (unsigned long long)step);
+    return move_choice(u, sp->weights[MOVE_STRETCH], sp->weights[MOVE_DE], sp->weights[MOVE_SNOOKER]);
+}
+
+static int move_propose(vag_ctx* c, const vag_move_spec* sp, uint64_t step, int which, const double* d_pos, double* d_prop,
+                        double* d_factor) {
+    const int half = sp->n_walkers / 2;
+    const dim3 groups((half + STRETCH_LANES - 1) / STRETCH_LANES), lanes(STRETCH_LANES);
+    const uint32_t seed_lo = (uint32_t)(sp->seed & 0xffffffffu), seed_hi = (uint32_t)(sp->seed >> 32);
+    switch (move_kind(sp, step)) {
+        case MOVE_STRETCH:
+            hipLaunchKernelGGL(vag_move_stretch_propose_kernel, groups, lanes, 0, c->stream, seed_lo, seed_hi, sp->a,
+                               (unsigned long long)step, which, half, sp->ndim, d_pos, d_prop, d_factor);
+            break;
+        case MOVE_DE:
+            hipLaunchKernelGGL(vag_de_propose_kernel, groups, lanes, 0, c->stream, seed_lo, seed_hi,
+                               sp->gamma0 > 0.0 ? sp->gamma0 : de_gamma0(sp->ndim), sp->sigma, (unsigned long long)step, which, half,
+                               sp->ndim, d_pos, d_prop, d_factor);
+            break;
+        default:
+            hipLaunchKernelGGL(vag_snooker_propose_kernel, groups, lanes, 0, c->stream, seed_lo, seed_hi, sp->gamma_snooker,
+                               (unsigned long long)step, which, half, sp->ndim, d_pos, d_prop, d_factor);
+    }
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+static int move_accept(vag_ctx* c, const vag_move_spec* sp, uint64_t step, int which, const double* d_prop, const double* d_factor,
+                       const double* d_lp_new, double* d_pos, double* d_lp, int64_t* d_accepted, double* d_chain_row, double* d_logp_row) {
+    const int half = sp->n_walkers / 2;
+    hipLaunchKernelGGL(vag_move_accept_kernel, dim3((half + STRETCH_LANES - 1) / STRETCH_LANES), dim3(STRETCH_LANES), 0, c->stream,
+                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), (unsigned long long)step, which, half, sp->ndim,
+                       d_prop, d_factor, d_lp_new, d_pos, d_lp, reinterpret_cast<long long*>(d_accepted), d_chain_row, d_logp_row);
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+int vag_move_propose_dev(vag_ctx* c, const vag_move_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop,
+                         double* d_factor) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !sp || !d_pos || !d_prop || !d_factor) return set_err(VAG_E_INVALID, "null context, move spec or buffer");
+    if (const int rc = move_spec_check(sp)) return rc;
+    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "move mix: half must be 0 or 1, got %d", half);
+    HIPCHK(hipSetDevice(c->device));
+    return move_propose(c, sp, step, half, d_pos, d_prop, d_factor);
+}
+
+int vag_move_accept_dev(vag_ctx* c, const vag_move_spec* sp, uint64_t step, int half, const double* d_prop, const double* d_factor,
+                        const double* d_lp_new, double* d_pos, double* d_lp, int64_t* d_accepted) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !sp || !d_prop || !d_factor || !d_lp_new || !d_pos || !d_lp || !d_accepted)
+        return set_err(VAG_E_INVALID, "null context, move spec or buffer");
+    if (const int rc = move_spec_check(sp)) return rc;
+    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "move mix: half must be 0 or 1, got %d", half);
+    HIPCHK(hipSetDevice(c->device));
+    return move_accept(c, sp, step, half, d_prop, d_factor, d_lp_new, d_pos, d_lp, d_accepted, nullptr, nullptr);
+}
+
+int vag_move_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_move_spec* sp, uint64_t step0, int n_steps, double* d_pos,
+                     double* d_lp, int64_t* d_accepted, double* d_chain, double* d_logp) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !q || !q->spec || !sp || !d_pos || !d_lp || !d_accepted)
+        return set_err(VAG_E_INVALID, "null context, request, fit spec, move spec or buffer");
+    if ((d_chain == nullptr) != (d_logp == nullptr)) return set_err(VAG_E_INVALID, "move mix: the chain and its ln p are stored together or not at all");
+    if (const int rc = move_spec_check(sp)) return rc;
+    if (sp->ndim != q->spec->ndim)
+        return set_err(VAG_E_INVALID, "move mix: ndim %d is not the fit spec's %d", sp->ndim, q->spec->ndim);
+    if (n_steps < 0) return set_err(VAG_E_INVALID, "move mix: n_steps must be >= 0, got %d", n_steps);
+    if (n_steps == 0) return VAG_OK;
+    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
+    int rc = fit_request_prepare(req);  // the scans, once per call of many steps
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const int ndim = sp->ndim, nw = sp->n_walkers, half = nw / 2;
+    req.ndim = ndim;
+    rc = upload_blocks(c, req);  // and the uploads
+    if (rc) return rc;
+    if (c->d_stretch_prop.ensure(sizeof(double) * (size_t)half * ndim)) return VAG_E_HIP;
+    if (c->d_stretch_lp.ensure(sizeof(double) * (size_t)half)) return VAG_E_HIP;
+    if (c->d_move_factor.ensure(sizeof(double) * (size_t)half)) return VAG_E_HIP;
+    double* d_prop = c->d_stretch_prop.as<double>();
+    double* d_lp_new = c->d_stretch_lp.as<double>();
+    double* d_factor = c->d_move_factor.as<double>();
+    size_t row = 0;  // stored rows so far
+    for (int k = 0; k < n_steps; ++k) {
+        const uint64_t step = step0 + (uint64_t)k;
+        const bool stored = d_chain && (step + 1) % (uint64_t)sp->thin == 0;
+        for (int which = 0; which < 2; ++which) {
+            if ((rc = move_propose(c, sp, step, which, d_pos, d_prop, d_factor))) return rc;
+            if ((rc = loglike_call(c, req, d_prop, half, ndim, d_lp_new))) return rc;
+            if ((rc = move_accept(c, sp, step, which, d_prop, d_factor, d_lp_new, d_pos, d_lp, d_accepted,
+                                  stored ? d_chain + row * (size_t)nw * ndim : nullptr, stored ? d_logp + row * (size_t)nw : nullptr)))
                 return rc;
         }
         if (stored) ++row;

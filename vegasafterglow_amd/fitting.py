@@ -1807,7 +1807,8 @@ class Fitter:
     # fitter.py:545-674 (the emcee branch; the stretch-move sampler of vegasafterglow_amd.sampling needs no third-party package)
     def fit(self, param_defs, nwalkers=None, nsteps=1000, nburn=0, seed=0, sampler="host", **kw):
         """sampling.fit on this fitter.  ``sampler="host"``: the numpy stretch move around one device call per half-step;
-        ``sampler="device"``: the whole run on the device (sampling.run_stretch_move_device); ``sampler="tempered"``: parallel
+        ``sampler="device"``: the whole run on the device (sampling.run_stretch_move_device, or with ``moves="reference"`` or a
+        sequence of (name, weight) sampling.run_moves_device: the DE and snooker moves of the reference); ``sampler="tempered"``: parallel
         tempering on the device (sampling.run_tempered_device; ``ntemps``, ``beta_min``, ``prior_rung`` shape the ladder, `nwalkers`
         is per temperature), which also returns the evidence by thermodynamic integration."""
         from . import sampling

@@ -11,6 +11,9 @@ walkers over a thread pool (VegasAfterglow/fitting/samplers.py:59-106).  Here th
 * ``run_stretch_move_device`` / ``StretchMove`` -- the stretch move itself on the device (fixed halves, Philox draws keyed by
   (seed, step, walker)): a run of steps is launches only, positions, ln p and the chain stay in HBM.  ``run_stretch_move_philox``,
   ``stretch_proposals`` and ``stretch_accepts`` state the same move in numpy, to the bit;
+* ``run_moves_device`` / ``EnsembleMoves`` -- the same sampler with the reference's proposals: the differential-evolution move and
+  the snooker move (``REFERENCE_MOVES``: DE at 0.8, snooker at 0.2), one kind per step chosen by weight, the stretch move among
+  them.  ``run_moves_philox``, ``move_kind``, ``de_proposals``, ``snooker_proposals`` and ``move_accepts`` state them in numpy;
 * ``run_tempered_device`` / ``TemperedMove`` -- parallel tempering around that move on the device: a ladder of inverse temperatures
   (``geometric_betas``), all temperatures' proposals in one likelihood call per half-step, exchanges between neighbours, and the
   evidence by thermodynamic integration (``thermodynamic_evidence``).  ``run_tempered_philox``, ``tempered_proposals``,
@@ -315,16 +318,9 @@ class StretchMove:
                                                   pos.data_ptr(), lp.data_ptr(), accepted.data_ptr())))
 
 
-def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, nsteps: int, seed: int = 0,
-                            a: float = 2.0, thin: int = 1, priors=None, chunk: int = 64, progress: Optional[Callable] = None):
-    """The stretch move of run_stretch_move_philox with everything on the device: the spec is built once, and every `chunk` steps are
-    ONE call (vag_stretch_run_dev) that scans and uploads the spec blocks once and then only launches -- positions, ln p, the chain
-    and the acceptance counts stay in HBM, nothing is copied and the stream is not synchronised between steps.  ln p is
-    ln L + sum ln prior with the bounds mask (Fitter.log_prob_batch); only priors that run on the device are accepted.
-
-    Returns (chain[nsteps // thin, nw, ndim], log_prob[nsteps // thin, nw], acceptance[nw]) as numpy arrays.  The chunk size does
-    not change a bit of them.  ``progress(step, pos, lp)`` is called once per chunk with the last step of the chunk; the context's
-    lock is free between chunks."""
+def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, who, entry, make_move):
+    """The body of run_stretch_move_device and run_moves_device: `entry` is the run entry's name and make_move(nw, ndim) the
+    struct it takes behind the request (after the Python-side checks, which make_move performs)."""
     import ctypes as C
     import torch
     from . import _lib
@@ -334,19 +330,18 @@ def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0
     if pos0.ndim != 2:
         raise ValueError("pos0 must be [nwalkers, ndim]")
     nw, ndim = pos0.shape
-    _check_stretch(nw, ndim, a, thin)
+    move = make_move(nw, ndim)
     if chunk < 1 or nsteps < 0:
         raise ValueError("chunk must be >= 1 and nsteps >= 0")
     spec, _, _ = fitter.build_spec(param_defs, priors=priors, use_priors=True)
     if spec.ndim != ndim:
         raise ValueError("pos0 must be [nwalkers, ndim]")
-    fitter._refuse_host_priors(param_defs, "run_stretch_move_device")
+    fitter._refuse_host_priors(param_defs, who)
     lib = _lib.load()
-    run = _lib.stretch_entry(lib, "vag_stretch_run_dev")
+    run = (_lib.stretch_entry if entry == "vag_stretch_run_dev" else _lib.move_entry)(lib, entry)
     h, lock = get_context(fitter.device)
     dev = torch.device("cuda", fitter.device)
     request = loglike_request(spec)
-    stretch = _lib.StretchSpec(int(seed) & (2 ** 64 - 1), float(a), nw, ndim, int(thin))
     pos = torch.from_numpy(pos0).to(dev)
     lp = torch.empty((nw,), dtype=torch.float64, device=dev)
     accepted = torch.zeros((nw,), dtype=torch.int64, device=dev)
@@ -367,7 +362,7 @@ def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0
         row = step0 // thin
         stored = row < rows
         on_current_stream(lib, h, lock, dev, lambda: _lib.check(run(
-            h, C.byref(request), C.byref(stretch), step0, n, pos.data_ptr(), lp.data_ptr(), accepted.data_ptr(),
+            h, C.byref(request), C.byref(move), step0, n, pos.data_ptr(), lp.data_ptr(), accepted.data_ptr(),
             chain.data_ptr() + 8 * row * nw * ndim if stored else None, logp.data_ptr() + 8 * row * nw if stored else None)))
         if progress is not None:
             progress(step0 + n - 1, pos.cpu().numpy(), lp.cpu().numpy())
@@ -377,6 +372,329 @@ def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0
     fitter._log_plan_warnings(plan, nw // 2)
     fitter.last_plan = plan
     return chain.cpu().numpy(), logp.cpu().numpy(), accepted.cpu().numpy() / max(nsteps, 1)
+
+
+def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, nsteps: int, seed: int = 0,
+                            a: float = 2.0, thin: int = 1, priors=None, chunk: int = 64, progress: Optional[Callable] = None):
+    """The stretch move of run_stretch_move_philox with everything on the device: the spec is built once, and every `chunk` steps are
+    ONE call (vag_stretch_run_dev) that scans and uploads the spec blocks once and then only launches -- positions, ln p, the chain
+    and the acceptance counts stay in HBM, nothing is copied and the stream is not synchronised between steps.  ln p is
+    ln L + sum ln prior with the bounds mask (Fitter.log_prob_batch); only priors that run on the device are accepted.
+
+    Returns (chain[nsteps // thin, nw, ndim], log_prob[nsteps // thin, nw], acceptance[nw]) as numpy arrays.  The chunk size does
+    not change a bit of them.  ``progress(step, pos, lp)`` is called once per chunk with the last step of the chunk; the context's
+    lock is free between chunks."""
+    def make_move(nw, ndim):
+        from . import _lib
+        _check_stretch(nw, ndim, a, thin)
+        return _lib.StretchSpec(int(seed) & (2 ** 64 - 1), float(a), nw, ndim, int(thin))
+    return _run_halves_device(fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, "run_stretch_move_device",
+                              "vag_stretch_run_dev", make_move)
+
+
+# ---- the move mix (INTEGRATION.md "The move mix"): the stretch move, the differential-evolution move and the snooker move, one kind
+#      per step chosen by weight.  The reference fits with DE at 0.8 and snooker at 0.2.  The numpy statement first, then the device. ----
+
+MOVE_KINDS = ("stretch", "de", "snooker")  # VAG_MOVE_*
+REFERENCE_MOVES = (("de", 0.8), ("snooker", 0.2))  # the reference's emcee configuration (config.py:160-161)
+DE_SIGMA, SNOOKER_GAMMA = 1e-5, 1.7
+_TWO_PI = 6.283185307179586  # vag::MOVE_TWO_PI
+
+
+def move_weights(moves) -> np.ndarray:
+    """(w_stretch, w_de, w_snooker) of ``moves``: "reference" (REFERENCE_MOVES) or a sequence of (name, weight) with names from
+    MOVE_KINDS, each at most once.  The weights are non-negative and finite with a sum > 0; only their ratios matter."""
+    if isinstance(moves, str):
+        if moves != "reference":
+            raise ValueError(f"unknown move mix {moves!r}: 'reference' or a sequence of (name, weight)")
+        moves = REFERENCE_MOVES
+    weights = np.zeros(3)
+    seen = set()
+    try:
+        pairs = [(name, float(weight)) for name, weight in moves]
+    except (TypeError, ValueError):
+        raise ValueError("moves must be 'reference' or a sequence of (name, weight)") from None
+    for name, weight in pairs:
+        if name not in MOVE_KINDS:
+            raise ValueError(f"unknown move {name!r}: one of {MOVE_KINDS}")
+        if name in seen:
+            raise ValueError(f"move {name!r} is listed twice")
+        seen.add(name)
+        weights[MOVE_KINDS.index(name)] = weight
+    if not np.all(np.isfinite(weights)) or np.any(weights < 0.0):
+        raise ValueError("move weights must be finite and >= 0")
+    if not weights.sum() > 0.0:
+        raise ValueError("move weights must not all be zero")
+    return weights
+
+
+def de_gamma0(ndim: int) -> float:
+    """vag::de_gamma0: 2.38 / sqrt(2 ndim), the customary scale of the DE move."""
+    return float(2.38 / np.sqrt(2.0 * ndim))
+
+
+def _check_moves(weights, nwalkers, ndim, a=2.0, gamma0=None, sigma=DE_SIGMA, gamma_snooker=SNOOKER_GAMMA, thin=1):
+    """The refusals of vag_move_spec on the Python side; returns gamma0 with None resolved."""
+    _check_stretch(nwalkers, ndim, a, thin)
+    if weights[1] > 0.0 and nwalkers // 2 < 2:
+        raise ValueError("the DE move needs two walkers of the other half: at least 4 walkers")
+    if weights[2] > 0.0 and nwalkers // 2 < 3:
+        raise ValueError("the snooker move needs three walkers of the other half: at least 6 walkers")
+    gamma0 = de_gamma0(ndim) if gamma0 is None else float(gamma0)
+    if not (np.isfinite(gamma0) and gamma0 > 0.0):
+        raise ValueError("gamma0 must be finite and > 0 (None: 2.38 / sqrt(2 ndim))")
+    if not (np.isfinite(sigma) and np.isfinite(gamma_snooker)):
+        raise ValueError("sigma and gamma_snooker must be finite")
+    return gamma0
+
+
+def move_kind(step, seed, weights) -> int:
+    """vag::move_choice at absolute step `step`: 0 stretch, 1 DE, 2 snooker (the index into MOVE_KINDS).  One choice per step, shared
+    by both halves: u of the first two words of counter (0, step lo, step hi, 3), times the sum of the weights, against the
+    cumulative weights.  A kind of weight 0 is never chosen."""
+    step, seed = int(step), int(seed)
+    w0, w1, w2 = (float(w) for w in weights)
+    x = philox4x32([0, step & 0xFFFFFFFF, (step >> 32) & 0xFFFFFFFF, 3], [seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF])
+    c1 = w0 + w1
+    t = float(_u53(x[0], x[1])) * (c1 + w2)
+    if t < w0:
+        return 0
+    if t < c1:
+        return 1
+    return 2 if w2 > 0.0 else (1 if w1 > 0.0 else 0)
+
+
+def _scaled_index(x, n):
+    """vag::stretch_partner: (uint64(x) n) >> 32."""
+    return ((x.astype(np.uint64) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+
+
+def _move_pair(xa, xb, nh):
+    """vag::move_pair: two distinct indices within a half of nh >= 2."""
+    a = _scaled_index(xa, nh)
+    return a, (a + 1 + _scaled_index(xb, nh - 1)) % nh
+
+
+def _move_triple(xa, xb, xc, nh):
+    """vag::move_triple: three distinct indices within a half of nh >= 3, the third stepped over the first two in ascending order."""
+    a, b = _move_pair(xa, xb, nh)
+    c = _scaled_index(xc, nh - 2)
+    c = c + (c >= np.minimum(a, b))
+    c = c + (c >= np.maximum(a, b))
+    return a, b, c
+
+
+def de_normal(u1, u2):
+    """vag::de_quantise(vag::de_normal(u1, u2)) and its slack: the Box-Muller normal sqrt(-2 log(1 - u1)) cos(2 pi u2) rounded to a
+    multiple of 2^-20, and the distance of n 2^20 from the nearest half-integer, in quanta.  The quantised value is the same on every
+    machine whose log and cos round n 2^20 (below 2^24) to the same side of that half-integer: where the slack is far above their
+    rounding (about 1e-9)."""
+    u1, u2 = np.asarray(u1, dtype=np.float64), np.asarray(u2, dtype=np.float64)
+    scaled = (np.sqrt(-2.0 * np.log(1.0 - u1)) * np.cos(_TWO_PI * u2)) * 2.0 ** 20
+    return np.rint(scaled) * 2.0 ** -20, np.abs((scaled - np.floor(scaled)) - 0.5)
+
+
+def de_proposals(pos, step, half, seed, gamma0=None, sigma=DE_SIGMA):
+    """The DE proposals of half `half` at absolute step `step`: (prop[nw / 2, ndim], factor[nw / 2] = 0, partners[nw / 2, 2],
+    slack[nw / 2]).  Walker w draws a != b of the other half (partners: their indices in the whole ensemble) from words 2 and 3 of
+    stream 0 and a quantised normal n_q (de_normal: u1 from words 0, 1 of stream 0, u2 from words 0, 1 of stream 4);
+    gamma = gamma0 fma(sigma, n_q, 1) and prop = fma(gamma, pos[a] - pos[b], pos[w]).  Bit for bit what vag_move_propose_dev computes
+    on a DE step wherever the slack is far above the rounding of log and cos."""
+    from .fitting import _fma
+    pos = np.asarray(pos, dtype=np.float64)
+    nw, ndim = pos.shape
+    nh = nw // 2
+    gamma0 = de_gamma0(ndim) if gamma0 is None else float(gamma0)
+    x, v = _stretch_words(nw, step, half, seed, 0), _stretch_words(nw, step, half, seed, 4)
+    a, b = _move_pair(x[:, 2], x[:, 3], nh)
+    a, b = (1 - half) * nh + a, (1 - half) * nh + b
+    n_q, slack = de_normal(_u53(x[:, 0], x[:, 1]), _u53(v[:, 0], v[:, 1]))
+    gamma = gamma0 * _fma(sigma, n_q, 1.0)
+    prop = _fma(gamma[:, None], pos[a] - pos[b], pos[half * nh:(half + 1) * nh])
+    return prop, np.zeros(nh), np.stack([a, b], axis=1), slack
+
+
+def snooker_proposals(pos, step, half, seed, gamma_snooker=SNOOKER_GAMMA):
+    """The snooker proposals of half `half` at absolute step `step`: (prop[nw / 2, ndim], factor[nw / 2], partners[nw / 2, 3]).
+    Walker w draws distinct z, z1, z2 of the other half (words 2, 3 of stream 0, word 2 of stream 4).  With delta = pos[w] - pos[z],
+    r2 = delta . delta and proj = delta . (pos[z1] - pos[z2]), summed in dimension order with one fma per term,
+    prop = fma(gamma_snooker (proj / r2), delta, pos[w]) -- the projection on the unit vector of ter Braak & Vrugt (2008), not
+    emcee's delta / sqrt(|delta|) -- and factor = (ndim - 1) / 2 log(|prop - pos[z]|^2 / r2), the ln of the Hastings factor.  A walker
+    with r2 = 0 or a factor that is not finite proposes its own position with factor -inf.  The proposals are bit for bit what
+    vag_move_propose_dev computes on a snooker step; the factor differs by the rounding of the logarithm."""
+    from .fitting import _fma
+    pos = np.asarray(pos, dtype=np.float64)
+    nw, ndim = pos.shape
+    nh = nw // 2
+    x, v = _stretch_words(nw, step, half, seed, 0), _stretch_words(nw, step, half, seed, 4)
+    partners = (1 - half) * nh + np.stack(_move_triple(x[:, 2], x[:, 3], v[:, 2], nh), axis=1)
+    mine = pos[half * nh:(half + 1) * nh]
+    pz, p1, p2 = pos[partners[:, 0]], pos[partners[:, 1]], pos[partners[:, 2]]
+    delta = mine - pz
+    r2, proj = np.zeros(nh), np.zeros(nh)
+    for d in range(ndim):
+        r2 = _fma(delta[:, d], delta[:, d], r2)
+        proj = _fma(delta[:, d], p1[:, d] - p2[:, d], proj)
+    with np.errstate(all="ignore"):
+        coef = gamma_snooker * (proj / r2)
+        q = _fma(coef[:, None], delta, mine)
+        e = q - pz
+        q2 = np.zeros(nh)
+        for d in range(ndim):
+            q2 = _fma(e[:, d], e[:, d], q2)
+        f = (0.5 * (ndim - 1.0)) * np.log(q2 / r2)
+    ok = (r2 > 0.0) & np.isfinite(f)
+    return np.where(ok[:, None], q, mine), np.where(ok, f, -np.inf), partners
+
+
+def move_accepts(step, half, seed, factor, lp_new, lp_old):
+    """The decisions of half `half` at step `step` for proposals of any kind: (take[nw / 2], margin[nw / 2]).  A proposal whose ln p
+    is not finite, or whose factor is -inf, is rejected (margin -inf); any other is taken iff
+    log(u_a) < factor + (lp_new - lp_old), u_a from stream 1 as in stretch_accepts, and margin is that right side minus the left."""
+    factor, lp_new, lp_old = (np.asarray(v, dtype=np.float64) for v in (factor, lp_new, lp_old))
+    y = _stretch_words(2 * factor.size, step, half, seed, 1)
+    finite = np.isfinite(lp_new) & (factor > -np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        margin = (factor + (lp_new - lp_old)) - np.log(_u53(y[:, 0], y[:, 1]))  # (u_a = 0: log = -inf, taken)
+    margin = np.where(finite, margin, -np.inf)
+    return finite & (margin > 0), margin
+
+
+def move_proposals(pos, step, half, seed, weights, a=2.0, gamma0=None, sigma=DE_SIGMA, gamma_snooker=SNOOKER_GAMMA):
+    """The proposals of the kind chosen at `step` (move_kind): (prop, factor, kind, slack), slack None unless the kind is DE.  The
+    stretch kind is stretch_proposals with factor = (ndim - 1) log z."""
+    kind = move_kind(step, seed, weights)
+    if kind == 0:
+        prop, z, _ = stretch_proposals(pos, step, half, seed, a)
+        return prop, (np.shape(pos)[1] - 1.0) * np.log(z), kind, None
+    if kind == 1:
+        prop, factor, _, slack = de_proposals(pos, step, half, seed, gamma0, sigma)
+        return prop, factor, kind, slack
+    prop, factor, _ = snooker_proposals(pos, step, half, seed, gamma_snooker)
+    return prop, factor, kind, None
+
+
+def run_moves_philox(log_prob_batch: Callable[[np.ndarray], np.ndarray], pos0: np.ndarray, nsteps: int, moves=REFERENCE_MOVES,
+                     seed: int = 0, a: float = 2.0, gamma0: Optional[float] = None, sigma: float = DE_SIGMA,
+                     gamma_snooker: float = SNOOKER_GAMMA, thin: int = 1, step0: int = 0, margins: Optional[list] = None,
+                     slacks: Optional[list] = None):
+    """run_stretch_move_philox with the move mix ``moves`` (move_weights): the chain of vag_move_run_dev through any host callable.
+    Per step one kind (move_kind), per half its proposals (move_proposals) in one call of log_prob_batch and the decisions
+    (move_accepts).  With only the stretch move the chain is run_stretch_move_philox's.
+
+    Returns (chain[rows, nw, ndim], log_prob[rows, nw], acceptance[nw]).  ``margins`` receives every half-step's margin array,
+    ``slacks`` every DE half-step's slack array (de_normal)."""
+    weights = move_weights(moves)
+    pos = np.array(pos0, dtype=np.float64, copy=True)
+    nw, ndim = pos.shape
+    gamma0 = _check_moves(weights, nw, ndim, a, gamma0, sigma, gamma_snooker, thin)
+    lp = np.asarray(log_prob_batch(pos), dtype=np.float64).copy()
+    if not np.all(np.isfinite(lp)):
+        raise ValueError("initial positions must have finite log-probability")
+    rows = (step0 + nsteps) // thin - step0 // thin
+    chain, logp = np.empty((rows, nw, ndim)), np.empty((rows, nw))
+    accepted = np.zeros(nw, dtype=np.int64)
+    nh, row = nw // 2, 0
+    for step in range(step0, step0 + nsteps):
+        for half in (0, 1):
+            s = slice(half * nh, (half + 1) * nh)
+            prop, factor, _, slack = move_proposals(pos, step, half, seed, weights, a, gamma0, sigma, gamma_snooker)
+            lp_new = np.asarray(log_prob_batch(prop), dtype=np.float64)
+            take, margin = move_accepts(step, half, seed, factor, lp_new, lp[s])
+            if margins is not None:
+                margins.append(margin)
+            if slacks is not None and slack is not None:
+                slacks.append(slack)
+            pos[s][take] = prop[take]
+            lp[s][take] = lp_new[take]
+            accepted[s][take] += 1
+        if (step + 1) % thin == 0:
+            chain[row], logp[row] = pos, lp
+            row += 1
+    return chain, logp, accepted / max(nsteps, 1)
+
+
+def _move_spec(weights, nwalkers, ndim, seed, a, gamma0, sigma, gamma_snooker, thin):
+    from . import _lib
+    return _lib.MoveSpec(int(seed) & (2 ** 64 - 1), float(a), float(gamma0), float(sigma), float(gamma_snooker),
+                         (_lib.C.c_double * 3)(*weights), int(nwalkers), int(ndim), int(thin))
+
+
+class EnsembleMoves:
+    """StretchMove for the move mix (vag_move_propose_dev / vag_move_accept_dev): the two halves of a half-step on float64 torch
+    tensors and torch's current stream, with the ln of the Hastings factor between them; they need no model::
+
+        move = EnsembleMoves(nw, ndim, moves=REFERENCE_MOVES, seed=7)
+        for step in range(nsteps):
+            for half in (0, 1):
+                prop, factor = move.propose(step, half, pos)          # [nw / 2, ndim], [nw / 2]
+                move.accept(step, half, prop, factor, evaluate(prop), pos, lp, accepted)   # pos, lp, accepted change in place
+
+    ``move.kind(step)`` is the index into MOVE_KINDS of the move of that step.  The chain is the one run_moves_philox makes from the
+    same ln p."""
+
+    def __init__(self, nwalkers: int, ndim: int, moves=REFERENCE_MOVES, seed: int = 0, a: float = 2.0, gamma0: Optional[float] = None,
+                 sigma: float = DE_SIGMA, gamma_snooker: float = SNOOKER_GAMMA, device: int = 0):
+        self.weights = move_weights(moves)
+        gamma0 = _check_moves(self.weights, nwalkers, ndim, a, gamma0, sigma, gamma_snooker)
+        import torch
+        from . import _lib
+        from .model import get_context
+        self.nwalkers, self.ndim, self.seed = int(nwalkers), int(ndim), int(seed)
+        self._lib = _lib.load()
+        self._propose = _lib.move_entry(self._lib, "vag_move_propose_dev")
+        self._accept = _lib.move_entry(self._lib, "vag_move_accept_dev")
+        self._spec = _move_spec(self.weights, nwalkers, ndim, seed, a, gamma0, sigma, gamma_snooker, 1)
+        self._h, self._lock = get_context(device)
+        self._dev = torch.device("cuda", device)
+
+    _run = StretchMove._run
+    _checked = StretchMove._checked
+
+    def kind(self, step: int) -> int:
+        return move_kind(step, self.seed, self.weights)
+
+    def propose(self, step: int, half: int, pos):
+        import ctypes as C
+        import torch
+        from . import _lib
+        nh = self.nwalkers // 2
+        self._checked(pos, (self.nwalkers, self.ndim), torch.float64, "pos")
+        prop = torch.empty((nh, self.ndim), dtype=torch.float64, device=self._dev)
+        factor = torch.empty((nh,), dtype=torch.float64, device=self._dev)
+        self._run(lambda: _lib.check(self._propose(self._h, C.byref(self._spec), int(step), int(half), pos.data_ptr(), prop.data_ptr(),
+                                                   factor.data_ptr())))
+        return prop, factor
+
+    def accept(self, step: int, half: int, prop, factor, lp_new, pos, lp, accepted):
+        import ctypes as C
+        import torch
+        from . import _lib
+        nh = self.nwalkers // 2
+        self._checked(prop, (nh, self.ndim), torch.float64, "prop")
+        self._checked(factor, (nh,), torch.float64, "factor")
+        self._checked(lp_new, (nh,), torch.float64, "lp_new")
+        self._checked(pos, (self.nwalkers, self.ndim), torch.float64, "pos")
+        self._checked(lp, (self.nwalkers,), torch.float64, "lp")
+        self._checked(accepted, (self.nwalkers,), torch.int64, "accepted")
+        self._run(lambda: _lib.check(self._accept(self._h, C.byref(self._spec), int(step), int(half), prop.data_ptr(), factor.data_ptr(),
+                                                  lp_new.data_ptr(), pos.data_ptr(), lp.data_ptr(), accepted.data_ptr())))
+
+
+def run_moves_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, nsteps: int, moves=REFERENCE_MOVES,
+                     seed: int = 0, a: float = 2.0, gamma0: Optional[float] = None, sigma: float = DE_SIGMA,
+                     gamma_snooker: float = SNOOKER_GAMMA, thin: int = 1, priors=None, chunk: int = 64,
+                     progress: Optional[Callable] = None):
+    """run_stretch_move_device with the move mix ``moves`` (move_weights; the default is the reference's DE 0.8 / snooker 0.2): every
+    `chunk` steps are ONE call of vag_move_run_dev, which chooses each step's kind on the host and launches its kernels around the
+    likelihood call.  Returns, chunking, thinning and ``progress`` as there; the chain is run_moves_philox's from the same ln p."""
+    weights = move_weights(moves)
+
+    def make_move(nw, ndim):
+        g0 = _check_moves(weights, nw, ndim, a, gamma0, sigma, gamma_snooker, thin)
+        return _move_spec(weights, nw, ndim, seed, a, g0, sigma, gamma_snooker, thin)
+    return _run_halves_device(fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, "run_moves_device", "vag_move_run_dev",
+                              make_move)
 
 
 # ---- parallel tempering around that move (INTEGRATION.md "Parallel tempering"): a ladder of T inverse temperatures, temperature t
@@ -735,12 +1053,13 @@ def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np
 
 def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: int, nburn: int = 0, seed: int = 0,
         loglike_fn: Optional[Callable] = None, center: Optional[np.ndarray] = None, spread: float = 0.1, sampler: str = "host",
-        ntemps: int = 8, beta_min: float = 1e-3, prior_rung: bool = True):
+        ntemps: int = 8, beta_min: float = 1e-3, prior_rung: bool = True, moves=None):
     """Convenience driver: uniform priors over the ParamDef boxes, stretch-move sampling on the device likelihood.
     Returns dict(samples[flat, ndim], log_prob[flat], acceptance, best) in sampler space (log10 for LOG parameters).
     ``sampler="host"``: run_stretch_move in numpy around one device call per half-step; ``"device"``: run_stretch_move_device, the
     whole run on the device (fixed halves and Philox draws keyed by `seed`: another chain than the host sampler's, the same
-    distribution); ``"tempered"``: run_tempered_device on the ladder geometric_betas(ntemps, beta_min, prior_rung), `nwalkers` per
+    distribution) -- with ``moves=None`` the stretch move, with ``moves="reference"`` (REFERENCE_MOVES: the DE move at 0.8 and the
+    snooker move at 0.2, the reference's own mix) or a sequence of (name, weight) over MOVE_KINDS run_moves_device; ``"tempered"``: run_tempered_device on the ladder geometric_betas(ntemps, beta_min, prior_rung), `nwalkers` per
     temperature.  The keys above are then filled from the cold chain (beta = 1, log_prob = ln L + ln prior), and the dict also holds
     "betas", "log_like" (the mean of ln L per rung after the burn-in), "log_evidence" and "log_evidence_error"
     (thermodynamic_evidence of those means: read its caveats) and "swap_fraction"."""
@@ -749,6 +1068,11 @@ def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: i
     if sampler != "host" and loglike_fn is not None:
         raise ValueError(f"sampler={sampler!r} evaluates the fitter's own likelihood on the device: it cannot be combined with "
                          "loglike_fn (compose sampling.StretchMove or sampling.TemperedMove with your evaluator instead)")
+    if moves is not None and sampler != "device":
+        raise ValueError(f"moves selects the proposals of sampler='device'; sampler={sampler!r} knows the stretch move alone "
+                         "(compose sampling.EnsembleMoves with your evaluator instead)")
+    if moves is not None:
+        move_weights(moves)  # (refused before anything is built)
     rng = np.random.default_rng(seed)
     if sampler == "tempered":
         betas = geometric_betas(ntemps, beta_min, prior_rung)
@@ -766,7 +1090,10 @@ def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: i
     _, lower, upper = fitter.build_spec(param_defs)
     if sampler == "device":
         pos0 = initial_positions(lower, upper, nwalkers, rng, center=center, spread=spread)
-        chain, logp, acc = run_stretch_move_device(fitter, param_defs, pos0, nsteps, seed=seed)
+        if moves is None:
+            chain, logp, acc = run_stretch_move_device(fitter, param_defs, pos0, nsteps, seed=seed)
+        else:
+            chain, logp, acc = run_moves_device(fitter, param_defs, pos0, nsteps, moves=moves, seed=seed)
     else:
         log_prob_batch = fitter.make_log_prob_batch(param_defs, loglike_fn=loglike_fn)
         pos0 = initial_positions(lower, upper, nwalkers, rng, center=center, spread=spread)
