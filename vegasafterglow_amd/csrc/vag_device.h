@@ -1017,11 +1017,19 @@ VAG_DEV double relu_f64(double z) {
     return r;
 #endif
 }
-template <class Tab>
+// RELU_FIRST: max(z, 0) is formed for every lane ahead of ONE masked region, the table side's, where the plain form has a masked
+// region per side: one more vector instruction where a whole wavefront takes the table side, three mask instructions and a branch
+// fewer in every call.  Same value per lane.  On for the split flux kernel's boundary team (profiles/flux_prefetch_ab.txt).
+template <bool RELU_FIRST = false, class Tab>
 VAG_DEV double sp_fast(double z, Tab tab) {
     const double a = fabs(z);
 #ifndef VAG_SP_BRANCHLESS
-    if (a > 20.0) return relu_f64(z);
+    if constexpr (RELU_FIRST) {
+        const double r = relu_f64(z);
+        if (a > 20.0) return r;
+    } else {
+        if (a > 20.0) return relu_f64(z);
+    }
 #endif
     const double t = fma(a, (double)SP_PER_UNIT, SP_MAGIC);  // nearest node: integer in the low mantissa word
     const int idx = (int)min((unsigned)__double2loint(t), (unsigned)(SP_INTERVALS - 1));  // the clamp only acts on NaN
@@ -1037,6 +1045,39 @@ VAG_DEV double sp_fast(double z, Tab tab) {
     p = a > 20.0 ? 0.0 : p;  // straight-line code: independent softplus terms of one evaluation interleave
 #endif
     return fma(0.5, z + a, p);  // max(z, 0) = (z + |z|) / 2, exact
+}
+
+// sp_fast in two phases, for a caller that requests the table rows of several terms before it uses the first (log2_I_nu_pair):
+// sp_issue does, under sp_fast's |z| <= 20 predicate, the node / tau arithmetic and the three 16-byte reads; sp_finish the five FMAs
+// and the 0.5 (z + |z|) term, or relu_f64 on the shortcut side.  sp_finish(z, sp_issue(z, tab)) has the bits of sp_fast(z, tab): the
+// same operations in the same order (tests/test_sp_pair_host.py).  Nothing of `SpPending` but `shortcut` is read on the shortcut side.
+struct SpPending {
+    vdouble2 c01, c23, c45;
+    double tau;
+    bool shortcut;  // |z| > 20: max(z, 0), no table row requested
+};
+template <class Tab>
+VAG_DEV SpPending sp_issue(double z, Tab tab) {
+    SpPending q;
+    const double a = fabs(z);
+    q.shortcut = a > 20.0;
+    if (!q.shortcut) {
+        const double t = fma(a, (double)SP_PER_UNIT, SP_MAGIC);
+        const int idx = (int)min((unsigned)__double2loint(t), (unsigned)(SP_INTERVALS - 1));
+        q.tau = fma(a, (double)SP_PER_UNIT, -(t - SP_MAGIC));
+        const auto c2 = sp_row(tab, idx);
+        q.c01 = c2[0], q.c23 = c2[1], q.c45 = c2[2];
+    }
+    return q;
+}
+VAG_DEV double sp_finish(double z, const SpPending& q) {
+    if (q.shortcut) return relu_f64(z);
+    double p = fma(q.c45.y, q.tau, q.c45.x);
+    p = fma(p, q.tau, q.c23.y);
+    p = fma(p, q.tau, q.c23.x);
+    p = fma(p, q.tau, q.c01.y);
+    p = fma(p, q.tau, q.c01.x);
+    return fma(0.5, z + fabs(z), p);
 }
 
 // 2^x: round-to-nearest split + degree-11 minimax polynomial in f on [-0.5, 0.5] (max rel err 2.1e-16) + ldexp.  Large |x|
@@ -1197,23 +1238,91 @@ VAG_DEV void lds_add_f64(double* p, double v) {
 // >= 0 (sp_fast), so lb >= th = 2.5 lg2_nu + VP_TB also after rounding, and with SAB > 0 (rounding is monotone)
 // SAB (thin - lb) <= SAB (thin - th): where the right side is < -20 the blend's softplus returns exactly 0 for either lb, and the
 // result has the bits of the full path.  NaN compares false and takes the full path.
-template <bool THICK_BOUND = false, class PtrT, class Tab>
+// RELU_FIRST: the softplus terms in sp_fast's form of that name (same bits).
+template <bool THICK_BOUND = false, bool RELU_FIRST = false, class PtrT, class Tab>
 VAG_DEV double log2_I_nu_fast(const PtrT& c, int st, const SpecConst& sc, double lg2_nu, Tab sp) {
     const double l_lo = c[VP_LG2_LO * st];
-    const double thin = (lg2_nu - l_lo) * (1.0 / 3.0) - sp_fast(c[VP_DLO * st] * (lg2_nu - l_lo), sp) * c[VP_INV_SLO * st] -
-                        sp_fast(fma(c[VP_DHI * st], lg2_nu, c[VP_BHI * st]), sp) * c[VP_INV_SHI * st];
+    const double thin = (lg2_nu - l_lo) * (1.0 / 3.0) - sp_fast<RELU_FIRST>(c[VP_DLO * st] * (lg2_nu - l_lo), sp) * c[VP_INV_SLO * st] -
+                        sp_fast<RELU_FIRST>(fma(c[VP_DHI * st], lg2_nu, c[VP_BHI * st]), sp) * c[VP_INV_SHI * st];
     const double lx = lg2_nu - c[VP_LG2_NUM * st];
     double lb = fma(2.5, lg2_nu, c[VP_TB * st]);  // thick branch 2.5 lx + log2_thick_norm_
     if (!(lx > sc.log2_x_far)) {
         if (!THICK_BOUND || !(c[VP_SAB * st] * (thin - lb) < -20.0 && c[VP_SAB * st] > 0)) {
             const double s = -sc.smooth_thick * exp2_fast(2. / 3 * lx);
-            lb += sp_fast(-0.5 * lx + s, sp);
+            lb += sp_fast<RELU_FIRST>(-0.5 * lx + s, sp);
         }
     }
-    const double smooth_one = thin - sp_fast(c[VP_SAB * st] * (thin - lb), sp) * c[VP_INV_SAB * st];
+    const double smooth_one = thin - sp_fast<RELU_FIRST>(c[VP_SAB * st] * (thin - lb), sp) * c[VP_INV_SAB * st];
     const double spec = c[VP_LG2_I_SLO * st] + smooth_one;
     if (lg2_nu - c[VP_LG2_NUMAX * st] < -20) return spec;
     return spec - c[VP_INV_NUMAX * st] * exp2_fast(lg2_nu);
+}
+
+// log2_I_nu_fast<THICK_BOUND> at the TWO frequencies xa, xb of a boundary work item, walked stage by stage so that the table rows of
+// independent softplus terms are requested together (sp_issue, sp_issue, sp_finish, sp_finish): (a) the lower- and upper-break terms
+// of both frequencies, (b) the two thick-branch terms, (c) the two absorption blends, (d) the nu_max cut.  Four LDS round trips per
+// item instead of eight.  Every branch and shortcut of log2_I_nu_fast is kept, per lane and per frequency, and within one frequency
+// the operations and their order are log2_I_nu_fast's: ba and bb have the bits of the two single calls
+// (tests/test_sp_pair_host.py on the host, tests/test_flux_split_prefetch.py on the device).  IN_FLIGHT: the break terms requested
+// together in stage (a): 4 = all of them (48 VGPRs of pending rows), 2 = the lower-break terms of both frequencies, then the
+// upper-break terms, 1 = one frequency's two terms at a time.
+// Measured on the split kernel's boundary team and NOT taken (-DVAG_FLUX_PAIR, profiles/flux_prefetch_ab.txt): the masks of the
+// split regions cost more scalar instructions than the earlier requests save in waiting.
+template <bool THICK_BOUND, int IN_FLIGHT = 4, class PtrT, class Tab>
+VAG_DEV void log2_I_nu_pair(const PtrT& c, const SpecConst& sc, double xa, double xb, Tab sp, double& ba, double& bb) {
+    static_assert(IN_FLIGHT == 4 || IN_FLIGHT == 2 || IN_FLIGHT == 1, "stage (a) of log2_I_nu_pair");
+    const double l_lo = c[VP_LG2_LO];
+    // (a) thin = (x - l_lo) / 3 - sp(lower break) / s_lo - sp(upper break) / s_hi
+    const double z_la = c[VP_DLO] * (xa - l_lo), z_lb = c[VP_DLO] * (xb - l_lo);
+    const double z_ha = fma(c[VP_DHI], xa, c[VP_BHI]), z_hb = fma(c[VP_DHI], xb, c[VP_BHI]);
+    double thin_a, thin_b;
+    if constexpr (IN_FLIGHT == 4) {
+        const SpPending p_la = sp_issue(z_la, sp), p_ha = sp_issue(z_ha, sp), p_lb = sp_issue(z_lb, sp), p_hb = sp_issue(z_hb, sp);
+        thin_a = (xa - l_lo) * (1.0 / 3.0) - sp_finish(z_la, p_la) * c[VP_INV_SLO] - sp_finish(z_ha, p_ha) * c[VP_INV_SHI];
+        thin_b = (xb - l_lo) * (1.0 / 3.0) - sp_finish(z_lb, p_lb) * c[VP_INV_SLO] - sp_finish(z_hb, p_hb) * c[VP_INV_SHI];
+    } else if constexpr (IN_FLIGHT == 2) {
+        const SpPending p_la = sp_issue(z_la, sp), p_lb = sp_issue(z_lb, sp);
+        const double u_a = (xa - l_lo) * (1.0 / 3.0) - sp_finish(z_la, p_la) * c[VP_INV_SLO];
+        const double u_b = (xb - l_lo) * (1.0 / 3.0) - sp_finish(z_lb, p_lb) * c[VP_INV_SLO];
+        const SpPending p_ha = sp_issue(z_ha, sp), p_hb = sp_issue(z_hb, sp);
+        thin_a = u_a - sp_finish(z_ha, p_ha) * c[VP_INV_SHI];
+        thin_b = u_b - sp_finish(z_hb, p_hb) * c[VP_INV_SHI];
+    } else {
+        const SpPending p_la = sp_issue(z_la, sp), p_ha = sp_issue(z_ha, sp);
+        thin_a = (xa - l_lo) * (1.0 / 3.0) - sp_finish(z_la, p_la) * c[VP_INV_SLO] - sp_finish(z_ha, p_ha) * c[VP_INV_SHI];
+        const SpPending p_lb = sp_issue(z_lb, sp), p_hb = sp_issue(z_hb, sp);
+        thin_b = (xb - l_lo) * (1.0 / 3.0) - sp_finish(z_lb, p_lb) * c[VP_INV_SLO] - sp_finish(z_hb, p_hb) * c[VP_INV_SHI];
+    }
+    // (b) thick branch 2.5 lx + log2_thick_norm_, its softplus term under the far cut and the thick-term bound, per lane as today
+    const double lx_a = xa - c[VP_LG2_NUM], lx_b = xb - c[VP_LG2_NUM];
+    double lb_a = fma(2.5, xa, c[VP_TB]), lb_b = fma(2.5, xb, c[VP_TB]);
+    auto thick_term = [&](double lx, double thin, double lb) {
+        return !(lx > sc.log2_x_far) && (!THICK_BOUND || !(c[VP_SAB] * (thin - lb) < -20.0 && c[VP_SAB] > 0));
+    };
+    const bool t_a = thick_term(lx_a, thin_a, lb_a), t_b = thick_term(lx_b, thin_b, lb_b);
+    double z_ta = 0, z_tb = 0;
+    SpPending p_ta, p_tb;
+    if (t_a) {
+        const double s = -sc.smooth_thick * exp2_fast(2. / 3 * lx_a);
+        z_ta = -0.5 * lx_a + s;
+        p_ta = sp_issue(z_ta, sp);
+    }
+    if (t_b) {
+        const double s = -sc.smooth_thick * exp2_fast(2. / 3 * lx_b);
+        z_tb = -0.5 * lx_b + s;
+        p_tb = sp_issue(z_tb, sp);
+    }
+    if (t_a) lb_a += sp_finish(z_ta, p_ta);
+    if (t_b) lb_b += sp_finish(z_tb, p_tb);
+    // (c) the absorption blends
+    const double z_sa = c[VP_SAB] * (thin_a - lb_a), z_sb = c[VP_SAB] * (thin_b - lb_b);
+    const SpPending p_sa = sp_issue(z_sa, sp), p_sb = sp_issue(z_sb, sp);
+    const double spec_a = c[VP_LG2_I_SLO] + (thin_a - sp_finish(z_sa, p_sa) * c[VP_INV_SAB]);
+    const double spec_b = c[VP_LG2_I_SLO] + (thin_b - sp_finish(z_sb, p_sb) * c[VP_INV_SAB]);
+    // (d) the nu_max cut
+    ba = spec_a, bb = spec_b;
+    if (!(xa - c[VP_LG2_NUMAX] < -20)) ba = spec_a - c[VP_INV_NUMAX] * exp2_fast(xa);
+    if (!(xb - c[VP_LG2_NUMAX] < -20)) bb = spec_b - c[VP_INV_NUMAX] * exp2_fast(xb);
 }
 
 // The same evaluator for the TWO frequencies of a boundary work item as one straight-line block: no lane-divergent branches (the

@@ -1625,6 +1625,10 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     };
     if (a_team) {
         const int atid = tid;  // the A team is the first wavefronts
+#ifdef VAG_FLUX_STAMPS  // developer aid: cycles an A wavefront spends in the boundary loop, and its passes (profiles/flux_stamps.sh)
+        long long c_loop = 0;
+        int n_pass = 0, n_rows_done = 0;
+#endif
         auto spectra_of = [&](int n, int j1, int i1, int tb1) {
             const int r = n + 1;
             if (r >= n_rows) return;
@@ -1654,6 +1658,11 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
             int kk = atid - __mul24(lg, nk);
             int bofs = __mul24(lg, 2 * KS);
             const int top = (nnu - 1) * KS;
+#ifdef VAG_FLUX_STAMPS
+            const long long c_in = __builtin_readcyclecounter();
+            n_pass += (total - (atid & ~63) + AL - 1) / AL;  // passes this wavefront makes (its first lane's count)
+            ++n_rows_done;
+#endif
             for (int q = atid; q < total; q += AL) {
                 const int k = k_lo + kk;
                 const int l0 = lg * 2, l1 = min(l0 + 1, nnu - 1);
@@ -1662,8 +1671,17 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
                 const double geom = eat_geom(lg2_dOmega, regs[VP_LG2_R2], dop);  // eat_row's s_geom[k]
                 // <true>: the thick-term bound.  By a CPU tally of the headline rows the thick softplus term is computed in 38 % of the
                 // wavefront-evaluations and needed in 17 % (profiles/flux_trim_ab.txt)
-                const double b0 = log2_I_nu_fast<true>(regs, 1, sc, s_nu[l0] - dop, sp_tab);
-                const double b1 = log2_I_nu_fast<true>(regs, 1, sc, s_nu[l1] - dop, sp_tab);
+#ifdef VAG_FLUX_PAIR  // measured and rejected (-DVAG_FLUX_PAIR=4, 2 or 1 break terms in flight): the item's two frequencies stage by stage,
+                      // the table rows of independent softplus terms requested together (log2_I_nu_pair).  Same bits, four LDS round
+                      // trips in series instead of eight, and +3.7 % per step: SQ_INSTS_SALU +27 % for the masks of the split
+                      // regions, and the wavefronts wait longer for the LDS, not shorter (profiles/flux_prefetch_ab.txt)
+                double b0, b1;
+                log2_I_nu_pair<true, VAG_FLUX_PAIR>(regs, sc, s_nu[l0] - dop, s_nu[l1] - dop, sp_tab, b0, b1);
+#else
+                // <.., true>: the softplus terms with one masked region each (sp_fast<RELU_FIRST>), -2 % per step
+                const double b0 = log2_I_nu_fast<true, true>(regs, 1, sc, s_nu[l0] - dop, sp_tab);
+                const double b1 = log2_I_nu_fast<true, true>(regs, 1, sc, s_nu[l1] - dop, sp_tab);
+#endif
                 sB[bofs + k] = b0 + geom;
                 sB[min(bofs + KS, top) + k] = b1 + geom;
                 kk += dq_k;
@@ -1675,12 +1693,23 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
                     bofs += 2 * KS;
                 }
             }
+#ifdef VAG_FLUX_STAMPS
+            c_loop += __builtin_readcyclecounter() - c_in;
+#endif
         };
         auto spectra = [&](int n, int j1, int i1, int j2, int i2, int, int tb1, int tb2, bool eat_now) {
             spectra_of(n, j1, i1, tb1);
             if (eat_now) eat(j2, i2, n + 2, tb2);
         };
+#ifdef VAG_FLUX_STAMPS
+        const long long c_item = __builtin_readcyclecounter();
+#endif
         pipeline(spectra, eat);
+#ifdef VAG_FLUX_STAMPS
+        if (m == 0 && blk == 1 && lane == 0)
+            printf("split A wave %d rows %d passes %d boundary-loop cycles %lld  per pass %lld  item %lld\n", wave, n_rows_done, n_pass, c_loop,
+                   c_loop / max(n_pass, 1), (long long)__builtin_readcyclecounter() - c_item);
+#endif
     } else {
         const int btid = tid - AL;
         const double w_lo = a.lg2_t_obs[0], w_hi = a.lg2_t_obs[nt - 1];  // == s_tobs[0], s_tobs[nt - 1]
@@ -1694,7 +1723,14 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
 #pragma unroll
             for (int l = 0; l < FLUX_SPLIT_MAX_NNU; ++l) acc[o][l] = 0;
         }
+#ifdef VAG_FLUX_STAMPS
+        long long c_interp = 0;
+        const long long c_item = __builtin_readcyclecounter();
+#endif
         auto interp = [&](int n, int, int, int, int, int tb0, int, int, bool) {
+#ifdef VAG_FLUX_STAMPS
+            const long long c_in = __builtin_readcyclecounter();
+#endif
             if (n >= 0) {
                 const double* s_tc = s_t + tb0 * KS;
                 const double row_t0 = s_tc[0], row_tN = s_tc[K - 1];
@@ -1737,8 +1773,15 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
                     }
                 }
             }
+#ifdef VAG_FLUX_STAMPS
+            c_interp += __builtin_readcyclecounter() - c_in;
+#endif
         };
         pipeline(interp, [](int, int, int, int) {});
+#ifdef VAG_FLUX_STAMPS
+        if (m == 0 && blk == 1 && lane == 0)
+            printf("split B wave %d interpolation cycles %lld  item %lld\n", wave, c_interp, (long long)__builtin_readcyclecounter() - c_item);
+#endif
         // partial grid of this workgroup, stored [l][idx] like the reference's F_nu (nu outer)
         double* my_partial = a.partial + ((size_t)m * a.max_blocks + blk) * ((size_t)nt * nnu);
 #pragma unroll
