@@ -1098,6 +1098,32 @@ int vag_tempered_run_dev(vag_ctx* ctx, const vag_loglike_request* request, const
                          double* d_pos, double* d_lnl, double* d_lnprior, int64_t* d_accepted, int64_t* d_swapped, double* d_chain,
                          double* d_lnl_chain, double* d_lnprior_chain);
 
+/* Chain autocorrelation on the device (added after VAG_ABI_VERSION 13, detect by symbol): the integrated autocorrelation time of
+ * every parameter of a chain in HBM, by the definition of INTEGRATION.md "Chain autocorrelation".
+ * The view: n_rows rows, nwalkers walkers, ndim parameters, element (t, w, d) at d_chain[t row_stride + w ndim + d] with
+ * row_stride >= nwalkers ndim (a plain chain [rows][W][D]: W D; the cold rung of a tempered chain [rows][T][W][D]: T W D).
+ * Per series s = w ndim + d: the two-pass mean m (m1 = (sum x) / n, m = m1 + (sum (x - m1)) / n, ascending t), y = x - m, and
+ * c_s(l) = sum_{t <= n - 1 - l} y[t] y[t + l] for l = 0 .. max_lag, one fma chain in ascending t, so its bits depend neither on the
+ * launch nor on max_lag.  Pooled over the walkers in ascending w: C_d(l), rho_d(l) = C_d(l) / C_d(0).  Sokal's window:
+ * tau_d(M) = 2 sum_{l <= M} rho_d(l) - 1 (a sequential sum), window[d] the smallest M <= max_lag with M >= c tau_d(M) and
+ * tau[d] = tau_d(window[d]); if there is none window[d] = -1 and tau[d] = tau_d(max_lag), a lower bound; if C_d(0) is zero or not
+ * finite tau[d] = NaN and window[d] = -1, for that parameter alone.  tau is in rows.
+ * Device pointers, the context's stream, no host synchronisation; the chain is read only, the outputs are d_rho[max_lag + 1][ndim]
+ * (may be NULL), d_tau[ndim], d_window[ndim], and the context's scratch holds the lag sums.
+ * Refused with VAG_E_INVALID (nothing is launched, the context stays usable): a null context, spec, chain, tau or window;
+ * n_rows < 2; nwalkers < 1 or ndim < 1; row_stride < nwalkers ndim; max_lag outside 1 .. n_rows - 1; c not finite and > 0.
+ * Refused with VAG_E_CAPACITY: lag sums (max_lag + 1) nwalkers ndim 8 bytes above VAG_CHAIN_SCRATCH_MAX (1 GiB: 16383 lags of 1024
+ * walkers x 8 parameters). */
+#define VAG_CHAIN_SCRATCH_MAX (1ll << 30)
+typedef struct vag_chain_spec {
+    int32_t nwalkers, ndim;
+    int64_t n_rows, row_stride;
+    int32_t max_lag;
+    double c;
+} vag_chain_spec;
+int vag_chain_autocorr_dev(vag_ctx* ctx, const vag_chain_spec* sp, const double* d_chain, double* d_rho, double* d_tau,
+                           int32_t* d_window);
+
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.
  * Stream-ordered on the context stream, but host-blocking: the call returns after the batch's device plan has been read back

@@ -256,6 +256,22 @@ def tempered_entry(lib, name):
     return getattr(lib, name)
 
 
+class ChainSpec(C.Structure):  # vag_chain_spec
+    _fields_ = [("nwalkers", C.c_int32), ("ndim", C.c_int32), ("n_rows", C.c_int64), ("row_stride", C.c_int64), ("max_lag", C.c_int32),
+                ("c", C.c_double)]
+
+
+CHAIN_SCRATCH_MAX = 1 << 30  # VAG_CHAIN_SCRATCH_MAX
+
+
+def chain_entry(lib, name="vag_chain_autocorr_dev"):
+    """The chain-autocorrelation entry point, added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build)."""
+    if not hasattr(lib, name):
+        raise RuntimeError(f"the loaded library has no {name}: the device autocorrelation estimate (sampling.chain_autocorr_device, "
+                           "converge= of the device run drivers, the tau of fit(sampler='device')) needs a newer build")
+    return getattr(lib, name)
+
+
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_LOG_UNIFORM, PRIOR_NONE, PRIOR_UNIFORM_RANGE = 0, 1, 2, 3, 4
 
 
@@ -310,7 +326,7 @@ EXPORTS = [
     "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev", "vag_loglike_tmpl_batch", "vag_loglike_tmpl_batch_dev",
     "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev", "vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev",
     "vag_loglike_split_dev", "vag_tempered_propose_dev", "vag_tempered_accept_dev", "vag_tempered_swap_dev", "vag_tempered_run_dev",
-    "vag_move_propose_dev", "vag_move_accept_dev", "vag_move_run_dev",
+    "vag_move_propose_dev", "vag_move_accept_dev", "vag_move_run_dev", "vag_chain_autocorr_dev",
 ]
 
 _lib = None
@@ -424,6 +440,8 @@ def load():
         lib.vag_tempered_accept_dev.argtypes = [v, tp, C.c_uint64, C.c_int, v, v, v, v, v, v, v]
         lib.vag_tempered_swap_dev.argtypes = [v, tp, C.c_uint64, v, v, v, v]
         lib.vag_tempered_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), tp, C.c_uint64, C.c_int, v, v, v, v, v, v, v, v]
+    if hasattr(lib, "vag_chain_autocorr_dev"):  # (detected by symbol: chain autocorrelation)
+        lib.vag_chain_autocorr_dev.argtypes = [v, C.POINTER(ChainSpec), v, v, v, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -33,6 +33,7 @@
 #include "vag_sampler.h"
 #include "vag_tempering.h"
 #include "vag_moves.h"
+#include "vag_chain_stats.h"
 #include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
 #include "vag_flux_plan.h"    // (host only: the launch decisions of the flux stage)
 
@@ -442,6 +443,7 @@ struct vag_ctx {
     DevBuf d_visblk, d_vispart;  // visibility groups of the likelihood (their data: vis below): their 64-visibility blocks, chi^2 partials
     DevBuf d_stretch_prop, d_stretch_lp;  // the device sampler (vag_stretch_run_dev): a half's proposals [half][ndim] and their ln p [half]
     DevBuf d_temper_prop, d_temper_lnl, d_temper_lnprior;  // parallel tempering (vag_tempered_run_dev): all temperatures' proposals of a half [T][half][ndim], their ln L and ln prior [T][half]
+    DevBuf d_chain_stats;  // chain autocorrelation (vag_chain_autocorr_dev): the means [S], the lag sums [L + 1][S], the pooled sums [L + 1][D]
     DevBuf d_move_factor;  // the move mix (vag_move_run_dev): ln of the Hastings factor of a half's proposals [half]; the proposals and their ln p go through d_stretch_prop / d_stretch_lp
     DevBuf d_polspec, d_polstokes;  // polarization groups of the likelihood (their data: pol below): the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
@@ -742,7 +744,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_stretch_prop, &c->d_stretch_lp, &c->d_temper_prop, &c->d_temper_lnl, &c->d_temper_lnprior, &c->d_move_factor})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_stretch_prop, &c->d_stretch_lp, &c->d_temper_prop, &c->d_temper_lnl, &c->d_temper_lnprior, &c->d_move_factor, &c->d_chain_stats})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -4274,6 +4276,49 @@ int vag_tempered_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_tem
             ++row;
         }
     }
+    return VAG_OK;
+}
+
+// ---- chain autocorrelation (kernels and the definition's pieces: vag_chain_stats.h; the definition: the public header) ----
+
+int vag_chain_autocorr_dev(vag_ctx* c, const vag_chain_spec* sp, const double* d_chain, double* d_rho, double* d_tau, int32_t* d_window) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !sp || !d_chain || !d_tau || !d_window) return set_err(VAG_E_INVALID, "null context, chain spec or buffer");
+    if (sp->n_rows < 2) return set_err(VAG_E_INVALID, "chain autocorrelation: n_rows must be >= 2, got %lld", (long long)sp->n_rows);
+    if (sp->nwalkers < 1 || sp->ndim < 1)
+        return set_err(VAG_E_INVALID, "chain autocorrelation: nwalkers and ndim must be >= 1, got %d and %d", sp->nwalkers, sp->ndim);
+    const long long series = (long long)sp->nwalkers * sp->ndim;
+    if (sp->row_stride < series)
+        return set_err(VAG_E_INVALID, "chain autocorrelation: row_stride must be >= nwalkers * ndim = %lld, got %lld", series, (long long)sp->row_stride);
+    if (sp->max_lag < 1 || (long long)sp->max_lag > (long long)sp->n_rows - 1)
+        return set_err(VAG_E_INVALID, "chain autocorrelation: max_lag must be 1..n_rows - 1 = %lld, got %d", (long long)sp->n_rows - 1, sp->max_lag);
+    if (!std::isfinite(sp->c) || !(sp->c > 0.0)) return set_err(VAG_E_INVALID, "chain autocorrelation: c must be finite and > 0, got %g", sp->c);
+    const long long lags = (long long)sp->max_lag + 1;
+    if (series > VAG_CHAIN_SCRATCH_MAX / 8 / lags)
+        return set_err(VAG_E_CAPACITY, "chain autocorrelation: the lag sums (max_lag + 1) * nwalkers * ndim * 8 = %lld * %lld * 8 bytes exceed %lld", lags,
+                       series, (long long)VAG_CHAIN_SCRATCH_MAX);
+    HIPCHK(hipSetDevice(c->device));
+    const int S = (int)series, L = sp->max_lag, D = sp->ndim;  // (S < 2^27 under the cap)
+    if (c->d_chain_stats.ensure(sizeof(double) * ((size_t)S + (size_t)lags * S + (size_t)lags * D))) return VAG_E_HIP;
+    double* d_mean = c->d_chain_stats.as<double>();
+    double* d_lag = d_mean + S;
+    double* d_pooled = d_lag + (size_t)lags * S;
+    const unsigned groups = (unsigned)((S + CHAIN_LANES - 1) / CHAIN_LANES);
+    const unsigned tiles = (unsigned)((lags + VAG_CHAIN_TILE - 1) / VAG_CHAIN_TILE);
+    hipLaunchKernelGGL(vag_chain_mean_kernel, dim3(groups), dim3(CHAIN_LANES), 0, c->stream, d_chain, (long long)sp->n_rows,
+                       (long long)sp->row_stride, S, d_mean);
+    HIPCHK(hipGetLastError());
+    const unsigned tile_groups = (tiles + VAG_CHAIN_WAVES - 1) / VAG_CHAIN_WAVES;  // (groups * tile_groups < 2^23 under the cap)
+    hipLaunchKernelGGL(vag_chain_acf_kernel, dim3(groups * tile_groups), dim3(CHAIN_LANES, VAG_CHAIN_WAVES), 0, c->stream, d_chain,
+                       (long long)sp->n_rows, (long long)sp->row_stride, S, (int)groups, L, d_mean, d_lag);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(vag_chain_pool_kernel, dim3((unsigned)((lags * D + 255) / 256)), dim3(256), 0, c->stream, d_lag, sp->nwalkers, D, L,
+                       d_pooled);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(vag_chain_tau_kernel, dim3((unsigned)((D + CHAIN_LANES - 1) / CHAIN_LANES)), dim3(CHAIN_LANES), 0, c->stream, d_pooled, D,
+                       L, sp->c, d_rho ? d_rho : d_pooled, d_tau, reinterpret_cast<int*>(d_window));
+    HIPCHK(hipGetLastError());
     return VAG_OK;
 }
 

@@ -1810,7 +1810,9 @@ class Fitter:
         ``sampler="device"``: the whole run on the device (sampling.run_stretch_move_device, or with ``moves="reference"`` or a
         sequence of (name, weight) sampling.run_moves_device: the DE and snooker moves of the reference); ``sampler="tempered"``: parallel
         tempering on the device (sampling.run_tempered_device; ``ntemps``, ``beta_min``, ``prior_rung`` shape the ladder, `nwalkers`
-        is per temperature), which also returns the evidence by thermodynamic integration."""
+        is per temperature), which also returns the evidence by thermodynamic integration.  Every sampler reports "tau" and
+        "tau_reliable", the autocorrelation time of each parameter after the burn-in; ``converge=sampling.Convergence(...)`` makes
+        `nsteps` a maximum for the device samplers and stops the run when tau has settled (sampling.fit)."""
         from . import sampling
         self.validate_parameters(param_defs)
         ndim = sum(1 for pd in param_defs if pd.scale is not Scale.fixed)

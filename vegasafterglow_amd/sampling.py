@@ -18,9 +18,14 @@ walkers over a thread pool (VegasAfterglow/fitting/samplers.py:59-106).  Here th
   (``geometric_betas``), all temperatures' proposals in one likelihood call per half-step, exchanges between neighbours, and the
   evidence by thermodynamic integration (``thermodynamic_evidence``).  ``run_tempered_philox``, ``tempered_proposals``,
   ``tempered_accepts`` and ``tempered_swaps`` state it in numpy, to the bit;
+* ``chain_autocorr_device`` / ``Convergence`` -- the integrated autocorrelation time of every parameter of a chain that lives on the
+  device (pooled over the walkers, Sokal's window), and the stopping rule built on it: ``converge=`` makes ``nsteps`` of the three
+  device run drivers a maximum.  ``chain_autocorr``, ``chain_mean`` and ``sokal_window`` state the estimate in numpy;
 * ``BatchPool`` -- the object handed to ``bilby.run_sampler(pool=...)`` in place of the reference's thread pool
   (samplers.py:146-170): ``pool.map(loglikelihood, points)`` becomes one device call over the whole live-point queue.
 """
+import math
+from collections import namedtuple
 from typing import Callable, Optional, Sequence
 
 import numpy as np
@@ -318,9 +323,11 @@ class StretchMove:
                                                   pos.data_ptr(), lp.data_ptr(), accepted.data_ptr())))
 
 
-def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, who, entry, make_move):
+def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, who, entry, make_move, converge=None,
+                       nburn=0, _record=False):
     """The body of run_stretch_move_device and run_moves_device: `entry` is the run entry's name and make_move(nw, ndim) the
-    struct it takes behind the request (after the Python-side checks, which make_move performs)."""
+    struct it takes behind the request (after the Python-side checks, which make_move performs).  converge, nburn: the stopping
+    rule (_ConvergenceMonitor); with converge=None the loop is the plain one, chunk by chunk."""
     import ctypes as C
     import torch
     from . import _lib
@@ -333,6 +340,7 @@ def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, c
     move = make_move(nw, ndim)
     if chunk < 1 or nsteps < 0:
         raise ValueError("chunk must be >= 1 and nsteps >= 0")
+    monitor = _ConvergenceMonitor(converge, nsteps, nburn, thin, chunk, fitter.device, lambda kept: kept)
     spec, _, _ = fitter.build_spec(param_defs, priors=priors, use_priors=True)
     if spec.ndim != ndim:
         raise ValueError("pos0 must be [nwalkers, ndim]")
@@ -357,8 +365,9 @@ def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, c
     on_current_stream(lib, h, lock, dev, initial)
     if not bool(torch.isfinite(lp).all()):
         raise ValueError("initial positions must have finite log-probability")
-    for step0 in range(0, nsteps, chunk):
-        n = min(chunk, nsteps - step0)
+    step0 = 0
+    while step0 < nsteps:
+        n = monitor.chunk_end(step0) - step0
         row = step0 // thin
         stored = row < rows
         on_current_stream(lib, h, lock, dev, lambda: _lib.check(run(
@@ -366,16 +375,23 @@ def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, c
             chain.data_ptr() + 8 * row * nw * ndim if stored else None, logp.data_ptr() + 8 * row * nw if stored else None)))
         if progress is not None:
             progress(step0 + n - 1, pos.cpu().numpy(), lp.cpu().numpy())
+        step0 += n
+        if monitor.stop(chain, step0):
+            break
     plan = _lib.Plan()
     with lock:
         lib.vag_last_plan(h, C.byref(plan))
     fitter._log_plan_warnings(plan, nw // 2)
     fitter.last_plan = plan
-    return chain.cpu().numpy(), logp.cpu().numpy(), accepted.cpu().numpy() / max(nsteps, 1)
+    if converge is None and not _record:
+        return chain.cpu().numpy(), logp.cpu().numpy(), accepted.cpu().numpy() / max(nsteps, 1)
+    kept = step0 // thin  # (step0: the steps run)
+    return (chain[:kept].cpu().numpy(), logp[:kept].cpu().numpy(), accepted.cpu().numpy() / max(step0, 1), monitor.record(chain, step0))
 
 
 def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, nsteps: int, seed: int = 0,
-                            a: float = 2.0, thin: int = 1, priors=None, chunk: int = 64, progress: Optional[Callable] = None):
+                            a: float = 2.0, thin: int = 1, priors=None, chunk: int = 64, progress: Optional[Callable] = None,
+                            converge: Optional["Convergence"] = None, nburn: int = 0, _record: bool = False):
     """The stretch move of run_stretch_move_philox with everything on the device: the spec is built once, and every `chunk` steps are
     ONE call (vag_stretch_run_dev) that scans and uploads the spec blocks once and then only launches -- positions, ln p, the chain
     and the acceptance counts stay in HBM, nothing is copied and the stream is not synchronised between steps.  ln p is
@@ -383,13 +399,19 @@ def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0
 
     Returns (chain[nsteps // thin, nw, ndim], log_prob[nsteps // thin, nw], acceptance[nw]) as numpy arrays.  The chunk size does
     not change a bit of them.  ``progress(step, pos, lp)`` is called once per chunk with the last step of the chunk; the context's
-    lock is free between chunks."""
+    lock is free between chunks.
+
+    ``converge=Convergence(...)`` makes ``nsteps`` a maximum: the chunks are clipped so that a check lands after every
+    ``converge.check`` steps, where the autocorrelation times of the stored rows from ``nburn // thin`` on are estimated on the device
+    (chain_autocorr_device: only tau and the windows come to the host), and the run stops at the first check that meets the rule
+    (Convergence).  The three arrays are then those of a plain run of the steps run, to the bit, and a fourth element follows: the
+    ConvergedAutocorr record.  With ``converge=None`` nothing changes."""
     def make_move(nw, ndim):
         from . import _lib
         _check_stretch(nw, ndim, a, thin)
         return _lib.StretchSpec(int(seed) & (2 ** 64 - 1), float(a), nw, ndim, int(thin))
     return _run_halves_device(fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, "run_stretch_move_device",
-                              "vag_stretch_run_dev", make_move)
+                              "vag_stretch_run_dev", make_move, converge, nburn, _record)
 
 
 # ---- the move mix (INTEGRATION.md "The move mix"): the stretch move, the differential-evolution move and the snooker move, one kind
@@ -684,17 +706,18 @@ class EnsembleMoves:
 def run_moves_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, nsteps: int, moves=REFERENCE_MOVES,
                      seed: int = 0, a: float = 2.0, gamma0: Optional[float] = None, sigma: float = DE_SIGMA,
                      gamma_snooker: float = SNOOKER_GAMMA, thin: int = 1, priors=None, chunk: int = 64,
-                     progress: Optional[Callable] = None):
+                     progress: Optional[Callable] = None, converge: Optional["Convergence"] = None, nburn: int = 0, _record: bool = False):
     """run_stretch_move_device with the move mix ``moves`` (move_weights; the default is the reference's DE 0.8 / snooker 0.2): every
     `chunk` steps are ONE call of vag_move_run_dev, which chooses each step's kind on the host and launches its kernels around the
-    likelihood call.  Returns, chunking, thinning and ``progress`` as there; the chain is run_moves_philox's from the same ln p."""
+    likelihood call.  Returns, chunking, thinning, ``progress``, ``converge`` and ``nburn`` as there; the chain is run_moves_philox's
+    from the same ln p."""
     weights = move_weights(moves)
 
     def make_move(nw, ndim):
         g0 = _check_moves(weights, nw, ndim, a, gamma0, sigma, gamma_snooker, thin)
         return _move_spec(weights, nw, ndim, seed, a, g0, sigma, gamma_snooker, thin)
     return _run_halves_device(fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, "run_moves_device", "vag_move_run_dev",
-                              make_move)
+                              make_move, converge, nburn, _record)
 
 
 # ---- parallel tempering around that move (INTEGRATION.md "Parallel tempering"): a ladder of T inverse temperatures, temperature t
@@ -981,7 +1004,8 @@ def loglike_split_device(fitter: Fitter, spec, theta, lnl, lnprior):
 
 
 def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, betas, nsteps: int, seed: int = 0,
-                        a: float = 2.0, thin: int = 1, priors=None, chunk: int = 64, progress: Optional[Callable] = None):
+                        a: float = 2.0, thin: int = 1, priors=None, chunk: int = 64, progress: Optional[Callable] = None,
+                        converge: Optional["Convergence"] = None, nburn: int = 0, _record: bool = False):
     """run_tempered_philox with everything on the device: the spec is built once, and every `chunk` steps are ONE call
     (vag_tempered_run_dev) that scans and uploads the spec blocks once and then only launches.  Per half-step the T nw / 2 proposals
     of all temperatures go through one likelihood call; positions, ln L, ln prior, the chain and the counts stay in HBM.  ln L is the
@@ -990,7 +1014,11 @@ def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np
 
     Returns (chain[nsteps // thin, T, nw, ndim], lnl[.., T, nw], lnprior[.., T, nw], acceptance[T, nw], swap_fraction[T - 1]) as
     numpy arrays.  The chunk size does not change a bit of them.  ``progress(step, pos, lnl, lnprior)`` is called once per chunk
-    with the last step of the chunk; the context's lock is free between chunks."""
+    with the last step of the chunk; the context's lock is free between chunks.
+
+    ``converge`` and ``nburn`` as in run_stretch_move_device, with the autocorrelation times of the cold rung (beta = 1), read in
+    place through its row stride: ``nsteps`` is then a maximum, the five values are those of a plain run of the steps run, and a
+    sixth follows, the ConvergedAutocorr record."""
     import ctypes as C
     import torch
     from . import _lib
@@ -1006,6 +1034,7 @@ def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np
     _check_stretch(nw, ndim, a, thin)
     if chunk < 1 or nsteps < 0:
         raise ValueError("chunk must be >= 1 and nsteps >= 0")
+    monitor = _ConvergenceMonitor(converge, nsteps, nburn, thin, chunk, fitter.device, lambda kept: kept[:, 0])
     spec, _, _ = fitter.build_spec(param_defs, priors=priors, use_priors=True)
     if spec.ndim != ndim:
         raise ValueError("pos0 must be [ntemps, nwalkers, ndim]")
@@ -1030,8 +1059,9 @@ def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np
     if not bool((torch.isfinite(lnl) & torch.isfinite(lnprior)).all()):
         raise ValueError("initial positions must have finite ln L and ln prior")
     per_row = ntemps * nw
-    for step0 in range(0, nsteps, chunk):
-        n = min(chunk, nsteps - step0)
+    step0 = 0
+    while step0 < nsteps:
+        n = monitor.chunk_end(step0) - step0
         row = step0 // thin
         stored = row < rows
         on_current_stream(lib, h, lock, dev, lambda: _lib.check(run(
@@ -1040,20 +1070,232 @@ def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np
             lnl_chain.data_ptr() + 8 * row * per_row if stored else None, lnprior_chain.data_ptr() + 8 * row * per_row if stored else None)))
         if progress is not None:
             progress(step0 + n - 1, pos.cpu().numpy(), lnl.cpu().numpy(), lnprior.cpu().numpy())
+        step0 += n
+        if monitor.stop(chain, step0):
+            break
+    plain = converge is None and not _record
+    ran = nsteps if plain else step0
     plan = _lib.Plan()
     with lock:
         lib.vag_last_plan(h, C.byref(plan))
     fitter._log_plan_warnings(plan, ntemps * nw // 2)
     fitter.last_plan = plan
-    attempts = swap_attempts(ntemps, 0, nsteps)
+    attempts = swap_attempts(ntemps, 0, ran)
     swap_fraction = swapped.cpu().numpy()[:ntemps - 1].sum(axis=1) / np.maximum(attempts * nw, 1)
-    return (chain.cpu().numpy(), lnl_chain.cpu().numpy(), lnprior_chain.cpu().numpy(), accepted.cpu().numpy() / max(nsteps, 1),
-            swap_fraction)
+    kept = ran // thin
+    out = (chain[:kept].cpu().numpy(), lnl_chain[:kept].cpu().numpy(), lnprior_chain[:kept].cpu().numpy(),
+           accepted.cpu().numpy() / max(ran, 1), swap_fraction)
+    return out if plain else out + (monitor.record(chain, ran),)
+
+
+# ---- chain autocorrelation (INTEGRATION.md "Chain autocorrelation"): the integrated autocorrelation time of every parameter, pooled over
+#      the walkers, with Sokal's window -- the number that says when a chain is long enough.  The numpy statement first, then the device,
+#      then the stopping rule of the three device run drivers. ----
+
+ChainAutocorr = namedtuple("ChainAutocorr", "tau window reliable rho n_rows max_lag")
+ChainAutocorr.__doc__ = """What chain_autocorr and chain_autocorr_device return: tau[D] in stored rows (NaN where the pooled variance is
+zero or not finite; a lower bound where window is -1), window[D] (Sokal's M, -1 = none within max_lag), reliable[D]
+(window >= 0 and n_rows >= tol tau), rho[max_lag + 1, D] (None where it was not asked for), the rows used and the lag range."""
+
+ConvergedAutocorr = namedtuple("ConvergedAutocorr", ChainAutocorr._fields + ("converged", "steps", "history", "thin"))
+ConvergedAutocorr.__doc__ = """The last element a device run driver returns under ``converge=``: the estimate at the end of the run,
+``converged`` (the stopping rule was met), ``steps`` (the steps run), ``history`` ([checks, D]: tau in rows at every check, NaN rows
+where fewer than two rows were kept) and ``thin``; tau * thin is tau in steps."""
+
+
+class Convergence:
+    """The stopping rule of the device run drivers (``converge=``): every ``check`` steps the autocorrelation times of the rows kept
+    so far are estimated on the device, and the run stops at the first check where every parameter is reliable (a window was found and
+    rows >= tol tau) and no tau moved by more than rtol tau since the check before.  c is Sokal's window constant."""
+
+    def __init__(self, check: int = 100, tol: float = 50.0, rtol: float = 0.01, c: float = 5.0):
+        if int(check) != check or check < 1:
+            raise ValueError("Convergence: check must be a whole number of steps >= 1")
+        for name, v in (("tol", tol), ("rtol", rtol), ("c", c)):
+            if not np.isfinite(v) or not v > 0:
+                raise ValueError(f"Convergence: {name} must be finite and > 0, got {v}")
+        self.check, self.tol, self.rtol, self.c = int(check), float(tol), float(rtol), float(c)
+
+    def __repr__(self):
+        return f"Convergence(check={self.check}, tol={self.tol}, rtol={self.rtol}, c={self.c})"
+
+    def met(self, tau, reliable, previous) -> bool:
+        """The rule at one check: tau[D] and reliable[D] of this check, ``previous`` the tau of the check before (None at the first)."""
+        if previous is None or not np.all(reliable):
+            return False
+        return bool(np.all(np.abs(tau - previous) <= self.rtol * tau))
+
+
+def default_max_lag(n_rows: int, c: float = 5.0, tol: float = 50.0) -> int:
+    """L = min(n - 1, ceil(c n / tol)): a window beyond it means tau > n / tol, which fails the tol tau rule whatever it is."""
+    return int(min(n_rows - 1, math.ceil(c * n_rows / tol)))
+
+
+def _chain_lags(n, c, tol, max_lag):
+    if not np.isfinite(c) or not c > 0 or not np.isfinite(tol) or not tol > 0:
+        raise ValueError("chain autocorrelation: c and tol must be finite and > 0")
+    if n < 2:
+        raise ValueError(f"chain autocorrelation: at least two rows are needed, got {n}")
+    if max_lag is None:
+        return default_max_lag(n, c, tol)
+    if int(max_lag) != max_lag or not 1 <= max_lag <= n - 1:
+        raise ValueError(f"chain autocorrelation: max_lag must be a whole number in 1..rows - 1 = {n - 1}, got {max_lag}")
+    return int(max_lag)
+
+
+def _chain_first(rows, first):
+    if int(first) != first or not 0 <= first <= rows:
+        raise ValueError(f"chain autocorrelation: first must be a whole number in 0..rows = {rows}, got {first}")
+    return int(first)
+
+
+def chain_mean(x) -> np.ndarray:
+    """The two-pass mean of every series of x[n, ...] over its first axis: m1 = (sum x) / n, m = m1 + (sum (x - m1)) / n, both sums
+    sequential in ascending t (vag::chain_mean, to the bit)."""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.shape[0]
+    m1 = np.cumsum(x, axis=0)[-1] / n
+    return m1 + np.cumsum(x - m1, axis=0)[-1] / n
+
+
+def sokal_window(rho, c: float = 5.0):
+    """Sokal's window on rho[L + 1] or rho[L + 1, D]: tau(M) = 2 sum_{l <= M} rho(l) - 1 (sequential), the smallest M with
+    M >= c tau(M).  Returns (tau, window): tau(M) at that M, or tau(L) and -1 where there is none (vag::sokal_window, to the bit)."""
+    rho = np.asarray(rho, dtype=np.float64)
+    flat = rho.reshape(rho.shape[0], -1)
+    with np.errstate(invalid="ignore"):
+        taus = 2.0 * np.cumsum(flat, axis=0) - 1.0
+        ok = np.arange(flat.shape[0], dtype=np.float64)[:, None] >= c * taus
+    found = ok.any(axis=0)
+    first = np.argmax(ok, axis=0)
+    window = np.where(found, first, -1).astype(np.int32)
+    tau = np.where(found, taus[first, np.arange(flat.shape[1])], taus[-1])
+    return tau.reshape(rho.shape[1:]), window.reshape(rho.shape[1:])
+
+
+def _chain_record(tau, window, rho, n, L, tol):
+    with np.errstate(invalid="ignore"):
+        reliable = (window >= 0) & (n >= tol * tau)
+    return ChainAutocorr(tau, window, reliable, rho, int(n), int(L))
+
+
+def chain_autocorr(chain, c: float = 5.0, tol: float = 50.0, max_lag: Optional[int] = None, first: int = 0) -> ChainAutocorr:
+    """The integrated autocorrelation time of every parameter of chain[rows, W, D] from row ``first`` on, in numpy, by direct sums (no
+    FFT): the two-pass mean of every walker's series, its lag sums c(l) = sum_t y[t] y[t + l] for l = 0 .. L, the sums pooled over the
+    walkers (one normalisation for the ensemble, so a walker that never moved adds zeros where emcee's per-walker normalisation gives
+    0 / 0), rho = C(l) / C(0) and Sokal's window with constant c.  L is ``max_lag`` or default_max_lag(n, c, tol).  The device estimate
+    (chain_autocorr_device) follows the same definition with every lag sum as one fma chain; the two differ by rounding alone."""
+    x = np.asarray(chain, dtype=np.float64)
+    if x.ndim != 3 or x.shape[1] < 1 or x.shape[2] < 1:
+        raise ValueError("chain autocorrelation: the chain must be [rows, nwalkers, ndim]")
+    first = _chain_first(x.shape[0], first)
+    n, W, D = x.shape[0] - first, x.shape[1], x.shape[2]
+    L = _chain_lags(n, c, tol, max_lag)
+    x = x[first:].reshape(n, W * D)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        y = x - chain_mean(x)
+        lag = np.empty((L + 1, W * D))
+        for l in range(L + 1):
+            lag[l] = np.sum(y[:n - l] * y[l:], axis=0)
+        pooled = np.cumsum(lag.reshape(L + 1, W, D), axis=1)[:, -1]  # (ascending w)
+        rho = pooled / pooled[0]
+    tau, window = sokal_window(rho, c)
+    bad = ~np.isfinite(pooled[0]) | (pooled[0] == 0.0)
+    return _chain_record(np.where(bad, np.nan, tau), np.where(bad, -1, window).astype(np.int32), rho, n, L, tol)
+
+
+def chain_autocorr_device(chain, c: float = 5.0, tol: float = 50.0, max_lag: Optional[int] = None, first: int = 0, device: int = 0,
+                          context=None, rho: bool = True) -> ChainAutocorr:
+    """chain_autocorr on a float64 torch tensor [rows, W, D] that lives on GPU ``device`` (vag_chain_autocorr_dev, on torch's current
+    stream): the chain is read where it is and only tau, the windows and, with ``rho``, rho come to the host.  A view whose last two
+    dimensions are contiguous is taken without a copy -- the cold rung ``chain[:, 0]`` of a tempered chain [rows, T, W, D] for
+    instance; anything else is refused.  ``context``: a (handle, lock) pair other than the device's shared context."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .fitting import on_current_stream
+    from .model import get_context
+    if not isinstance(chain, torch.Tensor) or chain.dtype != torch.float64 or chain.dim() != 3:
+        raise ValueError("chain autocorrelation: the chain must be a float64 torch tensor [rows, nwalkers, ndim]")
+    dev = torch.device("cuda", device)
+    if chain.device != dev:
+        raise ValueError(f"chain autocorrelation: the chain must be on {dev}, it is on {chain.device}")
+    rows, W, D = (int(v) for v in chain.shape)
+    if W < 1 or D < 1:
+        raise ValueError("chain autocorrelation: the chain must be [rows, nwalkers, ndim]")
+    first = _chain_first(rows, first)
+    n = rows - first
+    L = _chain_lags(n, c, tol, max_lag)
+    if chain.stride(2) != 1 or chain.stride(1) != D or chain.stride(0) < W * D:
+        raise ValueError("chain autocorrelation: the last two dimensions of the chain must be contiguous and the rows must not overlap "
+                         f"(strides {tuple(chain.stride())} of shape {tuple(chain.shape)}); make a contiguous copy")
+    lib = _lib.load()
+    entry = _lib.chain_entry(lib)
+    h, lock = get_context(device) if context is None else context
+    spec = _lib.ChainSpec(W, D, n, int(chain.stride(0)), L, float(c))
+    d_tau = torch.empty((D,), dtype=torch.float64, device=dev)
+    d_window = torch.empty((D,), dtype=torch.int32, device=dev)
+    d_rho = torch.empty((L + 1, D), dtype=torch.float64, device=dev) if rho else None
+    on_current_stream(lib, h, lock, dev, lambda: _lib.check(entry(
+        h, C.byref(spec), chain.data_ptr() + 8 * first * int(chain.stride(0)), d_rho.data_ptr() if rho else None, d_tau.data_ptr(),
+        d_window.data_ptr())))
+    return _chain_record(d_tau.cpu().numpy(), d_window.cpu().numpy(), d_rho.cpu().numpy() if rho else None, n, L, tol)
+
+
+def _empty_record(ndim):
+    return ChainAutocorr(np.full(ndim, np.nan), np.full(ndim, -1, dtype=np.int32), np.zeros(ndim, dtype=bool), None, 0, 0)
+
+
+class _ConvergenceMonitor:
+    """What the three device run drivers share of ``converge=``: where the chunks end, the estimate at a check, the final record."""
+
+    def __init__(self, converge, nsteps, nburn, thin, chunk, device, cold):
+        if converge is not None and not isinstance(converge, Convergence):
+            raise ValueError("converge must be a sampling.Convergence or None")
+        if int(nburn) != nburn or nburn < 0:
+            raise ValueError("nburn must be a whole number of steps >= 0")
+        self.rule, self.nsteps, self.first, self.thin, self.chunk = converge, int(nsteps), int(nburn) // thin, thin, chunk
+        self.device, self.cold = device, cold  # cold(chain, rows): the view [rows kept so far, W, D] the estimate reads
+        self.history, self.previous, self.last, self.last_step, self.converged = [], None, None, -1, False
+
+    def chunk_end(self, step0):
+        """The end of the chunk that starts at step0: a check lands after every `check` steps."""
+        end = min(step0 + self.chunk, self.nsteps)
+        if self.rule is not None:
+            end = min(end, (step0 // self.rule.check + 1) * self.rule.check)
+        return end
+
+    def estimate(self, chain, step):
+        rows = step // self.thin
+        rule = self.rule or Convergence()
+        if rows - self.first < 2:
+            self.last = _empty_record(int(chain.shape[-1]))
+        else:
+            self.last = chain_autocorr_device(self.cold(chain[:rows]), c=rule.c, tol=rule.tol, first=self.first, device=self.device,
+                                              rho=False)
+        self.last_step = step
+        return self.last
+
+    def stop(self, chain, step):
+        """After the chunk that ended at `step`: True when the run ends here."""
+        if self.rule is None or step % self.rule.check != 0:
+            return False
+        rec = self.estimate(chain, step)
+        self.history.append(rec.tau.copy())
+        self.converged = self.rule.met(rec.tau, rec.reliable, self.previous)
+        self.previous = rec.tau
+        return self.converged
+
+    def record(self, chain, step):
+        if self.last_step != step:
+            self.estimate(chain, step)
+        ndim = int(chain.shape[-1])
+        return ConvergedAutocorr(*self.last, self.converged, int(step), np.array(self.history).reshape(len(self.history), ndim), self.thin)
 
 
 def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: int, nburn: int = 0, seed: int = 0,
         loglike_fn: Optional[Callable] = None, center: Optional[np.ndarray] = None, spread: float = 0.1, sampler: str = "host",
-        ntemps: int = 8, beta_min: float = 1e-3, prior_rung: bool = True, moves=None):
+        ntemps: int = 8, beta_min: float = 1e-3, prior_rung: bool = True, moves=None, converge: Optional[Convergence] = None):
     """Convenience driver: uniform priors over the ParamDef boxes, stretch-move sampling on the device likelihood.
     Returns dict(samples[flat, ndim], log_prob[flat], acceptance, best) in sampler space (log10 for LOG parameters).
     ``sampler="host"``: run_stretch_move in numpy around one device call per half-step; ``"device"``: run_stretch_move_device, the
@@ -1062,9 +1304,25 @@ def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: i
     snooker move at 0.2, the reference's own mix) or a sequence of (name, weight) over MOVE_KINDS run_moves_device; ``"tempered"``: run_tempered_device on the ladder geometric_betas(ntemps, beta_min, prior_rung), `nwalkers` per
     temperature.  The keys above are then filled from the cold chain (beta = 1, log_prob = ln L + ln prior), and the dict also holds
     "betas", "log_like" (the mean of ln L per rung after the burn-in), "log_evidence" and "log_evidence_error"
-    (thermodynamic_evidence of those means: read its caveats) and "swap_fraction"."""
+    (thermodynamic_evidence of those means: read its caveats) and "swap_fraction".
+
+    Every sampler also returns "tau" (the integrated autocorrelation time of each parameter over the rows after `nburn`, in steps;
+    NaN when fewer than two rows are kept) and "tau_reliable" (a window was found and the kept rows number at least 50 tau, or
+    ``converge.tol`` tau): the device samplers from chain_autocorr_device on the chain in HBM ("tempered": the cold rung), the host
+    sampler from chain_autocorr.  ``converge=Convergence(...)`` (device samplers only) makes `nsteps` a maximum and stops the run by
+    that rule (run_stretch_move_device); the dict then also holds "converged" and "nsteps", the steps run."""
     if sampler not in ("host", "device", "tempered"):
         raise ValueError(f"unknown sampler {sampler!r}: 'host', 'device' or 'tempered'")
+    if converge is not None and sampler == "host":
+        raise ValueError("converge stops a run on the device: sampler='host' runs its fixed nsteps (sampler='device' or 'tempered')")
+    if converge is not None and not isinstance(converge, Convergence):
+        raise ValueError("converge must be a sampling.Convergence or None")
+
+    def tau_keys(rec, thin=1):
+        keys = {"tau": rec.tau * thin, "tau_reliable": rec.reliable}
+        if converge is not None:
+            keys.update(converged=rec.converged, nsteps=rec.steps)
+        return keys
     if sampler != "host" and loglike_fn is not None:
         raise ValueError(f"sampler={sampler!r} evaluates the fitter's own likelihood on the device: it cannot be combined with "
                          "loglike_fn (compose sampling.StretchMove or sampling.TemperedMove with your evaluator instead)")
@@ -1078,7 +1336,8 @@ def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: i
         betas = geometric_betas(ntemps, beta_min, prior_rung)
         _, lower, upper = fitter.build_spec(param_defs)
         pos0 = initial_positions(lower, upper, betas.size * nwalkers, rng, center=center, spread=spread).reshape(betas.size, nwalkers, -1)
-        chain, lnl, lnprior, acc, swap_fraction = run_tempered_device(fitter, param_defs, pos0, betas, nsteps, seed=seed)
+        chain, lnl, lnprior, acc, swap_fraction, rec = run_tempered_device(fitter, param_defs, pos0, betas, nsteps, seed=seed,
+                                                                           converge=converge, nburn=max(int(nburn), 0), _record=True)
         cold, logp = chain[:, 0], lnl[:, 0] + lnprior[:, 0]
         flat = cold[nburn:].reshape(-1, cold.shape[-1])
         flat_lp = logp[nburn:].reshape(-1)
@@ -1086,18 +1345,22 @@ def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: i
         ln_z, ln_z_err = thermodynamic_evidence(betas, log_like)
         return {"samples": flat, "log_prob": flat_lp, "acceptance": acc[0], "best": flat[np.argmax(flat_lp)], "chain": cold,
                 "betas": betas, "log_like": log_like, "log_evidence": ln_z, "log_evidence_error": ln_z_err,
-                "swap_fraction": swap_fraction}
+                "swap_fraction": swap_fraction, **tau_keys(rec)}
     _, lower, upper = fitter.build_spec(param_defs)
     if sampler == "device":
         pos0 = initial_positions(lower, upper, nwalkers, rng, center=center, spread=spread)
         if moves is None:
-            chain, logp, acc = run_stretch_move_device(fitter, param_defs, pos0, nsteps, seed=seed)
+            chain, logp, acc, rec = run_stretch_move_device(fitter, param_defs, pos0, nsteps, seed=seed, converge=converge,
+                                                            nburn=max(int(nburn), 0), _record=True)
         else:
-            chain, logp, acc = run_moves_device(fitter, param_defs, pos0, nsteps, moves=moves, seed=seed)
+            chain, logp, acc, rec = run_moves_device(fitter, param_defs, pos0, nsteps, moves=moves, seed=seed, converge=converge,
+                                                     nburn=max(int(nburn), 0), _record=True)
     else:
         log_prob_batch = fitter.make_log_prob_batch(param_defs, loglike_fn=loglike_fn)
         pos0 = initial_positions(lower, upper, nwalkers, rng, center=center, spread=spread)
         chain, logp, acc = run_stretch_move(log_prob_batch, pos0, nsteps, rng=rng)
+        kept = chain.shape[0] - min(max(int(nburn), 0), chain.shape[0])
+        rec = chain_autocorr(chain, first=chain.shape[0] - kept) if kept >= 2 else _empty_record(chain.shape[-1])
     flat = chain[nburn:].reshape(-1, chain.shape[-1])
     flat_lp = logp[nburn:].reshape(-1)
-    return {"samples": flat, "log_prob": flat_lp, "acceptance": acc, "best": flat[np.argmax(flat_lp)], "chain": chain}
+    return {"samples": flat, "log_prob": flat_lp, "acceptance": acc, "best": flat[np.argmax(flat_lp)], "chain": chain, **tau_keys(rec)}
