@@ -22,6 +22,14 @@ constexpr int FLUX_SPLIT_B = FLUX_THREADS / 64 - FLUX_SPLIT_A;      // the rest:
 constexpr int FLUX_SPLIT_TIMES = 2;                                 // requested times a B lane can own
 constexpr int FLUX_SPLIT_MAX_NT = FLUX_SPLIT_TIMES * FLUX_SPLIT_B * 64;
 constexpr int FLUX_SPLIT_MAX_NNU = 10;                              // accumulators per owned time
+// a / n (a, n > 0) from the estimate q = (int)((float)a * rcp_n) of the boundary loop's reciprocal: one compare-and-adjust each way,
+// so the quotient is exact for any estimate within one of it, whatever the last bit of the hardware's reciprocal
+// (tests/flux_quot_check.cpp: a = 384, every n in 1 .. 204, the reciprocal moved by up to four units in the last place)
+constexpr int flux_quot_adjust(int a, int n, int q) {
+    q -= q * n > a;
+    q += (q + 1) * n <= a;
+    return q;
+}
 
 // ---- the persistent launch and the split form: host thresholds ----
 constexpr int FLUX_PERSIST_MIN_PPB = 128;  // shortest items (rows per workgroup) the persistent form takes unforced (persist_plan)

@@ -758,6 +758,7 @@ VAG_DEV int sload_i32(const int* p) {
 }
 typedef int vag_v8i __attribute__((ext_vector_type(8)));
 typedef int vag_v4i __attribute__((ext_vector_type(4)));
+typedef int vag_v2i __attribute__((ext_vector_type(2)));
 struct RowGeo {
     double cos_th, sin_th, dth, cph, dph, cos_obs, sin_obs;
     int rep;
@@ -1564,6 +1565,12 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     // `work(n, j1, i1, j2, i2, tb0, tb1, tb2, eat_now)`: (j, i) of rows n + 1 and n + 2, the s_t buffers of rows n, n + 1, n + 2.  A row
     // n + 2 of another photon block is staged behind the barrier, when the A team is done with the present block; its EAT step
     // (`late_eat`) follows alone.  Both teams run this with the same block-uniform decisions, so their barriers pair up.
+#ifdef VAG_FLUX_STAMPS  // developer aid: where a wavefront's cycles go (profiles/flux_stamps.sh); c_rel is its last barrier release
+    long long c_rel = __builtin_readcyclecounter();
+#define VAG_STAMP_RELEASE() c_rel = __builtin_readcyclecounter()
+#else
+#define VAG_STAMP_RELEASE()
+#endif
     auto pipeline = [&](auto&& work, auto&& late_eat) {
         int j1 = p0 / n_phi_eff, i1 = p0 - j1 * n_phi_eff;
         int staged_rep = rep_at(j1);
@@ -1572,6 +1579,7 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
         __syncthreads();
         late_eat(j1, i1, 0, 0);
         __syncthreads();
+        VAG_STAMP_RELEASE();
         int tb0 = 2, tb1 = 0, tb2 = 1;
         for (int n = -1; n < n_rows; ++n) {
             int j2 = j1, i2 = i1 + 1;
@@ -1581,27 +1589,37 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
             const bool same = rep2 == staged_rep;
             work(n, j1, i1, j2, i2, tb0, tb1, tb2, have2 && same);
             __syncthreads();
+            VAG_STAMP_RELEASE();
             if (__builtin_expect(!same, 0)) {  // once per theta row
                 stage(rep2);
                 staged_rep = rep2;
                 __syncthreads();
                 late_eat(j2, i2, n + 2, tb2);
                 __syncthreads();
+                VAG_STAMP_RELEASE();
             }
             j1 = j2, i1 = i2;
             tb0 = tb1, tb1 = tb2, tb2 = tb2 == 2 ? 0 : tb2 + 1;
         }
     };
+#undef VAG_STAMP_RELEASE
 
+    // the window of the requested times is a constant of the item: in registers, not read from s_tobs again for every row
+    const double w_lo = a.lg2_t_obs[0], w_hi = a.lg2_t_obs[nt - 1];  // == s_tobs[0], s_tobs[nt - 1]
+#ifdef VAG_FLUX_STAMPS
+    long long c_pro_eat = 0;  // cycles from the end of an EAT wavefront's boundary loop (or its barrier release) to its first log2_tab_core
+#endif
     // EAT step of row r at (theta j, phi i) by the wavefronts FLUX_SPLIT_E0 .. + FLUX_SPLIT_E - 1: eat_row's expressions, rounding
     // for rounding; a wavefront's window counts go to its own pair of words (no atomics, nothing to clear)
     auto eat = [&](int j, int i, int r, int tb) {
         const int etid = tid - FLUX_SPLIT_E0 * 64, ew = wave - FLUX_SPLIT_E0;
         if (ew < 0) return;  // wavefront-uniform: the A wavefronts ahead of the EAT ones
-        const double w_lo = s_tobs[0], w_hi = s_tobs[nt - 1];
         const RowGeo g = sload_rowgeo(rg, rg_th, j, i);
         const double cos_v = g.cos_view();
         const double t_coeff = (1 - cos_v) * opz_over_c;
+#ifdef VAG_FLUX_STAMPS
+        c_pro_eat += __builtin_readcyclecounter() - c_rel;
+#endif
         double* st = s_t + tb * KS;
         double* sd = s_dop + (r & 1) * KS;
         int n_lt = 0, n_le = 0;
@@ -1626,23 +1644,24 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     if (a_team) {
         const int atid = tid;  // the A team is the first wavefronts
 #ifdef VAG_FLUX_STAMPS  // developer aid: cycles an A wavefront spends in the boundary loop, and its passes (profiles/flux_stamps.sh)
-        long long c_loop = 0;
+        long long c_loop = 0, c_pro = 0;  // c_pro: cycles from barrier release to the first boundary item
         int n_pass = 0, n_rows_done = 0;
 #endif
         auto spectra_of = [&](int n, int j1, int i1, int tb1) {
             const int r = n + 1;
             if (r >= n_rows) return;
             const double* s_tc = s_t + tb1 * KS;
-            const double row_t0 = s_tc[0], row_tN = s_tc[K - 1];
-            const double w_lo = s_tobs[0], w_hi = s_tobs[nt - 1];
+            // The row header in ONE LDS round trip: the ends of the row's lattice and the window words of the EAT wavefronts are
+            // requested together and pinned here.  Left alone the compiler sinks each read behind the branch before its use:
+            // three round trips in series at the head of every row (profiles/flux_prologue_ab.txt).
+            static_assert(NE == 2, "the window words of a row are read as two 8-byte words");
+            const vag_v2i* win = reinterpret_cast<const vag_v2i*>(s_win + (r & 1) * 2 * NE);
+            double row_t0 = s_tc[0], row_tN = s_tc[K - 1];
+            vag_v2i win0 = win[0], win1 = win[1];
+            asm volatile("" : "+v"(row_t0), "+v"(row_tN), "+v"(win0), "+v"(win1));
             if (row_tN < w_lo || row_t0 > w_hi) return;  // block-uniform: the B team skips the row too
-            const int* win = s_win + (r & 1) * 2 * NE;
-            int n_lt = 0, n_le = 0;
-#pragma unroll
-            for (int w = 0; w < NE; ++w) {
-                n_lt += __builtin_amdgcn_readfirstlane(win[2 * w]);
-                n_le += __builtin_amdgcn_readfirstlane(win[2 * w + 1]);
-            }
+            const int n_lt = __builtin_amdgcn_readfirstlane(win0[0]) + __builtin_amdgcn_readfirstlane(win1[0]);
+            const int n_le = __builtin_amdgcn_readfirstlane(win0[1]) + __builtin_amdgcn_readfirstlane(win1[1]);
             const int k_lo = n_lt > 0 ? n_lt - 1 : 0;
             const int k_hi = min(max(n_le, k_lo + 1), K - 1);
             const RowGeo g = sload_rowgeo(rg, rg_th, j1, i1);
@@ -1653,13 +1672,19 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
             const int nk = k_hi - k_lo + 1;
             const int total = nk * ((nnu + 1) >> 1);
             const float inv_nk = __builtin_amdgcn_rcpf((float)nk);
-            const int dq_l = AL / nk, dq_k = AL - dq_l * nk;
-            int lg = (int)(((float)atid + 0.5f) * inv_nk);
+            // AL / nk from the reciprocal the loop forms anyway (the scalar division was ~25 dependent instructions at the head of
+            // every row), exact by flux_quot_adjust; the lane's number is converted here (`at` is opaque: hoisted out of the rows,
+            // (float)atid + 0.5f was spilled and came back from scratch at the head of every row)
+            int at = atid;
+            asm volatile("" : "+v"(at));
+            const int dq_l = flux_quot_adjust(AL, nk, (int)((float)AL * inv_nk)), dq_k = AL - dq_l * nk;
+            int lg = (int)(((float)at + 0.5f) * inv_nk);
             int kk = atid - __mul24(lg, nk);
             int bofs = __mul24(lg, 2 * KS);
             const int top = (nnu - 1) * KS;
 #ifdef VAG_FLUX_STAMPS
             const long long c_in = __builtin_readcyclecounter();
+            c_pro += c_in - c_rel;
             n_pass += (total - (atid & ~63) + AL - 1) / AL;  // passes this wavefront makes (its first lane's count)
             ++n_rows_done;
 #endif
@@ -1694,7 +1719,8 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
                 }
             }
 #ifdef VAG_FLUX_STAMPS
-            c_loop += __builtin_readcyclecounter() - c_in;
+            c_rel = __builtin_readcyclecounter();  // the EAT step's prologue counts from here
+            c_loop += c_rel - c_in;
 #endif
         };
         auto spectra = [&](int n, int j1, int i1, int j2, int i2, int, int tb1, int tb2, bool eat_now) {
@@ -1707,12 +1733,11 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
         pipeline(spectra, eat);
 #ifdef VAG_FLUX_STAMPS
         if (m == 0 && blk == 1 && lane == 0)
-            printf("split A wave %d rows %d passes %d boundary-loop cycles %lld  per pass %lld  item %lld\n", wave, n_rows_done, n_pass, c_loop,
-                   c_loop / max(n_pass, 1), (long long)__builtin_readcyclecounter() - c_item);
+            printf("split A wave %d rows %d passes %d boundary-loop cycles %lld  per pass %lld  item %lld  prologue %lld  eat-prologue %lld\n", wave,
+                   n_rows_done, n_pass, c_loop, c_loop / max(n_pass, 1), (long long)__builtin_readcyclecounter() - c_item, c_pro, c_pro_eat);
 #endif
     } else {
         const int btid = tid - AL;
-        const double w_lo = a.lg2_t_obs[0], w_hi = a.lg2_t_obs[nt - 1];  // == s_tobs[0], s_tobs[nt - 1]
         double acc[FLUX_SPLIT_TIMES][FLUX_SPLIT_MAX_NNU];
         int hint[FLUX_SPLIT_TIMES];
         double tq[FLUX_SPLIT_TIMES];
@@ -1724,7 +1749,7 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
             for (int l = 0; l < FLUX_SPLIT_MAX_NNU; ++l) acc[o][l] = 0;
         }
 #ifdef VAG_FLUX_STAMPS
-        long long c_interp = 0;
+        long long c_interp = 0, c_pro = 0;  // c_pro: cycles from barrier release to the first bracket
         const long long c_item = __builtin_readcyclecounter();
 #endif
         auto interp = [&](int n, int, int, int, int, int tb0, int, int, bool) {
@@ -1739,6 +1764,9 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
                     for (int o = 0; o < FLUX_SPLIT_TIMES; ++o) hint[o] = 0;
                 } else {
                     const double* sB = s_B + (n & 1) * nnu * KS;
+#ifdef VAG_FLUX_STAMPS
+                    c_pro += __builtin_readcyclecounter() - c_rel;
+#endif
 #pragma unroll
                     for (int o = 0; o < FLUX_SPLIT_TIMES; ++o) {
                         const bool owned = btid + o * BL < nt;
@@ -1780,7 +1808,8 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
         pipeline(interp, [](int, int, int, int) {});
 #ifdef VAG_FLUX_STAMPS
         if (m == 0 && blk == 1 && lane == 0)
-            printf("split B wave %d interpolation cycles %lld  item %lld\n", wave, c_interp, (long long)__builtin_readcyclecounter() - c_item);
+            printf("split B wave %d interpolation cycles %lld  item %lld  prologue %lld\n", wave, c_interp, (long long)__builtin_readcyclecounter() - c_item,
+                   c_pro);
 #endif
         // partial grid of this workgroup, stored [l][idx] like the reference's F_nu (nu outer)
         double* my_partial = a.partial + ((size_t)m * a.max_blocks + blk) * ((size_t)nt * nnu);
