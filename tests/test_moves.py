@@ -12,11 +12,13 @@ differ by at most 2 h ulp(L) + ulp(h L) <= 4 h ulp(L), L the logarithm -- the bo
 1. proposals and factors of each kind over sizes, halves, steps beyond 2^32 and seeds beyond 2^32;
 2. decisions and chain bits on the Gaussian of tests/test_sampler_host.py with the reference mix, ln p formed on the host;
 3. vag_move_run_dev is the composition propose -> likelihood -> accept, whatever the chunk size; thinning; with the stretch move
-   alone it is vag_stretch_run_dev's chain; the smallest ensembles;
+   alone it is vag_stretch_run_dev's chain; the smallest ensembles; runs of the three entries of other sizes on one context;
 4. proposals that are not finite, a snooker walker on its z;
 5. Fitter.fit(sampler="device", moves="reference") end to end;
 6. the refusals of the raw C-ABI, the context usable afterwards, device memory back after vag_ctx_destroy."""
+import contextlib
 import ctypes as C
+import threading
 
 import numpy as np
 import pytest
@@ -26,6 +28,7 @@ import test_gpu_parity as tg
 import test_sampler as ts
 import test_sampler_host as sh
 import test_sky_visfit as tv
+import test_tempering as tt
 from vegasafterglow_amd import _lib, fitting, sampling
 from vegasafterglow_amd.fitting import _fma
 
@@ -221,6 +224,50 @@ def test_smallest_ensembles_are_the_composition(torch, c4, kind, nw, free):
     assert np.array_equal(logp[-1], c4.log_prob_batch(chain[-1], d)) and np.all(chain >= lo) and np.all(chain <= hi)
     partners = (sampling.snooker_proposals if kind == "snooker" else sampling.de_proposals)(pos0, 0, 0, 5)[2]
     assert all(sorted(row) == list(range(nw // 2, nw)) for row in partners.tolist())
+
+
+@contextlib.contextmanager
+def fresh_context():
+    """A new engine context in place of the process-wide one of device 0 (every call looks it up), destroyed on the way out."""
+    from vegasafterglow_amd import model
+    lib = _lib.load()
+    h = C.c_void_p()
+    _lib.check(lib.vag_ctx_create(0, C.byref(h)))
+    with model._ctx_lock:
+        shared = model._ctx.pop(0, None)
+        model._ctx[0] = (h, threading.RLock())
+    try:
+        yield
+    finally:
+        with model._ctx_lock:
+            del model._ctx[0]
+            if shared is not None:
+                model._ctx[0] = shared
+        lib.vag_ctx_destroy(h)
+
+
+def test_the_three_run_entries_share_their_scratch_without_a_trace(c4):
+    """One set of scratch buffers serves the three run entries, grown by whichever runs.  On one context, large, small, large: a
+    ladder of 3 x 8 walkers, a stretch run of 130 (a half of 65 straddles a wavefront), the snooker move alone on 6 walkers with one
+    free parameter (a half of 3), and the ladder again.  Every result is, array for array and bit for bit, that of the same call made
+    first on a context of its own: no run reads what another left in the scratch or past its own part of it."""
+    d3 = defs()
+    d1 = [P("theta_c", 0.02, 0.3)] + tv._c4_fixed(skip=("theta_c",))
+    ladder0, _, _ = tt.start(c4, d3, 3, 8, TRUTH)
+    pos130, _, _ = start(c4, d3, 130, TRUTH)
+    pos6, _, _ = start(c4, d1, 6, TRUTH[:1])
+    runs = [lambda: sampling.run_tempered_device(c4, d3, ladder0, tt.BETAS3, 2, seed=5, priors=tt.PRIORS),
+            lambda: sampling.run_stretch_move_device(c4, d3, pos130, 2, seed=5),
+            lambda: sampling.run_moves_device(c4, d1, pos6, 2, moves=ONLY["snooker"], seed=5)]
+    want = []
+    for run in runs:
+        with fresh_context():
+            want.append(run())
+    with fresh_context():
+        got = [runs[k]() for k in (0, 1, 2, 0)]
+    for g, w in zip(got, want + want[:1]):
+        assert len(g) == len(w) and all(np.array_equal(a, b) for a, b in zip(g, w))
+    assert all(np.all(np.isfinite(a)) for g in got for a in g)
 
 
 # ---------------------------------------------------------------- 4. what is not finite

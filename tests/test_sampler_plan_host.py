@@ -1,0 +1,50 @@
+"""The host-side decisions of the device sampler (csrc/vag_sampler_plan.h) under the host sanitizers: tests/sampler_plan_check.cpp is
+built with the system C++ compiler and AddressSanitizer + UndefinedBehaviorSanitizer linked in, and run as a child process.  The
+program holds every decision -- what the stretch, move-mix and tempered specs refuse and in which words, the ladder the kernels take,
+the kind of a step, what a run entry refuses of its arguments, the key, the half, workgroups, stored rows, exchange pairs and row
+offsets -- to literals worked out by hand from the entry points the decisions were moved out of, every threshold at its value and on
+each side; here: exit status 0 and one "ok" line per case.  No device, no library, nothing loaded into this process."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+CASES = ["common shape", "move spec", "move_kind", "tempered spec", "run arguments", "arithmetic"]
+STATIC = ["-static-libasan", "-static-libubsan"]  # g++ links its sanitizer runtimes dynamically unless told; clang++ statically, and knows no such flag
+
+
+def run(cmd):
+    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+
+
+@pytest.fixture(scope="module")
+def compile_cmd(tmp_path_factory):
+    """[compiler, flags...] that link the sanitizer runtimes into a binary, or a skip when the compiler cannot link a sanitized
+    hello-world at all."""
+    cxx = os.environ.get("CXX", "c++")
+    d = tmp_path_factory.mktemp("hello")
+    (d / "hello.cpp").write_text('#include <cstdio>\nint main() { std::puts("hello"); return 0; }\n')
+    out = ""
+    for extra in (STATIC, []):
+        try:
+            built = run([cxx] + FLAGS + extra + [str(d / "hello.cpp"), "-o", str(d / "hello")])
+        except OSError as e:
+            pytest.skip(f"{cxx} cannot be run: {e}")
+        if built.returncode == 0:
+            return [cxx] + FLAGS + extra
+        out = built.stdout
+    pytest.skip(f"{cxx} cannot link a hello-world with {FLAGS[3]}: {out[-300:]}")
+
+
+def test_the_sampler_decisions_hold_their_thresholds_under_asan_and_ubsan(compile_cmd, tmp_path):
+    exe = tmp_path / "sampler_plan_check"
+    built = run(compile_cmd + ["-Wall", "-Wextra", os.path.join(ROOT, "tests", "sampler_plan_check.cpp"), "-o", str(exe)])
+    assert built.returncode == 0, built.stdout
+    ran = run([str(exe)])
+    assert ran.returncode == 0, ran.stdout
+    lines = ran.stdout.splitlines()
+    for case in CASES:
+        assert f"ok {case}" in lines, (case, ran.stdout)
+    assert not any(ln.startswith("FAIL") for ln in lines), ran.stdout

@@ -213,12 +213,16 @@ class StretchSpec(C.Structure):  # vag_stretch_spec
 STRETCH_ENTRIES = ("vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev")
 
 
-def stretch_entry(lib, name):
-    """One of the device sampler's entry points, added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build)."""
+def _entry(lib, name, needs):
+    """An entry point added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build); `needs`: what needs it."""
     if not hasattr(lib, name):
-        raise RuntimeError(f"the loaded library has no {name}: the device sampler (sampling.StretchMove, run_stretch_move_device, "
-                           "fit(sampler='device')) needs a newer build")
+        raise RuntimeError(f"the loaded library has no {name}: {needs} a newer build")
     return getattr(lib, name)
+
+
+def stretch_entry(lib, name):
+    """One of the device sampler's entry points."""
+    return _entry(lib, name, "the device sampler (sampling.StretchMove, run_stretch_move_device, fit(sampler='device')) needs")
 
 
 class MoveSpec(C.Structure):  # vag_move_spec
@@ -231,11 +235,8 @@ MOVE_ENTRIES = ("vag_move_propose_dev", "vag_move_accept_dev", "vag_move_run_dev
 
 
 def move_entry(lib, name):
-    """One of the move-mix entry points, added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build)."""
-    if not hasattr(lib, name):
-        raise RuntimeError(f"the loaded library has no {name}: the DE and snooker moves (sampling.EnsembleMoves, run_moves_device, "
-                           "fit(sampler='device', moves=...)) need a newer build")
-    return getattr(lib, name)
+    """One of the move-mix entry points."""
+    return _entry(lib, name, "the DE and snooker moves (sampling.EnsembleMoves, run_moves_device, fit(sampler='device', moves=...)) need")
 
 
 class TemperedSpec(C.Structure):  # vag_tempered_spec; betas points into a host array the caller keeps
@@ -249,11 +250,9 @@ TEMPERED_ENTRIES = ("vag_loglike_split_dev", "vag_tempered_propose_dev", "vag_te
 
 
 def tempered_entry(lib, name):
-    """One of the parallel-tempering entry points, added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build)."""
-    if not hasattr(lib, name):
-        raise RuntimeError(f"the loaded library has no {name}: parallel tempering (sampling.TemperedMove, run_tempered_device, "
-                           "Fitter.log_like_and_prior_batch, fit(sampler='tempered')) needs a newer build")
-    return getattr(lib, name)
+    """One of the parallel-tempering entry points."""
+    return _entry(lib, name, "parallel tempering (sampling.TemperedMove, run_tempered_device, Fitter.log_like_and_prior_batch, "
+                  "fit(sampler='tempered')) needs")
 
 
 class ChainSpec(C.Structure):  # vag_chain_spec
@@ -265,11 +264,9 @@ CHAIN_SCRATCH_MAX = 1 << 30  # VAG_CHAIN_SCRATCH_MAX
 
 
 def chain_entry(lib, name="vag_chain_autocorr_dev"):
-    """The chain-autocorrelation entry point, added after ABI 13 and detected by symbol (VAG_LIB_PATH may name an older build)."""
-    if not hasattr(lib, name):
-        raise RuntimeError(f"the loaded library has no {name}: the device autocorrelation estimate (sampling.chain_autocorr_device, "
-                           "converge= of the device run drivers, the tau of fit(sampler='device')) needs a newer build")
-    return getattr(lib, name)
+    """The chain-autocorrelation entry point."""
+    return _entry(lib, name, "the device autocorrelation estimate (sampling.chain_autocorr_device, converge= of the device run drivers, "
+                  "the tau of fit(sampler='device')) needs")
 
 
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_LOG_UNIFORM, PRIOR_NONE, PRIOR_UNIFORM_RANGE = 0, 1, 2, 3, 4

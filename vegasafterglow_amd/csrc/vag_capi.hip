@@ -33,6 +33,7 @@
 #include "vag_sampler.h"
 #include "vag_tempering.h"
 #include "vag_moves.h"
+#include "vag_sampler_plan.h"
 #include "vag_chain_stats.h"
 #include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
 #include "vag_flux_plan.h"    // (host only: the launch decisions of the flux stage)
@@ -441,10 +442,8 @@ struct vag_ctx {
     DevBuf d_skyvis, d_skyuv;  // visibilities (vag_sky.h): a chunk's row-block partials + combined values, a chunk's baselines
     DevBuf d_skycen, d_skycmom;  // exact centroids (vag_sky.h): row-block partials, moments
     DevBuf d_visblk, d_vispart;  // visibility groups of the likelihood (their data: vis below): their 64-visibility blocks, chi^2 partials
-    DevBuf d_stretch_prop, d_stretch_lp;  // the device sampler (vag_stretch_run_dev): a half's proposals [half][ndim] and their ln p [half]
-    DevBuf d_temper_prop, d_temper_lnl, d_temper_lnprior;  // parallel tempering (vag_tempered_run_dev): all temperatures' proposals of a half [T][half][ndim], their ln L and ln prior [T][half]
+    DevBuf d_sampler_prop, d_sampler_fresh, d_sampler_aux;  // the device sampler's run entries (sampler_run), one set for the three moves, as large as the largest run so far: a half-step's proposals [nb][ndim], their ln p or ln L [nb], their Hastings factor or ln prior [nb]
     DevBuf d_chain_stats;  // chain autocorrelation (vag_chain_autocorr_dev): the means [S], the lag sums [L + 1][S], the pooled sums [L + 1][D]
-    DevBuf d_move_factor;  // the move mix (vag_move_run_dev): ln of the Hastings factor of a half's proposals [half]; the proposals and their ln p go through d_stretch_prop / d_stretch_lp
     DevBuf d_polspec, d_polstokes;  // polarization groups of the likelihood (their data: pol below): the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -744,7 +743,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_stretch_prop, &c->d_stretch_lp, &c->d_temper_prop, &c->d_temper_lnl, &c->d_temper_lnprior, &c->d_move_factor, &c->d_chain_stats})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_sampler_prop, &c->d_sampler_fresh, &c->d_sampler_aux, &c->d_chain_stats})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3893,184 +3892,163 @@ int vag_loglike_cov_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
     return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
-// ---- the device sampler (kernels: vag_sampler.h; the move: the public header) ----
+// ---- the device sampler: the stretch move, the move mix, parallel tempering (kernels: vag_sampler.h, vag_moves.h, vag_tempering.h;
+//      what the specs refuse and the arithmetic of the launches: vag_sampler_plan.h; the moves: the public header) ----
 
-static int stretch_spec_check(const vag_stretch_spec* sp) {  // (not null)
-    if (sp->ndim < 1 || sp->ndim > 16) return set_err(VAG_E_INVALID, "stretch move: ndim must be 1..16, got %d", sp->ndim);
-    if (sp->n_walkers < 2 * sp->ndim || (sp->n_walkers & 1))
-        return set_err(VAG_E_INVALID, "stretch move: need an even number of walkers, at least 2 * ndim = %d, got %d", 2 * sp->ndim, sp->n_walkers);
-    if (!std::isfinite(sp->a) || !(sp->a > 1.0)) return set_err(VAG_E_INVALID, "stretch move: the scale a must be finite and > 1, got %g", sp->a);
-    if (sp->thin < 1) return set_err(VAG_E_INVALID, "stretch move: thin must be >= 1, got %d", sp->thin);
+extern "C++" {  // (templates: this section lies within the extern "C" of the entry points)
+
+// A sampler kernel of one lane per item on the context's stream; the key of `seed` leads every such kernel's arguments.
+template <class Kernel, class... Args>
+static int sampler_launch(vag_ctx* c, Kernel kernel, long long items, uint64_t seed, Args... args) {
+    const SeedWords key = seed_words(seed);
+    hipLaunchKernelGGL(kernel, dim3(lane_groups(items)), dim3(STRETCH_LANES), 0, c->stream, key.lo, key.hi, args...);
+    HIPCHK(hipGetLastError());
     return VAG_OK;
 }
 
-static int stretch_propose(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int which, const double* d_pos, double* d_prop) {
-    const int half = sp->n_walkers / 2;
-    hipLaunchKernelGGL(vag_stretch_propose_kernel, dim3((half + STRETCH_LANES - 1) / STRETCH_LANES), dim3(STRETCH_LANES), 0, c->stream,
-                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), sp->a, (unsigned long long)step, which, half,
-                       sp->ndim, d_pos, d_prop);
-    HIPCHK(hipGetLastError());
+// The prologue of the seven building-block entries, in this order: lock, handoff, nulls (`given`: the context, the spec and every
+// buffer are there), the spec's checks, half (`who` null: the entry takes none), the device; then the launch.
+template <class Check, class Launch>
+static int sampler_entry(vag_ctx* c, bool given, const char* what, Check check, const char* who, int half, Launch launch) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!given) return set_err(VAG_E_INVALID, "null context, %s spec or buffer", what);
+    if (const int rc = check()) return rc;
+    if (const int rc = who ? half_check(who, half) : VAG_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return launch();
+}
+
+// the scratch of a half-step of nb proposals: one set for the three moves, grown by whichever runs
+struct SamplerScratch {
+    double* prop;   // the proposals [nb][ndim]
+    double* fresh;  // their ln p; under tempering their ln L [nb]
+    double* aux;    // the ln of their Hastings factor (the move mix), their ln prior (tempering) [nb]
+};
+
+// The steps step0 .. step0 + n_steps - 1 of a run entry whose arguments have passed their checks: the scans and the uploads once,
+// then per step and half propose, ONE likelihood call of the nb proposals, what the move runs behind it, accept; then what ends the
+// step.  Between the steps there is no copy to the host and no stream synchronisation.  accept and end_step are told whether the
+// step is stored and which row it fills.
+template <class Propose, class Behind, class Accept, class EndStep>
+static int sampler_run(vag_ctx* c, const vag_loglike_request* q, int ndim, int nb, int thin, bool storing, uint64_t step0, int n_steps,
+                       Propose propose, Behind behind, Accept accept, EndStep end_step) {
+    if (n_steps == 0) return VAG_OK;
+    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
+    int rc = fit_request_prepare(req);  // the scans, once per call of many steps
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    req.ndim = ndim;
+    rc = upload_blocks(c, req);  // and the uploads
+    if (rc) return rc;
+    if (c->d_sampler_prop.ensure(sizeof(double) * (size_t)nb * ndim)) return VAG_E_HIP;
+    if (c->d_sampler_fresh.ensure(sizeof(double) * (size_t)nb)) return VAG_E_HIP;
+    if (c->d_sampler_aux.ensure(sizeof(double) * (size_t)nb)) return VAG_E_HIP;
+    const SamplerScratch s{c->d_sampler_prop.as<double>(), c->d_sampler_fresh.as<double>(), c->d_sampler_aux.as<double>()};
+    size_t row = 0;  // stored rows so far
+    for (int k = 0; k < n_steps; ++k) {
+        const uint64_t step = step0 + (uint64_t)k;
+        const bool stored = storing && step_is_stored(step, thin);
+        for (int which = 0; which < 2; ++which) {
+            if ((rc = propose(step, which, s))) return rc;
+            if ((rc = loglike_call(c, req, s.prop, nb, ndim, s.fresh))) return rc;
+            if ((rc = behind(s))) return rc;
+            if ((rc = accept(step, which, s, stored, row))) return rc;
+        }
+        if ((rc = end_step(step, stored, row))) return rc;
+        if (stored) ++row;
+    }
     return VAG_OK;
+}
+static const auto no_hook = [](auto&&...) -> int { return VAG_OK; };  // a move with nothing to run there
+
+}  // extern "C++"
+
+// -- the stretch move --
+
+static int stretch_propose(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int which, const double* d_pos, double* d_prop) {
+    const int half = half_of(sp->n_walkers);
+    return sampler_launch(c, vag_stretch_propose_kernel, half, sp->seed, sp->a, (unsigned long long)step, which, half, sp->ndim, d_pos, d_prop);
 }
 
 static int stretch_accept(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int which, const double* d_prop, const double* d_lp_new,
                           double* d_pos, double* d_lp, int64_t* d_accepted, double* d_chain_row, double* d_logp_row) {
-    const int half = sp->n_walkers / 2;
-    hipLaunchKernelGGL(vag_stretch_accept_kernel, dim3((half + STRETCH_LANES - 1) / STRETCH_LANES), dim3(STRETCH_LANES), 0, c->stream,
-                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), sp->a, (unsigned long long)step, which, half,
-                       sp->ndim, d_prop, d_lp_new, d_pos, d_lp, reinterpret_cast<long long*>(d_accepted), d_chain_row, d_logp_row);
-    HIPCHK(hipGetLastError());
-    return VAG_OK;
+    const int half = half_of(sp->n_walkers);
+    return sampler_launch(c, vag_stretch_accept_kernel, half, sp->seed, sp->a, (unsigned long long)step, which, half, sp->ndim, d_prop,
+                          d_lp_new, d_pos, d_lp, reinterpret_cast<long long*>(d_accepted), d_chain_row, d_logp_row);
 }
 
 int vag_stretch_propose_dev(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c || !sp || !d_pos || !d_prop) return set_err(VAG_E_INVALID, "null context, stretch spec or buffer");
-    if (const int rc = stretch_spec_check(sp)) return rc;
-    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "stretch move: half must be 0 or 1, got %d", half);
-    HIPCHK(hipSetDevice(c->device));
-    return stretch_propose(c, sp, step, half, d_pos, d_prop);
+    return sampler_entry(c, c && sp && d_pos && d_prop, "stretch", [&] { return stretch_spec_check(sp); }, "stretch move", half,
+                         [&] { return stretch_propose(c, sp, step, half, d_pos, d_prop); });
 }
 
 int vag_stretch_accept_dev(vag_ctx* c, const vag_stretch_spec* sp, uint64_t step, int half, const double* d_prop, const double* d_lp_new,
                            double* d_pos, double* d_lp, int64_t* d_accepted) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c || !sp || !d_prop || !d_lp_new || !d_pos || !d_lp || !d_accepted)
-        return set_err(VAG_E_INVALID, "null context, stretch spec or buffer");
-    if (const int rc = stretch_spec_check(sp)) return rc;
-    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "stretch move: half must be 0 or 1, got %d", half);
-    HIPCHK(hipSetDevice(c->device));
-    return stretch_accept(c, sp, step, half, d_prop, d_lp_new, d_pos, d_lp, d_accepted, nullptr, nullptr);
+    return sampler_entry(c, c && sp && d_prop && d_lp_new && d_pos && d_lp && d_accepted, "stretch", [&] { return stretch_spec_check(sp); },
+                         "stretch move", half,
+                         [&] { return stretch_accept(c, sp, step, half, d_prop, d_lp_new, d_pos, d_lp, d_accepted, nullptr, nullptr); });
 }
 
+// (its own kernels, not the move mix with weights (1, 0, 0): the two round the acceptance margin differently)
 int vag_stretch_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_stretch_spec* sp, uint64_t step0, int n_steps, double* d_pos,
                         double* d_lp, int64_t* d_accepted, double* d_chain, double* d_logp) {
     ApiLock api_lock(c);
     HandoffScope handoff(c);
     if (!c || !q || !q->spec || !sp || !d_pos || !d_lp || !d_accepted)
         return set_err(VAG_E_INVALID, "null context, request, fit spec, stretch spec or buffer");
-    if ((d_chain == nullptr) != (d_logp == nullptr)) return set_err(VAG_E_INVALID, "stretch move: the chain and its ln p are stored together or not at all");
+    if (const int rc = run_chain_check("stretch move", "the chain and its ln p", (d_chain != nullptr) + (d_logp != nullptr), 2)) return rc;
     if (const int rc = stretch_spec_check(sp)) return rc;
-    if (sp->ndim != q->spec->ndim)
-        return set_err(VAG_E_INVALID, "stretch move: ndim %d is not the fit spec's %d", sp->ndim, q->spec->ndim);
-    if (n_steps < 0) return set_err(VAG_E_INVALID, "stretch move: n_steps must be >= 0, got %d", n_steps);
-    if (n_steps == 0) return VAG_OK;
-    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
-    int rc = fit_request_prepare(req);  // the scans, once per call of many steps
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const int ndim = sp->ndim, nw = sp->n_walkers, half = nw / 2;
-    req.ndim = ndim;
-    rc = upload_blocks(c, req);  // and the uploads
-    if (rc) return rc;
-    if (c->d_stretch_prop.ensure(sizeof(double) * (size_t)half * ndim)) return VAG_E_HIP;
-    if (c->d_stretch_lp.ensure(sizeof(double) * (size_t)half)) return VAG_E_HIP;
-    double* d_prop = c->d_stretch_prop.as<double>();
-    double* d_lp_new = c->d_stretch_lp.as<double>();
-    size_t row = 0;  // stored rows so far
-    for (int k = 0; k < n_steps; ++k) {
-        const uint64_t step = step0 + (uint64_t)k;
-        const bool stored = d_chain && (step + 1) % (uint64_t)sp->thin == 0;
-        for (int which = 0; which < 2; ++which) {
-            if ((rc = stretch_propose(c, sp, step, which, d_pos, d_prop))) return rc;
-            if ((rc = loglike_call(c, req, d_prop, half, ndim, d_lp_new))) return rc;
-            if ((rc = stretch_accept(c, sp, step, which, d_prop, d_lp_new, d_pos, d_lp, d_accepted,
-                                     stored ? d_chain + row * (size_t)nw * ndim : nullptr, stored ? d_logp + row * (size_t)nw : nullptr)))
-                return rc;
-        }
-        if (stored) ++row;
-    }
-    return VAG_OK;
+    if (const int rc = run_steps_check("stretch move", sp->ndim, q->spec->ndim, n_steps)) return rc;
+    const int nw = sp->n_walkers, ndim = sp->ndim;
+    return sampler_run(
+        c, q, ndim, half_of(nw), sp->thin, d_chain != nullptr, step0, n_steps,
+        [&](uint64_t step, int which, const SamplerScratch& s) { return stretch_propose(c, sp, step, which, d_pos, s.prop); }, no_hook,
+        [&](uint64_t step, int which, const SamplerScratch& s, bool stored, size_t row) {
+            return stretch_accept(c, sp, step, which, s.prop, s.fresh, d_pos, d_lp, d_accepted,
+                                  stored ? d_chain + ensemble_row_offset(row, nw, ndim) : nullptr,
+                                  stored ? d_logp + ensemble_row_offset(row, nw, 1) : nullptr);
+        },
+        no_hook);
 }
 
-// ---- the move mix: stretch, differential evolution, snooker (kernels and the choice: vag_moves.h; the moves: the public header) ----
-
-static_assert(VAG_MOVE_STRETCH == MOVE_STRETCH && VAG_MOVE_DE == MOVE_DE && VAG_MOVE_SNOOKER == MOVE_SNOOKER, "the public kinds are the header's");
-
-static int move_spec_check(const vag_move_spec* sp) {  // (not null)
-    const vag_stretch_spec one{sp->seed, sp->a, sp->n_walkers, sp->ndim, sp->thin};
-    if (const int rc = stretch_spec_check(&one)) return rc;
-    double sum = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        if (!std::isfinite(sp->weights[k]) || sp->weights[k] < 0.0)
-            return set_err(VAG_E_INVALID, "move mix: weight %d must be finite and >= 0, got %g", k, sp->weights[k]);
-        sum += sp->weights[k];
-    }
-    if (!(sum > 0.0) || !std::isfinite(sum)) return set_err(VAG_E_INVALID, "move mix: the weights must have a finite sum > 0");
-    const int half = sp->n_walkers / 2;
-    if (sp->weights[MOVE_DE] > 0.0 && half < 2)
-        return set_err(VAG_E_INVALID, "move mix: the DE move needs two walkers of the other half, n_walkers >= 4, got %d", sp->n_walkers);
-    if (sp->weights[MOVE_SNOOKER] > 0.0 && half < 3)
-        return set_err(VAG_E_INVALID, "move mix: the snooker move needs three walkers of the other half, n_walkers >= 6, got %d", sp->n_walkers);
-    if (!std::isfinite(sp->gamma0) || sp->gamma0 < 0.0)
-        return set_err(VAG_E_INVALID, "move mix: gamma0 must be finite and >= 0 (0: 2.38 / sqrt(2 ndim)), got %g", sp->gamma0);
-    if (!std::isfinite(sp->sigma)) return set_err(VAG_E_INVALID, "move mix: sigma must be finite, got %g", sp->sigma);
-    if (!std::isfinite(sp->gamma_snooker)) return set_err(VAG_E_INVALID, "move mix: gamma_snooker must be finite, got %g", sp->gamma_snooker);
-    return VAG_OK;
-}
-
-// the kind of `step`, chosen on the host: the kernels do not branch on it
-static int move_kind(const vag_move_spec* sp, uint64_t step) {
-    const double u = move_choice_uniform((uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), (unsigned long long)step);
-    return move_choice(u, sp->weights[MOVE_STRETCH], sp->weights[MOVE_DE], sp->weights[MOVE_SNOOKER]);
-}
+// -- the move mix: stretch, differential evolution, snooker; the kind of a step is chosen here, so no kernel branches on it --
 
 static int move_propose(vag_ctx* c, const vag_move_spec* sp, uint64_t step, int which, const double* d_pos, double* d_prop,
                         double* d_factor) {
-    const int half = sp->n_walkers / 2;
-    const dim3 groups((half + STRETCH_LANES - 1) / STRETCH_LANES), lanes(STRETCH_LANES);
-    const uint32_t seed_lo = (uint32_t)(sp->seed & 0xffffffffu), seed_hi = (uint32_t)(sp->seed >> 32);
+    const int half = half_of(sp->n_walkers);
     switch (move_kind(sp, step)) {
         case MOVE_STRETCH:
-            hipLaunchKernelGGL(vag_move_stretch_propose_kernel, groups, lanes, 0, c->stream, seed_lo, seed_hi, sp->a,
-                               (unsigned long long)step, which, half, sp->ndim, d_pos, d_prop, d_factor);
-            break;
+            return sampler_launch(c, vag_move_stretch_propose_kernel, half, sp->seed, sp->a, (unsigned long long)step, which, half, sp->ndim,
+                                  d_pos, d_prop, d_factor);
         case MOVE_DE:
-            hipLaunchKernelGGL(vag_de_propose_kernel, groups, lanes, 0, c->stream, seed_lo, seed_hi,
-                               sp->gamma0 > 0.0 ? sp->gamma0 : de_gamma0(sp->ndim), sp->sigma, (unsigned long long)step, which, half,
-                               sp->ndim, d_pos, d_prop, d_factor);
-            break;
+            return sampler_launch(c, vag_de_propose_kernel, half, sp->seed, sp->gamma0 > 0.0 ? sp->gamma0 : de_gamma0(sp->ndim), sp->sigma,
+                                  (unsigned long long)step, which, half, sp->ndim, d_pos, d_prop, d_factor);
         default:
-            hipLaunchKernelGGL(vag_snooker_propose_kernel, groups, lanes, 0, c->stream, seed_lo, seed_hi, sp->gamma_snooker,
-                               (unsigned long long)step, which, half, sp->ndim, d_pos, d_prop, d_factor);
+            return sampler_launch(c, vag_snooker_propose_kernel, half, sp->seed, sp->gamma_snooker, (unsigned long long)step, which, half,
+                                  sp->ndim, d_pos, d_prop, d_factor);
     }
-    HIPCHK(hipGetLastError());
-    return VAG_OK;
 }
 
 static int move_accept(vag_ctx* c, const vag_move_spec* sp, uint64_t step, int which, const double* d_prop, const double* d_factor,
                        const double* d_lp_new, double* d_pos, double* d_lp, int64_t* d_accepted, double* d_chain_row, double* d_logp_row) {
-    const int half = sp->n_walkers / 2;
-    hipLaunchKernelGGL(vag_move_accept_kernel, dim3((half + STRETCH_LANES - 1) / STRETCH_LANES), dim3(STRETCH_LANES), 0, c->stream,
-                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), (unsigned long long)step, which, half, sp->ndim,
-                       d_prop, d_factor, d_lp_new, d_pos, d_lp, reinterpret_cast<long long*>(d_accepted), d_chain_row, d_logp_row);
-    HIPCHK(hipGetLastError());
-    return VAG_OK;
+    const int half = half_of(sp->n_walkers);
+    return sampler_launch(c, vag_move_accept_kernel, half, sp->seed, (unsigned long long)step, which, half, sp->ndim, d_prop, d_factor,
+                          d_lp_new, d_pos, d_lp, reinterpret_cast<long long*>(d_accepted), d_chain_row, d_logp_row);
 }
 
 int vag_move_propose_dev(vag_ctx* c, const vag_move_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop,
                          double* d_factor) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c || !sp || !d_pos || !d_prop || !d_factor) return set_err(VAG_E_INVALID, "null context, move spec or buffer");
-    if (const int rc = move_spec_check(sp)) return rc;
-    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "move mix: half must be 0 or 1, got %d", half);
-    HIPCHK(hipSetDevice(c->device));
-    return move_propose(c, sp, step, half, d_pos, d_prop, d_factor);
+    return sampler_entry(c, c && sp && d_pos && d_prop && d_factor, "move", [&] { return move_spec_check(sp); }, "move mix", half,
+                         [&] { return move_propose(c, sp, step, half, d_pos, d_prop, d_factor); });
 }
 
 int vag_move_accept_dev(vag_ctx* c, const vag_move_spec* sp, uint64_t step, int half, const double* d_prop, const double* d_factor,
                         const double* d_lp_new, double* d_pos, double* d_lp, int64_t* d_accepted) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c || !sp || !d_prop || !d_factor || !d_lp_new || !d_pos || !d_lp || !d_accepted)
-        return set_err(VAG_E_INVALID, "null context, move spec or buffer");
-    if (const int rc = move_spec_check(sp)) return rc;
-    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "move mix: half must be 0 or 1, got %d", half);
-    HIPCHK(hipSetDevice(c->device));
-    return move_accept(c, sp, step, half, d_prop, d_factor, d_lp_new, d_pos, d_lp, d_accepted, nullptr, nullptr);
+    return sampler_entry(c, c && sp && d_prop && d_factor && d_lp_new && d_pos && d_lp && d_accepted, "move",
+                         [&] { return move_spec_check(sp); }, "move mix", half, [&] {
+                             return move_accept(c, sp, step, half, d_prop, d_factor, d_lp_new, d_pos, d_lp, d_accepted, nullptr, nullptr);
+                         });
 }
 
 int vag_move_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_move_spec* sp, uint64_t step0, int n_steps, double* d_pos,
@@ -4079,43 +4057,22 @@ int vag_move_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_move_sp
     HandoffScope handoff(c);
     if (!c || !q || !q->spec || !sp || !d_pos || !d_lp || !d_accepted)
         return set_err(VAG_E_INVALID, "null context, request, fit spec, move spec or buffer");
-    if ((d_chain == nullptr) != (d_logp == nullptr)) return set_err(VAG_E_INVALID, "move mix: the chain and its ln p are stored together or not at all");
+    if (const int rc = run_chain_check("move mix", "the chain and its ln p", (d_chain != nullptr) + (d_logp != nullptr), 2)) return rc;
     if (const int rc = move_spec_check(sp)) return rc;
-    if (sp->ndim != q->spec->ndim)
-        return set_err(VAG_E_INVALID, "move mix: ndim %d is not the fit spec's %d", sp->ndim, q->spec->ndim);
-    if (n_steps < 0) return set_err(VAG_E_INVALID, "move mix: n_steps must be >= 0, got %d", n_steps);
-    if (n_steps == 0) return VAG_OK;
-    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
-    int rc = fit_request_prepare(req);  // the scans, once per call of many steps
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const int ndim = sp->ndim, nw = sp->n_walkers, half = nw / 2;
-    req.ndim = ndim;
-    rc = upload_blocks(c, req);  // and the uploads
-    if (rc) return rc;
-    if (c->d_stretch_prop.ensure(sizeof(double) * (size_t)half * ndim)) return VAG_E_HIP;
-    if (c->d_stretch_lp.ensure(sizeof(double) * (size_t)half)) return VAG_E_HIP;
-    if (c->d_move_factor.ensure(sizeof(double) * (size_t)half)) return VAG_E_HIP;
-    double* d_prop = c->d_stretch_prop.as<double>();
-    double* d_lp_new = c->d_stretch_lp.as<double>();
-    double* d_factor = c->d_move_factor.as<double>();
-    size_t row = 0;  // stored rows so far
-    for (int k = 0; k < n_steps; ++k) {
-        const uint64_t step = step0 + (uint64_t)k;
-        const bool stored = d_chain && (step + 1) % (uint64_t)sp->thin == 0;
-        for (int which = 0; which < 2; ++which) {
-            if ((rc = move_propose(c, sp, step, which, d_pos, d_prop, d_factor))) return rc;
-            if ((rc = loglike_call(c, req, d_prop, half, ndim, d_lp_new))) return rc;
-            if ((rc = move_accept(c, sp, step, which, d_prop, d_factor, d_lp_new, d_pos, d_lp, d_accepted,
-                                  stored ? d_chain + row * (size_t)nw * ndim : nullptr, stored ? d_logp + row * (size_t)nw : nullptr)))
-                return rc;
-        }
-        if (stored) ++row;
-    }
-    return VAG_OK;
+    if (const int rc = run_steps_check("move mix", sp->ndim, q->spec->ndim, n_steps)) return rc;
+    const int nw = sp->n_walkers, ndim = sp->ndim;
+    return sampler_run(
+        c, q, ndim, half_of(nw), sp->thin, d_chain != nullptr, step0, n_steps,
+        [&](uint64_t step, int which, const SamplerScratch& s) { return move_propose(c, sp, step, which, d_pos, s.prop, s.aux); }, no_hook,
+        [&](uint64_t step, int which, const SamplerScratch& s, bool stored, size_t row) {
+            return move_accept(c, sp, step, which, s.prop, s.aux, s.fresh, d_pos, d_lp, d_accepted,
+                               stored ? d_chain + ensemble_row_offset(row, nw, ndim) : nullptr,
+                               stored ? d_logp + ensemble_row_offset(row, nw, 1) : nullptr);
+        },
+        no_hook);
 }
 
-// ---- parallel tempering (kernels: vag_tempering.h; the move: the public header) ----
+// -- parallel tempering --
 
 // ln L and ln prior of the last likelihood call's nb walkers apart, from what loglike_body leaves by evaluation slot
 static int fit_split(vag_ctx* c, int nb, double* d_lnl, double* d_lnprior) {
@@ -4137,96 +4094,51 @@ int vag_loglike_split_dev(vag_ctx* c, const vag_loglike_request* q, const double
     return fit_split(c, nb, d_lnl, d_lnprior);
 }
 
-static_assert(VAG_TEMPER_MAX == VAG_TEMPER_MAX_RUNGS, "the public ladder limit is the kernels'");
-
-// the checks of a tempered spec (not null); fills the ladder the kernels take by value
-static int tempered_spec_check(const vag_tempered_spec* sp, TemperLadder& ladder) {
-    const vag_stretch_spec one{sp->seed, sp->a, sp->n_walkers, sp->ndim, sp->thin};
-    if (const int rc = stretch_spec_check(&one)) return rc;
-    if (sp->n_temps < 1 || sp->n_temps > VAG_TEMPER_MAX)
-        return set_err(VAG_E_INVALID, "tempering: n_temps must be 1..%d, got %d", VAG_TEMPER_MAX, sp->n_temps);
-    if ((long long)sp->n_temps * sp->n_walkers > (1ll << 30))
-        return set_err(VAG_E_INVALID, "tempering: n_temps * n_walkers must not exceed 2^30, got %lld", (long long)sp->n_temps * sp->n_walkers);
-    if (!sp->betas) return set_err(VAG_E_INVALID, "tempering: null betas");
-    if (sp->betas[0] != 1.0) return set_err(VAG_E_INVALID, "tempering: betas[0] must be 1, got %g", sp->betas[0]);
-    for (int t = 0; t < VAG_TEMPER_MAX; ++t) ladder.beta[t] = 0.0;
-    for (int t = 0; t < sp->n_temps; ++t) {
-        const double b = sp->betas[t];
-        if (!std::isfinite(b) || b < 0.0 || (t > 0 && !(b < sp->betas[t - 1])))
-            return set_err(VAG_E_INVALID, "tempering: betas must be finite, strictly descending and >= 0; betas[%d] = %g", t, b);
-        ladder.beta[t] = b;
-    }
-    return VAG_OK;
-}
-
-static inline dim3 tempered_groups(long long items) { return dim3((unsigned)((items + STRETCH_LANES - 1) / STRETCH_LANES)); }
-
 static int tempered_propose(vag_ctx* c, const vag_tempered_spec* sp, uint64_t step, int which, const double* d_pos, double* d_prop) {
-    const int half = sp->n_walkers / 2;
-    hipLaunchKernelGGL(vag_tempered_propose_kernel, tempered_groups((long long)sp->n_temps * half), dim3(STRETCH_LANES), 0, c->stream,
-                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), sp->a, (unsigned long long)step, which, half,
-                       sp->ndim, sp->n_temps, d_pos, d_prop);
-    HIPCHK(hipGetLastError());
-    return VAG_OK;
+    const int half = half_of(sp->n_walkers);
+    return sampler_launch(c, vag_tempered_propose_kernel, (long long)sp->n_temps * half, sp->seed, sp->a, (unsigned long long)step, which,
+                          half, sp->ndim, sp->n_temps, d_pos, d_prop);
 }
 
 static int tempered_accept(vag_ctx* c, const vag_tempered_spec* sp, const TemperLadder& ladder, uint64_t step, int which,
                            const double* d_prop, const double* d_lnl_new, const double* d_lnprior_new, double* d_pos, double* d_lnl,
                            double* d_lnprior, int64_t* d_accepted) {
-    const int half = sp->n_walkers / 2;
-    hipLaunchKernelGGL(vag_tempered_accept_kernel, tempered_groups((long long)sp->n_temps * half), dim3(STRETCH_LANES), 0, c->stream,
-                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), sp->a, (unsigned long long)step, which, half,
-                       sp->ndim, sp->n_temps, ladder, d_prop, d_lnl_new, d_lnprior_new, d_pos, d_lnl, d_lnprior,
-                       reinterpret_cast<long long*>(d_accepted));
-    HIPCHK(hipGetLastError());
-    return VAG_OK;
+    const int half = half_of(sp->n_walkers);
+    return sampler_launch(c, vag_tempered_accept_kernel, (long long)sp->n_temps * half, sp->seed, sp->a, (unsigned long long)step, which,
+                          half, sp->ndim, sp->n_temps, ladder, d_prop, d_lnl_new, d_lnprior_new, d_pos, d_lnl, d_lnprior,
+                          reinterpret_cast<long long*>(d_accepted));
 }
 
 static int tempered_swap(vag_ctx* c, const vag_tempered_spec* sp, const TemperLadder& ladder, uint64_t step, double* d_pos, double* d_lnl,
                          double* d_lnprior, int64_t* d_swapped) {
-    const int n_pairs = (sp->n_temps - (int)(step & 1u)) / 2;  // the pairs (t, t + 1) with t + step even
+    const int n_pairs = swap_pairs(sp->n_temps, step);
     if (n_pairs <= 0) return VAG_OK;
-    hipLaunchKernelGGL(vag_tempered_swap_kernel, tempered_groups((long long)n_pairs * sp->n_walkers), dim3(STRETCH_LANES), 0, c->stream,
-                       (uint32_t)(sp->seed & 0xffffffffu), (uint32_t)(sp->seed >> 32), (unsigned long long)step, sp->n_walkers, sp->ndim,
-                       n_pairs, ladder, d_pos, d_lnl, d_lnprior, reinterpret_cast<long long*>(d_swapped));
-    HIPCHK(hipGetLastError());
-    return VAG_OK;
+    return sampler_launch(c, vag_tempered_swap_kernel, (long long)n_pairs * sp->n_walkers, sp->seed, (unsigned long long)step,
+                          sp->n_walkers, sp->ndim, n_pairs, ladder, d_pos, d_lnl, d_lnprior, reinterpret_cast<long long*>(d_swapped));
 }
 
 int vag_tempered_propose_dev(vag_ctx* c, const vag_tempered_spec* sp, uint64_t step, int half, const double* d_pos, double* d_prop) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c || !sp || !d_pos || !d_prop) return set_err(VAG_E_INVALID, "null context, tempered spec or buffer");
     TemperLadder ladder;
-    if (const int rc = tempered_spec_check(sp, ladder)) return rc;
-    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "tempering: half must be 0 or 1, got %d", half);
-    HIPCHK(hipSetDevice(c->device));
-    return tempered_propose(c, sp, step, half, d_pos, d_prop);
+    return sampler_entry(c, c && sp && d_pos && d_prop, "tempered", [&] { return tempered_spec_check(sp, ladder); }, "tempering", half,
+                         [&] { return tempered_propose(c, sp, step, half, d_pos, d_prop); });
 }
 
 int vag_tempered_accept_dev(vag_ctx* c, const vag_tempered_spec* sp, uint64_t step, int half, const double* d_prop,
                             const double* d_lnl_new, const double* d_lnprior_new, double* d_pos, double* d_lnl, double* d_lnprior,
                             int64_t* d_accepted) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c || !sp || !d_prop || !d_lnl_new || !d_lnprior_new || !d_pos || !d_lnl || !d_lnprior || !d_accepted)
-        return set_err(VAG_E_INVALID, "null context, tempered spec or buffer");
     TemperLadder ladder;
-    if (const int rc = tempered_spec_check(sp, ladder)) return rc;
-    if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "tempering: half must be 0 or 1, got %d", half);
-    HIPCHK(hipSetDevice(c->device));
-    return tempered_accept(c, sp, ladder, step, half, d_prop, d_lnl_new, d_lnprior_new, d_pos, d_lnl, d_lnprior, d_accepted);
+    return sampler_entry(c, c && sp && d_prop && d_lnl_new && d_lnprior_new && d_pos && d_lnl && d_lnprior && d_accepted, "tempered",
+                         [&] { return tempered_spec_check(sp, ladder); }, "tempering", half, [&] {
+                             return tempered_accept(c, sp, ladder, step, half, d_prop, d_lnl_new, d_lnprior_new, d_pos, d_lnl, d_lnprior,
+                                                    d_accepted);
+                         });
 }
 
 int vag_tempered_swap_dev(vag_ctx* c, const vag_tempered_spec* sp, uint64_t step, double* d_pos, double* d_lnl, double* d_lnprior,
                           int64_t* d_swapped) {
-    ApiLock api_lock(c);
-    HandoffScope handoff(c);
-    if (!c || !sp || !d_pos || !d_lnl || !d_lnprior || !d_swapped) return set_err(VAG_E_INVALID, "null context, tempered spec or buffer");
     TemperLadder ladder;
-    if (const int rc = tempered_spec_check(sp, ladder)) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    return tempered_swap(c, sp, ladder, step, d_pos, d_lnl, d_lnprior, d_swapped);
+    return sampler_entry(c, c && sp && d_pos && d_lnl && d_lnprior && d_swapped, "tempered", [&] { return tempered_spec_check(sp, ladder); },
+                         nullptr, 0, [&] { return tempered_swap(c, sp, ladder, step, d_pos, d_lnl, d_lnprior, d_swapped); });
 }
 
 int vag_tempered_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_tempered_spec* sp, uint64_t step0, int n_steps,
@@ -4236,47 +4148,29 @@ int vag_tempered_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_tem
     HandoffScope handoff(c);
     if (!c || !q || !q->spec || !sp || !d_pos || !d_lnl || !d_lnprior || !d_accepted || !d_swapped)
         return set_err(VAG_E_INVALID, "null context, request, fit spec, tempered spec or buffer");
-    if ((d_chain == nullptr) != (d_lnl_chain == nullptr) || (d_chain == nullptr) != (d_lnprior_chain == nullptr))
-        return set_err(VAG_E_INVALID, "tempering: the chain, its ln L and its ln prior are stored together or not at all");
+    if (const int rc = run_chain_check("tempering", "the chain, its ln L and its ln prior",
+                                       (d_chain != nullptr) + (d_lnl_chain != nullptr) + (d_lnprior_chain != nullptr), 3))
+        return rc;
     TemperLadder ladder;
     if (const int rc = tempered_spec_check(sp, ladder)) return rc;
-    if (sp->ndim != q->spec->ndim) return set_err(VAG_E_INVALID, "tempering: ndim %d is not the fit spec's %d", sp->ndim, q->spec->ndim);
-    if (n_steps < 0) return set_err(VAG_E_INVALID, "tempering: n_steps must be >= 0, got %d", n_steps);
-    if (n_steps == 0) return VAG_OK;
-    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
-    int rc = fit_request_prepare(req);  // the scans, once per call of many steps
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    const int ndim = sp->ndim, nw = sp->n_walkers, half = nw / 2, nb = sp->n_temps * half;
-    const size_t replicas = (size_t)sp->n_temps * nw;
-    req.ndim = ndim;
-    rc = upload_blocks(c, req);  // and the uploads
-    if (rc) return rc;
-    if (c->d_temper_prop.ensure(sizeof(double) * (size_t)nb * ndim)) return VAG_E_HIP;
-    if (c->d_temper_lnl.ensure(sizeof(double) * (size_t)nb)) return VAG_E_HIP;
-    if (c->d_temper_lnprior.ensure(sizeof(double) * (size_t)nb)) return VAG_E_HIP;
-    double* d_prop = c->d_temper_prop.as<double>();
-    double* d_lnl_new = c->d_temper_lnl.as<double>();
-    double* d_lnprior_new = c->d_temper_lnprior.as<double>();
-    size_t row = 0;  // stored rows so far
-    for (int k = 0; k < n_steps; ++k) {
-        const uint64_t step = step0 + (uint64_t)k;
-        for (int which = 0; which < 2; ++which) {  // all temperatures' proposals of the half in ONE likelihood call
-            if ((rc = tempered_propose(c, sp, step, which, d_pos, d_prop))) return rc;
-            if ((rc = loglike_call(c, req, d_prop, nb, ndim, d_lnl_new))) return rc;
-            if ((rc = fit_split(c, nb, d_lnl_new, d_lnprior_new))) return rc;
-            if ((rc = tempered_accept(c, sp, ladder, step, which, d_prop, d_lnl_new, d_lnprior_new, d_pos, d_lnl, d_lnprior, d_accepted)))
-                return rc;
-        }
-        if ((rc = tempered_swap(c, sp, ladder, step, d_pos, d_lnl, d_lnprior, d_swapped))) return rc;
-        if (d_chain && (step + 1) % (uint64_t)sp->thin == 0) {  // the state after the exchanges (device-to-device, stream-ordered)
-            HIPCHK(hipMemcpyAsync(d_chain + row * replicas * ndim, d_pos, sizeof(double) * replicas * ndim, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(d_lnl_chain + row * replicas, d_lnl, sizeof(double) * replicas, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(d_lnprior_chain + row * replicas, d_lnprior, sizeof(double) * replicas, hipMemcpyDeviceToDevice, c->stream));
-            ++row;
-        }
-    }
-    return VAG_OK;
+    if (const int rc = run_steps_check("tempering", sp->ndim, q->spec->ndim, n_steps)) return rc;
+    const int T = sp->n_temps, nw = sp->n_walkers, ndim = sp->ndim, nb = T * half_of(nw);
+    const size_t replicas = (size_t)T * nw;
+    return sampler_run(
+        c, q, ndim, nb, sp->thin, d_chain != nullptr, step0, n_steps,  // all temperatures' proposals of the half in ONE likelihood call
+        [&](uint64_t step, int which, const SamplerScratch& s) { return tempered_propose(c, sp, step, which, d_pos, s.prop); },
+        [&](const SamplerScratch& s) { return fit_split(c, nb, s.fresh, s.aux); },
+        [&](uint64_t step, int which, const SamplerScratch& s, bool, size_t) {
+            return tempered_accept(c, sp, ladder, step, which, s.prop, s.fresh, s.aux, d_pos, d_lnl, d_lnprior, d_accepted);
+        },
+        [&](uint64_t step, bool stored, size_t row) -> int {
+            if (const int rc = tempered_swap(c, sp, ladder, step, d_pos, d_lnl, d_lnprior, d_swapped)) return rc;
+            if (!stored) return VAG_OK;  // the state after the exchanges (device-to-device, stream-ordered)
+            HIPCHK(hipMemcpyAsync(d_chain + ladder_row_offset(row, T, nw, ndim), d_pos, sizeof(double) * replicas * ndim, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_lnl_chain + ladder_row_offset(row, T, nw, 1), d_lnl, sizeof(double) * replicas, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_lnprior_chain + ladder_row_offset(row, T, nw, 1), d_lnprior, sizeof(double) * replicas, hipMemcpyDeviceToDevice, c->stream));
+            return VAG_OK;
+        });
 }
 
 // ---- chain autocorrelation (kernels and the definition's pieces: vag_chain_stats.h; the definition: the public header) ----

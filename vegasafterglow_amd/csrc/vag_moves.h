@@ -97,32 +97,21 @@ struct MoveWords {  // the proposal words of a walker: stream 0 and stream 4
 };
 
 __device__ inline MoveWords move_words(uint32_t seed_lo, uint32_t seed_hi, unsigned long long step, int w) {
-    const uint32_t key[2] = {seed_lo, seed_hi};
-    const uint32_t c0[4] = {(uint32_t)w, (uint32_t)(step & 0xffffffffull), (uint32_t)(step >> 32), 0u};
-    const uint32_t c4[4] = {(uint32_t)w, (uint32_t)(step & 0xffffffffull), (uint32_t)(step >> 32), MOVE_STREAM_PROPOSAL2};
     MoveWords m;
-    philox4x32_10(c0, key, m.x);
-    philox4x32_10(c4, key, m.v);
+    stream_words(seed_lo, seed_hi, step, w, STREAM_PROPOSAL, m.x);
+    stream_words(seed_lo, seed_hi, step, w, MOVE_STREAM_PROPOSAL2, m.v);
     return m;
 }
 
-// The stretch move of vag_stretch_propose_kernel, bit for bit, which also writes factor[i] = (ndim - 1) log z.
+// The stretch move of vag_stretch_propose_kernel (the same stretch_proposal), which also writes factor[i] = (ndim - 1) log z.
 __global__ void __launch_bounds__(STRETCH_LANES)
 vag_move_stretch_propose_kernel(uint32_t seed_lo, uint32_t seed_hi, double a, unsigned long long step, int which, int half, int ndim,
                                 const double* __restrict__ pos /* [2 half][ndim] */, double* __restrict__ prop /* [half][ndim] */,
                                 double* __restrict__ factor /* [half] */) {
     const int i = blockIdx.x * STRETCH_LANES + threadIdx.x;
     if (i >= half) return;
-    const int w = which * half + i;
-    const StretchDraw dr = stretch_draw(seed_lo, seed_hi, step, w, half, a);
-    const double* mine = pos + (size_t)w * ndim;
-    const double* other = pos + (size_t)((1 - which) * half + dr.partner) * ndim;
-    double* out = prop + (size_t)i * ndim;
-    for (int d = 0; d < ndim; ++d) {
-        const double q = other[d];
-        out[d] = fma(dr.z, mine[d] - q, q);
-    }
-    factor[i] = (double)(ndim - 1) * log(dr.z);
+    const double z = stretch_proposal(seed_lo, seed_hi, a, step, which * half + i, which, half, i, ndim, pos, prop + (size_t)i * ndim);
+    factor[i] = (double)(ndim - 1) * log(z);
 }
 
 // The DE move: a != b of the other half from words 2 and 3 of stream 0, the normal from u1 = u(x0, x1) of stream 0 and
@@ -196,25 +185,13 @@ vag_move_accept_kernel(uint32_t seed_lo, uint32_t seed_hi, unsigned long long st
     const int i = blockIdx.x * STRETCH_LANES + threadIdx.x;
     if (i >= half) return;
     const int w = which * half + i;
-    const uint32_t ctr[4] = {(uint32_t)w, (uint32_t)(step & 0xffffffffull), (uint32_t)(step >> 32), 1u};
-    const uint32_t key[2] = {seed_lo, seed_hi};
-    uint32_t y[4];
-    philox4x32_10(ctr, key, y);
-    const double u_a = u53(y[0], y[1]);
+    const double u_a = stream_uniform(seed_lo, seed_hi, step, w, STREAM_ACCEPT);
     const double ln_new = lp_new[i], ln_old = lp[w];
     const bool take = isfinite(ln_new) && log(u_a) < factor[i] + (ln_new - ln_old);  // (log(0) = -inf accepts; factor -inf never does)
     double* mine = pos + (size_t)w * ndim;
     const double* p = prop + (size_t)i * ndim;
-    if (take) {
-        for (int d = 0; d < ndim; ++d) mine[d] = p[d];
-        lp[w] = ln_new;
-        accepted[w] += 1;
-    }
-    if (chain_row) {
-        double* row = chain_row + (size_t)w * ndim;
-        for (int d = 0; d < ndim; ++d) row[d] = take ? p[d] : mine[d];
-        logp_row[w] = take ? ln_new : ln_old;
-    }
+    if (take) take_proposal(mine, p, ndim, lp + w, ln_new, accepted + w);
+    if (chain_row) write_row(chain_row + (size_t)w * ndim, logp_row + w, take, p, mine, ndim, ln_new, ln_old);
 }
 
 }  // namespace vag

@@ -14,6 +14,8 @@
 
 namespace vag {
 
+constexpr int STRETCH_LANES = 256;  // lanes per workgroup of every sampler kernel: ceil(items / 256) groups (vag_sampler_plan.h)
+
 // out[4] = Philox4x32-10(counter[4], key[2]); out may be counter
 VAG_PHILOX_HD inline void philox4x32_10(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
     uint32_t c0 = counter[0], c1 = counter[1], c2 = counter[2], c3 = counter[3];

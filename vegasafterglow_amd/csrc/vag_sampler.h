@@ -2,7 +2,9 @@
 // move in its parallel form with fixed halves, its draws a pure function of (seed, step, walker) through Philox4x32-10.  One lane per
 // walker of the active half; the kernels are latency-sized (a half is a few hundred walkers): plain vector loads and stores, no LDS,
 // no atomics.  The fused operations are explicit fma() calls and the division is an IEEE one, so that a proposal reproduces on the
-// host to the bit (sampling.stretch_proposals).
+// host to the bit (sampling.stretch_proposals).  The pieces every sampler kernel is written through are here too -- the draw of a
+// stream, the stretch proposal of one walker, what an accepted walker takes, the walker's row of a stored step -- and vag_moves.h
+// and vag_tempering.h use them: a body that two kernels share is one text.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,20 +12,60 @@
 
 namespace vag {
 
-constexpr int STRETCH_LANES = 256;  // lanes per workgroup of both kernels: ceil(half / 256) groups
+constexpr uint32_t STREAM_PROPOSAL = 0u, STREAM_ACCEPT = 1u, STREAM_EXCHANGE = 2u;  // (3 and 4: vag_moves.h)
+
+// the words of stream `stream` of replica r at `step`: counter (r, step lo, step hi, stream) under the key (seed_lo, seed_hi)
+__device__ inline void stream_words(uint32_t seed_lo, uint32_t seed_hi, unsigned long long step, int r, uint32_t stream, uint32_t out[4]) {
+    const uint32_t ctr[4] = {(uint32_t)r, (uint32_t)(step & 0xffffffffull), (uint32_t)(step >> 32), stream};
+    const uint32_t key[2] = {seed_lo, seed_hi};
+    philox4x32_10(ctr, key, out);
+}
+
+// the uniform of the stream's first two words
+__device__ inline double stream_uniform(uint32_t seed_lo, uint32_t seed_hi, unsigned long long step, int r, uint32_t stream) {
+    uint32_t y[4];
+    stream_words(seed_lo, seed_hi, step, r, stream, y);
+    return u53(y[0], y[1]);
+}
 
 struct StretchDraw {  // what a walker draws for one half-step
     double z;         // the stretch factor
     int partner;      // index within the complementary half
 };
 
-// stream 0 of walker w at `step`: u_z from the first two words, the partner from the third
-__device__ inline StretchDraw stretch_draw(uint32_t seed_lo, uint32_t seed_hi, unsigned long long step, int w, int half, double a) {
-    const uint32_t ctr[4] = {(uint32_t)w, (uint32_t)(step & 0xffffffffull), (uint32_t)(step >> 32), 0u};
-    const uint32_t key[2] = {seed_lo, seed_hi};
+// stream 0 of replica r at `step`: u_z from the first two words, the partner from the third
+__device__ inline StretchDraw stretch_draw(uint32_t seed_lo, uint32_t seed_hi, unsigned long long step, int r, int half, double a) {
     uint32_t x[4];
-    philox4x32_10(ctr, key, x);
+    stream_words(seed_lo, seed_hi, step, r, STREAM_PROPOSAL, x);
     return {stretch_z(a, u53(x[0], x[1])), stretch_partner(x[2], half)};
+}
+
+// The stretch proposal of walker w = which * half + i of the ensemble ens[2 half][ndim], drawn as replica r:
+// out[d] = fma(z, ens[w][d] - ens[partner][d], ens[partner][d]), the partner of the complementary half.  Returns z.
+__device__ inline double stretch_proposal(uint32_t seed_lo, uint32_t seed_hi, double a, unsigned long long step, int r, int which, int half,
+                                          int i, int ndim, const double* ens, double* out) {
+    const StretchDraw dr = stretch_draw(seed_lo, seed_hi, step, r, half, a);
+    const double* mine = ens + (size_t)(which * half + i) * ndim;
+    const double* other = ens + (size_t)((1 - which) * half + dr.partner) * ndim;
+    for (int d = 0; d < ndim; ++d) {
+        const double q = other[d];
+        out[d] = fma(dr.z, mine[d] - q, q);
+    }
+    return dr.z;
+}
+
+// an accepted walker takes the proposal and its ln p (ln L under tempering) and counts one
+__device__ inline void take_proposal(double* mine, const double* p, int ndim, double* ln_p, double ln_new, long long* count) {
+    for (int d = 0; d < ndim; ++d) mine[d] = p[d];
+    *ln_p = ln_new;
+    *count += 1;
+}
+
+// the walker's row of a stored step, after its decision
+__device__ inline void write_row(double* row, double* ln_p_row, bool take, const double* p, const double* mine, int ndim, double ln_new,
+                                 double ln_old) {
+    for (int d = 0; d < ndim; ++d) row[d] = take ? p[d] : mine[d];
+    *ln_p_row = take ? ln_new : ln_old;
 }
 
 // prop[i][d] = fma(z, pos[w][d] - pos[partner][d], pos[partner][d]) for walker w = which * half + i of the active half `which`
@@ -32,15 +74,7 @@ vag_stretch_propose_kernel(uint32_t seed_lo, uint32_t seed_hi, double a, unsigne
                            const double* __restrict__ pos /* [2 half][ndim] */, double* __restrict__ prop /* [half][ndim] */) {
     const int i = blockIdx.x * STRETCH_LANES + threadIdx.x;
     if (i >= half) return;
-    const int w = which * half + i;
-    const StretchDraw dr = stretch_draw(seed_lo, seed_hi, step, w, half, a);
-    const double* mine = pos + (size_t)w * ndim;
-    const double* other = pos + (size_t)((1 - which) * half + dr.partner) * ndim;
-    double* out = prop + (size_t)i * ndim;
-    for (int d = 0; d < ndim; ++d) {
-        const double q = other[d];
-        out[d] = fma(dr.z, mine[d] - q, q);
-    }
+    stretch_proposal(seed_lo, seed_hi, a, step, which * half + i, which, half, i, ndim, pos, prop + (size_t)i * ndim);
 }
 
 // The decision of walker w = which * half + i: reject a proposal whose ln p is not finite, otherwise accept iff
@@ -57,25 +91,13 @@ vag_stretch_accept_kernel(uint32_t seed_lo, uint32_t seed_hi, double a, unsigned
     if (i >= half) return;
     const int w = which * half + i;
     const StretchDraw dr = stretch_draw(seed_lo, seed_hi, step, w, half, a);
-    const uint32_t ctr[4] = {(uint32_t)w, (uint32_t)(step & 0xffffffffull), (uint32_t)(step >> 32), 1u};
-    const uint32_t key[2] = {seed_lo, seed_hi};
-    uint32_t y[4];
-    philox4x32_10(ctr, key, y);
-    const double u_a = u53(y[0], y[1]);
+    const double u_a = stream_uniform(seed_lo, seed_hi, step, w, STREAM_ACCEPT);
     const double ln_new = lp_new[i], ln_old = lp[w];
     const bool take = isfinite(ln_new) && log(u_a) < (double)(ndim - 1) * log(dr.z) + (ln_new - ln_old);  // (log(0) = -inf accepts)
     double* mine = pos + (size_t)w * ndim;
     const double* p = prop + (size_t)i * ndim;
-    if (take) {
-        for (int d = 0; d < ndim; ++d) mine[d] = p[d];
-        lp[w] = ln_new;
-        accepted[w] += 1;
-    }
-    if (chain_row) {
-        double* row = chain_row + (size_t)w * ndim;
-        for (int d = 0; d < ndim; ++d) row[d] = take ? p[d] : mine[d];
-        logp_row[w] = take ? ln_new : ln_old;
-    }
+    if (take) take_proposal(mine, p, ndim, lp + w, ln_new, accepted + w);
+    if (chain_row) write_row(chain_row + (size_t)w * ndim, logp_row + w, take, p, mine, ndim, ln_new, ln_old);
 }
 
 }  // namespace vag

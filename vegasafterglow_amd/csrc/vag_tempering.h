@@ -12,6 +12,10 @@
 
 namespace vag {
 
+struct TemperLadder {  // the inverse temperatures, by value in the kernel arguments; filled by tempered_spec_check (vag_sampler_plan.h)
+    double beta[VAG_TEMPER_MAX_RUNGS];
+};
+
 // ln of the acceptance ratio of a move within temperature beta, without the (ndim - 1) log z of the stretch: one fma
 VAG_PHILOX_HD inline double tempered_log_ratio(double beta, double lnl_new, double lnl_old, double lnprior_new, double lnprior_old) {
     return std::fma(beta, lnl_new - lnl_old, lnprior_new - lnprior_old);
@@ -31,10 +35,6 @@ VAG_PHILOX_HD inline double swap_log_ratio(double beta_lo, double beta_hi, doubl
 
 namespace vag {
 
-struct TemperLadder {  // the inverse temperatures, by value in the kernel arguments
-    double beta[VAG_TEMPER_MAX_RUNGS];
-};
-
 // prop[t][i][d] = fma(z, pos[t][w][d] - pos[t][partner][d], pos[t][partner][d]) for walker w = which * half + i of temperature t:
 // every temperature's active half against its own complementary half.  One lane per (t, i).
 __global__ void __launch_bounds__(STRETCH_LANES)
@@ -44,16 +44,8 @@ vag_tempered_propose_kernel(uint32_t seed_lo, uint32_t seed_hi, double a, unsign
     const int item = blockIdx.x * STRETCH_LANES + threadIdx.x;
     if (item >= n_temps * half) return;
     const int t = item / half, i = item - t * half;
-    const int w = which * half + i;
-    const StretchDraw dr = stretch_draw(seed_lo, seed_hi, step, t * 2 * half + w, half, a);
-    const double* ens = pos + (size_t)t * 2 * half * ndim;
-    const double* mine = ens + (size_t)w * ndim;
-    const double* other = ens + (size_t)((1 - which) * half + dr.partner) * ndim;
-    double* out = prop + (size_t)item * ndim;
-    for (int d = 0; d < ndim; ++d) {
-        const double q = other[d];
-        out[d] = fma(dr.z, mine[d] - q, q);
-    }
+    stretch_proposal(seed_lo, seed_hi, a, step, t * 2 * half + which * half + i, which, half, i, ndim, pos + (size_t)t * 2 * half * ndim,
+                     prop + (size_t)item * ndim);
 }
 
 // The decision of walker w = which * half + i of temperature t: reject a proposal whose ln L or ln prior is not finite (at every
@@ -70,21 +62,13 @@ vag_tempered_accept_kernel(uint32_t seed_lo, uint32_t seed_hi, double a, unsigne
     const int t = item / half, i = item - t * half;
     const int r = t * 2 * half + which * half + i;  // the replica's index in the whole ladder
     const StretchDraw dr = stretch_draw(seed_lo, seed_hi, step, r, half, a);
-    const uint32_t ctr[4] = {(uint32_t)r, (uint32_t)(step & 0xffffffffull), (uint32_t)(step >> 32), 1u};
-    const uint32_t key[2] = {seed_lo, seed_hi};
-    uint32_t y[4];
-    philox4x32_10(ctr, key, y);
-    const double u_a = u53(y[0], y[1]);
+    const double u_a = stream_uniform(seed_lo, seed_hi, step, r, STREAM_ACCEPT);
     const double l_new = lnl_new[item], p_new = lnprior_new[item];
     const double ratio = tempered_log_ratio(ladder.beta[t], l_new, lnl[r], p_new, lnprior[r]);
     const bool take = isfinite(l_new) && isfinite(p_new) && log(u_a) < (double)(ndim - 1) * log(dr.z) + ratio;  // (log(0) = -inf accepts)
     if (take) {
-        double* mine = pos + (size_t)r * ndim;
-        const double* p = prop + (size_t)item * ndim;
-        for (int d = 0; d < ndim; ++d) mine[d] = p[d];
-        lnl[r] = l_new;
+        take_proposal(pos + (size_t)r * ndim, prop + (size_t)item * ndim, ndim, lnl + r, l_new, accepted + r);
         lnprior[r] = p_new;
-        accepted[r] += 1;
     }
 }
 
@@ -101,12 +85,9 @@ vag_tempered_swap_kernel(uint32_t seed_lo, uint32_t seed_hi, unsigned long long 
     const int pair = item / n_walkers, w = item - pair * n_walkers;
     const int t = 2 * pair + (int)(step & 1ull);
     const int lo = t * n_walkers + w, hi = lo + n_walkers;
-    const uint32_t ctr[4] = {(uint32_t)lo, (uint32_t)(step & 0xffffffffull), (uint32_t)(step >> 32), 2u};
-    const uint32_t key[2] = {seed_lo, seed_hi};
-    uint32_t y[4];
-    philox4x32_10(ctr, key, y);
+    const double u_s = stream_uniform(seed_lo, seed_hi, step, lo, STREAM_EXCHANGE);
     const double l_lo = lnl[lo], l_hi = lnl[hi];
-    if (!(log(u53(y[0], y[1])) < swap_log_ratio(ladder.beta[t], ladder.beta[t + 1], l_lo, l_hi))) return;
+    if (!(log(u_s) < swap_log_ratio(ladder.beta[t], ladder.beta[t + 1], l_lo, l_hi))) return;
     double* a_pos = pos + (size_t)lo * ndim;
     double* b_pos = pos + (size_t)hi * ndim;
     for (int d = 0; d < ndim; ++d) {

@@ -261,7 +261,36 @@ def run_stretch_move_philox(log_prob_batch: Callable[[np.ndarray], np.ndarray], 
     return chain, logp, accepted / max(nsteps, 1)
 
 
-class StretchMove:
+class _DeviceMove:
+    """What StretchMove, EnsembleMoves and TemperedMove share: the library, the device's context with its lock, the spec struct, the
+    entry points (lookup(lib, name), kept as self._<key>), the check of a tensor argument and the call of an entry point."""
+
+    def __init__(self, lookup, spec, device, **entries):
+        import torch
+        from . import _lib
+        from .model import get_context
+        self._lib = _lib.load()
+        for key, name in entries.items():
+            setattr(self, "_" + key, lookup(self._lib, name))
+        self._spec = spec
+        self._h, self._lock = get_context(device)
+        self._dev = torch.device("cuda", device)
+
+    def _checked(self, t, shape, dtype, what):
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != self._dev or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor {shape} on {self._dev}")
+        return t
+
+    def _call(self, entry, *args):
+        """entry(context, spec, *args) on torch's current stream, a tensor among args as its data pointer."""
+        import ctypes as C
+        from . import _lib
+        from .fitting import on_current_stream
+        args = [a.data_ptr() if hasattr(a, "data_ptr") else int(a) for a in args]
+        on_current_stream(self._lib, self._h, self._lock, self._dev, lambda: _lib.check(entry(self._h, C.byref(self._spec), *args)))
+
+
+class StretchMove(_DeviceMove):
     """The two halves of a half-step on the device (vag_stretch_propose_dev / vag_stretch_accept_dev), on float64 torch tensors and
     torch's current stream; nothing crosses PCIe and nothing synchronises.  They need no model: any evaluator on device tensors goes
     between them, a dist.WalkerSharder for instance::
@@ -279,48 +308,80 @@ class StretchMove:
 
     def __init__(self, nwalkers: int, ndim: int, seed: int = 0, a: float = 2.0, device: int = 0):
         _check_stretch(nwalkers, ndim, a)
-        import torch
         from . import _lib
-        from .model import get_context
         self.nwalkers, self.ndim = int(nwalkers), int(ndim)
-        self._lib = _lib.load()
-        self._propose = _lib.stretch_entry(self._lib, "vag_stretch_propose_dev")
-        self._accept = _lib.stretch_entry(self._lib, "vag_stretch_accept_dev")
-        self._spec = _lib.StretchSpec(int(seed) & (2 ** 64 - 1), float(a), self.nwalkers, self.ndim, 1)
-        self._h, self._lock = get_context(device)
-        self._dev = torch.device("cuda", device)
-
-    def _run(self, fn):
-        from .fitting import on_current_stream
-        return on_current_stream(self._lib, self._h, self._lock, self._dev, fn)
-
-    def _checked(self, t, shape, dtype, what):
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != self._dev or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous {dtype} tensor {shape} on {self._dev}")
-        return t
+        super().__init__(_lib.stretch_entry, _lib.StretchSpec(int(seed) & (2 ** 64 - 1), float(a), self.nwalkers, self.ndim, 1), device,
+                         propose="vag_stretch_propose_dev", accept="vag_stretch_accept_dev")
 
     def propose(self, step: int, half: int, pos):
-        import ctypes as C
         import torch
-        from . import _lib
-        nh = self.nwalkers // 2
         self._checked(pos, (self.nwalkers, self.ndim), torch.float64, "pos")
-        prop = torch.empty((nh, self.ndim), dtype=torch.float64, device=self._dev)
-        self._run(lambda: _lib.check(self._propose(self._h, C.byref(self._spec), int(step), int(half), pos.data_ptr(), prop.data_ptr())))
+        prop = torch.empty((self.nwalkers // 2, self.ndim), dtype=torch.float64, device=self._dev)
+        self._call(self._propose, step, half, pos, prop)
         return prop
 
     def accept(self, step: int, half: int, prop, lp_new, pos, lp, accepted):
-        import ctypes as C
         import torch
-        from . import _lib
         nh = self.nwalkers // 2
         self._checked(prop, (nh, self.ndim), torch.float64, "prop")
         self._checked(lp_new, (nh,), torch.float64, "lp_new")
         self._checked(pos, (self.nwalkers, self.ndim), torch.float64, "pos")
         self._checked(lp, (self.nwalkers,), torch.float64, "lp")
         self._checked(accepted, (self.nwalkers,), torch.int64, "accepted")
-        self._run(lambda: _lib.check(self._accept(self._h, C.byref(self._spec), int(step), int(half), prop.data_ptr(), lp_new.data_ptr(),
-                                                  pos.data_ptr(), lp.data_ptr(), accepted.data_ptr())))
+        self._call(self._accept, step, half, prop, lp_new, pos, lp, accepted)
+
+
+def _run_chunks(fitter: Fitter, param_defs, priors, who, pos0_text, ndim, proposals, nsteps, thin, chunk, progress, converge, nburn, record,
+                cold, entry, move, begin):
+    """The chunk driver behind run_stretch_move_device, run_moves_device and run_tempered_device.  The caller has checked pos0
+    (pos0_text: what it says of a pos0 of another ndim than the fit's) and made `move`, the struct the run entry `entry(lib)` takes
+    behind the request.  begin(lib, h, lock, dev, spec, rows) allocates and returns (state, counts, chains): the tensors of the
+    current state, positions first, evaluated and found finite; the count tensors; the tensors of `rows` stored rows, the chain
+    first -- each list in the order of the run entry's arguments.  cold(chain): the view [rows, W, D] the convergence monitor reads;
+    proposals: those of one likelihood call, for the plan's warnings.  ``progress(step, *state)`` gets numpy copies once per chunk.
+
+    Returns (chains, counts, ran, rec) as numpy arrays: the rows of the `ran` steps run, the counts, and the ConvergedAutocorr
+    record -- None for a plain run (converge=None and no `record`), which runs all its steps."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .fitting import loglike_request, on_current_stream
+    from .model import get_context
+    if chunk < 1 or nsteps < 0:
+        raise ValueError("chunk must be >= 1 and nsteps >= 0")
+    monitor = _ConvergenceMonitor(converge, nsteps, nburn, thin, chunk, fitter.device, cold)
+    spec, _, _ = fitter.build_spec(param_defs, priors=priors, use_priors=True)
+    if spec.ndim != ndim:
+        raise ValueError(pos0_text)
+    fitter._refuse_host_priors(param_defs, who)
+    lib = _lib.load()
+    run = entry(lib)
+    h, lock = get_context(fitter.device)
+    dev = torch.device("cuda", fitter.device)
+    request = loglike_request(spec)
+    rows = nsteps // thin
+    state, counts, chains = begin(lib, h, lock, dev, spec, rows)
+    step0 = 0
+    while step0 < nsteps:
+        n = monitor.chunk_end(step0) - step0
+        row = step0 // thin
+        at = [c[row].data_ptr() if row < rows else None for c in chains]  # (a chunk of no stored row stores nothing)
+        on_current_stream(lib, h, lock, dev, lambda: _lib.check(run(h, C.byref(request), C.byref(move), step0, n,
+                                                                    *[t.data_ptr() for t in state + counts], *at)))
+        if progress is not None:
+            progress(step0 + n - 1, *[t.cpu().numpy() for t in state])
+        step0 += n
+        if monitor.stop(chains[0], step0):
+            break
+    plan = _lib.Plan()
+    with lock:
+        lib.vag_last_plan(h, C.byref(plan))
+    fitter._log_plan_warnings(plan, proposals)
+    fitter.last_plan = plan
+    plain = converge is None and not record
+    kept = step0 // thin  # (step0: the steps run; a plain run has run nsteps)
+    return ([c[:kept].cpu().numpy() for c in chains], [t.cpu().numpy() for t in counts], step0,
+            None if plain else monitor.record(chains[0], step0))
 
 
 def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, who, entry, make_move, converge=None,
@@ -328,65 +389,38 @@ def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, c
     """The body of run_stretch_move_device and run_moves_device: `entry` is the run entry's name and make_move(nw, ndim) the
     struct it takes behind the request (after the Python-side checks, which make_move performs).  converge, nburn: the stopping
     rule (_ConvergenceMonitor); with converge=None the loop is the plain one, chunk by chunk."""
-    import ctypes as C
-    import torch
     from . import _lib
-    from .fitting import _widest_entry, loglike_request, on_current_stream
-    from .model import get_context
     pos0 = np.ascontiguousarray(pos0, dtype=np.float64)
     if pos0.ndim != 2:
         raise ValueError("pos0 must be [nwalkers, ndim]")
     nw, ndim = pos0.shape
     move = make_move(nw, ndim)
-    if chunk < 1 or nsteps < 0:
-        raise ValueError("chunk must be >= 1 and nsteps >= 0")
-    monitor = _ConvergenceMonitor(converge, nsteps, nburn, thin, chunk, fitter.device, lambda kept: kept)
-    spec, _, _ = fitter.build_spec(param_defs, priors=priors, use_priors=True)
-    if spec.ndim != ndim:
-        raise ValueError("pos0 must be [nwalkers, ndim]")
-    fitter._refuse_host_priors(param_defs, who)
-    lib = _lib.load()
-    run = (_lib.stretch_entry if entry == "vag_stretch_run_dev" else _lib.move_entry)(lib, entry)
-    h, lock = get_context(fitter.device)
-    dev = torch.device("cuda", fitter.device)
-    request = loglike_request(spec)
-    pos = torch.from_numpy(pos0).to(dev)
-    lp = torch.empty((nw,), dtype=torch.float64, device=dev)
-    accepted = torch.zeros((nw,), dtype=torch.int64, device=dev)
-    rows = nsteps // thin
-    chain = torch.empty((rows, nw, ndim), dtype=torch.float64, device=dev)
-    logp = torch.empty((rows, nw), dtype=torch.float64, device=dev)
-    ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
 
-    def initial():
-        fn, fold = _widest_entry(lib, spec, "_dev")
-        _lib.check(fn(h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
-                      ref(spec._counts), ref(spec._index), *fold, pos.data_ptr(), nw, ndim, lp.data_ptr()))
-    on_current_stream(lib, h, lock, dev, initial)
-    if not bool(torch.isfinite(lp).all()):
-        raise ValueError("initial positions must have finite log-probability")
-    step0 = 0
-    while step0 < nsteps:
-        n = monitor.chunk_end(step0) - step0
-        row = step0 // thin
-        stored = row < rows
-        on_current_stream(lib, h, lock, dev, lambda: _lib.check(run(
-            h, C.byref(request), C.byref(move), step0, n, pos.data_ptr(), lp.data_ptr(), accepted.data_ptr(),
-            chain.data_ptr() + 8 * row * nw * ndim if stored else None, logp.data_ptr() + 8 * row * nw if stored else None)))
-        if progress is not None:
-            progress(step0 + n - 1, pos.cpu().numpy(), lp.cpu().numpy())
-        step0 += n
-        if monitor.stop(chain, step0):
-            break
-    plan = _lib.Plan()
-    with lock:
-        lib.vag_last_plan(h, C.byref(plan))
-    fitter._log_plan_warnings(plan, nw // 2)
-    fitter.last_plan = plan
-    if converge is None and not _record:
-        return chain.cpu().numpy(), logp.cpu().numpy(), accepted.cpu().numpy() / max(nsteps, 1)
-    kept = step0 // thin  # (step0: the steps run)
-    return (chain[:kept].cpu().numpy(), logp[:kept].cpu().numpy(), accepted.cpu().numpy() / max(step0, 1), monitor.record(chain, step0))
+    def begin(lib, h, lock, dev, spec, rows):
+        import ctypes as C
+        import torch
+        from .fitting import _widest_entry, on_current_stream
+        pos = torch.from_numpy(pos0).to(dev)
+        lp = torch.empty((nw,), dtype=torch.float64, device=dev)
+        accepted = torch.zeros((nw,), dtype=torch.int64, device=dev)
+        chain = torch.empty((rows, nw, ndim), dtype=torch.float64, device=dev)
+        logp = torch.empty((rows, nw), dtype=torch.float64, device=dev)
+        ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+
+        def initial():
+            fn, fold = _widest_entry(lib, spec, "_dev")
+            _lib.check(fn(h, C.byref(spec), ref(spec._sky), ref(spec._vis), ref(spec._pol), ref(spec._lim), ref(spec._noise),
+                          ref(spec._counts), ref(spec._index), *fold, pos.data_ptr(), nw, ndim, lp.data_ptr()))
+        on_current_stream(lib, h, lock, dev, initial)
+        if not bool(torch.isfinite(lp).all()):
+            raise ValueError("initial positions must have finite log-probability")
+        return [pos, lp], [accepted], [chain, logp]
+    lookup = _lib.stretch_entry if entry == "vag_stretch_run_dev" else _lib.move_entry
+    (chain, logp), (accepted,), ran, rec = _run_chunks(fitter, param_defs, priors, who, "pos0 must be [nwalkers, ndim]", ndim, nw // 2, nsteps,
+                                                       thin, chunk, progress, converge, nburn, _record, lambda kept: kept,
+                                                       lambda lib: lookup(lib, entry), move, begin)
+    out = (chain, logp, accepted / max(ran, 1))
+    return out if rec is None else out + (rec,)
 
 
 def run_stretch_move_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, nsteps: int, seed: int = 0,
@@ -642,7 +676,7 @@ def _move_spec(weights, nwalkers, ndim, seed, a, gamma0, sigma, gamma_snooker, t
                          (_lib.C.c_double * 3)(*weights), int(nwalkers), int(ndim), int(thin))
 
 
-class EnsembleMoves:
+class EnsembleMoves(_DeviceMove):
     """StretchMove for the move mix (vag_move_propose_dev / vag_move_accept_dev): the two halves of a half-step on float64 torch
     tensors and torch's current stream, with the ln of the Hastings factor between them; they need no model::
 
@@ -659,39 +693,25 @@ class EnsembleMoves:
                  sigma: float = DE_SIGMA, gamma_snooker: float = SNOOKER_GAMMA, device: int = 0):
         self.weights = move_weights(moves)
         gamma0 = _check_moves(self.weights, nwalkers, ndim, a, gamma0, sigma, gamma_snooker)
-        import torch
-        from . import _lib
-        from .model import get_context
         self.nwalkers, self.ndim, self.seed = int(nwalkers), int(ndim), int(seed)
-        self._lib = _lib.load()
-        self._propose = _lib.move_entry(self._lib, "vag_move_propose_dev")
-        self._accept = _lib.move_entry(self._lib, "vag_move_accept_dev")
-        self._spec = _move_spec(self.weights, nwalkers, ndim, seed, a, gamma0, sigma, gamma_snooker, 1)
-        self._h, self._lock = get_context(device)
-        self._dev = torch.device("cuda", device)
-
-    _run = StretchMove._run
-    _checked = StretchMove._checked
+        from . import _lib
+        super().__init__(_lib.move_entry, _move_spec(self.weights, nwalkers, ndim, seed, a, gamma0, sigma, gamma_snooker, 1), device,
+                         propose="vag_move_propose_dev", accept="vag_move_accept_dev")
 
     def kind(self, step: int) -> int:
         return move_kind(step, self.seed, self.weights)
 
     def propose(self, step: int, half: int, pos):
-        import ctypes as C
         import torch
-        from . import _lib
         nh = self.nwalkers // 2
         self._checked(pos, (self.nwalkers, self.ndim), torch.float64, "pos")
         prop = torch.empty((nh, self.ndim), dtype=torch.float64, device=self._dev)
         factor = torch.empty((nh,), dtype=torch.float64, device=self._dev)
-        self._run(lambda: _lib.check(self._propose(self._h, C.byref(self._spec), int(step), int(half), pos.data_ptr(), prop.data_ptr(),
-                                                   factor.data_ptr())))
+        self._call(self._propose, step, half, pos, prop, factor)
         return prop, factor
 
     def accept(self, step: int, half: int, prop, factor, lp_new, pos, lp, accepted):
-        import ctypes as C
         import torch
-        from . import _lib
         nh = self.nwalkers // 2
         self._checked(prop, (nh, self.ndim), torch.float64, "prop")
         self._checked(factor, (nh,), torch.float64, "factor")
@@ -699,8 +719,7 @@ class EnsembleMoves:
         self._checked(pos, (self.nwalkers, self.ndim), torch.float64, "pos")
         self._checked(lp, (self.nwalkers,), torch.float64, "lp")
         self._checked(accepted, (self.nwalkers,), torch.int64, "accepted")
-        self._run(lambda: _lib.check(self._accept(self._h, C.byref(self._spec), int(step), int(half), prop.data_ptr(), factor.data_ptr(),
-                                                  lp_new.data_ptr(), pos.data_ptr(), lp.data_ptr(), accepted.data_ptr())))
+        self._call(self._accept, step, half, prop, factor, lp_new, pos, lp, accepted)
 
 
 def run_moves_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np.ndarray, nsteps: int, moves=REFERENCE_MOVES,
@@ -909,7 +928,7 @@ def thermodynamic_evidence(betas, mean_lnl):
     return ln_z, abs(ln_z - trapezoid(betas[coarse], mean_lnl[coarse]))
 
 
-class TemperedMove:
+class TemperedMove(_DeviceMove):
     """The building blocks of a tempered step on the device (vag_tempered_propose_dev / _accept_dev / _swap_dev), on float64 torch
     tensors and torch's current stream, like StretchMove; they need no model::
 
@@ -927,36 +946,22 @@ class TemperedMove:
         self.betas = _check_betas(betas)
         _check_stretch(nwalkers, ndim, a)
         import ctypes as C
-        import torch
         from . import _lib
-        from .model import get_context
         self.ntemps, self.nwalkers, self.ndim = int(self.betas.size), int(nwalkers), int(ndim)
-        self._lib = _lib.load()
-        self._propose = _lib.tempered_entry(self._lib, "vag_tempered_propose_dev")
-        self._accept = _lib.tempered_entry(self._lib, "vag_tempered_accept_dev")
-        self._swap = _lib.tempered_entry(self._lib, "vag_tempered_swap_dev")
-        self._spec = _lib.TemperedSpec(int(seed) & (2 ** 64 - 1), float(a), self.ntemps, self.nwalkers, self.ndim, 1,
-                                       self.betas.ctypes.data_as(C.POINTER(C.c_double)))
-        self._h, self._lock = get_context(device)
-        self._dev = torch.device("cuda", device)
-
-    _run = StretchMove._run
-    _checked = StretchMove._checked
+        spec = _lib.TemperedSpec(int(seed) & (2 ** 64 - 1), float(a), self.ntemps, self.nwalkers, self.ndim, 1,
+                                 self.betas.ctypes.data_as(C.POINTER(C.c_double)))
+        super().__init__(_lib.tempered_entry, spec, device, propose="vag_tempered_propose_dev", accept="vag_tempered_accept_dev",
+                         swap="vag_tempered_swap_dev")
 
     def propose(self, step: int, half: int, pos):
-        import ctypes as C
         import torch
-        from . import _lib
-        nh = self.nwalkers // 2
         self._checked(pos, (self.ntemps, self.nwalkers, self.ndim), torch.float64, "pos")
-        prop = torch.empty((self.ntemps, nh, self.ndim), dtype=torch.float64, device=self._dev)
-        self._run(lambda: _lib.check(self._propose(self._h, C.byref(self._spec), int(step), int(half), pos.data_ptr(), prop.data_ptr())))
+        prop = torch.empty((self.ntemps, self.nwalkers // 2, self.ndim), dtype=torch.float64, device=self._dev)
+        self._call(self._propose, step, half, pos, prop)
         return prop
 
     def accept(self, step: int, half: int, prop, lnl_new, lnprior_new, pos, lnl, lnprior, accepted):
-        import ctypes as C
         import torch
-        from . import _lib
         T, nw, nh = self.ntemps, self.nwalkers, self.nwalkers // 2
         self._checked(prop, (T, nh, self.ndim), torch.float64, "prop")
         self._checked(lnl_new, (T, nh), torch.float64, "lnl_new")
@@ -965,21 +970,16 @@ class TemperedMove:
         self._checked(lnl, (T, nw), torch.float64, "lnl")
         self._checked(lnprior, (T, nw), torch.float64, "lnprior")
         self._checked(accepted, (T, nw), torch.int64, "accepted")
-        self._run(lambda: _lib.check(self._accept(self._h, C.byref(self._spec), int(step), int(half), prop.data_ptr(), lnl_new.data_ptr(),
-                                                  lnprior_new.data_ptr(), pos.data_ptr(), lnl.data_ptr(), lnprior.data_ptr(),
-                                                  accepted.data_ptr())))
+        self._call(self._accept, step, half, prop, lnl_new, lnprior_new, pos, lnl, lnprior, accepted)
 
     def swap(self, step: int, pos, lnl, lnprior, swapped):
-        import ctypes as C
         import torch
-        from . import _lib
         T, nw = self.ntemps, self.nwalkers
         self._checked(pos, (T, nw, self.ndim), torch.float64, "pos")
         self._checked(lnl, (T, nw), torch.float64, "lnl")
         self._checked(lnprior, (T, nw), torch.float64, "lnprior")
         self._checked(swapped, (max(T - 1, 1), nw), torch.int64, "swapped")
-        self._run(lambda: _lib.check(self._swap(self._h, C.byref(self._spec), int(step), pos.data_ptr(), lnl.data_ptr(),
-                                                lnprior.data_ptr(), swapped.data_ptr())))
+        self._call(self._swap, step, pos, lnl, lnprior, swapped)
 
 
 def loglike_split_device(fitter: Fitter, spec, theta, lnl, lnprior):
@@ -1020,10 +1020,7 @@ def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np
     place through its row stride: ``nsteps`` is then a maximum, the five values are those of a plain run of the steps run, and a
     sixth follows, the ConvergedAutocorr record."""
     import ctypes as C
-    import torch
     from . import _lib
-    from .fitting import loglike_request, on_current_stream
-    from .model import get_context
     pos0 = np.ascontiguousarray(pos0, dtype=np.float64)
     if pos0.ndim != 3:
         raise ValueError("pos0 must be [ntemps, nwalkers, ndim]")
@@ -1032,60 +1029,28 @@ def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np
     if ntemps != betas.size:
         raise ValueError("pos0 must be [ntemps, nwalkers, ndim] with one ensemble per entry of betas")
     _check_stretch(nw, ndim, a, thin)
-    if chunk < 1 or nsteps < 0:
-        raise ValueError("chunk must be >= 1 and nsteps >= 0")
-    monitor = _ConvergenceMonitor(converge, nsteps, nburn, thin, chunk, fitter.device, lambda kept: kept[:, 0])
-    spec, _, _ = fitter.build_spec(param_defs, priors=priors, use_priors=True)
-    if spec.ndim != ndim:
-        raise ValueError("pos0 must be [ntemps, nwalkers, ndim]")
-    fitter._refuse_host_priors(param_defs, "run_tempered_device")
-    lib = _lib.load()
-    run = _lib.tempered_entry(lib, "vag_tempered_run_dev")
-    h, lock = get_context(fitter.device)
-    dev = torch.device("cuda", fitter.device)
-    request = loglike_request(spec)
     tempered = _lib.TemperedSpec(int(seed) & (2 ** 64 - 1), float(a), ntemps, nw, ndim, int(thin),
                                  betas.ctypes.data_as(C.POINTER(C.c_double)))
-    pos = torch.from_numpy(pos0).to(dev)
-    lnl = torch.empty((ntemps, nw), dtype=torch.float64, device=dev)
-    lnprior = torch.empty((ntemps, nw), dtype=torch.float64, device=dev)
-    accepted = torch.zeros((ntemps, nw), dtype=torch.int64, device=dev)
-    swapped = torch.zeros((max(ntemps - 1, 1), nw), dtype=torch.int64, device=dev)
-    rows = nsteps // thin
-    chain = torch.empty((rows, ntemps, nw, ndim), dtype=torch.float64, device=dev)
-    lnl_chain = torch.empty((rows, ntemps, nw), dtype=torch.float64, device=dev)
-    lnprior_chain = torch.empty((rows, ntemps, nw), dtype=torch.float64, device=dev)
-    loglike_split_device(fitter, spec, pos.view(-1, ndim), lnl.view(-1), lnprior.view(-1))
-    if not bool((torch.isfinite(lnl) & torch.isfinite(lnprior)).all()):
-        raise ValueError("initial positions must have finite ln L and ln prior")
-    per_row = ntemps * nw
-    step0 = 0
-    while step0 < nsteps:
-        n = monitor.chunk_end(step0) - step0
-        row = step0 // thin
-        stored = row < rows
-        on_current_stream(lib, h, lock, dev, lambda: _lib.check(run(
-            h, C.byref(request), C.byref(tempered), step0, n, pos.data_ptr(), lnl.data_ptr(), lnprior.data_ptr(), accepted.data_ptr(),
-            swapped.data_ptr(), chain.data_ptr() + 8 * row * per_row * ndim if stored else None,
-            lnl_chain.data_ptr() + 8 * row * per_row if stored else None, lnprior_chain.data_ptr() + 8 * row * per_row if stored else None)))
-        if progress is not None:
-            progress(step0 + n - 1, pos.cpu().numpy(), lnl.cpu().numpy(), lnprior.cpu().numpy())
-        step0 += n
-        if monitor.stop(chain, step0):
-            break
-    plain = converge is None and not _record
-    ran = nsteps if plain else step0
-    plan = _lib.Plan()
-    with lock:
-        lib.vag_last_plan(h, C.byref(plan))
-    fitter._log_plan_warnings(plan, ntemps * nw // 2)
-    fitter.last_plan = plan
-    attempts = swap_attempts(ntemps, 0, ran)
-    swap_fraction = swapped.cpu().numpy()[:ntemps - 1].sum(axis=1) / np.maximum(attempts * nw, 1)
-    kept = ran // thin
-    out = (chain[:kept].cpu().numpy(), lnl_chain[:kept].cpu().numpy(), lnprior_chain[:kept].cpu().numpy(),
-           accepted.cpu().numpy() / max(ran, 1), swap_fraction)
-    return out if plain else out + (monitor.record(chain, ran),)
+
+    def begin(lib, h, lock, dev, spec, rows):
+        import torch
+        pos = torch.from_numpy(pos0).to(dev)
+        lnl = torch.empty((ntemps, nw), dtype=torch.float64, device=dev)
+        lnprior = torch.empty((ntemps, nw), dtype=torch.float64, device=dev)
+        accepted = torch.zeros((ntemps, nw), dtype=torch.int64, device=dev)
+        swapped = torch.zeros((max(ntemps - 1, 1), nw), dtype=torch.int64, device=dev)
+        chains = [torch.empty((rows, ntemps, nw) + tail, dtype=torch.float64, device=dev) for tail in ((ndim,), (), ())]
+        loglike_split_device(fitter, spec, pos.view(-1, ndim), lnl.view(-1), lnprior.view(-1))
+        if not bool((torch.isfinite(lnl) & torch.isfinite(lnprior)).all()):
+            raise ValueError("initial positions must have finite ln L and ln prior")
+        return [pos, lnl, lnprior], [accepted, swapped], chains
+    chains, (accepted, swapped), ran, rec = _run_chunks(
+        fitter, param_defs, priors, "run_tempered_device", "pos0 must be [ntemps, nwalkers, ndim]", ndim, ntemps * nw // 2, nsteps, thin,
+        chunk, progress, converge, nburn, _record, lambda kept: kept[:, 0],
+        lambda lib: _lib.tempered_entry(lib, "vag_tempered_run_dev"), tempered, begin)
+    swap_fraction = swapped[:ntemps - 1].sum(axis=1) / np.maximum(swap_attempts(ntemps, 0, ran) * nw, 1)
+    out = (*chains, accepted / max(ran, 1), swap_fraction)
+    return out if rec is None else out + (rec,)
 
 
 # ---- chain autocorrelation (INTEGRATION.md "Chain autocorrelation"): the integrated autocorrelation time of every parameter, pooled over
