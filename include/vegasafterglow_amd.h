@@ -1124,6 +1124,40 @@ typedef struct vag_chain_spec {
 int vag_chain_autocorr_dev(vag_ctx* ctx, const vag_chain_spec* sp, const double* d_chain, double* d_rho, double* d_tau,
                            int32_t* d_window);
 
+/* Posterior-predictive quantile bands on the device (added after VAG_ABI_VERSION 13, detect by symbol), by the definition of
+ * INTEGRATION.md "Posterior-predictive bands" (its pieces as code: csrc/vag_predict.h).
+ * Draws F[S][M] in HBM, row s one draw.  A draw is valid when its flag is set (d_valid_in[s] != 0; NULL: every flag set) and all M
+ * of its values are finite; n is the number of valid draws, the same for every column.  For each quantile q[k] in [0, 1]:
+ * h = q (double)(n - 1) (one FP64 multiply), lo = floor(h), g = h - lo, and with y the column's valid values in ascending order
+ * out[k][m] = y[lo] when g == 0, else fma(g, y[lo + 1] - y[lo], y[lo]) -- numpy's default "linear" quantile as a distribution, the
+ * rounding fixed here.  A zero of either sign is read as +0.  n == 0: every output is NaN.  Order statistics are exact: the bits of
+ * the outputs depend neither on the launch nor on the context.
+ * vag_column_quantiles_dev: d_F is only read; outputs d_out[nq][M], d_valid_out[S] (may be NULL) and d_n_valid[1].
+ * vag_predict_bands_dev: the S rows of d_theta[S][ndim] go through the transformer of the likelihood (10^theta for log-scale
+ * parameters, slot VAG_P_A_V a draw's own A_V, slots above it ignored; no bounds, no priors; the data arrays of spec are not read),
+ * the S models through the path of vag_flux_density_grid_batch_dev on the grid d_t[nt] x d_nu[nnu], every flux is multiplied by
+ * exp(-A_V d_ext[inu]) where A_V != 0 and d_ext (0.4 ln 10 k(lambda_rest) per frequency, or NULL) is given, and the quantile stage runs
+ * on the columns m = inu nt + it.  A draw with a theta that is not finite, or whose model the engine could not evaluate (parameters,
+ * grid limits, an ODE row), is invalid and its fluxes are NaN.  Outputs d_bands[nq][nnu][nt], d_draws[S][nnu][nt] (NULL: the
+ * context's scratch holds them), d_valid[S] (may be NULL), d_n_valid[1].
+ * Both: device pointers, stream-ordered on the context's stream, scratch in the context's grown buffers (the quantile stage itself
+ * never waits for the host).  Refused (the context stays usable): VAG_E_INVALID for a null context, spec or required buffer, nq
+ * outside 1 .. VAG_PREDICT_MAX_Q, a q outside [0, 1] or NaN, S < 1 or M < 1, ndim other than the spec's, a slot that names no
+ * parameter; VAG_E_CAPACITY for S > VAG_PREDICT_MAX_DRAWS or S M > VAG_PREDICT_MAX_VALUES (1 GiB of draws). */
+#define VAG_PREDICT_MAX_DRAWS 4096
+#define VAG_PREDICT_MAX_Q 16
+#define VAG_PREDICT_MAX_VALUES (1ll << 27)
+typedef struct vag_quantile_spec {
+    int32_t nq;
+    int32_t pad;
+    double q[VAG_PREDICT_MAX_Q];
+} vag_quantile_spec;
+int vag_column_quantiles_dev(vag_ctx* ctx, const vag_quantile_spec* qs, const double* d_F, int S, int M, const int32_t* d_valid_in,
+                             double* d_out, int32_t* d_valid_out, int32_t* d_n_valid);
+int vag_predict_bands_dev(vag_ctx* ctx, const vag_fit_spec* spec, const double* d_theta, int S, int ndim, const double* d_t, int nt,
+                          const double* d_nu, int nnu, const double* d_ext, const vag_quantile_spec* qs, double* d_bands,
+                          double* d_draws, int32_t* d_valid, int32_t* d_n_valid);
+
 /* Same with theta/out in HBM.  The data arrays of spec are host pointers: their CONTENT is hashed on every call and they are
  * uploaded (one pinned staging copy) only when it differs from the previous call's, so a sampler loop moves no data.
  * Stream-ordered on the context stream, but host-blocking: the call returns after the batch's device plan has been read back

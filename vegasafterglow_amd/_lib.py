@@ -269,6 +269,27 @@ def chain_entry(lib, name="vag_chain_autocorr_dev"):
                   "the tau of fit(sampler='device')) needs")
 
 
+class QuantileSpec(C.Structure):  # vag_quantile_spec
+    _fields_ = [("nq", C.c_int32), ("pad", C.c_int32), ("q", C.c_double * 16)]
+
+
+PREDICT_MAX_DRAWS, PREDICT_MAX_Q, PREDICT_MAX_VALUES = 4096, 16, 1 << 27  # VAG_PREDICT_MAX_DRAWS, _Q, _VALUES
+PREDICT_ENTRIES = ("vag_column_quantiles_dev", "vag_predict_bands_dev")
+
+
+def predict_tile_columns(n_draws):
+    """vag::predict_tile_columns of csrc/vag_predict.h: adjacent columns per workgroup of the quantile kernel at ``n_draws`` draws."""
+    size = 1
+    while size < n_draws:
+        size <<= 1
+    return max(1, min(16, (128 * 1024) // (8 * size)))
+
+
+def predict_entry(lib, name):
+    """One of the two posterior-predictive entry points."""
+    return _entry(lib, name, "posterior-predictive bands (sampling.column_quantiles_device, Fitter.predict) need")
+
+
 PRIOR_UNIFORM, PRIOR_GAUSSIAN, PRIOR_LOG_UNIFORM, PRIOR_NONE, PRIOR_UNIFORM_RANGE = 0, 1, 2, 3, 4
 
 
@@ -324,6 +345,7 @@ EXPORTS = [
     "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev", "vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev",
     "vag_loglike_split_dev", "vag_tempered_propose_dev", "vag_tempered_accept_dev", "vag_tempered_swap_dev", "vag_tempered_run_dev",
     "vag_move_propose_dev", "vag_move_accept_dev", "vag_move_run_dev", "vag_chain_autocorr_dev",
+    "vag_column_quantiles_dev", "vag_predict_bands_dev",
 ]
 
 _lib = None
@@ -439,6 +461,10 @@ def load():
         lib.vag_tempered_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), tp, C.c_uint64, C.c_int, v, v, v, v, v, v, v, v]
     if hasattr(lib, "vag_chain_autocorr_dev"):  # (detected by symbol: chain autocorrelation)
         lib.vag_chain_autocorr_dev.argtypes = [v, C.POINTER(ChainSpec), v, v, v, v]
+    if hasattr(lib, "vag_predict_bands_dev"):  # (detected by symbol: posterior-predictive bands)
+        lib.vag_column_quantiles_dev.argtypes = [v, C.POINTER(QuantileSpec), v, C.c_int, C.c_int, v, v, v, v]
+        lib.vag_predict_bands_dev.argtypes = [v, C.POINTER(FitSpec), v, C.c_int, C.c_int, v, C.c_int, v, C.c_int, v, C.POINTER(QuantileSpec),
+                                              v, v, v, v]
     lib.vag_flux_density_components4_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_components4_batch.argtypes = [v, _pp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(_dp)]
     lib.vag_flux_density_batch.argtypes = [v, _pp, C.c_int, _dp, _dp, C.c_int, _dp]

@@ -35,6 +35,7 @@
 #include "vag_moves.h"
 #include "vag_sampler_plan.h"
 #include "vag_chain_stats.h"
+#include "vag_predict.h"
 #include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
 #include "vag_flux_plan.h"    // (host only: the launch decisions of the flux stage)
 
@@ -444,6 +445,7 @@ struct vag_ctx {
     DevBuf d_visblk, d_vispart;  // visibility groups of the likelihood (their data: vis below): their 64-visibility blocks, chi^2 partials
     DevBuf d_sampler_prop, d_sampler_fresh, d_sampler_aux;  // the device sampler's run entries (sampler_run), one set for the three moves, as large as the largest run so far: a half-step's proposals [nb][ndim], their ln p or ln L [nb], their Hastings factor or ln prior [nb]
     DevBuf d_chain_stats;  // chain autocorrelation (vag_chain_autocorr_dev): the means [S], the lag sums [L + 1][S], the pooled sums [L + 1][D]
+    DevBuf d_predict;  // posterior-predictive bands (vag_column_quantiles_dev, vag_predict_bands_dev): the draws' A_V [S] and, where the caller keeps none, their fluxes [S][M]; behind them int32: the engine's verdict [S], the validity [S]
     DevBuf d_polspec, d_polstokes;  // polarization groups of the likelihood (their data: pol below): the walkers' spec + its flag, jet-frame I, Q, U
     DevBuf d_icneed;  // [cells] bytes: 1 = some (theta, phi) row's observation window touches the cell (vag_ic_band_kernel)
     bool count_work = false;
@@ -641,6 +643,8 @@ static int ctx_init(vag_ctx* c) {
                            reinterpret_cast<const void*>(vag_flux_series_kernel<FLUX_SYN_IC, true>),
                            reinterpret_cast<const void*>(vag_flux_series_kernel<FLUX_SSC, true>)})
         HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    // the quantile kernel's sorted tile: 16 + VAG_PREDICT_LDS_BYTES at most (vag_predict.h)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(vag_predict_quantile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     {   // Klein-Nishina cross-section table (ComptonSigmaLUT, src/radiation/inverse-compton.cpp:285-300): request-independent
         std::vector<double> lut(2 * KN_LUT_N);
         const double step = (KN_LG2_XMAX - KN_LG2_XMIN) / (double)(KN_LUT_N - 1);
@@ -743,7 +747,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_sampler_prop, &c->d_sampler_fresh, &c->d_sampler_aux, &c->d_chain_stats})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_sampler_prop, &c->d_sampler_fresh, &c->d_sampler_aux, &c->d_chain_stats, &c->d_predict})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -4214,6 +4218,100 @@ int vag_chain_autocorr_dev(vag_ctx* c, const vag_chain_spec* sp, const double* d
                        L, sp->c, d_rho ? d_rho : d_pooled, d_tau, reinterpret_cast<int*>(d_window));
     HIPCHK(hipGetLastError());
     return VAG_OK;
+}
+
+// ---- posterior-predictive bands (kernels and the definition's pieces: vag_predict.h; the definition: the public header) ----
+
+static int quantile_spec_check(const vag_quantile_spec* qs) {
+    if (qs->nq < 1 || qs->nq > VAG_PREDICT_MAX_Q)
+        return set_err(VAG_E_INVALID, "column quantiles: nq must be 1..%d, got %d", VAG_PREDICT_MAX_Q, qs->nq);
+    for (int k = 0; k < qs->nq; ++k)
+        if (!(qs->q[k] >= 0.0 && qs->q[k] <= 1.0))
+            return set_err(VAG_E_INVALID, "column quantiles: q[%d] must be in [0, 1], got %g", k, qs->q[k]);
+    return VAG_OK;
+}
+
+static int quantile_shape_check(int S, long long M) {
+    if (S < 1 || M < 1) return set_err(VAG_E_INVALID, "column quantiles: draws and columns must be >= 1, got %d and %lld", S, M);
+    if (S > VAG_PREDICT_MAX_DRAWS)
+        return set_err(VAG_E_CAPACITY, "column quantiles: %d draws exceed VAG_PREDICT_MAX_DRAWS = %d", S, VAG_PREDICT_MAX_DRAWS);
+    if (M > VAG_PREDICT_MAX_VALUES / S)
+        return set_err(VAG_E_CAPACITY, "column quantiles: draws * columns = %d * %lld values exceed VAG_PREDICT_MAX_VALUES = %lld", S, M,
+                       (long long)VAG_PREDICT_MAX_VALUES);
+    return VAG_OK;
+}
+
+// The two launches of the quantile stage on checked arguments; d_flags: int32 [S] of context scratch for the draws' validity.
+static int column_quantiles(vag_ctx* c, const vag_quantile_spec* qs, const double* d_F, int S, int M, const int* d_valid_in, int* d_flags,
+                            double* d_out, int* d_valid_out, int* d_n_valid) {
+    PredictQ q{};
+    q.nq = qs->nq;
+    for (int k = 0; k < qs->nq; ++k) q.q[k] = qs->q[k];
+    hipLaunchKernelGGL(vag_predict_valid_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, c->stream, d_F, S, M, d_valid_in, d_flags,
+                       d_valid_out);
+    HIPCHK(hipGetLastError());
+    const int P = predict_network_size(S), T = predict_tile_columns(S);
+    const int lanes = std::min(1024, std::max(64, P * T / 2));
+    const size_t lds = 16 + sizeof(double) * (size_t)P * T;  // (<= 16 + VAG_PREDICT_LDS_BYTES)
+    hipLaunchKernelGGL(vag_predict_quantile_kernel, dim3((unsigned)((M + T - 1) / T)), dim3(lanes), lds, c->stream, d_F, S, M, d_flags, P,
+                       T, q, d_out, d_n_valid);
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+int vag_column_quantiles_dev(vag_ctx* c, const vag_quantile_spec* qs, const double* d_F, int S, int M, const int32_t* d_valid_in,
+                             double* d_out, int32_t* d_valid_out, int32_t* d_n_valid) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !qs || !d_F || !d_out || !d_n_valid) return set_err(VAG_E_INVALID, "null context, quantile spec or buffer");
+    if (const int rc = quantile_spec_check(qs)) return rc;
+    if (const int rc = quantile_shape_check(S, M)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_predict.ensure(sizeof(int) * (size_t)S)) return VAG_E_HIP;
+    c->handoff_dirty = true;
+    return column_quantiles(c, qs, d_F, S, M, reinterpret_cast<const int*>(d_valid_in), c->d_predict.as<int>(), d_out,
+                            reinterpret_cast<int*>(d_valid_out), reinterpret_cast<int*>(d_n_valid));
+}
+
+int vag_predict_bands_dev(vag_ctx* c, const vag_fit_spec* spec, const double* d_theta, int S, int ndim, const double* d_t, int nt,
+                          const double* d_nu, int nnu, const double* d_ext, const vag_quantile_spec* qs, double* d_bands, double* d_draws,
+                          int32_t* d_valid, int32_t* d_n_valid) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !spec || !d_theta || !d_t || !d_nu || !qs || !d_bands || !d_n_valid)
+        return set_err(VAG_E_INVALID, "null context, fit spec, quantile spec or buffer");
+    if (ndim != spec->ndim || ndim < 1 || ndim > 16) return set_err(VAG_E_INVALID, "predictive bands: ndim must match spec and be in 1..16");
+    for (int d = 0; d < ndim; ++d) {
+        const int s = spec->slot[d];
+        if (s < 0 || (s >= VAG_P_COUNT && s < VAG_P_RVS_EPS_E) || (s > VAG_P_MAG_Q && s < VAG_P_A_V))
+            return set_err(VAG_E_INVALID, "predictive bands: bad parameter slot %d of parameter %d", s, d);
+    }
+    if (nt < 1 || nnu < 1) return set_err(VAG_E_INVALID, "predictive bands: empty time or frequency array");
+    if (const int rc = quantile_spec_check(qs)) return rc;
+    const long long M = (long long)nnu * nt;
+    if (const int rc = quantile_shape_check(S, M)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n_flux = d_draws ? 0 : (size_t)S * (size_t)M;
+    if (c->d_params.ensure(sizeof(vag_model_params) * (size_t)S)) return VAG_E_HIP;
+    if (c->d_predict.ensure(sizeof(double) * ((size_t)S + n_flux) + sizeof(int) * 2 * (size_t)S)) return VAG_E_HIP;
+    double* d_av = c->d_predict.as<double>();
+    double* draws = d_draws ? d_draws : d_av + S;
+    int* d_ok = reinterpret_cast<int*>(d_av + S + n_flux);
+    int* d_flags = d_ok + S;
+    vag_model_params* d_params = c->d_params.as<vag_model_params>();
+    PredictSlots sl{};
+    for (int d = 0; d < ndim; ++d) sl.slot[d] = spec->slot[d], sl.is_log[d] = spec->is_log[d];
+    c->handoff_dirty = true;
+    hipLaunchKernelGGL(vag_predict_front_kernel, dim3((unsigned)((S + 127) / 128)), dim3(128), 0, c->stream, spec->base, d_theta, S, ndim, sl,
+                       spec->a_v_fixed, d_params, d_av);
+    HIPCHK(hipGetLastError());
+    c->mixed_flags_seen = false;  // (the draws share the base's flags: one flag set)
+    if (const int rc = grid_dev_body(c, d_params, S, d_t, nt, d_nu, nnu, draws)) return rc;
+    hipLaunchKernelGGL(vag_predict_back_kernel, dim3((unsigned)S), dim3(256), 0, c->stream, draws, nnu, nt, d_ext, d_av,
+                       c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(), d_ok);
+    HIPCHK(hipGetLastError());
+    return column_quantiles(c, qs, draws, S, (int)M, d_ok, d_flags, d_bands, reinterpret_cast<int*>(d_valid),
+                            reinterpret_cast<int*>(d_n_valid));
 }
 
 __global__ void vag_model_cost_kernel(const VagGridMeta* __restrict__ meta, int nb, double* __restrict__ cost,

@@ -1804,6 +1804,76 @@ class Fitter:
         nu_min, nu_max = band
         return self.model(best_params, param_defs, resolution).flux(t, nu_min, nu_max, num_points)
 
+    def predict(self, samples, param_defs, t, nu, quantiles=(0.16, 0.5, 0.84), draws=None, seed=0, resolution=None,
+                return_draws=False):
+        """Posterior-predictive quantile bands of the flux density on the grid t[nt] x nu[nnu], in ONE device call
+        (vag_predict_bands_dev; INTEGRATION.md "Posterior-predictive bands"): every drawn row of ``samples`` [N, ndim] (sampler space:
+        ``fit()["samples"]`` fits directly) becomes a model, the models run as one batch, each draw's fluxes take the fitter's
+        extinction law at ``nu`` with the draw's own A_V (as flux_density_grid applies it), and ``quantiles`` are taken over the valid
+        draws at every (nu, t) by the definition of sampling.column_quantiles.  ``draws=None`` uses every row; ``draws=k`` the rows
+        np.sort(np.random.default_rng(seed).choice(N, k, replace=False)).  ``resolution`` overrides the fitter's (phi, theta, t)
+        resolution.  A draw the engine cannot evaluate (or with a parameter that is not finite) is invalid and left out.  Returns a
+        sampling.Prediction; ``return_draws`` adds the draws' own fluxes [S, nnu, nt]."""
+        import torch
+        from . import sampling
+        spec, _, _ = self.build_spec(param_defs)
+        samples = np.asarray(samples, dtype=np.float64)
+        if samples.ndim != 2 or samples.shape[1] != spec.ndim:
+            raise ValueError(f"predict: samples must be [N, {spec.ndim}] in sampler space, got shape {samples.shape}")
+        n_rows = samples.shape[0]
+        q = sampling._quantile_levels(quantiles)
+        if draws is None:
+            if n_rows > sampling.PREDICT_MAX_DRAWS:
+                raise ValueError(f"predict: {n_rows} samples exceed the {sampling.PREDICT_MAX_DRAWS} draws of one call; pass draws= "
+                                 "to take a random subset")
+            index = np.arange(n_rows)
+        else:
+            if int(draws) != draws or draws < 1:
+                raise ValueError(f"predict: draws= must be a whole number >= 1, got {draws}")
+            if draws > n_rows:
+                raise ValueError(f"predict: draws={draws} exceeds the {n_rows} rows of samples")
+            if draws > sampling.PREDICT_MAX_DRAWS:
+                raise ValueError(f"predict: draws={draws} exceeds the {sampling.PREDICT_MAX_DRAWS} draws of one call")
+            index = np.sort(np.random.default_rng(seed).choice(n_rows, int(draws), replace=False))
+        if index.size < 1:
+            raise ValueError("predict: samples holds no row")
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        nu = np.ascontiguousarray(nu, dtype=np.float64)
+        if t.ndim != 1 or t.size < 1 or not np.all(np.isfinite(t) & (t > 0)) or np.any(np.diff(t) < 0):
+            raise ValueError("predict: t must be a non-empty 1-D array of positive finite times in ascending order")
+        if nu.ndim != 1 or nu.size < 1 or not np.all(np.isfinite(nu) & (nu > 0)):
+            raise ValueError("predict: nu must be a non-empty 1-D array of positive finite frequencies")
+        S, nt, nnu = int(index.size), int(t.size), int(nu.size)
+        if S * nt * nnu > sampling.PREDICT_MAX_VALUES:
+            raise ValueError(f"predict: {S} draws on a {nnu} x {nt} grid exceed the {sampling.PREDICT_MAX_VALUES} values of one call; "
+                             "pass a smaller draws= or a coarser grid")
+        if resolution is not None:
+            spec.base.phi_resol, spec.base.theta_resol, spec.base.t_resol = (float(x) for x in resolution)
+        ext = None
+        if self.extinction is not None:  # the law at nu, at the fitter's z, as flux_density_grid takes it
+            lam_rest_cm = (2.99792458e10 / nu) / (1.0 + self.z)
+            ext = np.ascontiguousarray(0.4 * np.log(10.0) * np.asarray(self._k_lambda(lam_rest_cm), dtype=np.float64))
+            if ext.shape != nu.shape:
+                raise ValueError("predict: the extinction law must return one k(lambda) per frequency")
+        lib = _lib.load()
+        entry = _lib.predict_entry(lib, "vag_predict_bands_dev")
+        h, lock = get_context(self.device)
+        dev = torch.device("cuda", self.device)
+        qspec = _lib.QuantileSpec(q.size, 0, (C.c_double * 16)(*q.tolist()))
+        d_theta = torch.as_tensor(np.ascontiguousarray(samples[index]), device=dev)
+        d_t, d_nu = torch.as_tensor(t, device=dev), torch.as_tensor(nu, device=dev)
+        d_ext = torch.as_tensor(ext, device=dev) if ext is not None else None
+        d_bands = torch.empty((q.size, nnu, nt), dtype=torch.float64, device=dev)
+        d_draws = torch.empty((S, nnu, nt), dtype=torch.float64, device=dev) if return_draws else None
+        d_valid = torch.empty((S,), dtype=torch.int32, device=dev)
+        d_n = torch.empty((1,), dtype=torch.int32, device=dev)
+        on_current_stream(lib, h, lock, dev, lambda: _lib.check(entry(
+            h, C.byref(spec), d_theta.data_ptr(), S, spec.ndim, d_t.data_ptr(), nt, d_nu.data_ptr(), nnu,
+            d_ext.data_ptr() if d_ext is not None else None, C.byref(qspec), d_bands.data_ptr(),
+            d_draws.data_ptr() if return_draws else None, d_valid.data_ptr(), d_n.data_ptr())))
+        return sampling.Prediction(q, d_bands.cpu().numpy(), int(d_n.cpu().numpy()[0]), d_valid.cpu().numpy() != 0, index, t, nu,
+                                   d_draws.cpu().numpy() if return_draws else None)
+
     # fitter.py:545-674 (the emcee branch; the stretch-move sampler of vegasafterglow_amd.sampling needs no third-party package)
     def fit(self, param_defs, nwalkers=None, nsteps=1000, nburn=0, seed=0, sampler="host", **kw):
         """sampling.fit on this fitter.  ``sampler="host"``: the numpy stretch move around one device call per half-step;

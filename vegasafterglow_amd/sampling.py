@@ -21,6 +21,8 @@ walkers over a thread pool (VegasAfterglow/fitting/samplers.py:59-106).  Here th
 * ``chain_autocorr_device`` / ``Convergence`` -- the integrated autocorrelation time of every parameter of a chain that lives on the
   device (pooled over the walkers, Sokal's window), and the stopping rule built on it: ``converge=`` makes ``nsteps`` of the three
   device run drivers a maximum.  ``chain_autocorr``, ``chain_mean`` and ``sokal_window`` state the estimate in numpy;
+* ``column_quantiles_device`` -- the quantiles of every column of an array of draws that lives on the device, over its valid draws:
+  the stage behind ``Fitter.predict``'s posterior-predictive bands.  ``column_quantiles`` states it in numpy, to the bit;
 * ``BatchPool`` -- the object handed to ``bilby.run_sampler(pool=...)`` in place of the reference's thread pool
   (samplers.py:146-170): ``pool.map(loglikelihood, points)`` becomes one device call over the whole live-point queue.
 """
@@ -1205,6 +1207,129 @@ def chain_autocorr_device(chain, c: float = 5.0, tol: float = 50.0, max_lag: Opt
         h, C.byref(spec), chain.data_ptr() + 8 * first * int(chain.stride(0)), d_rho.data_ptr() if rho else None, d_tau.data_ptr(),
         d_window.data_ptr())))
     return _chain_record(d_tau.cpu().numpy(), d_window.cpu().numpy(), d_rho.cpu().numpy() if rho else None, n, L, tol)
+
+
+# ---- posterior-predictive bands (INTEGRATION.md "Posterior-predictive bands"): the quantiles of every column of an array of draws over
+#      its valid draws.  The numpy statement first, then the device; Fitter.predict runs the draws' models and this stage in one call. ----
+
+PREDICT_MAX_DRAWS, PREDICT_MAX_Q, PREDICT_MAX_VALUES = 4096, 16, 1 << 27  # VAG_PREDICT_MAX_DRAWS, _Q, _VALUES
+
+Prediction = namedtuple("Prediction", "quantiles bands n_valid valid draw_index t nu draws")
+Prediction.__doc__ = """What Fitter.predict returns: the quantile levels [nq], bands[nq, nnu, nt] (NaN throughout when no draw is valid),
+the number of valid draws, valid[S], draw_index[S] (the rows of ``samples`` that were drawn, ascending), the grid t[nt] and nu[nnu],
+and draws[S, nnu, nt] (None unless asked for; an invalid draw as it came out: NaN where the engine did not evaluate it)."""
+
+
+def _quantile_levels(q) -> np.ndarray:
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or not 1 <= q.size <= PREDICT_MAX_Q:
+        raise ValueError(f"column quantiles: between 1 and {PREDICT_MAX_Q} quantiles are needed, got shape {q.shape}")
+    if not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError(f"column quantiles: every quantile must be in [0, 1], got {q.tolist()}")
+    return q
+
+
+def _quantile_shape(shape):
+    """(S, M) of draws [S, ...] with the trailing dimensions as one row of columns, or the refusal."""
+    if len(shape) < 2:
+        raise ValueError(f"column quantiles: the draws must be [draws, columns] (or [draws, ...]), got shape {tuple(shape)}")
+    S, M = int(shape[0]), int(np.prod(shape[1:], dtype=np.int64))
+    if S < 1 or M < 1:
+        raise ValueError(f"column quantiles: at least one draw and one column are needed, got shape {tuple(shape)}")
+    if S > PREDICT_MAX_DRAWS:
+        raise ValueError(f"column quantiles: {S} draws exceed the maximum of {PREDICT_MAX_DRAWS}")
+    if S * M > PREDICT_MAX_VALUES:
+        raise ValueError(f"column quantiles: {S} draws of {M} columns exceed the maximum of {PREDICT_MAX_VALUES} values")
+    return S, M
+
+
+def _exact_fma(g: float, d: float, a: float) -> float:
+    """g * d + a with one rounding (std::fma), by exact rational arithmetic."""
+    from fractions import Fraction
+    if not (math.isfinite(d) and math.isfinite(a)):
+        return g * d + a
+    try:
+        return float(Fraction(g) * Fraction(d) + Fraction(a))
+    except OverflowError:
+        return math.copysign(math.inf, a)
+
+
+def quantile_rank(q: float, n: int):
+    """(lo, g) of quantile q among n values: h = q * float(n - 1) as one FP64 multiply, lo = floor(h), g = h - lo (vag::predict_rank)."""
+    h = float(np.float64(q) * np.float64(n - 1))
+    lo = math.floor(h)
+    return int(lo), h - lo
+
+
+def column_quantiles(F, q, valid=None):
+    """The quantiles q[nq] of every column of the draws F[S, ...] over the valid draws, in numpy: (Q[nq, ...], valid[S], n_valid).  A
+    draw is valid when its flag is set (``valid``, default: all) and all of its values are finite; with n valid draws and y a column's
+    valid values in ascending order (np.sort; a zero of either sign read as +0), h = q (n - 1), lo = floor(h), g = h - lo and
+    Q = y[lo] where g == 0, else fma(g, y[lo + 1] - y[lo], y[lo]) with the fma evaluated exactly -- numpy's default "linear" quantile
+    with the rounding fixed.  No valid draw: Q is NaN.  The device (column_quantiles_device, Fitter.predict) gives the same bits."""
+    F = np.asarray(F)
+    if F.dtype != np.float64:
+        raise ValueError(f"column quantiles: the draws must be float64, got {F.dtype}")
+    q = _quantile_levels(q)
+    S, M = _quantile_shape(F.shape)
+    flat = F.reshape(S, M)
+    ok = np.all(np.isfinite(flat), axis=1)
+    if valid is not None:
+        flags = np.asarray(valid)
+        if flags.shape != (S,) or flags.dtype.kind not in "biu":
+            raise ValueError(f"column quantiles: valid must be {S} flags (bool or integer), got shape {flags.shape} of {flags.dtype}")
+        ok &= flags != 0
+    n = int(ok.sum())
+    Q = np.full((q.size, M), np.nan)
+    if n > 0:
+        y = flat[ok]
+        y = np.sort(np.where(y == 0.0, 0.0, y), axis=0)
+        for k in range(q.size):
+            lo, g = quantile_rank(q[k], n)
+            Q[k] = y[lo]
+            if g != 0.0:
+                d = y[lo + 1] - y[lo]
+                for m in np.nonzero(d != 0.0)[0]:  # (d == 0: the fma is y[lo])
+                    Q[k, m] = _exact_fma(g, float(d[m]), float(y[lo, m]))
+    return Q.reshape((q.size,) + F.shape[1:]), ok, n
+
+
+def column_quantiles_device(F, q, valid=None, device: int = 0, context=None):
+    """column_quantiles on a contiguous float64 torch tensor F[S, ...] that lives on GPU ``device`` (vag_column_quantiles_dev, on
+    torch's current stream): the draws are read where they are and only Q, the validity and its count come to the host, as numpy
+    arrays.  ``valid``: None or S flags (a torch tensor on the device, or anything numpy takes).  ``context``: a (handle, lock) pair
+    other than the device's shared context."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    from .fitting import on_current_stream
+    from .model import get_context
+    if not isinstance(F, torch.Tensor) or F.dtype != torch.float64:
+        raise ValueError("column quantiles: the draws must be a float64 torch tensor [draws, columns]")
+    dev = torch.device("cuda", device)
+    q = _quantile_levels(q)
+    S, M = _quantile_shape(tuple(F.shape))
+    if F.device != dev:
+        raise ValueError(f"column quantiles: the draws must be on {dev}, they are on {F.device}")
+    if not F.is_contiguous():
+        raise ValueError("column quantiles: the draws must be contiguous; make a contiguous copy")
+    flags = None
+    if valid is not None:
+        flags = valid if isinstance(valid, torch.Tensor) else torch.as_tensor(np.asarray(valid))
+        if tuple(flags.shape) != (S,) or flags.dtype.is_floating_point or flags.dtype.is_complex:
+            raise ValueError(f"column quantiles: valid must be {S} flags (bool or integer), got shape {tuple(flags.shape)} of {flags.dtype}")
+        flags = (flags != 0).to(device=dev, dtype=torch.int32).contiguous()
+    lib = _lib.load()
+    entry = _lib.predict_entry(lib, "vag_column_quantiles_dev")
+    h, lock = get_context(device) if context is None else context
+    spec = _lib.QuantileSpec(q.size, 0, (C.c_double * 16)(*q.tolist()))
+    d_out = torch.empty((q.size, M), dtype=torch.float64, device=dev)
+    d_valid = torch.empty((S,), dtype=torch.int32, device=dev)
+    d_n = torch.empty((1,), dtype=torch.int32, device=dev)
+    on_current_stream(lib, h, lock, dev, lambda: _lib.check(entry(
+        h, C.byref(spec), F.data_ptr(), S, M, flags.data_ptr() if flags is not None else None, d_out.data_ptr(), d_valid.data_ptr(),
+        d_n.data_ptr())))
+    return d_out.cpu().numpy().reshape((q.size,) + tuple(F.shape[1:])), d_valid.cpu().numpy() != 0, int(d_n.cpu().numpy()[0])
 
 
 def _empty_record(ndim):
