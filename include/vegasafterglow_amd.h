@@ -285,8 +285,23 @@ int vag_sky_stokes_image_batch(vag_ctx* ctx, const vag_model_params* params, int
  *                      out {Gamma_th, B, N_p, compression ratio} (n_in = 5, n_out = 4; m2 = 0, an unshocked cell, gives 1, 0, 0, 0);
  *   VAG_MATH_LDS_ADD   in  {slot, value}: the 64 lanes of a wavefront add their values into the slots (integers in [0, 64)) they
  *                      name with one ds_add_f64; out: slot `lane`'s total.
+ * The reverse shock's closed forms and what turns the pair solver's state into cells (vag_rs.h; internal units):
+ *   VAG_MATH_REL_GAMMA in  {g1, g2}; out {rel_Gamma, rel_Gamma_f} (n_in = 2, n_out = 2);
+ *   VAG_MATH_SHOCK_JUMP in {gamma_rel, sigma}; out {downstr_4vel, jump_4vel, jump_4vel_f} (n_in = 2, n_out = 3);
+ *   VAG_MATH_SOUND_SPEED in {G}; out {sound_speed, sound_speed_f} (n_in = 1, n_out = 2);
+ *   VAG_MATH_RVS_STATE in  {Gamma, x4, x3, m3, U3, r, eps4, m4, Gamma4, eps_B, crossing flag (0 / 1), and the cross state the frozen
+ *                      shell reads: V3_comv_x, rho3_x, B3_ordered_x}; out {Gamma_th, B, N_p of rvs_shock_state, then V3_comv, rho3,
+ *                      B3_ordered of rvs_cross_state on the same state} (n_in = 14, n_out = 6);
+ *   VAG_MATH_CROSS_LATTICE in {ts, t_end, t_dec, T0, t_num, base_t_num, k} (0 < ts < t_end, t_dec, T0 > 0, integers 2 <= t_num <= 4096,
+ *                      1 <= base_t_num <= 4096, 0 <= k < t_num); out {node(k), n_pre, n_post, plain} (n_in = 7, n_out = 4);
+ *   VAG_MATH_RVS_EXTRAP in {16 nodes of (r, Gamma_th, B, N_p), inj (an integer in [0, 16])}: one lane runs rvs_early_extrap on the row;
+ *                      out {the 16 (Gamma_th, B, N_p) after the call} (n_in = 65, n_out = 48);
+ *   VAG_MATH_PAIR_INIT in  {Gamma4 (> 1), deps0_dt, dm0_dt, T0 (> 0), t0 (> 0), eps_e_th, medium type (VAG_MEDIUM_ISM, or VAG_MEDIUM_WIND
+ *                      with k = 2), rho_ism, A, r02}; out the 11 entries of PairShock::init_state in state order: Gamma, x4, x3, m2, m3,
+ *                      U2, U3, r, t_comv, eps4, m4 (n_in = 10, n_out = 11).
  * The wave routines (WAVE_PREFIX_SUM, WAVE_SUM, SKY_WAVE_SUM, LDS_ADD) run one wavefront per 64 points and need n % 64 == 0.
- * 0, VAG_E_INVALID (unknown fn, n <= 0, a null pointer, n % 64 != 0 for a wave routine, a bad slot) or VAG_E_HIP. */
+ * 0, VAG_E_INVALID (unknown fn, n <= 0, a null pointer, n % 64 != 0 for a wave routine, a bad slot, a point outside the ranges stated
+ * above: a flag that is not 0 or 1, t_num < 2, k outside the lattice, an unknown medium type, ...) or VAG_E_HIP. */
 enum {
     VAG_MATH_EXP2_FAST = 0, VAG_MATH_EXP2_ODE, VAG_MATH_EXP2_SAT, VAG_MATH_EXP2_OR_ZERO,
     VAG_MATH_LOG2_FAST, VAG_MATH_LOG2_TAB, VAG_MATH_LOG2_TAB_NB,
@@ -299,6 +314,11 @@ enum {
     VAG_MATH_LOG_SLOPE, /* in {8 fluxes, 8 coefficients, K}, out the pivot-form log-slope of the spectral-index term (vag_loglike_index_batch) */
     VAG_MATH_ELEC_CELL, /* syn_cell: the electrons and break frequencies of one cell (vag_cells_kernel) */
     VAG_MATH_FWD_STATE, /* fwd_shock_state: Gamma_th, B, N_p of one forward-shock cell from the raw ODE state (vag_cells_kernel) */
+    VAG_MATH_REL_GAMMA, VAG_MATH_SHOCK_JUMP, VAG_MATH_SOUND_SPEED, /* the reverse shock's closed forms, exact and fast (vag_rs.h) */
+    VAG_MATH_RVS_STATE, /* rvs_shock_state and rvs_cross_state: the reverse-shock cell from the pair solver's state (vag_dynamics_pair_kernel) */
+    VAG_MATH_CROSS_LATTICE, /* CrossLattice: one node and the integers of a row's refined time lattice */
+    VAG_MATH_RVS_EXTRAP, /* rvs_early_extrap on one row of 16 nodes */
+    VAG_MATH_PAIR_INIT, /* PairShock::init_state */
     VAG_MATH_COUNT
 };
 int vag_debug_device_math(vag_ctx* ctx, int fn, const double* in, int n, double* out);

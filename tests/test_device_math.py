@@ -11,6 +11,7 @@ import pytest
 
 import _elecref as E
 import _mathref as R
+import _rsref as RS
 
 pytestmark = pytest.mark.gpu
 
@@ -247,6 +248,13 @@ def test_elementwise_shapes(dev, n):
         assert full.shape == (rows.shape[0], n_out) and not np.isnan(full[:, 0]).any()
         assert np.array_equal(dev(name, rows[:n], n_out), full[:n], equal_nan=True)
         assert np.array_equal(dev(name, rows[-n:], n_out), full[-n:], equal_nan=True)
+    # the reverse shock's closed forms and cell state (tests/test_reverse_state.py): rows of 1 ... 65 -> 2 ... 48 doubles
+    from vegasafterglow_amd import _lib
+    for name, (n_in, n_out) in _lib.MATH_RS_SHAPES.items():
+        rows = RS.probe_set(name)[0]
+        full = dev(name, rows, n_out)
+        assert rows.shape[1] == n_in and full.shape == (rows.shape[0], n_out) and not np.isnan(full).any()
+        assert np.array_equal(dev(name, rows[:n], n_out), full[:n]) and np.array_equal(dev(name, rows[-n:], n_out), full[-n:])
 
 
 # ---------------------------------------------------------------- synchrotron cell
@@ -520,6 +528,32 @@ def test_probe_rejects_bad_arguments(dev):
         assert lib.vag_debug_device_math(ctx, ids[name], px, 1, None) == -1
         assert lib.vag_debug_device_math(None, ids[name], px, 1, py) == -1
         assert lib.vag_debug_device_math(ctx, ids[name], px, 1, py) == 0  # (128 doubles hold one point of either)
+    # the reverse-state routines: the same argument checks, and the points they are not defined on
+    from vegasafterglow_amd import _lib
+    for name, (n_in, n_out) in _lib.MATH_RS_SHAPES.items():
+        good = np.ascontiguousarray(RS.probe_set(name)[0][:2])
+        pg, po = good.ctypes.data_as(_dp), np.zeros(2 * n_out).ctypes.data_as(_dp)
+        assert lib.vag_debug_device_math(ctx, ids[name], pg, 2, po) == 0
+        assert lib.vag_debug_device_math(ctx, ids[name], pg, 0, po) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], pg, -3, po) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], None, 2, po) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], pg, 2, None) == -1
+        assert lib.vag_debug_device_math(None, ids[name], pg, 2, po) == -1
+
+    def rejected(name, col, value, row=1):
+        pts = np.ascontiguousarray(RS.probe_set(name)[0][:2]).copy()
+        pts[row, col] = value
+        return lib.vag_debug_device_math(ctx, ids[name], pts.ctypes.data_as(_dp), 2, np.zeros(2 * _lib.MATH_RS_SHAPES[name][1]).ctypes.data_as(_dp)) == -1
+    assert rejected("rvs_state", 10, 2.0) and rejected("rvs_state", 10, 0.5) and rejected("rvs_state", 10, -1.0) and rejected("rvs_state", 10, np.nan)
+    t_num = RS.probe_set("cross_lattice")[0][1, 4]
+    assert rejected("cross_lattice", 4, 1.0) and rejected("cross_lattice", 4, 0.0) and rejected("cross_lattice", 4, 7.5)
+    assert rejected("cross_lattice", 4, 4097.0) and rejected("cross_lattice", 5, 0.0) and rejected("cross_lattice", 5, np.nan)
+    assert rejected("cross_lattice", 6, -1.0) and rejected("cross_lattice", 6, t_num) and rejected("cross_lattice", 6, 0.5)
+    assert rejected("cross_lattice", 0, 0.0) and rejected("cross_lattice", 1, 0.0) and rejected("cross_lattice", 0, np.inf)
+    assert rejected("rvs_extrap", 64, 17.0) and rejected("rvs_extrap", 64, -1.0) and rejected("rvs_extrap", 64, 2.5)
+    assert rejected("pair_init", 6, 2.0) and rejected("pair_init", 6, -1.0) and rejected("pair_init", 6, 0.5)
+    assert rejected("pair_init", 0, 1.0) and rejected("pair_init", 3, 0.0) and rejected("pair_init", 4, -1.0)
+    assert rejected("rvs_state", 10, 2.0, row=0), "a bad first point"
     assert lib.vag_debug_device_math(ctx, max(ids.values()) + 1, px, 1, py) == -1
     bad = np.zeros((64, 2))
     bad[5, 0] = 64.0

@@ -57,7 +57,12 @@ MATH = {name: i for i, name in enumerate([
     "syn_cell", "ic_cell", "wave_prefix_sum", "wave_sum", "sky_wave_sum", "lds_add", "log_ndtr"])}
 # VAG_MATH_* appended after VAG_MATH_LOG_NDTR.  They have a mapping of their own: MATH is pinned to end with log_ndtr
 # (tests/test_limits_host.py), and the ids of both mappings are the enum's, one numbering.
-MATH_MORE = {name: len(MATH) + i for i, name in enumerate(["poisson_deviance", "log_slope", "elec_cell", "fwd_state"])}
+MATH_MORE = {name: len(MATH) + i for i, name in enumerate([
+    "poisson_deviance", "log_slope", "elec_cell", "fwd_state",
+    "rel_gamma", "shock_jump", "sound_speed", "rvs_state", "cross_lattice", "rvs_extrap", "pair_init"])}
+# [n_in, n_out] per point of the routines of MATH_MORE that tests/_rsref.py restates (vag_debug_math.h)
+MATH_RS_SHAPES = {"rel_gamma": (2, 2), "shock_jump": (2, 3), "sound_speed": (1, 2), "rvs_state": (14, 6), "cross_lattice": (7, 4),
+                  "rvs_extrap": (65, 48), "pair_init": (10, 11)}
 
 P_A_V = 1000  # VAG_P_A_V
 # VAG_P_SKY_*: the sky placement of the centroid and visibility groups (vag_loglike_sky_batch / _vis_batch), not Model fields either

@@ -3154,6 +3154,8 @@ int vag_debug_device_math(vag_ctx* c, int fn, const double* in, int n, double* o
         for (int i = 0; i < n; ++i)
             if (!(in[2 * (size_t)i] >= 0 && in[2 * (size_t)i] < 64 && in[2 * (size_t)i] == std::floor(in[2 * (size_t)i])))
                 return set_err(VAG_E_INVALID, "point %d: lds_add_f64 slot must be an integer in [0, 64)", i);
+    for (int i = 0; i < n; ++i)
+        if (const char* why = math_point_error(fn, in + (size_t)i * n_in)) return set_err(VAG_E_INVALID, "device routine %d, point %d: %s", fn, i, why);
     HIPCHK(hipSetDevice(c->device));
     struct Bufs {
         DevBuf in, out, col;

@@ -19,6 +19,16 @@ constexpr int MATH_ELEC_IN = 12;                      // t_comv, r, Gamma_th, B,
 constexpr int MATH_ELEC_OUT = 11;                     // gamma_m, gamma_c, gamma_a, gamma_M, N_e, column_den, nu_m, nu_c, nu_a, nu_M, I_nu_max
 constexpr int MATH_FWD_IN = 5;                        // Gamma, rho, U_th, m2, eps_B
 constexpr int MATH_FWD_OUT = 4;                       // Gamma_th, B, N_p, compression
+constexpr int MATH_RVS_IN = 14;                       // Gamma, x4, x3, m3, U3, r, eps4, m4, Gamma4, eps_B, crossing, V3_comv_x, rho3_x, B3_ordered_x
+constexpr int MATH_RVS_OUT = 6;                       // Gamma_th, B, N_p (rvs_shock_state), V3_comv, rho3, B3_ordered (rvs_cross_state)
+constexpr int MATH_LAT_IN = 7;                        // ts, t_end, t_dec, T0, t_num, base_t_num, k
+constexpr int MATH_LAT_OUT = 4;                       // node(k), n_pre, n_post, plain
+constexpr int MATH_LAT_MAX = 4096;                    // largest t_num / base_t_num the probe takes
+constexpr int MATH_EXT_NODES = 16;                    // nodes of a VAG_MATH_RVS_EXTRAP row
+constexpr int MATH_EXT_IN = 4 * MATH_EXT_NODES + 1;   // 16 x (r, Gamma_th, B, N_p), inj
+constexpr int MATH_EXT_OUT = 3 * MATH_EXT_NODES;      // 16 x (Gamma_th, B, N_p)
+constexpr int MATH_INIT_IN = 10;                      // Gamma4, deps0_dt, dm0_dt, T0, t0, eps_e_th, medium type, rho_ism, A, r02
+constexpr int MATH_INIT_OUT = RS_N;                   // the state of PairShock::init_state
 
 // [n_in, n_out] per point of routine `fn` (VAG_MATH_*); 0 for an unknown routine
 inline int math_n_in(int fn) {
@@ -30,6 +40,12 @@ inline int math_n_in(int fn) {
         case VAG_MATH_LOG_SLOPE: return 2 * INDEX_MAX_NODES + 1;  // 8 fluxes, 8 coefficients, K
         case VAG_MATH_ELEC_CELL: return MATH_ELEC_IN;
         case VAG_MATH_FWD_STATE: return MATH_FWD_IN;
+        case VAG_MATH_REL_GAMMA: return 2;    // g1, g2
+        case VAG_MATH_SHOCK_JUMP: return 2;   // gamma_rel, sigma
+        case VAG_MATH_RVS_STATE: return MATH_RVS_IN;
+        case VAG_MATH_CROSS_LATTICE: return MATH_LAT_IN;
+        case VAG_MATH_RVS_EXTRAP: return MATH_EXT_IN;
+        case VAG_MATH_PAIR_INIT: return MATH_INIT_IN;
         default: return (fn >= 0 && fn < VAG_MATH_COUNT) ? 1 : 0;
     }
 }
@@ -39,11 +55,37 @@ inline int math_n_out(int fn) {
         case VAG_MATH_IC_CELL: return MATH_IC_OUT;
         case VAG_MATH_ELEC_CELL: return MATH_ELEC_OUT;
         case VAG_MATH_FWD_STATE: return MATH_FWD_OUT;
+        case VAG_MATH_REL_GAMMA: return 2;    // rel_Gamma, rel_Gamma_f
+        case VAG_MATH_SHOCK_JUMP: return 3;   // downstr_4vel, jump_4vel, jump_4vel_f
+        case VAG_MATH_SOUND_SPEED: return 2;  // sound_speed, sound_speed_f
+        case VAG_MATH_RVS_STATE: return MATH_RVS_OUT;
+        case VAG_MATH_CROSS_LATTICE: return MATH_LAT_OUT;
+        case VAG_MATH_RVS_EXTRAP: return MATH_EXT_OUT;
+        case VAG_MATH_PAIR_INIT: return MATH_INIT_OUT;
         default: return (fn >= 0 && fn < VAG_MATH_COUNT) ? 1 : 0;
     }
 }
 inline bool math_is_wave(int fn) {
     return fn == VAG_MATH_WAVE_PREFIX_SUM || fn == VAG_MATH_WAVE_SUM || fn == VAG_MATH_SKY_WAVE_SUM || fn == VAG_MATH_LDS_ADD;
+}
+// What is wrong with point `a` of routine `fn` (host side, before the launch), or nullptr: the integer and flag arguments that index or
+// branch on the device, and the ranges the routines are defined on.
+inline const char* math_point_error(int fn, const double* a) {
+    auto whole = [](double v, double lo, double hi) { return v >= lo && v <= hi && v == std::floor(v); };
+    auto pos = [](double v) { return std::isfinite(v) && v > 0; };
+    switch (fn) {
+        case VAG_MATH_RVS_STATE: return (a[10] == 0 || a[10] == 1) ? nullptr : "the crossing flag must be 0 or 1";
+        case VAG_MATH_CROSS_LATTICE:
+            if (!(pos(a[0]) && pos(a[1]) && a[0] < a[1] && pos(a[2]) && pos(a[3]))) return "need 0 < ts < t_end and t_dec, T0 > 0, all finite";
+            if (!whole(a[4], 2, MATH_LAT_MAX)) return "t_num must be an integer in [2, 4096]";
+            if (!whole(a[5], 1, MATH_LAT_MAX)) return "base_t_num must be an integer in [1, 4096]";
+            return whole(a[6], 0, a[4] - 1) ? nullptr : "k must be an integer in [0, t_num)";
+        case VAG_MATH_RVS_EXTRAP: return whole(a[MATH_EXT_IN - 1], 0, MATH_EXT_NODES) ? nullptr : "inj must be an integer in [0, 16]";
+        case VAG_MATH_PAIR_INIT:
+            if (!(a[6] == VAG_MEDIUM_ISM || a[6] == VAG_MEDIUM_WIND)) return "unknown medium type";
+            return (std::isfinite(a[0]) && a[0] > 1 && pos(a[3]) && pos(a[4])) ? nullptr : "need Gamma4 > 1, T0 > 0 and t0 > 0, all finite";
+        default: return nullptr;
+    }
 }
 
 // One point per lane, 64-lane workgroups (the wave routines' callers run wavefronts of 64; n % 64 == 0 for them).  The softplus / log2
@@ -143,6 +185,61 @@ __global__ void __launch_bounds__(64) vag_math_probe_kernel(int fn, int n, const
             const FwdState s = fwd_shock_state(a[0], a[1], a[2], a[3], a[4]);
             double* r = out + (size_t)i * MATH_FWD_OUT;
             r[0] = s.Gamma_th, r[1] = s.B, r[2] = s.N_p, r[3] = s.compression;
+            return;
+        }
+        case VAG_MATH_REL_GAMMA:
+            if (ok) out[2 * (size_t)i] = rel_Gamma(in[2 * (size_t)i], in[2 * (size_t)i + 1]), out[2 * (size_t)i + 1] = rel_Gamma_f(in[2 * (size_t)i], in[2 * (size_t)i + 1]);
+            return;
+        case VAG_MATH_SHOCK_JUMP: {
+            if (!ok) return;
+            const double g = in[2 * (size_t)i], sigma = in[2 * (size_t)i + 1];
+            double* r = out + 3 * (size_t)i;
+            r[0] = downstr_4vel(g, sigma), r[1] = jump_4vel(g, sigma), r[2] = jump_4vel_f(g, sigma);
+            return;
+        }
+        case VAG_MATH_SOUND_SPEED:
+            if (ok) out[2 * (size_t)i] = sound_speed(in[i]), out[2 * (size_t)i + 1] = sound_speed_f(in[i]);
+            return;
+        case VAG_MATH_RVS_STATE: {
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_RVS_IN;
+            const RvsCross held = {a[11], a[12], a[13]};
+            const RvsState s = rvs_shock_state(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10] != 0, held);
+            const RvsCross x = rvs_cross_state(a[0], a[1], a[2], a[5], a[6], a[7], a[8]);
+            double* r = out + (size_t)i * MATH_RVS_OUT;
+            r[0] = s.Gamma_th, r[1] = s.B, r[2] = s.N_p, r[3] = x.V3_comv, r[4] = x.rho3, r[5] = x.B3_ordered;
+            return;
+        }
+        case VAG_MATH_CROSS_LATTICE: {
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_LAT_IN;
+            CrossLattice lat;
+            lat.init(a[0], a[1], a[2], a[3], (int)a[4], (int)a[5]);
+            double* r = out + (size_t)i * MATH_LAT_OUT;
+            r[0] = lat.node((int)a[6]), r[1] = lat.n_pre, r[2] = lat.n_post, r[3] = lat.plain;
+            return;
+        }
+        case VAG_MATH_RVS_EXTRAP: {  // the row in this lane's own copy, nodes 4 doubles apart
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_EXT_IN;
+            double w[4 * MATH_EXT_NODES];
+            for (int q = 0; q < 4 * MATH_EXT_NODES; ++q) w[q] = a[q];
+            rvs_early_extrap(w + 1, w + 2, w + 3, w, 4, MATH_EXT_NODES, (int)a[MATH_EXT_IN - 1]);
+            double* r = out + (size_t)i * MATH_EXT_OUT;
+            for (int q = 0; q < MATH_EXT_NODES; ++q) r[3 * q] = w[4 * q + 1], r[3 * q + 1] = w[4 * q + 2], r[3 * q + 2] = w[4 * q + 3];
+            return;
+        }
+        case VAG_MATH_PAIR_INIT: {
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_INIT_IN;
+            PairShock eq = {};
+            eq.med.type = (int)a[6], eq.med.rho_ism = a[7], eq.med.A = a[8], eq.med.r02 = a[9], eq.med.k_m = 2;
+            eq.Gamma4 = a[0], eq.deps0_dt = a[1], eq.dm0_dt = a[2], eq.T0 = a[3];
+            eq.cs4 = sound_speed(eq.Gamma4);  // as vag_dynamics_pair_kernel sets them
+            eq.beta4 = gamma_to_beta(eq.Gamma4);
+            double s[RS_N];
+            eq.init_state(s, a[4], a[5]);
+            for (int q = 0; q < RS_N; ++q) out[(size_t)i * MATH_INIT_OUT + q] = s[q];
             return;
         }
         default: break;

@@ -150,15 +150,80 @@ VAG_DEV double sound_speed_f(double G) {
     return sqrt1(dmax(ad * (ad - 1) * (G - 1) * rcp1(1 + (G - 1) * ad), 0.0)) * C_C;
 }
 
-VAG_DEV double downstr_B(double eps_B, double rho_up, double B_up, double Gamma_th, double comp) {  // shock-physics.h:354-360
-    const double e_th = (Gamma_th - 1) * (rho_up * comp) * C_C2;
-    return sqrt(8 * C_PI * eps_B * e_th) + B_up * comp;
+// magnetisation of the unshocked shell from the state (PairShock::shell_sigma)
+VAG_DEV double shell_sigma_of(double eps4, double m4, double Gamma4) {
+    const double sigma = eps4 / (Gamma4 * m4 * C_C2) - 1;
+    return (sigma > SIGMA_CUT) ? sigma : 0;
 }
 
-VAG_DEV double Gamma_therm(double U_th, double mass, bool limiter) {  // shock-physics.h:290-301
-    if (mass == 0) return 1;
-    const double G = U_th / (mass * C_C2) + 1;
-    return (limiter && G < GAMMA_CUT) ? 1 : G;
+// ---- from the solved state to the cells the electron stage reads (tests/_rsref.py restates these three; tests/test_reverse_state.py
+//      holds them to it through VAG_MATH_RVS_STATE / VAG_MATH_RVS_EXTRAP) ----
+struct RvsCross {  // FRShockEqn::save_cross_state: what the frozen shell keeps from the crossing time
+    double V3_comv, rho3, B3_ordered;
+};
+struct RvsState {
+    double Gamma_th, B, N_p;
+};
+
+// save_cross_state, reverse-shock.tpp:297-310, on the exact closed forms
+VAG_DEV RvsCross rvs_cross_state(double Gamma, double x4, double x3, double r, double eps4, double m4, double Gamma4) {
+    RvsCross x;
+    x.V3_comv = r * r * x3;
+    const double sigma4 = shell_sigma_of(eps4, m4, Gamma4);
+    const double comp34 = jump_4vel(rel_Gamma(Gamma4, Gamma), sigma4);
+    const double rho4 = m4 / (r * r * x4);
+    x.rho3 = rho4 * comp34;
+    x.B3_ordered = sqrt((4 * C_PI * C_C2) * sigma4 * rho4) * comp34;
+    return x;
+}
+
+// save_rvs_shock_state, reverse-shock.tpp:393-426: compute_Gamma_therm (shock-physics.h:290-301, the limiter while crossing only) and
+// compute_downstr_B (shock-physics.h:354-360) on rcp_fast / sqrt_fast.  crossing: the shell is still being crossed (k <= injection_idx);
+// after it the frozen shell expands adiabatically from the cross state.
+VAG_DEV RvsState rvs_shock_state(double Gamma, double x4, double x3, double m3, double U3, double r, double eps4, double m4, double Gamma4,
+                                 double eps_B, bool crossing, const RvsCross& x) {
+    RvsState o;
+    const double Gth3 = m3 == 0 ? 1.0 : U3 * rcp_fast(m3 * C_C2) + 1;
+    o.N_p = m3 / C_MP;
+    if (crossing) {
+        const double sigma4 = shell_sigma_of(eps4, m4, Gamma4);
+        const double comp34 = jump_4vel_f(rel_Gamma_f(Gamma4, Gamma), sigma4);
+        const double rho4 = m4 * rcp_fast(r * r * x4);
+        const double Gth = Gth3 < GAMMA_CUT ? 1.0 : Gth3;  // the limiter of compute_Gamma_therm
+        const double B4 = sigma4 > 0 ? sqrt_fast((4 * C_PI * C_C2) * sigma4 * rho4) : 0.0;
+        const double e_th = (Gth - 1) * (rho4 * comp34) * C_C2;
+        o.Gamma_th = Gth;
+        o.B = sqrt_fast(8 * C_PI * eps_B * e_th) + B4 * comp34;
+    } else {
+        const double V3_comv = r * r * x3;
+        const double comp = x.V3_comv * rcp_fast(V3_comv);
+        const double e_th = (Gth3 - 1) * (x.rho3 * comp) * C_C2;
+        o.Gamma_th = Gth3;
+        o.B = sqrt_fast(8 * C_PI * eps_B * e_th) + x.B3_ordered * comp;
+    }
+    return o;
+}
+
+// reverse_shock_early_extrap, reverse-shock.tpp:428-469, on one row: node k of a quantity is base[k * stride].  The nodes before the first
+// one whose Gamma_th passed GAMMA_CUT (idx_cut) take the power law in r through nodes idx_cut and idx_cut + 2.
+VAG_DEV void rvs_early_extrap(double* rG, double* rB, double* rNp, const double* rr, long long stride, int nt, int inj) {
+    int idx_cut = 0;
+    for (; idx_cut < nt; ++idx_cut)
+        if (rG[idx_cut * stride] > GAMMA_CUT) break;
+    if (idx_cut == 0 || idx_cut >= nt - 2 || idx_cut >= inj) return;
+    const long long c = idx_cut * stride, c2 = (idx_cut + 2) * stride;
+    const double log2_r = log2(rr[c]);
+    const double log2_Gth = log2(rG[c] - 1), log2_B = log2(rB[c]), log2_Np = log2(rNp[c]);
+    const double dl = log2(rr[c2]) - log2_r;
+    const double g_slope = (log2(rG[c2] - 1) - log2_Gth) / dl;
+    const double B_slope = (log2(rB[c2]) - log2_B) / dl;
+    const double N_slope = (log2(rNp[c2]) - log2_Np) / dl;
+    for (int q = 0; q < idx_cut; q++) {
+        const double dlog2_r = log2(rr[q * stride]) - log2_r;
+        rG[q * stride] = 1 + exp2(log2_Gth + g_slope * dlog2_r);
+        rB[q * stride] = exp2(log2_B + B_slope * dlog2_r);
+        rNp[q * stride] = exp2(log2_Np + N_slope * dlog2_r);
+    }
 }
 
 // enclosed_thermal_energy (generic Simpson form for every medium), shock-physics.h:427-437
@@ -190,10 +255,7 @@ struct PairShock {
         w = w < 0.0 ? 0.0 : (w > 1.0 ? 1.0 : w);
         return w * w * (3.0 - 2.0 * w);
     }
-    VAG_DEV double shell_sigma(const double* s) const {
-        const double sigma = s[RS_EPS4] / (Gamma4 * s[RS_M4] * C_C2) - 1;
-        return (sigma > SIGMA_CUT) ? sigma : 0;
-    }
+    VAG_DEV double shell_sigma(const double* s) const { return shell_sigma_of(s[RS_EPS4], s[RS_M4], Gamma4); }
     VAG_DEV bool crossing_complete(const double* s, double t) const {  // reverse-shock.tpp:46-58
         if (s[RS_M3] < 0.999 * s[RS_M4]) return false;
         return !(inject_weight(t) > 1e-6);

@@ -102,7 +102,7 @@ vag_dynamics_pair_kernel(const vag_model_params* __restrict__ params, int nb, co
     const double eps_e_th = P.radiative_fireball ? P.eps_e : 0.0;
 
     int inj = nt;  // Shock::injection_idx default = t_size
-    double V3_comv_x = 0, rho3_x = 0, B3_ordered_x = 0;  // FRShockEqn::save_cross_state
+    RvsCross cross = {0, 0, 0};  // FRShockEqn::save_cross_state
     auto save_both = [&](int k, double t_k, const double* q) {
         {   // save_fwd_shock_state (forward-shock.tpp:151-173): region 2
             const double comp = compression_fwd(q[RS_GAMMA]);
@@ -111,22 +111,10 @@ vag_dynamics_pair_kernel(const vag_model_params* __restrict__ params, int nb, co
             const double e_th = (Gth - 1) * (rho * comp) * C_C2;
             put(F, k, t_k, q[RS_TCOMV], q[RS_R], q[RS_GAMMA], Gth, sqrt_fast(8 * C_PI * P.eps_B * e_th), q[RS_M2] / C_MP);
         }
-        const double Gth3 = q[RS_M3] == 0 ? 1.0 : q[RS_U3] * rcp_fast(q[RS_M3] * C_C2) + 1;
-        if (k <= inj) {  // save_rvs_shock_state (reverse-shock.tpp:393-426): still crossing
-            const double sigma4 = eq.shell_sigma(q);
-            const double comp34 = jump_4vel_f(rel_Gamma_f(eq.Gamma4, q[RS_GAMMA]), sigma4);
-            const double rho4 = q[RS_M4] * rcp_fast(q[RS_R] * q[RS_R] * q[RS_X4]);
-            const double Gth = Gth3 < GAMMA_CUT ? 1.0 : Gth3;  // the limiter of compute_Gamma_therm
-            const double B4 = sigma4 > 0 ? sqrt_fast((4 * C_PI * C_C2) * sigma4 * rho4) : 0.0;
-            const double e_th = (Gth - 1) * (rho4 * comp34) * C_C2;
-            put(R, k, t_k, q[RS_TCOMV], q[RS_R], q[RS_GAMMA], Gth, sqrt_fast(8 * C_PI * P.rvs_eps_B * e_th) + B4 * comp34, q[RS_M3] / C_MP);
-        } else {  // after the crossing: frozen shell expanding adiabatically
-            const double V3_comv = q[RS_R] * q[RS_R] * q[RS_X3];
-            const double comp = V3_comv_x * rcp_fast(V3_comv);
-            const double e_th = (Gth3 - 1) * (rho3_x * comp) * C_C2;
-            put(R, k, t_k, q[RS_TCOMV], q[RS_R], q[RS_GAMMA], Gth3, sqrt_fast(8 * C_PI * P.rvs_eps_B * e_th) + B3_ordered_x * comp,
-                q[RS_M3] / C_MP);
-        }
+        // save_rvs_shock_state: still crossing up to the injection index, the frozen shell after it
+        const RvsState rs = rvs_shock_state(q[RS_GAMMA], q[RS_X4], q[RS_X3], q[RS_M3], q[RS_U3], q[RS_R], q[RS_EPS4], q[RS_M4], eq.Gamma4,
+                                            P.rvs_eps_B, k <= inj, cross);
+        put(R, k, t_k, q[RS_TCOMV], q[RS_R], q[RS_GAMMA], rs.Gamma_th, rs.B, rs.N_p);
     };
 
     const double t_first = node(0), t_last = node(nt - 1);
@@ -203,14 +191,7 @@ vag_dynamics_pair_kernel(const vag_model_params* __restrict__ params, int nb, co
                         }
                         st.interp(t_hi, q);
                         t_cross = t_hi;
-                        {   // save_cross_state, reverse-shock.tpp:297-310
-                            V3_comv_x = q[RS_R] * q[RS_R] * q[RS_X3];
-                            const double sigma4 = eq.shell_sigma(q);
-                            const double comp34 = jump_4vel(rel_Gamma(eq.Gamma4, q[RS_GAMMA]), sigma4);
-                            const double rho4 = q[RS_M4] / (q[RS_R] * q[RS_R] * q[RS_X4]);
-                            rho3_x = rho4 * comp34;
-                            B3_ordered_x = sqrt((4 * C_PI * C_C2) * sigma4 * rho4) * comp34;
-                        }
+                        cross = rvs_cross_state(q[RS_GAMMA], q[RS_X4], q[RS_X3], q[RS_R], q[RS_EPS4], q[RS_M4], eq.Gamma4);
                         crossing = false;
                         pending = true;
                     }
@@ -278,14 +259,7 @@ vag_dynamics_pair_kernel(const vag_model_params* __restrict__ params, int nb, co
             }
             st.interp(t_hi, q);
             t_cross = t_hi;
-            {   // save_cross_state, reverse-shock.tpp:297-310
-                V3_comv_x = q[RS_R] * q[RS_R] * q[RS_X3];
-                const double sigma4 = eq.shell_sigma(q);
-                const double comp34 = jump_4vel(rel_Gamma(eq.Gamma4, q[RS_GAMMA]), sigma4);
-                const double rho4 = q[RS_M4] / (q[RS_R] * q[RS_R] * q[RS_X4]);
-                rho3_x = rho4 * comp34;
-                B3_ordered_x = sqrt((4 * C_PI * C_C2) * sigma4 * rho4) * comp34;
-            }
+            cross = rvs_cross_state(q[RS_GAMMA], q[RS_X4], q[RS_X3], q[RS_R], q[RS_EPS4], q[RS_M4], eq.Gamma4);
             crossing = false;
             pending = true;
         }
@@ -319,29 +293,7 @@ vag_dynamics_pair_kernel(const vag_model_params* __restrict__ params, int nb, co
     row_status[row] = status;
     if (status > 0 && status < 4) atomicAdd(fail + status, 1);
     // reverse_shock_early_extrap, reverse-shock.tpp:428-469 (this lane re-reads its own row)
-    {
-        const double* Gth = R + VS_GAMMA_TH * n_cells;
-        int idx_cut = 0;
-        for (; idx_cut < nt; ++idx_cut)
-            if (Gth[idx_cut] > GAMMA_CUT) break;
-        if (idx_cut == 0 || idx_cut >= nt - 2 || idx_cut >= inj) return;
-        double* rB = R + VS_B * n_cells;
-        double* rNp = R + VS_NP * n_cells;
-        double* rG = R + VS_GAMMA_TH * n_cells;
-        const double* rr = R + VS_R * n_cells;
-        const double log2_r = log2(rr[idx_cut]);
-        const double log2_Gth = log2(rG[idx_cut] - 1), log2_B = log2(rB[idx_cut]), log2_Np = log2(rNp[idx_cut]);
-        const double dl = log2(rr[idx_cut + 2]) - log2_r;
-        const double g_slope = (log2(rG[idx_cut + 2] - 1) - log2_Gth) / dl;
-        const double B_slope = (log2(rB[idx_cut + 2]) - log2_B) / dl;
-        const double N_slope = (log2(rNp[idx_cut + 2]) - log2_Np) / dl;
-        for (int q = 0; q < idx_cut; q++) {
-            const double dlog2_r = log2(rr[q]) - log2_r;
-            rG[q] = 1 + exp2(log2_Gth + g_slope * dlog2_r);
-            rB[q] = exp2(log2_B + B_slope * dlog2_r);
-            rNp[q] = exp2(log2_Np + N_slope * dlog2_r);
-        }
-    }
+    rvs_early_extrap(R + VS_GAMMA_TH * n_cells, R + VS_B * n_cells, R + VS_NP * n_cells, R + VS_R * n_cells, 1, nt, inj);
 }
 
 }  // namespace vag
