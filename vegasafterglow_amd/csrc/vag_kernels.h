@@ -925,6 +925,34 @@ VAG_DEV void stage_photon_block(double* __restrict__ s_par, const double* __rest
         s_par[(q - par * K) * VAG_NPAR + par] = src[(size_t)par * K_all + (q - par * K)];
     }
 }
+#ifndef VAG_HOST_DEBUG
+// The same for the split form (whole rows: K_all == K, so word q of the block goes to s_par[k][par] with q = par K + k), in one round
+// trip to HBM instead of one per word of a lane: a lane requests all its words of a chunk, then stores them.  A chunk is
+// FLUX_SPLIT_STAGE words per lane, all there are up to K = 227; a longer block takes another chunk.  (par, k) of a lane's next word
+// advance by (FLUX_THREADS / K, FLUX_THREADS % K) with a carry; its first from the float quotient, exact as in stage_photon_block.
+constexpr int FLUX_SPLIT_STAGE = 8;
+__device__ __forceinline__ void stage_photon_block_split(double* __restrict__ s_par, const double* __restrict__ src, int K, int tid) {
+    const int total = VAG_NPAR * K;
+    const int dq_p = FLUX_THREADS / K, dq_k = FLUX_THREADS - dq_p * K;
+    int par = (int)(((float)tid + 0.5f) / (float)K);
+    int k = tid - par * K;
+#pragma unroll 1
+    for (int q0 = tid; q0 < total; q0 += FLUX_SPLIT_STAGE * FLUX_THREADS) {
+        double v[FLUX_SPLIT_STAGE];
+        int dst[FLUX_SPLIT_STAGE];
+#pragma unroll
+        for (int i = 0; i < FLUX_SPLIT_STAGE; ++i) {
+            v[i] = src[min(q0 + i * FLUX_THREADS, total - 1)];  // past the block: its last word again, not stored
+            dst[i] = k * VAG_NPAR + par;
+            par += dq_p, k += dq_k;
+            if (k >= K) k -= K, ++par;
+        }
+#pragma unroll
+        for (int i = 0; i < FLUX_SPLIT_STAGE; ++i)
+            if (q0 + i * FLUX_THREADS < total) s_par[dst[i]] = v[i];
+    }
+}
+#endif
 
 // Bracket of one requested time in a row's sorted log2 observer times: kk with t_row[kk] <= tq < t_row[kk + 1] (iterate_to,
 // observer.h:309-313, 405-433) and the position w inside the interval, shared by all nu.  The caller has checked
@@ -1514,7 +1542,11 @@ struct FluxSplitLds {
     }
 };
 
-__device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, const int blk) {
+__device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, const int blk
+#ifdef VAG_FLUX_STAMPS
+                                                , const long long c_claim  // the wavefront's cycle count before the item's claim
+#endif
+) {
     constexpr int THREADS = FLUX_THREADS, NB = FLUX_SPLIT_B, AL = FLUX_SPLIT_A * 64, BL = NB * 64, NE = FLUX_SPLIT_E, EL = NE * 64;
     const VagGridMeta* Mp = a.meta + m;
     if (Mp->status != 0) return;
@@ -1558,7 +1590,7 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
 
     auto stage = [&](int rep) {  // all lanes: the photon block of a representative row
         const double* src = a.cellpar + (a.cell_off[m] + (long long)rep * K) * VAG_NPAR;
-        stage_photon_block(s_par, src, K, K, tid, THREADS);
+        stage_photon_block_split(s_par, src, K, tid);
     };
     // The rows of the item and the one barrier per row.  Interval n (n = -1: the pipeline fills; n = n_rows - 1: it drains):
     //   A team: spectra of row n + 1        B team: interpolation of row n        EAT wavefronts, behind their own work: row n + 2
@@ -1567,6 +1599,10 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     // (`late_eat`) follows alone.  Both teams run this with the same block-uniform decisions, so their barriers pair up.
 #ifdef VAG_FLUX_STAMPS  // developer aid: where a wavefront's cycles go (profiles/flux_stamps.sh); c_rel is its last barrier release
     long long c_rel = __builtin_readcyclecounter();
+    // between the rows: cycles from the item's claim to the release before its first row ("fill"), and from the release that finds
+    // another photon block to the release behind its staging and EAT step ("restage", with the count of them)
+    long long c_fill = 0, c_restage = 0;
+    int n_restage = 0;
 #define VAG_STAMP_RELEASE() c_rel = __builtin_readcyclecounter()
 #else
 #define VAG_STAMP_RELEASE()
@@ -1580,6 +1616,9 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
         late_eat(j1, i1, 0, 0);
         __syncthreads();
         VAG_STAMP_RELEASE();
+#ifdef VAG_FLUX_STAMPS
+        c_fill = c_rel - c_claim;
+#endif
         int tb0 = 2, tb1 = 0, tb2 = 1;
         for (int n = -1; n < n_rows; ++n) {
             int j2 = j1, i2 = i1 + 1;
@@ -1591,12 +1630,18 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
             __syncthreads();
             VAG_STAMP_RELEASE();
             if (__builtin_expect(!same, 0)) {  // once per theta row
+#ifdef VAG_FLUX_STAMPS
+                const long long c_found = c_rel;
+#endif
                 stage(rep2);
                 staged_rep = rep2;
                 __syncthreads();
                 late_eat(j2, i2, n + 2, tb2);
                 __syncthreads();
                 VAG_STAMP_RELEASE();
+#ifdef VAG_FLUX_STAMPS
+                c_restage += c_rel - c_found, ++n_restage;
+#endif
             }
             j1 = j2, i1 = i2;
             tb0 = tb1, tb1 = tb2, tb2 = tb2 == 2 ? 0 : tb2 + 1;
@@ -1727,14 +1772,12 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
             spectra_of(n, j1, i1, tb1);
             if (eat_now) eat(j2, i2, n + 2, tb2);
         };
-#ifdef VAG_FLUX_STAMPS
-        const long long c_item = __builtin_readcyclecounter();
-#endif
         pipeline(spectra, eat);
 #ifdef VAG_FLUX_STAMPS
         if (m == 0 && blk == 1 && lane == 0)
-            printf("split A wave %d rows %d passes %d boundary-loop cycles %lld  per pass %lld  item %lld  prologue %lld  eat-prologue %lld\n", wave,
-                   n_rows_done, n_pass, c_loop, c_loop / max(n_pass, 1), (long long)__builtin_readcyclecounter() - c_item, c_pro, c_pro_eat);
+            printf("split A wave %d rows %d passes %d boundary-loop cycles %lld  per pass %lld  item %lld  prologue %lld  eat-prologue %lld  fill %lld  restage %lld in %d\n",
+                   wave, n_rows_done, n_pass, c_loop, c_loop / max(n_pass, 1), (long long)__builtin_readcyclecounter() - c_claim, c_pro, c_pro_eat,
+                   c_fill, c_restage, n_restage);
 #endif
     } else {
         const int btid = tid - AL;
@@ -1750,7 +1793,6 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
         }
 #ifdef VAG_FLUX_STAMPS
         long long c_interp = 0, c_pro = 0;  // c_pro: cycles from barrier release to the first bracket
-        const long long c_item = __builtin_readcyclecounter();
 #endif
         auto interp = [&](int n, int, int, int, int, int tb0, int, int, bool) {
 #ifdef VAG_FLUX_STAMPS
@@ -1808,8 +1850,8 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
         pipeline(interp, [](int, int, int, int) {});
 #ifdef VAG_FLUX_STAMPS
         if (m == 0 && blk == 1 && lane == 0)
-            printf("split B wave %d interpolation cycles %lld  item %lld  prologue %lld\n", wave, c_interp, (long long)__builtin_readcyclecounter() - c_item,
-                   c_pro);
+            printf("split B wave %d interpolation cycles %lld  item %lld  prologue %lld  fill %lld  restage %lld in %d\n", wave, c_interp,
+                   (long long)__builtin_readcyclecounter() - c_claim, c_pro, c_fill, c_restage, n_restage);
 #endif
         // partial grid of this workgroup, stored [l][idx] like the reference's F_nu (nu outer)
         double* my_partial = a.partial + ((size_t)m * a.max_blocks + blk) * ((size_t)nt * nnu);
@@ -1832,13 +1874,20 @@ vag_flux_grid_split_kernel(FluxArgs a) {
     for (int i = threadIdx.x; i < SP_LDS_DOUBLES; i += FLUX_THREADS) lds[i] = a.sp_table[i];
     int* s_it = reinterpret_cast<int*>(lds + SP_LDS_DOUBLES);  // first word of s_par: an item writes it only after its first barrier
     for (;;) {
+#ifdef VAG_FLUX_STAMPS
+        const long long c_claim = __builtin_readcyclecounter();
+#endif
         __syncthreads();  // the previous item is done with the LDS
         if (threadIdx.x == 0) *s_it = __hip_atomic_fetch_add(a.work, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         const int it = __builtin_amdgcn_readfirstlane(*s_it);
         if (it >= a.n_items) break;
         const int r = it / a.max_blocks;
+#ifdef VAG_FLUX_STAMPS
+        flux_split_item(a, a.order[r], it - r * a.max_blocks, c_claim);
+#else
         flux_split_item(a, a.order[r], it - r * a.max_blocks);
+#endif
     }
 }
 #endif  // VAG_HOST_DEBUG
