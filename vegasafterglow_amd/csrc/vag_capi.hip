@@ -38,6 +38,7 @@
 #include "vag_predict.h"
 #include "vag_fit_request.h"  // (host only: set_err, the scans, FitRequest)
 #include "vag_flux_plan.h"    // (host only: the launch decisions of the flux stage)
+#include "vag_stage_plan.h"   // (host only: the arithmetic of the model stages, the grouping by flags)
 
 using namespace vag;
 
@@ -479,7 +480,6 @@ struct vag_ctx {
     VagDevPlan hint{};            // the last plan the host read back: sizes the next call of the same batch size in advance
     int hint_nb = 0;
     bool hint_valid = false;
-    bool allow_spec = false;      // set by the entry points that end with finish_speculation()
     bool spec_pending = false;    // the current call was planned from the hint and has not been verified yet
     VagDevPlan* d_hplan = nullptr;  // device address of h_plan
     int plan_seq = 0;
@@ -546,6 +546,17 @@ struct StageScope {
     ~StageScope() {
         if (span >= 0) (void)hipEventRecord(c->prof_ev[c->prof_spans[span].e1], c->stream);
     }
+};
+
+// A call mode: a context field that holds `v` for a scope and its earlier value after it, whichever way the scope is left
+// (ppb_pin, pending_bands, ic_soft_fail, ic_all_cells).
+template <class T>
+struct CallMode {
+    T& field;
+    const T before;
+    CallMode(T& f, T v) : field(f), before(f) { field = v; }
+    ~CallMode() { field = before; }
+    CallMode(const CallMode&) = delete;
 };
 
 extern "C" {
@@ -973,38 +984,20 @@ int wait_plan(vag_ctx* c) {
     return VAG_OK;
 }
 
-// ODE rows per wavefront of the dynamics kernels (one lane integrates one row).  Measured (profiles/r02_rpw.txt): fewer
-// rows per wavefront do NOT pay for the general kernel -- at 256 VGPRs only one wavefront fits a SIMD and the dispatcher
-// does not spread single-wavefront workgroups evenly -- so full wavefronts stay the default; the knob remains for tuning.
-// The coupled forward + reverse shock solver keeps its retry loop inside the step (a wavefront repeats an attempt while ANY of its
-// lanes rejects) and one wavefront fills a SIMD (256 VGPRs): fewer rows per wavefront mean fewer repeated attempts and -- while the
-// batch has fewer wavefronts than the chip has SIMDs -- more SIMDs at work.  VAG_PAIR_RPW overrides (tuning).
-int pair_rows_per_wave(int rows, const char* env = "VAG_PAIR_RPW") {
-    if (const char* e = vag_hook(env)) {
-        const int v = std::atoi(e);
-        if (v > 0) return std::min(v, 64);
-    }
-    // Measured (profiles/debug/pair_rpw_probe.py: one configs[2] model = 65 rows / 512 models = 33 k rows; general_rpw_probe.py: one
-    // spreading Gaussian jet = 49 rows / 256 of them = 12.5 k rows; same bits whatever the choice): 64 rows per wavefront 3.18 / 3.48 ms
-    // and 1.85 / 1.98 ms, 32: 2.83 / 5.35 and 1.57 / 2.28, 16: 2.68 / 5.89 and 1.77 / 2.30, 8: 2.32 / 16.3 and 1.41 / 4.36 -- fewer rows pay
-    // for a handful of models and cost as soon as there are a few hundred wavefronts (a 256-VGPR wavefront owns its SIMD and the
-    // dispatcher does not spread them evenly), so only small batches are split up.
-    for (int rpw = 8; rpw < 64; rpw *= 2)
-        if ((rows + rpw - 1) / rpw <= 64) return rpw;
-    return 64;
+// a hook as the decisions of vag_flux_plan.h / vag_stage_plan.h take it: std::atoi of the variable, HOOK_UNSET where it is not set
+static int hook_int(const char* name) {
+    const char* e = vag_hook(name);
+    return e ? std::max(std::atoi(e), HOOK_UNSET + 1) : HOOK_UNSET;
 }
-int dyn_rows_per_wave(int rows) {
-    (void)rows;
-    if (const char* e = vag_hook("VAG_DYN_RPW")) {
-        const int v = std::atoi(e);
-        if (v > 0) return std::min(v, 64);
-    }
-    return 64;
+static DynHooks dyn_hooks() {  // (DynHooks' members in their order)
+    return {hook_int("VAG_DYN_GENERAL"), hook_int("VAG_DYN_REFILL"), hook_int("VAG_DYN_REFILL_MIN"), hook_int("VAG_DYN_REFILL_WGS"),
+            hook_int("VAG_PAIR_RPW"), hook_int("VAG_DYN_RPW")};
 }
 
 // Stage 1-3: adaptive grid -> blast-wave dynamics -> per-cell radiation, for nb models whose
 // parameters are already in HBM.  d_tminmax holds the observer-time extrema [s].
-int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool want_details) {
+// may_plan: the caller ends with finish_speculation() and repeats the call where that says so
+int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool want_details, bool may_plan = false) {
     c->handoff_dirty = true;  // work is about to be queued on the context stream (ApiLock::~ApiLock)
     c->order_active = c->order_next;  // only a likelihood call that permuted its walkers sets order_next (vag_ctx::d_order)
     c->order_next = false;
@@ -1036,16 +1029,9 @@ int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool 
     // (0.716 vs 0.715 ms per 128-walker call) and slower when calls are queued back to back without reading ln L
     // (0.775 vs 0.693 ms), because its flux launches are sized for the margin -- so waiting is the default.
     static const bool plan_ahead = vag_hook("VAG_PLAN_AHEAD") != nullptr;
-    const bool spec = plan_ahead && c->allow_spec && !want_details && c->hint_valid && c->hint_nb == nb;
-    int cap_rows = INT32_MAX, cap_k = INT32_MAX, cap_pairs = INT32_MAX;
-    long long cap_cells = INT64_MAX;
-    if (spec) {
-        cap_rows = c->hint.rows + c->hint.rows / 4 + 64;
-        cap_cells = c->hint.cells + c->hint.cells / 4 + 4096;
-        cap_k = std::min(VAG_MAX_TIME, c->hint.max_k + c->spec_margin_k);  // LDS of the flux kernels scales with it: keep it tight
-        cap_pairs = c->hint.max_pairs + c->hint.max_pairs / 2 + 64;
-        c->spec_cap_k = cap_k;
-    }
+    const bool spec = may_plan_ahead(plan_ahead, may_plan, want_details, c->hint_valid, c->hint_nb, nb);
+    const StageCaps cap = spec ? plan_ahead_caps(c->hint, c->spec_margin_k) : StageCaps{};
+    if (spec) c->spec_cap_k = cap.k;
     if (c->d_plan.ensure(sizeof(VagDevPlan) + 64)) return VAG_E_HIP;
     if (!c->h_plan.p) {  // pinned, host-mapped, COHERENT (fine-grained: a store from a running kernel reaches the host after a
                          // system-scope fence, not only at the end of the queue): the grid kernel's last wavefront writes the
@@ -1074,7 +1060,7 @@ int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool 
                            c->d_rep_start.as<int>(), c->d_tdec.as<double>(), c->d_geo_th.as<double>(), c->d_geo_ph.as<double>(),
                            c->d_fail.as<int>(), reinterpret_cast<int*>(reinterpret_cast<char*>(c->d_plan.p) + sizeof(VagDevPlan)),
                            c->d_row_off.as<int>(), c->d_cell_off.as<long long>(), c->d_plan.as<VagDevPlan>(), c->d_hplan, ++c->plan_seq,
-                           cap_rows, cap_cells, cap_k, cap_pairs, spec ? (c->hint.flags_first < 0 ? 0 : c->hint.flags_first) : -1,
+                           cap.rows, cap.cells, cap.k, cap.pairs, spec ? plan_flags(c->hint) : -1,
                            spec ? c->hint.dyn_class : 0, c->d_cost_f.as<float>(), c->d_rowgeo.as<double>(),
                            large == 2 ? c->d_gridscratch.as<GridSharedHuge>() : nullptr);
     };
@@ -1113,14 +1099,14 @@ int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool 
                                               "(the flux entry points do that themselves)");
         rows = hp->rows, cells = hp->cells, pairs = hp->pairs, eat = hp->eat, max_k = hp->max_k, max_pairs = hp->max_pairs;
         n_ok = hp->n_ok, n_invalid = hp->n_invalid, n_capacity = hp->n_capacity, dyn_class = hp->dyn_class;
-        flags = hp->flags_first < 0 ? 0 : hp->flags_first;
+        flags = plan_flags(*hp);
         c->hint = *hp;
         c->hint_nb = nb;
         c->hint_valid = hp->n_ok > 0;
     } else {  // launch geometry and strides from the capacities, kernel choice from the previous call's flags
-        rows = cap_rows, cells = cap_cells, max_k = cap_k, max_pairs = cap_pairs;
+        rows = cap.rows, cells = cap.cells, max_k = cap.k, max_pairs = cap.pairs;
         pairs = c->hint.pairs, eat = c->hint.eat, n_ok = c->hint.n_ok, dyn_class = c->hint.dyn_class;
-        flags = c->hint.flags_first < 0 ? 0 : c->hint.flags_first;
+        flags = plan_flags(c->hint);
         c->spec_pending = true;
     }
     c->batch_flags = flags;
@@ -1150,8 +1136,10 @@ int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool 
         HIPCHK(hipEventRecord(c->ev[3], st));
         return VAG_OK;
     }
-    const bool rvs = (c->batch_flags & VAG_FLAG_RVS) != 0;
-    const bool spreading = (c->batch_flags & VAG_FLAG_SPREADING) != 0;
+    const DynHooks dyn_hk = dyn_hooks();
+    const DynPlan dyn = dyn_plan(c->batch_flags, dyn_class, rows, c->n_cus, dyn_hk);  // which solver, how many rows per wavefront
+    const bool rvs = dyn.family == DYN_PAIR, spreading = dyn.spreading;
+    const int rpw = dyn.rows_per_wave;
     if (c->d_shock.ensure(sizeof(double) * (size_t)cells * VAG_NSHOCK)) return VAG_E_HIP;
     if (c->d_row_status.ensure(sizeof(int) * (size_t)rows)) return VAG_E_HIP;
     Layout lay{c->d_row_off.as<int>(), c->d_cell_off.as<long long>()};
@@ -1163,35 +1151,22 @@ int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool 
         if (c->d_params_rvs.ensure(sizeof(vag_model_params) * (size_t)nb)) return VAG_E_HIP;
         hipLaunchKernelGGL(vag_rvs_params_kernel, dim3((nb + 127) / 128), dim3(128), 0, st, d_params, nb,
                            c->d_params_rvs.as<vag_model_params>());
-        const int prw = pair_rows_per_wave(rows);
-        hipLaunchKernelGGL(vag_dynamics_pair_kernel, dim3((rows + prw - 1) / prw), dim3(64), 0, st, d_params, nb,
+        hipLaunchKernelGGL(vag_dynamics_pair_kernel, dim3((rows + rpw - 1) / rpw), dim3(64), 0, st, d_params, nb,
                            c->d_meta.as<VagGridMeta>(), c->d_theta.as<double>(), c->d_rep_start.as<int>(),
                            c->d_tdec.as<double>(), lay, rows, c->d_shock.as<double>(), c->d_shock_r.as<double>(), cells,
                            c->d_inj.as<int>(), c->d_row_status.as<int>(), c->d_fail.as<int>(), c->d_phi.as<double>(),
-                           c->d_tminmax.as<double>(), prw);
-    } else if (dyn_class == 0 && !vag_hook("VAG_DYN_GENERAL")) {  // the common case: flat attempt loop, raw saves
+                           c->d_tminmax.as<double>(), rpw);
+    } else if (dyn.family != DYN_GENERAL) {  // the common case: flat attempt loop, raw saves
         raw_shock = true;
-        // Batches beyond one and a half rounds of the plain kernel's integrator slots (four two-wavefront workgroups per CU) take the
-        // persistent kernel whose lanes refill from a row queue and save inline (two integrators per SIMD instead of one integrator and
-        // its saver); smaller ones keep the plain kernel, which is built for the latency of one row (no preparation pass on the chain).
-        // Measured (profiles/r06_refill_probe.txt, C4 walkers, ODE stage plain / refill): 53.9 k rows 0.37 / 0.41 ms, 108.6 k rows
-        // 0.72 / 0.62, 218 k rows 1.22 / 0.89, 433.8 k rows 2.28 / 1.73.  The rows are queued longest first (vag_dyn_fast.h: a row's step
-        // count is predictable from its start record), by a counting sort of three small kernels.  VAG_DYN_REFILL=0 / 1 forces either; same bits (tests/test_gpu_parity.py).
-        bool refill = rows >= 96 * 4LL * c->n_cus;
-        if (const char* e = vag_hook("VAG_DYN_REFILL")) refill = std::atoi(e) != 0;
-        if (refill) {
-            int refill_min = 16;  // finished lanes a wavefront collects before it takes new rows (a refill is ~200 instructions for the whole wavefront; 1 / 4 / 8 / 16: 1.97 / 1.80 / 1.80 / 1.73 ms per 8192 walkers)
-            if (const char* e = vag_hook("VAG_DYN_REFILL_MIN")) refill_min = std::max(1, std::min(64, std::atoi(e)));
-            // records | the sorted queue (rows ints) | the queue's two counters | histogram / offsets [DYN_BUCKETS][chunks] | length class per row
-            const size_t n_chunks = ((size_t)rows + DYN_CHUNK - 1) / DYN_CHUNK;
-            const size_t rec_bytes = sizeof(double) * (size_t)rows * DYN_ROWREC, ord_bytes = sizeof(int) * (((size_t)rows + 1) & ~(size_t)1);
-            const size_t hist_bytes = sizeof(unsigned) * DYN_BUCKETS * n_chunks;
-            if (c->d_dynrec.ensure(rec_bytes + ord_bytes + 16 + hist_bytes + (size_t)rows)) return VAG_E_HIP;
+        if (dyn.family == DYN_REFILL) {  // the rows are queued longest first (vag_dyn_fast.h: a row's step count is predictable from its start record), by a counting sort of three small kernels
+            const DynRecLayout l = dynrec_layout(rows, {DYN_ROWREC, DYN_BUCKETS, DYN_CHUNK});
+            const size_t n_chunks = l.n_chunks;
+            if (c->d_dynrec.ensure(l.bytes)) return VAG_E_HIP;
             char* dyn_base = static_cast<char*>(c->d_dynrec.p);
-            int* d_dynorder = reinterpret_cast<int*>(dyn_base + rec_bytes);
-            unsigned* d_queue = reinterpret_cast<unsigned*>(dyn_base + rec_bytes + ord_bytes);
-            unsigned* d_hist = d_queue + 4;
-            signed char* d_cls = reinterpret_cast<signed char*>(dyn_base + rec_bytes + ord_bytes + 16 + hist_bytes);
+            int* d_dynorder = reinterpret_cast<int*>(dyn_base + l.order);
+            unsigned* d_queue = reinterpret_cast<unsigned*>(dyn_base + l.queue);
+            unsigned* d_hist = reinterpret_cast<unsigned*>(dyn_base + l.hist);
+            signed char* d_cls = reinterpret_cast<signed char*>(dyn_base + l.cls);
             hipLaunchKernelGGL(vag_dyn_prep_kernel, dim3((unsigned)n_chunks), dim3(DYN_CHUNK), 0, st, d_params, nb, c->d_meta.as<VagGridMeta>(),
                                c->d_theta.as<double>(), c->d_rep_start.as<int>(), c->d_tdec.as<double>(), lay, rows, c->d_shock.as<double>(), cells,
                                c->d_row_status.as<int>(), c->d_dynrec.as<double>(), d_cls, d_hist);
@@ -1203,23 +1178,18 @@ int run_model_stages(vag_ctx* c, const vag_model_params* d_params, int nb, bool 
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vag_dynamics_refill_kernel<false>, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 8;
                 c->dyn_refill_wg_per_cu = per_cu;
             }
-            long long slots = (long long)c->dyn_refill_wg_per_cu * c->n_cus;
-            if (const char* e = vag_hook("VAG_DYN_REFILL_WGS")) slots = std::max(1, std::atoi(e));
-            const unsigned wgs = (unsigned)std::max<long long>(1, std::min<long long>((rows + 63) / 64, slots));
+            const unsigned wgs = refill_workgroups(rows, c->dyn_refill_wg_per_cu, c->n_cus, dyn_hk.refill_wgs);
             hipLaunchKernelGGL(kern, dim3(wgs), dim3(64), 0, st, c->d_dynrec.as<double>(), rows, c->d_shock.as<double>(), cells,
-                               c->d_row_status.as<int>(), c->d_sptab.as<double>(), refill_min, c->d_fail.as<int>(), d_queue, d_dynorder);
+                               c->d_row_status.as<int>(), c->d_sptab.as<double>(), dyn.refill_min, c->d_fail.as<int>(), d_queue, d_dynorder);
         } else {
-        const int rpw = dyn_rows_per_wave(rows);
         hipLaunchKernelGGL(c->count_work ? vag_dynamics_fast_kernel<true> : vag_dynamics_fast_kernel<false>, dim3((rows + rpw - 1) / rpw),
                            dim3(128), 0, st, d_params, nb, c->d_meta.as<VagGridMeta>(), c->d_theta.as<double>(), c->d_rep_start.as<int>(),
                            c->d_tdec.as<double>(), lay, rows, c->d_shock.as<double>(), cells, c->d_row_status.as<int>(),
                            c->d_sptab.as<double>(), rpw, c->d_fail.as<int>());
         }
     } else {
-        const bool inject = (c->batch_flags & VAG_FLAG_MAGNETAR) != 0;
-        auto kern = spreading ? (inject ? vag_dynamics_kernel<true, true> : vag_dynamics_kernel<true, false>)
-                              : (inject ? vag_dynamics_kernel<false, true> : vag_dynamics_kernel<false, false>);
-        const int rpw = pair_rows_per_wave(rows, "VAG_DYN_RPW");  // (the general solver retries inside the step like the pair solver)
+        auto kern = spreading ? (dyn.inject ? vag_dynamics_kernel<true, true> : vag_dynamics_kernel<true, false>)
+                              : (dyn.inject ? vag_dynamics_kernel<false, true> : vag_dynamics_kernel<false, false>);
         hipLaunchKernelGGL(kern, dim3((rows + rpw - 1) / rpw), dim3(64), 0, st, d_params, nb, c->d_meta.as<VagGridMeta>(),
                            c->d_theta.as<double>(), c->d_rep_start.as<int>(), c->d_tdec.as<double>(), lay, rows,
                            c->d_shock.as<double>(), cells, c->d_row_status.as<int>(), c->d_sptab.as<double>(), rpw,
@@ -1258,10 +1228,7 @@ static FluxBatch flux_batch(const vag_ctx* c, int nb) {  // (FluxBatch's members
 }
 
 static FluxHooks flux_hooks() {  // (FluxHooks' members in their order)
-    auto get = [](const char* name) {
-        const char* e = vag_hook(name);
-        return e ? std::max(std::atoi(e), HOOK_UNSET + 1) : HOOK_UNSET;
-    };
+    const auto get = hook_int;
     return {get("VAG_PAIRS_PER_BLOCK"), get("VAG_FLUX_K_CAP"), get("VAG_FLUX_WIDE"), get("VAG_GRID_ROWWISE"),
             get("VAG_GRID_ROW_PER_WORKGROUP"), get("VAG_FLUX_PERSISTENT"), get("VAG_FLUX_SPLIT"), get("VAG_NO_FUSED"),
             get("VAG_FORCE_FUSED"), get("VAG_SERIES_ROW_PER_WAVE"), get("VAG_FIT_WAVES_PER_BLOCK"), get("VAG_SERIES_PPB"),
@@ -1719,10 +1686,8 @@ int check_ic_status(vag_ctx* c, int nb) {
 // clamped band: those models' tables unclamped).  `pass(rebuild)` builds the tables and runs the flux pass; returns the C-ABI code.
 template <class Pass>
 int ssc_attempts(vag_ctx* c, int nb, Pass pass) {
-    struct Reset {
-        vag_ctx* c;
-        ~Reset() { c->ic_all_cells = false; }
-    } reset{c};
+    // (false on entry -- nothing but the loop below sets it, and it is off again behind the pass --, so what the guard puts back is false)
+    CallMode<bool> all_cells(c->ic_all_cells, false);
     bool rebuild = false;
     int rc = VAG_OK;
     for (int attempt = 0; attempt < 3; ++attempt) {
@@ -2638,14 +2603,14 @@ int finish_speculation(vag_ctx* c) {
     c->spec_pending = false;
     VagDevPlan* hp = c->h_plan.as<VagDevPlan>();
     if (int rcw = wait_plan(c)) return rcw;  // the grid stage finished long ago: the later stages keep running behind this check
-    const int flags = hp->flags_first < 0 ? 0 : hp->flags_first, hflags = c->hint.flags_first < 0 ? 0 : c->hint.flags_first;
-    if (hp->overflow || hp->flags_mixed || (hp->n_ok > 0 && (flags != hflags || hp->dyn_class != c->hint.dyn_class))) {
+    const PlanVerdict v = plan_ahead_verdict(*hp, c->hint, c->spec_cap_k, c->spec_margin_k);
+    if (v.repeat) {
+        const int flags = plan_flags(*hp), hflags = plan_flags(c->hint);
         if (vag_hook("VAG_DEBUG_SPEC"))
             std::fprintf(stderr, "[vag] planned-ahead call repeated: overflow %d mixed %d flags %d/%d dyn %d/%d rows %d cells %lld max_k %d (cap %d) max_pairs %d; hint rows %d cells %lld max_k %d max_pairs %d\n",
                          hp->overflow, hp->flags_mixed, flags, hflags, hp->dyn_class, c->hint.dyn_class, hp->rows, (long long)hp->cells,
                          hp->max_k, c->spec_cap_k, hp->max_pairs, c->hint.rows, (long long)c->hint.cells, c->hint.max_k, c->hint.max_pairs);
-        if (hp->overflow && hp->max_k > c->spec_cap_k)  // the lattice outgrew its head room: plan the next calls with more
-            c->spec_margin_k = std::min(32, 2 * c->spec_margin_k + 2);
+        c->spec_margin_k = v.margin_k;  // (more where the lattice outgrew its head room)
         c->hint_valid = false;
         return VAG_RETRY;
     }
@@ -2697,18 +2662,7 @@ static bool uniform_flags(const vag_model_params* params, int nb) {
 template <class Call>
 static int run_flag_groups(const vag_model_params* params, int nb, const std::vector<OutRows>& outs, Call call,
                            const std::vector<OutRows>& ins = {}) {
-    std::vector<int> keys;
-    std::vector<std::vector<int>> groups;
-    for (int m = 0; m < nb; ++m) {
-        size_t g = 0;
-        while (g < keys.size() && keys[g] != params[m].flags) ++g;
-        if (g == keys.size()) {
-            keys.push_back(params[m].flags);
-            groups.emplace_back();
-        }
-        groups[g].push_back(m);
-    }
-    for (const std::vector<int>& idx : groups) {
+    for (const std::vector<int>& idx : group_by_flags(nb, [&](int m) { return params[m].flags; })) {
         const int ng = (int)idx.size();
         std::vector<vag_model_params> gp(ng);
         for (int i = 0; i < ng; ++i) gp[i] = params[idx[i]];
@@ -2736,6 +2690,66 @@ static int run_flag_groups(const vag_model_params* params, int nb, const std::ve
                                 sizeof(double) * outs[q].stride);
     }
     return VAG_OK;
+}
+
+// ---- the frame of the host-pointer model requests: a batch of models, times and (but for a band) frequencies on the host, outputs
+//      of one row per model.  An entry point keeps its own argument checks and its body -- the request it makes on device pointers;
+//      everything between the two is here. ----
+struct DevRows {  // where outs[first .. first + count) live on the device: in `buf`, [count][nb][stride] (sized for all of them)
+    DevBuf vag_ctx::*buf;
+    int first, count;
+};
+struct HostRequest {
+    const vag_model_params* params;
+    int nb;
+    const double* t;
+    int nt;
+    const double* nu;
+    int nnu;
+    std::vector<OutRows> outs;  // the caller's output arrays (p NULL: not requested)
+    std::vector<DevRows> dev;   // their device side; none: the body delivers to outs itself (sky_request copies in chunks)
+    bool times = true;          // collect_times behind the call (the flux events it reads are not recorded by the sky passes)
+    std::vector<OutRows> ins = {};  // per-model input arrays, gathered per group where the batch is split by flags
+    bool has_nu = true;  // false: the body makes its own frequencies (a band), d_nu is not touched here and nu is not looked at
+};
+// check_host_inputs -> a batch of mixed flags: every flag set as a request of its own, same body -> the device -> d_params, d_t, d_nu
+// and the output buffers, the uploads -> body(request, d_params, d_outs) -> the downloads -> the wait -> collect_times -> check_status.
+// d_outs[i]: the device array of outs[i], NULL where it is not requested or has no device side.
+template <class Body>
+static int host_request(vag_ctx* c, const HostRequest& r, Body body) {
+    int rc = check_host_inputs(r.params, r.nb, r.t, r.nt);
+    if (rc) return rc;
+    if (!uniform_flags(r.params, r.nb))
+        return run_flag_groups(r.params, r.nb, r.outs, [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
+            HostRequest g = r;
+            g.params = gp, g.nb = ng;
+            for (size_t i = 0; i < g.outs.size(); ++i) g.outs[i].p = o[i];
+            for (size_t i = 0; i < g.ins.size(); ++i) g.ins[i].p = o[g.outs.size() + i];
+            return host_request(c, g, body);
+        }, r.ins);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t nb = (size_t)r.nb;
+    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
+    if (c->d_t.ensure(sizeof(double) * r.nt)) return VAG_E_HIP;
+    if (r.has_nu && c->d_nu.ensure(sizeof(double) * r.nnu)) return VAG_E_HIP;
+    for (const DevRows& d : r.dev)
+        if ((c->*d.buf).ensure(sizeof(double) * d.count * nb * r.outs[d.first].stride)) return VAG_E_HIP;
+    HIPCHK(hipMemcpyAsync(c->d_params.p, r.params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_t.p, r.t, sizeof(double) * r.nt, hipMemcpyHostToDevice, c->stream));
+    if (r.has_nu) HIPCHK(hipMemcpyAsync(c->d_nu.p, r.nu, sizeof(double) * r.nnu, hipMemcpyHostToDevice, c->stream));
+    std::vector<double*> d_outs(r.outs.size(), nullptr);
+    for (const DevRows& d : r.dev)
+        for (int i = 0; i < d.count; ++i)
+            if (r.outs[d.first + i].p) d_outs[d.first + i] = (c->*d.buf).as<double>() + i * nb * r.outs[d.first].stride;
+    rc = body(r, c->d_params.as<vag_model_params>(), d_outs.data());
+    if (rc) return rc;
+    if (!r.dev.empty()) {
+        for (size_t i = 0; i < d_outs.size(); ++i)
+            if (d_outs[i]) HIPCHK(hipMemcpyAsync(r.outs[i].p, d_outs[i], sizeof(double) * nb * r.outs[i].stride, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (r.times) (void)collect_times(c);
+    return check_status(c, r.nb);
 }
 
 extern "C" {
@@ -2786,17 +2800,7 @@ static int flux_dev_by_flags(vag_ctx* c, const vag_model_params* d_params, int n
     std::vector<int> flags(nb), perm;
     HIPCHK(hipMemcpyAsync(flags.data(), c->d_mix_flags.p, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    std::vector<int> keys;
-    std::vector<std::vector<int>> groups;
-    for (int m = 0; m < nb; ++m) {
-        size_t g = 0;
-        while (g < keys.size() && keys[g] != flags[m]) ++g;
-        if (g == keys.size()) {
-            keys.push_back(flags[m]);
-            groups.emplace_back();
-        }
-        groups[g].push_back(m);
-    }
+    const std::vector<std::vector<int>> groups = group_by_flags(nb, [&](int m) { return flags[m]; });
     perm.reserve(nb);
     for (const auto& g : groups) perm.insert(perm.end(), g.begin(), g.end());
     HIPCHK(hipMemcpyAsync(c->d_mix_perm.p, perm.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, st));
@@ -2822,29 +2826,39 @@ static int flux_dev_by_flags(vag_ctx* c, const vag_model_params* d_params, int n
     return VAG_OK;
 }
 
-extern "C" {
-
-static int grid_dev_body(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_t, int nt, const double* d_nu, int nnu,
-                         double* d_out) {
+// A call on device pointers under the plan-ahead protocol.  attempt(may_plan): the model stages with that switch, then the request.
+// The first attempt may be planned from the previous call's summary (run_model_stages) and is verified at its end; where the plan
+// did not hold, or the planned call failed (an error while planning from stale sizes is not the caller's), the call is repeated
+// once on the waiting path.  A failure that is not a planned call's -- prep_times ahead of the stages, or any failure of the second
+// attempt -- is returned as it is: spec_pending is set by run_model_stages alone, which clears it first, and no path leaves it set
+// between calls.  what: "grid" / "series", for the VAG_DEBUG_SPEC line.
+template <class Attempt>
+static int plan_ahead_attempts(vag_ctx* c, const char* what, Attempt attempt) {
     int rc = VAG_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {  // planned ahead from the previous call's summary, verified at the end
-        rc = prep_times(c, d_t, nt, d_nu, nnu);
-        if (rc) return rc;
-        c->allow_spec = attempt == 0 && !c->count_work;
-        rc = run_model_stages(c, d_params, nb, false);
-        c->allow_spec = false;
-        if (rc == VAG_OK) rc = grid_request_chunked(c, d_params, nb, nt, nnu, nullptr, d_out, nullptr);
+    for (int n = 0; n < 2; ++n) {
+        rc = attempt(n == 0 && !c->count_work);
         if (rc) {
             if (!c->spec_pending) return rc;
-            c->spec_pending = false;  // an error while planning from stale sizes is not the caller's: repeat on the waiting path
+            c->spec_pending = false;
             c->hint_valid = false;
-            if (vag_hook("VAG_DEBUG_SPEC")) std::fprintf(stderr, "[vag] planned-ahead grid call failed (%d: %s): repeating\n", rc, g_err.c_str());
+            if (vag_hook("VAG_DEBUG_SPEC")) std::fprintf(stderr, "[vag] planned-ahead %s call failed (%d: %s): repeating\n", what, rc, g_err.c_str());
             continue;
         }
         rc = finish_speculation(c);
         if (rc != VAG_RETRY) break;
     }
     return rc;
+}
+
+extern "C" {
+
+static int grid_dev_body(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_t, int nt, const double* d_nu, int nnu,
+                         double* d_out) {
+    return plan_ahead_attempts(c, "grid", [&](bool may_plan) {
+        int rc = prep_times(c, d_t, nt, d_nu, nnu);
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false, may_plan);
+        return rc ? rc : grid_request_chunked(c, d_params, nb, nt, nnu, nullptr, d_out, nullptr);
+    });
 }
 
 int vag_flux_density_grid_batch_dev(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_t, int nt,
@@ -2869,46 +2883,39 @@ static int upload_series_bands(vag_ctx* c, const double* nu, int n);
 // The whole (t, nu) series already in c->d_lg2t / c->d_lg2nu (prep_times) -> d_out[nb][n], the sum of every enabled
 // component.  Longer series than one launch holds (exposure sampling, large data sets) go through in chunks of sorted
 // points on the same model grid.
-static int series_request(vag_ctx* c, const vag_model_params* d_params, int nb, int n, double* d_out, int n_bands) {
+// d4 (in place of d_out): the components {fwd.sync, fwd.ssc, rvs.sync, rvs.ssc} apart, [nb][n] each, NULL entries skipped.
+static int series_request(vag_ctx* c, const vag_model_params* d_params, int nb, int n, double* d_out, int n_bands,
+                          double* const* d4 = nullptr) {
     const int chunk = SERIES_THREADS * SERIES_MAX_SLOTS;
-    if (n <= chunk)
-        return series_chunk(c, d_params, nb, c->d_lg2t.as<double>(), c->d_lg2nu.as<double>(), n, c->d_lg2nu.as<double>(), n,
-                            d_out, n_bands);
+    const double *lg2t = c->d_lg2t.as<double>(), *lg2nu = c->d_lg2nu.as<double>();
+    if (n <= chunk) return series_chunk(c, d_params, nb, lg2t, lg2nu, n, lg2nu, n, d_out, n_bands, d4);
+    double* const total[1] = {d_out};
+    double* const* dst = d4 ? d4 : total;
+    const int n_dst = d4 ? 4 : 1;
+    const size_t rows = (size_t)nb * chunk;  // of one output: the scratch holds one set for the total, four for the components
     DevBuf& tmp = c->d_chunk;  // grow-only context scratch: the stream orders its reuse
-    if (tmp.ensure(sizeof(double) * (size_t)nb * chunk)) return VAG_E_HIP;
+    if (tmp.ensure(sizeof(double) * n_dst * rows)) return VAG_E_HIP;
     int rc = VAG_OK;
-    for (int s0 = 0; s0 < n && rc == VAG_OK; s0 += chunk) {
+    for (int s0 = 0; s0 < n && rc == VAG_OK; s0 += chunk) {  // chunks of sorted points on the same grid
         const int m = std::min(chunk, n - s0);
-        rc = series_chunk(c, d_params, nb, c->d_lg2t.as<double>() + s0, c->d_lg2nu.as<double>() + s0, m,
-                          c->d_lg2nu.as<double>(), n, tmp.as<double>());
-        if (rc == VAG_OK && hipMemcpy2DAsync(d_out + s0, sizeof(double) * n, tmp.p, sizeof(double) * m, sizeof(double) * m,
-                                             (size_t)nb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-            rc = VAG_E_HIP;
+        double* part[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int i = 0; i < n_dst; ++i) part[i] = dst[i] ? tmp.as<double>() + i * rows : nullptr;
+        rc = series_chunk(c, d_params, nb, lg2t + s0, lg2nu + s0, m, lg2nu, n, d4 ? nullptr : part[0], 0, d4 ? part : nullptr);
+        for (int i = 0; i < n_dst && rc == VAG_OK; ++i)
+            if (dst[i] && hipMemcpy2DAsync(dst[i] + s0, sizeof(double) * n, part[i], sizeof(double) * m, sizeof(double) * m, (size_t)nb,
+                                           hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+                rc = VAG_E_HIP;
     }
     return rc;
 }
 
 static int series_dev_body(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_t, const double* d_nu, int n,
                            double* d_out, int n_bands) {
-    int rc = VAG_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = prep_times(c, d_t, n, d_nu, n);  // the grid sees the extrema of ALL requested times
-        if (rc) return rc;
-        c->allow_spec = attempt == 0 && !c->count_work;
-        rc = run_model_stages(c, d_params, nb, false);
-        c->allow_spec = false;
-        if (rc == VAG_OK) rc = series_request(c, d_params, nb, n, d_out, n_bands);
-        if (rc) {
-            if (!c->spec_pending) return rc;
-            c->spec_pending = false;
-            c->hint_valid = false;
-            if (vag_hook("VAG_DEBUG_SPEC")) std::fprintf(stderr, "[vag] planned-ahead series call failed (%d: %s): repeating\n", rc, g_err.c_str());
-            continue;
-        }
-        rc = finish_speculation(c);
-        if (rc != VAG_RETRY) break;
-    }
-    return rc;
+    return plan_ahead_attempts(c, "series", [&](bool may_plan) {
+        int rc = prep_times(c, d_t, n, d_nu, n);  // the grid sees the extrema of ALL requested times
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false, may_plan);
+        return rc ? rc : series_request(c, d_params, nb, n, d_out, n_bands);
+    });
 }
 
 int vag_flux_density_batch_dev(vag_ctx* c, const vag_model_params* d_params, int nb, const double* d_t,
@@ -2936,27 +2943,10 @@ int vag_flux_density_grid_batch(vag_ctx* c, const vag_model_params* params, int 
     if (!c) return set_err(VAG_E_INVALID, "null context");
     if (!nu || !out) return set_err(VAG_E_INVALID, "null frequency or output array");
     if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
-    int rc = check_host_inputs(params, nb, t, nt);
-    if (rc) return rc;
-    if (!uniform_flags(params, nb))
-        return run_flag_groups(params, nb, {{out, (size_t)nnu * nt}}, [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-            return vag_flux_density_grid_batch(c, gp, ng, t, nt, nu, nnu, o[0]);
-        });
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
-    if (c->d_t.ensure(sizeof(double) * nt)) return VAG_E_HIP;
-    if (c->d_nu.ensure(sizeof(double) * nnu)) return VAG_E_HIP;
-    if (c->d_out.ensure(sizeof(double) * (size_t)nb * nnu * nt)) return VAG_E_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * nt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_nu.p, nu, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream));
-    rc = vag_flux_density_grid_batch_dev(c, c->d_params.as<vag_model_params>(), nb, c->d_t.as<double>(), nt,
-                                         c->d_nu.as<double>(), nnu, c->d_out.as<double>());
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, c->d_out.p, sizeof(double) * (size_t)nb * nnu * nt, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return check_status(c, nb);
+    const HostRequest r{params, nb, t, nt, nu, nnu, {{out, (size_t)nnu * nt}}, {{&vag_ctx::d_out, 0, 1}}};
+    return host_request(c, r, [&](const HostRequest& q, const vag_model_params* d_params, double* const* d) {
+        return vag_flux_density_grid_batch_dev(c, d_params, q.nb, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu, d[0]);
+    });
 }
 
 // out4 = {fwd.sync, fwd.ssc, rvs.sync, rvs.ssc}; NULL entries are skipped
@@ -2964,38 +2954,13 @@ static int grid_components_impl(vag_ctx* c, const vag_model_params* params, int 
                                 int nnu, double* const* out4) {
     if (!c) return set_err(VAG_E_INVALID, "null context");
     if (nnu <= 0) return set_err(VAG_E_INVALID, "frequency array must be non-empty");
-    int rc = check_host_inputs(params, nb, t, nt);
-    if (rc) return rc;
-    if (!uniform_flags(params, nb)) {
-        const size_t st = (size_t)nnu * nt;
-        return run_flag_groups(params, nb, {{out4[0], st}, {out4[1], st}, {out4[2], st}, {out4[3], st}},
-                               [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-                                   double* o4[4] = {o[0], o[1], o[2], o[3]};
-                                   return grid_components_impl(c, gp, ng, t, nt, nu, nnu, o4);
-                               });
-    }
-    HIPCHK(hipSetDevice(c->device));
-    const size_t n_out = (size_t)nb * nnu * nt;
-    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
-    if (c->d_t.ensure(sizeof(double) * nt)) return VAG_E_HIP;
-    if (c->d_nu.ensure(sizeof(double) * nnu)) return VAG_E_HIP;
-    if (c->d_comp.ensure(sizeof(double) * 4 * n_out)) return VAG_E_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * nt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_nu.p, nu, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream));
-    rc = prep_times(c, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu);
-    if (rc) return rc;
-    rc = run_model_stages(c, c->d_params.as<vag_model_params>(), nb, false);
-    if (rc) return rc;
-    double* d4[4];
-    for (int q = 0; q < 4; ++q) d4[q] = out4[q] ? c->d_comp.as<double>() + q * n_out : nullptr;
-    rc = grid_request_chunked(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, nullptr, nullptr, d4);
-    if (rc) return rc;
-    for (int q = 0; q < 4; ++q)
-        if (out4[q]) HIPCHK(hipMemcpyAsync(out4[q], d4[q], sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return check_status(c, nb);
+    const size_t st = (size_t)nnu * nt;
+    const HostRequest r{params, nb, t, nt, nu, nnu, {{out4[0], st}, {out4[1], st}, {out4[2], st}, {out4[3], st}}, {{&vag_ctx::d_comp, 0, 4}}};
+    return host_request(c, r, [&](const HostRequest& q, const vag_model_params* d_params, double* const* d4) {
+        int rc = prep_times(c, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu);
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, q.nb, false);
+        return rc ? rc : grid_request_chunked(c, d_params, q.nb, nt, nnu, nullptr, nullptr, d4);
+    });
 }
 
 int vag_flux_density_grid_components_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt,
@@ -3017,40 +2982,23 @@ int vag_flux_density_grid_components4_batch(vag_ctx* c, const vag_model_params* 
 static int sky_impl(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu, int n_az,
                     double fov, int npixel, double* image, double* outside, double* moments, const SkyVisReq* vr = nullptr,
                     const SkyPolReq* pr = nullptr) {
-    int rc = check_host_inputs(params, nb, t, nt);
-    if (rc) return rc;
-    if (!uniform_flags(params, nb)) {
-        const size_t st = (size_t)nnu * nt;
-        double* vis = vr ? vr->vis : nullptr;
-        const size_t vis_stride = vr ? st * vr->nbl * 2 : 0;
-        const SkyPolReq none{};
-        const SkyPolReq& P = pr ? *pr : none;
-        return run_flag_groups(
-            params, nb,
-            {{image, st * npixel * npixel}, {outside, st}, {moments, st * 6}, {vis, vis_stride}, {P.stokes, st * 3},
-             {P.image, st * 3 * npixel * npixel}, {P.outside, st * 3}},
-            [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-                SkyVisReq gv{};
-                if (vr) gv = *vr, gv.vis = o[3];
-                const SkyPolReq gpol{o[7], P.pa, o[4], o[5], o[6]};
-                return sky_impl(c, gp, ng, t, nt, nu, nnu, n_az, fov, npixel, o[0], o[1], o[2], vr ? &gv : nullptr, pr ? &gpol : nullptr);
-            },
-            {{const_cast<double*>(P.spec), 4}});
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
-    if (c->d_t.ensure(sizeof(double) * nt)) return VAG_E_HIP;
-    if (c->d_nu.ensure(sizeof(double) * nnu)) return VAG_E_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * nt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_nu.p, nu, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream));
-    rc = prep_times(c, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu);
-    if (rc) return rc;
-    rc = run_model_stages(c, c->d_params.as<vag_model_params>(), nb, false);
-    if (rc) return rc;
-    rc = sky_request(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, n_az, fov, npixel, image, outside, moments, vr, pr);
-    if (rc) return rc;
-    return check_status(c, nb);  // (no collect_times: the flux events it reads are not recorded by the sky passes)
+    const size_t st = (size_t)nnu * nt;
+    const SkyPolReq none{};
+    const SkyPolReq& P = pr ? *pr : none;
+    // (no device side: sky_request copies its outputs in chunks; no collect_times: the flux events it reads are not recorded by the sky passes)
+    const HostRequest r{params, nb, t, nt, nu, nnu,
+                        {{image, st * npixel * npixel}, {outside, st}, {moments, st * 6}, {vr ? vr->vis : nullptr, vr ? st * vr->nbl * 2 : 0},
+                         {P.stokes, st * 3}, {P.image, st * 3 * npixel * npixel}, {P.outside, st * 3}},
+                        {}, false, {{const_cast<double*>(P.spec), 4}}};
+    return host_request(c, r, [&](const HostRequest& q, const vag_model_params* d_params, double* const*) {
+        const std::vector<OutRows>& o = q.outs;
+        SkyVisReq gv{};
+        if (vr) gv = *vr, gv.vis = o[3].p;
+        const SkyPolReq gpol{q.ins[0].p, P.pa, o[4].p, o[5].p, o[6].p};
+        int rc = prep_times(c, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu);
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, q.nb, false);
+        return rc ? rc : sky_request(c, d_params, q.nb, nt, nnu, n_az, fov, npixel, o[0].p, o[1].p, o[2].p, vr ? &gv : nullptr, pr ? &gpol : nullptr);
+    });
 }
 
 int vag_sky_image_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
@@ -3180,31 +3128,12 @@ int vag_debug_device_math(vag_ctx* c, int fn, const double* in, int n, double* o
 // Model.sky_moments(exact=True) over a batch: the n_az -> infinity limit of sky_impl's moments (vag_sky_centroid_kernel)
 static int centroid_impl(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
                          double* moments) {
-    int rc = check_host_inputs(params, nb, t, nt);
-    if (rc) return rc;
-    if (!uniform_flags(params, nb))
-        return run_flag_groups(params, nb, {{moments, (size_t)nnu * nt * 6}},
-                               [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-                                   return centroid_impl(c, gp, ng, t, nt, nu, nnu, o[0]);
-                               });
-    HIPCHK(hipSetDevice(c->device));
-    const size_t n_out = (size_t)nb * nnu * nt * 6;
-    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
-    if (c->d_t.ensure(sizeof(double) * nt)) return VAG_E_HIP;
-    if (c->d_nu.ensure(sizeof(double) * nnu)) return VAG_E_HIP;
-    if (c->d_skycmom.ensure(sizeof(double) * n_out)) return VAG_E_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * nt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_nu.p, nu, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream));
-    rc = prep_times(c, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu);
-    if (rc) return rc;
-    rc = run_model_stages(c, c->d_params.as<vag_model_params>(), nb, false);
-    if (rc) return rc;
-    rc = centroid_request(c, c->d_params.as<vag_model_params>(), nb, nt, nnu, c->d_skycmom.as<double>());
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(moments, c->d_skycmom.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return check_status(c, nb);
+    const HostRequest r{params, nb, t, nt, nu, nnu, {{moments, (size_t)nnu * nt * 6}}, {{&vag_ctx::d_skycmom, 0, 1}}, false};
+    return host_request(c, r, [&](const HostRequest& q, const vag_model_params* d_params, double* const* d) {
+        int rc = prep_times(c, c->d_t.as<double>(), nt, c->d_nu.as<double>(), nnu);
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, q.nb, false);
+        return rc ? rc : centroid_request(c, d_params, q.nb, nt, nnu, d[0]);
+    });
 }
 
 int vag_sky_centroid_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, const double* nu, int nnu,
@@ -3221,29 +3150,11 @@ int vag_flux_density_batch(vag_ctx* c, const vag_model_params* params, int nb, c
     ApiLock api_lock(c);
     if (!c) return set_err(VAG_E_INVALID, "null context");
     if (!nu || !out) return set_err(VAG_E_INVALID, "null frequency or output array");
-    int rc = check_host_inputs(params, nb, t, n);
-    if (rc) return rc;
-    if (!uniform_flags(params, nb))
-        return run_flag_groups(params, nb, {{out, (size_t)n}}, [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-            return vag_flux_density_batch(c, gp, ng, t, nu, n, o[0]);
-        });
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
-    if (c->d_t.ensure(sizeof(double) * n)) return VAG_E_HIP;
-    if (c->d_nu.ensure(sizeof(double) * n)) return VAG_E_HIP;
-    if (c->d_out.ensure(sizeof(double) * (size_t)nb * n)) return VAG_E_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_nu.p, nu, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    c->pending_bands = upload_series_bands(c, nu, n);
-    rc = vag_flux_density_batch_dev(c, c->d_params.as<vag_model_params>(), nb, c->d_t.as<double>(), c->d_nu.as<double>(), n,
-                                    c->d_out.as<double>());
-    c->pending_bands = 0;
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, c->d_out.p, sizeof(double) * (size_t)nb * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return check_status(c, nb);
+    const HostRequest r{params, nb, t, n, nu, n, {{out, (size_t)n}}, {{&vag_ctx::d_out, 0, 1}}};
+    return host_request(c, r, [&](const HostRequest& q, const vag_model_params* d_params, double* const* d) {
+        CallMode<int> bands(c->pending_bands, upload_series_bands(c, nu, n));  // (the device-pointer entry point does not see the frequencies)
+        return vag_flux_density_batch_dev(c, d_params, q.nb, c->d_t.as<double>(), c->d_nu.as<double>(), n, d[0]);
+    });
 }
 
 // Model.flux_density with its components apart (FluxDict.fwd / .rvs of a series, pymodel.cpp:373-389): out4[i] != NULL
@@ -3254,56 +3165,14 @@ int vag_flux_density_components4_batch(vag_ctx* c, const vag_model_params* param
     if (!c) return set_err(VAG_E_INVALID, "null context");
     if (!out4) return set_err(VAG_E_INVALID, "out4 must not be null");
     if (!nu) return set_err(VAG_E_INVALID, "null frequency array");
-    int rc = check_host_inputs(params, nb, t, n);
-    if (rc) return rc;
-    if (!uniform_flags(params, nb))
-        return run_flag_groups(params, nb, {{out4[0], (size_t)n}, {out4[1], (size_t)n}, {out4[2], (size_t)n}, {out4[3], (size_t)n}},
-                               [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-                                   double* o4[4] = {o[0], o[1], o[2], o[3]};
-                                   return vag_flux_density_components4_batch(c, gp, ng, t, nu, n, o4);
-                               });
-    HIPCHK(hipSetDevice(c->device));
-    const size_t n_out = (size_t)nb * n;
-    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
-    if (c->d_t.ensure(sizeof(double) * n)) return VAG_E_HIP;
-    if (c->d_nu.ensure(sizeof(double) * n)) return VAG_E_HIP;
-    if (c->d_comp.ensure(sizeof(double) * 4 * n_out)) return VAG_E_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_nu.p, nu, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    const int n_bands = upload_series_bands(c, nu, n);
-    rc = prep_times(c, c->d_t.as<double>(), n, c->d_nu.as<double>(), n);  // the grid sees the extrema of ALL requested times
-    if (rc) return rc;
-    rc = run_model_stages(c, c->d_params.as<vag_model_params>(), nb, false);
-    if (rc) return rc;
-    double* d4[4];
-    for (int i = 0; i < 4; ++i) d4[i] = out4[i] ? c->d_comp.as<double>() + (size_t)i * n_out : nullptr;
-    const int chunk = SERIES_THREADS * SERIES_MAX_SLOTS;
-    if (n <= chunk) {
-        rc = series_chunk(c, c->d_params.as<vag_model_params>(), nb, c->d_lg2t.as<double>(), c->d_lg2nu.as<double>(), n,
-                          c->d_lg2nu.as<double>(), n, nullptr, n_bands, d4);
-        if (rc) return rc;
-    } else {  // long series (exposure sampling): chunks of sorted points on the same grid
-        DevBuf& tmp = c->d_chunk;  // grow-only context scratch: the stream orders its reuse
-        if (tmp.ensure(sizeof(double) * 4 * (size_t)nb * chunk)) return VAG_E_HIP;
-        for (int s0 = 0; s0 < n && rc == VAG_OK; s0 += chunk) {
-            const int mlen = std::min(chunk, n - s0);
-            double* t4[4];
-            for (int i = 0; i < 4; ++i) t4[i] = d4[i] ? tmp.as<double>() + (size_t)i * nb * chunk : nullptr;
-            rc = series_chunk(c, c->d_params.as<vag_model_params>(), nb, c->d_lg2t.as<double>() + s0, c->d_lg2nu.as<double>() + s0,
-                              mlen, c->d_lg2nu.as<double>(), n, nullptr, 0, t4);
-            for (int i = 0; i < 4 && rc == VAG_OK; ++i)
-                if (d4[i] && hipMemcpy2DAsync(d4[i] + s0, sizeof(double) * n, t4[i], sizeof(double) * mlen, sizeof(double) * mlen,
-                                              (size_t)nb, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-                    rc = VAG_E_HIP;
-        }
-        if (rc) return rc;
-    }
-    for (int i = 0; i < 4; ++i)
-        if (out4[i]) HIPCHK(hipMemcpyAsync(out4[i], d4[i], sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return check_status(c, nb);
+    const size_t st = (size_t)n;
+    const HostRequest r{params, nb, t, n, nu, n, {{out4[0], st}, {out4[1], st}, {out4[2], st}, {out4[3], st}}, {{&vag_ctx::d_comp, 0, 4}}};
+    return host_request(c, r, [&](const HostRequest& q, const vag_model_params* d_params, double* const* d4) {
+        const int n_bands = upload_series_bands(c, nu, n);
+        int rc = prep_times(c, c->d_t.as<double>(), n, c->d_nu.as<double>(), n);  // the grid sees the extrema of ALL requested times
+        if (rc == VAG_OK) rc = run_model_stages(c, d_params, q.nb, false);
+        return rc ? rc : series_request(c, d_params, q.nb, n, nullptr, n_bands, d4);  // (a long series, exposure sampling: in chunks)
+    });
 }
 
 // Band request with parameters and times already in HBM: nu = logspace(nu_min, nu_max, num_nu) nodes with Boole weights
@@ -3375,38 +3244,14 @@ static int flux_band_impl(vag_ctx* c, const vag_model_params* params, int nb, co
                           double nu_max, int num_nu, double* out_total, double* const* out4) {
     if (!c) return set_err(VAG_E_INVALID, "null context");
     if (!out_total && !out4) return set_err(VAG_E_INVALID, "null output array");
-    int rc = check_host_inputs(params, nb, t, nt);
-    if (rc) return rc;
-    if (!uniform_flags(params, nb)) {
-        const size_t st = (size_t)nt;
-        return run_flag_groups(params, nb,
-                               {{out_total, st}, {out4 ? out4[0] : nullptr, st}, {out4 ? out4[1] : nullptr, st},
-                                {out4 ? out4[2] : nullptr, st}, {out4 ? out4[3] : nullptr, st}},
-                               [&](const vag_model_params* gp, int ng, const std::vector<double*>& o) {
-                                   double* o4[4] = {o[1], o[2], o[3], o[4]};
-                                   return flux_band_impl(c, gp, ng, t, nt, nu_min, nu_max, num_nu, o[0], out4 ? o4 : nullptr);
-                               });
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if (c->d_params.ensure(sizeof(vag_model_params) * nb)) return VAG_E_HIP;
-    if (c->d_t.ensure(sizeof(double) * nt)) return VAG_E_HIP;
-    if (c->d_out.ensure(sizeof(double) * (size_t)nb * nt)) return VAG_E_HIP;
-    if (c->d_comp.ensure(sizeof(double) * (size_t)nb * nt * 4)) return VAG_E_HIP;
-    HIPCHK(hipMemcpyAsync(c->d_params.p, params, sizeof(vag_model_params) * nb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_t.p, t, sizeof(double) * nt, hipMemcpyHostToDevice, c->stream));
-    const size_t n_out = (size_t)nb * nt;
-    double* d4[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (out4)
-        for (int q = 0; q < 4; ++q) d4[q] = out4[q] ? c->d_comp.as<double>() + q * n_out : nullptr;
-    rc = band_request_dev(c, c->d_params.as<vag_model_params>(), nb, c->d_t.as<double>(), nt, nu_min, nu_max, num_nu,
-                          out_total ? c->d_out.as<double>() : nullptr, out4 ? d4 : nullptr);
-    if (rc) return rc;
-    if (out_total) HIPCHK(hipMemcpyAsync(out_total, c->d_out.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
-    for (int q = 0; q < 4; ++q)
-        if (d4[q]) HIPCHK(hipMemcpyAsync(out4[q], d4[q], sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)collect_times(c);
-    return check_status(c, nb);
+    const size_t st = (size_t)nt;
+    const HostRequest r{params, nb, t, nt, nullptr, 0,
+                        {{out_total, st}, {out4 ? out4[0] : nullptr, st}, {out4 ? out4[1] : nullptr, st}, {out4 ? out4[2] : nullptr, st},
+                         {out4 ? out4[3] : nullptr, st}},
+                        {{&vag_ctx::d_out, 0, 1}, {&vag_ctx::d_comp, 1, 4}}, /* times */ true, /* ins */ {}, /* has_nu */ false};
+    return host_request(c, r, [&](const HostRequest& q, const vag_model_params* d_params, double* const* d) {
+        return band_request_dev(c, d_params, q.nb, c->d_t.as<double>(), nt, nu_min, nu_max, num_nu, d[0], out4 ? d + 1 : nullptr);
+    });
 }
 
 int vag_flux_batch(vag_ctx* c, const vag_model_params* params, int nb, const double* t, int nt, double nu_min,
@@ -3492,7 +3337,7 @@ static int upload_blocks(vag_ctx* c, FitRequest& r, bool fit_only = false) {
 
 constexpr int COUNTS_PPB = 64;  // (theta, phi) pairs per flux workgroup of a counts pass (vag_ctx::ppb_pin)
 
-static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec) {
+static int loglike_passes(vag_ctx* c, const FitRequest& req, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec) {
     const vag_fit_spec* spec = req.spec;
     const vag_sky_fit_spec* sky = req.sky;
     int rc = VAG_OK;
@@ -3596,13 +3441,10 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
             rc = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), nu_pts ? upload_series_bands(c, nu_pts, (int)np) : 0);
         return VAG_OK;
     };
-    c->ic_soft_fail = true;
     if (n > 0) {  // point data: one (t, nu) series per walker (fitter.py:510-522)
         if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * n)) return VAG_E_HIP;
-        c->allow_spec = try_spec;
         begin_pass();
-        rc = run_model_stages(c, d_params, nb, false);
-        c->allow_spec = false;
+        rc = run_model_stages(c, d_params, nb, false, try_spec);
         if (rc == VAG_OK) rc = series_request(c, d_params, nb, n, c->d_series_flux.as<double>(), upload_series_bands(c, spec->nu, n));
         if (rc == VAG_OK)
             rc = back(c->d_series_flux.as<double>(), n, ln_flux, ln_err, weight, spec->ext_kernel ? ext : nullptr,
@@ -3703,9 +3545,10 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
         // 262144 pairs on, for bands of at most 4 nodes, the row-per-lane kernel -- so a band group's flux depends on the batch in its
         // last bits; here both are pinned (COUNTS_PPB pairs, the workgroup kernel), and a walker's counts term is the same bits alone
         // and in any batch whose lattices fit the staged row (512 nodes)
-        c->ppb_pin = COUNTS_PPB;
-        rc = band_request_dev(c, d_params, nb, dc, o.n_samples, o.nu_min, o.nu_max, o.num_points, c->d_series_flux.as<double>(), nullptr);
-        c->ppb_pin = 0;
+        {
+            CallMode<int> pin(c->ppb_pin, COUNTS_PPB);
+            rc = band_request_dev(c, d_params, nb, dc, o.n_samples, o.nu_min, o.nu_max, o.num_points, c->d_series_flux.as<double>(), nullptr);
+        }
         if (rc == VAG_OK) {
             hipLaunchKernelGGL(vag_fit_back_counts_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n_samples, o.n, o.m,
                                reinterpret_cast<const int*>(dc + ns + 4 * nr), dc + ns, dc + ns + nr, dc + ns + 2 * nr, dc + ns + 3 * nr,
@@ -3759,16 +3602,23 @@ static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta
             rc = end_pass();
         }
     }
-    c->ic_soft_fail = false;
     c->plan.n_models_capacity = n_cap;
     c->plan.n_models_invalid = n_inv;
     c->fit_stats_pending = true;
     if (rc == VAG_OK && order_made) {  // the order computed from this call's grids serves the next call of this size
         c->order_cur ^= 1;
         c->order_nb = nb;
-    } else if (rc != VAG_OK) {
-        c->order_nb = 0;
     }
+    return rc;
+}
+
+// One attempt of a likelihood call.  For its whole length the SSC tables' failures invalidate the walker instead of raising
+// (ic_soft_fail, put back whichever way the passes are left); a call that did not end well -- a failed allocation in the middle
+// of the passes included -- leaves no evaluation order to the next one.
+static int loglike_body(vag_ctx* c, const FitRequest& req, const double* d_theta, int nb, int ndim, double* d_out, bool try_spec) {
+    CallMode<bool> soft_fail(c->ic_soft_fail, true);
+    const int rc = loglike_passes(c, req, d_theta, nb, ndim, d_out, try_spec);
+    if (rc != VAG_OK) c->order_nb = 0;
     return rc;
 }
 
