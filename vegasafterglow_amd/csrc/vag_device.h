@@ -1019,13 +1019,15 @@ VAG_DEV double relu_f64(double z) {
 }
 // RELU_FIRST: max(z, 0) is formed for every lane ahead of ONE masked region, the table side's, where the plain form has a masked
 // region per side: one more vector instruction where a whole wavefront takes the table side, three mask instructions and a branch
-// fewer in every call.  Same value per lane.  On for the split flux kernel's boundary team (profiles/flux_prefetch_ab.txt).
+// fewer in every call, and the table side ends in r + p (an instruction fewer than the plain form's fma(0.5, z + |z|, p)).  Same
+// value per lane.  On for the split flux kernel's boundary team (profiles/flux_prefetch_ab.txt, profiles/flux_header_ab.txt).
 template <bool RELU_FIRST = false, class Tab>
 VAG_DEV double sp_fast(double z, Tab tab) {
     const double a = fabs(z);
 #ifndef VAG_SP_BRANCHLESS
+    [[maybe_unused]] double r = 0;  // max(z, 0), RELU_FIRST only
     if constexpr (RELU_FIRST) {
-        const double r = relu_f64(z);
+        r = relu_f64(z);
         if (a > 20.0) return r;
     } else {
         if (a > 20.0) return relu_f64(z);
@@ -1043,6 +1045,9 @@ VAG_DEV double sp_fast(double z, Tab tab) {
     p = fma(p, tau, c01.x);
 #ifdef VAG_SP_BRANCHLESS
     p = a > 20.0 ? 0.0 : p;  // straight-line code: independent softplus terms of one evaluation interleave
+#else
+    // max(z, 0) is held already: r + p rounds the sum that fma(0.5, z + |z|, p) rounds, once (tests/test_sp_relu_add_host.py)
+    if constexpr (RELU_FIRST) return r + p;
 #endif
     return fma(0.5, z + a, p);  // max(z, 0) = (z + |z|) / 2, exact
 }

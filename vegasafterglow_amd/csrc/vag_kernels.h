@@ -1528,17 +1528,19 @@ static_assert(FLUX_SPLIT_MAX_NNU % FLUX_SPLIT_GROUP == 0, "the full set of frequ
 
 // LDS layout of the split form, offsets in doubles (the kernel and the launch's budget read the same numbers)
 struct FluxSplitLds {
-    int par, t, dop, B, tobs, nu, win;
+    int par, t, dop, B, nu, win, it;
     size_t bytes;
     __host__ __device__ FluxSplitLds(int ks, int nt, int nnu) {
         par = SP_LDS_DOUBLES;        // [ks][VAG_NPAR] staged photon block, behind the softplus / log2 tables
         t = par + VAG_NPAR * ks;     // [3][ks] log2 observer times of rows p, p + 1, p + 2
         dop = t + 3 * ks;            // [2][ks] log2 Doppler factor
         B = dop + 2 * ks;            // [2][nnu][ks] boundary log2-luminosities
-        tobs = B + 2 * nnu * ks;     // [nt]
-        nu = tobs + nt;              // [nnu]
+        nu = B + 2 * nnu * ks;       // [nnu]
         win = nu + nnu;              // int [2][FLUX_SPLIT_E][2] window counts per wavefront of the EAT step
-        bytes = sizeof(double) * (size_t)win + sizeof(int) * 4 * FLUX_SPLIT_E;
+        it = win + 2 * FLUX_SPLIT_E; // int: the number of the workgroup's item, a word no item writes
+        // + nt doubles that nothing uses: the requested times have no LDS copy in this form any more (the item's window and a B
+        // lane's times live in registers), and the budget keeps ending the lattice where it was measured, 202 nodes at 10 nu x 200 t
+        bytes = sizeof(double) * (size_t)(it + 1 + nt);
     }
 };
 
@@ -1566,7 +1568,6 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     double* s_t = lds + L.t;
     double* s_dop = lds + L.dop;
     double* s_B = lds + L.B;
-    double* s_tobs = lds + L.tobs;
     double* s_nu = lds + L.nu;
     int* s_win = reinterpret_cast<int*>(lds + L.win);
 
@@ -1575,8 +1576,7 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     const double opz_over_c = one_plus_z / C_C;
     {
         const double lg2_1pz = Mp->lg2_1pz;
-        for (int i = tid; i < nt; i += THREADS) s_tobs[i] = a.lg2_t_obs[i];
-        for (int l = tid; l < nnu; l += THREADS) s_nu[l] = a.lg2_nu_obs[l] + lg2_1pz;
+        for (int l = tid; l < nnu; l += THREADS) s_nu[l] = a.lg2_nu_obs[l] + lg2_1pz;  // read behind the staging's barrier
     }
     SpecConst sc;
     sc.init(Pp->p);
@@ -1610,8 +1610,7 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     auto pipeline = [&](auto&& work, auto&& late_eat) {
         int j1 = p0 / n_phi_eff, i1 = p0 - j1 * n_phi_eff;
         int staged_rep = rep_at(j1);
-        __syncthreads();  // s_tobs, s_nu
-        stage(staged_rep);
+        stage(staged_rep);  // no barrier ahead of it: the item's number has a word of its own (FluxSplitLds::it), not s_par's first
         __syncthreads();
         late_eat(j1, i1, 0, 0);
         __syncthreads();
@@ -1649,8 +1648,8 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     };
 #undef VAG_STAMP_RELEASE
 
-    // the window of the requested times is a constant of the item: in registers, not read from s_tobs again for every row
-    const double w_lo = a.lg2_t_obs[0], w_hi = a.lg2_t_obs[nt - 1];  // == s_tobs[0], s_tobs[nt - 1]
+    // the window of the requested times is a constant of the item: in registers
+    const double w_lo = a.lg2_t_obs[0], w_hi = a.lg2_t_obs[nt - 1];
 #ifdef VAG_FLUX_STAMPS
     long long c_pro_eat = 0;  // cycles from the end of an EAT wavefront's boundary loop (or its barrier release) to its first log2_tab_core
 #endif
@@ -1872,7 +1871,8 @@ __global__ void __launch_bounds__(FLUX_THREADS, 4)
 vag_flux_grid_split_kernel(FluxArgs a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     for (int i = threadIdx.x; i < SP_LDS_DOUBLES; i += FLUX_THREADS) lds[i] = a.sp_table[i];
-    int* s_it = reinterpret_cast<int*>(lds + SP_LDS_DOUBLES);  // first word of s_par: an item writes it only after its first barrier
+    // the item number has a word of its own: an item stages into s_par without a barrier first, while a slower wavefront may still read this
+    int* s_it = reinterpret_cast<int*>(lds + FluxSplitLds(a.k_stride, a.nt, a.nnu).it);
     for (;;) {
 #ifdef VAG_FLUX_STAMPS
         const long long c_claim = __builtin_readcyclecounter();
