@@ -299,7 +299,37 @@ int vag_sky_stokes_image_batch(vag_ctx* ctx, const vag_model_params* params, int
  *   VAG_MATH_PAIR_INIT in  {Gamma4 (> 1), deps0_dt, dm0_dt, T0 (> 0), t0 (> 0), eps_e_th, medium type (VAG_MEDIUM_ISM, or VAG_MEDIUM_WIND
  *                      with k = 2), rho_ism, A, r02}; out the 11 entries of PairShock::init_state in state order: Gamma, x4, x3, m2, m3,
  *                      U2, U3, r, t_comv, eps4, m4 (n_in = 10, n_out = 11).
- * The wave routines (WAVE_PREFIX_SUM, WAVE_SUM, SKY_WAVE_SUM, LDS_ADD) run one wavefront per 64 points and need n % 64 == 0.
+ * The inverse-Compton routines below vag_ic_photon_kernel: the tables, Y(gamma), the cooling fixed points (vag_ic.h, vag_ic_kernels.h;
+ * internal units):
+ *   VAG_MATH_KN_LUT    in  {k (an integer in [0, 128))}; out {ratio, log2 ratio} of node k of the context's Klein-Nishina table, as
+ *                      vag_ctx_create filled it on the host (n_in = 1, n_out = 2);
+ *   VAG_MATH_KN_CORR   in  {lg2_nu, lg2_x}; out {corr, lg2_corr} of compton_correction_pair_lg2(lg2_nu), then {corr, lg2_corr} of
+ *                      compton_correction_pair_node(lg2_x, exp2(lg2_x)), both on that table; a NaN lg2_x stands for the
+ *                      argument the first form makes of lg2_nu itself, lg2_nu + log2(h / (m_e c^2)) (n_in = 2, n_out = 4);
+ *   VAG_MATH_IC_TABLE  in  {n (an integer in [-1, 16]), first, th_min, th_max, x, 16 table words}: ic_table_eval_hdr on the row's own
+ *                      words with last = first + 2 IC_Q (n - 1); out {value, breach bits} (n_in = 21, n_out = 2; words from n on are
+ *                      never used: for n < 2 words 0 and 1 are still loaded and the result discarded, so no index past the
+ *                      table is formed only for n >= 2);
+ *   VAG_MATH_IC_BIN_INTEGRAL in {f_lo, f_hi, nu_lo, nu_hi, lg2f_lo, lg2f_hi, lg2r, inv_lg2r, trap}; out power_law_bin_integral of
+ *                      them as given (n_in = 9, n_out = 1);
+ *   VAG_MATH_IC_SUFFIX_SCAN in {the lane's four words}: the 256 words of a wavefront go through suffix_scan4 in LDS; out word d is
+ *                      the sum of the wavefront's words from d on (n_in = 4, n_out = 4; a wave routine);
+ *   VAG_MATH_IC_COLUMN_DEN in {gamma, gamma_m, gamma_c, gamma_M, p, regime (an integer in [0, 6]), column_den, Y_c, Y(gamma)}; out
+ *                      electron_column_den (n_in = 9, n_out = 1);
+ *   VAG_MATH_IC_Y      in  {gamma_m, gamma_c, p, B, Y_T, Klein-Nishina flag (0 / 1), g0, g1, nu0, nu1}: IcY::init; out {gamma_m_hat,
+ *                      gamma_c_hat, gamma_self, regime, number of segments, the three (slope, lg2_lower, lg2_const) as icy_store writes
+ *                      them (0, inf, 0 past the number of segments), Y(gamma = g0), Y(g1), Y(nu0), Y(nu1)} (n_in = 10, n_out = 18);
+ *   VAG_MATH_IC_STEP   in  {t_comv, B, gamma_m, gamma_c, p, eps_e / eps_B, Klein-Nishina flag, gamma_M}: one pass of the body of
+ *                      gamma_c's fixed point at gamma_c and of gamma_M's at gamma_M; out {Y_T, Y(gamma_c), the next gamma_c,
+ *                      gamma_M_of(B, Y(gamma_c)), gamma_M_of(B, Y(gamma_M))} (n_in = 8, n_out = 5);
+ *   VAG_MATH_IC_FIXED_POINT in {t_comv, B, gamma_m, the cell's own gamma_c, the previous cell's cooled gamma_c, p, eps_e / eps_B,
+ *                      Klein-Nishina flag, the gamma_M to start from}: ic_gamma_c_cell, then ic_gamma_M on the Y(gamma) it leaves;
+ *                      out {gamma_c, the gamma_c its Y(gamma) is built for, Y_T, passes, gamma_M, passes} (n_in = 9, n_out = 6);
+ *   VAG_MATH_IC_GAMMA_A in {B, column_den, gamma_m, gamma_c, the gamma_c Y(gamma) is built for, p, Y_T, Klein-Nishina flag, and three
+ *                      numbers a, c, m}: IcY::init, Y_c = Y(gamma_c), syn_gamma_a_ic with syn_I_peak(B, column_den) and determine_regime
+ *                      as vag_photons_ic_kernel calls them; out {gamma_a, Y_c, determine_regime(gamma_a, gamma_c, gamma_m),
+ *                      determine_regime(a, c, m)} (n_in = 11, n_out = 4).
+ * The wave routines (WAVE_PREFIX_SUM, WAVE_SUM, SKY_WAVE_SUM, LDS_ADD, IC_SUFFIX_SCAN) run one wavefront per 64 points and need n % 64 == 0.
  * 0, VAG_E_INVALID (unknown fn, n <= 0, a null pointer, n % 64 != 0 for a wave routine, a bad slot, a point outside the ranges stated
  * above: a flag that is not 0 or 1, t_num < 2, k outside the lattice, an unknown medium type, ...) or VAG_E_HIP. */
 enum {
@@ -319,6 +349,15 @@ enum {
     VAG_MATH_CROSS_LATTICE, /* CrossLattice: one node and the integers of a row's refined time lattice */
     VAG_MATH_RVS_EXTRAP, /* rvs_early_extrap on one row of 16 nodes */
     VAG_MATH_PAIR_INIT, /* PairShock::init_state */
+    VAG_MATH_KN_LUT, VAG_MATH_KN_CORR, /* the Klein-Nishina table of the context and its two look-ups (vag_ic.h) */
+    VAG_MATH_IC_TABLE, /* ic_table_eval_hdr on a table carried in the row */
+    VAG_MATH_IC_BIN_INTEGRAL, /* power_law_bin_integral */
+    VAG_MATH_IC_SUFFIX_SCAN, /* suffix_scan4 over the 256 words of a wavefront */
+    VAG_MATH_IC_COLUMN_DEN, /* electron_column_den */
+    VAG_MATH_IC_Y, /* IcY::init and the Y(gamma) it builds */
+    VAG_MATH_IC_STEP, /* one pass of the bodies of the gamma_c and gamma_M fixed points */
+    VAG_MATH_IC_FIXED_POINT, /* ic_gamma_c_cell and ic_gamma_M: the loops vag_ic_cooling_kernel and vag_photons_ic_kernel run */
+    VAG_MATH_IC_GAMMA_A, /* syn_gamma_a_ic and determine_regime */
     VAG_MATH_COUNT
 };
 int vag_debug_device_math(vag_ctx* ctx, int fn, const double* in, int n, double* out);

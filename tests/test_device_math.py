@@ -11,6 +11,7 @@ import pytest
 
 import _elecref as E
 import _mathref as R
+import _icref as IC
 import _rsref as RS
 
 pytestmark = pytest.mark.gpu
@@ -255,6 +256,13 @@ def test_elementwise_shapes(dev, n):
         full = dev(name, rows, n_out)
         assert rows.shape[1] == n_in and full.shape == (rows.shape[0], n_out) and not np.isnan(full).any()
         assert np.array_equal(dev(name, rows[:n], n_out), full[:n]) and np.array_equal(dev(name, rows[-n:], n_out), full[-n:])
+    # the inverse-Compton routines (tests/test_ic_state.py): rows of 1 ... 21 -> 1 ... 18 doubles; the suffix scan takes whole wavefronts
+    for name, (n_in, n_out) in _lib.MATH_IC_SHAPES.items():
+        rows = IC.probe_set(name)[0]
+        full = dev(name, rows, n_out).reshape(rows.shape[0], -1)
+        assert rows.shape[1] == n_in and full.shape == (rows.shape[0], n_out) and not np.isnan(full).any()
+        m = min(64 * n if name == "ic_suffix_scan" else n, rows.shape[0])
+        assert np.array_equal(dev(name, rows[:m], n_out).reshape(m, -1), full[:m]) and np.array_equal(dev(name, rows[-m:], n_out).reshape(m, -1), full[-m:])
 
 
 # ---------------------------------------------------------------- synchrotron cell
@@ -539,6 +547,29 @@ def test_probe_rejects_bad_arguments(dev):
         assert lib.vag_debug_device_math(ctx, ids[name], None, 2, po) == -1
         assert lib.vag_debug_device_math(ctx, ids[name], pg, 2, None) == -1
         assert lib.vag_debug_device_math(None, ids[name], pg, 2, po) == -1
+    # the inverse-Compton routines: the same argument checks (64 points: one of them is a wave routine)
+    for name, (n_in, n_out) in _lib.MATH_IC_SHAPES.items():
+        good = np.ascontiguousarray(IC.probe_set(name)[0][:64])
+        pg, po = good.ctypes.data_as(_dp), np.zeros(64 * n_out).ctypes.data_as(_dp)
+        assert lib.vag_debug_device_math(ctx, ids[name], pg, 64, po) == 0
+        assert lib.vag_debug_device_math(ctx, ids[name], pg, 0, po) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], pg, -3, po) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], None, 64, po) == -1
+        assert lib.vag_debug_device_math(ctx, ids[name], pg, 64, None) == -1
+        assert lib.vag_debug_device_math(None, ids[name], pg, 64, po) == -1
+    assert lib.vag_debug_device_math(ctx, ids["ic_suffix_scan"], pg, 63, po) == -1
+
+    def ic_rejected(name, col, value, row=1):
+        pts = np.ascontiguousarray(IC.probe_set(name)[0][:2]).copy()
+        pts[row, col] = value
+        return lib.vag_debug_device_math(ctx, ids[name], pts.ctypes.data_as(_dp), 2, np.zeros(2 * _lib.MATH_IC_SHAPES[name][1]).ctypes.data_as(_dp)) == -1
+    assert ic_rejected("kn_lut", 0, 128.0) and ic_rejected("kn_lut", 0, -1.0) and ic_rejected("kn_lut", 0, 0.5) and ic_rejected("kn_lut", 0, np.nan)
+    assert ic_rejected("ic_table", 0, 17.0) and ic_rejected("ic_table", 0, -2.0) and ic_rejected("ic_table", 0, 1.5) and ic_rejected("ic_table", 0, np.nan)
+    assert ic_rejected("ic_column_den", 5, 7.0) and ic_rejected("ic_column_den", 5, -1.0) and ic_rejected("ic_column_den", 5, 2.5)
+    assert ic_rejected("ic_y", 5, 2.0) and ic_rejected("ic_y", 5, 0.5) and ic_rejected("ic_y", 5, np.nan)
+    assert ic_rejected("ic_step", 6, 2.0) and ic_rejected("ic_step", 6, -1.0) and ic_rejected("ic_fixed_point", 7, 0.5) and ic_rejected("ic_fixed_point", 7, np.nan)
+    assert ic_rejected("ic_gamma_a", 7, 2.0) and ic_rejected("ic_gamma_a", 7, 0.5)
+    assert ic_rejected("ic_table", 0, 17.0, row=0), "a bad first point"
 
     def rejected(name, col, value, row=1):
         pts = np.ascontiguousarray(RS.probe_set(name)[0][:2]).copy()

@@ -59,10 +59,15 @@ MATH = {name: i for i, name in enumerate([
 # (tests/test_limits_host.py), and the ids of both mappings are the enum's, one numbering.
 MATH_MORE = {name: len(MATH) + i for i, name in enumerate([
     "poisson_deviance", "log_slope", "elec_cell", "fwd_state",
-    "rel_gamma", "shock_jump", "sound_speed", "rvs_state", "cross_lattice", "rvs_extrap", "pair_init"])}
+    "rel_gamma", "shock_jump", "sound_speed", "rvs_state", "cross_lattice", "rvs_extrap", "pair_init",
+    "kn_lut", "kn_corr", "ic_table", "ic_bin_integral", "ic_suffix_scan", "ic_column_den",
+    "ic_y", "ic_step", "ic_fixed_point", "ic_gamma_a"])}
 # [n_in, n_out] per point of the routines of MATH_MORE that tests/_rsref.py restates (vag_debug_math.h)
 MATH_RS_SHAPES = {"rel_gamma": (2, 2), "shock_jump": (2, 3), "sound_speed": (1, 2), "rvs_state": (14, 6), "cross_lattice": (7, 4),
                   "rvs_extrap": (65, 48), "pair_init": (10, 11)}
+# the same for the inverse-Compton routines that tests/_icref.py restates
+MATH_IC_SHAPES = {"kn_lut": (1, 2), "kn_corr": (2, 4), "ic_table": (21, 2), "ic_bin_integral": (9, 1), "ic_suffix_scan": (4, 4),
+                  "ic_column_den": (9, 1), "ic_y": (10, 18), "ic_step": (8, 5), "ic_fixed_point": (9, 6), "ic_gamma_a": (11, 4)}
 
 P_A_V = 1000  # VAG_P_A_V
 # VAG_P_SKY_*: the sky placement of the centroid and visibility groups (vag_loglike_sky_batch / _vis_batch), not Model fields either

@@ -3118,7 +3118,7 @@ int vag_debug_device_math(vag_ctx* c, int fn, const double* in, int n, double* o
     if (fn == VAG_MATH_SYN_CELL && b.col.ensure(sizeof(double) * (size_t)n * VAG_NPAR)) return VAG_E_HIP;
     HIPCHK(hipMemcpyAsync(b.in.p, in, bytes_in, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(vag_math_probe_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), MATH_PROBE_LDS, c->stream, fn, n,
-                       b.in.as<double>(), b.out.as<double>(), c->d_sptab.as<double>(), b.col.as<double>());
+                       b.in.as<double>(), b.out.as<double>(), c->d_sptab.as<double>(), b.col.as<double>(), c->d_knlut.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, b.out.p, bytes_out, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

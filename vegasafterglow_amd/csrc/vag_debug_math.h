@@ -29,6 +29,16 @@ constexpr int MATH_EXT_IN = 4 * MATH_EXT_NODES + 1;   // 16 x (r, Gamma_th, B, N
 constexpr int MATH_EXT_OUT = 3 * MATH_EXT_NODES;      // 16 x (Gamma_th, B, N_p)
 constexpr int MATH_INIT_IN = 10;                      // Gamma4, deps0_dt, dm0_dt, T0, t0, eps_e_th, medium type, rho_ism, A, r02
 constexpr int MATH_INIT_OUT = RS_N;                   // the state of PairShock::init_state
+constexpr int MATH_ICY_IN = 10;                       // gamma_m, gamma_c, p, B, Y_T, is_KN, g0, g1, nu0, nu1
+constexpr int MATH_ICY_OUT = 18;                      // gamma_m_hat, gamma_c_hat, gamma_self, regime, seg.size, 3 x (slope, lg2_lower, lg2_const), Y(g0), Y(g1), Y(nu0), Y(nu1)
+constexpr int MATH_STEP_IN = 8;                       // t_comv, B, gamma_m, gc, p, eps_e / eps_B, kn, gM
+constexpr int MATH_STEP_OUT = 5;                      // Y_T, Y(gc), gc_new, gamma_M_of(B, Y(gc)), gamma_M_of(B, Y(gM))
+constexpr int MATH_FIX_IN = 9;                        // t_comv, B, gamma_m, gc_stored, gamma_c_last, p, eps_e / eps_B, kn, gM_start
+constexpr int MATH_FIX_OUT = 6;                       // gc, gc_used, Y_T, passes, gM, passes of gM
+constexpr int MATH_GA_IN = 11;                        // B, column_den, gamma_m, gamma_c, gc_used, p, Y_T, kn, then a, c, m
+constexpr int MATH_GA_OUT = 4;                        // gamma_a, Y_c, determine_regime(gamma_a, gamma_c, gamma_m), determine_regime(a, c, m)
+constexpr int MATH_TAB_WORDS = 16;                    // table words of a VAG_MATH_IC_TABLE row
+constexpr int MATH_TAB_IN = 5 + MATH_TAB_WORDS;       // n, first, th_min, th_max, x, 16 table words
 
 // [n_in, n_out] per point of routine `fn` (VAG_MATH_*); 0 for an unknown routine
 inline int math_n_in(int fn) {
@@ -46,6 +56,15 @@ inline int math_n_in(int fn) {
         case VAG_MATH_CROSS_LATTICE: return MATH_LAT_IN;
         case VAG_MATH_RVS_EXTRAP: return MATH_EXT_IN;
         case VAG_MATH_PAIR_INIT: return MATH_INIT_IN;
+        case VAG_MATH_KN_CORR: return 2;           // lg2_nu, lg2_x
+        case VAG_MATH_IC_Y: return MATH_ICY_IN;
+        case VAG_MATH_IC_STEP: return MATH_STEP_IN;
+        case VAG_MATH_IC_FIXED_POINT: return MATH_FIX_IN;
+        case VAG_MATH_IC_GAMMA_A: return MATH_GA_IN;
+        case VAG_MATH_IC_TABLE: return MATH_TAB_IN;
+        case VAG_MATH_IC_BIN_INTEGRAL: return 9;   // f_lo, f_hi, nu_lo, nu_hi, lg2f_lo, lg2f_hi, lg2r, inv_lg2r, trap
+        case VAG_MATH_IC_SUFFIX_SCAN: return 4;    // the lane's four words of its wavefront's 256
+        case VAG_MATH_IC_COLUMN_DEN: return 9;     // gamma, gamma_m, gamma_c, gamma_M, p, regime, column_den, Y_c, Y_at_gamma
         default: return (fn >= 0 && fn < VAG_MATH_COUNT) ? 1 : 0;
     }
 }
@@ -62,11 +81,20 @@ inline int math_n_out(int fn) {
         case VAG_MATH_CROSS_LATTICE: return MATH_LAT_OUT;
         case VAG_MATH_RVS_EXTRAP: return MATH_EXT_OUT;
         case VAG_MATH_PAIR_INIT: return MATH_INIT_OUT;
+        case VAG_MATH_KN_LUT: return 2;            // ratio, log2 ratio
+        case VAG_MATH_KN_CORR: return 4;           // corr, lg2_corr of _pair_lg2, then of _pair_node
+        case VAG_MATH_IC_TABLE: return 2;          // value, breach
+        case VAG_MATH_IC_SUFFIX_SCAN: return 4;
+        case VAG_MATH_IC_Y: return MATH_ICY_OUT;
+        case VAG_MATH_IC_STEP: return MATH_STEP_OUT;
+        case VAG_MATH_IC_FIXED_POINT: return MATH_FIX_OUT;
+        case VAG_MATH_IC_GAMMA_A: return MATH_GA_OUT;
         default: return (fn >= 0 && fn < VAG_MATH_COUNT) ? 1 : 0;
     }
 }
 inline bool math_is_wave(int fn) {
-    return fn == VAG_MATH_WAVE_PREFIX_SUM || fn == VAG_MATH_WAVE_SUM || fn == VAG_MATH_SKY_WAVE_SUM || fn == VAG_MATH_LDS_ADD;
+    return fn == VAG_MATH_WAVE_PREFIX_SUM || fn == VAG_MATH_WAVE_SUM || fn == VAG_MATH_SKY_WAVE_SUM || fn == VAG_MATH_LDS_ADD ||
+           fn == VAG_MATH_IC_SUFFIX_SCAN;
 }
 // What is wrong with point `a` of routine `fn` (host side, before the launch), or nullptr: the integer and flag arguments that index or
 // branch on the device, and the ranges the routines are defined on.
@@ -84,6 +112,13 @@ inline const char* math_point_error(int fn, const double* a) {
         case VAG_MATH_PAIR_INIT:
             if (!(a[6] == VAG_MEDIUM_ISM || a[6] == VAG_MEDIUM_WIND)) return "unknown medium type";
             return (std::isfinite(a[0]) && a[0] > 1 && pos(a[3]) && pos(a[4])) ? nullptr : "need Gamma4 > 1, T0 > 0 and t0 > 0, all finite";
+        case VAG_MATH_KN_LUT: return whole(a[0], 0, KN_LUT_N - 1) ? nullptr : "the node must be an integer in [0, 128)";
+        case VAG_MATH_IC_TABLE: return whole(a[0], -1, MATH_TAB_WORDS) ? nullptr : "n must be an integer in [-1, 16]";
+        case VAG_MATH_IC_COLUMN_DEN: return whole(a[5], 0, 6) ? nullptr : "the regime must be an integer in [0, 6]";
+        case VAG_MATH_IC_Y: return (a[5] == 0 || a[5] == 1) ? nullptr : "the Klein-Nishina flag must be 0 or 1";
+        case VAG_MATH_IC_STEP: return (a[6] == 0 || a[6] == 1) ? nullptr : "the Klein-Nishina flag must be 0 or 1";
+        case VAG_MATH_IC_FIXED_POINT: return (a[7] == 0 || a[7] == 1) ? nullptr : "the Klein-Nishina flag must be 0 or 1";
+        case VAG_MATH_IC_GAMMA_A: return (a[7] == 0 || a[7] == 1) ? nullptr : "the Klein-Nishina flag must be 0 or 1";
         default: return nullptr;
     }
 }
@@ -93,7 +128,8 @@ inline const char* math_point_error(int fn, const double* a) {
 // Dynamic LDS: tables, 64 staged cell blocks, the sky_wave_sum scratch, 64 lds_add_f64 slots.
 constexpr size_t MATH_PROBE_LDS = sizeof(double) * (SP_LDS_DOUBLES + 64 * VAG_NPAR + 64 + 64);
 __global__ void __launch_bounds__(64) vag_math_probe_kernel(int fn, int n, const double* __restrict__ in, double* __restrict__ out,
-                                                            const double* __restrict__ sp_table, double* __restrict__ col) {
+                                                            const double* __restrict__ sp_table, double* __restrict__ col,
+                                                            const double* __restrict__ knlut) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* s_sp = lds;
     for (int i = threadIdx.x; i < SP_LDS_DOUBLES; i += blockDim.x) s_sp[i] = sp_table[i];
@@ -240,6 +276,108 @@ __global__ void __launch_bounds__(64) vag_math_probe_kernel(int fn, int n, const
             double s[RS_N];
             eq.init_state(s, a[4], a[5]);
             for (int q = 0; q < RS_N; ++q) out[(size_t)i * MATH_INIT_OUT + q] = s[q];
+            return;
+        }
+        case VAG_MATH_KN_LUT:  // the context's own Klein-Nishina table, as vag_ctx_create filled it
+            if (ok) out[2 * (size_t)i] = knlut[(int)in[i]], out[2 * (size_t)i + 1] = knlut[KN_LUT_N + (int)in[i]];
+            return;
+        case VAG_MATH_KN_CORR: {
+            if (!ok) return;
+            const double lg2_nu = in[2 * (size_t)i];
+            double lg2_x = in[2 * (size_t)i + 1];
+            if (lg2_x != lg2_x) lg2_x = lg2_nu + log2(C_H / (C_ME * C_C2));  // NaN: the argument _pair_lg2 forms from lg2_nu itself
+            double* r = out + 4 * (size_t)i;
+            compton_correction_pair_lg2(lg2_nu, knlut, r[0], r[1]);
+            compton_correction_pair_node(lg2_x, exp2(lg2_x), knlut, r[2], r[3]);
+            return;
+        }
+        case VAG_MATH_IC_TABLE: {  // the table is the row's own 16 words; last as vag_ic_plan_kernel forms it
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_TAB_IN;
+            int breach = 0;
+            const double last = ic_out_node(a[1], 0.0, (int)a[0] - 1);
+            out[2 * (size_t)i] = ic_table_eval_hdr(a + 5, a[0], a[1], last, a[2], a[3], a[4], &breach);
+            out[2 * (size_t)i + 1] = (double)breach;
+            return;
+        }
+        case VAG_MATH_IC_BIN_INTEGRAL: {
+            if (!ok) return;
+            const double* a = in + (size_t)i * 9;
+            out[i] = power_law_bin_integral(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8]);
+            return;
+        }
+        case VAG_MATH_IC_SUFFIX_SCAN: {  // 256 words per wavefront, in LDS as vag_ic_photon_kernel's histograms are
+            for (int q = 0; q < 4; ++q) s_cell[4 * lane + q] = in[4 * (size_t)i + q];
+            wave_sync();
+            suffix_scan4(s_cell, lane);
+            wave_sync();
+            for (int q = 0; q < 4; ++q) out[4 * (size_t)i + q] = s_cell[4 * lane + q];
+            return;
+        }
+        case VAG_MATH_IC_COLUMN_DEN: {
+            if (!ok) return;
+            const double* a = in + (size_t)i * 9;
+            out[i] = electron_column_den(a[0], a[1], a[2], a[3], a[4], (int)a[5], a[6], a[7], a[8]);
+            return;
+        }
+        case VAG_MATH_IC_Y: {  // the constructor as vag_photons_ic_kernel calls it, the segments as icy_store writes them
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_ICY_IN;
+            IcY Ys;
+            Ys.init(a[0], a[1], a[2], a[3], a[4], a[5] != 0);
+            double w[VAG_NICY];
+            icy_store(Ys, w, 1, 0);
+            double* r = out + (size_t)i * MATH_ICY_OUT;
+            r[0] = Ys.gamma_m_hat, r[1] = Ys.gamma_c_hat, r[2] = Ys.gamma_self, r[3] = (double)Ys.regime, r[4] = w[VY_NSEG];
+            for (int q = 0; q < 9; ++q) r[5 + q] = w[VY_S0 + q];
+            r[14] = Ys.gamma_spectrum(a[6]), r[15] = Ys.gamma_spectrum(a[7]);
+            r[16] = icy_nu_spectrum(Ys, a[8]), r[17] = icy_nu_spectrum(Ys, a[9]);
+            return;
+        }
+        case VAG_MATH_IC_STEP: {  // one pass of the body of each fixed point of ic_gamma_c_cell and of ic_gamma_M
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_STEP_IN;
+            const double t_com = a[0], B = a[1], gm = a[2], gc = a[3], p = a[4];
+            const bool kn = a[6] != 0;
+            IcY Ys;
+            Ys.init_base(gm, p, B);
+            const double lg2_gc = log2_fast(gc);
+            const double Y_T = thomson_Y_lg(a[5], p, gc < gm, lg2_gc - Ys.lg2_gamma_m);
+            double Y = Y_T;
+            if (kn) {
+                Ys.update_cooling_breaks_lg(gc, lg2_gc, Y_T);
+                Y = Ys.gamma_spectrum_lg(lg2_gc);
+            } else {
+                Ys.init(gm, gc, p, B, Y_T, false);
+            }
+            double* r = out + (size_t)i * MATH_STEP_OUT;
+            r[0] = Y_T, r[1] = Y, r[2] = gamma_c_of(t_com, B, Y), r[3] = gamma_M_of(B, Y), r[4] = gamma_M_of(B, Ys.gamma_spectrum(a[7]));
+            return;
+        }
+        case VAG_MATH_IC_FIXED_POINT: {  // the loops themselves: the functions vag_ic_cooling_kernel and vag_photons_ic_kernel call
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_FIX_IN;
+            const bool kn = a[7] != 0;
+            IcY Ys;
+            double gc_used, Y_T;
+            int passes = 0, passes_M = 0;
+            const double gc = ic_gamma_c_cell(Ys, a[0], a[1], a[2], a[3], a[4], a[5], a[6], kn, gc_used, Y_T, &passes);
+            if (!kn) Ys.init(a[2], gc_used, a[5], a[1], Y_T, false);
+            const double gM = ic_gamma_M(a[1], a[8], Ys, &passes_M);
+            double* r = out + (size_t)i * MATH_FIX_OUT;
+            r[0] = gc, r[1] = gc_used, r[2] = Y_T, r[3] = (double)passes, r[4] = gM, r[5] = (double)passes_M;
+            return;
+        }
+        case VAG_MATH_IC_GAMMA_A: {  // as vag_photons_ic_kernel calls them
+            if (!ok) return;
+            const double* a = in + (size_t)i * MATH_GA_IN;
+            const double B = a[0], gm = a[2], gc = a[3], p = a[5];
+            IcY Ys;
+            Ys.init(gm, a[4], p, B, a[6], a[7] != 0);
+            const double Y_c = Ys.gamma_spectrum(gc);
+            const double ga = syn_gamma_a_ic(B, syn_I_peak(B, a[1]), gm, gc, p, Ys, Y_c);
+            double* r = out + (size_t)i * MATH_GA_OUT;
+            r[0] = ga, r[1] = Y_c, r[2] = (double)determine_regime(ga, gc, gm), r[3] = (double)determine_regime(a[8], a[9], a[10]);
             return;
         }
         default: break;

@@ -49,14 +49,53 @@ constexpr double IC_X0 = 0.47140452079103166;
 // is done one lane per CELL at the head of vag_photons_ic_kernel.
 // ------------------------------------------------------------------------------------------------
 // gamma_M's fixed point of one cell (update_gamma_M, inverse-compton.cpp:236-251)
-VAG_DEV double ic_gamma_M(double B, double gM, const IcY& Ys) {
+// (`passes`, here and below: how often the loop's body ran, for the probe of vag_debug_math.h; the kernels do not ask)
+VAG_DEV double ic_gamma_M(double B, double gM, const IcY& Ys, int* passes = nullptr) {
+    if (passes) *passes = 0;
     if (B == 0) return INFINITY;
     double gM_new = gamma_M_of(B, Ys.gamma_spectrum(gM));
-    for (int guard = 0; fabs((gM - gM_new) / gM_new) > 1e-3 && guard < 10000; ++guard) {
+    int guard = 0;
+    for (; fabs((gM - gM_new) / gM_new) > 1e-3 && guard < 10000; ++guard) {
         gM = gM_new;
         gM_new = gamma_M_of(B, Ys.gamma_spectrum(gM));
     }
+    if (passes) *passes = guard;
     return gM;
+}
+
+// gamma_c's fixed point of one cell (update_gamma_c_KN / update_gamma_c_Thomson, inverse-compton.cpp:200-234): `gc` the cell's own
+// synchrotron-only gamma_c, `gamma_c_last` the previous cell's cooled one, which the iteration starts from.  Returns the cooled gamma_c;
+// gc_used and Y_T are what the cell's Y(gamma) is built from, and with kn Ys holds that Y(gamma) (without, only its base).
+VAG_DEV double ic_gamma_c_cell(IcY& Ys, double t_com, double B, double gm, double gc, double gamma_c_last, double p, double e_over_B,
+                               bool kn, double& gc_used, double& Y_T, int* passes = nullptr) {
+    Ys.init_base(gm, p, B);
+    const double lg2_gm = Ys.lg2_gamma_m;
+    if (kn) {
+        double gc_new = gamma_c_last;  // (the constructor's own update with this start value is overwritten by the first pass)
+        int iter = 0;
+        do {
+            gc = gc_new;
+            const double lg2_gc = log2_fast(gc);
+            Y_T = thomson_Y_lg(e_over_B, p, gc < gm, lg2_gc - lg2_gm);
+            Ys.update_cooling_breaks_lg(gc, lg2_gc, Y_T);
+            gc_new = gamma_c_of(t_com, B, Ys.gamma_spectrum_lg(lg2_gc));
+            iter++;
+        } while (fabs((gc_new - gc) / gc) > 1e-3 && iter < 100);
+        if (passes) *passes = iter;
+        gc_used = gc;
+        return gc_new;
+    }
+    Y_T = thomson_Y_lg(e_over_B, p, gc < gm, log2_fast(gc) - lg2_gm);
+    double gc_new = gamma_c_last;
+    int guard = 0;
+    for (; fabs((gc_new - gc) / gc) > 1e-3 && guard < 10000; ++guard) {
+        gc = gc_new;
+        Y_T = thomson_Y_lg(e_over_B, p, gc < gm, log2_fast(gc) - lg2_gm);
+        gc_new = gamma_c_of(t_com, B, Y_T);
+    }
+    if (passes) *passes = guard;
+    gc_used = gc_new;
+    return gc_new;
 }
 
 __global__ void __launch_bounds__(64)
@@ -90,32 +129,7 @@ vag_ic_cooling_kernel(const vag_model_params* __restrict__ params, int nb, const
         }
         double gc_used, Y_T;  // what the cell's Y(gamma) is built from
         IcY Ys;
-        Ys.init_base(gm, P.p, B);
-        const double lg2_gm = Ys.lg2_gamma_m;
-        if (kn) {
-            double gc_new = gamma_c_last;  // (the constructor's own update with this start value is overwritten by the first pass)
-            int iter = 0;
-            do {
-                gc = gc_new;
-                const double lg2_gc = log2_fast(gc);
-                Y_T = thomson_Y_lg(e_over_B, P.p, gc < gm, lg2_gc - lg2_gm);
-                Ys.update_cooling_breaks_lg(gc, lg2_gc, Y_T);
-                gc_new = gamma_c_of(t_com, B, Ys.gamma_spectrum_lg(lg2_gc));
-                iter++;
-            } while (fabs((gc_new - gc) / gc) > 1e-3 && iter < 100);
-            gc_used = gc;
-            gc = gc_new;
-        } else {
-            Y_T = thomson_Y_lg(e_over_B, P.p, gc < gm, log2_fast(gc) - lg2_gm);
-            double gc_new = gamma_c_last;
-            for (int guard = 0; fabs((gc_new - gc) / gc) > 1e-3 && guard < 10000; ++guard) {
-                gc = gc_new;
-                Y_T = thomson_Y_lg(e_over_B, P.p, gc < gm, log2_fast(gc) - lg2_gm);
-                gc_new = gamma_c_of(t_com, B, Y_T);
-            }
-            gc = gc_new;
-            gc_used = gc;
-        }
+        gc = ic_gamma_c_cell(Ys, t_com, B, gm, gc, gamma_c_last, P.p, e_over_B, kn, gc_used, Y_T);
         if (k >= k_inj) {  // cool_relic_electrons inside IC_cooling, inverse-compton.h:752
             gc = cool_after_crossing(inj_gc, inj_gm, gm);
             det[VD_GAMMA_MAX * n_cells + c] = cool_after_crossing(inj_gM, inj_gm, gm);
