@@ -1157,6 +1157,58 @@ int vag_tempered_run_dev(vag_ctx* ctx, const vag_loglike_request* request, const
                          double* d_pos, double* d_lnl, double* d_lnprior, int64_t* d_accepted, int64_t* d_swapped, double* d_chain,
                          double* d_lnl_chain, double* d_lnprior_chain);
 
+/* Nested sampling on the device (added after VAG_ABI_VERSION 13, detect by symbol), by the definition of INTEGRATION.md "Nested
+ * sampling".  N = n_live live points, N even, 4 <= N <= VAG_NESTED_MAX_LIVE, ndim 1 .. 16, K = N / 2; every live point has finite
+ * ln L and ln prior.  Layouts: live[N][ndim], lnl[N], lnprior[N], order[N] (int32), lstar[1], prop[K][ndim], and per iteration a
+ * row of the dead record dead_theta[K][ndim], dead_lnl[K], dead_lnprior[K] and of the counts accepted[K].
+ * Iteration `it`: (rank) slot i comes before slot j iff (lnl[i], i) < (lnl[j], j); order[r] is the slot of rank r, the dead are
+ * ranks 0 .. K - 1, the survivors ranks K .. N - 1, and lstar[0] = lnl[order[K - 1]].  (retire) The dead row takes the dead in rank
+ * order, then slot order[r] becomes a copy of survivor order[K + j0], j0 = floor(u K).  (walk) For m = 1 .. walk: clone r proposes
+ * prop[r][d] = fma(gamma, live[s1][d] - live[s2][d], live[order[r]][d]) with the survivors s1 = order[K + a], s2 = order[K + b] and
+ * the scale gamma of the DE kind of the move mix above (a, b, n_q, gamma0 = 0 standing for 2.38 / sqrt(2 ndim)); the K proposals in
+ * rank order are one likelihood call; clone r takes its proposal iff ln L' and ln prior' are finite, ln L' > lstar[0] (strict) and
+ * log(u_a) < ln prior' - ln prior, and accepted[r] counts one.  The survivors do not move during an iteration.
+ * The draws are Philox4x32-10 with the key above and counter (r, tick & 0xffffffff, tick >> 32, stream), tick = it (walk + 1) + m:
+ * m = 0 the clone draw with u = u(first two words) of stream 5; m = 1 .. walk the walk steps with streams 0 and 4 (the proposal) and
+ * 1 (the acceptance) read as the DE kind reads them, nh = K.  The flattened dead record is non-decreasing in ln L; the evidence is
+ * formed on the host from it (sampling.nested_evidence). */
+#define VAG_NESTED_MAX_LIVE 16384
+typedef struct vag_nested_spec {
+    uint64_t seed;
+    int32_t n_live;  /* N: even, 4 .. VAG_NESTED_MAX_LIVE */
+    int32_t ndim;    /* 1 .. 16 */
+    int32_t walk;    /* constrained steps per iteration, >= 1 */
+    int32_t pad;
+    double gamma0;   /* the DE scale, finite and >= 0; 0: the default 2.38 / sqrt(2 ndim) */
+    double sigma;    /* the relative jitter of the DE scale, finite (1e-5 is customary) */
+} vag_nested_spec;
+
+/* The building blocks (no model): device pointers, the context's stream, no host synchronisation.  rank reads d_lnl and writes
+ * d_order and d_lstar; retire writes the dead row given and the dead slots of d_live / d_lnl / d_lnprior; propose writes d_prop;
+ * accept reads d_lstar and the proposals' ln L and ln prior, changes the clones in place and adds to d_accepted[K].  m is the walk
+ * step, 1 .. walk.  An entry of d_order outside 0 .. N - 1 is read as slot 0.  Refused with VAG_E_INVALID (the context stays usable):
+ * a null context, spec or buffer; n_live odd or outside 4 .. VAG_NESTED_MAX_LIVE; ndim outside 1 .. 16; walk < 1; gamma0 not finite
+ * or < 0; sigma not finite; m outside 1 .. walk. */
+int vag_nested_rank_dev(vag_ctx* ctx, const vag_nested_spec* sp, const double* d_lnl, int32_t* d_order, double* d_lstar);
+int vag_nested_retire_dev(vag_ctx* ctx, const vag_nested_spec* sp, uint64_t it, const int32_t* d_order, double* d_live, double* d_lnl,
+                          double* d_lnprior, double* d_dead_theta, double* d_dead_lnl, double* d_dead_lnprior);
+int vag_nested_propose_dev(vag_ctx* ctx, const vag_nested_spec* sp, uint64_t it, int m, const int32_t* d_order, const double* d_live,
+                           double* d_prop);
+int vag_nested_accept_dev(vag_ctx* ctx, const vag_nested_spec* sp, uint64_t it, int m, const int32_t* d_order, const double* d_lstar,
+                          const double* d_prop, const double* d_lnl_new, const double* d_lnprior_new, double* d_live, double* d_lnl,
+                          double* d_lnprior, int64_t* d_accepted);
+
+/* Iterations it0 .. it0 + n_iters - 1 on the likelihood of `request`: per iteration rank, retire, and `walk` times propose, ONE
+ * likelihood call of the K proposals, its split into ln L and ln prior, accept.  On entry d_lnl / d_lnprior hold those of d_live,
+ * all finite.  Iteration it0 + k fills row k of d_dead_theta[n_iters][K][ndim], d_dead_lnl[n_iters][K], d_dead_lnprior[n_iters][K]
+ * and adds to row k of d_accepted[n_iters][K], which the caller zeroes.  The blocks are scanned and uploaded once per call; between
+ * the iterations there is no copy to the host and no stream synchronisation (a likelihood call itself waits for its device plan).
+ * n_iters = 0 does nothing.  Refusals as above, and: a null request or request->spec, ndim different from request->spec->ndim,
+ * n_iters < 0, and whatever the likelihood call refuses. */
+int vag_nested_run_dev(vag_ctx* ctx, const vag_loglike_request* request, const vag_nested_spec* sp, uint64_t it0, int n_iters,
+                       double* d_live, double* d_lnl, double* d_lnprior, int64_t* d_accepted, double* d_dead_theta, double* d_dead_lnl,
+                       double* d_dead_lnprior);
+
 /* Chain autocorrelation on the device (added after VAG_ABI_VERSION 13, detect by symbol): the integrated autocorrelation time of
  * every parameter of a chain in HBM, by the definition of INTEGRATION.md "Chain autocorrelation".
  * The view: n_rows rows, nwalkers walkers, ndim parameters, element (t, w, d) at d_chain[t row_stride + w ndim + d] with

@@ -265,6 +265,20 @@ def tempered_entry(lib, name):
                   "fit(sampler='tempered')) needs")
 
 
+class NestedSpec(C.Structure):  # vag_nested_spec
+    _fields_ = [("seed", C.c_uint64), ("n_live", C.c_int32), ("ndim", C.c_int32), ("walk", C.c_int32), ("pad", C.c_int32),
+                ("gamma0", C.c_double), ("sigma", C.c_double)]
+
+
+NESTED_MAX_LIVE = 16384  # VAG_NESTED_MAX_LIVE
+NESTED_ENTRIES = ("vag_nested_rank_dev", "vag_nested_retire_dev", "vag_nested_propose_dev", "vag_nested_accept_dev", "vag_nested_run_dev")
+
+
+def nested_entry(lib, name):
+    """One of the nested-sampling entry points."""
+    return _entry(lib, name, "nested sampling (sampling.NestedMove, run_nested_device, fit(sampler='nested')) needs")
+
+
 class ChainSpec(C.Structure):  # vag_chain_spec
     _fields_ = [("nwalkers", C.c_int32), ("ndim", C.c_int32), ("n_rows", C.c_int64), ("row_stride", C.c_int64), ("max_lag", C.c_int32),
                 ("c", C.c_double)]
@@ -355,6 +369,7 @@ EXPORTS = [
     "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev", "vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev",
     "vag_loglike_split_dev", "vag_tempered_propose_dev", "vag_tempered_accept_dev", "vag_tempered_swap_dev", "vag_tempered_run_dev",
     "vag_move_propose_dev", "vag_move_accept_dev", "vag_move_run_dev", "vag_chain_autocorr_dev",
+    "vag_nested_rank_dev", "vag_nested_retire_dev", "vag_nested_propose_dev", "vag_nested_accept_dev", "vag_nested_run_dev",
     "vag_column_quantiles_dev", "vag_predict_bands_dev",
 ]
 
@@ -469,6 +484,13 @@ def load():
         lib.vag_tempered_accept_dev.argtypes = [v, tp, C.c_uint64, C.c_int, v, v, v, v, v, v, v]
         lib.vag_tempered_swap_dev.argtypes = [v, tp, C.c_uint64, v, v, v, v]
         lib.vag_tempered_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), tp, C.c_uint64, C.c_int, v, v, v, v, v, v, v, v]
+    if hasattr(lib, "vag_nested_run_dev"):  # (detected by symbol: nested sampling)
+        ns = C.POINTER(NestedSpec)
+        lib.vag_nested_rank_dev.argtypes = [v, ns, v, v, v]
+        lib.vag_nested_retire_dev.argtypes = [v, ns, C.c_uint64, v, v, v, v, v, v, v]
+        lib.vag_nested_propose_dev.argtypes = [v, ns, C.c_uint64, C.c_int, v, v, v]
+        lib.vag_nested_accept_dev.argtypes = [v, ns, C.c_uint64, C.c_int, v, v, v, v, v, v, v, v, v]
+        lib.vag_nested_run_dev.argtypes = [v, C.POINTER(LoglikeRequest), ns, C.c_uint64, C.c_int, v, v, v, v, v, v, v]
     if hasattr(lib, "vag_chain_autocorr_dev"):  # (detected by symbol: chain autocorrelation)
         lib.vag_chain_autocorr_dev.argtypes = [v, C.POINTER(ChainSpec), v, v, v, v]
     if hasattr(lib, "vag_predict_bands_dev"):  # (detected by symbol: posterior-predictive bands)

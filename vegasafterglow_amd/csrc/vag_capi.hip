@@ -33,6 +33,7 @@
 #include "vag_sampler.h"
 #include "vag_tempering.h"
 #include "vag_moves.h"
+#include "vag_nested.h"
 #include "vag_sampler_plan.h"
 #include "vag_chain_stats.h"
 #include "vag_predict.h"
@@ -445,6 +446,7 @@ struct vag_ctx {
     DevBuf d_skycen, d_skycmom;  // exact centroids (vag_sky.h): row-block partials, moments
     DevBuf d_visblk, d_vispart;  // visibility groups of the likelihood (their data: vis below): their 64-visibility blocks, chi^2 partials
     DevBuf d_sampler_prop, d_sampler_fresh, d_sampler_aux;  // the device sampler's run entries (sampler_run), one set for the three moves, as large as the largest run so far: a half-step's proposals [nb][ndim], their ln p or ln L [nb], their Hastings factor or ln prior [nb]
+    DevBuf d_nested_rank;  // nested sampling's run entry (vag_nested_run_dev): L* [1], then the slots by rank, int32 [N]
     DevBuf d_chain_stats;  // chain autocorrelation (vag_chain_autocorr_dev): the means [S], the lag sums [L + 1][S], the pooled sums [L + 1][D]
     DevBuf d_predict;  // posterior-predictive bands (vag_column_quantiles_dev, vag_predict_bands_dev): the draws' A_V [S] and, where the caller keeps none, their fluxes [S][M]; behind them int32: the engine's verdict [S], the validity [S]
     DevBuf d_polspec, d_polstokes;  // polarization groups of the likelihood (their data: pol below): the walkers' spec + its flag, jet-frame I, Q, U
@@ -758,7 +760,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_icwork.release();
     for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
     c->d_fitstat.release();
-    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_sampler_prop, &c->d_sampler_fresh, &c->d_sampler_aux, &c->d_chain_stats, &c->d_predict})
+    for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_sampler_prop, &c->d_sampler_fresh, &c->d_sampler_aux, &c->d_nested_rank, &c->d_chain_stats, &c->d_predict})
         b->release();
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3748,8 +3750,8 @@ int vag_loglike_cov_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
     return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
-// ---- the device sampler: the stretch move, the move mix, parallel tempering (kernels: vag_sampler.h, vag_moves.h, vag_tempering.h;
-//      what the specs refuse and the arithmetic of the launches: vag_sampler_plan.h; the moves: the public header) ----
+// ---- the device sampler: the stretch move, the move mix, parallel tempering, nested sampling (kernels: vag_sampler.h, vag_moves.h,
+//      vag_tempering.h, vag_nested.h; what the specs refuse and the arithmetic of the launches: vag_sampler_plan.h; the moves: the public header) ----
 
 extern "C++" {  // (templates: this section lies within the extern "C" of the entry points)
 
@@ -3762,7 +3764,7 @@ static int sampler_launch(vag_ctx* c, Kernel kernel, long long items, uint64_t s
     return VAG_OK;
 }
 
-// The prologue of the seven building-block entries, in this order: lock, handoff, nulls (`given`: the context, the spec and every
+// The prologue of the eleven building-block entries, in this order: lock, handoff, nulls (`given`: the context, the spec and every
 // buffer are there), the spec's checks, half (`who` null: the entry takes none), the device; then the launch.
 template <class Check, class Launch>
 static int sampler_entry(vag_ctx* c, bool given, const char* what, Check check, const char* who, int half, Launch launch) {
@@ -3775,20 +3777,21 @@ static int sampler_entry(vag_ctx* c, bool given, const char* what, Check check, 
     return launch();
 }
 
-// the scratch of a half-step of nb proposals: one set for the three moves, grown by whichever runs
+// the scratch of a phase of nb proposals: one set for the four samplers, grown by whichever runs
 struct SamplerScratch {
     double* prop;   // the proposals [nb][ndim]
-    double* fresh;  // their ln p; under tempering their ln L [nb]
-    double* aux;    // the ln of their Hastings factor (the move mix), their ln prior (tempering) [nb]
+    double* fresh;  // their ln p; under tempering and nested sampling their ln L [nb]
+    double* aux;    // the ln of their Hastings factor (the move mix), their ln prior (tempering, nested sampling) [nb]
 };
 
 // The steps step0 .. step0 + n_steps - 1 of a run entry whose arguments have passed their checks: the scans and the uploads once,
-// then per step and half propose, ONE likelihood call of the nb proposals, what the move runs behind it, accept; then what ends the
-// step.  Between the steps there is no copy to the host and no stream synchronisation.  accept and end_step are told whether the
-// step is stored and which row it fills.
-template <class Propose, class Behind, class Accept, class EndStep>
-static int sampler_run(vag_ctx* c, const vag_loglike_request* q, int ndim, int nb, int thin, bool storing, uint64_t step0, int n_steps,
-                       Propose propose, Behind behind, Accept accept, EndStep end_step) {
+// then per step what begins it and, per phase (`phases` of them: the two halves of a move, the walk steps of a nested iteration),
+// propose, ONE likelihood call of the nb proposals, what the move runs behind it, accept; then what ends the step.  Between the steps
+// there is no copy to the host and no stream synchronisation.  begin_step, accept and end_step are told whether the step is stored
+// and which row it fills.
+template <class BeginStep, class Propose, class Behind, class Accept, class EndStep>
+static int sampler_run(vag_ctx* c, const vag_loglike_request* q, int ndim, int nb, int phases, int thin, bool storing, uint64_t step0,
+                       int n_steps, BeginStep begin_step, Propose propose, Behind behind, Accept accept, EndStep end_step) {
     if (n_steps == 0) return VAG_OK;
     FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
     int rc = fit_request_prepare(req);  // the scans, once per call of many steps
@@ -3805,7 +3808,8 @@ static int sampler_run(vag_ctx* c, const vag_loglike_request* q, int ndim, int n
     for (int k = 0; k < n_steps; ++k) {
         const uint64_t step = step0 + (uint64_t)k;
         const bool stored = storing && step_is_stored(step, thin);
-        for (int which = 0; which < 2; ++which) {
+        if ((rc = begin_step(step, stored, row))) return rc;
+        for (int which = 0; which < phases; ++which) {
             if ((rc = propose(step, which, s))) return rc;
             if ((rc = loglike_call(c, req, s.prop, nb, ndim, s.fresh))) return rc;
             if ((rc = behind(s))) return rc;
@@ -3858,7 +3862,7 @@ int vag_stretch_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_stre
     if (const int rc = run_steps_check("stretch move", sp->ndim, q->spec->ndim, n_steps)) return rc;
     const int nw = sp->n_walkers, ndim = sp->ndim;
     return sampler_run(
-        c, q, ndim, half_of(nw), sp->thin, d_chain != nullptr, step0, n_steps,
+        c, q, ndim, half_of(nw), HALF_PHASES, sp->thin, d_chain != nullptr, step0, n_steps, no_hook,
         [&](uint64_t step, int which, const SamplerScratch& s) { return stretch_propose(c, sp, step, which, d_pos, s.prop); }, no_hook,
         [&](uint64_t step, int which, const SamplerScratch& s, bool stored, size_t row) {
             return stretch_accept(c, sp, step, which, s.prop, s.fresh, d_pos, d_lp, d_accepted,
@@ -3918,7 +3922,7 @@ int vag_move_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_move_sp
     if (const int rc = run_steps_check("move mix", sp->ndim, q->spec->ndim, n_steps)) return rc;
     const int nw = sp->n_walkers, ndim = sp->ndim;
     return sampler_run(
-        c, q, ndim, half_of(nw), sp->thin, d_chain != nullptr, step0, n_steps,
+        c, q, ndim, half_of(nw), HALF_PHASES, sp->thin, d_chain != nullptr, step0, n_steps, no_hook,
         [&](uint64_t step, int which, const SamplerScratch& s) { return move_propose(c, sp, step, which, d_pos, s.prop, s.aux); }, no_hook,
         [&](uint64_t step, int which, const SamplerScratch& s, bool stored, size_t row) {
             return move_accept(c, sp, step, which, s.prop, s.aux, s.fresh, d_pos, d_lp, d_accepted,
@@ -4013,7 +4017,7 @@ int vag_tempered_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_tem
     const int T = sp->n_temps, nw = sp->n_walkers, ndim = sp->ndim, nb = T * half_of(nw);
     const size_t replicas = (size_t)T * nw;
     return sampler_run(
-        c, q, ndim, nb, sp->thin, d_chain != nullptr, step0, n_steps,  // all temperatures' proposals of the half in ONE likelihood call
+        c, q, ndim, nb, HALF_PHASES, sp->thin, d_chain != nullptr, step0, n_steps, no_hook,  // all temperatures' proposals of the half in ONE likelihood call
         [&](uint64_t step, int which, const SamplerScratch& s) { return tempered_propose(c, sp, step, which, d_pos, s.prop); },
         [&](const SamplerScratch& s) { return fit_split(c, nb, s.fresh, s.aux); },
         [&](uint64_t step, int which, const SamplerScratch& s, bool, size_t) {
@@ -4027,6 +4031,99 @@ int vag_tempered_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_tem
             HIPCHK(hipMemcpyAsync(d_lnprior_chain + ladder_row_offset(row, T, nw, 1), d_lnprior, sizeof(double) * replicas, hipMemcpyDeviceToDevice, c->stream));
             return VAG_OK;
         });
+}
+
+// -- nested sampling: an iteration is rank, retire, then `walk` phases of propose, the likelihood call, its split, accept --
+
+static double nested_gamma0(const vag_nested_spec* sp) { return sp->gamma0 > 0.0 ? sp->gamma0 : de_gamma0(sp->ndim); }
+
+static int nested_rank(vag_ctx* c, const vag_nested_spec* sp, const double* d_lnl, int32_t* d_order, double* d_lstar) {
+    hipLaunchKernelGGL(vag_nested_rank_kernel, dim3(lane_groups(sp->n_live)), dim3(STRETCH_LANES), 0, c->stream, sp->n_live, d_lnl, d_order,
+                       d_lstar);  // (no draw: the one sampler kernel without the seed's key)
+    HIPCHK(hipGetLastError());
+    return VAG_OK;
+}
+
+static int nested_retire(vag_ctx* c, const vag_nested_spec* sp, uint64_t it, const int32_t* d_order, double* d_live, double* d_lnl,
+                         double* d_lnprior, double* d_dead_theta, double* d_dead_lnl, double* d_dead_lnprior) {
+    return sampler_launch(c, vag_nested_retire_kernel, half_of(sp->n_live), sp->seed, nested_tick(it, sp->walk, 0), sp->n_live, sp->ndim,
+                          d_order, d_live, d_lnl, d_lnprior, d_dead_theta, d_dead_lnl, d_dead_lnprior);
+}
+
+static int nested_propose(vag_ctx* c, const vag_nested_spec* sp, uint64_t it, int m, const int32_t* d_order, const double* d_live,
+                          double* d_prop) {
+    return sampler_launch(c, vag_nested_propose_kernel, half_of(sp->n_live), sp->seed, nested_gamma0(sp), sp->sigma,
+                          nested_tick(it, sp->walk, m), sp->n_live, sp->ndim, d_order, d_live, d_prop);
+}
+
+static int nested_accept(vag_ctx* c, const vag_nested_spec* sp, uint64_t it, int m, const int32_t* d_order, const double* d_lstar,
+                         const double* d_prop, const double* d_lnl_new, const double* d_lnprior_new, double* d_live, double* d_lnl,
+                         double* d_lnprior, int64_t* d_accepted) {
+    return sampler_launch(c, vag_nested_accept_kernel, half_of(sp->n_live), sp->seed, nested_tick(it, sp->walk, m), sp->n_live, sp->ndim,
+                          d_order, d_lstar, d_prop, d_lnl_new, d_lnprior_new, d_live, d_lnl, d_lnprior,
+                          reinterpret_cast<long long*>(d_accepted));
+}
+
+int vag_nested_rank_dev(vag_ctx* c, const vag_nested_spec* sp, const double* d_lnl, int32_t* d_order, double* d_lstar) {
+    return sampler_entry(c, c && sp && d_lnl && d_order && d_lstar, "nested", [&] { return nested_spec_check(sp); }, nullptr, 0,
+                         [&] { return nested_rank(c, sp, d_lnl, d_order, d_lstar); });
+}
+
+int vag_nested_retire_dev(vag_ctx* c, const vag_nested_spec* sp, uint64_t it, const int32_t* d_order, double* d_live, double* d_lnl,
+                          double* d_lnprior, double* d_dead_theta, double* d_dead_lnl, double* d_dead_lnprior) {
+    return sampler_entry(c, c && sp && d_order && d_live && d_lnl && d_lnprior && d_dead_theta && d_dead_lnl && d_dead_lnprior, "nested",
+                         [&] { return nested_spec_check(sp); }, nullptr, 0, [&] {
+                             return nested_retire(c, sp, it, d_order, d_live, d_lnl, d_lnprior, d_dead_theta, d_dead_lnl, d_dead_lnprior);
+                         });
+}
+
+int vag_nested_propose_dev(vag_ctx* c, const vag_nested_spec* sp, uint64_t it, int m, const int32_t* d_order, const double* d_live,
+                           double* d_prop) {
+    return sampler_entry(c, c && sp && d_order && d_live && d_prop, "nested",
+                         [&] { const int rc = nested_spec_check(sp); return rc ? rc : nested_walk_step_check(sp, m); }, nullptr, 0,
+                         [&] { return nested_propose(c, sp, it, m, d_order, d_live, d_prop); });
+}
+
+int vag_nested_accept_dev(vag_ctx* c, const vag_nested_spec* sp, uint64_t it, int m, const int32_t* d_order, const double* d_lstar,
+                          const double* d_prop, const double* d_lnl_new, const double* d_lnprior_new, double* d_live, double* d_lnl,
+                          double* d_lnprior, int64_t* d_accepted) {
+    return sampler_entry(c, c && sp && d_order && d_lstar && d_prop && d_lnl_new && d_lnprior_new && d_live && d_lnl && d_lnprior && d_accepted,
+                         "nested", [&] { const int rc = nested_spec_check(sp); return rc ? rc : nested_walk_step_check(sp, m); }, nullptr, 0,
+                         [&] {
+                             return nested_accept(c, sp, it, m, d_order, d_lstar, d_prop, d_lnl_new, d_lnprior_new, d_live, d_lnl, d_lnprior,
+                                                  d_accepted);
+                         });
+}
+
+int vag_nested_run_dev(vag_ctx* c, const vag_loglike_request* q, const vag_nested_spec* sp, uint64_t it0, int n_iters, double* d_live,
+                       double* d_lnl, double* d_lnprior, int64_t* d_accepted, double* d_dead_theta, double* d_dead_lnl,
+                       double* d_dead_lnprior) {
+    ApiLock api_lock(c);
+    HandoffScope handoff(c);
+    if (!c || !q || !q->spec || !sp || !d_live || !d_lnl || !d_lnprior || !d_accepted || !d_dead_theta || !d_dead_lnl || !d_dead_lnprior)
+        return set_err(VAG_E_INVALID, "null context, request, fit spec, nested spec or buffer");
+    if (const int rc = nested_spec_check(sp)) return rc;
+    if (const int rc = run_steps_check("nested sampling", sp->ndim, q->spec->ndim, n_iters)) return rc;
+    if (n_iters == 0) return VAG_OK;
+    const int n = sp->n_live, ndim = sp->ndim, nb = half_of(n);
+    HIPCHK(hipSetDevice(c->device));
+    if (c->d_nested_rank.ensure(sizeof(double) + sizeof(int32_t) * (size_t)n)) return VAG_E_HIP;
+    double* d_lstar = c->d_nested_rank.as<double>();
+    int32_t* d_order = reinterpret_cast<int32_t*>(d_lstar + 1);
+    return sampler_run(
+        c, q, ndim, nb, nested_phases(sp), 1, true, it0, n_iters,  // every iteration is stored: row = it - it0
+        [&](uint64_t it, bool, size_t row) -> int {
+            if (const int rc = nested_rank(c, sp, d_lnl, d_order, d_lstar)) return rc;
+            return nested_retire(c, sp, it, d_order, d_live, d_lnl, d_lnprior, d_dead_theta + dead_row_offset(row, n, ndim),
+                                 d_dead_lnl + dead_row_offset(row, n, 1), d_dead_lnprior + dead_row_offset(row, n, 1));
+        },
+        [&](uint64_t it, int phase, const SamplerScratch& s) { return nested_propose(c, sp, it, phase + 1, d_order, d_live, s.prop); },
+        [&](const SamplerScratch& s) { return fit_split(c, nb, s.fresh, s.aux); },  // the K proposals, in rank order, in ONE likelihood call
+        [&](uint64_t it, int phase, const SamplerScratch& s, bool, size_t row) {
+            return nested_accept(c, sp, it, phase + 1, d_order, d_lstar, s.prop, s.fresh, s.aux, d_live, d_lnl, d_lnprior,
+                                 d_accepted + dead_row_offset(row, n, 1));
+        },
+        no_hook);
 }
 
 // ---- chain autocorrelation (kernels and the definition's pieces: vag_chain_stats.h; the definition: the public header) ----

@@ -9,7 +9,8 @@
 // to the bit (sampling.de_proposals, sampling.snooker_proposals).
 //
 // Streams of the counter (w, step lo, step hi, stream): 0 the proposal, 1 the acceptance, 2 the exchange (vag_tempering.h), 3 the
-// move choice (w = 0: one choice per step, shared by both halves), 4 a second block of proposal words.
+// move choice (w = 0: one choice per step, shared by both halves), 4 a second block of proposal words, 5 the clone choice of nested
+// sampling (vag_nested.h).
 #pragma once
 #include "vag_philox.h"
 

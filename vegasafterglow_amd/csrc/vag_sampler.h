@@ -12,7 +12,7 @@
 
 namespace vag {
 
-constexpr uint32_t STREAM_PROPOSAL = 0u, STREAM_ACCEPT = 1u, STREAM_EXCHANGE = 2u;  // (3 and 4: vag_moves.h)
+constexpr uint32_t STREAM_PROPOSAL = 0u, STREAM_ACCEPT = 1u, STREAM_EXCHANGE = 2u;  // (3 and 4: vag_moves.h; 5: vag_nested.h)
 
 // the words of stream `stream` of replica r at `step`: counter (r, step lo, step hi, stream) under the key (seed_lo, seed_hi)
 __device__ inline void stream_words(uint32_t seed_lo, uint32_t seed_hi, unsigned long long step, int r, uint32_t stream, uint32_t out[4]) {

@@ -1,5 +1,5 @@
 // vag_sampler_plan.h -- the host side of the device sampler between "an entry point was called" and "a kernel is in the queue": what
-// the three specs (stretch move, move mix, parallel tempering) refuse, the kind of a step of the mix, what a run entry refuses of its
+// the four specs (stretch move, move mix, parallel tempering, nested sampling) refuse, the kind of a step of the mix, what a run entry refuses of its
 // arguments, and the integer arithmetic the launchers and the step loop share -- the seed's halves, the half, workgroups, stored
 // rows, exchange pairs, row offsets.  Plain C++17: no device header, no context, no allocation -- a host compiler builds it, and
 // tests/sampler_plan_check.cpp holds every decision at its threshold and on each side of it.  vag_capi.hip keeps the locks, the
@@ -11,12 +11,14 @@
 
 #include "vag_fit_request.h"  // set_err
 #include "vag_moves.h"        // move_choice, move_choice_uniform
+#include "vag_nested.h"       // VAG_NESTED_MAX_LIVE_POINTS
 #include "vag_tempering.h"    // TemperLadder
 
 namespace vag {
 
 static_assert(VAG_MOVE_STRETCH == MOVE_STRETCH && VAG_MOVE_DE == MOVE_DE && VAG_MOVE_SNOOKER == MOVE_SNOOKER, "the public kinds are the header's");
 static_assert(VAG_TEMPER_MAX == VAG_TEMPER_MAX_RUNGS, "the public ladder limit is the kernels'");
+static_assert(VAG_NESTED_MAX_LIVE == VAG_NESTED_MAX_LIVE_POINTS, "the public live-point limit is the kernels'");
 
 // ---- what the specs refuse ----
 
@@ -72,6 +74,24 @@ inline int tempered_spec_check(const vag_tempered_spec* sp, TemperLadder& ladder
     return VAG_OK;
 }
 
+// the checks of a nested spec (not null)
+inline int nested_spec_check(const vag_nested_spec* sp) {
+    if (sp->ndim < 1 || sp->ndim > 16) return set_err(VAG_E_INVALID, "nested sampling: ndim must be 1..16, got %d", sp->ndim);
+    if (sp->n_live < 4 || sp->n_live > VAG_NESTED_MAX_LIVE || (sp->n_live & 1))
+        return set_err(VAG_E_INVALID, "nested sampling: need an even number of live points, 4..%d, got %d", VAG_NESTED_MAX_LIVE, sp->n_live);
+    if (sp->walk < 1) return set_err(VAG_E_INVALID, "nested sampling: walk must be >= 1, got %d", sp->walk);
+    if (!std::isfinite(sp->gamma0) || sp->gamma0 < 0.0)
+        return set_err(VAG_E_INVALID, "nested sampling: gamma0 must be finite and >= 0 (0: 2.38 / sqrt(2 ndim)), got %g", sp->gamma0);
+    if (!std::isfinite(sp->sigma)) return set_err(VAG_E_INVALID, "nested sampling: sigma must be finite, got %g", sp->sigma);
+    return VAG_OK;
+}
+
+// the walk step of a nested building block: 1 .. walk (0 is the clone draw, which retire makes)
+inline int nested_walk_step_check(const vag_nested_spec* sp, int m) {
+    if (m < 1 || m > sp->walk) return set_err(VAG_E_INVALID, "nested sampling: the walk step m must be 1..walk = %d, got %d", sp->walk, m);
+    return VAG_OK;
+}
+
 // `who`: "stretch move", "move mix" or "tempering", the prefix of the entry's own refusals
 inline int half_check(const char* who, int half) {
     if (half != 0 && half != 1) return set_err(VAG_E_INVALID, "%s: half must be 0 or 1, got %d", who, half);
@@ -91,6 +111,11 @@ inline int run_steps_check(const char* who, int ndim, int fit_ndim, int n_steps)
     if (n_steps < 0) return set_err(VAG_E_INVALID, "%s: n_steps must be >= 0, got %d", who, n_steps);
     return VAG_OK;
 }
+
+// ---- the phases of a step of the shared step loop: each is propose, ONE likelihood call, accept ----
+
+constexpr int HALF_PHASES = 2;  // the three moves: half 0, then half 1
+inline int nested_phases(const vag_nested_spec* sp) { return sp->walk; }  // nested sampling: the walk steps m = phase + 1
 
 // ---- the kind of `step` of the mix, chosen on the host: the kernels do not branch on it ----
 
@@ -122,5 +147,7 @@ inline size_t ensemble_row_offset(size_t row, int n_walkers, int width) { return
 inline size_t ladder_row_offset(size_t row, int n_temps, int n_walkers, int width) {
     return row * ((size_t)n_temps * (size_t)n_walkers) * (size_t)width;
 }
+// of the dead record and the counts of nested sampling, [rows][n_live / 2][width]: an iteration retires half the live points
+inline size_t dead_row_offset(size_t row, int n_live, int width) { return ensemble_row_offset(row, half_of(n_live), width); }
 
 }  // namespace vag

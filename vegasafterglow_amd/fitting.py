@@ -1882,7 +1882,14 @@ class Fitter:
         tempering on the device (sampling.run_tempered_device; ``ntemps``, ``beta_min``, ``prior_rung`` shape the ladder, `nwalkers`
         is per temperature), which also returns the evidence by thermodynamic integration.  Every sampler reports "tau" and
         "tau_reliable", the autocorrelation time of each parameter after the burn-in; ``converge=sampling.Convergence(...)`` makes
-        `nsteps` a maximum for the device samplers and stops the run when tau has settled (sampling.fit)."""
+        `nsteps` a maximum for the device samplers and stops the run when tau has settled (sampling.fit).
+
+        ``sampler="nested"``: nested sampling on the device (sampling.run_nested_device) with `nwalkers` live points, `nsteps` the
+        maximum number of iterations, ``dlogz=0.1`` the stopping rule, ``walk=None`` the constrained steps per iteration and
+        ``priors=None`` the priors.  It returns the weighted samples, "log_evidence" with its error sqrt(H / N) from the run itself,
+        "information", "prior_fraction" and "log_prior_mass".  "log_evidence" includes ln prior_fraction (points where the model does
+        not evaluate count as L = 0); the tempered number excludes it; both are relative to the prior mass inside the boxes, which
+        is "log_prior_mass" (sampling.fit)."""
         from . import sampling
         self.validate_parameters(param_defs)
         ndim = sum(1 for pd in param_defs if pd.scale is not Scale.fixed)

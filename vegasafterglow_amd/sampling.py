@@ -18,6 +18,11 @@ walkers over a thread pool (VegasAfterglow/fitting/samplers.py:59-106).  Here th
   (``geometric_betas``), all temperatures' proposals in one likelihood call per half-step, exchanges between neighbours, and the
   evidence by thermodynamic integration (``thermodynamic_evidence``).  ``run_tempered_philox``, ``tempered_proposals``,
   ``tempered_accepts`` and ``tempered_swaps`` state it in numpy, to the bit;
+* ``run_nested_device`` / ``NestedMove`` -- nested sampling on the device: every iteration retires the lower half of the live points
+  and replaces each by a clone of a survivor that walks constrained DE steps, the half's proposals in one likelihood call per walk
+  step; the evidence and its error come out of the run (``nested_evidence``).  ``run_nested_philox``, ``nested_order``,
+  ``nested_clones``, ``nested_proposals`` and ``nested_accepts`` state it in numpy, to the bit; ``sample_prior`` and ``prior_mass``
+  draw from and integrate the priors the device evaluates;
 * ``chain_autocorr_device`` / ``Convergence`` -- the integrated autocorrelation time of every parameter of a chain that lives on the
   device (pooled over the walkers, Sokal's window), and the stopping rule built on it: ``converge=`` makes ``nsteps`` of the three
   device run drivers a maximum.  ``chain_autocorr``, ``chain_mean`` and ``sokal_window`` state the estimate in numpy;
@@ -264,7 +269,7 @@ def run_stretch_move_philox(log_prob_batch: Callable[[np.ndarray], np.ndarray], 
 
 
 class _DeviceMove:
-    """What StretchMove, EnsembleMoves and TemperedMove share: the library, the device's context with its lock, the spec struct, the
+    """What StretchMove, EnsembleMoves, TemperedMove and NestedMove share: the library, the device's context with its lock, the spec struct, the
     entry points (lookup(lib, name), kept as self._<key>), the check of a tensor argument and the call of an entry point."""
 
     def __init__(self, lookup, spec, device, **entries):
@@ -334,16 +339,18 @@ class StretchMove(_DeviceMove):
 
 
 def _run_chunks(fitter: Fitter, param_defs, priors, who, pos0_text, ndim, proposals, nsteps, thin, chunk, progress, converge, nburn, record,
-                cold, entry, move, begin):
-    """The chunk driver behind run_stretch_move_device, run_moves_device and run_tempered_device.  The caller has checked pos0
+                cold, entry, move, begin, stop=None):
+    """The chunk driver behind run_stretch_move_device, run_moves_device, run_tempered_device and run_nested_device.  The caller has checked pos0
     (pos0_text: what it says of a pos0 of another ndim than the fit's) and made `move`, the struct the run entry `entry(lib)` takes
     behind the request.  begin(lib, h, lock, dev, spec, rows) allocates and returns (state, counts, chains): the tensors of the
     current state, positions first, evaluated and found finite; the count tensors; the tensors of `rows` stored rows, the chain
     first -- each list in the order of the run entry's arguments.  cold(chain): the view [rows, W, D] the convergence monitor reads;
     proposals: those of one likelihood call, for the plan's warnings.  ``progress(step, *state)`` gets numpy copies once per chunk.
 
-    Returns (chains, counts, ran, rec) as numpy arrays: the rows of the `ran` steps run, the counts, and the ConvergedAutocorr
-    record -- None for a plain run (converge=None and no `record`), which runs all its steps."""
+    stop(state, chains, ran), if given, is asked after every chunk and ends the run where it returns True (nested sampling's dlogz).
+
+    Returns (chains, counts, ran, rec, state) as numpy arrays: the rows of the `ran` steps run, the counts, the ConvergedAutocorr
+    record -- None for a plain run (converge=None and no `record`), which runs all its steps -- and the state the run left."""
     import ctypes as C
     import torch
     from . import _lib
@@ -373,7 +380,7 @@ def _run_chunks(fitter: Fitter, param_defs, priors, who, pos0_text, ndim, propos
         if progress is not None:
             progress(step0 + n - 1, *[t.cpu().numpy() for t in state])
         step0 += n
-        if monitor.stop(chains[0], step0):
+        if monitor.stop(chains[0], step0) or (stop is not None and stop(state, chains, step0)):
             break
     plan = _lib.Plan()
     with lock:
@@ -383,7 +390,7 @@ def _run_chunks(fitter: Fitter, param_defs, priors, who, pos0_text, ndim, propos
     plain = converge is None and not record
     kept = step0 // thin  # (step0: the steps run; a plain run has run nsteps)
     return ([c[:kept].cpu().numpy() for c in chains], [t.cpu().numpy() for t in counts], step0,
-            None if plain else monitor.record(chains[0], step0))
+            None if plain else monitor.record(chains[0], step0), [t.cpu().numpy() for t in state])
 
 
 def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, chunk, progress, who, entry, make_move, converge=None,
@@ -418,7 +425,7 @@ def _run_halves_device(fitter: Fitter, param_defs, pos0, nsteps, thin, priors, c
             raise ValueError("initial positions must have finite log-probability")
         return [pos, lp], [accepted], [chain, logp]
     lookup = _lib.stretch_entry if entry == "vag_stretch_run_dev" else _lib.move_entry
-    (chain, logp), (accepted,), ran, rec = _run_chunks(fitter, param_defs, priors, who, "pos0 must be [nwalkers, ndim]", ndim, nw // 2, nsteps,
+    (chain, logp), (accepted,), ran, rec, _ = _run_chunks(fitter, param_defs, priors, who, "pos0 must be [nwalkers, ndim]", ndim, nw // 2, nsteps,
                                                        thin, chunk, progress, converge, nburn, _record, lambda kept: kept,
                                                        lambda lib: lookup(lib, entry), move, begin)
     out = (chain, logp, accepted / max(ran, 1))
@@ -1046,13 +1053,449 @@ def run_tempered_device(fitter: Fitter, param_defs: Sequence[ParamDef], pos0: np
         if not bool((torch.isfinite(lnl) & torch.isfinite(lnprior)).all()):
             raise ValueError("initial positions must have finite ln L and ln prior")
         return [pos, lnl, lnprior], [accepted, swapped], chains
-    chains, (accepted, swapped), ran, rec = _run_chunks(
+    chains, (accepted, swapped), ran, rec, _ = _run_chunks(
         fitter, param_defs, priors, "run_tempered_device", "pos0 must be [ntemps, nwalkers, ndim]", ndim, ntemps * nw // 2, nsteps, thin,
         chunk, progress, converge, nburn, _record, lambda kept: kept[:, 0],
         lambda lib: _lib.tempered_entry(lib, "vag_tempered_run_dev"), tempered, begin)
     swap_fraction = swapped[:ntemps - 1].sum(axis=1) / np.maximum(swap_attempts(ntemps, 0, ran) * nw, 1)
     out = (*chains, accepted / max(ran, 1), swap_fraction)
     return out if rec is None else out + (rec,)
+
+
+# ---- nested sampling (INTEGRATION.md "Nested sampling"): N live points; an iteration retires the K = N / 2 of lowest ln L and replaces
+#      each by a clone of a survivor that walks `walk` constrained DE steps against the survivors; the evidence from the stored ln L.
+#      The numpy statement first, then the device. ----
+
+NESTED_MAX_LIVE = 16384  # VAG_NESTED_MAX_LIVE
+_NESTED_STREAM_CLONE = 5  # vag::NESTED_STREAM_CLONE
+
+NestedRun = namedtuple("NestedRun", "dead_theta dead_lnl dead_lnprior live lnl lnprior accepted niter ncall")
+NestedRun.__doc__ = """What run_nested_philox and run_nested_device return: the dead record dead_theta[niter, K, ndim], dead_lnl[niter, K],
+dead_lnprior[niter, K] (row = iteration, in rank order: flattened it is non-decreasing in ln L), the final live points live[N, ndim]
+with lnl[N] and lnprior[N], accepted[niter] (the taken proposals of each iteration, of K walk), the iterations run and the likelihood
+evaluations N + niter K walk."""
+
+NestedEvidence = namedtuple("NestedEvidence", "ln_z ln_z_err information log_weights")
+NestedEvidence.__doc__ = """What nested_evidence returns: ln Z, its error sqrt(H / N), the information H, and the normalised log weights
+of the flattened dead points followed by the final live points (their exponentials sum to 1)."""
+
+
+def nested_default_walk(ndim: int) -> int:
+    """The default walk length: max(20, 5 ndim) -- a short walk is visibly biased, and the bias grows with the dimension."""
+    return max(20, 5 * int(ndim))
+
+
+def _check_nested(n_live, ndim, walk, gamma0=None, sigma=DE_SIGMA):
+    """The refusals of vag_nested_spec on the Python side; returns gamma0 with None resolved."""
+    if n_live % 2 or not 4 <= n_live <= NESTED_MAX_LIVE:
+        raise ValueError(f"need an even number of live points, 4..{NESTED_MAX_LIVE}")
+    if not 1 <= ndim <= 16:
+        raise ValueError("nested sampling takes 1..16 dimensions")
+    if int(walk) != walk or walk < 1:
+        raise ValueError("walk must be a whole number >= 1")
+    gamma0 = de_gamma0(ndim) if gamma0 is None else float(gamma0)
+    if not (np.isfinite(gamma0) and gamma0 > 0.0):
+        raise ValueError("gamma0 must be finite and > 0 (None: 2.38 / sqrt(2 ndim))")
+    if not np.isfinite(sigma):
+        raise ValueError("sigma must be finite")
+    return gamma0
+
+
+def nested_tick(it: int, walk: int, m: int) -> int:
+    """vag::nested_tick: the tick of draw m of iteration `it`, it (walk + 1) + m; m = 0 the clone draw, m = 1 .. walk the walk steps."""
+    return int(it) * (int(walk) + 1) + int(m)
+
+
+def _nested_words(k, tick, seed, stream):
+    """The four Philox words of the ranks r = 0 .. k - 1 at `tick`: counter (r, tick lo, tick hi, stream)."""
+    return _stretch_words(2 * k, tick, 0, seed, stream)
+
+
+def nested_order(lnl):
+    """(order[N], lstar): order[r] the live slot of rank r, slot i before slot j iff (lnl[i], i) < (lnl[j], j), so ties go to the lower
+    slot; the dead are ranks 0 .. K - 1, the survivors ranks K .. N - 1, and lstar = lnl[order[K - 1]].  What vag_nested_rank_dev writes."""
+    lnl = np.asarray(lnl, dtype=np.float64)
+    order = np.lexsort((np.arange(lnl.size), lnl))
+    return order, float(lnl[order[lnl.size // 2 - 1]])
+
+
+def nested_clones(order, it, walk, seed):
+    """The slot each dead rank r = 0 .. K - 1 is overwritten from at iteration `it`: survivor order[K + j0], j0 = floor(u K) with u the
+    uniform of the first two words of stream 5 at tick (it, 0).  What vag_nested_retire_dev copies."""
+    order = np.asarray(order)
+    k = order.size // 2
+    x = _nested_words(k, nested_tick(it, walk, 0), seed, _NESTED_STREAM_CLONE)
+    j0 = np.minimum((_u53(x[:, 0], x[:, 1]) * float(k)).astype(np.int64), k - 1)
+    return order[k + j0]
+
+
+def nested_proposals(live, order, it, m, walk, seed, gamma0=None, sigma=DE_SIGMA):
+    """The proposals of walk step m = 1 .. walk of iteration `it`, after the retirement: (prop[K, ndim], partners[K, 2], slack[K]).
+    Clone r (slot order[r]) draws survivors s1 != s2 = order[K + a], order[K + b] with (a, b) the pair of words 2 and 3 of stream 0
+    over the K survivors (partners: their slots) and the quantised normal of de_normal (u1 from words 0, 1 of stream 0, u2 from words
+    0, 1 of stream 4); gamma = gamma0 fma(sigma, n_q, 1) and prop = fma(gamma, live[s1] - live[s2], live[order[r]]).  Bit for bit what
+    vag_nested_propose_dev computes wherever the slack is far above the rounding of log and cos."""
+    from .fitting import _fma
+    live, order = np.asarray(live, dtype=np.float64), np.asarray(order)
+    n, ndim = live.shape
+    k = n // 2
+    gamma0 = de_gamma0(ndim) if gamma0 is None else float(gamma0)
+    tick = nested_tick(it, walk, m)
+    x, v = _nested_words(k, tick, seed, 0), _nested_words(k, tick, seed, 4)
+    a, b = _move_pair(x[:, 2], x[:, 3], k)
+    s1, s2 = order[k + a], order[k + b]
+    n_q, slack = de_normal(_u53(x[:, 0], x[:, 1]), _u53(v[:, 0], v[:, 1]))
+    gamma = gamma0 * _fma(sigma, n_q, 1.0)
+    return _fma(gamma[:, None], live[s1] - live[s2], live[order[:k]]), np.stack([s1, s2], axis=1), slack
+
+
+def nested_margin(lnl_new, lnprior_new, lnprior_old, lstar, log_u):
+    """vag::nested_margin in numpy: -inf where ln L' or ln prior' is not finite or ln L' is not strictly above lstar, whatever the
+    draw; otherwise (lnprior_new - lnprior_old) - log_u.  A proposal is taken iff its margin is > 0."""
+    lnl_new, lnprior_new, lnprior_old, log_u = (np.asarray(v, dtype=np.float64) for v in (lnl_new, lnprior_new, lnprior_old, log_u))
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(lnl_new) & np.isfinite(lnprior_new) & (lnl_new > lstar)
+        return np.where(ok, (np.where(ok, lnprior_new, 0.0) - lnprior_old) - log_u, -np.inf)
+
+
+def nested_accepts(it, m, walk, seed, lnl_new, lnprior_new, lnprior_old, lstar):
+    """The decisions of walk step m of iteration `it`: (take[K], margin[K]), u_a from the first two words of stream 1 at tick (it, m)
+    (u_a = 0: log = -inf, taken).  lnprior_old[K]: the clones' ln prior in rank order.  What vag_nested_accept_dev decides."""
+    lnl_new = np.asarray(lnl_new, dtype=np.float64)
+    y = _nested_words(lnl_new.size, nested_tick(it, walk, m), seed, 1)
+    with np.errstate(divide="ignore"):
+        margin = nested_margin(lnl_new, lnprior_new, lnprior_old, lstar, np.log(_u53(y[:, 0], y[:, 1])))
+    return margin > 0, margin
+
+
+def nested_live_count(j, n_live):
+    """vag::nested_live_count: the live count when dead point j (flattened index) leaves, N - (j mod K)."""
+    return int(n_live) - np.asarray(j, dtype=np.int64) % (int(n_live) // 2)
+
+
+def _nested_dead_terms(dead_lnl, n_live):
+    """(ln w of the flattened dead points, ln X after the last of them): n_j = N - (j mod K), ln X_j = -sum_{i <= j} 1 / n_i with
+    X_-1 = 1, ln w_j = lnl_j + ln X_{j-1} + ln(-expm1(-1 / n_j))."""
+    lnl = np.asarray(dead_lnl, dtype=np.float64).ravel()
+    shrink = 1.0 / nested_live_count(np.arange(lnl.size), n_live).astype(np.float64)
+    ln_x = -np.cumsum(shrink)
+    before = np.concatenate([[0.0], ln_x[:-1]])
+    return lnl + before + np.log(-np.expm1(-shrink)), float(ln_x[-1]) if lnl.size else 0.0
+
+
+def _logsumexp(x):
+    top = np.max(x)
+    return float(top + np.log(np.sum(np.exp(x - top))))
+
+
+def nested_evidence(dead_lnl, live_lnl) -> NestedEvidence:
+    """The evidence of a run from its stored ln L: dead_lnl[niter, K] (or flattened) and the N final live points' live_lnl[N].  Dead
+    point j left n_j = N - (j mod K) live points: ln X_j = -sum_{i <= j} 1 / n_i, ln w_j = lnl_j + ln X_{j-1} + ln(1 - exp(-1 / n_j));
+    each final live point gets lnl + ln X_last - ln N.  ln Z = logsumexp of all, H = sum p lnl - ln Z with p the normalised weights,
+    and the error is sqrt(H / N) (Skilling 2006).  Returns NestedEvidence(ln_z, ln_z_err, information, log_weights)."""
+    live_lnl = np.asarray(live_lnl, dtype=np.float64).ravel()
+    n = live_lnl.size
+    if n < 4 or n % 2:
+        raise ValueError("live_lnl must hold the N final live points, N even and >= 4")
+    dead = np.asarray(dead_lnl, dtype=np.float64).ravel()
+    if dead.size % (n // 2):
+        raise ValueError("dead_lnl must hold whole iterations of N / 2 points")
+    ln_w_dead, ln_x_last = _nested_dead_terms(dead, n)
+    ln_w = np.concatenate([ln_w_dead, live_lnl + ln_x_last - np.log(n)])
+    ln_z = _logsumexp(ln_w)
+    log_weights = ln_w - ln_z
+    information = float(np.sum(np.exp(log_weights) * np.concatenate([dead, live_lnl])) - ln_z)
+    return NestedEvidence(ln_z, math.sqrt(max(information, 0.0) / n), information, log_weights)
+
+
+def nested_remaining(dead_lnl, live_lnl) -> float:
+    """The termination measure after the iterations of dead_lnl: logaddexp(ln Z_dead, max(live lnl) + ln X_last) - ln Z_dead, an upper
+    bound on what the live points can still add to ln Z.  A run under ``dlogz`` stops at the first chunk end where it is < dlogz."""
+    live_lnl = np.asarray(live_lnl, dtype=np.float64).ravel()
+    ln_w_dead, ln_x_last = _nested_dead_terms(dead_lnl, live_lnl.size)
+    if not ln_w_dead.size:
+        return math.inf
+    ln_z_dead = _logsumexp(ln_w_dead)
+    return float(np.logaddexp(ln_z_dead, live_lnl.max() + ln_x_last) - ln_z_dead)
+
+
+def nested_equal_samples(log_weights, seed: int = 0, n: Optional[int] = None) -> np.ndarray:
+    """Indices of n equally weighted draws (default: as many as there are weights) from the normalised log weights, by systematic
+    resampling: the positions (u + i) / n, one uniform u from numpy's generator seeded by `seed`, through the cumulative weights."""
+    p = np.exp(np.asarray(log_weights, dtype=np.float64))
+    n = p.size if n is None else int(n)
+    cum = np.cumsum(p)
+    positions = (np.random.default_rng(seed).random() + np.arange(n)) / n * cum[-1]
+    return np.minimum(np.searchsorted(cum, positions, side="right"), p.size - 1)
+
+
+def _nested_stop(dlogz, niter, chunk):
+    if chunk < 1 or niter < 0:
+        raise ValueError("chunk must be >= 1 and niter >= 0")
+    if dlogz is not None and not (np.isfinite(dlogz) and dlogz > 0.0):
+        raise ValueError("dlogz must be finite and > 0, or None")
+
+
+def run_nested_philox(log_like_batch: Callable[[np.ndarray], np.ndarray], log_prior_batch: Callable[[np.ndarray], np.ndarray],
+                      live0: np.ndarray, niter: int, walk: int, seed: int = 0, it0: int = 0, margins: Optional[list] = None,
+                      gamma0: Optional[float] = None, sigma: float = DE_SIGMA, dlogz: Optional[float] = None, chunk: int = 4,
+                      slacks: Optional[list] = None) -> NestedRun:
+    """Nested sampling through any two host callables (ln L and ln prior of rows [n, ndim]): the run of the device's nested sampler.
+    live0[N, ndim], N even; iterations it0 .. it0 + niter - 1.  An iteration ranks the live points (nested_order), stores the K = N / 2
+    of lowest ln L as its row of the dead record, overwrites each by a copy of a survivor (nested_clones), and runs `walk` steps on the K
+    clones at once: the proposals of nested_proposals in rank order in one call of each callable, the decisions of nested_accepts
+    against L* of the iteration.  The survivors do not move during an iteration.  The draws are a function of (seed, it, m, rank), so
+    a continuation (it0 = the iterations run, live0 = the live points they left) repeats a single run to the bit.
+
+    With ``dlogz`` niter is a maximum: after every `chunk` iterations the run stops if nested_remaining(dead so far of this call, live)
+    < dlogz.  Returns a NestedRun.  ``margins`` receives every walk step's margin array, ``slacks`` its slack array (de_normal)."""
+    live = np.array(live0, dtype=np.float64, copy=True)
+    if live.ndim != 2:
+        raise ValueError("live0 must be [n_live, ndim]")
+    n, ndim = live.shape
+    gamma0 = _check_nested(n, ndim, walk, gamma0, sigma)
+    _nested_stop(dlogz, niter, chunk)
+    lnl = np.asarray(log_like_batch(live), dtype=np.float64).copy()
+    lnprior = np.asarray(log_prior_batch(live), dtype=np.float64).copy()
+    if not (np.all(np.isfinite(lnl)) and np.all(np.isfinite(lnprior))):
+        raise ValueError("live points must have finite ln L and ln prior")
+    k = n // 2
+    dead_theta, dead_lnl, dead_lnprior = np.empty((niter, k, ndim)), np.empty((niter, k)), np.empty((niter, k))
+    accepted = np.zeros(niter, dtype=np.int64)
+    ran = 0
+    for row in range(niter):
+        it = it0 + row
+        order, lstar = nested_order(lnl)
+        dead, source = order[:k], nested_clones(order, it, walk, seed)
+        dead_theta[row], dead_lnl[row], dead_lnprior[row] = live[dead], lnl[dead], lnprior[dead]
+        live[dead], lnl[dead], lnprior[dead] = live[source], lnl[source], lnprior[source]
+        for m in range(1, walk + 1):
+            prop, _, slack = nested_proposals(live, order, it, m, walk, seed, gamma0, sigma)
+            lnl_new = np.asarray(log_like_batch(prop), dtype=np.float64)
+            lnprior_new = np.asarray(log_prior_batch(prop), dtype=np.float64)
+            take, margin = nested_accepts(it, m, walk, seed, lnl_new, lnprior_new, lnprior[dead], lstar)
+            if margins is not None:
+                margins.append(margin)
+            if slacks is not None:
+                slacks.append(slack)
+            live[dead[take]], lnl[dead[take]], lnprior[dead[take]] = prop[take], lnl_new[take], lnprior_new[take]
+            accepted[row] += int(take.sum())
+        ran = row + 1
+        if dlogz is not None and (ran % chunk == 0 or ran == niter) and nested_remaining(dead_lnl[:ran], lnl) < dlogz:
+            break
+    return NestedRun(dead_theta[:ran], dead_lnl[:ran], dead_lnprior[:ran], live, lnl, lnprior, accepted[:ran], ran, n + ran * k * walk)
+
+
+def _norm_cdf(x):
+    """The standard normal CDF, 0.5 erfc(-x / sqrt 2), elementwise."""
+    return 0.5 * np.vectorize(math.erfc, otypes=[np.float64])(-np.asarray(x, dtype=np.float64) / math.sqrt(2.0))
+
+
+def _norm_ppf(p):
+    """The inverse of _norm_cdf for p in (0, 1): Acklam's rational approximation (relative error 1.2e-9) and one step of Halley's
+    method on the erfc form, which leaves the rounding of erfc."""
+    p = np.asarray(p, dtype=np.float64)
+    a = (-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02, 1.383577518672690e+02, -3.066479806614716e+01,
+         2.506628277459239e+00)
+    b = (-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01, -1.328068155288572e+01)
+    c = (-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00, -2.549732539343734e+00, 4.374664141464968e+00,
+         2.938163982698783e+00)
+    d = (7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00)
+    with np.errstate(all="ignore"):
+        q = p - 0.5
+        r = q * q
+        mid = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q / \
+              (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0)
+        t = np.sqrt(-2.0 * np.log(np.minimum(p, 1.0 - p)))
+        tail = (((((c[0] * t + c[1]) * t + c[2]) * t + c[3]) * t + c[4]) * t + c[5]) / ((((d[0] * t + d[1]) * t + d[2]) * t + d[3]) * t + 1.0)
+        x = np.where(np.abs(q) <= 0.47575, mid, np.where(q < 0, tail, -tail))
+        e = _norm_cdf(x) - p
+        u = e * math.sqrt(2.0 * math.pi) * np.exp(0.5 * x * x)
+        x = x - u / (1.0 + 0.5 * x * u)
+    return x
+
+
+def _prior_ranges(lower, upper, prior_specs, who):
+    """Per dimension (kind, a, b, lo, hi): the prior the device evaluates and the part [lo, hi] of the box where it is not zero."""
+    from . import _lib
+    lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    if lower.shape != upper.shape or lower.ndim != 1 or len(prior_specs) != lower.size:
+        raise ValueError("lower, upper and prior_specs must hold one entry per dimension")
+    host = [d for d, spec in enumerate(prior_specs) if spec[0] == _lib.PRIOR_NONE]
+    if host:
+        raise ValueError(f"{who}: only Uniform / Gaussian / LogUniform priors (or their tuple forms) run on the device; "
+                         f"got host-only priors for dimensions {host}")
+    out = []
+    for d, (kind, a, b, *_) in enumerate(prior_specs):
+        lo, hi = float(lower[d]), float(upper[d])
+        if kind in (_lib.PRIOR_UNIFORM_RANGE, _lib.PRIOR_LOG_UNIFORM):
+            lo, hi = max(lo, float(a)), min(hi, float(b))
+        if kind == _lib.PRIOR_LOG_UNIFORM and not a > 0.0:
+            raise ValueError(f"{who}: a LogUniform prior needs a minimum > 0 (dimension {d})")
+        if kind == _lib.PRIOR_GAUSSIAN and not b > 0.0:
+            raise ValueError(f"{who}: a Gaussian prior needs sigma > 0 (dimension {d})")
+        if not lo < hi:
+            raise ValueError(f"{who}: the prior of dimension {d} has no support inside the bounds")
+        out.append((kind, float(a), float(b), lo, hi))
+    return out
+
+
+def sample_prior(lower, upper, prior_specs, n: int, rng: np.random.Generator) -> np.ndarray:
+    """n draws [n, ndim] from the priors the device evaluates, within the bounds: prior_specs[d] = (kind, a, b, ...) as Fitter.build_spec
+    leaves them in ``fitter._prior_specs``.  Uniform: uniform over [lower, upper]; Uniform with its own range: over the part of it
+    inside the bounds; Gaussian(a, b): truncated to the bounds, by the inverse CDF; LogUniform(a, b): uniform in ln x over the part of
+    [a, b] inside the bounds.  Host-only priors are refused."""
+    from . import _lib
+    ranges = _prior_ranges(lower, upper, prior_specs, "sample_prior")
+    out = np.empty((int(n), len(ranges)))
+    for d, (kind, a, b, lo, hi) in enumerate(ranges):
+        u = rng.random(int(n))
+        if kind == _lib.PRIOR_GAUSSIAN:
+            p_lo, p_hi = _norm_cdf((lo - a) / b), _norm_cdf((hi - a) / b)
+            if not p_hi > p_lo:
+                raise ValueError(f"sample_prior: the Gaussian prior of dimension {d} has no mass inside the bounds in double precision")
+            x = a + b * _norm_ppf(p_lo + (p_hi - p_lo) * u)
+        elif kind == _lib.PRIOR_LOG_UNIFORM:
+            x = lo * np.exp(u * math.log(hi / lo))
+        else:
+            x = lo + (hi - lo) * u
+        out[:, d] = np.clip(x, lo, hi)
+    return out
+
+
+def prior_mass(lower, upper, prior_specs) -> float:
+    """The mass of the prior density, as the device evaluates it, inside the bounds: the product over the dimensions of 1 (Uniform:
+    the density is 1 / (upper - lower)), the covered fraction of its own range (Uniform(a, b)), Phi((upper - a) / b) - Phi((lower - a) / b)
+    (Gaussian(a, b)), ln(hi / lo) / ln(b / a) over the covered part [lo, hi] of [a, b] (LogUniform).  An evidence formed with these
+    priors is relative to this mass."""
+    from . import _lib
+    mass = 1.0
+    for kind, a, b, lo, hi in _prior_ranges(lower, upper, prior_specs, "prior_mass"):
+        if kind == _lib.PRIOR_UNIFORM_RANGE:
+            mass *= (hi - lo) / (b - a)
+        elif kind == _lib.PRIOR_GAUSSIAN:
+            mass *= float(_norm_cdf((hi - a) / b) - _norm_cdf((lo - a) / b))
+        elif kind == _lib.PRIOR_LOG_UNIFORM:
+            mass *= math.log(hi / lo) / math.log(b / a)
+    return mass
+
+
+def _nested_spec(n_live, ndim, walk, seed, gamma0, sigma):
+    from . import _lib
+    return _lib.NestedSpec(int(seed) & (2 ** 64 - 1), int(n_live), int(ndim), int(walk), 0, float(gamma0), float(sigma))
+
+
+class NestedMove(_DeviceMove):
+    """The building blocks of a nested iteration on the device (vag_nested_rank_dev / _retire_dev / _propose_dev / _accept_dev), on
+    float64 torch tensors and torch's current stream, like StretchMove; they need no model::
+
+        move = NestedMove(n, ndim, walk, seed=7)
+        for it in range(niter):
+            order, lstar = move.rank(lnl)                                          # int32[n], float64[1]
+            move.retire(it, order, live, lnl, lnprior, dead_theta[it], dead_lnl[it], dead_lnprior[it])   # rows [n / 2, ...]
+            for m in range(1, walk + 1):
+                prop = move.propose(it, m, order, live)                            # [n / 2, ndim], in rank order
+                lnl_new, lnprior_new = evaluate(prop)                              # any float64[n / 2] pair on the device
+                move.accept(it, m, order, lstar, prop, lnl_new, lnprior_new, live, lnl, lnprior, accepted[it])   # int64[n / 2]
+
+    The run is the one sampling.run_nested_philox makes from the same ln L and ln prior."""
+
+    def __init__(self, n_live: int, ndim: int, walk: int, seed: int = 0, gamma0: Optional[float] = None, sigma: float = DE_SIGMA,
+                 device: int = 0):
+        gamma0 = _check_nested(n_live, ndim, walk, gamma0, sigma)
+        from . import _lib
+        self.n_live, self.ndim, self.walk = int(n_live), int(ndim), int(walk)
+        super().__init__(_lib.nested_entry, _nested_spec(n_live, ndim, walk, seed, gamma0, sigma), device, rank="vag_nested_rank_dev",
+                         retire="vag_nested_retire_dev", propose="vag_nested_propose_dev", accept="vag_nested_accept_dev")
+
+    def _live(self, order, live=None, lnl=None, lnprior=None):
+        import torch
+        n = self.n_live
+        for t, shape, dtype, what in ((order, (n,), torch.int32, "order"), (live, (n, self.ndim), torch.float64, "live"),
+                                      (lnl, (n,), torch.float64, "lnl"), (lnprior, (n,), torch.float64, "lnprior")):
+            if t is not None:
+                self._checked(t, shape, dtype, what)
+
+    def rank(self, lnl):
+        import torch
+        self._live(None, lnl=lnl)
+        order = torch.empty((self.n_live,), dtype=torch.int32, device=self._dev)
+        lstar = torch.empty((1,), dtype=torch.float64, device=self._dev)
+        self._call(self._rank, lnl, order, lstar)
+        return order, lstar
+
+    def retire(self, it: int, order, live, lnl, lnprior, dead_theta, dead_lnl, dead_lnprior):
+        import torch
+        k = self.n_live // 2
+        self._live(order, live, lnl, lnprior)
+        self._checked(dead_theta, (k, self.ndim), torch.float64, "dead_theta")
+        self._checked(dead_lnl, (k,), torch.float64, "dead_lnl")
+        self._checked(dead_lnprior, (k,), torch.float64, "dead_lnprior")
+        self._call(self._retire, it, order, live, lnl, lnprior, dead_theta, dead_lnl, dead_lnprior)
+
+    def propose(self, it: int, m: int, order, live):
+        import torch
+        self._live(order, live)
+        prop = torch.empty((self.n_live // 2, self.ndim), dtype=torch.float64, device=self._dev)
+        self._call(self._propose, it, m, order, live, prop)
+        return prop
+
+    def accept(self, it: int, m: int, order, lstar, prop, lnl_new, lnprior_new, live, lnl, lnprior, accepted):
+        import torch
+        k = self.n_live // 2
+        self._live(order, live, lnl, lnprior)
+        self._checked(lstar, (1,), torch.float64, "lstar")
+        self._checked(prop, (k, self.ndim), torch.float64, "prop")
+        self._checked(lnl_new, (k,), torch.float64, "lnl_new")
+        self._checked(lnprior_new, (k,), torch.float64, "lnprior_new")
+        self._checked(accepted, (k,), torch.int64, "accepted")
+        self._call(self._accept, it, m, order, lstar, prop, lnl_new, lnprior_new, live, lnl, lnprior, accepted)
+
+
+def run_nested_device(fitter: Fitter, param_defs: Sequence[ParamDef], live0: np.ndarray, niter: int, walk: Optional[int] = None,
+                      seed: int = 0, dlogz: Optional[float] = None, priors=None, chunk: int = 4, progress: Optional[Callable] = None,
+                      gamma0: Optional[float] = None, sigma: float = DE_SIGMA) -> NestedRun:
+    """run_nested_philox with everything on the device: the spec is built once, and every `chunk` iterations are ONE call
+    (vag_nested_run_dev) that scans and uploads the spec blocks once and then only launches.  Per walk step the N / 2 proposals go
+    through one likelihood call; the live points, the dead record and the counts stay in HBM.  ln L is the fitter's, ln prior the sum
+    of the priors with the bounds mask (Fitter.log_like_and_prior_batch); only priors that run on the device are accepted.  The default
+    ``walk`` is max(20, 5 ndim).
+
+    With ``dlogz`` set, niter is a maximum and the rule (nested_remaining < dlogz) is tested at chunk ends, where ln L of the chunk's
+    dead points and of the live points come to the host.  The arrays of a run are those of a plain run of the same number of
+    iterations, to the bit, whatever the chunk.  ``progress(it, live, lnl, lnprior)`` is called once per chunk with the last iteration
+    of the chunk; the context's lock is free between chunks.  Returns a NestedRun as numpy arrays."""
+    from . import _lib
+    live0 = np.ascontiguousarray(live0, dtype=np.float64)
+    if live0.ndim != 2:
+        raise ValueError("live0 must be [n_live, ndim]")
+    n, ndim = live0.shape
+    walk = nested_default_walk(ndim) if walk is None else walk
+    gamma0 = _check_nested(n, ndim, walk, gamma0, sigma)
+    _nested_stop(dlogz, niter, chunk)
+    if not np.all(np.isfinite(live0)):
+        raise ValueError("live points must be finite")
+    k = n // 2
+    nested = _nested_spec(n, ndim, walk, seed, gamma0, sigma)
+
+    def begin(lib, h, lock, dev, spec, rows):
+        import torch
+        live = torch.from_numpy(live0).to(dev)
+        lnl = torch.empty((n,), dtype=torch.float64, device=dev)
+        lnprior = torch.empty((n,), dtype=torch.float64, device=dev)
+        loglike_split_device(fitter, spec, live, lnl, lnprior)
+        if not bool((torch.isfinite(lnl) & torch.isfinite(lnprior)).all()):
+            raise ValueError("live points must have finite ln L and ln prior")
+        accepted = torch.zeros((rows, k), dtype=torch.int64, device=dev)
+        dead = [torch.empty((rows, k) + tail, dtype=torch.float64, device=dev) for tail in ((ndim,), (), ())]
+        return [live, lnl, lnprior], [], [accepted] + dead
+
+    def stop(state, chains, ran):
+        return dlogz is not None and nested_remaining(chains[2][:ran].cpu().numpy(), state[1].cpu().numpy()) < dlogz
+    (accepted, dead_theta, dead_lnl, dead_lnprior), _, ran, _, (live, lnl, lnprior) = _run_chunks(
+        fitter, param_defs, priors, "run_nested_device", "live0 must be [n_live, ndim]", ndim, k, niter, 1, chunk, progress, None, 0, False,
+        lambda kept: kept, lambda lib: _lib.nested_entry(lib, "vag_nested_run_dev"), nested, begin, stop=stop)
+    return NestedRun(dead_theta, dead_lnl, dead_lnprior, live, lnl, lnprior, accepted.sum(axis=1), ran, n + ran * k * walk)
 
 
 # ---- chain autocorrelation (INTEGRATION.md "Chain autocorrelation"): the integrated autocorrelation time of every parameter, pooled over
@@ -1383,9 +1826,44 @@ class _ConvergenceMonitor:
         return ConvergedAutocorr(*self.last, self.converged, int(step), np.array(self.history).reshape(len(self.history), ndim), self.thin)
 
 
+def _fit_nested(fitter, param_defs, n_live, niter, seed, rng, dlogz, walk, priors):
+    """fit(sampler="nested"): the live points from the priors, the run, the evidence."""
+    spec, lower, upper = fitter.build_spec(param_defs, priors=priors, use_priors=True)
+    ndim = int(spec.ndim)
+    walk = nested_default_walk(ndim) if walk is None else walk
+    _check_nested(n_live, ndim, walk)
+    _nested_stop(dlogz, niter, 1)
+    fitter._refuse_host_priors(param_defs, "fit(sampler='nested')")
+    prior_specs = list(fitter._prior_specs)
+    log_mass = math.log(prior_mass(lower, upper, prior_specs))
+    kept, tried, finite = [], 0, 0
+    while sum(len(x) for x in kept) < n_live:
+        if tried >= 64 * n_live:
+            raise ValueError(f"fit(sampler='nested'): {finite} of {tried} prior draws have a finite ln L; no {n_live} live points")
+        x = sample_prior(lower, upper, prior_specs, n_live, rng)
+        lnl, lnprior = fitter.log_like_and_prior_batch(x, param_defs, priors=priors)
+        ok = np.isfinite(lnl) & np.isfinite(lnprior)
+        kept.append(x[ok])
+        tried, finite = tried + n_live, finite + int(ok.sum())
+    live0 = np.concatenate(kept)[:n_live]
+    fraction = finite / tried
+    run = run_nested_device(fitter, param_defs, live0, niter, walk=walk, seed=seed, dlogz=dlogz, priors=priors)
+    ev = nested_evidence(run.dead_lnl, run.lnl)
+    samples = np.concatenate([run.dead_theta.reshape(-1, ndim), run.live])
+    log_like = np.concatenate([run.dead_lnl.ravel(), run.lnl])
+    log_prior = np.concatenate([run.dead_lnprior.ravel(), run.lnprior])
+    fraction_err = math.sqrt((1.0 - fraction) / (fraction * tried))  # of ln prior_fraction: the binomial error of the share
+    return {"samples": samples, "log_like": log_like, "log_prior": log_prior, "log_weights": ev.log_weights,
+            "equal_samples": samples[nested_equal_samples(ev.log_weights, seed)], "best": samples[np.argmax(log_like + log_prior)],
+            "log_evidence": ev.ln_z + math.log(fraction), "log_evidence_error": math.hypot(ev.ln_z_err, fraction_err),
+            "information": ev.information, "prior_fraction": fraction, "log_prior_mass": log_mass, "niter": run.niter,
+            "ncall": tried + run.niter * (n_live // 2) * walk, "acceptance": run.accepted / float((n_live // 2) * walk)}
+
+
 def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: int, nburn: int = 0, seed: int = 0,
         loglike_fn: Optional[Callable] = None, center: Optional[np.ndarray] = None, spread: float = 0.1, sampler: str = "host",
-        ntemps: int = 8, beta_min: float = 1e-3, prior_rung: bool = True, moves=None, converge: Optional[Convergence] = None):
+        ntemps: int = 8, beta_min: float = 1e-3, prior_rung: bool = True, moves=None, converge: Optional[Convergence] = None,
+        dlogz: float = 0.1, walk: Optional[int] = None, priors=None):
     """Convenience driver: uniform priors over the ParamDef boxes, stretch-move sampling on the device likelihood.
     Returns dict(samples[flat, ndim], log_prob[flat], acceptance, best) in sampler space (log10 for LOG parameters).
     ``sampler="host"``: run_stretch_move in numpy around one device call per half-step; ``"device"``: run_stretch_move_device, the
@@ -1400,11 +1878,31 @@ def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: i
     NaN when fewer than two rows are kept) and "tau_reliable" (a window was found and the kept rows number at least 50 tau, or
     ``converge.tol`` tau): the device samplers from chain_autocorr_device on the chain in HBM ("tempered": the cold rung), the host
     sampler from chain_autocorr.  ``converge=Convergence(...)`` (device samplers only) makes `nsteps` a maximum and stops the run by
-    that rule (run_stretch_move_device); the dict then also holds "converged" and "nsteps", the steps run."""
-    if sampler not in ("host", "device", "tempered"):
-        raise ValueError(f"unknown sampler {sampler!r}: 'host', 'device' or 'tempered'")
+    that rule (run_stretch_move_device); the dict then also holds "converged" and "nsteps", the steps run.
+
+    ``sampler="nested"``: nested sampling on the device (run_nested_device) with `nwalkers` live points, `nsteps` the maximum number
+    of iterations, stopped by ``dlogz`` (nested_remaining), ``walk`` constrained steps per iteration (None: max(20, 5 ndim)) and the
+    priors ``priors`` (as Fitter.log_prob_batch takes them; device-evaluated ones only; None: uniform over the boxes).  The live points
+    are drawn from the priors inside the boxes (sample_prior) in batches through Fitter.log_like_and_prior_batch; the first `nwalkers`
+    with finite ln L are kept and "prior_fraction" is the share of all points tried whose ln L was finite.  The dict holds "samples"
+    (the dead points in the order they were retired, then the final live points) with "log_like", "log_prior" and the normalised
+    "log_weights", "equal_samples" (nested_equal_samples), "best" (the sample of highest ln L + ln prior), "log_evidence",
+    "log_evidence_error", "information", "prior_fraction", "log_prior_mass", "niter", "ncall" (the points tried included) and
+    "acceptance" (per iteration).  "log_evidence" includes ln prior_fraction: the points where the model does not evaluate count as
+    L = 0.  The tempered number excludes it: its beta = 0 rung is the prior restricted to where the model evaluates.  Both are
+    relative to the prior mass inside the boxes, returned here as "log_prior_mass" (prior_mass): the integral of L times the prior
+    density over the boxes is exp(log_evidence + log_prior_mass).  "log_evidence_error" is sqrt(H / N) and the binomial error of
+    ln prior_fraction in quadrature."""
+    if sampler not in ("host", "device", "tempered", "nested"):
+        raise ValueError(f"unknown sampler {sampler!r}: 'host', 'device', 'tempered' or 'nested'")
     if converge is not None and sampler == "host":
         raise ValueError("converge stops a run on the device: sampler='host' runs its fixed nsteps (sampler='device' or 'tempered')")
+    if converge is not None and sampler == "nested":
+        raise ValueError("converge stops a run by its autocorrelation times: sampler='nested' has no chain and stops by dlogz "
+                         "(sampler='device' or 'tempered')")
+    if priors is not None and sampler != "nested":
+        raise ValueError(f"priors shapes the live points and the evidence of sampler='nested'; sampler={sampler!r} samples uniform priors "
+                         "over the boxes (compose the run drivers, which take priors, instead)")
     if converge is not None and not isinstance(converge, Convergence):
         raise ValueError("converge must be a sampling.Convergence or None")
 
@@ -1422,6 +1920,8 @@ def fit(fitter: Fitter, param_defs: Sequence[ParamDef], nwalkers: int, nsteps: i
     if moves is not None:
         move_weights(moves)  # (refused before anything is built)
     rng = np.random.default_rng(seed)
+    if sampler == "nested":
+        return _fit_nested(fitter, param_defs, int(nwalkers), int(nsteps), seed, rng, dlogz, walk, priors)
     if sampler == "tempered":
         betas = geometric_betas(ntemps, beta_min, prior_rung)
         _, lower, upper = fitter.build_spec(param_defs)
