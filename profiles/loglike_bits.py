@@ -1,4 +1,4 @@
-"""ln L of three small seeded fits, written to an .npy, to compare two builds of the engine byte for byte: run it once per build
+"""ln L of four small seeded fits, written to an .npy, to compare two builds of the engine byte for byte: run it once per build
 (VAG_LIB_PATH selects the library) in the same visit and compare the files with --compare.
 
 The fits are those of tests/test_loglike_entry_points.py: (a) the 60 C4 point rows alone; (b) one fitter with a point block, a band
@@ -6,8 +6,10 @@ group, a centroid group, a visibility group, a degree-polarization group with a 
 calibration term, a counts group and a spectral-index group; (c) the same plus a count-spectrum group with a cross-section, a
 template on point rows and two correlated groups (2 and 65 rows): every spec block the likelihood has.  Each is evaluated with 3
 walkers (no ordering) and with 64 (the smallest batch evaluated in cost order), twice: the second call runs in the order the first
-one left.  The array is the twelve results in that order, concatenated (3 x (3 + 3 + 64 + 64) values).  The data of the fits are
-made by model calls of the build under test, so a difference may come from the model requests as well as from the likelihood.
+one left.  (d) the nine fitters of fixture (d) -- (c), (c) plus a second group of one list kind for each of the seven kinds, (c) plus
+all seven -- with 3 walkers, once each.  The array is the twelve results of (a) - (c) in that order, concatenated (3 x (3 + 3 + 64 +
+64) = 402 values), then the nine of (d) (27 values).  The data of the fits are made by model calls of the build under test, so a
+difference may come from the model requests as well as from the likelihood.
 
     VAG_LIB_PATH=a.so python profiles/loglike_bits.py --out a.npy
     VAG_LIB_PATH=b.so python profiles/loglike_bits.py --out b.npy
@@ -32,6 +34,8 @@ def evaluate():
             th = walkers(nb)
             for _ in range(2):
                 out.append(f.loglike_batch(th, d))
+    fits, d = ep.fixture_d()
+    out += [f.loglike_batch(ep.walkers_c(3), d) for f in fits]
     return np.concatenate(out)
 
 

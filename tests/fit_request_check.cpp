@@ -6,7 +6,8 @@
 // the scan computed.  Every input array lives on the heap at exactly its advertised length, so a read one element past it is an
 // AddressSanitizer report.  The four blocks that are hashed in place (fit, sky, pol, vis) are filled into a heap buffer of exactly the
 // scan's size; their hashes are compared across equal and changed content, and every one of their refusals is reached with its text.
-// Then two requests through fit_request_prepare, and one refusal per scan.  One "ok <case>" line per case.
+// Then two requests through fit_request_prepare, one refusal per scan, the block views (*_cols) against offsets worked out by hand
+// with every array read back through them, and the pass list of five requests.  One "ok <case>" line per case.
 #include <cstdio>
 #include <functional>
 #include <initializer_list>
@@ -825,6 +826,307 @@ static void check_refusals(const vag_fit_spec& spec) {
     }
 }
 
+// ---- the block views: every *_cols against offsets worked out by hand from the layout comment, at the smallest shapes where two
+//      columns can be confused, two groups of different shapes per block (with one group every off[g] is 0); then every input array
+//      read back through the view, element for element, from a heap copy of exactly the block's length
+static bool col_is(const double* block, size_t at, const double* src, size_t n) { return std::memcmp(block + at, src, sizeof(double) * n) == 0; }
+static bool icol_is(const double* block, size_t at, const int32_t* src, size_t n) { return std::memcmp(block + at, src, sizeof(int32_t) * n) == 0; }
+static bool col_zero(const double* block, size_t at, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (block[at + i] != 0.0) return false;
+    return true;
+}
+
+static void check_block_columns() {
+    const int before = g_failed;
+    {  // counts: [t_sample ns | N n | B n | a n | w n | idx n m]; n = 3, m = 2, ns = 5: 5 + 12 + 3 = 20; then n = 1, m = 3, ns = 2 (n m odd:
+       // the int32 tail has a pad): 2 + 4 + 2 = 8
+        vag_counts_obs a{}, b{};
+        a.nu_min = 1e17, a.nu_max = 2e17, a.num_points = 3, a.n = 3, a.m = 2, a.n_samples = 5;
+        a.t_sample = D({1e4, 2e4, 3e4, 4e4, 5e4}), a.sample_idx = I({0, 1, 2, 3, 3, 4});
+        a.counts = D({1.0, 2.0, 3.0}), a.background = D({0.1, 0.2, 0.3}), a.scale = D({4.0, 5.0, 6.0}), a.weight = D({7.0, 8.0, 9.0});
+        b.nu_min = 1e17, b.nu_max = 2e17, b.num_points = 2, b.n = 1, b.m = 3, b.n_samples = 2;
+        b.t_sample = D({6e4, 7e4}), b.sample_idx = I({1, 0, 1}), b.counts = D({11.0}), b.background = D({12.0}), b.scale = D({13.0}), b.weight = D({14.0});
+        vag_counts_fit_spec cs{};
+        cs.n_groups = 2, cs.groups = heap<vag_counts_obs>({a, b});
+        const CountsCols ka = counts_cols(a), kb = counts_cols(b);
+        CHECK(ka.N == 5 && ka.B == 8 && ka.a == 11 && ka.w == 14 && ka.idx == 17 && ka.doubles == 20);
+        CHECK(kb.N == 2 && kb.B == 3 && kb.a == 4 && kb.w == 5 && kb.idx == 6 && kb.doubles == 8);
+        std::vector<double> stage;
+        CountsLayout lay;
+        CHECK(counts_scan(&cs, stage, lay) == VAG_OK && longs(lay.off, {0, 20}) && (size_t)lay.off[1] == ka.doubles && stage.size() == 28);
+        if (stage.size() == 28) {
+            const double* blk = heap_v(stage);
+            for (int g = 0; g < 2; ++g) {
+                const vag_counts_obs& o = cs.groups[g];
+                const CountsCols k = counts_cols(o);
+                const double* p = blk + lay.off[g];
+                CHECK(col_is(p, 0, o.t_sample, o.n_samples) && col_is(p, k.N, o.counts, o.n) && col_is(p, k.B, o.background, o.n));
+                CHECK(col_is(p, k.a, o.scale, o.n) && col_is(p, k.w, o.weight, o.n) && icol_is(p, k.idx, o.sample_idx, (size_t)o.n * o.m));
+            }
+        }
+    }
+    {  // index: [t n K | nu n K | s n | sigma n | w n | c K]; n = 2, K = 3: 6 + 6 + 6 + 3 = 21; then n = 1, K = 2: 2 + 2 + 3 + 2 = 9
+        vag_index_obs a{}, b{};
+        a.n = 2, a.k = 3, a.nu = D({1e9, 2e9, 3e9}), a.coef = D({-1.0, 0.5, 1.0});
+        a.t = D({1e5, 2e5}), a.value = D({-0.5, -0.6}), a.err = D({0.1, 0.2}), a.weight = D({1.0, 2.0});
+        b.n = 1, b.k = 2, b.nu = D({4e9, 5e9}), b.coef = D({-2.0, 2.0}), b.t = D({3e5}), b.value = D({0.3}), b.err = D({0.05}), b.weight = D({1.5});
+        vag_index_fit_spec is{};
+        is.n_groups = 2, is.groups = heap<vag_index_obs>({a, b});
+        const IndexCols ka = index_cols(a), kb = index_cols(b);
+        CHECK(ka.nu == 6 && ka.value == 12 && ka.err == 14 && ka.weight == 16 && ka.coef == 18 && ka.doubles == 21);
+        CHECK(kb.nu == 2 && kb.value == 4 && kb.err == 5 && kb.weight == 6 && kb.coef == 7 && kb.doubles == 9);
+        std::vector<double> stage;
+        IndexLayout lay;
+        CHECK(index_scan(&is, stage, lay) == VAG_OK && longs(lay.off, {0, 21}) && (size_t)lay.off[1] == ka.doubles && stage.size() == 30);
+        if (stage.size() == 30) {
+            const double* blk = heap_v(stage);
+            for (int g = 0; g < 2; ++g) {
+                const vag_index_obs& o = is.groups[g];
+                const IndexCols k = index_cols(o);
+                const double* p = blk + lay.off[g];
+                for (int i = 0; i < o.n; ++i)
+                    for (int q = 0; q < o.k; ++q) CHECK(p[i * o.k + q] == o.t[i] && p[k.nu + i * o.k + q] == o.nu[q]);
+                CHECK(col_is(p, k.value, o.value, o.n) && col_is(p, k.err, o.err, o.n) && col_is(p, k.weight, o.weight, o.n));
+                CHECK(col_is(p, k.coef, o.coef, o.k));
+            }
+        }
+    }
+    for (const bool first_has_sigma : {true, false}) {
+        // fold: [t ns J | nu ns J | A J C | sigma J | exposure / m n | N n C | B n C | w n C | idx n m]; n = 2, C = 3, J = 2, ns = 3,
+        // m = 1: 6 + 6 + 6 + 2 + 2 + 18 + 1 = 41; then J = C = n = m = ns = 1: 9.  One of the two has a cross-section, the other zeros.
+        vag_fold_obs a{}, b{};
+        a.J = 2, a.C = 3, a.n = 2, a.m = 1, a.n_samples = 3;
+        a.nu = D({1e17, 2e17}), a.A = D({1.0, 2.0, 3.0, 4.0, 5.0, 6.0}), a.t_sample = D({1e4, 2e4, 3e4}), a.sample_idx = I({2, 1});
+        a.exposure_over_m = D({10.0, 20.0}), a.counts = D({0.0, 1.0, 2.0, 3.0, 4.0, 5.0}), a.background = D({0.1, 0.2, 0.3, 0.4, 0.5, 0.6});
+        a.weight = D({1.0, 0.0, 2.0, 1.0, 0.5, 1.0});
+        b.J = 1, b.C = 1, b.n = 1, b.m = 1, b.n_samples = 1;
+        b.nu = D({3e17}), b.A = D({50.0}), b.t_sample = D({4e4}), b.sample_idx = I({0}), b.exposure_over_m = D({100.0});
+        b.counts = D({7.0}), b.background = D({0.5}), b.weight = D({1.5});
+        (first_has_sigma ? a.sigma : b.sigma) = first_has_sigma ? D({3e-22, 2e-22}) : D({1e-22});
+        vag_fold_fit_spec fs{};
+        fs.n_groups = 2, fs.groups = heap<vag_fold_obs>({a, b});
+        const FoldCols ka = fold_cols(a), kb = fold_cols(b);
+        CHECK(ka.nu == 6 && ka.A == 12 && ka.sigma == 18 && ka.eom == 20 && ka.N == 22 && ka.B == 28 && ka.w == 34 && ka.idx == 40 && ka.doubles == 41);
+        CHECK(kb.nu == 1 && kb.A == 2 && kb.sigma == 3 && kb.eom == 4 && kb.N == 5 && kb.B == 6 && kb.w == 7 && kb.idx == 8 && kb.doubles == 9);
+        vag_fit_spec spec = fit_spec();  // (frees N_H: a group has a cross-section)
+        std::vector<double> stage;
+        FoldLayout lay;
+        CHECK(fold_scan(&spec, &fs, stage, lay) == VAG_OK && longs(lay.off, {0, 41}) && (size_t)lay.off[1] == ka.doubles && stage.size() == 50);
+        if (stage.size() == 50) {
+            const double* blk = heap_v(stage);
+            for (int g = 0; g < 2; ++g) {
+                const vag_fold_obs& o = fs.groups[g];
+                const FoldCols k = fold_cols(o);
+                const double* p = blk + lay.off[g];
+                for (int s = 0; s < o.n_samples; ++s)
+                    for (int j = 0; j < o.J; ++j) CHECK(p[s * o.J + j] == o.t_sample[s] && p[k.nu + s * o.J + j] == o.nu[j]);
+                CHECK(col_is(p, k.A, o.A, (size_t)o.J * o.C) && (o.sigma ? col_is(p, k.sigma, o.sigma, o.J) : col_zero(p, k.sigma, o.J)));
+                CHECK(col_is(p, k.eom, o.exposure_over_m, o.n) && col_is(p, k.N, o.counts, (size_t)o.n * o.C));
+                CHECK(col_is(p, k.B, o.background, (size_t)o.n * o.C) && col_is(p, k.w, o.weight, (size_t)o.n * o.C));
+                CHECK(icol_is(p, k.idx, o.sample_idx, (size_t)o.n * o.m));
+            }
+        }
+    }
+    {  // cov: [t n | nu n | ln_flux n | ext n | Wt n n]; n = 2 without ext: 8 + 4 = 12; then n = 65 with ext: 260 + 4225 = 4485
+        vag_cov_obs a{}, b{};
+        a.n = 2, a.weight = 1.0, a.t = D({1e5, 2e5}), a.nu = D({1e9, 2e9}), a.ln_flux = D({-60.0, -61.0}), a.whitener = D({1.0, NAN, 2.0, 3.0});
+        std::vector<double> W(65 * 65, NAN);
+        for (int i = 0; i < 65; ++i)
+            for (int j = 0; j <= i; ++j) W[i * 65 + j] = 1.0 + i * 65 + j;
+        b.n = 65, b.weight = 0.5, b.t = heap_v(ramp(65, 1e5)), b.nu = heap_v(ramp(65, 1e9)), b.ln_flux = heap_v(ramp(65, -100.0));
+        b.ext = heap_v(ramp(65, 0.5)), b.whitener = heap_v(W);
+        vag_cov_fit_spec cs{};
+        cs.n_groups = 2, cs.groups = heap<vag_cov_obs>({a, b});
+        const CovCols ka = cov_cols(a), kb = cov_cols(b);
+        CHECK(ka.nu == 2 && ka.ln_flux == 4 && ka.ext == 6 && ka.Wt == 8 && ka.doubles == 12);
+        CHECK(kb.nu == 65 && kb.ln_flux == 130 && kb.ext == 195 && kb.Wt == 260 && kb.doubles == 4485);
+        std::vector<double> stage;
+        CovLayout lay;
+        CHECK(cov_scan(&cs, stage, lay) == VAG_OK && longs(lay.off, {0, 12}) && (size_t)lay.off[1] == ka.doubles && stage.size() == 4497);
+        if (stage.size() == 4497) {
+            const double* blk = heap_v(stage);
+            for (int g = 0; g < 2; ++g) {
+                const vag_cov_obs& o = cs.groups[g];
+                const CovCols k = cov_cols(o);
+                const double* p = blk + lay.off[g];
+                CHECK(col_is(p, 0, o.t, o.n) && col_is(p, k.nu, o.nu, o.n) && col_is(p, k.ln_flux, o.ln_flux, o.n));
+                CHECK(o.ext ? col_is(p, k.ext, o.ext, o.n) : col_zero(p, k.ext, o.n));
+                bool same = true;
+                for (int i = 0; i < o.n; ++i)
+                    for (int j = 0; j < o.n; ++j) same = same && p[k.Wt + (size_t)j * o.n + i] == (j <= i ? o.whitener[(size_t)i * o.n + j] : 0.0);
+                CHECK(same);
+            }
+        }
+    }
+    {  // a flux block of limit rows: [limit n | sigma n | kind n]; the point rows, n = 3: 6 + 2 = 8; then band group 0, n = 2: 4 + 1 = 5
+        const int32_t det = VAG_OBS_DETECTION, lim = VAG_OBS_UPPER_LIMIT;
+        const vag_fit_spec spec = fit_spec();
+        vag_limit_fit_spec l{};
+        l.point = {I({lim, lim, det}), D({2.5, 3.5, 9.0}), D({0.5, 0.25, 9.0})};
+        l.n_bands = 2;
+        l.bands = heap<vag_limit_rows>({{I({det, lim}), D({7.0, 1.5}), D({7.0, 0.125})}, {I({det, det, det}), nullptr, nullptr}});
+        const LimCols ka = lim_cols(3), kb = lim_cols(2);
+        CHECK(ka.sigma == 3 && ka.kind == 6 && ka.doubles == 8);
+        CHECK(kb.sigma == 2 && kb.kind == 4 && kb.doubles == 5);
+        std::vector<double> stage;
+        LimLayout lay;
+        CHECK(lim_scan(&spec, nullptr, &l, stage, lay) == VAG_OK && lay.point == 0 && longs(lay.band, {8, -1}) && stage.size() == 13);
+        CHECK((size_t)lay.band[0] == ka.doubles);
+        if (stage.size() == 13) {
+            const double* blk = heap_v(stage);
+            const double* p = blk + lay.point;  // (a detection holds limit 0 and sigma 1)
+            CHECK(col_is(p, 0, D({2.5, 3.5, 0.0}), 3) && col_is(p, ka.sigma, D({0.5, 0.25, 1.0}), 3) && icol_is(p, ka.kind, l.point.kind, 3));
+            p = blk + lay.band[0];
+            CHECK(col_is(p, 0, D({0.0, 1.5}), 2) && col_is(p, kb.sigma, D({1.0, 0.125}), 2) && icol_is(p, kb.kind, l.bands[0].kind, 2));
+        }
+    }
+    {  // a band group in the fit block: [t n | ln_flux n | ln_err n | weight n]; n = 2 behind point rows of n = 3 (at 18): 8; then n = 3: 12
+        const vag_fit_spec s = fit_full(true);
+        const BandCols ka = band_cols(2), kb = band_cols(3);
+        CHECK(ka.ln_flux == 2 && ka.ln_err == 4 && ka.weight == 6 && ka.doubles == 8);
+        CHECK(kb.ln_flux == 3 && kb.ln_err == 6 && kb.weight == 9 && kb.doubles == 12);
+        FitLayout lay;
+        CHECK(fit_scan(&s, 2, FitAccepts{}, lay) == VAG_OK && sizes(lay.band, {18, 26}) && lay.band[1] == lay.band[0] + ka.doubles);
+        CHECK(lay.prior == lay.band[1] + kb.doubles);
+        const std::vector<double> got = filled(lay.doubles, [&](double* hp) { fit_fill(&s, lay, hp); });
+        for (int g = 0; g < 2 && lay.band.size() == 2; ++g) {
+            const vag_band_obs& bd = s.bands[g];
+            const BandCols k = band_cols(bd.n);
+            const double* p = got.data() + lay.band[g];
+            CHECK(col_is(p, 0, bd.t, bd.n) && col_is(p, k.ln_flux, bd.ln_flux, bd.n) && col_is(p, k.ln_err, bd.ln_err, bd.n));
+            CHECK(col_is(p, k.weight, bd.weight, bd.n));
+        }
+    }
+    {  // a centroid group: [nu | t n | east n | north n | err_east n | err_north n | weight n]; n = 1: 7; then n = 2: 13
+        const vag_sky_fit_spec s = sky_full();
+        const SixCols ka = six_cols(1), kb = six_cols(2);
+        CHECK(ka.rows == 1 && ka.col[0] == 1 && ka.col[1] == 2 && ka.col[2] == 3 && ka.col[3] == 4 && ka.col[4] == 5 && ka.col[5] == 6 && ka.doubles == 7);
+        CHECK(kb.rows == 1 && kb.col[0] == 1 && kb.col[1] == 3 && kb.col[2] == 5 && kb.col[3] == 7 && kb.col[4] == 9 && kb.col[5] == 11 && kb.doubles == 13);
+        SkyLayout lay;
+        CHECK(sky_scan(&s, lay) == VAG_OK && sizes(lay.off, {0, 7}) && lay.off[1] == ka.doubles && lay.doubles == 20);
+        const std::vector<double> got = filled(lay.doubles, [&](double* hp) { six_fill(&s, lay, hp); });
+        for (int g = 0; g < 2 && lay.off.size() == 2; ++g) {
+            const vag_centroid_obs& o = s.groups[g];
+            const SixCols k = six_cols(o.n);
+            const double* p = got.data() + lay.off[g];
+            const double* col[6] = {o.t, o.east, o.north, o.err_east, o.err_north, o.weight};
+            CHECK(p[0] == o.nu);
+            for (int q = 0; q < 6; ++q) CHECK(col_is(p, k.col[q], col[q], o.n));
+        }
+    }
+    {  // a visibility group: [nu | t n_epochs | u | v | re | im | err | weight] (n_vis each); 3 epochs, 130 visibilities: 4 + 780; then 1, 2: 14
+        const vag_vis_fit_spec s = vis_full();
+        const VisCols ka = vis_cols(s.groups[0]), kb = vis_cols(s.groups[1]);
+        CHECK(ka.t == 1 && ka.six == 4 && ka.doubles == 784 && kb.t == 1 && kb.six == 2 && kb.doubles == 14);
+        CHECK(six_cols(130, ka.six).col[0] == 4 && six_cols(130, ka.six).col[5] == 654 && six_cols(2, kb.six).col[5] == 12);
+        BlockKey key;
+        std::vector<VisLayout> lay;
+        std::vector<int> blocks;
+        CHECK(vis_scan(&s, key) == VAG_OK && vis_rows(&s, lay, blocks) == VAG_OK && key.doubles == 798 && lay[1].obs_off == ka.doubles);
+        const std::vector<double> got = filled(key.doubles, [&](double* hp) { vis_fill(&s, lay, hp); });
+        for (int g = 0; g < 2; ++g) {
+            const vag_visibility_obs& o = s.groups[g];
+            const VisCols k = vis_cols(o);
+            const SixCols six = six_cols(o.n_vis, k.six);
+            const double* p = got.data() + lay[g].obs_off;
+            const double* col[6] = {o.u, o.v, o.re, o.im, o.err, o.weight};
+            CHECK(p[0] == o.nu && col_is(p, k.t, o.t, o.n_epochs));
+            for (int q = 0; q < 6; ++q) CHECK(col[q] ? col_is(p, six.col[q], col[q], o.n_vis) : col_zero(p, six.col[q], o.n_vis));
+        }
+    }
+    {  // the host copy of a short series' frequencies: point i at nu[i % K], as the index and fold scans lay the nu column out
+        const double* nu = D({1e9, 2e9, 3e9});
+        double* pts = heap_v(std::vector<double>(6, NAN));
+        CHECK(short_series_nu(nu, 3, 6, 6, pts) == pts && col_is(pts, 0, D({1e9, 2e9, 3e9, 1e9, 2e9, 3e9}), 6));
+        CHECK(short_series_nu(nu, 3, 9, 6, pts) == nullptr);  // (above the bound: no shared-node test, nothing written)
+    }
+    done("block columns", before);
+}
+
+// ---- the pass list of a prepared request: kinds and groups in order, the size, the first and the last position; a request fit_scan
+//      accepts has a pass (the last pass writes the call's output), and the one with an empty list is the one it refuses
+static bool passes_are(const std::vector<PassItem>& got, std::initializer_list<PassItem> want) {
+    if (got.size() != want.size()) return false;
+    size_t i = 0;
+    for (const PassItem& w : want) {
+        if (got[i].kind != w.kind || got[i].group != w.group) return false;
+        ++i;
+    }
+    return true;
+}
+
+static bool scan_accepts(FitRequest& r) { return fit_scan(r.spec, r.spec->ndim, fit_accepts(r), r.fit) == VAG_OK; }
+
+static void check_pass_list() {
+    const int before = g_failed;
+    using K = PassKind;
+    vag_fit_spec point = fit_full(false);  // 3 point rows alone
+    point.n_bands = 0;
+    {
+        FitRequest r = fit_request(&point);
+        CHECK(fit_request_prepare(r) == VAG_OK && scan_accepts(r));
+        CHECK(passes_are(fit_pass_list(r), {{K::Point, 0}}));  // one pass: the first and the last
+    }
+    {  // no point row, two band groups
+        const vag_fit_spec s = fit_full(false, 0);
+        FitRequest r = fit_request(&s);
+        CHECK(fit_request_prepare(r) == VAG_OK && scan_accepts(r));
+        const std::vector<PassItem> list = fit_pass_list(r);
+        CHECK(passes_are(list, {{K::Band, 0}, {K::Band, 1}}));
+        CHECK(list.size() == 2 && list.front().kind == K::Band && list.front().group == 0 && list.back().group == 1);
+    }
+    {  // a visibility group without centroid groups: sky carries the placement only
+        vag_sky_fit_spec sky{};
+        sky.pa_fixed = 0.3;
+        const vag_vis_fit_spec vis = vis_full();
+        FitRequest r = fit_request(&point, &sky, &vis);
+        CHECK(fit_request_prepare(r) == VAG_OK && r.sky && r.placed && scan_accepts(r));
+        const std::vector<PassItem> list = fit_pass_list(r);
+        CHECK(passes_are(list, {{K::Point, 0}, {K::Vis, 0}, {K::Vis, 1}}));
+        CHECK(list.size() == 3 && list.front().kind == K::Point && list.back().kind == K::Vis && list.back().group == 1);
+    }
+    {  // empty group lists given as present specs: normalised away, the list is the narrower request's
+        const vag_fit_spec s = fit_full(false);
+        const vag_sky_fit_spec sky{};
+        const vag_vis_fit_spec vis{};
+        const vag_pol_fit_spec pol{};
+        const vag_counts_fit_spec counts{};
+        const vag_index_fit_spec index{};
+        const vag_fold_fit_spec fold{};
+        const vag_cov_fit_spec cov{};
+        FitRequest r = fit_request(&s, &sky, &vis, &pol, nullptr, nullptr, &counts, &index, &fold, nullptr, &cov), narrow = fit_request(&s);
+        CHECK(fit_request_prepare(r) == VAG_OK && fit_request_prepare(narrow) == VAG_OK && scan_accepts(r) && scan_accepts(narrow));
+        const std::vector<PassItem> list = fit_pass_list(r), want = fit_pass_list(narrow);
+        CHECK(passes_are(list, {{K::Point, 0}, {K::Band, 0}, {K::Band, 1}}) && passes_are(want, {{K::Point, 0}, {K::Band, 0}, {K::Band, 1}}));
+        CHECK(list.front().kind == K::Point && list.back().kind == K::Band && list.back().group == 1);
+    }
+    {  // every kind at once, two groups of each list kind
+        const vag_fit_spec s = fit_full(true);
+        const vag_sky_fit_spec sky = sky_full();
+        const vag_vis_fit_spec vis = vis_full();
+        const vag_pol_fit_spec pol = pol_full();
+        const vag_counts_fit_spec counts = counts_spec();
+        const vag_index_fit_spec index = index_spec();
+        const vag_fold_fit_spec fold = fold_spec();
+        const vag_cov_fit_spec cov = cov_spec();
+        FitRequest r = fit_request(&s, &sky, &vis, &pol, nullptr, nullptr, &counts, &index, &fold, nullptr, &cov);
+        CHECK(fit_request_prepare(r) == VAG_OK && scan_accepts(r));
+        const std::vector<PassItem> list = fit_pass_list(r);
+        CHECK(passes_are(list, {{K::Point, 0}, {K::Band, 0}, {K::Band, 1}, {K::Centroid, 0}, {K::Centroid, 1}, {K::Vis, 0}, {K::Vis, 1},
+                                {K::Pol, 0}, {K::Pol, 1}, {K::Counts, 0}, {K::Counts, 1}, {K::Index, 0}, {K::Index, 1}, {K::Fold, 0},
+                                {K::Fold, 1}, {K::Cov, 0}, {K::Cov, 1}}));
+        CHECK(list.size() == 17 && list.front().kind == K::Point && list.back().kind == K::Cov && list.back().group == 1);
+    }
+    {  // nothing at all: the empty list is the request fit_scan refuses
+        vag_fit_spec s = fit_full(false, 0);
+        s.n_bands = 0;
+        FitRequest r = fit_request(&s);
+        CHECK(fit_request_prepare(r) == VAG_OK && fit_pass_list(r).empty() && !scan_accepts(r));
+    }
+    done("pass list", before);
+}
+
 int main() {
     const vag_fit_spec spec = fit_spec();
     check_lim(spec);
@@ -843,6 +1145,8 @@ int main() {
     check_prepare(spec);
     check_refusals(spec);
     check_block_refusals();
+    check_block_columns();
+    check_pass_list();
     if (g_failed) std::printf("%d checks failed\n", g_failed);
     return g_failed ? 1 : 0;
 }

@@ -15,7 +15,7 @@ SCANS = ("lim", "noise", "tmpl", "counts", "index", "fold", "cov")
 BLOCKS = ("fit", "sky", "pol", "vis")  # hashed in place: a scan, and a miss half of row checks and a fill
 CASES = [f"{s}_scan layout" for s in SCANS] + [f"{b} block layout" for b in BLOCKS] + ["block hashes", "scan keys"] + \
         ["fit_request_prepare empty blocks", "fit_request_prepare full request"] + \
-        [f"{s}_scan refusal" for s in SCANS] + [f"{b} block refusals" for b in BLOCKS]
+        [f"{s}_scan refusal" for s in SCANS] + [f"{b} block refusals" for b in BLOCKS] + ["block columns", "pass list"]
 STATIC = ["-static-libasan", "-static-libubsan"]  # g++ links its sanitizer runtimes dynamically unless told; clang++ statically, and knows no such flag
 
 

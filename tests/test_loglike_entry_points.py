@@ -7,6 +7,7 @@ Three fixtures, all on C4 (configs.C4_TRUTH): (a) the 60 point rows alone; (b) o
 entry points take; (c) the same plus a count spectrum, a template and two correlated groups: every kind of data the likelihood takes,
 through the widest entry point.  Two batch sizes: 3 walkers (evaluated in the identity order) and 64, the smallest batch evaluated in cost order.
 profiles/loglike_bits.py writes ln L of the same fixtures to a file, to compare two builds."""
+import copy
 import ctypes as C
 
 import numpy as np
@@ -92,6 +93,51 @@ def fixture_c():
         f.add_correlated(**tcov.make_data(n, kind))
     free = len(tv.FLUX_DEFS + tv.SKY_DEFS) + 2
     return f, d[:free] + [P("amp_sn", 0.0, 1.0)] + tf.N_H_DEF + d[free:]
+
+
+def extra_groups():
+    """A second group, of another row count than fixture (c)'s one, for each of the seven list kinds of which (c) holds one group:
+    a band group (2 rows for 3), a centroid group (2 epochs for 3), a visibility group (5 visibilities in 2 epochs for 12 in 3), a
+    QU polarization group (3 epochs for 4), a counts group (2 rows for 3), a spectral-index group (4 rows of 3 frequencies for 3 of 2)
+    and a count-spectrum group (2 rows of 3 bins for 3 of 4).  The data are made once; returns seven functions that add one group
+    each to a fitter.  No new free parameter."""
+    truth = tv._c4_truth()
+    rng = np.random.default_rng(70)
+    bt = tc.EPOCHS[1::8][:2]
+    bflux = tc.device_flux([_abi.make_params(**configs.C4_TRUTH)], bt, tl.BAND, 7)[0]
+    band = dict(band=tl.BAND, t=bt, flux=bflux * (1 + 0.05 * rng.standard_normal(2)), err=0.1 * bflux, num_points=7)
+    ct = np.array([100.0, 300.0]) * DAY
+    sm = truth.sky_moments(ct, 5e9, exact=True)
+    err = np.full(2, 0.2 * tv.units.mas)
+    cen = dict(nu=5e9, t=ct, east=tv.EAST0_TRUE + sm.Xbar * np.sin(tv.PA_TRUE) + sm.Ybar * np.cos(tv.PA_TRUE) + 0.5 * err,
+               north=sm.Xbar * np.cos(tv.PA_TRUE) - sm.Ybar * np.sin(tv.PA_TRUE) - 0.5 * err, err_east=err, err_north=1.5 * err)
+    vd = tv.make_group(truth, tv.VIS_T[:2], tv.VIS_NU, (3, 2), tv.PA_TRUE, tv.EAST0_TRUE, seed=2)
+    pol = tp.make_group(truth, t=tp.POL_T[:3], seed=2)
+    counts = tc.make_group(tc.EPOCHS[5::6][:2], np.full(2, 5e4), 1, seed=12)
+    index = ti.make_group(ti.X_BAND, tc.EPOCHS[2::5][:4], 3, "slope", seed=34)
+    fold = tf.make_group(3, 2, tc.EPOCHS[5::7][:2], np.full(2, 4e4), 1, seed=52, absorption=True,
+                         truth=np.append(tc.TRUTH, tf.LOG_N_H_TRUE), d=tf.defs(tf.N_H_DEF))
+    return [lambda f: f.add_flux(**band), lambda f: f.add_centroid(**cen), lambda f: tv.add_group(f, vd, n_az=64),
+            lambda f: tp.add_group(f, pol), lambda f: f.add_counts(**counts), lambda f: f.add_spectral_index(**index),
+            lambda f: f.add_count_spectrum(**fold)]
+
+
+def fixture_d():
+    """Nine fitters on fixture (c)'s data: F0 = fixture (c); F_1 .. F_7 = F0 plus one of the extra_groups() each; F_all = F0 plus all
+    seven, so that every list kind has two groups of different row counts (the correlated groups are two already).  Returns
+    ([F0, F_1, ..., F_7, F_all], parameter list): the parameters are fixture (c)'s."""
+    base, d = fixture_c()
+    fits = [copy.deepcopy(base) for _ in range(9)]  # (before any of them has built a spec)
+    for k, add in enumerate(extra_groups()):
+        add(fits[1 + k])
+        add(fits[8])
+    return fits, d
+
+
+def n_passes(spec):
+    """The passes of a likelihood call on this spec: the point rows, then one per group of every list."""
+    lists = (spec._sky, spec._vis, spec._pol, spec._counts, spec._index, spec._fold, spec._cov)
+    return (1 if spec.n_data > 0 else 0) + spec.n_bands + sum(s.n_groups for s in lists if s is not None)
 
 
 def walkers_a(nb):
@@ -232,6 +278,34 @@ def test_every_kind_of_data_through_the_widest_entry_point(fit_c, nb):
     assert np.array_equal(tv._with_hook("VAG_NO_ORDER", "1", lambda: call("vag_loglike_cov_batch", spec, widest_specs(spec), th)), a)
     assert np.array_equal(f.loglike_batch(th, d), a)
     assert f.last_plan.n_walkers_rejected == 0
+
+
+def test_a_second_group_of_every_kind_adds_its_own_term():
+    """Fixture (d) at 3 walkers (the identity evaluation order).  With one group per kind every group starts at offset 0 of its
+    resident block and the call's last pass is the only one of its kind: a pass that read a column of the wrong group, or a wrong
+    first or last pass, could not show.  Two groups of different row counts is the smallest shape at which it can.  A pass adds one
+    chi^2 term per walker, so ln L(F_all) - ln L(F0) = sum_k (ln L(F_k) - ln L(F0)), exactly in real arithmetic; on the device each
+    side adds one term per pass in double, so the two sides agree within N 2^-52 max |ln L|, N the passes of the nine fits that
+    enter, counted from their specs.  Every value is finite and every extra group moves every walker.
+
+    Largest observed ratio of the residual to that bound on an MI355X: 0.0031 (a residual of 2.9e-11, half an ulp of the largest
+    |ln L| = 4.0e5, in one walker, against 9.3e-9 for N = 104; the other two walkers exact), in this build and in its parent alike."""
+    fits, d = fixture_d()
+    th = walkers_c(3)
+    specs = [f.build_spec(d)[0] for f in fits]
+    assert [n_passes(s) for s in specs] == [10] + [11] * 7 + [17]
+
+    def groups(s):
+        return (s.n_bands, s._sky.n_groups, s._vis.n_groups, s._pol.n_groups, s._counts.n_groups, s._index.n_groups, s._fold.n_groups)
+
+    assert groups(specs[0]) == (1,) * 7 and groups(specs[8]) == (2,) * 7 and specs[8]._cov.n_groups == 2
+    ll = np.array([f.loglike_batch(th, d) for f in fits])  # [9][3]
+    assert np.all(np.isfinite(ll))
+    assert np.all(ll[1:8] != ll[0])
+    residual = np.abs((ll[8] - ll[0]) - np.sum(ll[1:8] - ll[0], axis=0))
+    bound = sum(n_passes(s) for s in specs) * 2.0 ** -52 * np.max(np.abs(ll))
+    print(f"residual {residual.tolist()} bound {bound!r} ratio {np.max(residual) / bound!r} max |ln L| {np.max(np.abs(ll))!r}")
+    assert np.all(residual <= bound)
 
 
 @pytest.mark.parametrize("nb", BATCHES)

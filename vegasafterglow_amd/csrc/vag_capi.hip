@@ -2229,7 +2229,7 @@ int vis_chi2_request(vag_ctx* c, const vag_model_params* d_params, int nb, const
     if (c->d_vispart.ensure(sizeof(double) * 2 * (size_t)nb * n_blk_all)) return VAG_E_HIP;
     va.meta = c->d_meta.as<VagGridMeta>();
     va.phi = c->d_phi.as<double>();
-    va.obs = c->vis.d.as<double>() + lay.obs_off + 1 + nt;
+    va.obs = c->vis.d.as<double>() + lay.obs_off + vis_cols(o).six;
     va.blocks = c->d_visblk.as<int>() + 3 * (size_t)lay.blk_off;
     va.n_vis = o.n_vis;
     va.n_blk_all = n_blk_all;
@@ -3380,20 +3380,16 @@ static int loglike_passes(vag_ctx* c, const FitRequest& req, const double* d_the
         o.next_order = nxt.as<int>();
         return o;
     };
-    const int n_groups = sky ? sky->n_groups : 0, n_vis_groups = req.vis ? req.vis->n_groups : 0;
-    const int n_pol_groups = req.pol ? req.pol->n_groups : 0, n_counts_groups = req.counts ? req.counts->n_groups : 0;
-    const int n_index_groups = req.index ? req.index->n_groups : 0, n_fold_groups = req.fold ? req.fold->n_groups : 0;
-    const int n_cov_groups = req.cov ? req.cov->n_groups : 0;
-    const int n_pass = (n > 0 ? 1 : 0) + spec->n_bands + n_groups + n_vis_groups + n_pol_groups + n_counts_groups + n_index_groups +
-                       n_fold_groups + n_cov_groups;
-    int pass = 0, n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
+    const std::vector<PassItem> passes = fit_pass_list(req);  // the call's passes: position 0 is the first, the final one the last
+    size_t pass = 0;
+    int n_cap = 0, n_inv = 0;  // per-pass rejection counts: the call reports the worst pass
     // what the current pass's back kernel receives (built at its launch: the model stages may have moved the buffers); the SSC tables
     // of a pass report per-model failures in d_icstatus: in a fit they invalidate the walker, they do not raise
     auto fit_pass = [&]() -> FitPass {
         const bool ssc = (c->batch_flags & (VAG_FLAG_SSC | VAG_FLAG_RVS_SSC)) != 0;
         return {c->d_meta.as<VagGridMeta>(), c->d_row_status.as<int>(), c->d_row_off.as<int>(),
                 (ssc && c->d_icstatus.p) ? c->d_icstatus.as<int>() : nullptr, d_chi2, c->d_valid.as<int>(), d_lp, pass == 0 ? 1 : 0,
-                pass == n_pass - 1 ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order};
+                pass + 1 == passes.size() ? 1 : 0, d_out, c->d_fitstat.as<int>(), d_order};
     };
     auto begin_pass = [&] {  // before the pass's model request
         c->order_next = d_order != nullptr;
@@ -3401,7 +3397,6 @@ static int loglike_passes(vag_ctx* c, const FitRequest& req, const double* d_the
     };
     auto end_pass = [&]() -> int {  // behind the pass's back kernel
         HIPCHK(hipGetLastError());
-        ++pass;
         n_cap = std::max(n_cap, c->plan.n_models_capacity);
         n_inv = std::max(n_inv, c->plan.n_models_invalid);
         return VAG_OK;
@@ -3413,8 +3408,9 @@ static int loglike_passes(vag_ctx* c, const FitRequest& req, const double* d_the
     auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext,
                     long lim_off, long noise_off, unsigned present, long tmpl_off, unsigned tpresent) -> int {
         const double* lb = lim_off >= 0 ? c->lim.d.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
-        const int* lk = lb ? reinterpret_cast<const int*>(lb + 2 * (size_t)npts) : nullptr;
-        const double* ls = lb ? lb + npts : nullptr;
+        const LimCols lcol = lim_cols(npts);
+        const int* lk = lb ? reinterpret_cast<const int*>(lb + lcol.kind) : nullptr;
+        const double* ls = lb ? lb + lcol.sigma : nullptr;
         if (tmpl_off >= 0) {
             const double* nz = noise_off >= 0 ? c->noise.d.as<double>() : nullptr;
             const double* tp = c->tmpl.d.as<double>();  // [amp_fixed 8 | the passes' values]
@@ -3433,175 +3429,187 @@ static int loglike_passes(vag_ctx* c, const FitRequest& req, const double* d_the
     };
     // the front half of a series-group pass (index, fold, cov groups): the group's np points, whose times and frequencies lie at d_t
     // and d_nu of its resident block, through the model stages and one series request.  nu_pts: the points' frequencies on the host
-    // for the shared-node test of a short series, or null for none.  Leaves the fluxes in d_series_flux or sets rc; not 0: no memory.
+    // for the shared-node test of a short series, or null for none.  Leaves the fluxes in d_series_flux (room_for_flux(np) has made
+    // the room) or hands the failure back.
     auto series_group_flux = [&](const double* d_t, const double* d_nu, size_t np, const double* nu_pts) -> int {
-        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(np, (size_t)std::max(n, 1)))) return VAG_E_HIP;
-        rc = prep_times(c, d_t, (int)np, d_nu, (int)np);
+        int r = prep_times(c, d_t, (int)np, d_nu, (int)np);
         begin_pass();
-        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
-        if (rc == VAG_OK)  // (in chunks above 512 points)
-            rc = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), nu_pts ? upload_series_bands(c, nu_pts, (int)np) : 0);
-        return VAG_OK;
+        if (r == VAG_OK) r = run_model_stages(c, d_params, nb, false);
+        if (r == VAG_OK)  // (in chunks above 512 points)
+            r = series_request(c, d_params, nb, (int)np, c->d_series_flux.as<double>(), nu_pts ? upload_series_bands(c, nu_pts, (int)np) : 0);
+        return r;
     };
-    if (n > 0) {  // point data: one (t, nu) series per walker (fitter.py:510-522)
-        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * n)) return VAG_E_HIP;
+    // its counterpart for a centroid, visibility or polarization group, whose block is [nu | t ...] at ds with n times at ds + t_at:
+    // the times behind the one frequency, through the model stages; the group's own request follows
+    auto sky_group_stages = [&](const double* ds, size_t t_at, int nt) -> int {
+        int r = prep_times(c, ds + t_at, nt, ds, 1);
         begin_pass();
-        rc = run_model_stages(c, d_params, nb, false, try_spec);
-        if (rc == VAG_OK) rc = series_request(c, d_params, nb, n, c->d_series_flux.as<double>(), upload_series_bands(c, spec->nu, n));
-        if (rc == VAG_OK)
-            rc = back(c->d_series_flux.as<double>(), n, ln_flux, ln_err, weight, spec->ext_kernel ? ext : nullptr,
-                      req.lim ? req.llay.point : -1, req.noise ? req.nlay.point : -1, req.noise ? req.nlay.point_present : 0u,
-                      req.tmpl ? req.tlay.point : -1, req.tmpl ? req.tlay.point_present : 0u);
-        if (rc == VAG_OK) {
-            rc = finish_speculation(c);  // before a band group's own grid pass reuses the plan buffers
-            n_cap = std::max(n_cap, c->plan.n_models_capacity);
-            n_inv = std::max(n_inv, c->plan.n_models_invalid);
-        } else if (c->spec_pending) {  // an error while planning from stale sizes: repeat the call on the waiting path
-            if (vag_hook("VAG_DEBUG_SPEC")) std::fprintf(stderr, "[vag] planned-ahead likelihood call failed (%d: %s): repeating\n", rc, g_err.c_str());
-            c->spec_pending = false;
-            c->hint_valid = false;
-            rc = VAG_RETRY;
-        }
-    }
-    for (int g = 0; g < spec->n_bands && rc == VAG_OK; ++g) {  // band-integrated groups: one Model.flux request each (fitter.py:524-531)
-        const vag_band_obs& bd = spec->bands[g];
-        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(bd.n, n))) return VAG_E_HIP;
-        double* db = d + fl.band[g];  // [t | ln_flux | ln_err | weight]
-        begin_pass();
-        rc = band_request_dev(c, d_params, nb, db, bd.n, bd.nu_min, bd.nu_max, bd.num_points, c->d_series_flux.as<double>(), nullptr);
-        if (rc == VAG_OK)
-            rc = back(c->d_series_flux.as<double>(), bd.n, db + bd.n, db + 2 * (size_t)bd.n, db + 3 * (size_t)bd.n, nullptr,
-                      req.lim ? req.llay.band[g] : -1, req.noise ? req.nlay.band[g] : -1, req.noise ? req.nlay.band_present[g] : 0u,
-                      req.tmpl ? req.tlay.band[g] : -1, req.tmpl ? req.tlay.band_present[g] : 0u);
-    }
-    for (int g = 0; g < n_groups && rc == VAG_OK; ++g) {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
-        const vag_centroid_obs& o = sky->groups[g];
-        const double* ds = c->sky.d.as<double>() + req.slay.off[g];  // [nu | t | east | north | err_east | err_north | weight]
-        if (c->d_skycmom.ensure(sizeof(double) * (size_t)nb * o.n * 6)) return VAG_E_HIP;
-        rc = prep_times(c, ds + 1, o.n, ds, 1);
-        begin_pass();
-        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
-        if (rc == VAG_OK) rc = centroid_request(c, d_params, nb, o.n, 1, c->d_skycmom.as<double>());
-        if (rc == VAG_OK) {
-            hipLaunchKernelGGL(vag_fit_sky_back_kernel, dim3(nb), dim3(64), 0, st, c->d_skycmom.as<double>(), o.n, ds + 1, d_theta, ndim,
-                               d_prior, sky->pa_fixed, sky->east0_fixed, sky->north0_fixed, fit_pass());
-            rc = end_pass();
-        }
-    }
-    for (int g = 0; g < n_vis_groups && rc == VAG_OK; ++g) {  // visibility groups: one pass each, the chi^2 formed by the chi2 kernel
-        const vag_visibility_obs& o = req.vis->groups[g];
-        const VisLayout& lay = c->vis_layout[g];
-        const double* ds = c->vis.d.as<double>() + lay.obs_off;  // [nu | t | ...]
-        rc = prep_times(c, ds + 1, o.n_epochs, ds, 1);
-        begin_pass();
-        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
-        if (rc == VAG_OK) {
-            SkyVisFitArgs va{};
-            va.theta = d_theta;
-            va.prior = d_prior;
-            va.order = d_order;
-            va.ndim = ndim;
-            va.pa_fixed = sky ? sky->pa_fixed : 0.0;
-            va.east0_fixed = sky ? sky->east0_fixed : 0.0;
-            va.north0_fixed = sky ? sky->north0_fixed : 0.0;
-            rc = vis_chi2_request(c, d_params, nb, o, lay, va);
-        }
-        if (rc == VAG_OK) {
-            hipLaunchKernelGGL(vag_fit_vis_back_kernel, dim3(nb), dim3(64), 0, st, c->d_vispart.as<double>(), lay.epoch_blk[o.n_epochs],
-                               fit_pass());
-            rc = end_pass();
-        }
-    }
-    if (n_pol_groups > 0 && rc == VAG_OK) {  // the walkers' own field: once per call, in the evaluation order of d_params
-        if (c->d_polspec.ensure(sizeof(double) * 5 * (size_t)nb)) return VAG_E_HIP;  // [nb][4] spec | int [nb] flags
-        hipLaunchKernelGGL(vag_fit_pol_spec_kernel, dim3((nb + 127) / 128), dim3(128), 0, st, d_theta, nb, ndim, d_prior, d_params,
-                           req.pol->b_fixed[0], req.pol->b_fixed[1], req.pol->pi_max_fixed[0], req.pol->pi_max_fixed[1], d_order,
-                           c->d_polspec.as<double>(), reinterpret_cast<int*>(c->d_polspec.as<double>() + 4 * (size_t)nb));
-        HIPCHK(hipGetLastError());
-    }
-    for (int g = 0; g < n_pol_groups && rc == VAG_OK; ++g) {  // polarization groups: one pass each, the Stokes sums of sky_request
-        const vag_polarization_obs& o = req.pol->groups[g];
-        const double* ds = c->pol.d.as<double>() + req.play.off[g];  // [nu | t | q | u | err_q | err_u | weight]
-        if (c->d_polstokes.ensure(sizeof(double) * (size_t)nb * o.n * 3)) return VAG_E_HIP;
-        rc = prep_times(c, ds + 1, o.n, ds, 1);
-        begin_pass();
-        if (rc == VAG_OK) rc = run_model_stages(c, d_params, nb, false);
-        if (rc == VAG_OK)
-            rc = pol_stokes_request(c, d_params, nb, o.n, o.n_az > 0 ? o.n_az : 256, c->d_polspec.as<double>(), c->d_polstokes.as<double>());
-        if (rc == VAG_OK) {
-            const int* lk = (req.lim && req.llay.pol[g] >= 0) ? reinterpret_cast<const int*>(c->lim.d.as<double>() + req.llay.pol[g]) : nullptr;
-            const int* bad = reinterpret_cast<const int*>(c->d_polspec.as<double>() + 4 * (size_t)nb);
-            hipLaunchKernelGGL(lk ? vag_fit_pol_back_kernel<true> : vag_fit_pol_back_kernel<false>, dim3(nb), dim3(64), 0, st,
-                               c->d_polstokes.as<double>(), o.n, o.kind, ds + 1, bad, d_theta, ndim, d_prior, sky ? sky->pa_fixed : 0.0,
-                               fit_pass(), lk);
-            rc = end_pass();
-        }
-    }
-    for (int g = 0; g < n_counts_groups && rc == VAG_OK; ++g) {  // counts groups: one band request on the sample times each, then the Poisson term
-        const vag_counts_obs& o = req.counts->groups[g];
-        const double* dc = c->counts.d.as<double>() + req.clay.off[g];  // [t_sample | N | B | a | w | idx]
-        const size_t ns = (size_t)o.n_samples, nr = (size_t)o.n;
-        if (c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(ns, (size_t)std::max(n, 1)))) return VAG_E_HIP;
-        begin_pass();
-        // the band request takes two things from the batch's total work -- the number of (theta, phi) pairs per workgroup, and from
-        // 262144 pairs on, for bands of at most 4 nodes, the row-per-lane kernel -- so a band group's flux depends on the batch in its
-        // last bits; here both are pinned (COUNTS_PPB pairs, the workgroup kernel), and a walker's counts term is the same bits alone
-        // and in any batch whose lattices fit the staged row (512 nodes)
-        {
-            CallMode<int> pin(c->ppb_pin, COUNTS_PPB);
-            rc = band_request_dev(c, d_params, nb, dc, o.n_samples, o.nu_min, o.nu_max, o.num_points, c->d_series_flux.as<double>(), nullptr);
-        }
-        if (rc == VAG_OK) {
-            hipLaunchKernelGGL(vag_fit_back_counts_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n_samples, o.n, o.m,
-                               reinterpret_cast<const int*>(dc + ns + 4 * nr), dc + ns, dc + ns + nr, dc + ns + 2 * nr, dc + ns + 3 * nr,
-                               req.clay.const2[g], fit_pass(), next_order());
-            rc = end_pass();
-        }
-    }
-    for (int g = 0; g < n_index_groups && rc == VAG_OK; ++g) {  // spectral-index groups: the n K points as one series request each, then the slope term
-        const vag_index_obs& o = req.index->groups[g];
-        const double* di = c->index.d.as<double>() + req.ilay.off[g];  // [t n K | nu n K | s | sigma | w | c]
-        const size_t nr = (size_t)o.n, np = nr * (size_t)o.k;
-        double nu_pts[FITROWS_MAX_POINTS];  // K <= 8 distinct frequencies: the shared-node path of a short series
-        const bool is_short = np <= (size_t)FITROWS_MAX_POINTS;
-        for (size_t i = 0; is_short && i < np; ++i) nu_pts[i] = o.nu[i % (size_t)o.k];
-        if (series_group_flux(di, di + np, np, is_short ? nu_pts : nullptr)) return VAG_E_HIP;
-        if (rc == VAG_OK) {
-            hipLaunchKernelGGL(vag_fit_back_index_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, o.k,
-                               di + 2 * np, di + 2 * np + nr, di + 2 * np + 2 * nr, di + 2 * np + 3 * nr, o.ext_slope, d_av, fit_pass(),
-                               next_order());
-            rc = end_pass();
-        }
-    }
-    for (int g = 0; g < n_fold_groups && rc == VAG_OK; ++g) {  // fold groups: the n_samples J points as one series request each, then the folded Poisson term
-        const vag_fold_obs& o = req.fold->groups[g];
-        const double* df = c->fold.d.as<double>() + req.flay.off[g];  // [t ns J | nu ns J | A | sigma | exposure / m | N | B | w | idx]
-        const size_t J = (size_t)o.J, nc = (size_t)o.n * (size_t)o.C, np = (size_t)o.n_samples * J;
-        double nu_pts[FITROWS_MAX_POINTS];  // J <= 8 distinct frequencies: the shared-node path of a short series
-        const bool is_short = np <= (size_t)FITROWS_MAX_POINTS;
-        for (size_t i = 0; is_short && i < np; ++i) nu_pts[i] = o.nu[i % J];
-        if (series_group_flux(df, df + np, np, is_short ? nu_pts : nullptr)) return VAG_E_HIP;
-        if (rc == VAG_OK) {
-            const double* dA = df + 2 * np;
-            const double* dsig = dA + J * (size_t)o.C;
-            const double* deom = dsig + J;
-            const double* dN = deom + o.n;
-            hipLaunchKernelGGL(vag_fit_back_fold_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n_samples, o.J, o.C,
-                               o.n, o.m, reinterpret_cast<const int*>(dN + 3 * nc), dA, o.sigma ? dsig : nullptr, deom, dN, dN + nc,
-                               dN + 2 * nc, req.flay.const2[g], d_theta, ndim, d_prior, req.fold->n_h_fixed, fit_pass(), next_order());
-            rc = end_pass();
-        }
-    }
-    for (int g = 0; g < n_cov_groups && rc == VAG_OK; ++g) {  // correlated groups: the n rows as one series request each, then the whitened term
-        const vag_cov_obs& o = req.cov->groups[g];
-        const double* dv = c->cov.d.as<double>() + req.vlay.off[g];  // [t | nu | ln_flux | ext | Wt]
-        const size_t nr = (size_t)o.n;
-        // (n <= 256 points: the shared-node path of a short series when the rows hold <= 8 distinct frequencies)
-        if (series_group_flux(dv, dv + nr, nr, o.nu)) return VAG_E_HIP;
-        if (rc == VAG_OK) {
-            hipLaunchKernelGGL(vag_fit_back_cov_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, dv + 2 * nr,
-                               o.ext ? dv + 3 * nr : nullptr, dv + 4 * nr, o.weight, d_av, fit_pass(), next_order());
-            rc = end_pass();
+        if (r == VAG_OK) r = run_model_stages(c, d_params, nb, false);
+        return r;
+    };
+    // room in d_series_flux for a flux pass of np points per walker (never less than the point rows'); not 0: no memory
+    auto room_for_flux = [&](size_t np) { return c->d_series_flux.ensure(sizeof(double) * (size_t)nb * std::max(np, (size_t)std::max(n, 1))); };
+    for (; pass < passes.size() && rc == VAG_OK; ++pass) {  // (a failure ends the passes; what follows the loop still runs)
+        const int g = passes[pass].group;
+        switch (passes[pass].kind) {
+        case PassKind::Point: {  // point data: one (t, nu) series per walker (fitter.py:510-522)
+            if (room_for_flux(n)) return VAG_E_HIP;
+            begin_pass();
+            rc = run_model_stages(c, d_params, nb, false, try_spec);
+            if (rc == VAG_OK) rc = series_request(c, d_params, nb, n, c->d_series_flux.as<double>(), upload_series_bands(c, spec->nu, n));
+            if (rc == VAG_OK)
+                rc = back(c->d_series_flux.as<double>(), n, ln_flux, ln_err, weight, spec->ext_kernel ? ext : nullptr,
+                          req.lim ? req.llay.point : -1, req.noise ? req.nlay.point : -1, req.noise ? req.nlay.point_present : 0u,
+                          req.tmpl ? req.tlay.point : -1, req.tmpl ? req.tlay.point_present : 0u);
+            if (rc == VAG_OK) {
+                rc = finish_speculation(c);  // before a band group's own grid pass reuses the plan buffers
+                n_cap = std::max(n_cap, c->plan.n_models_capacity);
+                n_inv = std::max(n_inv, c->plan.n_models_invalid);
+            } else if (c->spec_pending) {  // an error while planning from stale sizes: repeat the call on the waiting path
+                if (vag_hook("VAG_DEBUG_SPEC"))
+                    std::fprintf(stderr, "[vag] planned-ahead likelihood call failed (%d: %s): repeating\n", rc, g_err.c_str());
+                c->spec_pending = false;
+                c->hint_valid = false;
+                rc = VAG_RETRY;
+            }
+        } break;
+        case PassKind::Band: {  // band-integrated groups: one Model.flux request each (fitter.py:524-531)
+            const vag_band_obs& bd = spec->bands[g];
+            if (room_for_flux(bd.n)) return VAG_E_HIP;
+            const double* db = d + fl.band[g];  // [t | ln_flux | ln_err | weight]
+            const BandCols k = band_cols(bd.n);
+            begin_pass();
+            rc = band_request_dev(c, d_params, nb, db, bd.n, bd.nu_min, bd.nu_max, bd.num_points, c->d_series_flux.as<double>(), nullptr);
+            if (rc == VAG_OK)
+                rc = back(c->d_series_flux.as<double>(), bd.n, db + k.ln_flux, db + k.ln_err, db + k.weight, nullptr,
+                          req.lim ? req.llay.band[g] : -1, req.noise ? req.nlay.band[g] : -1, req.noise ? req.nlay.band_present[g] : 0u,
+                          req.tmpl ? req.tlay.band[g] : -1, req.tmpl ? req.tlay.band_present[g] : 0u);
+        } break;
+        case PassKind::Centroid: {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
+            const vag_centroid_obs& o = sky->groups[g];
+            const double* ds = c->sky.d.as<double>() + req.slay.off[g];  // [nu | t | east | north | err_east | err_north | weight]
+            const SixCols k = six_cols(o.n);
+            if (c->d_skycmom.ensure(sizeof(double) * (size_t)nb * o.n * 6)) return VAG_E_HIP;
+            rc = sky_group_stages(ds, k.rows, o.n);
+            if (rc == VAG_OK) rc = centroid_request(c, d_params, nb, o.n, 1, c->d_skycmom.as<double>());
+            if (rc == VAG_OK) {
+                hipLaunchKernelGGL(vag_fit_sky_back_kernel, dim3(nb), dim3(64), 0, st, c->d_skycmom.as<double>(), o.n, ds + k.rows, d_theta,
+                                   ndim, d_prior, sky->pa_fixed, sky->east0_fixed, sky->north0_fixed, fit_pass());
+                rc = end_pass();
+            }
+        } break;
+        case PassKind::Vis: {  // visibility groups: one pass each, the chi^2 formed by the chi2 kernel
+            const vag_visibility_obs& o = req.vis->groups[g];
+            const VisLayout& lay = c->vis_layout[g];
+            const double* ds = c->vis.d.as<double>() + lay.obs_off;  // [nu | t | ...]
+            rc = sky_group_stages(ds, vis_cols(o).t, o.n_epochs);
+            if (rc == VAG_OK) {
+                SkyVisFitArgs va{};
+                va.theta = d_theta;
+                va.prior = d_prior;
+                va.order = d_order;
+                va.ndim = ndim;
+                va.pa_fixed = sky ? sky->pa_fixed : 0.0;
+                va.east0_fixed = sky ? sky->east0_fixed : 0.0;
+                va.north0_fixed = sky ? sky->north0_fixed : 0.0;
+                rc = vis_chi2_request(c, d_params, nb, o, lay, va);
+            }
+            if (rc == VAG_OK) {
+                hipLaunchKernelGGL(vag_fit_vis_back_kernel, dim3(nb), dim3(64), 0, st, c->d_vispart.as<double>(), lay.epoch_blk[o.n_epochs],
+                                   fit_pass());
+                rc = end_pass();
+            }
+        } break;
+        case PassKind::Pol: {  // polarization groups: one pass each, the Stokes sums of sky_request
+            if (g == 0) {  // the walkers' own field: once per call, in the evaluation order of d_params, before the first such pass
+                if (c->d_polspec.ensure(sizeof(double) * 5 * (size_t)nb)) return VAG_E_HIP;  // [nb][4] spec | int [nb] flags
+                hipLaunchKernelGGL(vag_fit_pol_spec_kernel, dim3((nb + 127) / 128), dim3(128), 0, st, d_theta, nb, ndim, d_prior, d_params,
+                                   req.pol->b_fixed[0], req.pol->b_fixed[1], req.pol->pi_max_fixed[0], req.pol->pi_max_fixed[1], d_order,
+                                   c->d_polspec.as<double>(), reinterpret_cast<int*>(c->d_polspec.as<double>() + 4 * (size_t)nb));
+                HIPCHK(hipGetLastError());
+            }
+            const vag_polarization_obs& o = req.pol->groups[g];
+            const double* ds = c->pol.d.as<double>() + req.play.off[g];  // [nu | t | q | u | err_q | err_u | weight]
+            const SixCols k = six_cols(o.n);
+            if (c->d_polstokes.ensure(sizeof(double) * (size_t)nb * o.n * 3)) return VAG_E_HIP;
+            rc = sky_group_stages(ds, k.rows, o.n);
+            if (rc == VAG_OK)
+                rc = pol_stokes_request(c, d_params, nb, o.n, o.n_az > 0 ? o.n_az : 256, c->d_polspec.as<double>(),
+                                        c->d_polstokes.as<double>());
+            if (rc == VAG_OK) {
+                const int* lk = (req.lim && req.llay.pol[g] >= 0) ? reinterpret_cast<const int*>(c->lim.d.as<double>() + req.llay.pol[g]) : nullptr;
+                const int* bad = reinterpret_cast<const int*>(c->d_polspec.as<double>() + 4 * (size_t)nb);
+                hipLaunchKernelGGL(lk ? vag_fit_pol_back_kernel<true> : vag_fit_pol_back_kernel<false>, dim3(nb), dim3(64), 0, st,
+                                   c->d_polstokes.as<double>(), o.n, o.kind, ds + k.rows, bad, d_theta, ndim, d_prior,
+                                   sky ? sky->pa_fixed : 0.0, fit_pass(), lk);
+                rc = end_pass();
+            }
+        } break;
+        case PassKind::Counts: {  // counts groups: one band request on the sample times each, then the Poisson term
+            const vag_counts_obs& o = req.counts->groups[g];
+            const double* dc = c->counts.d.as<double>() + req.clay.off[g];  // [t_sample | N | B | a | w | idx]
+            const CountsCols k = counts_cols(o);
+            if (room_for_flux((size_t)o.n_samples)) return VAG_E_HIP;
+            begin_pass();
+            // the band request takes two things from the batch's total work -- the number of (theta, phi) pairs per workgroup, and
+            // from 262144 pairs on, for bands of at most 4 nodes, the row-per-lane kernel -- so a band group's flux depends on the
+            // batch in its last bits; here both are pinned (COUNTS_PPB pairs, the workgroup kernel), and a walker's counts term is
+            // the same bits alone and in any batch whose lattices fit the staged row (512 nodes)
+            {
+                CallMode<int> pin(c->ppb_pin, COUNTS_PPB);
+                rc = band_request_dev(c, d_params, nb, dc, o.n_samples, o.nu_min, o.nu_max, o.num_points, c->d_series_flux.as<double>(),
+                                      nullptr);
+            }
+            if (rc == VAG_OK) {
+                hipLaunchKernelGGL(vag_fit_back_counts_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n_samples, o.n,
+                                   o.m, reinterpret_cast<const int*>(dc + k.idx), dc + k.N, dc + k.B, dc + k.a, dc + k.w, req.clay.const2[g],
+                                   fit_pass(), next_order());
+                rc = end_pass();
+            }
+        } break;
+        case PassKind::Index: {  // spectral-index groups: the n K points as one series request each, then the slope term
+            const vag_index_obs& o = req.index->groups[g];
+            const double* di = c->index.d.as<double>() + req.ilay.off[g];  // [t n K | nu n K | s | sigma | w | c]
+            const IndexCols k = index_cols(o);
+            const size_t np = k.nu;  // (n K points: the length of the t column)
+            double nu_pts[FITROWS_MAX_POINTS];  // K <= 8 distinct frequencies: the shared-node path of a short series
+            if (room_for_flux(np)) return VAG_E_HIP;
+            rc = series_group_flux(di, di + k.nu, np, short_series_nu(o.nu, (size_t)o.k, np, FITROWS_MAX_POINTS, nu_pts));
+            if (rc == VAG_OK) {
+                hipLaunchKernelGGL(vag_fit_back_index_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, o.k,
+                                   di + k.value, di + k.err, di + k.weight, di + k.coef, o.ext_slope, d_av, fit_pass(), next_order());
+                rc = end_pass();
+            }
+        } break;
+        case PassKind::Fold: {  // fold groups: the n_samples J points as one series request each, then the folded Poisson term
+            const vag_fold_obs& o = req.fold->groups[g];
+            const double* df = c->fold.d.as<double>() + req.flay.off[g];  // [t ns J | nu ns J | A | sigma | exposure / m | N | B | w | idx]
+            const FoldCols k = fold_cols(o);
+            const size_t np = k.nu;  // (n_samples J points: the length of the t column)
+            double nu_pts[FITROWS_MAX_POINTS];  // J <= 8 distinct frequencies: the shared-node path of a short series
+            if (room_for_flux(np)) return VAG_E_HIP;
+            rc = series_group_flux(df, df + k.nu, np, short_series_nu(o.nu, (size_t)o.J, np, FITROWS_MAX_POINTS, nu_pts));
+            if (rc == VAG_OK) {
+                hipLaunchKernelGGL(vag_fit_back_fold_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n_samples, o.J, o.C,
+                                   o.n, o.m, reinterpret_cast<const int*>(df + k.idx), df + k.A, o.sigma ? df + k.sigma : nullptr, df + k.eom,
+                                   df + k.N, df + k.B, df + k.w, req.flay.const2[g], d_theta, ndim, d_prior, req.fold->n_h_fixed, fit_pass(),
+                                   next_order());
+                rc = end_pass();
+            }
+        } break;
+        case PassKind::Cov: {  // correlated groups: the n rows as one series request each, then the whitened term
+            const vag_cov_obs& o = req.cov->groups[g];
+            const double* dv = c->cov.d.as<double>() + req.vlay.off[g];  // [t | nu | ln_flux | ext | Wt]
+            const CovCols k = cov_cols(o);
+            // (n <= 256 points: the shared-node path of a short series when the rows hold <= 8 distinct frequencies)
+            if (room_for_flux((size_t)o.n)) return VAG_E_HIP;
+            rc = series_group_flux(dv, dv + k.nu, (size_t)o.n, o.nu);
+            if (rc == VAG_OK) {
+                hipLaunchKernelGGL(vag_fit_back_cov_kernel, dim3(nb), dim3(64), 0, st, c->d_series_flux.as<double>(), o.n, dv + k.ln_flux,
+                                   o.ext ? dv + k.ext : nullptr, dv + k.Wt, o.weight, d_av, fit_pass(), next_order());
+                rc = end_pass();
+            }
+        } break;
         }
     }
     c->plan.n_models_capacity = n_cap;

@@ -53,11 +53,20 @@ static uint64_t hash_offsets(long point, const std::vector<long>& band) {
     return band.empty() ? h : fnv1a(h, band.data(), sizeof(long) * band.size());
 }
 
+// Block views.  Beside each layout below stands one *_cols function: the offsets of a group's columns, in doubles from the group's
+// start, and the group's length.  The scan or fill that writes the block and the pass that reads it (loglike_passes, vag_capi.hip)
+// both place every column through it; an int32 column is `(n + 1) / 2` doubles (ints_in).
+static size_t ints_in(size_t n) { return (n + 1) / 2; }
+static void put_doubles(double* dst, const double* src, size_t n) { std::memcpy(dst, src, sizeof(double) * n); }
+
 // ---- upper-limit rows (vag_loglike_lim_batch): the blocks that hold a limit row, in one device buffer, uploaded like the other spec
 //      blocks when the hash changes.  Layout in doubles: a flux block (the point rows, a band group) of n rows is
 //      [limit | sigma | kind] (n, n, int32 [n] in (n + 1) / 2 doubles), a polarization group's block [kind] alone (its L and sigma are
 //      the group's q and err_q in the pol block).  A block without a limit row is not stored (offset -1): its pass is the pass without
 //      limits.  Rows that are detections hold limit 0 and sigma 1, whatever the caller's arrays hold there. ----
+struct LimCols { size_t sigma, kind, doubles; };  // of a flux block of n rows (limit at 0)
+static LimCols lim_cols(int n) { return {(size_t)n, 2 * (size_t)n, 2 * (size_t)n + ints_in(n)}; }
+
 struct LimLayout : BlockKey {
     long point = -1;              // offset of the point rows' block in the lim block, or -1
     std::vector<long> band, pol;  // the same per band group / polarization group
@@ -66,7 +75,7 @@ struct LimLayout : BlockKey {
 
 static void lim_push_kinds(std::vector<double>& stage, const int32_t* kind, int n) {
     const size_t at = stage.size();
-    stage.resize(at + ((size_t)n + 1) / 2, 0.0);
+    stage.resize(at + ints_in(n), 0.0);
     std::memcpy(stage.data() + at, kind, sizeof(int32_t) * n);
 }
 
@@ -88,10 +97,15 @@ static int lim_flux_block(const vag_limit_rows& r, int n, const char* what, int 
     }
     if (!here) return VAG_OK;
     any = true;
+    const LimCols k = lim_cols(n);
     off = (long)stage.size();
-    for (int i = 0; i < n; ++i) stage.push_back(r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.limit[i] : 0.0);
-    for (int i = 0; i < n; ++i) stage.push_back(r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.sigma[i] : 1.0);
-    lim_push_kinds(stage, r.kind, n);
+    stage.resize(off + k.doubles, 0.0);
+    double* dst = stage.data() + off;
+    for (int i = 0; i < n; ++i) {
+        dst[i] = r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.limit[i] : 0.0;
+        dst[k.sigma + i] = r.kind[i] == VAG_OBS_UPPER_LIMIT ? r.sigma[i] : 1.0;
+    }
+    std::memcpy(dst + k.kind, r.kind, sizeof(int32_t) * n);
     return VAG_OK;
 }
 
@@ -283,6 +297,12 @@ static int tmpl_scan(const vag_fit_spec* spec, const vag_template_fit_spec* tp, 
 
 // ---- counts groups (vag_loglike_counts_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
 //      in doubles, per group: [t_sample ns | N n | B n | a n | w n], then the sample indices (int32 [n m] in (n m + 1) / 2 doubles). ----
+struct CountsCols { size_t N, B, a, w, idx, doubles; };  // (t_sample at 0)
+static CountsCols counts_cols(const vag_counts_obs& o) {
+    const size_t ns = (size_t)o.n_samples, n = (size_t)o.n;
+    return {ns, ns + n, ns + 2 * n, ns + 3 * n, ns + 4 * n, ns + 4 * n + ints_in(n * (size_t)o.m)};
+}
+
 struct CountsLayout : BlockKey {
     std::vector<long> off;       // where group g starts in the counts block
     std::vector<double> const2;  // -2 sum_i w_i S_i of group g (vag::poisson_const): the walker-independent half of its chi^2
@@ -330,18 +350,18 @@ static int counts_scan(const vag_counts_fit_spec* cs, std::vector<double>& stage
             }
             if (o.weight[i] > 0) wS += o.weight[i] * vag::poisson_const(N);
         }
-        const size_t at = stage.size(), n = (size_t)o.n, nm = n * (size_t)o.m;
+        const CountsCols k = counts_cols(o);
+        const size_t at = stage.size(), n = (size_t)o.n;
         lay.off.push_back((long)at);
         lay.const2.push_back(-2.0 * wS);
-        stage.resize(at + (size_t)o.n_samples + 4 * n + (nm + 1) / 2, 0.0);
+        stage.resize(at + k.doubles, 0.0);
         double* dst = stage.data() + at;
-        std::memcpy(dst, o.t_sample, sizeof(double) * o.n_samples);
-        dst += o.n_samples;
-        for (const double* src : {o.counts, o.background, o.scale, o.weight}) {
-            std::memcpy(dst, src, sizeof(double) * n);
-            dst += n;
-        }
-        std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
+        put_doubles(dst, o.t_sample, o.n_samples);
+        put_doubles(dst + k.N, o.counts, n);
+        put_doubles(dst + k.B, o.background, n);
+        put_doubles(dst + k.a, o.scale, n);
+        put_doubles(dst + k.w, o.weight, n);
+        std::memcpy(dst + k.idx, o.sample_idx, sizeof(int32_t) * n * o.m);
     }
     key_staged(lay, h, stage);
     return VAG_OK;
@@ -350,6 +370,12 @@ static int counts_scan(const vag_counts_fit_spec* cs, std::vector<double>& stage
 // ---- spectral-index groups (vag_loglike_index_batch): one device buffer, uploaded like the other spec blocks when the hash changes.
 //      Layout in doubles, per group: [t n K | nu n K | s n | sigma n | w n | c K]; the first two are the series points (t_i, nu_k), i
 //      outer, as prep_times takes them. ----
+struct IndexCols { size_t nu, value, err, weight, coef, doubles; };  // (t at 0; t and nu hold the n K series points)
+static IndexCols index_cols(const vag_index_obs& o) {
+    const size_t n = (size_t)o.n, K = (size_t)o.k, np = n * K;
+    return {np, 2 * np, 2 * np + n, 2 * np + 2 * n, 2 * np + 3 * n, 2 * np + 3 * n + K};
+}
+
 struct IndexLayout : BlockKey {
     std::vector<long> off;  // where group g starts in the index block
     int n_groups = 0;
@@ -386,21 +412,20 @@ static int index_scan(const vag_index_fit_spec* is, std::vector<double>& stage, 
             if (!std::isfinite(o.weight[i]) || o.weight[i] < 0)
                 return set_err(VAG_E_INVALID, "index group %d, row %d: the weight must be finite and >= 0", g, i);
         }
+        const IndexCols c = index_cols(o);
         const size_t at = stage.size(), n = (size_t)o.n, K = (size_t)o.k;
         lay.off.push_back((long)at);
-        stage.resize(at + 2 * n * K + 3 * n + K, 0.0);
+        stage.resize(at + c.doubles, 0.0);
         double* dst = stage.data() + at;
         for (size_t i = 0; i < n; ++i)
             for (size_t k = 0; k < K; ++k) {
                 dst[i * K + k] = o.t[i];
-                dst[n * K + i * K + k] = o.nu[k];
+                dst[c.nu + i * K + k] = o.nu[k];
             }
-        dst += 2 * n * K;
-        for (const double* src : {o.value, o.err, o.weight}) {
-            std::memcpy(dst, src, sizeof(double) * n);
-            dst += n;
-        }
-        std::memcpy(dst, o.coef, sizeof(double) * K);
+        put_doubles(dst + c.value, o.value, n);
+        put_doubles(dst + c.err, o.err, n);
+        put_doubles(dst + c.weight, o.weight, n);
+        put_doubles(dst + c.coef, o.coef, K);
     }
     key_staged(lay, h, stage);
     return VAG_OK;
@@ -410,6 +435,13 @@ static int index_scan(const vag_index_fit_spec* is, std::vector<double>& stage, 
 //      doubles, per group: [t ns J | nu ns J | A J C | sigma J | exposure / m n | N n C | B n C | w n C], then the sample indices
 //      (int32 [n m] in (n m + 1) / 2 doubles); the first two are the series points (t_sample_s, nu_j), s outer, as prep_times takes
 //      them; sigma is zeros for a group without one (the kernel is handed a null pointer then). ----
+struct FoldCols { size_t nu, A, sigma, eom, N, B, w, idx, doubles; };  // (t at 0; t and nu hold the n_samples J series points)
+static FoldCols fold_cols(const vag_fold_obs& o) {
+    const size_t J = (size_t)o.J, n = (size_t)o.n, nc = n * (size_t)o.C, np = (size_t)o.n_samples * J;
+    const size_t sigma = 2 * np + J * (size_t)o.C, N = sigma + J + n, idx = N + 3 * nc;
+    return {np, 2 * np, sigma, sigma + J, N, N + nc, N + 2 * nc, idx, idx + ints_in(n * (size_t)o.m)};
+}
+
 struct FoldLayout : BlockKey {
     std::vector<long> off;       // where group g starts in the fold block
     std::vector<double> const2;  // -2 sum_{i,c} w S of group g (vag::poisson_const): the walker-independent half of its chi^2
@@ -479,28 +511,24 @@ static int fold_scan(const vag_fit_spec* spec, const vag_fold_fit_spec* fs, std:
             }
         }
         if (o.sigma) lay.any_sigma = true;
-        const size_t at = stage.size(), J = (size_t)o.J, C = (size_t)o.C, n = (size_t)o.n, ns = (size_t)o.n_samples, nm = n * (size_t)o.m;
+        const FoldCols k = fold_cols(o);
+        const size_t at = stage.size(), J = (size_t)o.J, C = (size_t)o.C, n = (size_t)o.n, ns = (size_t)o.n_samples;
         lay.off.push_back((long)at);
         lay.const2.push_back(-2.0 * wS);
-        stage.resize(at + 2 * ns * J + J * C + J + n + 3 * n * C + (nm + 1) / 2, 0.0);
+        stage.resize(at + k.doubles, 0.0);
         double* dst = stage.data() + at;
         for (size_t q = 0; q < ns; ++q)
             for (size_t j = 0; j < J; ++j) {
                 dst[q * J + j] = o.t_sample[q];
-                dst[ns * J + q * J + j] = o.nu[j];
+                dst[k.nu + q * J + j] = o.nu[j];
             }
-        dst += 2 * ns * J;
-        std::memcpy(dst, o.A, sizeof(double) * J * C);
-        dst += J * C;
-        if (o.sigma) std::memcpy(dst, o.sigma, sizeof(double) * J);
-        dst += J;
-        std::memcpy(dst, o.exposure_over_m, sizeof(double) * n);
-        dst += n;
-        for (const double* src : {o.counts, o.background, o.weight}) {
-            std::memcpy(dst, src, sizeof(double) * n * C);
-            dst += n * C;
-        }
-        std::memcpy(dst, o.sample_idx, sizeof(int32_t) * nm);
+        put_doubles(dst + k.A, o.A, J * C);
+        if (o.sigma) put_doubles(dst + k.sigma, o.sigma, J);
+        put_doubles(dst + k.eom, o.exposure_over_m, n);
+        put_doubles(dst + k.N, o.counts, n * C);
+        put_doubles(dst + k.B, o.background, n * C);
+        put_doubles(dst + k.w, o.weight, n * C);
+        std::memcpy(dst + k.idx, o.sample_idx, sizeof(int32_t) * n * o.m);
     }
     // (N_H is read by groups with a cross-section only: without one it is refused as a free parameter, the rule of east0 / north0)
     if (!lay.any_sigma)
@@ -514,6 +542,12 @@ static int fold_scan(const vag_fit_spec* spec, const vag_fold_fit_spec* fs, std:
 //      in doubles, per group: [t n | nu n | ln_flux n | ext n | Wt n n]; the first two are the series points as prep_times takes
 //      them; ext is zeros for a group without one (the kernel is handed a null pointer then); Wt[j n + i] = W_ij for j <= i, else 0:
 //      the whitener transposed, so that a wavefront whose lanes hold consecutive rows i loads consecutive doubles. ----
+struct CovCols { size_t nu, ln_flux, ext, Wt, doubles; };  // (t at 0)
+static CovCols cov_cols(const vag_cov_obs& o) {
+    const size_t n = (size_t)o.n;
+    return {n, 2 * n, 3 * n, 4 * n, 4 * n + n * n};
+}
+
 struct CovLayout : BlockKey {
     std::vector<long> off;  // where group g starts in the cov block
     int n_groups = 0;
@@ -551,15 +585,16 @@ static int cov_scan(const vag_cov_fit_spec* cs, std::vector<double>& stage, CovL
             if (!(o.whitener[i * n + i] > 0))
                 return set_err(VAG_E_INVALID, "correlated group %d, row %d: the whitener's diagonal entry must be > 0", g, i);
         }
+        const CovCols k = cov_cols(o);
         const size_t at = stage.size();
         lay.off.push_back((long)at);
-        stage.resize(at + 4 * n + n * n, 0.0);
+        stage.resize(at + k.doubles, 0.0);
         double* dst = stage.data() + at;
-        std::memcpy(dst, o.t, sizeof(double) * n);
-        std::memcpy(dst + n, o.nu, sizeof(double) * n);
-        std::memcpy(dst + 2 * n, o.ln_flux, sizeof(double) * n);
-        if (o.ext) std::memcpy(dst + 3 * n, o.ext, sizeof(double) * n);
-        double* Wt = dst + 4 * n;
+        put_doubles(dst, o.t, n);
+        put_doubles(dst + k.nu, o.nu, n);
+        put_doubles(dst + k.ln_flux, o.ln_flux, n);
+        if (o.ext) put_doubles(dst + k.ext, o.ext, n);
+        double* Wt = dst + k.Wt;
         for (size_t i = 0; i < n; ++i)
             for (size_t j = 0; j <= i; ++j) Wt[j * n + i] = o.whitener[i * n + j];
     }
@@ -571,6 +606,9 @@ static int cov_scan(const vag_cov_fit_spec* cs, std::vector<double>& stage, CovL
 //      doubles: [t | nu | ln_flux | ln_err | weight | ext] (n each, in 6 max(n, 1); ext is zeros without an ext_kernel), then per band
 //      group [t | ln_flux | ln_err | weight] (bd.n each), then [lower | upper | prior_a | prior_b] (16 each), then int32
 //      [slot | is_log | prior_kind] (16 each). ----
+struct BandCols { size_t ln_flux, ln_err, weight, doubles; };  // of a band group of n rows (t at 0)
+static BandCols band_cols(int n) { return {(size_t)n, 2 * (size_t)n, 3 * (size_t)n, 4 * (size_t)n}; }
+
 struct FitLayout : BlockKey {
     size_t nu = 0, ln_flux = 0, ln_err = 0, weight = 0, ext = 0;  // the point rows' columns (t is at 0)
     std::vector<size_t> band;                                     // where band group g starts
@@ -623,7 +661,7 @@ static int fit_scan(const vag_fit_spec* spec, int ndim, const FitAccepts& acc, F
         h = fnv1a(h, &bd.n, sizeof bd.n);
         for (const double* arr : {bd.t, bd.ln_flux, bd.ln_err, bd.weight}) h = fnv1a(h, arr, sizeof(double) * bd.n);
         lay.band.push_back(total);
-        total += 4 * (size_t)bd.n;
+        total += band_cols(bd.n).doubles;
     }
     h = fnv1a(h, spec->slot, sizeof spec->slot);
     h = fnv1a(h, spec->is_log, sizeof spec->is_log);
@@ -662,8 +700,12 @@ static void fit_fill(const vag_fit_spec* spec, const FitLayout& lay, double* hp)
         if (src[q]) std::memcpy(hp + at[q], src[q], sizeof(double) * n);
     for (int g = 0; g < spec->n_bands; ++g) {
         const vag_band_obs& bd = spec->bands[g];
-        const double* col[4] = {bd.t, bd.ln_flux, bd.ln_err, bd.weight};
-        for (int q = 0; q < 4; ++q) std::memcpy(hp + lay.band[g] + (size_t)q * bd.n, col[q], sizeof(double) * bd.n);
+        const BandCols k = band_cols(bd.n);
+        double* dst = hp + lay.band[g];
+        put_doubles(dst, bd.t, bd.n);
+        put_doubles(dst + k.ln_flux, bd.ln_flux, bd.n);
+        put_doubles(dst + k.ln_err, bd.ln_err, bd.n);
+        put_doubles(dst + k.weight, bd.weight, bd.n);
     }
     const double* pd[4] = {spec->lower, spec->upper, spec->prior_a, spec->prior_b};
     for (int q = 0; q < 4; ++q) std::memcpy(hp + lay.prior + 16 * q, pd[q], sizeof spec->lower);
@@ -679,12 +721,18 @@ struct SixGroup {  // one such group; a null array is stored as zeros
     int n;
     const double* col[6];
 };
-static void six_cols(const double* const col[6], size_t n, double* dst) {  // n doubles of each array, zeros for a null one
-    for (int q = 0; q < 6; ++q, dst += n) {
+struct SixCols { size_t rows, col[6], doubles; };  // rows: the `+ 1` past nu, where the six arrays start (col[0], the times)
+static SixCols six_cols(int n, size_t rows = 1) {  // (rows: 1 behind nu; a visibility group's arrays lie behind its epochs' times)
+    SixCols k{rows, {}, rows + 6 * (size_t)n};
+    for (int q = 0; q < 6; ++q) k.col[q] = rows + (size_t)q * n;
+    return k;
+}
+static void six_put(const double* const col[6], size_t n, const SixCols& k, double* dst) {  // n doubles of each array, zeros for a null one
+    for (int q = 0; q < 6; ++q) {
         if (col[q])
-            std::memcpy(dst, col[q], sizeof(double) * n);
+            put_doubles(dst + k.col[q], col[q], n);
         else
-            std::memset(dst, 0, sizeof(double) * n);
+            std::memset(dst + k.col[q], 0, sizeof(double) * n);
     }
 }
 static SixGroup six_group(const vag_centroid_obs& o) { return {o.nu, o.n, {o.t, o.east, o.north, o.err_east, o.err_north, o.weight}}; }
@@ -704,14 +752,14 @@ static void six_push(SixLayout& lay, const SixGroup& g, const int* head, size_t 
     for (const double* arr : g.col)
         if (arr) lay.hash = fnv1a(lay.hash, arr, sizeof(double) * g.n);
     lay.off.push_back(lay.doubles);
-    lay.doubles += 1 + 6 * (size_t)g.n;
+    lay.doubles += six_cols(g.n).doubles;
 }
 template <class Spec>
 static void six_fill(const Spec* s, const SixLayout& lay, double* hp) {
     for (int g = 0; g < s->n_groups; ++g) {
         const SixGroup o = six_group(s->groups[g]);
         hp[lay.off[g]] = o.nu;
-        six_cols(o.col, o.n, hp + lay.off[g] + 1);
+        six_put(o.col, o.n, six_cols(o.n), hp + lay.off[g]);
     }
 }
 
@@ -785,6 +833,12 @@ static int pol_rows(const vag_pol_fit_spec* pol) {
 // ---- visibility groups (vag_loglike_vis_batch): one device buffer.  Layout in doubles, per group: [nu | t | u | v | re | im | err |
 //      weight] (1 + n_epochs + 6 n_vis), im of an AMPLITUDE group zeros; beside it, per group, the blocks of at most 64 visibilities of
 //      one epoch as int32 [epoch, first visibility, visibilities] (d_visblk). ----
+struct VisCols { size_t t, six, doubles; };  // t: the `+ 1` past nu; six: where [u | v | re | im | err | weight] (n_vis each) start
+static VisCols vis_cols(const vag_visibility_obs& o) {
+    const size_t six = 1 + (size_t)o.n_epochs;
+    return {1, six, six_cols(o.n_vis, six).doubles};
+}
+
 struct VisLayout {               // of one group; made on a miss, from the validated first[]
     size_t obs_off;              // its data in the vis block [doubles]
     int blk_off;                 // its blocks in d_visblk [blocks of 3 ints]
@@ -810,7 +864,7 @@ static int vis_scan(const vag_vis_fit_spec* vis, BlockKey& key) {
         h = fnv1a(h, o.first, sizeof(int32_t) * ((size_t)o.n_epochs + 1));
         for (const double* arr : {o.u, o.v, o.re, o.kind == VAG_VIS_COMPLEX ? o.im : nullptr, o.err, o.weight})
             if (arr) h = fnv1a(h, arr, sizeof(double) * o.n_vis);
-        key.doubles += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
+        key.doubles += vis_cols(o).doubles;
     }
     return VAG_OK;
 }
@@ -828,7 +882,7 @@ static int vis_rows(const vag_vis_fit_spec* vis, std::vector<VisLayout>& layout,
         VisLayout& lay = layout[g];
         lay.obs_off = off;
         lay.blk_off = (int)(blocks.size() / 3);
-        off += 1 + (size_t)o.n_epochs + 6 * (size_t)o.n_vis;
+        off += vis_cols(o).doubles;
         for (int e = 0; e < o.n_epochs; ++e) {
             if (!(o.t[e] > 0) || !std::isfinite(o.t[e]) || (e > 0 && !(o.t[e] > o.t[e - 1])))
                 return set_err(VAG_E_INVALID, "visibility group %d: times must be positive and strictly ascending", g);
@@ -854,10 +908,11 @@ static void vis_fill(const vag_vis_fit_spec* vis, const std::vector<VisLayout>& 
     for (int g = 0; g < vis->n_groups; ++g) {
         const vag_visibility_obs& o = vis->groups[g];
         const double* col[6] = {o.u, o.v, o.re, o.kind == VAG_VIS_COMPLEX ? o.im : nullptr, o.err, o.weight};
+        const VisCols k = vis_cols(o);
         double* dst = hp + layout[g].obs_off;
-        *dst++ = o.nu;
-        std::memcpy(dst, o.t, sizeof(double) * o.n_epochs);
-        six_cols(col, o.n_vis, dst + o.n_epochs);
+        dst[0] = o.nu;
+        put_doubles(dst + k.t, o.t, o.n_epochs);
+        six_put(col, o.n_vis, six_cols(o.n_vis, k.six), dst);
     }
 }
 
@@ -922,6 +977,31 @@ static int fit_request_prepare(FitRequest& r) {
     if (!r.pol && !r.placed) r.sky = nullptr;  // nothing reads the placement
     r.prepared = true;
     return VAG_OK;
+}
+
+// The passes of a prepared request, in the order they run: the point rows, then every group of each list.  Each adds one chi^2 term
+// per walker; position 0 is the call's first pass (FitPass::first), the final position its last, which writes the call's output.
+enum class PassKind { Point, Band, Centroid, Vis, Pol, Counts, Index, Fold, Cov };
+struct PassItem { PassKind kind; int group; };
+static std::vector<PassItem> fit_pass_list(const FitRequest& r) {
+    std::vector<PassItem> list;
+    if (r.spec->n_data > 0) list.push_back({PassKind::Point, 0});
+    const struct { PassKind kind; int n; } lists[8] = {
+        {PassKind::Band, r.spec->n_bands},   {PassKind::Centroid, r.sky ? r.sky->n_groups : 0}, {PassKind::Vis, r.vis ? r.vis->n_groups : 0},
+        {PassKind::Pol, r.pol ? r.pol->n_groups : 0}, {PassKind::Counts, r.counts ? r.counts->n_groups : 0},
+        {PassKind::Index, r.index ? r.index->n_groups : 0}, {PassKind::Fold, r.fold ? r.fold->n_groups : 0},
+        {PassKind::Cov, r.cov ? r.cov->n_groups : 0}};
+    for (const auto& l : lists)
+        for (int g = 0; g < l.n; ++g) list.push_back({l.kind, g});
+    return list;
+}
+
+// The frequencies of the np points of an index or fold group on the host (point i at nu[i % K], as its scan lays them out), for the
+// shared-node test of a short series: written to nu_pts [max_points] and handed back, or null for a series above max_points.
+static const double* short_series_nu(const double* nu, size_t K, size_t np, size_t max_points, double* nu_pts) {
+    if (np > max_points) return nullptr;
+    for (size_t i = 0; i < np; ++i) nu_pts[i] = nu[i % K];
+    return nu_pts;
 }
 
 static FitAccepts fit_accepts(const FitRequest& r) {
