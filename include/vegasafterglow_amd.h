@@ -358,6 +358,9 @@ enum {
     VAG_MATH_IC_STEP, /* one pass of the bodies of the gamma_c and gamma_M fixed points */
     VAG_MATH_IC_FIXED_POINT, /* ic_gamma_c_cell and ic_gamma_M: the loops vag_ic_cooling_kernel and vag_photons_ic_kernel run */
     VAG_MATH_IC_GAMMA_A, /* syn_gamma_a_ic and determine_regime */
+    /* the split flux kernel's instruction forms of exp2_fast and sp_fast<true> (vag_device.h: exp2_fast_as, sp_fast with its magic number in
+     * a vector register) and sp_fast<true> itself; one argument, one result each, on the domains of exp2_fast and sp_fast */
+    VAG_MATH_EXP2_FAST_CHAIN, VAG_MATH_SP_FAST_RELU, VAG_MATH_SP_FAST_RELU_VMAGIC,
     VAG_MATH_COUNT
 };
 int vag_debug_device_math(vag_ctx* ctx, int fn, const double* in, int n, double* out);

@@ -61,7 +61,8 @@ MATH_MORE = {name: len(MATH) + i for i, name in enumerate([
     "poisson_deviance", "log_slope", "elec_cell", "fwd_state",
     "rel_gamma", "shock_jump", "sound_speed", "rvs_state", "cross_lattice", "rvs_extrap", "pair_init",
     "kn_lut", "kn_corr", "ic_table", "ic_bin_integral", "ic_suffix_scan", "ic_column_den",
-    "ic_y", "ic_step", "ic_fixed_point", "ic_gamma_a"])}
+    "ic_y", "ic_step", "ic_fixed_point", "ic_gamma_a",
+    "exp2_fast_chain", "sp_fast_relu", "sp_fast_relu_vmagic"])}
 # [n_in, n_out] per point of the routines of MATH_MORE that tests/_rsref.py restates (vag_debug_math.h)
 MATH_RS_SHAPES = {"rel_gamma": (2, 2), "shock_jump": (2, 3), "sound_speed": (1, 2), "rvs_state": (14, 6), "cross_lattice": (7, 4),
                   "rvs_extrap": (65, 48), "pair_init": (10, 11)}

@@ -403,6 +403,14 @@ __global__ void __launch_bounds__(64) vag_math_probe_kernel(int fn, int n, const
         case VAG_MATH_SP_FAST_GLOBAL: y = sp_fast(x, sp_table); break;
         case VAG_MATH_SP_FAST_SEL: y = sp_fast_sel(x, sp); break;
         case VAG_MATH_LOG_NDTR: y = log_ndtr(x); break;
+        case VAG_MATH_EXP2_FAST_CHAIN: y = exp2_fast_as<EXP2_HEAD | EXP2_CHAIN>(x); break;
+        case VAG_MATH_SP_FAST_RELU: y = sp_fast<true>(x, sp); break;
+        case VAG_MATH_SP_FAST_RELU_VMAGIC: {  // the magic number opaque in a vector register, as flux_split_item holds it
+            double magic = SP_MAGIC;
+            asm volatile("" : "+v"(magic));
+            y = sp_fast<true>(x, sp, magic);
+            break;
+        }
         default: return;
     }
     out[i] = y;

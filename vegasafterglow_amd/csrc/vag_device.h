@@ -1021,8 +1021,11 @@ VAG_DEV double relu_f64(double z) {
 // region per side: one more vector instruction where a whole wavefront takes the table side, three mask instructions and a branch
 // fewer in every call, and the table side ends in r + p (an instruction fewer than the plain form's fma(0.5, z + |z|, p)).  Same
 // value per lane.  On for the split flux kernel's boundary team (profiles/flux_prefetch_ab.txt, profiles/flux_header_ab.txt).
+// `magic`: SP_MAGIC, or a register copy of it that the caller keeps opaque.  Both SP_PER_UNIT and SP_MAGIC are constants in scalar
+// registers, an instruction reads one scalar operand, and so the first FMA below costs a register copy of SP_MAGIC per call; with
+// the magic number in a vector register the table side is v_fma t, v_add n, v_fma tau (split flux kernel).
 template <bool RELU_FIRST = false, class Tab>
-VAG_DEV double sp_fast(double z, Tab tab) {
+VAG_DEV double sp_fast(double z, Tab tab, double magic = SP_MAGIC) {
     const double a = fabs(z);
 #ifndef VAG_SP_BRANCHLESS
     [[maybe_unused]] double r = 0;  // max(z, 0), RELU_FIRST only
@@ -1033,9 +1036,9 @@ VAG_DEV double sp_fast(double z, Tab tab) {
         if (a > 20.0) return relu_f64(z);
     }
 #endif
-    const double t = fma(a, (double)SP_PER_UNIT, SP_MAGIC);  // nearest node: integer in the low mantissa word
+    const double t = fma(a, (double)SP_PER_UNIT, magic);  // nearest node: integer in the low mantissa word
     const int idx = (int)min((unsigned)__double2loint(t), (unsigned)(SP_INTERVALS - 1));  // the clamp only acts on NaN
-    const double tau = fma(a, (double)SP_PER_UNIT, -(t - SP_MAGIC));  // in [-1/2, 1/2]
+    const double tau = fma(a, (double)SP_PER_UNIT, -(t - magic));  // in [-1/2, 1/2]
     const auto c2 = sp_row(tab, idx);
     const vdouble2 c01 = c2[0], c23 = c2[1], c45 = c2[2];
     double p = fma(c45.y, tau, c45.x);
@@ -1105,6 +1108,10 @@ VAG_DEV double fma3(double a, double b, double c) {
     return r;
 }
 #endif
+// minimax q of degree 10 for (2^f - 1) / f on [-1/2, 1/2], lowest power first (exp2_fast's Horner chain below)
+constexpr double EXP2_Q[11] = {0.6931471805599453,     0.24022650695910097,    0.05550410866482166,    0.009618129107606887,
+                               0.0013333558146396002,  0.00015403530441738514, 1.5252733853282354e-05, 1.321544258661287e-06,
+                               1.0178051727399186e-07, 7.072586181346367e-09,  4.4566755710138823e-10};
 VAG_DEV double exp2_fast(double x) {  // finite x only: +-inf would give inf - inf in the range reduction (see exp2_sat)
     const double n = rint(x);
     const double f = x - n;
@@ -1123,19 +1130,61 @@ VAG_DEV double exp2_fast(double x) {  // finite x only: +-inf would give inf - i
     // minimax q of degree 10 for (2^f - 1) / f on [-1/2, 1/2] (profiles/micro/exp2_minimax.py: Remez in 60-digit arithmetic;
     // the rounded Horner form is within 2.1e-16 of 2^f, the degree-12 Taylor form it replaces -- exp2_ode's -- is at 3.7e-16 with one
     // step more; tests/test_device_math.py)
-    double p = fma(4.4566755710138823e-10, f, 7.072586181346367e-09);
-    p = fma3(p, f, 1.0178051727399186e-07);
-    p = fma3(p, f, 1.321544258661287e-06);
-    p = fma3(p, f, 1.5252733853282354e-05);
-    p = fma3(p, f, 0.00015403530441738514);
-    p = fma3(p, f, 0.0013333558146396002);
-    p = fma3(p, f, 0.009618129107606887);
-    p = fma3(p, f, 0.05550410866482166);
-    p = fma3(p, f, 0.24022650695910097);
-    p = fma3(p, f, 0.6931471805599453);
+    double p = fma(EXP2_Q[10], f, EXP2_Q[9]);
+    p = fma3(p, f, EXP2_Q[8]);
+    p = fma3(p, f, EXP2_Q[7]);
+    p = fma3(p, f, EXP2_Q[6]);
+    p = fma3(p, f, EXP2_Q[5]);
+    p = fma3(p, f, EXP2_Q[4]);
+    p = fma3(p, f, EXP2_Q[3]);
+    p = fma3(p, f, EXP2_Q[2]);
+    p = fma3(p, f, EXP2_Q[1]);
+    p = fma3(p, f, EXP2_Q[0]);
     p = fma(p, f, 1.0);
 #endif
     return ldexp(p, (int)n);
+}
+
+// exp2_fast with its Horner chain in other instruction forms, for a kernel that pays per issued instruction (the split flux kernel,
+// DESIGN 4g item 14).  The same eleven FMAs with the same operands in the same order: the bits of exp2_fast
+// (tests/test_device_math_chains.py).
+//   EXP2_HEAD   the first step fma(Q10, f, Q9) as ONE v_fma_f64 (scalar multiplier, vector addend); the compiler's own form is a
+//               register copy of Q9 plus the two-address v_fmac_f64.
+//   EXP2_CHAIN  the nine scalar-addend steps as ONE asm statement instead of nine.  After an asm statement the compiler cannot see
+//               what kind of write produced the result, and where the next instruction reads it, it keeps one wait state (s_nop 0)
+//               for the partial-register writes that need one.  A v_fma_f64 needs none -- the hardware interlocks dependent VALU
+//               instructions -- and inside one statement nothing is inserted.
+constexpr int EXP2_HEAD = 1, EXP2_CHAIN = 2;
+#define VAG_FMA_STEP(p, f, c) "v_fma_f64 " p ", " p ", " f ", " c "\n\t"
+template <int FORM>
+VAG_DEV double exp2_horner(double f) {
+#ifdef VAG_HOST_DEBUG
+    double p = fma(EXP2_Q[10], f, EXP2_Q[9]);
+    for (int i = 8; i >= 0; --i) p = fma(p, f, EXP2_Q[i]);
+#else
+    double p;
+    if constexpr ((FORM & EXP2_HEAD) != 0)
+        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p) : "s"(EXP2_Q[10]), "v"(f), "v"(EXP2_Q[9]));
+    else
+        p = fma(EXP2_Q[10], f, EXP2_Q[9]);
+    if constexpr ((FORM & EXP2_CHAIN) != 0) {
+        asm(VAG_FMA_STEP("%0", "%1", "%2") VAG_FMA_STEP("%0", "%1", "%3") VAG_FMA_STEP("%0", "%1", "%4") VAG_FMA_STEP("%0", "%1", "%5")
+            VAG_FMA_STEP("%0", "%1", "%6") VAG_FMA_STEP("%0", "%1", "%7") VAG_FMA_STEP("%0", "%1", "%8") VAG_FMA_STEP("%0", "%1", "%9")
+            "v_fma_f64 %0, %0, %1, %10"
+            : "+v"(p)
+            : "v"(f), "s"(EXP2_Q[8]), "s"(EXP2_Q[7]), "s"(EXP2_Q[6]), "s"(EXP2_Q[5]), "s"(EXP2_Q[4]), "s"(EXP2_Q[3]), "s"(EXP2_Q[2]),
+              "s"(EXP2_Q[1]), "s"(EXP2_Q[0]));
+    } else {
+#pragma unroll
+        for (int i = 8; i >= 0; --i) p = fma3(p, f, EXP2_Q[i]);
+    }
+#endif
+    return fma(p, f, 1.0);
+}
+template <int FORM>
+VAG_DEV double exp2_fast_as(double x) {  // finite x only, like exp2_fast
+    const double n = rint(x);
+    return ldexp(exp2_horner<FORM>(x - n), (int)n);
 }
 
 // exp2_fast(isfinite(x) ? x : -2000.0) of the flux interpolation for x finite, -inf or NaN (a slope that is not finite): the select
@@ -1244,23 +1293,37 @@ VAG_DEV void lds_add_f64(double* p, double v) {
 // SAB (thin - lb) <= SAB (thin - th): where the right side is < -20 the blend's softplus returns exactly 0 for either lb, and the
 // result has the bits of the full path.  NaN compares false and takes the full path.
 // RELU_FIRST: the softplus terms in sp_fast's form of that name (same bits).
-template <bool THICK_BOUND = false, bool RELU_FIRST = false, class PtrT, class Tab>
-VAG_DEV double log2_I_nu_fast(const PtrT& c, int st, const SpecConst& sc, double lg2_nu, Tab sp) {
+// EXP2_FORM, LB_FMA, sp_magic: instruction forms for the split flux kernel, same bits: the two exponentials as
+// exp2_fast_as<EXP2_FORM>, the thick branch's fma(2.5, lg2_nu, VP_TB) as ONE v_fma_f64 with 2.5 in a scalar pair (the compiler's form
+// is a register copy plus v_fmac_f64), and sp_fast's magic number from the caller's vector register.
+template <bool THICK_BOUND = false, bool RELU_FIRST = false, int EXP2_FORM = 0, bool LB_FMA = false, class PtrT, class Tab>
+VAG_DEV double log2_I_nu_fast(const PtrT& c, int st, const SpecConst& sc, double lg2_nu, Tab sp, double sp_magic = SP_MAGIC) {
+    auto exp2_ = [](double x) {
+        if constexpr (EXP2_FORM != 0) return exp2_fast_as<EXP2_FORM>(x);
+        else return exp2_fast(x);
+    };
     const double l_lo = c[VP_LG2_LO * st];
-    const double thin = (lg2_nu - l_lo) * (1.0 / 3.0) - sp_fast<RELU_FIRST>(c[VP_DLO * st] * (lg2_nu - l_lo), sp) * c[VP_INV_SLO * st] -
-                        sp_fast<RELU_FIRST>(fma(c[VP_DHI * st], lg2_nu, c[VP_BHI * st]), sp) * c[VP_INV_SHI * st];
+    const double thin = (lg2_nu - l_lo) * (1.0 / 3.0) - sp_fast<RELU_FIRST>(c[VP_DLO * st] * (lg2_nu - l_lo), sp, sp_magic) * c[VP_INV_SLO * st] -
+                        sp_fast<RELU_FIRST>(fma(c[VP_DHI * st], lg2_nu, c[VP_BHI * st]), sp, sp_magic) * c[VP_INV_SHI * st];
     const double lx = lg2_nu - c[VP_LG2_NUM * st];
-    double lb = fma(2.5, lg2_nu, c[VP_TB * st]);  // thick branch 2.5 lx + log2_thick_norm_
+    double lb;  // thick branch 2.5 lx + log2_thick_norm_
+#ifndef VAG_HOST_DEBUG
+    if constexpr (LB_FMA) {
+        const double tb = c[VP_TB * st];
+        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(lb) : "s"(2.5), "v"(lg2_nu), "v"(tb));
+    } else
+#endif
+        lb = fma(2.5, lg2_nu, c[VP_TB * st]);
     if (!(lx > sc.log2_x_far)) {
         if (!THICK_BOUND || !(c[VP_SAB * st] * (thin - lb) < -20.0 && c[VP_SAB * st] > 0)) {
-            const double s = -sc.smooth_thick * exp2_fast(2. / 3 * lx);
-            lb += sp_fast<RELU_FIRST>(-0.5 * lx + s, sp);
+            const double s = -sc.smooth_thick * exp2_(2. / 3 * lx);
+            lb += sp_fast<RELU_FIRST>(-0.5 * lx + s, sp, sp_magic);
         }
     }
-    const double smooth_one = thin - sp_fast<RELU_FIRST>(c[VP_SAB * st] * (thin - lb), sp) * c[VP_INV_SAB * st];
+    const double smooth_one = thin - sp_fast<RELU_FIRST>(c[VP_SAB * st] * (thin - lb), sp, sp_magic) * c[VP_INV_SAB * st];
     const double spec = c[VP_LG2_I_SLO * st] + smooth_one;
     if (lg2_nu - c[VP_LG2_NUMAX * st] < -20) return spec;
-    return spec - c[VP_INV_NUMAX * st] * exp2_fast(lg2_nu);
+    return spec - c[VP_INV_NUMAX * st] * exp2_(lg2_nu);
 }
 
 // log2_I_nu_fast<THICK_BOUND> at the TWO frequencies xa, xb of a boundary work item, walked stage by stage so that the table rows of

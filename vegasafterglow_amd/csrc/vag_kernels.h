@@ -1525,6 +1525,17 @@ constexpr int FLUX_SPLIT_E0 = FLUX_SPLIT_A - FLUX_SPLIT_E;          // the first
 constexpr int FLUX_SPLIT_GROUP = 5;                                 // interpolation chains of one time the B team interleaves
 static_assert(FLUX_SPLIT_A >= FLUX_SPLIT_E && FLUX_SPLIT_B >= 1, "both teams need wavefronts, the A team those of the EAT step");
 static_assert(FLUX_SPLIT_MAX_NNU % FLUX_SPLIT_GROUP == 0, "the full set of frequencies is taken in whole groups");
+// Instruction forms of the boundary team's FMA chains (profiles/flux_chain_ab.txt), one bit per part so that a variant
+// build measures each alone (-DVAG_FLUX_CHAIN=<bits>); every value keeps its bits in every combination.  All four are on: together
+// -1.2 % per step, none of them 1 % alone.  The same one-statement chain on the interpolation team cost +1.6 % and is not built.
+constexpr int FLUX_CHAIN_SP_MAGIC = 1;   // sp_fast's magic number in a vector register pair
+constexpr int FLUX_CHAIN_HEAD = 2;       // the first Horner step of exp2_fast as one v_fma_f64
+constexpr int FLUX_CHAIN_LB = 4;         // the thick branch's fma(2.5, x, VP_TB) as one v_fma_f64
+constexpr int FLUX_CHAIN_A = 8;          // the nine scalar-addend Horner steps as one asm statement
+#ifndef VAG_FLUX_CHAIN
+#define VAG_FLUX_CHAIN 15
+#endif
+constexpr int FLUX_CHAIN = VAG_FLUX_CHAIN;
 
 // LDS layout of the split form, offsets in doubles (the kernel and the launch's budget read the same numbers)
 struct FluxSplitLds {
@@ -1586,6 +1597,8 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     const LdsTab sp_tab = lds_tab(s_sp), lg_tab = lds_tab(s_sp + SP_TABLE_DOUBLES);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool a_team = wave < FLUX_SPLIT_A;
+    constexpr int A_EXP2 = ((FLUX_CHAIN & FLUX_CHAIN_HEAD) ? EXP2_HEAD : 0) | ((FLUX_CHAIN & FLUX_CHAIN_A) ? EXP2_CHAIN : 0);
+    constexpr bool A_LB = (FLUX_CHAIN & FLUX_CHAIN_LB) != 0;
     const int lane = tid & 63;
 
     auto stage = [&](int rep) {  // all lanes: the photon block of a representative row
@@ -1687,6 +1700,10 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
     };
     if (a_team) {
         const int atid = tid;  // the A team is the first wavefronts
+        // sp_fast's magic number in a vector register pair for the whole item, opaque like `at` below: as a constant it sits in a
+        // scalar pair beside SP_PER_UNIT and costs every softplus term a register copy
+        [[maybe_unused]] double sp_magic = SP_MAGIC;
+        if constexpr ((FLUX_CHAIN & FLUX_CHAIN_SP_MAGIC) != 0) asm volatile("" : "+v"(sp_magic));
 #ifdef VAG_FLUX_STAMPS  // developer aid: cycles an A wavefront spends in the boundary loop, and its passes (profiles/flux_stamps.sh)
         long long c_loop = 0, c_pro = 0;  // c_pro: cycles from barrier release to the first boundary item
         int n_pass = 0, n_rows_done = 0;
@@ -1748,8 +1765,9 @@ __device__ __forceinline__ void flux_split_item(const FluxArgs& a, const int m, 
                 log2_I_nu_pair<true, VAG_FLUX_PAIR>(regs, sc, s_nu[l0] - dop, s_nu[l1] - dop, sp_tab, b0, b1);
 #else
                 // <.., true>: the softplus terms with one masked region each (sp_fast<RELU_FIRST>), -2 % per step
-                const double b0 = log2_I_nu_fast<true, true>(regs, 1, sc, s_nu[l0] - dop, sp_tab);
-                const double b1 = log2_I_nu_fast<true, true>(regs, 1, sc, s_nu[l1] - dop, sp_tab);
+                // <.., A_EXP2, A_LB>, sp_magic: the instruction forms of DESIGN 4g item 14
+                const double b0 = log2_I_nu_fast<true, true, A_EXP2, A_LB>(regs, 1, sc, s_nu[l0] - dop, sp_tab, sp_magic);
+                const double b1 = log2_I_nu_fast<true, true, A_EXP2, A_LB>(regs, 1, sc, s_nu[l1] - dop, sp_tab, sp_magic);
 #endif
                 sB[bofs + k] = b0 + geom;
                 sB[min(bofs + KS, top) + k] = b1 + geom;
