@@ -468,6 +468,12 @@ int vag_flux_density_batch_dev(vag_ctx* ctx, const vag_model_params* d_params, i
  * accepts VAG_P_TMPL_AMP0 + c, and only when its vag_template_fit_spec has template c (c < n_templates). */
 #define VAG_P_TMPL_AMP0 1017
 #define VAG_TMPL_MAX 8
+/* Nor are these: the outlier fraction P_g, the extra scatter b_g and the mean offset mu_g of robust noise group g of
+ * vag_loglike_robust_batch, g = 0 .. VAG_NOISE_MAX_GROUPS - 1.  Only a request with a vag_robust_fit_spec accepts them, and only for a
+ * group whose bit is set in its mask. */
+#define VAG_P_ROBUST_FRAC0 1025
+#define VAG_P_ROBUST_SCALE0 1033
+#define VAG_P_ROBUST_SHIFT0 1041
 
 /* One group of VLBI centroid positions at one frequency (added after VAG_ABI_VERSION 13, detect by symbol).  The model centroid
  * (Xbar, Ybar) of vag_sky_centroid_batch(t, nu) is placed on the sky as
@@ -998,7 +1004,37 @@ int vag_loglike_cov_batch_dev(vag_ctx* ctx, const vag_fit_spec* spec, const vag_
  * (uint64(x2) half) >> 32 of the other half, t = fma(a - 1, u_z, 1), z = t t / a (the largest double below a where that quotient reaches a), prop[d] = fma(z, pos[w][d] - pos[partner][d],
  * pos[partner][d]).  With y0, y1 of stream 1: u_a = u(y0, y1); a proposal whose ln p is not finite is rejected, any other is accepted
  * iff log(u_a) < (ndim - 1) log(z) + (lp_new - lp[w]).  A chain is therefore a function of (seed, step, walker) and of ln p alone. */
-typedef struct vag_loglike_request {  /* the spec blocks of vag_loglike_cov_batch_dev; a null pointer: the block is absent */
+/* Outlier groups (added after VAG_ABI_VERSION 13, detect by symbol): the mixture ("good / bad data") likelihood of Hogg, Bovy & Lang
+ * (2010, section 3) per data set.  An outlier group is a noise group g of vag_noise_fit_spec whose bit is set in `mask`.  It has three
+ * more parameters, each a free parameter or fixed: the outlier fraction P_g in [0, 1) (slot VAG_P_ROBUST_FRAC0 + g, else
+ * frac_fixed[g]), the extra scatter of outliers in ln F b_g >= 0 (VAG_P_ROBUST_SCALE0 + g, else scale_fixed[g]) and their mean offset
+ * in ln F mu_g, finite (VAG_P_ROBUST_SHIFT0 + g, else shift_fixed[g]).  With f_i the model value exactly as the template kernel forms
+ * it (templates, then extinction), r_i = ln F_obs,i - ln max(f_i, 1e-300) (a NaN stays NaN), sigma_i the row's ln_err, w_i its weight
+ * and s_g the group's systematic, every detection row of the group adds
+ *   v_in = sigma_i^2 + s_g^2,  v_out = v_in + b_g^2,
+ *   g_i = log1p(-P_g) - r_i^2 / (2 v_in)           - log1p(s_g^2 / sigma_i^2) / 2
+ *   o_i = ln P_g      - (r_i - mu_g)^2 / (2 v_out) - log1p((s_g^2 + b_g^2) / sigma_i^2) / 2
+ *   l_i = max(g_i, o_i) + log1p(exp(-|g_i - o_i|)),      chi^2 += -2 sum_i w_i l_i
+ * (a lane-strided sum closed by wave_sum, as the other back kernels) in place of the noise group's A + N.  ln 0 = -inf is used as it
+ * stands: P_g = 0 gives l_i = g_i, the noise group's term of the row.  exp(l_i) / (sqrt(2 pi) sigma_i) integrates to 1 over r_i, as the
+ * noise group's term does, so P, b and s can all be sampled; the row's outlier probability is exp(o_i - l_i).  Upper-limit rows of a
+ * robust group keep their limit term; ungrouped rows and the groups without the bit keep their terms statement for statement.  A
+ * robust group may span the point rows and any number of band groups (the sum is separable) and may not have calib > 0: the rank-one
+ * marginalisation does not commute with the mixture.  A walker whose free P_g is not finite or lies outside [0, 1), whose free b_g is
+ * not finite or is negative, or whose free mu_g is not finite scores -inf and is counted in vag_plan.n_walkers_rejected.  Out of
+ * scope: outliers on counts, index, fold, correlated, centroid, visibility and polarization groups, more than two components, per-row
+ * prior probabilities, and sharded calls. */
+typedef struct vag_robust_fit_spec {
+    int32_t n_groups;                         /* the noise spec's n_groups */
+    uint32_t mask;                            /* bit g: group g is robust */
+    double frac_fixed[VAG_NOISE_MAX_GROUPS];  /* P_g of a group without a free parameter, in [0, 1) (0 when not given) */
+    double scale_fixed[VAG_NOISE_MAX_GROUPS]; /* b_g, >= 0 */
+    double shift_fixed[VAG_NOISE_MAX_GROUPS]; /* mu_g, finite */
+} vag_robust_fit_spec;
+
+/* The spec blocks of a likelihood call; a null pointer: the block is absent.  `robust` is the twelfth member, added with the outlier
+ * groups: a caller compiled against the eleven-member struct must be rebuilt (the entry points read the member). */
+typedef struct vag_loglike_request {
     const vag_fit_spec* spec;
     const vag_sky_fit_spec* sky;
     const vag_vis_fit_spec* vis;
@@ -1010,7 +1046,21 @@ typedef struct vag_loglike_request {  /* the spec blocks of vag_loglike_cov_batc
     const vag_fold_fit_spec* fold;
     const vag_template_fit_spec* tmpl;
     const vag_cov_fit_spec* cov;
+    const vag_robust_fit_spec* robust;
 } vag_loglike_request;
+
+/* vag_loglike_cov_batch(_dev) in the request form, with outlier groups.  With request->robust NULL, or when no detection row lies in
+ * a robust group, the call is vag_loglike_cov_batch(_dev) of the request's other blocks, bit for bit: a pass without a detection row
+ * of a robust group launches what it launches there; a pass with one launches vag_fit_back_robust_kernel.  vag_stretch_run_dev,
+ * vag_move_run_dev, vag_tempered_run_dev, vag_nested_run_dev and vag_loglike_split_dev take the block through their request.  Refused
+ * with VAG_E_INVALID before the device is touched, the message naming the group: a robust block without a noise block; n_groups other
+ * than the noise spec's; a mask bit at or above n_groups; a robust group with calib > 0; a frac_fixed that is not finite or outside
+ * [0, 1); a scale_fixed that is not finite or negative; a shift_fixed that is not finite; and a parameter slot VAG_P_ROBUST_* + g for
+ * a group that is not robust ("bad parameter slot").  Results are bitwise reproducible, and a walker's value does not depend on the
+ * rest of the batch or on its evaluation slot.  The 24 fixed values stay resident on the device by content hash. */
+int vag_loglike_robust_batch(vag_ctx* ctx, const vag_loglike_request* request, const double* theta, int nb, int ndim, double* out);
+int vag_loglike_robust_batch_dev(vag_ctx* ctx, const vag_loglike_request* request, const double* d_theta, int nb, int ndim,
+                                 double* d_out);
 typedef struct vag_stretch_spec {
     uint64_t seed;
     double a;           /* the stretch scale, finite and > 1 (2 is customary) */

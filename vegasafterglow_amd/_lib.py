@@ -83,6 +83,10 @@ P_N_H = 1016
 # VAG_P_TMPL_AMP0 + c: the amplitude of additive template c (vag_loglike_tmpl_batch), the parameter "amp_<name>" of a Fitter
 P_TMPL_AMP0, TMPL_MAX = 1017, 8
 TMPL_PREFIX = "amp_"
+# VAG_P_ROBUST_FRAC0 / _SCALE0 / _SHIFT0 + g: the outlier fraction, extra scatter and mean offset of robust noise group g
+# (vag_loglike_robust_batch), the parameters "out_frac_<label>", "out_scale_<label>", "out_shift_<label>" of a Fitter
+P_ROBUST_FRAC0, P_ROBUST_SCALE0, P_ROBUST_SHIFT0 = 1025, 1033, 1041
+ROBUST_PREFIXES = {"out_frac_": P_ROBUST_FRAC0, "out_scale_": P_ROBUST_SCALE0, "out_shift_": P_ROBUST_SHIFT0}
 
 
 class CentroidObs(C.Structure):  # vag_centroid_obs
@@ -196,6 +200,11 @@ class CovFitSpec(C.Structure):  # vag_cov_fit_spec
     _fields_ = [("n_groups", C.c_int32), ("pad", C.c_int32), ("groups", C.POINTER(CovObs))]
 
 
+class RobustFitSpec(C.Structure):  # vag_robust_fit_spec
+    _fields_ = [("n_groups", C.c_int32), ("mask", C.c_uint32), ("frac_fixed", C.c_double * 8), ("scale_fixed", C.c_double * 8),
+                ("shift_fixed", C.c_double * 8)]
+
+
 class FitSpec(C.Structure):
     _fields_ = [
         ("base", ModelParams), ("ndim", C.c_int32), ("slot", C.c_int32 * 16), ("is_log", C.c_int32 * 16),
@@ -214,7 +223,7 @@ class LoglikeRequest(C.Structure):  # vag_loglike_request: the spec blocks of th
     _fields_ = [("spec", C.POINTER(FitSpec)), ("sky", C.POINTER(SkyFitSpec)), ("vis", C.POINTER(VisFitSpec)), ("pol", C.POINTER(PolFitSpec)),
                 ("lim", C.POINTER(LimitFitSpec)), ("noise", C.POINTER(NoiseFitSpec)), ("counts", C.POINTER(CountsFitSpec)),
                 ("index", C.POINTER(IndexFitSpec)), ("fold", C.POINTER(FoldFitSpec)), ("tmpl", C.POINTER(TemplateFitSpec)),
-                ("cov", C.POINTER(CovFitSpec))]
+                ("cov", C.POINTER(CovFitSpec)), ("robust", C.POINTER(RobustFitSpec))]
 
 
 class StretchSpec(C.Structure):  # vag_stretch_spec
@@ -367,7 +376,7 @@ EXPORTS = [
     "vag_loglike_lim_batch", "vag_loglike_lim_batch_dev", "vag_loglike_noise_batch", "vag_loglike_noise_batch_dev",
     "vag_loglike_counts_batch", "vag_loglike_counts_batch_dev", "vag_loglike_index_batch", "vag_loglike_index_batch_dev",
     "vag_loglike_fold_batch", "vag_loglike_fold_batch_dev", "vag_loglike_tmpl_batch", "vag_loglike_tmpl_batch_dev",
-    "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev", "vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev",
+    "vag_loglike_cov_batch", "vag_loglike_cov_batch_dev", "vag_loglike_robust_batch", "vag_loglike_robust_batch_dev", "vag_stretch_propose_dev", "vag_stretch_accept_dev", "vag_stretch_run_dev",
     "vag_loglike_split_dev", "vag_tempered_propose_dev", "vag_tempered_accept_dev", "vag_tempered_swap_dev", "vag_tempered_run_dev",
     "vag_move_propose_dev", "vag_move_accept_dev", "vag_move_run_dev", "vag_chain_autocorr_dev",
     "vag_nested_rank_dev", "vag_nested_retire_dev", "vag_nested_propose_dev", "vag_nested_accept_dev", "vag_nested_run_dev",
@@ -468,6 +477,9 @@ def load():
         if hasattr(lib, "vag_loglike_cov_batch"):  # (detected by symbol too: the template entry with the correlated groups behind it)
             lib.vag_loglike_cov_batch.argtypes = wide + [C.POINTER(CovFitSpec), _dp, C.c_int, C.c_int, _dp]
             lib.vag_loglike_cov_batch_dev.argtypes = wide + [C.POINTER(CovFitSpec), v, C.c_int, C.c_int, v]
+    if hasattr(lib, "vag_loglike_robust_batch"):  # (detected by symbol: the request form, with the outlier groups)
+        lib.vag_loglike_robust_batch.argtypes = [v, C.POINTER(LoglikeRequest), _dp, C.c_int, C.c_int, _dp]
+        lib.vag_loglike_robust_batch_dev.argtypes = [v, C.POINTER(LoglikeRequest), v, C.c_int, C.c_int, v]
     if hasattr(lib, "vag_stretch_run_dev"):  # (detected by symbol: the device sampler)
         sp = C.POINTER(StretchSpec)
         lib.vag_stretch_propose_dev.argtypes = [v, sp, C.c_uint64, C.c_int, v, v]

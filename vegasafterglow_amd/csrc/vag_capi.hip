@@ -513,6 +513,7 @@ struct vag_ctx {
     ResidentBlock fold;    // fold groups (vag_loglike_fold_batch): per group the block FoldLayout describes
     ResidentBlock tmpl;    // additive templates (vag_loglike_tmpl_batch): [amp_fixed 8] then per touched pass its [n_templates][n] values, see TmplLayout
     ResidentBlock cov;     // correlated groups (vag_loglike_cov_batch): per group [t | nu | ln_flux | ext | Wt], see CovLayout
+    ResidentBlock robust;  // outlier groups (vag_loglike_robust_batch): [frac_fixed 8 | scale_fixed 8 | shift_fixed 8], see RobustLayout
     std::vector<VisLayout> vis_layout;  // of the resident visibility groups: made by the miss that made them resident
     bool fit_stats_pending = false;  // d_fitstat of the last likelihood call not read back yet
     bool ic_need_reset = true;       // first SSC table build of a pass clears d_icstatus
@@ -758,7 +759,7 @@ void vag_ctx_destroy(vag_ctx* c) {
     c->d_plan.release();
     c->d_chunk.release();
     c->d_icwork.release();
-    for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov}) b->release();
+    for (ResidentBlock* b : {&c->fit, &c->sky, &c->vis, &c->pol, &c->lim, &c->noise, &c->counts, &c->index, &c->fold, &c->tmpl, &c->cov, &c->robust}) b->release();
     c->d_fitstat.release();
     for (DevBuf* b : {&c->d_mix_flags, &c->d_mix_perm, &c->d_mix_params, &c->d_mix_out, &c->shard_costs[0].cost, &c->shard_costs[1].cost, &c->shard_costs[2].cost, &c->shard_costs[3].cost, &c->shard_flights[0].table, &c->shard_flights[1].table, &c->shard_flights[2].table, &c->shard_flights[3].table, &c->shard_flights[4].table, &c->shard_flights[5].table, &c->shard_flights[6].table, &c->shard_flights[7].table, &c->d_shard_theta, &c->d_shard_ll, &c->d_order[0], &c->d_order[1], &c->d_cost_f, &c->d_rowgeo, &c->d_icneed, &c->d_skyterms, &c->d_skyimg, &c->d_skymom, &c->d_skyvis, &c->d_skyuv, &c->d_skypol, &c->d_skystokes, &c->d_skycen, &c->d_skycmom, &c->d_visblk, &c->d_vispart, &c->d_polspec, &c->d_polstokes, &c->d_sampler_prop, &c->d_sampler_fresh, &c->d_sampler_aux, &c->d_nested_rank, &c->d_chain_stats, &c->d_predict})
         b->release();
@@ -3325,11 +3326,11 @@ static int upload_blocks(vag_ctx* c, FitRequest& r, bool fit_only = false) {
     }
     if (!rc && r.pol && !(rc = pol_scan(r.pol, r.play)))
         rc = c->pol.upload(st, r.play, [&] { return pol_rows(r.pol); }, [&](double* hp) { six_fill(r.pol, r.play, hp); });
-    const struct { ResidentBlock* block; const void* spec; const BlockKey* key; const std::vector<double>* staged; } scanned[7] = {  // (spec null: not held)
+    const struct { ResidentBlock* block; const void* spec; const BlockKey* key; const std::vector<double>* staged; } scanned[8] = {  // (spec null: not held)
         {&c->lim, r.lim, &r.llay, &r.lstage},       {&c->noise, r.noise, &r.nlay, &r.nstage},
         {&c->counts, r.counts, &r.clay, &r.cstage}, {&c->index, r.index, &r.ilay, &r.istage},
         {&c->fold, r.fold, &r.flay, &r.fstage},     {&c->tmpl, r.tmpl, &r.tlay, &r.tstage},
-        {&c->cov, r.cov, &r.vlay, &r.vstage}};
+        {&c->cov, r.cov, &r.vlay, &r.vstage},       {&c->robust, r.robust, &r.rlay, &r.rstage}};
     for (const auto& s : scanned)
         if (!rc && s.spec)
             rc = s.block->upload(st, *s.key, [] { return VAG_OK; },
@@ -3404,14 +3405,22 @@ static int loglike_passes(vag_ctx* c, const FitRequest& req, const double* d_the
     // the back of a flux pass.  lim_off: where the pass's block of limit rows starts in lim.d, or -1 (no limit row: the kernel as it
     // was); noise_off, present: where the pass's group ids start in noise.d, or -1 (no grouped row: the kernels as they were), and
     // its groups; tmpl_off, tpresent: where the pass's template values start in tmpl.d, or -1 (no touched row: the kernels as they
-    // were), and the templates that touch it
+    // were), and the templates that touch it; robust: the pass holds a detection row of a robust group (its rows are grouped:
+    // noise_off >= 0), else the kernels as they were
     auto back = [&](const double* flux, int npts, const double* lnf, const double* lne, const double* w, const double* ext,
-                    long lim_off, long noise_off, unsigned present, long tmpl_off, unsigned tpresent) -> int {
+                    long lim_off, long noise_off, unsigned present, long tmpl_off, unsigned tpresent, bool robust) -> int {
         const double* lb = lim_off >= 0 ? c->lim.d.as<double>() + lim_off : nullptr;  // [limit | sigma | kind]
         const LimCols lcol = lim_cols(npts);
         const int* lk = lb ? reinterpret_cast<const int*>(lb + lcol.kind) : nullptr;
         const double* ls = lb ? lb + lcol.sigma : nullptr;
-        if (tmpl_off >= 0) {
+        if (robust && noise_off >= 0) {
+            const double* nz = c->noise.d.as<double>();
+            const double* tp = tmpl_off >= 0 ? c->tmpl.d.as<double>() : nullptr;  // [amp_fixed 8 | the passes' values], or no template here
+            hipLaunchKernelGGL(vag_fit_back_robust_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av, fit_pass(),
+                               next_order(), lk, lb, ls, d_theta, ndim, d_prior, nz, reinterpret_cast<const int*>(nz + noise_off), present,
+                               tp ? tp + tmpl_off : nullptr, tp ? req.tlay.n_templates : 0, tp ? tpresent : 0u, tp, req.tlay.ext_mask,
+                               c->robust.d.as<double>(), req.rlay.mask);
+        } else if (tmpl_off >= 0) {
             const double* nz = noise_off >= 0 ? c->noise.d.as<double>() : nullptr;
             const double* tp = c->tmpl.d.as<double>();  // [amp_fixed 8 | the passes' values]
             hipLaunchKernelGGL(vag_fit_back_tmpl_kernel, dim3(nb), dim3(64), 0, st, flux, npts, lnf, lne, w, ext, d_av, fit_pass(),
@@ -3460,7 +3469,7 @@ static int loglike_passes(vag_ctx* c, const FitRequest& req, const double* d_the
             if (rc == VAG_OK)
                 rc = back(c->d_series_flux.as<double>(), n, ln_flux, ln_err, weight, spec->ext_kernel ? ext : nullptr,
                           req.lim ? req.llay.point : -1, req.noise ? req.nlay.point : -1, req.noise ? req.nlay.point_present : 0u,
-                          req.tmpl ? req.tlay.point : -1, req.tmpl ? req.tlay.point_present : 0u);
+                          req.tmpl ? req.tlay.point : -1, req.tmpl ? req.tlay.point_present : 0u, req.robust && req.rlay.point);
             if (rc == VAG_OK) {
                 rc = finish_speculation(c);  // before a band group's own grid pass reuses the plan buffers
                 n_cap = std::max(n_cap, c->plan.n_models_capacity);
@@ -3483,7 +3492,7 @@ static int loglike_passes(vag_ctx* c, const FitRequest& req, const double* d_the
             if (rc == VAG_OK)
                 rc = back(c->d_series_flux.as<double>(), bd.n, db + k.ln_flux, db + k.ln_err, db + k.weight, nullptr,
                           req.lim ? req.llay.band[g] : -1, req.noise ? req.nlay.band[g] : -1, req.noise ? req.nlay.band_present[g] : 0u,
-                          req.tmpl ? req.tlay.band[g] : -1, req.tmpl ? req.tlay.band_present[g] : 0u);
+                          req.tmpl ? req.tlay.band[g] : -1, req.tmpl ? req.tlay.band_present[g] : 0u, req.robust && req.rlay.band[g]);
         } break;
         case PassKind::Centroid: {  // centroid groups: one vag_sky_centroid_batch request each, after every flux pass
             const vag_centroid_obs& o = sky->groups[g];
@@ -3758,6 +3767,13 @@ int vag_loglike_cov_batch_dev(vag_ctx* c, const vag_fit_spec* spec, const vag_sk
     return loglike_dev(c, r, d_theta, nb, ndim, d_out);
 }
 
+// the request form (with the outlier groups): a null request is refused like a null spec
+int vag_loglike_robust_batch_dev(vag_ctx* c, const vag_loglike_request* q, const double* d_theta, int nb, int ndim, double* d_out) {
+    if (!q) return set_err(VAG_E_INVALID, "null request");
+    FitRequest r = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov, q->robust);
+    return loglike_dev(c, r, d_theta, nb, ndim, d_out);
+}
+
 // ---- the device sampler: the stretch move, the move mix, parallel tempering, nested sampling (kernels: vag_sampler.h, vag_moves.h,
 //      vag_tempering.h, vag_nested.h; what the specs refuse and the arithmetic of the launches: vag_sampler_plan.h; the moves: the public header) ----
 
@@ -3801,7 +3817,7 @@ template <class BeginStep, class Propose, class Behind, class Accept, class EndS
 static int sampler_run(vag_ctx* c, const vag_loglike_request* q, int ndim, int nb, int phases, int thin, bool storing, uint64_t step0,
                        int n_steps, BeginStep begin_step, Propose propose, Behind behind, Accept accept, EndStep end_step) {
     if (n_steps == 0) return VAG_OK;
-    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
+    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov, q->robust);
     int rc = fit_request_prepare(req);  // the scans, once per call of many steps
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
@@ -3956,7 +3972,7 @@ int vag_loglike_split_dev(vag_ctx* c, const vag_loglike_request* q, const double
     ApiLock api_lock(c);
     HandoffScope handoff(c);  // (closes behind the split, after the one of the call inside)
     if (!c || !q || !q->spec || !d_theta || !d_lnl || !d_lnprior) return set_err(VAG_E_INVALID, "null context, request, fit spec or device pointer");
-    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov);
+    FitRequest req = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov, q->robust);
     const int rc = loglike_dev(c, req, d_theta, nb, ndim, d_lnl);  // (ln L + ln prior by walker, which the split then replaces)
     if (rc) return rc;
     return fit_split(c, nb, d_lnl, d_lnprior);
@@ -4599,6 +4615,12 @@ int vag_loglike_cov_batch(vag_ctx* c, const vag_fit_spec* spec, const vag_sky_fi
                           const vag_template_fit_spec* tmpl, const vag_cov_fit_spec* cov, const double* theta, int nb, int ndim,
                           double* out) {
     FitRequest r = fit_request(spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl, cov);
+    return loglike_host(c, r, theta, nb, ndim, out);
+}
+
+int vag_loglike_robust_batch(vag_ctx* c, const vag_loglike_request* q, const double* theta, int nb, int ndim, double* out) {
+    if (!q) return set_err(VAG_E_INVALID, "null request");
+    FitRequest r = fit_request(q->spec, q->sky, q->vis, q->pol, q->lim, q->noise, q->counts, q->index, q->fold, q->tmpl, q->cov, q->robust);
     return loglike_host(c, r, theta, nb, ndim, out);
 }
 

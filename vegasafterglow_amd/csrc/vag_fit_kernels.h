@@ -9,6 +9,7 @@
 #include "vag_kernels.h"
 #include "vag_log_ndtr.h"
 #include "vag_poisson.h"
+#include "vag_robust.h"
 #include "vag_sky.h"
 
 namespace vag {
@@ -373,6 +374,136 @@ vag_fit_back_tmpl_kernel(const double* __restrict__ flux /* [nb][n] */, int n, c
                 P = wave_sum(P);
                 const double c2 = cg * cg;
                 term = A - c2 * (B * B) / (1.0 + c2 * P) + N + log1p(c2 * P);
+            }
+            s += term;  // (every lane holds the same sums; lane 0 stores)
+        }
+    }
+    fit_close_pass(pass, m, lane, grid_ok, bad, s);
+}
+
+// The back of a flux pass that holds a detection row of a robust noise group (vag_loglike_robust_batch; INTEGRATION.md "Outlier
+// groups").  It is vag_fit_back_tmpl_kernel statement for statement and in the same lane-strided order -- n_tmpl = 0: no template,
+// tmpl and amp_fixed are not read and f_i is the other kernels' value -- but for the group walk: a group whose bit is set in rmask takes
+// the single sum R = sum w_i l_i, l_i = robust_row_lnl(...) (vag_robust.h), in place of A, B, P, N and adds -2 wave_sum(R); it has no
+// calibration (robust_scan refuses one).  The group's P, b, mu are found as s_g is found: the free parameters with the slots
+// VAG_P_ROBUST_FRAC0 / _SCALE0 / _SHIFT0 + g, else robust[g], robust[8 + g], robust[16 + g]; log1p(-P) and ln P are formed once per
+// group and are wave-uniform, as is the branch on the group's bit.  A free P that is not finite or lies outside [0, 1), a free b that is
+// not finite or is negative and a free mu that is not finite make the walker `bad`, like a refused template amplitude.  A kernel of its
+// own so that a pass without such a row runs the instructions it always ran.
+__global__ void __launch_bounds__(64)
+vag_fit_back_robust_kernel(const double* __restrict__ flux /* [nb][n] */, int n, const double* __restrict__ ln_flux,
+                           const double* __restrict__ ln_err, const double* __restrict__ weight, const double* __restrict__ ext /* or null */,
+                           const double* __restrict__ a_v, FitPass pass, FitOrderOut ord,
+                           const int* __restrict__ lim_kind /* [n] VAG_OBS_*, or null: no limit row in this pass */,
+                           const double* __restrict__ lim_L /* [n] */, const double* __restrict__ lim_sigma /* [n] */,
+                           const double* __restrict__ theta /* [nb][ndim] */, int ndim, const double* __restrict__ prior,
+                           const double* __restrict__ noise /* [sys_fixed 8 | calib 8] */, const int* __restrict__ grp /* [n] group id or -1 */,
+                           unsigned gpresent /* bit g: some row of the pass is in group g */,
+                           const double* __restrict__ tmpl /* [n_tmpl][n] the pass's template values, or null */, int n_tmpl,
+                           unsigned tpresent /* bit c: template c touches some row of the pass */,
+                           const double* __restrict__ amp_fixed /* [8], or null */, unsigned extm /* bit c: template c is extinguished */,
+                           const double* __restrict__ robust /* [frac_fixed 8 | scale_fixed 8 | shift_fixed 8] */,
+                           unsigned rmask /* bit g: group g is robust */) {
+    const int m = blockIdx.x, lane = threadIdx.x;
+    const bool grid_ok = pass.meta[m].status == 0;
+    fit_hand_over_order(pass, ord, m, lane);
+    const int walker = pass.order ? pass.order[m] : m;
+    const double av = (ext != nullptr) ? a_v[m] : 0.0;
+    const int* slot = reinterpret_cast<const int*>(prior + 64);
+    const int* is_log = slot + 16;
+    double a[VAG_TMPL_MAX];
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < VAG_TMPL_MAX; ++c) {
+        a[c] = 0.0;
+        if (c >= n_tmpl) continue;
+        a[c] = amp_fixed[c];
+        for (int d = 0; d < ndim; ++d) {
+            if (slot[d] != VAG_P_TMPL_AMP0 + c) continue;
+            const double v = theta[(size_t)walker * ndim + d];
+            a[c] = is_log[d] ? pow(10.0, v) : v;
+            bad = bad || !isfinite(a[c]) || a[c] < 0;
+        }
+    }
+    double s = 0;
+    if (grid_ok)
+        for (int i = lane; i < n; i += 64) {
+            const bool is_lim = lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT;
+            if (grp[i] >= 0 && !is_lim) continue;  // a grouped detection: in the turn of its group below
+            const double f = tmpl_model_value(flux[(size_t)m * n + i], i, n, tmpl, tpresent, extm, a, av, ext);
+            {
+#pragma clang fp contract(off)
+                if (is_lim) {
+                    s = s + weight[i] * (-2.0 * log_ndtr((lim_L[i] - f) / lim_sigma[i]));
+                    continue;
+                }
+                const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+                const double q = (ln_flux[i] - log(fm)) / ln_err[i];
+                s = s + weight[i] * (q * q);
+            }
+        }
+    s = wave_sum(s);
+    if (grid_ok) {
+        for (int g = 0; g < VAG_NOISE_MAX_GROUPS; ++g) {
+            if (!((gpresent >> g) & 1u)) continue;
+            const bool rob = (rmask >> g) & 1u;  // (wave-uniform: a kernel argument)
+            double sg = noise[g], P = 0, b = 0, mu = 0;
+            if (rob) P = robust[g], b = robust[VAG_NOISE_MAX_GROUPS + g], mu = robust[2 * VAG_NOISE_MAX_GROUPS + g];
+            for (int d = 0; d < ndim; ++d) {
+                const int sl = slot[d];
+                const bool mine = sl == VAG_P_NOISE_SYS0 + g ||
+                                  (rob && (sl == VAG_P_ROBUST_FRAC0 + g || sl == VAG_P_ROBUST_SCALE0 + g || sl == VAG_P_ROBUST_SHIFT0 + g));
+                if (!mine) continue;
+                const double v = theta[(size_t)walker * ndim + d];
+                const double val = is_log[d] ? pow(10.0, v) : v;
+                if (sl == VAG_P_NOISE_SYS0 + g) {
+                    sg = val;
+                } else if (sl == VAG_P_ROBUST_FRAC0 + g) {
+                    P = val;
+                    bad = bad || !isfinite(val) || val < 0 || !(val < 1);
+                } else if (sl == VAG_P_ROBUST_SCALE0 + g) {
+                    b = val;
+                    bad = bad || !isfinite(val) || val < 0;
+                } else {
+                    mu = val;
+                    bad = bad || !isfinite(val);
+                }
+            }
+            const double s2 = sg * sg;
+            if (rob) {  // (wave-uniform) the mixture: one sum, no calibration
+                const double b2 = b * b, ln_good = log1p(-P), ln_bad = log(P);
+                double R = 0;
+                for (int i = lane; i < n; i += 64) {
+                    if (grp[i] != g || (lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT)) continue;
+                    const double f = tmpl_model_value(flux[(size_t)m * n + i], i, n, tmpl, tpresent, extm, a, av, ext);
+                    const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+                    const double r = ln_flux[i] - log(fm), sig2 = ln_err[i] * ln_err[i];
+                    R += weight[i] * robust_row_lnl(r, sig2, s2, b2, mu, ln_good, ln_bad);
+                }
+                s += -2.0 * wave_sum(R);
+                continue;
+            }
+            const double cg = noise[VAG_NOISE_MAX_GROUPS + g];
+            double A = 0, B = 0, Pw = 0, N = 0;
+            for (int i = lane; i < n; i += 64) {
+                if (grp[i] != g || (lim_kind && lim_kind[i] == VAG_OBS_UPPER_LIMIT)) continue;
+                const double f = tmpl_model_value(flux[(size_t)m * n + i], i, n, tmpl, tpresent, extm, a, av, ext);
+                const double fm = (f != f) ? f : (f > 1e-300 ? f : 1e-300);
+                const double r = ln_flux[i] - log(fm), sig2 = ln_err[i] * ln_err[i];
+                const double p = weight[i] / (sig2 + s2);
+                A += p * (r * r);
+                B += p * r;
+                Pw += p;
+                N += weight[i] * log1p(s2 / sig2);
+            }
+            A = wave_sum(A);
+            N = wave_sum(N);
+            double term = A + N;
+            if (cg > 0) {  // (wave-uniform) the calibration scale marginalised, as in vag_fit_back_noise_kernel
+                B = wave_sum(B);
+                Pw = wave_sum(Pw);
+                const double c2 = cg * cg;
+                term = A - c2 * (B * B) / (1.0 + c2 * Pw) + N + log1p(c2 * Pw);
             }
             s += term;  // (every lane holds the same sums; lane 0 stores)
         }

@@ -1,5 +1,5 @@
-// vag_fit_request.h -- the host side of one likelihood request: what is done to its eleven spec blocks before a HIP call, the request
-// that carries them, and its normalisation.  Two conventions.  Scanned every call (lim, noise, tmpl, counts, index, fold, cov): *_scan
+// vag_fit_request.h -- the host side of one likelihood request: what is done to its twelve spec blocks before a HIP call, the request
+// that carries them, and its normalisation.  Two conventions.  Scanned every call (lim, noise, robust, tmpl, counts, index, fold, cov): *_scan
 // validates the block and lays it out in a stage vector (int32 arrays packed into doubles, transposed whiteners, ...); a miss copies
 // it.  Hashed in place, filled on a miss (fit, sky, vis, pol): *_scan makes the cheap checks and hashes the caller's arrays where they
 // lie; only a miss runs *_rows (the row validation), then *_fill (into the pinned buffer).  Either way the scan leaves the block's
@@ -230,6 +230,59 @@ static int noise_scan(const vag_fit_spec* spec, const vag_noise_fit_spec* nz, st
                            "noise group %d has a calibration fraction and rows in %d passes: such a group must hold point rows only or "
                            "exactly one band group", g, passes[g]);
     key_staged(lay, hash_offsets(lay.point, lay.band), stage);
+    return VAG_OK;
+}
+
+// ---- outlier groups (vag_loglike_robust_batch): one device buffer, uploaded like the other spec blocks when the hash changes.  Layout
+//      in doubles: [frac_fixed 8 | scale_fixed 8 | shift_fixed 8].  The rows' group ids are the noise block's. ----
+constexpr size_t ROBUST_STAGE_DOUBLES = 3 * VAG_NOISE_MAX_GROUPS;
+
+struct RobustLayout : BlockKey {
+    bool any = false;             // some detection row lies in a robust group
+    unsigned mask = 0;            // bit g: group g is robust
+    bool point = false;           // the point rows hold a detection row of a robust group
+    std::vector<char> band;       // the same per band group
+};
+
+// Validates the robust block against the fit spec, the noise block (which noise_scan has accepted) and the limit rows (which lim_scan
+// has accepted; null: no limit row), and lays its fixed values out in stage (host work only: no context is touched).
+static int robust_scan(const vag_fit_spec* spec, const vag_noise_fit_spec* nz, const vag_limit_fit_spec* lim, const vag_robust_fit_spec* rb,
+                       std::vector<double>& stage, RobustLayout& lay) {
+    if (!nz) return set_err(VAG_E_INVALID, "outlier groups need a noise block: a robust group is a noise group");
+    if (rb->n_groups != nz->n_groups)
+        return set_err(VAG_E_INVALID, "outlier groups: n_groups must be the noise spec's %d, got %d", nz->n_groups, rb->n_groups);
+    if ((rb->mask >> rb->n_groups) != 0u)  // (n_groups is the noise spec's: 0 .. 8)
+        return set_err(VAG_E_INVALID, "outlier groups: the mask 0x%x names a group at or above n_groups = %d", rb->mask, rb->n_groups);
+    for (int g = 0; g < rb->n_groups; ++g) {
+        if (((rb->mask >> g) & 1u) && nz->calib[g] > 0)
+            return set_err(VAG_E_INVALID, "outlier group %d has a calibration fraction: the marginalised scale does not commute with the mixture", g);
+        if (!std::isfinite(rb->frac_fixed[g]) || rb->frac_fixed[g] < 0 || !(rb->frac_fixed[g] < 1))
+            return set_err(VAG_E_INVALID, "outlier group %d: the outlier fraction must be finite and in [0, 1)", g);
+        if (!std::isfinite(rb->scale_fixed[g]) || rb->scale_fixed[g] < 0)
+            return set_err(VAG_E_INVALID, "outlier group %d: the outlier scatter must be finite and >= 0", g);
+        if (!std::isfinite(rb->shift_fixed[g])) return set_err(VAG_E_INVALID, "outlier group %d: the outlier offset must be finite", g);
+    }
+    lay.mask = rb->mask;
+    stage.assign(ROBUST_STAGE_DOUBLES, 0.0);
+    for (int g = 0; g < rb->n_groups; ++g) {
+        stage[g] = rb->frac_fixed[g];
+        stage[VAG_NOISE_MAX_GROUPS + g] = rb->scale_fixed[g];
+        stage[2 * VAG_NOISE_MAX_GROUPS + g] = rb->shift_fixed[g];
+    }
+    auto robust_id = [&](int id) { return id >= 0 && ((rb->mask >> id) & 1u); };
+    const int n = spec->n_data;
+    const int32_t* pk = lim ? lim->point.kind : nullptr;
+    if (nz->point_group)
+        for (int i = 0; i < n && !lay.point; ++i)
+            lay.point = robust_id(nz->point_group[i]) && !(pk && pk[i] == VAG_OBS_UPPER_LIMIT);
+    lay.band.assign(std::max(spec->n_bands, 0), 0);
+    for (int b = 0; b < nz->n_bands; ++b) {
+        if (!robust_id(nz->band_group[b])) continue;
+        const int32_t* bk = (lim && b < lim->n_bands) ? lim->bands[b].kind : nullptr;
+        for (int i = 0; i < spec->bands[b].n && !lay.band[b]; ++i) lay.band[b] = !(bk && bk[i] == VAG_OBS_UPPER_LIMIT);
+    }
+    lay.any = lay.point || std::find(lay.band.begin(), lay.band.end(), (char)1) != lay.band.end();
+    key_staged(lay, fnv1a(FNV_SEED, &lay.mask, sizeof lay.mask), stage);
     return VAG_OK;
 }
 
@@ -617,11 +670,20 @@ struct FitLayout : BlockKey {
 
 // The slots a fit spec may free beyond the model's own, by what else the request holds: the placement (some group reads it), the
 // field of polarization groups, N_H (a fold group with a cross-section), the systematic of a noise group and the amplitude of a
-// template that exist.  counts: some group is data without a flux row (counts, index, fold, cov).
+// template that exist, and the three outlier parameters of a robust group.  counts: some group is data without a flux row (counts,
+// index, fold, cov).
 struct FitAccepts {
     bool sky = false, pol = false, n_h = false, counts = false;
     int noise_groups = 0, n_templates = 0;
+    unsigned robust_mask = 0;  // bit g: noise group g is robust
 };
+
+// the group of an outlier-parameter slot (VAG_P_ROBUST_FRAC0 / _SCALE0 / _SHIFT0 + g), or -1
+static int robust_slot_group(int s) {
+    for (int base : {VAG_P_ROBUST_FRAC0, VAG_P_ROBUST_SCALE0, VAG_P_ROBUST_SHIFT0})
+        if (s >= base && s < base + VAG_NOISE_MAX_GROUPS) return s - base;
+    return -1;
+}
 
 static int fit_scan(const vag_fit_spec* spec, int ndim, const FitAccepts& acc, FitLayout& lay) {
     if (ndim != spec->ndim || ndim <= 0 || ndim > 16) return set_err(VAG_E_INVALID, "ndim must match spec and be in 1..16");
@@ -636,6 +698,7 @@ static int fit_scan(const vag_fit_spec* spec, int ndim, const FitAccepts& acc, F
         if (s >= VAG_P_NOISE_SYS0 && s < VAG_P_NOISE_SYS0 + acc.noise_groups) continue;
         if (acc.n_h && s == VAG_P_N_H) continue;
         if (s >= VAG_P_TMPL_AMP0 && s < VAG_P_TMPL_AMP0 + acc.n_templates) continue;
+        if (robust_slot_group(s) >= 0 && ((acc.robust_mask >> robust_slot_group(s)) & 1u)) continue;
         if (s < 0 || (s >= VAG_P_COUNT && (s < VAG_P_RVS_EPS_E || s > VAG_P_MAG_Q))) return set_err(VAG_E_INVALID, "bad parameter slot");
     }
     if (spec->use_priors)
@@ -932,6 +995,7 @@ struct FitRequest {
     const vag_fold_fit_spec* fold = nullptr;
     const vag_template_fit_spec* tmpl = nullptr;  // after fit_request_prepare: null when no row is touched (tlay.any)
     const vag_cov_fit_spec* cov = nullptr;        // after fit_request_prepare: null when it has no group
+    const vag_robust_fit_spec* robust = nullptr;  // after fit_request_prepare: null when no detection row lies in a robust group (rlay.any)
     int ndim = 0;                                 // of the call: fit_scan holds the spec's against it
     FitLayout fit;                                // the four blocks hashed in place (fit, sky, vis, pol): scanned in the upload sequence
     SkyLayout slay;
@@ -946,7 +1010,8 @@ struct FitRequest {
     FoldLayout flay;
     TmplLayout tlay;
     CovLayout vlay;
-    std::vector<double> lstage, nstage, cstage, istage, fstage, tstage, vstage;  // what the scans lay out: one resident block each
+    RobustLayout rlay;
+    std::vector<double> lstage, nstage, cstage, istage, fstage, tstage, vstage, rstage;  // what the scans lay out: one resident block each
     bool placed = false;                                 // some group reads east0 / north0
     bool prepared = false;                               // fit_request_prepare has run
 };
@@ -968,6 +1033,8 @@ static int fit_request_prepare(FitRequest& r) {
     if (r.counts && (rc = counts_scan(r.counts, r.cstage, r.clay))) return rc;
     if (r.noise && (rc = noise_scan(r.spec, r.noise, r.nstage, r.nlay))) return rc;
     if (r.lim && (rc = lim_scan(r.spec, r.pol, r.lim, r.lstage, r.llay))) return rc;  // (pol as given: an empty list checks n_pol_groups)
+    if (r.robust && (rc = robust_scan(r.spec, r.noise, r.lim, r.robust, r.rstage, r.rlay))) return rc;  // (noise and lim as given, and accepted)
+    if (!r.rlay.any) r.robust = nullptr;  // (rlay.mask stays: the outlier slots of the spec's robust groups are accepted)
     if (!r.nlay.any) r.noise = nullptr;
     if (!r.llay.any) r.lim = nullptr;
     if (!r.tlay.any) r.tmpl = nullptr;  // (tlay.n_templates stays: the amplitude slots of the spec's templates are accepted)
@@ -1006,12 +1073,13 @@ static const double* short_series_nu(const double* nu, size_t K, size_t np, size
 
 static FitAccepts fit_accepts(const FitRequest& r) {
     return {r.placed, r.pol != nullptr, r.fold && r.flay.any_sigma, r.counts || r.index || r.fold || r.cov,
-            r.noise ? r.nlay.n_groups : 0, r.tlay.n_templates};
+            r.noise ? r.nlay.n_groups : 0, r.tlay.n_templates, r.noise ? r.rlay.mask : 0u};
 }
 
 static FitRequest fit_request(const vag_fit_spec* spec, const vag_sky_fit_spec* sky = nullptr, const vag_vis_fit_spec* vis = nullptr,
                               const vag_pol_fit_spec* pol = nullptr, const vag_limit_fit_spec* lim = nullptr, const vag_noise_fit_spec* noise = nullptr,
                               const vag_counts_fit_spec* counts = nullptr, const vag_index_fit_spec* index = nullptr,
-                              const vag_fold_fit_spec* fold = nullptr, const vag_template_fit_spec* tmpl = nullptr, const vag_cov_fit_spec* cov = nullptr) {
-    return FitRequest{spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl, cov};
+                              const vag_fold_fit_spec* fold = nullptr, const vag_template_fit_spec* tmpl = nullptr, const vag_cov_fit_spec* cov = nullptr,
+                              const vag_robust_fit_spec* robust = nullptr) {
+    return FitRequest{spec, sky, vis, pol, lim, noise, counts, index, fold, tmpl, cov, robust};
 }

@@ -182,6 +182,15 @@ def _widest_entry(lib, spec, suffix):
     call bit for bit; a fit with correlated groups, templates or count spectra is an error where its entry is missing."""
     tmpl = getattr(spec, "_tmpl", None)
     cov = getattr(spec, "_cov", None)
+    if getattr(spec, "_robust", None) is not None:
+        # outlier groups: the request form.  The callers hand every entry (h, spec, the blocks ..., theta, nb, ndim, out); the blocks
+        # travel in the request here, so the function handed back keeps the context and the four trailing arguments
+        name = "vag_loglike_robust_batch" + suffix
+        if not hasattr(lib, name):
+            raise RuntimeError(f"the loaded library has no {name}: outlier groups (outliers=True of Fitter.add_flux_density / "
+                               "add_spectrum / add_flux) need a newer build")
+        entry, request = getattr(lib, name), loglike_request(spec)
+        return (lambda h, *args: entry(h, C.byref(request), *args[-4:])), ()
     if cov is not None:
         name = "vag_loglike_cov_batch" + suffix
         if not hasattr(lib, name):
@@ -218,11 +227,36 @@ def on_current_stream(lib, h, lock, dev, fn):
 
 
 def loglike_request(spec):
-    """vag_loglike_request of a spec made by Fitter.build_spec: the eleven blocks of the widest likelihood entry, None where the fit
+    """vag_loglike_request of a spec made by Fitter.build_spec: the twelve blocks of the widest likelihood entry, None where the fit
     has none.  The struct points into ``spec``: keep both."""
     ptr = lambda x: C.pointer(x) if x is not None else None  # noqa: E731
     return _lib.LoglikeRequest(C.pointer(spec), ptr(spec._sky), ptr(spec._vis), ptr(spec._pol), ptr(spec._lim), ptr(spec._noise),
-                               ptr(spec._counts), ptr(spec._index), ptr(spec._fold), ptr(spec._tmpl), ptr(spec._cov))
+                               ptr(spec._counts), ptr(spec._index), ptr(spec._fold), ptr(spec._tmpl), ptr(spec._cov),
+                               ptr(getattr(spec, "_robust", None)))
+
+
+def outlier_terms(r, sigma, w, s, frac, scale, shift):
+    """(lnl, p_out) of the detection rows of one outlier group, the numpy statement of the device's term (INTEGRATION.md "Outlier
+    groups"): r [..., n] the residuals ln F_obs - ln max(f, 1e-300), sigma [n] the rows' ln_err, w [n] their weights; s the group's
+    systematic, frac its outlier fraction P in [0, 1), scale the extra scatter b >= 0 and shift the mean offset mu of outliers in ln F,
+    each a scalar or [...] (one per walker).
+        v_in = sigma^2 + s^2,  v_out = v_in + b^2,
+        g = log1p(-P) - r^2 / (2 v_in)         - log1p(s^2 / sigma^2) / 2
+        o = ln P      - (r - mu)^2 / (2 v_out) - log1p((s^2 + b^2) / sigma^2) / 2
+        l = max(g, o) + log1p(exp(-|g - o|))
+    lnl [...] = sum_i w_i l_i is what the rows add to ln L; p_out [..., n] = exp(o - l) is each row's posterior probability of being
+    an outlier at these parameters.  ln 0 = -inf as it stands: P = 0 gives l = g, the noise group's term, and p_out = 0."""
+    r, sig, w = np.asarray(r, dtype=np.float64), np.asarray(sigma, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    s2, P, b2, mu = (np.asarray(v, dtype=np.float64)[..., None] for v in (s, frac, scale, shift))
+    s2, b2 = s2 * s2, b2 * b2
+    sig2 = sig * sig
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        g = np.log1p(-P) - 0.5 * (r * r) / (sig2 + s2) - 0.5 * np.log1p(s2 / sig2)
+        o = np.log(P) - 0.5 * ((r - mu) * (r - mu)) / (sig2 + s2 + b2) - 0.5 * np.log1p((s2 + b2) / sig2)
+        hi = np.where(g > o, g, o)
+        ell = hi + np.log1p(np.exp(-np.abs(g - o)))
+        p_out = np.exp(o - ell)
+        return np.sum(w * ell, axis=-1), p_out
 
 
 def _fma(a, b, c):
@@ -400,6 +434,7 @@ class Fitter:
         self._point_grp = []  # per add_* call: the noise group id of its rows (noise=...), -1 = none
         self._noise_labels = []  # the noise groups in order of first mention: group g is self._noise_labels[g]
         self._noise_calib = {}  # label -> its calibration fraction, once a call has stated one
+        self._noise_robust = {}  # label -> its outliers= flag, once a call has stated one (robust: the mixture likelihood)
         self._point_tmpl = []  # per add_* call: {template id: its values at the call's rows} (templates=...)
         self._tmpl_names = []  # the templates in order of first mention: template c is self._tmpl_names[c]
         self._tmpl_ext = []  # per template: its extinguished flag (add_template)
@@ -460,15 +495,23 @@ class Fitter:
             raise ValueError(f"{who}: an upper limit must be >= 0")
         return m.copy()
 
-    def _noise_group(self, noise, calibration, who):
+    def _noise_group(self, noise, calibration, who, outliers=None):
         """The id of the noise group ``noise`` names (-1 for None), declared at its first mention.  noise: a label matching
         [A-Za-z0-9_]+; the rows join the group whose fractional systematic is the parameter ``sys_<label>`` (free or fixed; 0 when
         not given), added in quadrature to each row's relative error with the Gaussian normalisation.  calibration: the fraction
         c >= 0 by which the group's common flux scale is uncertain (a Gaussian prior on ln scale, marginalised); every call that
-        states it for a label must state the same value.  At most 8 groups.  Nothing is recorded when the call raises."""
+        states it for a label must state the same value.  outliers: True makes the group robust -- each of its detection rows is an
+        inlier with probability 1 - P and is otherwise drawn from a broader, shifted Gaussian in ln F (the mixture of Hogg, Bovy &
+        Lang 2010; parameters ``out_frac_<label>``, ``out_scale_<label>``, ``out_shift_<label>``); every call that states it for a
+        label must state the same value, and a robust group takes no calibration.  At most 8 groups.  Nothing is recorded when the
+        call raises."""
+        if outliers is not None and not isinstance(outliers, (bool, np.bool_)):
+            raise ValueError(f"{who}: outliers must be a bool, got {outliers!r}")
         if noise is None:
             if calibration is not None:
                 raise ValueError(f"{who}: calibration needs noise=<label> (it is the calibration of a noise group)")
+            if outliers:
+                raise ValueError(f"{who}: outliers needs noise=<label> (a robust group is a noise group)")
             return -1
         if not isinstance(noise, str) or not re.fullmatch(r"[A-Za-z0-9_]+", noise):
             raise ValueError(f"{who}: noise must be a label matching [A-Za-z0-9_]+, got {noise!r}")
@@ -482,12 +525,23 @@ class Fitter:
             if self._noise_calib.get(noise, calibration) != calibration:
                 raise ValueError(f"{who}: noise group {noise!r} has calibration={self._noise_calib[noise]!r} from an earlier call, "
                                  f"got {calibration!r}")
+        if outliers is not None:
+            outliers = bool(outliers)
+            if self._noise_robust.get(noise, outliers) != outliers:
+                raise ValueError(f"{who}: noise group {noise!r} has outliers={self._noise_robust[noise]!r} from an earlier call, "
+                                 f"got {outliers!r}")
+        robust = self._noise_robust.get(noise, False) if outliers is None else outliers
+        if robust and (self._noise_calib.get(noise, 0.0) if calibration is None else calibration) > 0:
+            raise ValueError(f"{who}: noise group {noise!r} cannot have both outliers=True and a calibration fraction: the marginalised "
+                             "scale does not commute with the mixture")
         if noise not in self._noise_labels and len(self._noise_labels) >= _lib.NOISE_MAX_GROUPS:
             raise ValueError(f"{who}: at most {_lib.NOISE_MAX_GROUPS} noise groups, {noise!r} would be one more")
         if noise not in self._noise_labels:
             self._noise_labels.append(noise)
         if calibration is not None:
             self._noise_calib[noise] = calibration
+        if outliers is not None:
+            self._noise_robust[noise] = outliers
         return self._noise_labels.index(noise)
 
     def _checked_templates(self, templates, shape, who):
@@ -564,11 +618,11 @@ class Fitter:
 
     # fitter.py:256-282
     def add_flux_density(self, nu, t, f_nu, err, weights=None, label=None, upper_limit=None, noise=None, calibration=None,
-                         templates=None):
+                         templates=None, outliers=None):
         """Light-curve data at one frequency nu [Hz] (`label` is accepted for API compatibility; it only names plot legends).
         upper_limit: None, a bool or a boolean mask of the shape of t; on a flagged row f_nu is the limit L and err the noise level
-        sigma (Fitter._limit_mask).  noise, calibration: the noise group of the rows and its calibration fraction
-        (Fitter._noise_group).  templates: {name: values} of the additive templates at these rows, values a scalar or an array of the
+        sigma (Fitter._limit_mask).  noise, calibration, outliers: the noise group of the rows, its calibration fraction and whether
+        it is robust (Fitter._noise_group).  templates: {name: values} of the additive templates at these rows, values a scalar or an array of the
         shape of t in the unit of f_nu (Fitter.add_template); a host galaxy: templates={"host_r": 1.0} with the parameter
         amp_host_r."""
         nu_arr = np.asarray(nu, dtype=np.float64)
@@ -579,15 +633,16 @@ class Fitter:
             raise ValueError(f"add_flux_density: an array nu must have the shape of t, got {nu_arr.shape} vs {t.shape}")
         lim = self._limit_mask(upper_limit, t, f_nu, "add_flux_density")
         tmpl = self._checked_templates(templates, t.shape, "add_flux_density")
-        grp = self._noise_group(noise, calibration, "add_flux_density")
+        grp = self._noise_group(noise, calibration, "add_flux_density", outliers)
         self._add_points(t, np.full_like(t, float(nu_arr)) if nu_arr.ndim == 0 else nu_arr.copy(), f_nu, err, w, lim, grp,
                          self._record_templates(tmpl))
 
     # fitter.py:284-314
-    def add_spectrum(self, t, nu, f_nu, err, weights=None, upper_limit=None, noise=None, calibration=None, templates=None):
+    def add_spectrum(self, t, nu, f_nu, err, weights=None, upper_limit=None, noise=None, calibration=None, templates=None,
+                     outliers=None):
         """A broadband spectrum at one time t [s]: one point-data row per frequency.  upper_limit: None, a bool or a boolean mask of
-        the shape of nu; on a flagged row f_nu is the limit L and err the noise level sigma (Fitter._limit_mask).  noise, calibration:
-        the noise group of the rows and its calibration fraction (Fitter._noise_group).  templates: {name: values} of the additive
+        the shape of nu; on a flagged row f_nu is the limit L and err the noise level sigma (Fitter._limit_mask).  noise, calibration,
+        outliers: the noise group of the rows, its calibration fraction and whether it is robust (Fitter._noise_group).  templates: {name: values} of the additive
         templates at these rows, values a scalar or an array of the shape of nu (Fitter.add_template)."""
         if np.ndim(t) != 0 or not np.isfinite(t) or t <= 0:
             raise ValueError(f"add_spectrum: t must be finite and > 0, got {t}")
@@ -598,17 +653,17 @@ class Fitter:
         nu, f_nu, err, w = self._checked_observations(nu, f_nu, err, weights, "add_spectrum")  # nu is the axis array here
         lim = self._limit_mask(upper_limit, nu, f_nu, "add_spectrum")
         tmpl = self._checked_templates(templates, nu.shape, "add_spectrum")
-        grp = self._noise_group(noise, calibration, "add_spectrum")
+        grp = self._noise_group(noise, calibration, "add_spectrum", outliers)
         self._add_points(np.full_like(nu, float(t)), nu, f_nu, err, w, lim, grp, self._record_templates(tmpl))
 
     # fitter.py:316-377
     def add_flux(self, band, t, flux, err, num_points=5, weights=None, upper_limit=None, noise=None, calibration=None,
-                 templates=None):
+                 templates=None, outliers=None):
         """Band-integrated fluxes [erg/cm^2/s] over band = (nu_min, nu_max) [Hz]; each group is one Model.flux request.
         upper_limit: None, a bool or a boolean mask of the shape of t; on a flagged row flux is the limit L >= 0 and err the noise
         level sigma (Fitter._limit_mask); detections need strictly positive fluxes.  noise, calibration: the noise group of the rows
         and its calibration fraction (Fitter._noise_group); a group with calibration > 0 holds point rows only or exactly one
-        add_flux call (build_spec checks it).  templates: {name: values} of the additive templates at these rows, values a scalar or
+        add_flux call (build_spec checks it); outliers: whether the group is robust (Fitter._noise_group).  templates: {name: values} of the additive templates at these rows, values a scalar or
         an array of the shape of t in erg/cm^2/s (Fitter.add_template)."""
         try:
             nu_min, nu_max = band
@@ -629,7 +684,7 @@ class Fitter:
         order = np.argsort(t)
         bd = dict(nu_min=float(nu_min), nu_max=float(nu_max), num_points=int(num_points),
                   t=np.ascontiguousarray(t[order]), weights=np.ascontiguousarray(w[order]), lim=None,
-                  noise=self._noise_group(noise, calibration, "add_flux"))
+                  noise=self._noise_group(noise, calibration, "add_flux", outliers))
         bd["tmpl"] = {c: np.ascontiguousarray(v[order]) for c, v in self._record_templates(tmpl).items()}  # the values follow the sort
         if lim.any():  # limit rows: ln_flux / ln_err are not read there (0 and 1); L and sigma go into their own arrays
             lim, flux, err = lim[order], flux[order], err[order]
@@ -1085,6 +1140,11 @@ class Fitter:
         return bool(self._noise_labels)
 
     @property
+    def has_outlier_groups(self):
+        """Some noise group is robust (outliers=True of add_flux_density / add_spectrum / add_flux)."""
+        return any(self._noise_robust.get(label, False) for label in self._noise_labels)
+
+    @property
     def has_templates(self):
         """The fit has additive templates (templates=... of add_flux_density / add_spectrum / add_flux, or add_template)."""
         return bool(self._tmpl_names)
@@ -1192,6 +1252,7 @@ class Fitter:
         names another one), so that the device applies the bounds mask and adds sum ln prior (samplers.py:72-91)."""
         self._consolidate_data()
         self._check_noise_parameters(param_defs)
+        self._check_outlier_parameters(param_defs)
         self._check_template_parameters(param_defs)
         fixed = {pd.name: (pd.initial if pd.initial is not None else pd.lower) for pd in param_defs if pd.scale is Scale.fixed}
         free = [pd for pd in param_defs if pd.scale is not Scale.fixed]
@@ -1206,6 +1267,8 @@ class Fitter:
             if name in MODEL_PARAM_DEFAULTS or name in ("A_V", "N_H") or name in _lib.SKY_SLOTS or name in _lib.POL_SLOTS:
                 continue
             if self._noise_id(name) is not None:  # (goes into vag_noise_fit_spec.sys_fixed)
+                continue
+            if self._outlier_slot(name) is not None:  # (goes into vag_robust_fit_spec.frac_fixed / scale_fixed / shift_fixed)
                 continue
             if self._tmpl_id(name) is not None:  # (goes into vag_template_fit_spec.amp_fixed)
                 continue
@@ -1224,6 +1287,8 @@ class Fitter:
                 spec.slot[d] = _lib.POL_SLOTS[pd.name]
             elif self._noise_id(pd.name) is not None:
                 spec.slot[d] = _lib.P_NOISE_SYS0 + self._noise_id(pd.name)
+            elif self._outlier_slot(pd.name) is not None:
+                spec.slot[d] = self._outlier_slot(pd.name)
             elif self._tmpl_id(pd.name) is not None:
                 spec.slot[d] = _lib.P_TMPL_AMP0 + self._tmpl_id(pd.name)
             elif pd.name not in _lib.PARAM_SLOTS:
@@ -1239,6 +1304,7 @@ class Fitter:
         spec._pol = self._pol_spec(fixed) if self._pol_obs else None
         spec._lim = self._lim_spec() if self.has_limits else None
         spec._noise = self._noise_spec(fixed) if self.has_noise_groups else None
+        spec._robust = self._robust_spec(fixed) if self.has_outlier_groups else None
         spec._counts = self._counts_spec() if self._counts_obs else None
         spec._tmpl = self._tmpl_spec(fixed) if self.has_templates else None
         if self.extinction is not None and any(pd.name == "z" for pd in free):
@@ -1501,6 +1567,64 @@ class Fitter:
         nz._keep_alive = (self._all_grp, band_ids)
         return nz
 
+    def _outlier_slot(self, name):
+        """The slot of the parameter name ``out_frac_<label>`` / ``out_scale_<label>`` / ``out_shift_<label>`` of a robust noise
+        group, else None."""
+        for prefix, slot0 in _lib.ROBUST_PREFIXES.items():
+            label = name[len(prefix):]
+            if name.startswith(prefix) and label in self._noise_labels and self._noise_robust.get(label, False):
+                return slot0 + self._noise_labels.index(label)
+        return None
+
+    def _check_outlier_parameters(self, param_defs):
+        """``out_frac_<label>``, ``out_scale_<label>`` and ``out_shift_<label>`` need the robust noise group <label>.  out_frac: free on
+        linear scale with lower >= 0 and upper < 1, on log scale with lower > 0 (and upper < 1), or fixed in [0, 1); out_scale: free
+        on linear scale with lower >= 0, on log scale, or fixed >= 0; out_shift: free on linear scale only, or fixed and finite."""
+        for pd in param_defs:
+            prefix = next((q for q in _lib.ROBUST_PREFIXES if pd.name.startswith(q)), None)
+            if prefix is None:
+                continue
+            if self._outlier_slot(pd.name) is None:
+                robust = [label for label in self._noise_labels if self._noise_robust.get(label, False)]
+                raise ValueError(f"the parameter {pd.name!r} needs data added with noise={pd.name[len(prefix):]!r}, outliers=True "
+                                 f"(robust noise groups: {robust})")
+            if pd.scale is Scale.fixed:
+                value = pd.initial if pd.initial is not None else pd.lower
+                if prefix == "out_frac_" and (not np.isfinite(value) or value < 0 or not value < 1):
+                    raise ValueError(f"a fixed {pd.name} must be finite and in [0, 1), got {value!r}")
+                if prefix == "out_scale_" and (not np.isfinite(value) or value < 0):
+                    raise ValueError(f"a fixed {pd.name} must be finite and >= 0, got {value!r}")
+                if prefix == "out_shift_" and not np.isfinite(value):
+                    raise ValueError(f"a fixed {pd.name} must be finite, got {value!r}")
+            elif prefix == "out_frac_":
+                if not pd.lower >= 0 or (pd.scale is Scale.log and not pd.lower > 0) or not pd.upper < 1:
+                    raise ValueError(f"{pd.name}: a free outlier fraction needs lower >= 0 (> 0 on log scale) and upper < 1, got "
+                                     f"[{pd.lower!r}, {pd.upper!r}]")
+            elif prefix == "out_scale_":
+                if not pd.lower >= 0 or (pd.scale is Scale.log and not pd.lower > 0):
+                    raise ValueError(f"{pd.name}: a free outlier scatter needs lower >= 0 (> 0 on log scale), got lower={pd.lower!r}")
+            elif pd.scale is Scale.log:
+                raise ValueError(f"{pd.name}: the outlier offset is free on linear scale only (it may be negative)")
+
+    def _robust_spec(self, fixed):
+        """vag_robust_fit_spec of the robust noise groups: the mask and the fixed outlier fractions, scatters and offsets (0 when
+        not given)."""
+        rb = _lib.RobustFitSpec()
+        rb.n_groups = len(self._noise_labels)
+        mask = 0
+        for g, label in enumerate(self._noise_labels):
+            if not self._noise_robust.get(label, False):
+                continue
+            if self._noise_calib.get(label, 0.0) > 0:
+                raise ValueError(f"noise group {label!r} has outliers=True and calibration={self._noise_calib[label]!r}: the marginalised "
+                                 "scale does not commute with the mixture")
+            mask |= 1 << g
+            rb.frac_fixed[g] = float(fixed.get("out_frac_" + label, 0.0))
+            rb.scale_fixed[g] = float(fixed.get("out_scale_" + label, 0.0))
+            rb.shift_fixed[g] = float(fixed.get("out_shift_" + label, 0.0))
+        rb.mask = mask
+        return rb
+
     def _tmpl_id(self, name):
         """The id of the parameter name ``amp_<name>`` of a declared template, else None."""
         if not name.startswith(_lib.TMPL_PREFIX) or name[len(_lib.TMPL_PREFIX):] not in self._tmpl_names:
@@ -1684,6 +1808,88 @@ class Fitter:
             out.append(dict(model=f, residual=r, whitened=y, chi2=gd["weight"] * float(whitened_chi2(r, W))))
         return out
 
+    def outlier_probabilities(self, best_params, param_defs, resolution=None):
+        """The posterior probability, row by row, that a point of a robust noise group is an outlier, at a point of sampler space: a
+        list of dict(label, t, nu, band, residual, p_out), one per robust group in the order of the noise groups.  The rows are the
+        group's point rows in ascending t (``nu`` their frequency, ``band`` -1) followed by the rows of its band groups (``nu`` NaN,
+        ``band`` the index of the add_flux call).  residual = ln F_obs - ln max(f, 1e-300) with f the model value as the likelihood
+        forms it (templates, then extinction); p_out = exp(o - l) of outlier_terms at the sample's sys, out_frac, out_scale and
+        out_shift of the group.  Upper-limit rows carry NaN in both.  The model values come from the device -- one
+        vag_flux_density_batch request at the point rows, one vag_flux_batch request per band group, as Fitter.correlated and
+        Fitter.counts get theirs -- and the probabilities from outlier_terms on the host."""
+        spec, _, _ = self.build_spec(param_defs)
+        if spec._robust is None:
+            return []
+        p, a_v = self._params_at(best_params, param_defs, resolution)
+        sample = np.asarray(best_params, dtype=np.float64).reshape(-1)
+        labels = self._noise_labels
+        par = {g: dict(s=float(spec._noise.sys_fixed[g]), frac=float(spec._robust.frac_fixed[g]), scale=float(spec._robust.scale_fixed[g]),
+                       shift=float(spec._robust.shift_fixed[g])) for g in range(len(labels)) if (spec._robust.mask >> g) & 1}
+        families = (("s", _lib.P_NOISE_SYS0), ("frac", _lib.P_ROBUST_FRAC0), ("scale", _lib.P_ROBUST_SCALE0), ("shift", _lib.P_ROBUST_SHIFT0))
+        amp = np.array([float(spec._tmpl.amp_fixed[c]) if spec._tmpl is not None else 0.0 for c in range(len(self._tmpl_names))])
+        for d in range(spec.ndim):
+            val = 10.0 ** sample[d] if spec.is_log[d] else sample[d]
+            for key, slot0 in families:
+                if spec.slot[d] - slot0 in par and 0 <= spec.slot[d] - slot0 < _lib.NOISE_MAX_GROUPS:
+                    par[spec.slot[d] - slot0][key] = float(val)
+            if 0 <= spec.slot[d] - _lib.P_TMPL_AMP0 < amp.size:
+                amp[spec.slot[d] - _lib.P_TMPL_AMP0] = val
+        h, lock = get_context(self.device)
+        lib = _lib.load()
+
+        def with_templates(F, tmpl, ext):
+            """(F + x) exp(-A_V k) + e at the rows of one pass; tmpl: {template id: values}."""
+            e = x = 0.0
+            if tmpl:
+                T = np.zeros((amp.size, F.size))
+                for c, v in tmpl.items():
+                    T[c] = v
+                e, x = template_terms(T, amp, self._tmpl_ext)
+            f = F + x
+            if ext is not None and a_v != 0.0:
+                f = f * np.exp(-a_v * ext)
+            return f + e
+
+        def rows_of(f, ln_flux, ln_err, w, lim, g):
+            """(residual, p_out) of the rows of one pass that belong to group g; limit rows NaN."""
+            with np.errstate(all="ignore"):
+                r = ln_flux - np.log(np.where(f > 1e-300, f, np.where(np.isnan(f), f, 1e-300)))
+            det = np.ones(f.size, dtype=bool) if lim is None else np.asarray(lim) == 0
+            p_out = np.full(f.size, np.nan)
+            if det.any():
+                q = par[g]
+                p_out[det] = outlier_terms(r[det], ln_err[det], w[det], q["s"], q["frac"], q["scale"], q["shift"])[1]
+            return np.where(det, r, np.nan), p_out
+        point = None
+        if self._all_grp is not None and any((self._all_grp == g).any() for g in par):
+            n = self._all_t.size
+            F = np.empty(n)
+            with lock:
+                _lib.check(lib.vag_flux_density_batch(h, C.byref(p), 1, self._all_t.ctypes.data_as(_dp), self._all_nu.ctypes.data_as(_dp), n,
+                                                      F.ctypes.data_as(_dp)))
+            point = with_templates(F, self._all_tmpl, self._ext_kernel)
+        out = []
+        for g in sorted(par):
+            parts = []
+            if point is not None and (self._all_grp == g).any():
+                sel = self._all_grp == g
+                lim = self._all_lim["kind"][sel] if self._all_lim is not None else None
+                r, po = rows_of(point[sel], self._all_log_flux[sel], self._all_log_err[sel], self._all_weights[sel], lim, g)
+                parts.append((self._all_t[sel], self._all_nu[sel], np.full(int(sel.sum()), -1), r, po))
+            for k, bd in enumerate(self._band_obs):
+                if bd["noise"] != g:
+                    continue
+                n = bd["t"].size
+                F = np.empty(n)
+                with lock:
+                    _lib.check(lib.vag_flux_batch(h, C.byref(p), 1, bd["t"].ctypes.data_as(_dp), n, bd["nu_min"], bd["nu_max"],
+                                                  bd["num_points"], F.ctypes.data_as(_dp)))
+                r, po = rows_of(with_templates(F, bd.get("tmpl"), None), bd["ln_flux"], bd["ln_err"], bd["weights"], bd["lim"], g)
+                parts.append((bd["t"], np.full(n, np.nan), np.full(n, k), r, po))
+            cols = [np.concatenate(c) if parts else np.array([]) for c in (zip(*parts) if parts else [[]] * 5)]
+            out.append(dict(label=labels[g], t=cols[0], nu=cols[1], band=cols[2].astype(np.int64), residual=cols[3], p_out=cols[4]))
+        return out
+
     def count_spectra(self, best_params, param_defs, resolution=None):
         """The expected counts mu [n][C] of every count-spectrum group at a point of sampler space: a list of float64 arrays, one per
         group.  Each group is one vag_flux_density_batch request at its n_samples J points (t_sample_s, nu_j), s outer, and
@@ -1741,8 +1947,9 @@ class Fitter:
             raise ValueError("duplicate parameter names")
         for pd in param_defs:
             if pd.name not in ("A_V", "N_H") and pd.name not in _lib.PARAM_SLOTS and pd.name not in _lib.SKY_SLOTS and pd.name not in _lib.POL_SLOTS \
-                    and not pd.name.startswith(_lib.NOISE_PREFIX) and not pd.name.startswith(_lib.TMPL_PREFIX):
-                # (sys_<label>, amp_<name>: _check_noise_parameters, _check_template_parameters below)
+                    and not pd.name.startswith(_lib.NOISE_PREFIX) and not pd.name.startswith(_lib.TMPL_PREFIX) \
+                    and not pd.name.startswith(tuple(_lib.ROBUST_PREFIXES)):
+                # (sys_<label>, amp_<name>, out_*_<label>: _check_noise_parameters, _check_template_parameters, _check_outlier_parameters below)
                 raise ValueError(f"parameter {pd.name} is not accepted by the accelerated path")
             if pd.scale is Scale.fixed:
                 continue
@@ -1754,6 +1961,7 @@ class Fitter:
             raise ValueError("A_V needs Fitter(extinction=...)")
         self._check_pol_parameters(names)
         self._check_noise_parameters(param_defs)
+        self._check_outlier_parameters(param_defs)
         self._check_template_parameters(param_defs)
         self._check_n_h_parameter(param_defs)
 
